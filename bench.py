@@ -9,11 +9,16 @@ A step = one pass of the whole hot path (S2 electron/photon Monte Carlo, SPE gai
 record packing) over one batch of synthetic instructions that is already resident in HBM.  For N > 1 (weak scaling: every rank
 simulates its own M instructions; event clusters are independent) the step ends with the RCCL gather of the packed
 raw_records on rank 0 -- the exchange step north_star names --, posted as one grouped send/recv and overlapped with the next
-batch's kernels; `value` is that gathered rate.  The same run then times K steps WITHOUT the gather (`value_no_gather`: every rank
-keeps its records in its own HBM, the sharded delivery of DESIGN.md 6) and the gather alone (`config.gather_ms_per_step`).
+batch's kernels; `value` is that gathered rate.  With --full the same run then times K steps WITHOUT the gather (`value_no_gather`:
+every rank keeps its records in its own HBM, the sharded delivery of DESIGN.md 6) and the gather alone (`config.gather_ms_per_step`).
 --workload s2 (default) is the headline; s2map = the same batch under a position dependent S2 pattern map (bright tiles), mixed =
 configs[3] (S1 + S2 pairs, PMT afterpulses and noise on, synthetic tables), nveto = configs[4] (optical instructions at 1 MHz on 120
 channels), s1 = configs[1]; all run through the same step / gather code.  Prints ONE JSON line (rank 0).
+
+A plain run does only what the headline needs: set up, W warmup steps, K timed steps, the result line.  --full adds the side
+measurements: the CPU baseline (s2, one GPU), the rate with the records copied to the host, one profiled step (per-kernel
+times, roofline), the device-copy ceiling and, for N > 1, the rate without the gather and the gather alone.
+--dump-outputs DIR writes what the last timed step computed (rank 0's records, truth and counts) as .npy files, see dump_outputs.
 """
 import argparse
 import glob
@@ -139,6 +144,54 @@ def newest_profile(kind):
     return best[1] if best else None
 
 
+DUMP_BUDGET = 64 << 20       # bytes of all --dump-outputs files together
+DUMP_RECORDS = 100_000       # records kept in full (a fixed, seeded sample when the step made more)
+DUMP_TRUTH_ROWS = 65_536     # truth rows kept (the same kind of sample)
+DUMP_SEED = 20240601
+
+
+def _sample(n, k, salt):
+    """sorted indices of a fixed, seeded sample of k out of n (all of them when n <= k)"""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng([DUMP_SEED, salt]).choice(n, k, replace=False))
+
+
+def dump_outputs(eng, counts, out_dir):
+    """What a caller of the timed path receives from the last step, as float32 / float64 .npy files in out_dir:
+    counts.npy             the step's counts (float64, in the order Engine.run returns them: wfs_counts of include/wfsim_amd.h)
+    records_*.npy          the packed raw_records, field by field (`index` = the record's position in the step's output, `data`
+                           [k, samples_per_record]); every record when there are at most DUMP_RECORDS, else a fixed, seeded sample
+    channel_records.npy,   per channel over EVERY record of the step: number of records and sum of the ADC samples (exact in float64)
+    channel_adc_sum.npy
+    truth.npy,             the per-pulse-set truth sums [n_sets, 12] and timing [n_sets, 5] (float64), rows sampled like the records
+    truth_timing.npy       above DUMP_TRUTH_ROWS (the electron-time mean and spread of truth_timing are sums of floating-point
+                           atomics: equal to rounding, not bit for bit, from run to run)
+    Inputs, seeds and sample indices are fixed, so two builds run with the same arguments can be compared file by file."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = {'counts': np.array(list(counts.values()), dtype=np.float64)}
+    rec = eng.records()
+    idx = _sample(len(rec), DUMP_RECORDS, 1)
+    s = rec[idx]
+    out['records_index'] = idx.astype(np.float64)
+    out['records_time'] = s['time'].astype(np.float64)
+    for f in ('length', 'dt', 'channel', 'pulse_length', 'record_i', 'baseline'):
+        out['records_' + f] = s[f].astype(np.float32)
+    out['records_data'] = s['data'].astype(np.float32)
+    n_ch = int(rec['channel'].max()) + 1 if len(rec) else 0
+    ch = rec['channel'].astype(np.int64)
+    out['channel_records'] = np.bincount(ch, minlength=n_ch).astype(np.float64)
+    out['channel_adc_sum'] = np.bincount(ch, weights=rec['data'].sum(axis=1, dtype=np.int64).astype(np.float64), minlength=n_ch)
+    del rec
+    acc, ts = eng.truth()
+    rows = _sample(len(acc), DUMP_TRUTH_ROWS, 2)
+    out['truth'], out['truth_timing'] = np.ascontiguousarray(acc[rows], np.float64), np.ascontiguousarray(ts[rows], np.float64)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_BUDGET, f'--dump-outputs would write {total} bytes'
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -156,7 +209,12 @@ def main():
     ap.add_argument('--no-gather', action='store_true', help='N > 1: skip the gathered measurement, report only the rate with every rank keeping its records (then `value`)')
     ap.add_argument('--gather', action='store_true', help='(the default since round 4; kept for old command lines)')
     ap.add_argument('--sync-gather', action='store_true', help='do not overlap the gather with the next batch')
+    ap.add_argument('--full', action='store_true', help='also the side measurements: CPU baseline, records copied to the host, '
+                    'profiled step (per-kernel times, roofline), device-copy ceiling, N > 1: without the gather and the gather alone')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help="write what the last timed step computed (rank 0) as .npy files into DIR")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     rank = int(os.environ.get('RANK', 0))
     local_rank = int(os.environ.get('LOCAL_RANK', 0))
@@ -169,7 +227,7 @@ def main():
     cpu = None
     if args.instructions is None:
         args.instructions = DEFAULT_INSTRUCTIONS[args.workload]
-    if args.cpu_sample > 0 and world == 1 and args.workload == 's2':          # the CPU baseline is timed on rank 0 of the 1-GPU run only, before the GPU is touched
+    if args.full and args.cpu_sample > 0 and world == 1 and args.workload == 's2':     # the CPU baseline is timed on rank 0 of the 1-GPU run only, before the GPU is touched
         cpu = cpu_baseline(3, args.cpu_sample)
     import torch
     import torch.distributed as dist
@@ -268,8 +326,11 @@ def main():
 
     gathered = world > 1 and not args.no_gather
     elapsed, counts = timed(gathered)                      # the headline region: with the gather when N > 1
+    ms_per_step = 1e3 * elapsed / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, counts, args.dump_outputs)       # the last timed step's outputs, before anything else runs
     elapsed_ng, gather_ms = None, None
-    if gathered:
+    if gathered and args.full:
         elapsed_ng, _ = timed(False)                       # the same K steps, every rank keeping its records in its own HBM
         # the gather alone: one batch's records from every rank to rank 0, nothing else running
         mine = torch.empty(counts['n_records'] * 244, dtype=torch.uint8, device='cuda')
@@ -293,69 +354,31 @@ def main():
     else:
         total_pe, total_rec, total_ph = counts['n_pe'], counts['n_records'], counts['n_photons']
 
-    # PCIe-inclusive rate (never the headline value): steps whose records also travel to (pinned) host memory, the copy of
-    # batch k on the engine's copy stream under the kernels of batch k + 1 -- what ChunkRawRecords does with its record buffer
-    from wfsim_amd.ministrax import raw_record_dtype
-    host_bufs = [np.empty(int(counts['n_records'] * 1.05) + 1024, dtype=raw_record_dtype()) for _ in range(2)]
-    pinned = all([eng.pin(b) for b in host_bufs])
-    barrier()
-    n_pcie = max(2, min(args.steps, 6))
-    t1 = time.perf_counter()
-    for k in range(n_pcie):
-        c = step(False)
-        eng.wait_records()                      # the previous batch's copy (it ran under this batch's kernels)
-        eng.records_into_async(host_bufs[k & 1], c['n_records'])
-    eng.wait_records()
-    pcie_ms = 1e3 * (time.perf_counter() - t1) / n_pcie
-    eng.unpin_all()
-    del host_bufs
+    if args.full:
+        # PCIe-inclusive rate (never the headline value): steps whose records also travel to (pinned) host memory, the copy of
+        # batch k on the engine's copy stream under the kernels of batch k + 1 -- what ChunkRawRecords does with its record buffer
+        from wfsim_amd.ministrax import raw_record_dtype
+        host_bufs = [np.empty(int(counts['n_records'] * 1.05) + 1024, dtype=raw_record_dtype()) for _ in range(2)]
+        pinned = all([eng.pin(b) for b in host_bufs])
+        barrier()
+        n_pcie = max(2, min(args.steps, 6))
+        t1 = time.perf_counter()
+        for k in range(n_pcie):
+            c = step(False)
+            eng.wait_records()                      # the previous batch's copy (it ran under this batch's kernels)
+            eng.records_into_async(host_bufs[k & 1], c['n_records'])
+        eng.wait_records()
+        pcie_ms = 1e3 * (time.perf_counter() - t1) / n_pcie
+        eng.unpin_all()
+        del host_bufs
 
-    # one extra (untimed) profiled step: HIP-event duration of every kernel on the engine's stream
-    counts = step(False, profile=True)
-    ktimes = eng.kernel_times()
+        # one extra (untimed) profiled step: HIP-event duration of every kernel on the engine's stream
+        counts = step(False, profile=True)
+        ktimes = eng.kernel_times()
     if rank != 0:
         if world > 1:
             dist.destroy_process_group()
         return
-    # measured ceiling next to the spec peak: a plain device-to-device copy of 1 GiB (bytes read + written per second)
-    copy_gbs = None
-    if not args.no_copy_ceiling:
-        src_buf = torch.empty(1 << 30, dtype=torch.uint8, device='cuda'); dst_buf = torch.empty_like(src_buf)
-        for _ in range(2):
-            dst_buf.copy_(src_buf)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(10):
-            dst_buf.copy_(src_buf)
-        e1.record(); torch.cuda.synchronize()
-        copy_gbs = 2 * (1 << 30) * 10 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-        del src_buf, dst_buf
-    ms_per_step = 1e3 * elapsed / args.steps
-    dom = max(ktimes, key=lambda k: ktimes[k][0])
-    dom_ms, dom_launches = ktimes[dom]
-    b_alg = algorithmic_bytes(counts)
-    # HBM bytes per launch of the dominant kernel and what limits it, from the committed PMC profiles of this command (the newest round's
-    # profiles/r<NN>_traffic.json / _counters.json, written by tools/profile_round.sh + tools/make_profiles.py); only for the profiled workload
-    traffic, limiter, valu_util, prof_src = None, None, None, None
-    if args.workload == 's2' and M == 1000 and not overrides and not args.pmt_afterpulses:
-        for kind in ('traffic', 'counters'):
-            f = newest_profile(kind)
-            try:
-                kc = json.load(open(f))['kernels'][dom]
-            except (OSError, KeyError, TypeError):
-                continue
-            prof_src = os.path.basename(f)[:3]
-            if kind == 'traffic':
-                traffic = kc.get('hbm_bytes')
-            else:
-                limiter, valu_util = kc.get('limited_by'), kc.get('valu_busy')
-    achieved = b_alg / (dom_ms / dom_launches * 1e-3) / 1e9
-    # the dominant kernel's OWN algorithmic bytes (the pulse kernel reads every photon record once and adds into the raw
-    # accumulators once; the generator writes every photon record once): what "achieved" would be without crediting one
-    # kernel with the whole pipeline's bytes
-    # (k_s2_tile makes its photons in registers: what it moves are the tile buffers' samples, written once)
-    own = {'k_pulse_dense': 8 * counts['n_photons'] + 4 * counts['n_raw_samples'], 'k_photon_fill': 8 * counts['n_photons'],
-           'k_s2_tile': 4 * counts['n_raw_samples']}.get(dom)
     desc = {'s2': f'{M} S2 instructions per GPU, 1e4 electrons each (~1e6 PE), 494 PMTs, z=-10 cm, s2_secondary_sc_gain=100, noise/afterpulses off (BASELINE configs[2])',
             's2map': f'{M} S2 instructions per GPU as configs[2], spread over the TPC under a synthetic position dependent S2 pattern map (device evaluated; the PMT above '
                      f'the event takes ~5 % of the light) -- SIDE MEASUREMENT',
@@ -376,29 +399,69 @@ def main():
         raw_records_MB_per_s=total_rec * 244 * args.steps / elapsed / 1e6,
         config=dict(workload=desc, arithmetic='add_current with fused multiply-adds (one rounding per term)' if cfg.get('fused_multiply_add', True) else "add_current with numpy's two roundings per term (exact currents)",
                     instructions_per_gpu=M, instructions_per_s=M * world * args.steps / elapsed, pe_per_step=total_pe, photons_per_step=total_ph, records_per_step=total_rec,
-                    gather=gather_desc,
-                    ms_per_step_incl_d2h_of_records=pcie_ms, d2h='pinned host buffers, copy of batch k overlapped with batch k + 1' if pinned else 'pageable host buffers'),
-        # bound: the roofline these numbers are priced on (HBM bytes: there is no dense contraction for MFMA).  What actually
-        # limits the dominant kernel is in `limited_by` (SQ counters: f64 VALU issue + exposed latency, not HBM).
-        roofline=dict(bound='hbm', kernel=dom, achieved=achieved, peak=HBM_PEAK_GBS, unit='GB/s', frac=achieved / HBM_PEAK_GBS,
-                      traffic=traffic, algorithmic_bytes_per_launch=b_alg, kernel_ms=dom_ms / dom_launches,
-                      limited_by=limiter, valu_busy=valu_util, counters_from=prof_src,
-                      kernel_own_bytes=own, kernel_own_frac=(own / (dom_ms / dom_launches * 1e-3) / 1e9 / HBM_PEAK_GBS) if own else None,
-                      pipeline_frac=b_alg / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                      measured_copy_GBs=copy_gbs, frac_of_measured_copy=(achieved / copy_gbs) if copy_gbs else None,
-                      kernels_ms={k: round(v[0], 4) for k, v in sorted(ktimes.items(), key=lambda kv: -kv[1][0])}),
+                    gather=gather_desc),
     )
     if gathered:
-        out['value_no_gather'] = total_pe * args.steps / elapsed_ng
-        out['config']['ms_per_step_no_gather'] = 1e3 * elapsed_ng / args.steps
-        out['config']['gather_ms_per_step'] = gather_ms
         out['config']['gather_bytes_per_step'] = total_rec * 244
-    if cpu is not None:
-        out['cpu_baseline'] = cpu
+    if args.full:
+        # measured ceiling next to the spec peak: a plain device-to-device copy of 1 GiB (bytes read + written per second)
+        copy_gbs = None
+        if not args.no_copy_ceiling:
+            src_buf = torch.empty(1 << 30, dtype=torch.uint8, device='cuda'); dst_buf = torch.empty_like(src_buf)
+            for _ in range(2):
+                dst_buf.copy_(src_buf)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(10):
+                dst_buf.copy_(src_buf)
+            e1.record(); torch.cuda.synchronize()
+            copy_gbs = 2 * (1 << 30) * 10 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+            del src_buf, dst_buf
+        dom = max(ktimes, key=lambda k: ktimes[k][0])
+        dom_ms, dom_launches = ktimes[dom]
+        b_alg = algorithmic_bytes(counts)
+        # HBM bytes per launch of the dominant kernel and what limits it, from the committed PMC profiles of this command (the newest round's
+        # profiles/r<NN>_traffic.json / _counters.json, written by tools/profile_round.sh + tools/make_profiles.py); only for the profiled workload
+        traffic, limiter, valu_util, prof_src = None, None, None, None
+        if args.workload == 's2' and M == 1000 and not overrides and not args.pmt_afterpulses:
+            for kind in ('traffic', 'counters'):
+                f = newest_profile(kind)
+                try:
+                    kc = json.load(open(f))['kernels'][dom]
+                except (OSError, KeyError, TypeError):
+                    continue
+                prof_src = os.path.basename(f)[:3]
+                if kind == 'traffic':
+                    traffic = kc.get('hbm_bytes')
+                else:
+                    limiter, valu_util = kc.get('limited_by'), kc.get('valu_busy')
+        achieved = b_alg / (dom_ms / dom_launches * 1e-3) / 1e9
+        # the dominant kernel's OWN algorithmic bytes (the pulse kernel reads every photon record once and adds into the raw
+        # accumulators once; the generator writes every photon record once): what "achieved" would be without crediting one
+        # kernel with the whole pipeline's bytes
+        # (k_s2_tile makes its photons in registers: what it moves are the tile buffers' samples, written once)
+        own = {'k_pulse_dense': 8 * counts['n_photons'] + 4 * counts['n_raw_samples'], 'k_photon_fill': 8 * counts['n_photons'],
+               'k_s2_tile': 4 * counts['n_raw_samples']}.get(dom)
+        out['config'].update(ms_per_step_incl_d2h_of_records=pcie_ms,
+                             d2h='pinned host buffers, copy of batch k overlapped with batch k + 1' if pinned else 'pageable host buffers')
+        # bound: the roofline these numbers are priced on (HBM bytes: there is no dense contraction for MFMA).  What actually
+        # limits the dominant kernel is in `limited_by` (SQ counters: f64 VALU issue + exposed latency, not HBM).
+        out['roofline'] = dict(bound='hbm', kernel=dom, achieved=achieved, peak=HBM_PEAK_GBS, unit='GB/s', frac=achieved / HBM_PEAK_GBS,
+                               traffic=traffic, algorithmic_bytes_per_launch=b_alg, kernel_ms=dom_ms / dom_launches,
+                               limited_by=limiter, valu_busy=valu_util, counters_from=prof_src,
+                               kernel_own_bytes=own, kernel_own_frac=(own / (dom_ms / dom_launches * 1e-3) / 1e9 / HBM_PEAK_GBS) if own else None,
+                               pipeline_frac=b_alg / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                               measured_copy_GBs=copy_gbs, frac_of_measured_copy=(achieved / copy_gbs) if copy_gbs else None,
+                               kernels_ms={k: round(v[0], 4) for k, v in sorted(ktimes.items(), key=lambda kv: -kv[1][0])})
+        if gathered:
+            out['value_no_gather'] = total_pe * args.steps / elapsed_ng
+            out['config']['ms_per_step_no_gather'] = 1e3 * elapsed_ng / args.steps
+            out['config']['gather_ms_per_step'] = gather_ms
+        if cpu is not None:
+            out['cpu_baseline'] = cpu
     print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
-
 
 if __name__ == '__main__':
     main()

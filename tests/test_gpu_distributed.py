@@ -103,15 +103,15 @@ def test_bench_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT')}
     env['WFS_BENCH_BACKEND'] = 'gloo'
     # default: the step ends with the gather of every rank's records on rank 0 (the exchange step north_star names), overlapped with the
-    # next batch; the same run also reports the rate without it.  --no-gather: only that one.
-    for extra, gather in (([], 'send/recv'), (['--no-gather'], 'none')):
+    # next batch; with --full the same run also reports the rate without it.  --no-gather: only that one.
+    for extra, gather in ((['--full'], 'send/recv'), (['--no-gather'], 'none')):
         r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--instructions', '12', '--steps', '2', '--warmup', '1',
                             '--cpu-sample', '0'] + extra, capture_output=True, text=True, cwd=root, env=env, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         line = json.loads(r.stdout.strip().splitlines()[-1])
         assert line['n_gpus'] == 2 and line['scaling'] == 'weak' and line['value'] > 0
         assert line['config']['instructions_per_gpu'] == 12 and gather in line['config']['gather']
-        if not extra:
+        if extra == ['--full']:
             assert 'gloo send/recv to rank 0, overlapped' in line['config']['gather'] and 'gathered on rank 0' in line['metric']
             assert line['value_no_gather'] > 0 and line['config']['gather_ms_per_step'] > 0
             assert line['config']['gather_bytes_per_step'] == 244 * line['config']['records_per_step']

@@ -3,7 +3,7 @@
 TAG=$1; shift
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 240 rocprofv3 --pmc "$@" --output-format csv -d $OUT/pmc -- python3 $R/bench.py --cpu-sample 0 --steps 1 --warmup 0 $BENCH_ARGS > $OUT/pmc.log 2>&1; echo "pmc rc=$?"
+timeout -k 10 240 rocprofv3 --pmc "$@" --output-format csv -d $OUT/pmc -- python3 $R/bench.py --full --cpu-sample 0 --steps 1 --warmup 0 $BENCH_ARGS > $OUT/pmc.log 2>&1; echo "pmc rc=$?"
 python3 - <<PY
 import csv, glob, collections
 f = sorted(glob.glob('$OUT/pmc/**/*counter_collection.csv', recursive=True))[-1]
