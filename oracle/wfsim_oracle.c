@@ -92,6 +92,9 @@ typedef struct orc_session_s {
     /* all generated photons (channel sorted per pulse call) */
     vec_i64 ph_t; vec_i16 ph_ch; vec_u8 ph_dpe; vec_f64 ph_gain; vec_i64 call_ph_off; vec_i32 call_kind, call_runset;
     vec_i64 e_t; vec_i64 call_e_off;
+    /* optical input: the photons RawDataOptical.sim_primary hands to Pulse.__call__, before the transit-time draw (input order inside
+     * a call; the calls are those of call_ph_off) */
+    vec_i64 opt_in_t; vec_i16 opt_in_ch;
     /* digitise groups */
     vec_i64 dg_left, dg_right, dg_first_pulse, dg_n_pulses, dg_ix_rand, dg_row_off;
     vec_i32 row_ch; vec_i64 row_left, row_right, row_data_off; vec_i32 row_data;
@@ -267,7 +270,7 @@ void orc_free(orc_session *s)
         (void **)&s->dg_row_off.p, (void **)&s->row_ch.p, (void **)&s->row_left.p, (void **)&s->row_right.p,
         (void **)&s->row_data_off.p, (void **)&s->row_data.p, (void **)&s->zl_digit.p, (void **)&s->zl_left.p,
         (void **)&s->zl_right.p, (void **)&s->zl_data_off.p, (void **)&s->zl_ch.p, (void **)&s->zl_data.p,
-        (void **)&s->truth.p };
+        (void **)&s->truth.p, (void **)&s->opt_in_t.p, (void **)&s->opt_in_ch.p };
     for (size_t i = 0; i < sizeof(ptrs) / sizeof(ptrs[0]); i++) free(*ptrs[i]);
     for (int q = 0; q < TAB_N; q++) { free(s->tab[q].cum); free(s->tab[q].thr); free(s->tab[q].alias); }
     for (i32 k = 0; k < s->n_xtab; k++) { free(s->xtab[k].cum); free(s->xtab[k].thr); free(s->xtab[k].alias); }
@@ -1088,8 +1091,9 @@ i64 orc_optical(orc_session *s, u32 gid, int runset, i64 time, i64 n, const i64 
         int g1, g2; gain_code(s, B[1], &g1, &g2);
         int is_dpe = g2 != 0;
         i64 t = time + t_rel[k];
-        t += alias_sample(&s->tab[TAB_TTS], B[0]);
         int ch = chan[k];
+        VEC_PUSH(s->opt_in_t, i64, t); VEC_PUSH(s->opt_in_ch, int16_t, (int16_t)ch);
+        t += alias_sample(&s->tab[TAB_TTS], B[0]);
         int sc = c->n_spe_channels > ch ? ch : 0;
         const double *row = s->spe + (i64)sc * 2001;
         double G = s->gains[ch], gain = G * row[g1];
@@ -1257,7 +1261,7 @@ GETTER(pl_ch, pl_ch, i32) GETTER(pl_runset, pl_runset, i32) GETTER(pl_left, pl_l
 GETTER(pl_cur_off, pl_cur_off, i64) GETTER(pl_nph, pl_nph, i64) GETTER(cur, cur, double)
 GETTER(ph_t, ph_t, i64) GETTER(ph_ch, ph_ch, int16_t) GETTER(ph_dpe, ph_dpe, uint8_t) GETTER(ph_gain, ph_gain, double)
 GETTER(call_ph_off, call_ph_off, i64) GETTER(call_kind, call_kind, i32) GETTER(call_runset, call_runset, i32)
-GETTER(e_t, e_t, i64) GETTER(call_e_off, call_e_off, i64)
+GETTER(e_t, e_t, i64) GETTER(call_e_off, call_e_off, i64) GETTER(opt_in_t, opt_in_t, i64) GETTER(opt_in_ch, opt_in_ch, int16_t)
 GETTER(dg_left, dg_left, i64) GETTER(dg_right, dg_right, i64) GETTER(dg_first_pulse, dg_first_pulse, i64)
 GETTER(dg_n_pulses, dg_n_pulses, i64) GETTER(dg_ix_rand, dg_ix_rand, i64) GETTER(dg_row_off, dg_row_off, i64)
 GETTER(row_ch, row_ch, i32) GETTER(row_left, row_left, i64) GETTER(row_right, row_right, i64)

@@ -4,6 +4,7 @@
 Run once in the build container (needs /root/reference; the GPU box never runs this):
 
     python tests/golden/make_golden.py
+    python tests/golden/make_golden.py optical_chain pmt_ap_draws     # these two write their own files only
 
 The reference's hot-path modules are imported under the stubs of ``_ref_stubs.py`` (identity njit, so
 every draw comes from numpy's seeded global generator).  What is written is DATA only: inputs and
@@ -12,6 +13,7 @@ the bundled single-channel SPE distribution.  No reference source text is stored
 
 Stage boundaries captured per chain case (everything downstream of them is deterministic):
   * per Pulse.__call__   : post-TTS photon times, channels, DPE flags, per-photon gains  -> pulses
+                           (optical chains: also the photon list on entry, before the transit-time draw)
   * per digitize call    : pulse list -> (left, right, channel mask, raw rows in their active range)
   * per ZLE              : yielded (channel, left, right, data) tuples
   * truth rows
@@ -150,10 +152,20 @@ class Recorder:
 
         def call(self_, *a):
             rec._gain_parts = []
+            # the photon list as the caller left it (S1 / S2 fill theirs inside their own __call__ before this one: those
+            # entries are the generator's; for RawDataOptical.sim_primary this is what sim_primary itself decided)
+            in_t = np.array(self_.__dict__.get('_photon_timings', []), dtype=np.int64)
+            in_ch = np.array(self_.__dict__.get('_photon_channels', []), dtype=np.int64)
             orig_call(self_, *a)
             gains = np.concatenate(rec._gain_parts) if rec._gain_parts else np.zeros(0)
+            if len(gains) != len(self_._photon_timings):
+                # photons on turned-off PMTs are skipped before a gain is drawn (pulse.py:89): stored with gain 0
+                live = ~np.isin(self_._photon_channels, self_.config['turned_off_pmts'])
+                full = np.zeros(len(self_._photon_timings))
+                full[live] = gains
+                gains = full
             rec.calls.append(dict(
-                kind=type(self_).__name__,
+                kind=type(self_).__name__, in_t=in_t, in_ch=in_ch,
                 t=np.array(self_._photon_timings, dtype=np.int64),
                 ch=np.array(self_._photon_channels, dtype=np.int64),
                 dpe=np.array(self_._photon_is_dpe, dtype=bool),
@@ -251,7 +263,12 @@ def run_chain(ref, config, instructions, seed, pattern_maps=None, noise=None, ap
     if pattern_maps is not None:
         rd.resource.s1_pattern_map = pattern_maps['s1']
         rd.resource.s2_pattern_map = pattern_maps['s2']
-    truth_dtype = instruction_dtype + truth_extra_dtype + [('fill', bool)]
+    return record_chain(ref, rd, instructions, seed, instruction_dtype + truth_extra_dtype + [('fill', bool)],
+                        store_currents=store_currents, secondaries=secondaries if ele_ap is not None else None)
+
+
+def record_chain(ref, rd, instructions, seed, truth_dtype, store_currents=False, secondaries=None, store_entry=False):
+    """Run a constructed reference RawData / RawDataOptical over instructions under the Recorder; flat dict of arrays."""
     truth = np.zeros(max(len(instructions) * 2, 10), dtype=truth_dtype)
     rec = Recorder(ref)
     rec.install()
@@ -263,9 +280,13 @@ def run_chain(ref, config, instructions, seed, pattern_maps=None, noise=None, ap
         rec.uninstall()
 
     out = dict(instructions=instructions, seed=np.int64(seed))
-    if ele_ap is not None:
+    if secondaries is not None:
         out['secondaries'] = np.concatenate(secondaries) if secondaries else np.zeros(0, dtype=instructions.dtype)
     calls = rec.calls
+    if store_entry:
+        out['call_in_off'] = np.concatenate([[0], np.cumsum([len(c['in_t']) for c in calls])]).astype(np.int64)
+        out['in_t'] = np.concatenate([c['in_t'] for c in calls] + [np.zeros(0, np.int64)])
+        out['in_ch'] = np.concatenate([c['in_ch'] for c in calls] + [np.zeros(0, np.int64)]).astype(np.int16)
     kinds = ['Pulse', 'S1', 'S2', 'PMT_Afterpulse', 'PhotoIonization_Electron', 'PhotoElectric_Electron']
     out['call_kind'] = np.array([kinds.index(c['kind']) for c in calls], dtype=np.int8)
     out['call_has_gains'] = np.array([c['has_gains'] for c in calls], dtype=bool)
@@ -489,6 +510,182 @@ def fixture_chain_runsets(ref):
             dict(type=1, time=3 * MS, x=0, y=0, z=-30, amp=2000), dict(type=2, time=3 * MS, x=0, y=0, z=-30, amp=100)]
     np.savez_compressed(HERE + '/chain_runsets.npz',
                         **run_chain(ref, base_config(save_full_truth=False), make_instructions(rows), 707, pat))
+
+
+N_NVETO = 120
+
+
+def optical_chain_overrides(case):
+    """chains J: the 120-channel nVeto configuration of RawDataOptical (one dead PMT); shared with the tests through
+    chain_optical_config.json.  'main' leaves nveto_time_max_cutoff out (rawdata.py:481: default int(1e6))"""
+    gains = np.full(N_NVETO, 2e6)
+    gains[7] = 0.0
+    ov = dict(detector='XENONnT_neutron_veto', n_tpc_pmts=N_NVETO, n_top_pmts=0, gains=gains, channels_bottom=[],
+              channel_map=dict(nveto=(2000, 2119), sum_signal=800, he=(500, 752)), right_raw_extension=2000)
+    if case == 'cutoff':
+        ov['nveto_time_max_cutoff'] = 5000
+    return ov
+
+
+def optical_chain_inputs(case):
+    """instructions (_first / _last), flat channels and timings of the two optical chains"""
+    rng = np.random.default_rng(dict(main=1201, cutoff=1202)[case])
+    cutoff = optical_chain_overrides(case).get('nveto_time_max_cutoff', int(1e6))
+    n = dict(main=200, cutoff=40)[case]
+    # 1 us apart, with gaps above right_raw_extension: many clusters, some of several instructions
+    gap = np.where(rng.random(n) < 0.3, rng.integers(2500, 9000, n), 1000)
+    time = 1_000_000 + np.cumsum(gap)
+    nph = rng.integers(0, 9, n)
+    if case == 'main':
+        time[61] = time[60]                                 # two instructions with the same time
+        first_in_cluster = np.flatnonzero(gap > 2000)
+        nph[[0, first_in_cluster[5], 100, n - 1]] = 0       # _first == _last: first of the stream / of a cluster, inside, last of the stream
+        nph[[30, 150, n - 3]] = [4, 6, 8]
+    else:
+        nph[[3, n - 1]] = 0
+        nph[[10, 20]] = [5, 7]
+    ins = np.zeros(n, dtype=instruction_dtype + optical_extra_dtype)
+    ins['type'], ins['time'], ins['event_number'], ins['amp'], ins['recoil'] = 1, time, np.arange(n), nph, 7
+    ins['_last'] = np.cumsum(nph)
+    ins['_first'] = ins['_last'] - nph
+    tot = int(nph.sum())
+    channels = rng.integers(0, N_NVETO, tot).astype(np.int64)
+    channels[rng.random(tot) < 0.04] = 7                    # photons on the dead PMT
+    if case == 'main':
+        timings = rng.exponential(60, tot).astype(np.int64)
+        timings[rng.random(tot) < 0.03] = -rng.integers(1, 400)
+        timings[rng.random(tot) < 0.03] = cutoff + rng.integers(0, 5000)
+        late = rng.random(tot) < 0.02                       # a few late photons: pulses that reach into later clusters
+        timings[late] = rng.integers(1500, 12000, late.sum())
+        a = int(ins['_first'][30]); timings[a:a + 4] = [-1, cutoff, 2 * cutoff, -300]          # every photon of this one is cut
+        a = int(ins['_first'][150]); timings[a:a + 3] = [0, -1, 1]; channels[a:a + 3] = [11, 11, 7]
+        # the far end of the accepted window, near the end of the stream (a pulse 1 ms late keeps the cache open behind it)
+        a = int(ins['_first'][n - 3]); timings[a:a + 3] = [cutoff - 1, cutoff, cutoff + 1]; channels[a:a + 3] = [33, 33, 34]
+    else:
+        timings = rng.integers(-500, 2 * cutoff, tot).astype(np.int64)
+        a = int(ins['_first'][10]); timings[a:a + 5] = [cutoff - 1, cutoff, cutoff + 1, 0, -1]
+        a = int(ins['_first'][20]); timings[a:a + 3] = [4999, 5000, 4998]; channels[a:a + 3] = [50, 50, 50]
+    return ins, channels, timings, cutoff
+
+
+def fixture_chain_optical(ref):
+    """chains J: RawDataOptical (rawdata.py:461-495) over optical instructions -- sim_primary's slicing, window mask, channel sort and
+    event-time offset (the photon list on entry to Pulse.__call__: in_t / in_ch), then everything the other chains record"""
+    cfgs = {}
+    for case in ('main', 'cutoff'):
+        ov = optical_chain_overrides(case)
+        ins, channels, timings, cutoff = optical_chain_inputs(case)
+        cfg = base_config(**ov)
+        ref.load_resource._cached_configs.clear()
+        ref.pulse._cached_pmt_current_templates.clear()
+        ref.pulse._cached_uniform_to_pe_arr.clear()
+        orig_get = ref.load_resource.straxen.get_resource
+        # the nVeto Resource loads nv_pmt_qe, which only the Geant4 front end reads (strax_interface.py:253)
+        ref.load_resource.straxen.get_resource = lambda path, fmt='text': ({} if fmt == 'json' else orig_get(path, fmt=fmt))
+        try:
+            rd = ref.rawdata.RawDataOptical(cfg, channels=channels, timings=timings)
+        finally:
+            ref.load_resource.straxen.get_resource = orig_get
+        out = record_chain(ref, rd, ins, dict(main=1211, cutoff=1212)[case],
+                           instruction_dtype + optical_extra_dtype + truth_extra_dtype + [('fill', bool)], store_entry=True)
+        out.update(channels=channels, timings=timings, cutoff=np.int64(cutoff))
+        name = 'chain_optical.npz' if case == 'main' else 'chain_optical_cutoff.npz'
+        np.savez_compressed(HERE + '/' + name, **out)
+        cfgs[case] = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in ov.items()}
+        print(case, len(out['call_kind']), 'calls', len(out['dg_left']), 'windows', len(out['in_t']), 'photons of', len(timings))
+    with open(HERE + '/chain_optical_config.json', 'w') as f:
+        json.dump(cfgs, f)
+
+
+# the probability columns of pmt_ap_tables.npz scaled up for the draw fixture (and, through the fixture, for the tests that
+# compare with it): ~10 % afterpulses per parent and element instead of ~1 %, so that 10^5s of afterpulses need 10^6 parents,
+# not 10^7.  For 'Uniform' the column is also the upper end of the delay (afterpulse.py:213-216): delays U(48, 96) ns.
+# 'Uniform_hi': P = 0.3, with pmt_ap_modifier 1.8 a double-PE parent always makes one (P * modifier * 2 > 1)
+PMT_AP_SCALE = dict(He=5.0, Xe=8.0, Uniform=12.0, Uniform_hi=37.5)
+PMT_AP_T_MODIFIER = 3
+
+
+def fixture_pmt_ap_draws(ref):
+    """Draws of the reference's PMT_Afterpulse.photon_afterpulse (afterpulse.py:172-249), a static method, on plain objects: per
+    element alone (a one-element table) and pmt_ap_modifier, parents on all 494 channels at time 0 (the returned time is the
+    delay), double-PE fraction p_double_pe_emision, non-uniform gains, pmt_ap_t_modifier 3.  Stored as COUNTS: parents per
+    channel (single / double PE), afterpulses per channel, histograms over the delay bin index (Uniform: over the delay in whole
+    ns) and the amplitude bin index, for He the joint delay x amplitude table coarsened to 20 x 20; one call with all elements."""
+    import types
+    tab = np.load(HERE + '/pmt_ap_tables.npz')
+    cfg0 = base_config()
+    p_dpe = float(cfg0['p_double_pe_emision'])
+    gains = np.round(np.random.default_rng(31).uniform(1.0e6, 3.0e6, N_TPC))
+
+    def tables(name, scale):
+        el = name.split('_')[0]
+        return {el: dict(delaytime_cdf=tab[f'{el}_delaytime_cdf'] * scale, amplitude_cdf=tab[f'{el}_amplitude_cdf'],
+                         delaytime_bin_size=float(tab[f'{el}_delaytime_bin_size']), amplitude_bin_size=float(tab[f'{el}_amplitude_bin_size']))}
+
+    def draw(uniform_to_pmt_ap, modifier, n_min, rng, chunk=2_000_000, max_chunks=200):
+        config = dict(pmt_ap_modifier=modifier, pmt_ap_t_modifier=PMT_AP_T_MODIFIER, gains=gains)
+        resource = types.SimpleNamespace(uniform_to_pmt_ap=uniform_to_pmt_ap)
+        single, double = np.zeros(N_TPC, np.int64), np.zeros(N_TPC, np.int64)
+        out, n, ordered = [], 0, True
+        for _ in range(max_chunks):
+            ch = rng.integers(0, N_TPC, chunk)
+            dpe = rng.random(chunk) < p_dpe
+            single += np.bincount(ch[~dpe], minlength=N_TPC); double += np.bincount(ch[dpe], minlength=N_TPC)
+            parent = types.SimpleNamespace(_photon_timings=np.zeros(chunk, np.int64), _photon_channels=ch, _photon_is_dpe=dpe)
+            t, c, g = ref.afterpulse.PMT_Afterpulse.photon_afterpulse(parent, resource, config)
+            ordered &= bool(np.all(np.diff(c) >= 0))
+            out.append((np.asarray(t, np.float64), np.asarray(c, np.int64), np.asarray(g, np.float64)))
+            n += len(t)
+            if n >= n_min:
+                break
+        assert n >= n_min
+        t, c, g = (np.concatenate([o[k] for o in out]) for k in range(3))
+        return single, double, t, c, g, ordered
+
+    out = dict(p_dpe=np.float64(p_dpe), gains=gains, t_modifier=np.int64(PMT_AP_T_MODIFIER),
+               **{f'scale_{k}': np.float64(v) for k, v in PMT_AP_SCALE.items()})
+    cases = [(el, m) for el in ('He', 'Xe', 'Uniform') for m in (0.6, 1.0, 1.8)] + [('Uniform_hi', 1.8)]
+    names = []
+    np.random.seed(1301)                                  # photon_afterpulse draws from numpy's global generator
+    rng = np.random.default_rng(1302)                     # the parents
+    for name, m in cases:
+        el = name.split('_')[0]
+        case = f'{name}_m{int(round(m * 10)):02d}'
+        names.append(case)
+        T = tables(name, PMT_AP_SCALE[name])
+        single, double, t, c, g, ordered = draw(T, m, 400_000, rng)
+        assert ordered
+        out[f'{case}_par_single'], out[f'{case}_par_double'] = single, double
+        out[f'{case}_ap_ch'] = np.bincount(c, minlength=N_TPC).astype(np.int64)
+        if el == 'Uniform':
+            dbin = np.floor(t).astype(np.int64)          # Pulse.add_current receives the times .astype(int64) (pulse.py:130)
+            abin = np.rint(g / gains[c]).astype(np.int64)
+            out[f'{case}_delay'] = np.bincount(dbin, minlength=512).astype(np.int64)
+            out[f'{case}_amp'] = np.bincount(abin, minlength=4).astype(np.int64)
+        else:
+            dbin = np.rint((t + PMT_AP_T_MODIFIER) / T[el]['delaytime_bin_size']).astype(np.int64)
+            abin = np.rint(g / gains[c] / T[el]['amplitude_bin_size']).astype(np.int64)
+            assert np.allclose(dbin * T[el]['delaytime_bin_size'] - PMT_AP_T_MODIFIER, t) and dbin.min() >= 0 and dbin.max() < 200
+            assert np.allclose(abin * T[el]['amplitude_bin_size'] * gains[c], g, rtol=1e-9) and abin.max() < 100
+            out[f'{case}_delay'] = np.bincount(dbin, minlength=200).astype(np.int64)
+            out[f'{case}_amp'] = np.bincount(abin, minlength=100).astype(np.int64)
+            if el == 'He':
+                joint = np.zeros((20, 20), np.int64)
+                np.add.at(joint, (dbin // 10, abin // 5), 1)
+                out[f'{case}_joint'] = joint
+        print(case, 'parents', int(single.sum() + double.sum()), 'afterpulses', len(t))
+    # all elements in one call: the output is sorted by channel and the elements add
+    T = {}
+    for el in ('He', 'Xe', 'Uniform'):
+        T.update(tables(el, PMT_AP_SCALE[el]))
+    single, double, t, c, g, ordered = draw(T, 1.0, 400_000, rng)
+    names.append('all_m10')
+    out['all_m10_par_single'], out['all_m10_par_double'] = single, double
+    out['all_m10_ap_ch'] = np.bincount(c, minlength=N_TPC).astype(np.int64)
+    out['all_m10_channel_sorted'] = np.bool_(ordered)
+    print('all_m10', 'parents', int(single.sum() + double.sum()), 'afterpulses', len(t))
+    out['cases'] = np.array(names)
+    np.savez_compressed(HERE + '/pmt_ap_draws.npz', **out)
 
 
 class StubDelayHist:
@@ -1072,7 +1269,12 @@ def fixture_chain_stats(ref):
 if __name__ == '__main__':
     which = sys.argv[1:] or ['tables', 'add_current', 'chains', 'dists', 'models', 'stats', 'chunker', 'ele_ap_draws', 'gas_gap', 'aft_sigma', 'noise_float', 'diffusion', 'frontend']
     ref = import_reference_interface() if ('chunker' in which or 'frontend' in which) else import_reference()
-    p = fixture_tables(ref)
+    own = {'optical_chain', 'pmt_ap_draws'}           # these write their own files only
+    p = fixture_tables(ref) if set(which) - own else None
+    if 'optical_chain' in which:
+        fixture_chain_optical(ref)
+    if 'pmt_ap_draws' in which:
+        fixture_pmt_ap_draws(ref)
     if 'add_current' in which:
         fixture_add_current(ref, p)
     if 'chains' in which:

@@ -49,6 +49,33 @@ def geometry_chain_config():
     return xenonnt_test_config(**json.load(open(os.path.join(GOLDEN, 'chain_geometry_config.json'))))
 
 
+OPTICAL_CHAINS = dict(main='chain_optical.npz', cutoff='chain_optical_cutoff.npz')
+
+
+def optical_chain_config(case, **overrides):
+    """the config of the golden optical chains (make_golden.py: optical_chain_overrides): 120 nVeto channels, channel 7 dead,
+    right_raw_extension 2000; case 'cutoff' sets nveto_time_max_cutoff, 'main' leaves the key out"""
+    import json
+    ov = json.load(open(os.path.join(GOLDEN, 'chain_optical_config.json')))[case]
+    ov['gains'] = np.asarray(ov['gains'], dtype=np.float64)
+    ov['channels_bottom'] = np.asarray(ov['channels_bottom'], dtype=np.int64)
+    ov['channel_map'] = {k: (tuple(v) if isinstance(v, list) else v) for k, v in ov['channel_map'].items()}
+    c = xenonnt_test_config(**ov)
+    c['photon_area_distribution'] = dict(c['photon_area_distribution'], n_channels=len(ov['gains']))
+    c.update(overrides)
+    return c
+
+
+def photons_by_call_and_channel(off, t, ch):
+    """canonical form of a per-call photon list: per call the (channel, time) pairs sorted by channel, then time -- the order
+    inside a channel is not pinned (sim_primary sorts with numpy's default, unstable argsort)"""
+    out = []
+    for a, b in zip(off[:-1], off[1:]):
+        o = np.lexsort((np.asarray(t[a:b]), np.asarray(ch[a:b])))
+        out.append((np.asarray(ch[a:b], dtype=np.int64)[o].tolist(), np.asarray(t[a:b], dtype=np.int64)[o].tolist()))
+    return out
+
+
 def host_tables(config, resource=None):
     resource = resource or Resource(config)
     thr_truth, thr_zle = T.thresholds(config, N_ROWS)
@@ -138,7 +165,14 @@ def replay_chain_on_engine(eng, d, config, debug=True, force_dense=False):
     dpe = np.array(d['ph_dpe'], dtype=np.uint8)
     for k in np.where(d['call_has_gains'])[0]:        # pre-assigned gains: n_double_pe = 0 (pulse.py:105-106)
         dpe[d['call_ph_off'][k]:d['call_ph_off'][k + 1]] = 0
-    eng.load_photons(set_cluster, set_tmin, d['call_ph_off'], d['ph_t'], d['ph_ch'], d['ph_gain'], dpe)
+    off, t, ch, gain = d['call_ph_off'], d['ph_t'], d['ph_ch'], d['ph_gain']
+    live = np.asarray(config['gains'])[ch] > 0
+    if not live.all():
+        # photons on turned-off PMTs leave Pulse.__call__ before anything is made of them (pulse.py:89-90); wfs_load_photons wants them
+        # dropped (the optical chains carry some: RawDataOptical.sim_primary does not look at the gains)
+        off = np.concatenate([[0], np.cumsum(live)])[off]
+        t, ch, gain, dpe = t[live], ch[live], gain[live], dpe[live]
+    eng.load_photons(set_cluster, set_tmin, off, t, ch, gain, dpe)
     return eng.run()
 
 

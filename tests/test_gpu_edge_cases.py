@@ -12,6 +12,26 @@ from tests.test_gpu_generation import _instructions, _run_both, _compare, MS
 pytestmark = pytest.mark.gpu
 
 
+def _truth_rows_by_set(o, eng, s_ins):
+    """row of eng.truth() for every Pulse call of the oracle, by set identity: the oracle's calls are in processing order (cluster by
+    cluster, S1s before S2s), each primary call followed by its PMT-afterpulse call (kind 3) if it made photons; the engine's rows are
+    the caller's sets -- without run sets the sorted instructions (Engine._caller_sets gives None), then, when afterpulses are on, a
+    second block of the same size.  The pairing must be one to one."""
+    from wfsim_amd.scheduler import processing_order, schedule
+    assert eng._caller_sets(eng._lib_sets) is None
+    n = len(s_ins)
+    proc = iter(processing_order(s_ins, np.arange(n), schedule(s_ins, eng.config)[2]).tolist())
+    rows, cur = [], None
+    for kind in o['call_kind']:
+        if kind != 3:
+            cur = next(proc)
+            rows.append(cur)
+        else:
+            rows.append(n + cur)
+    assert len(set(rows)) == len(rows) == len(o['call_kind']) and max(rows) < len(eng.truth()[0])
+    return rows
+
+
 def test_batch_without_photons():
     cfg = xenonnt_test_config(seed=41, s1_detection_efficiency=0.0)
     ins = _instructions([dict(type=1, time=MS * (i + 1), x=0, y=0, z=-10, amp=100) for i in range(5)])
@@ -45,9 +65,12 @@ def test_very_large_tiles_dense_kernel_multi_window():
     # the oracle's in every column, n_pe_trigger (pulse.py:255: the first n_dpe photons of the channel slice) included
     acc, ts = eng.truth()
     tr = o['truth'].reshape(-1, 12)
-    for k in range(len(tr)):
-        kk = int(np.argmin(np.abs(acc[:, 0] - tr[k, 0])))
-        assert np.allclose(acc[kk], tr[k], rtol=1e-9), (k, acc[kk], tr[k])
+    # rows are paired by set identity, one to one (_truth_rows_by_set), not by the nearest photon number
+    rows_of = _truth_rows_by_set(o, eng, s_ins)
+    assert len(tr) == len(acc) == len(s_ins) == 2 and np.all(o['call_kind'] == 2)
+    for k, kk in enumerate(rows_of):
+        assert np.allclose(acc[kk], tr[k], rtol=1e-9), (k, kk, acc[kk], tr[k])
+    assert acc[rows_of[0], 0] != acc[rows_of[1], 0] and acc[:, 3].min() > 0          # (two different rows; n_pe_trigger is filled)
 
 
 def test_epoch_scale_times():
@@ -207,6 +230,8 @@ def test_generation_order_of_tiles_beyond_the_workgroup_sort():
     _compare(orc, o, eng, counts, s_ins)
     acc, ts = eng.truth()
     tr = o['truth'].reshape(-1, 12)
-    for k in range(len(tr)):
-        kk = int(np.argmin(np.abs(acc[:, 0] - tr[k, 0])))
-        assert np.allclose(acc[kk], tr[k], rtol=1e-9), (k, acc[kk], tr[k])
+    # rows are paired by set identity, one to one (_truth_rows_by_set): the two primaries and their afterpulse sets
+    rows_of = _truth_rows_by_set(o, eng, s_ins)
+    assert len(tr) == len(acc) == 2 * len(s_ins) == 4 and sorted(o['call_kind'].tolist()) == [1, 2, 3, 3]
+    for k, kk in enumerate(rows_of):
+        assert np.allclose(acc[kk], tr[k], rtol=1e-9), (k, kk, acc[kk], tr[k])

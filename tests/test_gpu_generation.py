@@ -426,3 +426,84 @@ def test_tile_generation_with_grouped_pulse_calls():
     assert eng.records().tobytes() == orc.pack_records().tobytes()
     acc, ts = eng.truth()
     assert acc.shape[0] == 3 and acc[:, 0].sum() == counts['n_photons']          # one truth row per Pulse call, every photon in one of them
+
+
+# ------------------------------------------------------------------------------------------------ against draws of the reference
+from tests.ap_statistics import DRAW_CASES as AP_DRAW_CASES      # noqa: E402
+
+
+def _device_ap_photons(cfg, ap, ins, rate, parents_per_instruction):
+    """the instructions through one engine alone (keep_photons): parents of instruction i in set i, its afterpulses in set n + i.
+    The library sizes its afterpulse arrays for a batch of P primary photons at P / 8 + 65536 and refuses a batch that makes more
+    (WFS_E_CAPACITY); the scaled tables make `rate` afterpulses per parent, up to 0.64, so the instructions go in batches small
+    enough for that rule (same engine, run-wide instruction numbers as RNG stream ids: the batches are independent draws)."""
+    cfg = dict(cfg, enable_pmt_afterpulses=True, uniform_to_pmt_ap=ap)
+    res = Resource(cfg)
+    order, key, cluster = schedule(ins, cfg)
+    s_ins = ins[order]
+    excess = 1.15 * rate - 0.125
+    per_batch = len(ins) if excess <= 0 else max(1, int(65536 / (excess * parents_per_instruction)))
+    eng = make_engine(cfg)
+    par, aps = {k: [] for k in ('t', 'ch', 'dpe', 'gain')}, {k: [] for k in ('t', 'ch', 'dpe', 'gain')}
+    for a in range(0, len(ins), per_batch):
+        b = min(a + per_batch, len(ins))
+        eng.load_instructions(s_ins[a:b], order[a:b].astype(np.uint32), cluster[a:b] - cluster[a], key[a:b], instruction_params(s_ins[a:b], cfg, res))
+        counts = eng.run()
+        ph = eng.photons()
+        n = b - a
+        assert counts['n_pulse_sets'] == 2 * n and len(ph['set_off']) == 2 * n + 1
+        cut = int(ph['set_off'][n])
+        for k in par:
+            par[k].append(ph[k][:cut]); aps[k].append(ph[k][cut:])
+    return eng, cfg, {k: np.concatenate(v) for k, v in par.items()}, {k: np.concatenate(v) for k, v in aps.items()}
+
+
+@pytest.mark.parametrize('element,modifier', AP_DRAW_CASES)
+def test_device_afterpulses_of_s1_parents_against_reference_draws(element, modifier):
+    """block-generated S1 parents without time spread (ap_generate, k_ap_finish, the integer screen ap_threshold): the inputs, the
+    statistics and the thresholds of tests/test_pmt_afterpulse_cpu.py::test_oracle_afterpulses_against_reference_draws, from
+    eng.photons(), against the same draws of the reference (tests/golden/pmt_ap_draws.npz).  Observed: the figures listed in the
+    docstring of tests/test_pmt_afterpulse_cpu.py, digit for digit (device and oracle make the same photons)"""
+    from tests import ap_statistics as S
+    ap = S.scaled_tables(element)
+    cfg = S.draw_config(modifier, 101)
+    ins = S.s1_instructions_for(element, modifier, cfg)
+    eng, cfg, par, aps = _device_ap_photons(cfg, ap, ins, S.afterpulses_per_parent(element, modifier, cfg['p_double_pe_emision']), 0.1 * ins['amp'][0])
+    counts, late = S.photon_counts(element, ap, cfg['gains'], cfg['pmt_ap_t_modifier'], par['t'], par['ch'], par['dpe'], aps['t'], aps['ch'], aps['gain'])
+    fx = S.fixture_counts(S.case_name(element, modifier))
+    assert counts['ap_ch'].sum() >= S.MIN_AFTERPULSES and counts['ap_ch'].min() > 0
+    if element.startswith('Uniform'):
+        assert np.array_equal(aps['gain'], np.asarray(cfg['gains'])[aps['ch']])
+    res = S.compare(counts, fx, late_fraction=late)
+    print(f'{S.case_name(element, modifier)} (device, S1 parents): {int(counts["ap_ch"].sum())} afterpulses: {S.fmt(res)}')
+    assert {'p_rate', 'z_total', 'p_delay', 'z_mean_delay'} <= set(res) and ('p_joint' in res) == (element == 'He')
+    assert S.accepted(res), S.fmt(res)
+
+
+@pytest.mark.parametrize('element', ['He', 'Xe', 'Uniform'])
+def test_device_afterpulses_of_tile_generated_s2_parents_against_reference_draws(element):
+    """tile-generated S2 parents (k_s2_tile<.., AP>, k_ap_seg): their time spread cannot be removed, so channels / rates and amplitude
+    bins are compared with the reference's draws; the delays of these afterpulses are covered photon by photon against the oracle
+    (test_pmt_afterpulses_of_large_tile_generated_tiles), and the oracle's delays against the same draws on the CPU.
+    Observed (seeds fixed): He 253583 afterpulses p_amp 0.695 p_rate 0.733 z_total -0.24; Xe 235317: 0.0761, 0.752, -0.47;
+    Uniform 239044: p_rate 0.132 z_total 0.80"""
+    from tests import ap_statistics as S
+    fxa = S.golden('pmt_ap_draws.npz')
+    ap = S.scaled_tables(element)
+    cfg = xenonnt_test_config(seed=103, s2_secondary_sc_gain=100.0, tile_local_min_photons=0, pmt_ap_modifier=1.0,
+                              pmt_ap_t_modifier=int(fxa['t_modifier']), gains=fxa['gains'])
+    eng, cfg, par, aps = _device_ap_photons(cfg, ap, S.s2_instructions_for(element, 1.0, cfg), S.afterpulses_per_parent(element, 1.0, cfg['p_double_pe_emision']), 300_000)
+    eng.set_profiling(True)          # (the last batch once more, with kernel timers: which generator made the parents)
+    eng.run()
+    kt = eng.kernel_times()
+    assert 'k_s2_tile' in kt and kt['k_s2_tile'][1] >= 1, sorted(kt)
+    counts, _ = S.photon_counts(element, ap, cfg['gains'], cfg['pmt_ap_t_modifier'], par['t'], par['ch'], par['dpe'], aps['t'], aps['ch'], aps['gain'],
+                                exact_delays=False)
+    fx = S.fixture_counts(S.case_name(element, 1.0))
+    assert counts['ap_ch'].sum() >= S.MIN_AFTERPULSES and counts['ap_ch'].min() > 0
+    if element == 'Uniform':
+        assert np.array_equal(aps['gain'], np.asarray(cfg['gains'])[aps['ch']])
+    res = S.compare(counts, fx, tables=('amp', 'rate'))
+    print(f'{S.case_name(element, 1.0)} (device, tile-generated S2 parents): {int(counts["ap_ch"].sum())} afterpulses: {S.fmt(res)}')
+    assert {'p_rate', 'z_total'} <= set(res) and ('p_amp' in res) == (element != 'Uniform')
+    assert S.accepted(res), S.fmt(res)

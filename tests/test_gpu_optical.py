@@ -3,9 +3,9 @@ import numpy as np
 import pytest
 
 import wfsim_amd
-from tests.helpers import make_oracle
+from tests.helpers import (OPTICAL_CHAINS, golden, make_engine, make_oracle, optical_chain_config, photons_by_call_and_channel)
 from wfsim_amd.config import xenonnt_test_config
-from wfsim_amd.dtypes import instruction_dtype, optical_extra_dtype
+from wfsim_amd.dtypes import instruction_dtype, optical_extra_dtype, truth_extra_dtype
 
 pytestmark = pytest.mark.gpu
 
@@ -118,3 +118,163 @@ def test_mc_chain_plugin_tpc_and_nveto():
     plugin = wfsim_amd.RawRecordsFromMcChain(dict(cfg, targets=('tpc',), entry_stop=None))
     out2 = ministrax.run_plugin(plugin)
     assert sum(len(c.data) for c in out2['raw_records_nv']) == 0 and sum(len(c.data) for c in out2['raw_records']) > 100
+
+
+# ------------------------------------------------------------------------------------------------ golden chains J
+# tests/golden/chain_optical.npz, chain_optical_cutoff.npz: runs of the reference's RawDataOptical (tests/test_optical_chain_reference.py
+# pins the oracle on them; here the device)
+TRUTH_COUNTS = ['n_photon', 'n_pe', 'n_photon_trigger', 'n_pe_trigger']
+
+
+def _assert_truth_of_fixture(eng, d):
+    acc, ts = eng.truth()
+    assert len(acc) == len(d['call_kind'])
+    for j, f in enumerate(TRUTH_COUNTS):
+        assert np.array_equal(acc[:, j], d['call_truth_' + f]), f
+        assert np.array_equal(acc[:, 6 + j], d['call_truth_' + f + '_bottom']), f
+    assert np.array_equal(acc[:, 0], d['truth']['n_photon'])
+    for j, f in [(4, 'raw_area'), (5, 'raw_area_trigger')]:
+        assert np.allclose(acc[:, j], d['call_truth_' + f], rtol=1e-12, atol=0), f
+
+
+@pytest.mark.parametrize('case', sorted(OPTICAL_CHAINS))
+def test_optical_chain_replay_vs_reference(case):
+    """the reference's photons (after its transit-time draw, with its gains; photons on the dead PMT dropped as Pulse.__call__ drops
+    them) injected per Pulse call on the nVeto configuration, with the debug copies on -- which keeps the rows in the HBM accumulators
+    (k_zle / k_pack; the resident kernel keeps no copies of currents or rows) -- in both arithmetic modes: pulses, windows, rows, ZLE
+    intervals and record heads equal the fixture, the integer truth accumulators too.  The resident path:
+    test_optical_chain_records_on_both_digitisation_paths"""
+    from tests.test_gpu_parity import _check_chain
+    d, eng = _check_chain(OPTICAL_CHAINS[case], optical_chain_config(case, row_resident=False))
+    _assert_truth_of_fixture(eng, d)
+
+
+@pytest.mark.parametrize('fma', [True, False])
+@pytest.mark.parametrize('row_resident', [True, False])
+@pytest.mark.parametrize('case', sorted(OPTICAL_CHAINS))
+def test_optical_chain_records_on_both_digitisation_paths(case, row_resident, fma):
+    """the same replay without debug copies, so that config row_resident selects the path: on -- every (window, channel) row made,
+    finished and zero-suppressed by k_row_pulse -- and off (accumulators, k_zle, k_pack); which kernel ran is asserted from the kernel
+    timers.  Either way, in both arithmetic modes, the records are the fixture's ZLE tuples fragment by fragment (time, channel,
+    pulse_length, record_i, length and every data sample, in the reference's yield order) and the integer truth is the fixture's."""
+    from tests.helpers import replay_chain_on_engine, with_fma
+    from wfsim_amd.dtypes import raw_record_dtype
+    d = golden(OPTICAL_CHAINS[case])
+    cfg = with_fma(optical_chain_config(case, row_resident=row_resident), fma)
+    eng = make_engine(cfg)
+    replay_chain_on_engine(eng, d, cfg, debug=False)
+    rec = eng.records()
+    spr = np.dtype(raw_record_dtype())['data'].shape[0]
+    plen = d['zle_right'] - d['zle_left'] + 1
+    nfrag = -(-plen // spr)
+    assert len(rec) == nfrag.sum() and len(plen) > 50
+    iv = np.repeat(np.arange(len(plen)), nfrag)                                   # interval of every fragment
+    frag = np.arange(len(rec)) - np.repeat(np.cumsum(nfrag) - nfrag, nfrag)       # its number inside the interval
+    assert np.array_equal(rec['record_i'], frag)
+    assert np.array_equal(rec['channel'], d['zle_ch'][iv])
+    assert np.array_equal(rec['time'], 10 * (d['zle_left'][iv] + spr * frag))
+    assert np.array_equal(rec['pulse_length'], plen[iv])
+    assert np.array_equal(rec['length'], np.minimum(spr, plen[iv] - spr * frag))
+    assert np.all(rec['dt'] == 10) and np.all(rec['baseline'] == 0)
+    data = np.concatenate([rec['data'][k][:rec['length'][k]] for k in range(len(rec))])
+    assert np.array_equal(data, d['zle_data'])
+    assert all(not rec['data'][k][rec['length'][k]:].any() for k in range(len(rec)))          # the tail of a last fragment is zero
+    _assert_truth_of_fixture(eng, d)
+    g = eng.groups()
+    keep = g['right'] >= g['left']
+    assert np.array_equal(g['left'][keep], d['dg_left']) and np.array_equal(g['right'][keep], d['dg_right'])
+    # which path made the rows: the same batch once more with the kernel timers on
+    eng.set_profiling(True)
+    eng.run()
+    kt = eng.kernel_times()
+    assert ('k_row_pulse' in kt) == row_resident, sorted(kt)
+    assert eng.records().tobytes() == rec.tobytes()
+
+
+@pytest.mark.parametrize('case', sorted(OPTICAL_CHAINS))
+def test_raw_data_optical_on_the_reference_inputs(case):
+    """wfsim_amd.RawDataOptical.iter_windows on the stored instructions / channels / timings (case 'cutoff': a non-default
+    nveto_time_max_cutoff through load_optical).  Calls, photons per call and channel and n_photon of the truth rows equal the
+    fixture; the entry times cannot be read off the device (it adds its own transit-time draw), so the device's photons equal the
+    oracle's photon by photon and the oracle's entry times equal the fixture's (as in tests/test_optical_chain_reference.py)"""
+    d = golden(OPTICAL_CHAINS[case])
+    cfg = optical_chain_config(case, seed=61)
+    ins, channels, timings = d['instructions'], d['channels'], d['timings']
+    cutoff = cfg.get('nveto_time_max_cutoff', int(1e6))
+    assert cutoff == int(d['cutoff']) and np.all(np.diff(ins['time']) >= 0)
+    rd = wfsim_amd.RawDataOptical(cfg, channels=channels, timings=timings)
+    rd.engine.keep_photons = True
+    tb = np.zeros(2 * len(ins), dtype=instruction_dtype + optical_extra_dtype + truth_extra_dtype + [('fill', bool)])
+    windows = list(rd.iter_windows(ins, truth_buffer=tb))
+    truth = tb[tb['fill']]
+    # ---- against the fixture: one call per instruction in the reference's order, live photons per call
+    assert len(truth) == len(d['truth']) == len(ins)
+    assert np.array_equal(truth['event_number'], d['truth']['event_number'])
+    assert np.array_equal(truth['n_photon'], d['truth']['n_photon'])
+    assert np.array_equal(truth['_first'], d['truth']['_first']) and np.array_equal(truth['_last'], d['truth']['_last'])
+    # ---- against the oracle, photon by photon (one batch: the engine still holds it)
+    orc = make_oracle(cfg)
+    orc.simulate_optical(ins, np.arange(len(ins), dtype=np.uint32), channels, timings, cutoff)
+    o = orc.results()
+    ph = rd.engine.photons()
+    live = np.asarray(cfg['gains']) > 0
+    assert len(ph['set_off']) - 1 == len(o['call_ph_off']) - 1 == len(ins)
+    for k in range(len(ins)):
+        a, b = o['call_ph_off'][k], o['call_ph_off'][k + 1]
+        c, e = ph['set_off'][k], ph['set_off'][k + 1]
+        mo, mg = live[o['ph_ch'][a:b]], live[ph['ch'][c:e]]
+        ko = np.lexsort((o['ph_gain'][a:b][mo], o['ph_t'][a:b][mo], o['ph_ch'][a:b][mo]))
+        kg = np.lexsort((ph['gain'][c:e][mg], ph['t'][c:e][mg], ph['ch'][c:e][mg]))
+        assert mo.sum() == mg.sum() == d['truth']['n_photon'][k], k
+        for f, g in [('ph_ch', 'ch'), ('ph_t', 't'), ('ph_gain', 'gain'), ('ph_dpe', 'dpe')]:
+            assert np.array_equal(o[f][a:b][mo][ko], ph[g][c:e][mg][kg]), (k, f)
+    # ---- photons per call and channel as the reference's sim_primary left them
+    chan_of = lambda off, ch: [np.bincount(np.asarray(ch[a:b])[live[ch[a:b]]], minlength=120).tolist() for a, b in zip(off[:-1], off[1:])]
+    assert chan_of(ph['set_off'], ph['ch']) == chan_of(d['call_in_off'], d['in_ch'])
+    assert photons_by_call_and_channel(o['call_ph_off'], o['opt_in_t'], o['opt_in_ch']) == \
+        photons_by_call_and_channel(d['call_in_off'], d['in_t'], d['in_ch'])
+    # ---- windows and records: the oracle's for the same streams
+    assert np.array_equal([w['left'] for w in windows], o['dg_left']) and np.array_equal([w['right'] for w in windows], o['dg_right'])
+    assert np.concatenate([w['records'] for w in windows]).tobytes() == orc.pack_records().tobytes()
+
+
+def test_optical_batch_after_a_run_set_batch_on_the_same_engine():
+    """Engine.load_optical after a batch with run sets (save_full_truth off: S1s that share Pulse calls, sets numbered by their first
+    instruction -- rows 0, 3, 5 of 6): truth(), photons() and electron_stats() of the optical batch are its own rows, not a remap
+    through the earlier batch's sets; the truth is the fixture's"""
+    from wfsim_amd.physics import instruction_params
+    from wfsim_amd.resource import Resource
+    from wfsim_amd.scheduler import schedule, run_sets
+    d = golden(OPTICAL_CHAINS['main'])
+    dummy = ['constant dummy', 1, [120]]
+    cfg = optical_chain_config('main', seed=62, save_full_truth=False, s1_pattern_map=dummy, s2_pattern_map=dummy)
+    eng = make_engine(cfg)
+    s1 = np.zeros(6, dtype=instruction_dtype)
+    s1['type'], s1['amp'], s1['z'], s1['recoil'] = 1, 400, -10, 7
+    s1['time'] = [1_000_000, 1_000_050, 1_000_090, 1_003_000, 1_003_020, 1_009_000]
+    order, key, cluster = schedule(s1, cfg)
+    rs, n_sets = run_sets(s1[order], key, cluster, cfg)
+    assert rs.tolist() == [0, 0, 0, 1, 1, 2]
+    eng.load_instructions(s1[order], order.astype(np.uint32), cluster, key, instruction_params(s1[order], cfg, Resource(cfg)), run_set=rs)
+    counts = eng.run()
+    acc, _ = eng.truth()
+    assert counts['n_pulse_sets'] == len(acc) == 3 and np.all(acc[:, 0] > 0)
+    # ---- the optical chain on the same engine
+    ins = d['instructions']
+    order, key, cluster = schedule(ins, cfg)
+    assert np.array_equal(order, np.arange(len(ins)))
+    eng.load_optical(ins, order.astype(np.uint32), cluster, key, d['channels'], d['timings'], int(d['cutoff']))
+    counts = eng.run()
+    acc, ts = eng.truth()
+    assert counts['n_pulse_sets'] == len(acc) == len(ins)
+    assert np.array_equal(acc[:, 0], d['truth']['n_photon'])
+    ph = eng.photons()
+    live = np.asarray(cfg['gains']) > 0
+    assert len(ph['set_off']) == len(ins) + 1
+    assert [int(live[ph['ch'][a:b]].sum()) for a, b in zip(ph['set_off'][:-1], ph['set_off'][1:])] == d['truth']['n_photon'].tolist()
+    assert len(eng.electron_stats()) == len(ins)
+    # and the same truth as a fresh engine
+    fresh = make_engine(cfg)
+    fresh.load_optical(ins, order.astype(np.uint32), cluster, key, d['channels'], d['timings'], int(d['cutoff']))
+    fresh.run()
+    assert np.array_equal(fresh.truth()[0], acc) and np.array_equal(fresh.truth()[1], ts, equal_nan=True)

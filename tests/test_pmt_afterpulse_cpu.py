@@ -3,7 +3,32 @@ afterpulse.py:172-249 checked on the CPU oracle.  Per element and parent photon 
 makes an afterpulse of the element when rU0 / pmt_ap_modifier (/ 2 for a double-PE parent) <= P_element(channel), its delay is the
 bin of the element's cumulative delay row nearest to that scaled uniform, its amplitude the bin of the amplitude row nearest to
 the second uniform.  Here: afterpulses per channel against sum_e P_e(channel) * modifier * (singles + 2 * doubles), and the delay
-and amplitude laws of single elements against the tables."""
+and amplitude laws of single elements against the tables.
+
+Second half: the oracle against DRAWS of the reference's own photon_afterpulse (tests/golden/pmt_ap_draws.npz; statistics and
+thresholds in tests/ap_statistics.py: p > 1e-3 per table, |z| < 4 per total -- conditions, not measurements).  Observed (seeds
+fixed: each figure is one deterministic number; the device leg,
+tests/test_gpu_generation.py::test_device_afterpulses_of_s1_parents_against_reference_draws, gives the same ones because device
+and oracle agree photon by photon):
+
+    case            afterpulses (fixture)   p_delay  p_amp   p_joint  p_rate  z_total  z_mean_delay
+    He_m06          229186 (446579)         0.654    0.379   0.842    0.768    0.66     0.35
+    He_m10          235483 (496935)         0.800    0.157   0.332    0.952    0.62     0.42
+    He_m18          238368 (447560)         0.232    0.567   0.286    0.323    0.37     0.30
+    Xe_m06          229598 (415664)         0.0625   0.256   -        0.696    0.41    -0.37
+    Xe_m10          231995 (461496)         0.704    0.640   -        0.976    0.07     0.75
+    Xe_m18          232630 (415471)         0.633    0.131   -        0.706   -1.45     0.50
+    Uniform_m06     227878 (420583)         0.134    -       -        0.711   -0.03    -0.14
+    Uniform_m10     227728 (467778)         0.926    -       -        0.0784  -0.64     1.30
+    Uniform_m18     236131 (421989)         0.984    -       -        0.0427  -1.82    -1.10
+    Uniform_hi_m18  265175 (1281542)        0.746    -       -        0.0156   0.62    -0.89
+    all_m10         253117 (713194)         -        -       -        0.0442   0.43     -
+
+(p_rate uses binomial variances: Poisson ones are up to a third too large at these probabilities, give p_rate up to 1.000 and would
+hide a rate error.  Uniform_hi: a double-PE parent always fires, the
+weight singles + 2 * doubles is then only approximate, see rate_tests.)  Power: the three wrong laws of
+test_the_statistics_reject_three_plausible_wrong_laws give p_delay 1.6e-11 / z_mean_delay 13 (first bin above), z_total -82 (no
+halving for double PE), p_joint 0 (one uniform for delay and amplitude, marginals p 0.03 / 0.08); the reference's law, drawn the same way, p 0.13 - 0.71."""
 import numpy as np
 import pytest
 from scipy.stats import chisquare
@@ -110,3 +135,98 @@ def test_delay_and_amplitude_of_one_element():
         got_a = np.bincount(np.clip(k, 0, len(ac0) - 1), minlength=len(ac0))
         keep = exp_a > 10
         assert chisquare(got_a[keep], exp_a[keep] * got_a[keep].sum() / exp_a[keep].sum())[1] > 1e-4
+
+
+# ------------------------------------------------------------------------------------------------ against draws of the reference
+from tests import ap_statistics as S      # noqa: E402
+
+DRAW_CASES, MIN_AFTERPULSES = S.DRAW_CASES, S.MIN_AFTERPULSES
+WRONG_LAWS = [('He', 'first_above', ('p_delay', 'z_mean_delay')), ('He', 'no_dpe', ('z_total',)), ('He', 'one_uniform', ('p_joint',))]
+
+
+def oracle_counts(element, modifier, seed=101):
+    ap = S.scaled_tables(element)
+    cfg = dict(S.draw_config(modifier, seed), enable_pmt_afterpulses=True, uniform_to_pmt_ap=ap)
+    ins = S.s1_instructions_for(element, modifier, cfg)
+    orc = make_oracle(cfg, ap)
+    orc.simulate(ins, np.arange(len(ins), dtype=np.uint32), instruction_params(ins, cfg, Resource(cfg)))
+    o = orc.results()
+    kind, n_call = o['call_kind'], np.diff(o['call_ph_off'])
+    is_ap = np.repeat(kind == 3, n_call)
+    par, aps = np.flatnonzero(~is_ap), np.flatnonzero(is_ap)
+    counts, late = S.photon_counts(element, ap, cfg['gains'], cfg['pmt_ap_t_modifier'], o['ph_t'][par], o['ph_ch'][par], o['ph_dpe'][par],
+                                   o['ph_t'][aps], o['ph_ch'][aps], o['ph_gain'][aps])
+    if element.startswith('Uniform'):
+        assert np.array_equal(o['ph_gain'][aps], cfg['gains'][o['ph_ch'][aps]])          # amplitude 1 (afterpulse.py:217)
+    return counts, late
+
+
+@pytest.mark.parametrize('element,modifier', DRAW_CASES)
+def test_oracle_afterpulses_against_reference_draws(element, modifier):
+    """the oracle's afterpulses of one element against the draws of the reference's photon_afterpulse with the same (scaled) tables:
+    delay bins, amplitude bins, the He joint table, afterpulses per channel relative to the parents' weight (p > 1e-3 each); total
+    rate and mean delay bin (|z| < 4 each).  Seeds are fixed: every figure below is one deterministic number."""
+    counts, late = oracle_counts(element, modifier)
+    fx = S.fixture_counts(S.case_name(element, modifier))
+    assert counts['ap_ch'].sum() >= MIN_AFTERPULSES and fx['ap_ch'].sum() >= 2 * MIN_AFTERPULSES
+    assert counts['ap_ch'].min() > 0 and fx['par_single'].min() > 0 and fx['par_double'].min() > 0
+    res = S.compare(counts, fx, late_fraction=late)
+    print(f'{S.case_name(element, modifier)}: {int(counts["ap_ch"].sum())} afterpulses of {int(counts["par_single"].sum() + counts["par_double"].sum())} parents '
+          f'(fixture {int(fx["ap_ch"].sum())}): {S.fmt(res)}')
+    expected = {'p_rate', 'z_total', 'p_delay', 'z_mean_delay'} | ({'p_amp'} if element in ('He', 'Xe') else set()) | ({'p_joint'} if element == 'He' else set())
+    assert set(res) == expected
+    assert S.accepted(res), S.fmt(res)
+
+
+def test_the_statistics_reject_three_plausible_wrong_laws():
+    """power check: numpy draws from the same (scaled He) tables at the sample size of the oracle leg (~1.9 x 10^6 parents, ~2.3 x 10^5
+    afterpulses) under three wrong laws -- the first delay bin above u instead of the nearest, no halving of the uniform of a double-PE
+    parent, the amplitude looked up with the delay's uniform (normalised, so that both marginals stay right) -- are each REJECTED by
+    the same helper at the same thresholds, through the statistic that is there for it; the law of afterpulse.py:172-249 as numpy_draws states it is accepted"""
+    fx_all = S.golden('pmt_ap_draws.npz')
+    fx = S.fixture_counts('He_m10')
+    tables, p_dpe = S.scaled_tables('He'), float(fx_all['p_dpe'])
+    n_parents = 1_900_000
+    good = S.compare(S.numpy_draws('He', tables, 1.0, p_dpe, n_parents, seed=501), fx)
+    print('reference law:', S.fmt(good))
+    assert S.accepted(good), S.fmt(good)
+    for k, (element, law, through) in enumerate(WRONG_LAWS):
+        c = S.numpy_draws(element, tables, 1.0, p_dpe, n_parents, seed=502 + k, law=law)
+        assert c['ap_ch'].sum() <= 1.25 * 235_483          # not more afterpulses than the oracle leg has (no_dpe has fewer)
+        res = S.compare(c, fx)
+        print(f'{law}:', S.fmt(res))
+        assert not S.accepted(res), (law, S.fmt(res))
+        for name in through:
+            v = res[name]
+            assert (v < S.P_MIN) if name.startswith('p_') else (abs(v) > S.Z_MAX), (law, name, v)
+    # 'one_uniform' keeps both marginals: only the joint table can see it
+    assert res['p_delay'] > S.P_MIN and res['p_amp'] > S.P_MIN
+
+
+def test_all_elements_in_one_call_add_and_come_out_channel_sorted():
+    """the fixture's all-elements call (afterpulse.py:236-246: the elements' afterpulses are stacked and sorted by channel): the
+    reference's output was channel sorted; its afterpulses per channel are the sum of the single-element cases' rates; and the oracle
+    with all three (scaled) elements makes afterpulses per channel at that rate, channel sorted inside every afterpulse call"""
+    fx_all = S.golden('pmt_ap_draws.npz')
+    assert bool(fx_all['all_m10_channel_sorted'])
+    fa = S.fixture_counts('all_m10')
+    w = lambda c: c['par_single'] + 2.0 * c['par_double']
+    parts = [S.fixture_counts(S.case_name(el, 1.0)) for el in S.ELEMENTS]
+    rate = sum(c['ap_ch'] / w(c) for c in parts)
+    var = sum(c['ap_ch'] / w(c) ** 2 for c in parts) * w(fa) ** 2 + fa['ap_ch']          # (Poisson bounds: variances from above)
+    z = (fa['ap_ch'] - rate * w(fa)) / np.sqrt(var)
+    assert abs(z.sum() / np.sqrt(len(z))) < S.Z_MAX and (z ** 2).sum() < len(z) + 5 * np.sqrt(2 * len(z))
+    ap = S.scaled_tables('He', only=False)
+    cfg = dict(S.draw_config(1.0, 107), enable_pmt_afterpulses=True, uniform_to_pmt_ap=ap)
+    ins = S.s1_instructions_for('He', 1.0, cfg)[:12]
+    orc = make_oracle(cfg, ap)
+    orc.simulate(ins, np.arange(len(ins), dtype=np.uint32), instruction_params(ins, cfg, Resource(cfg)))
+    o = orc.results()
+    kind, off = o['call_kind'], o['call_ph_off']
+    for k in np.flatnonzero(kind == 3):
+        assert np.all(np.diff(o['ph_ch'][off[k]:off[k + 1]]) >= 0)
+    is_ap = np.repeat(kind == 3, np.diff(off))
+    c = S.ap_counts('all', o['ph_ch'][~is_ap], o['ph_dpe'][~is_ap], o['ph_ch'][is_ap])
+    p_rate, z_total = S.rate_tests(c, fa, n_elements=3)
+    print(f'all_m10: {int(c["ap_ch"].sum())} afterpulses: p_rate={p_rate:.3g} z_total={z_total:.3g}')
+    assert c['ap_ch'].sum() > 150_000 and p_rate > S.P_MIN and abs(z_total) < S.Z_MAX

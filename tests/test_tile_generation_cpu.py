@@ -183,6 +183,16 @@ def test_run_sets_are_numbered_by_their_first_instruction():
     assert first_instruction_of_sets([0, 2, 2], 3) is None                  # a set number without instructions
 
 
+def test_run_set_numbers_outside_the_range_are_rejected():
+    """a negative set number would be wrapped round by np.minimum.at and silently name the first instruction of the LAST sets; one
+    beyond n_sets would fail deep inside numpy"""
+    import pytest
+    from wfsim_amd.engine import first_instruction_of_sets
+    for bad in ([0, -1, 1], [-1, -1, -1], [0, 1, 3]):
+        with pytest.raises(ValueError, match='run set numbers'):
+            first_instruction_of_sets(bad, 3)
+
+
 def test_grouped_pulse_calls_keep_the_per_electron_generator_their_neighbours_do_not():
     """save_full_truth=False (rawdata.py:106-127): S2s whose keys are at most int(0.2 / v) ns apart share a Pulse call and are generated
     electron by electron; an S2 alone in its call takes the tile path -- the same photons as with save_full_truth=True"""

@@ -157,6 +157,8 @@ def first_instruction_of_sets(run_set, n_sets):
     scheduler numbers the S1 calls of a cluster before its S2 calls, rawdata.py:102.)"""
     run_set = np.asarray(run_set)
     n = len(run_set)
+    if n and (run_set.min() < 0 or run_set.max() >= n_sets):      # (np.minimum.at would wrap a negative number round to the last sets)
+        raise ValueError(f'run set numbers must lie in [0, {n_sets}): got {int(run_set.min())} .. {int(run_set.max())}')
     first = np.full(n_sets, n, dtype=np.int64)
     np.minimum.at(first, run_set, np.arange(n))
     return first if np.all(first < n) else None
@@ -409,12 +411,19 @@ class Engine:
 
     def load_optical(self, ins, gid, cluster, tmin, channels, timings, time_cutoff):
         """ins: optical instructions (with _first/_last) sorted by time; channels/timings: the flat photon arrays"""
+        self._forget_run_sets()
         a = [_arr(ins['time'], np.int64), _arr(gid, np.uint32), _arr(cluster, np.int32), _arr(tmin, np.int64),
              _arr(ins['_first'], np.int32), _arr(ins['_last'], np.int32), _arr(channels, np.int32), _arr(timings, np.int64)]
         self._check(self.lib.wfs_load_optical(self._h, C.c_int64(len(ins)), *[_p(x) for x in a], C.c_int64(len(a[-1])),
                                               C.c_int64(int(time_cutoff))))
 
+    def _forget_run_sets(self):
+        """a batch without run sets follows (optical input, injected photons): the outputs are the library's rows again, not the rows
+        of the run sets of an earlier load_instructions"""
+        self._set_rows = self._n_run_sets = None
+
     def load_photons(self, set_cluster, set_tmin, set_off, t, ch, gain, dpe=None):
+        self._forget_run_sets()
         a = [_arr(set_cluster, np.int32), _arr(set_tmin, np.int64), _arr(set_off, np.int64), _arr(t, np.int64),
              _arr(ch, np.int16), _arr(gain, np.float64), _arr(dpe, np.uint8) if dpe is not None else None]
         self._check(self.lib.wfs_load_photons(self._h, C.c_int64(len(a[0])), *[_p(x) for x in a]))
