@@ -7,6 +7,7 @@
 // results can be compared photon by photon.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 typedef long long i64;
@@ -218,6 +219,67 @@ __host__ __device__ __forceinline__ i64 floormod(i64 a, i64 b) { i64 m = a % b; 
 constexpr int NOISE_PAD = 4;
 constexpr int WFS_SPR = 110;                   // samples per strax record (strax DEFAULT_RECORD_LENGTH; a compile-time constant: the divisions by it are in every row kernel)
 constexpr int NOISE_MIN_FAST = 512;            // shortest noise table of the fast row kernels (a block of 256 samples wraps at most once)
+
+// The device scalar block: counters that kernels bump with atomics, totals that the scans write, the error code, the origin of
+// the record sort keys.  wfs_run clears it at the start of a batch; the host copies it back (read_scal) and sizes the next stage
+// from it.  One member per 64-bit slot.  The layout is frozen: the tile-list counters were placed with their cache line in mind
+// (tile_list_append, wfs_kernels.h), so a new member takes a reserved slot and nothing moves.
+enum WfsDevError : i64 {            // raised with atomicMax (the highest code wins), decoded by device_error() on the host
+    // WfsScal::error
+    WFS_DEV_WINDOW = 1,             // digitise window of 10^6 samples or more; tile buffers of one instruction beyond 2^31 samples
+    WFS_DEV_TIME_RANGE = 2,         // a photon or electron time does not fit 32 bits relative to its origin
+    WFS_DEV_TILE_BUFFER = 3,        // internal: a tile of k_s2_tile did not fit its sample buffer
+    // WfsScal::opt_error (k_optical_bucket)
+    WFS_DEV_OPT_CHANNEL = 4,        // photon channel out of range
+    WFS_DEV_OPT_TIME = 5            // photon time beyond 2^31 ns
+};
+struct WfsScal {
+    i64 n_groups;           // digitise windows.  k_groups -> k_group_final, k_row_len, host
+    i64 error;              // WfsDevError.  generator, geometry and tile kernels -> host after the geometry (device_error)
+    i64 n_front_rows;       // rows of the accumulator path (k_zle / k_pack).  k_row_len -> host
+    i64 n_sparse_tiles;     // sparse work list.  tile_list_append -> host
+    i64 max_nb_sparse;      // most start bins of a sparse tile.  tile_list_append -> host (LDS of k_pulse_sparse)
+    i64 max_ph_sparse;      // most photons of a sparse tile.  tile_list_append -> host (LDS of k_pulse_sparse)
+    i64 n_block_photons;    // photons of the block generator.  scan of em_nph -> host
+    i64 n_tile_photons;     // photons in tile_off.  scan of tile_count -> host (wfs_load_optical)
+    i64 n_acc_samples;      // samples of the row accumulators.  scan of acc_len -> host
+    i64 n_itv_slots;        // reserved ZLE interval slots.  scan of itv_cap -> host
+    i64 n_records;          // records of the batch.  scan of row_nrec -> host
+    i64 n_dense_tiles;      // dense work list.  tile_list_append -> host
+    i64 max_nb_dense;       // most start bins of a dense tile.  tile_list_append -> host (variant of k_pulse)
+    i64 n_ap_candidates;    // PMT afterpulse candidates in the list (ApArgs::count).  ap_park, k_photon_fill, k_s2_tile -> afterpulse kernels, host (capacity check)
+    i64 n_ap_photons;       // accepted afterpulse photons.  scan of the afterpulse tiles' tile_count -> host
+    i64 max_ph_dense;       // most photons of a dense tile.  tile_list_append -> host (variant of k_pulse)
+    i64 n_tiny_tiles;       // tiny work list.  tile_list_append -> host
+    i64 n_wave_tiles;       // wave (medium) work list.  tile_list_append -> host
+    i64 opt_error;          // WfsDevError of the optical input.  k_optical_bucket -> wfs_load_optical (between its own memset and read_scal)
+    i64 n_order_huge;       // generation-order ranges beyond TILE_ORDER_MAX photons.  k_tile_order_scan -> host
+    i64 n_intervals;        // ZLE intervals of the batch.  k_counts -> wfs_get_counts
+    i64 n_pe;               // PE of the primary pulse sets.  k_counts -> wfs_get_counts
+    i64 key_origin;         // first sample of the batch, origin of the record sort keys.  host fill, k_row_desc -> k_rec_keys, host
+    i64 n_tbuf_samples;     // samples of all tile buffers.  scan of ins_bcap_all -> host
+    i64 n_tilegen_photons;  // photons of the tile-generated instructions.  k_tile_counts -> host
+    i64 n_full_tiles;       // tiles of k_s2_tile<FULL>, listed from the front of FuseArgs::tiles.  k_tile_counts -> host
+    i64 n_direct_samples;   // samples of the rows read from a tile buffer in place.  k_row_len -> host
+    i64 n_shared_rows;      // rows that several tiles of k_s2_tile share (k_tile_add is needed).  k_row_len -> host
+    i64 n_gen_tiles;        // generation-only tiles, listed from the back of FuseArgs::tiles.  k_tile_counts -> host
+    i64 key_end;            // end of the last row of the batch, span of the record sort keys.  host fill, k_row_desc -> host
+    i64 n_order_wave;       // generation-order ranges on the wave list.  k_tile_order_scan -> host
+    i64 n_order_big;        // generation-order ranges on the workgroup list.  k_tile_order_scan -> host
+    i64 n_short_rows;       // resident rows of at most RES_SHORT_LEN samples.  k_row_len -> host
+    i64 max_res_len;        // longest resident row.  k_row_len -> host (LDS of k_row_pulse)
+    i64 n_fin_samples;      // finished int16 samples of the resident rows.  scan of fin_len -> host
+    i64 n_res_tiles;        // tiles of the resident rows.  scan of res_cnt -> host
+    i64 n_res_samples;      // samples of the resident rows.  k_row_len -> host (wfs_get_counts)
+    i64 n_long_rows;        // resident rows longer than RES_SHORT_LEN.  k_row_len -> host
+    i64 reserved_[26];
+};
+static_assert(sizeof(WfsScal) == 512, "WfsScal: 64 slots of 8 bytes");
+#define WFS_SCAL_SLOT(m, slot) static_assert(offsetof(WfsScal, m) == 8 * (slot), "WfsScal::" #m " moved: the layout is frozen")
+WFS_SCAL_SLOT(error, 1); WFS_SCAL_SLOT(n_front_rows, 2); WFS_SCAL_SLOT(n_sparse_tiles, 3); WFS_SCAL_SLOT(n_dense_tiles, 11);
+WFS_SCAL_SLOT(n_tiny_tiles, 16); WFS_SCAL_SLOT(n_wave_tiles, 17); WFS_SCAL_SLOT(key_origin, 22); WFS_SCAL_SLOT(key_end, 29);
+WFS_SCAL_SLOT(n_ap_candidates, 13); WFS_SCAL_SLOT(n_order_huge, 19); WFS_SCAL_SLOT(n_long_rows, 37);
+#undef WFS_SCAL_SLOT
 
 // Everything a kernel needs, passed by value (fits the kernarg segment).
 struct WfsDev {

@@ -28,10 +28,10 @@
 
 #include <algorithm>
 #include <cstdio>
-#include <cstring>
 #include <cstdlib>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -47,6 +47,15 @@ struct ApElem { int n_bins_delay = 0, n_bins_amp = 0, amp_2d = 0, is_uniform = 0
                 int delay_sorted = 0, amp_sorted = 0; };
 
 struct KernelTime { std::string name; hipEvent_t a, b; };
+
+// bits of wfs_set_debug (wfs_handle::keep_currents); include/wfsim_amd.h documents them by number
+enum : int {
+    DBG_CURRENTS = 1,            // keep the f64 tile currents and the finished rows
+    DBG_FORCE_DENSE = 2,         // every tile to the dense pulse kernel
+    DBG_GEN_ONLY = 4,            // wfs_run stops after the photon generation
+    DBG_CHECK_LAUNCHES = 8,      // check every kernel launch on the spot
+    DBG_KEEP_PHOTONS = 16        // store the photons of tile-generated instructions
+};
 
 }  // namespace
 
@@ -90,7 +99,7 @@ struct wfs_handle {
     // host mirrors
     std::vector<i64> h_set_off;       // injected photons: per set photon offsets (channel sorted input order)
     wfs_counts counts{};
-    i64 *h_scal = nullptr;            // [64] host copy of scal in page-locked memory: read_scal's copy needs no staging buffer (five of them per batch)
+    WfsScal *h_scal = nullptr;        // host copy of scal in page-locked memory: read_scal's copy needs no staging buffer (five of them per batch)
     DevBuf pack_desc;
     DevBuf row_bad, fin_len, res_cnt, fin_off, res_toff, res_desc, fin, res_long, res_rows;      // resident rows (k_row_pulse)
     i64 n_front_rows = 0, n_res_rows = 0, n_short_rows = 0, n_res_tiles = 0, max_res_len = 0, s_fin = 0, s_res = 0; bool res_on = false;
@@ -193,7 +202,7 @@ struct Timer {
     ~Timer()
     {
         if (on) hipEventRecord(h->times.back().b, h->stream);
-        if (h->keep_currents & 8) {
+        if (h->keep_currents & DBG_CHECK_LAUNCHES) {
             hipError_t e = hipGetLastError();
             if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
             if (e != hipSuccess && h->launch_err.empty()) { try { h->launch_err = std::string(name) + ": " + hipGetErrorString(e); } catch (...) {} }
@@ -218,21 +227,21 @@ int fill32(wfs_handle *h, DevBuf &b, i64 n, i32 v)
     return WFS_OK;
 }
 
-// exclusive scan i32[n] -> i64[n+1]; total written to scal[slot]
-int scan_into(wfs_handle *h, const i32 *in, i64 n, i64 *outp, int scal_slot, i64 offset);
+// exclusive scan i32[n] -> i64[n+1]; total written to the member `total` of the device scalar block
+int scan_into(wfs_handle *h, const i32 *in, i64 n, i64 *outp, i64 WfsScal::*total_member, i64 offset);
 
-int scan(wfs_handle *h, const i32 *in, i64 n, DevBuf &out, int scal_slot)
+int scan(wfs_handle *h, const i32 *in, i64 n, DevBuf &out, i64 WfsScal::*total_member)
 {
     TRY(ensure(h, out, (size_t)(n + 1) * 8));
-    return scan_into(h, in, n, out.as<i64>(), scal_slot, 0);
+    return scan_into(h, in, n, out.as<i64>(), total_member, 0);
 }
 
 // exclusive scan into a caller-provided range, every output shifted by offset
-int scan_into(wfs_handle *h, const i32 *in, i64 n, i64 *outp, int scal_slot, i64 offset)
+int scan_into(wfs_handle *h, const i32 *in, i64 n, i64 *outp, i64 WfsScal::*total_member, i64 offset)
 {
     i64 nb = (n + SCAN_TILE - 1) / SCAN_TILE; if (nb < 1) nb = 1;
     TRY(ensure(h, h->scan_tmp, (size_t)nb * 8));
-    i64 *total = h->scal.as<i64>() + scal_slot;
+    i64 *total = &(h->scal.as<WfsScal>()->*total_member);       // (a device address: computed, never dereferenced here)
     if (n == 0) { h->zero64 = offset; HIPCHK(hipMemcpyAsync(outp, &h->zero64, 8, hipMemcpyHostToDevice, h->stream)); HIPCHK(hipMemsetAsync(total, 0, 8, h->stream)); return WFS_OK; }
     { Timer t(h, "k_scan_reduce"); hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)nb), dim3(SCAN_TPB), 0, h->stream, in, n, h->scan_tmp.as<i64>()); }
     { Timer t(h, "k_scan_spine"); hipLaunchKernelGGL(k_scan_spine, dim3(1), dim3(1024), 0, h->stream, h->scan_tmp.as<i64>(), nb, total); }
@@ -242,10 +251,30 @@ int scan_into(wfs_handle *h, const i32 *in, i64 n, i64 *outp, int scal_slot, i64
 
 int read_scal(wfs_handle *h)
 {
-    HIPCHK(hipMemcpyAsync(h->h_scal, h->scal.p, 512, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->h_scal, h->scal.p, sizeof(WfsScal), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (!h->launch_err.empty()) { const std::string m = h->launch_err; h->launch_err.clear(); return h->fail(WFS_E_HIP, m); }     // (wfs_set_debug bit 3)
     return WFS_OK;
+}
+
+// The row kernels take the kind of noise table as a template parameter (no branch between their loads): 0 none, 1 int16, 2 float.
+// f is called with a std::integral_constant of the kind.
+template <class F> void with_noise_kind(int kind, F &&f)
+{
+    if (kind == 0) f(std::integral_constant<int, 0>{}); else if (kind == 1) f(std::integral_constant<int, 1>{}); else f(std::integral_constant<int, 2>{});
+}
+
+// a code that kernels raised in the device scalar block (WfsDevError) -> error code and message of the C ABI
+int device_error(wfs_handle *h, i64 code)
+{
+    switch (code) {
+    case WFS_DEV_WINDOW: return h->fail(WFS_E_CAPACITY, "Pulse cache too long (digitise window of 10^6 samples or more, rawdata.py:219)");
+    case WFS_DEV_TIME_RANGE: return h->fail(WFS_E_CAPACITY, "photon time further than 2^31 ns from its instruction");
+    case WFS_DEV_TILE_BUFFER: return h->fail(WFS_E_STATE, "internal: a tile of k_s2_tile did not fit its sample buffer");
+    case WFS_DEV_OPT_CHANNEL: return h->fail(WFS_E_INVALID, "photon channel out of range");
+    case WFS_DEV_OPT_TIME: return h->fail(WFS_E_CAPACITY, "photon time beyond 2^31 ns");
+    default: return WFS_OK;
+    }
 }
 
 // cum[i] = P(trunc(Y) <= vmin + i) for Y ~ N(mu, sigma) (trunc = C cast, toward zero)
@@ -451,10 +480,10 @@ try {
     h->own_stream = true;
     if (hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&h->rec_copied[0], hipEventDisableTiming) != hipSuccess
         || hipEventCreateWithFlags(&h->rec_copied[1], hipEventDisableTiming) != hipSuccess) { delete h; return WFS_E_HIP; }
-    if (hipMalloc(&h->scal.p, 512) != hipSuccess) { delete h; return WFS_E_HIP; }
-    if (hipHostMalloc((void **)&h->h_scal, 512, hipHostMallocDefault) != hipSuccess) { hipFree(h->scal.p); delete h; return WFS_E_HIP; }
-    memset(h->h_scal, 0, 512);
-    h->scal.cap = 256;
+    if (hipMalloc(&h->scal.p, sizeof(WfsScal)) != hipSuccess) { delete h; return WFS_E_HIP; }
+    if (hipHostMalloc((void **)&h->h_scal, sizeof(WfsScal), hipHostMallocDefault) != hipSuccess) { hipFree(h->scal.p); delete h; return WFS_E_HIP; }
+    memset(h->h_scal, 0, sizeof(WfsScal));
+    h->scal.cap = sizeof(WfsScal);
 #ifdef WFS_STAMPS
     if (hipMalloc(&h->stamps.p, 4096 * 64 * 8) != hipSuccess) { delete h; return WFS_E_HIP; }
     h->stamps.cap = 4096 * 64 * 8; hipMemset(h->stamps.p, 0, 4096 * 64 * 8); h->dev.stamps = h->stamps.as<unsigned long long>();
@@ -1234,17 +1263,16 @@ try {
     TRY(ensure(h, h->tile_count, (size_t)T * 4)); TRY(ensure(h, h->tile_cursor, (size_t)T * 4)); TRY(ensure(h, h->tile_off, (size_t)(T + 1) * 8));
     TRY(ensure(h, h->opt_t, (size_t)n_ph * 4)); TRY(ensure(h, h->opt_item, (size_t)n_ph * 4));
     HIPCHK(hipMemsetAsync(h->tile_count.p, 0, (size_t)T * 4, h->stream)); HIPCHK(hipMemsetAsync(h->tile_cursor.p, 0, (size_t)T * 4, h->stream));
-    HIPCHK(hipMemsetAsync(h->scal.p, 0, 512, h->stream));
+    HIPCHK(hipMemsetAsync(h->scal.p, 0, sizeof(WfsScal), h->stream));
     OptLoadArgs oa{n, h->opt_first.as<i32>(), h->opt_last.as<i32>(), h->opt_ch.as<i32>(), h->opt_time.as<i64>(), cutoff, h->t_gains.as<double>(),
-                   h->tile_count.as<i32>(), h->tile_off.as<i64>(), h->tile_cursor.as<i32>(), h->opt_t.as<i32>(), h->opt_item.as<u32>(), h->scal.as<i64>()};
+                   h->tile_count.as<i32>(), h->tile_off.as<i64>(), h->tile_cursor.as<i32>(), h->opt_t.as<i32>(), h->opt_item.as<u32>(), h->scal.as<WfsScal>()};
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_optical_bucket<false>), dim3(nblocks(n, 256)), dim3(256), 0, h->stream, h->dev, oa);
-    TRY(scan_into(h, h->tile_count.as<i32>(), T, h->tile_off.as<i64>(), 7, 0));
+    TRY(scan_into(h, h->tile_count.as<i32>(), T, h->tile_off.as<i64>(), &WfsScal::n_tile_photons, 0));
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_optical_bucket<true>), dim3(nblocks(n, 256)), dim3(256), 0, h->stream, h->dev, oa);
     TRY(read_scal(h));
     HIPCHK(hipGetLastError());
-    if (h->h_scal[20] == 1) return h->fail(WFS_E_INVALID, "photon channel out of range");
-    if (h->h_scal[20] == 2) return h->fail(WFS_E_CAPACITY, "photon time beyond 2^31 ns");
-    const i64 P = h->h_scal[7];
+    TRY(device_error(h, h->h_scal->opt_error));
+    const i64 P = h->h_scal->n_tile_photons;
     h->n_photons = P;
     TRY(ensure(h, h->ph, (size_t)P * 8));
     TRY(ensure(h, h->tile_tmin, (size_t)h->n_tiles * 4)); TRY(ensure(h, h->tile_tmax, (size_t)h->n_tiles * 4));
@@ -1257,23 +1285,45 @@ try {
 } WFS_CATCH(h)
 
 // ---------------------------------------------------------------------------------------------- run
-static int run_generation(wfs_handle *h)
+// the batch came through wfs_load_instructions: its photons are made on the device (run_generation)
+static bool from_generator(const wfs_handle *h) { return !h->injected && !h->optical; }
+// pulses made by k_s2_tile<FULL> (wfs_tilegen.h): their tiles are on no work list
+static bool tiles_made(const wfs_handle *h) { return from_generator(h) && h->fuse_full && h->n_fused_tiles > 0; }
+// ph_gain holds the photons with an explicit gain only: every photon of an injected batch, or the PMT afterpulses, which follow the
+// n_photons primary ones; the kernels index it by photon number
+static const double *ph_gain_base(const wfs_handle *h) { return (!h->injected && h->ap_active) ? h->ph_gain.as<double>() - h->n_photons : h->ph_gain.as<double>(); }
+// the templates as the pulse kernels take them by value: t[tap * dt + ns remainder]
+static TemplateArg fill_template_arg(const wfs_handle *h)
+{
+    TemplateArg tp;
+    for (int k = 0; k < 22; k++) for (int r = 0; r < WFS_DT; r++) tp.t[k * WFS_DT + r] = h->h_templates[(size_t)r * 22 + k];
+    return tp;
+}
+// What crosses the stage boundaries of one run_generation (on its stack).
+struct GenRun {
+    GenArgs g{}; FuseArgs f{}; ApArgs ap{};
+    bool ext = false, ap_on = false;      // timing-model variants per instruction; PMT afterpulses
+    i64 TP = 0, P = 0, ap_cap = 0;        // primary tiles (afterpulse tiles follow); photons of the block generator; capacity of the afterpulse lists
+};
+
+// ---- generation 1: electrons, and which tiles make their own photons
+static int gen_electrons(wfs_handle *h, GenRun &r)
 {
     const WfsDev &d = h->dev;
+    GenArgs &g = r.g; FuseArgs &f = r.f;
     const i64 N = h->n_ins, E = h->n_emitters, T = h->n_tiles;
     TRY(ensure(h, h->em_time, (size_t)E * 8)); TRY(ensure(h, h->em_nph, (size_t)E * 4)); TRY(ensure(h, h->em_ins, (size_t)E * 4));
     TRY(ensure(h, h->el_stat, (size_t)N * 32)); TRY(ensure(h, h->el_minmax, (size_t)N * 16));
     HIPCHK(hipMemsetAsync(h->el_stat.p, 0, (size_t)N * 32, h->stream));
     hipLaunchKernelGGL(k_fill_minmax, dim3(nblocks(2 * N, 256)), dim3(256), 0, h->stream, h->el_minmax.as<i64>(), 2 * N);      // (min, max) pairs: (I64_MAX, I64_MIN)
-    GenArgs g{};
     g.n_ins = N; g.n_psets = h->n_psets; g.n_emitters = E;
     g.ins_embase = h->ins_embase.as<u32>(); g.ins_set = h->ins_set.as<i32>(); g.set_ins_off = h->set_ins_off.as<i64>(); g.set_ins_list = h->set_ins_list.as<i32>(); g.set_t0 = h->set_t0.as<i64>();
     g.ins_type = h->ins_type.as<int8_t>(); g.ins_time = h->ins_time.as<i64>(); g.ins_amp = h->ins_amp.as<i32>(); g.ins_gid = h->ins_gid.as<u32>();
     g.ins_p = h->ins_p.as<double>(); g.ins_dm = h->ins_dm.as<double>(); g.ins_ds = h->ins_ds.as<double>(); g.ins_sc = h->ins_sc.as<double>();
     g.ins_cdfrow = h->ins_cdfrow.as<i32>(); g.cdf_table = h->cdf_table.as<double>(); g.cdf_guide = h->cdf_guide.as<unsigned short>(); g.em_off = h->em_off.as<i64>();
     g.em_time = h->em_time.as<i64>(); g.em_nph = h->em_nph.as<i32>(); g.em_ins = h->em_ins.as<i32>();
-    g.el_stat = h->el_stat.as<double>(); g.el_minmax = h->el_minmax.as<i64>(); g.scal = h->scal.as<i64>();
-    const bool ext = h->ins_models;
+    g.el_stat = h->el_stat.as<double>(); g.el_minmax = h->el_minmax.as<i64>(); g.scal = h->scal.as<WfsScal>();
+    const bool ext = r.ext = h->ins_models;
     if (ext) {
         g.tabs = h->d_tabs.as<AliasTab>(); g.ins_tab = h->ins_tab.as<i32>(); g.ins_tabb = h->ins_tabb.as<i32>();
         g.ins_pzi = h->ins_pzi.as<i32>(); g.ins_pzf = h->ins_pzf.as<double>();
@@ -1286,12 +1336,10 @@ static int run_generation(wfs_handle *h)
     TRY(ensure(h, h->em_zg, (size_t)E * 8)); HIPCHK(hipMemsetAsync(h->em_zg.p, 0xff, (size_t)E * 8, h->stream)); g.em_zg = h->em_zg.as<double>();
     // tile-local generation (wfs_tilegen.h): which instructions take it is decided before the electrons are drawn -- theirs get no
     // photon numbers.  Debug modes that need the per-photon arrays (currents, generation only) run the generation half alone.
-    const bool ap_cfg = h->ap_active;
+    // (PMT afterpulses of tile-generated photons are screened inside k_s2_tile)
     h->fuse_on = h->cfg.tile_gen && !h->generic_geom && h->any_s2 && d.gain_spread == 0.0 && (!h->run_sets_given || h->sets_aligned) && h->n_diff_rows == 0;
-    (void)ap_cfg;                                // (PMT afterpulses of tile-generated photons are screened inside k_s2_tile)
-    h->fuse_full = h->fuse_on && !(h->keep_currents & 5);
+    h->fuse_full = h->fuse_on && !(h->keep_currents & (DBG_CURRENTS | DBG_GEN_ONLY));
     h->n_fused_tiles = 0; h->n_gen_tiles = 0; h->p_fused = 0;
-    FuseArgs f{};
     if (h->fuse_on) {
         f.lam_min = h->cfg.tile_gen_min; f.n_ins = N; f.nch = d.n_tpc; f.table_span = (i32)(1u << (32 - d.tab_s2.shift));
         f.set_ins_off = h->run_sets_given ? h->set_ins_off.as<i64>() : nullptr;
@@ -1343,7 +1391,7 @@ static int run_generation(wfs_handle *h)
         m.pre = h->diff_pre.as<double>();
         { Timer t(h, "k_map_rows"); hipLaunchKernelGGL(k_map_rows, dim3((unsigned)nr), dim3(256), (size_t)d.n_tpc * 8, h->stream, m, d.n_tpc); }
     }
-    const i64 TP = h->n_psets * d.n_tpc;        // primary tiles; afterpulse tiles follow
+    const i64 TP = r.TP = h->n_psets * d.n_tpc;
     TRY(ensure(h, h->tile_count, (size_t)T * 4)); TRY(ensure(h, h->tile_cursor, (size_t)T * 4));
     HIPCHK(hipMemsetAsync(h->tile_count.p, 0, (size_t)T * 4, h->stream)); HIPCHK(hipMemsetAsync(h->tile_cursor.p, 0, (size_t)T * 4, h->stream));
     TRY(fill32(h, h->tile_tmin, T, 0x7fffffff)); TRY(fill32(h, h->tile_tmax, T, (i32)0x80000000));
@@ -1351,26 +1399,36 @@ static int run_generation(wfs_handle *h)
     if (h->fuse_on) {
         // surviving electrons compacted per instruction, tile buffers sized from their time range, photons per tile (Poisson)
         { Timer t(h, "k_fuse_electrons"); hipLaunchKernelGGL(k_fuse_electrons, dim3((unsigned)N), dim3(256), 0, h->stream, d, f); }
-        TRY(scan(h, h->ins_bcap_all.as<i32>(), N, h->ins_boff, 23));
+        TRY(scan(h, h->ins_bcap_all.as<i32>(), N, h->ins_boff, &WfsScal::n_tbuf_samples));
         TRY(ensure(h, h->ftiles, (size_t)TP * sizeof(FTile))); TRY(ensure(h, h->tile_done, (size_t)TP * 4));
         f.ins_boff = h->ins_boff.as<i64>(); f.tile_count = h->tile_count.as<i32>(); f.tiles = h->ftiles.as<FTile>();
         f.tile_done = h->tile_done.as<i32>(); f.full = h->fuse_full ? 1 : 0; f.n_list = TP;
         { Timer t(h, "k_tile_counts"); hipLaunchKernelGGL(k_tile_counts, dim3(nblocks(TP, 256)), dim3(256), 0, h->stream, d, f); }
     }
-    TRY(scan(h, h->em_nph.as<i32>(), E, h->em_ph_off, 6));
+    TRY(scan(h, h->em_nph.as<i32>(), E, h->em_ph_off, &WfsScal::n_block_photons));
     TRY(read_scal(h));
-    const i64 P = h->h_scal[6];                 // photons of the block generator; the tiles' own photons come on top
-    if (h->fuse_on) { h->p_fused = h->h_scal[24]; h->n_fused_tiles = h->h_scal[25]; h->n_gen_tiles = h->h_scal[28]; }
-    h->n_photons = P + h->p_fused; h->n_ap_photons = 0;
+    const WfsScal &sc = *h->h_scal;
+    r.P = sc.n_block_photons;                   // the tiles' own photons come on top
+    if (h->fuse_on) { h->p_fused = sc.n_tilegen_photons; h->n_fused_tiles = sc.n_full_tiles; h->n_gen_tiles = sc.n_gen_tiles; }
+    h->n_photons = r.P + h->p_fused; h->n_ap_photons = 0;
+    return WFS_OK;
+}
+
+// ---- generation 2: the photons of the block generator, bucketed by tile
+static int gen_block_photons(wfs_handle *h, GenRun &r)
+{
+    const WfsDev &d = h->dev;
+    GenArgs &g = r.g; ApArgs &ap = r.ap;
+    const i64 N = h->n_ins, P = r.P, TP = r.TP;
+    const bool ext = r.ext;
     g.em_ph_off = h->em_ph_off.as<i64>(); g.n_photons = P;
-    const bool ap_on = h->ap_active;
-    const i64 ap_cap = ap_on ? (P + h->p_fused) / 8 + 65536 : 0;
+    const bool ap_on = r.ap_on = h->ap_active;
+    const i64 ap_cap = r.ap_cap = ap_on ? (P + h->p_fused) / 8 + 65536 : 0;
     TRY(ensure(h, h->ph, (size_t)(P + h->p_fused + ap_cap) * 8));
     TRY(ensure(h, h->ph_idx, (size_t)(P + h->p_fused + ap_cap) * 4)); g.ph_idx = h->ph_idx.as<u32>();
     g.tile_count = h->tile_count.as<i32>(); g.tile_cursor = h->tile_cursor.as<i32>(); g.tile_tmin = h->tile_tmin.as<i32>();
     g.tile_tmax = h->tile_tmax.as<i32>(); g.ph = h->ph.as<PhotonRec>();
     g.tile_off = h->tile_off.as<i64>();
-    ApArgs ap{};
     if (ap_on) {
         ap.n = d.n_ap;
         for (int e = 0; e < d.n_ap; e++) {
@@ -1392,7 +1450,7 @@ static int run_generation(wfs_handle *h)
         TRY(ensure(h, h->ap_gain, (size_t)ap_cap * 8)); TRY(ensure(h, h->ph_gain, (size_t)ap_cap * 8)); TRY(ensure(h, h->ap_key, (size_t)ap_cap * 4));
         ap.ap_key = h->ap_key.as<u32>();
         ap.cap = ap_cap; ap.ap_ins = h->ap_ins.as<i32>(); ap.ap_ch = h->ap_ch.as<i32>(); ap.ap_t = h->ap_t.as<i32>(); ap.ap_gain = h->ap_gain.as<double>();
-        ap.count = h->scal.as<i64>() + 13;
+        ap.count = &h->scal.as<WfsScal>()->n_ap_candidates;
         TRY(ensure(h, h->ap_cand, (size_t)ap_cap * sizeof(ApCand))); ap.cand = h->ap_cand.as<ApCand>();
     }
     TRY(ensure(h, h->ins_ph0, (size_t)(N + 1) * 8)); g.ins_ph0 = h->ins_ph0.as<i64>();
@@ -1424,7 +1482,7 @@ static int run_generation(wfs_handle *h)
         if (g.gg_inv) { Timer t(h, "k_gg_sum"); hipLaunchKernelGGL(k_gg_sum, dim3(nb), dim3(256), 0, h->stream, d, g); }
         { Timer t(h, "k_photon_count"); hipLaunchKernelGGL(k_photon_count, dim3(nbx), dim3(COUNT_TPB), GEN_COUNT_LDS(d.n_tpc, g.ch_lg), h->stream, d, g); }
         { Timer t(h, "k_block_ranges"); hipLaunchKernelGGL(k_block_ranges, dim3(nblocks(TP, 256)), dim3(256), 0, h->stream, d, g); }
-        TRY(scan_into(h, h->tile_count.as<i32>(), TP, h->tile_off.as<i64>(), 7, 0));
+        TRY(scan_into(h, h->tile_count.as<i32>(), TP, h->tile_off.as<i64>(), &WfsScal::n_tile_photons, 0));
         const size_t gen_lds = (size_t)gen_fill_lds(d.n_tpc, g.ch_lg, ap_on).total;
         { Timer t(h, "k_photon_fill");
           if (ext && ap_on) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_photon_fill<true, true>), dim3(nbx), dim3(FILL_TPB), gen_lds, h->stream, d, g, ap);
@@ -1432,19 +1490,27 @@ static int run_generation(wfs_handle *h)
           else if (ap_on) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_photon_fill<true, false>), dim3(nbx), dim3(FILL_TPB), gen_lds, h->stream, d, g, ap);
           else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_photon_fill<false, false>), dim3(nbx), dim3(FILL_TPB), gen_lds, h->stream, d, g, ap); }
     } else {
-        TRY(scan_into(h, h->tile_count.as<i32>(), TP, h->tile_off.as<i64>(), 7, 0));
+        TRY(scan_into(h, h->tile_count.as<i32>(), TP, h->tile_off.as<i64>(), &WfsScal::n_tile_photons, 0));
     }
+    return WFS_OK;
+}
+
+// ---- generation 3: the tiles that make their own photons (k_s2_tile) -- before the geometry: the tile time ranges come out of this kernel
+static int gen_tile_photons(wfs_handle *h, GenRun &r)
+{
+    const WfsDev &d = h->dev;
+    FuseArgs &f = r.f; ApArgs &ap = r.ap;
+    const i64 T = h->n_tiles, TP = r.TP;
+    const bool ap_on = r.ap_on;
     // (photon counts only -- wfs_set_debug bit 2 without bit 4, the electron-afterpulse pre-pass: the tiles' photon numbers are drawn
     // (k_tile_counts) and single photons are recomputed on request (wfs_gather_photon_times); no photon of a tile is generated)
-    const bool counts_only = (h->keep_currents & 4) && !(h->keep_currents & 16);
+    const bool counts_only = (h->keep_currents & DBG_GEN_ONLY) && !(h->keep_currents & DBG_KEEP_PHOTONS);
     if (h->fuse_on && h->n_fused_tiles + h->n_gen_tiles > 0 && !counts_only) {
-        // the tiles' photons and pulses (before the geometry: the tile time ranges come out of this kernel)
-        TRY(ensure(h, h->tbuf, (size_t)h->h_scal[23] * 4 + 64));
+        TRY(ensure(h, h->tbuf, (size_t)h->h_scal->n_tbuf_samples * 4 + 64));
         TRY(ensure(h, h->tile_truth, (size_t)T * 8 * 8));
         f.tile_off = h->tile_off.as<i64>(); f.tile_tmin = h->tile_tmin.as<i32>(); f.tile_tmax = h->tile_tmax.as<i32>(); f.tile_truth = h->tile_truth.as<double>();
-        f.tbuf = h->tbuf.as<i32>(); f.ph = h->ph.as<PhotonRec>(); f.keep_ph = (h->keep_currents & 16) ? 1 : 0;
-        TemplateArg tp;
-        for (int k = 0; k < 22; k++) for (int r = 0; r < WFS_DT; r++) tp.t[k * WFS_DT + r] = h->h_templates[r * 22 + k];
+        f.tbuf = h->tbuf.as<i32>(); f.ph = h->ph.as<PhotonRec>(); f.keep_ph = (h->keep_currents & DBG_KEEP_PHOTONS) ? 1 : 0;
+        const TemplateArg tp = fill_template_arg(h);
         // H table + the waves' counters; the exact form adds the tables of tap_block (the fused form gathers every sample densely)
         size_t lds = (size_t)(WFS_TILE_CHUNK + d.tlen - 1) * d.dt * 8 + 4 * 4 * 4 + (h->cfg.fma ? 16 : TAP_LDS_BYTES(256) + 64);
         lds = (lds + 15) / 16 * 16;
@@ -1454,7 +1520,7 @@ static int run_generation(wfs_handle *h)
             lds += (size_t)AP_STAGE * sizeof(ApCand);
             TRY(ensure(h, h->ap_seg, (size_t)(h->n_fused_tiles + h->n_gen_tiles) * sizeof(ApSeg))); ap.seg = h->ap_seg.as<ApSeg>(); ap.n_seg = h->n_fused_tiles + h->n_gen_tiles;
             f.n_ptiles = TP;
-            TRY(upload(h, h->ap_args_dev, &ap, sizeof ap)); app = h->ap_args_dev.as<ApArgs>();      // (`ap` outlives the copy: read_scal below)
+            TRY(upload(h, h->ap_args_dev, &ap, sizeof ap)); app = h->ap_args_dev.as<ApArgs>();      // (`ap` outlives the copy: read_scal of gen_afterpulses)
         }
         f.sparse_max = h->tap_sparse_max;
         // tiles of up to 2048 photons: photons and pulse in one workgroup (listed from the front); brighter ones -- and every tile in the
@@ -1473,89 +1539,119 @@ static int run_generation(wfs_handle *h)
         }
     }
     h->fuse_args = f;
-    if (ap_on) {
-        // afterpulse photons: count per tile of the afterpulse sets, offsets behind the primary photons, place
-        { Timer t(h, "k_ap_finish"); hipLaunchKernelGGL(k_ap_finish, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap); }
-        { Timer t(h, "k_ap_count"); hipLaunchKernelGGL(k_ap_count, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap);
-          if (ap.n_seg > 0) hipLaunchKernelGGL(k_ap_seg<false>, dim3(nblocks(ap.n_seg, 4)), dim3(256), 0, h->stream, d, g, ap, (double *)nullptr); }
-        TRY(scan_into(h, h->tile_count.as<i32>() + TP, TP, h->tile_off.as<i64>() + TP, 14, P + h->p_fused));      // (behind the slots of every primary tile, the tile-generated ones included)
-        { Timer t(h, "k_ap_place"); hipLaunchKernelGGL(k_ap_place, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap, h->ph_gain.as<double>() - (P + h->p_fused));
-          if (ap.n_seg > 0) hipLaunchKernelGGL(k_ap_seg<true>, dim3(nblocks(ap.n_seg, 4)), dim3(256), 0, h->stream, d, g, ap, h->ph_gain.as<double>() - (P + h->p_fused)); }
-        TRY(read_scal(h));
-        if (h->h_scal[13] > ap_cap) return h->fail(WFS_E_CAPACITY, "more PMT afterpulse photons than 1/8 of the primary photons: afterpulse probability unreasonably high");
-        h->n_ap_photons = h->h_scal[14];                             // (the accepted candidates: total of the afterpulse tiles' counts, the scan above)
-    }
-    if (P > 0 || ap_on) {
-        // every tile of the block generator into generation order (k_tile_order): the order the reference's Pulse call sees
-        TRY(ensure(h, h->order_list, (size_t)T * 2 * sizeof(OrderRange))); TRY(ensure(h, h->order_list2, (size_t)T * 2 * sizeof(OrderRange)));
-        OrderArgs oa{T, TP, h->tile_count.as<i32>(), h->tile_off.as<i64>(), h->ph.as<PhotonRec>(), h->ph_idx.as<u32>(),
-                     ap_on ? h->ph_gain.as<double>() : nullptr, P + h->p_fused, h->order_list.as<OrderRange>(), h->order_list2.as<OrderRange>(), h->scal.as<i64>(),
-                     (h->fuse_on && h->n_fused_tiles + h->n_gen_tiles > 0) ? h->ins_fused.as<i32>() : nullptr, d.n_tpc,
-                     h->tile_cursor.as<i32>(), h->tile_tailbase.as<i32>(), h->ins_fullsort.as<i32>(), h->set_ins_off.as<i64>(), h->set_ins_list.as<i32>()};
-        { Timer t(h, "k_tile_order_scan"); hipLaunchKernelGGL(k_tile_order_scan, dim3(nblocks(T, 256)), dim3(256), 0, h->stream, oa); }
-        TRY(read_scal(h));
-        const i64 n_wave = h->h_scal[30], n_big = h->h_scal[31];
-        if (n_wave > 0) { Timer t(h, "k_tile_order"); hipLaunchKernelGGL(k_tile_order, dim3(nblocks(n_wave, 4)), dim3(256), 0, h->stream, oa, n_wave); }
-        if (n_big > 0) {
-            Timer t(h, "k_tile_order_big");
-            hipLaunchKernelGGL(k_tile_order_big, dim3((unsigned)n_big), dim3(256), (size_t)TILE_ORDER_MAX * 24, h->stream, oa);
-        }
-        const i64 n_huge = h->h_scal[19];
-        if (n_huge > 0) {
-            // ranges beyond the workgroup sort: compact copies, one segmented radix sort over (order key, position), records to their ranks
-            std::vector<OrderRange> rg((size_t)n_huge);
-            HIPCHK(hipMemcpy(rg.data(), h->order_list2.as<OrderRange>() + (2 * T - n_huge), (size_t)n_huge * sizeof(OrderRange), hipMemcpyDeviceToHost));
-            std::sort(rg.begin(), rg.end(), [](const OrderRange &x, const OrderRange &y) { return x.start < y.start; });      // (appended with atomics: a fixed order for the offsets)
-            std::vector<i64> start((size_t)n_huge), cbeg((size_t)n_huge + 1, 0);
-            for (i64 k = 0; k < n_huge; k++) { start[(size_t)k] = rg[(size_t)k].start; cbeg[(size_t)k + 1] = cbeg[(size_t)k] + rg[(size_t)k].n; }
-            const i64 tot = cbeg[(size_t)n_huge];
-            if (tot > 0xffffffffLL) return h->fail(WFS_E_CAPACITY, "more than 2^32 photons in tiles beyond 4096 photons");
-            TRY(upload(h, h->huge_start, start.data(), start.size() * 8)); TRY(upload(h, h->huge_cbeg, cbeg.data(), cbeg.size() * 8));
-            TRY(ensure(h, h->huge_keys, (size_t)tot * 4)); TRY(ensure(h, h->huge_keys2, (size_t)tot * 4)); TRY(ensure(h, h->huge_vals, (size_t)tot * 4)); TRY(ensure(h, h->huge_vals2, (size_t)tot * 4));
-            TRY(ensure(h, h->huge_rec, (size_t)tot * 8)); TRY(ensure(h, h->huge_gain, (size_t)tot * 8));
-            HugeOrderArgs ha{n_huge, tot, h->huge_start.as<i64>(), h->huge_cbeg.as<i64>(), oa.ph, oa.ph_idx, oa.ph_gain, oa.gain_first,
-                             h->huge_keys.as<u32>(), h->huge_vals.as<u32>(), h->huge_rec.as<PhotonRec>(), h->huge_gain.as<double>()};
-            Timer t(h, "k_tile_order_huge");
-            hipLaunchKernelGGL(k_order_huge_pack, dim3(nblocks(tot, 256)), dim3(256), 0, h->stream, ha);
-            size_t bytes = 0;
-            HIPCHK(rocprim::segmented_radix_sort_pairs(nullptr, bytes, h->huge_keys.as<u32>(), h->huge_keys2.as<u32>(), h->huge_vals.as<u32>(), h->huge_vals2.as<u32>(),
-                                                       (unsigned)tot, (unsigned)n_huge, h->huge_cbeg.as<i64>(), h->huge_cbeg.as<i64>() + 1, 0u, 32u, h->stream));
-            TRY(ensure(h, h->sort_tmp, bytes));
-            HIPCHK(rocprim::segmented_radix_sort_pairs(h->sort_tmp.p, bytes, h->huge_keys.as<u32>(), h->huge_keys2.as<u32>(), h->huge_vals.as<u32>(), h->huge_vals2.as<u32>(),
-                                                       (unsigned)tot, (unsigned)n_huge, h->huge_cbeg.as<i64>(), h->huge_cbeg.as<i64>() + 1, 0u, 32u, h->stream));
-            hipLaunchKernelGGL(k_order_huge_apply, dim3(nblocks(tot, 256)), dim3(256), 0, h->stream, ha, h->huge_keys2.as<u32>(), h->huge_vals2.as<u32>(), h->ph.as<PhotonRec>(), h->ph_idx.as<u32>(),
-                               ap_on ? h->ph_gain.as<double>() : nullptr);
-        }
-    }
-    h->gen_args = g;
     return WFS_OK;
 }
 
-int wfs_run(wfs_handle *h)
-try {
-    if (!h) return WFS_E_INVALID;
-    if (!h->batch_loaded) return h->fail(WFS_E_STATE, "no batch loaded");
-    if (h->dev_rows_pending && !h->injected && !h->optical) return h->fail(WFS_E_STATE, "instructions with cdf_row -1: call wfs_eval_pattern_rows before wfs_run");
-    h->ran = false; h->gen_done = false; h->gen_order_ready = false;
-    HIPCHK(hipSetDevice(h->device));
-    for (auto &t : h->times) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
-    h->times.clear();
+// ---- generation 4: PMT afterpulse photons: count per tile of the afterpulse sets, offsets behind the primary photons, place
+static int gen_afterpulses(wfs_handle *h, GenRun &r)
+{
     const WfsDev &d = h->dev;
-    const i64 T = h->n_tiles, S = h->n_sets, C = h->n_clusters;
-    HIPCHK(hipMemsetAsync(h->scal.p, 0, 512, h->stream));
+    const GenArgs &g = r.g; const ApArgs &ap = r.ap;
+    const i64 P = r.P, TP = r.TP, ap_cap = r.ap_cap;
+    { Timer t(h, "k_ap_finish"); hipLaunchKernelGGL(k_ap_finish, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap); }
+    { Timer t(h, "k_ap_count"); hipLaunchKernelGGL(k_ap_count, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap);
+      if (ap.n_seg > 0) hipLaunchKernelGGL(k_ap_seg<false>, dim3(nblocks(ap.n_seg, 4)), dim3(256), 0, h->stream, d, g, ap, (double *)nullptr); }
+    TRY(scan_into(h, h->tile_count.as<i32>() + TP, TP, h->tile_off.as<i64>() + TP, &WfsScal::n_ap_photons, P + h->p_fused));      // (behind the slots of every primary tile, the tile-generated ones included)
+    { Timer t(h, "k_ap_place"); hipLaunchKernelGGL(k_ap_place, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap, h->ph_gain.as<double>() - (P + h->p_fused));
+      if (ap.n_seg > 0) hipLaunchKernelGGL(k_ap_seg<true>, dim3(nblocks(ap.n_seg, 4)), dim3(256), 0, h->stream, d, g, ap, h->ph_gain.as<double>() - (P + h->p_fused)); }
+    TRY(read_scal(h));
+    if (h->h_scal->n_ap_candidates > ap_cap) return h->fail(WFS_E_CAPACITY, "more PMT afterpulse photons than 1/8 of the primary photons: afterpulse probability unreasonably high");
+    h->n_ap_photons = h->h_scal->n_ap_photons;                   // (the accepted candidates: total of the afterpulse tiles' counts, the scan above)
+    return WFS_OK;
+}
+
+// ---- generation 5: every tile of the block generator into generation order (k_tile_order): the order the reference's Pulse call sees
+static int gen_order(wfs_handle *h, GenRun &r)
+{
+    const WfsDev &d = h->dev;
+    const i64 T = h->n_tiles, P = r.P, TP = r.TP;
+    const bool ap_on = r.ap_on;
+    TRY(ensure(h, h->order_list, (size_t)T * 2 * sizeof(OrderRange))); TRY(ensure(h, h->order_list2, (size_t)T * 2 * sizeof(OrderRange)));
+    OrderArgs oa{T, TP, h->tile_count.as<i32>(), h->tile_off.as<i64>(), h->ph.as<PhotonRec>(), h->ph_idx.as<u32>(),
+                 ap_on ? h->ph_gain.as<double>() : nullptr, P + h->p_fused, h->order_list.as<OrderRange>(), h->order_list2.as<OrderRange>(), h->scal.as<WfsScal>(),
+                 (h->fuse_on && h->n_fused_tiles + h->n_gen_tiles > 0) ? h->ins_fused.as<i32>() : nullptr, d.n_tpc,
+                 h->tile_cursor.as<i32>(), h->tile_tailbase.as<i32>(), h->ins_fullsort.as<i32>(), h->set_ins_off.as<i64>(), h->set_ins_list.as<i32>()};
+    { Timer t(h, "k_tile_order_scan"); hipLaunchKernelGGL(k_tile_order_scan, dim3(nblocks(T, 256)), dim3(256), 0, h->stream, oa); }
+    TRY(read_scal(h));
+    const i64 n_wave = h->h_scal->n_order_wave, n_big = h->h_scal->n_order_big;
+    if (n_wave > 0) { Timer t(h, "k_tile_order"); hipLaunchKernelGGL(k_tile_order, dim3(nblocks(n_wave, 4)), dim3(256), 0, h->stream, oa, n_wave); }
+    if (n_big > 0) {
+        Timer t(h, "k_tile_order_big");
+        hipLaunchKernelGGL(k_tile_order_big, dim3((unsigned)n_big), dim3(256), (size_t)TILE_ORDER_MAX * 24, h->stream, oa);
+    }
+    const i64 n_huge = h->h_scal->n_order_huge;
+    if (n_huge > 0) {
+        // ranges beyond the workgroup sort: compact copies, one segmented radix sort over (order key, position), records to their ranks
+        std::vector<OrderRange> rg((size_t)n_huge);
+        HIPCHK(hipMemcpy(rg.data(), h->order_list2.as<OrderRange>() + (2 * T - n_huge), (size_t)n_huge * sizeof(OrderRange), hipMemcpyDeviceToHost));
+        std::sort(rg.begin(), rg.end(), [](const OrderRange &x, const OrderRange &y) { return x.start < y.start; });      // (appended with atomics: a fixed order for the offsets)
+        std::vector<i64> start((size_t)n_huge), cbeg((size_t)n_huge + 1, 0);
+        for (i64 k = 0; k < n_huge; k++) { start[(size_t)k] = rg[(size_t)k].start; cbeg[(size_t)k + 1] = cbeg[(size_t)k] + rg[(size_t)k].n; }
+        const i64 tot = cbeg[(size_t)n_huge];
+        if (tot > 0xffffffffLL) return h->fail(WFS_E_CAPACITY, "more than 2^32 photons in tiles beyond 4096 photons");
+        TRY(upload(h, h->huge_start, start.data(), start.size() * 8)); TRY(upload(h, h->huge_cbeg, cbeg.data(), cbeg.size() * 8));
+        TRY(ensure(h, h->huge_keys, (size_t)tot * 4)); TRY(ensure(h, h->huge_keys2, (size_t)tot * 4)); TRY(ensure(h, h->huge_vals, (size_t)tot * 4)); TRY(ensure(h, h->huge_vals2, (size_t)tot * 4));
+        TRY(ensure(h, h->huge_rec, (size_t)tot * 8)); TRY(ensure(h, h->huge_gain, (size_t)tot * 8));
+        HugeOrderArgs ha{n_huge, tot, h->huge_start.as<i64>(), h->huge_cbeg.as<i64>(), oa.ph, oa.ph_idx, oa.ph_gain, oa.gain_first,
+                         h->huge_keys.as<u32>(), h->huge_vals.as<u32>(), h->huge_rec.as<PhotonRec>(), h->huge_gain.as<double>()};
+        Timer t(h, "k_tile_order_huge");
+        hipLaunchKernelGGL(k_order_huge_pack, dim3(nblocks(tot, 256)), dim3(256), 0, h->stream, ha);
+        size_t bytes = 0;
+        HIPCHK(rocprim::segmented_radix_sort_pairs(nullptr, bytes, h->huge_keys.as<u32>(), h->huge_keys2.as<u32>(), h->huge_vals.as<u32>(), h->huge_vals2.as<u32>(),
+                                                   (unsigned)tot, (unsigned)n_huge, h->huge_cbeg.as<i64>(), h->huge_cbeg.as<i64>() + 1, 0u, 32u, h->stream));
+        TRY(ensure(h, h->sort_tmp, bytes));
+        HIPCHK(rocprim::segmented_radix_sort_pairs(h->sort_tmp.p, bytes, h->huge_keys.as<u32>(), h->huge_keys2.as<u32>(), h->huge_vals.as<u32>(), h->huge_vals2.as<u32>(),
+                                                   (unsigned)tot, (unsigned)n_huge, h->huge_cbeg.as<i64>(), h->huge_cbeg.as<i64>() + 1, 0u, 32u, h->stream));
+        hipLaunchKernelGGL(k_order_huge_apply, dim3(nblocks(tot, 256)), dim3(256), 0, h->stream, ha, h->huge_keys2.as<u32>(), h->huge_vals2.as<u32>(), h->ph.as<PhotonRec>(), h->ph_idx.as<u32>(),
+                           ap_on ? h->ph_gain.as<double>() : nullptr);
+    }
+    return WFS_OK;
+}
+
+static int run_generation(wfs_handle *h)
+{
+    GenRun r;
+    TRY(gen_electrons(h, r));
+    TRY(gen_block_photons(h, r));
+    TRY(gen_tile_photons(h, r));
+    if (r.ap_on) TRY(gen_afterpulses(h, r));
+    if (r.P > 0 || r.ap_on) TRY(gen_order(h, r));
+    h->gen_args = r.g;
+    return WFS_OK;
+}
+
+// What crosses the stage boundaries of one wfs_run (on its stack).
+struct RunState {
+    GeomArgs ga{}; PulseArgs pa{}; ZleArgs za{};
+    bool tiles_done = false;                                // pulses made by k_s2_tile (wfs_tilegen.h)
+    i64 CG = 0, RS = 0;                                     // group slots; row slots
+    i64 first_sparse = 0, first_dense = 0, first_wave = 0;  // the one work list: tiny tiles, then sparse, dense, wave
+    int noise_kind = 0;                                     // with_noise_kind
+};
+
+// ---- input: photons bucketed by tile, whichever way the batch was loaded
+static int run_input(wfs_handle *h)
+{
+    const WfsDev &d = h->dev;
+    const i64 T = h->n_tiles;
     if (h->optical) {
         OpticalArgs oa{T, h->tile_count.as<i32>(), h->tile_off.as<i64>(), h->tile_tmin.as<i32>(), h->tile_tmax.as<i32>(), h->set_gid.as<u32>(),
-                       h->opt_t.as<i32>(), h->opt_item.as<u32>(), h->ph.as<PhotonRec>(), h->scal.as<i64>()};
+                       h->opt_t.as<i32>(), h->opt_item.as<u32>(), h->ph.as<PhotonRec>(), h->scal.as<WfsScal>()};
         Timer t(h, "k_optical_finish");
         hipLaunchKernelGGL(k_optical_finish, dim3(nblocks(T, 256)), dim3(256), 0, h->stream, d, oa);
     }
     else if (!h->injected) TRY(run_generation(h));
-    else { h->ap_active = false; TRY(scan(h, h->tile_count.as<i32>(), T, h->tile_off, 7)); }
-    h->gen_done = true;
-    if (h->keep_currents & 4) { HIPCHK(hipStreamSynchronize(h->stream)); return WFS_OK; }      // wfs_set_debug bit 2: photon generation only
+    else { h->ap_active = false; TRY(scan(h, h->tile_count.as<i32>(), T, h->tile_off, &WfsScal::n_tile_photons)); }
+    return WFS_OK;
+}
 
-    // ---- geometry: tiles -> clusters -> groups -> rows
-    const i64 CG = C + 1;         // group slots
+// ---- geometry: tiles -> clusters -> groups -> rows; the counters of the batch come back and size everything that follows
+static int run_geometry(wfs_handle *h, RunState &r)
+{
+    const WfsDev &d = h->dev;
+    GeomArgs &ga = r.ga;
+    const i64 T = h->n_tiles, S = h->n_sets, C = h->n_clusters;
+    const i64 CG = r.CG = C + 1;
     TRY(fill64(h, h->cl_end, C, I64_MIN)); TRY(ensure(h, h->cl_group, (size_t)C * 4));
     TRY(fill64(h, h->grp_lo, CG, I64_MAX)); TRY(fill64(h, h->grp_hi, CG, I64_MIN));
     TRY(ensure(h, h->grp_left, (size_t)CG * 8)); TRY(ensure(h, h->grp_right, (size_t)CG * 8)); TRY(ensure(h, h->grp_ixrand, (size_t)CG * 8));
@@ -1564,26 +1660,25 @@ try {
     TRY(ensure(h, h->acc_len, (size_t)CG * d.n_tpc * 4)); HIPCHK(hipMemsetAsync(h->acc_len.p, 0, (size_t)CG * d.n_tpc * 4, h->stream));
     TRY(ensure(h, h->itv_cap, (size_t)CG * d.row_slots * 4)); TRY(ensure(h, h->active_rows, (size_t)CG * d.row_slots * 4));
     TRY(ensure(h, h->active_tiles, (size_t)T * 4)); TRY(ensure(h, h->sparse_tiles, (size_t)T * 4)); TRY(ensure(h, h->dense_tiles, (size_t)T * 4)); TRY(ensure(h, h->wave_tiles, (size_t)T * 4));
-    GeomArgs ga{};
     ga.n_sets = S; ga.n_tiles = T; ga.n_clusters = C; ga.n_gslots = CG;
     ga.tile_count = h->tile_count.as<i32>(); ga.tile_tmin = h->tile_tmin.as<i32>(); ga.tile_tmax = h->tile_tmax.as<i32>();
     ga.set_cluster = h->set_cluster.as<i32>(); ga.set_t0 = h->set_t0.as<i64>(); ga.cl_tmin = h->cl_tmin.as<i64>(); ga.cl_gid = h->cl_gid.as<u32>();
     ga.cl_end = h->cl_end.as<i64>(); ga.cl_group = h->cl_group.as<i32>(); ga.grp_lo = h->grp_lo.as<i64>(); ga.grp_hi = h->grp_hi.as<i64>();
     ga.grp_left = h->grp_left.as<i64>(); ga.grp_right = h->grp_right.as<i64>(); ga.grp_ixrand = h->grp_ixrand.as<i64>(); ga.grp_gid = h->grp_gid.as<u32>();
     ga.row_lo = h->row_lo.as<i64>(); ga.row_hi = h->row_hi.as<i64>(); ga.acc_len = h->acc_len.as<i32>(); ga.itv_cap = h->itv_cap.as<i32>();
-    ga.active_rows = h->active_rows.as<i32>(); ga.scal = h->scal.as<i64>(); ga.active_tiles = h->active_tiles.as<i32>(); ga.sparse_tiles = h->sparse_tiles.as<i32>(); ga.dense_tiles = h->dense_tiles.as<i32>(); ga.wave_tiles = h->wave_tiles.as<i32>(); ga.force_dense = ((h->keep_currents & 2) || h->generic_geom) ? 1 : 0; ga.init_has = h->carry_has; ga.init_runmax = h->carry_runmax;
+    ga.active_rows = h->active_rows.as<i32>(); ga.scal = h->scal.as<WfsScal>(); ga.active_tiles = h->active_tiles.as<i32>(); ga.sparse_tiles = h->sparse_tiles.as<i32>(); ga.dense_tiles = h->dense_tiles.as<i32>(); ga.wave_tiles = h->wave_tiles.as<i32>(); ga.force_dense = ((h->keep_currents & DBG_FORCE_DENSE) || h->generic_geom) ? 1 : 0; ga.init_has = h->carry_has; ga.init_runmax = h->carry_runmax;
     ga.noise_override = h->n_noise_override ? h->noise_override.as<i64>() : nullptr; ga.n_noise_override = h->n_noise_override;
-    const bool tiles_done = !h->injected && !h->optical && h->fuse_full && h->n_fused_tiles > 0;      // pulses made by k_s2_tile (wfs_tilegen.h)
+    const bool tiles_done = r.tiles_done = tiles_made(h);
     // resident rows (k_row_pulse): the usual digitiser geometry, a hold-off of at least a chunk and a noise table the fast row loads
     // can walk (as the fast path of k_zle), no HE rows, no debug copies of currents or rows
     // 2 (auto, the default): on when the batch holds at least two photons per (pulse set, channel) slot -- rows that collect several
     // pulses are where the accumulators cost (memset, atomics, two more reads); a batch of sparse S1 or nVeto hits is as fast through
     // them, and the resident path's extra pass over the tiles does not pay there
     // (photons in the photon array: the tiles k_s2_tile made in one go hold theirs in their sample buffers and can never be resident)
-    const i64 p_all = h->n_photons - ((!h->injected && !h->optical && h->fuse_full) ? h->p_fused : 0) + ((!h->injected && !h->optical && h->ap_active) ? h->n_ap_photons : 0);
+    const i64 p_all = h->n_photons - ((from_generator(h) && h->fuse_full) ? h->p_fused : 0) + ((from_generator(h) && h->ap_active) ? h->n_ap_photons : 0);
     const bool res_auto = T > 0 && p_all >= 2 * T;
     const int res_mode = h->res_env >= 0 ? h->res_env : h->cfg.row_resident;
-    h->res_on = (res_mode == 2 ? res_auto : res_mode != 0) && !(h->keep_currents & 3) && !h->generic_geom && !d.he_rows && 2 * (i64)d.tw + 1 >= 63
+    h->res_on = (res_mode == 2 ? res_auto : res_mode != 0) && !(h->keep_currents & (DBG_CURRENTS | DBG_FORCE_DENSE)) && !h->generic_geom && !d.he_rows && 2 * (i64)d.tw + 1 >= 63
                 && (!d.enable_noise || d.noise_len >= NOISE_MIN_FAST);
     if (tiles_done || h->res_on) {
         TRY(ensure(h, h->row_cnt, (size_t)CG * d.n_tpc * 4)); TRY(ensure(h, h->row_tile, (size_t)CG * d.n_tpc * 4));
@@ -1607,60 +1702,74 @@ try {
     { Timer t(h, "k_tile_rows"); hipLaunchKernelGGL(k_tile_rows, dim3(nblocks(T, 256)), dim3(256), 0, h->stream, d, ga); }
     { Timer t(h, "k_group_final"); hipLaunchKernelGGL(k_group_final, dim3(nblocks(CG, 256)), dim3(256), 0, h->stream, d, ga); }
     { Timer t(h, "k_row_len"); hipLaunchKernelGGL(k_row_len, dim3(nblocks(CG * d.row_slots, 1024)), dim3(1024), 0, h->stream, d, ga); }
-    TRY(scan(h, h->acc_len.as<i32>(), CG * d.n_tpc, h->acc_off, 8));
-    TRY(scan(h, h->itv_cap.as<i32>(), CG * d.row_slots, h->itv_off, 9));
+    TRY(scan(h, h->acc_len.as<i32>(), CG * d.n_tpc, h->acc_off, &WfsScal::n_acc_samples));
+    TRY(scan(h, h->itv_cap.as<i32>(), CG * d.row_slots, h->itv_off, &WfsScal::n_itv_slots));
     if (h->res_on) {
-        TRY(scan(h, h->fin_len.as<i32>(), CG * d.n_tpc, h->fin_off, 34)); TRY(scan(h, h->res_cnt.as<i32>(), CG * d.n_tpc, h->res_toff, 35));
-        // rows are known: tiles onto their row's list or the work list of their class (descriptor slots for every tile: no host
-        // round trip for the number of resident ones)
+        TRY(scan(h, h->fin_len.as<i32>(), CG * d.n_tpc, h->fin_off, &WfsScal::n_fin_samples)); TRY(scan(h, h->res_cnt.as<i32>(), CG * d.n_tpc, h->res_toff, &WfsScal::n_res_tiles));
+        // rows are known: tiles onto their row's list or the work list of their class.  res_desc holds a descriptor slot for EVERY
+        // tile of the batch (T * sizeof(TileDesc) bytes) although only the resident ones are written: their number (n_res_tiles) is
+        // still on the device here, and sizing from it would cost one more host round trip before k_tile_assign
         TRY(ensure(h, h->res_desc, (size_t)std::max<i64>(T, 1) * sizeof(TileDesc)));
         ga.res_toff = h->res_toff.as<i64>(); ga.res_desc = h->res_desc.as<TileDesc>();
         DescArgs da{}; da.tile_off = h->tile_off.as<i64>(); da.set_mode = h->set_mode.as<i32>();
         TRY(ensure(h, h->tile_truth, (size_t)T * 8 * 8));
         PulseArgs pt{}; pt.ph = h->ph.as<PhotonRec>(); pt.tile_truth = h->tile_truth.as<double>();
-        pt.ph_gain = (!h->injected && h->ap_active) ? h->ph_gain.as<double>() - h->n_photons : h->ph_gain.as<double>();
+        pt.ph_gain = ph_gain_base(h);
         Timer t(h, "k_tile_assign"); hipLaunchKernelGGL(k_tile_assign, dim3(nblocks(T, 256)), dim3(256), 0, h->stream, d, ga, da, pt);
     }
     TRY(read_scal(h));
-    if (h->h_scal[1] == 1) return h->fail(WFS_E_CAPACITY, "Pulse cache too long (digitise window of 10^6 samples or more, rawdata.py:219)");
-    if (h->h_scal[1] == 2) return h->fail(WFS_E_CAPACITY, "photon time further than 2^31 ns from its instruction");
-    if (h->h_scal[1] == 3) return h->fail(WFS_E_STATE, "internal: a tile of k_s2_tile did not fit its sample buffer");
-    h->n_front_rows = h->h_scal[2]; h->n_short_rows = h->res_on ? h->h_scal[32] : 0; h->n_res_rows = h->res_on ? h->h_scal[32] + h->h_scal[37] : 0; h->max_res_len = h->h_scal[33]; h->s_fin = h->res_on ? h->h_scal[34] : 0;
-    h->n_res_tiles = h->res_on ? h->h_scal[35] : 0; h->s_res = h->res_on ? h->h_scal[36] : 0;
-    h->n_groups = h->h_scal[0]; h->n_active_rows = h->n_front_rows + h->n_res_rows;
-    if (h->res_on && getenv("WFS_RES_STATS"))
+    const WfsScal &sc = *h->h_scal;
+    TRY(device_error(h, sc.error));
+    h->n_groups = sc.n_groups;
+    h->n_front_rows = sc.n_front_rows;
+    h->n_short_rows = h->res_on ? sc.n_short_rows : 0;
+    h->n_res_rows = h->res_on ? sc.n_short_rows + sc.n_long_rows : 0;
+    h->n_active_rows = h->n_front_rows + h->n_res_rows;
+    h->max_res_len = sc.max_res_len;
+    h->s_fin = h->res_on ? sc.n_fin_samples : 0;
+    h->n_res_tiles = h->res_on ? sc.n_res_tiles : 0;
+    h->s_res = h->res_on ? sc.n_res_samples : 0;
+    h->n_tiny_tiles = sc.n_tiny_tiles;
+    h->n_sparse_tiles = sc.n_sparse_tiles; h->max_nb = sc.max_nb_sparse; h->max_tile = sc.max_ph_sparse;
+    h->n_dense_tiles = sc.n_dense_tiles; h->max_nb_dense = sc.max_nb_dense; h->max_tile_dense = sc.max_ph_dense;
+    h->n_wave_tiles = sc.n_wave_tiles;
+    h->n_active_tiles = h->n_tiny_tiles + h->n_sparse_tiles + h->n_dense_tiles + h->n_wave_tiles;
+    r.first_sparse = h->n_tiny_tiles; r.first_dense = r.first_sparse + h->n_sparse_tiles; r.first_wave = r.first_dense + h->n_dense_tiles;
+    h->s_raw = sc.n_acc_samples; h->n_itv_slots = sc.n_itv_slots;
+    h->s_raw_direct = tiles_done ? sc.n_direct_samples : 0;      // samples of the rows that are read from a tile buffer in place
+    if (h->res_on && getenv("WFS_RES_STATS")) {
         fprintf(stderr, "resident rows: %lld short + %lld long of %lld rows, %lld tiles of %lld listed + resident, longest %lld samples, %lld finished samples, accumulators %lld samples\n",
                 (long long)h->n_short_rows, (long long)(h->n_res_rows - h->n_short_rows), (long long)h->n_active_rows, (long long)h->n_res_tiles,
-                (long long)(h->n_res_tiles + h->h_scal[16] + h->h_scal[3] + h->h_scal[11] + h->h_scal[17]), (long long)h->max_res_len, (long long)h->s_fin, (long long)h->h_scal[8]); h->n_sparse_tiles = h->h_scal[3]; h->max_nb = h->h_scal[4]; h->max_tile = h->h_scal[5]; h->max_tile_dense = h->h_scal[15];
-    h->n_dense_tiles = h->h_scal[11]; h->max_nb_dense = h->h_scal[12]; h->n_tiny_tiles = h->h_scal[16];
-    h->n_wave_tiles = h->h_scal[17];
-    h->n_active_tiles = h->n_tiny_tiles + h->n_sparse_tiles + h->n_dense_tiles + h->n_wave_tiles;
-    // one work list: tiny tiles, then sparse, then dense
+                (long long)(h->n_res_tiles + h->n_active_tiles), (long long)h->max_res_len, (long long)h->s_fin, (long long)h->s_raw);
+    }
+    // one work list: the sparse, dense and wave tiles behind the tiny ones
     if (h->n_sparse_tiles > 0)
-        HIPCHK(hipMemcpyAsync(h->active_tiles.as<i32>() + h->n_tiny_tiles, h->sparse_tiles.p, (size_t)h->n_sparse_tiles * 4, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->active_tiles.as<i32>() + r.first_sparse, h->sparse_tiles.p, (size_t)h->n_sparse_tiles * 4, hipMemcpyDeviceToDevice, h->stream));
     if (h->n_dense_tiles > 0)
-        HIPCHK(hipMemcpyAsync(h->active_tiles.as<i32>() + h->n_tiny_tiles + h->n_sparse_tiles, h->dense_tiles.p, (size_t)h->n_dense_tiles * 4, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->active_tiles.as<i32>() + r.first_dense, h->dense_tiles.p, (size_t)h->n_dense_tiles * 4, hipMemcpyDeviceToDevice, h->stream));
     if (h->n_wave_tiles > 0)
-        HIPCHK(hipMemcpyAsync(h->active_tiles.as<i32>() + h->n_tiny_tiles + h->n_sparse_tiles + h->n_dense_tiles, h->wave_tiles.p, (size_t)h->n_wave_tiles * 4, hipMemcpyDeviceToDevice, h->stream));
-    h->s_raw = h->h_scal[8]; h->n_itv_slots = h->h_scal[9];
-    h->s_raw_direct = tiles_done ? h->h_scal[26] : 0;      // samples of the rows that are read from a tile buffer in place
-    // deterministic processing order of the work lists (they were appended with atomics)
-    // (results do not depend on it; sorting keeps profiles and debug dumps reproducible)
+        HIPCHK(hipMemcpyAsync(h->active_tiles.as<i32>() + r.first_wave, h->wave_tiles.p, (size_t)h->n_wave_tiles * 4, hipMemcpyDeviceToDevice, h->stream));
+    return WFS_OK;
+}
 
-    // ---- pulses
+// ---- pulses: every listed tile into its row's accumulators, by the kernel of its class
+static int run_pulses(wfs_handle *h, RunState &r)
+{
+    const WfsDev &d = h->dev;
+    PulseArgs &pa = r.pa;
+    const i64 T = h->n_tiles, S = h->n_sets;
     TRY(ensure(h, h->raw, (size_t)h->s_raw * 4 + 64)); HIPCHK(hipMemsetAsync(h->raw.p, 0, (size_t)h->s_raw * 4, h->stream));       // (+64: a lane of k_zle reads 4 samples from its first valid one)
     TRY(ensure(h, h->truth, (size_t)S * 16 * 8)); HIPCHK(hipMemsetAsync(h->truth.p, 0, (size_t)S * 16 * 8, h->stream));
     TRY(ensure(h, h->tminmax, (size_t)S * 16)); TRY(ensure(h, h->tile_truth, (size_t)T * 8 * 8));
-    PulseArgs pa{};
     pa.active_tiles = h->active_tiles.as<i32>(); pa.n_active = h->n_active_tiles;
     pa.tile_count = h->tile_count.as<i32>(); pa.tile_tmin = h->tile_tmin.as<i32>(); pa.tile_tmax = h->tile_tmax.as<i32>(); pa.tile_off = h->tile_off.as<i64>();
     pa.set_cluster = h->set_cluster.as<i32>(); pa.set_t0 = h->set_t0.as<i64>(); pa.set_mode = h->set_mode.as<i32>();
     pa.ph = h->ph.as<PhotonRec>();
-    pa.ph_gain = (!h->injected && h->ap_active) ? h->ph_gain.as<double>() - h->n_photons : h->ph_gain.as<double>();
+    pa.ph_gain = ph_gain_base(h);
     pa.cl_group = h->cl_group.as<i32>(); pa.row_lo = h->row_lo.as<i64>(); pa.acc_off = h->acc_off.as<i64>(); pa.raw = h->raw.as<i32>();
     pa.tile_truth = h->tile_truth.as<double>();
     h->cur_total = 0;
-    if ((h->keep_currents & 1) && h->n_active_tiles > 0) {
+    if ((h->keep_currents & DBG_CURRENTS) && h->n_active_tiles > 0) {
         // debug: tile lengths in work-list order -> offsets
         std::vector<i32> at((size_t)h->n_active_tiles), tmn((size_t)T), tmx((size_t)T);
         std::vector<i64> t0((size_t)S);
@@ -1694,18 +1803,17 @@ try {
         Timer t(h, "k_pulse_tiny");
         WFS_LAUNCH_F(h, K_PULSE_TINY, dim3(nblocks(h->n_tiny_tiles * TINY_LANES, 256)), dim3(256), 0, d, pt, h->n_tiny_tiles);
     }
-    if (h->n_wave_tiles > 0) {          // work list order: tiny | sparse | dense | wave
+    if (h->n_wave_tiles > 0) {
         PulseArgs pw = pa;
-        const i64 first = h->n_tiny_tiles + h->n_sparse_tiles + h->n_dense_tiles;
-        pw.desc = h->tile_desc.as<TileDesc>() + first;
-        if (pw.cur_off) pw.cur_off += first;
+        pw.desc = h->tile_desc.as<TileDesc>() + r.first_wave;
+        if (pw.cur_off) pw.cur_off += r.first_wave;
         Timer t(h, "k_pulse_wave");
         WFS_LAUNCH_F(h, K_PULSE_WAVE, dim3(nblocks(h->n_wave_tiles, 4)), dim3(256), 0, d, pw, h->n_wave_tiles);
     }
     if (h->n_sparse_tiles > 0) {
         PulseArgs ps = pa;
-        ps.active_tiles = h->active_tiles.as<i32>() + h->n_tiny_tiles;
-        if (ps.cur_off) ps.cur_off += h->n_tiny_tiles;
+        ps.active_tiles = h->active_tiles.as<i32>() + r.first_sparse;
+        if (ps.cur_off) ps.cur_off += r.first_sparse;
         ps.W = (int)((h->max_nb + 7) / 8 * 8); ps.NP = (int)((h->max_tile + 7) / 8 * 8);
         const bool small = h->max_tile <= 256 && h->max_nb <= 256;
         const int tpb = small ? 64 : 256;
@@ -1717,8 +1825,8 @@ try {
     }
     if (h->n_dense_tiles > 0 && h->generic_geom) {        // any digitiser geometry: one kernel for every tile
         PulseArgs pd = pa;
-        pd.desc = h->tile_desc.as<TileDesc>() + h->n_tiny_tiles + h->n_sparse_tiles;
-        if (pd.cur_off) pd.cur_off += h->n_tiny_tiles + h->n_sparse_tiles;
+        pd.desc = h->tile_desc.as<TileDesc>() + r.first_dense;
+        if (pd.cur_off) pd.cur_off += r.first_dense;
         size_t lds = (size_t)(256 + d.tlen - 1) * d.dt * 8 + (size_t)d.dt * d.tlen * 8 + 4 * 8 * 8 + 64;
         lds = (lds + 15) / 16 * 16;
         if (lds > 128 * 1024) return h->fail(WFS_E_CAPACITY, "sample_duration x template length too large for the LDS tables of k_pulse_generic");
@@ -1726,9 +1834,9 @@ try {
         WFS_LAUNCH_F(h, K_PULSE_GENERIC, dim3((unsigned)h->n_dense_tiles), dim3(256), lds, d, pd);
     } else if (h->n_dense_tiles > 0) {
         PulseArgs pd = pa;
-        pd.active_tiles = h->active_tiles.as<i32>() + h->n_tiny_tiles + h->n_sparse_tiles;
-        pd.desc = h->tile_desc.as<TileDesc>() + h->n_tiny_tiles + h->n_sparse_tiles;
-        if (pd.cur_off) pd.cur_off += h->n_tiny_tiles + h->n_sparse_tiles;
+        pd.active_tiles = h->active_tiles.as<i32>() + r.first_dense;
+        pd.desc = h->tile_desc.as<TileDesc>() + r.first_dense;
+        if (pd.cur_off) pd.cur_off += r.first_dense;
         // chunks of TPB live samples per pass (TPB + 21 start-bin rows of 80 bytes in LDS: 22 KB for 256 -> 7 workgroups per CU)
         const i64 n_live_max = h->max_nb_dense + d.tlen - 1;
         const bool small = n_live_max <= 128;
@@ -1738,11 +1846,10 @@ try {
         // registers; longer tiles: several workgroups per tile (each re-reads the tile's photons for its chunks)
         pd.n_win = (h->max_tile_dense <= (i64)tpb * DENSE_PPT) ? 1 : (int)std::min<i64>(NWIN_MAX, std::max<i64>(1, (n_live_max + tpb - 1) / tpb));
         pd.W = tpb;
-        TemplateArg tp;
-        for (int k = 0; k < 22; k++) for (int r = 0; r < WFS_DT; r++) tp.t[k * WFS_DT + r] = h->h_templates[(size_t)r * 22 + k];
+        const TemplateArg tp = fill_template_arg(h);
         size_t lds = (size_t)(tpb + d.tlen - 1) * d.dt * 8 + (size_t)8 * (tpb / 64) * 8 + 64 + TAP_LDS_BYTES(256) + 16;
         lds = (lds + 15) / 16 * 16;
-        pd.sparse_max = (h->keep_currents & 2) ? -1 : h->tap_sparse_max;      // (force_dense: every wave takes the dense gather)
+        pd.sparse_max = (h->keep_currents & DBG_FORCE_DENSE) ? -1 : h->tap_sparse_max;      // (force_dense: every wave takes the dense gather)
         pd.spe_lds = ((size_t)(tpb + d.tlen - 1) * d.dt >= 2001) ? 1 : 0;
         const unsigned grid = (unsigned)(h->n_dense_tiles * pd.n_win);
         Timer t(h, "k_pulse_dense");
@@ -1755,23 +1862,29 @@ try {
         }
     }
 
-    if (tiles_done && h->h_scal[27] > 0) {   // tiles of k_s2_tile that share their row with other pulses: added into the row's accumulators
+    if (r.tiles_done && h->h_scal->n_shared_rows > 0) {   // tiles of k_s2_tile that share their row with other pulses: added into the row's accumulators
         TileAddArgs ta{h->set_cluster.as<i32>(), h->cl_group.as<i32>(), h->row_lo.as<i64>(), h->acc_off.as<i64>(), h->row_cnt.as<i32>(), h->raw.as<i32>()};
         Timer t(h, "k_tile_add");
         hipLaunchKernelGGL(k_tile_add, dim3((unsigned)h->n_fused_tiles), dim3(256), 0, h->stream, d, h->fuse_args, ta);
     }
+    return WFS_OK;
+}
 
-    // ---- ZLE + records
-    const i64 RS = CG * d.row_slots;
+// ---- rows: resident rows (pulses, finished samples and intervals in one kernel), truth, ZLE of the accumulator rows
+static int run_rows(wfs_handle *h, RunState &r)
+{
+    const WfsDev &d = h->dev;
+    const GeomArgs &ga = r.ga; const PulseArgs &pa = r.pa; ZleArgs &za = r.za;
+    const i64 S = h->n_sets, CG = r.CG;
+    const i64 RS = r.RS = CG * d.row_slots;
     TRY(ensure(h, h->itv_left, (size_t)h->n_itv_slots * 8 + 16)); TRY(ensure(h, h->itv_right, (size_t)h->n_itv_slots * 8 + 16));      // (+16: k_pack reads the first two slots of a row whatever its capacity)
     TRY(ensure(h, h->itv_n, (size_t)RS * 4)); TRY(ensure(h, h->row_nrec, (size_t)RS * 4));
     HIPCHK(hipMemsetAsync(h->itv_n.p, 0, (size_t)RS * 4, h->stream)); HIPCHK(hipMemsetAsync(h->row_nrec.p, 0, (size_t)RS * 4, h->stream));
-    ZleArgs za{};
     za.active_rows = h->active_rows.as<i32>(); za.n_active_rows = h->n_active_rows; za.row_lo = h->row_lo.as<i64>(); za.row_hi = h->row_hi.as<i64>();
     za.acc_off = h->acc_off.as<i64>(); za.raw = h->raw.as<i32>(); za.grp_left = h->grp_left.as<i64>(); za.grp_ixrand = h->grp_ixrand.as<i64>();
     za.itv_off = h->itv_off.as<i64>(); za.itv_left = h->itv_left.as<i64>(); za.itv_right = h->itv_right.as<i64>();
     za.itv_n = h->itv_n.as<i32>(); za.row_nrec = h->row_nrec.as<i32>(); za.spr = WFS_SPR;
-    if (tiles_done) { za.tile_done = ga.tile_done; za.n_done = ga.n_done; za.row_cnt = ga.row_cnt; za.row_tile = ga.row_tile; za.ins_bcap = ga.ins_bcap; za.ins_boff = ga.ins_boff; za.tbuf = h->tbuf.as<i32>(); }
+    if (r.tiles_done) { za.tile_done = ga.tile_done; za.n_done = ga.n_done; za.row_cnt = ga.row_cnt; za.row_tile = ga.row_tile; za.ins_bcap = ga.ins_bcap; za.ins_boff = ga.ins_boff; za.tbuf = h->tbuf.as<i32>(); }
     za.n_front = h->n_front_rows; za.rows_cap = CG * d.row_slots;
     if (h->n_res_rows > 0) {
         TRY(ensure(h, h->fin, (size_t)h->s_fin * 2 + 16));
@@ -1780,7 +1893,7 @@ try {
         za.n_short = h->n_short_rows; za.res_long = h->res_long.as<i32>(); za.res_rows = h->res_rows.as<ResRow>();
     }
     h->row_dbg_total = 0;
-    if ((h->keep_currents & 1) && h->n_active_rows > 0) {
+    if ((h->keep_currents & DBG_CURRENTS) && h->n_active_rows > 0) {
         std::vector<i32> ar((size_t)h->n_active_rows);
         std::vector<i64> lo((size_t)CG * d.n_tpc), hi((size_t)CG * d.n_tpc);
         HIPCHK(hipMemcpy(ar.data(), h->active_rows.p, ar.size() * 4, hipMemcpyDeviceToHost));
@@ -1798,28 +1911,31 @@ try {
         za.row_dbg = h->row_dbg.as<i32>(); za.row_dbg_off = h->row_dbg_off.as<i64>();
     }
     TRY(ensure(h, h->row_desc, (size_t)h->n_active_rows * sizeof(RowDesc))); za.desc = h->row_desc.as<RowDesc>();
-    if (h->sort_records) {      // scal[22] / scal[29]: first sample / end of the last row of the batch (k_row_desc): origin and span of the sort keys
-        za.key_base = h->scal.as<i64>() + 22;
-        hipLaunchKernelGGL(k_fill_i64, dim3(1), dim3(64), 0, h->stream, za.key_base, (i64)1, I64_MAX);
-        hipLaunchKernelGGL(k_fill_i64, dim3(1), dim3(64), 0, h->stream, h->scal.as<i64>() + 29, (i64)1, I64_MIN);
+    if (h->sort_records) {      // key_origin / key_end: first sample / end of the last row of the batch (k_row_desc): origin and span of the sort keys
+        za.key_base = h->scal.as<WfsScal>();
+        hipLaunchKernelGGL(k_fill_i64, dim3(1), dim3(64), 0, h->stream, &za.key_base->key_origin, (i64)1, I64_MAX);
+        hipLaunchKernelGGL(k_fill_i64, dim3(1), dim3(64), 0, h->stream, &za.key_base->key_end, (i64)1, I64_MIN);
     }
     if (h->n_active_rows > 0) { Timer t(h, "k_row_desc"); hipLaunchKernelGGL(k_row_desc, dim3(nblocks(h->n_active_rows, 256)), dim3(256), 0, h->stream, d, za); }
-    const int noise_kind = !d.enable_noise ? 0 : (d.noise_f ? 2 : 1);      // (a template parameter of the row kernels: no branch between their loads)
+    r.noise_kind = !d.enable_noise ? 0 : (d.noise_f ? 2 : 1);
     if (h->n_res_rows > 0) {        // resident rows: pulses, finished samples and intervals by one wave per row
         PulseArgs pr = pa;
         pr.desc = h->res_desc.as<TileDesc>(); pr.currents = nullptr; pr.cur_off = nullptr;
         // two launches: the rows of at most RES_SHORT_LEN samples at full occupancy, the longer ones with LDS for the longest of them
         Timer t(h, "k_row_pulse");
-#define WFS_ROW_PULSE2(NK, F) do { if (part == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_row_pulse<NK, F, false>), grid, dim3(256), lds, h->stream, d, pr, za, first, n_rows, region); \
-                                   else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_row_pulse<NK, F, true>), grid, dim3(256), lds, h->stream, d, pr, za, first, n_rows, region); } while (0)
-#define WFS_ROW_PULSE(NK) do { if (h->cfg.fma) WFS_ROW_PULSE2(NK, true); else WFS_ROW_PULSE2(NK, false); } while (0)
+#define K_ROW_PULSE_SHORT(F) k_row_pulse<NK, F, false>
+#define K_ROW_PULSE_LONG(F) k_row_pulse<NK, F, true>
         for (int part = 0; part < 2; part++) {
             const i64 first = part == 0 ? 0 : h->n_short_rows, n_rows = part == 0 ? h->n_short_rows : h->n_res_rows - h->n_short_rows;
             if (n_rows <= 0) continue;
             const i32 region = part == 0 ? RES_SHORT_LEN : (i32)((std::min<i64>(h->max_res_len, h->res_max_len) + 255) / 256 * 256);
             const size_t lds = ROW_LDS_FIXED + (size_t)4 * region * 4;
             const dim3 grid(nblocks(n_rows, 4));
-            if (noise_kind == 0) WFS_ROW_PULSE(0); else if (noise_kind == 1) WFS_ROW_PULSE(1); else WFS_ROW_PULSE(2);
+            with_noise_kind(r.noise_kind, [&](auto nk) {
+                constexpr int NK = decltype(nk)::value;
+                if (part == 0) WFS_LAUNCH_F(h, K_ROW_PULSE_SHORT, grid, dim3(256), lds, d, pr, za, first, n_rows, region);
+                else WFS_LAUNCH_F(h, K_ROW_PULSE_LONG, grid, dim3(256), lds, d, pr, za, first, n_rows, region);
+            });
         }
     }
     {   // truth accumulators of every pulse set from the per-tile partial sums
@@ -1831,13 +1947,20 @@ try {
 
     if (h->n_front_rows > 0) {
         Timer t(h, "k_zle"); const dim3 grid(nblocks(h->n_front_rows, 4));
-        if (noise_kind == 0) hipLaunchKernelGGL(k_zle<0>, grid, dim3(256), 0, h->stream, d, za);
-        else if (noise_kind == 1) hipLaunchKernelGGL(k_zle<1>, grid, dim3(256), 0, h->stream, d, za);
-        else hipLaunchKernelGGL(k_zle<2>, grid, dim3(256), 0, h->stream, d, za);
+        with_noise_kind(r.noise_kind, [&](auto nk) { hipLaunchKernelGGL(k_zle<decltype(nk)::value>, grid, dim3(256), 0, h->stream, d, za); });
     }
-    TRY(scan(h, h->row_nrec.as<i32>(), RS, h->rec_off, 10));
+    return WFS_OK;
+}
+
+// ---- records: how many, where (sorted by time and channel on request), packing; the totals of wfs_get_counts
+static int run_records(wfs_handle *h, RunState &r)
+{
+    const WfsDev &d = h->dev;
+    ZleArgs &za = r.za;
+    const i64 RS = r.RS;
+    TRY(scan(h, h->row_nrec.as<i32>(), RS, h->rec_off, &WfsScal::n_records));
     TRY(read_scal(h));
-    h->n_records = h->h_scal[10];
+    h->n_records = h->h_scal->n_records;
     // the other arena: the previous batch's records may still be on their way to the host
     h->rec_cur ^= 1;
     if (h->rec_pending[h->rec_cur]) { HIPCHK(hipEventSynchronize(h->rec_copied[h->rec_cur])); h->rec_pending[h->rec_cur] = false; }
@@ -1853,7 +1976,7 @@ try {
         { Timer t(h, "k_rec_keys"); hipLaunchKernelGGL(k_rec_keys, dim3(nblocks(h->n_active_rows, 4)), dim3(256), 0, h->stream, d, za); }
         // rocPRIM's radix sort, over the key bits that are in use only: (samples the batch spans) << 12 | channel
         unsigned end_bit = 13;
-        { const u64 span = (u64)std::max<i64>(h->h_scal[29] - h->h_scal[22], 1); while (end_bit < 64 && ((span << 12) >> end_bit) != 0) end_bit++; }
+        { const u64 span = (u64)std::max<i64>(h->h_scal->key_end - h->h_scal->key_origin, 1); while (end_bit < 64 && ((span << 12) >> end_bit) != 0) end_bit++; }
         size_t bytes = 0;
         HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, h->rec_key.as<u64>(), h->rec_key2.as<u64>(), h->rec_val.as<u32>(), h->rec_val2.as<u32>(), (size_t)NR, 0u, end_bit, h->stream));
         TRY(ensure(h, h->sort_tmp, bytes));
@@ -1869,20 +1992,39 @@ try {
             Timer t(h, "k_pack_res"); hipLaunchKernelGGL(k_pack_res, dim3(nblocks(h->n_res_rows, 4)), dim3(256), 0, h->stream, pr);
         }
         if (h->n_front_rows > 0) {
-        Timer t(h, "k_pack"); const dim3 grid(nblocks(h->n_front_rows, 4));
-        if (noise_kind == 0) hipLaunchKernelGGL(k_pack<0>, grid, dim3(256), 0, h->stream, d, za);
-        else if (noise_kind == 1) hipLaunchKernelGGL(k_pack<1>, grid, dim3(256), 0, h->stream, d, za);
-        else hipLaunchKernelGGL(k_pack<2>, grid, dim3(256), 0, h->stream, d, za);
+            Timer t(h, "k_pack"); const dim3 grid(nblocks(h->n_front_rows, 4));
+            with_noise_kind(r.noise_kind, [&](auto nk) { hipLaunchKernelGGL(k_pack<decltype(nk)::value>, grid, dim3(256), 0, h->stream, d, za); });
         }
     }
     {   // totals of wfs_get_counts: afterpulse sets carry no truth (rawdata.py:322-323)
         const i64 n_prim = (!h->injected && h->ap_active) ? h->n_psets : h->n_sets;
         const i64 work = std::max<i64>(RS, n_prim);
-        hipLaunchKernelGGL(k_counts, dim3((unsigned)std::min<i64>(nblocks(work, 256), 128)), dim3(256), 0, h->stream, h->itv_n.as<i32>(), RS, h->truth.as<double>(), n_prim, h->scal.as<i64>());
+        hipLaunchKernelGGL(k_counts, dim3((unsigned)std::min<i64>(nblocks(work, 256), 128)), dim3(256), 0, h->stream, h->itv_n.as<i32>(), RS, h->truth.as<double>(), n_prim, h->scal.as<WfsScal>());
     }
     TRY(read_scal(h));
     HIPCHK(hipGetLastError());
     CHECK_LAUNCHES();
+    return WFS_OK;
+}
+
+int wfs_run(wfs_handle *h)
+try {
+    if (!h) return WFS_E_INVALID;
+    if (!h->batch_loaded) return h->fail(WFS_E_STATE, "no batch loaded");
+    if (h->dev_rows_pending && from_generator(h)) return h->fail(WFS_E_STATE, "instructions with cdf_row -1: call wfs_eval_pattern_rows before wfs_run");
+    h->ran = false; h->gen_done = false; h->gen_order_ready = false;
+    HIPCHK(hipSetDevice(h->device));
+    for (auto &t : h->times) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
+    h->times.clear();
+    HIPCHK(hipMemsetAsync(h->scal.p, 0, sizeof(WfsScal), h->stream));
+    TRY(run_input(h));
+    h->gen_done = true;
+    if (h->keep_currents & DBG_GEN_ONLY) { HIPCHK(hipStreamSynchronize(h->stream)); return WFS_OK; }      // wfs_set_debug bit 2: photon generation only
+    RunState r;
+    TRY(run_geometry(h, r));
+    TRY(run_pulses(h, r));
+    TRY(run_rows(h, r));
+    TRY(run_records(h, r));
     h->ran = true;
     return WFS_OK;
 } WFS_CATCH(h)
@@ -1893,11 +2035,11 @@ try {
     if (!h->ran) return h->fail(WFS_E_STATE, "wfs_run has not completed");
     wfs_counts c{};
     c.n_instructions = h->n_ins; c.n_pulse_sets = h->n_sets; c.n_emitters = h->n_emitters; c.n_photons = h->n_photons + ((!h->injected && h->ap_active) ? h->n_ap_photons : 0);
-    const bool tiles_done = !h->injected && !h->optical && h->fuse_full && h->n_fused_tiles > 0;
+    const bool tiles_done = tiles_made(h);
     c.n_tiles = h->n_active_tiles + (tiles_done ? h->n_fused_tiles : 0) + h->n_res_tiles; c.n_groups = h->n_groups; c.n_rows = h->n_active_rows;
     c.n_raw_samples = h->s_raw + (tiles_done ? h->s_raw_direct : 0) + h->s_res;
     c.n_records = h->n_records;
-    c.n_intervals = h->h_scal[20]; c.n_pe = h->h_scal[21];          // reduced on the device at the end of wfs_run (k_counts)
+    c.n_intervals = h->h_scal->n_intervals; c.n_pe = h->h_scal->n_pe;          // reduced on the device at the end of wfs_run (k_counts)
     *out = c; h->counts = c;
     return WFS_OK;
 } WFS_CATCH(h)
@@ -2050,7 +2192,7 @@ try {
 int wfs_copy_currents(wfs_handle *h, double *cur, int64_t cap)
 try {
     if (!h || !h->ran) return WFS_E_STATE;
-    if (!(h->keep_currents & 1)) return h->fail(WFS_E_STATE, "wfs_set_debug(h, 1) before wfs_run");
+    if (!(h->keep_currents & DBG_CURRENTS)) return h->fail(WFS_E_STATE, "wfs_set_debug(h, 1) before wfs_run");
     if (cap < h->cur_total) return h->fail(WFS_E_CAPACITY, "current buffer too small");
     if (h->cur_total) HIPCHK(hipMemcpy(cur, h->currents.p, (size_t)h->cur_total * 8, hipMemcpyDeviceToHost));
     return WFS_OK;
@@ -2059,7 +2201,7 @@ try {
 int wfs_copy_rows(wfs_handle *h, int32_t *group, int32_t *channel, int64_t *left, int64_t *right, int64_t *data_off, int64_t cap)
 try {
     if (!h || !h->ran) return WFS_E_STATE;
-    if (!(h->keep_currents & 1)) return h->fail(WFS_E_STATE, "wfs_set_debug(h, 1) before wfs_run");
+    if (!(h->keep_currents & DBG_CURRENTS)) return h->fail(WFS_E_STATE, "wfs_set_debug(h, 1) before wfs_run");
     const WfsDev &d = h->dev;
     const i64 A = h->n_active_rows;
     if (cap < A) return h->fail(WFS_E_CAPACITY, "row buffer too small");
@@ -2090,7 +2232,7 @@ try {
 int wfs_copy_photons(wfs_handle *h, int64_t *set_off, int64_t *t, int16_t *ch, double *gain, uint8_t *dpe, int64_t cap)
 try {
     if (!h || !h->ran) return WFS_E_STATE;
-    if (!h->injected && !h->optical && h->fuse_full && h->n_fused_tiles > 0 && !(h->keep_currents & 16))
+    if (tiles_made(h) && !(h->keep_currents & DBG_KEEP_PHOTONS))
         return h->fail(WFS_E_STATE, "the photons of tile-generated instructions were not kept: wfs_set_debug bit 4 before wfs_run");
     const WfsDev &d = h->dev;
     const i64 P = h->n_photons + ((!h->injected && h->ap_active) ? h->n_ap_photons : 0), T = h->n_tiles;

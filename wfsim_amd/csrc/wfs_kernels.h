@@ -21,14 +21,14 @@ __global__ void k_fill_i32(i32 *p, i64 n, i32 v) { i64 i = (i64)blockIdx.x * blo
 __global__ void k_fill_minmax(i64 *p, i64 n) { i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; if (i < n) p[i] = (i & 1) ? I64_MIN : I64_MAX; }
 
 // totals for wfs_get_counts, reduced on the device (copying itv_n back cost 300 MB per 10^5-cluster batch):
-// scal[20] = sum of itv_n (ZLE intervals), scal[21] = sum of the per-set n_pe (truth[s][1], integral doubles)
-__global__ void k_counts(const i32 *itv_n, i64 n_itv, const double *truth, i64 n_sets, i64 *scal)
+// n_intervals = sum of itv_n (ZLE intervals), n_pe = sum of the per-set n_pe (truth[s][1], integral doubles)
+__global__ void k_counts(const i32 *itv_n, i64 n_itv, const double *truth, i64 n_sets, WfsScal *scal)
 {
     i64 a = 0, b = 0;
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n_itv; i += (i64)gridDim.x * blockDim.x) a += itv_n[i];
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n_sets; i += (i64)gridDim.x * blockDim.x) b += (i64)(truth[i * 16 + 1] + 0.5);
     for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, o, 64); b += __shfl_down(b, o, 64); }
-    if ((threadIdx.x & 63) == 0) { if (a) atomicAdd((unsigned long long *)&scal[20], (unsigned long long)a); if (b) atomicAdd((unsigned long long *)&scal[21], (unsigned long long)b); }
+    if ((threadIdx.x & 63) == 0) { if (a) atomicAdd((unsigned long long *)&scal->n_intervals, (unsigned long long)a); if (b) atomicAdd((unsigned long long *)&scal->n_pe, (unsigned long long)b); }
 }
 
 // ------------------------------------------------------------------------------------------------ scan
@@ -123,12 +123,11 @@ struct GeomArgs {
     i64 *grp_lo, *grp_hi, *grp_left, *grp_right, *grp_ixrand; u32 *grp_gid;
     i64 *row_lo, *row_hi;
     i32 *acc_len, *itv_cap; i32 *active_rows;
-    i64 *scal;           // [0] n_groups [1] error flag [2] n_active_rows [3] n sparse tiles [4] their max start bins
-                         // [5] their max photons [11] n dense tiles [12] their max start bins
+    WfsScal *scal;       // the device scalar block (wfs_device.h)
     i32 *active_tiles;   // tiny tiles (thread per tile); the other two lists are copied behind them by the host side
     i32 *sparse_tiles;   // sparse-class tiles (few photons per start bin: sorted-list kernel)
     i32 *dense_tiles;    // everything else (dense H-table kernel, windows over time)
-    i32 *wave_tiles;     // medium tiles (at most 64 photons, any width: wave per tile); scal[17] = their number
+    i32 *wave_tiles;     // medium tiles (at most 64 photons, any width: wave per tile); scal->n_wave_tiles = their number
     const i32 *tile_done;       // [n_done] 1: the tile's pulse was made by k_s2_tile<FULL> (wfs_tilegen.h): on no work list (or nullptr)
     i64 n_done;                 // primary tiles (the tiles of the afterpulse sets, which follow them, are never done)
     i32 *row_cnt, *row_tile;    // [groups * n_tpc] tiles in the row; one of them
@@ -168,7 +167,7 @@ __device__ __forceinline__ void tile_bounds(const WfsDev &d, i64 t0, i32 tmin, i
 }
 
 // work lists and maxima: aggregated per workgroup in LDS, then one global atomic per workgroup and counter
-// (76k wave-level atomics on one cache line cost ~3 ms; the counters all live in the same line of scal[])
+// (76k wave-level atomics on one cache line cost ~3 ms; the counters all live in the same line of WfsScal)
 __device__ __forceinline__ void tile_list_append(const GeomArgs &a, bool listed, int cls, i64 nb, i32 cnt, i64 tile)
 {
     __shared__ i32 s_n[4]; __shared__ i64 s_b[4], s_mx[4];
@@ -181,14 +180,14 @@ __device__ __forceinline__ void tile_list_append(const GeomArgs &a, bool listed,
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        s_b[0] = s_n[0] ? (i64)atomicAdd((u64 *)&a.scal[16], (u64)s_n[0]) : 0;
-        s_b[1] = s_n[1] ? (i64)atomicAdd((u64 *)&a.scal[3], (u64)s_n[1]) : 0;
-        s_b[2] = s_n[2] ? (i64)atomicAdd((u64 *)&a.scal[11], (u64)s_n[2]) : 0;
-        s_b[3] = s_n[3] ? (i64)atomicAdd((u64 *)&a.scal[17], (u64)s_n[3]) : 0;
-        if (s_mx[0]) atomicMax(&a.scal[4], s_mx[0]);
-        if (s_mx[1]) atomicMax(&a.scal[5], s_mx[1]);
-        if (s_mx[2]) atomicMax(&a.scal[12], s_mx[2]);
-        if (s_mx[3]) atomicMax(&a.scal[15], s_mx[3]);
+        s_b[0] = s_n[0] ? (i64)atomicAdd((u64 *)&a.scal->n_tiny_tiles, (u64)s_n[0]) : 0;
+        s_b[1] = s_n[1] ? (i64)atomicAdd((u64 *)&a.scal->n_sparse_tiles, (u64)s_n[1]) : 0;
+        s_b[2] = s_n[2] ? (i64)atomicAdd((u64 *)&a.scal->n_dense_tiles, (u64)s_n[2]) : 0;
+        s_b[3] = s_n[3] ? (i64)atomicAdd((u64 *)&a.scal->n_wave_tiles, (u64)s_n[3]) : 0;
+        if (s_mx[0]) atomicMax(&a.scal->max_nb_sparse, s_mx[0]);
+        if (s_mx[1]) atomicMax(&a.scal->max_ph_sparse, s_mx[1]);
+        if (s_mx[2]) atomicMax(&a.scal->max_nb_dense, s_mx[2]);
+        if (s_mx[3]) atomicMax(&a.scal->max_ph_dense, s_mx[3]);
     }
     __syncthreads();
     if (listed) (cls == 0 ? a.active_tiles : (cls == 1 ? a.sparse_tiles : (cls == 2 ? a.dense_tiles : a.wave_tiles)))[s_b[cls] + rk] = (i32)tile;
@@ -288,7 +287,7 @@ __global__ __launch_bounds__(GROUPS_TPB) void k_groups(WfsDev d, GeomArgs a)
             if (e != I64_MIN) { atomicMin(&a.grp_gid[g], (u32)k); r = h ? (e > r ? e : r) : e; h = 1; }     // first cluster of the group with a pulse
         }
     }
-    if (tid == GROUPS_TPB - 1) a.scal[0] = ssum[tid] + 1;
+    if (tid == GROUPS_TPB - 1) a.scal->n_groups = ssum[tid] + 1;
 }
 
 __global__ void k_tile_rows(WfsDev d, GeomArgs a)
@@ -326,10 +325,10 @@ __global__ void k_tile_rows(WfsDev d, GeomArgs a)
 __global__ void k_group_final(WfsDev d, GeomArgs a)
 {
     i64 g = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= a.scal[0]) return;
+    if (g >= a.scal->n_groups) return;
     if (a.grp_lo[g] == I64_MAX) { a.grp_left[g] = 0; a.grp_right[g] = -1; a.grp_ixrand[g] = -1; return; }
     i64 left = a.grp_lo[g] - d.tw, right = a.grp_hi[g] + d.tw;
-    if (!(right - left < 1000000)) atomicMax(&a.scal[1], (i64)1);           // "Pulse cache too long", rawdata.py:219
+    if (!(right - left < 1000000)) atomicMax(&a.scal->error, (i64)WFS_DEV_WINDOW);           // "Pulse cache too long", rawdata.py:219
     if (floormod(left, 2) != 0) left -= 1;
     a.grp_left[g] = left; a.grp_right[g] = right;
     i64 ix = -1;
@@ -360,7 +359,7 @@ __global__ void k_row_len(WfsDev d, GeomArgs a)
     if (threadIdx.x == 0) { s_n = 0; s_nres = 0; s_nlong = 0; s_direct = 0; s_shared = 0; s_maxres = 0; s_reslen = 0; }
     __syncthreads();
     const i64 idx = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    const i64 n = a.scal[0] * d.row_slots;
+    const i64 n = a.scal->n_groups * d.row_slots;
     i32 cap = 0, rk = -1; bool resident = false, longrow = false;
     if (idx < n) {
         const i64 g = idx / d.row_slots; const i32 slot = (i32)(idx - g * d.row_slots);
@@ -386,12 +385,12 @@ __global__ void k_row_len(WfsDev d, GeomArgs a)
         }
     }
     __syncthreads();
-    if (threadIdx.x == 0 && s_n) s_base = (i64)atomicAdd((u64 *)&a.scal[2], (u64)s_n);
-    if (threadIdx.x == 0 && s_nres) s_rbase = (i64)atomicAdd((u64 *)&a.scal[32], (u64)s_nres);
-    if (threadIdx.x == 0 && s_nlong) s_lbase = (i64)atomicAdd((u64 *)&a.scal[37], (u64)s_nlong);
-    if (threadIdx.x == 0 && s_reslen) { atomicMax(&a.scal[33], (i64)s_maxres); atomicAdd((u64 *)&a.scal[36], (u64)s_reslen); }
-    if (threadIdx.x == 0 && s_direct) atomicAdd((u64 *)&a.scal[26], (u64)s_direct);      // samples of the rows read in place
-    if (threadIdx.x == 0 && s_shared) atomicAdd((u64 *)&a.scal[27], (u64)s_shared);      // rows made by several tiles (k_tile_add is needed)
+    if (threadIdx.x == 0 && s_n) s_base = (i64)atomicAdd((u64 *)&a.scal->n_front_rows, (u64)s_n);
+    if (threadIdx.x == 0 && s_nres) s_rbase = (i64)atomicAdd((u64 *)&a.scal->n_short_rows, (u64)s_nres);
+    if (threadIdx.x == 0 && s_nlong) s_lbase = (i64)atomicAdd((u64 *)&a.scal->n_long_rows, (u64)s_nlong);
+    if (threadIdx.x == 0 && s_reslen) { atomicMax(&a.scal->max_res_len, (i64)s_maxres); atomicAdd((u64 *)&a.scal->n_res_samples, (u64)s_reslen); }
+    if (threadIdx.x == 0 && s_direct) atomicAdd((u64 *)&a.scal->n_direct_samples, (u64)s_direct);      // samples of the rows read in place
+    if (threadIdx.x == 0 && s_shared) atomicAdd((u64 *)&a.scal->n_shared_rows, (u64)s_shared);      // rows made by several tiles (k_tile_add is needed)
     __syncthreads();
     if (rk >= 0) {
         if (!resident) a.active_rows[s_base + rk] = (i32)idx;
@@ -1079,7 +1078,7 @@ __global__ void k_tile_assign(WfsDev d, GeomArgs a, DescArgs da, PulseArgs pa)
 template <bool FMA>
 __global__ __launch_bounds__(256) void k_pulse_tiny(WfsDev d, PulseArgs a, i64 n_tiny)
 {
-    constexpr int dt = WFS_DT, tlen = 22, NP = TINY_MAX_PHOTONS;
+    constexpr int dt = WFS_DT, tlen = 22;
     __shared__ double sT[dt * tlen];                      // templates[r][k]
     __shared__ double s_cmax[dt];
     for (int i = threadIdx.x; i < dt * tlen; i += blockDim.x) sT[i] = d.templates[i];
@@ -1220,7 +1219,7 @@ __device__ __forceinline__ void wave_tile_pulse(const WfsDev &d, const PulseArgs
 template <bool FMA>
 __global__ __launch_bounds__(256) void k_pulse_wave(WfsDev d, PulseArgs a, i64 n_wave)
 {
-    constexpr int dt = WFS_DT, tlen = 22;
+    constexpr int dt = WFS_DT;
     __shared__ double sTz[WAVE_TZ_LEN];                   // templates[r][k] with a zero tap in front of and behind every row
     __shared__ double s_cmax[dt];
     __shared__ WavePhoton s_ph[4][64 + PW_U];             // the sorted, merged photons of each wave's tile, pad entries that reach nothing behind them
@@ -1471,7 +1470,7 @@ struct ZleArgs {
     i32 spr;                     // samples per record
     struct RowDesc *desc;        // [n_active_rows] everything a row's wave needs, prepared by k_row_desc
     const u32 *rec_dest;         // record order by (time, channel): slot of record r in the output (nullptr: row order)
-    u64 *rec_key; u32 *rec_val; i64 *key_base;     // k_rec_keys: sort key (sample - *key_base) << 12 | channel, and the record index; *key_base = first sample of the batch (k_row_desc)
+    u64 *rec_key; u32 *rec_val; WfsScal *key_base; // k_rec_keys: sort key (sample - key_base->key_origin) << 12 | channel, and the record index; the scalar block when the records are sorted, else nullptr
     const i32 *tile_done, *row_cnt, *row_tile; const i32 *ins_bcap; const i64 *ins_boff; const i32 *tbuf; i64 n_done;      // rows read from a tile buffer in place (wfs_tilegen.h)
     // resident rows (k_row_pulse): the rows behind the first n_front of the row list; their finished 16-bit samples
     i64 n_front, n_short, rows_cap; const i64 *res_toff, *fin_off; int16_t *fin; const i32 *res_long; struct ResRow *res_rows;
@@ -1517,7 +1516,7 @@ __global__ void k_row_desc(WfsDev d, ZleArgs a)
     q.thr = d.thr_zle[channel]; q.idx = idx; q.len = (i32)(a.row_hi[ridx] - a.row_lo[ridx] + 1 + 2 * (i64)d.tw);
     q.channel = channel; q.he = he ? 1 : 0;
     a.desc[r] = q;
-    if (a.key_base) { atomicMin(a.key_base, q.row_abs); atomicMax(a.key_base + 7, q.row_abs + (i64)q.len); }      // (scal[22], scal[29])
+    if (a.key_base) { atomicMin(&a.key_base->key_origin, q.row_abs); atomicMax(&a.key_base->key_end, q.row_abs + (i64)q.len); }
 }
 
 // finished sample of a row: accumulated ADC + noise + baseline, clamped at 0
@@ -1892,7 +1891,7 @@ __global__ __launch_bounds__(256) void k_rec_keys(WfsDev d, ZleArgs a)
     const i32 count = a.itv_n[q.idx];
     if (count == 0) return;
     i64 rec = a.rec_off[q.idx];
-    const i64 key_base = *a.key_base;
+    const i64 key_base = a.key_base->key_origin;
     for (i32 k = 0; k < count; k++) {
         const i64 left = a.itv_left[q.itv_base + k]; const i32 plen = (i32)(a.itv_right[q.itv_base + k] - left + 1);
         if (plen <= 0) continue;
@@ -2115,7 +2114,7 @@ struct GenArgs {
     i64 *ins_ph0;                 // [n_ins + 1] first photon (generation order) of every instruction: em_ph_off[em_off[i]]
     double *el_stat;              // [n_ins][4] electrons: n, sum t, sum t^2 ; el_minmax [n_ins][2]
     i64 *el_minmax;
-    i64 *scal;
+    WfsScal *scal;
     // model variants of the photon delays (wfs_set_delay_models / wfs_set_instruction_models); tabs == nullptr: the two default tables
     const AliasTab *tabs;         // [n_tables + 2] user tables, then the default S1 and S2 tables
     const i32 *ins_tab, *ins_tabb;        // [n_ins] table of the instruction's photons on top / bottom array channels
@@ -2392,7 +2391,7 @@ struct ApArgs {
     i64 cap;                        // capacity of the staging list
     i32 *ap_ins; i32 *ap_ch; i32 *ap_t; double *ap_gain;     // [cap] instruction, channel, ns relative to the instruction, gain
     u32 *ap_key;                    // [cap] order key: element << 29 | index of the parent photon among its instruction's photons
-    i64 *count;                     // number of afterpulse candidates in the list (device scalar, scal[13])
+    i64 *count;                     // number of afterpulse candidates in the list (device scalar, WfsScal::n_ap_candidates)
     struct ApSeg *seg; i64 n_seg;   // candidates of a k_s2_tile workgroup: one contiguous, key-ordered stretch of the list per tile (k_ap_seg)
     struct ApCand *cand;            // [cap] candidates of the generator (k_ap_finish turns entry i into afterpulse photon i, or a hole: ap_ch[i] = -1)
 };
@@ -2443,7 +2442,7 @@ __global__ void k_set_bases(GenArgs a)
     i64 run = 0;
     for (i64 q = a.set_ins_off[s]; q < a.set_ins_off[s + 1]; q++) {
         const i32 i = a.set_ins_list[q];
-        if (run > 0xffffffffLL) atomicMax(&a.scal[1], (i64)2);
+        if (run > 0xffffffffLL) atomicMax(&a.scal->error, (i64)WFS_DEV_TIME_RANGE);
         a.ins_sbase[i] = (u32)run;
         a.ins_fullsort[i] = a.set_ins_off[s + 1] - a.set_ins_off[s] > 1;       // (k_block_emitters adds the instructions with a generic block in their middle)
         run += a.em_ph_off[a.em_off[i + 1]] - a.em_ph_off[a.em_off[i]];
@@ -2476,7 +2475,7 @@ __device__ __forceinline__ double ap_uniform(const WfsDev &d, const ApCand &q, c
 }
 __device__ __forceinline__ u32x4 ap_call(const WfsDev &d, const ApCand &q) { return philox4x32_10(q.j, q.gid, q.m, SITE_AP + (u32)(q.e_dpe & 0xff), d.k0, d.k1); }
 __device__ __forceinline__ bool ap_accept(const WfsDev &d, const ApArgs &ap, const ApCand &q, const u32x4 &w) { return ap_uniform(d, q, w) <= ap.prob[q.e_dpe & 0xff][q.ch]; }
-__device__ __forceinline__ void ap_finish(const WfsDev &d, i64 *scal, const ApArgs &ap, const ApCand &q, const u32x4 &w, i64 gk)
+__device__ __forceinline__ void ap_finish(const WfsDev &d, WfsScal *scal, const ApArgs &ap, const ApCand &q, const u32x4 &w, i64 gk)
 {
     const int e = q.e_dpe & 0xff;
     const ApElemDev &el = ap.el[e];
@@ -2494,7 +2493,7 @@ __device__ __forceinline__ void ap_finish(const WfsDev &d, i64 *scal, const ApAr
     }
     const double tf = (double)(q.itime + q.t) + delay;          // afterpulse.py:235, int64 + float
     i64 tap = (i64)tf - q.itime;
-    if (tap > 0x7fffffffLL || tap < -0x7fffffffLL) { atomicMax(&scal[1], (i64)2); tap = 0; }
+    if (tap > 0x7fffffffLL || tap < -0x7fffffffLL) { atomicMax(&scal->error, (i64)WFS_DEV_TIME_RANGE); tap = 0; }
     if (gk < ap.cap) { ap.ap_ins[gk] = q.ins; ap.ap_ch[gk] = q.ch; ap.ap_t[gk] = (i32)tap; ap.ap_gain[gk] = d.gains[q.ch] * amp; ap.ap_key[gk] = q.key; }
 }
 // a candidate into the block's LDS list (or, past AP_STAGE, straight to the end)
@@ -3231,7 +3230,7 @@ __global__ __launch_bounds__(FILL_TPB) void k_photon_fill(WfsDev d, GenArgs a, A
             // the block's own emitters only (slot nwin - 1 is the sentinel behind them); I64_MIN: an electron that did not survive (no photons)
             i64 wt = (k < nwin - 1) ? a.em_time[bd.e_lo + k] : I64_MIN;
             wt = wt == I64_MIN ? 0 : wt - itime;
-            if (wt > 0x3fffffffLL || wt < -0x3fffffffLL) atomicMax(&a.scal[1], (i64)2);      // emitter further than 2^30 ns from its set's origin
+            if (wt > 0x3fffffffLL || wt < -0x3fffffffLL) atomicMax(&a.scal->error, (i64)WFS_DEV_TIME_RANGE);      // emitter further than 2^30 ns from its set's origin
             wtime[k] = (i32)wt;
         }
         __syncthreads();                                     // hist is complete
@@ -3333,7 +3332,7 @@ __global__ __launch_bounds__(FILL_TPB) void k_photon_fill(WfsDev d, GenArgs a, A
                 t += (i64)s1_propagation(a, ch >= d.n_top, a.ins_pzi[ins], a.ins_pzf[ins], X.x);
             }
             if (EXT && a.gg_inv && a.ins_gg[ins] >= 0) t += (i64)(gg_time(a, a.ins_gg[ins], a.ins_ggw[ins], photon_word(d, id, SITE_LUM)) - gg_mean(a, ins));
-            if (t > 0x7fffffffLL || t < -0x7fffffffLL) { atomicMax(&a.scal[1], (i64)2); t = 0; }
+            if (t > 0x7fffffffLL || t < -0x7fffffffLL) { atomicMax(&a.scal->error, (i64)WFS_DEV_TIME_RANGE); t = 0; }
             if (AP) ap_generate(d, ap, aps, id.j, id.gid, id.m, set, ch, (code >> 16) != 0, itime, t, a.ins_sbase[ins] + id.P);
             atomicMin(&a.tile_tmin[tile], (i32)t); atomicMax(&a.tile_tmax[tile], (i32)t);
             // photons of multi-instruction blocks take the first slots of their tile (k_block_ranges starts behind them)
@@ -3469,9 +3468,9 @@ __global__ __launch_bounds__(256) void k_ap_seg(WfsDev d, GenArgs a, ApArgs ap, 
 #define TILE_ORDER_INLINE 12        // ranges up to this many photons are sorted by the scanning thread itself
 struct OrderRange { i64 start; i32 n, pad; };          // photons [start, start + n) of the photon array
 struct OrderArgs { i64 n_tiles, n_ptiles; const i32 *tile_count; const i64 *tile_off; PhotonRec *ph; u32 *ph_idx; double *ph_gain; i64 gain_first;
-                   OrderRange *wave_list, *big_list; i64 *scal;      // ph_gain[p - gain_first] for photons p >= gain_first (afterpulses), or nullptr;
-                                                                     // scal[30] / scal[31]: ranges on the wave list / the workgroup list; ranges beyond
-                                                                     // TILE_ORDER_MAX photons: big_list[2 n_tiles - 1 - k], scal[19] of them
+                   OrderRange *wave_list, *big_list; WfsScal *scal;  // ph_gain[p - gain_first] for photons p >= gain_first (afterpulses), or nullptr;
+                                                                     // scal->n_order_wave / n_order_big: ranges on the wave list / the workgroup list; ranges beyond
+                                                                     // TILE_ORDER_MAX photons: big_list[2 n_tiles - 1 - k], scal->n_order_huge of them
                    const i32 *skip_ins; i32 nch;                     // [n_ins] 1: the tiles of this instruction (tile / nch) come from k_s2_tile, already in order (or nullptr)
                    const i32 *tile_cursor, *tile_tailbase; const i32 *ins_fullsort; const i64 *set_ins_off; const i32 *set_ins_list; };
                    // primary tiles of a set whose (first) instruction is not flagged ins_fullsort: head = [0, cursor), tail = [tailbase, n)
@@ -3523,7 +3522,10 @@ __global__ __launch_bounds__(256) void k_tile_order_scan(OrderArgs a)
         }
     }
     __syncthreads();
-    if (threadIdx.x < 3 && s_n[threadIdx.x]) s_base[threadIdx.x] = (i64)atomicAdd((u64 *)&a.scal[threadIdx.x < 2 ? 30 + threadIdx.x : 19], (u64)s_n[threadIdx.x]);
+    if (threadIdx.x < 3 && s_n[threadIdx.x]) {
+        i64 *const counter = threadIdx.x == 0 ? &a.scal->n_order_wave : (threadIdx.x == 1 ? &a.scal->n_order_big : &a.scal->n_order_huge);
+        s_base[threadIdx.x] = (i64)atomicAdd((u64 *)counter, (u64)s_n[threadIdx.x]);
+    }
     __syncthreads();
     for (int q = 0; q < 2; q++) {
         if (cls[q] == 0) a.wave_list[s_base[0] + rk[q]] = rg[q];
@@ -3643,13 +3645,13 @@ __global__ void k_photon_times(WfsDev d, GenArgs a, i64 n, const i64 *index, i64
 // side of the ABI; what is left of Pulse.__call__ before add_current is drawn here per photon: transit time spread
 // (pulse.py:53-56), double-PE flag (pulse.py:76-79) and the SPE gain indices (pulse.py:97-103): one Philox call.  One thread per tile.
 struct OpticalArgs { i64 n_tiles; const i32 *tile_count; const i64 *tile_off; i32 *tile_tmin, *tile_tmax; const u32 *set_gid;
-                     const i32 *in_t; const u32 *in_item; PhotonRec *ph; i64 *scal; };
+                     const i32 *in_t; const u32 *in_item; PhotonRec *ph; WfsScal *scal; };
 
 // Bucketing of the supplied photons by (instruction, channel) -- one thread per instruction, which owns the instruction's tiles
 // (plain read-modify-write).  The host used to do this over dense per-tile arrays: 0.4 s of 0.5 s per 4 x 10^5 nVeto instructions.
 // rawdata.py:485-486: photons with a negative time or beyond the cutoff are dropped; pulse.py:89-90: so are those of turned-off PMTs.
 struct OptLoadArgs { i64 n; const i32 *first, *last, *channels; const i64 *timings; i64 cutoff; const double *gains;
-                     i32 *tile_count; const i64 *tile_off; i32 *tile_cursor; i32 *in_t; u32 *in_item; i64 *scal; };
+                     i32 *tile_count; const i64 *tile_off; i32 *tile_cursor; i32 *in_t; u32 *in_item; WfsScal *scal; };
 
 template <bool PLACE>
 __global__ void k_optical_bucket(WfsDev d, OptLoadArgs a)
@@ -3661,9 +3663,9 @@ __global__ void k_optical_bucket(WfsDev d, OptLoadArgs a)
         const i64 t = a.timings[k];
         if (t < 0 || t >= a.cutoff) continue;
         const i32 ch = a.channels[k];
-        if (ch < 0 || ch >= d.n_tpc) { atomicMax(&a.scal[20], (i64)1); continue; }      // photon channel out of range
+        if (ch < 0 || ch >= d.n_tpc) { atomicMax(&a.scal->opt_error, (i64)WFS_DEV_OPT_CHANNEL); continue; }      // photon channel out of range
         if (a.gains[ch] == 0) continue;
-        if (t > 0x7ffffff0LL) { atomicMax(&a.scal[20], (i64)2); continue; }              // photon time beyond 2^31 ns
+        if (t > 0x7ffffff0LL) { atomicMax(&a.scal->opt_error, (i64)WFS_DEV_OPT_TIME); continue; }              // photon time beyond 2^31 ns
         const i64 tile = i * d.n_tpc + ch;
         if (!PLACE) a.tile_count[tile]++;
         else { const i64 pos = a.tile_off[tile] + a.tile_cursor[tile]++; a.in_t[pos] = (i32)t; a.in_item[pos] = (u32)(k - f); }
@@ -3684,7 +3686,7 @@ __global__ void k_optical_finish(WfsDev d, OpticalArgs a)
         const u32x4 B = philox4x32_10(0, gid, item, SITE_PH, d.k0, d.k1);
         i64 t = a.in_t[off + p];
         t += alias_sample(d.tab_tts, B.x);
-        if (t > 0x7fffffffLL || t < -0x7fffffffLL) { atomicMax(&a.scal[1], (i64)2); t = 0; }
+        if (t > 0x7fffffffLL || t < -0x7fffffffLL) { atomicMax(&a.scal->error, (i64)WFS_DEV_TIME_RANGE); t = 0; }
         a.ph[off + p] = PhotonRec{(i32)t, gain_code(B.y, d.thr_dpe, d.dpe_inv)};
         tmin = (i32)t < tmin ? (i32)t : tmin; tmax = (i32)t > tmax ? (i32)t : tmax;
     }
