@@ -5,6 +5,7 @@ Run once in the build container (needs /root/reference; the GPU box never runs t
 
     python tests/golden/make_golden.py
     python tests/golden/make_golden.py optical_chain pmt_ap_draws     # these two write their own files only
+    python tests/golden/make_golden.py pulse_edges                    # so does this one: the reference on designed photon lists
 
 The reference's hot-path modules are imported under the stubs of ``_ref_stubs.py`` (identity njit, so
 every draw comes from numpy's seeded global generator).  What is written is DATA only: inputs and
@@ -282,6 +283,13 @@ def record_chain(ref, rd, instructions, seed, truth_dtype, store_currents=False,
     out = dict(instructions=instructions, seed=np.int64(seed))
     if secondaries is not None:
         out['secondaries'] = np.concatenate(secondaries) if secondaries else np.zeros(0, dtype=instructions.dtype)
+    flatten_recorder(rec, out, store_currents=store_currents, store_entry=store_entry)
+    out['truth'] = truth[truth['fill']]
+    return out
+
+
+def flatten_recorder(rec, out, store_currents=False, store_entry=False):
+    """what the Recorder saw as flat arrays, added to out: call_*, ph_*, e_t, call_truth_*, pl_*, dg_*, row_*, zle_*"""
     calls = rec.calls
     if store_entry:
         out['call_in_off'] = np.concatenate([[0], np.cumsum([len(c['in_t']) for c in calls])]).astype(np.int64)
@@ -333,7 +341,6 @@ def record_chain(ref, rd, instructions, seed, truth_dtype, store_currents=False,
     out['zle_data_off'] = np.concatenate([[0], np.cumsum([len(x[4]) for x in z])]).astype(np.int64)
     out['zle_data'] = np.concatenate([x[4] for x in z] + [np.zeros(0, np.int64)]).astype(np.int32)
     assert np.all(out['zle_data'] == np.concatenate([x[4] for x in z] + [np.zeros(0, np.int64)]))
-    out['truth'] = truth[truth['fill']]
     return out
 
 
@@ -686,6 +693,108 @@ def fixture_pmt_ap_draws(ref):
     print('all_m10', 'parents', int(single.sum() + double.sum()), 'afterpulses', len(t))
     out['cases'] = np.array(names)
     np.savez_compressed(HERE + '/pmt_ap_draws.npz', **out)
+
+
+def pulse_edges_geometry_overrides():
+    """the geometry of chain I; the stored samples and the trigger window stay those of the bundled configuration"""
+    return dict(sample_duration=5, samples_before_pulse_center=3, samples_after_pulse_center=37)
+
+
+def run_pulse_edges(ref, config, builder, seed):
+    """The reference below the photon generators: per case one Pulse.__call__ with preassigned gains (pulse.py:53 skips the transit-time
+    draw, pulse.py:105-107 takes the gains as given), its _pulses handed to a RawData's _pulses_cache, and per group one
+    digitize_pulse_cache() + ZLE() (rawdata.py:204-311), all under the Recorder.  Returns the flat arrays of record_chain plus the
+    explicit pulse sets (set_cluster, set_tmin), the case / group names and the call -> case / group indices."""
+    ref.load_resource._cached_configs.clear()
+    ref.pulse._cached_pmt_current_templates.clear()
+    ref.pulse._cached_uniform_to_pe_arr.clear()
+    config = dict(config, enable_noise=False)
+    pulse = ref.pulse.Pulse(config)
+    rd = ref.rawdata.RawData(config)
+    rd._pulses_cache = []
+    rng = np.random.default_rng(seed)
+    rec = Recorder(ref)
+    rec.install()
+    np.random.seed(seed)          # (Pulse.__call__ still draws the double-PE flags, which a call with preassigned gains never reads)
+    try:
+        for gi in range(len(builder.groups)):
+            for case in builder.cases:
+                if case['group'] != gi:
+                    continue
+                t, ch, g = [], [], []
+                for times, gains, channel in case['tiles']:
+                    if gains is None:
+                        gains = rng.uniform(1e6, 3e6, len(times))
+                    elif callable(gains):
+                        gains = gains(rng, times)
+                    t.append(times); ch.append(np.full(len(times), channel, dtype=np.int64)); g.append(np.asarray(gains, dtype=np.float64))
+                pulse._photon_timings = np.concatenate(t).astype(np.int64)
+                pulse._photon_channels = np.concatenate(ch)
+                pulse._photon_gains = np.concatenate(g)
+                assert np.all(np.diff(pulse._photon_channels) >= 0)
+                pulse()
+                rd._pulses_cache += pulse._pulses
+            rd.digitize_pulse_cache()
+            for c, left, right, data in rd.ZLE():
+                rec.zle.append((len(rec.digits) - 1, int(c), int(left), int(right), np.array(data, dtype=np.int64)))
+    finally:
+        rec.uninstall()
+    assert len(rec.digits) == len(builder.groups)
+    out = dict(seed=np.int64(seed))
+    flatten_recorder(rec, out, store_currents=True)
+    out['set_cluster'] = np.array([c['group'] for c in builder.cases], dtype=np.int32)
+    out['set_tmin'] = np.array([c['set_tmin'] for c in builder.cases], dtype=np.int64)
+    out['case_names'] = np.array([c['name'] for c in builder.cases])
+    out['call_case'] = np.arange(len(builder.cases), dtype=np.int32)
+    out['group_names'] = np.array(builder.groups)
+    out['call_group'] = out['set_cluster'].copy()
+    return out, pulse
+
+
+def fixture_pulse_edges(ref):
+    """pulse_edges.npz / pulse_edges_geometry.npz: the reference on photon lists designed to sit on every boundary of the HIP pulse
+    kernels (tests/pulse_edges.py holds the case table).  No sample of any pulse may lie near a rounding tie (exact rational
+    arithmetic, tests/pulse_edges.py: fixture_exact): the random gains are redrawn with the next seed until none is within 4 B."""
+    from fractions import Fraction
+    from tests import pulse_edges as PE
+    for name, overrides, make_cases, seed0 in [('pulse_edges.npz', {}, PE.main_cases, 5101),
+                                               ('pulse_edges_geometry.npz', pulse_edges_geometry_overrides(), PE.geometry_cases, 5201)]:
+        cfg = base_config(**overrides)
+        ref.load_resource._cached_configs.clear()
+        ref.pulse._cached_pmt_current_templates.clear()
+        p = ref.pulse.Pulse(dict(cfg))
+        dt = int(cfg['sample_duration'])
+        templates, c2a = np.array(p._pmt_current_templates), float(p.current_2_adc)
+        ties = PE.find_ties(templates, c2a)
+        assert set(ties) == {'even', 'odd'}, ties
+        thr_gain = PE.truth_threshold_gain(p.current_max, c2a, cfg['zle_threshold'])
+        for seed in range(seed0, seed0 + 20):
+            builder = make_cases(thr_gain, ties)
+            out, pulse = run_pulse_edges(ref, cfg, builder, seed)
+            exact = PE.fixture_exact(out, templates, c2a, dt)
+            # the designed ties: the peak sample of the two single-photon pulses
+            names = [str(out['case_names'][k]) for k in out['call_case']]
+            skip, tie_pulse, tie_sample, tie_k = set(), [], [], []
+            for kind in ('even', 'odd'):
+                j = int(out['call_pulse_off'][names.index('e_tie_' + kind)])
+                cur = out['pl_current'][out['pl_cur_off'][j]:out['pl_cur_off'][j + 1]]
+                s = int(np.argmax(cur))
+                assert cur[s] * np.float64(c2a) == ties[kind][0] + 0.5 and exact[j]['dist'][s] < Fraction(1, 10 ** 9)
+                skip.add((j, s)); tie_pulse.append(j); tie_sample.append(s); tie_k.append(ties[kind][0])
+            bad, ratio, dist = PE.near_ties(exact, skip)
+            print(name, 'seed', seed, 'near ties', len(bad), 'smallest distance', float(dist), '= %.3g B' % float(ratio))
+            if not bad:
+                break
+        else:
+            raise RuntimeError('no seed without a near tie')
+        out['min_tie_distance'] = np.float64(float(dist))
+        out['min_tie_distance_over_B'] = np.float64(float(ratio))
+        out['tie_pulse'], out['tie_sample'], out['tie_k'] = (np.array(x, dtype=np.int64) for x in (tie_pulse, tie_sample, tie_k))
+        out['templates'], out['current_2_adc'] = templates, np.float64(c2a)
+        np.savez_compressed(HERE + '/' + name, **out)
+        print(name, len(out['call_kind']), 'calls', len(out['pl_ch']), 'pulses', len(out['ph_t']), 'photons', len(out['dg_left']), 'windows')
+    with open(HERE + '/pulse_edges_geometry_config.json', 'w') as f:
+        json.dump(pulse_edges_geometry_overrides(), f)
 
 
 class StubDelayHist:
@@ -1269,12 +1378,14 @@ def fixture_chain_stats(ref):
 if __name__ == '__main__':
     which = sys.argv[1:] or ['tables', 'add_current', 'chains', 'dists', 'models', 'stats', 'chunker', 'ele_ap_draws', 'gas_gap', 'aft_sigma', 'noise_float', 'diffusion', 'frontend']
     ref = import_reference_interface() if ('chunker' in which or 'frontend' in which) else import_reference()
-    own = {'optical_chain', 'pmt_ap_draws'}           # these write their own files only
+    own = {'optical_chain', 'pmt_ap_draws', 'pulse_edges'}           # these write their own files only
     p = fixture_tables(ref) if set(which) - own else None
     if 'optical_chain' in which:
         fixture_chain_optical(ref)
     if 'pmt_ap_draws' in which:
         fixture_pmt_ap_draws(ref)
+    if 'pulse_edges' in which:
+        fixture_pulse_edges(ref)
     if 'add_current' in which:
         fixture_add_current(ref, p)
     if 'chains' in which:

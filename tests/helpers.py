@@ -13,10 +13,13 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
 
 # Pulse.add_current with fused multiply-adds (config 'fused_multiply_add', the default of the HIP path; wfs_config.fma): every
-# term template * gain is added to the current with one rounding instead of numpy's two.  A sample sums at most tlen x (photons in
-# reach) terms; the two forms differ by at most half an ulp of the running sum per term, so by a few ulp of the tile maximum at the
-# end.  Tolerance of the golden comparisons in that mode (measured maximum on the golden chains: 2 ulp); everything downstream of the
-# per-pulse rounding (rows, ZLE intervals, records) is asserted EQUAL in both modes.
+# term template * gain is added to the current with one rounding instead of numpy's two.  What is shown about the currents of that form:
+#   * on the golden chains they stay within FMA_CURRENT_TOL_ULP ulp of the tile maximum of the reference's (asserted; measured maximum
+#     there: 2 ulp) -- a tolerance of THESE comparisons, not a bound for any input;
+#   * for any input, per sample: |current - exact| <= gamma(n + 1) * sum |template * gain| over the n terms that reach the sample
+#     (derived; tests/pulse_edges.py: fixture_exact), asserted on the designed fixtures pulse_edges*.npz, where the measured maximum
+#     distance from the reference's currents is 2 ulp of the tile maximum (3 ulp with 5 ns samples and 40-sample templates).
+# Everything downstream of the per-pulse rounding (rows, ZLE intervals, records) is asserted EQUAL in both modes.
 FMA_CURRENT_TOL_ULP = 8
 
 
@@ -47,6 +50,18 @@ def geometry_chain_config():
     """the config of golden chain I (make_golden.py: geometry_overrides): 5 ns samples, 3 + 37 template samples"""
     import json
     return xenonnt_test_config(**json.load(open(os.path.join(GOLDEN, 'chain_geometry_config.json'))))
+
+
+PULSE_EDGES = ['pulse_edges.npz', 'pulse_edges_geometry.npz']
+
+
+def pulse_edges_config(name):
+    """the configs of the designed-photon fixtures (make_golden.py pulse_edges): the bundled one, and chain I's sample duration and
+    template length with the bundled stored samples and trigger window"""
+    import json
+    if name == 'pulse_edges.npz':
+        return xenonnt_test_config()
+    return xenonnt_test_config(**json.load(open(os.path.join(GOLDEN, 'pulse_edges_geometry_config.json'))))
 
 
 OPTICAL_CHAINS = dict(main='chain_optical.npz', cutoff='chain_optical_cutoff.npz')
@@ -160,7 +175,12 @@ def chain_sets(d, config):
 
 
 def replay_chain_on_engine(eng, d, config, debug=True, force_dense=False):
-    set_cluster, set_tmin = chain_sets(d, config)
+    """d: a golden chain, or a fixture (or a subset of one, tests/pulse_edges.py: subset) that carries its pulse sets itself"""
+    if 'set_cluster' in d:
+        set_cluster, set_tmin = np.asarray(d['set_cluster'], np.int32), np.asarray(d['set_tmin'], np.int64)
+        set_cluster = set_cluster - set_cluster.min()
+    else:
+        set_cluster, set_tmin = chain_sets(d, config)
     eng.set_debug(debug, force_dense)
     dpe = np.array(d['ph_dpe'], dtype=np.uint8)
     for k in np.where(d['call_has_gains'])[0]:        # pre-assigned gains: n_double_pe = 0 (pulse.py:105-106)

@@ -30,9 +30,11 @@ def _check_chain(name, config, force_dense=False, noise_offsets=False):
     return _check_chain_mode(name, with_fma(config, True), force_dense, noise_offsets)
 
 
-def _check_chain_mode(name, config, force_dense=False, noise_offsets=False):
-    d = golden(name)
-    eng = make_engine(config)
+def _check_chain_mode(name, config, force_dense=False, noise_offsets=False, d=None, eng=None, currents=None):
+    """d: the fixture's arrays instead of the golden chain `name` (a fixture that carries its pulse sets, or a subset of its calls:
+    tests/pulse_edges.py); eng: an engine to reuse; currents(p, order): the current comparison instead of the one below"""
+    d = golden(name) if d is None else d
+    eng = make_engine(config) if eng is None else eng
     counts = replay_chain_on_engine(eng, d, config, force_dense=force_dense)
     if noise_offsets:
         # the reference drew its noise start index from numpy's stream: inject it per digitise window
@@ -48,7 +50,9 @@ def _check_chain_mode(name, config, force_dense=False, noise_offsets=False):
     assert np.array_equal(p['left'][order], d['pl_left'])
     assert np.array_equal(p['right'][order], d['pl_right'])
     assert np.array_equal(p['n_photons'][order], d['pl_photons'])
-    if 'pl_current' in d:
+    if currents is not None:
+        currents(p, order)
+    elif 'pl_current' in d:
         for j, k in enumerate(order):
             cur = p['current'][p['cur_off'][k]:p['cur_off'][k] + p['right'][k] - p['left'][k] + 1]
             ref = d['pl_current'][d['pl_cur_off'][j]:d['pl_cur_off'][j + 1]]

@@ -1827,7 +1827,10 @@ static int run_pulses(wfs_handle *h, RunState &r)
         PulseArgs pd = pa;
         pd.desc = h->tile_desc.as<TileDesc>() + r.first_dense;
         if (pd.cur_off) pd.cur_off += r.first_dense;
-        size_t lds = (size_t)(256 + d.tlen - 1) * d.dt * 8 + (size_t)d.dt * d.tlen * 8 + 4 * 8 * 8 + 64;
+        // two H tables (order-independent merge of the gains of one cell) where they fit, one otherwise
+        const size_t h_bytes = (size_t)(256 + d.tlen - 1) * d.dt * 8, rest = (size_t)d.dt * d.tlen * 8 + 4 * 8 * 8 + 64;
+        pd.n_win = (2 * h_bytes + rest + 15) / 16 * 16 <= 128 * 1024 ? 1 : 0;
+        size_t lds = (pd.n_win ? 2 : 1) * h_bytes + rest;
         lds = (lds + 15) / 16 * 16;
         if (lds > 128 * 1024) return h->fail(WFS_E_CAPACITY, "sample_duration x template length too large for the LDS tables of k_pulse_generic");
         Timer t(h, "k_pulse_generic");
@@ -1844,7 +1847,10 @@ static int run_pulses(wfs_handle *h, RunState &r)
         const int NWIN_MAX = 8;
         // tiles that fit one register batch: one workgroup per tile walks the chunks with the photons resident in
         // registers; longer tiles: several workgroups per tile (each re-reads the tile's photons for its chunks)
-        pd.n_win = (h->max_tile_dense <= (i64)tpb * DENSE_PPT) ? 1 : (int)std::min<i64>(NWIN_MAX, std::max<i64>(1, (n_live_max + tpb - 1) / tpb));
+        // (the resident form holds at most tpb x DENSE_PPT photons: a longer tile must take the windowed form even when its live samples
+        // fit one chunk and n_win comes out as 1 -- choosing the form by n_win dropped the photons behind the register batch)
+        const bool resident = h->max_tile_dense <= (i64)tpb * DENSE_PPT;
+        pd.n_win = resident ? 1 : (int)std::min<i64>(NWIN_MAX, std::max<i64>(1, (n_live_max + tpb - 1) / tpb));
         pd.W = tpb;
         const TemplateArg tp = fill_template_arg(h);
         size_t lds = (size_t)(tpb + d.tlen - 1) * d.dt * 8 + (size_t)8 * (tpb / 64) * 8 + 64 + TAP_LDS_BYTES(256) + 16;
@@ -1853,7 +1859,7 @@ static int run_pulses(wfs_handle *h, RunState &r)
         pd.spe_lds = ((size_t)(tpb + d.tlen - 1) * d.dt >= 2001) ? 1 : 0;
         const unsigned grid = (unsigned)(h->n_dense_tiles * pd.n_win);
         Timer t(h, "k_pulse_dense");
-        if (pd.n_win == 1) {
+        if (resident) {
             if (small) WFS_LAUNCH_F(h, K_PULSE_128_RES, dim3(grid), dim3(128), lds, d, pd, tp);
             else WFS_LAUNCH_F(h, K_PULSE_256_RES, dim3(grid), dim3(256), lds, d, pd, tp);
         } else {

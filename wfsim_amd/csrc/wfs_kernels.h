@@ -848,8 +848,15 @@ __global__ __launch_bounds__(TPB) void k_pulse_generic(WfsDev d, PulseArgs a)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int dt = d.dt, tlen = d.tlen;
     const int HROWS = TPB + tlen - 1;
+    // The gains of one (start bin, ns) cell are merged by atomic adds, whose order changes from run to run.  So that the merged gain does
+    // not depend on it, every gain is split at a power of two `grid` (2^-20 of the tile's largest gain): the multiples of grid add up
+    // EXACTLY in H (below 2^53 grid for any photon number), the remainders (below grid / 2) in Hlo, and the cell is their sum, rounded
+    // once -- for one or two photons numpy's value bit for bit (pulse.py:313), for more the correctly rounded sum up to 2^-23 n ulp.
     double *H = (double *)smem;                           // [HROWS][dt]
-    double *T = H + (size_t)HROWS * dt;                   // [dt][tlen] templates
+    // (a.n_win == 0: geometries whose two tables would not fit the LDS keep one table and the plain atomic merge)
+    const bool split = a.n_win != 0;
+    double *Hlo = H + (size_t)HROWS * dt;                 // [HROWS][dt]
+    double *T = H + (size_t)HROWS * dt * (split ? 2 : 1); // [dt][tlen] templates
     double *red = T + (size_t)dt * tlen;                  // [TPB / 64][8]
     __shared__ double s_cmax[WFS_MAX_DT];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -864,25 +871,38 @@ __global__ __launch_bounds__(TPB) void k_pulse_generic(WfsDev d, PulseArgs a)
     const double *spe_row = d.spe + (size_t)(d.n_spe > 1 ? td.ch : 0) * 2001;
     const i64 rel0 = td.rel0;
     const i64 n_live = nb + (tlen - 1);
-    // number of DPE photons of the tile (truth quirk pulse.py:255)
-    __shared__ i32 s_ndpe;
-    if (tid == 0) s_ndpe = 0;
+    auto gain_of = [&](const PhotonRec &rec, i32 p) -> double {
+        if (td.mode != 0) return a.ph_gain[off + p];
+        double g = G * spe_row[rec.code & 0xffffu];                 // pulse.py:97-98
+        if (rec.code >> 16) g += G * spe_row[rec.code >> 16];       // pulse.py:101-103
+        return g;
+    };
+    // number of DPE photons of the tile (truth quirk pulse.py:255) and the exponent field of its largest gain
+    __shared__ i32 s_ndpe, s_emax;
+    if (tid == 0) { s_ndpe = 0; s_emax = 0; }
     __syncthreads();
     {
-        i32 c = 0;
-        for (i32 p = tid; p < n; p += TPB) c += (a.ph[off + p].code >> 16) != 0;
-        c = wave_sum(c);
+        i32 c = 0, em = 0;
+        for (i32 p = tid; p < n; p += TPB) {
+            const PhotonRec rec = a.ph[off + p];
+            c += (rec.code >> 16) != 0;
+            em = max(em, (i32)((__double_as_longlong(gain_of(rec, p)) >> 52) & 0x7ff));
+        }
+        c = wave_sum(c); em = wave_max(em);
         if (lane == 0 && c) atomicAdd(&s_ndpe, c);
+        if (lane == 0) atomicMax(&s_emax, em);
     }
     __syncthreads();
     const i32 n_dpe_tile = s_ndpe;
+    const int gf = min(max(s_emax - 20, 1), 2045);
+    const double grid = __longlong_as_double((long long)gf << 52), inv_grid = __longlong_as_double((long long)(2046 - gf) << 52);
     double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // n, n_dpe, n_trig, n_trig_dpe, sum g, sum g trig, sum t, sum t^2
     if (a.currents) for (i64 sz = tid; sz < td.L; sz += TPB) if (sz < lead || sz >= lead + n_live) a.currents[a.cur_off[blockIdx.x] + sz] = 0.0;
     for (i64 c0 = 0; c0 < n_live; c0 += TPB) {
         const bool first = c0 == 0;
         const i64 b_lo = c0 - (tlen - 1);
         __syncthreads();
-        for (int i = tid; i < HROWS * dt; i += TPB) H[i] = 0.0;
+        for (int i = tid; i < (split ? 2 : 1) * HROWS * dt; i += TPB) H[i] = 0.0;           // (H and Hlo)
         __syncthreads();
         for (i32 p = tid; p < n; p += TPB) {
             const PhotonRec rec = a.ph[off + p];
@@ -891,10 +911,12 @@ __global__ __launch_bounds__(TPB) void k_pulse_generic(WfsDev d, PulseArgs a)
             const i64 jw = bin - b_lo;
             const bool mine = jw >= 0 && jw < HROWS;
             if (!first && !mine) continue;
-            double gain;
-            if (td.mode != 0) gain = a.ph_gain[off + p];
-            else { gain = G * spe_row[rec.code & 0xffffu]; if (rec.code >> 16) gain += G * spe_row[rec.code >> 16]; }      // pulse.py:97-103
-            if (mine) atomicAdd(&H[(int)jw * dt + r], gain);
+            const double gain = gain_of(rec, p);
+            if (mine && split) {
+                const double hi = rint(gain * inv_grid) * grid;
+                atomicAdd(&H[(int)jw * dt + r], hi);
+                atomicAdd(&Hlo[(int)jw * dt + r], gain - hi);
+            } else if (mine) atomicAdd(&H[(int)jw * dt + r], gain);
             if (first) {
                 const bool above = gain * s_cmax[r] * d.c2a > thr;
                 acc[0] += 1; acc[1] += (rec.code >> 16) != 0; acc[4] += gain;
@@ -904,6 +926,10 @@ __global__ __launch_bounds__(TPB) void k_pulse_generic(WfsDev d, PulseArgs a)
             }
         }
         __syncthreads();
+        if (split) {                                       // block-uniform
+            for (int i = tid; i < HROWS * dt; i += TPB) H[i] += Hlo[i];
+            __syncthreads();
+        }
         if (c0 + tid < n_live) {
             // sample c0 + tid sees the start bins (rows) tid (tap tlen - 1) .. tid + tlen - 1 (tap 0), ascending time (pulse.py:303-318)
             double c = 0.0;
