@@ -344,6 +344,14 @@ int wfs_set_noise_offsets(wfs_handle *h, const int64_t *ix_rand, int64_t n);
 int wfs_set_noise_float(wfs_handle *h, const double *noise, int32_t noise_len, int32_t noise_channels);
 int wfs_set_stream(wfs_handle *h, void *hip_stream);
 int wfs_synchronize(wfs_handle *h);
+/* Tiles of tile-generated S2s above 2048 photons whose H table fits the LDS of one workgroup are drawn and turned into their pulse by
+ * one kernel, without a photon array (k_s2_bright; config 'tile_local_bright').  on = 0: they take the generation-only kernel and the
+ * dense pulse kernel, as every bright tile that does not fit.  Results do not depend on it.  Default: on. */
+int wfs_set_bright_tiles(wfs_handle *h, int32_t on);
+/* Which kernel made every primary (pulse set, channel) tile of the last wfs_run, indexed set * n_tpc + channel: 0 no photons or not
+ * tile-generated, 1 photons and pulse in one workgroup (up to 2048 photons), 2 generation only + the pulse kernels, 3 k_s2_bright.
+ * capacity: entries the buffer holds (>= n_run_sets * n_tpc). */
+int wfs_copy_tile_kernels(wfs_handle *h, int8_t *kind, int64_t capacity);
 /* HIP-event timing of the kernels of the last wfs_run: names (NUL separated) and milliseconds */
 int wfs_kernel_times(wfs_handle *h, char *names, int64_t names_cap, float *ms, int32_t *n_launches, int32_t *n_kernels);
 int wfs_set_profiling(wfs_handle *h, int32_t on);

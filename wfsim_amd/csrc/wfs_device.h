@@ -272,13 +272,15 @@ struct WfsScal {
     i64 n_res_tiles;        // tiles of the resident rows.  scan of res_cnt -> host
     i64 n_res_samples;      // samples of the resident rows.  k_row_len -> host (wfs_get_counts)
     i64 n_long_rows;        // resident rows longer than RES_SHORT_LEN.  k_row_len -> host
-    i64 reserved_[26];
+    i64 n_bright_tiles;     // tiles of k_s2_bright, listed from FuseArgs::tiles[n_list].  k_tile_counts -> host
+    i64 max_bright_bins;    // most start bins the H table of a tile above TILE_MAX_PHOTONS could need, whichever kernel takes it.  k_tile_counts -> host (WFS_BRIGHT_STATS)
+    i64 reserved_[24];
 };
 static_assert(sizeof(WfsScal) == 512, "WfsScal: 64 slots of 8 bytes");
 #define WFS_SCAL_SLOT(m, slot) static_assert(offsetof(WfsScal, m) == 8 * (slot), "WfsScal::" #m " moved: the layout is frozen")
 WFS_SCAL_SLOT(error, 1); WFS_SCAL_SLOT(n_front_rows, 2); WFS_SCAL_SLOT(n_sparse_tiles, 3); WFS_SCAL_SLOT(n_dense_tiles, 11);
 WFS_SCAL_SLOT(n_tiny_tiles, 16); WFS_SCAL_SLOT(n_wave_tiles, 17); WFS_SCAL_SLOT(key_origin, 22); WFS_SCAL_SLOT(key_end, 29);
-WFS_SCAL_SLOT(n_ap_candidates, 13); WFS_SCAL_SLOT(n_order_huge, 19); WFS_SCAL_SLOT(n_long_rows, 37);
+WFS_SCAL_SLOT(n_ap_candidates, 13); WFS_SCAL_SLOT(n_order_huge, 19); WFS_SCAL_SLOT(n_long_rows, 37); WFS_SCAL_SLOT(n_bright_tiles, 38);
 #undef WFS_SCAL_SLOT
 
 // Everything a kernel needs, passed by value (fits the kernarg segment).

@@ -13,6 +13,8 @@
 #define K_S2_TILE_FULL_AP(F) k_s2_tile<true, true, F>
 #define K_S2_TILE_GEN(F) k_s2_tile<false, false, F>
 #define K_S2_TILE_GEN_AP(F) k_s2_tile<false, true, F>
+#define K_S2_BRIGHT(F) k_s2_bright<false, F>
+#define K_S2_BRIGHT_AP(F) k_s2_bright<true, F>
 #define K_PULSE_256_RES(F) k_pulse<256, true, F>
 #define K_PULSE_128_RES(F) k_pulse<128, true, F>
 #define K_PULSE_256_WIN(F) k_pulse<256, false, F>
@@ -136,9 +138,13 @@ struct wfs_handle {
 
     // tile-local generation (wfs_tilegen.h): S2 instructions whose photons are made inside the pulse workgroup
     DevBuf huge_start, huge_cbeg, huge_keys, huge_keys2, huge_vals, huge_vals2, huge_rec, huge_gain;      // ordering of tiles beyond TILE_ORDER_MAX photons
-    DevBuf row_pmax, ins_fused, ins_nsurv, ins_bcap, ins_bcap_all, ins_boff, et32, ftiles, tbuf, row_cnt, row_tile, tile_done;
+    DevBuf row_pmax, ins_fused, ins_nsurv, ins_bcap, ins_bcap_all, ins_boff, et32, ftiles, tbuf, row_cnt, row_tile, tile_done, tile_kind;
     bool fuse_on = false, fuse_full = false, run_sets_given = false, sets_aligned = true, any_s2 = false;
     i64 n_fused_tiles = 0 /* made by k_s2_tile<FULL> */, n_gen_tiles = 0 /* tile-generated, pulse by the ordinary kernels */, p_fused = 0, s_raw_direct = 0;
+    i64 n_bright_tiles = 0;      // made by k_s2_bright
+    bool bright_on = true;       // wfs_set_bright_tiles
+    i32 bright_lds = 0, bright_max_bins = 0;      // LDS a bright tile may take for H table + ballots (device grant, BRIGHT_LDS_MAX); start bins (WFS_BRIGHT_MAX_BINS)
+    BrightArgs bright_args{};
     int tap_sparse_max = 48;     // tap_block: occupied cells up to which a wave of the dense pulse kernels walks them (WFS_TAP_SPARSE_MAX)
     FuseArgs fuse_args{};
 
@@ -509,6 +515,19 @@ try {
     if (const char *e = getenv("WFS_RES_MAX_LEN")) h->res_max_len = std::max(256, std::min(atoi(e), 7168)) / 256 * 256;      // tuning knob (results do not depend on it)
     WFS_BIG_LDS_F(K_S2_TILE_FULL, 100); WFS_BIG_LDS_F(K_S2_TILE_FULL_AP, 100); WFS_BIG_LDS_F(K_S2_TILE_GEN, 100); WFS_BIG_LDS_F(K_S2_TILE_GEN_AP, 100);
     WFS_BIG_LDS_F(K_PULSE_SPARSE_64, 100); WFS_BIG_LDS_F(K_PULSE_SPARSE_256, 100);
+    {   // k_s2_bright: what the device grants one workgroup, less the SPE row, the afterpulse stage and the kernel's static arrays
+        int granted = 0;
+        if (hipDeviceGetAttribute(&granted, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess || granted <= 0) granted = 64 * 1024;
+        const int rest = BRIGHT_SPE_BYTES + AP_STAGE * (int)sizeof(ApCand) + 2048;
+        h->bright_lds = std::max(0, std::min(BRIGHT_LDS_MAX, granted - rest)) / 16 * 16;
+        h->bright_max_bins = std::max(0, h->bright_lds / (WFS_DT * 8) - 2 * 21);
+        if (const char *e = getenv("WFS_BRIGHT_MAX_BINS")) h->bright_max_bins = std::max(0, std::min(atoi(e), h->bright_max_bins));      // tuning knob (results do not depend on it)
+        const int total = h->bright_lds + rest - 2048;
+        hipFuncSetAttribute((const void *)k_s2_bright<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, total);
+        hipFuncSetAttribute((const void *)k_s2_bright<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, total);
+        hipFuncSetAttribute((const void *)k_s2_bright<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, total);
+        hipFuncSetAttribute((const void *)k_s2_bright<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, total);
+    }
     *out = h;
     return WFS_OK;
 } WFS_CATCH(nullptr)
@@ -537,7 +556,7 @@ try {
         &h->grp_gid, &h->row_lo, &h->row_hi, &h->acc_len, &h->acc_off, &h->itv_cap, &h->itv_off, &h->active_rows, &h->raw, &h->itv_left,
         &h->itv_right, &h->itv_n, &h->row_nrec, &h->rec_off, &h->records_ab[0], &h->records_ab[1], &h->truth, &h->tminmax, &h->tile_truth, &h->tile_desc, &h->gather_idx, &h->gather_out, &h->currents, &h->cur_len, &h->cur_off,
         &h->row_dbg, &h->row_dbg_len, &h->row_dbg_off, &h->scan_tmp, &h->scal,
-        &h->ph_idx, &h->ap_key, &h->order_list, &h->order_list2, &h->ins_sbase, &h->tile_tail, &h->tile_tailbase, &h->ins_fullsort, &h->row_pmax, &h->ins_fused, &h->ins_nsurv, &h->ins_bcap, &h->ins_bcap_all, &h->ins_boff, &h->et32, &h->ftiles, &h->tbuf, &h->row_cnt, &h->row_tile, &h->tile_done, &h->huge_start, &h->huge_cbeg, &h->huge_keys, &h->huge_keys2, &h->huge_vals, &h->huge_vals2, &h->huge_rec, &h->huge_gain,
+        &h->ph_idx, &h->ap_key, &h->order_list, &h->order_list2, &h->ins_sbase, &h->tile_tail, &h->tile_tailbase, &h->ins_fullsort, &h->row_pmax, &h->ins_fused, &h->ins_nsurv, &h->ins_bcap, &h->ins_bcap_all, &h->ins_boff, &h->et32, &h->ftiles, &h->tbuf, &h->row_cnt, &h->row_tile, &h->tile_done, &h->tile_kind, &h->huge_start, &h->huge_cbeg, &h->huge_keys, &h->huge_keys2, &h->huge_vals, &h->huge_vals2, &h->huge_rec, &h->huge_gain,
         &h->pack_desc, &h->row_bad, &h->fin_len, &h->res_cnt, &h->fin_off, &h->res_toff, &h->res_desc, &h->fin, &h->res_long, &h->res_rows,
         &h->pmap[0].cell_start, &h->pmap[0].cell_pts, &h->pmap[1].cell_start, &h->pmap[1].cell_pts};
     for (DevBuf *b : all) if (b->p) hipFree(b->p);
@@ -1288,7 +1307,9 @@ try {
 // the batch came through wfs_load_instructions: its photons are made on the device (run_generation)
 static bool from_generator(const wfs_handle *h) { return !h->injected && !h->optical; }
 // pulses made by k_s2_tile<FULL> (wfs_tilegen.h): their tiles are on no work list
-static bool tiles_made(const wfs_handle *h) { return from_generator(h) && h->fuse_full && h->n_fused_tiles > 0; }
+static bool tiles_made(const wfs_handle *h) { return from_generator(h) && h->fuse_full && h->n_fused_tiles + h->n_bright_tiles > 0; }
+// tiles that drew their own photons, whichever kernel made them
+static i64 n_tilegen_tiles(const wfs_handle *h) { return h->n_fused_tiles + h->n_gen_tiles + h->n_bright_tiles; }
 // ph_gain holds the photons with an explicit gain only: every photon of an injected batch, or the PMT afterpulses, which follow the
 // n_photons primary ones; the kernels index it by photon number
 static const double *ph_gain_base(const wfs_handle *h) { return (!h->injected && h->ap_active) ? h->ph_gain.as<double>() - h->n_photons : h->ph_gain.as<double>(); }
@@ -1339,7 +1360,7 @@ static int gen_electrons(wfs_handle *h, GenRun &r)
     // (PMT afterpulses of tile-generated photons are screened inside k_s2_tile)
     h->fuse_on = h->cfg.tile_gen && !h->generic_geom && h->any_s2 && d.gain_spread == 0.0 && (!h->run_sets_given || h->sets_aligned) && h->n_diff_rows == 0;
     h->fuse_full = h->fuse_on && !(h->keep_currents & (DBG_CURRENTS | DBG_GEN_ONLY));
-    h->n_fused_tiles = 0; h->n_gen_tiles = 0; h->p_fused = 0;
+    h->n_fused_tiles = 0; h->n_gen_tiles = 0; h->n_bright_tiles = 0; h->p_fused = 0;
     if (h->fuse_on) {
         f.lam_min = h->cfg.tile_gen_min; f.n_ins = N; f.nch = d.n_tpc; f.table_span = (i32)(1u << (32 - d.tab_s2.shift));
         f.set_ins_off = h->run_sets_given ? h->set_ins_off.as<i64>() : nullptr;
@@ -1400,16 +1421,24 @@ static int gen_electrons(wfs_handle *h, GenRun &r)
         // surviving electrons compacted per instruction, tile buffers sized from their time range, photons per tile (Poisson)
         { Timer t(h, "k_fuse_electrons"); hipLaunchKernelGGL(k_fuse_electrons, dim3((unsigned)N), dim3(256), 0, h->stream, d, f); }
         TRY(scan(h, h->ins_bcap_all.as<i32>(), N, h->ins_boff, &WfsScal::n_tbuf_samples));
-        TRY(ensure(h, h->ftiles, (size_t)TP * sizeof(FTile))); TRY(ensure(h, h->tile_done, (size_t)TP * 4));
+        // (the work list: TP entries for the tiles of k_s2_tile, from the front and from the back, and TP more for those of k_s2_bright)
+        TRY(ensure(h, h->ftiles, (size_t)2 * TP * sizeof(FTile))); TRY(ensure(h, h->tile_done, (size_t)TP * 4)); TRY(ensure(h, h->tile_kind, (size_t)TP));
         f.ins_boff = h->ins_boff.as<i64>(); f.tile_count = h->tile_count.as<i32>(); f.tiles = h->ftiles.as<FTile>();
         f.tile_done = h->tile_done.as<i32>(); f.full = h->fuse_full ? 1 : 0; f.n_list = TP;
-        { Timer t(h, "k_tile_counts"); hipLaunchKernelGGL(k_tile_counts, dim3(nblocks(TP, 256)), dim3(256), 0, h->stream, d, f); }
+        BrightArgs &b = h->bright_args;
+        b.on = (h->fuse_full && h->bright_on && h->bright_max_bins > 0) ? 1 : 0; b.lds_bytes = h->bright_lds; b.max_bins = h->bright_max_bins; b.pad = 0;
+        b.list_first = TP; b.tile_kind = h->tile_kind.as<int8_t>();
+        { Timer t(h, "k_tile_counts"); hipLaunchKernelGGL(k_tile_counts, dim3(nblocks(TP, 256)), dim3(256), 0, h->stream, d, f, b); }
     }
     TRY(scan(h, h->em_nph.as<i32>(), E, h->em_ph_off, &WfsScal::n_block_photons));
     TRY(read_scal(h));
     const WfsScal &sc = *h->h_scal;
     r.P = sc.n_block_photons;                   // the tiles' own photons come on top
-    if (h->fuse_on) { h->p_fused = sc.n_tilegen_photons; h->n_fused_tiles = sc.n_full_tiles; h->n_gen_tiles = sc.n_gen_tiles; }
+    if (h->fuse_on) { h->p_fused = sc.n_tilegen_photons; h->n_fused_tiles = sc.n_full_tiles; h->n_gen_tiles = sc.n_gen_tiles; h->n_bright_tiles = sc.n_bright_tiles; }
+    if (h->fuse_on && getenv("WFS_BRIGHT_STATS")) {
+        fprintf(stderr, "bright tiles: %lld by k_s2_bright, %lld generation only, %lld of up to %d photons; widest H table of a tile above that: %lld start bins (budget %d bins, %d bytes)\n",
+                (long long)h->n_bright_tiles, (long long)h->n_gen_tiles, (long long)h->n_fused_tiles, TILE_MAX_PHOTONS, (long long)sc.max_bright_bins, h->bright_max_bins, h->bright_lds);
+    }
     h->n_photons = r.P + h->p_fused; h->n_ap_photons = 0;
     return WFS_OK;
 }
@@ -1505,7 +1534,7 @@ static int gen_tile_photons(wfs_handle *h, GenRun &r)
     // (photon counts only -- wfs_set_debug bit 2 without bit 4, the electron-afterpulse pre-pass: the tiles' photon numbers are drawn
     // (k_tile_counts) and single photons are recomputed on request (wfs_gather_photon_times); no photon of a tile is generated)
     const bool counts_only = (h->keep_currents & DBG_GEN_ONLY) && !(h->keep_currents & DBG_KEEP_PHOTONS);
-    if (h->fuse_on && h->n_fused_tiles + h->n_gen_tiles > 0 && !counts_only) {
+    if (h->fuse_on && n_tilegen_tiles(h) > 0 && !counts_only) {
         TRY(ensure(h, h->tbuf, (size_t)h->h_scal->n_tbuf_samples * 4 + 64));
         TRY(ensure(h, h->tile_truth, (size_t)T * 8 * 8));
         f.tile_off = h->tile_off.as<i64>(); f.tile_tmin = h->tile_tmin.as<i32>(); f.tile_tmax = h->tile_tmax.as<i32>(); f.tile_truth = h->tile_truth.as<double>();
@@ -1518,7 +1547,7 @@ static int gen_tile_photons(wfs_handle *h, GenRun &r)
         const ApArgs *app = nullptr;
         if (ap_on) {
             lds += (size_t)AP_STAGE * sizeof(ApCand);
-            TRY(ensure(h, h->ap_seg, (size_t)(h->n_fused_tiles + h->n_gen_tiles) * sizeof(ApSeg))); ap.seg = h->ap_seg.as<ApSeg>(); ap.n_seg = h->n_fused_tiles + h->n_gen_tiles;
+            TRY(ensure(h, h->ap_seg, (size_t)n_tilegen_tiles(h) * sizeof(ApSeg))); ap.seg = h->ap_seg.as<ApSeg>(); ap.n_seg = n_tilegen_tiles(h);      // (one segment per tile of every class)
             f.n_ptiles = TP;
             TRY(upload(h, h->ap_args_dev, &ap, sizeof ap)); app = h->ap_args_dev.as<ApArgs>();      // (`ap` outlives the copy: read_scal of gen_afterpulses)
         }
@@ -1536,6 +1565,15 @@ static int gen_tile_photons(wfs_handle *h, GenRun &r)
             const dim3 grid((unsigned)h->n_gen_tiles);
             if (ap_on) WFS_LAUNCH_F(h, K_S2_TILE_GEN_AP, grid, dim3(256), lds, d, f, tp, app, ap_lds_off, TP - 1, -1, (int)h->n_fused_tiles);
             else WFS_LAUNCH_F(h, K_S2_TILE_GEN, grid, dim3(256), lds, d, f, tp, app, ap_lds_off, TP - 1, -1, (int)h->n_fused_tiles);
+        }
+        // tiles above 2048 photons whose H table fits the LDS as a whole: photons and pulse in one workgroup of 1024 threads, no photon array
+        if (h->n_bright_tiles > 0) {
+            Timer t(h, "k_s2_bright");
+            const dim3 grid((unsigned)h->n_bright_tiles);
+            const size_t blds = (size_t)h->bright_lds + BRIGHT_SPE_BYTES + (ap_on ? (size_t)AP_STAGE * sizeof(ApCand) : 0);
+            const int seg_first = (int)(h->n_fused_tiles + h->n_gen_tiles);
+            if (ap_on) WFS_LAUNCH_F(h, K_S2_BRIGHT_AP, grid, dim3(BRIGHT_TPB), blds, d, f, h->bright_args, tp, app, seg_first);
+            else WFS_LAUNCH_F(h, K_S2_BRIGHT, grid, dim3(BRIGHT_TPB), blds, d, f, h->bright_args, tp, app, seg_first);
         }
     }
     h->fuse_args = f;
@@ -1569,7 +1607,7 @@ static int gen_order(wfs_handle *h, GenRun &r)
     TRY(ensure(h, h->order_list, (size_t)T * 2 * sizeof(OrderRange))); TRY(ensure(h, h->order_list2, (size_t)T * 2 * sizeof(OrderRange)));
     OrderArgs oa{T, TP, h->tile_count.as<i32>(), h->tile_off.as<i64>(), h->ph.as<PhotonRec>(), h->ph_idx.as<u32>(),
                  ap_on ? h->ph_gain.as<double>() : nullptr, P + h->p_fused, h->order_list.as<OrderRange>(), h->order_list2.as<OrderRange>(), h->scal.as<WfsScal>(),
-                 (h->fuse_on && h->n_fused_tiles + h->n_gen_tiles > 0) ? h->ins_fused.as<i32>() : nullptr, d.n_tpc,
+                 (h->fuse_on && n_tilegen_tiles(h) > 0) ? h->ins_fused.as<i32>() : nullptr, d.n_tpc,
                  h->tile_cursor.as<i32>(), h->tile_tailbase.as<i32>(), h->ins_fullsort.as<i32>(), h->set_ins_off.as<i64>(), h->set_ins_list.as<i32>()};
     { Timer t(h, "k_tile_order_scan"); hipLaunchKernelGGL(k_tile_order_scan, dim3(nblocks(T, 256)), dim3(256), 0, h->stream, oa); }
     TRY(read_scal(h));
@@ -1871,7 +1909,11 @@ static int run_pulses(wfs_handle *h, RunState &r)
     if (r.tiles_done && h->h_scal->n_shared_rows > 0) {   // tiles of k_s2_tile that share their row with other pulses: added into the row's accumulators
         TileAddArgs ta{h->set_cluster.as<i32>(), h->cl_group.as<i32>(), h->row_lo.as<i64>(), h->acc_off.as<i64>(), h->row_cnt.as<i32>(), h->raw.as<i32>()};
         Timer t(h, "k_tile_add");
-        hipLaunchKernelGGL(k_tile_add, dim3((unsigned)h->n_fused_tiles), dim3(256), 0, h->stream, d, h->fuse_args, ta);
+        if (h->n_fused_tiles > 0) hipLaunchKernelGGL(k_tile_add, dim3((unsigned)h->n_fused_tiles), dim3(256), 0, h->stream, d, h->fuse_args, ta);
+        if (h->n_bright_tiles > 0) {                       // (the tiles of k_s2_bright: their own stretch of the work list)
+            FuseArgs fb = h->fuse_args; fb.tiles += h->bright_args.list_first;
+            hipLaunchKernelGGL(k_tile_add, dim3((unsigned)h->n_bright_tiles), dim3(256), 0, h->stream, d, fb, ta);
+        }
     }
     return WFS_OK;
 }
@@ -2280,7 +2322,7 @@ static int gen_order_tables(wfs_handle *h)
     HIPCHK(hipMemcpy(emo.data(), h->em_off.p, emo.size() * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(epo.data(), h->em_ph_off.p, epo.size() * 8, hipMemcpyDeviceToHost));
     h->go_fused.assign((size_t)N, 0); h->go_tile_count.clear();
-    const bool any_fused = h->fuse_on && h->n_fused_tiles + h->n_gen_tiles > 0;
+    const bool any_fused = h->fuse_on && n_tilegen_tiles(h) > 0;
     if (any_fused) {
         HIPCHK(hipMemcpy(h->go_fused.data(), h->ins_fused.p, (size_t)N * 4, hipMemcpyDeviceToHost));
         h->go_tile_count.resize((size_t)N * nch);
@@ -2415,6 +2457,26 @@ try {
         estat5[q * 5 + 2] = n > 0 ? (double)lo : NAN; estat5[q * 5 + 3] = n > 0 ? (double)hi : NAN;
         estat5[q * 5 + 4] = n > 0 ? sqrt(var > 0 ? var : 0) : NAN;
     }
+    return WFS_OK;
+} WFS_CATCH(h)
+
+int wfs_set_bright_tiles(wfs_handle *h, int32_t on)
+try {
+    if (!h) return WFS_E_INVALID;
+    h->bright_on = on != 0;
+    return WFS_OK;
+} WFS_CATCH(h)
+
+int wfs_copy_tile_kernels(wfs_handle *h, int8_t *kind, int64_t capacity)
+try {
+    if (!h || !h->ran) return WFS_E_STATE;
+    if (!kind) return h->fail(WFS_E_INVALID, "wfs_copy_tile_kernels: null argument");
+    const i64 TP = (from_generator(h) ? h->n_psets : h->n_sets) * h->cfg.n_tpc;      // (a batch of loaded photons has primary sets only)
+    if (capacity < TP) return h->fail(WFS_E_CAPACITY, "tile kernel buffer too small");
+    if (!from_generator(h) || !h->fuse_on || TP == 0) { memset(kind, 0, (size_t)TP); return WFS_OK; }
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(kind, h->tile_kind.p, (size_t)TP, hipMemcpyDeviceToHost));
     return WFS_OK;
 } WFS_CATCH(h)
 

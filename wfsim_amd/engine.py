@@ -104,7 +104,7 @@ EXPORTS = ['wfs_create', 'wfs_destroy', 'wfs_last_error', 'wfs_device_count', 'w
            'wfs_copy_records_dev', 'wfs_records_dev_ptr', 'wfs_copy_groups', 'wfs_copy_intervals',
            'wfs_copy_interval_data', 'wfs_copy_pulses', 'wfs_copy_currents', 'wfs_copy_rows', 'wfs_copy_row_data',
            'wfs_copy_photons', 'wfs_copy_truth', 'wfs_copy_truth_per_pmt', 'wfs_copy_instruction_photon_offsets', 'wfs_gather_photon_times', 'wfs_copy_electron_stats', 'wfs_set_window_carry', 'wfs_copy_cluster_groups', 'wfs_set_noise_offsets', 'wfs_set_debug', 'wfs_set_stream', 'wfs_synchronize',
-           'wfs_kernel_times', 'wfs_set_profiling', 'wfs_set_delay_models', 'wfs_set_s1_propagation', 'wfs_set_instruction_models',
+           'wfs_kernel_times', 'wfs_set_profiling', 'wfs_set_bright_tiles', 'wfs_copy_tile_kernels', 'wfs_set_delay_models', 'wfs_set_s1_propagation', 'wfs_set_instruction_models',
            'wfs_set_pattern_map', 'wfs_eval_pattern_rows', 'wfs_copy_cdf_rows', 'wfs_set_record_order', 'wfs_copy_records_range',
            'wfs_copy_records_range_async', 'wfs_wait_records', 'wfs_host_register', 'wfs_host_unregister',
            'wfs_set_gas_gap_model', 'wfs_set_instruction_gas_gap', 'wfs_set_pattern_map_points', 'wfs_set_instruction_aft',
@@ -206,6 +206,9 @@ class Engine:
                     self._h, C.c_int32(e), C.c_int32(dc.shape[1]), C.c_int32(ac.shape[-1]), C.c_int32(ac.ndim == 2),
                     C.c_int32('Uniform' in name), C.c_double(d['delaytime_bin_size']), C.c_double(d['amplitude_bin_size']), _p(dc), _p(ac)))
 
+        self.tile_local_bright = bool(params['tile_local_bright'])
+        if not self.tile_local_bright:         # (the library's default is on)
+            self._check(self.lib.wfs_set_bright_tiles(self._h, C.c_int32(0)))
         if self.keep_photons or os.environ.get('WFS_CHECK_LAUNCHES', '0') not in ('', '0'):
             self.set_debug(False)          # (every launch checked from the first run on)
         # HE records exist only when the HE rows can differ from a flat baseline (wfs_engine.hip refresh_dev): a non-zero
@@ -606,6 +609,17 @@ class Engine:
             self._check(self.lib.wfs_copy_truth_per_pmt(self._h, _p(acc), C.c_int64(s)))
         rows = self._caller_sets(s)
         return acc if rows is None else acc[rows]
+
+    def tile_kernels(self):
+        """[primary pulse set][channel] int8: which kernel made the tile in the last run -- 0 no photons or not tile-generated, 1 photons and
+        pulse in one workgroup (up to 2048 photons), 2 generation only + the pulse kernels, 3 the bright-tile kernel (k_s2_bright)"""
+        s, nch = self._lib_sets, int(self.params['n_tpc'])
+        kind = np.full(s * nch, -1, dtype=np.int8)
+        if s:
+            self._check(self.lib.wfs_copy_tile_kernels(self._h, _p(kind), C.c_int64(len(kind))))
+        kind = kind[kind >= 0].reshape(-1, nch)         # (the library fills the primary sets: PMT-afterpulse sets follow them and have no entry)
+        rows = getattr(self, '_set_rows', None)
+        return kind if rows is None or not self.counts['n_instructions'] else kind[rows]
 
     def set_noise_offsets(self, ix_rand):
         a = _arr(ix_rand, np.int64)
