@@ -51,7 +51,7 @@ typedef struct wfs_config {
     int32_t n_top;             /* n_top_pmts                                        rawdata.py:243   */
     int32_t he_first;          /* channel_map['he'][0]                              rawdata.py:244   */
     int32_t he_factor;         /* int(high_energy_deamplification_factor)           rawdata.py:242   */
-    int32_t sum_channel;       /* channel_map['sum_signal'] (never emitted)              */
+    int32_t sum_channel;       /* channel_map['sum_signal'] (emitted after wfs_set_sum_signal only)  */
     int32_t last_bottom;       /* channels_bottom[-1]                               rawdata.py:250   */
     int32_t detector_nt;       /* detector == 'XENONnT'                             rawdata.py:241   */
     int32_t enable_noise;      /* rawdata.py:263                                                     */
@@ -265,7 +265,8 @@ int wfs_run(wfs_handle *h);
 /* n_pulse_sets: rows of the per-set outputs (wfs_copy_truth, wfs_copy_truth_per_pmt, wfs_copy_electron_stats; set offsets of
  * wfs_copy_photons) = n_run_sets as given to wfs_load_instructions, unused set numbers included (their rows are empty), twice that with
  * PMT afterpulses (the afterpulse set of set q is n_run_sets + q).  n_raw_samples: samples of every digitised row, whichever way it was
- * made (accumulators, tile buffer read in place, resident row). */
+ * made (accumulators, tile buffer read in place, resident row).  n_rows and n_raw_samples include the bottom-array sum rows
+ * (wfs_set_sum_signal). */
 typedef struct wfs_counts {
     int64_t n_instructions, n_pulse_sets, n_emitters, n_photons /* primary + PMT afterpulse */, n_pe, n_tiles, n_groups, n_rows,
             n_raw_samples, n_intervals, n_records;
@@ -348,6 +349,23 @@ int wfs_synchronize(wfs_handle *h);
  * one kernel, without a photon array (k_s2_bright; config 'tile_local_bright').  on = 0: they take the generation-only kernel and the
  * dense pulse kernel, as every bright tile that does not fit.  Results do not depend on it.  Default: on. */
 int wfs_set_bright_tiles(wfs_handle *h, int32_t on);
+/* The bottom-array sum channel (row channel_map['sum_signal'] = 800 of the reference's digitiser array, rawdata.py:250-254, which the
+ * reference fills at every digitisation and never emits).  on = 1, detector XENONnT: every digitise window with at least one pulse on
+ * a bottom-array channel (n_top <= channel <= last_bottom) gets one more row on channel wfs_config.sum_channel, behind its TPC and HE
+ * rows: S[t] = int(he_factor) * sum over those pulses of their rounded ADC wave, carried in 64 bits (stored in 32 bits it saturates,
+ * which no finished sample can show: such a value clamps to 0), from min(pulse left) - trigger_window to max(pulse right) +
+ * trigger_window.  The row is finished, zero-suppressed and packed like every other row: noise from column sum_channel of the noise
+ * array when it has one, baseline, clamp at 0, ZLE threshold thr_zle[sum_channel].  It takes no part in the window's left / right or
+ * in its noise draw; truth is unchanged.  wfs_copy_rows / wfs_copy_intervals list it under channel = sum_channel.  With the switch on,
+ * bottom-array rows are kept off the resident-row path (wfs_config.row_resident); the records of every other channel are the same.
+ * Takes effect from the next wfs_run.  on = 1 needs sum_channel < n_rows, outside the TPC and the HE channels (WFS_E_INVALID
+ * otherwise); other detectors accept the switch and never have the row.  Default: off -- no kernel, no buffer, no record differs. */
+int wfs_set_sum_signal(wfs_handle *h, int32_t on);
+/* Parity entry: the sum rows of the last wfs_run before they are finished (a clamped finished row cannot be turned back into S).  Per
+ * row, in window order: its window (index of wfs_copy_groups), absolute first and last sample, and S[t] (times int(he_factor)) at
+ * data[data_off[k] .. data_off[k + 1]); data_off[rows] is written when capacity_rows exceeds the number of rows. */
+int wfs_copy_sum_signal(wfs_handle *h, int32_t *group, int64_t *left, int64_t *right, int64_t *data_off, int64_t *data,
+                        int64_t capacity_rows, int64_t capacity_samples);
 /* Which kernel made every primary (pulse set, channel) tile of the last wfs_run, indexed set * n_tpc + channel: 0 no photons or not
  * tile-generated, 1 photons and pulse in one workgroup (up to 2048 photons), 2 generation only + the pulse kernels, 3 k_s2_bright.
  * capacity: entries the buffer holds (>= n_run_sets * n_tpc). */

@@ -143,6 +143,11 @@ struct wfs_handle {
     i64 n_fused_tiles = 0 /* made by k_s2_tile<FULL> */, n_gen_tiles = 0 /* tile-generated, pulse by the ordinary kernels */, p_fused = 0, s_raw_direct = 0;
     i64 n_bright_tiles = 0;      // made by k_s2_bright
     bool bright_on = true;       // wfs_set_bright_tiles
+    // the bottom-array sum row (wfs_set_sum_signal, k_sum_signal): range, length, chunks and offsets per window; the rows' samples sit
+    // behind the accumulators in raw, from sample sum_base
+    bool sum_on = false;
+    DevBuf sum_lo, sum_hi, sum_len, sum_nchunk, sum_off, sum_chunk_off;
+    i64 s_sum = 0, n_sum_chunks = 0, sum_base = 0;
     i32 bright_lds = 0, bright_max_bins = 0;      // LDS a bright tile may take for H table + ballots (device grant, BRIGHT_LDS_MAX); start bins (WFS_BRIGHT_MAX_BINS)
     BrightArgs bright_args{};
     int tap_sparse_max = 48;     // tap_block: occupied cells up to which a wave of the dense pulse kernels walks them (WFS_TAP_SPARSE_MAX)
@@ -216,6 +221,9 @@ struct Timer {
     }
 };
 #define CHECK_LAUNCHES() do { if (!h->launch_err.empty()) { const std::string m_ = h->launch_err; h->launch_err.clear(); return h->fail(WFS_E_HIP, m_); } } while (0)
+
+// the last row slot of a window is its sum row when the switch is on (row_slot_is_sum on the device)
+inline bool slot_is_sum(const WfsDev &d, i32 slot) { return d.sum_channel >= 0 && slot == d.row_slots - 1; }
 
 // grid size for n items; never 0 (a launch with an empty grid is an error, every kernel bounds-checks its index)
 inline unsigned nblocks(i64 n, int tpb) { return n > 0 ? (unsigned)((n + tpb - 1) / tpb) : 1u; }
@@ -443,6 +451,9 @@ void refresh_dev(wfs_handle *h)
     bool he_noise = d.enable_noise && d.noise_channels > c.he_first;
     d.he_rows = (c.detector_nt && c.n_top > 0 && (c.he_factor != 0 || he_noise)) ? 1 : 0;
     d.row_slots = c.n_tpc + (d.he_rows ? c.n_top : 0);
+    // the bottom-array sum row: one more slot per window, behind the TPC and HE slots (XENONnT only, rawdata.py:241)
+    d.sum_channel = (h->sum_on && c.detector_nt) ? c.sum_channel : -1;
+    if (d.sum_channel >= 0) d.row_slots += 1;
 }
 
 }  // namespace
@@ -1706,6 +1717,12 @@ static int run_geometry(wfs_handle *h, RunState &r)
     ga.row_lo = h->row_lo.as<i64>(); ga.row_hi = h->row_hi.as<i64>(); ga.acc_len = h->acc_len.as<i32>(); ga.itv_cap = h->itv_cap.as<i32>();
     ga.active_rows = h->active_rows.as<i32>(); ga.scal = h->scal.as<WfsScal>(); ga.active_tiles = h->active_tiles.as<i32>(); ga.sparse_tiles = h->sparse_tiles.as<i32>(); ga.dense_tiles = h->dense_tiles.as<i32>(); ga.wave_tiles = h->wave_tiles.as<i32>(); ga.force_dense = ((h->keep_currents & DBG_FORCE_DENSE) || h->generic_geom) ? 1 : 0; ga.init_has = h->carry_has; ga.init_runmax = h->carry_runmax;
     ga.noise_override = h->n_noise_override ? h->noise_override.as<i64>() : nullptr; ga.n_noise_override = h->n_noise_override;
+    if (d.sum_channel >= 0) {
+        TRY(fill64(h, h->sum_lo, CG, I64_MAX)); TRY(fill64(h, h->sum_hi, CG, I64_MIN));
+        TRY(ensure(h, h->sum_len, (size_t)CG * 4)); TRY(ensure(h, h->sum_nchunk, (size_t)CG * 4));
+        HIPCHK(hipMemsetAsync(h->sum_len.p, 0, (size_t)CG * 4, h->stream)); HIPCHK(hipMemsetAsync(h->sum_nchunk.p, 0, (size_t)CG * 4, h->stream));
+        ga.sum_lo = h->sum_lo.as<i64>(); ga.sum_hi = h->sum_hi.as<i64>(); ga.sum_len = h->sum_len.as<i32>(); ga.sum_nchunk = h->sum_nchunk.as<i32>();
+    }
     const bool tiles_done = r.tiles_done = tiles_made(h);
     // resident rows (k_row_pulse): the usual digitiser geometry, a hold-off of at least a chunk and a noise table the fast row loads
     // can walk (as the fast path of k_zle), no HE rows, no debug copies of currents or rows
@@ -1742,6 +1759,10 @@ static int run_geometry(wfs_handle *h, RunState &r)
     { Timer t(h, "k_row_len"); hipLaunchKernelGGL(k_row_len, dim3(nblocks(CG * d.row_slots, 1024)), dim3(1024), 0, h->stream, d, ga); }
     TRY(scan(h, h->acc_len.as<i32>(), CG * d.n_tpc, h->acc_off, &WfsScal::n_acc_samples));
     TRY(scan(h, h->itv_cap.as<i32>(), CG * d.row_slots, h->itv_off, &WfsScal::n_itv_slots));
+    if (d.sum_channel >= 0) {
+        TRY(scan(h, h->sum_len.as<i32>(), CG, h->sum_off, &WfsScal::n_sum_samples));
+        TRY(scan(h, h->sum_nchunk.as<i32>(), CG, h->sum_chunk_off, &WfsScal::n_sum_chunks));
+    }
     if (h->res_on) {
         TRY(scan(h, h->fin_len.as<i32>(), CG * d.n_tpc, h->fin_off, &WfsScal::n_fin_samples)); TRY(scan(h, h->res_cnt.as<i32>(), CG * d.n_tpc, h->res_toff, &WfsScal::n_res_tiles));
         // rows are known: tiles onto their row's list or the work list of their class.  res_desc holds a descriptor slot for EVERY
@@ -1774,6 +1795,8 @@ static int run_geometry(wfs_handle *h, RunState &r)
     h->n_active_tiles = h->n_tiny_tiles + h->n_sparse_tiles + h->n_dense_tiles + h->n_wave_tiles;
     r.first_sparse = h->n_tiny_tiles; r.first_dense = r.first_sparse + h->n_sparse_tiles; r.first_wave = r.first_dense + h->n_dense_tiles;
     h->s_raw = sc.n_acc_samples; h->n_itv_slots = sc.n_itv_slots;
+    h->s_sum = d.sum_channel >= 0 ? sc.n_sum_samples : 0; h->n_sum_chunks = d.sum_channel >= 0 ? sc.n_sum_chunks : 0;
+    h->sum_base = (h->s_raw + 3) & ~(i64)3;
     h->s_raw_direct = tiles_done ? sc.n_direct_samples : 0;      // samples of the rows that are read from a tile buffer in place
     if (h->res_on && getenv("WFS_RES_STATS")) {
         fprintf(stderr, "resident rows: %lld short + %lld long of %lld rows, %lld tiles of %lld listed + resident, longest %lld samples, %lld finished samples, accumulators %lld samples\n",
@@ -1796,7 +1819,8 @@ static int run_pulses(wfs_handle *h, RunState &r)
     const WfsDev &d = h->dev;
     PulseArgs &pa = r.pa;
     const i64 T = h->n_tiles, S = h->n_sets;
-    TRY(ensure(h, h->raw, (size_t)h->s_raw * 4 + 64)); HIPCHK(hipMemsetAsync(h->raw.p, 0, (size_t)h->s_raw * 4, h->stream));       // (+64: a lane of k_zle reads 4 samples from its first valid one)
+    // (+64: a lane of k_zle reads 4 samples from its first valid one; the sum rows behind the accumulators are written whole by k_sum_signal)
+    TRY(ensure(h, h->raw, (size_t)(h->s_sum > 0 ? h->sum_base + h->s_sum : h->s_raw) * 4 + 64)); HIPCHK(hipMemsetAsync(h->raw.p, 0, (size_t)h->s_raw * 4, h->stream));
     TRY(ensure(h, h->truth, (size_t)S * 16 * 8)); HIPCHK(hipMemsetAsync(h->truth.p, 0, (size_t)S * 16 * 8, h->stream));
     TRY(ensure(h, h->tminmax, (size_t)S * 16)); TRY(ensure(h, h->tile_truth, (size_t)T * 8 * 8));
     pa.active_tiles = h->active_tiles.as<i32>(); pa.n_active = h->n_active_tiles;
@@ -1934,6 +1958,7 @@ static int run_rows(wfs_handle *h, RunState &r)
     za.itv_n = h->itv_n.as<i32>(); za.row_nrec = h->row_nrec.as<i32>(); za.spr = WFS_SPR;
     if (r.tiles_done) { za.tile_done = ga.tile_done; za.n_done = ga.n_done; za.row_cnt = ga.row_cnt; za.row_tile = ga.row_tile; za.ins_bcap = ga.ins_bcap; za.ins_boff = ga.ins_boff; za.tbuf = h->tbuf.as<i32>(); }
     za.n_front = h->n_front_rows; za.rows_cap = CG * d.row_slots;
+    if (d.sum_channel >= 0) { za.sum_lo = h->sum_lo.as<i64>(); za.sum_hi = h->sum_hi.as<i64>(); za.sum_off = h->sum_off.as<i64>(); za.sum_base = h->sum_base; }
     if (h->n_res_rows > 0) {
         TRY(ensure(h, h->fin, (size_t)h->s_fin * 2 + 16));
         TRY(ensure(h, h->res_rows, (size_t)h->n_res_rows * sizeof(ResRow)));
@@ -1947,10 +1972,16 @@ static int run_rows(wfs_handle *h, RunState &r)
         HIPCHK(hipMemcpy(ar.data(), h->active_rows.p, ar.size() * 4, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(lo.data(), h->row_lo.p, lo.size() * 8, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(hi.data(), h->row_hi.p, hi.size() * 8, hipMemcpyDeviceToHost));
+        std::vector<i64> slo, shi;
+        if (d.sum_channel >= 0) {
+            slo.resize((size_t)CG); shi.resize((size_t)CG);
+            HIPCHK(hipMemcpy(slo.data(), h->sum_lo.p, slo.size() * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(shi.data(), h->sum_hi.p, shi.size() * 8, hipMemcpyDeviceToHost));
+        }
         std::vector<i64> off(ar.size() + 1, 0);
         for (size_t k = 0; k < ar.size(); k++) {
             i64 g = ar[k] / d.row_slots; i32 slot = (i32)(ar[k] - g * d.row_slots); i32 c = slot < d.n_tpc ? slot : slot - d.n_tpc;
-            off[k + 1] = off[k] + hi[g * d.n_tpc + c] - lo[g * d.n_tpc + c] + 1 + 2 * d.tw;
+            if (slot_is_sum(d, slot)) off[k + 1] = off[k] + shi[g] - slo[g] + 1 + 2 * d.tw;
+            else off[k + 1] = off[k] + hi[g * d.n_tpc + c] - lo[g * d.n_tpc + c] + 1 + 2 * d.tw;
         }
         h->row_dbg_total = off.back();
         TRY(upload(h, h->row_dbg_off, off.data(), off.size() * 8));
@@ -1993,6 +2024,16 @@ static int run_rows(wfs_handle *h, RunState &r)
         hipLaunchKernelGGL(k_truth_reduce, dim3(nblocks(S, 4)), dim3(256), 0, h->stream, d, ta);
     }
 
+    // (WFS_SUM_SKIP_KERNEL: A/B runs that price what the switch costs apart from the kernel -- bottom rows off the resident path, one
+    // more row per window through k_zle / k_pack; the sum rows then hold whatever the buffer held)
+    if (h->n_sum_chunks > 0 && !getenv("WFS_SUM_SKIP_KERNEL")) {      // the windows' sum rows from their bottom rows: every accumulator and tile buffer is complete here (k_tile_add included)
+        if (h->n_sum_chunks > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "more than 2^31 chunks of sum rows in one batch");
+        SumArgs sa{h->sum_chunk_off.as<i64>(), CG, h->sum_lo.as<i64>(), h->sum_off.as<i64>(), h->sum_len.as<i32>(),
+                   h->row_lo.as<i64>(), h->row_hi.as<i64>(), h->acc_off.as<i64>(), h->raw.as<i32>(), r.tiles_done ? h->tbuf.as<i32>() : nullptr,
+                   r.tiles_done ? ga.tile_done : nullptr, ga.row_cnt, ga.row_tile, ga.ins_bcap, ga.ins_boff, ga.n_done, h->raw.as<i32>() + h->sum_base};
+        Timer t(h, "k_sum_signal");
+        hipLaunchKernelGGL(k_sum_signal, dim3((unsigned)h->n_sum_chunks), dim3(256), 0, h->stream, d, sa);
+    }
     if (h->n_front_rows > 0) {
         Timer t(h, "k_zle"); const dim3 grid(nblocks(h->n_front_rows, 4));
         with_noise_kind(r.noise_kind, [&](auto nk) { hipLaunchKernelGGL(k_zle<decltype(nk)::value>, grid, dim3(256), 0, h->stream, d, za); });
@@ -2085,7 +2126,7 @@ try {
     c.n_instructions = h->n_ins; c.n_pulse_sets = h->n_sets; c.n_emitters = h->n_emitters; c.n_photons = h->n_photons + ((!h->injected && h->ap_active) ? h->n_ap_photons : 0);
     const bool tiles_done = tiles_made(h);
     c.n_tiles = h->n_active_tiles + (tiles_done ? h->n_fused_tiles : 0) + h->n_res_tiles; c.n_groups = h->n_groups; c.n_rows = h->n_active_rows;
-    c.n_raw_samples = h->s_raw + (tiles_done ? h->s_raw_direct : 0) + h->s_res;
+    c.n_raw_samples = h->s_raw + (tiles_done ? h->s_raw_direct : 0) + h->s_res + h->s_sum;
     c.n_records = h->n_records;
     c.n_intervals = h->h_scal->n_intervals; c.n_pe = h->h_scal->n_pe;          // reduced on the device at the end of wfs_run (k_counts)
     *out = c; h->counts = c;
@@ -2185,7 +2226,7 @@ try {
     i64 k = 0, doff = 0;
     for (i64 idx = 0; idx < RS; idx++) {
         i64 g = idx / d.row_slots; i32 slot = (i32)(idx - g * d.row_slots);
-        i32 chn = slot < d.n_tpc ? slot : d.he_first + slot - d.n_tpc;
+        i32 chn = slot_is_sum(d, slot) ? d.sum_channel : (slot < d.n_tpc ? slot : d.he_first + slot - d.n_tpc);
         for (i32 q = 0; q < n[idx]; q++) {
             if (k >= cap) return h->fail(WFS_E_CAPACITY, "interval buffer too small");
             i64 l = L[off[idx] + q], r = R[off[idx] + q];
@@ -2258,12 +2299,19 @@ try {
     HIPCHK(hipMemcpy(lo.data(), h->row_lo.p, lo.size() * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(hi.data(), h->row_hi.p, hi.size() * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(gl.data(), h->grp_left.p, gl.size() * 8, hipMemcpyDeviceToHost));
+    std::vector<i64> slo, shi;
+    if (d.sum_channel >= 0) {
+        slo.resize((size_t)h->n_clusters + 1); shi.resize(slo.size());
+        HIPCHK(hipMemcpy(slo.data(), h->sum_lo.p, slo.size() * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(shi.data(), h->sum_hi.p, shi.size() * 8, hipMemcpyDeviceToHost));
+    }
     i64 off = 0;
     for (i64 k = 0; k < A; k++) {
         i64 g = ar[k] / d.row_slots; i32 slot = (i32)(ar[k] - g * d.row_slots); i32 c = slot < d.n_tpc ? slot : slot - d.n_tpc;
-        group[k] = (i32)g; channel[k] = slot < d.n_tpc ? slot : d.he_first + c;
+        const bool sum = slot_is_sum(d, slot);
+        group[k] = (i32)g; channel[k] = sum ? d.sum_channel : (slot < d.n_tpc ? slot : d.he_first + c);
         // relative to the window like the reference's channel mask (rawdata.py:258-259)
-        left[k] = lo[g * d.n_tpc + c] - gl[g] - d.tw; right[k] = hi[g * d.n_tpc + c] - gl[g] + d.tw;
+        if (sum) { left[k] = slo[g] - gl[g] - d.tw; right[k] = shi[g] - gl[g] + d.tw; }
+        else { left[k] = lo[g * d.n_tpc + c] - gl[g] - d.tw; right[k] = hi[g * d.n_tpc + c] - gl[g] + d.tw; }
         data_off[k] = off; off += right[k] - left[k] + 1;
     }
     return WFS_OK;
@@ -2464,6 +2512,47 @@ int wfs_set_bright_tiles(wfs_handle *h, int32_t on)
 try {
     if (!h) return WFS_E_INVALID;
     h->bright_on = on != 0;
+    return WFS_OK;
+} WFS_CATCH(h)
+
+int wfs_set_sum_signal(wfs_handle *h, int32_t on)
+try {
+    if (!h) return WFS_E_INVALID;
+    const wfs_config &c = h->cfg;
+    if (on && c.detector_nt) {
+        // the row takes the noise column, the threshold and the record channel of sum_channel: a channel of its own
+        if (c.sum_channel < 0 || c.sum_channel >= c.n_rows) return h->fail(WFS_E_INVALID, "wfs_set_sum_signal: sum_channel outside the rows of the digitiser array");
+        if (c.sum_channel < c.n_tpc || (c.sum_channel >= c.he_first && c.sum_channel < c.he_first + c.n_top))
+            return h->fail(WFS_E_INVALID, "wfs_set_sum_signal: sum_channel lies inside the TPC or the high-energy channel range");
+        if (c.n_top < 0 || c.last_bottom >= c.n_tpc) return h->fail(WFS_E_INVALID, "wfs_set_sum_signal: bottom array outside the TPC channels");
+    }
+    h->sum_on = on != 0;
+    h->ran = false;             // (the row slots of the last wfs_run no longer match: run again before copying)
+    refresh_dev(h);
+    return WFS_OK;
+} WFS_CATCH(h)
+
+// Parity entry: the sum rows before they are finished, S[t] = int(he_factor) * sum of the bottom rows (64 bits)
+int wfs_copy_sum_signal(wfs_handle *h, int32_t *group, int64_t *left, int64_t *right, int64_t *data_off, int64_t *data, int64_t cap_rows, int64_t cap_samples)
+try {
+    if (!h || !h->ran) return WFS_E_STATE;
+    const WfsDev &d = h->dev;
+    if (d.sum_channel < 0 || h->n_groups == 0) { if (cap_rows > 0 && data_off) data_off[0] = 0; return WFS_OK; }
+    const i64 G = h->n_groups;
+    std::vector<i64> lo((size_t)G), hi((size_t)G), off((size_t)G + 1); std::vector<i32> acc((size_t)h->s_sum);
+    HIPCHK(hipMemcpy(lo.data(), h->sum_lo.p, lo.size() * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(hi.data(), h->sum_hi.p, hi.size() * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(off.data(), h->sum_off.p, off.size() * 8, hipMemcpyDeviceToHost));
+    if (h->s_sum) HIPCHK(hipMemcpy(acc.data(), h->raw.as<i32>() + h->sum_base, acc.size() * 4, hipMemcpyDeviceToHost));
+    i64 k = 0, doff = 0;
+    for (i64 g = 0; g < G; g++) {
+        if (lo[g] == I64_MAX) continue;
+        const i64 len = hi[g] - lo[g] + 1 + 2 * (i64)d.tw;
+        if (k >= cap_rows || doff + len > cap_samples) return h->fail(WFS_E_CAPACITY, "sum signal buffer too small");
+        group[k] = (i32)g; left[k] = lo[g] - d.tw; right[k] = hi[g] + d.tw; data_off[k] = doff;
+        for (i64 i = 0; i < len; i++) data[doff + i] = (i64)acc[(size_t)(off[g] + i)] * d.he_factor;
+        doff += len; k++;
+    }
+    if (k < cap_rows) data_off[k] = doff;
     return WFS_OK;
 } WFS_CATCH(h)
 

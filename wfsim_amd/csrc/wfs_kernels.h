@@ -144,6 +144,9 @@ struct GeomArgs {
     i32 force_dense;     // debug: send every tile to the dense kernel
     i32 init_has; i64 init_runmax;      // last_pulse_end_time carried in from earlier batches
     const i64 *noise_override; i64 n_noise_override;
+    // the bottom-array sum row of every window (wfs_set_sum_signal; nullptr when the switch is off): union of the bottom rows' ranges,
+    // its length and its chunks for k_sum_signal
+    i64 *sum_lo, *sum_hi; i32 *sum_len, *sum_nchunk;
 };
 
 #define SPARSE_MAX_PHOTONS 32      // tiles with a handful of photons (S1-like) go to the sorted-list kernel
@@ -294,31 +297,45 @@ __global__ void k_tile_rows(WfsDev d, GeomArgs a)
 {
     i64 tile = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = tile < a.n_tiles && a.tile_count[tile] > 0;
-    i64 left = I64_MAX, right = I64_MIN, g = -1;
+    i64 left = I64_MAX, right = I64_MIN, g = -1; bool bottom = false;
     if (live) {
         i64 set = tile / d.n_tpc; i32 ch = (i32)(tile - set * d.n_tpc);
         i64 bin0, nb;
         tile_bounds(d, a.set_t0[set], a.tile_tmin[tile], a.tile_tmax[tile], left, right, bin0, nb);
         g = a.cl_group[a.set_cluster[set]];
+        bottom = a.sum_lo && ch >= d.n_top && ch <= d.last_bottom;      // the row feeds the window's sum row (rawdata.py:250-254)
         atomicMin(&a.row_lo[g * d.n_tpc + ch], left); atomicMax(&a.row_hi[g * d.n_tpc + ch], right);
         if (a.row_cnt) { atomicAdd(&a.row_cnt[g * d.n_tpc + ch], 1); a.row_tile[g * d.n_tpc + ch] = (i32)tile; }      // (row_tile: only read when the row has ONE tile)
         if (a.res_on) {         // a tile of more than a wave's photons, or one whose pulse exists already, keeps its row off the resident path
             const bool done = a.tile_done && tile < a.n_done && a.tile_done[tile];
-            if (done || a.tile_count[tile] > WAVE_MAX_PHOTONS || nb > WAVE_MAX_BINS) a.row_bad[g * d.n_tpc + ch] = 1;
+            // (so does the sum row: k_sum_signal adds up rows before they are finished, and a resident row only ever exists finished)
+            if (done || a.tile_count[tile] > WAVE_MAX_PHOTONS || nb > WAVE_MAX_BINS || bottom) a.row_bad[g * d.n_tpc + ch] = 1;
         }
     }
+    const i64 bl0 = bottom ? left : I64_MAX, br0 = bottom ? right : I64_MIN;
     // the group's range: the 494 tiles of a pulse set all aim at one address -- reduce inside the wave first when its
     // live lanes share the group (the usual case), one atomic pair per wave instead of 64
     const u64 lm = ballot64(live);
     if (lm == 0) return;
     const i64 g0 = __shfl(g, __ffsll((long long)lm) - 1, 64);
-    if (all64(!live || g == g0)) {
+    const bool one_group = all64(!live || g == g0);
+    if (one_group) {
         for (int o = 32; o > 0; o >>= 1) {
             const i64 l2 = __shfl_xor(left, o, 64), r2 = __shfl_xor(right, o, 64);
             left = l2 < left ? l2 : left; right = r2 > right ? r2 : right;
         }
         if ((threadIdx.x & 63) == 0) { atomicMin(&a.grp_lo[g0], left); atomicMax(&a.grp_hi[g0], right); }
     } else if (live) { atomicMin(&a.grp_lo[g], left); atomicMax(&a.grp_hi[g], right); }
+    // the range of the window's sum row: the same reduction over the bottom-array tiles (wave-uniform branches)
+    if (!any64(bottom)) return;
+    if (one_group) {
+        i64 bl = bl0, br = br0;
+        for (int o = 32; o > 0; o >>= 1) {
+            const i64 l2 = __shfl_xor(bl, o, 64), r2 = __shfl_xor(br, o, 64);
+            bl = l2 < bl ? l2 : bl; br = r2 > br ? r2 : br;
+        }
+        if ((threadIdx.x & 63) == 0) { atomicMin(&a.sum_lo[g0], bl); atomicMax(&a.sum_hi[g0], br); }
+    } else if (bottom) { atomicMin(&a.sum_lo[g], bl0); atomicMax(&a.sum_hi[g], br0); }
 }
 
 // per group: window (rawdata.py:215-224) and the noise offset (rawdata.py:407-417)
@@ -344,6 +361,10 @@ __global__ void k_group_final(WfsDev d, GeomArgs a)
     a.grp_ixrand[g] = ix;
 }
 
+// the last row slot of a window is its bottom-array sum row when the switch is on (wfs_set_sum_signal)
+#define SUM_CHUNK 1024             // samples of a sum row per workgroup of k_sum_signal
+__device__ __forceinline__ bool row_slot_is_sum(const WfsDev &d, i32 slot) { return d.sum_channel >= 0 && slot == d.row_slots - 1; }
+
 __device__ __forceinline__ bool row_is_direct(const i32 *tile_done, i64 n_done, const i32 *row_cnt, const i32 *row_tile, i64 ridx)
 {
     if (!tile_done || row_cnt[ridx] != 1) return false;
@@ -363,9 +384,20 @@ __global__ void k_row_len(WfsDev d, GeomArgs a)
     i32 cap = 0, rk = -1; bool resident = false, longrow = false;
     if (idx < n) {
         const i64 g = idx / d.row_slots; const i32 slot = (i32)(idx - g * d.row_slots);
+        const bool sum = row_slot_is_sum(d, slot);
         const i32 ch = slot < d.n_tpc ? slot : slot - d.n_tpc;         // HE slot -> its top channel
-        const i64 lo = a.row_lo[g * d.n_tpc + ch];
-        if (lo != I64_MAX) {
+        const i64 lo = sum ? a.sum_lo[g] : a.row_lo[g * d.n_tpc + ch];
+        if (sum) {
+            // the sum row spans the union of the window's bottom rows (rawdata.py:234-235, 258-259); an accumulator row like any other,
+            // filled by k_sum_signal in SUM_CHUNK samples per workgroup
+            if (lo != I64_MAX) {
+                const i64 len = a.sum_hi[g] - lo + 1 + 2 * (i64)d.tw;
+                i64 hold = 2 * (i64)d.tw + 1; if (hold < 1) hold = 1;
+                cap = (i32)((len + hold) / (hold + 1));
+                a.sum_len[g] = (i32)len; a.sum_nchunk[g] = (i32)((len + SUM_CHUNK - 1) / SUM_CHUNK);
+                rk = atomicAdd(&s_n, 1);
+            }
+        } else if (lo != I64_MAX) {
             const i64 len = a.row_hi[g * d.n_tpc + ch] - lo + 1 + 2 * (i64)d.tw;
             i64 hold = 2 * (i64)d.tw + 1; if (hold < 1) hold = 1;
             cap = (i32)((len + hold) / (hold + 1));
@@ -1501,6 +1533,8 @@ struct ZleArgs {
     // resident rows (k_row_pulse): the rows behind the first n_front of the row list; their finished 16-bit samples
     i64 n_front, n_short, rows_cap; const i64 *res_toff, *fin_off; int16_t *fin; const i32 *res_long; struct ResRow *res_rows;
     struct PackDesc *pdesc;      // [n_active_rows] what k_pack needs of a row, in one scalar load (k_pack_desc)
+    // sum rows (k_sum_signal): range per window, first sample of the window's row behind raw[sum_base]
+    const i64 *sum_lo, *sum_hi, *sum_off; i64 sum_base;
 };
 
 // One 64-byte descriptor per active row (thread per row: the divisions and the five dependent look-ups of a row are
@@ -1525,6 +1559,17 @@ __global__ void k_row_desc(WfsDev d, ZleArgs a)
     // row list order: accumulator rows | short resident rows (from the end of active_rows backwards, k_row_len) | long resident rows
     const i64 idx = r < a.n_front ? a.active_rows[r] : (r < a.n_front + a.n_short ? a.active_rows[a.rows_cap - 1 - (r - a.n_front)] : a.res_long[r - a.n_front - a.n_short]);
     const i64 g = idx / d.row_slots; const i32 slot = (i32)(idx - g * d.row_slots);
+    if (row_slot_is_sum(d, slot)) {
+        // the window's sum row: an accumulator row (src 0) behind the accumulators proper, times int(he_factor) when it is finished
+        // like an HE row (rawdata.py:242, 251-254), noise column and threshold of the sum channel
+        RowDesc q;
+        q.acc_off = a.sum_base + a.sum_off[g]; q.row_abs = a.sum_lo[g] - d.tw; q.ixr = a.grp_ixrand[g]; q.itv_base = a.itv_off[idx];
+        q.thr = d.thr_zle[d.sum_channel]; q.idx = idx; q.len = (i32)(a.sum_hi[g] - a.sum_lo[g] + 1 + 2 * (i64)d.tw);
+        q.channel = d.sum_channel; q.he = 1; q.src = 0;
+        a.desc[r] = q;
+        if (a.key_base) { atomicMin(&a.key_base->key_origin, q.row_abs); atomicMax(&a.key_base->key_end, q.row_abs + (i64)q.len); }
+        return;
+    }
     const bool he = slot >= d.n_tpc; const i32 acc_ch = he ? slot - d.n_tpc : slot, channel = he ? d.he_first + acc_ch : slot;
     const i64 ridx = g * d.n_tpc + acc_ch;
     RowDesc q;
@@ -1561,9 +1606,11 @@ __device__ __forceinline__ i32 finish_sample(const WfsDev &d, const i32 *acc, i6
     return v < 0 ? 0 : (i32)v;
 }
 
+// (acc_ch -1: the window's sum row, which has no accumulator row of a channel behind it)
 __device__ __forceinline__ void row_of_slot(const WfsDev &d, i64 idx, i64 &g, i32 &channel, i32 &acc_ch, bool &he)
 {
     g = idx / d.row_slots; i32 slot = (i32)(idx - g * d.row_slots);
+    if (row_slot_is_sum(d, slot)) { he = true; acc_ch = -1; channel = d.sum_channel; return; }
     he = slot >= d.n_tpc; acc_ch = he ? slot - d.n_tpc : slot; channel = he ? d.he_first + acc_ch : slot;
 }
 
@@ -1802,6 +1849,82 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
     if (lane == 0 && count > 0) nrec += close_interval(count - 1, open_left, carry_last);
     for (int o = 32; o > 0; o >>= 1) nrec += __shfl_down(nrec, o, 64);
     if (lane == 0) { a.itv_n[idx] = count; a.row_nrec[idx] = nrec; }
+}
+
+// The bottom-array sum row of a window (wfs_set_sum_signal): row 800 of the reference's digitiser array, the per-pulse rounded ADC
+// wave of every bottom PMT added up (rawdata.py:250-254, sum_signal at :392-396).  The reference never masks that row in, so it is
+// never finished or emitted there; here it becomes one more accumulator row of the window.  A pass over rows that exist already: the
+// i32 accumulators and the sample buffers of single-tile rows (k_tile_rows keeps bottom rows off the resident path).  One workgroup
+// per (window, SUM_CHUNK samples of its sum row): the window's bottom rows that reach into the chunk are listed in LDS once -- offset
+// into raw or tbuf, first sample relative to the chunk, length --, then every lane walks the list for its four samples, 256 apart, so
+// that a wave's load is 256 consecutive bytes.  Row bases and ranges are wave-uniform and travel in SGPRs (readfirstlane of the LDS
+// broadcast); loads are unconditional (a lane outside the row reads the row's sample 0 and drops it), two rows -- eight loads -- in flight.
+// The sum is carried in 64 bits and stored saturated to 32: the factor int(he_factor) is applied where the row is finished.
+struct SumArgs {
+    const i64 *chunk_off; i64 n_gslots;          // exclusive scan of the windows' chunk counts: workgroup -> (window, chunk)
+    const i64 *sum_lo, *sum_off; const i32 *sum_len;
+    const i64 *row_lo, *row_hi, *acc_off; const i32 *raw, *tbuf;
+    const i32 *tile_done, *row_cnt, *row_tile, *ins_bcap; const i64 *ins_boff; i64 n_done;      // rows read from a tile buffer in place
+    i32 *out;                                    // raw + sum_base
+};
+__global__ __launch_bounds__(256) void k_sum_signal(WfsDev d, SumArgs a)
+{
+    __shared__ i64 s_off[WFS_MAX_CH + 1]; __shared__ i32 s_rel[WFS_MAX_CH + 1], s_len[WFS_MAX_CH + 1]; __shared__ i32 s_n;      // (+1: the list is walked in pairs)
+    const i64 b = blockIdx.x;
+    // window of the workgroup: the last one whose first chunk is not behind b (scalar loads; windows without a sum row have no chunks)
+    i64 g = 0;
+    { i64 hi = a.n_gslots; while (hi - g > 1) { const i64 mid = (g + hi) >> 1; if (a.chunk_off[mid] <= b) g = mid; else hi = mid; } }
+    const i32 len = a.sum_len[g];
+    const i32 s0 = (i32)(b - a.chunk_off[g]) * SUM_CHUNK;
+    if (s0 >= len) return;                                  // (cannot happen: the grid is the scan's total)
+    const i64 slo = a.sum_lo[g];
+    if (threadIdx.x == 0) s_n = 0;
+    __syncthreads();
+    const i32 n_bottom = d.last_bottom - d.n_top + 1;       // (<= n_tpc <= WFS_MAX_CH, wfs_create)
+    for (i32 t = threadIdx.x; t < n_bottom; t += blockDim.x) {
+        const i64 ridx = g * d.n_tpc + d.n_top + t;
+        const i64 lo = a.row_lo[ridx];
+        if (lo == I64_MAX) continue;
+        const i32 rel = (i32)(lo - slo) - s0, rl = (i32)(a.row_hi[ridx] - lo + 1 + 2 * (i64)d.tw);      // both rows start tw samples ahead of their first pulse
+        if (rel >= SUM_CHUNK || rel + rl <= 0) continue;
+        i64 off;                                                // sample offset into raw, or ~(offset into tbuf)
+        if (row_is_direct(a.tile_done, a.n_done, a.row_cnt, a.row_tile, ridx)) {
+            const i32 tile = a.row_tile[ridx]; const i32 ins = tile / d.n_tpc;
+            off = ~(a.ins_boff[ins] + (i64)(tile - ins * d.n_tpc) * a.ins_bcap[ins]);
+        } else off = a.acc_off[ridx];
+        const i32 k = atomicAdd(&s_n, 1);
+        s_off[k] = off; s_rel[k] = rel; s_len[k] = rl;
+    }
+    __syncthreads();
+    const i32 n = s_n;
+    if (threadIdx.x == 0) { s_off[n] = s_off[0]; s_rel[n] = 0; s_len[n] = 0; }      // an empty row closes an odd list (a chunk between two pulses far apart has no row at all: the loop below is not entered, zeros are stored)
+    __syncthreads();
+    i64 acc[4] = {0, 0, 0, 0};
+    for (i32 k = 0; k < n; k += 2) {                            // two rows, eight loads in flight
+        const i32 *p[2]; i32 rel[2], rl[2]; i32 v[2][4];
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+            const i64 ob = s_off[k + q];
+            const i64 off = (i64)(((u64)(u32)__builtin_amdgcn_readfirstlane((i32)(u32)((u64)ob >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((i32)(u32)(u64)ob));
+            p[q] = off < 0 ? a.tbuf + ~off : a.raw + off;       // (kernel arguments: the loads keep their global address space and a scalar base)
+            rel[q] = __builtin_amdgcn_readfirstlane(s_rel[k + q]); rl[q] = __builtin_amdgcn_readfirstlane(s_len[k + q]);
+        }
+#pragma unroll
+        for (int q = 0; q < 2; q++)
+#pragma unroll
+            for (int u = 0; u < 4; u++) { const i32 j = (i32)threadIdx.x + 256 * u - rel[q]; v[q][u] = p[q][(u32)j < (u32)rl[q] ? j : 0]; }
+#pragma unroll
+        for (int q = 0; q < 2; q++)
+#pragma unroll
+            for (int u = 0; u < 4; u++) { const i32 j = (i32)threadIdx.x + 256 * u - rel[q]; acc[u] += (u32)j < (u32)rl[q] ? (i64)v[q][u] : 0; }
+    }
+    i32 *out = a.out + a.sum_off[g];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const i32 s = s0 + (i32)threadIdx.x + 256 * u;
+        const i64 c = acc[u] > 0x7fffffffLL ? 0x7fffffffLL : (acc[u] < -0x80000000LL ? -0x80000000LL : acc[u]);
+        if (s < len) out[s] = (i32)c;
+    }
 }
 
 // Resident rows: ONE wave makes a whole (window, channel) row -- zeroes it in LDS, adds the rounded pulses of the row's tiles

@@ -109,7 +109,8 @@ EXPORTS = ['wfs_create', 'wfs_destroy', 'wfs_last_error', 'wfs_device_count', 'w
            'wfs_copy_records_range_async', 'wfs_wait_records', 'wfs_host_register', 'wfs_host_unregister',
            'wfs_set_gas_gap_model', 'wfs_set_instruction_gas_gap', 'wfs_set_pattern_map_points', 'wfs_set_instruction_aft',
            'wfs_scalar_map_grid', 'wfs_scalar_map_points', 'wfs_scalar_map_spline', 'wfs_scalar_map_eval', 'wfs_set_noise_float', 'wfs_set_instruction_diffusion',
-           'wfs_scalar_map_grid_array', 'wfs_scalar_map_points_array', 'wfs_scalar_map_linear', 'wfs_scalar_map_eval_array']
+           'wfs_scalar_map_grid_array', 'wfs_scalar_map_points_array', 'wfs_scalar_map_linear', 'wfs_scalar_map_eval_array',
+           'wfs_set_sum_signal', 'wfs_copy_sum_signal']
 
 
 def load_library():
@@ -209,6 +210,9 @@ class Engine:
         self.tile_local_bright = bool(params['tile_local_bright'])
         if not self.tile_local_bright:         # (the library's default is on)
             self._check(self.lib.wfs_set_bright_tiles(self._h, C.c_int32(0)))
+        # the bottom-array sum channel (config 'emit_sum_signal'; the library's default is off): XENONnT only (rawdata.py:241)
+        self._check(self.lib.wfs_set_sum_signal(self._h, C.c_int32(params['sum_signal'])))
+        self.emits_sum_records = bool(params['sum_signal'] and params['detector_nt'])
         if self.keep_photons or os.environ.get('WFS_CHECK_LAUNCHES', '0') not in ('', '0'):
             self.set_debug(False)          # (every launch checked from the first run on)
         # HE records exist only when the HE rows can differ from a flat baseline (wfs_engine.hip refresh_dev): a non-zero
@@ -568,6 +572,17 @@ class Engine:
         data = np.zeros(total, dtype=np.int32)
         self._check(self.lib.wfs_copy_row_data(self._h, _p(data), C.c_int64(total)))
         return dict(group=g, channel=ch, left=left, right=right, data_off=off, data=data)
+
+    def sum_signal(self):
+        """the bottom-array sum rows of the last run before they are finished (config 'emit_sum_signal'): per row its window, its
+        absolute first and last sample and S[t] = int(he_factor) * sum of the bottom rows, at data[data_off[k]:data_off[k + 1]]"""
+        n, total = self.counts['n_groups'], self.counts['n_raw_samples']
+        g = np.zeros(n, np.int32)
+        left, right, off = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n + 1, np.int64)
+        data = np.zeros(total, dtype=np.int64)
+        self._check(self.lib.wfs_copy_sum_signal(self._h, _p(g), _p(left), _p(right), _p(off), _p(data), C.c_int64(n + 1), C.c_int64(total)))
+        k = int(np.argmax(off))         # rows: data_off rises up to the total, the entries behind it stay 0
+        return dict(group=g[:k], left=left[:k], right=right[:k], data_off=off[:k + 1], data=data[:int(off[k])])
 
     def _caller_sets(self, s):
         """rows of the library's pulse sets that belong to the caller's run sets (None: all of them, in order): primaries, then -- when the

@@ -387,15 +387,15 @@ class ChunkRawRecords(object):
         elif det == 'XENONnT':
             he = self.config['channel_map']['he']
             engine = getattr(self.rawdata, 'engine', None)
-            if in_chunk is None and engine is not None and not engine.emits_he_records:
-                # every record is a TPC record (no HE rows are digitised, row 800 is never emitted): the buffer's prefix as it is
+            if in_chunk is None and engine is not None and not engine.emits_he_records and not getattr(engine, 'emits_sum_records', False):
+                # every record is a TPC record (no HE rows are digitised, the sum row is not asked for): the buffer's prefix as it is
                 empty = records[:0].copy()
                 records, moved = self._hand_out(n_out)
                 yield dict(raw_records=records, raw_records_he=empty, raw_records_aqmon=empty.copy(), truth=_truth)
             else:
                 ch = records['channel']
                 yield dict(raw_records=records[ch < he[0]], raw_records_he=records[(ch >= he[0]) & (ch <= he[-1])],
-                           raw_records_aqmon=records[ch == 800], truth=_truth)
+                           raw_records_aqmon=records[ch == self.config['channel_map']['sum_signal']], truth=_truth)
         if moved:
             return                  # _hand_out switched buffers and moved the records behind the cut
         if in_chunk is None:
