@@ -3,7 +3,7 @@ photons and pulse in one workgroup of 1024 threads, the tile's whole H table in 
 
 Every case is a handful of instructions with s2_secondary_sc_gain = 100 under a constant hit pattern whose one or two hot channels
 steer the tile sizes, compared with the CPU oracle as tests/test_gpu_generation.py does: photons, digitise windows, record bytes, n_pe.
-Which kernel made a tile is read back with Engine.tile_kernels() (0 none, 1 k_s2_tile<FULL>, 2 generation only + pulse kernels,
+Which kernel made a tile is read back with Engine.tile_kernels() (0 none, 1 k_s2_tile, 2 generation only + pulse kernels,
 3 k_s2_bright).  Photon q of a tile has the same Philox coordinates whichever kernel draws it, so the oracle is the comparand as it is.
 
 Sizes at z = -8 cm (bundled config): the surviving electrons of an S2 arrive within ~4 us, the S2 delay table has 8192 cells, so the
@@ -66,7 +66,7 @@ def _tile_photons(eng, n_ins):
 
 
 def _expected_kinds(s_ins, n_tile):
-    """every tile of an S2 above 2048 photons by k_s2_bright, the others with photons by k_s2_tile<FULL>; S1s are not tile-generated"""
+    """every tile of an S2 above 2048 photons by k_s2_bright, the others with photons by k_s2_tile; S1s are not tile-generated"""
     kind = np.where(n_tile > BRIGHT, 3, np.where(n_tile > 0, 1, 0))
     kind[s_ins['type'] != 2] = 0
     return kind.astype(np.int8)
@@ -119,7 +119,7 @@ def test_bright_tiles_take_the_fused_kernel(monkeypatch):
     _compare(orc, o, eng, counts, s_ins)
     _assert_truth_rows(eng, o)
     per_pmt = eng.truth_per_pmt()
-    for ch in (17, 300, 5):          # (channel 5: a tile of k_s2_tile<FULL> next to them)
+    for ch in (17, 300, 5):          # (channel 5: a tile of k_s2_tile next to them)
         ref = _oracle_truth_per_pmt(eng.config, o, 0, ch)
         assert ref[3] > ref[2] > 0
         assert np.allclose(per_pmt[0, ch], ref, rtol=1e-9), (ch, per_pmt[0, ch], ref)
@@ -186,19 +186,27 @@ def test_bright_tiles_sharing_a_row():
     _assert_truth_rows(eng, o)
 
 
-@pytest.mark.parametrize('scale', [1.0, 4.0])
-def test_pmt_afterpulses_of_bright_tiles(scale):
+# (the cases of the default route keep the ids they had before the second parameter)
+@pytest.mark.parametrize('scale,tile_local_bright', [pytest.param(1.0, True, id='1.0'), pytest.param(4.0, True, id='4.0'),
+                                                     pytest.param(1.0, False, id='1.0-photon_array'), pytest.param(4.0, False, id='4.0-photon_array')])
+def test_pmt_afterpulses_of_bright_tiles(scale, tile_local_bright):
     """PMT afterpulses on: every photon of a bright tile is screened inside its pass and the candidates leave as one key-ordered
     stretch per tile (k_ap_seg places the afterpulse tile in generation order).  The hot tile of ~22000 photons has more candidates
     than the workgroup's stage holds (AP_STAGE = 128) -- with the afterpulse probabilities x 4 so has the one of ~4400 --: the excess
-    takes the overflow path.  Device == oracle photon by photon, the afterpulse sets included."""
+    takes the overflow path.  Device == oracle photon by photon, the afterpulse sets included.  tile_local_bright = False: the same
+    tiles through the generation-only kernel (k_s2_tile_gen, passes of 2048 photons, 256 threads), which screens and flushes with the
+    same steps."""
     ap = ap_tables_from_golden()
     for name in ap:
         ap[name] = dict(ap[name], delaytime_cdf=ap[name]['delaytime_cdf'] * scale)
-    cfg = dict(xenonnt_test_config(s2_secondary_sc_gain=100.0), seed=78)
+    cfg = dict(xenonnt_test_config(s2_secondary_sc_gain=100.0, tile_local_bright=tile_local_bright), seed=78)
     orc, o, eng, counts, s_ins = _run(cfg, THREE_SIZES, _pattern(THREE_SIZES_PATTERN), ap=ap)
     kind = eng.tile_kernels()
-    assert kind.shape == (len(s_ins), NCH) and (kind == 3).sum() == 3 and not (kind == 2).any()
+    assert kind.shape == (len(s_ins), NCH)
+    if tile_local_bright:
+        assert (kind == 3).sum() == 3 and not (kind == 2).any()
+    else:
+        assert (kind == 2).sum() == 3 and not (kind == 3).any()
     ph = eng.photons()
     n = len(s_ins)
     big = int(np.argmax(np.diff(ph['set_off'])[:n]))

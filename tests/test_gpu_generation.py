@@ -130,7 +130,7 @@ def test_mixed_clusters_and_large_s2():
 
 def test_tiles_above_one_register_batch():
     """an S2 of ~4x10^6 PE: ~6000 photons per PMT, more than the 2048 a pulse workgroup keeps in registers -> its tiles are generated
-    in passes (k_s2_tile<!FULL>, photons to the photon array in generation order) and pulsed by the dense kernel, one workgroup per
+    in passes (k_s2_tile_gen, photons to the photon array in generation order) and pulsed by the dense kernel, one workgroup per
     (tile, window); a second, small S2 rides along in the same launch"""
     cfg = xenonnt_test_config(s2_secondary_sc_gain=100.0)
     rows = [dict(type=2, time=MS, x=2, y=-1, z=-12, amp=40000), dict(type=2, time=3 * MS, x=0, y=0, z=-30, amp=200),

@@ -177,7 +177,7 @@ def test_add_current_vectors_on_the_device(fma):
 @pytest.mark.parametrize('fma', [False, True], ids=['exact', 'fused'])
 def test_s2_tile_pulses_against_the_oracle_on_reported_photons(fma):
     """k_s2_tile cannot take injected photons.  A batch of tile-generated S2s whose tiles hold 1 to about 2000 photons keeps its photons
-    (debug bit 4 only: k_s2_tile<FULL> makes the pulses); the photons the device reports go to the oracle's pulse_call with preassigned
+    (debug bit 4 only: k_s2_tile makes the pulses); the photons the device reports go to the oracle's pulse_call with preassigned
     gains, whose arithmetic the designed fixtures pin on the reference -- the records must be the same bytes, whatever the generators
     agree on"""
     from tests.test_gpu_generation import _instructions, MS

@@ -259,7 +259,7 @@ struct WfsScal {
     i64 key_origin;         // first sample of the batch, origin of the record sort keys.  host fill, k_row_desc -> k_rec_keys, host
     i64 n_tbuf_samples;     // samples of all tile buffers.  scan of ins_bcap_all -> host
     i64 n_tilegen_photons;  // photons of the tile-generated instructions.  k_tile_counts -> host
-    i64 n_full_tiles;       // tiles of k_s2_tile<FULL>, listed from the front of FuseArgs::tiles.  k_tile_counts -> host
+    i64 n_full_tiles;       // tiles of k_s2_tile, listed from the front of FuseArgs::tiles.  k_tile_counts -> host
     i64 n_direct_samples;   // samples of the rows read from a tile buffer in place.  k_row_len -> host
     i64 n_shared_rows;      // rows that several tiles of k_s2_tile share (k_tile_add is needed).  k_row_len -> host
     i64 n_gen_tiles;        // generation-only tiles, listed from the back of FuseArgs::tiles.  k_tile_counts -> host

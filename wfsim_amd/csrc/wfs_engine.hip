@@ -9,10 +9,8 @@
 
 // Every pulse kernel exists in two forms: FMA = true (wfs_config.fma, one rounding per template * gain term) and FMA = false (numpy's two
 // roundings, currents bit-exact with the reference).  The handle's switch picks one at launch time.
-#define K_S2_TILE_FULL(F) k_s2_tile<true, false, F>
-#define K_S2_TILE_FULL_AP(F) k_s2_tile<true, true, F>
-#define K_S2_TILE_GEN(F) k_s2_tile<false, false, F>
-#define K_S2_TILE_GEN_AP(F) k_s2_tile<false, true, F>
+#define K_S2_TILE(F) k_s2_tile<false, F>
+#define K_S2_TILE_AP(F) k_s2_tile<true, F>
 #define K_S2_BRIGHT(F) k_s2_bright<false, F>
 #define K_S2_BRIGHT_AP(F) k_s2_bright<true, F>
 #define K_PULSE_256_RES(F) k_pulse<256, true, F>
@@ -82,7 +80,7 @@ struct wfs_handle {
     ApElem ap[WFS_MAX_AP];
     // instructions
     i64 n_ins = 0, n_psets = 0, n_sets = 0, n_clusters = 0, n_emitters = 0, n_photons = 0, n_tiles = 0;
-    DevBuf ins_type, ins_time, ins_amp, ins_gid, ins_p, ins_dm, ins_ds, ins_sc, ins_cdfrow, cdf_table, cdf_guide, chan_alias, em_off, em_zg, ins_embase, ins_set, set_ins_off, set_ins_list;
+    DevBuf ins_type, ins_time, ins_amp, ins_gid, ins_p, ins_dm, ins_ds, ins_sc, ins_cdfrow, cdf_table, chan_alias, em_off, em_zg, ins_embase, ins_set, set_ins_off, set_ins_list;
     DevBuf set_cluster, set_t0, set_mode, cl_tmin, cl_gid, cl_end, cl_group;
     DevBuf em_time, em_nph, em_ins, em_ph_off, el_stat, el_minmax, blk_e, blk_base, blk_cnt, blk_ins, eblk_ins, ins_ph0, blk_desc;
     DevBuf tile_count, tile_off, tile_cursor, tile_tmin, tile_tmax, active_tiles, sparse_tiles, dense_tiles, wave_tiles;
@@ -140,7 +138,7 @@ struct wfs_handle {
     DevBuf huge_start, huge_cbeg, huge_keys, huge_keys2, huge_vals, huge_vals2, huge_rec, huge_gain;      // ordering of tiles beyond TILE_ORDER_MAX photons
     DevBuf row_pmax, ins_fused, ins_nsurv, ins_bcap, ins_bcap_all, ins_boff, et32, ftiles, tbuf, row_cnt, row_tile, tile_done, tile_kind;
     bool fuse_on = false, fuse_full = false, run_sets_given = false, sets_aligned = true, any_s2 = false;
-    i64 n_fused_tiles = 0 /* made by k_s2_tile<FULL> */, n_gen_tiles = 0 /* tile-generated, pulse by the ordinary kernels */, p_fused = 0, s_raw_direct = 0;
+    i64 n_fused_tiles = 0 /* made by k_s2_tile */, n_gen_tiles = 0 /* tile-generated, pulse by the ordinary kernels */, p_fused = 0, s_raw_direct = 0;
     i64 n_bright_tiles = 0;      // made by k_s2_bright
     bool bright_on = true;       // wfs_set_bright_tiles
     // the bottom-array sum row (wfs_set_sum_signal, k_sum_signal): range, length, chunks and offsets per window; the rows' samples sit
@@ -524,7 +522,7 @@ try {
     WFS_BIG_LDS_F(K_ROW_PULSE_0, 128); WFS_BIG_LDS_F(K_ROW_PULSE_1, 128); WFS_BIG_LDS_F(K_ROW_PULSE_2, 128);
     if (const char *e = getenv("WFS_ROW_RESIDENT")) h->res_env = atoi(e);          // 0 / 1 / 2 as the config switch (A/B runs)
     if (const char *e = getenv("WFS_RES_MAX_LEN")) h->res_max_len = std::max(256, std::min(atoi(e), 7168)) / 256 * 256;      // tuning knob (results do not depend on it)
-    WFS_BIG_LDS_F(K_S2_TILE_FULL, 100); WFS_BIG_LDS_F(K_S2_TILE_FULL_AP, 100); WFS_BIG_LDS_F(K_S2_TILE_GEN, 100); WFS_BIG_LDS_F(K_S2_TILE_GEN_AP, 100);
+    WFS_BIG_LDS_F(K_S2_TILE, 100); WFS_BIG_LDS_F(K_S2_TILE_AP, 100);
     WFS_BIG_LDS_F(K_PULSE_SPARSE_64, 100); WFS_BIG_LDS_F(K_PULSE_SPARSE_256, 100);
     {   // k_s2_bright: what the device grants one workgroup, less the SPE row, the afterpulse stage and the kernel's static arrays
         int granted = 0;
@@ -560,7 +558,7 @@ try {
     }
 #endif
     DevBuf *all[] = {&h->rec_key, &h->rec_key2, &h->rec_val, &h->rec_val2, &h->rec_dest, &h->sort_tmp, &h->row_desc, &h->pmap[0].values, &h->pmap[1].values, &h->map_row_ins[0], &h->map_row_ins[1], &h->map_row_id[0], &h->map_row_id[1], &h->map_x, &h->map_y, &h->map_z, &h->map_nb_idx[0], &h->map_nb_idx[1], &h->map_nb_w[0], &h->map_nb_w[1], &h->d_tabs, &h->gg_inv, &h->ins_gg, &h->ins_ggw, &h->ins_ggsum, &h->prop_top, &h->prop_bot, &h->ins_tab, &h->ins_tabb, &h->ins_pzi, &h->ins_pzf, &h->blk_e, &h->blk_base, &h->blk_cnt, &h->blk_ins, &h->eblk_ins, &h->ins_ph0, &h->blk_desc, &h->noise_override, &h->ap_ins, &h->ap_ch, &h->ap_t, &h->ap_gain, &h->ap_cand, &h->ap_args_dev, &h->ap_seg, &h->set_gid, &h->opt_t, &h->opt_item, &h->opt_first, &h->opt_last, &h->opt_ch, &h->opt_time, &h->t_templates, &h->t_spe, &h->t_gains, &h->t_thr_truth, &h->t_thr_zle, &h->t_lumx, &h->t_lumt, &h->t_noise, &h->t_noise_f,
-        &h->ins_type, &h->ins_time, &h->ins_amp, &h->ins_gid, &h->ins_p, &h->ins_dm, &h->ins_ds, &h->ins_sc, &h->ins_cdfrow, &h->cdf_table, &h->cdf_guide, &h->chan_alias, &h->ins_embase, &h->ins_set, &h->set_ins_off, &h->set_ins_list,
+        &h->ins_type, &h->ins_time, &h->ins_amp, &h->ins_gid, &h->ins_p, &h->ins_dm, &h->ins_ds, &h->ins_sc, &h->ins_cdfrow, &h->cdf_table, &h->chan_alias, &h->ins_embase, &h->ins_set, &h->set_ins_off, &h->set_ins_list,
         &h->em_off, &h->em_zg, &h->pois_cdf, &h->pois_kmin, &h->set_cluster, &h->set_t0, &h->set_mode, &h->cl_tmin, &h->cl_gid, &h->cl_end, &h->cl_group, &h->em_time, &h->em_nph,
         &h->em_ins, &h->em_ph_off, &h->el_stat, &h->el_minmax, &h->tile_count, &h->tile_off, &h->tile_cursor, &h->tile_tmin, &h->tile_tmax,
         &h->active_tiles, &h->sparse_tiles, &h->dense_tiles, &h->wave_tiles, &h->ph, &h->ph_gain, &h->grp_lo, &h->grp_hi, &h->grp_left, &h->grp_right, &h->grp_ixrand,
@@ -813,23 +811,10 @@ try {
         for (i64 i = 0; i < n; i++) if (rows[i] < 0) { rows[i] = (i32)(n_cdf + (i64)h->dev_row_ins.size()); h->dev_row_ins.push_back((i32)i); }
         h->dev_rows_pending = !h->dev_row_ins.empty(); h->ins_aft_set = false; h->n_diff_rows = 0; h->ins_diff.clear();
         const size_t total = (size_t)n_cdf + h->dev_row_ins.size();
-        TRY(ensure(h, h->cdf_table, total * h->cfg.n_tpc * 8)); TRY(ensure(h, h->cdf_guide, total * (CDF_G + 2) * 2));
+        TRY(ensure(h, h->cdf_table, total * h->cfg.n_tpc * 8));
         TRY(upload(h, h->ins_cdfrow, rows.data(), (size_t)n * 4)); HIPCHK(hipStreamSynchronize(h->stream));
     }
     TRY(upload(h, h->cdf_table, cdf_table, (size_t)n_cdf * h->cfg.n_tpc * 8));
-    {   // guide table of every channel-CDF row: guide[c] = first channel whose cumulative probability exceeds c / CDF_G
-        const int nch = h->cfg.n_tpc;
-        std::vector<unsigned short> guide((size_t)n_cdf * (CDF_G + 2));
-        for (int r = 0; r < n_cdf; r++) {
-            const double *row = cdf_table + (size_t)r * nch; int ch = 0;
-            for (int c = 0; c <= CDF_G + 1; c++) {
-                const double x = (double)c / CDF_G;
-                while (ch < nch - 1 && row[ch] <= x) ch++;
-                guide[(size_t)r * (CDF_G + 2) + c] = (unsigned short)ch;
-            }
-        }
-        TRY(upload(h, h->cdf_guide, guide.data(), guide.size() * 2));
-    }
     TRY(upload(h, h->em_off, em_off.data(), em_off.size() * 8));
     {
         std::vector<i32> sc((size_t)S), sm((size_t)S, 0); std::vector<i64> st((size_t)S);
@@ -1134,7 +1119,7 @@ try {
         m.aft = (w == 1 && h->ins_aft_set) ? h->ins_aft.as<double>() : nullptr; m.n_top = h->cfg.n_top;
         m.x = h->map_x.as<float>(); m.y = h->map_y.as<float>(); m.z = h->map_z.as<float>();
         m.nb_idx = h->map_nb_idx[w].as<i64>(); m.nb_w = h->map_nb_w[w].as<double>();
-        m.cdf_table = h->cdf_table.as<double>(); m.cdf_guide = h->cdf_guide.as<unsigned short>(); m.gains = h->t_gains.as<double>();
+        m.cdf_table = h->cdf_table.as<double>(); m.gains = h->t_gains.as<double>();
         launch_neighbours(h, m);
         { Timer t(h, "k_map_rows"); hipLaunchKernelGGL(k_map_rows, dim3((unsigned)nr), dim3(256), (size_t)nch * 8, h->stream, m, nch); }
     }
@@ -1317,7 +1302,7 @@ try {
 // ---------------------------------------------------------------------------------------------- run
 // the batch came through wfs_load_instructions: its photons are made on the device (run_generation)
 static bool from_generator(const wfs_handle *h) { return !h->injected && !h->optical; }
-// pulses made by k_s2_tile<FULL> (wfs_tilegen.h): their tiles are on no work list
+// pulses made by k_s2_tile (wfs_tilegen.h): their tiles are on no work list
 static bool tiles_made(const wfs_handle *h) { return from_generator(h) && h->fuse_full && h->n_fused_tiles + h->n_bright_tiles > 0; }
 // tiles that drew their own photons, whichever kernel made them
 static i64 n_tilegen_tiles(const wfs_handle *h) { return h->n_fused_tiles + h->n_gen_tiles + h->n_bright_tiles; }
@@ -1352,7 +1337,7 @@ static int gen_electrons(wfs_handle *h, GenRun &r)
     g.ins_embase = h->ins_embase.as<u32>(); g.ins_set = h->ins_set.as<i32>(); g.set_ins_off = h->set_ins_off.as<i64>(); g.set_ins_list = h->set_ins_list.as<i32>(); g.set_t0 = h->set_t0.as<i64>();
     g.ins_type = h->ins_type.as<int8_t>(); g.ins_time = h->ins_time.as<i64>(); g.ins_amp = h->ins_amp.as<i32>(); g.ins_gid = h->ins_gid.as<u32>();
     g.ins_p = h->ins_p.as<double>(); g.ins_dm = h->ins_dm.as<double>(); g.ins_ds = h->ins_ds.as<double>(); g.ins_sc = h->ins_sc.as<double>();
-    g.ins_cdfrow = h->ins_cdfrow.as<i32>(); g.cdf_table = h->cdf_table.as<double>(); g.cdf_guide = h->cdf_guide.as<unsigned short>(); g.em_off = h->em_off.as<i64>();
+    g.ins_cdfrow = h->ins_cdfrow.as<i32>(); g.cdf_table = h->cdf_table.as<double>(); g.em_off = h->em_off.as<i64>();
     g.em_time = h->em_time.as<i64>(); g.em_nph = h->em_nph.as<i32>(); g.em_ins = h->em_ins.as<i32>();
     g.el_stat = h->el_stat.as<double>(); g.el_minmax = h->el_minmax.as<i64>(); g.scal = h->scal.as<WfsScal>();
     const bool ext = r.ext = h->ins_models;
@@ -1416,7 +1401,7 @@ static int gen_electrons(wfs_handle *h, GenRun &r)
         map_args(pm, m);
         m.n_rows = nr; m.row_ins = h->diff_row_ins.as<i32>(); m.row_id = h->diff_row_id.as<i64>();
         m.x = h->map_x.as<float>(); m.y = h->map_y.as<float>(); m.z = h->map_z.as<float>();
-        m.cdf_table = h->cdf_table.as<double>(); m.cdf_guide = h->cdf_guide.as<unsigned short>(); m.gains = h->t_gains.as<double>();
+        m.cdf_table = h->cdf_table.as<double>(); m.gains = h->t_gains.as<double>();
         m.aft = h->ins_aft_set ? h->ins_aft.as<double>() : nullptr; m.n_top = h->cfg.n_top;
         DiffArgs q{nr, m.row_ins, h->ins_sigr.as<double>(), h->ins_siga.as<double>(), h->diff_r2, h->diff_pre.as<double>()};
         { Timer t(h, "k_diffuse_patterns"); hipLaunchKernelGGL(k_diffuse_patterns, dim3((unsigned)nr), dim3(256), 0, h->stream, d, g, m, q); }
@@ -1568,14 +1553,14 @@ static int gen_tile_photons(wfs_handle *h, GenRun &r)
         if (h->n_fused_tiles > 0) {
             Timer t(h, "k_s2_tile");
             const dim3 grid((unsigned)h->n_fused_tiles);
-            if (ap_on) WFS_LAUNCH_F(h, K_S2_TILE_FULL_AP, grid, dim3(256), lds, d, f, tp, app, ap_lds_off, (i64)0, 1, 0);
-            else WFS_LAUNCH_F(h, K_S2_TILE_FULL, grid, dim3(256), lds, d, f, tp, app, ap_lds_off, (i64)0, 1, 0);
+            if (ap_on) WFS_LAUNCH_F(h, K_S2_TILE_AP, grid, dim3(256), lds, d, f, tp, app, ap_lds_off);
+            else WFS_LAUNCH_F(h, K_S2_TILE, grid, dim3(256), lds, d, f, tp, app, ap_lds_off);
         }
         if (h->n_gen_tiles > 0) {
             Timer t(h, "k_s2_tile_gen");
             const dim3 grid((unsigned)h->n_gen_tiles);
-            if (ap_on) WFS_LAUNCH_F(h, K_S2_TILE_GEN_AP, grid, dim3(256), lds, d, f, tp, app, ap_lds_off, TP - 1, -1, (int)h->n_fused_tiles);
-            else WFS_LAUNCH_F(h, K_S2_TILE_GEN, grid, dim3(256), lds, d, f, tp, app, ap_lds_off, TP - 1, -1, (int)h->n_fused_tiles);
+            if (ap_on) hipLaunchKernelGGL(k_s2_tile_gen<true>, grid, dim3(256), (size_t)AP_STAGE * sizeof(ApCand), h->stream, d, f, app, (int)h->n_fused_tiles);
+            else hipLaunchKernelGGL(k_s2_tile_gen<false>, grid, dim3(256), 0, h->stream, d, f, app, (int)h->n_fused_tiles);
         }
         // tiles above 2048 photons whose H table fits the LDS as a whole: photons and pulse in one workgroup of 1024 threads, no photon array
         if (h->n_bright_tiles > 0) {

@@ -128,7 +128,7 @@ struct GeomArgs {
     i32 *sparse_tiles;   // sparse-class tiles (few photons per start bin: sorted-list kernel)
     i32 *dense_tiles;    // everything else (dense H-table kernel, windows over time)
     i32 *wave_tiles;     // medium tiles (at most 64 photons, any width: wave per tile); scal->n_wave_tiles = their number
-    const i32 *tile_done;       // [n_done] 1: the tile's pulse was made by k_s2_tile<FULL> (wfs_tilegen.h): on no work list (or nullptr)
+    const i32 *tile_done;       // [n_done] 1: the tile's pulse was made by k_s2_tile (wfs_tilegen.h): on no work list (or nullptr)
     i64 n_done;                 // primary tiles (the tiles of the afterpulse sets, which follow them, are never done)
     i32 *row_cnt, *row_tile;    // [groups * n_tpc] tiles in the row; one of them
     const i32 *ins_bcap; const i64 *ins_boff;      // tile sample buffers (wfs_tilegen.h)
@@ -2235,7 +2235,6 @@ struct GenArgs {
     const i64 *set_t0;            // [n_sets] time origin of the set's photon times
     const int8_t *ins_type; const i64 *ins_time; const i32 *ins_amp; const u32 *ins_gid;
     const double *ins_p, *ins_dm, *ins_ds, *ins_sc; const i32 *ins_cdfrow; const double *cdf_table;
-    const unsigned short *cdf_guide;      // [n_cdf][CDF_G + 2] guide table of every CDF row (host; no longer used by the generator)
     const uint2 *chan_alias; i32 ch_lg;   // [n_cdf][1 << ch_lg] Walker alias cells of every channel CDF row (k_chan_alias): {threshold, alias channel}
     const i64 *em_off;            // [n_ins + 1] first emitter of each instruction
     i64 *em_time; i32 *em_nph; i32 *em_ins; const i64 *em_ph_off;
@@ -2491,7 +2490,6 @@ __device__ __forceinline__ int channel_from_cdf(const double *cdf, int n, double
 #endif
 #define GEN_BLOCK (1 << GEN_LOG)   // photons per block of the generator
 #define GEN_WIN 512                // emitter offsets staged in LDS per block
-#define CDF_G 512                  // guide cells of the per-block channel search
 
 // Guide of a non-decreasing CDF row: cell j = int(u * scale), clamped to AP_GUIDE - 1, holds a bracket [lo, hi] of "the first entry >= u"
 // for every u of the cell (built on the host from the row itself with a margin on either side of the cell, wfs_set_ap_element): the
@@ -2656,22 +2654,7 @@ __device__ __forceinline__ void ap_park(const ApArgs &ap, const ApStage &st, u32
     if (kq < AP_STAGE) { if (seg) q.ins |= AP_SEG_MARK; st.cand[kq] = q; }
     else { const i64 gk = (i64)atomicAdd((u64 *)ap.count, 1ull); if (gk < ap.cap) ap.cand[gk] = q; }      // (a block with more candidates than the stage holds)
 }
-// the screen alone: bit e set when element e of this photon is a candidate (k_s2_tile keeps eight photons in registers and parks the
-// rare candidates in a loop of its own); ap_screen_word recomputes a candidate's screen word
-__device__ __forceinline__ u32 ap_screen_mask(const WfsDev &d, const ApArgs &ap, u32 j, u32 gid, u32 m, int ch, bool is_dpe)
-{
-    u32 mask = 0;
-    for (int e0 = 0; e0 < ap.n; e0 += 4) {
-        const u32x4 S = philox4x32_10(j, gid, m, SITE_AP_SCREEN + (u32)(e0 >> 2), d.k0, d.k1);
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int e = e0 + k;
-            if (e >= ap.n) break;
-            if ((word_of(S, k) >> 5) >= ap.thr[e][ch * 2 + (is_dpe ? 1 : 0)]) mask |= 1u << e;
-        }
-    }
-    return mask;
-}
+// the screen word of element e of a photon, recomputed for a candidate (tile_ap_screen in wfs_tilegen.h screens eight photons in registers)
 __device__ __forceinline__ u32 ap_screen_word(const WfsDev &d, u32 j, u32 gid, u32 m, int e)
 {
     return word_of(philox4x32_10(j, gid, m, SITE_AP_SCREEN + (u32)(e >> 2), d.k0, d.k1), e & 3);
@@ -2706,7 +2689,7 @@ __device__ __forceinline__ void ap_generate(const WfsDev &d, const ApArgs &ap, c
 //   LDS counters and staged at its bucket position in LDS; the block then stores in BUCKET order: neighbouring lanes write
 //   photons of the same tile to consecutive addresses (a scattered 8-byte store per lane is bound by the L2 request rate).
 // Fast path ("single": all photons of the block belong to one instruction, the normal case for an S2): emitter window,
-//   channel thresholds + guide table and tile offsets of the block live in LDS.
+//   the channel alias table (channel_lookup) and the tile offsets of the block live in LDS.
 // Generic path (a block spanning instructions: S1s, small S2s): per-photon global lookups and atomics.
 
 // exclusive prefix sum over n <= 4 * TPB LDS integers, in place; v[n] receives the total.  All TPB threads call it.
@@ -2734,7 +2717,7 @@ __device__ __forceinline__ void block_excl_scan(i32 *v, int n, i32 *wtmp)
 // straxen.InterpolatingMap objects built by load_resource.make_patternmap, method WeightedNearestNeighbors): the hit
 // pattern at a position is the inverse-distance weighted average of the 2 * dims nearest grid nodes (distance clipped at
 // 1e-6).  On the host that costs ~0.4 ms per instruction (10^4 S1: seconds); here one thread finds the neighbours of
-// an instruction and one workgroup turns them into the instruction's channel CDF row and its guide table.
+// an instruction and one workgroup turns them into the instruction's channel CDF row.
 #define MAP_K 6                    // 2 * dims neighbours, dims <= 3
 struct MapArgs {
     i32 dims, n[3], w[3];          // regular grid: nodes per axis; half-width of the candidate block per axis
@@ -2750,7 +2733,7 @@ struct MapArgs {
     const double *pos;             // or: [n_rows][dims] positions (scalar maps)
     const i64 *row_id;             // [n_rows] cdf row to write
     i64 *nb_idx; double *nb_w;     // [n_rows][MAP_K]
-    double *cdf_table; unsigned short *cdf_guide;
+    double *cdf_table;
     const double *gains;           // [n_tpc] 0: turned-off PMT
     const double *aft;             // [n_ins] s2_aft_sigma: factor on the top-array fraction of the instruction's pattern, or nullptr
     i32 n_top;
@@ -3036,8 +3019,7 @@ __global__ void k_map_spline(SplineArgs a)
     a.out[r] = sp;
 }
 
-// one workgroup per row: weighted average of the neighbours' patterns, turned-off PMTs removed, normalised, cumulative sum,
-// guide table (guide[c] = first channel whose cumulative probability exceeds c / CDF_G, as the host builds it)
+// one workgroup per row: weighted average of the neighbours' patterns, turned-off PMTs removed, normalised, cumulative sum
 __global__ __launch_bounds__(256) void k_map_rows(MapArgs m, int nch)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -3083,15 +3065,7 @@ __global__ __launch_bounds__(256) void k_map_rows(MapArgs m, int nch)
     __syncthreads();
     const i64 rid = m.row_id[r];
     double *row = m.cdf_table + rid * nch;
-    for (int c = tid; c < nch; c += 256) { p[c] = p[c] / s_sum; row[c] = p[c]; }
-    __syncthreads();
-    unsigned short *g = m.cdf_guide + rid * (CDF_G + 2);
-    for (int c = tid; c <= CDF_G + 1; c += 256) {
-        const double x = (double)c / CDF_G;
-        int lo = 0, hi = nch - 1;                   // first channel with p[ch] > x, at most nch - 1
-        while (lo < hi) { const int mid = (lo + hi) >> 1; if (p[mid] > x) hi = mid; else lo = mid + 1; }
-        g[c] = (unsigned short)lo;
-    }
+    for (int c = tid; c < nch; c += 256) row[c] = p[c] / s_sum;
 }
 
 // Between the passes: where in its tile every single-instruction block puts its photons.  Thread = (instruction,
