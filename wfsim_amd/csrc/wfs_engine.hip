@@ -5,6 +5,7 @@
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 #include "wfs_kernels.h"
 #include "wfs_tilegen.h"
+#include "wfs_boundary.h"
 #include "../../include/wfsim_amd.h"
 
 // Every pulse kernel exists in two forms: FMA = true (wfs_config.fma, one rounding per template * gain term) and FMA = false (numpy's two
@@ -100,6 +101,10 @@ struct wfs_handle {
     std::vector<i64> h_set_off;       // injected photons: per set photon offsets (channel sorted input order)
     wfs_counts counts{};
     WfsScal *h_scal = nullptr;        // host copy of scal in page-locked memory: read_scal's copy needs no staging buffer (five of them per batch)
+    // step boundaries that publish (read_scal): h_scal is mapped and coherent, k_publish copies the block into it and stores the
+    // sequence number of the boundary into the word on the cache line behind it; the host spins on that word (wfs_boundary.h)
+    bool publish = false;             // false: the copy + synchronise path (the mapped allocation failed, or WFS_HOST_SYNC=copy)
+    uint64_t *h_seq = nullptr; u64 *d_hseq = nullptr, seq = 0; WfsScal *d_hscal = nullptr;
     DevBuf pack_desc;
     DevBuf row_bad, fin_len, res_cnt, fin_off, res_toff, res_desc, fin, res_long, res_rows;      // resident rows (k_row_pulse)
     i64 n_front_rows = 0, n_res_rows = 0, n_short_rows = 0, n_res_tiles = 0, max_res_len = 0, s_fin = 0, s_res = 0; bool res_on = false;
@@ -152,7 +157,8 @@ struct wfs_handle {
     FuseArgs fuse_args{};
 
     std::string launch_err;      // first failed launch of the current call (wfs_set_debug bit 3: every launch is checked)
-    int fail(int code, const std::string &msg) { err = msg; return code; }
+    int n_fail = 0;              // calls of fail(): a FillGroup that dies with segments checks that an error return is why
+    int fail(int code, const std::string &msg) { err = msg; n_fail++; return code; }
 };
 
 namespace {
@@ -226,18 +232,43 @@ inline bool slot_is_sum(const WfsDev &d, i32 slot) { return d.sum_channel >= 0 &
 // grid size for n items; never 0 (a launch with an empty grid is an error, every kernel bounds-checks its index)
 inline unsigned nblocks(i64 n, int tpb) { return n > 0 ? (unsigned)((n + tpb - 1) / tpb) : 1u; }
 
-int fill64(wfs_handle *h, DevBuf &b, i64 n, i64 v)
-{
-    TRY(ensure(h, b, (size_t)n * 8));
-    if (n) { Timer t(h, "k_fill_i64"); hipLaunchKernelGGL(k_fill_i64, dim3(nblocks(n, 256)), dim3(256), 0, h->stream, b.as<i64>(), n, v); }
-    return WFS_OK;
-}
-int fill32(wfs_handle *h, DevBuf &b, i64 n, i32 v)
-{
-    TRY(ensure(h, b, (size_t)n * 4));
-    if (n) { Timer t(h, "k_fill_i32"); hipLaunchKernelGGL(k_fill_i32, dim3(nblocks(n, 256)), dim3(256), 0, h->stream, b.as<i32>(), n, v); }
-    return WFS_OK;
-}
+// The fills of one stage, collected and written by one dispatch of k_fill_group instead of one runtime fill or fill kernel each.
+// A stage adds its segments where it used to fill them and calls flush() before it launches the first kernel that reads or writes
+// one of them; nothing else is launched in between, so only fills change places with fills.  One Timer entry per dispatch, named
+// for the stage.  A segment above FILL_RUNTIME_BYTES stays with the runtime's fill: its time is bandwidth, not dispatch, and the
+// group's grid is sized for the small segments beside it (the accumulators of a mixed batch are 10.9 GB).
+struct FillGroup {
+    static constexpr size_t FILL_RUNTIME_BYTES = (size_t)64 << 20;
+    wfs_handle *h; const char *name; FillSegs a{}; int n = 0; size_t longest = 0;
+    FillGroup(wfs_handle *h_, const char *name_) : h(h_), name(name_), n_fail0(h_->n_fail) {}
+    // a group may die with segments only on an error return (HIPCHK / TRY between add and flush); anywhere else a flush() is missing
+    ~FillGroup() { if (n > 0 && h->n_fail == n_fail0) fprintf(stderr, "wfsim_amd: internal error: fill group %s dropped %d fills\n", name, n); }
+    int n_fail0 = 0;
+    int add(void *p, size_t bytes, u32 p0, u32 p1, u32 p2, u32 p3)
+    {
+        if (bytes == 0) return WFS_OK;
+        if (bytes > FILL_RUNTIME_BYTES && p0 == p1 && p0 == p2 && p0 == p3 && (bytes & 3) == 0) { HIPCHK(hipMemsetD32Async((hipDeviceptr_t)p, (int)p0, bytes / 4, h->stream)); return WFS_OK; }
+        if (n == FILL_GROUP_MAX) TRY(flush());
+        a.s[n].p = (unsigned char *)p; a.s[n].bytes = bytes; a.s[n].pat[0] = p0; a.s[n].pat[1] = p1; a.s[n].pat[2] = p2; a.s[n].pat[3] = p3;
+        n++; longest = std::max(longest, bytes);
+        return WFS_OK;
+    }
+    int bytes(void *p, size_t nbytes, unsigned char v) { const u32 w = 0x01010101u * v; return add(p, nbytes, w, w, w, w); }
+    int zero(void *p, size_t nbytes) { return add(p, nbytes, 0, 0, 0, 0); }
+    int i32s(void *p, i64 count, i32 v) { return add(p, (size_t)count * 4, (u32)v, (u32)v, (u32)v, (u32)v); }
+    int i64s(void *p, i64 count, i64 v) { return pairs(p, count, v, v); }
+    // count i64 that alternate between even and odd
+    int pairs(void *p, i64 count, i64 even, i64 odd) { return add(p, (size_t)count * 8, (u32)(u64)even, (u32)((u64)even >> 32), (u32)(u64)odd, (u32)((u64)odd >> 32)); }
+    int flush()
+    {
+        if (n == 0) return WFS_OK;
+        // 64 bytes per thread of the longest segment, at most 1024 workgroups per segment (the rest is the grid stride)
+        const unsigned gx = (unsigned)std::min<size_t>((longest + 256 * 64 - 1) / (256 * 64), 1024);
+        { Timer t(h, name); hipLaunchKernelGGL(k_fill_group, dim3(gx, (unsigned)n), dim3(256), 0, h->stream, a); }
+        n = 0; longest = 0;
+        return WFS_OK;
+    }
+};
 
 // exclusive scan i32[n] -> i64[n+1]; total written to the member `total` of the device scalar block
 int scan_into(wfs_handle *h, const i32 *in, i64 n, i64 *outp, i64 WfsScal::*total_member, i64 offset);
@@ -261,10 +292,29 @@ int scan_into(wfs_handle *h, const i32 *in, i64 n, i64 *outp, i64 WfsScal::*tota
     return WFS_OK;
 }
 
+// A step boundary: on return *h->h_scal is the device scalar block as of this point of the stream.  By default k_publish writes
+// it into the mapped host copy and the host spins on the sequence word (no copy command, no wake-up through the runtime's signal);
+// a stream given by wfs_set_stream, the launch-checking debug mode, WFS_HOST_SYNC=copy and a handle without mapped memory copy and
+// synchronise.  So does a boundary whose stream ran dry without the word arriving (the launch of k_publish failed).
 int read_scal(wfs_handle *h)
 {
-    HIPCHK(hipMemcpyAsync(h->h_scal, h->scal.p, sizeof(WfsScal), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    bool published = false;
+    if (h->publish && h->own_stream && !(h->keep_currents & DBG_CHECK_LAUNCHES)) {
+        const u64 seq = ++h->seq;
+        // (the profiled step counts the boundaries that publish: one "k_publish" entry each, none for one that copies)
+        { Timer t(h, "k_publish"); hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, h->stream, h->scal.as<WfsScal>(), h->d_hscal, h->d_hseq, seq); }
+        hipError_t qe = hipSuccess;
+        const WfsWait w = wfs_wait_seq(h->h_seq, seq, [&]() {
+            qe = hipStreamQuery(h->stream);
+            return qe == hipSuccess ? WFS_QUERY_DONE : (qe == hipErrorNotReady ? WFS_QUERY_NOT_READY : WFS_QUERY_ERROR);
+        });
+        if (w == WFS_WAIT_ERROR) return h->fail(WFS_E_HIP, std::string("hipStreamQuery(h->stream): ") + hipGetErrorString(qe));
+        published = w == WFS_WAIT_OK;
+    }
+    if (!published) {
+        HIPCHK(hipMemcpyAsync(h->h_scal, h->scal.p, sizeof(WfsScal), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
     if (!h->launch_err.empty()) { const std::string m = h->launch_err; h->launch_err.clear(); return h->fail(WFS_E_HIP, m); }     // (wfs_set_debug bit 3)
     return WFS_OK;
 }
@@ -496,8 +546,22 @@ try {
     if (hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&h->rec_copied[0], hipEventDisableTiming) != hipSuccess
         || hipEventCreateWithFlags(&h->rec_copied[1], hipEventDisableTiming) != hipSuccess) { delete h; return WFS_E_HIP; }
     if (hipMalloc(&h->scal.p, sizeof(WfsScal)) != hipSuccess) { delete h; return WFS_E_HIP; }
-    if (hipHostMalloc((void **)&h->h_scal, sizeof(WfsScal), hipHostMallocDefault) != hipSuccess) { hipFree(h->scal.p); delete h; return WFS_E_HIP; }
-    memset(h->h_scal, 0, sizeof(WfsScal));
+    {   // the host copy of the scalar block; mapped and coherent with the sequence word on the cache line behind it where the
+        // device may write it (read_scal), else -- or with WFS_HOST_SYNC=copy, A/B runs -- page-locked for the copy as before
+        const char *e = getenv("WFS_HOST_SYNC");
+        const size_t bytes = sizeof(WfsScal) + 64;
+        static_assert(sizeof(WfsScal) % 64 == 0, "the sequence word starts a cache line");
+        void *dp = nullptr;
+        if (!(e && !strcmp(e, "copy")) && hipHostMalloc((void **)&h->h_scal, bytes, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
+            if (hipHostGetDevicePointer(&dp, h->h_scal, 0) == hipSuccess && dp) h->publish = true;
+            else { hipHostFree(h->h_scal); h->h_scal = nullptr; }
+        }
+        (void)hipGetLastError();
+        if (!h->publish && hipHostMalloc((void **)&h->h_scal, bytes, hipHostMallocDefault) != hipSuccess) { hipFree(h->scal.p); delete h; return WFS_E_HIP; }
+        memset(h->h_scal, 0, bytes);
+        h->h_seq = (uint64_t *)(h->h_scal + 1);
+        if (h->publish) { h->d_hscal = (WfsScal *)dp; h->d_hseq = (u64 *)(h->d_hscal + 1); }
+    }
     h->scal.cap = sizeof(WfsScal);
 #ifdef WFS_STAMPS
     if (hipMalloc(&h->stamps.p, 4096 * 64 * 8) != hipSuccess) { delete h; return WFS_E_HIP; }
@@ -1277,8 +1341,11 @@ try {
     TRY(upload(h, h->opt_ch, channels, (size_t)n_ph * 4)); TRY(upload(h, h->opt_time, timings, (size_t)n_ph * 8));
     TRY(ensure(h, h->tile_count, (size_t)T * 4)); TRY(ensure(h, h->tile_cursor, (size_t)T * 4)); TRY(ensure(h, h->tile_off, (size_t)(T + 1) * 8));
     TRY(ensure(h, h->opt_t, (size_t)n_ph * 4)); TRY(ensure(h, h->opt_item, (size_t)n_ph * 4));
-    HIPCHK(hipMemsetAsync(h->tile_count.p, 0, (size_t)T * 4, h->stream)); HIPCHK(hipMemsetAsync(h->tile_cursor.p, 0, (size_t)T * 4, h->stream));
-    HIPCHK(hipMemsetAsync(h->scal.p, 0, sizeof(WfsScal), h->stream));
+    {
+        FillGroup fg(h, "fills_optical");
+        TRY(fg.zero(h->tile_count.p, (size_t)T * 4)); TRY(fg.zero(h->tile_cursor.p, (size_t)T * 4)); TRY(fg.zero(h->scal.p, sizeof(WfsScal)));
+        TRY(fg.flush());
+    }
     OptLoadArgs oa{n, h->opt_first.as<i32>(), h->opt_last.as<i32>(), h->opt_ch.as<i32>(), h->opt_time.as<i64>(), cutoff, h->t_gains.as<double>(),
                    h->tile_count.as<i32>(), h->tile_off.as<i64>(), h->tile_cursor.as<i32>(), h->opt_t.as<i32>(), h->opt_item.as<u32>(), h->scal.as<WfsScal>()};
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_optical_bucket<false>), dim3(nblocks(n, 256)), dim3(256), 0, h->stream, h->dev, oa);
@@ -1324,15 +1391,16 @@ struct GenRun {
 };
 
 // ---- generation 1: electrons, and which tiles make their own photons
-static int gen_electrons(wfs_handle *h, GenRun &r)
+static int gen_electrons(wfs_handle *h, GenRun &r, FillGroup &fg)
 {
     const WfsDev &d = h->dev;
     GenArgs &g = r.g; FuseArgs &f = r.f;
     const i64 N = h->n_ins, E = h->n_emitters, T = h->n_tiles;
     TRY(ensure(h, h->em_time, (size_t)E * 8)); TRY(ensure(h, h->em_nph, (size_t)E * 4)); TRY(ensure(h, h->em_ins, (size_t)E * 4));
     TRY(ensure(h, h->el_stat, (size_t)N * 32)); TRY(ensure(h, h->el_minmax, (size_t)N * 16));
-    HIPCHK(hipMemsetAsync(h->el_stat.p, 0, (size_t)N * 32, h->stream));
-    hipLaunchKernelGGL(k_fill_minmax, dim3(nblocks(2 * N, 256)), dim3(256), 0, h->stream, h->el_minmax.as<i64>(), 2 * N);      // (min, max) pairs: (I64_MAX, I64_MIN)
+    // (fg: the fills at the head of the generation, behind the scalar block's of wfs_run; flushed in front of the first kernel)
+    TRY(fg.zero(h->el_stat.p, (size_t)N * 32));
+    TRY(fg.pairs(h->el_minmax.p, 2 * N, I64_MAX, I64_MIN));      // (min, max) pairs: (I64_MAX, I64_MIN)
     g.n_ins = N; g.n_psets = h->n_psets; g.n_emitters = E;
     g.ins_embase = h->ins_embase.as<u32>(); g.ins_set = h->ins_set.as<i32>(); g.set_ins_off = h->set_ins_off.as<i64>(); g.set_ins_list = h->set_ins_list.as<i32>(); g.set_t0 = h->set_t0.as<i64>();
     g.ins_type = h->ins_type.as<int8_t>(); g.ins_time = h->ins_time.as<i64>(); g.ins_amp = h->ins_amp.as<i32>(); g.ins_gid = h->ins_gid.as<u32>();
@@ -1346,11 +1414,12 @@ static int gen_electrons(wfs_handle *h, GenRun &r)
         g.ins_pzi = h->ins_pzi.as<i32>(); g.ins_pzf = h->ins_pzf.as<double>();
         if (h->prop_nz >= 2) { g.prop_top = h->prop_top.as<double>(); g.prop_bot = h->prop_bot.as<double>(); g.prop_nu = h->prop_nu; g.prop_u0 = h->prop_u0; g.prop_du = h->prop_du; }
         if (h->ins_gg_set && h->gg_n >= 1) {
-            TRY(ensure(h, h->ins_ggsum, (size_t)(N + 1) * 8)); HIPCHK(hipMemsetAsync(h->ins_ggsum.p, 0, (size_t)(N + 1) * 8, h->stream));
+            TRY(ensure(h, h->ins_ggsum, (size_t)(N + 1) * 8)); TRY(fg.zero(h->ins_ggsum.p, (size_t)(N + 1) * 8));
             g.gg_inv = h->gg_inv.as<double>(); g.gg_n = h->gg_n; g.gg_L = h->gg_L; g.ins_gg = h->ins_gg.as<i32>(); g.ins_ggw = h->ins_ggw.as<double>(); g.ins_ggsum = h->ins_ggsum.as<i64>();
         }
     }
-    TRY(ensure(h, h->em_zg, (size_t)E * 8)); HIPCHK(hipMemsetAsync(h->em_zg.p, 0xff, (size_t)E * 8, h->stream)); g.em_zg = h->em_zg.as<double>();
+    // em_zg is NaN wherever k_s2_electrons did not store a gain: k_s2_photons alone reads it, and it runs only with any_ptrs
+    TRY(ensure(h, h->em_zg, (size_t)E * 8)); if (h->any_ptrs) TRY(fg.bytes(h->em_zg.p, (size_t)E * 8, 0xff)); g.em_zg = h->em_zg.as<double>();
     // tile-local generation (wfs_tilegen.h): which instructions take it is decided before the electrons are drawn -- theirs get no
     // photon numbers.  Debug modes that need the per-photon arrays (currents, generation only) run the generation half alone.
     // (PMT afterpulses of tile-generated photons are screened inside k_s2_tile)
@@ -1369,18 +1438,20 @@ static int gen_electrons(wfs_handle *h, GenRun &r)
         f.cdf_table = g.cdf_table; f.ins_time = g.ins_time; f.em_off = g.em_off; f.em_time = g.em_time; f.el_minmax = g.el_minmax; f.scal = g.scal;
         TRY(ensure(h, h->ins_fused, (size_t)N * 4)); TRY(ensure(h, h->ins_nsurv, (size_t)N * 4)); TRY(ensure(h, h->ins_bcap, (size_t)N * 4));
         TRY(ensure(h, h->ins_bcap_all, (size_t)N * 4)); TRY(ensure(h, h->et32, (size_t)E * 4));
-        HIPCHK(hipMemsetAsync(h->ins_bcap.p, 0, (size_t)N * 4, h->stream)); HIPCHK(hipMemsetAsync(h->ins_bcap_all.p, 0, (size_t)N * 4, h->stream));
+        TRY(fg.zero(h->ins_bcap.p, (size_t)N * 4)); TRY(fg.zero(h->ins_bcap_all.p, (size_t)N * 4));
         f.ins_fused = h->ins_fused.as<i32>(); f.ins_nsurv = h->ins_nsurv.as<i32>(); f.ins_bcap = h->ins_bcap.as<i32>(); f.ins_bcap_all = h->ins_bcap_all.as<i32>();
         f.et32 = h->et32.as<i32>();
         {
             const i64 n_rows = h->n_host_rows + (i64)h->dev_row_ins.size();
             TRY(ensure(h, h->row_pmax, (size_t)n_rows * 8)); f.row_pmax = h->row_pmax.as<double>();
+            TRY(fg.flush());
             Timer t(h, "k_fuse_decide");
             hipLaunchKernelGGL(k_row_pmax, dim3(nblocks(n_rows, 4)), dim3(256), 0, h->stream, f.cdf_table, d.n_tpc, n_rows, h->row_pmax.as<double>());
             hipLaunchKernelGGL(k_fuse_decide, dim3(nblocks(N, 256)), dim3(256), 0, h->stream, f);
         }
         g.ins_fused = f.ins_fused;
     }
+    TRY(fg.flush());
     { Timer t(h, "k_s1_hits"); hipLaunchKernelGGL(k_s1_hits, dim3(nblocks(N, 4)), dim3(256), 0, h->stream, d, g); }
     {
         const i64 neb = (E + 255) / 256;
@@ -1410,8 +1481,13 @@ static int gen_electrons(wfs_handle *h, GenRun &r)
     }
     const i64 TP = r.TP = h->n_psets * d.n_tpc;
     TRY(ensure(h, h->tile_count, (size_t)T * 4)); TRY(ensure(h, h->tile_cursor, (size_t)T * 4));
-    HIPCHK(hipMemsetAsync(h->tile_count.p, 0, (size_t)T * 4, h->stream)); HIPCHK(hipMemsetAsync(h->tile_cursor.p, 0, (size_t)T * 4, h->stream));
-    TRY(fill32(h, h->tile_tmin, T, 0x7fffffff)); TRY(fill32(h, h->tile_tmax, T, (i32)0x80000000));
+    TRY(ensure(h, h->tile_tmin, (size_t)T * 4)); TRY(ensure(h, h->tile_tmax, (size_t)T * 4));
+    {
+        FillGroup ft(h, "fills_tiles");
+        TRY(ft.zero(h->tile_count.p, (size_t)T * 4)); TRY(ft.zero(h->tile_cursor.p, (size_t)T * 4));
+        TRY(ft.i32s(h->tile_tmin.p, T, 0x7fffffff)); TRY(ft.i32s(h->tile_tmax.p, T, (i32)0x80000000));
+        TRY(ft.flush());
+    }
     TRY(ensure(h, h->tile_off, (size_t)(T + 1) * 8));
     if (h->fuse_on) {
         // surviving electrons compacted per instruction, tile buffers sized from their time range, photons per tile (Poisson)
@@ -1483,7 +1559,11 @@ static int gen_block_photons(wfs_handle *h, GenRun &r)
     TRY(ensure(h, h->ins_sbase, (size_t)N * 4)); g.ins_sbase = h->ins_sbase.as<u32>();
     TRY(ensure(h, h->ins_fullsort, (size_t)N * 4)); g.ins_fullsort = h->ins_fullsort.as<i32>();
     TRY(ensure(h, h->tile_tail, (size_t)TP * 4)); TRY(ensure(h, h->tile_tailbase, (size_t)TP * 4));
-    HIPCHK(hipMemsetAsync(h->tile_tail.p, 0, (size_t)TP * 4, h->stream)); HIPCHK(hipMemsetAsync(h->tile_tailbase.p, 0, (size_t)TP * 4, h->stream));
+    {
+        FillGroup fg(h, "fills_block_photons");
+        TRY(fg.zero(h->tile_tail.p, (size_t)TP * 4)); TRY(fg.zero(h->tile_tailbase.p, (size_t)TP * 4));
+        TRY(fg.flush());
+    }
     g.tile_tail = h->tile_tail.as<i32>(); g.tile_tailbase = h->tile_tailbase.as<i32>();
     { Timer t(h, "k_set_bases"); hipLaunchKernelGGL(k_set_bases, dim3(nblocks(h->n_psets, 256)), dim3(256), 0, h->stream, g); }
     if (P > 0) {
@@ -1642,10 +1722,10 @@ static int gen_order(wfs_handle *h, GenRun &r)
     return WFS_OK;
 }
 
-static int run_generation(wfs_handle *h)
+static int run_generation(wfs_handle *h, FillGroup &fg)
 {
     GenRun r;
-    TRY(gen_electrons(h, r));
+    TRY(gen_electrons(h, r, fg));
     TRY(gen_block_photons(h, r));
     TRY(gen_tile_photons(h, r));
     if (r.ap_on) TRY(gen_afterpulses(h, r));
@@ -1668,13 +1748,17 @@ static int run_input(wfs_handle *h)
 {
     const WfsDev &d = h->dev;
     const i64 T = h->n_tiles;
+    // the scalar block is cleared with the first fills of the run: the generator's (gen_electrons), or alone
+    FillGroup fg(h, from_generator(h) ? "fills_electrons" : "fills_input");
+    TRY(fg.zero(h->scal.p, sizeof(WfsScal)));
+    if (from_generator(h)) return run_generation(h, fg);
+    TRY(fg.flush());
     if (h->optical) {
         OpticalArgs oa{T, h->tile_count.as<i32>(), h->tile_off.as<i64>(), h->tile_tmin.as<i32>(), h->tile_tmax.as<i32>(), h->set_gid.as<u32>(),
                        h->opt_t.as<i32>(), h->opt_item.as<u32>(), h->ph.as<PhotonRec>(), h->scal.as<WfsScal>()};
         Timer t(h, "k_optical_finish");
         hipLaunchKernelGGL(k_optical_finish, dim3(nblocks(T, 256)), dim3(256), 0, h->stream, d, oa);
     }
-    else if (!h->injected) TRY(run_generation(h));
     else { h->ap_active = false; TRY(scan(h, h->tile_count.as<i32>(), T, h->tile_off, &WfsScal::n_tile_photons)); }
     return WFS_OK;
 }
@@ -1686,12 +1770,15 @@ static int run_geometry(wfs_handle *h, RunState &r)
     GeomArgs &ga = r.ga;
     const i64 T = h->n_tiles, S = h->n_sets, C = h->n_clusters;
     const i64 CG = r.CG = C + 1;
-    TRY(fill64(h, h->cl_end, C, I64_MIN)); TRY(ensure(h, h->cl_group, (size_t)C * 4));
-    TRY(fill64(h, h->grp_lo, CG, I64_MAX)); TRY(fill64(h, h->grp_hi, CG, I64_MIN));
+    FillGroup fg(h, "fills_geometry");
+    TRY(ensure(h, h->cl_end, (size_t)C * 8)); TRY(fg.i64s(h->cl_end.p, C, I64_MIN)); TRY(ensure(h, h->cl_group, (size_t)C * 4));
+    TRY(ensure(h, h->grp_lo, (size_t)CG * 8)); TRY(ensure(h, h->grp_hi, (size_t)CG * 8));
+    TRY(fg.i64s(h->grp_lo.p, CG, I64_MAX)); TRY(fg.i64s(h->grp_hi.p, CG, I64_MIN));
     TRY(ensure(h, h->grp_left, (size_t)CG * 8)); TRY(ensure(h, h->grp_right, (size_t)CG * 8)); TRY(ensure(h, h->grp_ixrand, (size_t)CG * 8));
-    TRY(ensure(h, h->grp_gid, (size_t)CG * 4)); HIPCHK(hipMemsetAsync(h->grp_gid.p, 0xff, (size_t)CG * 4, h->stream));
-    TRY(fill64(h, h->row_lo, CG * d.n_tpc, I64_MAX)); TRY(fill64(h, h->row_hi, CG * d.n_tpc, I64_MIN));
-    TRY(ensure(h, h->acc_len, (size_t)CG * d.n_tpc * 4)); HIPCHK(hipMemsetAsync(h->acc_len.p, 0, (size_t)CG * d.n_tpc * 4, h->stream));
+    TRY(ensure(h, h->grp_gid, (size_t)CG * 4)); TRY(fg.bytes(h->grp_gid.p, (size_t)CG * 4, 0xff));
+    TRY(ensure(h, h->row_lo, (size_t)CG * d.n_tpc * 8)); TRY(ensure(h, h->row_hi, (size_t)CG * d.n_tpc * 8));
+    TRY(fg.i64s(h->row_lo.p, CG * d.n_tpc, I64_MAX)); TRY(fg.i64s(h->row_hi.p, CG * d.n_tpc, I64_MIN));
+    TRY(ensure(h, h->acc_len, (size_t)CG * d.n_tpc * 4)); TRY(fg.zero(h->acc_len.p, (size_t)CG * d.n_tpc * 4));
     TRY(ensure(h, h->itv_cap, (size_t)CG * d.row_slots * 4)); TRY(ensure(h, h->active_rows, (size_t)CG * d.row_slots * 4));
     TRY(ensure(h, h->active_tiles, (size_t)T * 4)); TRY(ensure(h, h->sparse_tiles, (size_t)T * 4)); TRY(ensure(h, h->dense_tiles, (size_t)T * 4)); TRY(ensure(h, h->wave_tiles, (size_t)T * 4));
     ga.n_sets = S; ga.n_tiles = T; ga.n_clusters = C; ga.n_gslots = CG;
@@ -1703,9 +1790,10 @@ static int run_geometry(wfs_handle *h, RunState &r)
     ga.active_rows = h->active_rows.as<i32>(); ga.scal = h->scal.as<WfsScal>(); ga.active_tiles = h->active_tiles.as<i32>(); ga.sparse_tiles = h->sparse_tiles.as<i32>(); ga.dense_tiles = h->dense_tiles.as<i32>(); ga.wave_tiles = h->wave_tiles.as<i32>(); ga.force_dense = ((h->keep_currents & DBG_FORCE_DENSE) || h->generic_geom) ? 1 : 0; ga.init_has = h->carry_has; ga.init_runmax = h->carry_runmax;
     ga.noise_override = h->n_noise_override ? h->noise_override.as<i64>() : nullptr; ga.n_noise_override = h->n_noise_override;
     if (d.sum_channel >= 0) {
-        TRY(fill64(h, h->sum_lo, CG, I64_MAX)); TRY(fill64(h, h->sum_hi, CG, I64_MIN));
+        TRY(ensure(h, h->sum_lo, (size_t)CG * 8)); TRY(ensure(h, h->sum_hi, (size_t)CG * 8));
+        TRY(fg.i64s(h->sum_lo.p, CG, I64_MAX)); TRY(fg.i64s(h->sum_hi.p, CG, I64_MIN));
         TRY(ensure(h, h->sum_len, (size_t)CG * 4)); TRY(ensure(h, h->sum_nchunk, (size_t)CG * 4));
-        HIPCHK(hipMemsetAsync(h->sum_len.p, 0, (size_t)CG * 4, h->stream)); HIPCHK(hipMemsetAsync(h->sum_nchunk.p, 0, (size_t)CG * 4, h->stream));
+        TRY(fg.zero(h->sum_len.p, (size_t)CG * 4)); TRY(fg.zero(h->sum_nchunk.p, (size_t)CG * 4));
         ga.sum_lo = h->sum_lo.as<i64>(); ga.sum_hi = h->sum_hi.as<i64>(); ga.sum_len = h->sum_len.as<i32>(); ga.sum_nchunk = h->sum_nchunk.as<i32>();
     }
     const bool tiles_done = r.tiles_done = tiles_made(h);
@@ -1722,7 +1810,7 @@ static int run_geometry(wfs_handle *h, RunState &r)
                 && (!d.enable_noise || d.noise_len >= NOISE_MIN_FAST);
     if (tiles_done || h->res_on) {
         TRY(ensure(h, h->row_cnt, (size_t)CG * d.n_tpc * 4)); TRY(ensure(h, h->row_tile, (size_t)CG * d.n_tpc * 4));
-        HIPCHK(hipMemsetAsync(h->row_cnt.p, 0, (size_t)CG * d.n_tpc * 4, h->stream));
+        TRY(fg.zero(h->row_cnt.p, (size_t)CG * d.n_tpc * 4));
         ga.row_cnt = h->row_cnt.as<i32>(); ga.row_tile = h->row_tile.as<i32>();
     }
     if (tiles_done) {
@@ -1732,11 +1820,12 @@ static int run_geometry(wfs_handle *h, RunState &r)
     if (h->res_on) {
         const size_t nr = (size_t)CG * d.n_tpc;
         TRY(ensure(h, h->row_bad, nr * 4)); TRY(ensure(h, h->fin_len, nr * 4)); TRY(ensure(h, h->res_cnt, nr * 4));
-        HIPCHK(hipMemsetAsync(h->row_bad.p, 0, nr * 4, h->stream)); HIPCHK(hipMemsetAsync(h->fin_len.p, 0, nr * 4, h->stream)); HIPCHK(hipMemsetAsync(h->res_cnt.p, 0, nr * 4, h->stream));
+        TRY(fg.zero(h->row_bad.p, nr * 4)); TRY(fg.zero(h->fin_len.p, nr * 4)); TRY(fg.zero(h->res_cnt.p, nr * 4));
         ga.res_on = 1; ga.res_max_len = h->res_max_len; ga.row_bad = h->row_bad.as<i32>(); ga.fin_len = h->fin_len.as<i32>(); ga.res_cnt = h->res_cnt.as<i32>();
         ga.rows_cap = CG * d.row_slots;
         TRY(ensure(h, h->res_long, nr * 4)); ga.res_long = h->res_long.as<i32>();
     }
+    TRY(fg.flush());
     { Timer t(h, "k_tile_geom"); hipLaunchKernelGGL(k_tile_geom, dim3(nblocks(T, 1024)), dim3(1024), 0, h->stream, d, ga); }
     { Timer t(h, "k_groups"); hipLaunchKernelGGL(k_groups, dim3(1), dim3(GROUPS_TPB), 0, h->stream, d, ga); }
     { Timer t(h, "k_tile_rows"); hipLaunchKernelGGL(k_tile_rows, dim3(nblocks(T, 256)), dim3(256), 0, h->stream, d, ga); }
@@ -1805,8 +1894,13 @@ static int run_pulses(wfs_handle *h, RunState &r)
     PulseArgs &pa = r.pa;
     const i64 T = h->n_tiles, S = h->n_sets;
     // (+64: a lane of k_zle reads 4 samples from its first valid one; the sum rows behind the accumulators are written whole by k_sum_signal)
-    TRY(ensure(h, h->raw, (size_t)(h->s_sum > 0 ? h->sum_base + h->s_sum : h->s_raw) * 4 + 64)); HIPCHK(hipMemsetAsync(h->raw.p, 0, (size_t)h->s_raw * 4, h->stream));
-    TRY(ensure(h, h->truth, (size_t)S * 16 * 8)); HIPCHK(hipMemsetAsync(h->truth.p, 0, (size_t)S * 16 * 8, h->stream));
+    TRY(ensure(h, h->raw, (size_t)(h->s_sum > 0 ? h->sum_base + h->s_sum : h->s_raw) * 4 + 64));
+    TRY(ensure(h, h->truth, (size_t)S * 16 * 8));
+    {
+        FillGroup fg(h, "fills_pulses");
+        TRY(fg.zero(h->raw.p, (size_t)h->s_raw * 4)); TRY(fg.zero(h->truth.p, (size_t)S * 16 * 8));
+        TRY(fg.flush());
+    }
     TRY(ensure(h, h->tminmax, (size_t)S * 16)); TRY(ensure(h, h->tile_truth, (size_t)T * 8 * 8));
     pa.active_tiles = h->active_tiles.as<i32>(); pa.n_active = h->n_active_tiles;
     pa.tile_count = h->tile_count.as<i32>(); pa.tile_tmin = h->tile_tmin.as<i32>(); pa.tile_tmax = h->tile_tmax.as<i32>(); pa.tile_off = h->tile_off.as<i64>();
@@ -1936,7 +2030,8 @@ static int run_rows(wfs_handle *h, RunState &r)
     const i64 RS = r.RS = CG * d.row_slots;
     TRY(ensure(h, h->itv_left, (size_t)h->n_itv_slots * 8 + 16)); TRY(ensure(h, h->itv_right, (size_t)h->n_itv_slots * 8 + 16));      // (+16: k_pack reads the first two slots of a row whatever its capacity)
     TRY(ensure(h, h->itv_n, (size_t)RS * 4)); TRY(ensure(h, h->row_nrec, (size_t)RS * 4));
-    HIPCHK(hipMemsetAsync(h->itv_n.p, 0, (size_t)RS * 4, h->stream)); HIPCHK(hipMemsetAsync(h->row_nrec.p, 0, (size_t)RS * 4, h->stream));
+    FillGroup fg(h, "fills_rows");
+    TRY(fg.zero(h->itv_n.p, (size_t)RS * 4)); TRY(fg.zero(h->row_nrec.p, (size_t)RS * 4));
     za.active_rows = h->active_rows.as<i32>(); za.n_active_rows = h->n_active_rows; za.row_lo = h->row_lo.as<i64>(); za.row_hi = h->row_hi.as<i64>();
     za.acc_off = h->acc_off.as<i64>(); za.raw = h->raw.as<i32>(); za.grp_left = h->grp_left.as<i64>(); za.grp_ixrand = h->grp_ixrand.as<i64>();
     za.itv_off = h->itv_off.as<i64>(); za.itv_left = h->itv_left.as<i64>(); za.itv_right = h->itv_right.as<i64>();
@@ -1977,9 +2072,9 @@ static int run_rows(wfs_handle *h, RunState &r)
     TRY(ensure(h, h->row_desc, (size_t)h->n_active_rows * sizeof(RowDesc))); za.desc = h->row_desc.as<RowDesc>();
     if (h->sort_records) {      // key_origin / key_end: first sample / end of the last row of the batch (k_row_desc): origin and span of the sort keys
         za.key_base = h->scal.as<WfsScal>();
-        hipLaunchKernelGGL(k_fill_i64, dim3(1), dim3(64), 0, h->stream, &za.key_base->key_origin, (i64)1, I64_MAX);
-        hipLaunchKernelGGL(k_fill_i64, dim3(1), dim3(64), 0, h->stream, &za.key_base->key_end, (i64)1, I64_MIN);
+        TRY(fg.i64s(&za.key_base->key_origin, 1, I64_MAX)); TRY(fg.i64s(&za.key_base->key_end, 1, I64_MIN));
     }
+    TRY(fg.flush());
     if (h->n_active_rows > 0) { Timer t(h, "k_row_desc"); hipLaunchKernelGGL(k_row_desc, dim3(nblocks(h->n_active_rows, 256)), dim3(256), 0, h->stream, d, za); }
     r.noise_kind = !d.enable_noise ? 0 : (d.noise_f ? 2 : 1);
     if (h->n_res_rows > 0) {        // resident rows: pulses, finished samples and intervals by one wave per row
@@ -2090,7 +2185,6 @@ try {
     HIPCHK(hipSetDevice(h->device));
     for (auto &t : h->times) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
     h->times.clear();
-    HIPCHK(hipMemsetAsync(h->scal.p, 0, sizeof(WfsScal), h->stream));
     TRY(run_input(h));
     h->gen_done = true;
     if (h->keep_currents & DBG_GEN_ONLY) { HIPCHK(hipStreamSynchronize(h->stream)); return WFS_OK; }      // wfs_set_debug bit 2: photon generation only

@@ -16,9 +16,36 @@
 #define I64_MIN (-I64_MAX - 1)
 
 // ------------------------------------------------------------------------------------------------ fills
-__global__ void k_fill_i64(i64 *p, i64 n, i64 v) { i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; if (i < n) p[i] = v; }
-__global__ void k_fill_i32(i32 *p, i64 n, i32 v) { i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; if (i < n) p[i] = v; }
-__global__ void k_fill_minmax(i64 *p, i64 n) { i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; if (i < n) p[i] = (i & 1) ? I64_MIN : I64_MAX; }
+// The fills of one stage in one dispatch (FillGroup, wfs_engine.hip).  A segment is [p, p + bytes) and a pattern of 16 bytes that
+// repeats from p: byte fills, one i32, one i64 and the (I64_MAX, I64_MIN) pairs of el_minmax are all of that form.
+#define FILL_GROUP_MAX 16
+struct FillSeg { unsigned char *p; u64 bytes; u32 pat[4]; };
+struct FillSegs { FillSeg s[FILL_GROUP_MAX]; };
+// blockIdx.y: the segment; blockIdx.x walks it with a grid stride.  16-byte stores where p is 16-byte aligned (every DevBuf is),
+// the tail -- or a segment at an odd address, the two sort-key slots of the scalar block -- byte by byte.
+__global__ void __launch_bounds__(256) k_fill_group(const FillSegs a)
+{
+    const FillSeg &s = a.s[blockIdx.y];
+    const u64 stride = (u64)gridDim.x * blockDim.x, first = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    const u64 n16 = (((u64)s.p & 15) == 0) ? s.bytes >> 4 : 0;
+    const uint4 v = make_uint4(s.pat[0], s.pat[1], s.pat[2], s.pat[3]);
+    for (u64 i = first; i < n16; i += stride) ((uint4 *)s.p)[i] = v;
+    for (u64 i = (n16 << 4) + first; i < s.bytes; i += stride) {
+        const u32 k = (u32)(i >> 2) & 3, w = k == 0 ? v.x : (k == 1 ? v.y : (k == 2 ? v.z : v.w));
+        s.p[i] = (unsigned char)(w >> (8 * ((u32)i & 3)));
+    }
+}
+
+// A step boundary (read_scal): the scalar block into the host's mapped copy, then the sequence word behind it.  One wave, one
+// 8-byte store per lane; the fence orders every lane's store before the barrier, lane 0's release store publishes them.
+__global__ void __launch_bounds__(64) k_publish(const WfsScal *scal, WfsScal *host, u64 *host_seq, u64 seq)
+{
+    static_assert(sizeof(WfsScal) == 64 * 8, "k_publish: one 8-byte slot per lane");
+    ((i64 *)host)[threadIdx.x] = ((const i64 *)scal)[threadIdx.x];
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store(host_seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 
 // totals for wfs_get_counts, reduced on the device (copying itv_n back cost 300 MB per 10^5-cluster batch):
 // n_intervals = sum of itv_n (ZLE intervals), n_pe = sum of the per-set n_pe (truth[s][1], integral doubles)
