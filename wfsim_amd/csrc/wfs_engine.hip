@@ -1319,6 +1319,9 @@ try {
     return WFS_OK;
 } WFS_CATCH(h)
 
+// capacity of the afterpulse lists of an optical batch of P photons: the generator's rule (gen_block_photons)
+static i64 optical_ap_cap(i64 P) { return P / 8 + 65536; }
+
 int wfs_load_optical(wfs_handle *h, int64_t n, const int64_t *time, const uint32_t *gid, const int32_t *cluster, const int64_t *tmin,
                      const int32_t *first, const int32_t *last, const int32_t *channels, const int64_t *timings, int64_t n_ph, int64_t cutoff)
 try {
@@ -1328,18 +1331,28 @@ try {
         return h->fail(WFS_E_INVALID, "wfs_load_optical: null or empty input");
     HIPCHK(hipSetDevice(h->device));
     const int nch = h->cfg.n_tpc;
-    h->n_ins = n; h->n_sets = n; h->n_tiles = n * nch; h->n_emitters = 0; h->ap_active = false;
+    // PMT afterpulses are a second pulse set per instruction (rawdata.py:176-178, behind every primary Pulse call): set n + i belongs to set i
+    h->ap_active = h->cfg.enable_pmt_ap && h->dev.n_ap > 0;
+    const i64 S = h->ap_active ? 2 * n : n;
+    h->n_ins = n; h->n_psets = n; h->n_sets = S; h->n_tiles = S * nch; h->n_emitters = 0; h->n_ap_photons = 0;
     if (h->n_tiles > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "too many tiles in one batch");
-    for (i64 i = 0; i < n; i++)
+    for (i64 i = 0; i < n; i++) {
         if (first[i] < 0 || last[i] < first[i] || last[i] > n_ph) return h->fail(WFS_E_INVALID, "_first/_last out of range");
-    // the photons are bucketed by (instruction, channel) on the device: count, scan, place (k_optical_bucket)
-    const i64 T = h->n_tiles;
-    std::vector<i32> mode((size_t)n, 0);
-    TRY(upload(h, h->set_cluster, cluster, (size_t)n * 4)); TRY(upload(h, h->set_t0, time, (size_t)n * 8)); TRY(upload(h, h->set_mode, mode.data(), (size_t)n * 4));
-    TRY(upload(h, h->set_gid, gid, (size_t)n * 4)); TRY(upload(h, h->ins_time, time, (size_t)n * 8));
+        if (h->ap_active && (i64)last[i] - first[i] >= (1LL << 29))      // (the order key of an afterpulse holds 29 bits of its parent's index)
+            return h->fail(WFS_E_CAPACITY, "an instruction of 2^29 or more supplied photons with PMT afterpulses on");
+    }
+    // the photons are bucketed by (instruction, channel) on the device: count, scan, place (k_optical_bucket) -- the primary tiles only
+    const i64 T = n * nch;
+    {
+        std::vector<i32> mode((size_t)S, 0), sc((size_t)S); std::vector<i64> st((size_t)S); std::vector<u32> sg((size_t)S);
+        for (i64 q = 0; q < S; q++) { sc[q] = cluster[q % n]; st[q] = time[q % n]; sg[q] = gid[q % n]; mode[q] = q >= n ? 1 : 0; }
+        TRY(upload(h, h->set_cluster, sc.data(), (size_t)S * 4)); TRY(upload(h, h->set_t0, st.data(), (size_t)S * 8)); TRY(upload(h, h->set_mode, mode.data(), (size_t)S * 4));
+        TRY(upload(h, h->set_gid, sg.data(), (size_t)S * 4)); TRY(upload(h, h->ins_time, time, (size_t)n * 8));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
     TRY(upload(h, h->opt_first, first, (size_t)n * 4)); TRY(upload(h, h->opt_last, last, (size_t)n * 4));
     TRY(upload(h, h->opt_ch, channels, (size_t)n_ph * 4)); TRY(upload(h, h->opt_time, timings, (size_t)n_ph * 8));
-    TRY(ensure(h, h->tile_count, (size_t)T * 4)); TRY(ensure(h, h->tile_cursor, (size_t)T * 4)); TRY(ensure(h, h->tile_off, (size_t)(T + 1) * 8));
+    TRY(ensure(h, h->tile_count, (size_t)h->n_tiles * 4)); TRY(ensure(h, h->tile_cursor, (size_t)h->n_tiles * 4)); TRY(ensure(h, h->tile_off, (size_t)(h->n_tiles + 1) * 8));
     TRY(ensure(h, h->opt_t, (size_t)n_ph * 4)); TRY(ensure(h, h->opt_item, (size_t)n_ph * 4));
     {
         FillGroup fg(h, "fills_optical");
@@ -1356,7 +1369,8 @@ try {
     TRY(device_error(h, h->h_scal->opt_error));
     const i64 P = h->h_scal->n_tile_photons;
     h->n_photons = P;
-    TRY(ensure(h, h->ph, (size_t)P * 8));
+    // (with afterpulses the array also holds theirs, behind the primary photons: sized here, k_optical_finish writes into it)
+    TRY(ensure(h, h->ph, (size_t)(P + (h->ap_active ? optical_ap_cap(P) : 0)) * 8));
     TRY(ensure(h, h->tile_tmin, (size_t)h->n_tiles * 4)); TRY(ensure(h, h->tile_tmax, (size_t)h->n_tiles * 4));
     TRY(ensure(h, h->el_stat, (size_t)n * 32)); TRY(ensure(h, h->el_minmax, (size_t)n * 16));
     HIPCHK(hipMemsetAsync(h->el_stat.p, 0, (size_t)n * 32, h->stream));
@@ -1515,6 +1529,36 @@ static int gen_electrons(wfs_handle *h, GenRun &r, FillGroup &fg)
     return WFS_OK;
 }
 
+// the afterpulse kernels' arguments: element tables, acceptance probabilities, screening thresholds of the current modifier and the
+// candidate / photon lists of ap_cap entries (ph_gain: the explicit gains of the afterpulse photons, which follow the primary ones)
+static int fill_ap_args(wfs_handle *h, ApArgs &ap, i64 ap_cap)
+{
+    const WfsDev &d = h->dev;
+    ap.n = d.n_ap;
+    for (int e = 0; e < d.n_ap; e++) {
+        const ApElem &s = h->ap[e];
+        ap.el[e] = ApElemDev{s.n_bins_delay, s.n_bins_amp, s.amp_2d, s.is_uniform, s.delay_bin, s.amp_bin, s.delay_cdf.as<double>(), s.amp_cdf.as<double>(),
+                             s.delay_sorted, s.amp_sorted, s.delay_guide.as<ApGuide>(), s.amp_guide.as<ApGuide>()};
+        ap.prob[e] = s.prob.as<double>();
+        ApElem &sm = h->ap[e];
+        if (sm.thr_mod != d.pmt_ap_modifier || !sm.thr.p) {           // screening thresholds of the generator (ap_threshold), once per modifier
+            std::vector<u32> th(sm.prob_h.size() * 2);
+            for (size_t c = 0; c < sm.prob_h.size(); c++) for (int dpe = 0; dpe < 2; dpe++) th[2 * c + dpe] = ap_threshold(sm.prob_h[c], d.pmt_ap_modifier, dpe != 0);
+            TRY(upload(h, sm.thr, th.data(), th.size() * 4));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            sm.thr_mod = d.pmt_ap_modifier;
+        }
+        ap.thr[e] = sm.thr.as<u32>();
+    }
+    TRY(ensure(h, h->ap_ins, (size_t)ap_cap * 4)); TRY(ensure(h, h->ap_ch, (size_t)ap_cap * 4)); TRY(ensure(h, h->ap_t, (size_t)ap_cap * 4));
+    TRY(ensure(h, h->ap_gain, (size_t)ap_cap * 8)); TRY(ensure(h, h->ph_gain, (size_t)ap_cap * 8)); TRY(ensure(h, h->ap_key, (size_t)ap_cap * 4));
+    ap.ap_key = h->ap_key.as<u32>();
+    ap.cap = ap_cap; ap.ap_ins = h->ap_ins.as<i32>(); ap.ap_ch = h->ap_ch.as<i32>(); ap.ap_t = h->ap_t.as<i32>(); ap.ap_gain = h->ap_gain.as<double>();
+    ap.count = &h->scal.as<WfsScal>()->n_ap_candidates;
+    TRY(ensure(h, h->ap_cand, (size_t)ap_cap * sizeof(ApCand))); ap.cand = h->ap_cand.as<ApCand>();
+    return WFS_OK;
+}
+
 // ---- generation 2: the photons of the block generator, bucketed by tile
 static int gen_block_photons(wfs_handle *h, GenRun &r)
 {
@@ -1530,30 +1574,7 @@ static int gen_block_photons(wfs_handle *h, GenRun &r)
     g.tile_count = h->tile_count.as<i32>(); g.tile_cursor = h->tile_cursor.as<i32>(); g.tile_tmin = h->tile_tmin.as<i32>();
     g.tile_tmax = h->tile_tmax.as<i32>(); g.ph = h->ph.as<PhotonRec>();
     g.tile_off = h->tile_off.as<i64>();
-    if (ap_on) {
-        ap.n = d.n_ap;
-        for (int e = 0; e < d.n_ap; e++) {
-            const ApElem &s = h->ap[e];
-            ap.el[e] = ApElemDev{s.n_bins_delay, s.n_bins_amp, s.amp_2d, s.is_uniform, s.delay_bin, s.amp_bin, s.delay_cdf.as<double>(), s.amp_cdf.as<double>(),
-                                 s.delay_sorted, s.amp_sorted, s.delay_guide.as<ApGuide>(), s.amp_guide.as<ApGuide>()};
-            ap.prob[e] = s.prob.as<double>();
-            ApElem &sm = h->ap[e];
-            if (sm.thr_mod != d.pmt_ap_modifier || !sm.thr.p) {           // screening thresholds of the generator (ap_threshold), once per modifier
-                std::vector<u32> th(sm.prob_h.size() * 2);
-                for (size_t c = 0; c < sm.prob_h.size(); c++) for (int dpe = 0; dpe < 2; dpe++) th[2 * c + dpe] = ap_threshold(sm.prob_h[c], d.pmt_ap_modifier, dpe != 0);
-                TRY(upload(h, sm.thr, th.data(), th.size() * 4));
-                HIPCHK(hipStreamSynchronize(h->stream));
-                sm.thr_mod = d.pmt_ap_modifier;
-            }
-            ap.thr[e] = sm.thr.as<u32>();
-        }
-        TRY(ensure(h, h->ap_ins, (size_t)ap_cap * 4)); TRY(ensure(h, h->ap_ch, (size_t)ap_cap * 4)); TRY(ensure(h, h->ap_t, (size_t)ap_cap * 4));
-        TRY(ensure(h, h->ap_gain, (size_t)ap_cap * 8)); TRY(ensure(h, h->ph_gain, (size_t)ap_cap * 8)); TRY(ensure(h, h->ap_key, (size_t)ap_cap * 4));
-        ap.ap_key = h->ap_key.as<u32>();
-        ap.cap = ap_cap; ap.ap_ins = h->ap_ins.as<i32>(); ap.ap_ch = h->ap_ch.as<i32>(); ap.ap_t = h->ap_t.as<i32>(); ap.ap_gain = h->ap_gain.as<double>();
-        ap.count = &h->scal.as<WfsScal>()->n_ap_candidates;
-        TRY(ensure(h, h->ap_cand, (size_t)ap_cap * sizeof(ApCand))); ap.cand = h->ap_cand.as<ApCand>();
-    }
+    if (ap_on) TRY(fill_ap_args(h, ap, ap_cap));
     TRY(ensure(h, h->ins_ph0, (size_t)(N + 1) * 8)); g.ins_ph0 = h->ins_ph0.as<i64>();
     { Timer t(h, "k_ins_ph0"); hipLaunchKernelGGL(k_ins_ph0, dim3(nblocks(N + 1, 256)), dim3(256), 0, h->stream, g); }
     TRY(ensure(h, h->ins_sbase, (size_t)N * 4)); g.ins_sbase = h->ins_sbase.as<u32>();
@@ -1674,6 +1695,8 @@ static int gen_afterpulses(wfs_handle *h, GenRun &r)
     return WFS_OK;
 }
 
+static int order_ranges(wfs_handle *h, const OrderArgs &oa);
+
 // ---- generation 5: every tile of the block generator into generation order (k_tile_order): the order the reference's Pulse call sees
 static int gen_order(wfs_handle *h, GenRun &r)
 {
@@ -1685,6 +1708,13 @@ static int gen_order(wfs_handle *h, GenRun &r)
                  ap_on ? h->ph_gain.as<double>() : nullptr, P + h->p_fused, h->order_list.as<OrderRange>(), h->order_list2.as<OrderRange>(), h->scal.as<WfsScal>(),
                  (h->fuse_on && n_tilegen_tiles(h) > 0) ? h->ins_fused.as<i32>() : nullptr, d.n_tpc,
                  h->tile_cursor.as<i32>(), h->tile_tailbase.as<i32>(), h->ins_fullsort.as<i32>(), h->set_ins_off.as<i64>(), h->set_ins_list.as<i32>()};
+    return order_ranges(h, oa);
+}
+
+// the order pass over the tiles oa describes: scan, then every listed range by the kernel of its class
+static int order_ranges(wfs_handle *h, const OrderArgs &oa)
+{
+    const i64 T = oa.n_tiles;
     { Timer t(h, "k_tile_order_scan"); hipLaunchKernelGGL(k_tile_order_scan, dim3(nblocks(T, 256)), dim3(256), 0, h->stream, oa); }
     TRY(read_scal(h));
     const i64 n_wave = h->h_scal->n_order_wave, n_big = h->h_scal->n_order_big;
@@ -1697,7 +1727,7 @@ static int gen_order(wfs_handle *h, GenRun &r)
     if (n_huge > 0) {
         // ranges beyond the workgroup sort: compact copies, one segmented radix sort over (order key, position), records to their ranks
         std::vector<OrderRange> rg((size_t)n_huge);
-        HIPCHK(hipMemcpy(rg.data(), h->order_list2.as<OrderRange>() + (2 * T - n_huge), (size_t)n_huge * sizeof(OrderRange), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(rg.data(), oa.big_list + (2 * T - n_huge), (size_t)n_huge * sizeof(OrderRange), hipMemcpyDeviceToHost));
         std::sort(rg.begin(), rg.end(), [](const OrderRange &x, const OrderRange &y) { return x.start < y.start; });      // (appended with atomics: a fixed order for the offsets)
         std::vector<i64> start((size_t)n_huge), cbeg((size_t)n_huge + 1, 0);
         for (i64 k = 0; k < n_huge; k++) { start[(size_t)k] = rg[(size_t)k].start; cbeg[(size_t)k + 1] = cbeg[(size_t)k] + rg[(size_t)k].n; }
@@ -1717,7 +1747,7 @@ static int gen_order(wfs_handle *h, GenRun &r)
         HIPCHK(rocprim::segmented_radix_sort_pairs(h->sort_tmp.p, bytes, h->huge_keys.as<u32>(), h->huge_keys2.as<u32>(), h->huge_vals.as<u32>(), h->huge_vals2.as<u32>(),
                                                    (unsigned)tot, (unsigned)n_huge, h->huge_cbeg.as<i64>(), h->huge_cbeg.as<i64>() + 1, 0u, 32u, h->stream));
         hipLaunchKernelGGL(k_order_huge_apply, dim3(nblocks(tot, 256)), dim3(256), 0, h->stream, ha, h->huge_keys2.as<u32>(), h->huge_vals2.as<u32>(), h->ph.as<PhotonRec>(), h->ph_idx.as<u32>(),
-                           ap_on ? h->ph_gain.as<double>() : nullptr);
+                           oa.ph_gain);
     }
     return WFS_OK;
 }
@@ -1743,23 +1773,62 @@ struct RunState {
     int noise_kind = 0;                                     // with_noise_kind
 };
 
+// ---- PMT afterpulses of an optical batch: the supplied photons are screened (k_optical_ap_screen), the candidates go through the
+// generator's stages (gen_afterpulses) into the tiles of the afterpulse sets, and those tiles into generation order.  The primary
+// tiles are in item order as k_optical_bucket wrote them and are on none of the lists the order pass reads for a generator batch:
+// the pass is given the afterpulse tiles alone.
+static int optical_afterpulses(wfs_handle *h)
+{
+    const WfsDev &d = h->dev;
+    const i64 P = h->n_photons, TP = h->n_ins * d.n_tpc, ap_cap = optical_ap_cap(P);
+    GenArgs g{}; ApArgs ap{};
+    TRY(fill_ap_args(h, ap, ap_cap));
+    TRY(ensure(h, h->ph_idx, (size_t)(P + ap_cap) * 4));
+    g.n_psets = h->n_psets; g.tile_count = h->tile_count.as<i32>(); g.tile_cursor = h->tile_cursor.as<i32>(); g.tile_off = h->tile_off.as<i64>();
+    g.tile_tmin = h->tile_tmin.as<i32>(); g.tile_tmax = h->tile_tmax.as<i32>(); g.ph = h->ph.as<PhotonRec>(); g.ph_idx = h->ph_idx.as<u32>();
+    g.scal = h->scal.as<WfsScal>();
+    if (P > 0) {
+        OptApArgs sa{P, TP, h->tile_off.as<i64>(), h->set_gid.as<u32>(), h->set_t0.as<i64>(), h->opt_item.as<u32>(), h->ph.as<PhotonRec>()};
+        Timer t(h, "k_optical_ap_screen");
+        hipLaunchKernelGGL(k_optical_ap_screen, dim3(nblocks(P, 256)), dim3(256), 0, h->stream, d, sa, ap);
+    }
+    double *const gain_base = h->ph_gain.as<double>() - P;
+    { Timer t(h, "k_ap_finish"); hipLaunchKernelGGL(k_ap_finish, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap); }
+    { Timer t(h, "k_ap_count"); hipLaunchKernelGGL(k_ap_count, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap); }
+    TRY(scan_into(h, h->tile_count.as<i32>() + TP, TP, h->tile_off.as<i64>() + TP, &WfsScal::n_ap_photons, P));
+    { Timer t(h, "k_ap_place"); hipLaunchKernelGGL(k_ap_place, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap, gain_base); }
+    TRY(read_scal(h));
+    if (h->h_scal->n_ap_candidates > ap_cap) return h->fail(WFS_E_CAPACITY, "more PMT afterpulse photons than 1/8 of the primary photons: afterpulse probability unreasonably high");
+    h->n_ap_photons = h->h_scal->n_ap_photons;
+    TRY(ensure(h, h->order_list, (size_t)TP * 2 * sizeof(OrderRange))); TRY(ensure(h, h->order_list2, (size_t)TP * 2 * sizeof(OrderRange)));
+    OrderArgs oa{TP, 0, h->tile_count.as<i32>() + TP, h->tile_off.as<i64>() + TP, h->ph.as<PhotonRec>(), h->ph_idx.as<u32>(), h->ph_gain.as<double>(), P,
+                 h->order_list.as<OrderRange>(), h->order_list2.as<OrderRange>(), h->scal.as<WfsScal>(), nullptr, d.n_tpc, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return order_ranges(h, oa);
+}
+
 // ---- input: photons bucketed by tile, whichever way the batch was loaded
 static int run_input(wfs_handle *h)
 {
     const WfsDev &d = h->dev;
-    const i64 T = h->n_tiles;
     // the scalar block is cleared with the first fills of the run: the generator's (gen_electrons), or alone
     FillGroup fg(h, from_generator(h) ? "fills_electrons" : "fills_input");
     TRY(fg.zero(h->scal.p, sizeof(WfsScal)));
     if (from_generator(h)) return run_generation(h, fg);
+    if (h->optical && h->ap_active) {
+        // the afterpulse tiles start every run empty (the primary tiles keep the counts and offsets of wfs_load_optical)
+        const i64 TP = h->n_ins * d.n_tpc;
+        TRY(fg.zero(h->tile_count.as<i32>() + TP, (size_t)TP * 4)); TRY(fg.zero(h->tile_cursor.as<i32>() + TP, (size_t)TP * 4));
+        TRY(fg.i32s(h->tile_tmin.as<i32>() + TP, TP, 0x7fffffff)); TRY(fg.i32s(h->tile_tmax.as<i32>() + TP, TP, (i32)0x80000000));
+    }
     TRY(fg.flush());
     if (h->optical) {
+        const i64 T = h->n_ins * d.n_tpc;                    // the primary tiles (afterpulse tiles follow them)
         OpticalArgs oa{T, h->tile_count.as<i32>(), h->tile_off.as<i64>(), h->tile_tmin.as<i32>(), h->tile_tmax.as<i32>(), h->set_gid.as<u32>(),
                        h->opt_t.as<i32>(), h->opt_item.as<u32>(), h->ph.as<PhotonRec>(), h->scal.as<WfsScal>()};
-        Timer t(h, "k_optical_finish");
-        hipLaunchKernelGGL(k_optical_finish, dim3(nblocks(T, 256)), dim3(256), 0, h->stream, d, oa);
+        { Timer t(h, "k_optical_finish"); hipLaunchKernelGGL(k_optical_finish, dim3(nblocks(T, 256)), dim3(256), 0, h->stream, d, oa); }
+        if (h->ap_active) TRY(optical_afterpulses(h));
     }
-    else { h->ap_active = false; TRY(scan(h, h->tile_count.as<i32>(), T, h->tile_off, &WfsScal::n_tile_photons)); }
+    else { h->ap_active = false; TRY(scan(h, h->tile_count.as<i32>(), h->n_tiles, h->tile_off, &WfsScal::n_tile_photons)); }
     return WFS_OK;
 }
 
@@ -1803,7 +1872,7 @@ static int run_geometry(wfs_handle *h, RunState &r)
     // pulses are where the accumulators cost (memset, atomics, two more reads); a batch of sparse S1 or nVeto hits is as fast through
     // them, and the resident path's extra pass over the tiles does not pay there
     // (photons in the photon array: the tiles k_s2_tile made in one go hold theirs in their sample buffers and can never be resident)
-    const i64 p_all = h->n_photons - ((from_generator(h) && h->fuse_full) ? h->p_fused : 0) + ((from_generator(h) && h->ap_active) ? h->n_ap_photons : 0);
+    const i64 p_all = h->n_photons - ((from_generator(h) && h->fuse_full) ? h->p_fused : 0) + ((!h->injected && h->ap_active) ? h->n_ap_photons : 0);
     const bool res_auto = T > 0 && p_all >= 2 * T;
     const int res_mode = h->res_env >= 0 ? h->res_env : h->cfg.row_resident;
     h->res_on = (res_mode == 2 ? res_auto : res_mode != 0) && !(h->keep_currents & (DBG_CURRENTS | DBG_FORCE_DENSE)) && !h->generic_geom && !d.he_rows && 2 * (i64)d.tw + 1 >= 63

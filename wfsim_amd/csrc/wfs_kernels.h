@@ -3843,3 +3843,47 @@ __global__ void k_optical_finish(WfsDev d, OpticalArgs a)
     a.tile_tmin[tile] = tmin; a.tile_tmax[tile] = tmax;
 }
 
+// PMT afterpulses of supplied photons: the screening of ap_generate, one thread per PHOTON of the bucketed array (behind
+// k_optical_finish, which made its time and double-PE flag).  Tiles of optical input hold 0 .. 3 photons (nVeto) or 10^2 .. 10^4
+// (an optical S1 in the TPC): a thread per tile would diverge over four orders of magnitude.  The photon's tile is found by bisection
+// of the primary tiles' offsets (the top levels stay in L2); its counter is (0, gid, item, site) with item = its index inside the
+// instruction's _first:_last range, the coordinate of its SITE_PH draw.  Candidates leave wave-aggregated: one atomic on the list's
+// counter per wave and element, every lane at base + its rank among the wave's candidates (no LDS stage, no segments).
+struct OptApArgs { i64 n_photons, n_ptiles; const i64 *tile_off; const u32 *set_gid; const i64 *set_t0; const u32 *in_item; const PhotonRec *ph; };
+
+__global__ __launch_bounds__(256) void k_optical_ap_screen(WfsDev d, OptApArgs a, ApArgs ap)
+{
+    const i64 p = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool v = p < a.n_photons;                          // (every lane stays for the ballots)
+    i32 ins = 0, ch = 0, t = 0; u32 gid = 0, item = 0; bool dpe = false; i64 itime = 0;
+    if (v) {
+        i64 lo = 0, hi = a.n_ptiles;                         // the last tile that starts at or before p (it holds p: empty tiles start where the next one does)
+        while (hi - lo > 1) { const i64 mid = (lo + hi) >> 1; if (a.tile_off[mid] <= p) lo = mid; else hi = mid; }
+        ins = (i32)(lo / d.n_tpc); ch = (i32)(lo - (i64)ins * d.n_tpc);
+        gid = a.set_gid[ins]; itime = a.set_t0[ins]; item = a.in_item[p];
+        const PhotonRec r = a.ph[p];
+        t = r.t; dpe = (r.code >> 16) != 0;
+    }
+    for (int e0 = 0; e0 < ap.n; e0 += 4) {
+        const u32x4 S = philox4x32_10(0u, gid, item, SITE_AP_SCREEN + (u32)(e0 >> 2), d.k0, d.k1);
+        for (int k = 0; k < 4 && e0 + k < ap.n; k++) {
+            const int e = e0 + k;
+            const u32 x = word_of(S, k);
+            const bool c = v && (x >> 5) >= ap.thr[e][ch * 2 + (dpe ? 1 : 0)];       // (below the threshold: surely rejected, ap_threshold)
+            const u64 m = ballot64(c);
+            if (!m) continue;                                // (wave-uniform)
+            const int leader = __builtin_ctzll(m);
+            i64 base = 0;
+            if (lane == leader) base = (i64)atomicAdd((u64 *)ap.count, (u64)__popcll(m));
+            base = __shfl(base, leader, 64);
+            if (!c) continue;
+            const i64 gk = base + __popcll(m & ((1ull << lane) - 1ull));
+            if (gk >= ap.cap) continue;                      // (more candidates than the list holds: the host reports it from the counter)
+            ApCand q;
+            q.itime = itime; q.x = x; q.ins = ins; q.ch = ch; q.t = t; q.key = ((u32)e << 29) | (item & 0x1fffffffu);
+            q.j = 0u; q.m = item; q.gid = gid; q.e_dpe = e | (dpe ? 256 : 0); q.pad = 0;
+            ap.cand[gk] = q;
+        }
+    }
+}
