@@ -3336,8 +3336,10 @@ __global__ __launch_bounds__(FILL_TPB) void k_photon_fill(WfsDev d, GenArgs a, A
     ApStage aps;
     aps.cand = (ApCand *)(smem + o.ap);
     __shared__ i32 s_apn; __shared__ i64 s_apbase;
+    __shared__ i32 s_long;                                  // a (block, channel) segment of more than 64 photons exists (fast path)
     aps.n = &s_apn;
     if (AP && tid == 0) s_apn = 0;
+    if (tid == 0) s_long = 0;
     const i64 vb = block_of_workgroup(a);
     if (vb >= a.n_blocks) return;
     STAMP_INIT;
@@ -3444,7 +3446,8 @@ __global__ __launch_bounds__(FILL_TPB) void k_photon_fill(WfsDev d, GenArgs a, A
         // blocks owning consecutive ranges the tile is then in generation order as it is written, k_tile_order finds nothing to do
         for (int c = tid; c < nch; c += TPB) {
             const int s0 = hist[c], s1 = hist[c + 1];
-            if (s1 - s0 < 2 || s1 - s0 > 64) continue;       // (longer segments: left to k_tile_order)
+            if (s1 - s0 > 64) s_long = 1;                    // (every writer stores the same value)
+            if (s1 - s0 < 2 || s1 - s0 > 64) continue;       // (longer segments: by the whole workgroup, below)
             for (int i = s0 + 1; i < s1; i++) {
                 const unsigned short key = pidx[i]; const PhotonRec r = stage[i];
                 int j = i - 1;
@@ -3453,6 +3456,33 @@ __global__ __launch_bounds__(FILL_TPB) void k_photon_fill(WfsDev d, GenArgs a, A
             }
         }
         __syncthreads();
+        if (s_long) {                                        // block-uniform
+            // A peaked pattern row puts more than 64 photons of a block on one channel (a flat one never does: 2048 photons over
+            // 494 channels).  Nothing behind this kernel looks at the block ranges of a single-instruction set (k_tile_order_scan: head
+            // and tail only; no order keys are written for them), so such a segment is put into photon order here: every thread ranks
+            // up to GEN_BLOCK / TPB of its photons by counting the smaller indices (they are distinct), then the records move.
+            constexpr int EPT = GEN_BLOCK / TPB;
+            for (int c = 0; c < nch; c++) {
+                const int s0 = hist[c], n_seg = hist[c + 1] - s0;
+                if (n_seg <= 64) continue;                   // block-uniform
+                unsigned short key[EPT]; PhotonRec rec[EPT]; int rank[EPT];
+#pragma unroll
+                for (int q = 0; q < EPT; q++) {
+                    const int i = tid + q * TPB;
+                    rank[q] = -1;
+                    if (i < n_seg) {
+                        key[q] = pidx[s0 + i]; rec[q] = stage[s0 + i];
+                        int rk = 0;
+                        for (int j = 0; j < n_seg; j++) rk += pidx[s0 + j] < key[q] ? 1 : 0;
+                        rank[q] = rk;                        // < n_seg
+                    }
+                }
+                __syncthreads();                             // every record is read before any is written
+#pragma unroll
+                for (int q = 0; q < EPT; q++) if (rank[q] >= 0) { pidx[s0 + rank[q]] = key[q]; stage[s0 + rank[q]] = rec[q]; }
+                __syncthreads();
+            }
+        }
         STAMP(d, 3);
         // ---- bucket order: neighbouring lanes store photons of the same tile to consecutive addresses
         // (order keys only where the tile is sorted as a whole: the block ranges of a single-instruction set are in order as written)
