@@ -6,6 +6,7 @@ Run once in the build container (needs /root/reference; the GPU box never runs t
     python tests/golden/make_golden.py
     python tests/golden/make_golden.py optical_chain pmt_ap_draws     # these two write their own files only
     python tests/golden/make_golden.py pulse_edges                    # so does this one: the reference on designed photon lists
+    python tests/golden/make_golden.py window_edges                   # and this one: the reference on designed instruction spacings
 
 The reference's hot-path modules are imported under the stubs of ``_ref_stubs.py`` (identity njit, so
 every draw comes from numpy's seeded global generator).  What is written is DATA only: inputs and
@@ -601,6 +602,84 @@ def fixture_chain_optical(ref):
         cfgs[case] = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in ov.items()}
         print(case, len(out['call_kind']), 'calls', len(out['dg_left']), 'windows', len(out['in_t']), 'photons of', len(timings))
     with open(HERE + '/chain_optical_config.json', 'w') as f:
+        json.dump(cfgs, f)
+
+
+def window_edges_overrides(name):
+    """the two configs of the designed-spacing fixtures (tests/window_edges.py), shared with the tests through window_edges_config.json:
+    the optical chains' nVeto configuration and the bundled TPC one, both with pmt_transit_time_spread 0 -- the transit-time draw
+    (pulse.py:53-56) is then the constant pmt_transit_time_mean"""
+    return dict(optical_chain_overrides('main') if name == 'nveto' else {}, pmt_transit_time_spread=0)
+
+
+def fixture_window_edges(ref):
+    """window_edges.npz / window_edges_tpc.npz: RawDataOptical (rawdata.py:24-157, 461-495) over instruction streams whose every
+    digitise decision is designed to the ns (tests/window_edges.py holds the case table).  Recorded like the optical chains, plus
+    flush_at_call: the number of Pulse calls made whenever RawData.__call__ entered digitize_pulse_cache -- the reference's verdict on
+    every decision, empty caches included.  Asserted here: the recorded photon times are timings + instruction time +
+    pmt_transit_time_mean, every recorded pulse has the bounds the case table predicts, every decision got the verdict in `expect`,
+    and the windows are the predicted ones."""
+    from tests import window_edges as WE
+    cfgs = {}
+    for name in ('nveto', 'tpc'):
+        ov = window_edges_overrides(name)
+        cfg = base_config(**ov)
+        s = WE.CASES[name](cfg)
+        ins, channels, timings = s.inputs()
+        ref.load_resource._cached_configs.clear()
+        ref.pulse._cached_pmt_current_templates.clear()
+        ref.pulse._cached_uniform_to_pe_arr.clear()
+        orig_get = ref.load_resource.straxen.get_resource
+        if name == 'nveto':         # (nv_pmt_qe, as in fixture_chain_optical)
+            ref.load_resource.straxen.get_resource = lambda path, fmt='text': ({} if fmt == 'json' else orig_get(path, fmt=fmt))
+        try:
+            rd = ref.rawdata.RawDataOptical(cfg, channels=channels, timings=timings)
+        finally:
+            ref.load_resource.straxen.get_resource = orig_get
+        n_calls, flush_at = [0], []
+        sim_primary = rd.sim_primary
+
+        def counted_sim_primary(*a, **k):
+            n_calls[0] += 1
+            return sim_primary(*a, **k)
+
+        def counted_digitize():
+            flush_at.append(n_calls[0])
+            return type(rd).digitize_pulse_cache(rd)         # (the Recorder's, looked up when called)
+        rd.sim_primary, rd.digitize_pulse_cache = counted_sim_primary, counted_digitize
+        out = record_chain(ref, rd, ins, dict(nveto=1221, tpc=1222)[name],
+                           instruction_dtype + optical_extra_dtype + truth_extra_dtype + [('fill', bool)], store_entry=True)
+        for k in ('dg_sum_min', 'dg_sum_total'):
+            out.pop(k, None)
+        cutoff = cfg.get('nveto_time_max_cutoff', int(1e6))
+        out.update(channels=channels, timings=timings, cutoff=np.int64(cutoff), flush_at_call=np.array(flush_at, dtype=np.int64))
+        out.update(s.table())
+        # ---- the three assertions of the generator
+        n = len(ins)
+        assert len(out['call_kind']) == n == n_calls[0] and flush_at[-1] == n         # one call per instruction, in input order; the last digitise
+        ttm = int(cfg['pmt_transit_time_mean'])
+        for k in range(n):
+            a, b = int(ins['_first'][k]), int(ins['_last'][k])
+            keep = (timings[a:b] >= 0) & (timings[a:b] < cutoff)
+            want = sorted(zip(channels[a:b][keep].tolist(), (timings[a:b][keep] + ins['time'][k] + ttm).tolist()))
+            c, e = int(out['call_ph_off'][k]), int(out['call_ph_off'][k + 1])
+            assert sorted(zip(out['ph_ch'][c:e].tolist(), out['ph_t'][c:e].tolist())) == want, ('photon times of call', k)
+        off, pch, pl, pr = s.predicted_pulses()
+        assert np.array_equal(out['call_pulse_off'], off) and np.array_equal(out['pl_ch'], pch), 'pulses per call'
+        assert np.array_equal(out['pl_left'], pl) and np.array_equal(out['pl_right'], pr), 'pulse bounds'
+        verdict = np.isin(out['dec_first'], out['flush_at_call'][:-1])
+        wrong = np.flatnonzero(verdict != out['dec_expect'])
+        assert len(wrong) == 0, ('the reference disagrees with expect at clusters', wrong.tolist(), [s.clusters[i] for i in wrong])
+        assert set(out['flush_at_call'][:-1].tolist()) <= set(out['dec_first'].tolist())
+        wl, wr = s.predicted_windows()
+        assert np.array_equal(out['dg_left'], wl) and np.array_equal(out['dg_right'], wr), 'windows'
+        fname = WE.FIXTURES[name]
+        np.savez_compressed(HERE + '/' + fname, **out)
+        cfgs[name] = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in ov.items()}
+        designed = out['dec_has_delta']
+        print(fname, n, 'instructions', len(out['dec_first']), 'decisions', int(designed.sum()), 'designed', len(out['dg_left']), 'windows',
+              len(out['zle_ch']), 'ZLE tuples', os.path.getsize(HERE + '/' + fname), 'bytes')
+    with open(HERE + '/window_edges_config.json', 'w') as f:
         json.dump(cfgs, f)
 
 
@@ -1378,7 +1457,7 @@ def fixture_chain_stats(ref):
 if __name__ == '__main__':
     which = sys.argv[1:] or ['tables', 'add_current', 'chains', 'dists', 'models', 'stats', 'chunker', 'ele_ap_draws', 'gas_gap', 'aft_sigma', 'noise_float', 'diffusion', 'frontend']
     ref = import_reference_interface() if ('chunker' in which or 'frontend' in which) else import_reference()
-    own = {'optical_chain', 'pmt_ap_draws', 'pulse_edges'}           # these write their own files only
+    own = {'optical_chain', 'pmt_ap_draws', 'pulse_edges', 'window_edges'}           # these write their own files only
     p = fixture_tables(ref) if set(which) - own else None
     if 'optical_chain' in which:
         fixture_chain_optical(ref)
@@ -1386,6 +1465,8 @@ if __name__ == '__main__':
         fixture_pmt_ap_draws(ref)
     if 'pulse_edges' in which:
         fixture_pulse_edges(ref)
+    if 'window_edges' in which:
+        fixture_window_edges(ref)
     if 'add_current' in which:
         fixture_add_current(ref, p)
     if 'chains' in which:

@@ -81,6 +81,22 @@ def optical_chain_config(case, **overrides):
     return c
 
 
+def window_edges_config(name, **overrides):
+    """the configs of the designed-spacing fixtures (make_golden.py: window_edges_overrides; tests/window_edges.py): 'nveto' -- the optical
+    chains' 120 channels, channel 7 dead, right_raw_extension 2000 -- and 'tpc', the bundled configuration; pmt_transit_time_spread 0 in both"""
+    import json
+    ov = json.load(open(os.path.join(GOLDEN, 'window_edges_config.json')))[name]
+    if 'gains' in ov:
+        ov['gains'] = np.asarray(ov['gains'], dtype=np.float64)
+        ov['channels_bottom'] = np.asarray(ov['channels_bottom'], dtype=np.int64)
+        ov['channel_map'] = {k: (tuple(v) if isinstance(v, list) else v) for k, v in ov['channel_map'].items()}
+    c = xenonnt_test_config(**ov)
+    if 'gains' in ov:
+        c['photon_area_distribution'] = dict(c['photon_area_distribution'], n_channels=len(ov['gains']))
+    c.update(overrides)
+    return c
+
+
 def photons_by_call_and_channel(off, t, ch):
     """canonical form of a per-call photon list: per call the (channel, time) pairs sorted by channel, then time -- the order
     inside a channel is not pinned (sim_primary sorts with numpy's default, unstable argsort)"""

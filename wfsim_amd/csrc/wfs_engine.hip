@@ -1336,8 +1336,10 @@ try {
     const i64 S = h->ap_active ? 2 * n : n;
     h->n_ins = n; h->n_psets = n; h->n_sets = S; h->n_tiles = S * nch; h->n_emitters = 0; h->n_ap_photons = 0;
     if (h->n_tiles > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "too many tiles in one batch");
+    i64 n_ranged = 0;        // photons the instructions name: ranges may overlap (rawdata.py:477 takes any), so this can exceed n_ph
     for (i64 i = 0; i < n; i++) {
         if (first[i] < 0 || last[i] < first[i] || last[i] > n_ph) return h->fail(WFS_E_INVALID, "_first/_last out of range");
+        n_ranged += (i64)last[i] - first[i];
         if (h->ap_active && (i64)last[i] - first[i] >= (1LL << 29))      // (the order key of an afterpulse holds 29 bits of its parent's index)
             return h->fail(WFS_E_CAPACITY, "an instruction of 2^29 or more supplied photons with PMT afterpulses on");
     }
@@ -1353,7 +1355,8 @@ try {
     TRY(upload(h, h->opt_first, first, (size_t)n * 4)); TRY(upload(h, h->opt_last, last, (size_t)n * 4));
     TRY(upload(h, h->opt_ch, channels, (size_t)n_ph * 4)); TRY(upload(h, h->opt_time, timings, (size_t)n_ph * 8));
     TRY(ensure(h, h->tile_count, (size_t)h->n_tiles * 4)); TRY(ensure(h, h->tile_cursor, (size_t)h->n_tiles * 4)); TRY(ensure(h, h->tile_off, (size_t)(h->n_tiles + 1) * 8));
-    TRY(ensure(h, h->opt_t, (size_t)n_ph * 4)); TRY(ensure(h, h->opt_item, (size_t)n_ph * 4));
+    // (the bucketed copies hold a slot per photon of every instruction's range, not per entry of the flat arrays)
+    TRY(ensure(h, h->opt_t, (size_t)n_ranged * 4)); TRY(ensure(h, h->opt_item, (size_t)n_ranged * 4));
     {
         FillGroup fg(h, "fills_optical");
         TRY(fg.zero(h->tile_count.p, (size_t)T * 4)); TRY(fg.zero(h->tile_cursor.p, (size_t)T * 4)); TRY(fg.zero(h->scal.p, sizeof(WfsScal)));
