@@ -7,6 +7,7 @@ Run once in the build container (needs /root/reference; the GPU box never runs t
     python tests/golden/make_golden.py optical_chain pmt_ap_draws     # these two write their own files only
     python tests/golden/make_golden.py pulse_edges                    # so does this one: the reference on designed photon lists
     python tests/golden/make_golden.py window_edges                   # and this one: the reference on designed instruction spacings
+    python tests/golden/make_golden.py zle_edges                      # and this one: the reference on rows designed through the noise table
 
 The reference's hot-path modules are imported under the stubs of ``_ref_stubs.py`` (identity njit, so
 every draw comes from numpy's seeded global generator).  What is written is DATA only: inputs and
@@ -141,6 +142,7 @@ class Recorder:
         self.zle = []          # (digitize index, ch, left, right, data)
         self._gain_parts = None
         self._randint = []
+        self.designed_ix = None  # per digitise window the noise start index to hand out instead of the draw (zle_edges)
 
     def install(self):
         P = self.ref.pulse.Pulse
@@ -192,6 +194,10 @@ class Recorder:
 
             def randint(*a, **k):
                 v = old(*a, **k)
+                if rec.designed_ix is not None:
+                    # a designed start index: one the reference could have drawn (rawdata.py:417: low=0, high=high)
+                    v = int(rec.designed_ix[len(rec.digits)])
+                    assert k.get('low', 0) == 0 and 0 <= v < k['high'], (len(rec.digits), v, k)
                 rec._randint.append(int(v))
                 return v
             np.random.randint = randint
@@ -876,6 +882,79 @@ def fixture_pulse_edges(ref):
         json.dump(pulse_edges_geometry_overrides(), f)
 
 
+def run_zle_edges(ref, config, fam, seed):
+    """run_pulse_edges' route with the noise on: per case one Pulse.__call__ with preassigned gains, per window one
+    digitize_pulse_cache() + ZLE() under the Recorder, which hands the window's designed ix_rand to add_noise in place of the draw (and
+    asserts it is below the `high` the reference passed).  The designed table is installed as run_chain installs noise=."""
+    ref.load_resource._cached_configs.clear()
+    ref.pulse._cached_pmt_current_templates.clear()
+    ref.pulse._cached_uniform_to_pe_arr.clear()
+    path = TMP + '/noise_zle_edges.npz'
+    np.savez(path, arr_0=fam.table())
+    config = dict(config, noise_file=path, enable_noise=True)
+    pulse = ref.pulse.Pulse(config)
+    rd = ref.rawdata.RawData(config)
+    assert rd.resource.noise_data.shape == (fam.N, fam.columns) and np.array_equal(rd.resource.noise_data, fam.table())
+    rd._pulses_cache = []
+    rec = Recorder(ref)
+    rec.designed_ix = fam.ix_rands()
+    rec.install()
+    np.random.seed(seed)
+    c2a = None
+    try:
+        for w in fam.windows:
+            for ci in w['cases']:
+                case = fam.cases[ci]
+                pulse._photon_timings = case['times'].copy()
+                pulse._photon_channels = np.full(len(case['times']), case['channel'], dtype=np.int64)
+                pulse._photon_gains = case['gains'].copy()
+                pulse()
+                assert len(pulse._pulses) == 1
+                # no sample of a designed pulse near a rounding tie: either arithmetic form rounds it like the reference
+                x = np.abs(pulse._pulses[0]['current'] * pulse.current_2_adc)
+                assert np.all(np.abs(x - np.floor(x) - 0.5) > 1e-6 * np.maximum(x, 1.0)), case['name']
+                rd._pulses_cache += pulse._pulses
+            rd.digitize_pulse_cache()
+            for c, left, right, data in rd.ZLE():
+                rec.zle.append((len(rec.digits) - 1, int(c), int(left), int(right), np.array(data, dtype=np.int64)))
+    finally:
+        rec.uninstall()
+    assert len(rec.digits) == len(fam.windows)
+    out = {}
+    flatten_recorder(rec, out)
+    assert np.array_equal(out['dg_ix_rand'], fam.ix_rands()), (out['dg_ix_rand'], fam.ix_rands())
+    order = [ci for w in fam.windows for ci in w['cases']]
+    out['set_cluster'] = np.array([fam.cases[ci]['window'] for ci in order], dtype=np.int32)
+    out['set_tmin'] = np.array([int(fam.cases[ci]['times'].min()) for ci in order], dtype=np.int64)
+    out['call_case'] = np.array(order, dtype=np.int32)
+    out['case_names'] = np.array([c['name'] for c in fam.cases])
+    out['noise_shape'] = np.array([fam.N, fam.columns], dtype=np.int64)
+    for k in [k for k in out if k.startswith('call_truth_')] + ['e_t', 'call_e_off', 'dg_sum_min', 'dg_sum_total']:
+        del out[k]              # (the truth of the designed photons and the sum row are not what this fixture is about)
+    return out
+
+
+def fixture_zle_edges(ref):
+    """zle_edges.npz: the reference on rows designed sample by sample through the noise table (tests/zle_edges.py holds the case
+    table): per family (a configuration and a table) the flatten_recorder layout under '<family>/<name>'"""
+    from tests import zle_edges as ZE
+    tab = np.load(HERE + '/tables.npz')
+    templates, c2a = tab['templates'], float(tab['current_2_adc'])
+    out, cfgs = dict(families=np.array(ZE.FAMILIES)), {}
+    for i, name in enumerate(ZE.FAMILIES):
+        cfgs[name] = ZE.overrides(name)
+        cfg = base_config(**cfgs[name])
+        fam = ZE.family(name, cfg, templates, c2a)
+        r = run_zle_edges(ref, cfg, fam, 6100 + i)
+        for k, v in r.items():
+            out[f'{name}/{k}'] = v
+        print(name, 'windows', len(fam.windows), 'rows', len(r['row_ch']), 'samples', len(r['row_data']), 'intervals', len(r['zle_ch']),
+              'table', (fam.N, fam.columns))
+    np.savez_compressed(HERE + '/zle_edges.npz', **out)
+    with open(HERE + '/zle_edges_config.json', 'w') as f:
+        json.dump(cfgs, f, indent=0, sort_keys=True)
+
+
 class StubDelayHist:
     """stand-in for the multihist.Hist1d the reference loads as uniform_to_ele_ap (private resource): the members
     afterpulse.py touches -- n, bin_centers, get_random (bin by content, uniform inside the bin)"""
@@ -1457,7 +1536,7 @@ def fixture_chain_stats(ref):
 if __name__ == '__main__':
     which = sys.argv[1:] or ['tables', 'add_current', 'chains', 'dists', 'models', 'stats', 'chunker', 'ele_ap_draws', 'gas_gap', 'aft_sigma', 'noise_float', 'diffusion', 'frontend']
     ref = import_reference_interface() if ('chunker' in which or 'frontend' in which) else import_reference()
-    own = {'optical_chain', 'pmt_ap_draws', 'pulse_edges', 'window_edges'}           # these write their own files only
+    own = {'optical_chain', 'pmt_ap_draws', 'pulse_edges', 'window_edges', 'zle_edges'}           # these write their own files only
     p = fixture_tables(ref) if set(which) - own else None
     if 'optical_chain' in which:
         fixture_chain_optical(ref)
@@ -1467,6 +1546,8 @@ if __name__ == '__main__':
         fixture_pulse_edges(ref)
     if 'window_edges' in which:
         fixture_window_edges(ref)
+    if 'zle_edges' in which:
+        fixture_zle_edges(ref)
     if 'add_current' in which:
         fixture_add_current(ref, p)
     if 'chains' in which:

@@ -97,6 +97,16 @@ def window_edges_config(name, **overrides):
     return c
 
 
+def zle_edges_config(name, **overrides):
+    """the settings of a family of the designed-row fixture (make_golden.py zle_edges; tests/zle_edges.py: overrides): the bundled
+    configuration with the family's trigger window, thresholds and HE factor, noise on -- the table itself is built from the case
+    table (tests/zle_edges.py: Family.table) and goes in as noise_data"""
+    import json
+    c = xenonnt_test_config(**json.load(open(os.path.join(GOLDEN, 'zle_edges_config.json')))[name])
+    c.update(overrides)
+    return c
+
+
 def photons_by_call_and_channel(off, t, ch):
     """canonical form of a per-call photon list: per call the (channel, time) pairs sorted by channel, then time -- the order
     inside a channel is not pinned (sim_primary sorts with numpy's default, unstable argsort)"""
