@@ -93,6 +93,7 @@ int wfs_create(const wfs_config *cfg, int device, wfs_handle **out);
 int wfs_destroy(wfs_handle *h);
 const char *wfs_last_error(const wfs_handle *h);
 int wfs_device_count(int *n);
+int wfs_device_allocations(int64_t *buffers, int64_t *bytes);      /* device buffers, and their bytes, that the handles of this process hold now */
 
 /* Init-time tables (host pointers, copied to HBM once).
  *   templates  f64[10][tlen]        Pulse.init_pmt_current_templates            pulse.py:146-187

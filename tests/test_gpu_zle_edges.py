@@ -56,7 +56,7 @@ def _engine(name, mode, monkeypatch):
 
 
 def _resident_admitted(fam):
-    """the engine's rule for resident rows (wfs_engine.hip:1881-1882)"""
+    """the engine's rule for resident rows (wfs_engine.hip run_geometry: res_on)"""
     return fam.hold >= ZE.FAST_HOLD and fam.N >= ZE.NOISE_MIN_FAST and not fam.name.startswith('he')
 
 

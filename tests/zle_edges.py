@@ -19,12 +19,12 @@ import numpy as np
 CHUNK = 64                  # ZleFast: "only the first hit of a 64-sample chunk can open an interval" (wfs_kernels.h:1706-1746); 64 slots per flush (:1719-1724)
 BLOCK = 256                 # samples per wave load of k_zle's fast path, the step of the scalar noise start (wfs_kernels.h:1808-1810)
 TRIP = 1024                 # G = 4 blocks per trip of k_zle's fast path (wfs_kernels.h:1795)
-FAST_HOLD = 63              # ZleFast / resident rows need a hold-off of at least this (wfs_kernels.h:1792, wfs_engine.hip:1881)
-NOISE_MIN_FAST = 512        # shortest table of the fast row loads and of resident rows (wfs_device.h:221, wfs_engine.hip:1882)
+FAST_HOLD = 63              # ZleFast / resident rows need a hold-off of at least this (wfs_kernels.h:1792, wfs_engine.hip run_geometry: res_on)
+NOISE_MIN_FAST = 512        # shortest table of the fast row loads and of resident rows (wfs_device.h:221, wfs_engine.hip run_geometry: res_on)
 NOISE_PAD = 4               # a noise row is followed by its own first samples (wfs_device.h:219)
 WFS_SPR = 110               # samples per record (wfs_device.h:220)
 PACK_U = 4                  # records in flight in k_pack (wfs_kernels.h:2180)
-RES_SEGMENTS = (1024, 256)  # resident segment: res_max_len (wfs_engine.hip:73) and WFS_RES_MAX_LEN=256 (wfs_engine.hip:588)
+RES_SEGMENTS = (1024, 256)  # resident segment: wfs_handle::res_max_len and WFS_RES_MAX_LEN=256 (wfs_engine.hip wfs_create)
 RES_SHORT_LEN = 768         # resident rows up to this length take the short launch (wfs_kernels.h:187)
 SEAMS = (64, 256, 512, 768, 1024, 2048)          # chunk, block / 256-sample segment, RES_SHORT_LEN, trip / 1024-sample segment, second trip
 

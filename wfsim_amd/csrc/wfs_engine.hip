@@ -6,6 +6,7 @@
 #include "wfs_kernels.h"
 #include "wfs_tilegen.h"
 #include "wfs_boundary.h"
+#include "wfs_devbuf.h"
 #include "../../include/wfsim_amd.h"
 
 // Every pulse kernel exists in two forms: FMA = true (wfs_config.fma, one rounding per template * gain term) and FMA = false (numpy's two
@@ -37,10 +38,6 @@
 
 namespace {
 
-struct DevBuf {
-    void *p = nullptr; size_t cap = 0;
-    template <class T> T *as() const { return (T *)p; }
-};
 struct Pmf { std::vector<double> p; long vmin = 0; };      // probability mass function of an integer delay term
 
 struct ApElem { int n_bins_delay = 0, n_bins_amp = 0, amp_2d = 0, is_uniform = 0; double delay_bin = 0, amp_bin = 0; DevBuf delay_cdf, amp_cdf, prob, thr, delay_guide, amp_guide;
@@ -48,6 +45,11 @@ struct ApElem { int n_bins_delay = 0, n_bins_amp = 0, amp_2d = 0, is_uniform = 0
                 int delay_sorted = 0, amp_sorted = 0; };
 
 struct KernelTime { std::string name; hipEvent_t a, b; };
+inline void clear_times(std::vector<KernelTime> &times)
+{
+    for (auto &t : times) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
+    times.clear();
+}
 
 // bits of wfs_set_debug (wfs_handle::keep_currents); include/wfsim_amd.h documents them by number
 enum : int {
@@ -59,6 +61,10 @@ enum : int {
 };
 
 }  // namespace
+
+// the allocator of wfs_devbuf.h
+static int wfs_dev_alloc(void **p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+static void wfs_dev_free(void *p) { (void)hipFree(p); }
 
 struct wfs_handle {
     wfs_config cfg;
@@ -159,6 +165,16 @@ struct wfs_handle {
     std::string launch_err;      // first failed launch of the current call (wfs_set_debug bit 3: every launch is checked)
     int n_fail = 0;              // calls of fail(): a FillGroup that dies with segments checks that an error return is why
     int fail(int code, const std::string &msg) { err = msg; n_fail++; return code; }
+
+    // what is not a DevBuf; the buffers, and the members that hold some, free themselves after this body
+    ~wfs_handle()
+    {
+        clear_times(times);
+        if (own_stream) hipStreamDestroy(stream);
+        if (copy_stream) { hipStreamSynchronize(copy_stream); hipStreamDestroy(copy_stream); }
+        for (hipEvent_t e : rec_copied) if (e) hipEventDestroy(e);
+        if (h_scal) hipHostFree(h_scal);
+    }
 };
 
 namespace {
@@ -182,13 +198,7 @@ static u32 ap_threshold(double prob, double modifier, bool dpe)
 
 int ensure(wfs_handle *h, DevBuf &b, size_t bytes)
 {
-    if (bytes == 0) bytes = 16;
-    if (b.cap >= bytes) return WFS_OK;
-    if (b.p) HIPCHK(hipFree(b.p));
-    size_t want = bytes + bytes / 8 + 256;
-    b.p = nullptr; b.cap = 0;
-    HIPCHK(hipMalloc(&b.p, want));
-    b.cap = want;
+    if (int e = b.ensure(bytes)) return h->fail(WFS_E_HIP, std::string("hipMalloc: ") + hipGetErrorString((hipError_t)e));
     return WFS_OK;
 }
 
@@ -526,6 +536,13 @@ extern "C" {
 
 int wfs_device_count(int *n) try { return hipGetDeviceCount(n) == hipSuccess ? WFS_OK : WFS_E_HIP; } WFS_CATCH(nullptr)
 
+int wfs_device_allocations(int64_t *buffers, int64_t *bytes)
+{
+    if (!buffers || !bytes) return WFS_E_INVALID;
+    *buffers = wfs_dev_live_buffers.load(std::memory_order_relaxed); *bytes = wfs_dev_live_bytes.load(std::memory_order_relaxed);
+    return WFS_OK;
+}
+
 int wfs_create(const wfs_config *cfg, int device, wfs_handle **out)
 try {
     if (!cfg || !out) return WFS_E_INVALID;
@@ -536,16 +553,17 @@ try {
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return WFS_E_HIP;      // fail loudly: no CPU fallback
     if (device < 0 || device >= ndev) return WFS_E_INVALID;
     if (hipSetDevice(device) != hipSuccess) return WFS_E_HIP;
-    wfs_handle *h = new wfs_handle();
+    std::unique_ptr<wfs_handle> owner(new wfs_handle());
+    wfs_handle *h = owner.get();
     h->cfg = *cfg; h->device = device;
     h->generic_geom = cfg->dt != WFS_DT || cfg->tlen != 22;
     { hipDeviceProp_t prop; h->n_cus = (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256; }
     memset(&h->dev, 0, sizeof(h->dev));
-    if (hipStreamCreate(&h->stream) != hipSuccess) { delete h; return WFS_E_HIP; }
+    if (hipStreamCreate(&h->stream) != hipSuccess) return WFS_E_HIP;
     h->own_stream = true;
     if (hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&h->rec_copied[0], hipEventDisableTiming) != hipSuccess
-        || hipEventCreateWithFlags(&h->rec_copied[1], hipEventDisableTiming) != hipSuccess) { delete h; return WFS_E_HIP; }
-    if (hipMalloc(&h->scal.p, sizeof(WfsScal)) != hipSuccess) { delete h; return WFS_E_HIP; }
+        || hipEventCreateWithFlags(&h->rec_copied[1], hipEventDisableTiming) != hipSuccess) return WFS_E_HIP;
+    if (ensure(h, h->scal, sizeof(WfsScal)) != WFS_OK) return WFS_E_HIP;
     {   // the host copy of the scalar block; mapped and coherent with the sequence word on the cache line behind it where the
         // device may write it (read_scal), else -- or with WFS_HOST_SYNC=copy, A/B runs -- page-locked for the copy as before
         const char *e = getenv("WFS_HOST_SYNC");
@@ -557,19 +575,18 @@ try {
             else { hipHostFree(h->h_scal); h->h_scal = nullptr; }
         }
         (void)hipGetLastError();
-        if (!h->publish && hipHostMalloc((void **)&h->h_scal, bytes, hipHostMallocDefault) != hipSuccess) { hipFree(h->scal.p); delete h; return WFS_E_HIP; }
+        if (!h->publish && hipHostMalloc((void **)&h->h_scal, bytes, hipHostMallocDefault) != hipSuccess) return WFS_E_HIP;
         memset(h->h_scal, 0, bytes);
         h->h_seq = (uint64_t *)(h->h_scal + 1);
         if (h->publish) { h->d_hscal = (WfsScal *)dp; h->d_hseq = (u64 *)(h->d_hscal + 1); }
     }
-    h->scal.cap = sizeof(WfsScal);
 #ifdef WFS_STAMPS
-    if (hipMalloc(&h->stamps.p, 4096 * 64 * 8) != hipSuccess) { delete h; return WFS_E_HIP; }
-    h->stamps.cap = 4096 * 64 * 8; hipMemset(h->stamps.p, 0, 4096 * 64 * 8); h->dev.stamps = h->stamps.as<unsigned long long>();
+    if (ensure(h, h->stamps, 4096 * 64 * 8) != WFS_OK) return WFS_E_HIP;
+    hipMemset(h->stamps.p, 0, 4096 * 64 * 8); h->dev.stamps = h->stamps.as<unsigned long long>();
 #endif
     refresh_dev(h);
     if (const char *e = getenv("WFS_TAP_SPARSE_MAX")) h->tap_sparse_max = std::min(atoi(e), TAP_LIST_LEN - 1);      // tuning knob of tap_block (results do not depend on it)
-    if (build_time_tables(h) != WFS_OK) { delete h; return WFS_E_HIP; }
+    if (build_time_tables(h) != WFS_OK) return WFS_E_HIP;
     // the pulse kernel stages up to 1024 start bins per tile: (10 * 1024 + 220) * 8 + 1024 * 4 bytes of LDS
 #define WFS_BIG_LDS(K, B) hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, (B) * 1024)
 #define WFS_BIG_LDS_F(KM, B) do { WFS_BIG_LDS(HIP_KERNEL_NAME(KM(true)), B); WFS_BIG_LDS(HIP_KERNEL_NAME(KM(false)), B); } while (0)
@@ -601,7 +618,7 @@ try {
         hipFuncSetAttribute((const void *)k_s2_bright<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, total);
         hipFuncSetAttribute((const void *)k_s2_bright<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, total);
     }
-    *out = h;
+    *out = owner.release();
     return WFS_OK;
 } WFS_CATCH(nullptr)
 
@@ -618,31 +635,8 @@ try {
             for (size_t r = 0; r < 4096; r++) for (int i = 0; i < 64; i++) v[i] += all[r * 64 + i];
             for (int i = 0; i < 32; i++) if (v[i + 32]) fprintf(stderr, "stamp %2d: %10.0f cycles/wg  (%llu wgs, %.3e cycles total)\n", i, (double)v[i] / (double)v[i + 32], v[i + 32], (double)v[i]);
         }
-        hipFree(h->stamps.p);
     }
 #endif
-    DevBuf *all[] = {&h->rec_key, &h->rec_key2, &h->rec_val, &h->rec_val2, &h->rec_dest, &h->sort_tmp, &h->row_desc, &h->pmap[0].values, &h->pmap[1].values, &h->map_row_ins[0], &h->map_row_ins[1], &h->map_row_id[0], &h->map_row_id[1], &h->map_x, &h->map_y, &h->map_z, &h->map_nb_idx[0], &h->map_nb_idx[1], &h->map_nb_w[0], &h->map_nb_w[1], &h->d_tabs, &h->gg_inv, &h->ins_gg, &h->ins_ggw, &h->ins_ggsum, &h->prop_top, &h->prop_bot, &h->ins_tab, &h->ins_tabb, &h->ins_pzi, &h->ins_pzf, &h->blk_e, &h->blk_base, &h->blk_cnt, &h->blk_ins, &h->eblk_ins, &h->ins_ph0, &h->blk_desc, &h->noise_override, &h->ap_ins, &h->ap_ch, &h->ap_t, &h->ap_gain, &h->ap_cand, &h->ap_args_dev, &h->ap_seg, &h->set_gid, &h->opt_t, &h->opt_item, &h->opt_first, &h->opt_last, &h->opt_ch, &h->opt_time, &h->t_templates, &h->t_spe, &h->t_gains, &h->t_thr_truth, &h->t_thr_zle, &h->t_lumx, &h->t_lumt, &h->t_noise, &h->t_noise_f,
-        &h->ins_type, &h->ins_time, &h->ins_amp, &h->ins_gid, &h->ins_p, &h->ins_dm, &h->ins_ds, &h->ins_sc, &h->ins_cdfrow, &h->cdf_table, &h->chan_alias, &h->ins_embase, &h->ins_set, &h->set_ins_off, &h->set_ins_list,
-        &h->em_off, &h->em_zg, &h->pois_cdf, &h->pois_kmin, &h->set_cluster, &h->set_t0, &h->set_mode, &h->cl_tmin, &h->cl_gid, &h->cl_end, &h->cl_group, &h->em_time, &h->em_nph,
-        &h->em_ins, &h->em_ph_off, &h->el_stat, &h->el_minmax, &h->tile_count, &h->tile_off, &h->tile_cursor, &h->tile_tmin, &h->tile_tmax,
-        &h->active_tiles, &h->sparse_tiles, &h->dense_tiles, &h->wave_tiles, &h->ph, &h->ph_gain, &h->grp_lo, &h->grp_hi, &h->grp_left, &h->grp_right, &h->grp_ixrand,
-        &h->grp_gid, &h->row_lo, &h->row_hi, &h->acc_len, &h->acc_off, &h->itv_cap, &h->itv_off, &h->active_rows, &h->raw, &h->itv_left,
-        &h->itv_right, &h->itv_n, &h->row_nrec, &h->rec_off, &h->records_ab[0], &h->records_ab[1], &h->truth, &h->tminmax, &h->tile_truth, &h->tile_desc, &h->gather_idx, &h->gather_out, &h->currents, &h->cur_len, &h->cur_off,
-        &h->row_dbg, &h->row_dbg_len, &h->row_dbg_off, &h->scan_tmp, &h->scal,
-        &h->ph_idx, &h->ap_key, &h->order_list, &h->order_list2, &h->ins_sbase, &h->tile_tail, &h->tile_tailbase, &h->ins_fullsort, &h->row_pmax, &h->ins_fused, &h->ins_nsurv, &h->ins_bcap, &h->ins_bcap_all, &h->ins_boff, &h->et32, &h->ftiles, &h->tbuf, &h->row_cnt, &h->row_tile, &h->tile_done, &h->tile_kind, &h->huge_start, &h->huge_cbeg, &h->huge_keys, &h->huge_keys2, &h->huge_vals, &h->huge_vals2, &h->huge_rec, &h->huge_gain,
-        &h->pack_desc, &h->row_bad, &h->fin_len, &h->res_cnt, &h->fin_off, &h->res_toff, &h->res_desc, &h->fin, &h->res_long, &h->res_rows,
-        &h->pmap[0].cell_start, &h->pmap[0].cell_pts, &h->pmap[1].cell_start, &h->pmap[1].cell_pts};
-    for (DevBuf *b : all) if (b->p) hipFree(b->p);
-    if (h->h_scal) hipHostFree(h->h_scal);
-    for (DevBuf *b : {&h->pmap[0].points, &h->pmap[1].points, &h->smap_pos, &h->smap_out, &h->smap_nb_idx, &h->smap_nb_w, &h->ins_aft, &h->ins_sigr, &h->ins_siga, &h->diff_row_ins, &h->diff_row_id, &h->diff_pre}) if (b->p) hipFree(b->p);
-    for (auto &m : h->smaps) for (DevBuf *b : {&m->g.values, &m->g.points, &m->tx, &m->ty, &m->c}) if (b->p) hipFree(b->p);
-    for (int q = 0; q < 6; q++) if (h->tt_alias[q].p) hipFree(h->tt_alias[q].p);
-    for (auto &b : h->x_alias) if (b.p) hipFree(b.p);
-    for (auto &a : h->ap) { if (a.delay_cdf.p) hipFree(a.delay_cdf.p); if (a.amp_cdf.p) hipFree(a.amp_cdf.p); if (a.prob.p) hipFree(a.prob.p); if (a.thr.p) hipFree(a.thr.p); if (a.delay_guide.p) hipFree(a.delay_guide.p); if (a.amp_guide.p) hipFree(a.amp_guide.p); }
-    for (auto &t : h->times) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
-    if (h->own_stream) hipStreamDestroy(h->stream);
-    if (h->copy_stream) { hipStreamSynchronize(h->copy_stream); hipStreamDestroy(h->copy_stream); }
-    for (int q = 0; q < 2; q++) if (h->rec_copied[q]) hipEventDestroy(h->rec_copied[q]);
     delete h;
     return WFS_OK;
 } WFS_CATCH(nullptr)
@@ -767,7 +761,7 @@ try {
     // guides of the sorted rows (ApGuide): for every cell of u * scale a bracket of "first entry >= u" that holds for every u the
     // device can put into the cell -- the cell's ends moved outwards by 2^-40 (the one rounding of u * scale is 2^-53)
     auto build_guides = [&](DevBuf &buf, const double *c, size_t rows, int n) -> int {
-        if (buf.p) { hipFree(buf.p); buf.p = nullptr; buf.cap = 0; }
+        buf.reset();
         if (n < 1 || n > 65535) return WFS_OK;
         std::vector<ApGuide> g(rows);
         const double margin = 9.094947017729282e-13;            // 2^-40
@@ -787,8 +781,8 @@ try {
         HIPCHK(hipStreamSynchronize(h->stream));
         return WFS_OK;
     };
-    if (a.delay_sorted) TRY(build_guides(a.delay_guide, delay_cdf, (size_t)h->cfg.n_tpc, n_bins_delay)); else if (a.delay_guide.p) { hipFree(a.delay_guide.p); a.delay_guide.p = nullptr; a.delay_guide.cap = 0; }
-    if (a.amp_sorted) TRY(build_guides(a.amp_guide, amp_cdf, (size_t)(amp_2d ? h->cfg.n_tpc : 1), n_bins_amp)); else if (a.amp_guide.p) { hipFree(a.amp_guide.p); a.amp_guide.p = nullptr; a.amp_guide.cap = 0; }
+    if (a.delay_sorted) TRY(build_guides(a.delay_guide, delay_cdf, (size_t)h->cfg.n_tpc, n_bins_delay)); else a.delay_guide.reset();
+    if (a.amp_sorted) TRY(build_guides(a.amp_guide, amp_cdf, (size_t)(amp_2d ? h->cfg.n_tpc : 1), n_bins_amp)); else a.amp_guide.reset();
     h->dev.n_ap = std::max(h->dev.n_ap, e + 1);
     HIPCHK(hipStreamSynchronize(h->stream));
     return WFS_OK;
@@ -910,8 +904,8 @@ try {
     if (!h->tables_set) return h->fail(WFS_E_STATE, "wfs_set_tables must be called first");
     if (n_tables < 0 || n_tables > 65536 || (n_tables > 0 && (!base || !pmf_off || !pmf || !vmin))) return h->fail(WFS_E_INVALID, "wfs_set_delay_models: bad arguments");
     HIPCHK(hipSetDevice(h->device));
-    for (auto &b : h->x_alias) if (b.p) hipFree(b.p);
-    h->x_alias.assign((size_t)n_tables, DevBuf{});
+    h->x_alias.clear();
+    h->x_alias.resize((size_t)n_tables);
     h->h_tabs.assign((size_t)n_tables + 2, AliasTab{});
     h->n_user_tabs = n_tables; h->ins_models = false;
     for (int k = 0; k < n_tables; k++) {
@@ -2255,8 +2249,7 @@ try {
     if (h->dev_rows_pending && from_generator(h)) return h->fail(WFS_E_STATE, "instructions with cdf_row -1: call wfs_eval_pattern_rows before wfs_run");
     h->ran = false; h->gen_done = false; h->gen_order_ready = false;
     HIPCHK(hipSetDevice(h->device));
-    for (auto &t : h->times) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
-    h->times.clear();
+    clear_times(h->times);
     TRY(run_input(h));
     h->gen_done = true;
     if (h->keep_currents & DBG_GEN_ONLY) { HIPCHK(hipStreamSynchronize(h->stream)); return WFS_OK; }      // wfs_set_debug bit 2: photon generation only

@@ -110,7 +110,7 @@ EXPORTS = ['wfs_create', 'wfs_destroy', 'wfs_last_error', 'wfs_device_count', 'w
            'wfs_set_gas_gap_model', 'wfs_set_instruction_gas_gap', 'wfs_set_pattern_map_points', 'wfs_set_instruction_aft',
            'wfs_scalar_map_grid', 'wfs_scalar_map_points', 'wfs_scalar_map_spline', 'wfs_scalar_map_eval', 'wfs_set_noise_float', 'wfs_set_instruction_diffusion',
            'wfs_scalar_map_grid_array', 'wfs_scalar_map_points_array', 'wfs_scalar_map_linear', 'wfs_scalar_map_eval_array',
-           'wfs_set_sum_signal', 'wfs_copy_sum_signal']
+           'wfs_set_sum_signal', 'wfs_copy_sum_signal', 'wfs_device_allocations']
 
 
 def load_library():
@@ -134,6 +134,7 @@ def load_library():
         lib.wfs_last_error.argtypes = [C.c_void_p]
         lib.wfs_records_dev_ptr.restype = C.c_void_p
         lib.wfs_records_dev_ptr.argtypes = [C.c_void_p]
+        lib.wfs_device_allocations.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         _lib = lib
     return _lib
 
@@ -142,6 +143,15 @@ def device_count():
     n = C.c_int(0)
     rc = load_library().wfs_device_count(C.byref(n))
     return n.value if rc == 0 else 0
+
+
+def device_allocations():
+    """(buffers, bytes) of device memory that the engines of this process hold now; every ``close()`` gives its share back."""
+    n, b = C.c_int64(0), C.c_int64(0)
+    rc = load_library().wfs_device_allocations(C.byref(n), C.byref(b))
+    if rc != 0:
+        raise WfsError(f'wfs_device_allocations failed ({rc})')
+    return n.value, b.value
 
 
 def _p(a):
