@@ -344,6 +344,25 @@ int wfs_set_noise_offsets(wfs_handle *h, const int64_t *ix_rand, int64_t n);
 /* A noise array of floats, f64[noise_len][noise_channels] (call after wfs_set_tables; replaces its int16 table): add_noise
  * (rawdata.py:436, numba) adds noise_data[ix, ch] into the int64 row, which stores the truncated SUM. */
 int wfs_set_noise_float(wfs_handle *h, const double *noise, int32_t noise_len, int32_t noise_channels);
+/* The noise model: digitiser noise drawn per sample on the device instead of replayed from the noise array (white noise only).
+ * pmf f64[n_channels][n_values]: per channel the probability of the ADC offsets vmin .. vmin + n_values - 1.  For the row sample with
+ * absolute index t (record time t * dt) of channel ch < n_channels -- TPC, HE and sum channel are channels of their own --
+ *     w[4] = philox4x32_10(counter (low 32 bits of t >> 2, high 32 bits of t >> 2, ch, 65), key = seed)      (arithmetic shift)
+ *     noise(ch, t) = vmin + Walker draw from the channel's alias cells with the 32-bit word w[t & 3]
+ * (cell c = word >> shift; value c if (word << (32 - shift)) < thr[c], else alias[c]): the value depends on (seed, ch, t) alone,
+ * whichever kernel, window or batch holds the sample.  It is added where the noise array is (after the HE / sum factor, before
+ * baseline and clamp) and channels >= n_channels get none (rawdata.py:421).  With a model set and wfs_config.enable_noise on no
+ * noise start index is drawn (wfs_copy_groups reports 0), wfs_set_noise_offsets is accepted without effect and the noise array of
+ * wfs_set_tables, if any, is not read; with enable_noise off no noise is added.  n_channels = 0 clears the model: the noise array is
+ * back.  WFS_E_INVALID: n_channels > n_rows, n_values outside 1 .. 4096, values outside int16, a negative entry, a row whose sum
+ * differs from 1 by more than 1e-9.  Takes effect from the next wfs_run. */
+int wfs_set_noise_model(wfs_handle *h, int32_t n_channels, int32_t n_values, int32_t vmin, const double *pmf);
+/* noise(channel, t0 .. t0 + n - 1) of the model, evaluated on the device (n <= 2^30).  WFS_E_STATE without a model. */
+int wfs_noise_model_samples(wfs_handle *h, int32_t channel, int64_t t0, int64_t n, int16_t *out);
+/* The alias cells of a channel as the device holds them: thr[n_cells], alias[n_cells] (n_cells = 2^k >= max(2, n_values), the same for
+ * every channel), shift = 32 - k and vmin.  capacity_cells: entries the two buffers hold. */
+int wfs_copy_noise_model(wfs_handle *h, int32_t channel, uint32_t *thr, uint32_t *alias, int32_t capacity_cells, int32_t *n_cells,
+                         int32_t *shift, int32_t *vmin);
 int wfs_set_stream(wfs_handle *h, void *hip_stream);
 int wfs_synchronize(wfs_handle *h);
 /* Tiles of tile-generated S2s above 2048 photons whose H table fits the LDS of one workgroup are drawn and turned into their pulse by

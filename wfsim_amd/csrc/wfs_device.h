@@ -34,7 +34,10 @@ enum WfsSite : u32 {
     SITE_TILE_E = 25,    // item = P >> 2 (P: photon of the tile), word P & 3 -> surviving electron
     SITE_TILE_DELAY = 26,    // -> summed delay (alias table)
     SITE_TILE_GAIN = 27,     // -> SPE indices and double-PE flag
-    SITE_AP = 32, SITE_AP_SCREEN = 40, SITE_AP_X = 48, SITE_NOISE = 64
+    SITE_AP = 32, SITE_AP_SCREEN = 40, SITE_AP_X = 48, SITE_NOISE = 64,
+    // digitiser noise drawn per sample (wfs_set_noise_model): counter (low, high 32 bits of t >> 2, channel, site), t = absolute sample
+    // index; sample t owns word t & 3
+    SITE_NOISE_SAMPLE = 65
 };
 
 struct u32x4 { u32 x, y, z, w; };
@@ -80,6 +83,12 @@ __device__ __forceinline__ void box_muller(u32x4 w, double &z0, double &z1)
     double s, c;
     sincos(a, &s, &c);
     z0 = r * c; z1 = r * s;
+}
+
+// The Philox call of the noise model that covers samples 4 q .. 4 q + 3 of a channel (q = t >> 2, arithmetic shift)
+__device__ __forceinline__ u32x4 noise_quad(u32 k0, u32 k1, i32 channel, i64 q)
+{
+    return philox4x32_10((u32)(u64)q, (u32)((u64)q >> 32), (u32)channel, SITE_NOISE_SAMPLE, k0, k1);
 }
 
 // Integer-valued delays.  The reference draws float variates and truncates each to int64 before adding it (pulse.py:54-56
@@ -306,4 +315,8 @@ struct WfsDev {
     const i64 *thr_zle;
     const int16_t *noise;
     const double *noise_f;       // a float noise array (wfs_set_noise_float): the sum is stored truncated (rawdata.py:436 into an int64 row)
+    // the noise model (wfs_set_noise_model): alias cells [channel][nm_cells_per_ch] of the channels' ADC distributions, nullptr without a
+    // model; noise_channels then counts the model's channels and the table above is not read
+    const uint2 *nm_cells;
+    i32 nm_cells_per_ch, nm_shift, nm_vmin;
 };

@@ -103,6 +103,9 @@ struct wfs_handle {
     DevBuf stamps;
     DevBuf row_desc, rec_key, rec_key2, rec_val, rec_val2, rec_dest, sort_tmp, scan_tmp, scal, noise_override;
     bool sort_records = false; i64 n_noise_override = 0;
+    // the noise model (wfs_set_noise_model): alias cells [nm_channels][nm_k] on the device and on the host; nm_channels 0: no model
+    DevBuf nm_cells; std::vector<uint2> h_nm_cells; i32 nm_channels = 0, nm_k = 0, nm_shift = 0, nm_vmin = 0;
+    i32 table_channels = 0;           // columns of the noise table (dev.noise_channels counts the model's channels while a model is set)
     // host mirrors
     std::vector<i64> h_set_off;       // injected photons: per set photon offsets (channel sorted input order)
     wfs_counts counts{};
@@ -329,11 +332,13 @@ int read_scal(wfs_handle *h)
     return WFS_OK;
 }
 
-// The row kernels take the kind of noise table as a template parameter (no branch between their loads): 0 none, 1 int16, 2 float.
+// The row kernels take the kind of noise as a template parameter (no branch between their loads): 0 none, 1 int16 table, 2 float
+// table, 3 the noise model.
 // f is called with a std::integral_constant of the kind.
 template <class F> void with_noise_kind(int kind, F &&f)
 {
-    if (kind == 0) f(std::integral_constant<int, 0>{}); else if (kind == 1) f(std::integral_constant<int, 1>{}); else f(std::integral_constant<int, 2>{});
+    if (kind == 0) f(std::integral_constant<int, 0>{}); else if (kind == 1) f(std::integral_constant<int, 1>{}); else if (kind == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 3>{});
 }
 
 // a code that kernels raised in the device scalar block (WfsDevError) -> error code and message of the C ABI
@@ -505,7 +510,11 @@ void refresh_dev(wfs_handle *h)
     d.thr_dpe = thr(c.p_dpe); d.dpe_inv = d.thr_dpe ? 2000.0 / (double)d.thr_dpe : 0.0;
     // HE rows are only materialised when they can differ from a flat baseline: a non-zero int(factor)
     // (rawdata.py:242) or noise columns for the HE channels
-    d.enable_noise = (c.enable_noise && d.noise != nullptr) ? 1 : 0;
+    // a noise model takes precedence over the table, which stays where it is for wfs_set_noise_model(h, 0, ...)
+    const bool model = h->nm_channels > 0;
+    d.nm_cells = model ? h->nm_cells.as<uint2>() : nullptr; d.nm_cells_per_ch = h->nm_k; d.nm_shift = h->nm_shift; d.nm_vmin = h->nm_vmin;
+    d.noise_channels = model ? h->nm_channels : h->table_channels;
+    d.enable_noise = (c.enable_noise && (model || d.noise != nullptr)) ? 1 : 0;
     bool he_noise = d.enable_noise && d.noise_channels > c.he_first;
     d.he_rows = (c.detector_nt && c.n_top > 0 && (c.he_factor != 0 || he_noise)) ? 1 : 0;
     d.row_slots = c.n_tpc + (d.he_rows ? c.n_top : 0);
@@ -600,7 +609,8 @@ try {
 #define K_ROW_PULSE_0(F) k_row_pulse<0, F, true>
 #define K_ROW_PULSE_1(F) k_row_pulse<1, F, true>
 #define K_ROW_PULSE_2(F) k_row_pulse<2, F, true>
-    WFS_BIG_LDS_F(K_ROW_PULSE_0, 128); WFS_BIG_LDS_F(K_ROW_PULSE_1, 128); WFS_BIG_LDS_F(K_ROW_PULSE_2, 128);
+#define K_ROW_PULSE_3(F) k_row_pulse<3, F, true>
+    WFS_BIG_LDS_F(K_ROW_PULSE_0, 128); WFS_BIG_LDS_F(K_ROW_PULSE_1, 128); WFS_BIG_LDS_F(K_ROW_PULSE_2, 128); WFS_BIG_LDS_F(K_ROW_PULSE_3, 128);
     if (const char *e = getenv("WFS_ROW_RESIDENT")) h->res_env = atoi(e);          // 0 / 1 / 2 as the config switch (A/B runs)
     if (const char *e = getenv("WFS_RES_MAX_LEN")) h->res_max_len = std::max(256, std::min(atoi(e), 7168)) / 256 * 256;      // tuning knob (results do not depend on it)
     WFS_BIG_LDS_F(K_S2_TILE, 100); WFS_BIG_LDS_F(K_S2_TILE_AP, 100);
@@ -666,7 +676,7 @@ try {
     TRY(upload(h, h->t_noise_f, nt.data(), sizeof(double) * nt.size()));
     HIPCHK(hipStreamSynchronize(h->stream));
     WfsDev &d = h->dev;
-    d.noise_f = h->t_noise_f.as<double>(); d.noise = (const int16_t *)d.noise_f; d.noise_len = noise_len; d.noise_channels = noise_channels; d.noise_stride = (i32)stride;
+    d.noise_f = h->t_noise_f.as<double>(); d.noise = (const int16_t *)d.noise_f; d.noise_len = noise_len; h->table_channels = noise_channels; d.noise_stride = (i32)stride;
     refresh_dev(h);
     return WFS_OK;
 } WFS_CATCH(h)
@@ -711,7 +721,7 @@ try {
         d.n_lum = n_lum; h->h_lum_x.assign(lum_x, lum_x + n_lum); h->h_lum_t.assign(lum_t, lum_t + n_lum);
     }
     TRY(build_time_tables(h));         // the S2 delay table contains the luminescence term
-    d.noise = nullptr; d.noise_f = nullptr; d.noise_len = 0; d.noise_channels = 0; d.noise_stride = 0;
+    d.noise = nullptr; d.noise_f = nullptr; d.noise_len = 0; h->table_channels = 0; d.noise_stride = 0;
     if (noise && noise_len > 0 && noise_channels > 0) {
         // channel-major on the device ([channel][sample]; the reference's array is [sample][channel], rawdata.py:429): a row reads
         // consecutive samples of ONE channel -- time-major that is one cache line per sample
@@ -721,7 +731,7 @@ try {
         for (int64_t i = 0; i < (int64_t)stride; i++) for (int c = 0; c < noise_channels; c++) nt[(size_t)c * stride + i] = noise[(size_t)(i % noise_len) * noise_channels + c];
         TRY(upload(h, h->t_noise, nt.data(), sizeof(int16_t) * nt.size()));
         HIPCHK(hipStreamSynchronize(h->stream));
-        d.noise = h->t_noise.as<int16_t>(); d.noise_len = noise_len; d.noise_channels = noise_channels; d.noise_stride = (i32)stride;
+        d.noise = h->t_noise.as<int16_t>(); d.noise_len = noise_len; h->table_channels = noise_channels; d.noise_stride = (i32)stride;
     }
     d.templates = h->t_templates.as<double>(); d.spe = h->t_spe.as<double>(); d.n_spe = n_spe; d.gains = h->t_gains.as<double>();
     d.thr_truth = h->t_thr_truth.as<double>(); d.thr_zle = h->t_thr_zle.as<i64>(); d.lum_x = h->t_lumx.as<double>(); d.lum_t = h->t_lumt.as<double>();
@@ -1873,7 +1883,7 @@ static int run_geometry(wfs_handle *h, RunState &r)
     const bool res_auto = T > 0 && p_all >= 2 * T;
     const int res_mode = h->res_env >= 0 ? h->res_env : h->cfg.row_resident;
     h->res_on = (res_mode == 2 ? res_auto : res_mode != 0) && !(h->keep_currents & (DBG_CURRENTS | DBG_FORCE_DENSE)) && !h->generic_geom && !d.he_rows && 2 * (i64)d.tw + 1 >= 63
-                && (!d.enable_noise || d.noise_len >= NOISE_MIN_FAST);
+                && (!d.enable_noise || d.nm_cells || d.noise_len >= NOISE_MIN_FAST);
     if (tiles_done || h->res_on) {
         TRY(ensure(h, h->row_cnt, (size_t)CG * d.n_tpc * 4)); TRY(ensure(h, h->row_tile, (size_t)CG * d.n_tpc * 4));
         TRY(fg.zero(h->row_cnt.p, (size_t)CG * d.n_tpc * 4));
@@ -2142,7 +2152,7 @@ static int run_rows(wfs_handle *h, RunState &r)
     }
     TRY(fg.flush());
     if (h->n_active_rows > 0) { Timer t(h, "k_row_desc"); hipLaunchKernelGGL(k_row_desc, dim3(nblocks(h->n_active_rows, 256)), dim3(256), 0, h->stream, d, za); }
-    r.noise_kind = !d.enable_noise ? 0 : (d.noise_f ? 2 : 1);
+    r.noise_kind = !d.enable_noise ? 0 : (d.nm_cells ? 3 : (d.noise_f ? 2 : 1));
     if (h->n_res_rows > 0) {        // resident rows: pulses, finished samples and intervals by one wave per row
         PulseArgs pr = pa;
         pr.desc = h->res_desc.as<TileDesc>(); pr.currents = nullptr; pr.cur_off = nullptr;
@@ -2697,6 +2707,78 @@ try {
         doff += len; k++;
     }
     if (k < cap_rows) data_off[k] = doff;
+    return WFS_OK;
+} WFS_CATCH(h)
+
+// The noise model: one Walker table per channel from its probability mass function, all of one size (build_alias, the construction of
+// the delay tables), sampled by the row kernels from the Philox word of the sample (wfs_device.h SITE_NOISE_SAMPLE).
+int wfs_set_noise_model(wfs_handle *h, int32_t n_channels, int32_t n_values, int32_t vmin, const double *pmf)
+try {
+    if (!h) return WFS_E_INVALID;
+    HIPCHK(hipSetDevice(h->device));
+    if (n_channels == 0) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        h->nm_channels = 0; h->h_nm_cells.clear(); h->nm_cells.reset();
+        h->ran = false;
+        refresh_dev(h);
+        return WFS_OK;
+    }
+    if (n_channels < 0 || n_channels > h->cfg.n_rows) return h->fail(WFS_E_INVALID, "wfs_set_noise_model: n_channels outside 0 .. n_rows of the digitiser array");
+    if (n_values < 1 || n_values > 4096) return h->fail(WFS_E_INVALID, "wfs_set_noise_model: n_values outside 1 .. 4096");
+    if (vmin < -32768 || (i64)vmin + n_values - 1 > 32767) return h->fail(WFS_E_INVALID, "wfs_set_noise_model: vmin .. vmin + n_values - 1 leaves the int16 range");
+    if (!pmf) return h->fail(WFS_E_INVALID, "wfs_set_noise_model: null pmf");
+    std::vector<uint2> cells, cell; std::vector<double> cum((size_t)n_values); int shift = 31;
+    for (i32 c = 0; c < n_channels; c++) {
+        const double *row = pmf + (size_t)c * n_values;
+        double acc = 0;
+        for (i32 v = 0; v < n_values; v++) {
+            if (!(row[v] >= 0.0)) return h->fail(WFS_E_INVALID, "wfs_set_noise_model: pmf has a negative (or NaN) entry in channel " + std::to_string(c));
+            acc += row[v]; cum[(size_t)v] = acc;
+        }
+        if (!(fabs(acc - 1.0) <= 1e-9)) return h->fail(WFS_E_INVALID, "wfs_set_noise_model: pmf of channel " + std::to_string(c) + " does not sum to 1");
+        build_alias(cum, cell, shift);
+        cells.insert(cells.end(), cell.begin(), cell.end());
+    }
+    const i32 K = (i32)(cells.size() / (size_t)n_channels);
+    TRY(upload(h, h->nm_cells, cells.data(), cells.size() * sizeof(uint2)));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->h_nm_cells.swap(cells); h->nm_channels = n_channels; h->nm_k = K; h->nm_shift = shift; h->nm_vmin = vmin;
+    h->ran = false;             // (HE rows may appear or go with the model's channel count: run again before copying)
+    refresh_dev(h);
+    return WFS_OK;
+} WFS_CATCH(h)
+
+int wfs_noise_model_samples(wfs_handle *h, int32_t channel, int64_t t0, int64_t n, int16_t *out)
+try {
+    if (!h) return WFS_E_INVALID;
+    if (h->nm_channels <= 0) return h->fail(WFS_E_STATE, "wfs_noise_model_samples: no noise model is set");
+    if (channel < 0 || channel >= h->nm_channels) return h->fail(WFS_E_INVALID, "wfs_noise_model_samples: channel outside the model");
+    if (n < 0 || n > ((i64)1 << 30) || (n > 0 && !out)) return h->fail(WFS_E_INVALID, "wfs_noise_model_samples: n outside 0 .. 2^30 or null buffer");
+    if (t0 > I64_MAX - n) return h->fail(WFS_E_INVALID, "wfs_noise_model_samples: t0 + n overflows");
+    if (n == 0) return WFS_OK;
+    HIPCHK(hipSetDevice(h->device));
+    DevBuf buf;
+    TRY(ensure(h, buf, (size_t)n * sizeof(int16_t)));
+    { Timer t(h, "k_noise_model_samples"); hipLaunchKernelGGL(k_noise_model_samples, dim3(nblocks((n + 3) / 4, 256)), dim3(256), 0, h->stream, h->dev, channel, t0, n, buf.as<int16_t>()); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, buf.p, (size_t)n * sizeof(int16_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    CHECK_LAUNCHES();
+    return WFS_OK;
+} WFS_CATCH(h)
+
+int wfs_copy_noise_model(wfs_handle *h, int32_t channel, uint32_t *thr, uint32_t *alias, int32_t capacity_cells, int32_t *n_cells, int32_t *shift, int32_t *vmin)
+try {
+    if (!h) return WFS_E_INVALID;
+    if (h->nm_channels <= 0) return h->fail(WFS_E_STATE, "wfs_copy_noise_model: no noise model is set");
+    if (channel < 0 || channel >= h->nm_channels) return h->fail(WFS_E_INVALID, "wfs_copy_noise_model: channel outside the model");
+    if (!thr || !alias || !n_cells || !shift || !vmin) return h->fail(WFS_E_INVALID, "wfs_copy_noise_model: null argument");
+    if (capacity_cells < h->nm_k) return h->fail(WFS_E_CAPACITY, "wfs_copy_noise_model: cell buffers too small");
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<uint2> cell((size_t)h->nm_k);            // what the device samples from, not the host copy
+    HIPCHK(hipMemcpy(cell.data(), h->nm_cells.as<uint2>() + (size_t)channel * h->nm_k, cell.size() * sizeof(uint2), hipMemcpyDeviceToHost));
+    for (i32 k = 0; k < h->nm_k; k++) { thr[k] = cell[(size_t)k].x; alias[k] = cell[(size_t)k].y; }
+    *n_cells = h->nm_k; *shift = h->nm_shift; *vmin = h->nm_vmin;
     return WFS_OK;
 } WFS_CATCH(h)
 

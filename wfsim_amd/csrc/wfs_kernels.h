@@ -376,7 +376,8 @@ __global__ void k_group_final(WfsDev d, GeomArgs a)
     if (floormod(left, 2) != 0) left -= 1;
     a.grp_left[g] = left; a.grp_right[g] = right;
     i64 ix = -1;
-    if (d.enable_noise) {
+    if (d.enable_noise && d.nm_cells) ix = 0;                  // the noise model (wfs_set_noise_model) has no start index: nothing is drawn
+    else if (d.enable_noise) {
         i64 nl = a.grp_lo[g] - left - d.tw, nr = a.grp_hi[g] - left + d.tw;
         i64 N = d.noise_len, high = (N - nr + nl - 1 < 0) ? N - 1 : N - nr + nl - 1;
         if (high <= 0) ix = 0;
@@ -1619,10 +1620,45 @@ __global__ void k_row_desc(WfsDev d, ZleArgs a)
 
 // finished sample of a row: accumulated ADC + noise + baseline, clamped at 0
 // (rawdata.py:398-458 add_noise / add_baseline / digitizer_saturation, fused into the read)
-__device__ __forceinline__ i32 finish_sample(const WfsDev &d, const i32 *acc, i64 i, i32 slot_ch, bool he, i64 ix_rand)
+// The noise model (wfs_set_noise_model): noise(ch, t) = vmin + alias_sample(cells[ch], word t & 3 of the Philox call of
+// (t >> 2, ch)), t the absolute sample index -- integer arithmetic from the random word to the ADC value.  cells: those of the channel.
+__device__ __forceinline__ i32 noise_model_sample(const WfsDev &d, const uint2 *cells, i32 channel, i64 t)
+{
+    const AliasTab tab{cells, d.nm_vmin, d.nm_shift};
+    const u32x4 a = noise_quad(d.k0, d.k1, channel, t >> 2);
+    const u32 m = (u32)t & 3u;
+    return alias_sample(tab, m == 0 ? a.x : (m == 1 ? a.y : (m == 2 ? a.z : a.w)));
+}
+// Samples t0 + i .. t0 + i + 3 of a lane whose i is a multiple of four and whose t0 is wave-uniform: the four words lie in the lane's
+// aligned call and, unless t0 is aligned itself, the one behind it -- which of them is the same for the whole wave (t0 & 3), so the
+// second call sits behind a scalar branch and the words are picked without a select.  One call per four samples for aligned rows, two
+// otherwise.
+__device__ __forceinline__ void noise_model_four(const WfsDev &d, const uint2 *cells, i32 channel, i64 t0, i32 i, i32 *out)
+{
+    const AliasTab tab{cells, d.nm_vmin, d.nm_shift};
+    const i64 q = (t0 + i) >> 2;
+    const u32 m = (u32)t0 & 3u;
+    const u32x4 a = noise_quad(d.k0, d.k1, channel, q);
+    u32 w[4] = {a.x, a.y, a.z, a.w};
+    if (m != 0) {
+        const u32x4 b = noise_quad(d.k0, d.k1, channel, q + 1);
+        if (m == 1) { w[0] = a.y; w[1] = a.z; w[2] = a.w; w[3] = b.x; }
+        else if (m == 2) { w[0] = a.z; w[1] = a.w; w[2] = b.x; w[3] = b.y; }
+        else { w[0] = a.w; w[1] = b.x; w[2] = b.y; w[3] = b.z; }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) out[j] = alias_sample(tab, w[j]);
+}
+
+// (NK: the noise kind of the row kernels below; row_abs, the row's first absolute sample, is what kind 3 counts from)
+template <int NK>
+__device__ __forceinline__ i32 finish_sample(const WfsDev &d, const i32 *acc, i64 i, i32 slot_ch, bool he, i64 ix_rand, i64 row_abs)
 {
     i64 v = acc[i];
     if (he) v *= d.he_factor;                                   // rawdata.py:242-246
+    if constexpr (NK == 3) {
+        if (slot_ch < d.noise_channels) v += noise_model_sample(d, d.nm_cells + (i64)slot_ch * d.nm_cells_per_ch, slot_ch, row_abs + i);
+    } else
     if (d.enable_noise && slot_ch < d.noise_channels) {
         const u32 in = ((u32)ix_rand + (u32)i) % (u32)d.noise_len;      // rawdata.py:433-434 (ix_rand < noise_len <= 2^31, i < 2^20: 32 bits hold the sum)
         // channel-major copy (wfs_set_tables): consecutive samples, consecutive addresses
@@ -1631,6 +1667,23 @@ __device__ __forceinline__ i32 finish_sample(const WfsDev &d, const i32 *acc, i6
     }
     v += d.baseline;
     return v < 0 ? 0 : (i32)v;
+}
+
+// wfs_noise_model_samples: noise(channel, t0 .. t0 + n - 1) through the two forms the row kernels use -- a thread takes four
+// consecutive samples as a lane of the fast paths does (t0 is wave-uniform, 4 k a multiple of four), the last n & 3 one by one
+__global__ __launch_bounds__(256) void k_noise_model_samples(WfsDev d, i32 channel, i64 t0, i64 n, int16_t *out)
+{
+    const i64 k = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (4 * k >= n) return;
+    const uint2 *cells = d.nm_cells + (i64)channel * d.nm_cells_per_ch;
+    if (4 * k + 3 < n) {
+        i32 v[4];
+        noise_model_four(d, cells, channel, t0, (i32)(4 * k), v);
+#pragma unroll
+        for (int j = 0; j < 4; j++) out[4 * k + j] = (int16_t)v[j];
+    } else {
+        for (i64 s = 4 * k; s < n; s++) out[s] = (int16_t)noise_model_sample(d, cells, channel, t0 + s);
+    }
 }
 
 // (acc_ch -1: the window's sum row, which has no accumulator row of a channel behind it)
@@ -1644,20 +1697,23 @@ __device__ __forceinline__ void row_of_slot(const WfsDev &d, i64 idx, i64 &g, i3
 // The same in two steps, for loops that want ALL their loads in flight before the first use: with the load inside finish_sample
 // the compiler waits for every load right behind it (a branch follows), and a wave spends one memory round trip per load.
 // A row no longer than the noise array wraps at most once (ix_rand < noise_len, i < len <= noise_len): no loop on the load path.
-// NK, the noise table of the batch, is a template parameter (0: none, 1: int16, 2: float64) and a row outside the table
+// NK, the noise of the batch, is a template parameter (0: none, 1: int16 table, 2: float64 table, 3: the noise model, drawn where the
+// tables are loaded: noise_row then points at the channel's alias cells, nullptr for a row outside the model) and a row outside the table
 // (noisy false, wave-uniform) reads row 0 and drops the value: NO branch sits between two loads -- with a branch around the
 // noise load the compiler drained the memory counter after every one of them.
 template <int NK> struct RawSample;
 template <> struct RawSample<0> { i32 acc; };
 template <> struct RawSample<1> { i32 acc; i32 nz; };
 template <> struct RawSample<2> { i32 acc; double nzf; };
+template <> struct RawSample<3> { i32 acc; i32 nz; };
 template <int NK>
-__device__ __forceinline__ RawSample<NK> load_sample(const WfsDev &d, const i32 *acc, i32 i, const void *noise_row, u32 nstart, u32 noff)
+__device__ __forceinline__ RawSample<NK> load_sample(const WfsDev &d, const i32 *acc, i32 i, const void *noise_row, u32 nstart, u32 noff, i32 channel = 0, i64 row_abs = 0)
 {
     // (32-bit offsets from wave-uniform row pointers: the address arithmetic is one add per load, the bases stay in SGPRs)
     // noise sample nstart + noff of the row, nstart < noise_len a scalar, noff < noise_len: one conditional subtraction wraps it
     RawSample<NK> s; s.acc = acc[(u32)i];
-    if constexpr (NK != 0) {
+    if constexpr (NK == 3) s.nz = noise_row ? noise_model_sample(d, (const uint2 *)noise_row, channel, row_abs + i) : 0;      // (wave-uniform)
+    else if constexpr (NK != 0) {
         u32 in = nstart + noff;
         in = in >= (u32)d.noise_len ? in - (u32)d.noise_len : in;
         if constexpr (NK == 2) s.nzf = ((const double *)noise_row)[in]; else s.nz = ((const int16_t *)noise_row)[in];
@@ -1671,6 +1727,7 @@ __device__ __forceinline__ i32 finish_loaded(const WfsDev &d, const RawSample<NK
     if (he) v *= d.he_factor;
     if constexpr (NK == 1) v += noisy ? s.nz : 0;
     if constexpr (NK == 2) { const i64 w = (i64)((double)v + s.nzf); v = noisy ? w : v; }
+    if constexpr (NK == 3) v += s.nz;
     v += d.baseline;
     return v < 0 ? 0 : (i32)v;
 }
@@ -1681,11 +1738,15 @@ template <int NK> struct Raw4;
 template <> struct Raw4<0> { i32 acc[4]; };
 template <> struct Raw4<1> { i32 acc[4]; int16_t nz[4]; };
 template <> struct Raw4<2> { i32 acc[4]; double nzf[4]; };
+template <> struct Raw4<3> { i32 acc[4]; i32 nz[4]; };
 template <int NK>
-__device__ __forceinline__ Raw4<NK> load_four(const WfsDev &d, const i32 *acc, i32 i, const void *noise_row, u32 nstart, u32 noff)
+__device__ __forceinline__ Raw4<NK> load_four(const WfsDev &d, const i32 *acc, i32 i, const void *noise_row, u32 nstart, u32 noff, i32 channel = 0, i64 row_abs = 0)
 {
     Raw4<NK> s; __builtin_memcpy(s.acc, acc + (u32)i, 16);
-    if constexpr (NK != 0) {
+    if constexpr (NK == 3) {
+        if (noise_row) noise_model_four(d, (const uint2 *)noise_row, channel, row_abs, i, s.nz);      // (wave-uniform; i is a multiple of four)
+        else s.nz[0] = s.nz[1] = s.nz[2] = s.nz[3] = 0;
+    } else if constexpr (NK != 0) {
         u32 in = nstart + noff;
         in = in >= (u32)d.noise_len ? in - (u32)d.noise_len : in;
         if constexpr (NK == 2) __builtin_memcpy(s.nzf, (const double *)noise_row + in, 32); else __builtin_memcpy(s.nz, (const int16_t *)noise_row + in, 8);
@@ -1699,6 +1760,7 @@ __device__ __forceinline__ i32 finish_four(const WfsDev &d, const Raw4<NK> &s, i
     if (he) v *= d.he_factor;
     if constexpr (NK == 1) v += noisy ? (i32)s.nz[j] : 0;
     if constexpr (NK == 2) { const i64 w = (i64)((double)v + s.nzf[j]); v = noisy ? w : v; }
+    if constexpr (NK == 3) v += s.nz[j];
     v += d.baseline;
     return v < 0 ? 0 : (i32)v;
 }
@@ -1786,9 +1848,12 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
     // the noise index of a row's sample i is (ix + i) mod noise_len (rawdata.py:433-434): a scalar start per block of samples that
     // steps with the block and wraps, plus the lane's offset inside the block -- rows may be any number of noise lengths long.
     // (A table shorter than NOISE_MIN_FAST samples would wrap more than once inside a block: the general path below.)
-    const bool fast_loads = len32 >= 1 && (NK == 0 || d.noise_len >= NOISE_MIN_FAST);
+    // (The noise model, kind 3, has no table and no wrap: the fast paths wherever kind 0 takes them.)
+    constexpr bool TABLE = NK == 1 || NK == 2;
+    const bool fast_loads = len32 >= 1 && (!TABLE || d.noise_len >= NOISE_MIN_FAST);
     const i64 noise_off = noisy ? (i64)channel * d.noise_stride : 0; const u32 nixr = noisy ? (u32)ixr : 0u;
-    const void *noise_row = NK == 2 ? (const void *)(d.noise_f + noise_off) : (const void *)(d.noise + noise_off);
+    const void *noise_row = NK == 3 ? (const void *)(noisy ? d.nm_cells + (i64)channel * d.nm_cells_per_ch : nullptr)
+                                    : (NK == 2 ? (const void *)(d.noise_f + noise_off) : (const void *)(d.noise + noise_off));
     if (hold32 >= 63 && fast_loads && !a.row_dbg) {
         // The usual geometry (hold-off of at least a chunk): the interval bookkeeping is scalar work on the ballot mask (ZleFast), and
         // the vector unit is left with load, finish and compare.
@@ -1806,8 +1871,8 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
 #pragma unroll
             for (int u = 0; u < G; u++) {
                 const i32 i = g0 + 256 * u + 4 * lane;
-                buf[u] = load_four<NK>(d, acc, i < len32 ? i : 0, noise_row, nrun, 4u * (u32)lane);
-                if constexpr (NK != 0) { nrun += 256u; nrun = nrun >= (u32)d.noise_len ? nrun - (u32)d.noise_len : nrun; }
+                buf[u] = load_four<NK>(d, acc, i < len32 ? i : 0, noise_row, nrun, 4u * (u32)lane, channel, row_abs);
+                if constexpr (TABLE) { nrun += 256u; nrun = nrun >= (u32)d.noise_len ? nrun - (u32)d.noise_len : nrun; }
             }
         };
         auto look = [&](const Raw4<NK> *buf, i32 g0) {
@@ -1837,14 +1902,14 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
 #pragma unroll
             for (int u = 0; u < ZLE_GROUP; u++) {
                 const i32 i = g0 + 64 * u + lane;
-                rs[u] = load_sample<NK>(d, acc, i < len32 ? i : len32 - 1, noise_row, nrun1, (u32)lane);
-                if constexpr (NK != 0) { nrun1 += 64u; nrun1 = nrun1 >= (u32)d.noise_len ? nrun1 - (u32)d.noise_len : nrun1; }
+                rs[u] = load_sample<NK>(d, acc, i < len32 ? i : len32 - 1, noise_row, nrun1, (u32)lane, channel, row_abs);
+                if constexpr (TABLE) { nrun1 += 64u; nrun1 = nrun1 >= (u32)d.noise_len ? nrun1 - (u32)d.noise_len : nrun1; }
             }
 #pragma unroll
             for (int u = 0; u < ZLE_GROUP; u++) { const i32 i = g0 + 64 * u + lane; vv[u] = i < len32 ? finish_loaded(d, rs[u], he, noisy) : 0x7fffffff; }
         } else {
 #pragma unroll
-            for (int u = 0; u < ZLE_GROUP; u++) { const i32 i = g0 + 64 * u + lane; vv[u] = i < len32 ? finish_sample(d, acc, i, channel, he, ixr) : 0x7fffffff; }
+            for (int u = 0; u < ZLE_GROUP; u++) { const i32 i = g0 + 64 * u + lane; vv[u] = i < len32 ? finish_sample<NK>(d, acc, i, channel, he, ixr, row_abs) : 0x7fffffff; }
         }
         if (a.row_dbg) {
 #pragma unroll
@@ -1983,12 +2048,17 @@ __global__ __launch_bounds__(256) void k_row_pulse(WfsDev d, PulseArgs a, ZleArg
     const i32 hold32 = (i32)hold;
     const bool noisy = NK != 0 && q.channel < d.noise_channels;
     const i64 noise_off = noisy ? (i64)q.channel * d.noise_stride : 0;
-    const void *noise_row = NK == 2 ? (const void *)(d.noise_f + noise_off) : (const void *)(d.noise + noise_off);
-    u32 nrun = noisy ? (u32)q.ixr : 0u;                    // noise index of the next block's first sample (rawdata.py:433-434)
+    const void *noise_row = NK == 3 ? (const void *)(noisy ? d.nm_cells + (i64)q.channel * d.nm_cells_per_ch : nullptr)
+                                    : (NK == 2 ? (const void *)(d.noise_f + noise_off) : (const void *)(d.noise + noise_off));
+    u32 nrun = (noisy && NK != 3) ? (u32)q.ixr : 0u;       // noise index of the next block's first sample (rawdata.py:433-434); kind 3: that sample's index in the row
     int16_t *fin = z.fin + q.acc_off;
     const i32 fin_len = (len32 + 3) & ~3;
     auto load_noise = [&](Raw4<NK> &o) {
-        if constexpr (NK != 0) {
+        if constexpr (NK == 3) {                          // drawn, not loaded: the block's first absolute sample is wave-uniform
+            if (noise_row) noise_model_four(d, (const uint2 *)noise_row, q.channel, row_abs + (i64)nrun, 4 * lane, o.nz);
+            else o.nz[0] = o.nz[1] = o.nz[2] = o.nz[3] = 0;
+            nrun += 256u;
+        } else if constexpr (NK != 0) {
             u32 in = nrun + 4u * (u32)lane;
             in = in >= (u32)d.noise_len ? in - (u32)d.noise_len : in;
             if constexpr (NK == 2) __builtin_memcpy(o.nzf, (const double *)noise_row + in, 32); else __builtin_memcpy(o.nz, (const int16_t *)noise_row + in, 8);
@@ -2042,6 +2112,7 @@ __global__ __launch_bounds__(256) void k_row_pulse(WfsDev d, PulseArgs a, ZleArg
                 for (int j = 0; j < 4; j++) {
                     i32 add = d.baseline;
                     if constexpr (NK == 1) add += noisy ? (i32)s4.nz[j] : 0;
+                    if constexpr (NK == 3) add += s4.nz[j];
                     i32 v = __builtin_elementwise_add_sat(s4.acc[j], add);
                     v = v < 0 ? 0 : v;
                     nib |= (j < live && v < thr32) ? (1u << j) : 0u; v16[j] = (u32)v;
@@ -2173,9 +2244,11 @@ __global__ __launch_bounds__(256) void k_pack(WfsDev d, ZleArgs a)
     constexpr int spr = WFS_SPR; constexpr int rec_dwords = (24 + 2 * spr) / 4;
     const i64 rec_bytes = 24 + 2 * (i64)spr;
     const bool noisy = NK != 0 && channel < d.noise_channels;
-    const bool fast_loads = NK == 0 || (d.noise_len >= NOISE_MIN_FAST && spr <= NOISE_MIN_FAST / 2);       // (as in k_zle: a scalar noise start per record)
+    constexpr bool TABLE = NK == 1 || NK == 2;
+    const bool fast_loads = !TABLE || (d.noise_len >= NOISE_MIN_FAST && spr <= NOISE_MIN_FAST / 2);       // (as in k_zle: a scalar noise start per record)
     const i64 noise_off = noisy ? (i64)channel * d.noise_stride : 0; const u32 nixr = noisy ? (u32)ixr : 0u;
-    const void *noise_row = NK == 2 ? (const void *)(d.noise_f + noise_off) : (const void *)(d.noise + noise_off);
+    const void *noise_row = NK == 3 ? (const void *)(noisy ? d.nm_cells + (i64)channel * d.nm_cells_per_ch : nullptr)
+                                    : (NK == 2 ? (const void *)(d.noise_f + noise_off) : (const void *)(d.noise + noise_off));
     const u32 w3 = ((u32)(uint16_t)d.dt) | ((u32)(uint16_t)channel << 16);
     constexpr int PACK_U = 4;
     i64 rec = q.rec;
@@ -2188,7 +2261,7 @@ __global__ __launch_bounds__(256) void k_pack(WfsDev d, ZleArgs a)
             const int qd = q0 + lane;
             const int s0 = (qd - 6) * 2;                            // first of the lane's two samples (lanes of the header: negative)
             u32 nrun = 0;                                           // noise index of the next record's first sample (a scalar)
-            if constexpr (NK != 0) { if (fast_loads) nrun = (nixr + (u32)off) % (u32)d.noise_len; }
+            if constexpr (TABLE) { if (fast_loads) nrun = (nixr + (u32)off) % (u32)d.noise_len; }
             const u32 noff = (u32)(s0 < 0 ? 0 : s0);
             for (i32 f0 = 0; f0 < need; f0 += PACK_U) {
                 RawSample<NK> lo[PACK_U], hi[PACK_U];
@@ -2200,8 +2273,8 @@ __global__ __launch_bounds__(256) void k_pack(WfsDev d, ZleArgs a)
                         i32 i0 = off + spr * f + (i32)noff;
                         i0 = i0 > len32 - 1 ? len32 - 1 : i0;       // (lanes past the record's samples read a valid sample and drop it)
                         const i32 i1 = i0 + 1 > len32 - 1 ? len32 - 1 : i0 + 1;
-                        lo[u] = load_sample<NK>(d, acc, i0, noise_row, nrun, noff); hi[u] = load_sample<NK>(d, acc, i1, noise_row, nrun, noff + 1u);
-                        if constexpr (NK != 0) { nrun += (u32)spr; nrun = nrun >= (u32)d.noise_len ? nrun - (u32)d.noise_len : nrun; }
+                        lo[u] = load_sample<NK>(d, acc, i0, noise_row, nrun, noff, channel, row_abs); hi[u] = load_sample<NK>(d, acc, i1, noise_row, nrun, noff + 1u, channel, row_abs);
+                        if constexpr (TABLE) { nrun += (u32)spr; nrun = nrun >= (u32)d.noise_len ? nrun - (u32)d.noise_len : nrun; }
                     }
                 }
 #pragma unroll
@@ -2218,8 +2291,8 @@ __global__ __launch_bounds__(256) void k_pack(WfsDev d, ZleArgs a)
                         if (fast_loads) { vlo = (u32)(uint16_t)finish_loaded(d, lo[u], he, noisy); vhi = (u32)(uint16_t)finish_loaded(d, hi[u], he, noisy); }
                         else {
                             const i64 i0 = (i64)off + spr * f + s0;
-                            vlo = s0 < length ? (u32)(uint16_t)finish_sample(d, acc, i0, channel, he, ixr) : 0u;
-                            vhi = s0 + 1 < length ? (u32)(uint16_t)finish_sample(d, acc, i0 + 1, channel, he, ixr) : 0u;
+                            vlo = s0 < length ? (u32)(uint16_t)finish_sample<NK>(d, acc, i0, channel, he, ixr, row_abs) : 0u;
+                            vhi = s0 + 1 < length ? (u32)(uint16_t)finish_sample<NK>(d, acc, i0 + 1, channel, he, ixr, row_abs) : 0u;
                         }
                         w = (s0 < length ? vlo : 0u) | ((s0 + 1 < length ? vhi : 0u) << 16);
                     }

@@ -110,7 +110,8 @@ EXPORTS = ['wfs_create', 'wfs_destroy', 'wfs_last_error', 'wfs_device_count', 'w
            'wfs_set_gas_gap_model', 'wfs_set_instruction_gas_gap', 'wfs_set_pattern_map_points', 'wfs_set_instruction_aft',
            'wfs_scalar_map_grid', 'wfs_scalar_map_points', 'wfs_scalar_map_spline', 'wfs_scalar_map_eval', 'wfs_set_noise_float', 'wfs_set_instruction_diffusion',
            'wfs_scalar_map_grid_array', 'wfs_scalar_map_points_array', 'wfs_scalar_map_linear', 'wfs_scalar_map_eval_array',
-           'wfs_set_sum_signal', 'wfs_copy_sum_signal', 'wfs_device_allocations']
+           'wfs_set_sum_signal', 'wfs_copy_sum_signal', 'wfs_device_allocations',
+           'wfs_set_noise_model', 'wfs_noise_model_samples', 'wfs_copy_noise_model']
 
 
 def load_library():
@@ -199,11 +200,14 @@ class Engine:
             raise WfsError(f'wfs_create failed with code {rc}: no usable MI355X / HIP runtime (device {device})')
         thr_truth, thr_zle = T.thresholds(config, N_ROWS)
         lum_x, lum_t = T.luminescence_table(config)
+        # a noise model (noise_model.py) takes precedence over the noise array of the resource, which is then not uploaded
+        from .noise_model import noise_pmf
+        self.noise_model = noise_pmf(config, params['n_rows']) if params['enable_noise'] else None
         self.tables = dict(
             templates=T.pmt_current_templates(config), spe=T.spe_scaling_table(resource.spe_charge, resource.spe_pdfs),
             gains=_arr(config['gains'], np.float64), thr_truth=_arr(thr_truth, np.float64), thr_zle=_arr(thr_zle, np.int64),
             lum_x=_arr(lum_x, np.float64), lum_t=_arr(lum_t, np.float64),
-            noise=_arr(resource.noise_data, np.int16) if (params['enable_noise'] and hasattr(resource, 'noise_data')) else None)
+            noise=_arr(resource.noise_data, np.int16) if (params['enable_noise'] and self.noise_model is None and hasattr(resource, 'noise_data')) else None)
         t = self.tables
         assert t['templates'].shape == (params['dt'], params['tlen'])
         nl, nc = t['noise'].shape if t['noise'] is not None else (0, 0)
@@ -233,6 +237,9 @@ class Engine:
             nf = _arr(resource.noise_data, np.float64)
             self._check(self.lib.wfs_set_noise_float(self._h, _p(nf), C.c_int32(nl), C.c_int32(nc)))
         # int(high_energy_deamplification_factor) (rawdata.py:242) or noise columns for the HE channels
+        if self.noise_model is not None:
+            self.set_noise_model(*self.noise_model)
+            nc = self.noise_model[0].shape[0]
         he_noise = bool(params['enable_noise']) and nc > params['he_first']
         self.emits_he_records = bool(params['detector_nt'] and params['n_top'] > 0 and (params['he_factor'] != 0 or he_noise))
         # pattern maps on regular grids are evaluated on the device (one channel CDF row per instruction)
@@ -649,6 +656,32 @@ class Engine:
     def set_noise_offsets(self, ix_rand):
         a = _arr(ix_rand, np.int64)
         self._check(self.lib.wfs_set_noise_offsets(self._h, _p(a), C.c_int64(len(a))))
+
+    def set_noise_model(self, pmf, vmin=0):
+        """pmf[n_channels][n_values] over the ADC offsets vmin .. vmin + n_values - 1 (noise_model.py); None clears the model: the noise
+        array, if any, is replayed again.  Acts with enable_noise, from the next run."""
+        if pmf is None:
+            self._check(self.lib.wfs_set_noise_model(self._h, C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_void_p(0)))
+            return
+        pmf = _arr(pmf, np.float64)
+        if pmf.ndim != 2:
+            raise ValueError('set_noise_model: pmf must be [n_channels][n_values]')
+        self._check(self.lib.wfs_set_noise_model(self._h, C.c_int32(pmf.shape[0]), C.c_int32(pmf.shape[1]), C.c_int32(int(vmin)), _p(pmf)))
+
+    def noise_samples(self, channel, t0, n):
+        """noise(channel, t0 .. t0 + n - 1) of the noise model, evaluated on the device: t is the absolute sample index (time / dt)"""
+        out = np.zeros(int(n), dtype=np.int16)
+        self._check(self.lib.wfs_noise_model_samples(self._h, C.c_int32(int(channel)), C.c_int64(int(t0)), C.c_int64(int(n)), _p(out)))
+        return out
+
+    def noise_model_cells(self, channel):
+        """the Walker alias cells the device samples a channel's noise from: dict(thr, alias, shift, vmin); cell c = word >> shift gives
+        vmin + c if (word << (32 - shift)) mod 2^32 < thr[c], else vmin + alias[c]"""
+        cap = 4096
+        thr, alias = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
+        n, shift, vmin = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._check(self.lib.wfs_copy_noise_model(self._h, C.c_int32(int(channel)), _p(thr), _p(alias), C.c_int32(cap), C.byref(n), C.byref(shift), C.byref(vmin)))
+        return dict(thr=thr[:n.value].copy(), alias=alias[:n.value].copy(), shift=shift.value, vmin=vmin.value)
 
     def set_window_carry(self, has_pulse, last_pulse_end_time):
         self._check(self.lib.wfs_set_window_carry(self._h, C.c_int32(int(has_pulse)), C.c_int64(int(last_pulse_end_time))))

@@ -199,7 +199,8 @@ class Resource:
                 self.spe_pdfs = np.asarray(pad['pdfs'], dtype=np.float64)
             else:
                 self.spe_pdfs = np.asarray(pad['pdf'], dtype=np.float64)[None, :]   # one shared distribution
-        if c.get('enable_noise', False):
+        # (with a 'noise_model' the noise is drawn on the device, noise_model.py: no array is needed, one that is given is kept but not used)
+        if c.get('enable_noise', False) and (c.get('noise_model') is None or 'noise_data' in c):
             self.noise_data = np.ascontiguousarray(c['noise_data'])
         if c.get('enable_pmt_afterpulses', False):
             self.uniform_to_pmt_ap = c['uniform_to_pmt_ap']
