@@ -357,8 +357,23 @@ int wfs_set_noise_float(wfs_handle *h, const double *noise, int32_t noise_len, i
  * back.  WFS_E_INVALID: n_channels > n_rows, n_values outside 1 .. 4096, values outside int16, a negative entry, a row whose sum
  * differs from 1 by more than 1e-9.  Takes effect from the next wfs_run. */
 int wfs_set_noise_model(wfs_handle *h, int32_t n_channels, int32_t n_values, int32_t vmin, const double *pmf);
-/* noise(channel, t0 .. t0 + n - 1) of the model, evaluated on the device (n <= 2^30).  WFS_E_STATE without a model. */
+/* noise(channel, t0 .. t0 + n - 1) of the model (with its colour, if one is set), evaluated on the device (n <= 2^30).  WFS_E_STATE
+ * without a model. */
 int wfs_noise_model_samples(wfs_handle *h, int32_t channel, int64_t t0, int64_t n, int16_t *out);
+/* A colour for the noise model: every stream r -- the model's n_channels channels, then n_groups common streams -- is a white
+ * sequence w(r, t) drawn as above (common stream g under the counter of "channel" g at site 66, from cells built of
+ * common_pmf[g][n_values] over the model's values) and run through the FIR taps_q[r][n_taps] (Q16, 65536 = 1.0):
+ *   F(r, t) = sum_k taps_q[r][k] w(r, t - k)
+ *   noise(ch, t) = (F(ch, t) + ((int64) mix_q[ch] * F(n_channels + group[ch], t) >> 16) + 32768) >> 16      (group[ch] = -1: no common part)
+ * in exact integer arithmetic.  Needs a model (WFS_E_STATE without one); wfs_set_noise_model clears the colour; n_taps = 0 clears it
+ * and the white values return.  WFS_E_INVALID, with the argument named: n_taps outside 1 .. 16; a row of taps_q with
+ * sum |taps_q| * max(|vmin|, |vmin + n_values - 1|) >= 2^29; group outside -1 .. n_groups - 1; |mix_q| > 65536; a row of common_pmf
+ * that has a negative entry or does not sum to 1 within 1e-9.  group, mix_q and common_pmf may be null with n_groups = 0.  With
+ * n_taps = 1, taps_q = 65536 and no groups the values are those of the white model. */
+int wfs_set_noise_colour(wfs_handle *h, int32_t n_taps, const int32_t *taps_q, int32_t n_groups, const int32_t *group, const int32_t *mix_q,
+                         const double *common_pmf);
+/* The white sequence w(row, t0 .. t0 + n - 1) of a stream: row < n_channels a channel, n_channels + g common stream g. */
+int wfs_noise_white_samples(wfs_handle *h, int32_t row, int64_t t0, int64_t n, int16_t *out);
 /* The alias cells of a channel as the device holds them: thr[n_cells], alias[n_cells] (n_cells = 2^k >= max(2, n_values), the same for
  * every channel), shift = 32 - k and vmin.  capacity_cells: entries the two buffers hold. */
 int wfs_copy_noise_model(wfs_handle *h, int32_t channel, uint32_t *thr, uint32_t *alias, int32_t capacity_cells, int32_t *n_cells,

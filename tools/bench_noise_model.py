@@ -4,12 +4,14 @@ The mixed batch of workloads.mixed_config (S1 + S2 pairs, PMT afterpulses and no
 
 * ``table_3000``   its 3000-sample noise table, replayed from a random offset per window (what every workload here does);
 * ``table_1e6``    a 10^6-sample table of the same distribution: long enough not to repeat inside a row, 2 B of HBM per sample read;
-* ``model``        noise_model = {'sigma': 2.2}: drawn per sample, no table.
+* ``model``        noise_model = {'sigma': 2.2}: drawn per sample, no table (noise kind 3);
+* ``colour_L4``, ``colour_L16``, ``colour_L4_common``, ``colour_L16_common``  the same with unit-power FIR taps of 4 / 16 samples, without and
+  with one common stream shared by all channels (gain 0.5): noise kind 4, one or two streams per row.
 
-Prints one JSON line: ms per step of each (several repeats), and the per-kernel times of k_zle, k_pack, k_row_pulse and k_pack_res from
+``--variants a,b`` runs a subset.  Prints one JSON line: ms per step of each (several repeats), and the per-kernel times of k_zle, k_pack, k_row_pulse and k_pack_res from
 one profiled step (wfs_kernel_times).  Report only: the three compute different noise, so records and intervals differ in number.
 
-usage: python tools/bench_noise_model.py [--instructions 10000] [--steps 10] [--warmup 3] [--out profiles/noise_model_cost.json]
+usage: python tools/bench_noise_model.py [--instructions 10000] [--steps 10] [--warmup 3] [--variants model,colour_L4] [--out profiles/noise_model_cost.json]
 """
 import argparse
 import json
@@ -61,16 +63,26 @@ def main():
     ap.add_argument('--instructions', type=int, default=10000)
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--variants', default=None)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     import torch  # noqa: F401  (torch.cuda before the library, engine.load_library)
     variants = [('table_3000', {}),
                 ('table_1e6', dict(noise_data=long_noise(10 ** 6))),
                 ('model', dict(noise_model={'sigma': 2.2}))]
+    from wfsim_amd.noise_model import unit_power
+    n_ch = len(W.mixed_config(seed=3)['gains'])
+    for L in (4, 16):
+        taps = unit_power(np.hanning(L + 2)[1:-1])
+        common = dict(groups=np.zeros(n_ch, dtype=np.int64), gain=0.5, sigma=2.2, taps=taps)
+        variants += [(f'colour_L{L}', dict(noise_model={'sigma': 2.2, 'taps': taps})),
+                     (f'colour_L{L}_common', dict(noise_model={'sigma': 2.2, 'taps': taps, 'common': common}))]
+    if args.variants:
+        variants = [v for v in variants if v[0] in args.variants.split(',')]
     res = dict(workload='mixed', instructions=args.instructions, steps=args.steps, warmup=args.warmup)
     for name, ov in variants:
         eng = make(args.instructions, **ov)
-        assert (eng.noise_model is not None) == (name == 'model')
+        assert (eng.noise_model is not None) == (not name.startswith('table')) and (eng.noise_colour is not None) == name.startswith('colour')
         ms, c = timed(eng, args.steps, args.warmup)
         eng.set_profiling(True)
         eng.run()

@@ -37,7 +37,9 @@ enum WfsSite : u32 {
     SITE_AP = 32, SITE_AP_SCREEN = 40, SITE_AP_X = 48, SITE_NOISE = 64,
     // digitiser noise drawn per sample (wfs_set_noise_model): counter (low, high 32 bits of t >> 2, channel, site), t = absolute sample
     // index; sample t owns word t & 3
-    SITE_NOISE_SAMPLE = 65
+    SITE_NOISE_SAMPLE = 65,
+    // the common streams of the coloured model (wfs_set_noise_colour): the same counter with the group in place of the channel
+    SITE_NOISE_COMMON = 66
 };
 
 struct u32x4 { u32 x, y, z, w; };
@@ -90,6 +92,18 @@ __device__ __forceinline__ u32x4 noise_quad(u32 k0, u32 k1, i32 channel, i64 q)
 {
     return philox4x32_10((u32)(u64)q, (u32)((u64)q >> 32), (u32)channel, SITE_NOISE_SAMPLE, k0, k1);
 }
+// The same for any white stream of the coloured model: (channel, SITE_NOISE_SAMPLE) or (group, SITE_NOISE_COMMON)
+__device__ __forceinline__ u32x4 noise_quad_of(u32 k0, u32 k1, u32 id, u32 site, i64 q)
+{
+    return philox4x32_10((u32)(u64)q, (u32)((u64)q >> 32), id, site, k0, k1);
+}
+
+// The FIR taps of the coloured model on the device: one row of NC_TAP_STRIDE int32 (Q16) per stream, tap k at [NC_TAP_PAD + k], zeros in
+// front and behind -- a lane that holds a quad of whites multiplies all four words by the taps their distance asks for, and the
+// distances that fall outside 0 .. L - 1 (at most NC_TAP_PAD to either side) meet a zero instead of a branch.
+constexpr int NC_MAX_TAPS = 16;
+constexpr int NC_TAP_PAD = 6;
+constexpr int NC_TAP_STRIDE = NC_MAX_TAPS + 2 * NC_TAP_PAD;
 
 // Integer-valued delays.  The reference draws float variates and truncates each to int64 before adding it (pulse.py:54-56
 // transit time, s1.py:193-194, s2.py:338, pulse.py:339-341, s2.py:550); only the SUM reaches the pulse, and the sum of
@@ -319,4 +333,8 @@ struct WfsDev {
     // model; noise_channels then counts the model's channels and the table above is not read
     const uint2 *nm_cells;
     i32 nm_cells_per_ch, nm_shift, nm_vmin;
+    // the colour of the model (wfs_set_noise_colour, noise kind 4): nc_taps [noise_channels + nc_groups][NC_TAP_STRIDE], nullptr without a
+    // colour; the cells of common stream g are row noise_channels + g of nm_cells; group (-1: none) and Q16 gain per channel
+    const i32 *nc_taps, *nc_group, *nc_mix;
+    i32 nc_n_taps, nc_groups;
 };

@@ -104,7 +104,10 @@ struct wfs_handle {
     DevBuf row_desc, rec_key, rec_key2, rec_val, rec_val2, rec_dest, sort_tmp, scan_tmp, scal, noise_override;
     bool sort_records = false; i64 n_noise_override = 0;
     // the noise model (wfs_set_noise_model): alias cells [nm_channels][nm_k] on the device and on the host; nm_channels 0: no model
-    DevBuf nm_cells; std::vector<uint2> h_nm_cells; i32 nm_channels = 0, nm_k = 0, nm_shift = 0, nm_vmin = 0;
+    DevBuf nm_cells; std::vector<uint2> h_nm_cells; i32 nm_channels = 0, nm_k = 0, nm_shift = 0, nm_vmin = 0, nm_values = 0;
+    // its colour (wfs_set_noise_colour): nc_buf holds taps [nm_channels + nc_groups][NC_TAP_STRIDE] | group [nm_channels] | mix [nm_channels];
+    // the cells of the common streams follow the channels' in nm_cells (h_nm_cells keeps the channels' alone).  nc_n_taps 0: white
+    DevBuf nc_buf; i32 nc_n_taps = 0, nc_groups = 0;
     i32 table_channels = 0;           // columns of the noise table (dev.noise_channels counts the model's channels while a model is set)
     // host mirrors
     std::vector<i64> h_set_off;       // injected photons: per set photon offsets (channel sorted input order)
@@ -333,12 +336,13 @@ int read_scal(wfs_handle *h)
 }
 
 // The row kernels take the kind of noise as a template parameter (no branch between their loads): 0 none, 1 int16 table, 2 float
-// table, 3 the noise model.
+// table, 3 the noise model, 4 the noise model with a colour.
 // f is called with a std::integral_constant of the kind.
 template <class F> void with_noise_kind(int kind, F &&f)
 {
     if (kind == 0) f(std::integral_constant<int, 0>{}); else if (kind == 1) f(std::integral_constant<int, 1>{}); else if (kind == 2) f(std::integral_constant<int, 2>{});
-    else f(std::integral_constant<int, 3>{});
+    else if (kind == 3) f(std::integral_constant<int, 3>{});
+    else f(std::integral_constant<int, 4>{});
 }
 
 // a code that kernels raised in the device scalar block (WfsDevError) -> error code and message of the C ABI
@@ -514,6 +518,11 @@ void refresh_dev(wfs_handle *h)
     const bool model = h->nm_channels > 0;
     d.nm_cells = model ? h->nm_cells.as<uint2>() : nullptr; d.nm_cells_per_ch = h->nm_k; d.nm_shift = h->nm_shift; d.nm_vmin = h->nm_vmin;
     d.noise_channels = model ? h->nm_channels : h->table_channels;
+    // the colour of the model (wfs_set_noise_colour): taps of every stream, then group and gain of every channel, in one buffer
+    const bool colour = model && h->nc_n_taps > 0;
+    d.nc_taps = colour ? h->nc_buf.as<i32>() : nullptr; d.nc_n_taps = colour ? h->nc_n_taps : 0; d.nc_groups = colour ? h->nc_groups : 0;
+    d.nc_group = (colour && h->nc_groups > 0) ? d.nc_taps + (size_t)(h->nm_channels + h->nc_groups) * NC_TAP_STRIDE : nullptr;
+    d.nc_mix = d.nc_group ? d.nc_group + h->nm_channels : nullptr;
     d.enable_noise = (c.enable_noise && (model || d.noise != nullptr)) ? 1 : 0;
     bool he_noise = d.enable_noise && d.noise_channels > c.he_first;
     d.he_rows = (c.detector_nt && c.n_top > 0 && (c.he_factor != 0 || he_noise)) ? 1 : 0;
@@ -2152,7 +2161,7 @@ static int run_rows(wfs_handle *h, RunState &r)
     }
     TRY(fg.flush());
     if (h->n_active_rows > 0) { Timer t(h, "k_row_desc"); hipLaunchKernelGGL(k_row_desc, dim3(nblocks(h->n_active_rows, 256)), dim3(256), 0, h->stream, d, za); }
-    r.noise_kind = !d.enable_noise ? 0 : (d.nm_cells ? 3 : (d.noise_f ? 2 : 1));
+    r.noise_kind = !d.enable_noise ? 0 : (d.nm_cells ? (d.nc_taps ? 4 : 3) : (d.noise_f ? 2 : 1));
     if (h->n_res_rows > 0) {        // resident rows: pulses, finished samples and intervals by one wave per row
         PulseArgs pr = pa;
         pr.desc = h->res_desc.as<TileDesc>(); pr.currents = nullptr; pr.cur_off = nullptr;
@@ -2719,6 +2728,7 @@ try {
     if (n_channels == 0) {
         HIPCHK(hipStreamSynchronize(h->stream));
         h->nm_channels = 0; h->h_nm_cells.clear(); h->nm_cells.reset();
+        h->nc_n_taps = 0; h->nc_groups = 0; h->nc_buf.reset();
         h->ran = false;
         refresh_dev(h);
         return WFS_OK;
@@ -2742,7 +2752,8 @@ try {
     const i32 K = (i32)(cells.size() / (size_t)n_channels);
     TRY(upload(h, h->nm_cells, cells.data(), cells.size() * sizeof(uint2)));
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->h_nm_cells.swap(cells); h->nm_channels = n_channels; h->nm_k = K; h->nm_shift = shift; h->nm_vmin = vmin;
+    h->h_nm_cells.swap(cells); h->nm_channels = n_channels; h->nm_k = K; h->nm_shift = shift; h->nm_vmin = vmin; h->nm_values = n_values;
+    h->nc_n_taps = 0; h->nc_groups = 0; h->nc_buf.reset();          // a colour belongs to the shapes of the model it was set on
     h->ran = false;             // (HE rows may appear or go with the model's channel count: run again before copying)
     refresh_dev(h);
     return WFS_OK;
@@ -2759,7 +2770,81 @@ try {
     HIPCHK(hipSetDevice(h->device));
     DevBuf buf;
     TRY(ensure(h, buf, (size_t)n * sizeof(int16_t)));
-    { Timer t(h, "k_noise_model_samples"); hipLaunchKernelGGL(k_noise_model_samples, dim3(nblocks((n + 3) / 4, 256)), dim3(256), 0, h->stream, h->dev, channel, t0, n, buf.as<int16_t>()); }
+    if (h->dev.nc_taps) { Timer t(h, "k_noise_colour_samples"); hipLaunchKernelGGL(k_noise_colour_samples, dim3(nblocks((n + 255) / 256, 4)), dim3(256), 0, h->stream, h->dev, channel, t0, n, buf.as<int16_t>()); }
+    else { Timer t(h, "k_noise_model_samples"); hipLaunchKernelGGL(k_noise_model_samples, dim3(nblocks((n + 3) / 4, 256)), dim3(256), 0, h->stream, h->dev, channel, t0, n, buf.as<int16_t>()); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, buf.p, (size_t)n * sizeof(int16_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    CHECK_LAUNCHES();
+    return WFS_OK;
+} WFS_CATCH(h)
+
+// The colour of the noise model: FIR taps per stream and common streams shared by groups of channels.  Everything the
+// kernels rely on is checked here: the tap count, the bound that keeps the int32 sums of the kernels exact, groups and gains.
+int wfs_set_noise_colour(wfs_handle *h, int32_t n_taps, const int32_t *taps_q, int32_t n_groups, const int32_t *group, const int32_t *mix_q, const double *common_pmf)
+try {
+    if (!h) return WFS_E_INVALID;
+    if (h->nm_channels <= 0) return h->fail(WFS_E_STATE, "wfs_set_noise_colour: no noise model is set");
+    HIPCHK(hipSetDevice(h->device));
+    const i32 C = h->nm_channels, V = h->nm_values;
+    if (n_taps == 0) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (h->nc_groups > 0) { TRY(upload(h, h->nm_cells, h->h_nm_cells.data(), h->h_nm_cells.size() * sizeof(uint2))); HIPCHK(hipStreamSynchronize(h->stream)); }
+        h->nc_n_taps = 0; h->nc_groups = 0; h->nc_buf.reset();
+        refresh_dev(h);
+        return WFS_OK;
+    }
+    if (n_taps < 1 || n_taps > NC_MAX_TAPS) return h->fail(WFS_E_INVALID, "wfs_set_noise_colour: n_taps outside 1 .. 16");
+    if (n_groups < 0 || n_groups > 1024) return h->fail(WFS_E_INVALID, "wfs_set_noise_colour: n_groups outside 0 .. 1024");
+    if (!taps_q) return h->fail(WFS_E_INVALID, "wfs_set_noise_colour: null taps_q");
+    if (n_groups > 0 && (!group || !mix_q || !common_pmf)) return h->fail(WFS_E_INVALID, "wfs_set_noise_colour: null group, mix_q or common_pmf with n_groups > 0");
+    const i32 R = C + n_groups;
+    const i64 vmax = std::max<i64>(std::llabs((long long)h->nm_vmin), std::llabs((long long)h->nm_vmin + V - 1));
+    std::vector<i32> buf((size_t)R * NC_TAP_STRIDE + 2 * (size_t)C, 0);
+    for (i32 r = 0; r < R; r++) {
+        i64 sum = 0;
+        for (i32 k = 0; k < n_taps; k++) { const i32 v = taps_q[(size_t)r * n_taps + k]; sum += std::llabs((long long)v); buf[(size_t)r * NC_TAP_STRIDE + NC_TAP_PAD + k] = v; }
+        if (sum * vmax >= ((i64)1 << 29)) return h->fail(WFS_E_INVALID, "wfs_set_noise_colour: taps_q of row " + std::to_string(r) + ": sum |taps| * max |value| reaches 2^29");
+    }
+    i32 *grp = buf.data() + (size_t)R * NC_TAP_STRIDE, *mix = grp + C;
+    for (i32 c = 0; c < C; c++) {
+        grp[c] = n_groups > 0 ? group[c] : -1; mix[c] = n_groups > 0 ? mix_q[c] : 0;
+        if (grp[c] < -1 || grp[c] >= n_groups) return h->fail(WFS_E_INVALID, "wfs_set_noise_colour: group of channel " + std::to_string(c) + " outside -1 .. n_groups - 1");
+        if (mix[c] < -65536 || mix[c] > 65536) return h->fail(WFS_E_INVALID, "wfs_set_noise_colour: mix_q of channel " + std::to_string(c) + " beyond 65536 in magnitude");
+    }
+    std::vector<uint2> cells(h->h_nm_cells), cell; std::vector<double> cum((size_t)V); int shift = 31;
+    for (i32 g = 0; g < n_groups; g++) {
+        const double *row = common_pmf + (size_t)g * V;
+        double acc = 0;
+        for (i32 v = 0; v < V; v++) {
+            if (!(row[v] >= 0.0)) return h->fail(WFS_E_INVALID, "wfs_set_noise_colour: common_pmf has a negative (or NaN) entry in group " + std::to_string(g));
+            acc += row[v]; cum[(size_t)v] = acc;
+        }
+        if (!(fabs(acc - 1.0) <= 1e-9)) return h->fail(WFS_E_INVALID, "wfs_set_noise_colour: common_pmf of group " + std::to_string(g) + " does not sum to 1");
+        build_alias(cum, cell, shift);
+        cells.insert(cells.end(), cell.begin(), cell.end());
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (n_groups > 0 || h->nc_groups > 0) TRY(upload(h, h->nm_cells, cells.data(), cells.size() * sizeof(uint2)));
+    TRY(upload(h, h->nc_buf, buf.data(), buf.size() * sizeof(i32)));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->nc_n_taps = n_taps; h->nc_groups = n_groups;
+    refresh_dev(h);
+    return WFS_OK;
+} WFS_CATCH(h)
+
+int wfs_noise_white_samples(wfs_handle *h, int32_t row, int64_t t0, int64_t n, int16_t *out)
+try {
+    if (!h) return WFS_E_INVALID;
+    if (h->nm_channels <= 0) return h->fail(WFS_E_STATE, "wfs_noise_white_samples: no noise model is set");
+    if (row < 0 || row >= h->nm_channels + h->nc_groups) return h->fail(WFS_E_INVALID, "wfs_noise_white_samples: row outside the model's channels and common streams");
+    if (n < 0 || n > ((i64)1 << 30) || (n > 0 && !out)) return h->fail(WFS_E_INVALID, "wfs_noise_white_samples: n outside 0 .. 2^30 or null buffer");
+    if (t0 > I64_MAX - n) return h->fail(WFS_E_INVALID, "wfs_noise_white_samples: t0 + n overflows");
+    if (n == 0) return WFS_OK;
+    HIPCHK(hipSetDevice(h->device));
+    DevBuf buf;
+    TRY(ensure(h, buf, (size_t)n * sizeof(int16_t)));
+    { Timer t(h, "k_noise_white_samples"); hipLaunchKernelGGL(k_noise_white_samples, dim3(nblocks(n, 256)), dim3(256), 0, h->stream, h->dev, row, t0, n, buf.as<int16_t>()); }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, buf.p, (size_t)n * sizeof(int16_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));

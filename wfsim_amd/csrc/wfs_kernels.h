@@ -1650,7 +1650,102 @@ __device__ __forceinline__ void noise_model_four(const WfsDev &d, const uint2 *c
     for (int j = 0; j < 4; j++) out[j] = alias_sample(tab, w[j]);
 }
 
-// (NK: the noise kind of the row kernels below; row_abs, the row's first absolute sample, is what kind 3 counts from)
+// The coloured model (wfs_set_noise_colour, noise kind 4): every stream r -- the channels, then the common streams -- has a
+// white sequence w(r, t) as above (a common stream g under the counter (.., g, SITE_NOISE_COMMON)) and L Q16 taps;
+//   F(r, t) = sum_k taps[r][k] w(r, t - k),   noise(ch, t) = (F(ch, t) + ((i64)mix[ch] F(common of ch, t) >> 16) + 32768) >> 16,
+// all in integers: the host has checked that F fits 30 bits (wfs_set_noise_colour).
+//
+// Single-sample form: a lane draws the quads that cover t - L + 1 .. t itself (up to (L + 6) / 4 calls).  No cross-lane traffic, so it
+// may be called from divergent code and with any t per lane: the record-ordered lanes of k_pack, the 64-sample chunks of k_zle's
+// general path, finish_sample.
+__device__ __forceinline__ i32 colour_stream_sample(const WfsDev &d, i32 row, u32 id, u32 site, i64 t)
+{
+    const AliasTab tab{d.nm_cells + (i64)row * d.nm_cells_per_ch, d.nm_vmin, d.nm_shift};
+    const i32 *taps = d.nc_taps + (i64)row * NC_TAP_STRIDE + NC_TAP_PAD;
+    const i64 q1 = t >> 2;
+    i32 F = 0;
+#pragma nounroll
+    for (i64 q = (t - (d.nc_n_taps - 1)) >> 2; q <= q1; q++) {
+        const u32x4 a = noise_quad_of(d.k0, d.k1, id, site, q);
+        const u32 w[4] = {a.x, a.y, a.z, a.w};
+        const i32 k0 = (i32)(t - 4 * q);                       // distance of the quad's first white: -3 .. L + 2, inside the zero pads
+#pragma unroll
+        for (int c = 0; c < 4; c++) F += taps[k0 - c] * alias_sample(tab, w[c]);
+    }
+    return F;
+}
+// The streams of a channel are walked by a loop that stays a loop (the channel's own with gain 1.0, then its common stream with mix):
+// one copy of the draws per call site, whatever the number of streams -- unrolled and interleaved they took every register there is.
+__device__ __forceinline__ i32 noise_colour_sample(const WfsDev &d, i32 channel, i64 t)
+{
+    const i32 g = d.nc_group ? d.nc_group[channel] : -1;        // (wave-uniform wherever a wave works on one row)
+    const i32 mix = g >= 0 ? d.nc_mix[channel] : 0;
+    i32 sum = 0;
+#pragma nounroll
+    for (int s = 0; s < (g >= 0 ? 2 : 1); s++) {
+        const i32 F = colour_stream_sample(d, s ? d.noise_channels + g : channel, (u32)(s ? g : channel), s ? SITE_NOISE_COMMON : SITE_NOISE_SAMPLE, t);
+        sum += (i32)(((i64)(s ? mix : 65536) * F) >> 16);       // (65536 F >> 16 is F)
+    }
+    return (sum + 32768) >> 16;
+}
+// Four-sample form: lane l of a wave takes samples tb + 4 l .. tb + 4 l + 3, tb wave-uniform.  The 256 + L - 1 whites of the wave lie in
+// the aligned quads qb .. qb + 64 + dmax - 1, qb = (tb - L + 1) >> 2, dmax <= 5: lane l draws quad qb + l and alias-samples it, lanes
+// 0 .. dmax - 1 draw quad qb + 64 + l in a second call, and the four cell values of a quad travel as two packed words.  The whites of
+// lane l sit in the quads of lanes l .. l + dmax (lanes past 63: the second call's): one cross-lane fetch of two words per step, the
+// same step for every lane, and sixteen multiply-adds against the seven taps the step's distances ask for (scalar loads; zeros outside
+// 0 .. L - 1).  Two Philox calls and eight alias gathers per lane and stream whatever L and tb & 3.
+// ALL 64 LANES MUST BE EXECUTING (ds_bpermute reads nothing from a switched-off lane): call it before any per-lane bound.
+__device__ __forceinline__ void colour_stream_four(const WfsDev &d, i32 row, u32 id, u32 site, i64 tb, int lane, i32 *F)
+{
+    const AliasTab tab{d.nm_cells + (i64)row * d.nm_cells_per_ch, d.nm_vmin, d.nm_shift};
+    const i32 *taps = d.nc_taps + (i64)row * NC_TAP_STRIDE + NC_TAP_PAD;
+    const i64 s0 = tb - (d.nc_n_taps - 1);                      // the first white lane 0 needs
+    const i64 qb = s0 >> 2;
+    const i32 reach = __builtin_amdgcn_readfirstlane(d.nc_n_taps - 1 + (i32)(s0 & 3));      // distance of sample 0 of a lane from word 0 of its own quad
+    const i32 dmax = (reach + 3) >> 2;
+    auto quad = [&](i64 q, u32 &lo, u32 &hi) {
+        const u32x4 a = noise_quad_of(d.k0, d.k1, id, site, q);
+        lo = ((u32)alias_sample(tab, a.x) & 0xffffu) | ((u32)alias_sample(tab, a.y) << 16);
+        hi = ((u32)alias_sample(tab, a.z) & 0xffffu) | ((u32)alias_sample(tab, a.w) << 16);
+    };
+    u32 p0, p1, r0 = 0, r1 = 0;
+    quad(qb + lane, p0, p1);
+    if (lane < dmax) quad(qb + 64 + lane, r0, r1);
+    F[0] = F[1] = F[2] = F[3] = 0;
+#pragma nounroll
+    for (i32 dd = 0; dd <= dmax; dd++) {                        // (wave-uniform)
+        // lanes below dd are read by nobody at this step but the lanes that wrap: they lend the second call's quads
+        const i32 src = ((lane + dd) & 63) << 2;
+        const u32 g0 = (u32)__builtin_amdgcn_ds_bpermute(src, (int)(lane < dd ? r0 : p0));
+        const u32 g1 = (u32)__builtin_amdgcn_ds_bpermute(src, (int)(lane < dd ? r1 : p1));
+        const i32 w[4] = {(i32)(int16_t)g0, (i32)g0 >> 16, (i32)(int16_t)g1, (i32)g1 >> 16};
+        const i32 kb = reach - 4 * dd;                          // sample j against word c: tap kb + j - c
+        i32 tp[7];
+#pragma unroll
+        for (int u = 0; u < 7; u++) tp[u] = taps[kb - 3 + u];
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+#pragma unroll
+            for (int j = 0; j < 4; j++) F[j] += tp[3 + j - c] * w[c];
+    }
+}
+__device__ __forceinline__ void noise_colour_four(const WfsDev &d, i32 channel, i64 tb, int lane, i32 *out)
+{
+    const i32 g = __builtin_amdgcn_readfirstlane(d.nc_group ? d.nc_group[channel] : -1);        // (one row per wave)
+    const i32 mix = g >= 0 ? d.nc_mix[channel] : 0;
+    i32 sum[4] = {0, 0, 0, 0};
+#pragma nounroll
+    for (int s = 0; s < (g >= 0 ? 2 : 1); s++) {
+        i32 F[4];
+        colour_stream_four(d, s ? d.noise_channels + g : channel, (u32)(s ? g : channel), s ? SITE_NOISE_COMMON : SITE_NOISE_SAMPLE, tb, lane, F);
+#pragma unroll
+        for (int j = 0; j < 4; j++) sum[j] += (i32)(((i64)(s ? mix : 65536) * F[j]) >> 16);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) out[j] = (sum[j] + 32768) >> 16;
+}
+
+// (NK: the noise kind of the row kernels below; row_abs, the row's first absolute sample, is what kinds 3 and 4 count from)
 template <int NK>
 __device__ __forceinline__ i32 finish_sample(const WfsDev &d, const i32 *acc, i64 i, i32 slot_ch, bool he, i64 ix_rand, i64 row_abs)
 {
@@ -1658,6 +1753,8 @@ __device__ __forceinline__ i32 finish_sample(const WfsDev &d, const i32 *acc, i6
     if (he) v *= d.he_factor;                                   // rawdata.py:242-246
     if constexpr (NK == 3) {
         if (slot_ch < d.noise_channels) v += noise_model_sample(d, d.nm_cells + (i64)slot_ch * d.nm_cells_per_ch, slot_ch, row_abs + i);
+    } else if constexpr (NK == 4) {
+        if (slot_ch < d.noise_channels) v += noise_colour_sample(d, slot_ch, row_abs + i);
     } else
     if (d.enable_noise && slot_ch < d.noise_channels) {
         const u32 in = ((u32)ix_rand + (u32)i) % (u32)d.noise_len;      // rawdata.py:433-434 (ix_rand < noise_len <= 2^31, i < 2^20: 32 bits hold the sum)
@@ -1686,6 +1783,35 @@ __global__ __launch_bounds__(256) void k_noise_model_samples(WfsDev d, i32 chann
     }
 }
 
+// The same for the coloured model: a wave takes 256 consecutive samples through the four-sample form -- every lane draws and exchanges,
+// whatever n, and only the stores look at n -- and the last n & 3 samples go through the single-sample form.
+__global__ __launch_bounds__(256) void k_noise_colour_samples(WfsDev d, i32 channel, i64 t0, i64 n, int16_t *out)
+{
+    const int lane = threadIdx.x & 63;
+    const i64 b = ((i64)blockIdx.x * 4 + wave_in_block()) * 256;
+    i32 v[4];
+    noise_colour_four(d, channel, t0 + b, lane, v);
+    const i64 s = b + 4 * lane;
+    if (s + 3 < n) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) out[s + j] = (int16_t)v[j];
+    } else {
+        for (i64 u = s; u < n; u++) out[u] = (int16_t)noise_colour_sample(d, channel, t0 + u);
+    }
+}
+// wfs_noise_white_samples: the white sequence w(row, t0 .. t0 + n - 1) of a stream, a channel or (row >= noise_channels) a common stream
+__global__ __launch_bounds__(256) void k_noise_white_samples(WfsDev d, i32 row, i64 t0, i64 n, int16_t *out)
+{
+    const i64 s = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const AliasTab tab{d.nm_cells + (i64)row * d.nm_cells_per_ch, d.nm_vmin, d.nm_shift};
+    const bool common = row >= d.noise_channels;
+    const i64 t = t0 + s;
+    const u32x4 a = noise_quad_of(d.k0, d.k1, (u32)(common ? row - d.noise_channels : row), common ? SITE_NOISE_COMMON : SITE_NOISE_SAMPLE, t >> 2);
+    const u32 m = (u32)t & 3u;
+    out[s] = (int16_t)alias_sample(tab, m == 0 ? a.x : (m == 1 ? a.y : (m == 2 ? a.z : a.w)));
+}
+
 // (acc_ch -1: the window's sum row, which has no accumulator row of a channel behind it)
 __device__ __forceinline__ void row_of_slot(const WfsDev &d, i64 idx, i64 &g, i32 &channel, i32 &acc_ch, bool &he)
 {
@@ -1698,7 +1824,8 @@ __device__ __forceinline__ void row_of_slot(const WfsDev &d, i64 idx, i64 &g, i3
 // the compiler waits for every load right behind it (a branch follows), and a wave spends one memory round trip per load.
 // A row no longer than the noise array wraps at most once (ix_rand < noise_len, i < len <= noise_len): no loop on the load path.
 // NK, the noise of the batch, is a template parameter (0: none, 1: int16 table, 2: float64 table, 3: the noise model, drawn where the
-// tables are loaded: noise_row then points at the channel's alias cells, nullptr for a row outside the model) and a row outside the table
+// tables are loaded: noise_row then points at the channel's alias cells, nullptr for a row outside the model; 4: the coloured model,
+// drawn at the same places -- load_sample through the single-sample form, load_four through the shared draws) and a row outside the table
 // (noisy false, wave-uniform) reads row 0 and drops the value: NO branch sits between two loads -- with a branch around the
 // noise load the compiler drained the memory counter after every one of them.
 template <int NK> struct RawSample;
@@ -1706,6 +1833,7 @@ template <> struct RawSample<0> { i32 acc; };
 template <> struct RawSample<1> { i32 acc; i32 nz; };
 template <> struct RawSample<2> { i32 acc; double nzf; };
 template <> struct RawSample<3> { i32 acc; i32 nz; };
+template <> struct RawSample<4> { i32 acc; i32 nz; };
 template <int NK>
 __device__ __forceinline__ RawSample<NK> load_sample(const WfsDev &d, const i32 *acc, i32 i, const void *noise_row, u32 nstart, u32 noff, i32 channel = 0, i64 row_abs = 0)
 {
@@ -1713,6 +1841,7 @@ __device__ __forceinline__ RawSample<NK> load_sample(const WfsDev &d, const i32 
     // noise sample nstart + noff of the row, nstart < noise_len a scalar, noff < noise_len: one conditional subtraction wraps it
     RawSample<NK> s; s.acc = acc[(u32)i];
     if constexpr (NK == 3) s.nz = noise_row ? noise_model_sample(d, (const uint2 *)noise_row, channel, row_abs + i) : 0;      // (wave-uniform)
+    else if constexpr (NK == 4) s.nz = noise_row ? noise_colour_sample(d, channel, row_abs + i) : 0;
     else if constexpr (NK != 0) {
         u32 in = nstart + noff;
         in = in >= (u32)d.noise_len ? in - (u32)d.noise_len : in;
@@ -1727,7 +1856,7 @@ __device__ __forceinline__ i32 finish_loaded(const WfsDev &d, const RawSample<NK
     if (he) v *= d.he_factor;
     if constexpr (NK == 1) v += noisy ? s.nz : 0;
     if constexpr (NK == 2) { const i64 w = (i64)((double)v + s.nzf); v = noisy ? w : v; }
-    if constexpr (NK == 3) v += s.nz;
+    if constexpr (NK == 3 || NK == 4) v += s.nz;
     v += d.baseline;
     return v < 0 ? 0 : (i32)v;
 }
@@ -1739,12 +1868,18 @@ template <> struct Raw4<0> { i32 acc[4]; };
 template <> struct Raw4<1> { i32 acc[4]; int16_t nz[4]; };
 template <> struct Raw4<2> { i32 acc[4]; double nzf[4]; };
 template <> struct Raw4<3> { i32 acc[4]; i32 nz[4]; };
+template <> struct Raw4<4> { i32 acc[4]; i32 nz[4]; };
 template <int NK>
 __device__ __forceinline__ Raw4<NK> load_four(const WfsDev &d, const i32 *acc, i32 i, const void *noise_row, u32 nstart, u32 noff, i32 channel = 0, i64 row_abs = 0)
 {
     Raw4<NK> s; __builtin_memcpy(s.acc, acc + (u32)i, 16);
     if constexpr (NK == 3) {
         if (noise_row) noise_model_four(d, (const uint2 *)noise_row, channel, row_abs, i, s.nz);      // (wave-uniform; i is a multiple of four)
+        else s.nz[0] = s.nz[1] = s.nz[2] = s.nz[3] = 0;
+    } else if constexpr (NK == 4) {
+        // i may be clamped into the row (k_zle, lanes past its end): the position is nstart, the UNCLAMPED wave-uniform index of the
+        // block's first sample in the row, plus the lane's noff = 4 lane -- a lane past the end still draws the quad its neighbours need
+        if (noise_row) noise_colour_four(d, channel, row_abs + (i64)nstart, (int)(noff >> 2), s.nz);      // (wave-uniform)
         else s.nz[0] = s.nz[1] = s.nz[2] = s.nz[3] = 0;
     } else if constexpr (NK != 0) {
         u32 in = nstart + noff;
@@ -1760,7 +1895,7 @@ __device__ __forceinline__ i32 finish_four(const WfsDev &d, const Raw4<NK> &s, i
     if (he) v *= d.he_factor;
     if constexpr (NK == 1) v += noisy ? (i32)s.nz[j] : 0;
     if constexpr (NK == 2) { const i64 w = (i64)((double)v + s.nzf[j]); v = noisy ? w : v; }
-    if constexpr (NK == 3) v += s.nz[j];
+    if constexpr (NK == 3 || NK == 4) v += s.nz[j];
     v += d.baseline;
     return v < 0 ? 0 : (i32)v;
 }
@@ -1848,16 +1983,16 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
     // the noise index of a row's sample i is (ix + i) mod noise_len (rawdata.py:433-434): a scalar start per block of samples that
     // steps with the block and wraps, plus the lane's offset inside the block -- rows may be any number of noise lengths long.
     // (A table shorter than NOISE_MIN_FAST samples would wrap more than once inside a block: the general path below.)
-    // (The noise model, kind 3, has no table and no wrap: the fast paths wherever kind 0 takes them.)
+    // (The noise model, kinds 3 and 4, has no table and no wrap: the fast paths wherever kind 0 takes them.)
     constexpr bool TABLE = NK == 1 || NK == 2;
     const bool fast_loads = len32 >= 1 && (!TABLE || d.noise_len >= NOISE_MIN_FAST);
     const i64 noise_off = noisy ? (i64)channel * d.noise_stride : 0; const u32 nixr = noisy ? (u32)ixr : 0u;
-    const void *noise_row = NK == 3 ? (const void *)(noisy ? d.nm_cells + (i64)channel * d.nm_cells_per_ch : nullptr)
+    const void *noise_row = (NK == 3 || NK == 4) ? (const void *)(noisy ? d.nm_cells + (i64)channel * d.nm_cells_per_ch : nullptr)
                                     : (NK == 2 ? (const void *)(d.noise_f + noise_off) : (const void *)(d.noise + noise_off));
     if (hold32 >= 63 && fast_loads && !a.row_dbg) {
         // The usual geometry (hold-off of at least a chunk): the interval bookkeeping is scalar work on the ballot mask (ZleFast), and
         // the vector unit is left with load, finish and compare.
-        constexpr int G = 4;
+        constexpr int G = NK == 4 ? 1 : 4;          // (kind 4 draws instead of loading: one block's draws at a time, one copy of their code)
         ZleFast z;
         // A lane takes FOUR consecutive samples (one 16-byte load of the row, one 8-byte load of the noise): a wave instruction moves
         // 1 KB of the row, and the hits of a lane are a nibble.
@@ -1871,7 +2006,7 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
 #pragma unroll
             for (int u = 0; u < G; u++) {
                 const i32 i = g0 + 256 * u + 4 * lane;
-                buf[u] = load_four<NK>(d, acc, i < len32 ? i : 0, noise_row, nrun, 4u * (u32)lane, channel, row_abs);
+                buf[u] = load_four<NK>(d, acc, i < len32 ? i : 0, noise_row, NK == 4 ? (u32)(g0 + 256 * u) : nrun, 4u * (u32)lane, channel, row_abs);
                 if constexpr (TABLE) { nrun += 256u; nrun = nrun >= (u32)d.noise_len ? nrun - (u32)d.noise_len : nrun; }
             }
         };
@@ -1893,11 +2028,11 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
     }
     // chunks of 64 samples; the loads of ZLE_GROUP chunks are issued together (one dependent load per chunk leaves the wave
     // waiting a memory round trip per 64 samples)
-    constexpr int ZLE_GROUP = 2;
+    constexpr int ZLE_GROUP = NK == 4 ? 1 : 2;      // (kind 4: nothing to overlap, one copy of the draws)
     u32 nrun1 = nixr;
     for (i32 g0 = 0; g0 < len32; g0 += 64 * ZLE_GROUP) {
         i32 vv[ZLE_GROUP];
-        if (fast_loads) {                                       // (wave-uniform) every load of the group first, then the arithmetic
+        if (NK == 4 || fast_loads) {                            // (wave-uniform) every load of the group first, then the arithmetic; kind 4 has no other path: a row it cannot take fast is empty
             RawSample<NK> rs[ZLE_GROUP];
 #pragma unroll
             for (int u = 0; u < ZLE_GROUP; u++) {
@@ -2048,14 +2183,18 @@ __global__ __launch_bounds__(256) void k_row_pulse(WfsDev d, PulseArgs a, ZleArg
     const i32 hold32 = (i32)hold;
     const bool noisy = NK != 0 && q.channel < d.noise_channels;
     const i64 noise_off = noisy ? (i64)q.channel * d.noise_stride : 0;
-    const void *noise_row = NK == 3 ? (const void *)(noisy ? d.nm_cells + (i64)q.channel * d.nm_cells_per_ch : nullptr)
+    const void *noise_row = (NK == 3 || NK == 4) ? (const void *)(noisy ? d.nm_cells + (i64)q.channel * d.nm_cells_per_ch : nullptr)
                                     : (NK == 2 ? (const void *)(d.noise_f + noise_off) : (const void *)(d.noise + noise_off));
-    u32 nrun = (noisy && NK != 3) ? (u32)q.ixr : 0u;       // noise index of the next block's first sample (rawdata.py:433-434); kind 3: that sample's index in the row
+    u32 nrun = (noisy && NK != 3 && NK != 4) ? (u32)q.ixr : 0u;       // noise index of the next block's first sample (rawdata.py:433-434); kinds 3, 4: that sample's index in the row
     int16_t *fin = z.fin + q.acc_off;
     const i32 fin_len = (len32 + 3) & ~3;
     auto load_noise = [&](Raw4<NK> &o) {
         if constexpr (NK == 3) {                          // drawn, not loaded: the block's first absolute sample is wave-uniform
             if (noise_row) noise_model_four(d, (const uint2 *)noise_row, q.channel, row_abs + (i64)nrun, 4 * lane, o.nz);
+            else o.nz[0] = o.nz[1] = o.nz[2] = o.nz[3] = 0;
+            nrun += 256u;
+        } else if constexpr (NK == 4) {                   // the shared draws: every lane of the wave is here (the callers' conditions are wave-uniform)
+            if (noise_row) noise_colour_four(d, q.channel, row_abs + (i64)nrun, lane, o.nz);
             else o.nz[0] = o.nz[1] = o.nz[2] = o.nz[3] = 0;
             nrun += 256u;
         } else if constexpr (NK != 0) {
@@ -2112,7 +2251,7 @@ __global__ __launch_bounds__(256) void k_row_pulse(WfsDev d, PulseArgs a, ZleArg
                 for (int j = 0; j < 4; j++) {
                     i32 add = d.baseline;
                     if constexpr (NK == 1) add += noisy ? (i32)s4.nz[j] : 0;
-                    if constexpr (NK == 3) add += s4.nz[j];
+                    if constexpr (NK == 3 || NK == 4) add += s4.nz[j];
                     i32 v = __builtin_elementwise_add_sat(s4.acc[j], add);
                     v = v < 0 ? 0 : v;
                     nib |= (j < live && v < thr32) ? (1u << j) : 0u; v16[j] = (u32)v;
@@ -2247,10 +2386,10 @@ __global__ __launch_bounds__(256) void k_pack(WfsDev d, ZleArgs a)
     constexpr bool TABLE = NK == 1 || NK == 2;
     const bool fast_loads = !TABLE || (d.noise_len >= NOISE_MIN_FAST && spr <= NOISE_MIN_FAST / 2);       // (as in k_zle: a scalar noise start per record)
     const i64 noise_off = noisy ? (i64)channel * d.noise_stride : 0; const u32 nixr = noisy ? (u32)ixr : 0u;
-    const void *noise_row = NK == 3 ? (const void *)(noisy ? d.nm_cells + (i64)channel * d.nm_cells_per_ch : nullptr)
+    const void *noise_row = (NK == 3 || NK == 4) ? (const void *)(noisy ? d.nm_cells + (i64)channel * d.nm_cells_per_ch : nullptr)
                                     : (NK == 2 ? (const void *)(d.noise_f + noise_off) : (const void *)(d.noise + noise_off));
     const u32 w3 = ((u32)(uint16_t)d.dt) | ((u32)(uint16_t)channel << 16);
-    constexpr int PACK_U = 4;
+    constexpr int PACK_U = NK == 4 ? 1 : 4;         // (kind 4 draws where the others load: one record's draws at a time, one copy of their code)
     i64 rec = q.rec;
     for (i32 k = 0; k < count; k++) {
         const i64 left = k == 0 ? q.left0 : a.itv_left[base + k]; const i32 plen = k == 0 ? q.plen0 : (i32)(a.itv_right[base + k] - left + 1);

@@ -111,7 +111,7 @@ EXPORTS = ['wfs_create', 'wfs_destroy', 'wfs_last_error', 'wfs_device_count', 'w
            'wfs_scalar_map_grid', 'wfs_scalar_map_points', 'wfs_scalar_map_spline', 'wfs_scalar_map_eval', 'wfs_set_noise_float', 'wfs_set_instruction_diffusion',
            'wfs_scalar_map_grid_array', 'wfs_scalar_map_points_array', 'wfs_scalar_map_linear', 'wfs_scalar_map_eval_array',
            'wfs_set_sum_signal', 'wfs_copy_sum_signal', 'wfs_device_allocations',
-           'wfs_set_noise_model', 'wfs_noise_model_samples', 'wfs_copy_noise_model']
+           'wfs_set_noise_model', 'wfs_noise_model_samples', 'wfs_copy_noise_model', 'wfs_set_noise_colour', 'wfs_noise_white_samples']
 
 
 def load_library():
@@ -201,8 +201,9 @@ class Engine:
         thr_truth, thr_zle = T.thresholds(config, N_ROWS)
         lum_x, lum_t = T.luminescence_table(config)
         # a noise model (noise_model.py) takes precedence over the noise array of the resource, which is then not uploaded
-        from .noise_model import noise_pmf
+        from .noise_model import noise_colour, noise_pmf
         self.noise_model = noise_pmf(config, params['n_rows']) if params['enable_noise'] else None
+        self.noise_colour = noise_colour(config, params['n_rows']) if params['enable_noise'] else None
         self.tables = dict(
             templates=T.pmt_current_templates(config), spe=T.spe_scaling_table(resource.spe_charge, resource.spe_pdfs),
             gains=_arr(config['gains'], np.float64), thr_truth=_arr(thr_truth, np.float64), thr_zle=_arr(thr_zle, np.int64),
@@ -240,6 +241,8 @@ class Engine:
         if self.noise_model is not None:
             self.set_noise_model(*self.noise_model)
             nc = self.noise_model[0].shape[0]
+            if self.noise_colour is not None:
+                self.set_noise_colour(**self.noise_colour)
         he_noise = bool(params['enable_noise']) and nc > params['he_first']
         self.emits_he_records = bool(params['detector_nt'] and params['n_top'] > 0 and (params['he_factor'] != 0 or he_noise))
         # pattern maps on regular grids are evaluated on the device (one channel CDF row per instruction)
@@ -667,6 +670,31 @@ class Engine:
         if pmf.ndim != 2:
             raise ValueError('set_noise_model: pmf must be [n_channels][n_values]')
         self._check(self.lib.wfs_set_noise_model(self._h, C.c_int32(pmf.shape[0]), C.c_int32(pmf.shape[1]), C.c_int32(int(vmin)), _p(pmf)))
+
+    def set_noise_colour(self, taps_q, group=None, mix_q=None, common_pmf=None):
+        """The colour of the noise model that is set (noise_model.py, wfs_set_noise_colour): taps_q int32[n_channels + n_groups][L] in Q16,
+        group int32[n_channels] (-1: none), mix_q int32[n_channels] in Q16, common_pmf[n_groups][n_values] on the model's values; the
+        last three may be None without common streams.  taps_q None clears the colour: the white values return.  From the next run."""
+        if taps_q is None:
+            self._check(self.lib.wfs_set_noise_colour(self._h, C.c_int32(0), C.c_void_p(0), C.c_int32(0), C.c_void_p(0), C.c_void_p(0), C.c_void_p(0)))
+            return
+        taps_q = _arr(taps_q, np.int32)
+        if taps_q.ndim != 2:
+            raise ValueError('set_noise_colour: taps_q must be [n_channels + n_groups][n_taps]')
+        n_groups = 0 if common_pmf is None else len(common_pmf)
+        if n_groups:
+            group, mix_q, common_pmf = _arr(group, np.int32), _arr(mix_q, np.int32), _arr(common_pmf, np.float64)
+            if group.ndim != 1 or mix_q.shape != group.shape or common_pmf.ndim != 2 or taps_q.shape[0] != len(group) + n_groups:
+                raise ValueError('set_noise_colour: group and mix_q must be [n_channels], common_pmf [n_groups][n_values], taps_q [n_channels + n_groups][n_taps]')
+        self._check(self.lib.wfs_set_noise_colour(
+            self._h, C.c_int32(taps_q.shape[1]), _p(taps_q), C.c_int32(n_groups), _p(group) if n_groups else C.c_void_p(0),
+            _p(mix_q) if n_groups else C.c_void_p(0), _p(common_pmf) if n_groups else C.c_void_p(0)))
+
+    def noise_white_samples(self, row, t0, n):
+        """the white sequence w(row, t0 .. t0 + n - 1) under the colour: row < n_channels a channel, n_channels + g common stream g"""
+        out = np.zeros(int(n), dtype=np.int16)
+        self._check(self.lib.wfs_noise_white_samples(self._h, C.c_int32(int(row)), C.c_int64(int(t0)), C.c_int64(int(n)), _p(out)))
+        return out
 
     def noise_samples(self, channel, t0, n):
         """noise(channel, t0 .. t0 + n - 1) of the noise model, evaluated on the device: t is the absolute sample index (time / dt)"""

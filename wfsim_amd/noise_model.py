@@ -18,12 +18,32 @@ noise only: samples are independent of each other and of the other channels.
   (see ``pmf_from_samples``).
 
 The model only acts with ``enable_noise``; it takes precedence over ``noise_data``.
+
+Colour (wfs_set_noise_colour).  Two optional keys turn the white sequences into coloured, channel-correlated noise while
+keeping the value a function of (seed, channel, absolute sample index):
+
+* ``'taps'``: FIR taps, a float array ``[L]`` for all channels or ``[n_channels][L]``, 1 <= L <= 16.  The channel's noise becomes
+  ``sum_k h[k] w(ch, t - k)``.  The taps are used as given, quantised with ``round(h * 65536)``: no hidden normalisation, see
+  ``unit_power`` and ``taps_from_psd``;
+* ``'common'``: ``{'groups': int[n_channels] (-1: none), 'gain': number | [n_channels], 'sigma': number | [n_groups]}`` or, in place
+  of ``'sigma'``, ``'pmf': [n_groups][n_values]`` on the model's ``vmin``; optional ``'taps'``: ``[L']`` or ``[n_groups][L']``.  Every
+  group has one white common stream c(g, t); a channel of group g adds ``gain * sum_k h_c[k] c(g, t - k)``: the coherent part of the
+  channels of one digitiser board.  With ``'sigma'`` for channels and groups the Gaussians are built together and share ``half``.
+
+Tap rows shorter than the longest are zero-padded.  The sum is rounded to the nearest integer (half up), so the variance of a channel is
+
+    Var ~ Var_w * sum h^2 + gain^2 * Var_c * sum h_c^2 + 1/12
+
+with Var_w, Var_c the variances of the channel's and the group's distributions.  The arithmetic is exact in integers (Q16 taps); a
+model is refused unless ``sum |h_q| * max |value| < 2^29`` for every row of taps.
 """
 import math
 
 import numpy as np
 
 MAX_VALUES = 4096           # wfs_set_noise_model
+MAX_TAPS = 16               # wfs_set_noise_colour
+Q16 = 65536
 SUM_TOLERANCE = 1e-9
 
 
@@ -88,7 +108,13 @@ def noise_pmf(config, n_rows):
         sigma = np.asarray(m['sigma'], dtype=np.float64)
         if sigma.ndim == 0:
             sigma = np.full(len(config['gains']), float(sigma))
-        pmf, vmin = gaussian_pmf(sigma)
+        common = m.get('common')
+        if isinstance(common, dict) and 'sigma' in common and sigma.ndim == 1:
+            # channels and common streams in one call: one half, one vmin (noise_colour takes the groups' rows from the same call)
+            pmf, vmin = gaussian_pmf(np.concatenate([sigma, _group_sigmas(common, len(sigma))]))
+            pmf = pmf[:len(sigma)]
+        else:
+            pmf, vmin = gaussian_pmf(sigma)
     else:
         if 'vmin' not in m:
             raise ValueError("noise_model: 'pmf' needs 'vmin'")
@@ -114,3 +140,141 @@ def pmf_from_samples(noise_data):
         pmf[c] = np.bincount(a[:, c] - vmin, minlength=n_val) / a.shape[0]
     check_pmf(pmf, vmin)
     return dict(pmf=pmf, vmin=vmin)
+
+
+# ---------------------------------------------------------------------------------------------------- colour
+def _n_groups(common, n_channels):
+    if not isinstance(common, dict) or 'groups' not in common or 'gain' not in common or ('sigma' in common) == ('pmf' in common):
+        raise ValueError("noise_model['common'] must be a dict with 'groups', 'gain' and either 'sigma' or 'pmf'")
+    g = np.asarray(common['groups'])
+    if g.ndim != 1 or len(g) != n_channels or g.dtype.kind not in 'iu':
+        raise ValueError(f"noise_model['common']['groups'] must be an integer array [{n_channels}] (-1: no group)")
+    if g.min() < -1:
+        raise ValueError("noise_model['common']['groups']: entries below -1")
+    return int(g.max()) + 1
+
+
+def _group_sigmas(common, n_channels):
+    n_groups = _n_groups(common, n_channels)
+    s = np.asarray(common['sigma'], dtype=np.float64)
+    if s.ndim == 0:
+        s = np.full(n_groups, float(s))
+    if s.ndim != 1 or len(s) != n_groups:
+        raise ValueError(f"noise_model['common']['sigma'] must be a number or an array [{n_groups}] (one per group)")
+    return s
+
+
+def _tap_rows(taps, n_rows, name):
+    t = np.asarray(taps, dtype=np.float64)
+    if t.ndim == 1:
+        t = np.tile(t, (n_rows, 1))
+    if t.ndim != 2 or t.shape[0] != n_rows or t.shape[1] < 1:
+        raise ValueError(f'{name} must be a float array [L] or [{n_rows}][L]')
+    if t.shape[1] > MAX_TAPS:
+        raise ValueError(f'{name}: {t.shape[1]} taps, more than {MAX_TAPS}')
+    if not np.all(np.isfinite(t)):
+        raise ValueError(f'{name} must be finite')
+    return t
+
+
+def quantise_taps(taps):
+    """round(h * 65536) as int64 (the caller checks the range)"""
+    return np.floor(np.asarray(taps, dtype=np.float64) * Q16 + 0.5).astype(np.int64)
+
+
+def check_colour(taps_q, group, mix_q, common_pmf, n_channels, n_values, vmin):
+    """validates what wfs_set_noise_colour validates, with the argument named; returns the arrays in the dtypes of the C ABI"""
+    taps_q = np.asarray(taps_q, dtype=np.int64)
+    group, mix_q = np.asarray(group, dtype=np.int64), np.asarray(mix_q, dtype=np.int64)
+    common_pmf = np.asarray(common_pmf, dtype=np.float64).reshape(-1, n_values)
+    n_groups = common_pmf.shape[0]
+    if taps_q.ndim != 2 or taps_q.shape[0] != n_channels + n_groups:
+        raise ValueError(f'noise colour: taps_q must be [{n_channels + n_groups}][n_taps] (channels, then common streams)')
+    if taps_q.shape[1] < 1 or taps_q.shape[1] > MAX_TAPS:
+        raise ValueError(f'noise colour: n_taps {taps_q.shape[1]} outside 1 .. {MAX_TAPS}')
+    vmax = max(abs(int(vmin)), abs(int(vmin) + int(n_values) - 1))
+    bound = np.abs(taps_q).sum(axis=1) * vmax
+    bad = np.where(bound >= 2 ** 29)[0]
+    if len(bad):
+        raise ValueError(f'noise colour: taps_q of row {int(bad[0])}: sum |taps| * max |value| = {int(bound[bad[0]])} reaches 2^29')
+    if group.shape != (n_channels,) or mix_q.shape != (n_channels,):
+        raise ValueError(f'noise colour: group and mix_q must be [{n_channels}]')
+    bad = np.where((group < -1) | (group >= n_groups))[0]
+    if len(bad):
+        raise ValueError(f'noise colour: group of channel {int(bad[0])} outside -1 .. {n_groups - 1}')
+    bad = np.where(np.abs(mix_q) > Q16)[0]
+    if len(bad):
+        raise ValueError(f'noise colour: mix_q of channel {int(bad[0])} beyond {Q16} in magnitude (|gain| > 1)')
+    if not np.all(common_pmf >= 0):
+        raise ValueError('noise colour: common_pmf has a negative entry')
+    bad = np.where(np.abs(common_pmf.sum(axis=1) - 1.0) > SUM_TOLERANCE)[0]
+    if len(bad):
+        raise ValueError(f'noise colour: common_pmf of group {int(bad[0])} does not sum to 1')
+    return (np.ascontiguousarray(taps_q, dtype=np.int32), np.ascontiguousarray(group, dtype=np.int32),
+            np.ascontiguousarray(mix_q, dtype=np.int32), np.ascontiguousarray(common_pmf))
+
+
+def noise_colour(config, n_rows):
+    """dict(taps_q int32[n_channels + n_groups][L], group int32[n_channels], mix_q int32[n_channels], common_pmf f64[n_groups][n_values])
+    from the 'taps' and 'common' keys of ``config['noise_model']``, or None when it has neither (a white model, or no model)"""
+    m = config.get('noise_model')
+    if not isinstance(m, dict) or ('taps' not in m and 'common' not in m):
+        return None
+    pmf, vmin = noise_pmf(config, n_rows)
+    n_ch, n_val = pmf.shape
+    taps = _tap_rows(m['taps'], n_ch, "noise_model['taps']") if 'taps' in m else np.ones((n_ch, 1))
+    group, mix_q, common_pmf, ctaps = np.full(n_ch, -1, dtype=np.int64), np.zeros(n_ch, dtype=np.int64), np.zeros((0, n_val)), np.zeros((0, 1))
+    common = m.get('common')
+    if common is not None:
+        n_groups = _n_groups(common, n_ch)
+        group = np.asarray(common['groups'], dtype=np.int64)
+        gain = np.asarray(common['gain'], dtype=np.float64)
+        gain = np.full(n_ch, float(gain)) if gain.ndim == 0 else gain
+        if gain.shape != (n_ch,) or not np.all(np.isfinite(gain)):
+            raise ValueError(f"noise_model['common']['gain'] must be a number or an array [{n_ch}]")
+        mix_q = np.where(group >= 0, quantise_taps(gain), 0)
+        if 'sigma' in common:
+            if 'sigma' not in m:
+                raise ValueError("noise_model['common']['sigma'] needs the channels given by 'sigma' too (with a 'pmf' give the groups a 'pmf')")
+            sigma = np.asarray(m['sigma'], dtype=np.float64)
+            sigma = np.full(n_ch, float(sigma)) if sigma.ndim == 0 else sigma
+            both, vmin_c = gaussian_pmf(np.concatenate([sigma, _group_sigmas(common, n_ch)]))
+            assert vmin_c == vmin and both.shape[1] == n_val
+            common_pmf = both[n_ch:]
+        else:
+            common_pmf = np.asarray(common['pmf'], dtype=np.float64)
+            if common_pmf.ndim != 2 or common_pmf.shape != (n_groups, n_val):
+                raise ValueError(f"noise_model['common']['pmf'] must be [{n_groups}][{n_val}] (one row per group, on the model's values)")
+        ctaps = _tap_rows(common['taps'], n_groups, "noise_model['common']['taps']") if 'taps' in common else np.ones((n_groups, 1))
+    L = max(taps.shape[1], ctaps.shape[1])
+    rows = np.zeros((n_ch + len(ctaps), L), dtype=np.float64)
+    rows[:n_ch, :taps.shape[1]] = taps
+    rows[n_ch:, :ctaps.shape[1]] = ctaps
+    taps_q, group, mix_q, common_pmf = check_colour(quantise_taps(rows), group, mix_q, common_pmf, n_ch, n_val, vmin)
+    return dict(taps_q=taps_q, group=group, mix_q=mix_q, common_pmf=common_pmf)
+
+
+def unit_power(taps):
+    """the taps, every row scaled to sum h^2 = 1: the filtered sequence keeps the variance of the white one"""
+    t = np.asarray(taps, dtype=np.float64)
+    p = np.sqrt((t * t).sum(axis=-1, keepdims=True))
+    if np.any(p == 0):
+        raise ValueError('unit_power: a row of zeros')
+    return t / p
+
+
+def taps_from_psd(freqs_hz, psd, n_taps, dt_ns=10):
+    """Linear-phase FIR taps whose power response follows a measured power spectral density (frequency sampling): sqrt(psd) is
+    interpolated onto the n_taps-point rFFT grid k / (n_taps * dt), taken as a zero-phase amplitude response, inverted and rotated to
+    the causal, symmetric form; the taps are scaled to unit power.  At the grid frequencies |H|^2 is the (scaled) psd exactly."""
+    n_taps = int(n_taps)
+    if n_taps < 1 or n_taps > MAX_TAPS:
+        raise ValueError(f'taps_from_psd: n_taps outside 1 .. {MAX_TAPS}')
+    f, p = np.asarray(freqs_hz, dtype=np.float64), np.asarray(psd, dtype=np.float64)
+    if f.ndim != 1 or f.shape != p.shape or len(f) < 1 or np.any(np.diff(f) <= 0) or np.any(p < 0) or not np.all(np.isfinite(p)):
+        raise ValueError('taps_from_psd: freqs_hz must be increasing, psd non-negative and of the same length')
+    grid = np.fft.rfftfreq(n_taps, d=float(dt_ns) * 1e-9)
+    amp = np.sqrt(np.interp(grid, f, p))
+    h = np.fft.irfft(amp, n=n_taps)                 # zero phase: real, symmetric about index 0
+    h = np.roll(h, (n_taps - 1) // 2)               # a circular shift: the same magnitudes at the grid frequencies
+    return unit_power(h)
