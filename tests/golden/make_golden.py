@@ -8,6 +8,7 @@ Run once in the build container (needs /root/reference; the GPU box never runs t
     python tests/golden/make_golden.py pulse_edges                    # so does this one: the reference on designed photon lists
     python tests/golden/make_golden.py window_edges                   # and this one: the reference on designed instruction spacings
     python tests/golden/make_golden.py zle_edges                      # and this one: the reference on rows designed through the noise table
+    python tests/golden/make_golden.py spe_channels                   # and this one: the reference on per-channel SPE columns
 
 The reference's hot-path modules are imported under the stubs of ``_ref_stubs.py`` (identity njit, so
 every draw comes from numpy's seeded global generator).  What is written is DATA only: inputs and
@@ -955,6 +956,96 @@ def fixture_zle_edges(ref):
         json.dump(cfgs, f, indent=0, sort_keys=True)
 
 
+def run_spe_channels(ref, family, seed):
+    """run_pulse_edges' route with the gains left to the reference: per case one Pulse.__call__ on a designed photon list WITHOUT
+    _photon_gains (pulse.py:53-56 draws the transit times, :97-103 the gains through uniform_to_pe_arr(p, channel)), per group one
+    digitize_pulse_cache() + ZLE(), all under the Recorder.  The columns go in as a CSV, as a real SPE file does.  Returns the flat
+    arrays, the reference's table and the charge axis as the reference parsed it."""
+    from tests import spe_channels as SC
+    csv = SC.write_csv(family, TMP + f'/spe_channels_{family}.csv', SC.N_WIDE)
+    csv494 = SC.write_csv(family, TMP + f'/spe_channels_{family}_494.csv', SC.N_TPC)
+    tables, pulses = {}, {}
+    for key, path, p_dpe in [('wide', csv, None), ('tpc', csv494, None), ('dpe', csv494, SC.P_DPE_HIGH)]:
+        ref.load_resource._cached_configs.clear()
+        ref.pulse._cached_pmt_current_templates.clear()
+        ref.pulse._cached_uniform_to_pe_arr.clear()
+        config = base_config(photon_area_distribution=path, gains=SC.gains(N_TPC), enable_noise=False)
+        if p_dpe is not None:
+            config['p_double_pe_emision'] = p_dpe
+        pulses[key] = ref.pulse.Pulse(config)
+        tables[key] = np.array(pulses[key]._Pulse__uniform_to_pe_arr)
+        shapes = pulses[key].resource.photon_area_distribution
+        charge = shapes['charge'].values.astype(np.float64)
+        parsed = np.stack([shapes[k].values.astype(np.float64) for k in shapes.columns[1:]])
+        # the rule rebuilds the columns the reference read; the charge axis comes back from the CSV an ulp off on a few bins and is stored as parsed
+        assert np.array_equal(parsed, SC.pdfs(family, len(parsed))) and np.allclose(charge, SC.charge_axis()[0], rtol=1e-15, atol=0)
+    assert tables['wide'].shape == (SC.N_WIDE, SC.N_GRID) and np.array_equal(tables['wide'][:N_TPC], tables['tpc'])
+    assert np.array_equal(tables['dpe'], tables['tpc'])
+    SC.assert_design(family, SC.pdfs(family, SC.N_WIDE), tables['wide'], charge)
+    rd = ref.rawdata.RawData(dict(pulses['tpc'].config))
+    rd._pulses_cache = []
+    rec = Recorder(ref)
+    rec.install()
+    np.random.seed(seed)
+    cases = SC.reference_cases(N_TPC, int(pulses['tpc'].config.get('sample_duration', 10)))
+    try:
+        for gi in range(len(SC.GROUPS)):
+            for case in cases:
+                if case['group'] != gi:
+                    continue
+                pulse = pulses['tpc' if case['p_dpe'] is None else 'dpe']
+                pulse.__dict__.pop('_photon_gains', None)
+                pulse._photon_timings = np.concatenate([t for t, _, _ in case['tiles']]).astype(np.int64)
+                pulse._photon_channels = np.concatenate([np.full(len(t), c, dtype=np.int64) for t, _, c in case['tiles']])
+                assert np.all(np.diff(pulse._photon_channels) >= 0)
+                pulse()
+                assert not rec.calls[-1]['has_gains']
+                rd._pulses_cache += pulse._pulses
+            rd.digitize_pulse_cache()
+            for c, left, right, data in rd.ZLE():
+                rec.zle.append((len(rec.digits) - 1, int(c), int(left), int(right), np.array(data, dtype=np.int64)))
+    finally:
+        rec.uninstall()
+    assert len(rec.digits) == len(SC.GROUPS)
+    out = dict(seed=np.int64(seed))
+    flatten_recorder(rec, out)
+    out['set_cluster'] = np.array([c['group'] for c in cases], dtype=np.int32)
+    out['set_tmin'] = np.array([int(out['ph_t'][a:b].min()) for a, b in zip(out['call_ph_off'][:-1], out['call_ph_off'][1:])], dtype=np.int64)
+    out['case_names'] = np.array([c['name'] for c in cases])
+    out['call_case'] = np.arange(len(cases), dtype=np.int32)
+    out['group_names'] = np.array(SC.GROUPS)
+    out['call_group'] = out['set_cluster'].copy()
+    out['call_p_dpe'] = np.array([float(pulses['tpc' if c['p_dpe'] is None else 'dpe'].config['p_double_pe_emision']) for c in cases])
+    for k in ['e_t', 'call_e_off', 'dg_sum_min', 'dg_sum_total']:
+        del out[k]
+    # the design, on what the reference did: every channel hit, the marked ones at least 50 times, double PEs plentiful
+    hit = np.bincount(out['ph_ch'], minlength=N_TPC)
+    assert hit.min() >= 1 and all(hit[c] >= 50 for c in SC.SPECIAL + SC.EDGE_CHANNELS)
+    a, b = out['call_ph_off'][-2:]
+    assert out['ph_dpe'][a:b].mean() > 0.5 and out['ph_dpe'][:a].any()
+    out['table'] = tables['wide']
+    out['charge'] = charge
+    return out
+
+
+def fixture_spe_channels(ref):
+    """spe_channels.npz: per family of per-channel SPE columns (tests/spe_channels.py) the reference's table for 500 columns and its
+    Pulse calls on designed photon lists with the gains drawn by the reference, under '<family>/<name>'"""
+    from tests import spe_channels as SC
+    out = dict(families=np.array(SC.FAMILIES))
+    for i, family in enumerate(SC.FAMILIES):
+        r = run_spe_channels(ref, family, 7100 + i)
+        for k, v in r.items():
+            out[f'{family}/{k}'] = v
+        print(family, 'calls', len(r['call_kind']), 'photons', len(r['ph_t']), 'double PE', int(r['ph_dpe'].sum()), 'channels hit',
+              len(np.unique(r['ph_ch'])), 'pulses', len(r['pl_ch']), 'rows', len(r['row_ch']), 'intervals', len(r['zle_ch']))
+    np.savez_compressed(HERE + '/spe_channels.npz', **out)
+    with open(HERE + '/spe_channels_config.json', 'w') as f:
+        json.dump(dict(gains=SC.gains(N_TPC).tolist(), p_double_pe_emision_high=SC.P_DPE_HIGH, n_columns=SC.N_WIDE,
+                       special_columns=dict(zero=SC.ZERO_CH, first_positive_bin=SC.FIRST_CH, last_bin=SC.LAST_CH, gain_zero=SC.DEAD_CH)),
+                  f, indent=0, sort_keys=True)
+
+
 class StubDelayHist:
     """stand-in for the multihist.Hist1d the reference loads as uniform_to_ele_ap (private resource): the members
     afterpulse.py touches -- n, bin_centers, get_random (bin by content, uniform inside the bin)"""
@@ -1536,7 +1627,7 @@ def fixture_chain_stats(ref):
 if __name__ == '__main__':
     which = sys.argv[1:] or ['tables', 'add_current', 'chains', 'dists', 'models', 'stats', 'chunker', 'ele_ap_draws', 'gas_gap', 'aft_sigma', 'noise_float', 'diffusion', 'frontend']
     ref = import_reference_interface() if ('chunker' in which or 'frontend' in which) else import_reference()
-    own = {'optical_chain', 'pmt_ap_draws', 'pulse_edges', 'window_edges', 'zle_edges'}           # these write their own files only
+    own = {'optical_chain', 'pmt_ap_draws', 'pulse_edges', 'window_edges', 'zle_edges', 'spe_channels'}           # these write their own files only
     p = fixture_tables(ref) if set(which) - own else None
     if 'optical_chain' in which:
         fixture_chain_optical(ref)
@@ -1548,6 +1639,8 @@ if __name__ == '__main__':
         fixture_window_edges(ref)
     if 'zle_edges' in which:
         fixture_zle_edges(ref)
+    if 'spe_channels' in which:
+        fixture_spe_channels(ref)
     if 'add_current' in which:
         fixture_add_current(ref, p)
     if 'chains' in which:

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from tests.helpers import ap_tables_from_golden, make_engine, make_oracle
-from tests.test_gpu_generation import MS, _compare, _instructions
+from tests.test_gpu_generation import MS, _assert_truth_rows, _compare, _instructions
 from wfsim_amd import tables as T
 from wfsim_amd.config import N_ROWS, current_2_adc, xenonnt_test_config
 from wfsim_amd.physics import instruction_params
@@ -85,15 +85,6 @@ def _oracle_truth_per_pmt(cfg, o, call, ch):
     return np.array([n, n + n_dpe, above.sum(), above.sum() + above[:n_dpe].sum(), gain.sum() / G, gain[above].sum() / G])
 
 
-def _assert_truth_rows(eng, o):
-    acc, ts = eng.truth()
-    tr = o['truth'].reshape(-1, 12)
-    assert len(acc) == len(tr)
-    for k in range(len(tr)):
-        kk = int(np.argmin(np.abs(acc[:, 0] - tr[k, 0])))          # (sets are matched by their photon number)
-        assert np.allclose(acc[kk], tr[k], rtol=1e-9), (k, acc[kk], tr[k])
-
-
 THREE_SIZES = [dict(type=2, time=MS, x=0, y=0, z=-8, amp=6000), dict(type=2, time=3 * MS, x=1, y=1, z=-20, amp=900),
                dict(type=1, time=5 * MS, x=0, y=0, z=-30, amp=2000)]
 THREE_SIZES_PATTERN = {17: 0.05, 300: 0.01}          # the first S2 then holds tiles of ~22000, ~4400 and ~900 photons
@@ -117,7 +108,7 @@ def test_bright_tiles_take_the_fused_kernel(monkeypatch):
     assert (kind == 3).sum() == 3 and kind[0, 17] == kind[0, 300] == kind[1, 17] == 3 and (kind == 1).sum() > 900      # (the small S2 holds ~3300 photons on channel 17)
     assert kt['k_s2_bright'][1] == 1 and 'k_s2_tile' in kt and 'k_s2_tile_gen' not in kt and 'k_pulse_dense' not in kt, sorted(kt)
     _compare(orc, o, eng, counts, s_ins)
-    _assert_truth_rows(eng, o)
+    _assert_truth_rows(eng, o, s_ins)
     per_pmt = eng.truth_per_pmt()
     for ch in (17, 300, 5):          # (channel 5: a tile of k_s2_tile next to them)
         ref = _oracle_truth_per_pmt(eng.config, o, 0, ch)
@@ -140,7 +131,7 @@ def test_pass_boundaries():
     assert np.array_equal(kind, _expected_kinds(s_ins, _tile_photons(eng, len(s_ins))))
     assert (kind == 3).sum() == len(amps) and set(np.where(kind == 3)[1]) == {17}
     _compare(orc, o, eng, counts, s_ins)
-    _assert_truth_rows(eng, o)
+    _assert_truth_rows(eng, o, s_ins)
 
 
 def test_fallback_by_the_fit_rule(monkeypatch):
@@ -161,7 +152,7 @@ def test_fallback_by_the_fit_rule(monkeypatch):
     assert np.all(kind[0][bright[0]] == 3) and np.all(kind[1][bright[1]] == 2), (kind[0][bright[0]], kind[1][bright[1]])
     assert np.all(kind[~bright & (n_tile > 0) & (s_ins['type'] == 2)[:, None]] == 1)
     _compare(orc, o, eng, counts, s_ins)
-    _assert_truth_rows(eng, o)
+    _assert_truth_rows(eng, o, s_ins)
     first = eng.records().tobytes()
     monkeypatch.setenv('WFS_BRIGHT_MAX_BINS', '0')
     _, _, eng0, _, _ = _run(cfg, rows, p, oracle=False)
@@ -183,7 +174,7 @@ def test_bright_tiles_sharing_a_row():
     kt = eng.kernel_times()
     assert 'k_tile_add' in kt and 'k_s2_bright' in kt and 'k_s2_tile_gen' not in kt, sorted(kt)
     _compare(orc, o, eng, counts, s_ins)
-    _assert_truth_rows(eng, o)
+    _assert_truth_rows(eng, o, s_ins)
 
 
 # (the cases of the default route keep the ids they had before the second parameter)
@@ -213,7 +204,7 @@ def test_pmt_afterpulses_of_bright_tiles(scale, tile_local_bright):
     ap_hot = int(np.sum(ph['ch'][ph['set_off'][n + big]:ph['set_off'][n + big + 1]] == 17))
     assert ap_hot > 128, ap_hot          # (afterpulses of the hot tile alone: more than the stage holds)
     _compare(orc, o, eng, counts, s_ins)
-    _assert_truth_rows(eng, o)
+    _assert_truth_rows(eng, o, s_ins)
 
 
 @pytest.mark.parametrize('fma', [True, False])
@@ -257,4 +248,4 @@ def test_per_instruction_model_tables():
     kind = eng.tile_kernels()
     assert (kind == 3).sum() == 4 and np.all(kind[s_ins['type'] == 2][:, [17, 300]] == 3)
     _compare(orc, o, eng, counts, s_ins)
-    _assert_truth_rows(eng, o)
+    _assert_truth_rows(eng, o, s_ins)

@@ -51,18 +51,15 @@ def _run_both(cfg, ins, seed=7, ap=None):
     return orc, o, eng, counts, s_ins
 
 
-def _compare(orc, o, eng, counts, s_ins):
-    # ---- photons per pulse set (oracle runs S1s before S2s inside a cluster; sets are matched by instruction)
-    ph = eng.photons()
-    assert counts['n_photons'] == len(o['ph_t'])
-    # oracle call -> sorted instruction index: calls are in processing order; run-set id increases with it
+def _call_sets(o, s_ins, config):
+    """device pulse set of every oracle call.  Calls are in processing order (the oracle runs S1s before S2s inside a cluster): per
+    instruction its primary call, then (PMT afterpulses on and photons present) a kind-3 call; device sets: instruction i and, for its
+    afterpulses, n_ins + i"""
     from wfsim_amd.scheduler import processing_order
     # the oracle received sorted instructions, so 'order' is the identity
-    cluster = schedule(s_ins, eng.config)[2]
+    cluster = schedule(s_ins, config)[2]
     proc = processing_order(s_ins, np.arange(len(s_ins)), cluster)
     n_ins = len(s_ins)
-    # oracle calls: per instruction its primary call, then (PMT afterpulses on and photons present) a kind-3 call;
-    # device sets: instruction i and, for its afterpulses, n_ins + i
     sets, it = [], iter(proc)
     for kind in o['call_kind']:
         if kind != 3:
@@ -70,7 +67,28 @@ def _compare(orc, o, eng, counts, s_ins):
             sets.append(cur)
         else:
             sets.append(n_ins + cur)
-    assert len(sets) == len(o['call_kind'])
+    assert len(sets) == len(o['call_kind']) and len(set(sets)) == len(sets)
+    return sets
+
+
+def _assert_truth_rows(eng, o, s_ins):
+    """the 12 truth columns of every oracle call against the device row of ITS pulse set (one to one, by set index); a set without a
+    call holds nothing"""
+    acc, ts = eng.truth()
+    tr = o['truth'].reshape(-1, 12)
+    sets = _call_sets(o, s_ins, eng.config)
+    assert len(tr) == len(sets) and max(sets) < len(acc)
+    for k, i in enumerate(sets):
+        assert np.allclose(acc[i], tr[k], rtol=1e-9), (k, i, acc[i], tr[k])
+    assert not acc[np.setdiff1d(np.arange(len(acc)), sets)].any()
+
+
+def _compare(orc, o, eng, counts, s_ins):
+    # ---- photons per pulse set (sets are matched by instruction)
+    ph = eng.photons()
+    assert counts['n_photons'] == len(o['ph_t'])
+    n_ins = len(s_ins)
+    sets = _call_sets(o, s_ins, eng.config)
     if 3 in o['call_kind']:
         assert counts['n_pulse_sets'] == 2 * n_ins and (o['call_kind'] == 3).sum() > 0
     for k, i in enumerate(sets):
@@ -322,12 +340,7 @@ def test_bright_tiles_next_to_ordinary_ones(afterpulses):
     per_channel = np.bincount(o['ph_ch'][o['call_ph_off'][0]:o['call_ph_off'][1]], minlength=494)
     assert per_channel[17] > 20000 and 2048 < per_channel[300] < 10000 and np.median(per_channel) < 2048
     _compare(orc, o, eng, counts, s_ins)
-    acc, ts = eng.truth()
-    tr = o['truth'].reshape(-1, 12)
-    assert len(acc) == len(tr)
-    for k in range(len(tr)):
-        kk = int(np.argmin(np.abs(acc[:, 0] - tr[k, 0])))          # (sets are matched by their photon number)
-        assert np.allclose(acc[kk], tr[k], rtol=1e-9), (k, acc[kk], tr[k])
+    _assert_truth_rows(eng, o, s_ins)
 
 
 def test_prepass_counts_and_photon_times_of_tile_generated_instructions():
