@@ -114,6 +114,12 @@ int wfs_set_ap_element(wfs_handle *h, int32_t element, int32_t n_bins_delay, int
                        const double *delay_cdf, const double *amp_cdf);
 
 /* ---- batch input ------------------------------------------------------------------------------------- */
+/* A handle holds one batch: the one the last successful wfs_load_instructions, wfs_load_photons or wfs_load_optical call
+ * described.  Each of the three replaces the batch before it as a whole: its kind, its sizes, every per-instruction option
+ * (wfs_set_instruction_*, wfs_eval_pattern_rows) and the results of its last run.  A load that returns an error after its
+ * argument checks (a value out of range inside the arrays, a failed upload) leaves the handle with NO batch, not with the one
+ * before: wfs_run and the per-instruction setters then return WFS_E_STATE ("no batch loaded") until a load succeeds.  A call that
+ * is refused for a null or empty argument, or before wfs_set_tables, touches nothing. */
 /* One batch of primary instructions (host pointers; SoA because instruction_dtype is a packed 70-byte record
  * with an unaligned int64, strax_interface.py:25-42).  Sorted by the scheduler key; cluster[] non-decreasing.
  *   type i8, time i64, amp i32               instruction fields
@@ -289,6 +295,11 @@ int wfs_gather_photon_times(wfs_handle *h, int64_t n, const int64_t *index, int6
 int wfs_copy_truth_per_pmt(wfs_handle *h, double *acc6, int64_t cap);
 
 /* ---- results (host copies) ---------------------------------------------------------------------------- */
+/* Every copy-out returns WFS_E_STATE until wfs_run has come to its end for the loaded batch, and again after a per-instruction
+ * option of the batch or the delay tables changed.  wfs_copy_groups, wfs_copy_intervals, wfs_copy_rows, wfs_copy_row_data and
+ * wfs_copy_sum_signal are decoded with the row layout of the device view (row slots per window, HE rows, sum channel, noise
+ * channels): when a wfs_set_* call changes that layout after the run (wfs_set_tables, wfs_set_noise_float, wfs_set_noise_model,
+ * wfs_set_sum_signal), these five return WFS_E_STATE until the next wfs_run; the others still read the last run. */
 /* raw_records, 244-byte packed strax layout, in the order the reference yields them (group, channel, interval,
  * fragment); dst may be a host or a device pointer (wfs_copy_records_dev). */
 int wfs_copy_records(wfs_handle *h, void *dst_host, int64_t capacity_records);

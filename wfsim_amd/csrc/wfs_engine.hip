@@ -7,6 +7,7 @@
 #include "wfs_tilegen.h"
 #include "wfs_boundary.h"
 #include "wfs_devbuf.h"
+#include "wfs_batch.h"
 #include "../../include/wfsim_amd.h"
 
 // Every pulse kernel exists in two forms: FMA = true (wfs_config.fma, one rounding per template * gain term) and FMA = false (numpy's two
@@ -51,7 +52,7 @@ inline void clear_times(std::vector<KernelTime> &times)
     times.clear();
 }
 
-// bits of wfs_set_debug (wfs_handle::keep_currents); include/wfsim_amd.h documents them by number
+// bits of wfs_set_debug (wfs_handle::debug_bits); include/wfsim_amd.h documents them by number
 enum : int {
     DBG_CURRENTS = 1,            // keep the f64 tile currents and the finished rows
     DBG_FORCE_DENSE = 2,         // every tile to the dense pulse kernel
@@ -67,26 +68,73 @@ static int wfs_dev_alloc(void **p, size_t bytes) { return (int)hipMalloc(p, byte
 static void wfs_dev_free(void *p) { (void)hipFree(p); }
 
 struct wfs_handle {
-    wfs_config cfg;
+    // ---------------- the handle: written by wfs_create and the wfs_set_* calls, kept until wfs_destroy; no load and no run resets it
+    // device and streams
     int device = 0, n_cus = 256;
     hipStream_t stream = nullptr; bool own_stream = false;
-    std::string err;
-    WfsDev dev;
-    bool tables_set = false, batch_loaded = false, injected = false, optical = false, ran = false;
-    DevBuf set_gid, opt_t, opt_item, opt_first, opt_last, opt_ch, opt_time;
-    int keep_currents = 0, profiling = 0;
+    WfsScal *h_scal = nullptr;        // host copy of scal in page-locked memory: read_scal's copy needs no staging buffer (five of them per batch)
+    // step boundaries that publish (read_scal): h_scal is mapped and coherent, k_publish copies the block into it and stores the
+    // sequence number of the boundary into the word on the cache line behind it; the host spins on that word (wfs_boundary.h)
+    bool publish = false;             // false: the copy + synchronise path (the mapped allocation failed, or WFS_HOST_SYNC=copy)
+    uint64_t *h_seq = nullptr; u64 *d_hseq = nullptr, seq = 0; WfsScal *d_hscal = nullptr;
+    i64 zero64 = 0;                   // host source of the one value an empty scan uploads (scan_into)
+    std::string err, launch_err; // wfs_last_error; first failed launch of the current call (wfs_set_debug bit 3: every launch is checked)
+    int n_fail = 0;             // calls of fail(): a FillGroup that dies with segments checks that an error return is why
+    int fail(int code, const std::string &msg) { err = msg; n_fail++; return code; }
+
+    // config and device view: dev is what the kernels see, rebuilt from cfg and the switches below by refresh_dev
+    wfs_config cfg; WfsDev dev;
+    bool generic_geom = false;            // sample_duration / template length other than 10 ns / 22 samples: k_pulse_generic for every tile
     i32 res_env = -1;                // WFS_ROW_RESIDENT=0/1 overrides the config switch (A/B runs)
     i32 res_max_len = 1024;          // segment of a resident row (k_row_pulse: 4 bytes of LDS per sample and wave; longer rows take several); WFS_RES_MAX_LEN overrides
-    bool gen_done = false;
-    bool gen_order_ready = false;          // host tables of the generation order (gen_order_tables), valid for the current generation
-    std::vector<i64> go_off, go_block0; std::vector<i32> go_fused, go_tile_count;
-    GenArgs gen_args{};           // the generator's view of the batch (kept for wfs_gather_photon_times)
-    int carry_has = 0; i64 carry_runmax = 0;
-    // tables
-    DevBuf t_templates, t_spe, t_gains, t_thr_truth, t_thr_zle, t_lumx, t_lumt, t_noise, t_noise_f;
+    int tap_sparse_max = 48;     // tap_block: occupied cells up to which a wave of the dense pulse kernels walks them (WFS_TAP_SPARSE_MAX)
+    i32 bright_lds = 0, bright_max_bins = 0;      // LDS a bright tile may take for H table + ballots (device grant, BRIGHT_LDS_MAX); start bins (WFS_BRIGHT_MAX_BINS)
+    bool bright_on = true, sum_on = false, sort_records = false;      // wfs_set_bright_tiles, wfs_set_sum_signal (one more row slot per window), wfs_set_record_order
+    int carry_has = 0; i64 carry_runmax = 0, n_noise_override = 0;    // wfs_set_window_carry; wfs_set_noise_offsets
+
+    // tables, maps and noise
+    bool tables_set = false;
+    std::vector<double> h_templates, h_gains, h_lum_x, h_lum_t;      // host copies: [dt][tlen]; per channel; the luminescence table (enters the S2 delay table)
     ApElem ap[WFS_MAX_AP];
-    // instructions
-    i64 n_ins = 0, n_psets = 0, n_sets = 0, n_clusters = 0, n_emitters = 0, n_photons = 0, n_tiles = 0;
+    // model variants of the photon delays
+    std::vector<DevBuf> x_alias; std::vector<AliasTab> h_tabs; i32 n_user_tabs = 0;
+    std::vector<Pmf> base_pmf;           // transit time only, S1 terms, S2 terms, S2 terms without the 'simple' luminescence
+    i32 prop_nz = 0, prop_nu = 0; double prop_u0 = 0, prop_du = 1;      // wfs_set_s1_propagation
+    i32 gg_n = 0, gg_L = 0;              // 'garfield_gas_gap' luminescence (wfs_set_gas_gap_model)
+    // pattern maps evaluated on the device
+    struct PatternMap { bool set = false; i32 dims = 0, n[3] = {1, 1, 1}, w[3] = {0, 0, 0}, n_map_ch = 0; double lo[3] = {0, 0, 0}, hgrid[3] = {1, 1, 1}; DevBuf values;
+                        i64 n_points = 0; DevBuf points;
+                        DevBuf cell_start, cell_pts; i32 cnx = 0, cny = 0; double cell_lo[2] = {0, 0}, cell_h = 1; } pmap[2];       // 2-D point lists: cell index (transverse diffusion)
+    // scalar maps (kind 0: weighted nearest neighbours on a regular grid, 1: on a point list, 2: RectBivariateSpline)
+    struct ScalarMap { int kind = 0; int nv = 1; PatternMap g; i32 nx = 0, ny = 0, kx = 0, ky = 0; DevBuf tx, ty, c; };      // kind 0 / 1: nearest neighbours on a grid / a point list, 2: spline, 3: multilinear grid
+    std::vector<std::unique_ptr<ScalarMap>> smaps;
+    // the noise model (wfs_set_noise_model): alias cells [nm_channels][nm_k] on the device (nm_cells) and on the host; nm_channels 0: no model
+    std::vector<uint2> h_nm_cells; i32 nm_channels = 0, nm_k = 0, nm_shift = 0, nm_vmin = 0, nm_values = 0;
+    // its colour (wfs_set_noise_colour): nc_buf holds taps [nm_channels + nc_groups][NC_TAP_STRIDE] | group [nm_channels] | mix [nm_channels];
+    // the cells of the common streams follow the channels' in nm_cells (h_nm_cells keeps the channels' alone).  nc_n_taps 0: white
+    i32 nc_n_taps = 0, nc_groups = 0;
+    i32 table_channels = 0;           // columns of the noise table (dev.noise_channels counts the model's channels while a model is set)
+
+    // packed records: two arenas used in turn, so that the device -> host copy of one batch (copy stream, pinned host memory)
+    // runs under the kernels of the next batch
+    DevBuf records_ab[2]; int rec_cur = 0; hipStream_t copy_stream = nullptr; hipEvent_t rec_copied[2] = {nullptr, nullptr}; bool rec_pending[2] = {false, false};
+    DevBuf &records_buf() { return records_ab[rec_cur]; }
+
+    // profiling and debug
+    int debug_bits = 0, profiling = 0;      // wfs_set_debug (DBG_*), wfs_set_profiling
+    std::vector<KernelTime> times;
+
+    // ---------------- the loaded batch: reset when a wfs_load_* call begins, filled by that call and the per-instruction setters
+    BatchState batch;
+    // ---------------- the last run: reset when wfs_run begins (and with the batch)
+    RunResult run;
+    // kernel arguments of the last generation (HIP types, hence not in RunResult): written by every generation, read from stage Generated on
+    GenArgs gen_args{}; FuseArgs fuse_args{}; BrightArgs bright_args{};      // (gen_args: kept for wfs_gather_photon_times)
+    BatchRun state() { return BatchRun{batch, run}; }        // the transitions of wfs_batch.h: the only writers of batch.kind and run.stage
+
+    // ---------------- device buffers: capacity, not state.  They grow on demand, free themselves, and no reset touches them
+    DevBuf set_gid, opt_t, opt_item, opt_first, opt_last, opt_ch, opt_time;
+    DevBuf t_templates, t_spe, t_gains, t_thr_truth, t_thr_zle, t_lumx, t_lumt, t_noise, t_noise_f;
     DevBuf ins_type, ins_time, ins_amp, ins_gid, ins_p, ins_dm, ins_ds, ins_sc, ins_cdfrow, cdf_table, chan_alias, em_off, em_zg, ins_embase, ins_set, set_ins_off, set_ins_list;
     DevBuf set_cluster, set_t0, set_mode, cl_tmin, cl_gid, cl_end, cl_group;
     DevBuf em_time, em_nph, em_ins, em_ph_off, el_stat, el_minmax, blk_e, blk_base, blk_cnt, blk_ins, eblk_ins, ins_ph0, blk_desc;
@@ -95,82 +143,21 @@ struct wfs_handle {
     DevBuf grp_lo, grp_hi, grp_left, grp_right, grp_ixrand, grp_gid;
     DevBuf row_lo, row_hi, acc_len, acc_off, itv_cap, itv_off, active_rows, raw;
     DevBuf itv_left, itv_right, itv_n, row_nrec, rec_off;
-    // packed records: two arenas used in turn, so that the device -> host copy of one batch (copy stream, pinned host memory)
-    // runs under the kernels of the next batch
-    DevBuf records_ab[2]; int rec_cur = 0; hipStream_t copy_stream = nullptr; hipEvent_t rec_copied[2] = {nullptr, nullptr}; bool rec_pending[2] = {false, false};
-    DevBuf &records_buf() { return records_ab[rec_cur]; }
     DevBuf truth, tminmax, tile_truth, tile_desc, gather_idx, gather_out, currents, cur_len, cur_off, row_dbg, row_dbg_len, row_dbg_off;
-    DevBuf stamps;
-    DevBuf row_desc, rec_key, rec_key2, rec_val, rec_val2, rec_dest, sort_tmp, scan_tmp, scal, noise_override;
-    bool sort_records = false; i64 n_noise_override = 0;
-    // the noise model (wfs_set_noise_model): alias cells [nm_channels][nm_k] on the device and on the host; nm_channels 0: no model
-    DevBuf nm_cells; std::vector<uint2> h_nm_cells; i32 nm_channels = 0, nm_k = 0, nm_shift = 0, nm_vmin = 0, nm_values = 0;
-    // its colour (wfs_set_noise_colour): nc_buf holds taps [nm_channels + nc_groups][NC_TAP_STRIDE] | group [nm_channels] | mix [nm_channels];
-    // the cells of the common streams follow the channels' in nm_cells (h_nm_cells keeps the channels' alone).  nc_n_taps 0: white
-    DevBuf nc_buf; i32 nc_n_taps = 0, nc_groups = 0;
-    i32 table_channels = 0;           // columns of the noise table (dev.noise_channels counts the model's channels while a model is set)
-    // host mirrors
-    std::vector<i64> h_set_off;       // injected photons: per set photon offsets (channel sorted input order)
-    wfs_counts counts{};
-    WfsScal *h_scal = nullptr;        // host copy of scal in page-locked memory: read_scal's copy needs no staging buffer (five of them per batch)
-    // step boundaries that publish (read_scal): h_scal is mapped and coherent, k_publish copies the block into it and stores the
-    // sequence number of the boundary into the word on the cache line behind it; the host spins on that word (wfs_boundary.h)
-    bool publish = false;             // false: the copy + synchronise path (the mapped allocation failed, or WFS_HOST_SYNC=copy)
-    uint64_t *h_seq = nullptr; u64 *d_hseq = nullptr, seq = 0; WfsScal *d_hscal = nullptr;
-    DevBuf pack_desc;
+    DevBuf stamps, row_desc, rec_key, rec_key2, rec_val, rec_val2, rec_dest, sort_tmp, scan_tmp, scal, noise_override, nm_cells, nc_buf, pack_desc;
     DevBuf row_bad, fin_len, res_cnt, fin_off, res_toff, res_desc, fin, res_long, res_rows;      // resident rows (k_row_pulse)
-    i64 n_front_rows = 0, n_res_rows = 0, n_short_rows = 0, n_res_tiles = 0, max_res_len = 0, s_fin = 0, s_res = 0; bool res_on = false;
-    i64 n_active_tiles = 0, n_tiny_tiles = 0, n_sparse_tiles = 0, n_dense_tiles = 0, n_wave_tiles = 0, max_nb_dense = 0, n_active_rows = 0, n_groups = 0, s_raw = 0, n_itv_slots = 0, n_records = 0, max_nb = 0, max_tile = 0, max_tile_dense = 0;
-    i64 cur_total = 0, row_dbg_total = 0;
-    std::vector<KernelTime> times;
-    std::vector<double> h_templates;      // [dt][tlen]
-    bool generic_geom = false;            // sample_duration / template length other than 10 ns / 22 samples: k_pulse_generic for every tile
-    std::vector<double> h_gains;
-    i64 zero64 = 0;
-    DevBuf tt_alias[6];
-    std::vector<i64> h_rs_off; std::vector<i32> h_rs_list;        // run set -> instructions (host copy)
-    std::vector<double> h_lum_x, h_lum_t;          // luminescence table (host copy, enters the S2 delay table)
-    DevBuf ap_ins, ap_ch, ap_t, ap_gain, ap_cand, ap_args_dev, ap_seg; i64 n_ap_photons = 0; bool ap_active = false;
-    // model variants of the photon delays
-    std::vector<DevBuf> x_alias; std::vector<AliasTab> h_tabs; DevBuf d_tabs; i32 n_user_tabs = 0;
-    std::vector<Pmf> base_pmf;           // transit time only, S1 terms, S2 terms, S2 terms without the 'simple' luminescence
-    DevBuf prop_top, prop_bot; i32 prop_nz = 0, prop_nu = 0; double prop_u0 = 0, prop_du = 1;
-    DevBuf ins_tab, ins_tabb, ins_pzi, ins_pzf; bool ins_models = false;
-    DevBuf pois_cdf, pois_kmin; bool any_ptrs = false;         // Poisson tables of the secondary gain per instruction (k_poisson_tables)
-    DevBuf gg_inv, ins_gg, ins_ggw, ins_ggsum; i32 gg_n = 0, gg_L = 0; bool ins_gg_set = false;       // 'garfield_gas_gap' luminescence
-    // pattern maps evaluated on the device
-    struct PatternMap { bool set = false; i32 dims = 0, n[3] = {1, 1, 1}, w[3] = {0, 0, 0}, n_map_ch = 0; double lo[3] = {0, 0, 0}, hgrid[3] = {1, 1, 1}; DevBuf values;
-                        i64 n_points = 0; DevBuf points;
-                        DevBuf cell_start, cell_pts; i32 cnx = 0, cny = 0; double cell_lo[2] = {0, 0}, cell_h = 1; } pmap[2];       // 2-D point lists: cell index (transverse diffusion)
-    // scalar maps (kind 0: weighted nearest neighbours on a regular grid, 1: on a point list, 2: RectBivariateSpline)
-    struct ScalarMap { int kind = 0; int nv = 1; PatternMap g; i32 nx = 0, ny = 0, kx = 0, ky = 0; DevBuf tx, ty, c; };      // kind 0 / 1: nearest neighbours on a grid / a point list, 2: spline, 3: multilinear grid
-    std::vector<std::unique_ptr<ScalarMap>> smaps;
-    DevBuf smap_pos, smap_out, smap_nb_idx, smap_nb_w, ins_aft; bool ins_aft_set = false;
+    DevBuf tt_alias[6], ap_ins, ap_ch, ap_t, ap_gain, ap_cand, ap_args_dev, ap_seg;
+    DevBuf d_tabs, prop_top, prop_bot, ins_tab, ins_tabb, ins_pzi, ins_pzf, gg_inv, ins_gg, ins_ggw, ins_ggsum;
+    DevBuf pois_cdf, pois_kmin;         // Poisson tables of the secondary gain per instruction (k_poisson_tables)
+    DevBuf smap_pos, smap_out, smap_nb_idx, smap_nb_w, ins_aft;
     // transverse diffusion with field maps: instructions whose pattern is averaged over their electrons (k_diffuse_patterns)
-    DevBuf ins_sigr, ins_siga, diff_row_ins, diff_row_id, diff_pre; std::vector<uint8_t> ins_diff; i64 n_diff_rows = 0; double diff_r2 = 0;
-    std::vector<i32> dev_row_ins; std::vector<int8_t> h_ins_type; i64 n_host_rows = 0; bool dev_rows_pending = false;
+    DevBuf ins_sigr, ins_siga, diff_row_ins, diff_row_id, diff_pre;
     DevBuf map_row_ins[2], map_row_id[2], map_x, map_y, map_z, map_nb_idx[2], map_nb_w[2];
-
     // tile-local generation (wfs_tilegen.h): S2 instructions whose photons are made inside the pulse workgroup
     DevBuf huge_start, huge_cbeg, huge_keys, huge_keys2, huge_vals, huge_vals2, huge_rec, huge_gain;      // ordering of tiles beyond TILE_ORDER_MAX photons
     DevBuf row_pmax, ins_fused, ins_nsurv, ins_bcap, ins_bcap_all, ins_boff, et32, ftiles, tbuf, row_cnt, row_tile, tile_done, tile_kind;
-    bool fuse_on = false, fuse_full = false, run_sets_given = false, sets_aligned = true, any_s2 = false;
-    i64 n_fused_tiles = 0 /* made by k_s2_tile */, n_gen_tiles = 0 /* tile-generated, pulse by the ordinary kernels */, p_fused = 0, s_raw_direct = 0;
-    i64 n_bright_tiles = 0;      // made by k_s2_bright
-    bool bright_on = true;       // wfs_set_bright_tiles
-    // the bottom-array sum row (wfs_set_sum_signal, k_sum_signal): range, length, chunks and offsets per window; the rows' samples sit
-    // behind the accumulators in raw, from sample sum_base
-    bool sum_on = false;
+    // the bottom-array sum row (k_sum_signal): range, length, chunks, offsets per window; its samples sit behind the accumulators in raw, from run.sum_base
     DevBuf sum_lo, sum_hi, sum_len, sum_nchunk, sum_off, sum_chunk_off;
-    i64 s_sum = 0, n_sum_chunks = 0, sum_base = 0;
-    i32 bright_lds = 0, bright_max_bins = 0;      // LDS a bright tile may take for H table + ballots (device grant, BRIGHT_LDS_MAX); start bins (WFS_BRIGHT_MAX_BINS)
-    BrightArgs bright_args{};
-    int tap_sparse_max = 48;     // tap_block: occupied cells up to which a wave of the dense pulse kernels walks them (WFS_TAP_SPARSE_MAX)
-    FuseArgs fuse_args{};
-
-    std::string launch_err;      // first failed launch of the current call (wfs_set_debug bit 3: every launch is checked)
-    int n_fail = 0;              // calls of fail(): a FillGroup that dies with segments checks that an error return is why
-    int fail(int code, const std::string &msg) { err = msg; n_fail++; return code; }
 
     // what is not a DevBuf; the buffers, and the members that hold some, free themselves after this body
     ~wfs_handle()
@@ -233,7 +220,7 @@ struct Timer {
     ~Timer()
     {
         if (on) hipEventRecord(h->times.back().b, h->stream);
-        if (h->keep_currents & DBG_CHECK_LAUNCHES) {
+        if (h->debug_bits & DBG_CHECK_LAUNCHES) {
             hipError_t e = hipGetLastError();
             if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
             if (e != hipSuccess && h->launch_err.empty()) { try { h->launch_err = std::string(name) + ": " + hipGetErrorString(e); } catch (...) {} }
@@ -315,7 +302,7 @@ int scan_into(wfs_handle *h, const i32 *in, i64 n, i64 *outp, i64 WfsScal::*tota
 int read_scal(wfs_handle *h)
 {
     bool published = false;
-    if (h->publish && h->own_stream && !(h->keep_currents & DBG_CHECK_LAUNCHES)) {
+    if (h->publish && h->own_stream && !(h->debug_bits & DBG_CHECK_LAUNCHES)) {
         const u64 seq = ++h->seq;
         // (the profiled step counts the boundaries that publish: one "k_publish" entry each, none for one that copies)
         { Timer t(h, "k_publish"); hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, h->stream, h->scal.as<WfsScal>(), h->d_hscal, h->d_hseq, seq); }
@@ -498,9 +485,12 @@ int build_time_tables(wfs_handle *h)
     return WFS_OK;
 }
 
+// The device view, rebuilt from the config and the handle's switches.  The copy-outs of rows and intervals decode the last run with its
+// row_slots, he_rows, sum_channel and noise_channels: when one of them moves, whichever wfs_set_* call it was, that run is no longer Complete.
 void refresh_dev(wfs_handle *h)
 {
     const wfs_config &c = h->cfg; WfsDev &d = h->dev;
+    const i32 layout0[4] = {d.row_slots, d.he_rows, d.sum_channel, d.noise_channels};
     d.dt = c.dt; d.samples_before = c.samples_before; d.samples_after = c.samples_after; d.store_before = c.store_before;
     d.store_after = c.store_after; d.tlen = c.tlen; d.tw = c.trigger_window; d.baseline = c.baseline; d.n_rows = c.n_rows;
     d.n_tpc = c.n_tpc; d.n_top = c.n_top; d.he_first = c.he_first; d.he_factor = c.he_factor; d.last_bottom = c.last_bottom;
@@ -530,7 +520,21 @@ void refresh_dev(wfs_handle *h)
     // the bottom-array sum row: one more slot per window, behind the TPC and HE slots (XENONnT only, rawdata.py:241)
     d.sum_channel = (h->sum_on && c.detector_nt) ? c.sum_channel : -1;
     if (d.sum_channel >= 0) d.row_slots += 1;
+    if (layout0[0] != d.row_slots || layout0[1] != d.he_rows || layout0[2] != d.sum_channel || layout0[3] != d.noise_channels) h->state().view_changed();
 }
+
+// the batch came through wfs_load_instructions: its photons are made on the device (run_generation)
+bool from_generator(const wfs_handle *h) { return h->batch.kind == BatchKind::Instructions; }
+// ... and has n instructions: what the per-instruction setters take
+bool generator_batch_of(const wfs_handle *h, i64 n) { return from_generator(h) && n == h->batch.n_ins; }
+// wfs_run came to its end: records, counts, truth, photons and pulses may be copied out
+bool run_finished(const wfs_handle *h) { return h->run.stage >= RunStage::Finished; }
+// ... and the device view still has the row layout it ran with: what is decoded with row_slots, he_rows or sum_channel may be too
+bool run_complete(const wfs_handle *h) { return h->run.stage == RunStage::Complete; }
+// the photons of a generator batch are made (a run that stopped after the generation, wfs_set_debug bit 2, counts)
+bool generated(const wfs_handle *h) { return from_generator(h) && h->run.stage >= RunStage::Generated; }
+// photons in front of the PMT afterpulse photons: made by the generator, or brought by the load
+i64 n_primary_photons(const wfs_handle *h) { return from_generator(h) ? h->run.n_gen_photons : h->batch.n_photons; }
 
 }  // namespace
 
@@ -700,12 +704,12 @@ try {
 int wfs_set_window_carry(wfs_handle *h, int32_t has, int64_t t) try { if (!h) return WFS_E_INVALID; h->carry_has = has; h->carry_runmax = t; return WFS_OK; } WFS_CATCH(h)
 int wfs_copy_cluster_groups(wfs_handle *h, int32_t *group, int64_t cap)
 try {
-    if (!h || !h->ran) return WFS_E_STATE;
-    if (cap < h->n_clusters) return h->fail(WFS_E_CAPACITY, "cluster buffer too small");
-    HIPCHK(hipMemcpy(group, h->cl_group.p, (size_t)h->n_clusters * 4, hipMemcpyDeviceToHost));
+    if (!h || !run_finished(h)) return WFS_E_STATE;
+    if (cap < h->batch.n_clusters) return h->fail(WFS_E_CAPACITY, "cluster buffer too small");
+    HIPCHK(hipMemcpy(group, h->cl_group.p, (size_t)h->batch.n_clusters * 4, hipMemcpyDeviceToHost));
     return WFS_OK;
 } WFS_CATCH(h)
-int wfs_set_debug(wfs_handle *h, int32_t keep) try { if (!h) return WFS_E_INVALID; h->keep_currents = keep; return WFS_OK; } WFS_CATCH(h)
+int wfs_set_debug(wfs_handle *h, int32_t keep) try { if (!h) return WFS_E_INVALID; h->debug_bits = keep; return WFS_OK; } WFS_CATCH(h)
 int wfs_set_profiling(wfs_handle *h, int32_t on) try { if (!h) return WFS_E_INVALID; h->profiling = on; return WFS_OK; } WFS_CATCH(h)
 
 int wfs_set_tables(wfs_handle *h, const double *templates, const double *spe, int32_t n_spe, const double *gains,
@@ -818,7 +822,7 @@ static int load_clusters(wfs_handle *h, i64 n, const int32_t *cluster, const int
         if ((i64)cl_tmin.size() <= cluster[i]) { cl_tmin.push_back(tmin[i]); cl_gid.push_back(gid ? gid[i] : (u32)i); }
         else cl_tmin[cluster[i]] = std::min(cl_tmin[cluster[i]], (i64)tmin[i]);
     }
-    h->n_clusters = (i64)cl_tmin.size();
+    h->batch.n_clusters = (i64)cl_tmin.size();
     TRY(upload(h, h->cl_tmin, cl_tmin.data(), cl_tmin.size() * 8));
     TRY(upload(h, h->cl_gid, cl_gid.data(), cl_gid.size() * 4));
     HIPCHK(hipStreamSynchronize(h->stream));       // vectors go out of scope
@@ -835,9 +839,9 @@ try {
     if (n <= 0 || !type || !time || !amp || !gid || !cluster || !tmin || !p_hit || !drift_mean || !drift_spread || !sc_gain || !cdf_row || !cdf_table || n_cdf <= 0)
         return h->fail(WFS_E_INVALID, "wfs_load_instructions: null or empty input");
     HIPCHK(hipSetDevice(h->device));
+    h->state().load_begins(); BatchState &b = h->batch;
     std::vector<i64> em_off((size_t)n + 1);
     em_off[0] = 0;
-    bool any_ptrs = false;
     for (i64 i = 0; i < n; i++) {
         if (type[i] != 1 && type[i] != 2 && type[i] != 4 && type[i] != 6)      // 4 / 6: electron afterpulses, simulated like an S2 (afterpulse.py:14, 94)
             return h->fail(WFS_E_INVALID, "instruction types: 1 (S1), 2 (S2), 4 / 6 (photo-ionisation / photo-electric electrons)");
@@ -846,7 +850,7 @@ try {
         if (cdf_row[i] == -1 && !h->pmap[type[i] == 1 ? 0 : 1].set) return h->fail(WFS_E_STATE, "cdf_row -1 needs wfs_set_pattern_map for the instruction type");
         if (type[i] != 1 && h->dev.n_lum < 2) return h->fail(WFS_E_STATE, "S2 instructions need the luminescence table");
         em_off[i + 1] = em_off[i] + (type[i] == 1 ? 1 : (i64)amp[i]);
-        if (type[i] != 1 && sc_gain[i] > 217.0) any_ptrs = true;          // POIS_LAM_MAX: the electrons of such an instruction draw with PTRS (k_s2_photons)
+        if (type[i] != 1 && sc_gain[i] > 217.0) b.any_ptrs = true;         // POIS_LAM_MAX: the electrons of such an instruction draw with PTRS (k_s2_photons)
     }
     // pulse sets (one Pulse.__call__ each, rawdata.py:108-127): the caller's run sets, by default one per instruction
     std::vector<i32> ins_set((size_t)n);
@@ -867,27 +871,26 @@ try {
             if (cluster[set_list[k]] != cluster[set_list[set_off[q]]] || type[set_list[k]] != type[set_list[set_off[q]]])
                 return h->fail(WFS_E_INVALID, "the instructions of a run set must share cluster and type");
     // PMT afterpulses are a second pulse set per primary set (rawdata.py:176-178): set PS + q belongs to set q
-    h->ap_active = h->cfg.enable_pmt_ap && h->dev.n_ap > 0;
-    const i64 S = h->ap_active ? 2 * PS : PS;
-    h->any_ptrs = any_ptrs;
-    h->run_sets_given = run_set != nullptr;
-    h->sets_aligned = PS == n;                     // every set carries the index of its first instruction
-    for (i64 q = 0; q < PS && h->sets_aligned; q++) if (set_off[q + 1] > set_off[q] && set_list[set_off[q]] != (i32)q) h->sets_aligned = false;
-    h->any_s2 = false; for (i64 i = 0; i < n; i++) if (type[i] == 2) { h->any_s2 = true; break; }
-    h->n_ins = n; h->n_psets = PS; h->n_sets = S; h->n_emitters = em_off[n]; h->n_tiles = S * h->cfg.n_tpc;
-    h->h_rs_off = set_off; h->h_rs_list = set_list;
-    if (h->n_tiles > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "too many tiles in one batch");
+    b.ap_sets = h->cfg.enable_pmt_ap && h->dev.n_ap > 0;
+    const i64 S = b.ap_sets ? 2 * PS : PS;
+    b.run_sets_given = run_set != nullptr;
+    b.sets_aligned = PS == n;                     // every set carries the index of its first instruction
+    for (i64 q = 0; q < PS && b.sets_aligned; q++) if (set_off[q + 1] > set_off[q] && set_list[set_off[q]] != (i32)q) b.sets_aligned = false;
+    for (i64 i = 0; i < n; i++) if (type[i] == 2) { b.any_s2 = true; break; }
+    b.n_ins = n; b.n_psets = PS; b.n_sets = S; b.n_emitters = em_off[n]; b.n_tiles = S * h->cfg.n_tpc;
+    b.h_rs_off = set_off; b.h_rs_list = set_list;
+    if (b.n_tiles > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "too many tiles in one batch");
     TRY(upload(h, h->ins_type, type, (size_t)n)); TRY(upload(h, h->ins_time, time, (size_t)n * 8)); TRY(upload(h, h->ins_amp, amp, (size_t)n * 4));
     { std::vector<u32> eb((size_t)n, 0u); if (em_base) eb.assign(em_base, em_base + n); TRY(upload(h, h->ins_embase, eb.data(), (size_t)n * 4)); HIPCHK(hipStreamSynchronize(h->stream)); }
     TRY(upload(h, h->ins_gid, gid, (size_t)n * 4)); TRY(upload(h, h->ins_p, p_hit, (size_t)n * 8)); TRY(upload(h, h->ins_dm, drift_mean, (size_t)n * 8));
     TRY(upload(h, h->ins_ds, drift_spread, (size_t)n * 8)); TRY(upload(h, h->ins_sc, sc_gain, (size_t)n * 8));
     // rows -1: the channel CDF of the instruction comes from the device pattern map (wfs_eval_pattern_rows), stored behind the host rows
-    h->dev_row_ins.clear(); h->h_ins_type.assign(type, type + n); h->n_host_rows = n_cdf;
+    b.h_ins_type.assign(type, type + n); b.n_host_rows = n_cdf;
     {
         std::vector<i32> rows(cdf_row, cdf_row + n);
-        for (i64 i = 0; i < n; i++) if (rows[i] < 0) { rows[i] = (i32)(n_cdf + (i64)h->dev_row_ins.size()); h->dev_row_ins.push_back((i32)i); }
-        h->dev_rows_pending = !h->dev_row_ins.empty(); h->ins_aft_set = false; h->n_diff_rows = 0; h->ins_diff.clear();
-        const size_t total = (size_t)n_cdf + h->dev_row_ins.size();
+        for (i64 i = 0; i < n; i++) if (rows[i] < 0) { rows[i] = (i32)(n_cdf + (i64)b.dev_row_ins.size()); b.dev_row_ins.push_back((i32)i); }
+        b.dev_rows_pending = !b.dev_row_ins.empty();
+        const size_t total = (size_t)n_cdf + b.dev_row_ins.size();
         TRY(ensure(h, h->cdf_table, total * h->cfg.n_tpc * 8));
         TRY(upload(h, h->ins_cdfrow, rows.data(), (size_t)n * 4)); HIPCHK(hipStreamSynchronize(h->stream));
     }
@@ -910,7 +913,7 @@ try {
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     TRY(load_clusters(h, n, cluster, tmin, gid));
-    h->injected = false; h->optical = false; h->batch_loaded = true; h->ran = false; h->gen_done = false; h->ins_models = false; h->ins_gg_set = false;
+    h->state().load_commits(BatchKind::Instructions);
     return WFS_OK;
 } WFS_CATCH(h)
 
@@ -926,7 +929,7 @@ try {
     h->x_alias.clear();
     h->x_alias.resize((size_t)n_tables);
     h->h_tabs.assign((size_t)n_tables + 2, AliasTab{});
-    h->n_user_tabs = n_tables; h->ins_models = false;
+    h->n_user_tabs = n_tables; h->batch.ins_models = false; h->state().option_changed();      // (the instructions' table numbers meant the tables before)
     for (int k = 0; k < n_tables; k++) {
         if (base[k] < 0 || base[k] > 3 || pmf_off[k + 1] <= pmf_off[k]) return h->fail(WFS_E_INVALID, "wfs_set_delay_models: bad base or empty pmf");
         Pmf e; e.vmin = vmin[k]; e.p.assign(pmf + pmf_off[k], pmf + pmf_off[k + 1]);
@@ -1032,12 +1035,13 @@ try {
 int wfs_set_instruction_aft(wfs_handle *h, int64_t n, const double *factor)
 try {
     if (!h) return WFS_E_INVALID;
-    if (!h->batch_loaded || h->injected || h->optical || n != h->n_ins) return h->fail(WFS_E_STATE, "wfs_set_instruction_aft follows wfs_load_instructions of the same batch");
-    if (!factor) { h->ins_aft_set = false; return WFS_OK; }
+    if (!generator_batch_of(h, n)) return h->fail(WFS_E_STATE, "wfs_set_instruction_aft follows wfs_load_instructions of the same batch");
+    h->batch.ins_aft_set = false; h->state().option_changed();
+    if (!factor) return WFS_OK;
     HIPCHK(hipSetDevice(h->device));
     TRY(upload(h, h->ins_aft, factor, (size_t)n * 8));
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->ins_aft_set = true;
+    h->batch.ins_aft_set = true;
     return WFS_OK;
 } WFS_CATCH(h)
 
@@ -1048,22 +1052,22 @@ try {
 int wfs_set_instruction_diffusion(wfs_handle *h, int64_t n, const double *sigma_r, const double *sigma_a, double tpc_radius)
 try {
     if (!h) return WFS_E_INVALID;
-    if (!h->batch_loaded || h->injected || h->optical || n != h->n_ins || !sigma_r || !sigma_a) return h->fail(WFS_E_STATE, "wfs_set_instruction_diffusion follows wfs_load_instructions of the same batch");
+    if (!generator_batch_of(h, n) || !sigma_r || !sigma_a) return h->fail(WFS_E_STATE, "wfs_set_instruction_diffusion follows wfs_load_instructions of the same batch");
     const auto &pm = h->pmap[1];
     if (!pm.set || pm.dims != 2 || (pm.n_points && !pm.cnx)) return h->fail(WFS_E_STATE, "wfs_set_instruction_diffusion needs a two-dimensional S2 pattern map on the device (wfs_set_pattern_map / wfs_set_pattern_map_points)");
     HIPCHK(hipSetDevice(h->device));
-    h->ins_diff.assign((size_t)n, 0);
+    h->batch.ins_diff.assign((size_t)n, 0); h->state().option_changed();
     std::vector<char> is_dev((size_t)n, 0);
-    for (i32 i : h->dev_row_ins) is_dev[i] = 1;
+    for (i32 i : h->batch.dev_row_ins) is_dev[i] = 1;
     std::vector<i32> rows; std::vector<i64> ids;
-    for (size_t k = 0; k < h->dev_row_ins.size(); k++) {
-        const i32 i = h->dev_row_ins[k];
-        if (h->h_ins_type[i] == 1 || !(sigma_r[i] == sigma_r[i]) || !(sigma_a[i] == sigma_a[i])) continue;
-        h->ins_diff[i] = 1; rows.push_back(i); ids.push_back(h->n_host_rows + (i64)k);
+    for (size_t k = 0; k < h->batch.dev_row_ins.size(); k++) {
+        const i32 i = h->batch.dev_row_ins[k];
+        if (h->batch.h_ins_type[i] == 1 || !(sigma_r[i] == sigma_r[i]) || !(sigma_a[i] == sigma_a[i])) continue;
+        h->batch.ins_diff[i] = 1; rows.push_back(i); ids.push_back(h->batch.n_host_rows + (i64)k);
     }
     for (i64 i = 0; i < n; i++)
-        if (h->h_ins_type[i] != 1 && sigma_r[i] == sigma_r[i] && !is_dev[i]) return h->fail(WFS_E_STATE, "transverse diffusion: the instruction must take its pattern from the device map (cdf_row = -1)");
-    h->n_diff_rows = (i64)rows.size(); h->diff_r2 = tpc_radius * tpc_radius;
+        if (h->batch.h_ins_type[i] != 1 && sigma_r[i] == sigma_r[i] && !is_dev[i]) return h->fail(WFS_E_STATE, "transverse diffusion: the instruction must take its pattern from the device map (cdf_row = -1)");
+    h->batch.n_diff_rows = (i64)rows.size(); h->batch.diff_r2 = tpc_radius * tpc_radius;
     TRY(upload(h, h->ins_sigr, sigma_r, (size_t)n * 8)); TRY(upload(h, h->ins_siga, sigma_a, (size_t)n * 8));
     TRY(upload(h, h->diff_row_ins, rows.data(), rows.size() * 4)); TRY(upload(h, h->diff_row_id, ids.data(), ids.size() * 8));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1172,17 +1176,17 @@ try { return scalar_map_eval(h, map_id, n, pos, out, n_values); } WFS_CATCH(h)
 int wfs_eval_pattern_rows(wfs_handle *h, int64_t n, const float *x, const float *y, const float *z)
 try {
     if (!h) return WFS_E_INVALID;
-    if (!h->batch_loaded || h->injected || h->optical || n != h->n_ins || !x || !y || !z) return h->fail(WFS_E_STATE, "wfs_eval_pattern_rows follows wfs_load_instructions of the same batch");
-    if (h->dev_row_ins.empty()) return WFS_OK;
+    if (!generator_batch_of(h, n) || !x || !y || !z) return h->fail(WFS_E_STATE, "wfs_eval_pattern_rows follows wfs_load_instructions of the same batch");
+    if (h->batch.dev_row_ins.empty()) return WFS_OK;
     HIPCHK(hipSetDevice(h->device));
     const int nch = h->cfg.n_tpc;
     TRY(upload(h, h->map_x, x, (size_t)n * 4)); TRY(upload(h, h->map_y, y, (size_t)n * 4)); TRY(upload(h, h->map_z, z, (size_t)n * 4));
-    i64 first = h->n_host_rows;
+    i64 first = h->batch.n_host_rows;
     // rows were numbered in instruction order; evaluate them map by map, each over its own (ordered) subset
     std::vector<i32> rows_of[2]; std::vector<i64> row_id[2];
-    for (size_t k = 0; k < h->dev_row_ins.size(); k++) {
-        if (!h->ins_diff.empty() && h->ins_diff[h->dev_row_ins[k]]) continue;       // averaged over its electrons inside wfs_run
-        const int w = h->h_ins_type[h->dev_row_ins[k]] == 1 ? 0 : 1; rows_of[w].push_back(h->dev_row_ins[k]); row_id[w].push_back(first + (i64)k);
+    for (size_t k = 0; k < h->batch.dev_row_ins.size(); k++) {
+        if (!h->batch.ins_diff.empty() && h->batch.ins_diff[h->batch.dev_row_ins[k]]) continue;       // averaged over its electrons inside wfs_run
+        const int w = h->batch.h_ins_type[h->batch.dev_row_ins[k]] == 1 ? 0 : 1; rows_of[w].push_back(h->batch.dev_row_ins[k]); row_id[w].push_back(first + (i64)k);
     }
     for (int w = 0; w < 2; w++) {
         if (rows_of[w].empty()) continue;
@@ -1193,7 +1197,7 @@ try {
         MapArgs m{};
         map_args(pm, m);
         m.n_rows = nr; m.row_ins = h->map_row_ins[w].as<i32>(); m.row_id = h->map_row_id[w].as<i64>();
-        m.aft = (w == 1 && h->ins_aft_set) ? h->ins_aft.as<double>() : nullptr; m.n_top = h->cfg.n_top;
+        m.aft = (w == 1 && h->batch.ins_aft_set) ? h->ins_aft.as<double>() : nullptr; m.n_top = h->cfg.n_top;
         m.x = h->map_x.as<float>(); m.y = h->map_y.as<float>(); m.z = h->map_z.as<float>();
         m.nb_idx = h->map_nb_idx[w].as<i64>(); m.nb_w = h->map_nb_w[w].as<double>();
         m.cdf_table = h->cdf_table.as<double>(); m.gains = h->t_gains.as<double>();
@@ -1202,19 +1206,19 @@ try {
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipGetLastError());
-    h->dev_rows_pending = false; h->gen_done = false;
+    h->batch.dev_rows_pending = false; h->state().option_changed();
     return WFS_OK;
 } WFS_CATCH(h)
 
 // channel CDF rows of the loaded batch as the generator sees them (host rows followed by the device-evaluated ones)
 int wfs_copy_cdf_rows(wfs_handle *h, int32_t *cdf_row, double *cdf_table, int64_t cap_rows)
 try {
-    if (!h || !h->batch_loaded || h->injected || h->optical) return WFS_E_STATE;
-    if (h->dev_rows_pending) return h->fail(WFS_E_STATE, "wfs_eval_pattern_rows has not been called for this batch");
-    const i64 total = h->n_host_rows + (i64)h->dev_row_ins.size();
+    if (!h || !from_generator(h)) return WFS_E_STATE;
+    if (h->batch.dev_rows_pending) return h->fail(WFS_E_STATE, "wfs_eval_pattern_rows has not been called for this batch");
+    const i64 total = h->batch.n_host_rows + (i64)h->batch.dev_row_ins.size();
     if (cap_rows < total) return h->fail(WFS_E_CAPACITY, "cdf row buffer too small");
     HIPCHK(hipSetDevice(h->device));
-    if (cdf_row) HIPCHK(hipMemcpy(cdf_row, h->ins_cdfrow.p, (size_t)h->n_ins * 4, hipMemcpyDeviceToHost));
+    if (cdf_row) HIPCHK(hipMemcpy(cdf_row, h->ins_cdfrow.p, (size_t)h->batch.n_ins * 4, hipMemcpyDeviceToHost));
     if (cdf_table) HIPCHK(hipMemcpy(cdf_table, h->cdf_table.p, (size_t)total * h->cfg.n_tpc * 8, hipMemcpyDeviceToHost));
     return WFS_OK;
 } WFS_CATCH(h)
@@ -1234,7 +1238,7 @@ try {
 int wfs_set_instruction_models(wfs_handle *h, int64_t n, const int32_t *tab, const int32_t *tab_bottom, const int32_t *prop_zi, const double *prop_zf)
 try {
     if (!h) return WFS_E_INVALID;
-    if (!h->batch_loaded || h->injected || h->optical || n != h->n_ins) return h->fail(WFS_E_STATE, "wfs_set_instruction_models follows wfs_load_instructions of the same batch");
+    if (!generator_batch_of(h, n)) return h->fail(WFS_E_STATE, "wfs_set_instruction_models follows wfs_load_instructions of the same batch");
     if (h->d_tabs.p == nullptr) TRY(wfs_set_delay_models(h, 0, nullptr, nullptr, nullptr, nullptr));
     HIPCHK(hipSetDevice(h->device));
     std::vector<int8_t> type((size_t)n);
@@ -1253,7 +1257,7 @@ try {
     TRY(upload(h, h->ins_tab, t.data(), (size_t)n * 4)); TRY(upload(h, h->ins_tabb, tb.data(), (size_t)n * 4));
     TRY(upload(h, h->ins_pzi, zi.data(), (size_t)n * 4)); TRY(upload(h, h->ins_pzf, zf.data(), (size_t)n * 8));
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->ins_models = true; h->gen_done = false;
+    h->batch.ins_models = true; h->state().option_changed();
     return WFS_OK;
 } WFS_CATCH(h)
 
@@ -1273,13 +1277,13 @@ try {
 int wfs_set_instruction_gas_gap(wfs_handle *h, int64_t n, const int32_t *table, const double *weight)
 try {
     if (!h) return WFS_E_INVALID;
-    if (!h->batch_loaded || h->injected || h->optical || n != h->n_ins || !table || !weight) return h->fail(WFS_E_STATE, "wfs_set_instruction_gas_gap follows wfs_load_instructions of the same batch");
+    if (!generator_batch_of(h, n) || !table || !weight) return h->fail(WFS_E_STATE, "wfs_set_instruction_gas_gap follows wfs_load_instructions of the same batch");
     if (h->gg_n < 1) return h->fail(WFS_E_STATE, "wfs_set_gas_gap_model first");
     for (i64 i = 0; i < n; i++) if (table[i] < -1 || table[i] >= h->gg_n) return h->fail(WFS_E_INVALID, "gas gap table index out of range");
     HIPCHK(hipSetDevice(h->device));
     TRY(upload(h, h->ins_gg, table, (size_t)n * 4)); TRY(upload(h, h->ins_ggw, weight, (size_t)n * 8));
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->ins_gg_set = true; h->gen_done = false;
+    h->batch.ins_gg_set = true; h->state().option_changed();
     return WFS_OK;
 } WFS_CATCH(h)
 
@@ -1290,11 +1294,12 @@ try {
     if (!h->tables_set) return h->fail(WFS_E_STATE, "wfs_set_tables must be called first");
     if (n_sets <= 0 || !set_cluster || !set_tmin || !set_off) return h->fail(WFS_E_INVALID, "wfs_load_photons: null or empty input");
     HIPCHK(hipSetDevice(h->device));
+    h->state().load_begins(); BatchState &b = h->batch;
     const i64 P = set_off[n_sets]; const int nch = h->cfg.n_tpc;
-    h->n_ins = 0; h->n_sets = n_sets; h->n_tiles = n_sets * nch; h->n_photons = P; h->n_emitters = 0;
-    if (h->n_tiles > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "too many tiles in one batch");
+    b.n_sets = n_sets; b.n_tiles = n_sets * nch; b.n_photons = P;
+    if (b.n_tiles > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "too many tiles in one batch");
     // host bucketing: the input is already channel sorted inside each set
-    std::vector<i32> count((size_t)h->n_tiles, 0), tmn((size_t)h->n_tiles, 0x7fffffff), tmx((size_t)h->n_tiles, (i32)0x80000000), rel((size_t)P);
+    std::vector<i32> count((size_t)b.n_tiles, 0), tmn((size_t)b.n_tiles, 0x7fffffff), tmx((size_t)b.n_tiles, (i32)0x80000000), rel((size_t)P);
     std::vector<i64> t0((size_t)n_sets, 0);
     std::vector<i32> mode((size_t)n_sets, 1);
     for (i64 s = 0; s < n_sets; s++) {
@@ -1315,7 +1320,7 @@ try {
             count[tile]++; tmn[tile] = std::min(tmn[tile], (i32)r); tmx[tile] = std::max(tmx[tile], (i32)r);
         }
     }
-    h->h_set_off.assign(set_off, set_off + n_sets + 1);
+    b.h_set_off.assign(set_off, set_off + n_sets + 1);
     TRY(upload(h, h->set_cluster, set_cluster, (size_t)n_sets * 4)); TRY(upload(h, h->set_t0, t0.data(), (size_t)n_sets * 8));
     TRY(upload(h, h->set_mode, mode.data(), (size_t)n_sets * 4));
     TRY(upload(h, h->tile_count, count.data(), count.size() * 4)); TRY(upload(h, h->tile_tmin, tmn.data(), tmn.size() * 4));
@@ -1328,7 +1333,7 @@ try {
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     TRY(load_clusters(h, n_sets, set_cluster, set_tmin, nullptr));
-    h->injected = true; h->optical = false; h->batch_loaded = true; h->ran = false; h->gen_done = false;
+    h->state().load_commits(BatchKind::Photons);
     return WFS_OK;
 } WFS_CATCH(h)
 
@@ -1343,17 +1348,18 @@ try {
     if (n <= 0 || !time || !gid || !cluster || !tmin || !first || !last || (n_ph > 0 && (!channels || !timings)))
         return h->fail(WFS_E_INVALID, "wfs_load_optical: null or empty input");
     HIPCHK(hipSetDevice(h->device));
+    h->state().load_begins(); BatchState &b = h->batch;
     const int nch = h->cfg.n_tpc;
     // PMT afterpulses are a second pulse set per instruction (rawdata.py:176-178, behind every primary Pulse call): set n + i belongs to set i
-    h->ap_active = h->cfg.enable_pmt_ap && h->dev.n_ap > 0;
-    const i64 S = h->ap_active ? 2 * n : n;
-    h->n_ins = n; h->n_psets = n; h->n_sets = S; h->n_tiles = S * nch; h->n_emitters = 0; h->n_ap_photons = 0;
-    if (h->n_tiles > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "too many tiles in one batch");
+    b.ap_sets = h->cfg.enable_pmt_ap && h->dev.n_ap > 0;
+    const i64 S = b.ap_sets ? 2 * n : n;
+    b.n_ins = n; b.n_psets = n; b.n_sets = S; b.n_tiles = S * nch;
+    if (b.n_tiles > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "too many tiles in one batch");
     i64 n_ranged = 0;        // photons the instructions name: ranges may overlap (rawdata.py:477 takes any), so this can exceed n_ph
     for (i64 i = 0; i < n; i++) {
         if (first[i] < 0 || last[i] < first[i] || last[i] > n_ph) return h->fail(WFS_E_INVALID, "_first/_last out of range");
         n_ranged += (i64)last[i] - first[i];
-        if (h->ap_active && (i64)last[i] - first[i] >= (1LL << 29))      // (the order key of an afterpulse holds 29 bits of its parent's index)
+        if (b.ap_sets && (i64)last[i] - first[i] >= (1LL << 29))      // (the order key of an afterpulse holds 29 bits of its parent's index)
             return h->fail(WFS_E_CAPACITY, "an instruction of 2^29 or more supplied photons with PMT afterpulses on");
     }
     // the photons are bucketed by (instruction, channel) on the device: count, scan, place (k_optical_bucket) -- the primary tiles only
@@ -1367,7 +1373,7 @@ try {
     }
     TRY(upload(h, h->opt_first, first, (size_t)n * 4)); TRY(upload(h, h->opt_last, last, (size_t)n * 4));
     TRY(upload(h, h->opt_ch, channels, (size_t)n_ph * 4)); TRY(upload(h, h->opt_time, timings, (size_t)n_ph * 8));
-    TRY(ensure(h, h->tile_count, (size_t)h->n_tiles * 4)); TRY(ensure(h, h->tile_cursor, (size_t)h->n_tiles * 4)); TRY(ensure(h, h->tile_off, (size_t)(h->n_tiles + 1) * 8));
+    TRY(ensure(h, h->tile_count, (size_t)b.n_tiles * 4)); TRY(ensure(h, h->tile_cursor, (size_t)b.n_tiles * 4)); TRY(ensure(h, h->tile_off, (size_t)(b.n_tiles + 1) * 8));
     // (the bucketed copies hold a slot per photon of every instruction's range, not per entry of the flat arrays)
     TRY(ensure(h, h->opt_t, (size_t)n_ranged * 4)); TRY(ensure(h, h->opt_item, (size_t)n_ranged * 4));
     {
@@ -1383,29 +1389,26 @@ try {
     TRY(read_scal(h));
     HIPCHK(hipGetLastError());
     TRY(device_error(h, h->h_scal->opt_error));
-    const i64 P = h->h_scal->n_tile_photons;
-    h->n_photons = P;
+    const i64 P = b.n_photons = h->h_scal->n_tile_photons;
     // (with afterpulses the array also holds theirs, behind the primary photons: sized here, k_optical_finish writes into it)
-    TRY(ensure(h, h->ph, (size_t)(P + (h->ap_active ? optical_ap_cap(P) : 0)) * 8));
-    TRY(ensure(h, h->tile_tmin, (size_t)h->n_tiles * 4)); TRY(ensure(h, h->tile_tmax, (size_t)h->n_tiles * 4));
+    TRY(ensure(h, h->ph, (size_t)(P + (b.ap_sets ? optical_ap_cap(P) : 0)) * 8));
+    TRY(ensure(h, h->tile_tmin, (size_t)b.n_tiles * 4)); TRY(ensure(h, h->tile_tmax, (size_t)b.n_tiles * 4));
     TRY(ensure(h, h->el_stat, (size_t)n * 32)); TRY(ensure(h, h->el_minmax, (size_t)n * 16));
     HIPCHK(hipMemsetAsync(h->el_stat.p, 0, (size_t)n * 32, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     TRY(load_clusters(h, n, cluster, tmin, gid));
-    h->injected = false; h->optical = true; h->batch_loaded = true; h->ran = false; h->gen_done = false;
+    h->state().load_commits(BatchKind::Optical);
     return WFS_OK;
 } WFS_CATCH(h)
 
 // ---------------------------------------------------------------------------------------------- run
-// the batch came through wfs_load_instructions: its photons are made on the device (run_generation)
-static bool from_generator(const wfs_handle *h) { return !h->injected && !h->optical; }
 // pulses made by k_s2_tile (wfs_tilegen.h): their tiles are on no work list
-static bool tiles_made(const wfs_handle *h) { return from_generator(h) && h->fuse_full && h->n_fused_tiles + h->n_bright_tiles > 0; }
+static bool tiles_made(const wfs_handle *h) { return from_generator(h) && h->run.fuse_full && h->run.n_fused_tiles + h->run.n_bright_tiles > 0; }
 // tiles that drew their own photons, whichever kernel made them
-static i64 n_tilegen_tiles(const wfs_handle *h) { return h->n_fused_tiles + h->n_gen_tiles + h->n_bright_tiles; }
+static i64 n_tilegen_tiles(const wfs_handle *h) { return h->run.n_fused_tiles + h->run.n_gen_tiles + h->run.n_bright_tiles; }
 // ph_gain holds the photons with an explicit gain only: every photon of an injected batch, or the PMT afterpulses, which follow the
 // n_photons primary ones; the kernels index it by photon number
-static const double *ph_gain_base(const wfs_handle *h) { return (!h->injected && h->ap_active) ? h->ph_gain.as<double>() - h->n_photons : h->ph_gain.as<double>(); }
+static const double *ph_gain_base(const wfs_handle *h) { return h->batch.ap_sets ? h->ph_gain.as<double>() - n_primary_photons(h) : h->ph_gain.as<double>(); }
 // the templates as the pulse kernels take them by value: t[tap * dt + ns remainder]
 static TemplateArg fill_template_arg(const wfs_handle *h)
 {
@@ -1425,40 +1428,39 @@ static int gen_electrons(wfs_handle *h, GenRun &r, FillGroup &fg)
 {
     const WfsDev &d = h->dev;
     GenArgs &g = r.g; FuseArgs &f = r.f;
-    const i64 N = h->n_ins, E = h->n_emitters, T = h->n_tiles;
+    const i64 N = h->batch.n_ins, E = h->batch.n_emitters, T = h->batch.n_tiles;
     TRY(ensure(h, h->em_time, (size_t)E * 8)); TRY(ensure(h, h->em_nph, (size_t)E * 4)); TRY(ensure(h, h->em_ins, (size_t)E * 4));
     TRY(ensure(h, h->el_stat, (size_t)N * 32)); TRY(ensure(h, h->el_minmax, (size_t)N * 16));
     // (fg: the fills at the head of the generation, behind the scalar block's of wfs_run; flushed in front of the first kernel)
     TRY(fg.zero(h->el_stat.p, (size_t)N * 32));
     TRY(fg.pairs(h->el_minmax.p, 2 * N, I64_MAX, I64_MIN));      // (min, max) pairs: (I64_MAX, I64_MIN)
-    g.n_ins = N; g.n_psets = h->n_psets; g.n_emitters = E;
+    g.n_ins = N; g.n_psets = h->batch.n_psets; g.n_emitters = E;
     g.ins_embase = h->ins_embase.as<u32>(); g.ins_set = h->ins_set.as<i32>(); g.set_ins_off = h->set_ins_off.as<i64>(); g.set_ins_list = h->set_ins_list.as<i32>(); g.set_t0 = h->set_t0.as<i64>();
     g.ins_type = h->ins_type.as<int8_t>(); g.ins_time = h->ins_time.as<i64>(); g.ins_amp = h->ins_amp.as<i32>(); g.ins_gid = h->ins_gid.as<u32>();
     g.ins_p = h->ins_p.as<double>(); g.ins_dm = h->ins_dm.as<double>(); g.ins_ds = h->ins_ds.as<double>(); g.ins_sc = h->ins_sc.as<double>();
     g.ins_cdfrow = h->ins_cdfrow.as<i32>(); g.cdf_table = h->cdf_table.as<double>(); g.em_off = h->em_off.as<i64>();
     g.em_time = h->em_time.as<i64>(); g.em_nph = h->em_nph.as<i32>(); g.em_ins = h->em_ins.as<i32>();
     g.el_stat = h->el_stat.as<double>(); g.el_minmax = h->el_minmax.as<i64>(); g.scal = h->scal.as<WfsScal>();
-    const bool ext = r.ext = h->ins_models;
+    const bool ext = r.ext = h->batch.ins_models;
     if (ext) {
         g.tabs = h->d_tabs.as<AliasTab>(); g.ins_tab = h->ins_tab.as<i32>(); g.ins_tabb = h->ins_tabb.as<i32>();
         g.ins_pzi = h->ins_pzi.as<i32>(); g.ins_pzf = h->ins_pzf.as<double>();
         if (h->prop_nz >= 2) { g.prop_top = h->prop_top.as<double>(); g.prop_bot = h->prop_bot.as<double>(); g.prop_nu = h->prop_nu; g.prop_u0 = h->prop_u0; g.prop_du = h->prop_du; }
-        if (h->ins_gg_set && h->gg_n >= 1) {
+        if (h->batch.ins_gg_set && h->gg_n >= 1) {
             TRY(ensure(h, h->ins_ggsum, (size_t)(N + 1) * 8)); TRY(fg.zero(h->ins_ggsum.p, (size_t)(N + 1) * 8));
             g.gg_inv = h->gg_inv.as<double>(); g.gg_n = h->gg_n; g.gg_L = h->gg_L; g.ins_gg = h->ins_gg.as<i32>(); g.ins_ggw = h->ins_ggw.as<double>(); g.ins_ggsum = h->ins_ggsum.as<i64>();
         }
     }
     // em_zg is NaN wherever k_s2_electrons did not store a gain: k_s2_photons alone reads it, and it runs only with any_ptrs
-    TRY(ensure(h, h->em_zg, (size_t)E * 8)); if (h->any_ptrs) TRY(fg.bytes(h->em_zg.p, (size_t)E * 8, 0xff)); g.em_zg = h->em_zg.as<double>();
+    TRY(ensure(h, h->em_zg, (size_t)E * 8)); if (h->batch.any_ptrs) TRY(fg.bytes(h->em_zg.p, (size_t)E * 8, 0xff)); g.em_zg = h->em_zg.as<double>();
     // tile-local generation (wfs_tilegen.h): which instructions take it is decided before the electrons are drawn -- theirs get no
     // photon numbers.  Debug modes that need the per-photon arrays (currents, generation only) run the generation half alone.
     // (PMT afterpulses of tile-generated photons are screened inside k_s2_tile)
-    h->fuse_on = h->cfg.tile_gen && !h->generic_geom && h->any_s2 && d.gain_spread == 0.0 && (!h->run_sets_given || h->sets_aligned) && h->n_diff_rows == 0;
-    h->fuse_full = h->fuse_on && !(h->keep_currents & (DBG_CURRENTS | DBG_GEN_ONLY));
-    h->n_fused_tiles = 0; h->n_gen_tiles = 0; h->n_bright_tiles = 0; h->p_fused = 0;
-    if (h->fuse_on) {
+    h->run.fuse_on = h->cfg.tile_gen && !h->generic_geom && h->batch.any_s2 && d.gain_spread == 0.0 && (!h->batch.run_sets_given || h->batch.sets_aligned) && h->batch.n_diff_rows == 0;
+    h->run.fuse_full = h->run.fuse_on && !(h->debug_bits & (DBG_CURRENTS | DBG_GEN_ONLY));
+    if (h->run.fuse_on) {
         f.lam_min = h->cfg.tile_gen_min; f.n_ins = N; f.nch = d.n_tpc; f.table_span = (i32)(1u << (32 - d.tab_s2.shift));
-        f.set_ins_off = h->run_sets_given ? h->set_ins_off.as<i64>() : nullptr;
+        f.set_ins_off = h->batch.run_sets_given ? h->set_ins_off.as<i64>() : nullptr;
         f.n_top = d.n_top;
         if (ext) {       // timing-model variants: the instruction's tables (the longest one bounds every tile buffer)
             f.tabs = g.tabs; f.ins_tab = g.ins_tab; f.ins_tabb = g.ins_tabb; f.ins_gg = g.gg_inv ? g.ins_gg : nullptr;
@@ -1472,7 +1474,7 @@ static int gen_electrons(wfs_handle *h, GenRun &r, FillGroup &fg)
         f.ins_fused = h->ins_fused.as<i32>(); f.ins_nsurv = h->ins_nsurv.as<i32>(); f.ins_bcap = h->ins_bcap.as<i32>(); f.ins_bcap_all = h->ins_bcap_all.as<i32>();
         f.et32 = h->et32.as<i32>();
         {
-            const i64 n_rows = h->n_host_rows + (i64)h->dev_row_ins.size();
+            const i64 n_rows = h->batch.n_host_rows + (i64)h->batch.dev_row_ins.size();
             TRY(ensure(h, h->row_pmax, (size_t)n_rows * 8)); f.row_pmax = h->row_pmax.as<double>();
             TRY(fg.flush());
             Timer t(h, "k_fuse_decide");
@@ -1491,25 +1493,25 @@ static int gen_electrons(wfs_handle *h, GenRun &r, FillGroup &fg)
         g.pois_cdf = h->pois_cdf.as<double>(); g.pois_kmin = h->pois_kmin.as<i32>();
         { Timer t(h, "k_poisson_tables"); hipLaunchKernelGGL(k_poisson_tables, dim3((unsigned)N), dim3(POIS_W), 0, h->stream, g, h->pois_cdf.as<double>(), h->pois_kmin.as<i32>()); }
         { Timer t(h, "k_s2_electrons"); hipLaunchKernelGGL(k_s2_electrons, dim3(nblocks(E, 256)), dim3(256), 0, h->stream, d, g); }
-        if (h->any_ptrs) { Timer t(h, "k_s2_photons"); hipLaunchKernelGGL(k_s2_photons, dim3(nblocks(E, 256)), dim3(256), 0, h->stream, d, g); }
+        if (h->batch.any_ptrs) { Timer t(h, "k_s2_photons"); hipLaunchKernelGGL(k_s2_photons, dim3(nblocks(E, 256)), dim3(256), 0, h->stream, d, g); }
     }
-    if (h->n_diff_rows > 0) {
+    if (h->batch.n_diff_rows > 0) {
         // transverse diffusion maps: the pattern of these instructions is the average over their surviving electrons (s2.py:560-613)
         const auto &pm = h->pmap[1];
-        const i64 nr = h->n_diff_rows;
+        const i64 nr = h->batch.n_diff_rows;
         TRY(ensure(h, h->diff_pre, (size_t)nr * pm.n_map_ch * 8));
         MapArgs m{};
         map_args(pm, m);
         m.n_rows = nr; m.row_ins = h->diff_row_ins.as<i32>(); m.row_id = h->diff_row_id.as<i64>();
         m.x = h->map_x.as<float>(); m.y = h->map_y.as<float>(); m.z = h->map_z.as<float>();
         m.cdf_table = h->cdf_table.as<double>(); m.gains = h->t_gains.as<double>();
-        m.aft = h->ins_aft_set ? h->ins_aft.as<double>() : nullptr; m.n_top = h->cfg.n_top;
-        DiffArgs q{nr, m.row_ins, h->ins_sigr.as<double>(), h->ins_siga.as<double>(), h->diff_r2, h->diff_pre.as<double>()};
+        m.aft = h->batch.ins_aft_set ? h->ins_aft.as<double>() : nullptr; m.n_top = h->cfg.n_top;
+        DiffArgs q{nr, m.row_ins, h->ins_sigr.as<double>(), h->ins_siga.as<double>(), h->batch.diff_r2, h->diff_pre.as<double>()};
         { Timer t(h, "k_diffuse_patterns"); hipLaunchKernelGGL(k_diffuse_patterns, dim3((unsigned)nr), dim3(256), 0, h->stream, d, g, m, q); }
         m.pre = h->diff_pre.as<double>();
         { Timer t(h, "k_map_rows"); hipLaunchKernelGGL(k_map_rows, dim3((unsigned)nr), dim3(256), (size_t)d.n_tpc * 8, h->stream, m, d.n_tpc); }
     }
-    const i64 TP = r.TP = h->n_psets * d.n_tpc;
+    const i64 TP = r.TP = h->batch.n_psets * d.n_tpc;
     TRY(ensure(h, h->tile_count, (size_t)T * 4)); TRY(ensure(h, h->tile_cursor, (size_t)T * 4));
     TRY(ensure(h, h->tile_tmin, (size_t)T * 4)); TRY(ensure(h, h->tile_tmax, (size_t)T * 4));
     {
@@ -1519,16 +1521,16 @@ static int gen_electrons(wfs_handle *h, GenRun &r, FillGroup &fg)
         TRY(ft.flush());
     }
     TRY(ensure(h, h->tile_off, (size_t)(T + 1) * 8));
-    if (h->fuse_on) {
+    if (h->run.fuse_on) {
         // surviving electrons compacted per instruction, tile buffers sized from their time range, photons per tile (Poisson)
         { Timer t(h, "k_fuse_electrons"); hipLaunchKernelGGL(k_fuse_electrons, dim3((unsigned)N), dim3(256), 0, h->stream, d, f); }
         TRY(scan(h, h->ins_bcap_all.as<i32>(), N, h->ins_boff, &WfsScal::n_tbuf_samples));
         // (the work list: TP entries for the tiles of k_s2_tile, from the front and from the back, and TP more for those of k_s2_bright)
         TRY(ensure(h, h->ftiles, (size_t)2 * TP * sizeof(FTile))); TRY(ensure(h, h->tile_done, (size_t)TP * 4)); TRY(ensure(h, h->tile_kind, (size_t)TP));
         f.ins_boff = h->ins_boff.as<i64>(); f.tile_count = h->tile_count.as<i32>(); f.tiles = h->ftiles.as<FTile>();
-        f.tile_done = h->tile_done.as<i32>(); f.full = h->fuse_full ? 1 : 0; f.n_list = TP;
+        f.tile_done = h->tile_done.as<i32>(); f.full = h->run.fuse_full ? 1 : 0; f.n_list = TP;
         BrightArgs &b = h->bright_args;
-        b.on = (h->fuse_full && h->bright_on && h->bright_max_bins > 0) ? 1 : 0; b.lds_bytes = h->bright_lds; b.max_bins = h->bright_max_bins; b.pad = 0;
+        b.on = (h->run.fuse_full && h->bright_on && h->bright_max_bins > 0) ? 1 : 0; b.lds_bytes = h->bright_lds; b.max_bins = h->bright_max_bins; b.pad = 0;
         b.list_first = TP; b.tile_kind = h->tile_kind.as<int8_t>();
         { Timer t(h, "k_tile_counts"); hipLaunchKernelGGL(k_tile_counts, dim3(nblocks(TP, 256)), dim3(256), 0, h->stream, d, f, b); }
     }
@@ -1536,12 +1538,12 @@ static int gen_electrons(wfs_handle *h, GenRun &r, FillGroup &fg)
     TRY(read_scal(h));
     const WfsScal &sc = *h->h_scal;
     r.P = sc.n_block_photons;                   // the tiles' own photons come on top
-    if (h->fuse_on) { h->p_fused = sc.n_tilegen_photons; h->n_fused_tiles = sc.n_full_tiles; h->n_gen_tiles = sc.n_gen_tiles; h->n_bright_tiles = sc.n_bright_tiles; }
-    if (h->fuse_on && getenv("WFS_BRIGHT_STATS")) {
+    if (h->run.fuse_on) { h->run.p_fused = sc.n_tilegen_photons; h->run.n_fused_tiles = sc.n_full_tiles; h->run.n_gen_tiles = sc.n_gen_tiles; h->run.n_bright_tiles = sc.n_bright_tiles; }
+    if (h->run.fuse_on && getenv("WFS_BRIGHT_STATS")) {
         fprintf(stderr, "bright tiles: %lld by k_s2_bright, %lld generation only, %lld of up to %d photons; widest H table of a tile above that: %lld start bins (budget %d bins, %d bytes)\n",
-                (long long)h->n_bright_tiles, (long long)h->n_gen_tiles, (long long)h->n_fused_tiles, TILE_MAX_PHOTONS, (long long)sc.max_bright_bins, h->bright_max_bins, h->bright_lds);
+                (long long)h->run.n_bright_tiles, (long long)h->run.n_gen_tiles, (long long)h->run.n_fused_tiles, TILE_MAX_PHOTONS, (long long)sc.max_bright_bins, h->bright_max_bins, h->bright_lds);
     }
-    h->n_photons = r.P + h->p_fused; h->n_ap_photons = 0;
+    h->run.n_gen_photons = r.P + h->run.p_fused;
     return WFS_OK;
 }
 
@@ -1580,13 +1582,13 @@ static int gen_block_photons(wfs_handle *h, GenRun &r)
 {
     const WfsDev &d = h->dev;
     GenArgs &g = r.g; ApArgs &ap = r.ap;
-    const i64 N = h->n_ins, P = r.P, TP = r.TP;
+    const i64 N = h->batch.n_ins, P = r.P, TP = r.TP;
     const bool ext = r.ext;
     g.em_ph_off = h->em_ph_off.as<i64>(); g.n_photons = P;
-    const bool ap_on = r.ap_on = h->ap_active;
-    const i64 ap_cap = r.ap_cap = ap_on ? (P + h->p_fused) / 8 + 65536 : 0;
-    TRY(ensure(h, h->ph, (size_t)(P + h->p_fused + ap_cap) * 8));
-    TRY(ensure(h, h->ph_idx, (size_t)(P + h->p_fused + ap_cap) * 4)); g.ph_idx = h->ph_idx.as<u32>();
+    const bool ap_on = r.ap_on = h->batch.ap_sets;
+    const i64 ap_cap = r.ap_cap = ap_on ? (P + h->run.p_fused) / 8 + 65536 : 0;
+    TRY(ensure(h, h->ph, (size_t)(P + h->run.p_fused + ap_cap) * 8));
+    TRY(ensure(h, h->ph_idx, (size_t)(P + h->run.p_fused + ap_cap) * 4)); g.ph_idx = h->ph_idx.as<u32>();
     g.tile_count = h->tile_count.as<i32>(); g.tile_cursor = h->tile_cursor.as<i32>(); g.tile_tmin = h->tile_tmin.as<i32>();
     g.tile_tmax = h->tile_tmax.as<i32>(); g.ph = h->ph.as<PhotonRec>();
     g.tile_off = h->tile_off.as<i64>();
@@ -1602,7 +1604,7 @@ static int gen_block_photons(wfs_handle *h, GenRun &r)
         TRY(fg.flush());
     }
     g.tile_tail = h->tile_tail.as<i32>(); g.tile_tailbase = h->tile_tailbase.as<i32>();
-    { Timer t(h, "k_set_bases"); hipLaunchKernelGGL(k_set_bases, dim3(nblocks(h->n_psets, 256)), dim3(256), 0, h->stream, g); }
+    { Timer t(h, "k_set_bases"); hipLaunchKernelGGL(k_set_bases, dim3(nblocks(h->batch.n_psets, 256)), dim3(256), 0, h->stream, g); }
     if (P > 0) {
         const unsigned nb = (unsigned)((P + GEN_BLOCK - 1) / GEN_BLOCK);
         g.n_blocks = nb;
@@ -1615,7 +1617,7 @@ static int gen_block_photons(wfs_handle *h, GenRun &r)
         g.xcd_chunk = (nb + 7) / 8;
         const unsigned nbx = (unsigned)(g.xcd_chunk * 8);
         {   // alias cells of every channel CDF row (host rows + rows from the device maps, the electron-averaged ones included)
-            const i64 n_rows = h->n_host_rows + (i64)h->dev_row_ins.size();
+            const i64 n_rows = h->batch.n_host_rows + (i64)h->batch.dev_row_ins.size();
             int lg = 1; while ((1 << lg) < d.n_tpc) lg++;
             TRY(ensure(h, h->chan_alias, (size_t)n_rows * ((size_t)8 << lg)));
             g.chan_alias = h->chan_alias.as<uint2>(); g.ch_lg = lg;
@@ -1642,16 +1644,16 @@ static int gen_tile_photons(wfs_handle *h, GenRun &r)
 {
     const WfsDev &d = h->dev;
     FuseArgs &f = r.f; ApArgs &ap = r.ap;
-    const i64 T = h->n_tiles, TP = r.TP;
+    const i64 T = h->batch.n_tiles, TP = r.TP;
     const bool ap_on = r.ap_on;
     // (photon counts only -- wfs_set_debug bit 2 without bit 4, the electron-afterpulse pre-pass: the tiles' photon numbers are drawn
     // (k_tile_counts) and single photons are recomputed on request (wfs_gather_photon_times); no photon of a tile is generated)
-    const bool counts_only = (h->keep_currents & DBG_GEN_ONLY) && !(h->keep_currents & DBG_KEEP_PHOTONS);
-    if (h->fuse_on && n_tilegen_tiles(h) > 0 && !counts_only) {
+    const bool counts_only = (h->debug_bits & DBG_GEN_ONLY) && !(h->debug_bits & DBG_KEEP_PHOTONS);
+    if (h->run.fuse_on && n_tilegen_tiles(h) > 0 && !counts_only) {
         TRY(ensure(h, h->tbuf, (size_t)h->h_scal->n_tbuf_samples * 4 + 64));
         TRY(ensure(h, h->tile_truth, (size_t)T * 8 * 8));
         f.tile_off = h->tile_off.as<i64>(); f.tile_tmin = h->tile_tmin.as<i32>(); f.tile_tmax = h->tile_tmax.as<i32>(); f.tile_truth = h->tile_truth.as<double>();
-        f.tbuf = h->tbuf.as<i32>(); f.ph = h->ph.as<PhotonRec>(); f.keep_ph = (h->keep_currents & DBG_KEEP_PHOTONS) ? 1 : 0;
+        f.tbuf = h->tbuf.as<i32>(); f.ph = h->ph.as<PhotonRec>(); f.keep_ph = (h->debug_bits & DBG_KEEP_PHOTONS) ? 1 : 0;
         const TemplateArg tp = fill_template_arg(h);
         // H table + the waves' counters; the exact form adds the tables of tap_block (the fused form gathers every sample densely)
         size_t lds = (size_t)(WFS_TILE_CHUNK + d.tlen - 1) * d.dt * 8 + 4 * 4 * 4 + (h->cfg.fma ? 16 : TAP_LDS_BYTES(256) + 64);
@@ -1667,24 +1669,24 @@ static int gen_tile_photons(wfs_handle *h, GenRun &r)
         f.sparse_max = h->tap_sparse_max;
         // tiles of up to 2048 photons: photons and pulse in one workgroup (listed from the front); brighter ones -- and every tile in the
         // debug modes -- generation only (listed from the back), their pulses are made by the ordinary kernels below
-        if (h->n_fused_tiles > 0) {
+        if (h->run.n_fused_tiles > 0) {
             Timer t(h, "k_s2_tile");
-            const dim3 grid((unsigned)h->n_fused_tiles);
+            const dim3 grid((unsigned)h->run.n_fused_tiles);
             if (ap_on) WFS_LAUNCH_F(h, K_S2_TILE_AP, grid, dim3(256), lds, d, f, tp, app, ap_lds_off);
             else WFS_LAUNCH_F(h, K_S2_TILE, grid, dim3(256), lds, d, f, tp, app, ap_lds_off);
         }
-        if (h->n_gen_tiles > 0) {
+        if (h->run.n_gen_tiles > 0) {
             Timer t(h, "k_s2_tile_gen");
-            const dim3 grid((unsigned)h->n_gen_tiles);
-            if (ap_on) hipLaunchKernelGGL(k_s2_tile_gen<true>, grid, dim3(256), (size_t)AP_STAGE * sizeof(ApCand), h->stream, d, f, app, (int)h->n_fused_tiles);
-            else hipLaunchKernelGGL(k_s2_tile_gen<false>, grid, dim3(256), 0, h->stream, d, f, app, (int)h->n_fused_tiles);
+            const dim3 grid((unsigned)h->run.n_gen_tiles);
+            if (ap_on) hipLaunchKernelGGL(k_s2_tile_gen<true>, grid, dim3(256), (size_t)AP_STAGE * sizeof(ApCand), h->stream, d, f, app, (int)h->run.n_fused_tiles);
+            else hipLaunchKernelGGL(k_s2_tile_gen<false>, grid, dim3(256), 0, h->stream, d, f, app, (int)h->run.n_fused_tiles);
         }
         // tiles above 2048 photons whose H table fits the LDS as a whole: photons and pulse in one workgroup of 1024 threads, no photon array
-        if (h->n_bright_tiles > 0) {
+        if (h->run.n_bright_tiles > 0) {
             Timer t(h, "k_s2_bright");
-            const dim3 grid((unsigned)h->n_bright_tiles);
+            const dim3 grid((unsigned)h->run.n_bright_tiles);
             const size_t blds = (size_t)h->bright_lds + BRIGHT_SPE_BYTES + (ap_on ? (size_t)AP_STAGE * sizeof(ApCand) : 0);
-            const int seg_first = (int)(h->n_fused_tiles + h->n_gen_tiles);
+            const int seg_first = (int)(h->run.n_fused_tiles + h->run.n_gen_tiles);
             if (ap_on) WFS_LAUNCH_F(h, K_S2_BRIGHT_AP, grid, dim3(BRIGHT_TPB), blds, d, f, h->bright_args, tp, app, seg_first);
             else WFS_LAUNCH_F(h, K_S2_BRIGHT, grid, dim3(BRIGHT_TPB), blds, d, f, h->bright_args, tp, app, seg_first);
         }
@@ -1702,12 +1704,12 @@ static int gen_afterpulses(wfs_handle *h, GenRun &r)
     { Timer t(h, "k_ap_finish"); hipLaunchKernelGGL(k_ap_finish, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap); }
     { Timer t(h, "k_ap_count"); hipLaunchKernelGGL(k_ap_count, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap);
       if (ap.n_seg > 0) hipLaunchKernelGGL(k_ap_seg<false>, dim3(nblocks(ap.n_seg, 4)), dim3(256), 0, h->stream, d, g, ap, (double *)nullptr); }
-    TRY(scan_into(h, h->tile_count.as<i32>() + TP, TP, h->tile_off.as<i64>() + TP, &WfsScal::n_ap_photons, P + h->p_fused));      // (behind the slots of every primary tile, the tile-generated ones included)
-    { Timer t(h, "k_ap_place"); hipLaunchKernelGGL(k_ap_place, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap, h->ph_gain.as<double>() - (P + h->p_fused));
-      if (ap.n_seg > 0) hipLaunchKernelGGL(k_ap_seg<true>, dim3(nblocks(ap.n_seg, 4)), dim3(256), 0, h->stream, d, g, ap, h->ph_gain.as<double>() - (P + h->p_fused)); }
+    TRY(scan_into(h, h->tile_count.as<i32>() + TP, TP, h->tile_off.as<i64>() + TP, &WfsScal::n_ap_photons, P + h->run.p_fused));      // (behind the slots of every primary tile, the tile-generated ones included)
+    { Timer t(h, "k_ap_place"); hipLaunchKernelGGL(k_ap_place, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap, h->ph_gain.as<double>() - (P + h->run.p_fused));
+      if (ap.n_seg > 0) hipLaunchKernelGGL(k_ap_seg<true>, dim3(nblocks(ap.n_seg, 4)), dim3(256), 0, h->stream, d, g, ap, h->ph_gain.as<double>() - (P + h->run.p_fused)); }
     TRY(read_scal(h));
     if (h->h_scal->n_ap_candidates > ap_cap) return h->fail(WFS_E_CAPACITY, "more PMT afterpulse photons than 1/8 of the primary photons: afterpulse probability unreasonably high");
-    h->n_ap_photons = h->h_scal->n_ap_photons;                   // (the accepted candidates: total of the afterpulse tiles' counts, the scan above)
+    h->run.n_ap_photons = h->h_scal->n_ap_photons;                   // (the accepted candidates: total of the afterpulse tiles' counts, the scan above)
     return WFS_OK;
 }
 
@@ -1717,12 +1719,12 @@ static int order_ranges(wfs_handle *h, const OrderArgs &oa);
 static int gen_order(wfs_handle *h, GenRun &r)
 {
     const WfsDev &d = h->dev;
-    const i64 T = h->n_tiles, P = r.P, TP = r.TP;
+    const i64 T = h->batch.n_tiles, P = r.P, TP = r.TP;
     const bool ap_on = r.ap_on;
     TRY(ensure(h, h->order_list, (size_t)T * 2 * sizeof(OrderRange))); TRY(ensure(h, h->order_list2, (size_t)T * 2 * sizeof(OrderRange)));
     OrderArgs oa{T, TP, h->tile_count.as<i32>(), h->tile_off.as<i64>(), h->ph.as<PhotonRec>(), h->ph_idx.as<u32>(),
-                 ap_on ? h->ph_gain.as<double>() : nullptr, P + h->p_fused, h->order_list.as<OrderRange>(), h->order_list2.as<OrderRange>(), h->scal.as<WfsScal>(),
-                 (h->fuse_on && n_tilegen_tiles(h) > 0) ? h->ins_fused.as<i32>() : nullptr, d.n_tpc,
+                 ap_on ? h->ph_gain.as<double>() : nullptr, P + h->run.p_fused, h->order_list.as<OrderRange>(), h->order_list2.as<OrderRange>(), h->scal.as<WfsScal>(),
+                 (h->run.fuse_on && n_tilegen_tiles(h) > 0) ? h->ins_fused.as<i32>() : nullptr, d.n_tpc,
                  h->tile_cursor.as<i32>(), h->tile_tailbase.as<i32>(), h->ins_fullsort.as<i32>(), h->set_ins_off.as<i64>(), h->set_ins_list.as<i32>()};
     return order_ranges(h, oa);
 }
@@ -1796,11 +1798,11 @@ struct RunState {
 static int optical_afterpulses(wfs_handle *h)
 {
     const WfsDev &d = h->dev;
-    const i64 P = h->n_photons, TP = h->n_ins * d.n_tpc, ap_cap = optical_ap_cap(P);
+    const i64 P = h->batch.n_photons, TP = h->batch.n_ins * d.n_tpc, ap_cap = optical_ap_cap(P);
     GenArgs g{}; ApArgs ap{};
     TRY(fill_ap_args(h, ap, ap_cap));
     TRY(ensure(h, h->ph_idx, (size_t)(P + ap_cap) * 4));
-    g.n_psets = h->n_psets; g.tile_count = h->tile_count.as<i32>(); g.tile_cursor = h->tile_cursor.as<i32>(); g.tile_off = h->tile_off.as<i64>();
+    g.n_psets = h->batch.n_psets; g.tile_count = h->tile_count.as<i32>(); g.tile_cursor = h->tile_cursor.as<i32>(); g.tile_off = h->tile_off.as<i64>();
     g.tile_tmin = h->tile_tmin.as<i32>(); g.tile_tmax = h->tile_tmax.as<i32>(); g.ph = h->ph.as<PhotonRec>(); g.ph_idx = h->ph_idx.as<u32>();
     g.scal = h->scal.as<WfsScal>();
     if (P > 0) {
@@ -1815,7 +1817,7 @@ static int optical_afterpulses(wfs_handle *h)
     { Timer t(h, "k_ap_place"); hipLaunchKernelGGL(k_ap_place, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap, gain_base); }
     TRY(read_scal(h));
     if (h->h_scal->n_ap_candidates > ap_cap) return h->fail(WFS_E_CAPACITY, "more PMT afterpulse photons than 1/8 of the primary photons: afterpulse probability unreasonably high");
-    h->n_ap_photons = h->h_scal->n_ap_photons;
+    h->run.n_ap_photons = h->h_scal->n_ap_photons;
     TRY(ensure(h, h->order_list, (size_t)TP * 2 * sizeof(OrderRange))); TRY(ensure(h, h->order_list2, (size_t)TP * 2 * sizeof(OrderRange)));
     OrderArgs oa{TP, 0, h->tile_count.as<i32>() + TP, h->tile_off.as<i64>() + TP, h->ph.as<PhotonRec>(), h->ph_idx.as<u32>(), h->ph_gain.as<double>(), P,
                  h->order_list.as<OrderRange>(), h->order_list2.as<OrderRange>(), h->scal.as<WfsScal>(), nullptr, d.n_tpc, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -1830,21 +1832,22 @@ static int run_input(wfs_handle *h)
     FillGroup fg(h, from_generator(h) ? "fills_electrons" : "fills_input");
     TRY(fg.zero(h->scal.p, sizeof(WfsScal)));
     if (from_generator(h)) return run_generation(h, fg);
-    if (h->optical && h->ap_active) {
+    const bool optical = h->batch.kind == BatchKind::Optical;
+    if (optical && h->batch.ap_sets) {
         // the afterpulse tiles start every run empty (the primary tiles keep the counts and offsets of wfs_load_optical)
-        const i64 TP = h->n_ins * d.n_tpc;
+        const i64 TP = h->batch.n_ins * d.n_tpc;
         TRY(fg.zero(h->tile_count.as<i32>() + TP, (size_t)TP * 4)); TRY(fg.zero(h->tile_cursor.as<i32>() + TP, (size_t)TP * 4));
         TRY(fg.i32s(h->tile_tmin.as<i32>() + TP, TP, 0x7fffffff)); TRY(fg.i32s(h->tile_tmax.as<i32>() + TP, TP, (i32)0x80000000));
     }
     TRY(fg.flush());
-    if (h->optical) {
-        const i64 T = h->n_ins * d.n_tpc;                    // the primary tiles (afterpulse tiles follow them)
+    if (optical) {
+        const i64 T = h->batch.n_ins * d.n_tpc;                    // the primary tiles (afterpulse tiles follow them)
         OpticalArgs oa{T, h->tile_count.as<i32>(), h->tile_off.as<i64>(), h->tile_tmin.as<i32>(), h->tile_tmax.as<i32>(), h->set_gid.as<u32>(),
                        h->opt_t.as<i32>(), h->opt_item.as<u32>(), h->ph.as<PhotonRec>(), h->scal.as<WfsScal>()};
         { Timer t(h, "k_optical_finish"); hipLaunchKernelGGL(k_optical_finish, dim3(nblocks(T, 256)), dim3(256), 0, h->stream, d, oa); }
-        if (h->ap_active) TRY(optical_afterpulses(h));
+        if (h->batch.ap_sets) TRY(optical_afterpulses(h));
     }
-    else { h->ap_active = false; TRY(scan(h, h->tile_count.as<i32>(), h->n_tiles, h->tile_off, &WfsScal::n_tile_photons)); }
+    else { TRY(scan(h, h->tile_count.as<i32>(), h->batch.n_tiles, h->tile_off, &WfsScal::n_tile_photons)); }
     return WFS_OK;
 }
 
@@ -1853,7 +1856,7 @@ static int run_geometry(wfs_handle *h, RunState &r)
 {
     const WfsDev &d = h->dev;
     GeomArgs &ga = r.ga;
-    const i64 T = h->n_tiles, S = h->n_sets, C = h->n_clusters;
+    const i64 T = h->batch.n_tiles, S = h->batch.n_sets, C = h->batch.n_clusters;
     const i64 CG = r.CG = C + 1;
     FillGroup fg(h, "fills_geometry");
     TRY(ensure(h, h->cl_end, (size_t)C * 8)); TRY(fg.i64s(h->cl_end.p, C, I64_MIN)); TRY(ensure(h, h->cl_group, (size_t)C * 4));
@@ -1872,7 +1875,7 @@ static int run_geometry(wfs_handle *h, RunState &r)
     ga.cl_end = h->cl_end.as<i64>(); ga.cl_group = h->cl_group.as<i32>(); ga.grp_lo = h->grp_lo.as<i64>(); ga.grp_hi = h->grp_hi.as<i64>();
     ga.grp_left = h->grp_left.as<i64>(); ga.grp_right = h->grp_right.as<i64>(); ga.grp_ixrand = h->grp_ixrand.as<i64>(); ga.grp_gid = h->grp_gid.as<u32>();
     ga.row_lo = h->row_lo.as<i64>(); ga.row_hi = h->row_hi.as<i64>(); ga.acc_len = h->acc_len.as<i32>(); ga.itv_cap = h->itv_cap.as<i32>();
-    ga.active_rows = h->active_rows.as<i32>(); ga.scal = h->scal.as<WfsScal>(); ga.active_tiles = h->active_tiles.as<i32>(); ga.sparse_tiles = h->sparse_tiles.as<i32>(); ga.dense_tiles = h->dense_tiles.as<i32>(); ga.wave_tiles = h->wave_tiles.as<i32>(); ga.force_dense = ((h->keep_currents & DBG_FORCE_DENSE) || h->generic_geom) ? 1 : 0; ga.init_has = h->carry_has; ga.init_runmax = h->carry_runmax;
+    ga.active_rows = h->active_rows.as<i32>(); ga.scal = h->scal.as<WfsScal>(); ga.active_tiles = h->active_tiles.as<i32>(); ga.sparse_tiles = h->sparse_tiles.as<i32>(); ga.dense_tiles = h->dense_tiles.as<i32>(); ga.wave_tiles = h->wave_tiles.as<i32>(); ga.force_dense = ((h->debug_bits & DBG_FORCE_DENSE) || h->generic_geom) ? 1 : 0; ga.init_has = h->carry_has; ga.init_runmax = h->carry_runmax;
     ga.noise_override = h->n_noise_override ? h->noise_override.as<i64>() : nullptr; ga.n_noise_override = h->n_noise_override;
     if (d.sum_channel >= 0) {
         TRY(ensure(h, h->sum_lo, (size_t)CG * 8)); TRY(ensure(h, h->sum_hi, (size_t)CG * 8));
@@ -1888,21 +1891,21 @@ static int run_geometry(wfs_handle *h, RunState &r)
     // pulses are where the accumulators cost (memset, atomics, two more reads); a batch of sparse S1 or nVeto hits is as fast through
     // them, and the resident path's extra pass over the tiles does not pay there
     // (photons in the photon array: the tiles k_s2_tile made in one go hold theirs in their sample buffers and can never be resident)
-    const i64 p_all = h->n_photons - ((from_generator(h) && h->fuse_full) ? h->p_fused : 0) + ((!h->injected && h->ap_active) ? h->n_ap_photons : 0);
+    const i64 p_all = n_primary_photons(h) - (h->run.fuse_full ? h->run.p_fused : 0) + h->run.n_ap_photons;
     const bool res_auto = T > 0 && p_all >= 2 * T;
     const int res_mode = h->res_env >= 0 ? h->res_env : h->cfg.row_resident;
-    h->res_on = (res_mode == 2 ? res_auto : res_mode != 0) && !(h->keep_currents & (DBG_CURRENTS | DBG_FORCE_DENSE)) && !h->generic_geom && !d.he_rows && 2 * (i64)d.tw + 1 >= 63
+    h->run.res_on = (res_mode == 2 ? res_auto : res_mode != 0) && !(h->debug_bits & (DBG_CURRENTS | DBG_FORCE_DENSE)) && !h->generic_geom && !d.he_rows && 2 * (i64)d.tw + 1 >= 63
                 && (!d.enable_noise || d.nm_cells || d.noise_len >= NOISE_MIN_FAST);
-    if (tiles_done || h->res_on) {
+    if (tiles_done || h->run.res_on) {
         TRY(ensure(h, h->row_cnt, (size_t)CG * d.n_tpc * 4)); TRY(ensure(h, h->row_tile, (size_t)CG * d.n_tpc * 4));
         TRY(fg.zero(h->row_cnt.p, (size_t)CG * d.n_tpc * 4));
         ga.row_cnt = h->row_cnt.as<i32>(); ga.row_tile = h->row_tile.as<i32>();
     }
     if (tiles_done) {
-        ga.tile_done = h->tile_done.as<i32>(); ga.n_done = h->n_psets * d.n_tpc;
+        ga.tile_done = h->tile_done.as<i32>(); ga.n_done = h->batch.n_psets * d.n_tpc;
         ga.ins_bcap = h->ins_bcap.as<i32>(); ga.ins_boff = h->ins_boff.as<i64>();
     }
-    if (h->res_on) {
+    if (h->run.res_on) {
         const size_t nr = (size_t)CG * d.n_tpc;
         TRY(ensure(h, h->row_bad, nr * 4)); TRY(ensure(h, h->fin_len, nr * 4)); TRY(ensure(h, h->res_cnt, nr * 4));
         TRY(fg.zero(h->row_bad.p, nr * 4)); TRY(fg.zero(h->fin_len.p, nr * 4)); TRY(fg.zero(h->res_cnt.p, nr * 4));
@@ -1922,7 +1925,7 @@ static int run_geometry(wfs_handle *h, RunState &r)
         TRY(scan(h, h->sum_len.as<i32>(), CG, h->sum_off, &WfsScal::n_sum_samples));
         TRY(scan(h, h->sum_nchunk.as<i32>(), CG, h->sum_chunk_off, &WfsScal::n_sum_chunks));
     }
-    if (h->res_on) {
+    if (h->run.res_on) {
         TRY(scan(h, h->fin_len.as<i32>(), CG * d.n_tpc, h->fin_off, &WfsScal::n_fin_samples)); TRY(scan(h, h->res_cnt.as<i32>(), CG * d.n_tpc, h->res_toff, &WfsScal::n_res_tiles));
         // rows are known: tiles onto their row's list or the work list of their class.  res_desc holds a descriptor slot for EVERY
         // tile of the batch (T * sizeof(TileDesc) bytes) although only the resident ones are written: their number (n_res_tiles) is
@@ -1938,37 +1941,37 @@ static int run_geometry(wfs_handle *h, RunState &r)
     TRY(read_scal(h));
     const WfsScal &sc = *h->h_scal;
     TRY(device_error(h, sc.error));
-    h->n_groups = sc.n_groups;
-    h->n_front_rows = sc.n_front_rows;
-    h->n_short_rows = h->res_on ? sc.n_short_rows : 0;
-    h->n_res_rows = h->res_on ? sc.n_short_rows + sc.n_long_rows : 0;
-    h->n_active_rows = h->n_front_rows + h->n_res_rows;
-    h->max_res_len = sc.max_res_len;
-    h->s_fin = h->res_on ? sc.n_fin_samples : 0;
-    h->n_res_tiles = h->res_on ? sc.n_res_tiles : 0;
-    h->s_res = h->res_on ? sc.n_res_samples : 0;
-    h->n_tiny_tiles = sc.n_tiny_tiles;
-    h->n_sparse_tiles = sc.n_sparse_tiles; h->max_nb = sc.max_nb_sparse; h->max_tile = sc.max_ph_sparse;
-    h->n_dense_tiles = sc.n_dense_tiles; h->max_nb_dense = sc.max_nb_dense; h->max_tile_dense = sc.max_ph_dense;
-    h->n_wave_tiles = sc.n_wave_tiles;
-    h->n_active_tiles = h->n_tiny_tiles + h->n_sparse_tiles + h->n_dense_tiles + h->n_wave_tiles;
-    r.first_sparse = h->n_tiny_tiles; r.first_dense = r.first_sparse + h->n_sparse_tiles; r.first_wave = r.first_dense + h->n_dense_tiles;
-    h->s_raw = sc.n_acc_samples; h->n_itv_slots = sc.n_itv_slots;
-    h->s_sum = d.sum_channel >= 0 ? sc.n_sum_samples : 0; h->n_sum_chunks = d.sum_channel >= 0 ? sc.n_sum_chunks : 0;
-    h->sum_base = (h->s_raw + 3) & ~(i64)3;
-    h->s_raw_direct = tiles_done ? sc.n_direct_samples : 0;      // samples of the rows that are read from a tile buffer in place
-    if (h->res_on && getenv("WFS_RES_STATS")) {
+    h->run.n_groups = sc.n_groups;
+    h->run.n_front_rows = sc.n_front_rows;
+    h->run.n_short_rows = h->run.res_on ? sc.n_short_rows : 0;
+    h->run.n_res_rows = h->run.res_on ? sc.n_short_rows + sc.n_long_rows : 0;
+    h->run.n_active_rows = h->run.n_front_rows + h->run.n_res_rows;
+    h->run.max_res_len = sc.max_res_len;
+    h->run.s_fin = h->run.res_on ? sc.n_fin_samples : 0;
+    h->run.n_res_tiles = h->run.res_on ? sc.n_res_tiles : 0;
+    h->run.s_res = h->run.res_on ? sc.n_res_samples : 0;
+    h->run.n_tiny_tiles = sc.n_tiny_tiles;
+    h->run.n_sparse_tiles = sc.n_sparse_tiles; h->run.max_nb = sc.max_nb_sparse; h->run.max_tile = sc.max_ph_sparse;
+    h->run.n_dense_tiles = sc.n_dense_tiles; h->run.max_nb_dense = sc.max_nb_dense; h->run.max_tile_dense = sc.max_ph_dense;
+    h->run.n_wave_tiles = sc.n_wave_tiles;
+    h->run.n_active_tiles = h->run.n_tiny_tiles + h->run.n_sparse_tiles + h->run.n_dense_tiles + h->run.n_wave_tiles;
+    r.first_sparse = h->run.n_tiny_tiles; r.first_dense = r.first_sparse + h->run.n_sparse_tiles; r.first_wave = r.first_dense + h->run.n_dense_tiles;
+    h->run.s_raw = sc.n_acc_samples; h->run.n_itv_slots = sc.n_itv_slots;
+    h->run.s_sum = d.sum_channel >= 0 ? sc.n_sum_samples : 0; h->run.n_sum_chunks = d.sum_channel >= 0 ? sc.n_sum_chunks : 0;
+    h->run.sum_base = (h->run.s_raw + 3) & ~(i64)3;
+    h->run.s_raw_direct = tiles_done ? sc.n_direct_samples : 0;      // samples of the rows that are read from a tile buffer in place
+    if (h->run.res_on && getenv("WFS_RES_STATS")) {
         fprintf(stderr, "resident rows: %lld short + %lld long of %lld rows, %lld tiles of %lld listed + resident, longest %lld samples, %lld finished samples, accumulators %lld samples\n",
-                (long long)h->n_short_rows, (long long)(h->n_res_rows - h->n_short_rows), (long long)h->n_active_rows, (long long)h->n_res_tiles,
-                (long long)(h->n_res_tiles + h->n_active_tiles), (long long)h->max_res_len, (long long)h->s_fin, (long long)h->s_raw);
+                (long long)h->run.n_short_rows, (long long)(h->run.n_res_rows - h->run.n_short_rows), (long long)h->run.n_active_rows, (long long)h->run.n_res_tiles,
+                (long long)(h->run.n_res_tiles + h->run.n_active_tiles), (long long)h->run.max_res_len, (long long)h->run.s_fin, (long long)h->run.s_raw);
     }
     // one work list: the sparse, dense and wave tiles behind the tiny ones
-    if (h->n_sparse_tiles > 0)
-        HIPCHK(hipMemcpyAsync(h->active_tiles.as<i32>() + r.first_sparse, h->sparse_tiles.p, (size_t)h->n_sparse_tiles * 4, hipMemcpyDeviceToDevice, h->stream));
-    if (h->n_dense_tiles > 0)
-        HIPCHK(hipMemcpyAsync(h->active_tiles.as<i32>() + r.first_dense, h->dense_tiles.p, (size_t)h->n_dense_tiles * 4, hipMemcpyDeviceToDevice, h->stream));
-    if (h->n_wave_tiles > 0)
-        HIPCHK(hipMemcpyAsync(h->active_tiles.as<i32>() + r.first_wave, h->wave_tiles.p, (size_t)h->n_wave_tiles * 4, hipMemcpyDeviceToDevice, h->stream));
+    if (h->run.n_sparse_tiles > 0)
+        HIPCHK(hipMemcpyAsync(h->active_tiles.as<i32>() + r.first_sparse, h->sparse_tiles.p, (size_t)h->run.n_sparse_tiles * 4, hipMemcpyDeviceToDevice, h->stream));
+    if (h->run.n_dense_tiles > 0)
+        HIPCHK(hipMemcpyAsync(h->active_tiles.as<i32>() + r.first_dense, h->dense_tiles.p, (size_t)h->run.n_dense_tiles * 4, hipMemcpyDeviceToDevice, h->stream));
+    if (h->run.n_wave_tiles > 0)
+        HIPCHK(hipMemcpyAsync(h->active_tiles.as<i32>() + r.first_wave, h->wave_tiles.p, (size_t)h->run.n_wave_tiles * 4, hipMemcpyDeviceToDevice, h->stream));
     return WFS_OK;
 }
 
@@ -1977,27 +1980,26 @@ static int run_pulses(wfs_handle *h, RunState &r)
 {
     const WfsDev &d = h->dev;
     PulseArgs &pa = r.pa;
-    const i64 T = h->n_tiles, S = h->n_sets;
+    const i64 T = h->batch.n_tiles, S = h->batch.n_sets;
     // (+64: a lane of k_zle reads 4 samples from its first valid one; the sum rows behind the accumulators are written whole by k_sum_signal)
-    TRY(ensure(h, h->raw, (size_t)(h->s_sum > 0 ? h->sum_base + h->s_sum : h->s_raw) * 4 + 64));
+    TRY(ensure(h, h->raw, (size_t)(h->run.s_sum > 0 ? h->run.sum_base + h->run.s_sum : h->run.s_raw) * 4 + 64));
     TRY(ensure(h, h->truth, (size_t)S * 16 * 8));
     {
         FillGroup fg(h, "fills_pulses");
-        TRY(fg.zero(h->raw.p, (size_t)h->s_raw * 4)); TRY(fg.zero(h->truth.p, (size_t)S * 16 * 8));
+        TRY(fg.zero(h->raw.p, (size_t)h->run.s_raw * 4)); TRY(fg.zero(h->truth.p, (size_t)S * 16 * 8));
         TRY(fg.flush());
     }
     TRY(ensure(h, h->tminmax, (size_t)S * 16)); TRY(ensure(h, h->tile_truth, (size_t)T * 8 * 8));
-    pa.active_tiles = h->active_tiles.as<i32>(); pa.n_active = h->n_active_tiles;
+    pa.active_tiles = h->active_tiles.as<i32>(); pa.n_active = h->run.n_active_tiles;
     pa.tile_count = h->tile_count.as<i32>(); pa.tile_tmin = h->tile_tmin.as<i32>(); pa.tile_tmax = h->tile_tmax.as<i32>(); pa.tile_off = h->tile_off.as<i64>();
     pa.set_cluster = h->set_cluster.as<i32>(); pa.set_t0 = h->set_t0.as<i64>(); pa.set_mode = h->set_mode.as<i32>();
     pa.ph = h->ph.as<PhotonRec>();
     pa.ph_gain = ph_gain_base(h);
     pa.cl_group = h->cl_group.as<i32>(); pa.row_lo = h->row_lo.as<i64>(); pa.acc_off = h->acc_off.as<i64>(); pa.raw = h->raw.as<i32>();
     pa.tile_truth = h->tile_truth.as<double>();
-    h->cur_total = 0;
-    if ((h->keep_currents & DBG_CURRENTS) && h->n_active_tiles > 0) {
+    if ((h->debug_bits & DBG_CURRENTS) && h->run.n_active_tiles > 0) {
         // debug: tile lengths in work-list order -> offsets
-        std::vector<i32> at((size_t)h->n_active_tiles), tmn((size_t)T), tmx((size_t)T);
+        std::vector<i32> at((size_t)h->run.n_active_tiles), tmn((size_t)T), tmx((size_t)T);
         std::vector<i64> t0((size_t)S);
         HIPCHK(hipStreamSynchronize(h->stream));
         HIPCHK(hipMemcpy(at.data(), h->active_tiles.p, at.size() * 4, hipMemcpyDeviceToHost));
@@ -2010,46 +2012,46 @@ static int run_pulses(wfs_handle *h, RunState &r)
             i64 b0 = floordiv(t0[set] + tmn[at[k]], (i64)d.dt), b1 = floordiv(t0[set] + tmx[at[k]], (i64)d.dt);
             off[k + 1] = off[k] + (b1 - b0 + 1) + d.store_before + d.samples_before + d.store_after + d.samples_after;
         }
-        h->cur_total = off.back();
+        h->run.cur_total = off.back();
         TRY(upload(h, h->cur_off, off.data(), off.size() * 8));
-        TRY(ensure(h, h->currents, (size_t)h->cur_total * 8));
+        TRY(ensure(h, h->currents, (size_t)h->run.cur_total * 8));
         HIPCHK(hipStreamSynchronize(h->stream));
         pa.currents = h->currents.as<double>(); pa.cur_off = h->cur_off.as<i64>();
     }
-    if (h->n_active_tiles > 0) {        // tile descriptors of the whole work list (used by the tiny and the dense kernel)
-        TRY(ensure(h, h->tile_desc, (size_t)h->n_active_tiles * sizeof(TileDesc)));
-        DescArgs da{pa.active_tiles, h->n_active_tiles, pa.tile_count, pa.tile_tmin, pa.tile_tmax, pa.tile_off, pa.set_cluster, pa.set_t0, pa.set_mode,
+    if (h->run.n_active_tiles > 0) {        // tile descriptors of the whole work list (used by the tiny and the dense kernel)
+        TRY(ensure(h, h->tile_desc, (size_t)h->run.n_active_tiles * sizeof(TileDesc)));
+        DescArgs da{pa.active_tiles, h->run.n_active_tiles, pa.tile_count, pa.tile_tmin, pa.tile_tmax, pa.tile_off, pa.set_cluster, pa.set_t0, pa.set_mode,
                     pa.cl_group, pa.row_lo, pa.acc_off, h->tile_desc.as<TileDesc>()};
         Timer t(h, "k_tile_desc");
-        hipLaunchKernelGGL(k_tile_desc, dim3(nblocks(h->n_active_tiles, 256)), dim3(256), 0, h->stream, d, da);
+        hipLaunchKernelGGL(k_tile_desc, dim3(nblocks(h->run.n_active_tiles, 256)), dim3(256), 0, h->stream, d, da);
     }
-    if (h->n_tiny_tiles > 0) {
+    if (h->run.n_tiny_tiles > 0) {
         PulseArgs pt = pa;
         pt.desc = h->tile_desc.as<TileDesc>();
         Timer t(h, "k_pulse_tiny");
-        WFS_LAUNCH_F(h, K_PULSE_TINY, dim3(nblocks(h->n_tiny_tiles * TINY_LANES, 256)), dim3(256), 0, d, pt, h->n_tiny_tiles);
+        WFS_LAUNCH_F(h, K_PULSE_TINY, dim3(nblocks(h->run.n_tiny_tiles * TINY_LANES, 256)), dim3(256), 0, d, pt, h->run.n_tiny_tiles);
     }
-    if (h->n_wave_tiles > 0) {
+    if (h->run.n_wave_tiles > 0) {
         PulseArgs pw = pa;
         pw.desc = h->tile_desc.as<TileDesc>() + r.first_wave;
         if (pw.cur_off) pw.cur_off += r.first_wave;
         Timer t(h, "k_pulse_wave");
-        WFS_LAUNCH_F(h, K_PULSE_WAVE, dim3(nblocks(h->n_wave_tiles, 4)), dim3(256), 0, d, pw, h->n_wave_tiles);
+        WFS_LAUNCH_F(h, K_PULSE_WAVE, dim3(nblocks(h->run.n_wave_tiles, 4)), dim3(256), 0, d, pw, h->run.n_wave_tiles);
     }
-    if (h->n_sparse_tiles > 0) {
+    if (h->run.n_sparse_tiles > 0) {
         PulseArgs ps = pa;
         ps.active_tiles = h->active_tiles.as<i32>() + r.first_sparse;
         if (ps.cur_off) ps.cur_off += r.first_sparse;
-        ps.W = (int)((h->max_nb + 7) / 8 * 8); ps.NP = (int)((h->max_tile + 7) / 8 * 8);
-        const bool small = h->max_tile <= 256 && h->max_nb <= 256;
+        ps.W = (int)((h->run.max_nb + 7) / 8 * 8); ps.NP = (int)((h->run.max_tile + 7) / 8 * 8);
+        const bool small = h->run.max_tile <= 256 && h->run.max_nb <= 256;
         const int tpb = small ? 64 : 256;
         size_t lds = (size_t)ps.NP * 12 + (size_t)8 * (tpb / 64) * 8 + ((size_t)d.dt * ps.W + 8) * 2 + 8 * 4 + std::max((size_t)d.dt * ps.W * 2, (size_t)1 * 260 * 8) + 16;
         lds = (lds + 15) / 16 * 16;
         Timer t(h, "k_pulse_sparse");
-        if (small) WFS_LAUNCH_F(h, K_PULSE_SPARSE_64, dim3((unsigned)h->n_sparse_tiles), dim3(64), lds, d, ps);
-        else WFS_LAUNCH_F(h, K_PULSE_SPARSE_256, dim3((unsigned)h->n_sparse_tiles), dim3(256), lds, d, ps);
+        if (small) WFS_LAUNCH_F(h, K_PULSE_SPARSE_64, dim3((unsigned)h->run.n_sparse_tiles), dim3(64), lds, d, ps);
+        else WFS_LAUNCH_F(h, K_PULSE_SPARSE_256, dim3((unsigned)h->run.n_sparse_tiles), dim3(256), lds, d, ps);
     }
-    if (h->n_dense_tiles > 0 && h->generic_geom) {        // any digitiser geometry: one kernel for every tile
+    if (h->run.n_dense_tiles > 0 && h->generic_geom) {        // any digitiser geometry: one kernel for every tile
         PulseArgs pd = pa;
         pd.desc = h->tile_desc.as<TileDesc>() + r.first_dense;
         if (pd.cur_off) pd.cur_off += r.first_dense;
@@ -2060,14 +2062,14 @@ static int run_pulses(wfs_handle *h, RunState &r)
         lds = (lds + 15) / 16 * 16;
         if (lds > 128 * 1024) return h->fail(WFS_E_CAPACITY, "sample_duration x template length too large for the LDS tables of k_pulse_generic");
         Timer t(h, "k_pulse_generic");
-        WFS_LAUNCH_F(h, K_PULSE_GENERIC, dim3((unsigned)h->n_dense_tiles), dim3(256), lds, d, pd);
-    } else if (h->n_dense_tiles > 0) {
+        WFS_LAUNCH_F(h, K_PULSE_GENERIC, dim3((unsigned)h->run.n_dense_tiles), dim3(256), lds, d, pd);
+    } else if (h->run.n_dense_tiles > 0) {
         PulseArgs pd = pa;
         pd.active_tiles = h->active_tiles.as<i32>() + r.first_dense;
         pd.desc = h->tile_desc.as<TileDesc>() + r.first_dense;
         if (pd.cur_off) pd.cur_off += r.first_dense;
         // chunks of TPB live samples per pass (TPB + 21 start-bin rows of 80 bytes in LDS: 22 KB for 256 -> 7 workgroups per CU)
-        const i64 n_live_max = h->max_nb_dense + d.tlen - 1;
+        const i64 n_live_max = h->run.max_nb_dense + d.tlen - 1;
         const bool small = n_live_max <= 128;
         const int tpb = small ? 128 : 256;
         const int NWIN_MAX = 8;
@@ -2075,15 +2077,15 @@ static int run_pulses(wfs_handle *h, RunState &r)
         // registers; longer tiles: several workgroups per tile (each re-reads the tile's photons for its chunks)
         // (the resident form holds at most tpb x DENSE_PPT photons: a longer tile must take the windowed form even when its live samples
         // fit one chunk and n_win comes out as 1 -- choosing the form by n_win dropped the photons behind the register batch)
-        const bool resident = h->max_tile_dense <= (i64)tpb * DENSE_PPT;
+        const bool resident = h->run.max_tile_dense <= (i64)tpb * DENSE_PPT;
         pd.n_win = resident ? 1 : (int)std::min<i64>(NWIN_MAX, std::max<i64>(1, (n_live_max + tpb - 1) / tpb));
         pd.W = tpb;
         const TemplateArg tp = fill_template_arg(h);
         size_t lds = (size_t)(tpb + d.tlen - 1) * d.dt * 8 + (size_t)8 * (tpb / 64) * 8 + 64 + TAP_LDS_BYTES(256) + 16;
         lds = (lds + 15) / 16 * 16;
-        pd.sparse_max = (h->keep_currents & DBG_FORCE_DENSE) ? -1 : h->tap_sparse_max;      // (force_dense: every wave takes the dense gather)
+        pd.sparse_max = (h->debug_bits & DBG_FORCE_DENSE) ? -1 : h->tap_sparse_max;      // (force_dense: every wave takes the dense gather)
         pd.spe_lds = ((size_t)(tpb + d.tlen - 1) * d.dt >= 2001) ? 1 : 0;
-        const unsigned grid = (unsigned)(h->n_dense_tiles * pd.n_win);
+        const unsigned grid = (unsigned)(h->run.n_dense_tiles * pd.n_win);
         Timer t(h, "k_pulse_dense");
         if (resident) {
             if (small) WFS_LAUNCH_F(h, K_PULSE_128_RES, dim3(grid), dim3(128), lds, d, pd, tp);
@@ -2097,10 +2099,10 @@ static int run_pulses(wfs_handle *h, RunState &r)
     if (r.tiles_done && h->h_scal->n_shared_rows > 0) {   // tiles of k_s2_tile that share their row with other pulses: added into the row's accumulators
         TileAddArgs ta{h->set_cluster.as<i32>(), h->cl_group.as<i32>(), h->row_lo.as<i64>(), h->acc_off.as<i64>(), h->row_cnt.as<i32>(), h->raw.as<i32>()};
         Timer t(h, "k_tile_add");
-        if (h->n_fused_tiles > 0) hipLaunchKernelGGL(k_tile_add, dim3((unsigned)h->n_fused_tiles), dim3(256), 0, h->stream, d, h->fuse_args, ta);
-        if (h->n_bright_tiles > 0) {                       // (the tiles of k_s2_bright: their own stretch of the work list)
+        if (h->run.n_fused_tiles > 0) hipLaunchKernelGGL(k_tile_add, dim3((unsigned)h->run.n_fused_tiles), dim3(256), 0, h->stream, d, h->fuse_args, ta);
+        if (h->run.n_bright_tiles > 0) {                       // (the tiles of k_s2_bright: their own stretch of the work list)
             FuseArgs fb = h->fuse_args; fb.tiles += h->bright_args.list_first;
-            hipLaunchKernelGGL(k_tile_add, dim3((unsigned)h->n_bright_tiles), dim3(256), 0, h->stream, d, fb, ta);
+            hipLaunchKernelGGL(k_tile_add, dim3((unsigned)h->run.n_bright_tiles), dim3(256), 0, h->stream, d, fb, ta);
         }
     }
     return WFS_OK;
@@ -2111,28 +2113,27 @@ static int run_rows(wfs_handle *h, RunState &r)
 {
     const WfsDev &d = h->dev;
     const GeomArgs &ga = r.ga; const PulseArgs &pa = r.pa; ZleArgs &za = r.za;
-    const i64 S = h->n_sets, CG = r.CG;
+    const i64 S = h->batch.n_sets, CG = r.CG;
     const i64 RS = r.RS = CG * d.row_slots;
-    TRY(ensure(h, h->itv_left, (size_t)h->n_itv_slots * 8 + 16)); TRY(ensure(h, h->itv_right, (size_t)h->n_itv_slots * 8 + 16));      // (+16: k_pack reads the first two slots of a row whatever its capacity)
+    TRY(ensure(h, h->itv_left, (size_t)h->run.n_itv_slots * 8 + 16)); TRY(ensure(h, h->itv_right, (size_t)h->run.n_itv_slots * 8 + 16));      // (+16: k_pack reads the first two slots of a row whatever its capacity)
     TRY(ensure(h, h->itv_n, (size_t)RS * 4)); TRY(ensure(h, h->row_nrec, (size_t)RS * 4));
     FillGroup fg(h, "fills_rows");
     TRY(fg.zero(h->itv_n.p, (size_t)RS * 4)); TRY(fg.zero(h->row_nrec.p, (size_t)RS * 4));
-    za.active_rows = h->active_rows.as<i32>(); za.n_active_rows = h->n_active_rows; za.row_lo = h->row_lo.as<i64>(); za.row_hi = h->row_hi.as<i64>();
+    za.active_rows = h->active_rows.as<i32>(); za.n_active_rows = h->run.n_active_rows; za.row_lo = h->row_lo.as<i64>(); za.row_hi = h->row_hi.as<i64>();
     za.acc_off = h->acc_off.as<i64>(); za.raw = h->raw.as<i32>(); za.grp_left = h->grp_left.as<i64>(); za.grp_ixrand = h->grp_ixrand.as<i64>();
     za.itv_off = h->itv_off.as<i64>(); za.itv_left = h->itv_left.as<i64>(); za.itv_right = h->itv_right.as<i64>();
     za.itv_n = h->itv_n.as<i32>(); za.row_nrec = h->row_nrec.as<i32>(); za.spr = WFS_SPR;
     if (r.tiles_done) { za.tile_done = ga.tile_done; za.n_done = ga.n_done; za.row_cnt = ga.row_cnt; za.row_tile = ga.row_tile; za.ins_bcap = ga.ins_bcap; za.ins_boff = ga.ins_boff; za.tbuf = h->tbuf.as<i32>(); }
-    za.n_front = h->n_front_rows; za.rows_cap = CG * d.row_slots;
-    if (d.sum_channel >= 0) { za.sum_lo = h->sum_lo.as<i64>(); za.sum_hi = h->sum_hi.as<i64>(); za.sum_off = h->sum_off.as<i64>(); za.sum_base = h->sum_base; }
-    if (h->n_res_rows > 0) {
-        TRY(ensure(h, h->fin, (size_t)h->s_fin * 2 + 16));
-        TRY(ensure(h, h->res_rows, (size_t)h->n_res_rows * sizeof(ResRow)));
+    za.n_front = h->run.n_front_rows; za.rows_cap = CG * d.row_slots;
+    if (d.sum_channel >= 0) { za.sum_lo = h->sum_lo.as<i64>(); za.sum_hi = h->sum_hi.as<i64>(); za.sum_off = h->sum_off.as<i64>(); za.sum_base = h->run.sum_base; }
+    if (h->run.n_res_rows > 0) {
+        TRY(ensure(h, h->fin, (size_t)h->run.s_fin * 2 + 16));
+        TRY(ensure(h, h->res_rows, (size_t)h->run.n_res_rows * sizeof(ResRow)));
         za.res_toff = h->res_toff.as<i64>(); za.fin_off = h->fin_off.as<i64>(); za.fin = h->fin.as<int16_t>();
-        za.n_short = h->n_short_rows; za.res_long = h->res_long.as<i32>(); za.res_rows = h->res_rows.as<ResRow>();
+        za.n_short = h->run.n_short_rows; za.res_long = h->res_long.as<i32>(); za.res_rows = h->res_rows.as<ResRow>();
     }
-    h->row_dbg_total = 0;
-    if ((h->keep_currents & DBG_CURRENTS) && h->n_active_rows > 0) {
-        std::vector<i32> ar((size_t)h->n_active_rows);
+    if ((h->debug_bits & DBG_CURRENTS) && h->run.n_active_rows > 0) {
+        std::vector<i32> ar((size_t)h->run.n_active_rows);
         std::vector<i64> lo((size_t)CG * d.n_tpc), hi((size_t)CG * d.n_tpc);
         HIPCHK(hipMemcpy(ar.data(), h->active_rows.p, ar.size() * 4, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(lo.data(), h->row_lo.p, lo.size() * 8, hipMemcpyDeviceToHost));
@@ -2148,21 +2149,21 @@ static int run_rows(wfs_handle *h, RunState &r)
             if (slot_is_sum(d, slot)) off[k + 1] = off[k] + shi[g] - slo[g] + 1 + 2 * d.tw;
             else off[k + 1] = off[k] + hi[g * d.n_tpc + c] - lo[g * d.n_tpc + c] + 1 + 2 * d.tw;
         }
-        h->row_dbg_total = off.back();
+        h->run.row_dbg_total = off.back();
         TRY(upload(h, h->row_dbg_off, off.data(), off.size() * 8));
-        TRY(ensure(h, h->row_dbg, (size_t)h->row_dbg_total * 4));
+        TRY(ensure(h, h->row_dbg, (size_t)h->run.row_dbg_total * 4));
         HIPCHK(hipStreamSynchronize(h->stream));
         za.row_dbg = h->row_dbg.as<i32>(); za.row_dbg_off = h->row_dbg_off.as<i64>();
     }
-    TRY(ensure(h, h->row_desc, (size_t)h->n_active_rows * sizeof(RowDesc))); za.desc = h->row_desc.as<RowDesc>();
+    TRY(ensure(h, h->row_desc, (size_t)h->run.n_active_rows * sizeof(RowDesc))); za.desc = h->row_desc.as<RowDesc>();
     if (h->sort_records) {      // key_origin / key_end: first sample / end of the last row of the batch (k_row_desc): origin and span of the sort keys
         za.key_base = h->scal.as<WfsScal>();
         TRY(fg.i64s(&za.key_base->key_origin, 1, I64_MAX)); TRY(fg.i64s(&za.key_base->key_end, 1, I64_MIN));
     }
     TRY(fg.flush());
-    if (h->n_active_rows > 0) { Timer t(h, "k_row_desc"); hipLaunchKernelGGL(k_row_desc, dim3(nblocks(h->n_active_rows, 256)), dim3(256), 0, h->stream, d, za); }
+    if (h->run.n_active_rows > 0) { Timer t(h, "k_row_desc"); hipLaunchKernelGGL(k_row_desc, dim3(nblocks(h->run.n_active_rows, 256)), dim3(256), 0, h->stream, d, za); }
     r.noise_kind = !d.enable_noise ? 0 : (d.nm_cells ? (d.nc_taps ? 4 : 3) : (d.noise_f ? 2 : 1));
-    if (h->n_res_rows > 0) {        // resident rows: pulses, finished samples and intervals by one wave per row
+    if (h->run.n_res_rows > 0) {        // resident rows: pulses, finished samples and intervals by one wave per row
         PulseArgs pr = pa;
         pr.desc = h->res_desc.as<TileDesc>(); pr.currents = nullptr; pr.cur_off = nullptr;
         // two launches: the rows of at most RES_SHORT_LEN samples at full occupancy, the longer ones with LDS for the longest of them
@@ -2170,9 +2171,9 @@ static int run_rows(wfs_handle *h, RunState &r)
 #define K_ROW_PULSE_SHORT(F) k_row_pulse<NK, F, false>
 #define K_ROW_PULSE_LONG(F) k_row_pulse<NK, F, true>
         for (int part = 0; part < 2; part++) {
-            const i64 first = part == 0 ? 0 : h->n_short_rows, n_rows = part == 0 ? h->n_short_rows : h->n_res_rows - h->n_short_rows;
+            const i64 first = part == 0 ? 0 : h->run.n_short_rows, n_rows = part == 0 ? h->run.n_short_rows : h->run.n_res_rows - h->run.n_short_rows;
             if (n_rows <= 0) continue;
-            const i32 region = part == 0 ? RES_SHORT_LEN : (i32)((std::min<i64>(h->max_res_len, h->res_max_len) + 255) / 256 * 256);
+            const i32 region = part == 0 ? RES_SHORT_LEN : (i32)((std::min<i64>(h->run.max_res_len, h->res_max_len) + 255) / 256 * 256);
             const size_t lds = ROW_LDS_FIXED + (size_t)4 * region * 4;
             const dim3 grid(nblocks(n_rows, 4));
             with_noise_kind(r.noise_kind, [&](auto nk) {
@@ -2191,16 +2192,16 @@ static int run_rows(wfs_handle *h, RunState &r)
 
     // (WFS_SUM_SKIP_KERNEL: A/B runs that price what the switch costs apart from the kernel -- bottom rows off the resident path, one
     // more row per window through k_zle / k_pack; the sum rows then hold whatever the buffer held)
-    if (h->n_sum_chunks > 0 && !getenv("WFS_SUM_SKIP_KERNEL")) {      // the windows' sum rows from their bottom rows: every accumulator and tile buffer is complete here (k_tile_add included)
-        if (h->n_sum_chunks > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "more than 2^31 chunks of sum rows in one batch");
+    if (h->run.n_sum_chunks > 0 && !getenv("WFS_SUM_SKIP_KERNEL")) {      // the windows' sum rows from their bottom rows: every accumulator and tile buffer is complete here (k_tile_add included)
+        if (h->run.n_sum_chunks > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "more than 2^31 chunks of sum rows in one batch");
         SumArgs sa{h->sum_chunk_off.as<i64>(), CG, h->sum_lo.as<i64>(), h->sum_off.as<i64>(), h->sum_len.as<i32>(),
                    h->row_lo.as<i64>(), h->row_hi.as<i64>(), h->acc_off.as<i64>(), h->raw.as<i32>(), r.tiles_done ? h->tbuf.as<i32>() : nullptr,
-                   r.tiles_done ? ga.tile_done : nullptr, ga.row_cnt, ga.row_tile, ga.ins_bcap, ga.ins_boff, ga.n_done, h->raw.as<i32>() + h->sum_base};
+                   r.tiles_done ? ga.tile_done : nullptr, ga.row_cnt, ga.row_tile, ga.ins_bcap, ga.ins_boff, ga.n_done, h->raw.as<i32>() + h->run.sum_base};
         Timer t(h, "k_sum_signal");
-        hipLaunchKernelGGL(k_sum_signal, dim3((unsigned)h->n_sum_chunks), dim3(256), 0, h->stream, d, sa);
+        hipLaunchKernelGGL(k_sum_signal, dim3((unsigned)h->run.n_sum_chunks), dim3(256), 0, h->stream, d, sa);
     }
-    if (h->n_front_rows > 0) {
-        Timer t(h, "k_zle"); const dim3 grid(nblocks(h->n_front_rows, 4));
+    if (h->run.n_front_rows > 0) {
+        Timer t(h, "k_zle"); const dim3 grid(nblocks(h->run.n_front_rows, 4));
         with_noise_kind(r.noise_kind, [&](auto nk) { hipLaunchKernelGGL(k_zle<decltype(nk)::value>, grid, dim3(256), 0, h->stream, d, za); });
     }
     return WFS_OK;
@@ -2214,20 +2215,20 @@ static int run_records(wfs_handle *h, RunState &r)
     const i64 RS = r.RS;
     TRY(scan(h, h->row_nrec.as<i32>(), RS, h->rec_off, &WfsScal::n_records));
     TRY(read_scal(h));
-    h->n_records = h->h_scal->n_records;
+    h->run.n_records = h->h_scal->n_records;
     // the other arena: the previous batch's records may still be on their way to the host
     h->rec_cur ^= 1;
     if (h->rec_pending[h->rec_cur]) { HIPCHK(hipEventSynchronize(h->rec_copied[h->rec_cur])); h->rec_pending[h->rec_cur] = false; }
-    TRY(ensure(h, h->records_buf(), (size_t)h->n_records * 244));
-    za.rec_off = h->rec_off.as<i64>(); za.records = h->records_buf().as<uint8_t>(); za.rec_capacity = h->n_records;
-    if (h->sort_records && h->n_records > 1 && h->n_active_rows > 0) {
+    TRY(ensure(h, h->records_buf(), (size_t)h->run.n_records * 244));
+    za.rec_off = h->rec_off.as<i64>(); za.records = h->records_buf().as<uint8_t>(); za.rec_capacity = h->run.n_records;
+    if (h->sort_records && h->run.n_records > 1 && h->run.n_active_rows > 0) {
         // records by (time, channel): keys per record, one radix sort of the batch, k_pack writes to the sorted slots
-        const i64 NR = h->n_records;
+        const i64 NR = h->run.n_records;
         if (NR > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "more than 2^31 records in one batch (the device sort takes an int count)");
         TRY(ensure(h, h->rec_key, (size_t)NR * 8)); TRY(ensure(h, h->rec_key2, (size_t)NR * 8));
         TRY(ensure(h, h->rec_val, (size_t)NR * 4)); TRY(ensure(h, h->rec_val2, (size_t)NR * 4)); TRY(ensure(h, h->rec_dest, (size_t)NR * 4));
         za.rec_key = h->rec_key.as<u64>(); za.rec_val = h->rec_val.as<u32>();
-        { Timer t(h, "k_rec_keys"); hipLaunchKernelGGL(k_rec_keys, dim3(nblocks(h->n_active_rows, 4)), dim3(256), 0, h->stream, d, za); }
+        { Timer t(h, "k_rec_keys"); hipLaunchKernelGGL(k_rec_keys, dim3(nblocks(h->run.n_active_rows, 4)), dim3(256), 0, h->stream, d, za); }
         // rocPRIM's radix sort, over the key bits that are in use only: (samples the batch spans) << 12 | channel
         unsigned end_bit = 13;
         { const u64 span = (u64)std::max<i64>(h->h_scal->key_end - h->h_scal->key_origin, 1); while (end_bit < 64 && ((span << 12) >> end_bit) != 0) end_bit++; }
@@ -2238,20 +2239,20 @@ static int run_records(wfs_handle *h, RunState &r)
         { Timer t(h, "k_invert_perm"); hipLaunchKernelGGL(k_invert_perm, dim3(nblocks(NR, 256)), dim3(256), 0, h->stream, h->rec_val2.as<u32>(), h->rec_dest.as<u32>(), NR); }
         za.rec_dest = h->rec_dest.as<u32>();
     }
-    if (h->n_active_rows > 0 && h->n_records > 0) {
-        TRY(ensure(h, h->pack_desc, (size_t)h->n_active_rows * sizeof(PackDesc))); za.pdesc = h->pack_desc.as<PackDesc>();
-        { Timer t(h, "k_pack_desc"); hipLaunchKernelGGL(k_pack_desc, dim3(nblocks(h->n_active_rows, 256)), dim3(256), 0, h->stream, za); }
-        if (h->n_res_rows > 0) {
-            PackResArgs pr{h->pack_desc.as<PackDesc>() + h->n_front_rows, h->fin.as<int16_t>(), za.itv_left, za.itv_right, za.records, za.rec_dest, za.rec_capacity, h->n_res_rows, za.spr, (i32)d.dt};
-            Timer t(h, "k_pack_res"); hipLaunchKernelGGL(k_pack_res, dim3(nblocks(h->n_res_rows, 4)), dim3(256), 0, h->stream, pr);
+    if (h->run.n_active_rows > 0 && h->run.n_records > 0) {
+        TRY(ensure(h, h->pack_desc, (size_t)h->run.n_active_rows * sizeof(PackDesc))); za.pdesc = h->pack_desc.as<PackDesc>();
+        { Timer t(h, "k_pack_desc"); hipLaunchKernelGGL(k_pack_desc, dim3(nblocks(h->run.n_active_rows, 256)), dim3(256), 0, h->stream, za); }
+        if (h->run.n_res_rows > 0) {
+            PackResArgs pr{h->pack_desc.as<PackDesc>() + h->run.n_front_rows, h->fin.as<int16_t>(), za.itv_left, za.itv_right, za.records, za.rec_dest, za.rec_capacity, h->run.n_res_rows, za.spr, (i32)d.dt};
+            Timer t(h, "k_pack_res"); hipLaunchKernelGGL(k_pack_res, dim3(nblocks(h->run.n_res_rows, 4)), dim3(256), 0, h->stream, pr);
         }
-        if (h->n_front_rows > 0) {
-            Timer t(h, "k_pack"); const dim3 grid(nblocks(h->n_front_rows, 4));
+        if (h->run.n_front_rows > 0) {
+            Timer t(h, "k_pack"); const dim3 grid(nblocks(h->run.n_front_rows, 4));
             with_noise_kind(r.noise_kind, [&](auto nk) { hipLaunchKernelGGL(k_pack<decltype(nk)::value>, grid, dim3(256), 0, h->stream, d, za); });
         }
     }
     {   // totals of wfs_get_counts: afterpulse sets carry no truth (rawdata.py:322-323)
-        const i64 n_prim = (!h->injected && h->ap_active) ? h->n_psets : h->n_sets;
+        const i64 n_prim = h->batch.ap_sets ? h->batch.n_psets : h->batch.n_sets;
         const i64 work = std::max<i64>(RS, n_prim);
         hipLaunchKernelGGL(k_counts, dim3((unsigned)std::min<i64>(nblocks(work, 256), 128)), dim3(256), 0, h->stream, h->itv_n.as<i32>(), RS, h->truth.as<double>(), n_prim, h->scal.as<WfsScal>());
     }
@@ -2264,35 +2265,35 @@ static int run_records(wfs_handle *h, RunState &r)
 int wfs_run(wfs_handle *h)
 try {
     if (!h) return WFS_E_INVALID;
-    if (!h->batch_loaded) return h->fail(WFS_E_STATE, "no batch loaded");
-    if (h->dev_rows_pending && from_generator(h)) return h->fail(WFS_E_STATE, "instructions with cdf_row -1: call wfs_eval_pattern_rows before wfs_run");
-    h->ran = false; h->gen_done = false; h->gen_order_ready = false;
+    if (h->batch.kind == BatchKind::None) return h->fail(WFS_E_STATE, "no batch loaded");
+    if (h->batch.dev_rows_pending) return h->fail(WFS_E_STATE, "instructions with cdf_row -1: call wfs_eval_pattern_rows before wfs_run");
+    h->state().run_begins();
     HIPCHK(hipSetDevice(h->device));
     clear_times(h->times);
     TRY(run_input(h));
-    h->gen_done = true;
-    if (h->keep_currents & DBG_GEN_ONLY) { HIPCHK(hipStreamSynchronize(h->stream)); return WFS_OK; }      // wfs_set_debug bit 2: photon generation only
+    h->state().generation_done();
+    if (h->debug_bits & DBG_GEN_ONLY) { HIPCHK(hipStreamSynchronize(h->stream)); return WFS_OK; }      // wfs_set_debug bit 2: photon generation only
     RunState r;
     TRY(run_geometry(h, r));
     TRY(run_pulses(h, r));
     TRY(run_rows(h, r));
     TRY(run_records(h, r));
-    h->ran = true;
+    h->state().run_complete();
     return WFS_OK;
 } WFS_CATCH(h)
 
 int wfs_get_counts(wfs_handle *h, wfs_counts *out)
 try {
     if (!h || !out) return WFS_E_INVALID;
-    if (!h->ran) return h->fail(WFS_E_STATE, "wfs_run has not completed");
+    if (!run_finished(h)) return h->fail(WFS_E_STATE, "wfs_run has not completed");
     wfs_counts c{};
-    c.n_instructions = h->n_ins; c.n_pulse_sets = h->n_sets; c.n_emitters = h->n_emitters; c.n_photons = h->n_photons + ((!h->injected && h->ap_active) ? h->n_ap_photons : 0);
+    c.n_instructions = h->batch.n_ins; c.n_pulse_sets = h->batch.n_sets; c.n_emitters = h->batch.n_emitters; c.n_photons = n_primary_photons(h) + h->run.n_ap_photons;
     const bool tiles_done = tiles_made(h);
-    c.n_tiles = h->n_active_tiles + (tiles_done ? h->n_fused_tiles : 0) + h->n_res_tiles; c.n_groups = h->n_groups; c.n_rows = h->n_active_rows;
-    c.n_raw_samples = h->s_raw + (tiles_done ? h->s_raw_direct : 0) + h->s_res + h->s_sum;
-    c.n_records = h->n_records;
+    c.n_tiles = h->run.n_active_tiles + (tiles_done ? h->run.n_fused_tiles : 0) + h->run.n_res_tiles; c.n_groups = h->run.n_groups; c.n_rows = h->run.n_active_rows;
+    c.n_raw_samples = h->run.s_raw + (tiles_done ? h->run.s_raw_direct : 0) + h->run.s_res + h->run.s_sum;
+    c.n_records = h->run.n_records;
     c.n_intervals = h->h_scal->n_intervals; c.n_pe = h->h_scal->n_pe;          // reduced on the device at the end of wfs_run (k_counts)
-    *out = c; h->counts = c;
+    *out = c;
     return WFS_OK;
 } WFS_CATCH(h)
 
@@ -2300,16 +2301,16 @@ const void *wfs_records_dev_ptr(wfs_handle *h) { return h ? h->records_buf().p :
 
 int wfs_copy_records(wfs_handle *h, void *dst, int64_t cap)
 try {
-    if (!h || !h->ran) return WFS_E_STATE;
-    if (cap < h->n_records) return h->fail(WFS_E_CAPACITY, "record buffer too small");
-    if (h->n_records) HIPCHK(hipMemcpy(dst, h->records_buf().p, (size_t)h->n_records * 244, hipMemcpyDeviceToHost));
+    if (!h || !run_finished(h)) return WFS_E_STATE;
+    if (cap < h->run.n_records) return h->fail(WFS_E_CAPACITY, "record buffer too small");
+    if (h->run.n_records) HIPCHK(hipMemcpy(dst, h->records_buf().p, (size_t)h->run.n_records * 244, hipMemcpyDeviceToHost));
     return WFS_OK;
 } WFS_CATCH(h)
 
 int wfs_copy_records_range(wfs_handle *h, void *dst, int64_t first, int64_t count)
 try {
-    if (!h || !h->ran) return WFS_E_STATE;
-    if (first < 0 || count < 0 || first + count > h->n_records) return h->fail(WFS_E_INVALID, "record range outside the batch");
+    if (!h || !run_finished(h)) return WFS_E_STATE;
+    if (first < 0 || count < 0 || first + count > h->run.n_records) return h->fail(WFS_E_INVALID, "record range outside the batch");
     if (count) HIPCHK(hipMemcpy(dst, (const uint8_t *)h->records_buf().p + (size_t)first * 244, (size_t)count * 244, hipMemcpyDeviceToHost));
     return WFS_OK;
 } WFS_CATCH(h)
@@ -2326,8 +2327,8 @@ int wfs_host_unregister(void *ptr) try { return (ptr && hipHostUnregister(ptr) =
 
 int wfs_copy_records_range_async(wfs_handle *h, void *dst, int64_t first, int64_t count)
 try {
-    if (!h || !h->ran) return WFS_E_STATE;
-    if (first < 0 || count < 0 || first + count > h->n_records) return h->fail(WFS_E_INVALID, "record range outside the batch");
+    if (!h || !run_finished(h)) return WFS_E_STATE;
+    if (first < 0 || count < 0 || first + count > h->run.n_records) return h->fail(WFS_E_INVALID, "record range outside the batch");
     HIPCHK(hipSetDevice(h->device));
     if (count) HIPCHK(hipMemcpyAsync(dst, (const uint8_t *)h->records_buf().p + (size_t)first * 244, (size_t)count * 244, hipMemcpyDeviceToHost, h->copy_stream));
     HIPCHK(hipEventRecord(h->rec_copied[h->rec_cur], h->copy_stream));
@@ -2347,9 +2348,9 @@ try {
 
 int wfs_copy_records_dev(wfs_handle *h, void *dst, int64_t cap)
 try {
-    if (!h || !h->ran) return WFS_E_STATE;
-    if (cap < h->n_records) return h->fail(WFS_E_CAPACITY, "record buffer too small");
-    if (h->n_records) { HIPCHK(hipMemcpyAsync(dst, h->records_buf().p, (size_t)h->n_records * 244, hipMemcpyDeviceToDevice, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); }
+    if (!h || !run_finished(h)) return WFS_E_STATE;
+    if (cap < h->run.n_records) return h->fail(WFS_E_CAPACITY, "record buffer too small");
+    if (h->run.n_records) { HIPCHK(hipMemcpyAsync(dst, h->records_buf().p, (size_t)h->run.n_records * 244, hipMemcpyDeviceToDevice, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); }
     return WFS_OK;
 } WFS_CATCH(h)
 
@@ -2364,8 +2365,8 @@ try {
 
 int wfs_copy_groups(wfs_handle *h, int64_t *left, int64_t *right, int64_t *first_record, int64_t *ix_rand)
 try {
-    if (!h || !h->ran) return WFS_E_STATE;
-    const i64 G = h->n_groups;
+    if (!h || !run_complete(h)) return WFS_E_STATE;
+    const i64 G = h->run.n_groups;
     if (left) HIPCHK(hipMemcpy(left, h->grp_left.p, (size_t)G * 8, hipMemcpyDeviceToHost));
     if (right) HIPCHK(hipMemcpy(right, h->grp_right.p, (size_t)G * 8, hipMemcpyDeviceToHost));
     if (ix_rand) HIPCHK(hipMemcpy(ix_rand, h->grp_ixrand.p, (size_t)G * 8, hipMemcpyDeviceToHost));
@@ -2376,13 +2377,13 @@ try {
 
 int wfs_copy_intervals(wfs_handle *h, int32_t *group, int32_t *channel, int64_t *left, int64_t *right, int64_t *data_off, int64_t cap)
 try {
-    if (!h || !h->ran) return WFS_E_STATE;
+    if (!h || !run_complete(h)) return WFS_E_STATE;
     const WfsDev &d = h->dev;
-    const i64 RS = (h->n_clusters + 1) * d.row_slots;
-    std::vector<i32> n((size_t)RS); std::vector<i64> off((size_t)RS + 1), L((size_t)h->n_itv_slots), R((size_t)h->n_itv_slots);
+    const i64 RS = (h->batch.n_clusters + 1) * d.row_slots;
+    std::vector<i32> n((size_t)RS); std::vector<i64> off((size_t)RS + 1), L((size_t)h->run.n_itv_slots), R((size_t)h->run.n_itv_slots);
     HIPCHK(hipMemcpy(n.data(), h->itv_n.p, n.size() * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(off.data(), h->itv_off.p, off.size() * 8, hipMemcpyDeviceToHost));
-    if (h->n_itv_slots) {
+    if (h->run.n_itv_slots) {
         HIPCHK(hipMemcpy(L.data(), h->itv_left.p, L.size() * 8, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(R.data(), h->itv_right.p, R.size() * 8, hipMemcpyDeviceToHost));
     }
@@ -2404,11 +2405,11 @@ try {
 int wfs_copy_interval_data(wfs_handle *h, int16_t *data, int64_t cap)
 try {
     // unpack the records: fragments of one interval are consecutive
-    if (!h || !h->ran) return WFS_E_STATE;
-    std::vector<uint8_t> rec((size_t)h->n_records * 244);
-    if (h->n_records) HIPCHK(hipMemcpy(rec.data(), h->records_buf().p, rec.size(), hipMemcpyDeviceToHost));
+    if (!h || !run_finished(h)) return WFS_E_STATE;
+    std::vector<uint8_t> rec((size_t)h->run.n_records * 244);
+    if (h->run.n_records) HIPCHK(hipMemcpy(rec.data(), h->records_buf().p, rec.size(), hipMemcpyDeviceToHost));
     i64 k = 0;
-    for (i64 r = 0; r < h->n_records; r++) {
+    for (i64 r = 0; r < h->run.n_records; r++) {
         i32 len; memcpy(&len, &rec[(size_t)r * 244 + 8], 4);
         if (k + len > cap) return h->fail(WFS_E_CAPACITY, "interval data buffer too small");
         memcpy(data + k, &rec[(size_t)r * 244 + 24], (size_t)len * 2);
@@ -2419,12 +2420,12 @@ try {
 
 int wfs_copy_pulses(wfs_handle *h, int32_t *set, int32_t *channel, int64_t *left, int64_t *right, int64_t *nph, int64_t *cur_off, int64_t cap)
 try {
-    if (!h || !h->ran) return WFS_E_STATE;
+    if (!h || !run_finished(h)) return WFS_E_STATE;
     const WfsDev &d = h->dev;
-    const i64 A = h->n_active_tiles;
+    const i64 A = h->run.n_active_tiles;
     if (cap < A) return h->fail(WFS_E_CAPACITY, "pulse buffer too small");
-    std::vector<i32> at((size_t)A), cnt((size_t)h->n_tiles), tmn((size_t)h->n_tiles), tmx((size_t)h->n_tiles);
-    std::vector<i64> t0((size_t)h->n_sets);
+    std::vector<i32> at((size_t)A), cnt((size_t)h->batch.n_tiles), tmn((size_t)h->batch.n_tiles), tmx((size_t)h->batch.n_tiles);
+    std::vector<i64> t0((size_t)h->batch.n_sets);
     if (A) HIPCHK(hipMemcpy(at.data(), h->active_tiles.p, at.size() * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(cnt.data(), h->tile_count.p, cnt.size() * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(tmn.data(), h->tile_tmin.p, tmn.size() * 4, hipMemcpyDeviceToHost));
@@ -2443,28 +2444,28 @@ try {
 
 int wfs_copy_currents(wfs_handle *h, double *cur, int64_t cap)
 try {
-    if (!h || !h->ran) return WFS_E_STATE;
-    if (!(h->keep_currents & DBG_CURRENTS)) return h->fail(WFS_E_STATE, "wfs_set_debug(h, 1) before wfs_run");
-    if (cap < h->cur_total) return h->fail(WFS_E_CAPACITY, "current buffer too small");
-    if (h->cur_total) HIPCHK(hipMemcpy(cur, h->currents.p, (size_t)h->cur_total * 8, hipMemcpyDeviceToHost));
+    if (!h || !run_finished(h)) return WFS_E_STATE;
+    if (!(h->debug_bits & DBG_CURRENTS)) return h->fail(WFS_E_STATE, "wfs_set_debug(h, 1) before wfs_run");
+    if (cap < h->run.cur_total) return h->fail(WFS_E_CAPACITY, "current buffer too small");
+    if (h->run.cur_total) HIPCHK(hipMemcpy(cur, h->currents.p, (size_t)h->run.cur_total * 8, hipMemcpyDeviceToHost));
     return WFS_OK;
 } WFS_CATCH(h)
 
 int wfs_copy_rows(wfs_handle *h, int32_t *group, int32_t *channel, int64_t *left, int64_t *right, int64_t *data_off, int64_t cap)
 try {
-    if (!h || !h->ran) return WFS_E_STATE;
-    if (!(h->keep_currents & DBG_CURRENTS)) return h->fail(WFS_E_STATE, "wfs_set_debug(h, 1) before wfs_run");
+    if (!h || !run_complete(h)) return WFS_E_STATE;
+    if (!(h->debug_bits & DBG_CURRENTS)) return h->fail(WFS_E_STATE, "wfs_set_debug(h, 1) before wfs_run");
     const WfsDev &d = h->dev;
-    const i64 A = h->n_active_rows;
+    const i64 A = h->run.n_active_rows;
     if (cap < A) return h->fail(WFS_E_CAPACITY, "row buffer too small");
-    std::vector<i32> ar((size_t)A); std::vector<i64> lo((size_t)(h->n_clusters + 1) * d.n_tpc), hi(lo.size()), gl((size_t)h->n_groups);
+    std::vector<i32> ar((size_t)A); std::vector<i64> lo((size_t)(h->batch.n_clusters + 1) * d.n_tpc), hi(lo.size()), gl((size_t)h->run.n_groups);
     if (A) HIPCHK(hipMemcpy(ar.data(), h->active_rows.p, ar.size() * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(lo.data(), h->row_lo.p, lo.size() * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(hi.data(), h->row_hi.p, hi.size() * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(gl.data(), h->grp_left.p, gl.size() * 8, hipMemcpyDeviceToHost));
     std::vector<i64> slo, shi;
     if (d.sum_channel >= 0) {
-        slo.resize((size_t)h->n_clusters + 1); shi.resize(slo.size());
+        slo.resize((size_t)h->batch.n_clusters + 1); shi.resize(slo.size());
         HIPCHK(hipMemcpy(slo.data(), h->sum_lo.p, slo.size() * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(shi.data(), h->sum_hi.p, shi.size() * 8, hipMemcpyDeviceToHost));
     }
     i64 off = 0;
@@ -2482,21 +2483,21 @@ try {
 
 int wfs_copy_row_data(wfs_handle *h, int32_t *data, int64_t cap)
 try {
-    if (!h || !h->ran) return WFS_E_STATE;
-    if (cap < h->row_dbg_total) return h->fail(WFS_E_CAPACITY, "row data buffer too small");
-    if (h->row_dbg_total) HIPCHK(hipMemcpy(data, h->row_dbg.p, (size_t)h->row_dbg_total * 4, hipMemcpyDeviceToHost));
+    if (!h || !run_complete(h)) return WFS_E_STATE;
+    if (cap < h->run.row_dbg_total) return h->fail(WFS_E_CAPACITY, "row data buffer too small");
+    if (h->run.row_dbg_total) HIPCHK(hipMemcpy(data, h->row_dbg.p, (size_t)h->run.row_dbg_total * 4, hipMemcpyDeviceToHost));
     return WFS_OK;
 } WFS_CATCH(h)
 
 int wfs_copy_photons(wfs_handle *h, int64_t *set_off, int64_t *t, int16_t *ch, double *gain, uint8_t *dpe, int64_t cap)
 try {
-    if (!h || !h->ran) return WFS_E_STATE;
-    if (tiles_made(h) && !(h->keep_currents & DBG_KEEP_PHOTONS))
+    if (!h || !run_finished(h)) return WFS_E_STATE;
+    if (tiles_made(h) && !(h->debug_bits & DBG_KEEP_PHOTONS))
         return h->fail(WFS_E_STATE, "the photons of tile-generated instructions were not kept: wfs_set_debug bit 4 before wfs_run");
     const WfsDev &d = h->dev;
-    const i64 P = h->n_photons + ((!h->injected && h->ap_active) ? h->n_ap_photons : 0), T = h->n_tiles;
+    const i64 n_prim = n_primary_photons(h), P = n_prim + h->run.n_ap_photons, T = h->batch.n_tiles;
     if (cap < P) return h->fail(WFS_E_CAPACITY, "photon buffer too small");
-    std::vector<i64> off((size_t)T + 1), t0((size_t)h->n_sets);
+    std::vector<i64> off((size_t)T + 1), t0((size_t)h->batch.n_sets);
     std::vector<PhotonRec> recs((size_t)P);
     HIPCHK(hipMemcpy(off.data(), h->tile_off.p, off.size() * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(t0.data(), h->set_t0.p, t0.size() * 8, hipMemcpyDeviceToHost));
@@ -2504,17 +2505,17 @@ try {
     std::vector<double> gains((size_t)d.n_tpc), spe((size_t)2001 * d.n_spe), pg;
     HIPCHK(hipMemcpy(gains.data(), h->t_gains.p, gains.size() * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(spe.data(), h->t_spe.p, spe.size() * 8, hipMemcpyDeviceToHost));
-    const i64 gain_first = h->injected ? 0 : h->n_photons;         // ph_gain covers the explicit-gain photons only
-    if (P - gain_first > 0 && (h->injected || h->ap_active)) { pg.resize((size_t)(P - gain_first)); HIPCHK(hipMemcpy(pg.data(), h->ph_gain.p, pg.size() * 8, hipMemcpyDeviceToHost)); }
-    if (off[(size_t)T] != P) { char msg[160]; snprintf(msg, sizeof msg, "wfs_copy_photons: tile offsets end at %lld, %lld photons (T %lld, sets %lld)", (long long)off[(size_t)T], (long long)P, (long long)T, (long long)h->n_sets); return h->fail(WFS_E_STATE, msg); }
-    for (i64 s = 0; s <= h->n_sets; s++) set_off[s] = off[(size_t)s * d.n_tpc];
+    const i64 gain_first = h->batch.kind == BatchKind::Photons ? 0 : n_prim;        // ph_gain covers the explicit-gain photons only
+    if (P - gain_first > 0) { pg.resize((size_t)(P - gain_first)); HIPCHK(hipMemcpy(pg.data(), h->ph_gain.p, pg.size() * 8, hipMemcpyDeviceToHost)); }
+    if (off[(size_t)T] != P) { char msg[160]; snprintf(msg, sizeof msg, "wfs_copy_photons: tile offsets end at %lld, %lld photons (T %lld, sets %lld)", (long long)off[(size_t)T], (long long)P, (long long)T, (long long)h->batch.n_sets); return h->fail(WFS_E_STATE, msg); }
+    for (i64 s = 0; s <= h->batch.n_sets; s++) set_off[s] = off[(size_t)s * d.n_tpc];
     for (i64 tile = 0; tile < T; tile++) {
         i64 s = tile / d.n_tpc; int c = (int)(tile - s * d.n_tpc);
         const double *row = &spe[(size_t)(d.n_spe > 1 ? c : 0) * 2001];
         for (i64 p = off[tile]; p < off[tile + 1]; p++) {
             t[p] = t0[s] + recs[p].t; ch[p] = (int16_t)c;
             u32 g1 = recs[p].code & 0xffffu, g2 = recs[p].code >> 16;
-            if (h->injected || p >= h->n_photons) { gain[p] = pg[(size_t)(p - gain_first)]; dpe[p] = g2 != 0; }
+            if (p >= gain_first) { gain[p] = pg[(size_t)(p - gain_first)]; dpe[p] = g2 != 0; }
             else { double g = gains[c] * row[g1]; if (g2) g += gains[c] * row[g2]; gain[p] = g; dpe[p] = g2 != 0; }
         }
     }
@@ -2527,56 +2528,56 @@ try {
 // built once per generation.
 static int gen_order_tables(wfs_handle *h)
 {
-    if (h->gen_order_ready) return WFS_OK;
-    const i64 N = h->n_ins; const int nch = h->dev.n_tpc;
-    std::vector<i64> emo((size_t)N + 1), epo((size_t)h->n_emitters + 1);
+    if (h->run.gen_order_ready) return WFS_OK;
+    const i64 N = h->batch.n_ins; const int nch = h->dev.n_tpc;
+    std::vector<i64> emo((size_t)N + 1), epo((size_t)h->batch.n_emitters + 1);
     HIPCHK(hipMemcpy(emo.data(), h->em_off.p, emo.size() * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(epo.data(), h->em_ph_off.p, epo.size() * 8, hipMemcpyDeviceToHost));
-    h->go_fused.assign((size_t)N, 0); h->go_tile_count.clear();
-    const bool any_fused = h->fuse_on && n_tilegen_tiles(h) > 0;
+    h->run.go_fused.assign((size_t)N, 0); h->run.go_tile_count.clear();
+    const bool any_fused = h->run.fuse_on && n_tilegen_tiles(h) > 0;
     if (any_fused) {
-        HIPCHK(hipMemcpy(h->go_fused.data(), h->ins_fused.p, (size_t)N * 4, hipMemcpyDeviceToHost));
-        h->go_tile_count.resize((size_t)N * nch);
-        HIPCHK(hipMemcpy(h->go_tile_count.data(), h->tile_count.p, h->go_tile_count.size() * 4, hipMemcpyDeviceToHost));      // (one pulse set per instruction: tile = instruction * n_tpc + channel)
+        HIPCHK(hipMemcpy(h->run.go_fused.data(), h->ins_fused.p, (size_t)N * 4, hipMemcpyDeviceToHost));
+        h->run.go_tile_count.resize((size_t)N * nch);
+        HIPCHK(hipMemcpy(h->run.go_tile_count.data(), h->tile_count.p, h->run.go_tile_count.size() * 4, hipMemcpyDeviceToHost));      // (one pulse set per instruction: tile = instruction * n_tpc + channel)
     }
-    h->go_off.assign((size_t)N + 1, 0); h->go_block0.assign((size_t)N, 0);
+    h->run.go_off.assign((size_t)N + 1, 0); h->run.go_block0.assign((size_t)N, 0);
     for (i64 i = 0; i < N; i++) {
         i64 n = epo[(size_t)emo[i + 1]] - epo[(size_t)emo[i]];           // (0 for a tile-generated instruction: its electrons carry no photon numbers)
-        h->go_block0[i] = epo[(size_t)emo[i]];
-        if (any_fused && h->go_fused[i]) for (int c = 0; c < nch; c++) n += h->go_tile_count[(size_t)i * nch + c];
-        h->go_off[i + 1] = h->go_off[i] + n;
+        h->run.go_block0[i] = epo[(size_t)emo[i]];
+        if (any_fused && h->run.go_fused[i]) for (int c = 0; c < nch; c++) n += h->run.go_tile_count[(size_t)i * nch + c];
+        h->run.go_off[i + 1] = h->run.go_off[i] + n;
     }
-    h->gen_order_ready = true;
+    h->run.gen_order_ready = true;
     return WFS_OK;
 }
 
 int wfs_copy_instruction_photon_offsets(wfs_handle *h, int64_t *off, int64_t cap)
 try {
-    if (!h || !h->gen_done || h->injected || h->optical) return WFS_E_STATE;
-    const i64 N = h->n_ins;
+    if (!h || !generated(h)) return WFS_E_STATE;
+    const i64 N = h->batch.n_ins;
     if (cap < N + 1) return h->fail(WFS_E_CAPACITY, "offset buffer too small");
     TRY(gen_order_tables(h));
-    for (i64 i = 0; i <= N; i++) off[i] = h->go_off[(size_t)i];
+    for (i64 i = 0; i <= N; i++) off[i] = h->run.go_off[(size_t)i];
     return WFS_OK;
 } WFS_CATCH(h)
 
 int wfs_gather_photon_times(wfs_handle *h, int64_t n, const int64_t *index, int64_t *t_out)
 try {
-    if (!h || !h->gen_done || h->injected || h->optical) return WFS_E_STATE;
+    if (!h || !generated(h)) return WFS_E_STATE;
     if (n <= 0) return WFS_OK;
     if (!index || !t_out) return h->fail(WFS_E_INVALID, "wfs_gather_photon_times: null argument");
     TRY(gen_order_tables(h));
-    const i64 N = h->n_ins; const int nch = h->dev.n_tpc;
-    for (i64 i = 0; i < n; i++) if (index[i] < 0 || index[i] >= h->go_off[(size_t)N]) return h->fail(WFS_E_INVALID, "photon index out of range");
+    const i64 N = h->batch.n_ins; const int nch = h->dev.n_tpc;
+    for (i64 i = 0; i < n; i++) if (index[i] < 0 || index[i] >= h->run.go_off[(size_t)N]) return h->fail(WFS_E_INVALID, "photon index out of range");
     HIPCHK(hipSetDevice(h->device));
     // requests of the per-electron generator (index in ITS photon order) and of tile-generated instructions (instruction, channel, q)
     std::vector<i64> blk_idx, blk_pos, tile_pos; std::vector<TileTimeReq> treq;
     for (i64 k = 0; k < n; k++) {
-        const i64 i = (i64)(std::upper_bound(h->go_off.begin(), h->go_off.end(), (i64)index[k]) - h->go_off.begin()) - 1;
-        i64 local = index[k] - h->go_off[(size_t)i];
-        if (!h->go_fused[(size_t)i]) { blk_idx.push_back(h->go_block0[(size_t)i] + local); blk_pos.push_back(k); continue; }
+        const i64 i = (i64)(std::upper_bound(h->run.go_off.begin(), h->run.go_off.end(), (i64)index[k]) - h->run.go_off.begin()) - 1;
+        i64 local = index[k] - h->run.go_off[(size_t)i];
+        if (!h->run.go_fused[(size_t)i]) { blk_idx.push_back(h->run.go_block0[(size_t)i] + local); blk_pos.push_back(k); continue; }
         int c = 0;
-        const i32 *cnt = &h->go_tile_count[(size_t)i * nch];
+        const i32 *cnt = &h->run.go_tile_count[(size_t)i * nch];
         while (c < nch - 1 && local >= cnt[c]) { local -= cnt[c]; c++; }
         treq.push_back(TileTimeReq{(i32)i, (i32)c, (i32)local, 0}); tile_pos.push_back(k);
     }
@@ -2604,8 +2605,8 @@ try {
 
 int wfs_copy_truth(wfs_handle *h, double *acc12, double *tstat5, int64_t cap)
 try {
-    if (!h || !h->ran) return WFS_E_STATE;
-    const i64 S = h->n_sets;
+    if (!h || !run_finished(h)) return WFS_E_STATE;
+    const i64 S = h->batch.n_sets;
     if (cap < S) return h->fail(WFS_E_CAPACITY, "truth buffer too small");
     std::vector<double> tr((size_t)S * 16); std::vector<i64> mm((size_t)S * 2), t0((size_t)S);
     HIPCHK(hipMemcpy(tr.data(), h->truth.p, tr.size() * 8, hipMemcpyDeviceToHost));
@@ -2624,8 +2625,8 @@ try {
 
 int wfs_copy_truth_per_pmt(wfs_handle *h, double *acc6, int64_t cap)
 try {
-    if (!h || !h->ran) return WFS_E_STATE;
-    const i64 S = h->n_sets, nch = h->cfg.n_tpc, T = S * nch;
+    if (!h || !run_finished(h)) return WFS_E_STATE;
+    const i64 S = h->batch.n_sets, nch = h->cfg.n_tpc, T = S * nch;
     if (cap < S) return h->fail(WFS_E_CAPACITY, "per-PMT truth buffer too small");
     std::vector<double> tt((size_t)T * 8); std::vector<i32> cnt((size_t)T); std::vector<double> gains((size_t)nch);
     HIPCHK(hipMemcpy(tt.data(), h->tile_truth.p, tt.size() * 8, hipMemcpyDeviceToHost));
@@ -2642,10 +2643,10 @@ try {
 
 int wfs_copy_electron_stats(wfs_handle *h, double *estat5, int64_t cap)
 try {
-    if (!h || !h->ran) return WFS_E_STATE;
-    const i64 N = h->n_ins;
-    if (h->optical) { for (i64 i = 0; i < N && i < cap; i++) { estat5[i * 5] = 0; for (int q = 1; q < 5; q++) estat5[i * 5 + q] = NAN; } return WFS_OK; }
-    const i64 PS = h->n_psets;
+    if (!h || !run_finished(h)) return WFS_E_STATE;
+    const i64 N = h->batch.n_ins;
+    if (h->batch.kind == BatchKind::Optical) { for (i64 i = 0; i < N && i < cap; i++) { estat5[i * 5] = 0; for (int q = 1; q < 5; q++) estat5[i * 5 + q] = NAN; } return WFS_OK; }
+    const i64 PS = h->batch.n_psets;
     if (cap < PS) return h->fail(WFS_E_CAPACITY, "electron stats buffer too small");
     if (N == 0) return WFS_OK;
     std::vector<double> st((size_t)N * 4); std::vector<i64> mm((size_t)N * 2), t0((size_t)N);
@@ -2654,10 +2655,10 @@ try {
     HIPCHK(hipMemcpy(t0.data(), h->ins_time.p, t0.size() * 8, hipMemcpyDeviceToHost));
     for (i64 q = 0; q < PS; q++) {
         // moments of the electrons of all instructions of the run set (rawdata.py:334-341), about the first instruction's time
-        const i64 ref = h->h_rs_off[q + 1] > h->h_rs_off[q] ? t0[h->h_rs_list[h->h_rs_off[q]]] : 0;      // (an unused set number: no instructions, zero electrons)
+        const i64 ref = h->batch.h_rs_off[q + 1] > h->batch.h_rs_off[q] ? t0[h->batch.h_rs_list[h->batch.h_rs_off[q]]] : 0;      // (an unused set number: no instructions, zero electrons)
         double n = 0, s1 = 0, s2 = 0; i64 lo = I64_MAX, hi = I64_MIN;
-        for (i64 k = h->h_rs_off[q]; k < h->h_rs_off[q + 1]; k++) {
-            const i64 i = h->h_rs_list[k];
+        for (i64 k = h->batch.h_rs_off[q]; k < h->batch.h_rs_off[q + 1]; k++) {
+            const i64 i = h->batch.h_rs_list[k];
             const double ni = st[i * 4], a1 = st[i * 4 + 1], a2 = st[i * 4 + 2], dlt = (double)(t0[i] - ref);
             if (!(ni > 0)) continue;
             n += ni; s1 += a1 + ni * dlt; s2 += a2 + 2 * dlt * a1 + ni * dlt * dlt;
@@ -2690,22 +2691,21 @@ try {
         if (c.n_top < 0 || c.last_bottom >= c.n_tpc) return h->fail(WFS_E_INVALID, "wfs_set_sum_signal: bottom array outside the TPC channels");
     }
     h->sum_on = on != 0;
-    h->ran = false;             // (the row slots of the last wfs_run no longer match: run again before copying)
-    refresh_dev(h);
+    refresh_dev(h);             // (a switch that changes the row slots: run again before copying rows)
     return WFS_OK;
 } WFS_CATCH(h)
 
 // Parity entry: the sum rows before they are finished, S[t] = int(he_factor) * sum of the bottom rows (64 bits)
 int wfs_copy_sum_signal(wfs_handle *h, int32_t *group, int64_t *left, int64_t *right, int64_t *data_off, int64_t *data, int64_t cap_rows, int64_t cap_samples)
 try {
-    if (!h || !h->ran) return WFS_E_STATE;
+    if (!h || !run_complete(h)) return WFS_E_STATE;
     const WfsDev &d = h->dev;
-    if (d.sum_channel < 0 || h->n_groups == 0) { if (cap_rows > 0 && data_off) data_off[0] = 0; return WFS_OK; }
-    const i64 G = h->n_groups;
-    std::vector<i64> lo((size_t)G), hi((size_t)G), off((size_t)G + 1); std::vector<i32> acc((size_t)h->s_sum);
+    if (d.sum_channel < 0 || h->run.n_groups == 0) { if (cap_rows > 0 && data_off) data_off[0] = 0; return WFS_OK; }
+    const i64 G = h->run.n_groups;
+    std::vector<i64> lo((size_t)G), hi((size_t)G), off((size_t)G + 1); std::vector<i32> acc((size_t)h->run.s_sum);
     HIPCHK(hipMemcpy(lo.data(), h->sum_lo.p, lo.size() * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(hi.data(), h->sum_hi.p, hi.size() * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(off.data(), h->sum_off.p, off.size() * 8, hipMemcpyDeviceToHost));
-    if (h->s_sum) HIPCHK(hipMemcpy(acc.data(), h->raw.as<i32>() + h->sum_base, acc.size() * 4, hipMemcpyDeviceToHost));
+    if (h->run.s_sum) HIPCHK(hipMemcpy(acc.data(), h->raw.as<i32>() + h->run.sum_base, acc.size() * 4, hipMemcpyDeviceToHost));
     i64 k = 0, doff = 0;
     for (i64 g = 0; g < G; g++) {
         if (lo[g] == I64_MAX) continue;
@@ -2729,7 +2729,6 @@ try {
         HIPCHK(hipStreamSynchronize(h->stream));
         h->nm_channels = 0; h->h_nm_cells.clear(); h->nm_cells.reset();
         h->nc_n_taps = 0; h->nc_groups = 0; h->nc_buf.reset();
-        h->ran = false;
         refresh_dev(h);
         return WFS_OK;
     }
@@ -2754,8 +2753,7 @@ try {
     HIPCHK(hipStreamSynchronize(h->stream));
     h->h_nm_cells.swap(cells); h->nm_channels = n_channels; h->nm_k = K; h->nm_shift = shift; h->nm_vmin = vmin; h->nm_values = n_values;
     h->nc_n_taps = 0; h->nc_groups = 0; h->nc_buf.reset();          // a colour belongs to the shapes of the model it was set on
-    h->ran = false;             // (HE rows may appear or go with the model's channel count: run again before copying)
-    refresh_dev(h);
+    refresh_dev(h);             // (HE rows may appear or go with the model's channel count: run again before copying rows)
     return WFS_OK;
 } WFS_CATCH(h)
 
@@ -2869,11 +2867,11 @@ try {
 
 int wfs_copy_tile_kernels(wfs_handle *h, int8_t *kind, int64_t capacity)
 try {
-    if (!h || !h->ran) return WFS_E_STATE;
+    if (!h || !run_finished(h)) return WFS_E_STATE;
     if (!kind) return h->fail(WFS_E_INVALID, "wfs_copy_tile_kernels: null argument");
-    const i64 TP = (from_generator(h) ? h->n_psets : h->n_sets) * h->cfg.n_tpc;      // (a batch of loaded photons has primary sets only)
+    const i64 TP = (from_generator(h) ? h->batch.n_psets : h->batch.n_sets) * h->cfg.n_tpc;      // (a batch of loaded photons has primary sets only)
     if (capacity < TP) return h->fail(WFS_E_CAPACITY, "tile kernel buffer too small");
-    if (!from_generator(h) || !h->fuse_on || TP == 0) { memset(kind, 0, (size_t)TP); return WFS_OK; }
+    if (!from_generator(h) || !h->run.fuse_on || TP == 0) { memset(kind, 0, (size_t)TP); return WFS_OK; }
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(kind, h->tile_kind.p, (size_t)TP, hipMemcpyDeviceToHost));
