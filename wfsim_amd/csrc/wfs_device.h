@@ -118,17 +118,21 @@ __device__ __forceinline__ u32 alias_cell(const AliasTab &t, u32 w) { return w >
 __device__ __forceinline__ i32 alias_pick(const AliasTab &t, u32 w, u32 c, uint2 e) { return t.vmin + (i32)(((w << (32 - t.shift)) < e.x) ? c : e.y); }
 __device__ __forceinline__ i32 alias_sample(const AliasTab &t, u32 w) { const u32 c = alias_cell(t, w); return alias_pick(t, w, c, t.cell[c]); }
 
-// SPE indices and double-PE flag of a photon from ONE word (pulse.py:76-79, 97-103, 226): w * 2000 = g * 2^32 + frac;
-// g + 1 = int(u * 2000) + 1 is the first index; frac (the 32 low bits, equidistributed for every g) < thr is the double-PE
-// Bernoulli trial, and given frac < thr it is uniform on [0, thr): int(frac * 2000 / thr) + 1 is the second index.
+// A channel's SPE row (pulse.py:97: a photon's gain is entry int(u * SPE_BINS) + 1 of it): SPE_BINS quantiles behind an entry 0 that no
+// photon indexes.
+constexpr int SPE_BINS = 2000, SPE_ROW_LEN = SPE_BINS + 1;
+
+// SPE indices and double-PE flag of a photon from ONE word (pulse.py:76-79, 97-103, 226): w * SPE_BINS = g * 2^32 + frac;
+// g + 1 = int(u * SPE_BINS) + 1 is the first index; frac (the 32 low bits, equidistributed for every g) < thr is the double-PE
+// Bernoulli trial, and given frac < thr it is uniform on [0, thr): int(frac * SPE_BINS / thr) + 1 is the second index.
 // Returns g1 | g2 << 16 with g2 = 0 when the photon makes a single PE.
 __device__ __forceinline__ u32 gain_code(u32 w, u64 thr_dpe, double dpe_inv)
 {
-    const u64 prod = (u64)w * 2000u;
+    const u64 prod = (u64)w * (u32)SPE_BINS;
     const u32 g1 = (u32)(prod >> 32) + 1u, frac = (u32)prod;
     if (!((u64)frac < thr_dpe)) return g1;
     u32 g2 = (u32)((double)frac * dpe_inv) + 1u;
-    g2 = g2 > 2000u ? 2000u : g2;
+    g2 = g2 > (u32)SPE_BINS ? (u32)SPE_BINS : g2;
     return g1 | (g2 << 16);
 }
 
@@ -321,7 +325,7 @@ struct WfsDev {
     u32 k0, k1;
     unsigned long long *stamps;                // -DWFS_STAMPS builds only: per-phase cycle sums of the instrumented kernels (nullptr otherwise)
     u64 thr_dpe;                               // Bernoulli threshold on a 32-bit word: floor(p * 2^32)
-    double dpe_inv;                            // 2000 / thr_dpe
+    double dpe_inv;                            // SPE_BINS / thr_dpe
     double current_max[16];                    // pulse.py:32, per ns remainder (sample_duration <= 16 ns)
     AliasTab tab_tts, tab_s1, tab_s2;          // alias tables of integer delays: transit time alone, all terms of an S1 / S2 photon
     // tables

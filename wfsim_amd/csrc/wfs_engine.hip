@@ -501,7 +501,7 @@ void refresh_dev(wfs_handle *h)
     d.pmt_ap_modifier = c.pmt_ap_modifier; d.pmt_ap_t_modifier = c.pmt_ap_t_modifier; d.rext = c.rext;
     d.k0 = (u32)c.seed; d.k1 = (u32)(c.seed >> 32);
     auto thr = [](double p) -> u64 { if (!(p > 0)) return 0; if (p >= 1) return 4294967296ull; return (u64)(p * 4294967296.0); };
-    d.thr_dpe = thr(c.p_dpe); d.dpe_inv = d.thr_dpe ? 2000.0 / (double)d.thr_dpe : 0.0;
+    d.thr_dpe = thr(c.p_dpe); d.dpe_inv = d.thr_dpe ? (double)SPE_BINS / (double)d.thr_dpe : 0.0;
     // HE rows are only materialised when they can differ from a flat baseline: a non-zero int(factor)
     // (rawdata.py:242) or noise columns for the HE channels
     // a noise model takes precedence over the table, which stays where it is for wfs_set_noise_model(h, 0, ...)
@@ -721,7 +721,7 @@ try {
     HIPCHK(hipSetDevice(h->device));
     const wfs_config &c = h->cfg;
     TRY(upload(h, h->t_templates, templates, sizeof(double) * c.dt * c.tlen));
-    TRY(upload(h, h->t_spe, spe, sizeof(double) * 2001 * (size_t)n_spe));
+    TRY(upload(h, h->t_spe, spe, sizeof(double) * SPE_ROW_LEN * (size_t)n_spe));
     TRY(upload(h, h->t_gains, gains, sizeof(double) * c.n_tpc));
     TRY(upload(h, h->t_thr_truth, thr_truth, sizeof(double) * c.n_rows));
     TRY(upload(h, h->t_thr_zle, thr_zle, sizeof(int64_t) * c.n_rows));
@@ -1990,12 +1990,9 @@ static int run_pulses(wfs_handle *h, RunState &r)
         TRY(fg.flush());
     }
     TRY(ensure(h, h->tminmax, (size_t)S * 16)); TRY(ensure(h, h->tile_truth, (size_t)T * 8 * 8));
-    pa.active_tiles = h->active_tiles.as<i32>(); pa.n_active = h->run.n_active_tiles;
-    pa.tile_count = h->tile_count.as<i32>(); pa.tile_tmin = h->tile_tmin.as<i32>(); pa.tile_tmax = h->tile_tmax.as<i32>(); pa.tile_off = h->tile_off.as<i64>();
-    pa.set_cluster = h->set_cluster.as<i32>(); pa.set_t0 = h->set_t0.as<i64>(); pa.set_mode = h->set_mode.as<i32>();
     pa.ph = h->ph.as<PhotonRec>();
     pa.ph_gain = ph_gain_base(h);
-    pa.cl_group = h->cl_group.as<i32>(); pa.row_lo = h->row_lo.as<i64>(); pa.acc_off = h->acc_off.as<i64>(); pa.raw = h->raw.as<i32>();
+    pa.raw = h->raw.as<i32>();
     pa.tile_truth = h->tile_truth.as<double>();
     if ((h->debug_bits & DBG_CURRENTS) && h->run.n_active_tiles > 0) {
         // debug: tile lengths in work-list order -> offsets
@@ -2010,7 +2007,7 @@ static int run_pulses(wfs_handle *h, RunState &r)
         for (size_t k = 0; k < at.size(); k++) {
             i64 set = at[k] / d.n_tpc;
             i64 b0 = floordiv(t0[set] + tmn[at[k]], (i64)d.dt), b1 = floordiv(t0[set] + tmx[at[k]], (i64)d.dt);
-            off[k + 1] = off[k] + (b1 - b0 + 1) + d.store_before + d.samples_before + d.store_after + d.samples_after;
+            off[k + 1] = off[k] + (b1 - b0 + 1) + tile_lead(d) + d.store_after + d.samples_after;
         }
         h->run.cur_total = off.back();
         TRY(upload(h, h->cur_off, off.data(), off.size() * 8));
@@ -2018,10 +2015,11 @@ static int run_pulses(wfs_handle *h, RunState &r)
         HIPCHK(hipStreamSynchronize(h->stream));
         pa.currents = h->currents.as<double>(); pa.cur_off = h->cur_off.as<i64>();
     }
-    if (h->run.n_active_tiles > 0) {        // tile descriptors of the whole work list (used by the tiny and the dense kernel)
+    if (h->run.n_active_tiles > 0) {        // tile descriptors of the whole work list (read by every pulse kernel)
         TRY(ensure(h, h->tile_desc, (size_t)h->run.n_active_tiles * sizeof(TileDesc)));
-        DescArgs da{pa.active_tiles, h->run.n_active_tiles, pa.tile_count, pa.tile_tmin, pa.tile_tmax, pa.tile_off, pa.set_cluster, pa.set_t0, pa.set_mode,
-                    pa.cl_group, pa.row_lo, pa.acc_off, h->tile_desc.as<TileDesc>()};
+        DescArgs da{h->active_tiles.as<i32>(), h->run.n_active_tiles, h->tile_count.as<i32>(), h->tile_tmin.as<i32>(), h->tile_tmax.as<i32>(), h->tile_off.as<i64>(),
+                    h->set_cluster.as<i32>(), h->set_t0.as<i64>(), h->set_mode.as<i32>(), h->cl_group.as<i32>(), h->row_lo.as<i64>(), h->acc_off.as<i64>(),
+                    h->tile_desc.as<TileDesc>()};
         Timer t(h, "k_tile_desc");
         hipLaunchKernelGGL(k_tile_desc, dim3(nblocks(h->run.n_active_tiles, 256)), dim3(256), 0, h->stream, d, da);
     }
@@ -2040,7 +2038,7 @@ static int run_pulses(wfs_handle *h, RunState &r)
     }
     if (h->run.n_sparse_tiles > 0) {
         PulseArgs ps = pa;
-        ps.active_tiles = h->active_tiles.as<i32>() + r.first_sparse;
+        ps.desc = h->tile_desc.as<TileDesc>() + r.first_sparse;
         if (ps.cur_off) ps.cur_off += r.first_sparse;
         ps.W = (int)((h->run.max_nb + 7) / 8 * 8); ps.NP = (int)((h->run.max_tile + 7) / 8 * 8);
         const bool small = h->run.max_tile <= 256 && h->run.max_nb <= 256;
@@ -2065,7 +2063,6 @@ static int run_pulses(wfs_handle *h, RunState &r)
         WFS_LAUNCH_F(h, K_PULSE_GENERIC, dim3((unsigned)h->run.n_dense_tiles), dim3(256), lds, d, pd);
     } else if (h->run.n_dense_tiles > 0) {
         PulseArgs pd = pa;
-        pd.active_tiles = h->active_tiles.as<i32>() + r.first_dense;
         pd.desc = h->tile_desc.as<TileDesc>() + r.first_dense;
         if (pd.cur_off) pd.cur_off += r.first_dense;
         // chunks of TPB live samples per pass (TPB + 21 start-bin rows of 80 bytes in LDS: 22 KB for 256 -> 7 workgroups per CU)
@@ -2084,7 +2081,7 @@ static int run_pulses(wfs_handle *h, RunState &r)
         size_t lds = (size_t)(tpb + d.tlen - 1) * d.dt * 8 + (size_t)8 * (tpb / 64) * 8 + 64 + TAP_LDS_BYTES(256) + 16;
         lds = (lds + 15) / 16 * 16;
         pd.sparse_max = (h->debug_bits & DBG_FORCE_DENSE) ? -1 : h->tap_sparse_max;      // (force_dense: every wave takes the dense gather)
-        pd.spe_lds = ((size_t)(tpb + d.tlen - 1) * d.dt >= 2001) ? 1 : 0;
+        pd.spe_lds = ((size_t)(tpb + d.tlen - 1) * d.dt >= SPE_ROW_LEN) ? 1 : 0;
         const unsigned grid = (unsigned)(h->run.n_dense_tiles * pd.n_win);
         Timer t(h, "k_pulse_dense");
         if (resident) {
@@ -2502,7 +2499,7 @@ try {
     HIPCHK(hipMemcpy(off.data(), h->tile_off.p, off.size() * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(t0.data(), h->set_t0.p, t0.size() * 8, hipMemcpyDeviceToHost));
     if (P) HIPCHK(hipMemcpy(recs.data(), h->ph.p, recs.size() * 8, hipMemcpyDeviceToHost));
-    std::vector<double> gains((size_t)d.n_tpc), spe((size_t)2001 * d.n_spe), pg;
+    std::vector<double> gains((size_t)d.n_tpc), spe((size_t)SPE_ROW_LEN * d.n_spe), pg;
     HIPCHK(hipMemcpy(gains.data(), h->t_gains.p, gains.size() * 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(spe.data(), h->t_spe.p, spe.size() * 8, hipMemcpyDeviceToHost));
     const i64 gain_first = h->batch.kind == BatchKind::Photons ? 0 : n_prim;        // ph_gain covers the explicit-gain photons only
@@ -2511,12 +2508,12 @@ try {
     for (i64 s = 0; s <= h->batch.n_sets; s++) set_off[s] = off[(size_t)s * d.n_tpc];
     for (i64 tile = 0; tile < T; tile++) {
         i64 s = tile / d.n_tpc; int c = (int)(tile - s * d.n_tpc);
-        const double *row = &spe[(size_t)(d.n_spe > 1 ? c : 0) * 2001];
+        const double *row = &spe[(size_t)(d.n_spe > 1 ? c : 0) * SPE_ROW_LEN];
         for (i64 p = off[tile]; p < off[tile + 1]; p++) {
             t[p] = t0[s] + recs[p].t; ch[p] = (int16_t)c;
             u32 g1 = recs[p].code & 0xffffu, g2 = recs[p].code >> 16;
             if (p >= gain_first) { gain[p] = pg[(size_t)(p - gain_first)]; dpe[p] = g2 != 0; }
-            else { double g = gains[c] * row[g1]; if (g2) g += gains[c] * row[g2]; gain[p] = g; dpe[p] = g2 != 0; }
+            else { gain[p] = spe_gain(gains[c], row[g1], row[g2], recs[p].code); dpe[p] = g2 != 0; }
         }
     }
     return WFS_OK;

@@ -482,25 +482,100 @@ struct TileDesc {
 };
 
 struct PulseArgs {
-    const i32 *active_tiles; i64 n_active;
-    const TileDesc *desc;   // per work-list entry (dense kernel)
-    const i32 *tile_count, *tile_tmin, *tile_tmax; const i64 *tile_off;
-    const i32 *set_cluster; const i64 *set_t0; const i32 *set_mode;       // mode 0: SPE codes, 1: explicit gains
-    const PhotonRec *ph; const double *ph_gain;
-    const i32 *cl_group; const i64 *row_lo; const i64 *acc_off;
+    const TileDesc *desc;   // per entry of the kernel's stretch of the work list (k_tile_desc)
+    const PhotonRec *ph; const double *ph_gain;       // ph_gain: the photons of the sets of mode 1 (TileDesc::mode; 0: SPE codes)
     i32 *raw;
     double *tile_truth;   // [n_tiles][8] per-tile partial sums: n, n_dpe, n_trig, n_trig_dpe, sum g, sum g trig, sum t, sum t^2 -> k_truth_reduce
     double *currents; const i64 *cur_off;     // debug: f64 tile currents
     i32 W;                // bins capacity of the sparse kernel's LDS tables
     i32 NP;               // photon capacity of the sparse kernel's LDS list
     i32 n_win;            // dense kernel: workgroups per tile (each takes every n_win-th chunk of TPB samples)
-    i32 spe_lds;          // dense resident kernel: the H table has room for the channel's SPE row (2001 doubles), staged there before the gains are looked up
+    i32 spe_lds;          // dense resident kernel: the H table has room for the channel's SPE row (SPE_ROW_LEN doubles), staged there before the gains are looked up
     i32 sparse_max;       // dense kernel: a wave whose samples see at most this many occupied cells walks them instead of gathering all 220 per sample (tap_block)
 };
 
 #define DENSE_PPT 8        // photons per thread per batch held in registers
 
 struct TemplateArg { double t[22 * WFS_DT]; };    // t[k * dt + r] = templates[r][k]; kernarg segment -> scalar loads, the taps live in SGPRs
+
+// ---- the reference's per-photon rules, one definition each: every pulse kernel below and the tile generator (wfs_tilegen.h) call these
+// The SPE row of a channel (pulse.py:97-103): one row per channel, or one row shared by all of them.
+__device__ __forceinline__ const double *spe_row_of(const WfsDev &d, i32 ch) { return d.spe + (size_t)(d.n_spe > 1 ? ch : 0) * SPE_ROW_LEN; }
+// The row (16 KB) into LDS past the registers (global_load_lds: 16 bytes per lane, a wave fills 1 KB of LDS per instruction).  The
+// caller waits (vmcnt) and synchronises before it reads H.
+template <int TPB>
+__device__ __forceinline__ void spe_row_to_lds(const double *row, double *H, int tid)
+{
+    constexpr int NIT = (SPE_ROW_LEN * 8 + TPB * 16 - 1) / (TPB * 16);
+#pragma unroll
+    for (int it = 0; it < NIT; it++) {
+        // first double of this lane's 16 bytes; the lanes behind the row re-read its last entry (index SPE_BINS: its second
+        // half is the first entry of the next row or, behind the last row, the slack every device buffer has)
+        const int i = (it * TPB + tid) * 2;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(row + (i < SPE_ROW_LEN ? i : SPE_BINS)),
+                                         (__attribute__((address_space(3))) void *)(H + (it * TPB + (tid & ~63)) * 2), 16, 0, 0);
+    }
+}
+// Gain of a photon from the row's entries s1 = spe[code & 0xffff], s2 = spe[code >> 16] (pulse.py:97-98; the second photoelectron of a
+// double-PE photon, code >> 16 != 0: pulse.py:101-103).  Two products, each rounded, and a conditional add.  s2() is asked for a
+// double PE only: spe_gain has the entry at hand (batched loads), photon_gain loads both at the point of use.
+template <class Second>
+__host__ __device__ __forceinline__ double spe_gain_of(double G, double s1, u32 code, Second s2)
+{
+    double g = G * s1;
+    if (code >> 16) g += G * s2();
+    return g;
+}
+__host__ __device__ __forceinline__ double spe_gain(double G, double s1, double s2, u32 code) { return spe_gain_of(G, s1, code, [=] { return s2; }); }
+__device__ __forceinline__ double photon_gain(const double *row, double G, u32 code) { return spe_gain_of(G, row[code & 0xffffu], code, [=] { return row[code >> 16]; }); }
+// Truth sums of a tile (pulse.py:229-271): acc = n, n_dpe, n_trig, n_trig_dpe, sum g, sum g trig, sum t, sum t^2 -> k_truth_reduce.
+// A photon triggers when its pulse height exceeds the channel's threshold; cmax_r = current_max[ns % dt] (pulse.py:32).
+__device__ __forceinline__ bool truth_above(const WfsDev &d, double gain, double cmax_r, double thr) { return gain * cmax_r * d.c2a > thr; }
+// One photon.  rank_below_ndpe: its index in the channel slice is below the tile's DPE count -- the reference marks the FIRST n_dpe
+// photons of the slice as the double-PE ones, whichever they are (pulse.py:255).  tr: its time relative to the set origin.
+__device__ __forceinline__ void truth_add(double (&acc)[8], double gain, bool above, bool is_dpe, bool rank_below_ndpe, double tr)
+{
+    acc[0] += 1; acc[1] += is_dpe; acc[4] += gain;
+    if (above) { acc[2] += 1; acc[5] += gain; if (rank_below_ndpe) acc[3] += 1; }
+    acc[6] += tr; acc[7] += tr * tr;
+}
+// Sum of a per-thread count over the workgroup (the tile's DPE photons); wsum: [TPB / 64].  Holds a barrier.
+template <int TPB>
+__device__ __forceinline__ i32 block_sum_u32(i32 c, u32 *wsum)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+    if (lane == 0) wsum[wid] = (u32)c;
+    __syncthreads();
+    i32 sum = 0;
+    for (int w = 0; w < TPB / 64; w++) sum += (i32)wsum[w];
+    return sum;
+}
+// The eight sums over a wave, then over the waves in a fixed order (red: [TPB / 64][8]) -> out[8].  The order of a floating-point sum is
+// behaviour: each kernel keeps its wave reduction, the shuffle tree or the DPP tree of wave_sum.
+__device__ __forceinline__ void truth_wave_shfl(double (&acc)[8])
+{
+#pragma unroll
+    for (int q = 0; q < 8; q++) for (int o = 32; o > 0; o >>= 1) acc[q] += __shfl_down(acc[q], o, 64);
+}
+__device__ __forceinline__ void truth_wave_dpp(double (&acc)[8])
+{
+#pragma unroll
+    for (int q = 0; q < 8; q++) acc[q] = wave_sum(acc[q]);
+}
+template <int TPB>
+__device__ __forceinline__ void truth_store_block(const double (&acc)[8], double *red, double *out)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    if (lane == 0) for (int q = 0; q < 8; q++) red[wid * 8 + q] = acc[q];
+    __syncthreads();
+    if (tid < 8) { double sum = 0; for (int w = 0; w < TPB / 64; w++) sum += red[w * 8 + tid]; out[tid] = sum; }
+}
+// ADC count of a current (rawdata.py:236; np.around = round half to even)
+__device__ __forceinline__ double adc_round(const WfsDev &d, double c) { return rint(c * d.c2a); }
+__device__ __forceinline__ i64 adc_of(const WfsDev &d, double c) { return -(i64)adc_round(d, c); }
+// Samples of a tile in front of its first start bin (pulse.py:118-127)
+__host__ __device__ __forceinline__ int tile_lead(const WfsDev &d) { return d.store_before + d.samples_before; }
 
 struct DescArgs { const i32 *list; i64 n; const i32 *tile_count, *tile_tmin, *tile_tmax; const i64 *tile_off; const i32 *set_cluster; const i64 *set_t0;
                   const i32 *set_mode; const i32 *cl_group; const i64 *row_lo; const i64 *acc_off; TileDesc *desc; };
@@ -645,11 +720,11 @@ __global__ __launch_bounds__(TPB) void k_pulse(WfsDev d, PulseArgs a, TemplateAr
     const TileDesc td = a.desc[tidx];                     // block-uniform: scalar loads
     const i64 tile = td.tile; const i32 n = td.n; const i64 off = td.off; const i32 ch = td.ch;
     const i64 nb = td.nb, L = td.L;
-    const int lead = d.store_before + d.samples_before;
+    const int lead = tile_lead(d);
     i32 *dst = a.raw + td.dst;
     const int mode = td.mode;
     const double G = td.G;
-    const double *spe_row = d.spe + (size_t)(d.n_spe > 1 ? ch : 0) * 2001;
+    const double *spe_row = spe_row_of(d, ch);
     const double thr = td.thr;
     const i64 rel0 = td.rel0;                             // ns of the tile's first start bin relative to t0
 
@@ -662,10 +737,7 @@ __global__ __launch_bounds__(TPB) void k_pulse(WfsDev d, PulseArgs a, TemplateAr
     if (!RESIDENT && win == 0 && !one_batch) {
         i32 c = 0;
         for (i32 p = tid; p < n; p += TPB) c += (a.ph[off + p].code >> 16) != 0;
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-        if (lane == 0) wsum[wid] = (u32)c;
-        __syncthreads();
-        for (int w = 0; w < TPB / 64; w++) n_dpe_tile += (i32)wsum[w];
+        n_dpe_tile = block_sum_u32<TPB>(c, wsum);
     }
     double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // n, n_dpe, n_trig, n_trig_dpe, sum g, sum g trig, sum t, sum t^2
     STAMP_INIT;
@@ -678,19 +750,8 @@ __global__ __launch_bounds__(TPB) void k_pulse(WfsDev d, PulseArgs a, TemplateAr
         // The channel's SPE row (16 KB) goes through LDS (H is still free): two data-dependent 8-byte gathers per photon from
         // global memory cost the texture addresser ~64 cycles per wave instruction, from LDS a few.  Its loads are issued
         // together with the photon loads: one global round trip for both.
-        // They bypass the registers (global_load_lds: 16 bytes per lane, a wave fills 1 KB of LDS per instruction).
         const bool spe_lds = mode == 0 && a.spe_lds;         // block-uniform
-        if (spe_lds) {
-            constexpr int NIT = (2001 * 8 + TPB * 16 - 1) / (TPB * 16);
-#pragma unroll
-            for (int it = 0; it < NIT; it++) {
-                // first double of this lane's 16 bytes; the lanes behind the row re-read its last entry (index 2000: its second
-                // half is the first entry of the next row or, behind the last row, the slack every device buffer has)
-                const int i = (it * TPB + tid) * 2;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(spe_row + (i < 2001 ? i : 2000)),
-                                                 (__attribute__((address_space(3))) void *)(H + (it * TPB + (tid & ~63)) * 2), 16, 0, 0);
-            }
-        }
+        if (spe_lds) spe_row_to_lds<TPB>(spe_row, H, tid);
 #pragma unroll
         for (int k = 0; k < DENSE_PPT; k++) {
             const i32 p = tid + k * TPB;
@@ -710,11 +771,9 @@ __global__ __launch_bounds__(TPB) void k_pulse(WfsDev d, PulseArgs a, TemplateAr
             i32 c = 0;
 #pragma unroll
             for (int k = 0; k < DENSE_PPT; k++) c += (code[k] >> 16) != 0;
-            for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-            if (lane == 0) wsum[wid] = (u32)c;
-            if (spe_lds) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the SPE row has landed in LDS
-            __syncthreads();
-            for (int w = 0; w < TPB / 64; w++) n_dpe_tile += (i32)wsum[w];
+            // the SPE row has landed in LDS (issued ahead of the photon loads the count depends on: the wait costs nothing here)
+            if (spe_lds) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            n_dpe_tile = block_sum_u32<TPB>(c, wsum);
         }
         if (mode == 0) {
             if (spe_lds) {
@@ -725,11 +784,7 @@ __global__ __launch_bounds__(TPB) void k_pulse(WfsDev d, PulseArgs a, TemplateAr
 #pragma unroll
                     for (int k = 0; k < DENSE_PPT / 2; k++) { s1[k] = H[code[h0 + k] & 0xffffu]; s2[k] = H[code[h0 + k] >> 16]; }     // H[0] for "no second PE": unused
 #pragma unroll
-                    for (int k = 0; k < DENSE_PPT / 2; k++) {
-                        double gk = G * s1[k];                          // pulse.py:97-98
-                        if (code[h0 + k] >> 16) gk += G * s2[k];        // pulse.py:101-103
-                        r_gain[h0 + k] = gk;
-                    }
+                    for (int k = 0; k < DENSE_PPT / 2; k++) r_gain[h0 + k] = spe_gain(G, s1[k], s2[k], code[h0 + k]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 __syncthreads();                             // H is reused below
@@ -742,11 +797,7 @@ __global__ __launch_bounds__(TPB) void k_pulse(WfsDev d, PulseArgs a, TemplateAr
                     if (code[k] >> 16) s2[k] = spe_row[code[k] >> 16];
                 }
 #pragma unroll
-                for (int k = 0; k < DENSE_PPT; k++) {
-                    double gk = G * s1[k];                              // pulse.py:97-98
-                    if (code[k] >> 16) gk += G * s2[k];                 // pulse.py:101-103
-                    r_gain[k] = gk;
-                }
+                for (int k = 0; k < DENSE_PPT; k++) r_gain[k] = spe_gain(G, s1[k], s2[k], code[k]);
             }
         }
         STAMP(d, 8);
@@ -758,7 +809,7 @@ __global__ __launch_bounds__(TPB) void k_pulse(WfsDev d, PulseArgs a, TemplateAr
         for (int k = 0; k < DENSE_PPT; k++) {
             const bool v = r_ns[k] >= 0;
             const int r = v ? r_ns[k] % dt : 0;
-            const bool above = v && (r_gain[k] * s_cmax[r] * d.c2a > thr);
+            const bool above = v && truth_above(d, r_gain[k], s_cmax[r], thr);
             c_trig += (u32)__popcll(ballot64(above));
             c_trig_dpe += (u32)__popcll(ballot64(above && tid + k * TPB < n_dpe_tile));
             if (v) {
@@ -831,10 +882,7 @@ __global__ __launch_bounds__(TPB) void k_pulse(WfsDev d, PulseArgs a, TemplateAr
                 i32 c = 0;
 #pragma unroll
                 for (int k = 0; k < DENSE_PPT; k++) c += (code[k] >> 16) != 0;
-                for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-                if (lane == 0) wsum[wid] = (u32)c;
-                __syncthreads();
-                for (int w = 0; w < TPB / 64; w++) n_dpe_tile += (i32)wsum[w];
+                n_dpe_tile = block_sum_u32<TPB>(c, wsum);
             }
             if (mode == 0) {
                 double s1[DENSE_PPT], s2[DENSE_PPT];
@@ -844,11 +892,7 @@ __global__ __launch_bounds__(TPB) void k_pulse(WfsDev d, PulseArgs a, TemplateAr
                     if (use[k]) { s1[k] = spe_row[code[k] & 0xffffu]; if (code[k] >> 16) s2[k] = spe_row[code[k] >> 16]; }
                 }
 #pragma unroll
-                for (int k = 0; k < DENSE_PPT; k++) {
-                    double gk = G * s1[k];                              // pulse.py:97-98
-                    if (code[k] >> 16) gk += G * s2[k];                 // pulse.py:101-103
-                    gain[k] = gk;
-                }
+                for (int k = 0; k < DENSE_PPT; k++) gain[k] = spe_gain(G, s1[k], s2[k], code[k]);
             }
 #pragma unroll
             for (int k = 0; k < DENSE_PPT; k++) {
@@ -857,7 +901,8 @@ __global__ __launch_bounds__(TPB) void k_pulse(WfsDev d, PulseArgs a, TemplateAr
                 const i64 jw = bin - b_lo;
                 if (jw >= 0 && jw < HROWS) atomicAdd(&H[(int)jw * dt + r], gain[k]);
                 if (first) {
-                    const bool above = gain[k] * s_cmax[r] * d.c2a > thr;
+                    const bool above = truth_above(d, gain[k], s_cmax[r], thr);
+                    // (truth_add, written out: through the helper this kernel, at the edge of its register budget, takes one VGPR more)
                     const bool is_dpe = (code[k] >> 16) != 0;
                     acc[0] += 1; acc[1] += is_dpe; acc[4] += gain[k];
                     if (above) { acc[2] += 1; acc[5] += gain[k]; if (base + tid + k * TPB < n_dpe_tile) acc[3] += 1; }
@@ -877,7 +922,7 @@ __global__ __launch_bounds__(TPB) void k_pulse(WfsDev d, PulseArgs a, TemplateAr
             if (act) {
                 const i64 sx = lead + c0 + tid;            // sample of the tile
                 if (a.currents) a.currents[a.cur_off[tidx] + sx] = c;
-                const i64 adc = -(i64)rint(c * d.c2a);     // rawdata.py:236, np.around = round half to even
+                const i64 adc = adc_of(d, c);
                 if (adc != 0) atomicAdd(&dst[sx], (i32)adc);
             }
         }
@@ -885,12 +930,9 @@ __global__ __launch_bounds__(TPB) void k_pulse(WfsDev d, PulseArgs a, TemplateAr
     }
 
     if (!RESIDENT && a.tile_truth && win == 0) {
-#pragma unroll
-        for (int q = 0; q < 8; q++) for (int o = 32; o > 0; o >>= 1) acc[q] += __shfl_down(acc[q], o, 64);
+        truth_wave_shfl(acc);
         __syncthreads();
-        if (lane == 0) for (int q = 0; q < 8; q++) red[wid * 8 + q] = acc[q];
-        __syncthreads();
-        if (tid < 8) { double sum = 0; for (int w = 0; w < TPB / 64; w++) sum += red[w * 8 + tid]; a.tile_truth[tile * 8 + tid] = sum; }
+        truth_store_block<TPB>(acc, red, a.tile_truth + tile * 8);
     }
 }
 
@@ -919,23 +961,21 @@ __global__ __launch_bounds__(TPB) void k_pulse_generic(WfsDev d, PulseArgs a)
     double *T = H + (size_t)HROWS * dt * (split ? 2 : 1); // [dt][tlen] templates
     double *red = T + (size_t)dt * tlen;                  // [TPB / 64][8]
     __shared__ double s_cmax[WFS_MAX_DT];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     for (int i = tid; i < dt * tlen; i += TPB) T[i] = d.templates[i];
     if (tid < dt) s_cmax[tid] = d.current_max[tid];
     const TileDesc td = a.desc[blockIdx.x];
     const i64 tile = td.tile; const i32 n = td.n; const i64 off = td.off;
     const i64 nb = td.nb;
-    const int lead = d.store_before + d.samples_before;
+    const int lead = tile_lead(d);
     i32 *dst = a.raw + td.dst;
     const double G = td.G, thr = td.thr;
-    const double *spe_row = d.spe + (size_t)(d.n_spe > 1 ? td.ch : 0) * 2001;
+    const double *spe_row = spe_row_of(d, td.ch);
     const i64 rel0 = td.rel0;
     const i64 n_live = nb + (tlen - 1);
     auto gain_of = [&](const PhotonRec &rec, i32 p) -> double {
         if (td.mode != 0) return a.ph_gain[off + p];
-        double g = G * spe_row[rec.code & 0xffffu];                 // pulse.py:97-98
-        if (rec.code >> 16) g += G * spe_row[rec.code >> 16];       // pulse.py:101-103
-        return g;
+        return photon_gain(spe_row, G, rec.code);
     };
     // number of DPE photons of the tile (truth quirk pulse.py:255) and the exponent field of its largest gain
     __shared__ i32 s_ndpe, s_emax;
@@ -978,11 +1018,8 @@ __global__ __launch_bounds__(TPB) void k_pulse_generic(WfsDev d, PulseArgs a)
                 atomicAdd(&Hlo[(int)jw * dt + r], gain - hi);
             } else if (mine) atomicAdd(&H[(int)jw * dt + r], gain);
             if (first) {
-                const bool above = gain * s_cmax[r] * d.c2a > thr;
-                acc[0] += 1; acc[1] += (rec.code >> 16) != 0; acc[4] += gain;
-                if (above) { acc[2] += 1; acc[5] += gain; if (p < n_dpe_tile) acc[3] += 1; }
-                const double tr = (double)(ns + rel0);
-                acc[6] += tr; acc[7] += tr * tr;
+                const bool above = truth_above(d, gain, s_cmax[r], thr);
+                truth_add(acc, gain, above, (rec.code >> 16) != 0, p < n_dpe_tile, (double)(ns + rel0));
             }
         }
         __syncthreads();
@@ -999,17 +1036,14 @@ __global__ __launch_bounds__(TPB) void k_pulse_generic(WfsDev d, PulseArgs a)
             }
             const i64 sx = lead + c0 + tid;
             if (a.currents) a.currents[a.cur_off[blockIdx.x] + sx] = c;
-            const i64 adc = -(i64)rint(c * d.c2a);         // rawdata.py:236
+            const i64 adc = adc_of(d, c);
             if (adc != 0) atomicAdd(&dst[sx], (i32)adc);
         }
     }
     if (a.tile_truth) {
-#pragma unroll
-        for (int q = 0; q < 8; q++) acc[q] = wave_sum(acc[q]);
+        truth_wave_dpp(acc);
         __syncthreads();
-        if (lane == 0) for (int q = 0; q < 8; q++) red[wid * 8 + q] = acc[q];
-        __syncthreads();
-        if (tid < 8) { double sum = 0; for (int w = 0; w < TPB / 64; w++) sum += red[w * 8 + tid]; a.tile_truth[tile * 8 + tid] = sum; }
+        truth_store_block<TPB>(acc, red, a.tile_truth + tile * 8);
     }
 }
 
@@ -1026,9 +1060,9 @@ __device__ __forceinline__ TinyPrep tiny_tile_prepare(const WfsDev &d, const Pul
 {
     constexpr int dt = WFS_DT, tlen = 22, NP = TINY_MAX_PHOTONS;
     const int n = td.n, L = td.L;
-    const int lead = d.store_before + d.samples_before;
+    const int lead = tile_lead(d);
     const double G = td.G;
-    const double *spe_row = d.spe + (size_t)(d.n_spe > 1 ? td.ch : 0) * 2001;
+    const double *spe_row = spe_row_of(d, td.ch);
     i32 ns[NP]; double g[NP]; u32 code[NP];
 #pragma unroll
     for (int k = 0; k < NP; k++) {
@@ -1039,7 +1073,7 @@ __device__ __forceinline__ TinyPrep tiny_tile_prepare(const WfsDev &d, const Pul
         g[k] = 0.0;
         if (v) {
             if (td.mode != 0) g[k] = a.ph_gain[td.off + k];
-            else { g[k] = G * spe_row[code[k] & 0xffffu]; if (code[k] >> 16) g[k] += G * spe_row[code[k] >> 16]; }      // pulse.py:97-103
+            else g[k] = photon_gain(spe_row, G, code[k]);
         }
     }
     if (a.tile_truth && sub == 0) {        // pulse.py:229-271, photons in their order in the channel slice
@@ -1050,11 +1084,8 @@ __device__ __forceinline__ TinyPrep tiny_tile_prepare(const WfsDev &d, const Pul
 #pragma unroll
         for (int k = 0; k < NP; k++) {
             if (k >= n) continue;
-            const bool above = g[k] * s_cmax[ns[k] % dt] * d.c2a > td.thr;
-            v[0] += 1; v[1] += (code[k] >> 16) != 0; v[4] += g[k];
-            if (above) { v[2] += 1; v[5] += g[k]; if (k < n_dpe) v[3] += 1; }
-            const double tr = (double)(ns[k] + td.rel0);
-            v[6] += tr; v[7] += tr * tr;
+            const bool above = truth_above(d, g[k], s_cmax[ns[k] % dt], td.thr);
+            truth_add(v, g[k], above, (code[k] >> 16) != 0, k < n_dpe, (double)(ns[k] + td.rel0));
         }
         for (int q = 0; q < 8; q++) a.tile_truth[(i64)td.tile * 8 + q] = v[q];
     }
@@ -1095,7 +1126,7 @@ template <bool FMA, int LANES, bool CUR, class Tap, class Sink>
 __device__ __forceinline__ void tiny_tile_samples(const WfsDev &d, const PulseArgs &a, const TinyPrep &q, i64 idx, int sub, Tap tap, Sink sink)
 {
     constexpr int tlen = 22, NP = TINY_MAX_PHOTONS;
-    const int lead = d.store_before + d.samples_before;
+    const int lead = tile_lead(d);
     for (int s = q.s_first + sub; s <= q.s_last; s += LANES) {
         double cur = 0.0;
 #pragma unroll
@@ -1104,7 +1135,7 @@ __device__ __forceinline__ void tiny_tile_samples(const WfsDev &d, const PulseAr
             if (k < q.n && kk >= 0 && kk < tlen) cur = mac<FMA>(tap(q.rr[k], kk), q.g[k], cur);
         }
         if (CUR && a.currents) a.currents[a.cur_off[idx] + s] = cur;
-        const i64 adc = -(i64)rint(cur * d.c2a);                 // rawdata.py:236
+        const i64 adc = adc_of(d, cur);
         if (adc != 0) sink(s, (i32)adc);
     }
 }
@@ -1208,7 +1239,7 @@ __device__ __forceinline__ void wave_tile_pulse(const WfsDev &d, const PulseArgs
 {
     constexpr int dt = WFS_DT, tlen = 22;
     const int n = td.n, L = td.L;
-    const int lead = d.store_before + d.samples_before;
+    const int lead = tile_lead(d);
     const bool v = lane < n;
     // ---- lane = photon
     const PhotonRec rec = a.ph[td.off + (v ? lane : 0)];
@@ -1217,16 +1248,16 @@ __device__ __forceinline__ void wave_tile_pulse(const WfsDev &d, const PulseArgs
     double g = 0.0;
     if (td.mode != 0) { if (v) g = a.ph_gain[td.off + lane]; }
     else {
-        const double *spe_row = d.spe + (size_t)(d.n_spe > 1 ? td.ch : 0) * 2001;
+        const double *spe_row = spe_row_of(d, td.ch);
         const double s1 = spe_row[code & 0xffffu], s2 = spe_row[code >> 16];
-        g = td.G * s1;                                                       // pulse.py:97-98
-        if (code >> 16) g += td.G * s2;                                      // pulse.py:101-103
+        g = td.G * s1;                                                       // (spe_gain, written out: td.G read at either use -- the
+        if (code >> 16) g += td.G * s2;                                      //  helper holds it in two more SGPRs of k_row_pulse)
         if (!v) g = 0.0;
     }
     if (a.tile_truth) {        // pulse.py:229-271, photons in their order in the channel slice (= lane order)
         const bool is_dpe = v && (code >> 16) != 0;
         const i32 n_dpe = __popcll(ballot64(is_dpe));
-        const bool above = v && (g * s_cmax[v ? ns0 % dt : 0] * d.c2a > td.thr);
+        const bool above = v && truth_above(d, g, s_cmax[v ? ns0 % dt : 0], td.thr);
         const i32 n_trig = __popcll(ballot64(above)), n_trig_dpe = __popcll(ballot64(above && lane < n_dpe));
         const double tr = v ? (double)(ns0 + td.rel0) : 0.0;
         // (DPP: no LDS crossbar trips; every photon above the threshold -- the usual tile -- : the triggered area IS the area, same bits)
@@ -1293,7 +1324,7 @@ __device__ __forceinline__ void wave_tile_pulse(const WfsDev &d, const PulseArgs
         }
         if (sp < n_live) {
             if (CUR && a.currents) a.currents[a.cur_off[idx] + lead + sp] = c;
-            const double x = rint(c * d.c2a);                  // rawdata.py:236
+            const double x = adc_round(d, c);
             // (|x| < 2^31 unless a current is absurd: the one-instruction conversion; the general one otherwise, same value)
             const i32 adc = fabs(x) < 2147483648.0 ? -(i32)x : (i32)(-(i64)x);
             if (adc != 0) sink(lead + sp, adc);
@@ -1346,21 +1377,16 @@ __global__ __launch_bounds__(TPB) void k_pulse_sparse(WfsDev d, PulseArgs a)
     __shared__ double s_cmax[WFS_DT];                    // pulse.py:32 current_max (see k_pulse)
     if (tid < WFS_DT) s_cmax[tid] = d.current_max[tid];
 
-    const i64 tile = a.active_tiles[blockIdx.x];
-    const i32 n = a.tile_count[tile];
-    const i64 off = a.tile_off[tile];
-    const i64 set = tile / d.n_tpc; const i32 ch = (i32)(tile - set * d.n_tpc);
-    const i64 t0 = a.set_t0[set];
-    i64 left, right, bin0, nb64;
-    tile_bounds(d, t0, a.tile_tmin[tile], a.tile_tmax[tile], left, right, bin0, nb64);
-    const int nb = (int)nb64, nns = nb * dt;
-    const int L = (int)(right - left + 1);
-    const int lead = d.store_before + d.samples_before;
-    const int mode = a.set_mode[set];
-    const double G = d.gains[ch];
-    const double *spe_row = d.spe + (size_t)(d.n_spe > 1 ? ch : 0) * 2001;
-    const double thr = d.thr_truth[ch];
-    const i32 rel0 = (i32)(bin0 * dt - t0);              // ns of the tile's first start bin relative to t0
+    const TileDesc td = a.desc[blockIdx.x];              // block-uniform: scalar loads
+    const i64 tile = td.tile; const i32 n = td.n; const i64 off = td.off;
+    const int nb = td.nb, nns = nb * dt;
+    const int L = td.L;
+    const int lead = tile_lead(d);
+    const int mode = td.mode;
+    const double G = td.G;
+    const double *spe_row = spe_row_of(d, td.ch);
+    const double thr = td.thr;
+    const i32 rel0 = (i32)td.rel0;                       // ns of the tile's first start bin relative to t0
 
     // ---- all photons of the tile into registers: independent loads, all in flight together
     i32 ns[SPARSE_PPT]; u32 code[SPARSE_PPT]; double gain[SPARSE_PPT];
@@ -1382,11 +1408,7 @@ __global__ __launch_bounds__(TPB) void k_pulse_sparse(WfsDev d, PulseArgs a)
             if (k < kmax) { s1[k] = spe_row[code[k] & 0xffffu]; if (any64((code[k] >> 16) != 0)) s2[k] = spe_row[code[k] >> 16]; }
         }
 #pragma unroll
-        for (int k = 0; k < SPARSE_PPT; k++) {
-            double gk = G * s1[k];                                  // pulse.py:97-98
-            if (code[k] >> 16) gk += G * s2[k];                     // pulse.py:101-103
-            gain[k] = gk;
-        }
+        for (int k = 0; k < SPARSE_PPT; k++) gain[k] = spe_gain(G, s1[k], s2[k], code[k]);
     }
     for (int i = tid; i < (nns + 1) / 2; i += TPB) cnt[i] = 0;
     i32 n_dpe_tile = 0;
@@ -1394,10 +1416,7 @@ __global__ __launch_bounds__(TPB) void k_pulse_sparse(WfsDev d, PulseArgs a)
         i32 c = 0;
 #pragma unroll
         for (int k = 0; k < SPARSE_PPT; k++) c += (code[k] >> 16) != 0;
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-        if (lane == 0) wsum[wid] = (u32)c;
-        __syncthreads();
-        for (int w = 0; w < TPB / 64; w++) n_dpe_tile += (i32)wsum[w];
+        n_dpe_tile = block_sum_u32<TPB>(c, wsum);
     }
     __syncthreads();
 
@@ -1408,12 +1427,8 @@ __global__ __launch_bounds__(TPB) void k_pulse_sparse(WfsDev d, PulseArgs a)
         if (ns[k] < 0) continue;
         atomicAdd(&cnt[ns[k] >> 1], 1u << ((ns[k] & 1) * 16));
         const int r = ns[k] % dt;
-        const bool above = gain[k] * s_cmax[r] * d.c2a > thr;
-        const bool is_dpe = (code[k] >> 16) != 0;
-        acc[0] += 1; acc[1] += is_dpe; acc[4] += gain[k];
-        if (above) { acc[2] += 1; acc[5] += gain[k]; if (tid + k * TPB < n_dpe_tile) acc[3] += 1; }
-        const double tr = (double)(ns[k] + rel0);
-        acc[6] += tr; acc[7] += tr * tr;
+        const bool above = truth_above(d, gain[k], s_cmax[r], thr);
+        truth_add(acc, gain[k], above, (code[k] >> 16) != 0, tid + k * TPB < n_dpe_tile, (double)(ns[k] + rel0));
     }
     __syncthreads();
 
@@ -1465,9 +1480,7 @@ __global__ __launch_bounds__(TPB) void k_pulse_sparse(WfsDev d, PulseArgs a)
     __syncthreads();
 
     // ---- gather: two samples per lane; sample s <- photons of start bins [s - lead - (tlen-1), s - lead], ascending time
-    const i64 g = a.cl_group[a.set_cluster[set]];
-    const i64 ridx = g * d.n_tpc + ch;
-    i32 *dst = a.raw + a.acc_off[ridx] + (left - (a.row_lo[ridx] - d.tw));
+    i32 *dst = a.raw + td.dst;
     for (int sa = 2 * tid; sa < L; sa += 2 * TPB) {
         int jlo = sa - lead - (tlen - 1), jhi = sa + 1 - lead;
         if (jlo < 0) jlo = 0;
@@ -1487,7 +1500,7 @@ __global__ __launch_bounds__(TPB) void k_pulse_sparse(WfsDev d, PulseArgs a)
             if (q < q1) { const i32 o0 = ctoff[q]; const double g0 = cg[q]; cur0 = mac<FMA>(Ts[o0], g0, cur0); cur1 = mac<FMA>(Ts[o0 + 1], g0, cur1); }
         }
         if (a.currents) { a.currents[a.cur_off[blockIdx.x] + sa] = cur0; if (sa + 1 < L) a.currents[a.cur_off[blockIdx.x] + sa + 1] = cur1; }
-        const i64 adc0 = -(i64)rint(cur0 * d.c2a), adc1 = -(i64)rint(cur1 * d.c2a);      // rawdata.py:236
+        const i64 adc0 = adc_of(d, cur0), adc1 = adc_of(d, cur1);
         if (adc0 != 0) atomicAdd(&dst[sa], (i32)adc0);
         if (adc1 != 0 && sa + 1 < L) atomicAdd(&dst[sa + 1], (i32)adc1);
     }
@@ -1495,11 +1508,8 @@ __global__ __launch_bounds__(TPB) void k_pulse_sparse(WfsDev d, PulseArgs a)
     if (a.tile_truth) {
         // (wave_sum: the order of wave_tile_pulse -- a tile of this class holds at most 32 photons, photon p in lane p of the first wave,
         // so its f64 truth sums are the same bits whether this kernel, k_pulse_wave or k_row_pulse made the tile)
-#pragma unroll
-        for (int q = 0; q < 8; q++) acc[q] = wave_sum(acc[q]);
-        if (lane == 0) for (int q = 0; q < 8; q++) red[wid * 8 + q] = acc[q];
-        __syncthreads();
-        if (tid < 8) { double sum = 0; for (int w = 0; w < TPB / 64; w++) sum += red[w * 8 + tid]; a.tile_truth[tile * 8 + tid] = sum; }
+        truth_wave_dpp(acc);
+        truth_store_block<TPB>(acc, red, a.tile_truth + tile * 8);
     }
 }
 
