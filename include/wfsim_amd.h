@@ -385,6 +385,21 @@ int wfs_set_noise_colour(wfs_handle *h, int32_t n_taps, const int32_t *taps_q, i
                          const double *common_pmf);
 /* The white sequence w(row, t0 .. t0 + n - 1) of a stream: row < n_channels a channel, n_channels + g common stream g. */
 int wfs_noise_white_samples(wfs_handle *h, int32_t row, int64_t t0, int64_t n, int16_t *out);
+/* Slow levels for the noise model, with or without a colour: baseline motion with memory far beyond the taps.  Level j of
+ * stream r (rows as for taps_q) is a sequence of knots 2^shifts[j] samples apart, joined by linear interpolation:
+ *   knot(r, j, m) = a draw from the stream's own cells with word m & 3 of the Philox call of (m >> 2, channel at site 80 + j | group at
+ *                   site 96 + j)
+ *   m = t >> shifts[j], f = t & (2^shifts[j] - 1), P0 = slow_q[r][j] knot(r, j, m), P1 = slow_q[r][j] knot(r, j, m + 1)
+ *   S(r, t) = sum_j P0 + (((int64) (P1 - P0) * f) >> shifts[j])                                  (Q16, arithmetic shifts)
+ * and F(r, t) + S(r, t) takes the place of F(r, t) above; without a colour F(r, t) = 65536 w(r, t) and there are no common streams.
+ * slow_q: [n_channels + n_groups][n_levels], Q16.  Needs a model (WFS_E_STATE without one); n_levels = 0 clears the levels, and so do
+ * wfs_set_noise_model and wfs_set_noise_colour (set the colour first).  WFS_E_INVALID, with the argument named: n_levels outside
+ * 0 .. 8; a shift outside 4 .. 30 or shifts not strictly ascending; a row with
+ * (sum |taps_q| + sum |slow_q|) * max(|vmin|, |vmin + n_values - 1|) >= 2^29 (sum |taps_q| = 65536 without a colour).  With all
+ * amplitudes zero the values are those of the model without the levels. */
+int wfs_set_noise_slow(wfs_handle *h, int32_t n_levels, const int32_t *shifts, const int32_t *slow_q);
+/* S(row, t0 .. t0 + n - 1) in Q16: row < n_channels a channel, n_channels + g common stream g.  WFS_E_STATE without slow levels. */
+int wfs_noise_slow_samples(wfs_handle *h, int32_t row, int64_t t0, int64_t n, int32_t *out);
 /* The alias cells of a channel as the device holds them: thr[n_cells], alias[n_cells] (n_cells = 2^k >= max(2, n_values), the same for
  * every channel), shift = 32 - k and vmin.  capacity_cells: entries the two buffers hold. */
 int wfs_copy_noise_model(wfs_handle *h, int32_t channel, uint32_t *thr, uint32_t *alias, int32_t capacity_cells, int32_t *n_cells,

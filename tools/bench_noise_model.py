@@ -6,7 +6,9 @@ The mixed batch of workloads.mixed_config (S1 + S2 pairs, PMT afterpulses and no
 * ``table_1e6``    a 10^6-sample table of the same distribution: long enough not to repeat inside a row, 2 B of HBM per sample read;
 * ``model``        noise_model = {'sigma': 2.2}: drawn per sample, no table (noise kind 3);
 * ``colour_L4``, ``colour_L16``, ``colour_L4_common``, ``colour_L16_common``  the same with unit-power FIR taps of 4 / 16 samples, without and
-  with one common stream shared by all channels (gain 0.5): noise kind 4, one or two streams per row.
+  with one common stream shared by all channels (gain 0.5): noise kind 4, one or two streams per row;
+* ``slow_1``, ``slow_8``, ``slow_8_common``, ``colour_L16_common+slow_8``  the white model with one (shift 8) or eight (shifts 4 .. 11) slow
+  levels of amplitude 0.25, then with a common stream that has the eight levels too, then on top of ``colour_L16_common``: noise kind 5.
 
 ``--variants a,b`` runs a subset.  Prints one JSON line: ms per step of each (several repeats), and the per-kernel times of k_zle, k_pack, k_row_pulse and k_pack_res from
 one profiled step (wfs_kernel_times).  Report only: the three compute different noise, so records and intervals differ in number.
@@ -77,12 +79,19 @@ def main():
         common = dict(groups=np.zeros(n_ch, dtype=np.int64), gain=0.5, sigma=2.2, taps=taps)
         variants += [(f'colour_L{L}', dict(noise_model={'sigma': 2.2, 'taps': taps})),
                      (f'colour_L{L}_common', dict(noise_model={'sigma': 2.2, 'taps': taps, 'common': common}))]
+    slow8 = dict(shifts=list(range(4, 12)), amplitude=[0.25] * 8)
+    variants += [('slow_1', dict(noise_model={'sigma': 2.2, 'slow': dict(shifts=[8], amplitude=[0.25])})),
+                 ('slow_8', dict(noise_model={'sigma': 2.2, 'slow': slow8})),
+                 ('slow_8_common', dict(noise_model={'sigma': 2.2, 'slow': slow8, 'common': dict(groups=np.zeros(n_ch, dtype=np.int64), gain=0.5, sigma=2.2,
+                                                                                                   slow=[0.25] * 8)})),
+                 ('colour_L16_common+slow_8', dict(noise_model={'sigma': 2.2, 'taps': taps, 'slow': slow8, 'common': dict(common, slow=[0.25] * 8)}))]
     if args.variants:
         variants = [v for v in variants if v[0] in args.variants.split(',')]
     res = dict(workload='mixed', instructions=args.instructions, steps=args.steps, warmup=args.warmup)
     for name, ov in variants:
         eng = make(args.instructions, **ov)
-        assert (eng.noise_model is not None) == (not name.startswith('table')) and (eng.noise_colour is not None) == name.startswith('colour')
+        assert (eng.noise_model is not None) == (not name.startswith('table')) and (eng.noise_colour is not None) == (name.startswith('colour') or 'common' in name)
+        assert (eng.noise_slow is not None) == ('slow' in name)
         ms, c = timed(eng, args.steps, args.warmup)
         eng.set_profiling(True)
         eng.run()

@@ -39,7 +39,10 @@ enum WfsSite : u32 {
     // index; sample t owns word t & 3
     SITE_NOISE_SAMPLE = 65,
     // the common streams of the coloured model (wfs_set_noise_colour): the same counter with the group in place of the channel
-    SITE_NOISE_COMMON = 66
+    SITE_NOISE_COMMON = 66,
+    // the slow levels of the model (wfs_set_noise_slow): level j of a channel at site 80 + j, of common stream g (in place of the
+    // channel) at 96 + j, j < 8; counter (low, high 32 bits of m >> 2, ..), m the knot index t >> shift[j]; knot m owns word m & 3
+    SITE_NOISE_SLOW = 80, SITE_NOISE_SLOW_COMMON = 96
 };
 
 struct u32x4 { u32 x, y, z, w; };
@@ -104,6 +107,9 @@ __device__ __forceinline__ u32x4 noise_quad_of(u32 k0, u32 k1, u32 id, u32 site,
 constexpr int NC_MAX_TAPS = 16;
 constexpr int NC_TAP_PAD = 6;
 constexpr int NC_TAP_STRIDE = NC_MAX_TAPS + 2 * NC_TAP_PAD;
+// The slow levels (wfs_set_noise_slow): at most NS_MAX_LEVELS, knots 2^shift samples apart with NS_MIN_SHIFT <= shift <= NS_MAX_SHIFT.
+// A block of 256 samples touches at most 255 / 2^NS_MIN_SHIFT + 3 = 18 knots of a level, which lie in at most NS_QUADS aligned quads.
+constexpr int NS_MAX_LEVELS = 8, NS_MIN_SHIFT = 4, NS_MAX_SHIFT = 30, NS_QUADS = 6;
 
 // Integer-valued delays.  The reference draws float variates and truncates each to int64 before adding it (pulse.py:54-56
 // transit time, s1.py:193-194, s2.py:338, pulse.py:339-341, s2.py:550); only the SUM reaches the pulse, and the sum of
@@ -341,4 +347,8 @@ struct WfsDev {
     // colour; the cells of common stream g are row noise_channels + g of nm_cells; group (-1: none) and Q16 gain per channel
     const i32 *nc_taps, *nc_group, *nc_mix;
     i32 nc_n_taps, nc_groups;
+    // the slow levels of the model (wfs_set_noise_slow, noise kind 5): ns_shift [NS_MAX_LEVELS], nullptr without levels; Q16 amplitudes
+    // ns_amp [noise_channels + nc_groups][NS_MAX_LEVELS].  With levels nc_taps is never null: a model without a colour gets unit taps
+    const i32 *ns_shift, *ns_amp;
+    i32 ns_levels;
 };

@@ -112,7 +112,11 @@ struct wfs_handle {
     std::vector<uint2> h_nm_cells; i32 nm_channels = 0, nm_k = 0, nm_shift = 0, nm_vmin = 0, nm_values = 0;
     // its colour (wfs_set_noise_colour): nc_buf holds taps [nm_channels + nc_groups][NC_TAP_STRIDE] | group [nm_channels] | mix [nm_channels];
     // the cells of the common streams follow the channels' in nm_cells (h_nm_cells keeps the channels' alone).  nc_n_taps 0: white
-    i32 nc_n_taps = 0, nc_groups = 0;
+    i32 nc_n_taps = 0, nc_groups = 0; std::vector<i64> h_nc_tapsum;      // (sum |taps_q| per row: the bound of wfs_set_noise_slow)
+    // its slow levels (wfs_set_noise_slow): ns_buf holds shift [NS_MAX_LEVELS] | amplitudes [nm_channels + nc_groups][NS_MAX_LEVELS] | for a
+    // model without a colour, unit taps [nm_channels][NC_TAP_STRIDE] that stand in for nc_buf.  ns_levels 0: none
+    i32 ns_levels = 0;
+    void clear_noise_colour() { nc_n_taps = 0; nc_groups = 0; nc_buf.reset(); h_nc_tapsum.clear(); ns_levels = 0; ns_buf.reset(); }
     i32 table_channels = 0;           // columns of the noise table (dev.noise_channels counts the model's channels while a model is set)
 
     // packed records: two arenas used in turn, so that the device -> host copy of one batch (copy stream, pinned host memory)
@@ -144,7 +148,7 @@ struct wfs_handle {
     DevBuf row_lo, row_hi, acc_len, acc_off, itv_cap, itv_off, active_rows, raw;
     DevBuf itv_left, itv_right, itv_n, row_nrec, rec_off;
     DevBuf truth, tminmax, tile_truth, tile_desc, gather_idx, gather_out, currents, cur_len, cur_off, row_dbg, row_dbg_len, row_dbg_off;
-    DevBuf stamps, row_desc, rec_key, rec_key2, rec_val, rec_val2, rec_dest, sort_tmp, scan_tmp, scal, noise_override, nm_cells, nc_buf, pack_desc;
+    DevBuf stamps, row_desc, rec_key, rec_key2, rec_val, rec_val2, rec_dest, sort_tmp, scan_tmp, scal, noise_override, nm_cells, nc_buf, ns_buf, pack_desc;
     DevBuf row_bad, fin_len, res_cnt, fin_off, res_toff, res_desc, fin, res_long, res_rows;      // resident rows (k_row_pulse)
     DevBuf tt_alias[6], ap_ins, ap_ch, ap_t, ap_gain, ap_cand, ap_args_dev, ap_seg;
     DevBuf d_tabs, prop_top, prop_bot, ins_tab, ins_tabb, ins_pzi, ins_pzf, gg_inv, ins_gg, ins_ggw, ins_ggsum;
@@ -323,13 +327,14 @@ int read_scal(wfs_handle *h)
 }
 
 // The row kernels take the kind of noise as a template parameter (no branch between their loads): 0 none, 1 int16 table, 2 float
-// table, 3 the noise model, 4 the noise model with a colour.
+// table, 3 the noise model, 4 the noise model with a colour, 5 the same with slow levels.
 // f is called with a std::integral_constant of the kind.
 template <class F> void with_noise_kind(int kind, F &&f)
 {
     if (kind == 0) f(std::integral_constant<int, 0>{}); else if (kind == 1) f(std::integral_constant<int, 1>{}); else if (kind == 2) f(std::integral_constant<int, 2>{});
     else if (kind == 3) f(std::integral_constant<int, 3>{});
-    else f(std::integral_constant<int, 4>{});
+    else if (kind == 4) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 5>{});
 }
 
 // a code that kernels raised in the device scalar block (WfsDevError) -> error code and message of the C ABI
@@ -513,6 +518,10 @@ void refresh_dev(wfs_handle *h)
     d.nc_taps = colour ? h->nc_buf.as<i32>() : nullptr; d.nc_n_taps = colour ? h->nc_n_taps : 0; d.nc_groups = colour ? h->nc_groups : 0;
     d.nc_group = (colour && h->nc_groups > 0) ? d.nc_taps + (size_t)(h->nm_channels + h->nc_groups) * NC_TAP_STRIDE : nullptr;
     d.nc_mix = d.nc_group ? d.nc_group + h->nm_channels : nullptr;
+    // its slow levels (wfs_set_noise_slow); without a colour the unit taps behind the amplitudes are the taps
+    const bool slow = model && h->ns_levels > 0;
+    d.ns_shift = slow ? h->ns_buf.as<i32>() : nullptr; d.ns_amp = slow ? d.ns_shift + NS_MAX_LEVELS : nullptr; d.ns_levels = slow ? h->ns_levels : 0;
+    if (slow && !colour) { d.nc_taps = d.ns_amp + (size_t)h->nm_channels * NS_MAX_LEVELS; d.nc_n_taps = 1; }
     d.enable_noise = (c.enable_noise && (model || d.noise != nullptr)) ? 1 : 0;
     bool he_noise = d.enable_noise && d.noise_channels > c.he_first;
     d.he_rows = (c.detector_nt && c.n_top > 0 && (c.he_factor != 0 || he_noise)) ? 1 : 0;
@@ -623,7 +632,10 @@ try {
 #define K_ROW_PULSE_1(F) k_row_pulse<1, F, true>
 #define K_ROW_PULSE_2(F) k_row_pulse<2, F, true>
 #define K_ROW_PULSE_3(F) k_row_pulse<3, F, true>
+#define K_ROW_PULSE_4(F) k_row_pulse<4, F, true>
+#define K_ROW_PULSE_5(F) k_row_pulse<5, F, true>
     WFS_BIG_LDS_F(K_ROW_PULSE_0, 128); WFS_BIG_LDS_F(K_ROW_PULSE_1, 128); WFS_BIG_LDS_F(K_ROW_PULSE_2, 128); WFS_BIG_LDS_F(K_ROW_PULSE_3, 128);
+    WFS_BIG_LDS_F(K_ROW_PULSE_4, 128); WFS_BIG_LDS_F(K_ROW_PULSE_5, 128);
     if (const char *e = getenv("WFS_ROW_RESIDENT")) h->res_env = atoi(e);          // 0 / 1 / 2 as the config switch (A/B runs)
     if (const char *e = getenv("WFS_RES_MAX_LEN")) h->res_max_len = std::max(256, std::min(atoi(e), 7168)) / 256 * 256;      // tuning knob (results do not depend on it)
     WFS_BIG_LDS_F(K_S2_TILE, 100); WFS_BIG_LDS_F(K_S2_TILE_AP, 100);
@@ -2159,7 +2171,7 @@ static int run_rows(wfs_handle *h, RunState &r)
     }
     TRY(fg.flush());
     if (h->run.n_active_rows > 0) { Timer t(h, "k_row_desc"); hipLaunchKernelGGL(k_row_desc, dim3(nblocks(h->run.n_active_rows, 256)), dim3(256), 0, h->stream, d, za); }
-    r.noise_kind = !d.enable_noise ? 0 : (d.nm_cells ? (d.nc_taps ? 4 : 3) : (d.noise_f ? 2 : 1));
+    r.noise_kind = !d.enable_noise ? 0 : (d.nm_cells ? (d.ns_shift ? 5 : (d.nc_taps ? 4 : 3)) : (d.noise_f ? 2 : 1));
     if (h->run.n_res_rows > 0) {        // resident rows: pulses, finished samples and intervals by one wave per row
         PulseArgs pr = pa;
         pr.desc = h->res_desc.as<TileDesc>(); pr.currents = nullptr; pr.cur_off = nullptr;
@@ -2725,7 +2737,7 @@ try {
     if (n_channels == 0) {
         HIPCHK(hipStreamSynchronize(h->stream));
         h->nm_channels = 0; h->h_nm_cells.clear(); h->nm_cells.reset();
-        h->nc_n_taps = 0; h->nc_groups = 0; h->nc_buf.reset();
+        h->clear_noise_colour();
         refresh_dev(h);
         return WFS_OK;
     }
@@ -2749,7 +2761,7 @@ try {
     TRY(upload(h, h->nm_cells, cells.data(), cells.size() * sizeof(uint2)));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->h_nm_cells.swap(cells); h->nm_channels = n_channels; h->nm_k = K; h->nm_shift = shift; h->nm_vmin = vmin; h->nm_values = n_values;
-    h->nc_n_taps = 0; h->nc_groups = 0; h->nc_buf.reset();          // a colour belongs to the shapes of the model it was set on
+    h->clear_noise_colour();            // a colour and slow levels belong to the shapes of the model they were set on
     refresh_dev(h);             // (HE rows may appear or go with the model's channel count: run again before copying rows)
     return WFS_OK;
 } WFS_CATCH(h)
@@ -2765,7 +2777,8 @@ try {
     HIPCHK(hipSetDevice(h->device));
     DevBuf buf;
     TRY(ensure(h, buf, (size_t)n * sizeof(int16_t)));
-    if (h->dev.nc_taps) { Timer t(h, "k_noise_colour_samples"); hipLaunchKernelGGL(k_noise_colour_samples, dim3(nblocks((n + 255) / 256, 4)), dim3(256), 0, h->stream, h->dev, channel, t0, n, buf.as<int16_t>()); }
+    if (h->dev.ns_shift) { Timer t(h, "k_noise_colour_samples"); hipLaunchKernelGGL(k_noise_colour_samples<true>, dim3(nblocks((n + 255) / 256, 4)), dim3(256), 0, h->stream, h->dev, channel, t0, n, buf.as<int16_t>()); }
+    else if (h->dev.nc_taps) { Timer t(h, "k_noise_colour_samples"); hipLaunchKernelGGL(k_noise_colour_samples<false>, dim3(nblocks((n + 255) / 256, 4)), dim3(256), 0, h->stream, h->dev, channel, t0, n, buf.as<int16_t>()); }
     else { Timer t(h, "k_noise_model_samples"); hipLaunchKernelGGL(k_noise_model_samples, dim3(nblocks((n + 3) / 4, 256)), dim3(256), 0, h->stream, h->dev, channel, t0, n, buf.as<int16_t>()); }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, buf.p, (size_t)n * sizeof(int16_t), hipMemcpyDeviceToHost, h->stream));
@@ -2785,7 +2798,7 @@ try {
     if (n_taps == 0) {
         HIPCHK(hipStreamSynchronize(h->stream));
         if (h->nc_groups > 0) { TRY(upload(h, h->nm_cells, h->h_nm_cells.data(), h->h_nm_cells.size() * sizeof(uint2))); HIPCHK(hipStreamSynchronize(h->stream)); }
-        h->nc_n_taps = 0; h->nc_groups = 0; h->nc_buf.reset();
+        h->clear_noise_colour();
         refresh_dev(h);
         return WFS_OK;
     }
@@ -2795,10 +2808,11 @@ try {
     if (n_groups > 0 && (!group || !mix_q || !common_pmf)) return h->fail(WFS_E_INVALID, "wfs_set_noise_colour: null group, mix_q or common_pmf with n_groups > 0");
     const i32 R = C + n_groups;
     const i64 vmax = std::max<i64>(std::llabs((long long)h->nm_vmin), std::llabs((long long)h->nm_vmin + V - 1));
-    std::vector<i32> buf((size_t)R * NC_TAP_STRIDE + 2 * (size_t)C, 0);
+    std::vector<i32> buf((size_t)R * NC_TAP_STRIDE + 2 * (size_t)C, 0); std::vector<i64> tapsum((size_t)R);
     for (i32 r = 0; r < R; r++) {
         i64 sum = 0;
         for (i32 k = 0; k < n_taps; k++) { const i32 v = taps_q[(size_t)r * n_taps + k]; sum += std::llabs((long long)v); buf[(size_t)r * NC_TAP_STRIDE + NC_TAP_PAD + k] = v; }
+        tapsum[(size_t)r] = sum;
         if (sum * vmax >= ((i64)1 << 29)) return h->fail(WFS_E_INVALID, "wfs_set_noise_colour: taps_q of row " + std::to_string(r) + ": sum |taps| * max |value| reaches 2^29");
     }
     i32 *grp = buf.data() + (size_t)R * NC_TAP_STRIDE, *mix = grp + C;
@@ -2823,8 +2837,66 @@ try {
     if (n_groups > 0 || h->nc_groups > 0) TRY(upload(h, h->nm_cells, cells.data(), cells.size() * sizeof(uint2)));
     TRY(upload(h, h->nc_buf, buf.data(), buf.size() * sizeof(i32)));
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->nc_n_taps = n_taps; h->nc_groups = n_groups;
+    h->nc_n_taps = n_taps; h->nc_groups = n_groups; h->h_nc_tapsum.swap(tapsum);
+    h->ns_levels = 0; h->ns_buf.reset();            // the slow levels belong to the rows of the colour they were set on
     refresh_dev(h);
+    return WFS_OK;
+} WFS_CATCH(h)
+
+// The slow levels of the noise model: interpolated knot sequences per stream, octaves apart.  The bound of the colour with
+// the slow amplitudes added keeps every int32 sum of the kernels exact.
+int wfs_set_noise_slow(wfs_handle *h, int32_t n_levels, const int32_t *shifts, const int32_t *slow_q)
+try {
+    if (!h) return WFS_E_INVALID;
+    if (h->nm_channels <= 0) return h->fail(WFS_E_STATE, "wfs_set_noise_slow: no noise model is set");
+    HIPCHK(hipSetDevice(h->device));
+    if (n_levels == 0) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        h->ns_levels = 0; h->ns_buf.reset();
+        refresh_dev(h);
+        return WFS_OK;
+    }
+    if (n_levels < 0 || n_levels > NS_MAX_LEVELS) return h->fail(WFS_E_INVALID, "wfs_set_noise_slow: n_levels outside 0 .. 8");
+    if (!shifts || !slow_q) return h->fail(WFS_E_INVALID, "wfs_set_noise_slow: null shifts or slow_q");
+    for (i32 j = 0; j < n_levels; j++) {
+        if (shifts[j] < NS_MIN_SHIFT || shifts[j] > NS_MAX_SHIFT) return h->fail(WFS_E_INVALID, "wfs_set_noise_slow: shifts[" + std::to_string(j) + "] outside 4 .. 30");
+        if (j > 0 && shifts[j] <= shifts[j - 1]) return h->fail(WFS_E_INVALID, "wfs_set_noise_slow: shifts not strictly ascending at level " + std::to_string(j));
+    }
+    const bool colour = h->nc_n_taps > 0;
+    const i32 C = h->nm_channels, R = C + (colour ? h->nc_groups : 0);
+    const i64 vmax = std::max<i64>(std::llabs((long long)h->nm_vmin), std::llabs((long long)h->nm_vmin + h->nm_values - 1));
+    std::vector<i32> buf((size_t)NS_MAX_LEVELS * (1 + (size_t)R) + (colour ? 0 : (size_t)C * NC_TAP_STRIDE), 0);
+    for (i32 j = 0; j < NS_MAX_LEVELS; j++) buf[(size_t)j] = shifts[j < n_levels ? j : n_levels - 1];
+    for (i32 r = 0; r < R; r++) {
+        i64 sum = colour ? h->h_nc_tapsum[(size_t)r] : 65536;     // (without a colour F = 65536 w)
+        for (i32 j = 0; j < n_levels; j++) { const i32 v = slow_q[(size_t)r * n_levels + j]; sum += std::llabs((long long)v); buf[(size_t)NS_MAX_LEVELS * (1 + (size_t)r) + j] = v; }
+        if (sum * vmax >= ((i64)1 << 29)) return h->fail(WFS_E_INVALID, "wfs_set_noise_slow: slow_q of row " + std::to_string(r) + ": (sum |taps| + sum |slow|) * max |value| reaches 2^29");
+    }
+    if (!colour) for (i32 c = 0; c < C; c++) buf[(size_t)NS_MAX_LEVELS * (1 + (size_t)R) + (size_t)c * NC_TAP_STRIDE + NC_TAP_PAD] = 65536;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    TRY(upload(h, h->ns_buf, buf.data(), buf.size() * sizeof(i32)));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->ns_levels = n_levels;
+    refresh_dev(h);
+    return WFS_OK;
+} WFS_CATCH(h)
+
+int wfs_noise_slow_samples(wfs_handle *h, int32_t row, int64_t t0, int64_t n, int32_t *out)
+try {
+    if (!h) return WFS_E_INVALID;
+    if (h->nm_channels <= 0 || h->ns_levels <= 0) return h->fail(WFS_E_STATE, "wfs_noise_slow_samples: no noise model with slow levels is set");
+    if (row < 0 || row >= h->nm_channels + h->nc_groups) return h->fail(WFS_E_INVALID, "wfs_noise_slow_samples: row outside the model's channels and common streams");
+    if (n < 0 || n > ((i64)1 << 30) || (n > 0 && !out)) return h->fail(WFS_E_INVALID, "wfs_noise_slow_samples: n outside 0 .. 2^30 or null buffer");
+    if (t0 > I64_MAX - n) return h->fail(WFS_E_INVALID, "wfs_noise_slow_samples: t0 + n overflows");
+    if (n == 0) return WFS_OK;
+    HIPCHK(hipSetDevice(h->device));
+    DevBuf buf;
+    TRY(ensure(h, buf, (size_t)n * sizeof(i32)));
+    { Timer t(h, "k_noise_slow_samples"); hipLaunchKernelGGL(k_noise_slow_samples, dim3(nblocks((n + 255) / 256, 4)), dim3(256), 0, h->stream, h->dev, row, t0, n, buf.as<i32>()); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, buf.p, (size_t)n * sizeof(i32), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    CHECK_LAUNCHES();
     return WFS_OK;
 } WFS_CATCH(h)
 

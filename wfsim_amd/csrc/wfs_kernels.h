@@ -1684,8 +1684,89 @@ __device__ __forceinline__ i32 colour_stream_sample(const WfsDev &d, i32 row, u3
     }
     return F;
 }
+// The slow levels (wfs_set_noise_slow, noise kind 5): level j of stream r is a sequence of knots 2^s_j samples apart, knot m
+// drawn from the stream's own alias cells with word m & 3 of the Philox call of (m >> 2, channel | group, SITE_NOISE_SLOW(_COMMON) + j),
+// joined by linear interpolation in integers:
+//   m = t >> s_j, f = t & (2^s_j - 1), P0 = amp[r][j] knot(m), P1 = amp[r][j] knot(m + 1),  S(r, t) = sum_j P0 + (((i64)(P1 - P0) f) >> s_j)
+// and F'(r, t) = F(r, t) + S(r, t) takes the place of F in the coloured model: the host has checked that F' fits 30 bits.
+//
+// Single-sample form: a lane draws its own two knots per level (one call, two when the pair straddles a quad).  No cross-lane traffic:
+// legal in divergent code and with any t and row per lane, like colour_stream_sample.
+__device__ __forceinline__ i32 slow_stream_sample(const WfsDev &d, i32 row, u32 id, u32 site, i64 t)
+{
+    const AliasTab tab{d.nm_cells + (i64)row * d.nm_cells_per_ch, d.nm_vmin, d.nm_shift};
+    const i32 *amp = d.ns_amp + (i64)row * NS_MAX_LEVELS;
+    i32 S = 0;
+#pragma nounroll
+    for (int j = 0; j < d.ns_levels; j++) {
+        const i32 a = amp[j];
+        if (a == 0) continue;
+        const i32 s = d.ns_shift[j];
+        const i64 m = t >> s;
+        const i32 f = (i32)((u32)t & ((1u << s) - 1u));         // (s <= 30: the phase fits 32 bits, and the product below is one 32 x 32 -> 64 multiply)
+        const u32x4 q = noise_quad_of(d.k0, d.k1, id, site + (u32)j, m >> 2);
+        const u32 c = (u32)m & 3u;
+        const u32 w0 = c == 0 ? q.x : (c == 1 ? q.y : (c == 2 ? q.z : q.w));
+        u32 w1 = c == 0 ? q.y : (c == 1 ? q.z : q.w);
+        if (c == 3) w1 = noise_quad_of(d.k0, d.k1, id, site + (u32)j, (m >> 2) + 1).x;
+        const i32 P0 = a * alias_sample(tab, w0), P1 = a * alias_sample(tab, w1);
+        S += P0 + (i32)(((i64)(P1 - P0) * (i64)f) >> s);
+    }
+    return S;
+}
+// Four-sample form: lane l of a wave takes samples tb + 4 l .. tb + 4 l + 3, tb wave-uniform.  With s >= NS_MIN_SHIFT the 256 samples of
+// the wave touch at most 18 knots of a level, which lie in the NS_QUADS aligned quads from qb_j = (tb >> s_j) >> 2 on: lane 8 j + k draws
+// quad qb_j + k of level j and alias-samples it -- ONE Philox call per lane for all levels together -- and its four knots travel as two
+// packed words.  Four consecutive samples cross at most one knot, so a lane needs three consecutive knots of a level; they sit in one
+// or two neighbouring quads, fetched by four ds_bpermute per level with an amplitude (levels with amplitude 0 are skipped: the
+// amplitude is the row's, wave-uniform).
+// ALL 64 LANES MUST BE EXECUTING, as for colour_stream_four: call it before any per-lane bound.
+__device__ __forceinline__ void slow_stream_four(const WfsDev &d, i32 row, u32 id, u32 site, i64 tb, int lane, i32 *S)
+{
+    const AliasTab tab{d.nm_cells + (i64)row * d.nm_cells_per_ch, d.nm_vmin, d.nm_shift};
+    const i32 *amp = d.ns_amp + (i64)row * NS_MAX_LEVELS;
+    const int nl = d.ns_levels;
+    const int lj = (lane >> 3) < nl ? (lane >> 3) : nl - 1;    // (the lanes of levels that are not there repeat the last one; nobody reads them)
+    const i64 qown = ((tb >> d.ns_shift[lj]) >> 2) + (lane & 7);
+    const u32x4 a = noise_quad_of(d.k0, d.k1, id, site + (u32)lj, qown);
+    const u32 p0 = ((u32)alias_sample(tab, a.x) & 0xffffu) | ((u32)alias_sample(tab, a.y) << 16);
+    const u32 p1 = ((u32)alias_sample(tab, a.z) & 0xffffu) | ((u32)alias_sample(tab, a.w) << 16);
+    const i64 t0 = tb + 4 * lane;
+    S[0] = S[1] = S[2] = S[3] = 0;
+#pragma nounroll
+    for (int j = 0; j < nl; j++) {                              // (wave-uniform, and so is the skip)
+        const i32 aq = __builtin_amdgcn_readfirstlane(amp[j]);
+        if (aq == 0) continue;
+        const i32 s = __builtin_amdgcn_readfirstlane(d.ns_shift[j]);
+        const i64 m0 = t0 >> s;
+        const i32 k0 = (i32)(m0 - (((tb >> s) >> 2) << 2));    // the lane's first knot among the level's 4 NS_QUADS: 0 .. 19, the third at most 21
+        const i32 qa = k0 >> 2, qc = (k0 + 2) >> 2;
+        const i32 src_a = (8 * j + qa) << 2, src_c = (8 * j + qc) << 2;
+        const u32 a0 = (u32)__builtin_amdgcn_ds_bpermute(src_a, (int)p0), a1 = (u32)__builtin_amdgcn_ds_bpermute(src_a, (int)p1);
+        const u32 c0 = (u32)__builtin_amdgcn_ds_bpermute(src_c, (int)p0), c1 = (u32)__builtin_amdgcn_ds_bpermute(src_c, (int)p1);
+        i32 P[3];
+#pragma unroll
+        for (int u = 0; u < 3; u++) {
+            const i32 k = k0 + u;
+            const bool first = (k >> 2) == qa;
+            const u32 w = (k & 2) ? (first ? a1 : c1) : (first ? a0 : c0);
+            P[u] = aq * ((k & 1) ? (i32)w >> 16 : (i32)(int16_t)w);
+        }
+        const u32 mask = (1u << s) - 1u, f0 = (u32)t0 & mask;    // the phase of the lane's first sample; the others in 32 bits from it
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const bool next = f0 + (u32)c > mask;               // (c < 4 <= 2^s: at most one knot is crossed)
+            const i32 f = (i32)((f0 + (u32)c) & mask);
+            const i32 Pa = next ? P[1] : P[0], Pb = next ? P[2] : P[1];
+            S[c] += Pa + (i32)(((i64)(Pb - Pa) * (i64)f) >> s);
+        }
+    }
+}
+
 // The streams of a channel are walked by a loop that stays a loop (the channel's own with gain 1.0, then its common stream with mix):
 // one copy of the draws per call site, whatever the number of streams -- unrolled and interleaved they took every register there is.
+// (SLOW: kind 5, the slow levels of every stream added to its F.)
+template <bool SLOW = false>
 __device__ __forceinline__ i32 noise_colour_sample(const WfsDev &d, i32 channel, i64 t)
 {
     const i32 g = d.nc_group ? d.nc_group[channel] : -1;        // (wave-uniform wherever a wave works on one row)
@@ -1693,7 +1774,8 @@ __device__ __forceinline__ i32 noise_colour_sample(const WfsDev &d, i32 channel,
     i32 sum = 0;
 #pragma nounroll
     for (int s = 0; s < (g >= 0 ? 2 : 1); s++) {
-        const i32 F = colour_stream_sample(d, s ? d.noise_channels + g : channel, (u32)(s ? g : channel), s ? SITE_NOISE_COMMON : SITE_NOISE_SAMPLE, t);
+        i32 F = colour_stream_sample(d, s ? d.noise_channels + g : channel, (u32)(s ? g : channel), s ? SITE_NOISE_COMMON : SITE_NOISE_SAMPLE, t);
+        if constexpr (SLOW) F += slow_stream_sample(d, s ? d.noise_channels + g : channel, (u32)(s ? g : channel), s ? SITE_NOISE_SLOW_COMMON : SITE_NOISE_SLOW, t);
         sum += (i32)(((i64)(s ? mix : 65536) * F) >> 16);       // (65536 F >> 16 is F)
     }
     return (sum + 32768) >> 16;
@@ -1739,6 +1821,7 @@ __device__ __forceinline__ void colour_stream_four(const WfsDev &d, i32 row, u32
             for (int j = 0; j < 4; j++) F[j] += tp[3 + j - c] * w[c];
     }
 }
+template <bool SLOW = false>
 __device__ __forceinline__ void noise_colour_four(const WfsDev &d, i32 channel, i64 tb, int lane, i32 *out)
 {
     const i32 g = __builtin_amdgcn_readfirstlane(d.nc_group ? d.nc_group[channel] : -1);        // (one row per wave)
@@ -1748,6 +1831,12 @@ __device__ __forceinline__ void noise_colour_four(const WfsDev &d, i32 channel, 
     for (int s = 0; s < (g >= 0 ? 2 : 1); s++) {
         i32 F[4];
         colour_stream_four(d, s ? d.noise_channels + g : channel, (u32)(s ? g : channel), s ? SITE_NOISE_COMMON : SITE_NOISE_SAMPLE, tb, lane, F);
+        if constexpr (SLOW) {
+            i32 S[4];
+            slow_stream_four(d, s ? d.noise_channels + g : channel, (u32)(s ? g : channel), s ? SITE_NOISE_SLOW_COMMON : SITE_NOISE_SLOW, tb, lane, S);
+#pragma unroll
+            for (int j = 0; j < 4; j++) F[j] += S[j];
+        }
 #pragma unroll
         for (int j = 0; j < 4; j++) sum[j] += (i32)(((i64)(s ? mix : 65536) * F[j]) >> 16);
     }
@@ -1755,7 +1844,8 @@ __device__ __forceinline__ void noise_colour_four(const WfsDev &d, i32 channel, 
     for (int j = 0; j < 4; j++) out[j] = (sum[j] + 32768) >> 16;
 }
 
-// (NK: the noise kind of the row kernels below; row_abs, the row's first absolute sample, is what kinds 3 and 4 count from)
+// (NK: the noise kind of the row kernels below; row_abs, the row's first absolute sample, is what kinds 3, 4 and 5 count from; kind 5 is
+// kind 4 with the slow levels and goes wherever kind 4 goes)
 template <int NK>
 __device__ __forceinline__ i32 finish_sample(const WfsDev &d, const i32 *acc, i64 i, i32 slot_ch, bool he, i64 ix_rand, i64 row_abs)
 {
@@ -1763,8 +1853,8 @@ __device__ __forceinline__ i32 finish_sample(const WfsDev &d, const i32 *acc, i6
     if (he) v *= d.he_factor;                                   // rawdata.py:242-246
     if constexpr (NK == 3) {
         if (slot_ch < d.noise_channels) v += noise_model_sample(d, d.nm_cells + (i64)slot_ch * d.nm_cells_per_ch, slot_ch, row_abs + i);
-    } else if constexpr (NK == 4) {
-        if (slot_ch < d.noise_channels) v += noise_colour_sample(d, slot_ch, row_abs + i);
+    } else if constexpr (NK == 4 || NK == 5) {
+        if (slot_ch < d.noise_channels) v += noise_colour_sample<NK == 5>(d, slot_ch, row_abs + i);
     } else
     if (d.enable_noise && slot_ch < d.noise_channels) {
         const u32 in = ((u32)ix_rand + (u32)i) % (u32)d.noise_len;      // rawdata.py:433-434 (ix_rand < noise_len <= 2^31, i < 2^20: 32 bits hold the sum)
@@ -1794,19 +1884,38 @@ __global__ __launch_bounds__(256) void k_noise_model_samples(WfsDev d, i32 chann
 }
 
 // The same for the coloured model: a wave takes 256 consecutive samples through the four-sample form -- every lane draws and exchanges,
-// whatever n, and only the stores look at n -- and the last n & 3 samples go through the single-sample form.
+// whatever n, and only the stores look at n -- and the last n & 3 samples go through the single-sample form.  (SLOW: with the slow levels)
+template <bool SLOW>
 __global__ __launch_bounds__(256) void k_noise_colour_samples(WfsDev d, i32 channel, i64 t0, i64 n, int16_t *out)
 {
     const int lane = threadIdx.x & 63;
     const i64 b = ((i64)blockIdx.x * 4 + wave_in_block()) * 256;
     i32 v[4];
-    noise_colour_four(d, channel, t0 + b, lane, v);
+    noise_colour_four<SLOW>(d, channel, t0 + b, lane, v);
     const i64 s = b + 4 * lane;
     if (s + 3 < n) {
 #pragma unroll
         for (int j = 0; j < 4; j++) out[s + j] = (int16_t)v[j];
     } else {
-        for (i64 u = s; u < n; u++) out[u] = (int16_t)noise_colour_sample(d, channel, t0 + u);
+        for (i64 u = s; u < n; u++) out[u] = (int16_t)noise_colour_sample<SLOW>(d, channel, t0 + u);
+    }
+}
+// wfs_noise_slow_samples: S(row, t0 .. t0 + n - 1) in Q16 of a stream, a channel or (row >= noise_channels) a common stream, through the
+// same two forms
+__global__ __launch_bounds__(256) void k_noise_slow_samples(WfsDev d, i32 row, i64 t0, i64 n, i32 *out)
+{
+    const int lane = threadIdx.x & 63;
+    const i64 b = ((i64)blockIdx.x * 4 + wave_in_block()) * 256;
+    const bool common = row >= d.noise_channels;
+    const u32 id = (u32)(common ? row - d.noise_channels : row), site = common ? SITE_NOISE_SLOW_COMMON : SITE_NOISE_SLOW;
+    i32 v[4];
+    slow_stream_four(d, row, id, site, t0 + b, lane, v);
+    const i64 s = b + 4 * lane;
+    if (s + 3 < n) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) out[s + j] = v[j];
+    } else {
+        for (i64 u = s; u < n; u++) out[u] = slow_stream_sample(d, row, id, site, t0 + u);
     }
 }
 // wfs_noise_white_samples: the white sequence w(row, t0 .. t0 + n - 1) of a stream, a channel or (row >= noise_channels) a common stream
@@ -1835,7 +1944,8 @@ __device__ __forceinline__ void row_of_slot(const WfsDev &d, i64 idx, i64 &g, i3
 // A row no longer than the noise array wraps at most once (ix_rand < noise_len, i < len <= noise_len): no loop on the load path.
 // NK, the noise of the batch, is a template parameter (0: none, 1: int16 table, 2: float64 table, 3: the noise model, drawn where the
 // tables are loaded: noise_row then points at the channel's alias cells, nullptr for a row outside the model; 4: the coloured model,
-// drawn at the same places -- load_sample through the single-sample form, load_four through the shared draws) and a row outside the table
+// drawn at the same places -- load_sample through the single-sample form, load_four through the shared draws; 5: the same with the
+// slow levels added to every stream) and a row outside the table
 // (noisy false, wave-uniform) reads row 0 and drops the value: NO branch sits between two loads -- with a branch around the
 // noise load the compiler drained the memory counter after every one of them.
 template <int NK> struct RawSample;
@@ -1844,6 +1954,7 @@ template <> struct RawSample<1> { i32 acc; i32 nz; };
 template <> struct RawSample<2> { i32 acc; double nzf; };
 template <> struct RawSample<3> { i32 acc; i32 nz; };
 template <> struct RawSample<4> { i32 acc; i32 nz; };
+template <> struct RawSample<5> { i32 acc; i32 nz; };
 template <int NK>
 __device__ __forceinline__ RawSample<NK> load_sample(const WfsDev &d, const i32 *acc, i32 i, const void *noise_row, u32 nstart, u32 noff, i32 channel = 0, i64 row_abs = 0)
 {
@@ -1851,7 +1962,7 @@ __device__ __forceinline__ RawSample<NK> load_sample(const WfsDev &d, const i32 
     // noise sample nstart + noff of the row, nstart < noise_len a scalar, noff < noise_len: one conditional subtraction wraps it
     RawSample<NK> s; s.acc = acc[(u32)i];
     if constexpr (NK == 3) s.nz = noise_row ? noise_model_sample(d, (const uint2 *)noise_row, channel, row_abs + i) : 0;      // (wave-uniform)
-    else if constexpr (NK == 4) s.nz = noise_row ? noise_colour_sample(d, channel, row_abs + i) : 0;
+    else if constexpr (NK == 4 || NK == 5) s.nz = noise_row ? noise_colour_sample<NK == 5>(d, channel, row_abs + i) : 0;
     else if constexpr (NK != 0) {
         u32 in = nstart + noff;
         in = in >= (u32)d.noise_len ? in - (u32)d.noise_len : in;
@@ -1866,7 +1977,7 @@ __device__ __forceinline__ i32 finish_loaded(const WfsDev &d, const RawSample<NK
     if (he) v *= d.he_factor;
     if constexpr (NK == 1) v += noisy ? s.nz : 0;
     if constexpr (NK == 2) { const i64 w = (i64)((double)v + s.nzf); v = noisy ? w : v; }
-    if constexpr (NK == 3 || NK == 4) v += s.nz;
+    if constexpr (NK >= 3) v += s.nz;
     v += d.baseline;
     return v < 0 ? 0 : (i32)v;
 }
@@ -1879,6 +1990,7 @@ template <> struct Raw4<1> { i32 acc[4]; int16_t nz[4]; };
 template <> struct Raw4<2> { i32 acc[4]; double nzf[4]; };
 template <> struct Raw4<3> { i32 acc[4]; i32 nz[4]; };
 template <> struct Raw4<4> { i32 acc[4]; i32 nz[4]; };
+template <> struct Raw4<5> { i32 acc[4]; i32 nz[4]; };
 template <int NK>
 __device__ __forceinline__ Raw4<NK> load_four(const WfsDev &d, const i32 *acc, i32 i, const void *noise_row, u32 nstart, u32 noff, i32 channel = 0, i64 row_abs = 0)
 {
@@ -1886,10 +1998,10 @@ __device__ __forceinline__ Raw4<NK> load_four(const WfsDev &d, const i32 *acc, i
     if constexpr (NK == 3) {
         if (noise_row) noise_model_four(d, (const uint2 *)noise_row, channel, row_abs, i, s.nz);      // (wave-uniform; i is a multiple of four)
         else s.nz[0] = s.nz[1] = s.nz[2] = s.nz[3] = 0;
-    } else if constexpr (NK == 4) {
+    } else if constexpr (NK == 4 || NK == 5) {
         // i may be clamped into the row (k_zle, lanes past its end): the position is nstart, the UNCLAMPED wave-uniform index of the
         // block's first sample in the row, plus the lane's noff = 4 lane -- a lane past the end still draws the quad its neighbours need
-        if (noise_row) noise_colour_four(d, channel, row_abs + (i64)nstart, (int)(noff >> 2), s.nz);      // (wave-uniform)
+        if (noise_row) noise_colour_four<NK == 5>(d, channel, row_abs + (i64)nstart, (int)(noff >> 2), s.nz);      // (wave-uniform)
         else s.nz[0] = s.nz[1] = s.nz[2] = s.nz[3] = 0;
     } else if constexpr (NK != 0) {
         u32 in = nstart + noff;
@@ -1905,7 +2017,7 @@ __device__ __forceinline__ i32 finish_four(const WfsDev &d, const Raw4<NK> &s, i
     if (he) v *= d.he_factor;
     if constexpr (NK == 1) v += noisy ? (i32)s.nz[j] : 0;
     if constexpr (NK == 2) { const i64 w = (i64)((double)v + s.nzf[j]); v = noisy ? w : v; }
-    if constexpr (NK == 3 || NK == 4) v += s.nz[j];
+    if constexpr (NK >= 3) v += s.nz[j];
     v += d.baseline;
     return v < 0 ? 0 : (i32)v;
 }
@@ -1993,16 +2105,16 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
     // the noise index of a row's sample i is (ix + i) mod noise_len (rawdata.py:433-434): a scalar start per block of samples that
     // steps with the block and wraps, plus the lane's offset inside the block -- rows may be any number of noise lengths long.
     // (A table shorter than NOISE_MIN_FAST samples would wrap more than once inside a block: the general path below.)
-    // (The noise model, kinds 3 and 4, has no table and no wrap: the fast paths wherever kind 0 takes them.)
+    // (The noise model, kinds 3, 4 and 5, has no table and no wrap: the fast paths wherever kind 0 takes them.)
     constexpr bool TABLE = NK == 1 || NK == 2;
     const bool fast_loads = len32 >= 1 && (!TABLE || d.noise_len >= NOISE_MIN_FAST);
     const i64 noise_off = noisy ? (i64)channel * d.noise_stride : 0; const u32 nixr = noisy ? (u32)ixr : 0u;
-    const void *noise_row = (NK == 3 || NK == 4) ? (const void *)(noisy ? d.nm_cells + (i64)channel * d.nm_cells_per_ch : nullptr)
+    const void *noise_row = NK >= 3 ? (const void *)(noisy ? d.nm_cells + (i64)channel * d.nm_cells_per_ch : nullptr)
                                     : (NK == 2 ? (const void *)(d.noise_f + noise_off) : (const void *)(d.noise + noise_off));
     if (hold32 >= 63 && fast_loads && !a.row_dbg) {
         // The usual geometry (hold-off of at least a chunk): the interval bookkeeping is scalar work on the ballot mask (ZleFast), and
         // the vector unit is left with load, finish and compare.
-        constexpr int G = NK == 4 ? 1 : 4;          // (kind 4 draws instead of loading: one block's draws at a time, one copy of their code)
+        constexpr int G = NK >= 4 ? 1 : 4;          // (kind 4 draws instead of loading: one block's draws at a time, one copy of their code)
         ZleFast z;
         // A lane takes FOUR consecutive samples (one 16-byte load of the row, one 8-byte load of the noise): a wave instruction moves
         // 1 KB of the row, and the hits of a lane are a nibble.
@@ -2016,7 +2128,7 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
 #pragma unroll
             for (int u = 0; u < G; u++) {
                 const i32 i = g0 + 256 * u + 4 * lane;
-                buf[u] = load_four<NK>(d, acc, i < len32 ? i : 0, noise_row, NK == 4 ? (u32)(g0 + 256 * u) : nrun, 4u * (u32)lane, channel, row_abs);
+                buf[u] = load_four<NK>(d, acc, i < len32 ? i : 0, noise_row, NK >= 4 ? (u32)(g0 + 256 * u) : nrun, 4u * (u32)lane, channel, row_abs);
                 if constexpr (TABLE) { nrun += 256u; nrun = nrun >= (u32)d.noise_len ? nrun - (u32)d.noise_len : nrun; }
             }
         };
@@ -2038,11 +2150,11 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
     }
     // chunks of 64 samples; the loads of ZLE_GROUP chunks are issued together (one dependent load per chunk leaves the wave
     // waiting a memory round trip per 64 samples)
-    constexpr int ZLE_GROUP = NK == 4 ? 1 : 2;      // (kind 4: nothing to overlap, one copy of the draws)
+    constexpr int ZLE_GROUP = NK >= 4 ? 1 : 2;      // (kind 4: nothing to overlap, one copy of the draws)
     u32 nrun1 = nixr;
     for (i32 g0 = 0; g0 < len32; g0 += 64 * ZLE_GROUP) {
         i32 vv[ZLE_GROUP];
-        if (NK == 4 || fast_loads) {                            // (wave-uniform) every load of the group first, then the arithmetic; kind 4 has no other path: a row it cannot take fast is empty
+        if (NK >= 4 || fast_loads) {                            // (wave-uniform) every load of the group first, then the arithmetic; kind 4 has no other path: a row it cannot take fast is empty
             RawSample<NK> rs[ZLE_GROUP];
 #pragma unroll
             for (int u = 0; u < ZLE_GROUP; u++) {
@@ -2193,9 +2305,9 @@ __global__ __launch_bounds__(256) void k_row_pulse(WfsDev d, PulseArgs a, ZleArg
     const i32 hold32 = (i32)hold;
     const bool noisy = NK != 0 && q.channel < d.noise_channels;
     const i64 noise_off = noisy ? (i64)q.channel * d.noise_stride : 0;
-    const void *noise_row = (NK == 3 || NK == 4) ? (const void *)(noisy ? d.nm_cells + (i64)q.channel * d.nm_cells_per_ch : nullptr)
+    const void *noise_row = NK >= 3 ? (const void *)(noisy ? d.nm_cells + (i64)q.channel * d.nm_cells_per_ch : nullptr)
                                     : (NK == 2 ? (const void *)(d.noise_f + noise_off) : (const void *)(d.noise + noise_off));
-    u32 nrun = (noisy && NK != 3 && NK != 4) ? (u32)q.ixr : 0u;       // noise index of the next block's first sample (rawdata.py:433-434); kinds 3, 4: that sample's index in the row
+    u32 nrun = (noisy && NK < 3) ? (u32)q.ixr : 0u;       // noise index of the next block's first sample (rawdata.py:433-434); kinds 3, 4: that sample's index in the row
     int16_t *fin = z.fin + q.acc_off;
     const i32 fin_len = (len32 + 3) & ~3;
     auto load_noise = [&](Raw4<NK> &o) {
@@ -2203,8 +2315,8 @@ __global__ __launch_bounds__(256) void k_row_pulse(WfsDev d, PulseArgs a, ZleArg
             if (noise_row) noise_model_four(d, (const uint2 *)noise_row, q.channel, row_abs + (i64)nrun, 4 * lane, o.nz);
             else o.nz[0] = o.nz[1] = o.nz[2] = o.nz[3] = 0;
             nrun += 256u;
-        } else if constexpr (NK == 4) {                   // the shared draws: every lane of the wave is here (the callers' conditions are wave-uniform)
-            if (noise_row) noise_colour_four(d, q.channel, row_abs + (i64)nrun, lane, o.nz);
+        } else if constexpr (NK == 4 || NK == 5) {        // the shared draws: every lane of the wave is here (the callers' conditions are wave-uniform)
+            if (noise_row) noise_colour_four<NK == 5>(d, q.channel, row_abs + (i64)nrun, lane, o.nz);
             else o.nz[0] = o.nz[1] = o.nz[2] = o.nz[3] = 0;
             nrun += 256u;
         } else if constexpr (NK != 0) {
@@ -2261,7 +2373,7 @@ __global__ __launch_bounds__(256) void k_row_pulse(WfsDev d, PulseArgs a, ZleArg
                 for (int j = 0; j < 4; j++) {
                     i32 add = d.baseline;
                     if constexpr (NK == 1) add += noisy ? (i32)s4.nz[j] : 0;
-                    if constexpr (NK == 3 || NK == 4) add += s4.nz[j];
+                    if constexpr (NK >= 3) add += s4.nz[j];
                     i32 v = __builtin_elementwise_add_sat(s4.acc[j], add);
                     v = v < 0 ? 0 : v;
                     nib |= (j < live && v < thr32) ? (1u << j) : 0u; v16[j] = (u32)v;
@@ -2396,10 +2508,10 @@ __global__ __launch_bounds__(256) void k_pack(WfsDev d, ZleArgs a)
     constexpr bool TABLE = NK == 1 || NK == 2;
     const bool fast_loads = !TABLE || (d.noise_len >= NOISE_MIN_FAST && spr <= NOISE_MIN_FAST / 2);       // (as in k_zle: a scalar noise start per record)
     const i64 noise_off = noisy ? (i64)channel * d.noise_stride : 0; const u32 nixr = noisy ? (u32)ixr : 0u;
-    const void *noise_row = (NK == 3 || NK == 4) ? (const void *)(noisy ? d.nm_cells + (i64)channel * d.nm_cells_per_ch : nullptr)
+    const void *noise_row = NK >= 3 ? (const void *)(noisy ? d.nm_cells + (i64)channel * d.nm_cells_per_ch : nullptr)
                                     : (NK == 2 ? (const void *)(d.noise_f + noise_off) : (const void *)(d.noise + noise_off));
     const u32 w3 = ((u32)(uint16_t)d.dt) | ((u32)(uint16_t)channel << 16);
-    constexpr int PACK_U = NK == 4 ? 1 : 4;         // (kind 4 draws where the others load: one record's draws at a time, one copy of their code)
+    constexpr int PACK_U = NK >= 4 ? 1 : 4;         // (kind 4 draws where the others load: one record's draws at a time, one copy of their code)
     i64 rec = q.rec;
     for (i32 k = 0; k < count; k++) {
         const i64 left = k == 0 ? q.left0 : a.itv_left[base + k]; const i32 plen = k == 0 ? q.plen0 : (i32)(a.itv_right[base + k] - left + 1);

@@ -111,7 +111,7 @@ EXPORTS = ['wfs_create', 'wfs_destroy', 'wfs_last_error', 'wfs_device_count', 'w
            'wfs_scalar_map_grid', 'wfs_scalar_map_points', 'wfs_scalar_map_spline', 'wfs_scalar_map_eval', 'wfs_set_noise_float', 'wfs_set_instruction_diffusion',
            'wfs_scalar_map_grid_array', 'wfs_scalar_map_points_array', 'wfs_scalar_map_linear', 'wfs_scalar_map_eval_array',
            'wfs_set_sum_signal', 'wfs_copy_sum_signal', 'wfs_device_allocations',
-           'wfs_set_noise_model', 'wfs_noise_model_samples', 'wfs_copy_noise_model', 'wfs_set_noise_colour', 'wfs_noise_white_samples']
+           'wfs_set_noise_model', 'wfs_noise_model_samples', 'wfs_copy_noise_model', 'wfs_set_noise_colour', 'wfs_noise_white_samples', 'wfs_set_noise_slow', 'wfs_noise_slow_samples']
 
 
 def load_library():
@@ -201,9 +201,10 @@ class Engine:
         thr_truth, thr_zle = T.thresholds(config, N_ROWS)
         lum_x, lum_t = T.luminescence_table(config)
         # a noise model (noise_model.py) takes precedence over the noise array of the resource, which is then not uploaded
-        from .noise_model import noise_colour, noise_pmf
+        from .noise_model import noise_colour, noise_pmf, noise_slow
         self.noise_model = noise_pmf(config, params['n_rows']) if params['enable_noise'] else None
         self.noise_colour = noise_colour(config, params['n_rows']) if params['enable_noise'] else None
+        self.noise_slow = noise_slow(config, params['n_rows']) if params['enable_noise'] else None
         self.tables = dict(
             templates=T.pmt_current_templates(config), spe=T.spe_scaling_table(resource.spe_charge, resource.spe_pdfs),
             gains=_arr(config['gains'], np.float64), thr_truth=_arr(thr_truth, np.float64), thr_zle=_arr(thr_zle, np.int64),
@@ -243,6 +244,8 @@ class Engine:
             nc = self.noise_model[0].shape[0]
             if self.noise_colour is not None:
                 self.set_noise_colour(**self.noise_colour)
+            if self.noise_slow is not None:
+                self.set_noise_slow(**self.noise_slow)
         he_noise = bool(params['enable_noise']) and nc > params['he_first']
         self.emits_he_records = bool(params['detector_nt'] and params['n_top'] > 0 and (params['he_factor'] != 0 or he_noise))
         # pattern maps on regular grids are evaluated on the device (one channel CDF row per instruction)
@@ -660,16 +663,22 @@ class Engine:
         a = _arr(ix_rand, np.int64)
         self._check(self.lib.wfs_set_noise_offsets(self._h, _p(a), C.c_int64(len(a))))
 
+    _noise_rows = None          # (channels, common streams) of the noise model that is set
+
     def set_noise_model(self, pmf, vmin=0):
         """pmf[n_channels][n_values] over the ADC offsets vmin .. vmin + n_values - 1 (noise_model.py); None clears the model: the noise
         array, if any, is replayed again.  Acts with enable_noise, from the next run."""
         if pmf is None:
             self._check(self.lib.wfs_set_noise_model(self._h, C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_void_p(0)))
+            self._noise_rows = None
             return
         pmf = _arr(pmf, np.float64)
         if pmf.ndim != 2:
             raise ValueError('set_noise_model: pmf must be [n_channels][n_values]')
         self._check(self.lib.wfs_set_noise_model(self._h, C.c_int32(pmf.shape[0]), C.c_int32(pmf.shape[1]), C.c_int32(int(vmin)), _p(pmf)))
+        # (channels, common streams) of the model as the library holds it: the C entry points of the colour and of the slow levels take
+        # no row count and read n_channels + n_groups rows, so the arrays are checked against it here
+        self._noise_rows = (int(pmf.shape[0]), 0)
 
     def set_noise_colour(self, taps_q, group=None, mix_q=None, common_pmf=None):
         """The colour of the noise model that is set (noise_model.py, wfs_set_noise_colour): taps_q int32[n_channels + n_groups][L] in Q16,
@@ -677,11 +686,16 @@ class Engine:
         last three may be None without common streams.  taps_q None clears the colour: the white values return.  From the next run."""
         if taps_q is None:
             self._check(self.lib.wfs_set_noise_colour(self._h, C.c_int32(0), C.c_void_p(0), C.c_int32(0), C.c_void_p(0), C.c_void_p(0), C.c_void_p(0)))
+            self._noise_rows = (self._noise_rows[0], 0) if self._noise_rows else None
             return
         taps_q = _arr(taps_q, np.int32)
         if taps_q.ndim != 2:
             raise ValueError('set_noise_colour: taps_q must be [n_channels + n_groups][n_taps]')
         n_groups = 0 if common_pmf is None else len(common_pmf)
+        n_ch = self._noise_rows
+        if n_ch is not None and (taps_q.shape[0] != n_ch[0] + n_groups or (n_groups and len(np.atleast_1d(group)) != n_ch[0])):
+            raise ValueError(f'set_noise_colour: the model has {n_ch[0]} channels: taps_q must have {n_ch[0] + n_groups} rows ({n_groups} groups), '
+                             f'group and mix_q {n_ch[0]} entries')
         if n_groups:
             group, mix_q, common_pmf = _arr(group, np.int32), _arr(mix_q, np.int32), _arr(common_pmf, np.float64)
             if group.ndim != 1 or mix_q.shape != group.shape or common_pmf.ndim != 2 or taps_q.shape[0] != len(group) + n_groups:
@@ -689,6 +703,29 @@ class Engine:
         self._check(self.lib.wfs_set_noise_colour(
             self._h, C.c_int32(taps_q.shape[1]), _p(taps_q), C.c_int32(n_groups), _p(group) if n_groups else C.c_void_p(0),
             _p(mix_q) if n_groups else C.c_void_p(0), _p(common_pmf) if n_groups else C.c_void_p(0)))
+        self._noise_rows = (self._noise_rows[0], n_groups) if self._noise_rows else None
+
+    def set_noise_slow(self, shifts, slow_q=None):
+        """The slow levels of the noise model that is set (noise_model.py, wfs_set_noise_slow): shifts int32[n_levels] (knots 2^shift
+        samples apart), slow_q int32[n_channels + n_groups][n_levels] in Q16.  Set the colour first: setting a model or a colour clears
+        the levels.  shifts None clears them.  From the next run."""
+        if shifts is None:
+            self._check(self.lib.wfs_set_noise_slow(self._h, C.c_int32(0), C.c_void_p(0), C.c_void_p(0)))
+            return
+        shifts, slow_q = _arr(shifts, np.int32), _arr(slow_q, np.int32)
+        if shifts.ndim != 1 or slow_q.ndim != 2 or slow_q.shape[1] != len(shifts):
+            raise ValueError('set_noise_slow: shifts must be [n_levels], slow_q [n_channels + n_groups][n_levels]')
+        rows = self._noise_rows
+        if rows is not None and slow_q.shape[0] != rows[0] + rows[1]:
+            raise ValueError(f'set_noise_slow: the model has {rows[0]} channels and {rows[1]} common streams: slow_q must have {rows[0] + rows[1]} rows, '
+                             f'not {slow_q.shape[0]}')
+        self._check(self.lib.wfs_set_noise_slow(self._h, C.c_int32(len(shifts)), _p(shifts), _p(slow_q)))
+
+    def noise_slow_samples(self, row, t0, n):
+        """the slow part S(row, t0 .. t0 + n - 1) in Q16 (int32): row < n_channels a channel, n_channels + g common stream g"""
+        out = np.zeros(int(n), dtype=np.int32)
+        self._check(self.lib.wfs_noise_slow_samples(self._h, C.c_int32(int(row)), C.c_int64(int(t0)), C.c_int64(int(n)), _p(out)))
+        return out
 
     def noise_white_samples(self, row, t0, n):
         """the white sequence w(row, t0 .. t0 + n - 1) under the colour: row < n_channels a channel, n_channels + g common stream g"""
@@ -697,7 +734,8 @@ class Engine:
         return out
 
     def noise_samples(self, channel, t0, n):
-        """noise(channel, t0 .. t0 + n - 1) of the noise model, evaluated on the device: t is the absolute sample index (time / dt)"""
+        """noise(channel, t0 .. t0 + n - 1) of the noise model (colour and slow levels included), evaluated on the device: t is the
+        absolute sample index (time / dt)"""
         out = np.zeros(int(n), dtype=np.int16)
         self._check(self.lib.wfs_noise_model_samples(self._h, C.c_int32(int(channel)), C.c_int64(int(t0)), C.c_int64(int(n)), _p(out)))
         return out

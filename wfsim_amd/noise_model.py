@@ -36,6 +36,19 @@ Tap rows shorter than the longest are zero-padded.  The sum is rounded to the ne
 
 with Var_w, Var_c the variances of the channel's and the group's distributions.  The arithmetic is exact in integers (Q16 taps); a
 model is refused unless ``sum |h_q| * max |value| < 2^29`` for every row of taps.
+
+Slow levels (wfs_set_noise_slow).  The taps reach 16 samples; baseline motion slower than that comes from the key
+
+* ``'slow'``: ``{'shifts': int[n_levels], 'amplitude': [n_levels] | [n_channels][n_levels]}``, 1 <= n_levels <= 8, shifts strictly
+  ascending in 4 .. 30.  Level j is a sequence of knots ``2^shifts[j]`` samples apart, each a draw from the channel's own distribution
+  (its own counter-based word), joined by linear interpolation and scaled by the amplitude; the levels are added to the channel's
+  filtered sequence before the rounding.  ``'period_ns'`` may stand in place of ``'shifts'``: knot periods in ns, each ``dt * 2^s``.
+  Amplitudes are quantised with ``round(a * 65536)``, no hidden normalisation; averaged over the phase a level has the variance
+  ``a^2 Var_w (2/3 + 1/(3 * 4^s))`` (``slow_levels`` picks amplitudes for a stated rms);
+* ``noise_model['common']['slow']``: amplitudes ``[n_levels]`` or ``[n_groups][n_levels]`` of the same levels on the common streams: slow
+  motion that is coherent over a group and adds linearly in a sum of its channels.
+
+With slow levels the bound reads ``(sum |h_q| + sum |a_q|) * max |value| < 2^29`` per row (``sum |h_q| = 65536`` without taps).
 """
 import math
 
@@ -43,6 +56,7 @@ import numpy as np
 
 MAX_VALUES = 4096           # wfs_set_noise_model
 MAX_TAPS = 16               # wfs_set_noise_colour
+MAX_LEVELS, MIN_SHIFT, MAX_SHIFT = 8, 4, 30        # wfs_set_noise_slow
 Q16 = 65536
 SUM_TOLERANCE = 1e-9
 
@@ -252,6 +266,110 @@ def noise_colour(config, n_rows):
     rows[n_ch:, :ctaps.shape[1]] = ctaps
     taps_q, group, mix_q, common_pmf = check_colour(quantise_taps(rows), group, mix_q, common_pmf, n_ch, n_val, vmin)
     return dict(taps_q=taps_q, group=group, mix_q=mix_q, common_pmf=common_pmf)
+
+
+# ---------------------------------------------------------------------------------------------------- slow levels
+def check_slow(shifts, slow_q, taps_q, n_channels, n_groups, n_values, vmin):
+    """validates what wfs_set_noise_slow validates, with the argument named; taps_q: those of the colour, None without one (a unit tap per
+    channel, no groups).  Returns (shifts int32[n_levels], slow_q int32[n_channels + n_groups][n_levels])"""
+    shifts, slow_q = np.asarray(shifts, dtype=np.int64), np.asarray(slow_q, dtype=np.int64)
+    if shifts.ndim != 1 or len(shifts) < 1 or len(shifts) > MAX_LEVELS:
+        raise ValueError(f'noise slow: n_levels {shifts.size if shifts.ndim == 1 else shifts.shape} outside 1 .. {MAX_LEVELS}')
+    bad = np.where((shifts < MIN_SHIFT) | (shifts > MAX_SHIFT))[0]
+    if len(bad):
+        raise ValueError(f'noise slow: shifts[{int(bad[0])}] = {int(shifts[bad[0]])} outside {MIN_SHIFT} .. {MAX_SHIFT}')
+    bad = np.where(np.diff(shifts) <= 0)[0]
+    if len(bad):
+        raise ValueError(f'noise slow: shifts not strictly ascending at level {int(bad[0]) + 1}')
+    n_rows = n_channels + (n_groups if taps_q is not None else 0)
+    if slow_q.shape != (n_rows, len(shifts)):
+        raise ValueError(f'noise slow: slow_q must be [{n_rows}][{len(shifts)}] (channels, then common streams)')
+    tapsum = np.abs(np.asarray(taps_q, dtype=np.int64)).sum(axis=1) if taps_q is not None else np.full(n_rows, Q16, dtype=np.int64)
+    vmax = max(abs(int(vmin)), abs(int(vmin) + int(n_values) - 1))
+    bound = (tapsum + np.abs(slow_q).sum(axis=1)) * vmax
+    bad = np.where(bound >= 2 ** 29)[0]
+    if len(bad):
+        raise ValueError(f'noise slow: slow_q of row {int(bad[0])}: (sum |taps| + sum |slow|) * max |value| = {int(bound[bad[0]])} reaches 2^29')
+    return np.ascontiguousarray(shifts, dtype=np.int32), np.ascontiguousarray(slow_q, dtype=np.int32)
+
+
+def _slow_shifts(slow, dt_ns):
+    if not isinstance(slow, dict) or 'amplitude' not in slow or ('shifts' in slow) == ('period_ns' in slow):
+        raise ValueError("noise_model['slow'] must be a dict with 'amplitude' and either 'shifts' or 'period_ns'")
+    if 'shifts' in slow:
+        sh = np.asarray(slow['shifts'])
+        if sh.ndim != 1 or sh.dtype.kind not in 'iu':
+            raise ValueError("noise_model['slow']['shifts'] must be a 1-D integer array")
+        return sh.astype(np.int64)
+    period = np.atleast_1d(np.asarray(slow['period_ns'], dtype=np.float64))
+    if period.ndim != 1:
+        raise ValueError("noise_model['slow']['period_ns'] must be a number or a 1-D array")
+    sh = np.zeros(len(period), dtype=np.int64)
+    for j, p in enumerate(period):
+        s = int(round(math.log2(p / dt_ns))) if np.isfinite(p) and p > 0 else -1
+        if s < 0 or dt_ns * 2 ** s != p:
+            raise ValueError(f"noise_model['slow']['period_ns'][{j}] = {p:g} ns is not dt * 2^s (dt = {dt_ns:g} ns)")
+        sh[j] = s
+    return sh
+
+
+def _amp_rows(amp, n_rows, n_levels, name):
+    a = np.asarray(amp, dtype=np.float64)
+    if a.ndim == 1:
+        a = np.tile(a, (n_rows, 1))
+    if a.ndim != 2 or a.shape != (n_rows, n_levels):
+        raise ValueError(f'{name} must be a float array [{n_levels}] or [{n_rows}][{n_levels}]')
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f'{name} must be finite')
+    return a
+
+
+def noise_slow(config, n_rows):
+    """dict(shifts int32[n_levels], slow_q int32[n_channels + n_groups][n_levels]) from the 'slow' keys of ``config['noise_model']`` and
+    of its 'common', or None when the model has no slow levels"""
+    m = config.get('noise_model')
+    if not isinstance(m, dict):
+        return None
+    common = m.get('common')
+    if 'slow' not in m:
+        if isinstance(common, dict) and 'slow' in common:
+            raise ValueError("noise_model['common']['slow'] needs noise_model['slow'] (the shifts; its amplitudes may be zero)")
+        return None
+    pmf, vmin = noise_pmf(config, n_rows)
+    n_ch, n_val = pmf.shape
+    colour = noise_colour(config, n_rows)
+    shifts = _slow_shifts(m['slow'], float(config.get('sample_duration', 10)))
+    amp = _amp_rows(m['slow']['amplitude'], n_ch, len(shifts), "noise_model['slow']['amplitude']")
+    n_groups = len(colour['common_pmf']) if colour is not None else 0
+    camp = np.zeros((n_groups, len(shifts)))
+    if isinstance(common, dict) and 'slow' in common:
+        camp = _amp_rows(common['slow'], n_groups, len(shifts), "noise_model['common']['slow']")
+    shifts, slow_q = check_slow(shifts, quantise_taps(np.concatenate([amp, camp])), None if colour is None else colour['taps_q'],
+                                n_ch, n_groups, n_val, vmin)
+    return dict(shifts=shifts, slow_q=slow_q)
+
+
+def slow_level_variance(amplitude, shift, var_w):
+    """the variance of one level averaged over the phase: a knot pair weighted (1 - u, u), u = f / 2^s, has (1 - u)^2 + u^2 of the knot
+    variance, and the mean of that over f = 0 .. 2^s - 1 is 2/3 + 1/(3 * 4^s)"""
+    return amplitude ** 2 * var_w * (2.0 / 3.0 + 1.0 / (3.0 * 4.0 ** shift))
+
+
+def slow_levels(f_lo_hz, f_hi_hz, rms_adc, white_sigma, dt_ns=10):
+    """A ``noise_model['slow']`` of one level per octave between two frequencies: a level whose knots are 2^s samples apart moves no
+    faster than the Nyquist frequency of its knots, 1 / (2 * dt * 2^s), and the levels taken are those with that frequency inside
+    [f_lo_hz, f_hi_hz].  Equal amplitudes, chosen so that the slow part has the stated rms [ADC counts] on a channel whose white
+    distribution is the discretised Gaussian of ``white_sigma`` (variance sigma^2 + 1/12)."""
+    if not (0 < f_lo_hz <= f_hi_hz) or not rms_adc >= 0 or not white_sigma > 0:
+        raise ValueError('slow_levels: needs 0 < f_lo_hz <= f_hi_hz, rms_adc >= 0 and white_sigma > 0')
+    shifts = [s for s in range(MIN_SHIFT, MAX_SHIFT + 1) if f_lo_hz <= 1.0 / (2.0 * dt_ns * 1e-9 * 2 ** s) <= f_hi_hz]
+    if not 1 <= len(shifts) <= MAX_LEVELS:
+        raise ValueError(f'slow_levels: {len(shifts)} octaves between {f_lo_hz:g} and {f_hi_hz:g} Hz, outside 1 .. {MAX_LEVELS} '
+                         f'(knot periods are dt * 2^s, s = {MIN_SHIFT} .. {MAX_SHIFT})')
+    var_w = float(white_sigma) ** 2 + 1.0 / 12.0
+    unit = sum(slow_level_variance(1.0, s, var_w) for s in shifts)
+    a = float(rms_adc) / math.sqrt(unit)
+    return dict(shifts=shifts, amplitude=[a] * len(shifts))
 
 
 def unit_power(taps):
