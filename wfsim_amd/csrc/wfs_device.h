@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "wfs_noise.h"       // NoiseKind, the NC_ / NS_ constants of the coloured model and its slow levels
 
 typedef long long i64;
 typedef unsigned long long u64;
@@ -90,26 +91,17 @@ __device__ __forceinline__ void box_muller(u32x4 w, double &z0, double &z1)
     z0 = r * c; z1 = r * s;
 }
 
-// The Philox call of the noise model that covers samples 4 q .. 4 q + 3 of a channel (q = t >> 2, arithmetic shift)
-__device__ __forceinline__ u32x4 noise_quad(u32 k0, u32 k1, i32 channel, i64 q)
-{
-    return philox4x32_10((u32)(u64)q, (u32)((u64)q >> 32), (u32)channel, SITE_NOISE_SAMPLE, k0, k1);
-}
-// The same for any white stream of the coloured model: (channel, SITE_NOISE_SAMPLE) or (group, SITE_NOISE_COMMON)
+// word k & 3 of a Philox call (k a lane's own: a select, no indexing)
+__device__ __forceinline__ u32 word_of(const u32x4 &W, int k) { return k == 0 ? W.x : (k == 1 ? W.y : (k == 2 ? W.z : W.w)); }
+
+// The Philox call that covers items 4 q .. 4 q + 3 (q = t >> 2, arithmetic shift) of a stream of the noise model: samples of
+// (channel, SITE_NOISE_SAMPLE) or (group, SITE_NOISE_COMMON), knots of a slow level (.., SITE_NOISE_SLOW(_COMMON) + level)
 __device__ __forceinline__ u32x4 noise_quad_of(u32 k0, u32 k1, u32 id, u32 site, i64 q)
 {
     return philox4x32_10((u32)(u64)q, (u32)((u64)q >> 32), id, site, k0, k1);
 }
-
-// The FIR taps of the coloured model on the device: one row of NC_TAP_STRIDE int32 (Q16) per stream, tap k at [NC_TAP_PAD + k], zeros in
-// front and behind -- a lane that holds a quad of whites multiplies all four words by the taps their distance asks for, and the
-// distances that fall outside 0 .. L - 1 (at most NC_TAP_PAD to either side) meet a zero instead of a branch.
-constexpr int NC_MAX_TAPS = 16;
-constexpr int NC_TAP_PAD = 6;
-constexpr int NC_TAP_STRIDE = NC_MAX_TAPS + 2 * NC_TAP_PAD;
-// The slow levels (wfs_set_noise_slow): at most NS_MAX_LEVELS, knots 2^shift samples apart with NS_MIN_SHIFT <= shift <= NS_MAX_SHIFT.
-// A block of 256 samples touches at most 255 / 2^NS_MIN_SHIFT + 3 = 18 knots of a level, which lie in at most NS_QUADS aligned quads.
-constexpr int NS_MAX_LEVELS = 8, NS_MIN_SHIFT = 4, NS_MAX_SHIFT = 30, NS_QUADS = 6;
+// the white samples of a channel
+__device__ __forceinline__ u32x4 noise_quad(u32 k0, u32 k1, i32 channel, i64 q) { return noise_quad_of(k0, k1, (u32)channel, SITE_NOISE_SAMPLE, q); }
 
 // Integer-valued delays.  The reference draws float variates and truncates each to int64 before adding it (pulse.py:54-56
 // transit time, s1.py:193-194, s2.py:338, pulse.py:339-341, s2.py:550); only the SUM reaches the pulse, and the sum of
@@ -123,6 +115,8 @@ struct AliasTab { const uint2 *cell; i32 vmin, shift; };      // shift = 32 - k
 __device__ __forceinline__ u32 alias_cell(const AliasTab &t, u32 w) { return w >> t.shift; }
 __device__ __forceinline__ i32 alias_pick(const AliasTab &t, u32 w, u32 c, uint2 e) { return t.vmin + (i32)(((w << (32 - t.shift)) < e.x) ? c : e.y); }
 __device__ __forceinline__ i32 alias_sample(const AliasTab &t, u32 w) { const u32 c = alias_cell(t, w); return alias_pick(t, w, c, t.cell[c]); }
+// two samples of an int16 range as one word for a cross-lane fetch: that of wa in the low half, that of wb in the high half
+__device__ __forceinline__ u32 alias_pair(const AliasTab &t, u32 wa, u32 wb) { return ((u32)alias_sample(t, wa) & 0xffffu) | ((u32)alias_sample(t, wb) << 16); }
 
 // A channel's SPE row (pulse.py:97: a photon's gain is entry int(u * SPE_BINS) + 1 of it): SPE_BINS quantiles behind an entry 0 that no
 // photon indexes.

@@ -108,15 +108,16 @@ struct wfs_handle {
     // scalar maps (kind 0: weighted nearest neighbours on a regular grid, 1: on a point list, 2: RectBivariateSpline)
     struct ScalarMap { int kind = 0; int nv = 1; PatternMap g; i32 nx = 0, ny = 0, kx = 0, ky = 0; DevBuf tx, ty, c; };      // kind 0 / 1: nearest neighbours on a grid / a point list, 2: spline, 3: multilinear grid
     std::vector<std::unique_ptr<ScalarMap>> smaps;
-    // the noise model (wfs_set_noise_model): alias cells [nm_channels][nm_k] on the device (nm_cells) and on the host; nm_channels 0: no model
-    std::vector<uint2> h_nm_cells; i32 nm_channels = 0, nm_k = 0, nm_shift = 0, nm_vmin = 0, nm_values = 0;
-    // its colour (wfs_set_noise_colour): nc_buf holds taps [nm_channels + nc_groups][NC_TAP_STRIDE] | group [nm_channels] | mix [nm_channels];
-    // the cells of the common streams follow the channels' in nm_cells (h_nm_cells keeps the channels' alone).  nc_n_taps 0: white
-    i32 nc_n_taps = 0, nc_groups = 0; std::vector<i64> h_nc_tapsum;      // (sum |taps_q| per row: the bound of wfs_set_noise_slow)
-    // its slow levels (wfs_set_noise_slow): ns_buf holds shift [NS_MAX_LEVELS] | amplitudes [nm_channels + nc_groups][NS_MAX_LEVELS] | for a
-    // model without a colour, unit taps [nm_channels][NC_TAP_STRIDE] that stand in for nc_buf.  ns_levels 0: none
-    i32 ns_levels = 0;
-    void clear_noise_colour() { nc_n_taps = 0; nc_groups = 0; nc_buf.reset(); h_nc_tapsum.clear(); ns_levels = 0; ns_buf.reset(); }
+    // the noise model, its colour and its slow levels (wfs_noise.h): written by the transitions alone, which name the device buffers
+    // (nm_cells, nc_buf: NoiseColourLayout, ns_buf: NoiseSlowLayout) that go with what they reset
+    NoiseModelState noise;
+    NoiseTransitions noise_state() { return NoiseTransitions{noise}; }
+    void noise_moves(unsigned dropped)
+    {
+        if (dropped & NOISE_BUF_CELLS) nm_cells.reset();
+        if (dropped & NOISE_BUF_COLOUR) nc_buf.reset();
+        if (dropped & NOISE_BUF_SLOW) ns_buf.reset();
+    }
     i32 table_channels = 0;           // columns of the noise table (dev.noise_channels counts the model's channels while a model is set)
 
     // packed records: two arenas used in turn, so that the device -> host copy of one batch (copy stream, pinned host memory)
@@ -326,15 +327,37 @@ int read_scal(wfs_handle *h)
     return WFS_OK;
 }
 
-// The row kernels take the kind of noise as a template parameter (no branch between their loads): 0 none, 1 int16 table, 2 float
-// table, 3 the noise model, 4 the noise model with a colour, 5 the same with slow levels.
-// f is called with a std::integral_constant of the kind.
-template <class F> void with_noise_kind(int kind, F &&f)
+// The row kernels take the kind of noise as a template parameter (no branch between their loads): NoiseKind of wfs_noise.h, 0 none,
+// 1 int16 table, 2 float table, 3 the noise model, 4 the noise model with a colour, 5 the same with slow levels.
+// The kind that the device view holds, whether or not the configuration enables noise (wfs_run asks d.enable_noise first):
+static NoiseKind noise_kind_of(const WfsDev &d)
 {
-    if (kind == 0) f(std::integral_constant<int, 0>{}); else if (kind == 1) f(std::integral_constant<int, 1>{}); else if (kind == 2) f(std::integral_constant<int, 2>{});
-    else if (kind == 3) f(std::integral_constant<int, 3>{});
-    else if (kind == 4) f(std::integral_constant<int, 4>{});
-    else f(std::integral_constant<int, 5>{});
+    if (d.nm_cells) return d.ns_shift ? NOISE_SLOW : (d.nc_taps ? NOISE_COLOUR : NOISE_MODEL);
+    return d.noise_f ? NOISE_TABLE_F64 : (d.noise ? NOISE_TABLE_I16 : NOISE_NONE);
+}
+// f is called with a std::integral_constant of the kind.
+template <class F, int... K> void with_noise_kind(int kind, F &&f, std::integer_sequence<int, K...>)
+{
+    (void)((kind == K && (f(std::integral_constant<int, K>{}), true)) || ...);
+}
+template <class F> void with_noise_kind(int kind, F &&f) { with_noise_kind(kind, f, std::make_integer_sequence<int, NOISE_KINDS>{}); }
+
+// What the probe entry points of the noise model share once they know their stream: the checks of (t0, n, out), a scratch buffer of n
+// elements, the launch into it (launch(T *device_buffer): timer and kernel) and the copy back.  fn: the entry point, for the messages.
+template <class T, class Launch> int noise_probe(wfs_handle *h, const char *fn, int64_t t0, int64_t n, T *out, Launch &&launch)
+{
+    if (n < 0 || n > ((i64)1 << 30) || (n > 0 && !out)) return h->fail(WFS_E_INVALID, std::string(fn) + ": n outside 0 .. 2^30 or null buffer");
+    if (t0 > I64_MAX - n) return h->fail(WFS_E_INVALID, std::string(fn) + ": t0 + n overflows");
+    if (n == 0) return WFS_OK;
+    HIPCHK(hipSetDevice(h->device));
+    DevBuf buf;
+    TRY(ensure(h, buf, (size_t)n * sizeof(T)));
+    launch(buf.as<T>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, buf.p, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    CHECK_LAUNCHES();
+    return WFS_OK;
 }
 
 // a code that kernels raised in the device scalar block (WfsDevError) -> error code and message of the C ABI
@@ -369,7 +392,8 @@ static void normal_trunc_table(double mu, double sigma, std::vector<double> &cum
 // q[i] = p[i] * K; "small" (q < 1) and "large" cells on two stacks filled in ascending index order; pop a small s, pair it
 // with the large l on top: cell s = {thr = floor(q[s] * 2^32), alias = l}, q[l] = (q[l] + q[s]) - 1, l moves to the small
 // stack when it drops below 1; what is left over keeps its own outcome.  Sampling: wfs_device.h alias_sample.
-static void build_alias(const std::vector<double> &cum, std::vector<uint2> &cell, int &shift)
+// (Cell: uint2, or the NoiseCell of wfs_noise.h, which has the same two words)
+template <class Cell> static void build_alias(const std::vector<double> &cum, std::vector<Cell> &cell, int &shift)
 {
     const size_t n = cum.size();
     size_t K = 2; int lg = 1;
@@ -379,7 +403,7 @@ static void build_alias(const std::vector<double> &cum, std::vector<uint2> &cell
     for (size_t i = 0; i < n; i++) q[i] = (cum[i] - (i ? cum[i - 1] : 0.0)) * (double)K;
     std::vector<u32> small, large; small.reserve(K); large.reserve(K);
     for (size_t i = 0; i < K; i++) (q[i] < 1.0 ? small : large).push_back((u32)i);
-    cell.assign(K, uint2{0xffffffffu, 0u});
+    cell.assign(K, Cell{0xffffffffu, 0u});
     for (size_t i = 0; i < K; i++) cell[i].y = (u32)i;                       // default: own outcome with certainty
     while (!small.empty() && !large.empty()) {
         const u32 sidx = small.back(); small.pop_back();
@@ -510,18 +534,19 @@ void refresh_dev(wfs_handle *h)
     // HE rows are only materialised when they can differ from a flat baseline: a non-zero int(factor)
     // (rawdata.py:242) or noise columns for the HE channels
     // a noise model takes precedence over the table, which stays where it is for wfs_set_noise_model(h, 0, ...)
-    const bool model = h->nm_channels > 0;
-    d.nm_cells = model ? h->nm_cells.as<uint2>() : nullptr; d.nm_cells_per_ch = h->nm_k; d.nm_shift = h->nm_shift; d.nm_vmin = h->nm_vmin;
-    d.noise_channels = model ? h->nm_channels : h->table_channels;
-    // the colour of the model (wfs_set_noise_colour): taps of every stream, then group and gain of every channel, in one buffer
-    const bool colour = model && h->nc_n_taps > 0;
-    d.nc_taps = colour ? h->nc_buf.as<i32>() : nullptr; d.nc_n_taps = colour ? h->nc_n_taps : 0; d.nc_groups = colour ? h->nc_groups : 0;
-    d.nc_group = (colour && h->nc_groups > 0) ? d.nc_taps + (size_t)(h->nm_channels + h->nc_groups) * NC_TAP_STRIDE : nullptr;
-    d.nc_mix = d.nc_group ? d.nc_group + h->nm_channels : nullptr;
-    // its slow levels (wfs_set_noise_slow); without a colour the unit taps behind the amplitudes are the taps
-    const bool slow = model && h->ns_levels > 0;
-    d.ns_shift = slow ? h->ns_buf.as<i32>() : nullptr; d.ns_amp = slow ? d.ns_shift + NS_MAX_LEVELS : nullptr; d.ns_levels = slow ? h->ns_levels : 0;
-    if (slow && !colour) { d.nc_taps = d.ns_amp + (size_t)h->nm_channels * NS_MAX_LEVELS; d.nc_n_taps = 1; }
+    {   // the device view of the model: the state and the layouts of its two buffers (wfs_noise.h)
+        const NoiseModelState &m = h->noise;
+        const bool model = m.set(), colour = m.coloured(), slow = m.levels() > 0, grouped = colour && m.colour.groups > 0;
+        const NoiseColourLayout cl(m.channels, m.colour.groups); const NoiseSlowLayout sl(m.channels, m.colour.groups, colour);
+        const i32 *nc = h->nc_buf.as<i32>(), *ns = h->ns_buf.as<i32>();
+        d.nm_cells = model ? h->nm_cells.as<uint2>() : nullptr; d.nm_cells_per_ch = m.k; d.nm_shift = m.shift; d.nm_vmin = m.vmin;
+        d.noise_channels = model ? m.channels : h->table_channels;
+        // slow levels without a colour: the unit taps of the slow buffer are the taps
+        d.nc_taps = colour ? nc + cl.taps : (slow ? ns + sl.unit_taps : nullptr); d.nc_n_taps = colour ? m.colour.n_taps : (slow ? 1 : 0);
+        d.nc_groups = colour ? m.colour.groups : 0; d.nc_group = grouped ? nc + cl.group : nullptr; d.nc_mix = grouped ? nc + cl.mix : nullptr;
+        d.ns_shift = slow ? ns + sl.shifts : nullptr; d.ns_amp = slow ? ns + sl.amps : nullptr; d.ns_levels = m.levels();
+    }
+    const bool model = h->noise.set();
     d.enable_noise = (c.enable_noise && (model || d.noise != nullptr)) ? 1 : 0;
     bool he_noise = d.enable_noise && d.noise_channels > c.he_first;
     d.he_rows = (c.detector_nt && c.n_top > 0 && (c.he_factor != 0 || he_noise)) ? 1 : 0;
@@ -628,14 +653,9 @@ try {
     hipFuncSetAttribute((const void *)k_photon_fill<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
     hipFuncSetAttribute((const void *)k_tile_order_big, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
     WFS_BIG_LDS_F(K_PULSE_GENERIC, 128);
-#define K_ROW_PULSE_0(F) k_row_pulse<0, F, true>
-#define K_ROW_PULSE_1(F) k_row_pulse<1, F, true>
-#define K_ROW_PULSE_2(F) k_row_pulse<2, F, true>
-#define K_ROW_PULSE_3(F) k_row_pulse<3, F, true>
-#define K_ROW_PULSE_4(F) k_row_pulse<4, F, true>
-#define K_ROW_PULSE_5(F) k_row_pulse<5, F, true>
-    WFS_BIG_LDS_F(K_ROW_PULSE_0, 128); WFS_BIG_LDS_F(K_ROW_PULSE_1, 128); WFS_BIG_LDS_F(K_ROW_PULSE_2, 128); WFS_BIG_LDS_F(K_ROW_PULSE_3, 128);
-    WFS_BIG_LDS_F(K_ROW_PULSE_4, 128); WFS_BIG_LDS_F(K_ROW_PULSE_5, 128);
+#define K_ROW_PULSE_SEG(F) k_row_pulse<NK, F, true>
+    for (int kind = 0; kind < NOISE_KINDS; kind++)           // every kind that with_noise_kind can launch
+        with_noise_kind(kind, [](auto nk) { constexpr int NK = decltype(nk)::value; WFS_BIG_LDS_F(K_ROW_PULSE_SEG, 128); });
     if (const char *e = getenv("WFS_ROW_RESIDENT")) h->res_env = atoi(e);          // 0 / 1 / 2 as the config switch (A/B runs)
     if (const char *e = getenv("WFS_RES_MAX_LEN")) h->res_max_len = std::max(256, std::min(atoi(e), 7168)) / 256 * 256;      // tuning knob (results do not depend on it)
     WFS_BIG_LDS_F(K_S2_TILE, 100); WFS_BIG_LDS_F(K_S2_TILE_AP, 100);
@@ -2171,7 +2191,7 @@ static int run_rows(wfs_handle *h, RunState &r)
     }
     TRY(fg.flush());
     if (h->run.n_active_rows > 0) { Timer t(h, "k_row_desc"); hipLaunchKernelGGL(k_row_desc, dim3(nblocks(h->run.n_active_rows, 256)), dim3(256), 0, h->stream, d, za); }
-    r.noise_kind = !d.enable_noise ? 0 : (d.nm_cells ? (d.ns_shift ? 5 : (d.nc_taps ? 4 : 3)) : (d.noise_f ? 2 : 1));
+    r.noise_kind = d.enable_noise ? noise_kind_of(d) : NOISE_NONE;
     if (h->run.n_res_rows > 0) {        // resident rows: pulses, finished samples and intervals by one wave per row
         PulseArgs pr = pa;
         pr.desc = h->res_desc.as<TileDesc>(); pr.currents = nullptr; pr.cur_off = nullptr;
@@ -2730,38 +2750,37 @@ try {
 
 // The noise model: one Walker table per channel from its probability mass function, all of one size (build_alias, the construction of
 // the delay tables), sampled by the row kernels from the Philox word of the sample (wfs_device.h SITE_NOISE_SAMPLE).
+// The three setters check and pack through wfs_noise.h, upload, and then move the state through its transitions.
+static_assert(sizeof(NoiseCell) == sizeof(uint2) && sizeof(NoiseCell) == 2 * sizeof(u32) && offsetof(NoiseCell, y) == sizeof(u32) && alignof(NoiseCell) <= alignof(uint2),
+              "the host's cells are uploaded as the uint2 {x, y} the kernels read");
+// the alias cells of n_rows cumulative rows of n_values, appended to cells
+static void append_alias_rows(const std::vector<double> &cum, i32 n_rows, i32 n_values, std::vector<NoiseCell> &cells, int &shift)
+{
+    std::vector<NoiseCell> cell;
+    for (i32 r = 0; r < n_rows; r++) {
+        build_alias(std::vector<double>(cum.begin() + (size_t)r * n_values, cum.begin() + (size_t)(r + 1) * n_values), cell, shift);
+        cells.insert(cells.end(), cell.begin(), cell.end());
+    }
+}
+
 int wfs_set_noise_model(wfs_handle *h, int32_t n_channels, int32_t n_values, int32_t vmin, const double *pmf)
 try {
     if (!h) return WFS_E_INVALID;
     HIPCHK(hipSetDevice(h->device));
     if (n_channels == 0) {
         HIPCHK(hipStreamSynchronize(h->stream));
-        h->nm_channels = 0; h->h_nm_cells.clear(); h->nm_cells.reset();
-        h->clear_noise_colour();
+        h->noise_moves(h->noise_state().model_cleared());
         refresh_dev(h);
         return WFS_OK;
     }
-    if (n_channels < 0 || n_channels > h->cfg.n_rows) return h->fail(WFS_E_INVALID, "wfs_set_noise_model: n_channels outside 0 .. n_rows of the digitiser array");
-    if (n_values < 1 || n_values > 4096) return h->fail(WFS_E_INVALID, "wfs_set_noise_model: n_values outside 1 .. 4096");
-    if (vmin < -32768 || (i64)vmin + n_values - 1 > 32767) return h->fail(WFS_E_INVALID, "wfs_set_noise_model: vmin .. vmin + n_values - 1 leaves the int16 range");
-    if (!pmf) return h->fail(WFS_E_INVALID, "wfs_set_noise_model: null pmf");
-    std::vector<uint2> cells, cell; std::vector<double> cum((size_t)n_values); int shift = 31;
-    for (i32 c = 0; c < n_channels; c++) {
-        const double *row = pmf + (size_t)c * n_values;
-        double acc = 0;
-        for (i32 v = 0; v < n_values; v++) {
-            if (!(row[v] >= 0.0)) return h->fail(WFS_E_INVALID, "wfs_set_noise_model: pmf has a negative (or NaN) entry in channel " + std::to_string(c));
-            acc += row[v]; cum[(size_t)v] = acc;
-        }
-        if (!(fabs(acc - 1.0) <= 1e-9)) return h->fail(WFS_E_INVALID, "wfs_set_noise_model: pmf of channel " + std::to_string(c) + " does not sum to 1");
-        build_alias(cum, cell, shift);
-        cells.insert(cells.end(), cell.begin(), cell.end());
-    }
+    std::vector<double> cum; std::string err;
+    if (!noise_model_check(n_channels, h->cfg.n_rows, n_values, vmin, pmf, cum, err)) return h->fail(WFS_E_INVALID, err);
+    std::vector<NoiseCell> cells; int shift = 31;
+    append_alias_rows(cum, n_channels, n_values, cells, shift);
     const i32 K = (i32)(cells.size() / (size_t)n_channels);
-    TRY(upload(h, h->nm_cells, cells.data(), cells.size() * sizeof(uint2)));
+    TRY(upload(h, h->nm_cells, cells.data(), cells.size() * sizeof(NoiseCell)));
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->h_nm_cells.swap(cells); h->nm_channels = n_channels; h->nm_k = K; h->nm_shift = shift; h->nm_vmin = vmin; h->nm_values = n_values;
-    h->clear_noise_colour();            // a colour and slow levels belong to the shapes of the model they were set on
+    h->noise_moves(h->noise_state().model_set(n_channels, K, shift, vmin, n_values, std::move(cells)));
     refresh_dev(h);             // (HE rows may appear or go with the model's channel count: run again before copying rows)
     return WFS_OK;
 } WFS_CATCH(h)
@@ -2769,114 +2788,65 @@ try {
 int wfs_noise_model_samples(wfs_handle *h, int32_t channel, int64_t t0, int64_t n, int16_t *out)
 try {
     if (!h) return WFS_E_INVALID;
-    if (h->nm_channels <= 0) return h->fail(WFS_E_STATE, "wfs_noise_model_samples: no noise model is set");
-    if (channel < 0 || channel >= h->nm_channels) return h->fail(WFS_E_INVALID, "wfs_noise_model_samples: channel outside the model");
-    if (n < 0 || n > ((i64)1 << 30) || (n > 0 && !out)) return h->fail(WFS_E_INVALID, "wfs_noise_model_samples: n outside 0 .. 2^30 or null buffer");
-    if (t0 > I64_MAX - n) return h->fail(WFS_E_INVALID, "wfs_noise_model_samples: t0 + n overflows");
-    if (n == 0) return WFS_OK;
-    HIPCHK(hipSetDevice(h->device));
-    DevBuf buf;
-    TRY(ensure(h, buf, (size_t)n * sizeof(int16_t)));
-    if (h->dev.ns_shift) { Timer t(h, "k_noise_colour_samples"); hipLaunchKernelGGL(k_noise_colour_samples<true>, dim3(nblocks((n + 255) / 256, 4)), dim3(256), 0, h->stream, h->dev, channel, t0, n, buf.as<int16_t>()); }
-    else if (h->dev.nc_taps) { Timer t(h, "k_noise_colour_samples"); hipLaunchKernelGGL(k_noise_colour_samples<false>, dim3(nblocks((n + 255) / 256, 4)), dim3(256), 0, h->stream, h->dev, channel, t0, n, buf.as<int16_t>()); }
-    else { Timer t(h, "k_noise_model_samples"); hipLaunchKernelGGL(k_noise_model_samples, dim3(nblocks((n + 3) / 4, 256)), dim3(256), 0, h->stream, h->dev, channel, t0, n, buf.as<int16_t>()); }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, buf.p, (size_t)n * sizeof(int16_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    CHECK_LAUNCHES();
-    return WFS_OK;
+    if (!h->noise.set()) return h->fail(WFS_E_STATE, "wfs_noise_model_samples: no noise model is set");
+    if (channel < 0 || channel >= h->noise.channels) return h->fail(WFS_E_INVALID, "wfs_noise_model_samples: channel outside the model");
+    return noise_probe(h, __func__, t0, n, out, [&](int16_t *buf) {
+        const NoiseKind kind = noise_kind_of(h->dev);
+        const dim3 waves(nblocks((n + 255) / 256, 4));          // (the coloured forms: a wave takes 256 samples)
+        if (kind == NOISE_SLOW) { Timer t(h, "k_noise_colour_samples"); hipLaunchKernelGGL(k_noise_colour_samples<true>, waves, dim3(256), 0, h->stream, h->dev, channel, t0, n, buf); }
+        else if (kind == NOISE_COLOUR) { Timer t(h, "k_noise_colour_samples"); hipLaunchKernelGGL(k_noise_colour_samples<false>, waves, dim3(256), 0, h->stream, h->dev, channel, t0, n, buf); }
+        else { Timer t(h, "k_noise_model_samples"); hipLaunchKernelGGL(k_noise_model_samples, dim3(nblocks((n + 3) / 4, 256)), dim3(256), 0, h->stream, h->dev, channel, t0, n, buf); }
+    });
 } WFS_CATCH(h)
 
 // The colour of the noise model: FIR taps per stream and common streams shared by groups of channels.  Everything the
-// kernels rely on is checked here: the tap count, the bound that keeps the int32 sums of the kernels exact, groups and gains.
+// kernels rely on is checked in noise_colour_pack: the tap count, the bound that keeps the int32 sums of the kernels exact, groups and gains.
 int wfs_set_noise_colour(wfs_handle *h, int32_t n_taps, const int32_t *taps_q, int32_t n_groups, const int32_t *group, const int32_t *mix_q, const double *common_pmf)
 try {
     if (!h) return WFS_E_INVALID;
-    if (h->nm_channels <= 0) return h->fail(WFS_E_STATE, "wfs_set_noise_colour: no noise model is set");
+    const NoiseModelState &m = h->noise;
+    if (!m.set()) return h->fail(WFS_E_STATE, "wfs_set_noise_colour: no noise model is set");
     HIPCHK(hipSetDevice(h->device));
-    const i32 C = h->nm_channels, V = h->nm_values;
     if (n_taps == 0) {
         HIPCHK(hipStreamSynchronize(h->stream));
-        if (h->nc_groups > 0) { TRY(upload(h, h->nm_cells, h->h_nm_cells.data(), h->h_nm_cells.size() * sizeof(uint2))); HIPCHK(hipStreamSynchronize(h->stream)); }
-        h->clear_noise_colour();
+        // (the cells of the common streams leave the device with them)
+        if (m.colour.groups > 0) { TRY(upload(h, h->nm_cells, m.cells.data(), m.cells.size() * sizeof(NoiseCell))); HIPCHK(hipStreamSynchronize(h->stream)); }
+        h->noise_moves(h->noise_state().colour_cleared());
         refresh_dev(h);
         return WFS_OK;
     }
-    if (n_taps < 1 || n_taps > NC_MAX_TAPS) return h->fail(WFS_E_INVALID, "wfs_set_noise_colour: n_taps outside 1 .. 16");
-    if (n_groups < 0 || n_groups > 1024) return h->fail(WFS_E_INVALID, "wfs_set_noise_colour: n_groups outside 0 .. 1024");
-    if (!taps_q) return h->fail(WFS_E_INVALID, "wfs_set_noise_colour: null taps_q");
-    if (n_groups > 0 && (!group || !mix_q || !common_pmf)) return h->fail(WFS_E_INVALID, "wfs_set_noise_colour: null group, mix_q or common_pmf with n_groups > 0");
-    const i32 R = C + n_groups;
-    const i64 vmax = std::max<i64>(std::llabs((long long)h->nm_vmin), std::llabs((long long)h->nm_vmin + V - 1));
-    std::vector<i32> buf((size_t)R * NC_TAP_STRIDE + 2 * (size_t)C, 0); std::vector<i64> tapsum((size_t)R);
-    for (i32 r = 0; r < R; r++) {
-        i64 sum = 0;
-        for (i32 k = 0; k < n_taps; k++) { const i32 v = taps_q[(size_t)r * n_taps + k]; sum += std::llabs((long long)v); buf[(size_t)r * NC_TAP_STRIDE + NC_TAP_PAD + k] = v; }
-        tapsum[(size_t)r] = sum;
-        if (sum * vmax >= ((i64)1 << 29)) return h->fail(WFS_E_INVALID, "wfs_set_noise_colour: taps_q of row " + std::to_string(r) + ": sum |taps| * max |value| reaches 2^29");
-    }
-    i32 *grp = buf.data() + (size_t)R * NC_TAP_STRIDE, *mix = grp + C;
-    for (i32 c = 0; c < C; c++) {
-        grp[c] = n_groups > 0 ? group[c] : -1; mix[c] = n_groups > 0 ? mix_q[c] : 0;
-        if (grp[c] < -1 || grp[c] >= n_groups) return h->fail(WFS_E_INVALID, "wfs_set_noise_colour: group of channel " + std::to_string(c) + " outside -1 .. n_groups - 1");
-        if (mix[c] < -65536 || mix[c] > 65536) return h->fail(WFS_E_INVALID, "wfs_set_noise_colour: mix_q of channel " + std::to_string(c) + " beyond 65536 in magnitude");
-    }
-    std::vector<uint2> cells(h->h_nm_cells), cell; std::vector<double> cum((size_t)V); int shift = 31;
-    for (i32 g = 0; g < n_groups; g++) {
-        const double *row = common_pmf + (size_t)g * V;
-        double acc = 0;
-        for (i32 v = 0; v < V; v++) {
-            if (!(row[v] >= 0.0)) return h->fail(WFS_E_INVALID, "wfs_set_noise_colour: common_pmf has a negative (or NaN) entry in group " + std::to_string(g));
-            acc += row[v]; cum[(size_t)v] = acc;
-        }
-        if (!(fabs(acc - 1.0) <= 1e-9)) return h->fail(WFS_E_INVALID, "wfs_set_noise_colour: common_pmf of group " + std::to_string(g) + " does not sum to 1");
-        build_alias(cum, cell, shift);
-        cells.insert(cells.end(), cell.begin(), cell.end());
-    }
+    std::vector<i32> buf; std::vector<i64> tapsum; std::vector<double> cum; std::string err;
+    if (!noise_colour_pack(m, n_taps, taps_q, n_groups, group, mix_q, common_pmf, buf, tapsum, cum, err)) return h->fail(WFS_E_INVALID, err);
+    std::vector<NoiseCell> cells(m.cells); int shift = 31;
+    append_alias_rows(cum, n_groups, m.values, cells, shift);
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (n_groups > 0 || h->nc_groups > 0) TRY(upload(h, h->nm_cells, cells.data(), cells.size() * sizeof(uint2)));
+    if (n_groups > 0 || m.colour.groups > 0) TRY(upload(h, h->nm_cells, cells.data(), cells.size() * sizeof(NoiseCell)));
     TRY(upload(h, h->nc_buf, buf.data(), buf.size() * sizeof(i32)));
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->nc_n_taps = n_taps; h->nc_groups = n_groups; h->h_nc_tapsum.swap(tapsum);
-    h->ns_levels = 0; h->ns_buf.reset();            // the slow levels belong to the rows of the colour they were set on
+    h->noise_moves(h->noise_state().colour_set(n_taps, n_groups, std::move(tapsum)));
     refresh_dev(h);
     return WFS_OK;
 } WFS_CATCH(h)
 
 // The slow levels of the noise model: interpolated knot sequences per stream, octaves apart.  The bound of the colour with
-// the slow amplitudes added keeps every int32 sum of the kernels exact.
+// the slow amplitudes added (noise_slow_pack) keeps every int32 sum of the kernels exact.
 int wfs_set_noise_slow(wfs_handle *h, int32_t n_levels, const int32_t *shifts, const int32_t *slow_q)
 try {
     if (!h) return WFS_E_INVALID;
-    if (h->nm_channels <= 0) return h->fail(WFS_E_STATE, "wfs_set_noise_slow: no noise model is set");
+    if (!h->noise.set()) return h->fail(WFS_E_STATE, "wfs_set_noise_slow: no noise model is set");
     HIPCHK(hipSetDevice(h->device));
     if (n_levels == 0) {
         HIPCHK(hipStreamSynchronize(h->stream));
-        h->ns_levels = 0; h->ns_buf.reset();
+        h->noise_moves(h->noise_state().slow_cleared());
         refresh_dev(h);
         return WFS_OK;
     }
-    if (n_levels < 0 || n_levels > NS_MAX_LEVELS) return h->fail(WFS_E_INVALID, "wfs_set_noise_slow: n_levels outside 0 .. 8");
-    if (!shifts || !slow_q) return h->fail(WFS_E_INVALID, "wfs_set_noise_slow: null shifts or slow_q");
-    for (i32 j = 0; j < n_levels; j++) {
-        if (shifts[j] < NS_MIN_SHIFT || shifts[j] > NS_MAX_SHIFT) return h->fail(WFS_E_INVALID, "wfs_set_noise_slow: shifts[" + std::to_string(j) + "] outside 4 .. 30");
-        if (j > 0 && shifts[j] <= shifts[j - 1]) return h->fail(WFS_E_INVALID, "wfs_set_noise_slow: shifts not strictly ascending at level " + std::to_string(j));
-    }
-    const bool colour = h->nc_n_taps > 0;
-    const i32 C = h->nm_channels, R = C + (colour ? h->nc_groups : 0);
-    const i64 vmax = std::max<i64>(std::llabs((long long)h->nm_vmin), std::llabs((long long)h->nm_vmin + h->nm_values - 1));
-    std::vector<i32> buf((size_t)NS_MAX_LEVELS * (1 + (size_t)R) + (colour ? 0 : (size_t)C * NC_TAP_STRIDE), 0);
-    for (i32 j = 0; j < NS_MAX_LEVELS; j++) buf[(size_t)j] = shifts[j < n_levels ? j : n_levels - 1];
-    for (i32 r = 0; r < R; r++) {
-        i64 sum = colour ? h->h_nc_tapsum[(size_t)r] : 65536;     // (without a colour F = 65536 w)
-        for (i32 j = 0; j < n_levels; j++) { const i32 v = slow_q[(size_t)r * n_levels + j]; sum += std::llabs((long long)v); buf[(size_t)NS_MAX_LEVELS * (1 + (size_t)r) + j] = v; }
-        if (sum * vmax >= ((i64)1 << 29)) return h->fail(WFS_E_INVALID, "wfs_set_noise_slow: slow_q of row " + std::to_string(r) + ": (sum |taps| + sum |slow|) * max |value| reaches 2^29");
-    }
-    if (!colour) for (i32 c = 0; c < C; c++) buf[(size_t)NS_MAX_LEVELS * (1 + (size_t)R) + (size_t)c * NC_TAP_STRIDE + NC_TAP_PAD] = 65536;
+    std::vector<i32> buf; std::string err;
+    if (!noise_slow_pack(h->noise, n_levels, shifts, slow_q, buf, err)) return h->fail(WFS_E_INVALID, err);
     HIPCHK(hipStreamSynchronize(h->stream));
     TRY(upload(h, h->ns_buf, buf.data(), buf.size() * sizeof(i32)));
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->ns_levels = n_levels;
+    h->noise_moves(h->noise_state().slow_set(n_levels));
     refresh_dev(h);
     return WFS_OK;
 } WFS_CATCH(h)
@@ -2884,53 +2854,36 @@ try {
 int wfs_noise_slow_samples(wfs_handle *h, int32_t row, int64_t t0, int64_t n, int32_t *out)
 try {
     if (!h) return WFS_E_INVALID;
-    if (h->nm_channels <= 0 || h->ns_levels <= 0) return h->fail(WFS_E_STATE, "wfs_noise_slow_samples: no noise model with slow levels is set");
-    if (row < 0 || row >= h->nm_channels + h->nc_groups) return h->fail(WFS_E_INVALID, "wfs_noise_slow_samples: row outside the model's channels and common streams");
-    if (n < 0 || n > ((i64)1 << 30) || (n > 0 && !out)) return h->fail(WFS_E_INVALID, "wfs_noise_slow_samples: n outside 0 .. 2^30 or null buffer");
-    if (t0 > I64_MAX - n) return h->fail(WFS_E_INVALID, "wfs_noise_slow_samples: t0 + n overflows");
-    if (n == 0) return WFS_OK;
-    HIPCHK(hipSetDevice(h->device));
-    DevBuf buf;
-    TRY(ensure(h, buf, (size_t)n * sizeof(i32)));
-    { Timer t(h, "k_noise_slow_samples"); hipLaunchKernelGGL(k_noise_slow_samples, dim3(nblocks((n + 255) / 256, 4)), dim3(256), 0, h->stream, h->dev, row, t0, n, buf.as<i32>()); }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, buf.p, (size_t)n * sizeof(i32), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    CHECK_LAUNCHES();
-    return WFS_OK;
+    if (h->noise.levels() <= 0) return h->fail(WFS_E_STATE, "wfs_noise_slow_samples: no noise model with slow levels is set");
+    if (row < 0 || row >= h->noise.rows()) return h->fail(WFS_E_INVALID, "wfs_noise_slow_samples: row outside the model's channels and common streams");
+    return noise_probe(h, __func__, t0, n, out, [&](int32_t *buf) {
+        Timer t(h, "k_noise_slow_samples"); hipLaunchKernelGGL(k_noise_slow_samples, dim3(nblocks((n + 255) / 256, 4)), dim3(256), 0, h->stream, h->dev, row, t0, n, buf);
+    });
 } WFS_CATCH(h)
 
 int wfs_noise_white_samples(wfs_handle *h, int32_t row, int64_t t0, int64_t n, int16_t *out)
 try {
     if (!h) return WFS_E_INVALID;
-    if (h->nm_channels <= 0) return h->fail(WFS_E_STATE, "wfs_noise_white_samples: no noise model is set");
-    if (row < 0 || row >= h->nm_channels + h->nc_groups) return h->fail(WFS_E_INVALID, "wfs_noise_white_samples: row outside the model's channels and common streams");
-    if (n < 0 || n > ((i64)1 << 30) || (n > 0 && !out)) return h->fail(WFS_E_INVALID, "wfs_noise_white_samples: n outside 0 .. 2^30 or null buffer");
-    if (t0 > I64_MAX - n) return h->fail(WFS_E_INVALID, "wfs_noise_white_samples: t0 + n overflows");
-    if (n == 0) return WFS_OK;
-    HIPCHK(hipSetDevice(h->device));
-    DevBuf buf;
-    TRY(ensure(h, buf, (size_t)n * sizeof(int16_t)));
-    { Timer t(h, "k_noise_white_samples"); hipLaunchKernelGGL(k_noise_white_samples, dim3(nblocks(n, 256)), dim3(256), 0, h->stream, h->dev, row, t0, n, buf.as<int16_t>()); }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, buf.p, (size_t)n * sizeof(int16_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    CHECK_LAUNCHES();
-    return WFS_OK;
+    if (!h->noise.set()) return h->fail(WFS_E_STATE, "wfs_noise_white_samples: no noise model is set");
+    if (row < 0 || row >= h->noise.rows()) return h->fail(WFS_E_INVALID, "wfs_noise_white_samples: row outside the model's channels and common streams");
+    return noise_probe(h, __func__, t0, n, out, [&](int16_t *buf) {
+        Timer t(h, "k_noise_white_samples"); hipLaunchKernelGGL(k_noise_white_samples, dim3(nblocks(n, 256)), dim3(256), 0, h->stream, h->dev, row, t0, n, buf);
+    });
 } WFS_CATCH(h)
 
 int wfs_copy_noise_model(wfs_handle *h, int32_t channel, uint32_t *thr, uint32_t *alias, int32_t capacity_cells, int32_t *n_cells, int32_t *shift, int32_t *vmin)
 try {
     if (!h) return WFS_E_INVALID;
-    if (h->nm_channels <= 0) return h->fail(WFS_E_STATE, "wfs_copy_noise_model: no noise model is set");
-    if (channel < 0 || channel >= h->nm_channels) return h->fail(WFS_E_INVALID, "wfs_copy_noise_model: channel outside the model");
+    const NoiseModelState &m = h->noise;
+    if (!m.set()) return h->fail(WFS_E_STATE, "wfs_copy_noise_model: no noise model is set");
+    if (channel < 0 || channel >= m.channels) return h->fail(WFS_E_INVALID, "wfs_copy_noise_model: channel outside the model");
     if (!thr || !alias || !n_cells || !shift || !vmin) return h->fail(WFS_E_INVALID, "wfs_copy_noise_model: null argument");
-    if (capacity_cells < h->nm_k) return h->fail(WFS_E_CAPACITY, "wfs_copy_noise_model: cell buffers too small");
+    if (capacity_cells < m.k) return h->fail(WFS_E_CAPACITY, "wfs_copy_noise_model: cell buffers too small");
     HIPCHK(hipSetDevice(h->device));
-    std::vector<uint2> cell((size_t)h->nm_k);            // what the device samples from, not the host copy
-    HIPCHK(hipMemcpy(cell.data(), h->nm_cells.as<uint2>() + (size_t)channel * h->nm_k, cell.size() * sizeof(uint2), hipMemcpyDeviceToHost));
-    for (i32 k = 0; k < h->nm_k; k++) { thr[k] = cell[(size_t)k].x; alias[k] = cell[(size_t)k].y; }
-    *n_cells = h->nm_k; *shift = h->nm_shift; *vmin = h->nm_vmin;
+    std::vector<NoiseCell> cell((size_t)m.k);            // what the device samples from, not the host copy
+    HIPCHK(hipMemcpy(cell.data(), h->nm_cells.as<NoiseCell>() + (size_t)channel * m.k, cell.size() * sizeof(NoiseCell), hipMemcpyDeviceToHost));
+    for (i32 k = 0; k < m.k; k++) { thr[k] = cell[(size_t)k].x; alias[k] = cell[(size_t)k].y; }
+    *n_cells = m.k; *shift = m.shift; *vmin = m.vmin;
     return WFS_OK;
 } WFS_CATCH(h)
 

@@ -1628,8 +1628,6 @@ __global__ void k_row_desc(WfsDev d, ZleArgs a)
     if (a.key_base) { atomicMin(&a.key_base->key_origin, q.row_abs); atomicMax(&a.key_base->key_end, q.row_abs + (i64)q.len); }
 }
 
-// finished sample of a row: accumulated ADC + noise + baseline, clamped at 0
-// (rawdata.py:398-458 add_noise / add_baseline / digitizer_saturation, fused into the read)
 // The noise model (wfs_set_noise_model): noise(ch, t) = vmin + alias_sample(cells[ch], word t & 3 of the Philox call of
 // (t >> 2, ch)), t the absolute sample index -- integer arithmetic from the random word to the ADC value.  cells: those of the channel.
 __device__ __forceinline__ i32 noise_model_sample(const WfsDev &d, const uint2 *cells, i32 channel, i64 t)
@@ -1637,7 +1635,7 @@ __device__ __forceinline__ i32 noise_model_sample(const WfsDev &d, const uint2 *
     const AliasTab tab{cells, d.nm_vmin, d.nm_shift};
     const u32x4 a = noise_quad(d.k0, d.k1, channel, t >> 2);
     const u32 m = (u32)t & 3u;
-    return alias_sample(tab, m == 0 ? a.x : (m == 1 ? a.y : (m == 2 ? a.z : a.w)));
+    return alias_sample(tab, m == 0 ? a.x : (m == 1 ? a.y : (m == 2 ? a.z : a.w)));      // (word_of, written out: the call costs k_pack<3> four registers)
 }
 // Samples t0 + i .. t0 + i + 3 of a lane whose i is a multiple of four and whose t0 is wave-uniform: the four words lie in the lane's
 // aligned call and, unless t0 is aligned itself, the one behind it -- which of them is the same for the whole wave (t0 & 3), so the
@@ -1660,27 +1658,42 @@ __device__ __forceinline__ void noise_model_four(const WfsDev &d, const uint2 *c
     for (int j = 0; j < 4; j++) out[j] = alias_sample(tab, w[j]);
 }
 
-// The coloured model (wfs_set_noise_colour, noise kind 4): every stream r -- the channels, then the common streams -- has a
-// white sequence w(r, t) as above (a common stream g under the counter (.., g, SITE_NOISE_COMMON)) and L Q16 taps;
+// A stream of the coloured model (wfs_set_noise_colour): a channel, or a common stream shared by a group of channels.  Its
+// row of the alias cells, of the taps and of the slow amplitudes (the common streams' rows follow the channels'), the id that takes
+// the channel's place in its Philox counters, and the sites of its whites and of its slow levels.  (taps / amp: of a view that has
+// them; nobody reads the others.)
+struct NoiseStream {
+    AliasTab tab; const i32 *taps, *amp; u32 id, site_white, site_slow;
+    __device__ __forceinline__ NoiseStream(const WfsDev &d, i32 n /* channel, or group of a common stream */, bool common)
+    {
+        const i64 row = common ? d.noise_channels + n : n;
+        tab = AliasTab{d.nm_cells + row * d.nm_cells_per_ch, d.nm_vmin, d.nm_shift};
+        taps = d.nc_taps + row * NC_TAP_STRIDE + NC_TAP_PAD; amp = d.ns_amp + row * NS_MAX_LEVELS;
+        id = (u32)n; site_white = common ? SITE_NOISE_COMMON : SITE_NOISE_SAMPLE; site_slow = common ? SITE_NOISE_SLOW_COMMON : SITE_NOISE_SLOW;
+    }
+    // the probes address a stream by its row: a channel, or (row >= noise_channels) a common stream
+    static __device__ __forceinline__ NoiseStream of_row(const WfsDev &d, i32 row) { const bool common = row >= d.noise_channels; return NoiseStream(d, common ? row - d.noise_channels : row, common); }
+};
+
+// The coloured model (noise kind 4): every stream r -- the channels, then the common streams -- has a white sequence w(r, t) as above
+// (a common stream g under the counter (.., g, SITE_NOISE_COMMON)) and L Q16 taps;
 //   F(r, t) = sum_k taps[r][k] w(r, t - k),   noise(ch, t) = (F(ch, t) + ((i64)mix[ch] F(common of ch, t) >> 16) + 32768) >> 16,
 // all in integers: the host has checked that F fits 30 bits (wfs_set_noise_colour).
 //
 // Single-sample form: a lane draws the quads that cover t - L + 1 .. t itself (up to (L + 6) / 4 calls).  No cross-lane traffic, so it
 // may be called from divergent code and with any t per lane: the record-ordered lanes of k_pack, the 64-sample chunks of k_zle's
 // general path, finish_sample.
-__device__ __forceinline__ i32 colour_stream_sample(const WfsDev &d, i32 row, u32 id, u32 site, i64 t)
+__device__ __forceinline__ i32 colour_stream_sample(const WfsDev &d, const NoiseStream &st, i64 t)
 {
-    const AliasTab tab{d.nm_cells + (i64)row * d.nm_cells_per_ch, d.nm_vmin, d.nm_shift};
-    const i32 *taps = d.nc_taps + (i64)row * NC_TAP_STRIDE + NC_TAP_PAD;
     const i64 q1 = t >> 2;
     i32 F = 0;
 #pragma nounroll
     for (i64 q = (t - (d.nc_n_taps - 1)) >> 2; q <= q1; q++) {
-        const u32x4 a = noise_quad_of(d.k0, d.k1, id, site, q);
+        const u32x4 a = noise_quad_of(d.k0, d.k1, st.id, st.site_white, q);
         const u32 w[4] = {a.x, a.y, a.z, a.w};
         const i32 k0 = (i32)(t - 4 * q);                       // distance of the quad's first white: -3 .. L + 2, inside the zero pads
 #pragma unroll
-        for (int c = 0; c < 4; c++) F += taps[k0 - c] * alias_sample(tab, w[c]);
+        for (int c = 0; c < 4; c++) F += st.taps[k0 - c] * alias_sample(st.tab, w[c]);
     }
     return F;
 }
@@ -1692,24 +1705,22 @@ __device__ __forceinline__ i32 colour_stream_sample(const WfsDev &d, i32 row, u3
 //
 // Single-sample form: a lane draws its own two knots per level (one call, two when the pair straddles a quad).  No cross-lane traffic:
 // legal in divergent code and with any t and row per lane, like colour_stream_sample.
-__device__ __forceinline__ i32 slow_stream_sample(const WfsDev &d, i32 row, u32 id, u32 site, i64 t)
+__device__ __forceinline__ i32 slow_stream_sample(const WfsDev &d, const NoiseStream &st, i64 t)
 {
-    const AliasTab tab{d.nm_cells + (i64)row * d.nm_cells_per_ch, d.nm_vmin, d.nm_shift};
-    const i32 *amp = d.ns_amp + (i64)row * NS_MAX_LEVELS;
     i32 S = 0;
 #pragma nounroll
     for (int j = 0; j < d.ns_levels; j++) {
-        const i32 a = amp[j];
+        const i32 a = st.amp[j];
         if (a == 0) continue;
         const i32 s = d.ns_shift[j];
         const i64 m = t >> s;
         const i32 f = (i32)((u32)t & ((1u << s) - 1u));         // (s <= 30: the phase fits 32 bits, and the product below is one 32 x 32 -> 64 multiply)
-        const u32x4 q = noise_quad_of(d.k0, d.k1, id, site + (u32)j, m >> 2);
-        const u32 c = (u32)m & 3u;
-        const u32 w0 = c == 0 ? q.x : (c == 1 ? q.y : (c == 2 ? q.z : q.w));
-        u32 w1 = c == 0 ? q.y : (c == 1 ? q.z : q.w);
-        if (c == 3) w1 = noise_quad_of(d.k0, d.k1, id, site + (u32)j, (m >> 2) + 1).x;
-        const i32 P0 = a * alias_sample(tab, w0), P1 = a * alias_sample(tab, w1);
+        const u32x4 q = noise_quad_of(d.k0, d.k1, st.id, st.site_slow + (u32)j, m >> 2);
+        const int c = (int)((u32)m & 3u);
+        const u32 w0 = word_of(q, c);
+        u32 w1 = word_of(q, c + 1);                             // (of c = 3: the next call's first)
+        if (c == 3) w1 = noise_quad_of(d.k0, d.k1, st.id, st.site_slow + (u32)j, (m >> 2) + 1).x;
+        const i32 P0 = a * alias_sample(st.tab, w0), P1 = a * alias_sample(st.tab, w1);
         S += P0 + (i32)(((i64)(P1 - P0) * (i64)f) >> s);
     }
     return S;
@@ -1721,21 +1732,18 @@ __device__ __forceinline__ i32 slow_stream_sample(const WfsDev &d, i32 row, u32 
 // or two neighbouring quads, fetched by four ds_bpermute per level with an amplitude (levels with amplitude 0 are skipped: the
 // amplitude is the row's, wave-uniform).
 // ALL 64 LANES MUST BE EXECUTING, as for colour_stream_four: call it before any per-lane bound.
-__device__ __forceinline__ void slow_stream_four(const WfsDev &d, i32 row, u32 id, u32 site, i64 tb, int lane, i32 *S)
+__device__ __forceinline__ void slow_stream_four(const WfsDev &d, const NoiseStream &st, i64 tb, int lane, i32 *S)
 {
-    const AliasTab tab{d.nm_cells + (i64)row * d.nm_cells_per_ch, d.nm_vmin, d.nm_shift};
-    const i32 *amp = d.ns_amp + (i64)row * NS_MAX_LEVELS;
     const int nl = d.ns_levels;
     const int lj = (lane >> 3) < nl ? (lane >> 3) : nl - 1;    // (the lanes of levels that are not there repeat the last one; nobody reads them)
     const i64 qown = ((tb >> d.ns_shift[lj]) >> 2) + (lane & 7);
-    const u32x4 a = noise_quad_of(d.k0, d.k1, id, site + (u32)lj, qown);
-    const u32 p0 = ((u32)alias_sample(tab, a.x) & 0xffffu) | ((u32)alias_sample(tab, a.y) << 16);
-    const u32 p1 = ((u32)alias_sample(tab, a.z) & 0xffffu) | ((u32)alias_sample(tab, a.w) << 16);
+    const u32x4 a = noise_quad_of(d.k0, d.k1, st.id, st.site_slow + (u32)lj, qown);
+    const u32 p0 = alias_pair(st.tab, a.x, a.y), p1 = alias_pair(st.tab, a.z, a.w);
     const i64 t0 = tb + 4 * lane;
     S[0] = S[1] = S[2] = S[3] = 0;
 #pragma nounroll
     for (int j = 0; j < nl; j++) {                              // (wave-uniform, and so is the skip)
-        const i32 aq = __builtin_amdgcn_readfirstlane(amp[j]);
+        const i32 aq = __builtin_amdgcn_readfirstlane(st.amp[j]);
         if (aq == 0) continue;
         const i32 s = __builtin_amdgcn_readfirstlane(d.ns_shift[j]);
         const i64 m0 = t0 >> s;
@@ -1774,8 +1782,9 @@ __device__ __forceinline__ i32 noise_colour_sample(const WfsDev &d, i32 channel,
     i32 sum = 0;
 #pragma nounroll
     for (int s = 0; s < (g >= 0 ? 2 : 1); s++) {
-        i32 F = colour_stream_sample(d, s ? d.noise_channels + g : channel, (u32)(s ? g : channel), s ? SITE_NOISE_COMMON : SITE_NOISE_SAMPLE, t);
-        if constexpr (SLOW) F += slow_stream_sample(d, s ? d.noise_channels + g : channel, (u32)(s ? g : channel), s ? SITE_NOISE_SLOW_COMMON : SITE_NOISE_SLOW, t);
+        const NoiseStream st(d, s ? g : channel, s != 0);
+        i32 F = colour_stream_sample(d, st, t);
+        if constexpr (SLOW) F += slow_stream_sample(d, st, t);
         sum += (i32)(((i64)(s ? mix : 65536) * F) >> 16);       // (65536 F >> 16 is F)
     }
     return (sum + 32768) >> 16;
@@ -1787,18 +1796,15 @@ __device__ __forceinline__ i32 noise_colour_sample(const WfsDev &d, i32 channel,
 // same step for every lane, and sixteen multiply-adds against the seven taps the step's distances ask for (scalar loads; zeros outside
 // 0 .. L - 1).  Two Philox calls and eight alias gathers per lane and stream whatever L and tb & 3.
 // ALL 64 LANES MUST BE EXECUTING (ds_bpermute reads nothing from a switched-off lane): call it before any per-lane bound.
-__device__ __forceinline__ void colour_stream_four(const WfsDev &d, i32 row, u32 id, u32 site, i64 tb, int lane, i32 *F)
+__device__ __forceinline__ void colour_stream_four(const WfsDev &d, const NoiseStream &st, i64 tb, int lane, i32 *F)
 {
-    const AliasTab tab{d.nm_cells + (i64)row * d.nm_cells_per_ch, d.nm_vmin, d.nm_shift};
-    const i32 *taps = d.nc_taps + (i64)row * NC_TAP_STRIDE + NC_TAP_PAD;
     const i64 s0 = tb - (d.nc_n_taps - 1);                      // the first white lane 0 needs
     const i64 qb = s0 >> 2;
     const i32 reach = __builtin_amdgcn_readfirstlane(d.nc_n_taps - 1 + (i32)(s0 & 3));      // distance of sample 0 of a lane from word 0 of its own quad
     const i32 dmax = (reach + 3) >> 2;
     auto quad = [&](i64 q, u32 &lo, u32 &hi) {
-        const u32x4 a = noise_quad_of(d.k0, d.k1, id, site, q);
-        lo = ((u32)alias_sample(tab, a.x) & 0xffffu) | ((u32)alias_sample(tab, a.y) << 16);
-        hi = ((u32)alias_sample(tab, a.z) & 0xffffu) | ((u32)alias_sample(tab, a.w) << 16);
+        const u32x4 a = noise_quad_of(d.k0, d.k1, st.id, st.site_white, q);
+        lo = alias_pair(st.tab, a.x, a.y); hi = alias_pair(st.tab, a.z, a.w);
     };
     u32 p0, p1, r0 = 0, r1 = 0;
     quad(qb + lane, p0, p1);
@@ -1814,7 +1820,7 @@ __device__ __forceinline__ void colour_stream_four(const WfsDev &d, i32 row, u32
         const i32 kb = reach - 4 * dd;                          // sample j against word c: tap kb + j - c
         i32 tp[7];
 #pragma unroll
-        for (int u = 0; u < 7; u++) tp[u] = taps[kb - 3 + u];
+        for (int u = 0; u < 7; u++) tp[u] = st.taps[kb - 3 + u];
 #pragma unroll
         for (int c = 0; c < 4; c++)
 #pragma unroll
@@ -1829,11 +1835,12 @@ __device__ __forceinline__ void noise_colour_four(const WfsDev &d, i32 channel, 
     i32 sum[4] = {0, 0, 0, 0};
 #pragma nounroll
     for (int s = 0; s < (g >= 0 ? 2 : 1); s++) {
+        const NoiseStream st(d, s ? g : channel, s != 0);
         i32 F[4];
-        colour_stream_four(d, s ? d.noise_channels + g : channel, (u32)(s ? g : channel), s ? SITE_NOISE_COMMON : SITE_NOISE_SAMPLE, tb, lane, F);
+        colour_stream_four(d, st, tb, lane, F);
         if constexpr (SLOW) {
             i32 S[4];
-            slow_stream_four(d, s ? d.noise_channels + g : channel, (u32)(s ? g : channel), s ? SITE_NOISE_SLOW_COMMON : SITE_NOISE_SLOW, tb, lane, S);
+            slow_stream_four(d, st, tb, lane, S);
 #pragma unroll
             for (int j = 0; j < 4; j++) F[j] += S[j];
         }
@@ -1842,28 +1849,6 @@ __device__ __forceinline__ void noise_colour_four(const WfsDev &d, i32 channel, 
     }
 #pragma unroll
     for (int j = 0; j < 4; j++) out[j] = (sum[j] + 32768) >> 16;
-}
-
-// (NK: the noise kind of the row kernels below; row_abs, the row's first absolute sample, is what kinds 3, 4 and 5 count from; kind 5 is
-// kind 4 with the slow levels and goes wherever kind 4 goes)
-template <int NK>
-__device__ __forceinline__ i32 finish_sample(const WfsDev &d, const i32 *acc, i64 i, i32 slot_ch, bool he, i64 ix_rand, i64 row_abs)
-{
-    i64 v = acc[i];
-    if (he) v *= d.he_factor;                                   // rawdata.py:242-246
-    if constexpr (NK == 3) {
-        if (slot_ch < d.noise_channels) v += noise_model_sample(d, d.nm_cells + (i64)slot_ch * d.nm_cells_per_ch, slot_ch, row_abs + i);
-    } else if constexpr (NK == 4 || NK == 5) {
-        if (slot_ch < d.noise_channels) v += noise_colour_sample<NK == 5>(d, slot_ch, row_abs + i);
-    } else
-    if (d.enable_noise && slot_ch < d.noise_channels) {
-        const u32 in = ((u32)ix_rand + (u32)i) % (u32)d.noise_len;      // rawdata.py:433-434 (ix_rand < noise_len <= 2^31, i < 2^20: 32 bits hold the sum)
-        // channel-major copy (wfs_set_tables): consecutive samples, consecutive addresses
-        if (d.noise_f) v = (i64)((double)v + d.noise_f[(i64)slot_ch * d.noise_stride + in]);     // numba: int64 += float64 stores the truncated sum
-        else v += d.noise[(i64)slot_ch * d.noise_stride + in];
-    }
-    v += d.baseline;
-    return v < 0 ? 0 : (i32)v;
 }
 
 // wfs_noise_model_samples: noise(channel, t0 .. t0 + n - 1) through the two forms the row kernels use -- a thread takes four
@@ -1900,35 +1885,32 @@ __global__ __launch_bounds__(256) void k_noise_colour_samples(WfsDev d, i32 chan
         for (i64 u = s; u < n; u++) out[u] = (int16_t)noise_colour_sample<SLOW>(d, channel, t0 + u);
     }
 }
-// wfs_noise_slow_samples: S(row, t0 .. t0 + n - 1) in Q16 of a stream, a channel or (row >= noise_channels) a common stream, through the
-// same two forms
+// wfs_noise_slow_samples: S(row, t0 .. t0 + n - 1) in Q16 of a stream through the same two forms
 __global__ __launch_bounds__(256) void k_noise_slow_samples(WfsDev d, i32 row, i64 t0, i64 n, i32 *out)
 {
     const int lane = threadIdx.x & 63;
     const i64 b = ((i64)blockIdx.x * 4 + wave_in_block()) * 256;
-    const bool common = row >= d.noise_channels;
-    const u32 id = (u32)(common ? row - d.noise_channels : row), site = common ? SITE_NOISE_SLOW_COMMON : SITE_NOISE_SLOW;
+    const NoiseStream st = NoiseStream::of_row(d, row);
     i32 v[4];
-    slow_stream_four(d, row, id, site, t0 + b, lane, v);
+    slow_stream_four(d, st, t0 + b, lane, v);
     const i64 s = b + 4 * lane;
     if (s + 3 < n) {
 #pragma unroll
         for (int j = 0; j < 4; j++) out[s + j] = v[j];
     } else {
-        for (i64 u = s; u < n; u++) out[u] = slow_stream_sample(d, row, id, site, t0 + u);
+        for (i64 u = s; u < n; u++) out[u] = slow_stream_sample(d, st, t0 + u);
     }
 }
-// wfs_noise_white_samples: the white sequence w(row, t0 .. t0 + n - 1) of a stream, a channel or (row >= noise_channels) a common stream
+// wfs_noise_white_samples: the white sequence w(row, t0 .. t0 + n - 1) of a stream
 __global__ __launch_bounds__(256) void k_noise_white_samples(WfsDev d, i32 row, i64 t0, i64 n, int16_t *out)
 {
     const i64 s = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
-    const AliasTab tab{d.nm_cells + (i64)row * d.nm_cells_per_ch, d.nm_vmin, d.nm_shift};
-    const bool common = row >= d.noise_channels;
+    const NoiseStream st = NoiseStream::of_row(d, row);
     const i64 t = t0 + s;
-    const u32x4 a = noise_quad_of(d.k0, d.k1, (u32)(common ? row - d.noise_channels : row), common ? SITE_NOISE_COMMON : SITE_NOISE_SAMPLE, t >> 2);
+    const u32x4 a = noise_quad_of(d.k0, d.k1, st.id, st.site_white, t >> 2);
     const u32 m = (u32)t & 3u;
-    out[s] = (int16_t)alias_sample(tab, m == 0 ? a.x : (m == 1 ? a.y : (m == 2 ? a.z : a.w)));
+    out[s] = (int16_t)alias_sample(st.tab, m == 0 ? a.x : (m == 1 ? a.y : (m == 2 ? a.z : a.w)));      // (word_of, written out: the call costs this kernel four registers)
 }
 
 // (acc_ch -1: the window's sum row, which has no accumulator row of a channel behind it)
@@ -1939,22 +1921,61 @@ __device__ __forceinline__ void row_of_slot(const WfsDev &d, i64 idx, i64 &g, i3
     he = slot >= d.n_tpc; acc_ch = he ? slot - d.n_tpc : slot; channel = he ? d.he_first + acc_ch : slot;
 }
 
+// NK, the noise of the batch, is a template parameter of the row kernels (NoiseKind of wfs_noise.h; 0: none, 1: int16 table, 2: float64
+// table, 3: the noise model, drawn where the tables are loaded, 4: the coloured model, drawn at the same places, 5: the same with the
+// slow levels added to every stream, which goes wherever kind 4 goes).  row_abs, the row's first absolute sample, is what kinds 3, 4
+// and 5 count from.
+//
+// The finished sample of a row: accumulated ADC (times the HE factor, rawdata.py:242-246) + noise + baseline, clamped at 0
+// (rawdata.py:398-458 add_noise / add_baseline / digitizer_saturation, fused into the read).  nz: the integer noise of kinds 1, 3, 4, 5;
+// nzf: that of kind 2, added in floating point -- numba's int64 += float64 stores the TRUNCATED SUM, not the sum with the truncated
+// noise.  noisy false (a row outside the table, wave-uniform): the tables' value was read from row 0 and is dropped here; the drawn
+// kinds hand in 0.
+template <int NK>
+__device__ __forceinline__ i32 finish_value(const WfsDev &d, i32 acc, bool he, bool noisy, i32 nz, double nzf)
+{
+    i64 v = acc;
+    if (he) v *= d.he_factor;
+    if constexpr (NK == 1) v += noisy ? nz : 0;
+    if constexpr (NK == 2) { const i64 w = (i64)((double)v + nzf); v = noisy ? w : v; }
+    if constexpr (NK >= 3) v += nz;
+    v += d.baseline;
+    return v < 0 ? 0 : (i32)v;
+}
+// Sample i of a row in one step, its noise fetched behind a branch: the general paths of k_zle and k_pack
+template <int NK>
+__device__ __forceinline__ i32 finish_sample(const WfsDev &d, const i32 *acc, i64 i, i32 slot_ch, bool he, i64 ix_rand, i64 row_abs)
+{
+    const bool noisy = NK != 0 && (NK >= 3 || d.enable_noise) && slot_ch < d.noise_channels;
+    i32 nz = 0; double nzf = 0;
+    if (noisy) {
+        if constexpr (NK == 3) nz = noise_model_sample(d, d.nm_cells + (i64)slot_ch * d.nm_cells_per_ch, slot_ch, row_abs + i);
+        else if constexpr (NK == 4 || NK == 5) nz = noise_colour_sample<NK == 5>(d, slot_ch, row_abs + i);
+        else if constexpr (NK != 0) {
+            const u32 in = ((u32)ix_rand + (u32)i) % (u32)d.noise_len;      // rawdata.py:433-434 (ix_rand < noise_len <= 2^31, i < 2^20: 32 bits hold the sum)
+            // channel-major copy (wfs_set_tables): consecutive samples, consecutive addresses
+            if constexpr (NK == 2) nzf = d.noise_f[(i64)slot_ch * d.noise_stride + in]; else nz = d.noise[(i64)slot_ch * d.noise_stride + in];
+        }
+    }
+    return finish_value<NK>(d, acc[i], he, noisy, nz, nzf);
+}
+
 // The same in two steps, for loops that want ALL their loads in flight before the first use: with the load inside finish_sample
 // the compiler waits for every load right behind it (a branch follows), and a wave spends one memory round trip per load.
 // A row no longer than the noise array wraps at most once (ix_rand < noise_len, i < len <= noise_len): no loop on the load path.
-// NK, the noise of the batch, is a template parameter (0: none, 1: int16 table, 2: float64 table, 3: the noise model, drawn where the
-// tables are loaded: noise_row then points at the channel's alias cells, nullptr for a row outside the model; 4: the coloured model,
-// drawn at the same places -- load_sample through the single-sample form, load_four through the shared draws; 5: the same with the
-// slow levels added to every stream) and a row outside the table
-// (noisy false, wave-uniform) reads row 0 and drops the value: NO branch sits between two loads -- with a branch around the
-// noise load the compiler drained the memory counter after every one of them.
-template <int NK> struct RawSample;
+// noise_row points at the channel's row of the table, for the drawn kinds at its alias cells (noise_row_of), and a row outside the
+// table (noisy false, wave-uniform) reads row 0 and drops the value, a row outside the model (nullptr) draws nothing: NO branch sits
+// between two loads -- with a branch around the noise load the compiler drained the memory counter after every one of them.
+template <int NK>
+__device__ __forceinline__ const void *noise_row_of(const WfsDev &d, i32 channel, bool noisy)
+{
+    const i64 noise_off = noisy ? (i64)channel * d.noise_stride : 0;
+    return NK >= 3 ? (const void *)(noisy ? d.nm_cells + (i64)channel * d.nm_cells_per_ch : nullptr)
+                   : (NK == 2 ? (const void *)(d.noise_f + noise_off) : (const void *)(d.noise + noise_off));
+}
+template <int NK> struct RawSample { i32 acc; i32 nz; };
 template <> struct RawSample<0> { i32 acc; };
-template <> struct RawSample<1> { i32 acc; i32 nz; };
 template <> struct RawSample<2> { i32 acc; double nzf; };
-template <> struct RawSample<3> { i32 acc; i32 nz; };
-template <> struct RawSample<4> { i32 acc; i32 nz; };
-template <> struct RawSample<5> { i32 acc; i32 nz; };
 template <int NK>
 __device__ __forceinline__ RawSample<NK> load_sample(const WfsDev &d, const i32 *acc, i32 i, const void *noise_row, u32 nstart, u32 noff, i32 channel = 0, i64 row_abs = 0)
 {
@@ -1973,53 +1994,48 @@ __device__ __forceinline__ RawSample<NK> load_sample(const WfsDev &d, const i32 
 template <int NK>
 __device__ __forceinline__ i32 finish_loaded(const WfsDev &d, const RawSample<NK> &s, bool he, bool noisy)
 {
-    i64 v = s.acc;
-    if (he) v *= d.he_factor;
-    if constexpr (NK == 1) v += noisy ? s.nz : 0;
-    if constexpr (NK == 2) { const i64 w = (i64)((double)v + s.nzf); v = noisy ? w : v; }
-    if constexpr (NK >= 3) v += s.nz;
-    v += d.baseline;
-    return v < 0 ? 0 : (i32)v;
+    i32 nz = 0; double nzf = 0;
+    if constexpr (NK == 2) nzf = s.nzf; else if constexpr (NK != 0) nz = s.nz;
+    return finish_value<NK>(d, s.acc, he, noisy, nz, nzf);
 }
 
 // Four consecutive samples of a row per lane (k_zle): 16 bytes of the row at a 4-byte aligned address, 8 (32) bytes of the noise at a
 // 2 (8)-byte aligned one -- the hardware takes both as single loads; NOISE_PAD keeps the noise read off the wrap.
-template <int NK> struct Raw4;
+template <int NK> struct Raw4 { i32 acc[4]; i32 nz[4]; };
 template <> struct Raw4<0> { i32 acc[4]; };
 template <> struct Raw4<1> { i32 acc[4]; int16_t nz[4]; };
 template <> struct Raw4<2> { i32 acc[4]; double nzf[4]; };
-template <> struct Raw4<3> { i32 acc[4]; i32 nz[4]; };
-template <> struct Raw4<4> { i32 acc[4]; i32 nz[4]; };
-template <> struct Raw4<5> { i32 acc[4]; i32 nz[4]; };
+// The noise of lane `lane` of a wave that takes the 256 samples of a row from nstart on, four per lane.  Tables: nstart < noise_len is
+// the (scalar) table index of the block's first sample, wrapped once.  Drawn kinds: nstart is the UNCLAMPED wave-uniform index of the
+// block's first sample in the row, so that (row_abs + nstart) & 3 is wave-uniform and, for kinds 4 and 5, every lane draws the quad its
+// neighbours need whether or not its own samples lie in the row: ALL 64 LANES MUST BE EXECUTING (colour_stream_four).
 template <int NK>
-__device__ __forceinline__ Raw4<NK> load_four(const WfsDev &d, const i32 *acc, i32 i, const void *noise_row, u32 nstart, u32 noff, i32 channel = 0, i64 row_abs = 0)
+__device__ __forceinline__ void noise_four(const WfsDev &d, Raw4<NK> &o, const void *noise_row, i32 channel, i64 row_abs, u32 nstart, int lane)
+{
+    if constexpr (NK >= 3) {
+        if (!noise_row) o.nz[0] = o.nz[1] = o.nz[2] = o.nz[3] = 0;      // (wave-uniform)
+        else if constexpr (NK == 3) noise_model_four(d, (const uint2 *)noise_row, channel, row_abs + (i64)nstart, 4 * lane, o.nz);
+        else noise_colour_four<NK == 5>(d, channel, row_abs + (i64)nstart, lane, o.nz);
+    } else if constexpr (NK != 0) {
+        u32 in = nstart + 4u * (u32)lane;
+        in = in >= (u32)d.noise_len ? in - (u32)d.noise_len : in;
+        if constexpr (NK == 2) __builtin_memcpy(o.nzf, (const double *)noise_row + in, 32); else __builtin_memcpy(o.nz, (const int16_t *)noise_row + in, 8);
+    }
+}
+// (i may be clamped into the row -- k_zle, lanes past its end: the noise goes by nstart and the lane)
+template <int NK>
+__device__ __forceinline__ Raw4<NK> load_four(const WfsDev &d, const i32 *acc, i32 i, const void *noise_row, u32 nstart, int lane, i32 channel = 0, i64 row_abs = 0)
 {
     Raw4<NK> s; __builtin_memcpy(s.acc, acc + (u32)i, 16);
-    if constexpr (NK == 3) {
-        if (noise_row) noise_model_four(d, (const uint2 *)noise_row, channel, row_abs, i, s.nz);      // (wave-uniform; i is a multiple of four)
-        else s.nz[0] = s.nz[1] = s.nz[2] = s.nz[3] = 0;
-    } else if constexpr (NK == 4 || NK == 5) {
-        // i may be clamped into the row (k_zle, lanes past its end): the position is nstart, the UNCLAMPED wave-uniform index of the
-        // block's first sample in the row, plus the lane's noff = 4 lane -- a lane past the end still draws the quad its neighbours need
-        if (noise_row) noise_colour_four<NK == 5>(d, channel, row_abs + (i64)nstart, (int)(noff >> 2), s.nz);      // (wave-uniform)
-        else s.nz[0] = s.nz[1] = s.nz[2] = s.nz[3] = 0;
-    } else if constexpr (NK != 0) {
-        u32 in = nstart + noff;
-        in = in >= (u32)d.noise_len ? in - (u32)d.noise_len : in;
-        if constexpr (NK == 2) __builtin_memcpy(s.nzf, (const double *)noise_row + in, 32); else __builtin_memcpy(s.nz, (const int16_t *)noise_row + in, 8);
-    }
+    noise_four<NK>(d, s, noise_row, channel, row_abs, nstart, lane);
     return s;
 }
 template <int NK>
 __device__ __forceinline__ i32 finish_four(const WfsDev &d, const Raw4<NK> &s, int j, bool he, bool noisy)
 {
-    i64 v = s.acc[j];
-    if (he) v *= d.he_factor;
-    if constexpr (NK == 1) v += noisy ? (i32)s.nz[j] : 0;
-    if constexpr (NK == 2) { const i64 w = (i64)((double)v + s.nzf[j]); v = noisy ? w : v; }
-    if constexpr (NK >= 3) v += s.nz[j];
-    v += d.baseline;
-    return v < 0 ? 0 : (i32)v;
+    i32 nz = 0; double nzf = 0;
+    if constexpr (NK == 2) nzf = s.nzf[j]; else if constexpr (NK != 0) nz = s.nz[j];
+    return finish_value<NK>(d, s.acc[j], he, noisy, nz, nzf);
 }
 
 // The interval bookkeeping of a row whose hold-off is at least a chunk of 64 samples: two hits of one chunk are never more than the
@@ -2108,9 +2124,8 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
     // (The noise model, kinds 3, 4 and 5, has no table and no wrap: the fast paths wherever kind 0 takes them.)
     constexpr bool TABLE = NK == 1 || NK == 2;
     const bool fast_loads = len32 >= 1 && (!TABLE || d.noise_len >= NOISE_MIN_FAST);
-    const i64 noise_off = noisy ? (i64)channel * d.noise_stride : 0; const u32 nixr = noisy ? (u32)ixr : 0u;
-    const void *noise_row = NK >= 3 ? (const void *)(noisy ? d.nm_cells + (i64)channel * d.nm_cells_per_ch : nullptr)
-                                    : (NK == 2 ? (const void *)(d.noise_f + noise_off) : (const void *)(d.noise + noise_off));
+    const u32 nixr = noisy ? (u32)ixr : 0u;
+    const void *noise_row = noise_row_of<NK>(d, channel, noisy);
     if (hold32 >= 63 && fast_loads && !a.row_dbg) {
         // The usual geometry (hold-off of at least a chunk): the interval bookkeeping is scalar work on the ballot mask (ZleFast), and
         // the vector unit is left with load, finish and compare.
@@ -2128,7 +2143,15 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
 #pragma unroll
             for (int u = 0; u < G; u++) {
                 const i32 i = g0 + 256 * u + 4 * lane;
-                buf[u] = load_four<NK>(d, acc, i < len32 ? i : 0, noise_row, NK >= 4 ? (u32)(g0 + 256 * u) : nrun, 4u * (u32)lane, channel, row_abs);
+                if constexpr (NK == 3) {
+                    // load_four, written out (with the call k_zle<3> takes 76 registers for 71 and loses a wave of occupancy): the draw
+                    // counts from the row's start with the lane's clamped index, which has the same t0 & 3 as noise_four's
+                    const i32 ic = i < len32 ? i : 0;
+                    __builtin_memcpy(buf[u].acc, acc + (u32)ic, 16);
+                    if (noise_row) noise_model_four(d, (const uint2 *)noise_row, channel, row_abs, ic, buf[u].nz);      // (wave-uniform)
+                    else buf[u].nz[0] = buf[u].nz[1] = buf[u].nz[2] = buf[u].nz[3] = 0;
+                } else
+                buf[u] = load_four<NK>(d, acc, i < len32 ? i : 0, noise_row, NK >= 4 ? (u32)(g0 + 256 * u) : nrun, lane, channel, row_abs);
                 if constexpr (TABLE) { nrun += 256u; nrun = nrun >= (u32)d.noise_len ? nrun - (u32)d.noise_len : nrun; }
             }
         };
@@ -2304,27 +2327,14 @@ __global__ __launch_bounds__(256) void k_row_pulse(WfsDev d, PulseArgs a, ZleArg
     i64 hold = 2 * (i64)d.tw + 1; if (hold < 1) hold = 1;
     const i32 hold32 = (i32)hold;
     const bool noisy = NK != 0 && q.channel < d.noise_channels;
-    const i64 noise_off = noisy ? (i64)q.channel * d.noise_stride : 0;
-    const void *noise_row = NK >= 3 ? (const void *)(noisy ? d.nm_cells + (i64)q.channel * d.nm_cells_per_ch : nullptr)
-                                    : (NK == 2 ? (const void *)(d.noise_f + noise_off) : (const void *)(d.noise + noise_off));
+    const void *noise_row = noise_row_of<NK>(d, q.channel, noisy);
     u32 nrun = (noisy && NK < 3) ? (u32)q.ixr : 0u;       // noise index of the next block's first sample (rawdata.py:433-434); kinds 3, 4: that sample's index in the row
     int16_t *fin = z.fin + q.acc_off;
     const i32 fin_len = (len32 + 3) & ~3;
-    auto load_noise = [&](Raw4<NK> &o) {
-        if constexpr (NK == 3) {                          // drawn, not loaded: the block's first absolute sample is wave-uniform
-            if (noise_row) noise_model_four(d, (const uint2 *)noise_row, q.channel, row_abs + (i64)nrun, 4 * lane, o.nz);
-            else o.nz[0] = o.nz[1] = o.nz[2] = o.nz[3] = 0;
-            nrun += 256u;
-        } else if constexpr (NK == 4 || NK == 5) {        // the shared draws: every lane of the wave is here (the callers' conditions are wave-uniform)
-            if (noise_row) noise_colour_four<NK == 5>(d, q.channel, row_abs + (i64)nrun, lane, o.nz);
-            else o.nz[0] = o.nz[1] = o.nz[2] = o.nz[3] = 0;
-            nrun += 256u;
-        } else if constexpr (NK != 0) {
-            u32 in = nrun + 4u * (u32)lane;
-            in = in >= (u32)d.noise_len ? in - (u32)d.noise_len : in;
-            if constexpr (NK == 2) __builtin_memcpy(o.nzf, (const double *)noise_row + in, 32); else __builtin_memcpy(o.nz, (const int16_t *)noise_row + in, 8);
-            nrun += 256u; nrun = nrun >= (u32)d.noise_len ? nrun - (u32)d.noise_len : nrun;
-        }
+    auto load_noise = [&](Raw4<NK> &o) {                  // (every lane of the wave is here: the callers' conditions are wave-uniform)
+        noise_four<NK>(d, o, noise_row, q.channel, row_abs, nrun, lane);
+        if constexpr (NK != 0) nrun += 256u;
+        if constexpr (NK == 1 || NK == 2) nrun = nrun >= (u32)d.noise_len ? nrun - (u32)d.noise_len : nrun;
     };
     Raw4<NK> s4;
     load_noise(s4);                                       // the first block's noise: on its way under the pulses
@@ -2366,7 +2376,8 @@ __global__ __launch_bounds__(256) void k_row_pulse(WfsDev d, PulseArgs a, ZleArg
 #pragma unroll
                 for (int j = 0; j < 4; j++) { const i32 v = finish_four<NK>(d, s4, j, false, noisy); nib |= (i + j < len32 && (i64)v < thr) ? (1u << j) : 0u; v16[j] = (u32)(uint16_t)v; }
             } else {
-                // integer noise: 32-bit arithmetic with a saturating add -- the values of finish_four for every accumulator that is not within
+                // integer noise: NOT finish_value but a deliberately cheaper rule (no HE rows here, so no factor), 32-bit arithmetic with
+                // a saturating add -- the values of finish_value for every accumulator that is not within
                 // 2^16 of overflowing an int32 (a row of a 14-bit digitiser is some 10^5 times smaller)
                 const i32 live = len32 - i;                  // samples of the lane inside the row
 #pragma unroll
@@ -2507,9 +2518,8 @@ __global__ __launch_bounds__(256) void k_pack(WfsDev d, ZleArgs a)
     const bool noisy = NK != 0 && channel < d.noise_channels;
     constexpr bool TABLE = NK == 1 || NK == 2;
     const bool fast_loads = !TABLE || (d.noise_len >= NOISE_MIN_FAST && spr <= NOISE_MIN_FAST / 2);       // (as in k_zle: a scalar noise start per record)
-    const i64 noise_off = noisy ? (i64)channel * d.noise_stride : 0; const u32 nixr = noisy ? (u32)ixr : 0u;
-    const void *noise_row = NK >= 3 ? (const void *)(noisy ? d.nm_cells + (i64)channel * d.nm_cells_per_ch : nullptr)
-                                    : (NK == 2 ? (const void *)(d.noise_f + noise_off) : (const void *)(d.noise + noise_off));
+    const u32 nixr = noisy ? (u32)ixr : 0u;
+    const void *noise_row = noise_row_of<NK>(d, channel, noisy);
     const u32 w3 = ((u32)(uint16_t)d.dt) | ((u32)(uint16_t)channel << 16);
     constexpr int PACK_U = NK >= 4 ? 1 : 4;         // (kind 4 draws where the others load: one record's draws at a time, one copy of their code)
     i64 rec = q.rec;
@@ -2956,8 +2966,6 @@ __global__ void k_set_bases(GenArgs a)
         run += a.em_ph_off[a.em_off[i + 1]] - a.em_ph_off[a.em_off[i]];
     }
 }
-
-__device__ __forceinline__ u32 word_of(const u32x4 &W, int k) { return k == 0 ? W.x : (k == 1 ? W.y : (k == 2 ? W.z : W.w)); }
 
 // PMT afterpulses of one photon (afterpulse.py:172-249): one uniform pair per element.  RNG spec v10: the top 32 bits of the FIRST
 // uniform of elements 4k .. 4k + 3 are the four words of one call (site SITE_AP_SCREEN + k); its low bits and the second uniform come
