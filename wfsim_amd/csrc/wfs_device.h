@@ -10,15 +10,14 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "wfs_noise.h"       // NoiseKind, the NC_ / NS_ constants of the coloured model and its slow levels
+#include "wfs_layout.h"      // the sizes the LDS layouts are made of (WFS_DT, WFS_MAX_CH, SPE_ROW_LEN, ..), floordiv, the window rules
 
 typedef long long i64;
 typedef unsigned long long u64;
 typedef int i32;
 typedef unsigned int u32;
 
-#define WFS_MAX_CH 1024          // channels that fit the LDS histograms of the bucketing kernels
 #define WFS_MAX_AP 8
-#define WFS_DT 10                // sample_duration [ns]; wfs_create rejects anything else
 
 enum WfsSite : u32 {
     SITE_S1_HIT = 1, SITE_S2_SURVIVE = 2, SITE_EL_A = 3, SITE_EL_B = 4, SITE_EL_POIS = 5,
@@ -119,9 +118,7 @@ __device__ __forceinline__ i32 alias_sample(const AliasTab &t, u32 w) { const u3
 __device__ __forceinline__ u32 alias_pair(const AliasTab &t, u32 wa, u32 wb) { return ((u32)alias_sample(t, wa) & 0xffffu) | ((u32)alias_sample(t, wb) << 16); }
 
 // A channel's SPE row (pulse.py:97: a photon's gain is entry int(u * SPE_BINS) + 1 of it): SPE_BINS quantiles behind an entry 0 that no
-// photon indexes.
-constexpr int SPE_BINS = 2000, SPE_ROW_LEN = SPE_BINS + 1;
-
+// photon indexes (SPE_ROW_LEN entries, wfs_layout.h).
 // SPE indices and double-PE flag of a photon from ONE word (pulse.py:76-79, 97-103, 226): w * SPE_BINS = g * 2^32 + frac;
 // g + 1 = int(u * SPE_BINS) + 1 is the first index; frac (the 32 low bits, equidistributed for every g) < thr is the double-PE
 // Bernoulli trial, and given frac < thr it is uniform on [0, thr): int(frac * SPE_BINS / thr) + 1 is the second index.
@@ -238,13 +235,14 @@ __device__ __forceinline__ double wave_sum(double v)
 #endif
 
 // python-style floor division / modulo on int64 (numpy // and % on int64, pulse.py:305-306)
-__host__ __device__ __forceinline__ i64 floordiv(i64 a, i64 b) { i64 q = a / b; return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q; }
 __host__ __device__ __forceinline__ i64 floormod(i64 a, i64 b) { i64 m = a % b; return (m != 0 && ((m < 0) != (b < 0))) ? m + b : m; }
 
 // A lane of k_zle reads 4 consecutive noise samples from any start below noise_len: every channel row of the device copy is
 // followed by its own first NOISE_PAD samples, so the read never meets the wrap (rawdata.py:433-434 indexes modulo noise_len).
 constexpr int NOISE_PAD = 4;
 constexpr int WFS_SPR = 110;                   // samples per strax record (strax DEFAULT_RECORD_LENGTH; a compile-time constant: the divisions by it are in every row kernel)
+constexpr int WFS_RECORD_BYTES = 24 + 2 * WFS_SPR;       // one packed raw_record: 24 bytes of header, the samples (strax_interface.py:391-436)
+static_assert(WFS_RECORD_BYTES == 244, "the record layout of include/wfsim_amd.h");
 constexpr int NOISE_MIN_FAST = 512;            // shortest noise table of the fast row kernels (a block of 256 samples wraps at most once)
 
 // The device scalar block: counters that kernels bump with atomics, totals that the scans write, the error code, the origin of

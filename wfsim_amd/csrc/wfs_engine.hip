@@ -21,8 +21,7 @@
 #define K_PULSE_256_WIN(F) k_pulse<256, false, F>
 #define K_PULSE_128_WIN(F) k_pulse<128, false, F>
 #define K_PULSE_GENERIC(F) k_pulse_generic<256, F>
-#define K_PULSE_SPARSE_64(F) k_pulse_sparse<64, F>
-#define K_PULSE_SPARSE_256(F) k_pulse_sparse<256, F>
+#define K_PULSE_SPARSE(F) k_pulse_sparse<SPARSE_TPB, F>
 #define K_PULSE_TINY(F) k_pulse_tiny<F>
 #define K_PULSE_WAVE(F) k_pulse_wave<F>
 #define WFS_LAUNCH_F(h, KM, grid, block, lds, ...) do { \
@@ -207,7 +206,65 @@ int upload(wfs_handle *h, DevBuf &b, const void *src, size_t bytes)
     return WFS_OK;
 }
 
+// n elements of a device buffer on the host, a blocking copy.  A HIP error is recorded on the handle (fail) and thrown: the firewall of
+// the C ABI (wfs_caught) hands its code back like the return of a HIPCHK.
+struct WfsHipError { int code; };
+template <class T>
+std::vector<T> download(wfs_handle *h, const DevBuf &b, size_t n)
+{
+    std::vector<T> v(n);
+    if (n) { const hipError_t e = hipMemcpy(v.data(), b.p, n * sizeof(T), hipMemcpyDeviceToHost); if (e != hipSuccess) throw WfsHipError{h->fail(WFS_E_HIP, std::string("hipMemcpy (download): ") + hipGetErrorString(e))}; }
+    return v;
+}
+
 #define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+
+// The listed tiles in work-list order with their sample windows, and the offsets of their currents (the total behind the last): what a
+// run with DBG_CURRENTS uploads as cur_off and what wfs_copy_pulses hands out.
+struct ListedTiles { std::vector<i32> tile; std::vector<TileWindow> win; std::vector<i64> off; };
+ListedTiles listed_tiles(wfs_handle *h)
+{
+    const WfsDev &d = h->dev;
+    ListedTiles r;
+    r.tile = download<i32>(h, h->active_tiles, (size_t)h->run.n_active_tiles);
+    const std::vector<i32> tmn = download<i32>(h, h->tile_tmin, (size_t)h->batch.n_tiles), tmx = download<i32>(h, h->tile_tmax, (size_t)h->batch.n_tiles);
+    const std::vector<i64> t0 = download<i64>(h, h->set_t0, (size_t)h->batch.n_sets);
+    r.win.resize(r.tile.size()); r.off.assign(r.tile.size() + 1, 0);
+    for (size_t k = 0; k < r.tile.size(); k++) {
+        const i32 tile = r.tile[k];
+        r.win[k] = tile_window(d, t0[tile / d.n_tpc], tmn[tile], tmx[tile]);
+        r.off[k + 1] = r.off[k] + r.win[k].L;
+    }
+    return r;
+}
+// The rows with data in row-list order: slot, first and last pulse sample (absolute) of each, and the offsets of their debug copies
+// (the total behind the last): row_dbg_off of a run with DBG_CURRENTS and data_off of wfs_copy_rows.
+struct ListedRows { std::vector<RowSlot> slot; std::vector<i64> lo, hi, off; };
+ListedRows listed_rows(wfs_handle *h)
+{
+    const WfsDev &d = h->dev;
+    const size_t CG = (size_t)h->batch.n_clusters + 1;
+    const std::vector<i32> ar = download<i32>(h, h->active_rows, (size_t)h->run.n_active_rows);
+    const std::vector<i64> lo = download<i64>(h, h->row_lo, CG * d.n_tpc), hi = download<i64>(h, h->row_hi, CG * d.n_tpc);
+    std::vector<i64> slo, shi;
+    if (d.sum_channel >= 0) { slo = download<i64>(h, h->sum_lo, CG); shi = download<i64>(h, h->sum_hi, CG); }
+    ListedRows r;
+    r.slot.resize(ar.size()); r.lo.resize(ar.size()); r.hi.resize(ar.size()); r.off.assign(ar.size() + 1, 0);
+    for (size_t k = 0; k < ar.size(); k++) {
+        const RowSlot s = r.slot[k] = row_slot(d, ar[k]);
+        r.lo[k] = s.sum ? slo[s.g] : lo[s.g * d.n_tpc + s.acc_ch]; r.hi[k] = s.sum ? shi[s.g] : hi[s.g * d.n_tpc + s.acc_ch];
+        r.off[k + 1] = r.off[k] + row_span(r.lo[k], r.hi[k], d.tw).len;
+    }
+    return r;
+}
+// n, mean + origin, min, max, sigma of n values with sum s1 and sum of squares s2 about `origin`; NaN for all but n when there are none
+void stat5(double *o, double n, double s1, double s2, double origin, i64 lo, i64 hi)
+{
+    const double mean = n > 0 ? s1 / n : 0, var = n > 0 ? s2 / n - mean * mean : 0;
+    o[0] = n; o[1] = n > 0 ? origin + mean : NAN;
+    o[2] = n > 0 ? (double)lo : NAN; o[3] = n > 0 ? (double)hi : NAN;
+    o[4] = n > 0 ? sqrt(var > 0 ? var : 0) : NAN;
+}
 
 // Brackets one kernel launch: HIP events when profiling is on; with wfs_set_debug bit 3 the launch is checked on the spot
 // (hipGetLastError + a stream synchronisation), so that a failed launch or a faulting kernel is reported under its own name
@@ -233,9 +290,6 @@ struct Timer {
     }
 };
 #define CHECK_LAUNCHES() do { if (!h->launch_err.empty()) { const std::string m_ = h->launch_err; h->launch_err.clear(); return h->fail(WFS_E_HIP, m_); } } while (0)
-
-// the last row slot of a window is its sum row when the switch is on (row_slot_is_sum on the device)
-inline bool slot_is_sum(const WfsDev &d, i32 slot) { return d.sum_channel >= 0 && slot == d.row_slots - 1; }
 
 // grid size for n items; never 0 (a launch with an empty grid is an error, every kernel bounds-checks its index)
 inline unsigned nblocks(i64 n, int tpb) { return n > 0 ? (unsigned)((n + tpb - 1) / tpb) : 1u; }
@@ -580,6 +634,7 @@ static int wfs_caught(wfs_handle *h, const char *fn) noexcept
     int code = WFS_E_INVALID; const char *what = "unknown C++ exception";
     char buf[256];
     try { throw; }
+    catch (const WfsHipError &e) { return e.code; }      // (download: the message is on the handle already)
     catch (const std::bad_alloc &) { code = WFS_E_NOMEM; what = "out of host memory (std::bad_alloc)"; }
     catch (const std::exception &e) { snprintf(buf, sizeof buf, "%s", e.what()); what = buf; }
     catch (...) {}
@@ -643,35 +698,30 @@ try {
     refresh_dev(h);
     if (const char *e = getenv("WFS_TAP_SPARSE_MAX")) h->tap_sparse_max = std::min(atoi(e), TAP_LIST_LEN - 1);      // tuning knob of tap_block (results do not depend on it)
     if (build_time_tables(h) != WFS_OK) return WFS_E_HIP;
-    // the pulse kernel stages up to 1024 start bins per tile: (10 * 1024 + 220) * 8 + 1024 * 4 bytes of LDS
-#define WFS_BIG_LDS(K, B) hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, (B) * 1024)
+    // dynamic-LDS caps: the LDS_CAP_ constants of wfs_layout.h, each checked there against the largest total of its kernel's layout
+#define WFS_BIG_LDS(K, B) hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, (B))
 #define WFS_BIG_LDS_F(KM, B) do { WFS_BIG_LDS(HIP_KERNEL_NAME(KM(true)), B); WFS_BIG_LDS(HIP_KERNEL_NAME(KM(false)), B); } while (0)
-    WFS_BIG_LDS_F(K_PULSE_256_RES, 100); WFS_BIG_LDS_F(K_PULSE_128_RES, 100); WFS_BIG_LDS_F(K_PULSE_256_WIN, 100); WFS_BIG_LDS_F(K_PULSE_128_WIN, 100);
-    hipFuncSetAttribute((const void *)k_photon_fill<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-    hipFuncSetAttribute((const void *)k_photon_fill<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-    hipFuncSetAttribute((const void *)k_photon_fill<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-    hipFuncSetAttribute((const void *)k_photon_fill<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-    hipFuncSetAttribute((const void *)k_tile_order_big, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-    WFS_BIG_LDS_F(K_PULSE_GENERIC, 128);
+    WFS_BIG_LDS_F(K_PULSE_256_RES, LDS_CAP_PULSE); WFS_BIG_LDS_F(K_PULSE_128_RES, LDS_CAP_PULSE); WFS_BIG_LDS_F(K_PULSE_256_WIN, LDS_CAP_PULSE); WFS_BIG_LDS_F(K_PULSE_128_WIN, LDS_CAP_PULSE);
+    WFS_BIG_LDS(HIP_KERNEL_NAME(k_photon_fill<false, false>), LDS_CAP_FILL); WFS_BIG_LDS(HIP_KERNEL_NAME(k_photon_fill<true, false>), LDS_CAP_FILL);
+    WFS_BIG_LDS(HIP_KERNEL_NAME(k_photon_fill<false, true>), LDS_CAP_FILL); WFS_BIG_LDS(HIP_KERNEL_NAME(k_photon_fill<true, true>), LDS_CAP_FILL);
+    WFS_BIG_LDS(k_tile_order_big, LDS_CAP_ORDER);
+    WFS_BIG_LDS_F(K_PULSE_GENERIC, LDS_CAP_GENERIC);
 #define K_ROW_PULSE_SEG(F) k_row_pulse<NK, F, true>
     for (int kind = 0; kind < NOISE_KINDS; kind++)           // every kind that with_noise_kind can launch
-        with_noise_kind(kind, [](auto nk) { constexpr int NK = decltype(nk)::value; WFS_BIG_LDS_F(K_ROW_PULSE_SEG, 128); });
+        with_noise_kind(kind, [](auto nk) { constexpr int NK = decltype(nk)::value; WFS_BIG_LDS_F(K_ROW_PULSE_SEG, LDS_CAP_ROW); });
     if (const char *e = getenv("WFS_ROW_RESIDENT")) h->res_env = atoi(e);          // 0 / 1 / 2 as the config switch (A/B runs)
-    if (const char *e = getenv("WFS_RES_MAX_LEN")) h->res_max_len = std::max(256, std::min(atoi(e), 7168)) / 256 * 256;      // tuning knob (results do not depend on it)
-    WFS_BIG_LDS_F(K_S2_TILE, 100); WFS_BIG_LDS_F(K_S2_TILE_AP, 100);
-    WFS_BIG_LDS_F(K_PULSE_SPARSE_64, 100); WFS_BIG_LDS_F(K_PULSE_SPARSE_256, 100);
+    if (const char *e = getenv("WFS_RES_MAX_LEN")) h->res_max_len = std::max(256, std::min(atoi(e), RES_MAX_LEN)) / 256 * 256;      // tuning knob (results do not depend on it)
+    WFS_BIG_LDS_F(K_S2_TILE, LDS_CAP_TILE); WFS_BIG_LDS_F(K_S2_TILE_AP, LDS_CAP_TILE);
+    WFS_BIG_LDS_F(K_PULSE_SPARSE, LDS_CAP_SPARSE);
     {   // k_s2_bright: what the device grants one workgroup, less the SPE row, the afterpulse stage and the kernel's static arrays
         int granted = 0;
         if (hipDeviceGetAttribute(&granted, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess || granted <= 0) granted = 64 * 1024;
-        const int rest = BRIGHT_SPE_BYTES + AP_STAGE * (int)sizeof(ApCand) + 2048;
-        h->bright_lds = std::max(0, std::min(BRIGHT_LDS_MAX, granted - rest)) / 16 * 16;
-        h->bright_max_bins = std::max(0, h->bright_lds / (WFS_DT * 8) - 2 * 21);
+        h->bright_lds = bright_lds_of_grant(granted);
+        h->bright_max_bins = bright_bins_of_lds(h->bright_lds);
         if (const char *e = getenv("WFS_BRIGHT_MAX_BINS")) h->bright_max_bins = std::max(0, std::min(atoi(e), h->bright_max_bins));      // tuning knob (results do not depend on it)
-        const int total = h->bright_lds + rest - 2048;
-        hipFuncSetAttribute((const void *)k_s2_bright<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, total);
-        hipFuncSetAttribute((const void *)k_s2_bright<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, total);
-        hipFuncSetAttribute((const void *)k_s2_bright<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, total);
-        hipFuncSetAttribute((const void *)k_s2_bright<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, total);
+        const int total = bright_lds_layout(h->bright_lds, true).total;      // (the AP forms: the largest layout)
+        WFS_BIG_LDS(HIP_KERNEL_NAME(k_s2_bright<false, false>), total); WFS_BIG_LDS(HIP_KERNEL_NAME(k_s2_bright<false, true>), total);
+        WFS_BIG_LDS(HIP_KERNEL_NAME(k_s2_bright<true, false>), total); WFS_BIG_LDS(HIP_KERNEL_NAME(k_s2_bright<true, true>), total);
     }
     *out = owner.release();
     return WFS_OK;
@@ -1234,7 +1284,7 @@ try {
         m.nb_idx = h->map_nb_idx[w].as<i64>(); m.nb_w = h->map_nb_w[w].as<double>();
         m.cdf_table = h->cdf_table.as<double>(); m.gains = h->t_gains.as<double>();
         launch_neighbours(h, m);
-        { Timer t(h, "k_map_rows"); hipLaunchKernelGGL(k_map_rows, dim3((unsigned)nr), dim3(256), (size_t)nch * 8, h->stream, m, nch); }
+        { Timer t(h, "k_map_rows"); hipLaunchKernelGGL(k_map_rows, dim3((unsigned)nr), dim3(256), (size_t)map_rows_lds(nch).total, h->stream, m, nch); }
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipGetLastError());
@@ -1541,7 +1591,7 @@ static int gen_electrons(wfs_handle *h, GenRun &r, FillGroup &fg)
         DiffArgs q{nr, m.row_ins, h->ins_sigr.as<double>(), h->ins_siga.as<double>(), h->batch.diff_r2, h->diff_pre.as<double>()};
         { Timer t(h, "k_diffuse_patterns"); hipLaunchKernelGGL(k_diffuse_patterns, dim3((unsigned)nr), dim3(256), 0, h->stream, d, g, m, q); }
         m.pre = h->diff_pre.as<double>();
-        { Timer t(h, "k_map_rows"); hipLaunchKernelGGL(k_map_rows, dim3((unsigned)nr), dim3(256), (size_t)d.n_tpc * 8, h->stream, m, d.n_tpc); }
+        { Timer t(h, "k_map_rows"); hipLaunchKernelGGL(k_map_rows, dim3((unsigned)nr), dim3(256), (size_t)map_rows_lds(d.n_tpc).total, h->stream, m, d.n_tpc); }
     }
     const i64 TP = r.TP = h->batch.n_psets * d.n_tpc;
     TRY(ensure(h, h->tile_count, (size_t)T * 4)); TRY(ensure(h, h->tile_cursor, (size_t)T * 4));
@@ -1656,7 +1706,7 @@ static int gen_block_photons(wfs_handle *h, GenRun &r)
             Timer t(h, "k_chan_alias"); hipLaunchKernelGGL(k_chan_alias, dim3((unsigned)n_rows), dim3(64), 0, h->stream, g.cdf_table, d.n_tpc, lg, h->chan_alias.as<uint2>());
         }
         if (g.gg_inv) { Timer t(h, "k_gg_sum"); hipLaunchKernelGGL(k_gg_sum, dim3(nb), dim3(256), 0, h->stream, d, g); }
-        { Timer t(h, "k_photon_count"); hipLaunchKernelGGL(k_photon_count, dim3(nbx), dim3(COUNT_TPB), GEN_COUNT_LDS(d.n_tpc, g.ch_lg), h->stream, d, g); }
+        { Timer t(h, "k_photon_count"); hipLaunchKernelGGL(k_photon_count, dim3(nbx), dim3(COUNT_TPB), (size_t)count_lds(d.n_tpc, g.ch_lg).total, h->stream, d, g); }
         { Timer t(h, "k_block_ranges"); hipLaunchKernelGGL(k_block_ranges, dim3(nblocks(TP, 256)), dim3(256), 0, h->stream, d, g); }
         TRY(scan_into(h, h->tile_count.as<i32>(), TP, h->tile_off.as<i64>(), &WfsScal::n_tile_photons, 0));
         const size_t gen_lds = (size_t)gen_fill_lds(d.n_tpc, g.ch_lg, ap_on).total;
@@ -1687,13 +1737,9 @@ static int gen_tile_photons(wfs_handle *h, GenRun &r)
         f.tile_off = h->tile_off.as<i64>(); f.tile_tmin = h->tile_tmin.as<i32>(); f.tile_tmax = h->tile_tmax.as<i32>(); f.tile_truth = h->tile_truth.as<double>();
         f.tbuf = h->tbuf.as<i32>(); f.ph = h->ph.as<PhotonRec>(); f.keep_ph = (h->debug_bits & DBG_KEEP_PHOTONS) ? 1 : 0;
         const TemplateArg tp = fill_template_arg(h);
-        // H table + the waves' counters; the exact form adds the tables of tap_block (the fused form gathers every sample densely)
-        size_t lds = (size_t)(WFS_TILE_CHUNK + d.tlen - 1) * d.dt * 8 + 4 * 4 * 4 + (h->cfg.fma ? 16 : TAP_LDS_BYTES(256) + 64);
-        lds = (lds + 15) / 16 * 16;
-        const int ap_lds_off = (int)lds;                         // afterpulse candidates of the tile (AP variants)
+        const size_t lds = (size_t)tile_lds(h->cfg.fma != 0, ap_on).total;
         const ApArgs *app = nullptr;
         if (ap_on) {
-            lds += (size_t)AP_STAGE * sizeof(ApCand);
             TRY(ensure(h, h->ap_seg, (size_t)n_tilegen_tiles(h) * sizeof(ApSeg))); ap.seg = h->ap_seg.as<ApSeg>(); ap.n_seg = n_tilegen_tiles(h);      // (one segment per tile of every class)
             f.n_ptiles = TP;
             TRY(upload(h, h->ap_args_dev, &ap, sizeof ap)); app = h->ap_args_dev.as<ApArgs>();      // (`ap` outlives the copy: read_scal of gen_afterpulses)
@@ -1704,20 +1750,20 @@ static int gen_tile_photons(wfs_handle *h, GenRun &r)
         if (h->run.n_fused_tiles > 0) {
             Timer t(h, "k_s2_tile");
             const dim3 grid((unsigned)h->run.n_fused_tiles);
-            if (ap_on) WFS_LAUNCH_F(h, K_S2_TILE_AP, grid, dim3(256), lds, d, f, tp, app, ap_lds_off);
-            else WFS_LAUNCH_F(h, K_S2_TILE, grid, dim3(256), lds, d, f, tp, app, ap_lds_off);
+            if (ap_on) WFS_LAUNCH_F(h, K_S2_TILE_AP, grid, dim3(256), lds, d, f, tp, app);
+            else WFS_LAUNCH_F(h, K_S2_TILE, grid, dim3(256), lds, d, f, tp, app);
         }
         if (h->run.n_gen_tiles > 0) {
             Timer t(h, "k_s2_tile_gen");
             const dim3 grid((unsigned)h->run.n_gen_tiles);
-            if (ap_on) hipLaunchKernelGGL(k_s2_tile_gen<true>, grid, dim3(256), (size_t)AP_STAGE * sizeof(ApCand), h->stream, d, f, app, (int)h->run.n_fused_tiles);
-            else hipLaunchKernelGGL(k_s2_tile_gen<false>, grid, dim3(256), 0, h->stream, d, f, app, (int)h->run.n_fused_tiles);
+            if (ap_on) hipLaunchKernelGGL(k_s2_tile_gen<true>, grid, dim3(256), (size_t)tile_gen_lds(true).total, h->stream, d, f, app, (int)h->run.n_fused_tiles);
+            else hipLaunchKernelGGL(k_s2_tile_gen<false>, grid, dim3(256), (size_t)tile_gen_lds(false).total, h->stream, d, f, app, (int)h->run.n_fused_tiles);
         }
         // tiles above 2048 photons whose H table fits the LDS as a whole: photons and pulse in one workgroup of 1024 threads, no photon array
         if (h->run.n_bright_tiles > 0) {
             Timer t(h, "k_s2_bright");
             const dim3 grid((unsigned)h->run.n_bright_tiles);
-            const size_t blds = (size_t)h->bright_lds + BRIGHT_SPE_BYTES + (ap_on ? (size_t)AP_STAGE * sizeof(ApCand) : 0);
+            const size_t blds = (size_t)bright_lds_layout(h->bright_lds, ap_on).total;
             const int seg_first = (int)(h->run.n_fused_tiles + h->run.n_gen_tiles);
             if (ap_on) WFS_LAUNCH_F(h, K_S2_BRIGHT_AP, grid, dim3(BRIGHT_TPB), blds, d, f, h->bright_args, tp, app, seg_first);
             else WFS_LAUNCH_F(h, K_S2_BRIGHT, grid, dim3(BRIGHT_TPB), blds, d, f, h->bright_args, tp, app, seg_first);
@@ -1771,7 +1817,7 @@ static int order_ranges(wfs_handle *h, const OrderArgs &oa)
     if (n_wave > 0) { Timer t(h, "k_tile_order"); hipLaunchKernelGGL(k_tile_order, dim3(nblocks(n_wave, 4)), dim3(256), 0, h->stream, oa, n_wave); }
     if (n_big > 0) {
         Timer t(h, "k_tile_order_big");
-        hipLaunchKernelGGL(k_tile_order_big, dim3((unsigned)n_big), dim3(256), (size_t)TILE_ORDER_MAX * 24, h->stream, oa);
+        hipLaunchKernelGGL(k_tile_order_big, dim3((unsigned)n_big), dim3(256), (size_t)order_lds(TILE_ORDER_MAX).total, h->stream, oa);
     }
     const i64 n_huge = h->h_scal->n_order_huge;
     if (n_huge > 0) {
@@ -2028,21 +2074,10 @@ static int run_pulses(wfs_handle *h, RunState &r)
     pa.tile_truth = h->tile_truth.as<double>();
     if ((h->debug_bits & DBG_CURRENTS) && h->run.n_active_tiles > 0) {
         // debug: tile lengths in work-list order -> offsets
-        std::vector<i32> at((size_t)h->run.n_active_tiles), tmn((size_t)T), tmx((size_t)T);
-        std::vector<i64> t0((size_t)S);
         HIPCHK(hipStreamSynchronize(h->stream));
-        HIPCHK(hipMemcpy(at.data(), h->active_tiles.p, at.size() * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(tmn.data(), h->tile_tmin.p, tmn.size() * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(tmx.data(), h->tile_tmax.p, tmx.size() * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(t0.data(), h->set_t0.p, t0.size() * 8, hipMemcpyDeviceToHost));
-        std::vector<i64> off(at.size() + 1, 0);
-        for (size_t k = 0; k < at.size(); k++) {
-            i64 set = at[k] / d.n_tpc;
-            i64 b0 = floordiv(t0[set] + tmn[at[k]], (i64)d.dt), b1 = floordiv(t0[set] + tmx[at[k]], (i64)d.dt);
-            off[k + 1] = off[k] + (b1 - b0 + 1) + tile_lead(d) + d.store_after + d.samples_after;
-        }
-        h->run.cur_total = off.back();
-        TRY(upload(h, h->cur_off, off.data(), off.size() * 8));
+        const ListedTiles lt = listed_tiles(h);
+        h->run.cur_total = lt.off.back();
+        TRY(upload(h, h->cur_off, lt.off.data(), lt.off.size() * 8));
         TRY(ensure(h, h->currents, (size_t)h->run.cur_total * 8));
         HIPCHK(hipStreamSynchronize(h->stream));
         pa.currents = h->currents.as<double>(); pa.cur_off = h->cur_off.as<i64>();
@@ -2073,24 +2108,19 @@ static int run_pulses(wfs_handle *h, RunState &r)
         ps.desc = h->tile_desc.as<TileDesc>() + r.first_sparse;
         if (ps.cur_off) ps.cur_off += r.first_sparse;
         ps.W = (int)((h->run.max_nb + 7) / 8 * 8); ps.NP = (int)((h->run.max_tile + 7) / 8 * 8);
-        const bool small = h->run.max_tile <= 256 && h->run.max_nb <= 256;
-        const int tpb = small ? 64 : 256;
-        size_t lds = (size_t)ps.NP * 12 + (size_t)8 * (tpb / 64) * 8 + ((size_t)d.dt * ps.W + 8) * 2 + 8 * 4 + std::max((size_t)d.dt * ps.W * 2, (size_t)1 * 260 * 8) + 16;
-        lds = (lds + 15) / 16 * 16;
+        // (tile_class lists a tile here with at most SPARSE_MAX_PHOTONS photons in at most SPARSE_MAX_BINS start bins: one form, 64 threads)
+        const size_t lds = (size_t)sparse_lds(ps.NP, ps.W, SPARSE_TPB).total;
         Timer t(h, "k_pulse_sparse");
-        if (small) WFS_LAUNCH_F(h, K_PULSE_SPARSE_64, dim3((unsigned)h->run.n_sparse_tiles), dim3(64), lds, d, ps);
-        else WFS_LAUNCH_F(h, K_PULSE_SPARSE_256, dim3((unsigned)h->run.n_sparse_tiles), dim3(256), lds, d, ps);
+        WFS_LAUNCH_F(h, K_PULSE_SPARSE, dim3((unsigned)h->run.n_sparse_tiles), dim3(SPARSE_TPB), lds, d, ps);
     }
     if (h->run.n_dense_tiles > 0 && h->generic_geom) {        // any digitiser geometry: one kernel for every tile
         PulseArgs pd = pa;
         pd.desc = h->tile_desc.as<TileDesc>() + r.first_dense;
         if (pd.cur_off) pd.cur_off += r.first_dense;
         // two H tables (order-independent merge of the gains of one cell) where they fit, one otherwise
-        const size_t h_bytes = (size_t)(256 + d.tlen - 1) * d.dt * 8, rest = (size_t)d.dt * d.tlen * 8 + 4 * 8 * 8 + 64;
-        pd.n_win = (2 * h_bytes + rest + 15) / 16 * 16 <= 128 * 1024 ? 1 : 0;
-        size_t lds = (pd.n_win ? 2 : 1) * h_bytes + rest;
-        lds = (lds + 15) / 16 * 16;
-        if (lds > 128 * 1024) return h->fail(WFS_E_CAPACITY, "sample_duration x template length too large for the LDS tables of k_pulse_generic");
+        pd.n_win = generic_lds_split(d.dt, d.tlen) ? 1 : 0;
+        const size_t lds = (size_t)generic_lds(d.dt, d.tlen, pd.n_win != 0).total;
+        if (lds > (size_t)LDS_CAP_GENERIC) return h->fail(WFS_E_CAPACITY, "sample_duration x template length too large for the LDS tables of k_pulse_generic");
         Timer t(h, "k_pulse_generic");
         WFS_LAUNCH_F(h, K_PULSE_GENERIC, dim3((unsigned)h->run.n_dense_tiles), dim3(256), lds, d, pd);
     } else if (h->run.n_dense_tiles > 0) {
@@ -2110,8 +2140,7 @@ static int run_pulses(wfs_handle *h, RunState &r)
         pd.n_win = resident ? 1 : (int)std::min<i64>(NWIN_MAX, std::max<i64>(1, (n_live_max + tpb - 1) / tpb));
         pd.W = tpb;
         const TemplateArg tp = fill_template_arg(h);
-        size_t lds = (size_t)(tpb + d.tlen - 1) * d.dt * 8 + (size_t)8 * (tpb / 64) * 8 + 64 + TAP_LDS_BYTES(256) + 16;
-        lds = (lds + 15) / 16 * 16;
+        const size_t lds = (size_t)pulse_lds(tpb).total;
         pd.sparse_max = (h->debug_bits & DBG_FORCE_DENSE) ? -1 : h->tap_sparse_max;      // (force_dense: every wave takes the dense gather)
         pd.spe_lds = ((size_t)(tpb + d.tlen - 1) * d.dt >= SPE_ROW_LEN) ? 1 : 0;
         const unsigned grid = (unsigned)(h->run.n_dense_tiles * pd.n_win);
@@ -2162,24 +2191,9 @@ static int run_rows(wfs_handle *h, RunState &r)
         za.n_short = h->run.n_short_rows; za.res_long = h->res_long.as<i32>(); za.res_rows = h->res_rows.as<ResRow>();
     }
     if ((h->debug_bits & DBG_CURRENTS) && h->run.n_active_rows > 0) {
-        std::vector<i32> ar((size_t)h->run.n_active_rows);
-        std::vector<i64> lo((size_t)CG * d.n_tpc), hi((size_t)CG * d.n_tpc);
-        HIPCHK(hipMemcpy(ar.data(), h->active_rows.p, ar.size() * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(lo.data(), h->row_lo.p, lo.size() * 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(hi.data(), h->row_hi.p, hi.size() * 8, hipMemcpyDeviceToHost));
-        std::vector<i64> slo, shi;
-        if (d.sum_channel >= 0) {
-            slo.resize((size_t)CG); shi.resize((size_t)CG);
-            HIPCHK(hipMemcpy(slo.data(), h->sum_lo.p, slo.size() * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(shi.data(), h->sum_hi.p, shi.size() * 8, hipMemcpyDeviceToHost));
-        }
-        std::vector<i64> off(ar.size() + 1, 0);
-        for (size_t k = 0; k < ar.size(); k++) {
-            i64 g = ar[k] / d.row_slots; i32 slot = (i32)(ar[k] - g * d.row_slots); i32 c = slot < d.n_tpc ? slot : slot - d.n_tpc;
-            if (slot_is_sum(d, slot)) off[k + 1] = off[k] + shi[g] - slo[g] + 1 + 2 * d.tw;
-            else off[k + 1] = off[k] + hi[g * d.n_tpc + c] - lo[g * d.n_tpc + c] + 1 + 2 * d.tw;
-        }
-        h->run.row_dbg_total = off.back();
-        TRY(upload(h, h->row_dbg_off, off.data(), off.size() * 8));
+        const ListedRows lr = listed_rows(h);
+        h->run.row_dbg_total = lr.off.back();
+        TRY(upload(h, h->row_dbg_off, lr.off.data(), lr.off.size() * 8));
         TRY(ensure(h, h->row_dbg, (size_t)h->run.row_dbg_total * 4));
         HIPCHK(hipStreamSynchronize(h->stream));
         za.row_dbg = h->row_dbg.as<i32>(); za.row_dbg_off = h->row_dbg_off.as<i64>();
@@ -2203,7 +2217,7 @@ static int run_rows(wfs_handle *h, RunState &r)
             const i64 first = part == 0 ? 0 : h->run.n_short_rows, n_rows = part == 0 ? h->run.n_short_rows : h->run.n_res_rows - h->run.n_short_rows;
             if (n_rows <= 0) continue;
             const i32 region = part == 0 ? RES_SHORT_LEN : (i32)((std::min<i64>(h->run.max_res_len, h->res_max_len) + 255) / 256 * 256);
-            const size_t lds = ROW_LDS_FIXED + (size_t)4 * region * 4;
+            const size_t lds = (size_t)row_pulse_lds(region).total;
             const dim3 grid(nblocks(n_rows, 4));
             with_noise_kind(r.noise_kind, [&](auto nk) {
                 constexpr int NK = decltype(nk)::value;
@@ -2248,7 +2262,7 @@ static int run_records(wfs_handle *h, RunState &r)
     // the other arena: the previous batch's records may still be on their way to the host
     h->rec_cur ^= 1;
     if (h->rec_pending[h->rec_cur]) { HIPCHK(hipEventSynchronize(h->rec_copied[h->rec_cur])); h->rec_pending[h->rec_cur] = false; }
-    TRY(ensure(h, h->records_buf(), (size_t)h->run.n_records * 244));
+    TRY(ensure(h, h->records_buf(), (size_t)h->run.n_records * WFS_RECORD_BYTES));
     za.rec_off = h->rec_off.as<i64>(); za.records = h->records_buf().as<uint8_t>(); za.rec_capacity = h->run.n_records;
     if (h->sort_records && h->run.n_records > 1 && h->run.n_active_rows > 0) {
         // records by (time, channel): keys per record, one radix sort of the batch, k_pack writes to the sorted slots
@@ -2332,7 +2346,7 @@ int wfs_copy_records(wfs_handle *h, void *dst, int64_t cap)
 try {
     if (!h || !run_finished(h)) return WFS_E_STATE;
     if (cap < h->run.n_records) return h->fail(WFS_E_CAPACITY, "record buffer too small");
-    if (h->run.n_records) HIPCHK(hipMemcpy(dst, h->records_buf().p, (size_t)h->run.n_records * 244, hipMemcpyDeviceToHost));
+    if (h->run.n_records) HIPCHK(hipMemcpy(dst, h->records_buf().p, (size_t)h->run.n_records * WFS_RECORD_BYTES, hipMemcpyDeviceToHost));
     return WFS_OK;
 } WFS_CATCH(h)
 
@@ -2340,7 +2354,7 @@ int wfs_copy_records_range(wfs_handle *h, void *dst, int64_t first, int64_t coun
 try {
     if (!h || !run_finished(h)) return WFS_E_STATE;
     if (first < 0 || count < 0 || first + count > h->run.n_records) return h->fail(WFS_E_INVALID, "record range outside the batch");
-    if (count) HIPCHK(hipMemcpy(dst, (const uint8_t *)h->records_buf().p + (size_t)first * 244, (size_t)count * 244, hipMemcpyDeviceToHost));
+    if (count) HIPCHK(hipMemcpy(dst, (const uint8_t *)h->records_buf().p + (size_t)first * WFS_RECORD_BYTES, (size_t)count * WFS_RECORD_BYTES, hipMemcpyDeviceToHost));
     return WFS_OK;
 } WFS_CATCH(h)
 
@@ -2359,7 +2373,7 @@ try {
     if (!h || !run_finished(h)) return WFS_E_STATE;
     if (first < 0 || count < 0 || first + count > h->run.n_records) return h->fail(WFS_E_INVALID, "record range outside the batch");
     HIPCHK(hipSetDevice(h->device));
-    if (count) HIPCHK(hipMemcpyAsync(dst, (const uint8_t *)h->records_buf().p + (size_t)first * 244, (size_t)count * 244, hipMemcpyDeviceToHost, h->copy_stream));
+    if (count) HIPCHK(hipMemcpyAsync(dst, (const uint8_t *)h->records_buf().p + (size_t)first * WFS_RECORD_BYTES, (size_t)count * WFS_RECORD_BYTES, hipMemcpyDeviceToHost, h->copy_stream));
     HIPCHK(hipEventRecord(h->rec_copied[h->rec_cur], h->copy_stream));
     h->rec_pending[h->rec_cur] = true;
     return WFS_OK;
@@ -2379,7 +2393,7 @@ int wfs_copy_records_dev(wfs_handle *h, void *dst, int64_t cap)
 try {
     if (!h || !run_finished(h)) return WFS_E_STATE;
     if (cap < h->run.n_records) return h->fail(WFS_E_CAPACITY, "record buffer too small");
-    if (h->run.n_records) { HIPCHK(hipMemcpyAsync(dst, h->records_buf().p, (size_t)h->run.n_records * 244, hipMemcpyDeviceToDevice, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); }
+    if (h->run.n_records) { HIPCHK(hipMemcpyAsync(dst, h->records_buf().p, (size_t)h->run.n_records * WFS_RECORD_BYTES, hipMemcpyDeviceToDevice, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); }
     return WFS_OK;
 } WFS_CATCH(h)
 
@@ -2409,21 +2423,16 @@ try {
     if (!h || !run_complete(h)) return WFS_E_STATE;
     const WfsDev &d = h->dev;
     const i64 RS = (h->batch.n_clusters + 1) * d.row_slots;
-    std::vector<i32> n((size_t)RS); std::vector<i64> off((size_t)RS + 1), L((size_t)h->run.n_itv_slots), R((size_t)h->run.n_itv_slots);
-    HIPCHK(hipMemcpy(n.data(), h->itv_n.p, n.size() * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(off.data(), h->itv_off.p, off.size() * 8, hipMemcpyDeviceToHost));
-    if (h->run.n_itv_slots) {
-        HIPCHK(hipMemcpy(L.data(), h->itv_left.p, L.size() * 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(R.data(), h->itv_right.p, R.size() * 8, hipMemcpyDeviceToHost));
-    }
+    const std::vector<i32> n = download<i32>(h, h->itv_n, (size_t)RS);
+    const std::vector<i64> off = download<i64>(h, h->itv_off, (size_t)RS + 1);
+    const std::vector<i64> L = download<i64>(h, h->itv_left, (size_t)h->run.n_itv_slots), R = download<i64>(h, h->itv_right, (size_t)h->run.n_itv_slots);
     i64 k = 0, doff = 0;
     for (i64 idx = 0; idx < RS; idx++) {
-        i64 g = idx / d.row_slots; i32 slot = (i32)(idx - g * d.row_slots);
-        i32 chn = slot_is_sum(d, slot) ? d.sum_channel : (slot < d.n_tpc ? slot : d.he_first + slot - d.n_tpc);
+        const RowSlot s = row_slot(d, idx);
         for (i32 q = 0; q < n[idx]; q++) {
             if (k >= cap) return h->fail(WFS_E_CAPACITY, "interval buffer too small");
             i64 l = L[off[idx] + q], r = R[off[idx] + q];
-            group[k] = (i32)g; channel[k] = chn; left[k] = l; right[k] = r; data_off[k] = doff;
+            group[k] = (i32)s.g; channel[k] = s.channel; left[k] = l; right[k] = r; data_off[k] = doff;
             doff += (r - l + 1 > 0) ? r - l + 1 : 0; k++;
         }
     }
@@ -2435,13 +2444,13 @@ int wfs_copy_interval_data(wfs_handle *h, int16_t *data, int64_t cap)
 try {
     // unpack the records: fragments of one interval are consecutive
     if (!h || !run_finished(h)) return WFS_E_STATE;
-    std::vector<uint8_t> rec((size_t)h->run.n_records * 244);
+    std::vector<uint8_t> rec((size_t)h->run.n_records * WFS_RECORD_BYTES);
     if (h->run.n_records) HIPCHK(hipMemcpy(rec.data(), h->records_buf().p, rec.size(), hipMemcpyDeviceToHost));
     i64 k = 0;
     for (i64 r = 0; r < h->run.n_records; r++) {
-        i32 len; memcpy(&len, &rec[(size_t)r * 244 + 8], 4);
+        i32 len; memcpy(&len, &rec[(size_t)r * WFS_RECORD_BYTES + 8], 4);
         if (k + len > cap) return h->fail(WFS_E_CAPACITY, "interval data buffer too small");
-        memcpy(data + k, &rec[(size_t)r * 244 + 24], (size_t)len * 2);
+        memcpy(data + k, &rec[(size_t)r * WFS_RECORD_BYTES + 24], (size_t)len * 2);
         k += len;
     }
     return WFS_OK;
@@ -2453,20 +2462,13 @@ try {
     const WfsDev &d = h->dev;
     const i64 A = h->run.n_active_tiles;
     if (cap < A) return h->fail(WFS_E_CAPACITY, "pulse buffer too small");
-    std::vector<i32> at((size_t)A), cnt((size_t)h->batch.n_tiles), tmn((size_t)h->batch.n_tiles), tmx((size_t)h->batch.n_tiles);
-    std::vector<i64> t0((size_t)h->batch.n_sets);
-    if (A) HIPCHK(hipMemcpy(at.data(), h->active_tiles.p, at.size() * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(cnt.data(), h->tile_count.p, cnt.size() * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(tmn.data(), h->tile_tmin.p, tmn.size() * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(tmx.data(), h->tile_tmax.p, tmx.size() * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(t0.data(), h->set_t0.p, t0.size() * 8, hipMemcpyDeviceToHost));
-    i64 off = 0;
+    const ListedTiles lt = listed_tiles(h);
+    const std::vector<i32> cnt = download<i32>(h, h->tile_count, (size_t)h->batch.n_tiles);
     for (i64 k = 0; k < A; k++) {
-        i64 tile = at[k], s = tile / d.n_tpc;
-        i64 b0 = floordiv(t0[s] + tmn[tile], (i64)d.dt), b1 = floordiv(t0[s] + tmx[tile], (i64)d.dt);
+        const i64 tile = lt.tile[k], s = tile / d.n_tpc;
         set[k] = (i32)s; channel[k] = (i32)(tile - s * d.n_tpc);
-        left[k] = b0 - d.store_before - d.samples_before; right[k] = b1 + d.store_after + d.samples_after;
-        nph[k] = cnt[tile]; cur_off[k] = off; off += right[k] - left[k] + 1;
+        left[k] = lt.win[k].left; right[k] = lt.win[k].right;
+        nph[k] = cnt[tile]; cur_off[k] = lt.off[k];
     }
     return WFS_OK;
 } WFS_CATCH(h)
@@ -2487,25 +2489,15 @@ try {
     const WfsDev &d = h->dev;
     const i64 A = h->run.n_active_rows;
     if (cap < A) return h->fail(WFS_E_CAPACITY, "row buffer too small");
-    std::vector<i32> ar((size_t)A); std::vector<i64> lo((size_t)(h->batch.n_clusters + 1) * d.n_tpc), hi(lo.size()), gl((size_t)h->run.n_groups);
-    if (A) HIPCHK(hipMemcpy(ar.data(), h->active_rows.p, ar.size() * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(lo.data(), h->row_lo.p, lo.size() * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(hi.data(), h->row_hi.p, hi.size() * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(gl.data(), h->grp_left.p, gl.size() * 8, hipMemcpyDeviceToHost));
-    std::vector<i64> slo, shi;
-    if (d.sum_channel >= 0) {
-        slo.resize((size_t)h->batch.n_clusters + 1); shi.resize(slo.size());
-        HIPCHK(hipMemcpy(slo.data(), h->sum_lo.p, slo.size() * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(shi.data(), h->sum_hi.p, shi.size() * 8, hipMemcpyDeviceToHost));
-    }
-    i64 off = 0;
+    const ListedRows lr = listed_rows(h);
+    const std::vector<i64> gl = download<i64>(h, h->grp_left, (size_t)h->run.n_groups);
     for (i64 k = 0; k < A; k++) {
-        i64 g = ar[k] / d.row_slots; i32 slot = (i32)(ar[k] - g * d.row_slots); i32 c = slot < d.n_tpc ? slot : slot - d.n_tpc;
-        const bool sum = slot_is_sum(d, slot);
-        group[k] = (i32)g; channel[k] = sum ? d.sum_channel : (slot < d.n_tpc ? slot : d.he_first + c);
+        const RowSlot &s = lr.slot[k];
+        group[k] = (i32)s.g; channel[k] = s.channel;
         // relative to the window like the reference's channel mask (rawdata.py:258-259)
-        if (sum) { left[k] = slo[g] - gl[g] - d.tw; right[k] = shi[g] - gl[g] + d.tw; }
-        else { left[k] = lo[g * d.n_tpc + c] - gl[g] - d.tw; right[k] = hi[g * d.n_tpc + c] - gl[g] + d.tw; }
-        data_off[k] = off; off += right[k] - left[k] + 1;
+        const RowSpan sp = row_span(lr.lo[k] - gl[s.g], lr.hi[k] - gl[s.g], d.tw);
+        left[k] = sp.left; right[k] = sp.right;
+        data_off[k] = lr.off[k];
     }
     return WFS_OK;
 } WFS_CATCH(h)
@@ -2559,15 +2551,12 @@ static int gen_order_tables(wfs_handle *h)
 {
     if (h->run.gen_order_ready) return WFS_OK;
     const i64 N = h->batch.n_ins; const int nch = h->dev.n_tpc;
-    std::vector<i64> emo((size_t)N + 1), epo((size_t)h->batch.n_emitters + 1);
-    HIPCHK(hipMemcpy(emo.data(), h->em_off.p, emo.size() * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(epo.data(), h->em_ph_off.p, epo.size() * 8, hipMemcpyDeviceToHost));
+    const std::vector<i64> emo = download<i64>(h, h->em_off, (size_t)N + 1), epo = download<i64>(h, h->em_ph_off, (size_t)h->batch.n_emitters + 1);
     h->run.go_fused.assign((size_t)N, 0); h->run.go_tile_count.clear();
     const bool any_fused = h->run.fuse_on && n_tilegen_tiles(h) > 0;
     if (any_fused) {
-        HIPCHK(hipMemcpy(h->run.go_fused.data(), h->ins_fused.p, (size_t)N * 4, hipMemcpyDeviceToHost));
-        h->run.go_tile_count.resize((size_t)N * nch);
-        HIPCHK(hipMemcpy(h->run.go_tile_count.data(), h->tile_count.p, h->run.go_tile_count.size() * 4, hipMemcpyDeviceToHost));      // (one pulse set per instruction: tile = instruction * n_tpc + channel)
+        h->run.go_fused = download<i32>(h, h->ins_fused, (size_t)N);
+        h->run.go_tile_count = download<i32>(h, h->tile_count, (size_t)N * nch);      // (one pulse set per instruction: tile = instruction * n_tpc + channel)
     }
     h->run.go_off.assign((size_t)N + 1, 0); h->run.go_block0.assign((size_t)N, 0);
     for (i64 i = 0; i < N; i++) {
@@ -2637,17 +2626,11 @@ try {
     if (!h || !run_finished(h)) return WFS_E_STATE;
     const i64 S = h->batch.n_sets;
     if (cap < S) return h->fail(WFS_E_CAPACITY, "truth buffer too small");
-    std::vector<double> tr((size_t)S * 16); std::vector<i64> mm((size_t)S * 2), t0((size_t)S);
-    HIPCHK(hipMemcpy(tr.data(), h->truth.p, tr.size() * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(mm.data(), h->tminmax.p, mm.size() * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(t0.data(), h->set_t0.p, t0.size() * 8, hipMemcpyDeviceToHost));
+    const std::vector<double> tr = download<double>(h, h->truth, (size_t)S * 16);
+    const std::vector<i64> mm = download<i64>(h, h->tminmax, (size_t)S * 2), t0 = download<i64>(h, h->set_t0, (size_t)S);
     for (i64 s = 0; s < S; s++) {
         for (int f = 0; f < 12; f++) acc12[s * 12 + f] = tr[s * 16 + f];
-        double n = tr[s * 16 + 12], st = tr[s * 16 + 13], st2 = tr[s * 16 + 14];
-        double mean = n > 0 ? st / n : 0, var = n > 0 ? st2 / n - mean * mean : 0;
-        tstat5[s * 5 + 0] = n; tstat5[s * 5 + 1] = n > 0 ? (double)t0[s] + mean : NAN;
-        tstat5[s * 5 + 2] = n > 0 ? (double)mm[2 * s] : NAN; tstat5[s * 5 + 3] = n > 0 ? (double)mm[2 * s + 1] : NAN;
-        tstat5[s * 5 + 4] = n > 0 ? sqrt(var > 0 ? var : 0) : NAN;
+        stat5(tstat5 + s * 5, tr[s * 16 + 12], tr[s * 16 + 13], tr[s * 16 + 14], (double)t0[s], mm[2 * s], mm[2 * s + 1]);
     }
     return WFS_OK;
 } WFS_CATCH(h)
@@ -2657,10 +2640,8 @@ try {
     if (!h || !run_finished(h)) return WFS_E_STATE;
     const i64 S = h->batch.n_sets, nch = h->cfg.n_tpc, T = S * nch;
     if (cap < S) return h->fail(WFS_E_CAPACITY, "per-PMT truth buffer too small");
-    std::vector<double> tt((size_t)T * 8); std::vector<i32> cnt((size_t)T); std::vector<double> gains((size_t)nch);
-    HIPCHK(hipMemcpy(tt.data(), h->tile_truth.p, tt.size() * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(cnt.data(), h->tile_count.p, cnt.size() * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(gains.data(), h->t_gains.p, gains.size() * 8, hipMemcpyDeviceToHost));
+    const std::vector<double> tt = download<double>(h, h->tile_truth, (size_t)T * 8), gains = download<double>(h, h->t_gains, (size_t)nch);
+    const std::vector<i32> cnt = download<i32>(h, h->tile_count, (size_t)T);
     for (i64 t = 0; t < T; t++) {
         double *o = acc6 + t * 6;
         if (cnt[t] <= 0) { for (int q = 0; q < 6; q++) o[q] = 0.0; continue; }     // tiles without photons were never written
@@ -2678,10 +2659,8 @@ try {
     const i64 PS = h->batch.n_psets;
     if (cap < PS) return h->fail(WFS_E_CAPACITY, "electron stats buffer too small");
     if (N == 0) return WFS_OK;
-    std::vector<double> st((size_t)N * 4); std::vector<i64> mm((size_t)N * 2), t0((size_t)N);
-    HIPCHK(hipMemcpy(st.data(), h->el_stat.p, st.size() * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(mm.data(), h->el_minmax.p, mm.size() * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(t0.data(), h->ins_time.p, t0.size() * 8, hipMemcpyDeviceToHost));
+    const std::vector<double> st = download<double>(h, h->el_stat, (size_t)N * 4);
+    const std::vector<i64> mm = download<i64>(h, h->el_minmax, (size_t)N * 2), t0 = download<i64>(h, h->ins_time, (size_t)N);
     for (i64 q = 0; q < PS; q++) {
         // moments of the electrons of all instructions of the run set (rawdata.py:334-341), about the first instruction's time
         const i64 ref = h->batch.h_rs_off[q + 1] > h->batch.h_rs_off[q] ? t0[h->batch.h_rs_list[h->batch.h_rs_off[q]]] : 0;      // (an unused set number: no instructions, zero electrons)
@@ -2693,10 +2672,7 @@ try {
             n += ni; s1 += a1 + ni * dlt; s2 += a2 + 2 * dlt * a1 + ni * dlt * dlt;
             lo = std::min(lo, mm[2 * i]); hi = std::max(hi, mm[2 * i + 1]);
         }
-        double mean = n > 0 ? s1 / n : 0, var = n > 0 ? s2 / n - mean * mean : 0;
-        estat5[q * 5 + 0] = n; estat5[q * 5 + 1] = n > 0 ? (double)ref + mean : NAN;
-        estat5[q * 5 + 2] = n > 0 ? (double)lo : NAN; estat5[q * 5 + 3] = n > 0 ? (double)hi : NAN;
-        estat5[q * 5 + 4] = n > 0 ? sqrt(var > 0 ? var : 0) : NAN;
+        stat5(estat5 + q * 5, n, s1, s2, (double)ref, lo, hi);
     }
     return WFS_OK;
 } WFS_CATCH(h)

@@ -176,25 +176,13 @@ struct GeomArgs {
     i64 *sum_lo, *sum_hi; i32 *sum_len, *sum_nchunk;
 };
 
-#define SPARSE_MAX_PHOTONS 32      // tiles with a handful of photons (S1-like) go to the sorted-list kernel
-#define SPARSE_MAX_BINS 64
-#define TINY_MAX_PHOTONS 4         // tiles of a few photons in a few start bins (the bulk of an S1): one THREAD per tile
+// (SPARSE_MAX_PHOTONS, SPARSE_MAX_BINS, the class of the sorted-list kernel, and RES_SHORT_LEN: wfs_layout.h, which sizes LDS by them)
+#define TINY_MAX_PHOTONS 4        // tiles of a few photons in a few start bins (the bulk of an S1): one THREAD per tile
 #define TINY_MAX_BINS 32
 #define TINY_LANES 16              // lanes that share the samples of one tiny tile (k_pulse_tiny)
 #define WAVE_MAX_PHOTONS 64        // medium tiles: photons fit the lanes of one wave (any width): k_pulse_wave
 #define WAVE_MAX_BINS 16384
 #define RES_MAX_TILE_VISITS 256      // a resident row longer than the LDS of its wave: tiles x segments it may cost
-#define RES_SHORT_LEN 768          // resident rows up to this length: 4 waves x 3 KB of LDS per workgroup, eight workgroups per CU
-
-__device__ __forceinline__ void tile_bounds(const WfsDev &d, i64 t0, i32 tmin, i32 tmax, i64 &left, i64 &right, i64 &bin0, i64 &nb)
-{
-    // pulse.py:118-127
-    bin0 = floordiv(t0 + tmin, (i64)d.dt);
-    i64 bin1 = floordiv(t0 + tmax, (i64)d.dt);
-    nb = bin1 - bin0 + 1;
-    left = bin0 - d.store_before - d.samples_before;
-    right = bin1 + d.store_after + d.samples_after;
-}
 
 // work lists and maxima: aggregated per workgroup in LDS, then one global atomic per workgroup and counter
 // (76k wave-level atomics on one cache line cost ~3 ms; the counters all live in the same line of WfsScal)
@@ -240,9 +228,9 @@ __global__ void k_tile_geom(WfsDev d, GeomArgs a)
     int cls = 2; i64 nb = 0; i32 cnt = 0; i32 cl = -1; i64 end = I64_MIN;      // class 0 tiny, 1 sparse, 2 dense, 3 wave (medium)
     if (live) {
         const i64 set = tile / d.n_tpc;
-        i64 left, right, bin0;
-        tile_bounds(d, a.set_t0[set], a.tile_tmin[tile], a.tile_tmax[tile], left, right, bin0, nb);
-        cl = a.set_cluster[set]; end = right * d.dt;
+        const TileWindow w = tile_window(d, a.set_t0[set], a.tile_tmin[tile], a.tile_tmax[tile]);
+        nb = w.nb;
+        cl = a.set_cluster[set]; end = w.right * d.dt;
         cnt = a.tile_count[tile];
         cls = tile_class(a, cnt, nb);
         if (a.tile_done && tile < a.n_done && a.tile_done[tile]) cls = -1;      // its pulse exists already (k_s2_tile): no work list
@@ -327,8 +315,8 @@ __global__ void k_tile_rows(WfsDev d, GeomArgs a)
     i64 left = I64_MAX, right = I64_MIN, g = -1; bool bottom = false;
     if (live) {
         i64 set = tile / d.n_tpc; i32 ch = (i32)(tile - set * d.n_tpc);
-        i64 bin0, nb;
-        tile_bounds(d, a.set_t0[set], a.tile_tmin[tile], a.tile_tmax[tile], left, right, bin0, nb);
+        const TileWindow w = tile_window(d, a.set_t0[set], a.tile_tmin[tile], a.tile_tmax[tile]);
+        left = w.left; right = w.right; const i64 nb = w.nb;
         g = a.cl_group[a.set_cluster[set]];
         bottom = a.sum_lo && ch >= d.n_top && ch <= d.last_bottom;      // the row feeds the window's sum row (rawdata.py:250-254)
         atomicMin(&a.row_lo[g * d.n_tpc + ch], left); atomicMax(&a.row_hi[g * d.n_tpc + ch], right);
@@ -389,9 +377,8 @@ __global__ void k_group_final(WfsDev d, GeomArgs a)
     a.grp_ixrand[g] = ix;
 }
 
-// the last row slot of a window is its bottom-array sum row when the switch is on (wfs_set_sum_signal)
+// the last row slot of a window is its bottom-array sum row when the switch is on (wfs_set_sum_signal; row_slot_is_sum, wfs_layout.h)
 #define SUM_CHUNK 1024             // samples of a sum row per workgroup of k_sum_signal
-__device__ __forceinline__ bool row_slot_is_sum(const WfsDev &d, i32 slot) { return d.sum_channel >= 0 && slot == d.row_slots - 1; }
 
 __device__ __forceinline__ bool row_is_direct(const i32 *tile_done, i64 n_done, const i32 *row_cnt, const i32 *row_tile, i64 ridx)
 {
@@ -586,13 +573,12 @@ __global__ void k_tile_desc(WfsDev d, DescArgs a)
     const i64 tile = a.list[i];
     const i64 set = tile / d.n_tpc; const i32 ch = (i32)(tile - set * d.n_tpc);
     const i64 t0 = a.set_t0[set];
-    i64 left, right, bin0, nb;
-    tile_bounds(d, t0, a.tile_tmin[tile], a.tile_tmax[tile], left, right, bin0, nb);
+    const TileWindow w = tile_window(d, t0, a.tile_tmin[tile], a.tile_tmax[tile]);
     const i64 ridx = (i64)a.cl_group[a.set_cluster[set]] * d.n_tpc + ch;
     TileDesc t;
-    t.off = a.tile_off[tile]; t.dst = a.acc_off[ridx] + (left - (a.row_lo[ridx] - d.tw)); t.rel0 = bin0 * d.dt - t0;
+    t.off = a.tile_off[tile]; t.dst = a.acc_off[ridx] + (w.left - (a.row_lo[ridx] - d.tw)); t.rel0 = w.bin0 * d.dt - t0;
     t.G = d.gains[ch]; t.thr = d.thr_truth[ch];
-    t.n = a.tile_count[tile]; t.nb = (i32)nb; t.L = (i32)(right - left + 1); t.tile = (i32)tile;
+    t.n = a.tile_count[tile]; t.nb = (i32)w.nb; t.L = (i32)w.L; t.tile = (i32)tile;
     t.ch = ch; t.mode = a.set_mode[set];
     a.desc[i] = t;
 }
@@ -630,15 +616,13 @@ __device__ __forceinline__ double tap_gather(const double *H, const TemplateArg 
 // outside the reach of its sample) and adds the product with a separate multiply and add -- the additions of the dense gather in
 // the same order minus the additions of +0.0, hence the same bits (pulse.py:303-318).  W2[k * dt + (dt - 1 - r)] = templates[r][k].
 // A cell counts as occupied when the high word of its merged gain is non-zero (any gain of at least 2^-1022).
-#define TAP_W2_LEN (22 * WFS_DT + 2)
-#define TAP_LIST_LEN 64                // entries of a wave's list (unsigned short): one per lane
-#define TAP_LDS_BYTES(tpb) (TAP_W2_LEN * 8 + ((tpb) / 64) * TAP_LIST_LEN * 2)
+// (TAP_W2_LEN taps, TAP_LIST_LEN entries of a wave's list: wfs_layout.h)
 __device__ __forceinline__ void tap_w2_fill(double *W2, const double *templates, int tid, int tpb)
 {
     constexpr int dt = WFS_DT, tlen = 22;
     for (int i = tid; i < TAP_W2_LEN; i += tpb) W2[i] = i < tlen * dt ? templates[(dt - 1 - i % dt) * tlen + i / dt] : 0.0;
 }
-// W2 is followed by the waves' lists: [TAP_W2_LEN doubles][tpb / 64][TAP_LIST_LEN] unsigned short
+// W2 is followed by the waves' lists: [TAP_W2_LEN doubles][tpb / 64][TAP_LIST_LEN] unsigned short (tap_lds_bytes, wfs_layout.h)
 // n_cells: the cells of H that hold data (the caller may have cleared only the rows its live samples can see)
 template <bool FMA>
 __device__ __forceinline__ double tap_block(const double *H, double *W2, const TemplateArg &tp, int tid, int sparse_max, int n_cells)
@@ -648,6 +632,7 @@ __device__ __forceinline__ double tap_block(const double *H, double *W2, const T
     if (sparse_max < 0) return tap_gather<FMA>(H, tp, tid);
     const double *Hw = H + (tid & ~63) * dt;            // first cell of the wave's reach
     const u32 *Hhi = (const u32 *)Hw + 1;               // high words
+    static_assert(TAP_LISTS_OFF == TAP_W2_LEN * 8, "the lists follow W2");
     unsigned short *list = (unsigned short *)(W2 + TAP_W2_LEN) + (tid >> 6) * TAP_LIST_LEN;
     const u64 below = (1ull << lane) - 1ull;
     const int c_end = min(REACH, n_cells - (tid & ~63) * dt);      // cells of the reach that hold data
@@ -704,10 +689,12 @@ __global__ __launch_bounds__(TPB) void k_pulse(WfsDev d, PulseArgs a, TemplateAr
     // The live samples of a tile (sample s' = s - lead sees the start bins s' - 21 .. s') are worked off in chunks of TPB
     // consecutive samples, one per thread; a chunk needs the TPB + tlen - 1 start bins from 21 before its first sample on.
     constexpr int HROWS = TPB + tlen - 1;
-    double *H = (double *)smem;                           // [HROWS][dt]: merged gain per (start bin, ns remainder)
-    double *red = H + (size_t)HROWS * dt;                 // [TPB / 64][8]
-    u32 *wsum = (u32 *)(red + 8 * (TPB / 64));            // [16]
-    double *W2 = (double *)(wsum + 16);                   // [TAP_W2_LEN] taps by time difference + the waves' records (tap_block)
+    constexpr PulseLds o = pulse_lds(TPB);
+    static_assert(tlen == TILE_TLEN, "the layout is sized for 22 taps");
+    double *H = (double *)(smem + o.H);                   // [HROWS][dt]: merged gain per (start bin, ns remainder)
+    double *red = (double *)(smem + o.red);               // [TPB / 64][8]
+    u32 *wsum = (u32 *)(smem + o.wsum);                   // [16]
+    double *W2 = (double *)(smem + o.W2);                 // [TAP_W2_LEN] taps by time difference + the waves' records (tap_block)
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     // pulse.py:32 current_max, indexed per photon: from LDS (indexing the kernarg copy per lane becomes a global load)
     __shared__ double s_cmax[WFS_DT];
@@ -942,8 +929,7 @@ __global__ __launch_bounds__(TPB) void k_pulse(WfsDev d, PulseArgs a, TemplateAr
 // separate multiply and add, templates read from LDS.  One workgroup per tile, chunks of TPB samples, the tile's photons re-read per
 // chunk; none of the specialisations of the 10 ns / 22 tap kernels (they keep the taps in SGPRs and unroll over dt): this is the
 // path of every tile when the configuration differs from the XENONnT TPC digitiser.  Same bits as the reference (add_current).
-#define WFS_MAX_DT 16
-#define WFS_MAX_TLEN 256
+// (WFS_MAX_DT, WFS_MAX_TLEN: wfs_layout.h)
 template <int TPB, bool FMA>
 __global__ __launch_bounds__(TPB) void k_pulse_generic(WfsDev d, PulseArgs a)
 {
@@ -954,12 +940,14 @@ __global__ __launch_bounds__(TPB) void k_pulse_generic(WfsDev d, PulseArgs a)
     // not depend on it, every gain is split at a power of two `grid` (2^-20 of the tile's largest gain): the multiples of grid add up
     // EXACTLY in H (below 2^53 grid for any photon number), the remainders (below grid / 2) in Hlo, and the cell is their sum, rounded
     // once -- for one or two photons numpy's value bit for bit (pulse.py:313), for more the correctly rounded sum up to 2^-23 n ulp.
-    double *H = (double *)smem;                           // [HROWS][dt]
     // (a.n_win == 0: geometries whose two tables would not fit the LDS keep one table and the plain atomic merge)
     const bool split = a.n_win != 0;
-    double *Hlo = H + (size_t)HROWS * dt;                 // [HROWS][dt]
-    double *T = H + (size_t)HROWS * dt * (split ? 2 : 1); // [dt][tlen] templates
-    double *red = T + (size_t)dt * tlen;                  // [TPB / 64][8]
+    static_assert(TPB == 256, "generic_lds is the layout of the 256-thread form");
+    const GenericLds o = generic_lds(dt, tlen, split);
+    double *H = (double *)(smem + o.H);                   // [HROWS][dt]
+    double *Hlo = (double *)(smem + o.Hlo);               // [HROWS][dt] (split)
+    double *T = (double *)(smem + o.T);                   // [dt][tlen] templates
+    double *red = (double *)(smem + o.red);               // [TPB / 64][8]
     __shared__ double s_cmax[WFS_MAX_DT];
     const int tid = threadIdx.x, lane = tid & 63;
     for (int i = tid; i < dt * tlen; i += TPB) T[i] = d.templates[i];
@@ -1162,17 +1150,17 @@ __global__ void k_tile_assign(WfsDev d, GeomArgs a, DescArgs da, PulseArgs pa)
     if (live) {
         const i64 set = tile / d.n_tpc; const i32 ch = (i32)(tile - set * d.n_tpc);
         const i64 t0 = a.set_t0[set];
-        i64 left, right, bin0;
-        tile_bounds(d, t0, a.tile_tmin[tile], a.tile_tmax[tile], left, right, bin0, nb);
+        const TileWindow w = tile_window(d, t0, a.tile_tmin[tile], a.tile_tmax[tile]);
+        nb = w.nb;
         cnt = a.tile_count[tile];
         const i64 ridx = (i64)a.cl_group[a.set_cluster[set]] * d.n_tpc + ch;
         const i64 first = a.res_toff[ridx];
         if (a.res_toff[ridx + 1] > first) {
             const i32 k = atomicSub(&a.res_cnt[ridx], 1) - 1;          // (the scan has consumed the counts: they serve as the rows' cursors)
             TileDesc t;
-            t.off = da.tile_off[tile]; t.dst = left - (a.row_lo[ridx] - d.tw); t.rel0 = bin0 * d.dt - t0;
+            t.off = da.tile_off[tile]; t.dst = w.left - (a.row_lo[ridx] - d.tw); t.rel0 = w.bin0 * d.dt - t0;
             t.G = d.gains[ch]; t.thr = d.thr_truth[ch];
-            t.n = cnt; t.nb = (i32)nb; t.L = (i32)(right - left + 1); t.tile = (i32)tile;
+            t.n = cnt; t.nb = (i32)nb; t.L = (i32)w.L; t.tile = (i32)tile;
             t.ch = ch; t.mode = da.set_mode[set];
             if (cnt <= TINY_MAX_PHOTONS && nb <= TINY_MAX_BINS) {       // (the tiny class of the work lists: the same tiles, the same order of their truth sums)
                 // a handful of photons: everything that does not depend on the sample is done here, one LANE per tile (sorted and merged
@@ -1222,8 +1210,8 @@ __global__ __launch_bounds__(256) void k_pulse_tiny(WfsDev d, PulseArgs a, i64 n
 // reach adds templates[r][k] * gain with a separate multiply and add, in ascending time: the arithmetic of add_current
 // (pulse.py:276-318), the same bits as the other kernels.
 struct __attribute__((aligned(16))) WavePhoton { i32 bin, row; double g; };       // start bin, first tap of its template row in sTz, merged gain
-#define PW_U 2
-#define WAVE_TZ_LEN (WFS_DT * (22 + 2))
+static_assert(sizeof(WavePhoton) == WAVE_PHOTON_BYTES, "row_pulse_lds sizes the waves' lists by it");
+// (PW_U, WAVE_TZ_LEN: wfs_layout.h)
 __device__ __forceinline__ void wave_tables_fill(const WfsDev &d, double *sTz, double *s_cmax)      // (every thread of the workgroup; a barrier follows)
 {
     constexpr int dt = WFS_DT, tlen = 22;
@@ -1356,8 +1344,7 @@ __global__ __launch_bounds__(256) void k_pulse_wave(WfsDev d, PulseArgs a, i64 n
 // photons of equal ns are merged (first of the run gets the summed gain, the others 0.0, which add nothing) --
 // i.e. the sorted, merged photon list add_current walks (pulse.py:297-318) -- and every sample gathers its
 // contributions from the contiguous slice of that list in ascending time.  Same bits as the dense kernel.
-#define SPARSE_PPT 16      // photons per thread held in registers: tile photons <= TPB * SPARSE_PPT
-
+// (SPARSE_PPT photons per thread held in registers, tile photons <= TPB * SPARSE_PPT: wfs_layout.h)
 template <int TPB, bool FMA>
 __global__ __launch_bounds__(TPB) void k_pulse_sparse(WfsDev d, PulseArgs a)
 {
@@ -1365,14 +1352,15 @@ __global__ __launch_bounds__(TPB) void k_pulse_sparse(WfsDev d, PulseArgs a)
     const int tlen = d.tlen; constexpr int dt = WFS_DT;      // sample_duration is 10 ns (checked by wfs_create)
     // T replicas: 8 copies of the templates, rows padded to tlen + 2 with a zero tap on either side, copies offset by
     // 4 bank pairs so that the 64 lanes' data-dependent template reads spread over the LDS banks
-    constexpr int TROW = 24, TREP = 260, NREP = 1;       // requires tlen == 22 (tiny tiles: bank conflicts do not matter)
-    double *cg = (double *)smem;                         // [NP] merged gain of the sorted photons
-    double *red = cg + a.NP;                             // [TPB / 64][8]
-    i32 *ctoff = (i32 *)(red + 8 * (TPB / 64));          // [NP] r * TROW - start bin
-    unsigned short *boff = (unsigned short *)(ctoff + a.NP);           // [dt * W + 2] exclusive offsets
-    u32 *wsum = (u32 *)(boff + ((dt * a.W + 2 + 3) & ~3));             // [TPB / 64]
-    u32 *cnt = wsum + 8;                                 // [dt * W / 2] packed u16 pairs: photons per ns ...
-    double *Trep = (double *)cnt;                        // ... later reused for [NREP][TREP] template copies
+    constexpr int TROW = 24, TREP = SPARSE_TREP, NREP = 1;       // requires tlen == 22 (tiny tiles: bank conflicts do not matter)
+    const SparseLds o = sparse_lds(a.NP, a.W, TPB);
+    double *cg = (double *)(smem + o.cg);                // [NP] merged gain of the sorted photons
+    double *red = (double *)(smem + o.red);              // [TPB / 64][8]
+    i32 *ctoff = (i32 *)(smem + o.ctoff);                // [NP] r * TROW - start bin
+    unsigned short *boff = (unsigned short *)(smem + o.boff);          // [dt * W + 2] exclusive offsets
+    u32 *wsum = (u32 *)(smem + o.wsum);                  // [TPB / 64]
+    u32 *cnt = (u32 *)(smem + o.cnt);                    // [dt * W / 2] packed u16 pairs: photons per ns ...
+    double *Trep = (double *)(smem + o.cnt);             // ... later reused for [NREP][TREP] template copies: one region, sized for the larger
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     __shared__ double s_cmax[WFS_DT];                    // pulse.py:32 current_max (see k_pulse)
     if (tid < WFS_DT) s_cmax[tid] = d.current_max[tid];
@@ -1596,20 +1584,21 @@ __global__ void k_row_desc(WfsDev d, ZleArgs a)
     if (r >= a.n_active_rows) return;
     // row list order: accumulator rows | short resident rows (from the end of active_rows backwards, k_row_len) | long resident rows
     const i64 idx = r < a.n_front ? a.active_rows[r] : (r < a.n_front + a.n_short ? a.active_rows[a.rows_cap - 1 - (r - a.n_front)] : a.res_long[r - a.n_front - a.n_short]);
-    const i64 g = idx / d.row_slots; const i32 slot = (i32)(idx - g * d.row_slots);
-    if (row_slot_is_sum(d, slot)) {
+    const RowSlot rs = row_slot(d, idx);
+    const i64 g = rs.g;
+    if (rs.sum) {
         // the window's sum row: an accumulator row (src 0) behind the accumulators proper, times int(he_factor) when it is finished
         // like an HE row (rawdata.py:242, 251-254), noise column and threshold of the sum channel
         RowDesc q;
         q.acc_off = a.sum_base + a.sum_off[g]; q.row_abs = a.sum_lo[g] - d.tw; q.ixr = a.grp_ixrand[g]; q.itv_base = a.itv_off[idx];
-        q.thr = d.thr_zle[d.sum_channel]; q.idx = idx; q.len = (i32)(a.sum_hi[g] - a.sum_lo[g] + 1 + 2 * (i64)d.tw);
-        q.channel = d.sum_channel; q.he = 1; q.src = 0;
+        q.thr = d.thr_zle[rs.channel]; q.idx = idx; q.len = (i32)row_span(a.sum_lo[g], a.sum_hi[g], d.tw).len;
+        q.channel = rs.channel; q.he = 1; q.src = 0;
         a.desc[r] = q;
         if (a.key_base) { atomicMin(&a.key_base->key_origin, q.row_abs); atomicMax(&a.key_base->key_end, q.row_abs + (i64)q.len); }
         return;
     }
-    const bool he = slot >= d.n_tpc; const i32 acc_ch = he ? slot - d.n_tpc : slot, channel = he ? d.he_first + acc_ch : slot;
-    const i64 ridx = g * d.n_tpc + acc_ch;
+    const bool he = rs.he; const i32 channel = rs.channel;
+    const i64 ridx = g * d.n_tpc + rs.acc_ch;
     RowDesc q;
     q.acc_off = a.acc_off[ridx]; q.row_abs = a.row_lo[ridx] - d.tw; q.ixr = a.grp_ixrand[g]; q.itv_base = a.itv_off[idx];
     q.src = 0;
@@ -1622,7 +1611,7 @@ __global__ void k_row_desc(WfsDev d, ZleArgs a)
         const i32 tile = a.row_tile[ridx]; const i32 ins = tile / d.n_tpc;
         q.acc_off = a.ins_boff[ins] + (i64)(tile - ins * d.n_tpc) * a.ins_bcap[ins]; q.src = 1;
     }
-    q.thr = d.thr_zle[channel]; q.idx = idx; q.len = (i32)(a.row_hi[ridx] - a.row_lo[ridx] + 1 + 2 * (i64)d.tw);
+    q.thr = d.thr_zle[channel]; q.idx = idx; q.len = (i32)row_span(a.row_lo[ridx], a.row_hi[ridx], d.tw).len;
     q.channel = channel; q.he = he ? 1 : 0;
     a.desc[r] = q;
     if (a.key_base) { atomicMin(&a.key_base->key_origin, q.row_abs); atomicMax(&a.key_base->key_end, q.row_abs + (i64)q.len); }
@@ -1913,13 +1902,6 @@ __global__ __launch_bounds__(256) void k_noise_white_samples(WfsDev d, i32 row, 
     out[s] = (int16_t)alias_sample(st.tab, m == 0 ? a.x : (m == 1 ? a.y : (m == 2 ? a.z : a.w)));      // (word_of, written out: the call costs this kernel four registers)
 }
 
-// (acc_ch -1: the window's sum row, which has no accumulator row of a channel behind it)
-__device__ __forceinline__ void row_of_slot(const WfsDev &d, i64 idx, i64 &g, i32 &channel, i32 &acc_ch, bool &he)
-{
-    g = idx / d.row_slots; i32 slot = (i32)(idx - g * d.row_slots);
-    if (row_slot_is_sum(d, slot)) { he = true; acc_ch = -1; channel = d.sum_channel; return; }
-    he = slot >= d.n_tpc; acc_ch = he ? slot - d.n_tpc : slot; channel = he ? d.he_first + acc_ch : slot;
-}
 
 // NK, the noise of the batch, is a template parameter of the row kernels (NoiseKind of wfs_noise.h; 0: none, 1: int16 table, 2: float64
 // table, 3: the noise model, drawn where the tables are loaded, 4: the coloured model, drawn at the same places, 5: the same with the
@@ -2304,14 +2286,14 @@ __global__ __launch_bounds__(256) void k_sum_signal(WfsDev d, SumArgs a)
 // (noise, baseline, clamp: rawdata.py:398-458), runs the zero-length encoding on them and writes them ONCE, as 16-bit samples.
 // Against the accumulator path (memset 4 B + atomics + 6 B read by k_zle + 6 B read by k_pack per sample) a row costs 2 B of noise
 // read and 2 B written here and 2 B read by k_pack.  rawdata.py:231-239 (per-pulse rounding into the row), :302-311 (intervals).
-#define ROW_LDS_FIXED ((WAVE_TZ_LEN + 16) * 8 + 4 * (64 + PW_U) * 16)
 template <int NK, bool FMA, bool SEG>
 __global__ __launch_bounds__(256) void k_row_pulse(WfsDev d, PulseArgs a, ZleArgs z, i64 first, i64 n_res, i32 region)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char row_lds[];
-    double *sTz = (double *)row_lds; double *s_cmax = sTz + WAVE_TZ_LEN;
-    WavePhoton *s_ph = (WavePhoton *)(s_cmax + 16);
-    i32 *s_acc = (i32 *)(s_ph + 4 * (64 + PW_U));
+    constexpr RowLds o = row_pulse_lds(0);                      // (the offsets do not depend on the region, which comes last)
+    double *sTz = (double *)(row_lds + o.sTz); double *s_cmax = (double *)(row_lds + o.cmax);
+    WavePhoton *s_ph = (WavePhoton *)(row_lds + o.ph);
+    i32 *s_acc = (i32 *)(row_lds + o.acc);
     wave_tables_fill(d, sTz, s_cmax);
     __syncthreads();
     const int lane = threadIdx.x & 63, w = wave_in_block();
@@ -2856,11 +2838,7 @@ __device__ __forceinline__ int channel_from_cdf(const double *cdf, int n, double
     return lo < n ? lo : n - 1;
 }
 
-#ifndef GEN_LOG
-#define GEN_LOG 11
-#endif
-#define GEN_BLOCK (1 << GEN_LOG)   // photons per block of the generator
-#define GEN_WIN 512                // emitter offsets staged in LDS per block
+// (GEN_LOG, GEN_BLOCK photons per block of the generator, GEN_WIN emitter offsets staged in LDS per block: wfs_layout.h)
 
 // Guide of a non-decreasing CDF row: cell j = int(u * scale), clamped to AP_GUIDE - 1, holds a bracket [lo, hi] of "the first entry >= u"
 // for every u of the cell (built on the host from the row itself with a margin on either side of the cell, wfs_set_ap_element): the
@@ -2913,7 +2891,7 @@ struct ApArgs {
     struct ApSeg *seg; i64 n_seg;   // candidates of a k_s2_tile workgroup: one contiguous, key-ordered stretch of the list per tile (k_ap_seg)
     struct ApCand *cand;            // [cap] candidates of the generator (k_ap_finish turns entry i into afterpulse photon i, or a hole: ap_ch[i] = -1)
 };
-#define AP_STAGE 128               // afterpulse candidates a block parks in LDS (48 bytes each; a block of 2048 photons has ~60)
+// (AP_STAGE afterpulse candidates a block parks in LDS: wfs_layout.h)
 
 // first and last emitter of every photon block: one bisection per thread, all in flight together (a block doing
 // its own two bisections serially costs ~20 us of dependent HBM latency before its 2048 photons can start)
@@ -2978,6 +2956,7 @@ __global__ void k_set_bases(GenArgs a)
 // candidate, which with p ~ 1 % per element is most of the time; behind the loop, once per block, it still kept the block's LDS
 // and its eight mostly idle waves on the CU for tens of microseconds (fill pass 5.1 -> 2.7 ms -> see DESIGN.md for the last step).
 struct __attribute__((aligned(8))) ApCand { i64 itime; u32 x; i32 ins, ch, t; u32 key, j, m, gid; i32 e_dpe, pad; };     // (48 bytes)
+static_assert(sizeof(ApCand) == AP_CAND_BYTES, "the layouts size the afterpulse stage by it");
 struct ApStage { i32 *n; ApCand *cand; };
 struct ApSeg { i64 base; i32 n, tile; };     // list entries [base, base + n) belong to afterpulse tile `tile`
 #define AP_SEG_MARK (1 << 30)                // in ApCand.ins / ap_ins: the entry belongs to a segment (k_ap_seg places it, k_ap_count / k_ap_place skip it)
@@ -3392,7 +3371,7 @@ __global__ void k_map_spline(SplineArgs a)
 __global__ __launch_bounds__(256) void k_map_rows(MapArgs m, int nch)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    double *p = (double *)smem;                    // [nch]
+    double *p = (double *)(smem + map_rows_lds(nch).p);      // [nch]
     __shared__ double s_part[4]; __shared__ double s_sum;
     const i64 r = blockIdx.x; const int tid = threadIdx.x;
     double w[MAP_K]; i64 idx[MAP_K]; double wsum = 0;
@@ -3598,15 +3577,14 @@ __global__ __launch_bounds__(256) void k_gg_sum(WfsDev d, GenArgs a)
     }
 }
 
-#define GEN_COUNT_LDS(nch, lg) ((size_t)(8u << (lg)) + (size_t)(nch) * 4)
-
 __global__ __launch_bounds__(COUNT_TPB) void k_photon_count(WfsDev d, GenArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int nch = d.n_tpc, tid = threadIdx.x;
     const int lg = a.ch_lg, K = 1 << lg;
-    uint2 *A = (uint2 *)smem;                                       // [K] alias cells of the instruction's channel row
-    i32 *hist = (i32 *)(smem + (size_t)K * 8);                      // [nch]
+    const CountLds o = count_lds(nch, lg);
+    uint2 *A = (uint2 *)(smem + o.A);                               // [K] alias cells of the instruction's channel row
+    i32 *hist = (i32 *)(smem + o.hist);                             // [nch]
     const i64 vb = block_of_workgroup(a);
     if (vb >= a.n_blocks) return;                            // block-uniform (padding of the XCD order)
     const BlockDesc bd = a.blk_desc[vb];                     // block-uniform: scalar loads
@@ -3637,28 +3615,7 @@ __global__ __launch_bounds__(COUNT_TPB) void k_photon_count(WfsDev d, GenArgs a)
     }
 }
 
-// LDS layout of the fill pass (byte offsets; plain integer offsets: a pointer that went through an integer cast loses its
-// LDS address space)
-struct GenFillLds { int wtime, T, hist, cur, hmin, hmax, hoff, chmap, pidx, stage, ap, total; };
-__host__ __device__ inline GenFillLds gen_fill_lds(int nch, int lg, bool with_ap)
-{
-    const int nch1 = nch + 1 + ((nch + 1) & 1);              // even: keeps what follows 8-byte aligned
-    GenFillLds o;
-    o.wtime = GEN_WIN * 4;                                    // win i32[GEN_WIN] at 0: first photon of the block's emitters, relative to the block
-    o.T = o.wtime + GEN_WIN * 4;                              // wtime i32[GEN_WIN]: emitter times relative to the set's origin
-    o.hist = o.T + (8 << lg);                                 // T: uint2[2^lg] alias cells of the channel row; hist i32[nch1]: photons per channel, then their prefix sums
-    o.cur = o.hist + nch1 * 4;                                // i32[nch]: rank counters
-    o.hmin = o.cur + nch * 4;                                 // i32[nch], i32[nch]: earliest / latest photon of the block per channel
-    o.hmax = o.hmin + nch * 4;
-    o.hoff = o.hmax + nch * 4;                                // i32[nch]: slot of bucket position 0 of every channel, relative to the set's first photon
-    o.chmap = o.hoff + nch * 4;                               // u16[GEN_BLOCK]: channel of every bucket position
-    o.pidx = o.chmap + GEN_BLOCK * 2;                         // u16[GEN_BLOCK]: block-relative photon index of every bucket position
-    o.stage = (o.pidx + GEN_BLOCK * 2 + 7) & ~7;              // PhotonRec[GEN_BLOCK]: the block's photons in bucket order
-    o.ap = o.stage + GEN_BLOCK * 8;                           // afterpulse staging
-    o.total = ((o.ap + (with_ap ? AP_STAGE * (int)sizeof(ApCand) : 0) + 7) & ~7) + 16;
-    return o;
-}
-
+// (LDS layout of the fill pass: gen_fill_lds, wfs_layout.h)
 // EXT: delay tables per instruction and array (model variants), S1 optical propagation term
 template <bool AP, bool EXT>
 __global__ __launch_bounds__(FILL_TPB) void k_photon_fill(WfsDev d, GenArgs a, ApArgs ap)
@@ -3986,7 +3943,7 @@ __global__ __launch_bounds__(256) void k_ap_seg(WfsDev d, GenArgs a, ApArgs ap, 
 // generator beyond 4096 photons: S2s of 10^5 electrons with a gain spread or inside run sets -- go on a third list and through a
 // segmented radix sort over (order key, position) pairs (k_order_huge_pack / rocPRIM / k_order_huge_apply, wfs_engine.hip).
 // Explicit gains (afterpulses) move along.
-#define TILE_ORDER_MAX 4096
+// (TILE_ORDER_MAX: wfs_layout.h)
 #define TILE_ORDER_INLINE 12        // ranges up to this many photons are sorted by the scanning thread itself
 struct OrderRange { i64 start; i32 n, pad; };          // photons [start, start + n) of the photon array
 struct OrderArgs { i64 n_tiles, n_ptiles; const i32 *tile_count; const i64 *tile_off; PhotonRec *ph; u32 *ph_idx; double *ph_gain; i64 gain_first;
@@ -4106,10 +4063,13 @@ __global__ __launch_bounds__(256) void k_tile_order(OrderArgs a, i64 n_list)
 __global__ __launch_bounds__(256) void k_tile_order_big(OrderArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    u64 *key = (u64 *)smem;                                  // [npow2] key << 32 | position
     const OrderRange rg = a.big_list[blockIdx.x];
     const i32 n = rg.n; const i64 off = rg.start;
     int np2 = 128; while (np2 < n) np2 <<= 1;
+    // (the carve is written out: taking the offsets from order_lds(np2) costs the kernel a scalar register; the asserts tie the two)
+    static_assert(order_lds(128).key == 0 && order_lds(128).rec == 128 * sizeof(u64) && order_lds(128).gain == order_lds(128).rec + 128 * sizeof(PhotonRec)
+                  && order_lds(128).total == order_lds(128).gain + 128 * sizeof(double), "k_tile_order_big carves [key | rec | gain] of np2 entries each");
+    u64 *key = (u64 *)smem;                                  // [np2] key << 32 | position (np2 <= TILE_ORDER_MAX, which the launch reserves for)
     const int tid = threadIdx.x;
     for (int i = tid; i < np2; i += 256) key[i] = i < n ? ((u64)a.ph_idx[off + i] << 32) | (u32)i : ~0ull;
     __syncthreads();
