@@ -15,17 +15,17 @@ of an interval differ from each other, and a record read one sample off is a dif
 """
 import numpy as np
 
-# The dispatch constants of the HIP back end, mirrored HERE and nowhere else in the tests, with the line they come from.
-CHUNK = 64                  # ZleFast: "only the first hit of a 64-sample chunk can open an interval" (wfs_kernels.h:1706-1746); 64 slots per flush (:1719-1724)
-BLOCK = 256                 # samples per wave load of k_zle's fast path, the step of the scalar noise start (wfs_kernels.h:1808-1810)
-TRIP = 1024                 # G = 4 blocks per trip of k_zle's fast path (wfs_kernels.h:1795)
-FAST_HOLD = 63              # ZleFast / resident rows need a hold-off of at least this (wfs_kernels.h:1792, wfs_engine.hip run_geometry: res_on)
-NOISE_MIN_FAST = 512        # shortest table of the fast row loads and of resident rows (wfs_device.h:221, wfs_engine.hip run_geometry: res_on)
-NOISE_PAD = 4               # a noise row is followed by its own first samples (wfs_device.h:219)
-WFS_SPR = 110               # samples per record (wfs_device.h:220)
-PACK_U = 4                  # records in flight in k_pack (wfs_kernels.h:2180)
+# The dispatch constants of the HIP back end, mirrored HERE and nowhere else in the tests, with the place they come from.
+CHUNK = 64                  # ZleFast (wfs_kernels.h): "only the first hit of a 64-sample chunk can open an interval"; 64 slots per flush (ZleFast::close)
+BLOCK = 256                 # samples per wave load of k_zle's fast path, the step of the scalar noise start (k_zle: fetch, noise_advance)
+TRIP = 1024                 # G = 4 blocks per trip of k_zle's fast path (k_zle: G)
+FAST_HOLD = 63              # ZleFast / resident rows need a hold-off of at least this (wfs_rows.h ZLE_FAST_HOLD: k_zle's dispatch, wfs_engine.hip run_geometry: res_on)
+NOISE_MIN_FAST = 512        # shortest table of the fast row loads and of resident rows (wfs_rows.h NOISE_MIN_FAST, wfs_engine.hip run_geometry: res_on)
+NOISE_PAD = 4               # a noise row is followed by its own first samples (wfs_device.h NOISE_PAD)
+WFS_SPR = 110               # samples per record (wfs_rows.h WFS_SPR)
+PACK_U = 4                  # records in flight in k_pack (k_pack: PACK_U)
 RES_SEGMENTS = (1024, 256)  # resident segment: wfs_handle::res_max_len and WFS_RES_MAX_LEN=256 (wfs_engine.hip wfs_create)
-RES_SHORT_LEN = 768         # resident rows up to this length take the short launch (wfs_kernels.h:187)
+RES_SHORT_LEN = 768         # resident rows up to this length take the short launch (wfs_layout.h RES_SHORT_LEN)
 SEAMS = (64, 256, 512, 768, 1024, 2048)          # chunk, block / 256-sample segment, RES_SHORT_LEN, trip / 1024-sample segment, second trip
 
 GROUP_SPACING = 10_000_000  # ns between windows: far above right_raw_extension plus the longest designed row

@@ -11,6 +11,7 @@
 #include <stdint.h>
 #include "wfs_noise.h"       // NoiseKind, the NC_ / NS_ constants of the coloured model and its slow levels
 #include "wfs_layout.h"      // the sizes the LDS layouts are made of (WFS_DT, WFS_MAX_CH, SPE_ROW_LEN, ..), floordiv, the window rules
+#include "wfs_rows.h"        // the rules of the back end of a row: ZLE intervals, records, the noise index, the finished sample
 
 typedef long long i64;
 typedef unsigned long long u64;
@@ -239,11 +240,8 @@ __host__ __device__ __forceinline__ i64 floormod(i64 a, i64 b) { i64 m = a % b; 
 
 // A lane of k_zle reads 4 consecutive noise samples from any start below noise_len: every channel row of the device copy is
 // followed by its own first NOISE_PAD samples, so the read never meets the wrap (rawdata.py:433-434 indexes modulo noise_len).
+// (WFS_SPR, WFS_RECORD_BYTES and NOISE_MIN_FAST: wfs_rows.h)
 constexpr int NOISE_PAD = 4;
-constexpr int WFS_SPR = 110;                   // samples per strax record (strax DEFAULT_RECORD_LENGTH; a compile-time constant: the divisions by it are in every row kernel)
-constexpr int WFS_RECORD_BYTES = 24 + 2 * WFS_SPR;       // one packed raw_record: 24 bytes of header, the samples (strax_interface.py:391-436)
-static_assert(WFS_RECORD_BYTES == 244, "the record layout of include/wfsim_amd.h");
-constexpr int NOISE_MIN_FAST = 512;            // shortest noise table of the fast row kernels (a block of 256 samples wraps at most once)
 
 // The device scalar block: counters that kernels bump with atomics, totals that the scans write, the error code, the origin of
 // the record sort keys.  wfs_run clears it at the start of a batch; the host copies it back (read_scal) and sizes the next stage

@@ -1972,7 +1972,7 @@ static int run_geometry(wfs_handle *h, RunState &r)
     const i64 p_all = n_primary_photons(h) - (h->run.fuse_full ? h->run.p_fused : 0) + h->run.n_ap_photons;
     const bool res_auto = T > 0 && p_all >= 2 * T;
     const int res_mode = h->res_env >= 0 ? h->res_env : h->cfg.row_resident;
-    h->run.res_on = (res_mode == 2 ? res_auto : res_mode != 0) && !(h->debug_bits & (DBG_CURRENTS | DBG_FORCE_DENSE)) && !h->generic_geom && !d.he_rows && 2 * (i64)d.tw + 1 >= 63
+    h->run.res_on = (res_mode == 2 ? res_auto : res_mode != 0) && !(h->debug_bits & (DBG_CURRENTS | DBG_FORCE_DENSE)) && !h->generic_geom && !d.he_rows && zle_holdoff(d.tw) >= ZLE_FAST_HOLD
                 && (!d.enable_noise || d.nm_cells || d.noise_len >= NOISE_MIN_FAST);
     if (tiles_done || h->run.res_on) {
         TRY(ensure(h, h->row_cnt, (size_t)CG * d.n_tpc * 4)); TRY(ensure(h, h->row_tile, (size_t)CG * d.n_tpc * 4));
@@ -2448,9 +2448,9 @@ try {
     if (h->run.n_records) HIPCHK(hipMemcpy(rec.data(), h->records_buf().p, rec.size(), hipMemcpyDeviceToHost));
     i64 k = 0;
     for (i64 r = 0; r < h->run.n_records; r++) {
-        i32 len; memcpy(&len, &rec[(size_t)r * WFS_RECORD_BYTES + 8], 4);
+        i32 len; memcpy(&len, &rec[(size_t)r * WFS_RECORD_BYTES + REC_LENGTH_BYTE], 4);
         if (k + len > cap) return h->fail(WFS_E_CAPACITY, "interval data buffer too small");
-        memcpy(data + k, &rec[(size_t)r * WFS_RECORD_BYTES + 24], (size_t)len * 2);
+        memcpy(data + k, &rec[(size_t)r * WFS_RECORD_BYTES + REC_DATA_BYTE], (size_t)len * 2);
         k += len;
     }
     return WFS_OK;
@@ -2714,9 +2714,9 @@ try {
     i64 k = 0, doff = 0;
     for (i64 g = 0; g < G; g++) {
         if (lo[g] == I64_MAX) continue;
-        const i64 len = hi[g] - lo[g] + 1 + 2 * (i64)d.tw;
+        const RowSpan sp = row_span(lo[g], hi[g], d.tw); const i64 len = sp.len;
         if (k >= cap_rows || doff + len > cap_samples) return h->fail(WFS_E_CAPACITY, "sum signal buffer too small");
-        group[k] = (i32)g; left[k] = lo[g] - d.tw; right[k] = hi[g] + d.tw; data_off[k] = doff;
+        group[k] = (i32)g; left[k] = sp.left; right[k] = sp.right; data_off[k] = doff;
         for (i64 i = 0; i < len; i++) data[doff + i] = (i64)acc[(size_t)(off[g] + i)] * d.he_factor;
         doff += len; k++;
     }

@@ -406,16 +406,14 @@ __global__ void k_row_len(WfsDev d, GeomArgs a)
             // the sum row spans the union of the window's bottom rows (rawdata.py:234-235, 258-259); an accumulator row like any other,
             // filled by k_sum_signal in SUM_CHUNK samples per workgroup
             if (lo != I64_MAX) {
-                const i64 len = a.sum_hi[g] - lo + 1 + 2 * (i64)d.tw;
-                i64 hold = 2 * (i64)d.tw + 1; if (hold < 1) hold = 1;
-                cap = (i32)((len + hold) / (hold + 1));
+                const i64 len = row_span(lo, a.sum_hi[g], d.tw).len;
+                cap = (i32)zle_slots(len, zle_holdoff(d.tw));
                 a.sum_len[g] = (i32)len; a.sum_nchunk[g] = (i32)((len + SUM_CHUNK - 1) / SUM_CHUNK);
                 rk = atomicAdd(&s_n, 1);
             }
         } else if (lo != I64_MAX) {
-            const i64 len = a.row_hi[g * d.n_tpc + ch] - lo + 1 + 2 * (i64)d.tw;
-            i64 hold = 2 * (i64)d.tw + 1; if (hold < 1) hold = 1;
-            cap = (i32)((len + hold) / (hold + 1));
+            const i64 len = row_span(lo, a.row_hi[g * d.n_tpc + ch], d.tw).len;
+            cap = (i32)zle_slots(len, zle_holdoff(d.tw));
             // a row made by ONE tile whose samples exist already (k_s2_tile) is read from the tile's buffer: no accumulators
             const bool direct = row_is_direct(a.tile_done, a.n_done, a.row_cnt, a.row_tile, g * d.n_tpc + ch);
             // a short row of small tiles is made in LDS by one wave (k_row_pulse): no accumulators either, 16-bit finished samples instead
@@ -424,7 +422,7 @@ __global__ void k_row_len(WfsDev d, GeomArgs a)
                        && (len <= a.res_max_len || (i64)a.row_cnt[g * d.n_tpc + ch] * ((len + a.res_max_len - 1) / a.res_max_len) <= RES_MAX_TILE_VISITS);
             if (slot < d.n_tpc) {
                 a.acc_len[g * d.n_tpc + ch] = (direct || resident) ? 0 : (i32)len; if (direct) atomicAdd(&s_direct, (i32)len);
-                if (a.res_on) { a.fin_len[g * d.n_tpc + ch] = resident ? (i32)((len + 3) & ~(i64)3) : 0; a.res_cnt[g * d.n_tpc + ch] = resident ? a.row_cnt[g * d.n_tpc + ch] : 0; }
+                if (a.res_on) { a.fin_len[g * d.n_tpc + ch] = resident ? fin_padded_len((i32)len) : 0; a.res_cnt[g * d.n_tpc + ch] = resident ? a.row_cnt[g * d.n_tpc + ch] : 0; }
                 if (resident) { atomicMax(&s_maxres, (i32)len); atomicAdd(&s_reslen, (i32)len); longrow = len > RES_SHORT_LEN; }
             }
             if (slot < d.n_tpc && !resident && a.row_cnt && a.row_cnt[g * d.n_tpc + ch] > 1) atomicAdd(&s_shared, 1);
@@ -1906,24 +1904,8 @@ __global__ __launch_bounds__(256) void k_noise_white_samples(WfsDev d, i32 row, 
 // NK, the noise of the batch, is a template parameter of the row kernels (NoiseKind of wfs_noise.h; 0: none, 1: int16 table, 2: float64
 // table, 3: the noise model, drawn where the tables are loaded, 4: the coloured model, drawn at the same places, 5: the same with the
 // slow levels added to every stream, which goes wherever kind 4 goes).  row_abs, the row's first absolute sample, is what kinds 3, 4
-// and 5 count from.
+// and 5 count from.  The finished sample itself -- finish_value, and finish_resident of k_row_pulse -- is a rule of wfs_rows.h.
 //
-// The finished sample of a row: accumulated ADC (times the HE factor, rawdata.py:242-246) + noise + baseline, clamped at 0
-// (rawdata.py:398-458 add_noise / add_baseline / digitizer_saturation, fused into the read).  nz: the integer noise of kinds 1, 3, 4, 5;
-// nzf: that of kind 2, added in floating point -- numba's int64 += float64 stores the TRUNCATED SUM, not the sum with the truncated
-// noise.  noisy false (a row outside the table, wave-uniform): the tables' value was read from row 0 and is dropped here; the drawn
-// kinds hand in 0.
-template <int NK>
-__device__ __forceinline__ i32 finish_value(const WfsDev &d, i32 acc, bool he, bool noisy, i32 nz, double nzf)
-{
-    i64 v = acc;
-    if (he) v *= d.he_factor;
-    if constexpr (NK == 1) v += noisy ? nz : 0;
-    if constexpr (NK == 2) { const i64 w = (i64)((double)v + nzf); v = noisy ? w : v; }
-    if constexpr (NK >= 3) v += nz;
-    v += d.baseline;
-    return v < 0 ? 0 : (i32)v;
-}
 // Sample i of a row in one step, its noise fetched behind a branch: the general paths of k_zle and k_pack
 template <int NK>
 __device__ __forceinline__ i32 finish_sample(const WfsDev &d, const i32 *acc, i64 i, i32 slot_ch, bool he, i64 ix_rand, i64 row_abs)
@@ -1962,13 +1944,12 @@ template <int NK>
 __device__ __forceinline__ RawSample<NK> load_sample(const WfsDev &d, const i32 *acc, i32 i, const void *noise_row, u32 nstart, u32 noff, i32 channel = 0, i64 row_abs = 0)
 {
     // (32-bit offsets from wave-uniform row pointers: the address arithmetic is one add per load, the bases stay in SGPRs)
-    // noise sample nstart + noff of the row, nstart < noise_len a scalar, noff < noise_len: one conditional subtraction wraps it
+    // noise sample nstart + noff of the row, nstart < noise_len a scalar, noff < noise_len (noise_wrap)
     RawSample<NK> s; s.acc = acc[(u32)i];
     if constexpr (NK == 3) s.nz = noise_row ? noise_model_sample(d, (const uint2 *)noise_row, channel, row_abs + i) : 0;      // (wave-uniform)
     else if constexpr (NK == 4 || NK == 5) s.nz = noise_row ? noise_colour_sample<NK == 5>(d, channel, row_abs + i) : 0;
     else if constexpr (NK != 0) {
-        u32 in = nstart + noff;
-        in = in >= (u32)d.noise_len ? in - (u32)d.noise_len : in;
+        const u32 in = noise_wrap(nstart + noff, (u32)d.noise_len);
         if constexpr (NK == 2) s.nzf = ((const double *)noise_row)[in]; else s.nz = ((const int16_t *)noise_row)[in];
     }
     return s;
@@ -1999,8 +1980,7 @@ __device__ __forceinline__ void noise_four(const WfsDev &d, Raw4<NK> &o, const v
         else if constexpr (NK == 3) noise_model_four(d, (const uint2 *)noise_row, channel, row_abs + (i64)nstart, 4 * lane, o.nz);
         else noise_colour_four<NK == 5>(d, channel, row_abs + (i64)nstart, lane, o.nz);
     } else if constexpr (NK != 0) {
-        u32 in = nstart + 4u * (u32)lane;
-        in = in >= (u32)d.noise_len ? in - (u32)d.noise_len : in;
+        const u32 in = noise_wrap(nstart + 4u * (u32)lane, (u32)d.noise_len);
         if constexpr (NK == 2) __builtin_memcpy(o.nzf, (const double *)noise_row + in, 32); else __builtin_memcpy(o.nz, (const int16_t *)noise_row + in, 8);
     }
 }
@@ -2027,20 +2007,17 @@ __device__ __forceinline__ i32 finish_four(const WfsDev &d, const Raw4<NK> &s, i
 // for EVERYTHING at the top of the loop; the flush of a row with more than 64 intervals drains the counter itself.
 struct ZleFast {
     i32 s_last = -1, s_left = -1, s_count = 0, s_nrec = 0, my_l = 0, my_r = 0;
-    // close interval k = [rawl, rawr] (first / last hit): window, clip, even landing (rawdata.py:302-308); returns the records it needs
+    // close interval k = [rawl, rawr] (first / last hit, zle_window); returns the records it needs
     __device__ __forceinline__ i32 close(const WfsDev &d, const ZleArgs &a, int lane, i64 base, i64 row_abs, i32 len32, i32 k, i32 rawl, i32 rawr)
     {
-        i32 l = rawl - d.tw, rr = rawr + d.tw;
-        l = l < 0 ? 0 : (l > len32 - 1 ? len32 - 1 : l); rr = rr < 0 ? 0 : (rr > len32 - 1 ? len32 - 1 : rr);
-        l = (l + 1) / 2 * 2; rr = rr / 2 * 2;                  // ceil(l/2)*2, floor(r/2)*2 for non-negative ints
+        const ZleWindow w = zle_window(rawl, rawr, d.tw, len32);
         const int slot = k & 63;
-        if (lane == slot) { my_l = l; my_r = rr; }
+        if (lane == slot) { my_l = w.left; my_r = w.right; }
         if (slot == 63) {
             a.itv_left[base + (k - 63) + lane] = row_abs + my_l; a.itv_right[base + (k - 63) + lane] = row_abs + my_r;      // absolute sample indices (rawdata.py:311)
             __builtin_amdgcn_s_waitcnt(0x0F70);             // vmcnt(0)
         }
-        const i32 plen = rr - l + 1;
-        return plen > 0 ? (plen + WFS_SPR - 1) / WFS_SPR : 0;
+        return w.nrec;
     }
     // 256 samples: lane q holds the hits of samples i .. i + 3 (i = block start + 4 q) as a nibble; 16 lanes are a chunk of 64 samples,
     // whose first and last hit come from the ballot of the non-empty nibbles and two readlanes
@@ -2080,25 +2057,20 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
     if (r >= a.n_front) return;                             // (the rows behind n_front are resident: k_row_pulse has made their intervals)
     const RowDesc q = a.desc[r];
     const i64 idx = q.idx; const i32 channel = q.channel; const bool he = q.he != 0;
-    const i64 len = q.len;
     const i32 *acc = (q.src ? a.tbuf : a.raw) + q.acc_off;
     const i64 thr = q.thr;
     const i64 ixr = q.ixr;
-    i64 hold = 2 * (i64)d.tw + 1; if (hold < 1) hold = 1;
     const i64 base = q.itv_base;
     const i64 row_abs = q.row_abs;
-    // close interval k = [rawl, rawr] (first / last hit): window, clip, even landing (rawdata.py:302-308),
-    // absolute sample indices (rawdata.py:311); returns the number of records it needs
-    auto close_interval = [&](i32 k, i64 rawl, i64 rawr) -> i32 {
-        i64 l = rawl - d.tw, rr = rawr + d.tw;
-        l = l < 0 ? 0 : (l > len - 1 ? len - 1 : l); rr = rr < 0 ? 0 : (rr > len - 1 ? len - 1 : rr);
-        l = (l + 1) / 2 * 2; rr = rr / 2 * 2;                  // ceil(l/2)*2, floor(r/2)*2 for non-negative ints
-        a.itv_left[base + k] = row_abs + l; a.itv_right[base + k] = row_abs + rr;
-        const i32 plen = (i32)(rr - l + 1);                     // a row is shorter than 10^6 samples (k_group_final)
-        return plen > 0 ? (plen + WFS_SPR - 1) / WFS_SPR : 0;
-    };
     i32 carry_last = -1, open_left = -1; i32 count = 0, nrec = 0;      // (a row is shorter than 10^6 samples: 32-bit indices)
-    const i32 len32 = (i32)len, hold32 = (i32)hold;
+    const i32 len32 = q.len, hold32 = (i32)zle_holdoff(d.tw);
+    // the general path closes interval k = [rawl, rawr] (first / last hit, zle_window) in the lane that found it: absolute sample
+    // indices (rawdata.py:311); returns the records it needs
+    auto close_at = [&](i32 k, i32 rawl, i32 rawr) -> i32 {
+        const ZleWindow w = zle_window(rawl, rawr, d.tw, len32);
+        a.itv_left[base + k] = row_abs + w.left; a.itv_right[base + k] = row_abs + w.right;
+        return w.nrec;
+    };
     const bool noisy = NK != 0 && channel < d.noise_channels;
     // the noise index of a row's sample i is (ix + i) mod noise_len (rawdata.py:433-434): a scalar start per block of samples that
     // steps with the block and wraps, plus the lane's offset inside the block -- rows may be any number of noise lengths long.
@@ -2108,7 +2080,7 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
     const bool fast_loads = len32 >= 1 && (!TABLE || d.noise_len >= NOISE_MIN_FAST);
     const u32 nixr = noisy ? (u32)ixr : 0u;
     const void *noise_row = noise_row_of<NK>(d, channel, noisy);
-    if (hold32 >= 63 && fast_loads && !a.row_dbg) {
+    if (hold32 >= ZLE_FAST_HOLD && fast_loads && !a.row_dbg) {
         // The usual geometry (hold-off of at least a chunk): the interval bookkeeping is scalar work on the ballot mask (ZleFast), and
         // the vector unit is left with load, finish and compare.
         constexpr int G = NK >= 4 ? 1 : 4;          // (kind 4 draws instead of loading: one block's draws at a time, one copy of their code)
@@ -2134,7 +2106,7 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
                     else buf[u].nz[0] = buf[u].nz[1] = buf[u].nz[2] = buf[u].nz[3] = 0;
                 } else
                 buf[u] = load_four<NK>(d, acc, i < len32 ? i : 0, noise_row, NK >= 4 ? (u32)(g0 + 256 * u) : nrun, lane, channel, row_abs);
-                if constexpr (TABLE) { nrun += 256u; nrun = nrun >= (u32)d.noise_len ? nrun - (u32)d.noise_len : nrun; }
+                if constexpr (TABLE) nrun = noise_advance(nrun, 256u, (u32)d.noise_len);
             }
         };
         auto look = [&](const Raw4<NK> *buf, i32 g0) {
@@ -2165,7 +2137,7 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
             for (int u = 0; u < ZLE_GROUP; u++) {
                 const i32 i = g0 + 64 * u + lane;
                 rs[u] = load_sample<NK>(d, acc, i < len32 ? i : len32 - 1, noise_row, nrun1, (u32)lane, channel, row_abs);
-                if constexpr (TABLE) { nrun1 += 64u; nrun1 = nrun1 >= (u32)d.noise_len ? nrun1 - (u32)d.noise_len : nrun1; }
+                if constexpr (TABLE) nrun1 = noise_advance(nrun1, 64u, (u32)d.noise_len);
             }
 #pragma unroll
             for (int u = 0; u < ZLE_GROUP; u++) { const i32 i = g0 + 64 * u + lane; vv[u] = i < len32 ? finish_loaded(d, rs[u], he, noisy) : 0x7fffffff; }
@@ -2193,14 +2165,14 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
                 const u64 sbelow = smask & lt;
                 const i32 k = count + __popcll(sbelow);
                 const i32 prev_left = sbelow ? c0 + 63 - __clzll(sbelow) : open_left;
-                if (k > 0) nrec += close_interval(k - 1, prev_left, prev);
+                if (k > 0) nrec += close_at(k - 1, prev_left, prev);
             }
             count += __popcll(smask);
             if (smask) open_left = c0 + 63 - __clzll(smask);
             if (mask) carry_last = c0 + 63 - __clzll(mask);
         }
     }
-    if (lane == 0 && count > 0) nrec += close_interval(count - 1, open_left, carry_last);
+    if (lane == 0 && count > 0) nrec += close_at(count - 1, open_left, carry_last);
     for (int o = 32; o > 0; o >>= 1) nrec += __shfl_down(nrec, o, 64);
     if (lane == 0) { a.itv_n[idx] = count; a.row_nrec[idx] = nrec; }
 }
@@ -2239,7 +2211,7 @@ __global__ __launch_bounds__(256) void k_sum_signal(WfsDev d, SumArgs a)
         const i64 ridx = g * d.n_tpc + d.n_top + t;
         const i64 lo = a.row_lo[ridx];
         if (lo == I64_MAX) continue;
-        const i32 rel = (i32)(lo - slo) - s0, rl = (i32)(a.row_hi[ridx] - lo + 1 + 2 * (i64)d.tw);      // both rows start tw samples ahead of their first pulse
+        const i32 rel = (i32)(lo - slo) - s0, rl = (i32)row_span(lo, a.row_hi[ridx], d.tw).len;      // both rows start tw samples ahead of their first pulse
         if (rel >= SUM_CHUNK || rel + rl <= 0) continue;
         i64 off;                                                // sample offset into raw, or ~(offset into tbuf)
         if (row_is_direct(a.tile_done, a.n_done, a.row_cnt, a.row_tile, ridx)) {
@@ -2305,18 +2277,17 @@ __global__ __launch_bounds__(256) void k_row_pulse(WfsDev d, PulseArgs a, ZleArg
     WavePhoton *wph = s_ph + w * (64 + PW_U);
     const i32 len32 = q.len;
     const i64 thr = q.thr; const i64 base = q.itv_base, row_abs = q.row_abs, idx = q.idx;
-    const i32 thr32 = thr > 0x7fffffffLL ? 0x7fffffff : (thr < -0x7fffffffLL ? -0x7fffffff : (i32)thr);      // (finished samples are 0 .. 2^31 - 1: the comparison is the same)
-    i64 hold = 2 * (i64)d.tw + 1; if (hold < 1) hold = 1;
-    const i32 hold32 = (i32)hold;
+    const i32 thr32 = zle_thr32(thr);
+    const i32 hold32 = (i32)zle_holdoff(d.tw);
     const bool noisy = NK != 0 && q.channel < d.noise_channels;
     const void *noise_row = noise_row_of<NK>(d, q.channel, noisy);
     u32 nrun = (noisy && NK < 3) ? (u32)q.ixr : 0u;       // noise index of the next block's first sample (rawdata.py:433-434); kinds 3, 4: that sample's index in the row
     int16_t *fin = z.fin + q.acc_off;
-    const i32 fin_len = (len32 + 3) & ~3;
+    const i32 fin_len = fin_padded_len(len32);
     auto load_noise = [&](Raw4<NK> &o) {                  // (every lane of the wave is here: the callers' conditions are wave-uniform)
         noise_four<NK>(d, o, noise_row, q.channel, row_abs, nrun, lane);
-        if constexpr (NK != 0) nrun += 256u;
-        if constexpr (NK == 1 || NK == 2) nrun = nrun >= (u32)d.noise_len ? nrun - (u32)d.noise_len : nrun;
+        if constexpr (NK == 1 || NK == 2) nrun = noise_advance(nrun, 256u, (u32)d.noise_len);
+        else if constexpr (NK != 0) nrun += 256u;
     };
     Raw4<NK> s4;
     load_noise(s4);                                       // the first block's noise: on its way under the pulses
@@ -2358,17 +2329,13 @@ __global__ __launch_bounds__(256) void k_row_pulse(WfsDev d, PulseArgs a, ZleArg
 #pragma unroll
                 for (int j = 0; j < 4; j++) { const i32 v = finish_four<NK>(d, s4, j, false, noisy); nib |= (i + j < len32 && (i64)v < thr) ? (1u << j) : 0u; v16[j] = (u32)(uint16_t)v; }
             } else {
-                // integer noise: NOT finish_value but a deliberately cheaper rule (no HE rows here, so no factor), 32-bit arithmetic with
-                // a saturating add -- the values of finish_value for every accumulator that is not within
-                // 2^16 of overflowing an int32 (a row of a 14-bit digitiser is some 10^5 times smaller)
+                // integer noise: NOT finish_value but the deliberately cheaper finish_resident (wfs_rows.h has its domain)
                 const i32 live = len32 - i;                  // samples of the lane inside the row
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
-                    i32 add = d.baseline;
-                    if constexpr (NK == 1) add += noisy ? (i32)s4.nz[j] : 0;
-                    if constexpr (NK >= 3) add += s4.nz[j];
-                    i32 v = __builtin_elementwise_add_sat(s4.acc[j], add);
-                    v = v < 0 ? 0 : v;
+                    i32 nz = 0;
+                    if constexpr (NK != 0) nz = s4.nz[j];
+                    const i32 v = finish_resident<NK>(d, s4.acc[j], noisy, nz);
                     nib |= (j < live && v < thr32) ? (1u << j) : 0u; v16[j] = (u32)v;
                 }
             }
@@ -2396,10 +2363,10 @@ __global__ __launch_bounds__(256) void k_rec_keys(WfsDev d, ZleArgs a)
     for (i32 k = 0; k < count; k++) {
         const i64 left = a.itv_left[q.itv_base + k]; const i32 plen = (i32)(a.itv_right[q.itv_base + k] - left + 1);
         if (plen <= 0) continue;
-        const i32 need = (plen + WFS_SPR - 1) / WFS_SPR;
+        const i32 need = records_of(plen);
         for (i32 f = lane; f < need; f += 64) {
             if (rec + f >= a.rec_capacity) break;
-            a.rec_key[rec + f] = ((u64)(left + (i64)WFS_SPR * f - key_base) << 12) | (u64)(u32)q.channel;
+            a.rec_key[rec + f] = ((u64)(rec_fragment_sample(left, (i64)f) - key_base) << 12) | (u64)(u32)q.channel;
             a.rec_val[rec + f] = (u32)(rec + f);
         }
         rec += need;
@@ -2441,19 +2408,19 @@ __global__ __launch_bounds__(256) void k_pack_res(PackResArgs a)
     const PackDesc q = a.pdesc[r];
     if (q.count == 0) return;
     const int16_t *fin = a.fin + q.acc_off;
-    const i32 last = (((q.len_he_src & 0xfffff) + 3) & ~3) - 2;
-    constexpr int spr = WFS_SPR; constexpr int rec_dwords = (24 + 2 * spr) / 4;
-    const i64 rec_bytes = 24 + 2 * (i64)spr;
-    const u32 w3 = ((u32)(uint16_t)a.dt) | ((u32)(uint16_t)q.channel << 16);
+    const i32 last = fin_last_pair(q.len_he_src & 0xfffff);
+    constexpr int spr = WFS_SPR; constexpr int rec_dwords = REC_DWORDS;
+    const i64 rec_bytes = WFS_RECORD_BYTES;
+    const u32 w3 = rec_dt_channel(a.dt, q.channel);
     i64 rec = q.rec;
     for (i32 k = 0; k < q.count; k++) {
         const i64 left = k == 0 ? q.left0 : a.itv_left[q.itv_base + k]; const i32 plen = k == 0 ? q.plen0 : (i32)(a.itv_right[q.itv_base + k] - left + 1);
         if (plen <= 0) continue;
-        const i32 need = (plen + spr - 1) / spr;
+        const i32 need = records_of(plen);
         const i32 off = (i32)(left - q.row_abs);                   // even (rawdata.py:305-306), and the row starts on a multiple of four samples of fin
         for (int q0 = 0; q0 < rec_dwords; q0 += 64) {              // (one pass unless a record is longer than 64 dwords)
             const int qd = q0 + lane;
-            const int s0 = (qd - 6) * 2;                            // first of the lane's two samples (lanes of the header: negative)
+            const int s0 = (qd - REC_HEADER_DWORDS) * 2;            // first of the lane's two samples (lanes of the header: negative)
             const i32 lane_off = off + (s0 < 0 ? 0 : s0);
             for (i32 f0 = 0; f0 < need; f0 += 4) {
                 u32 two[4];
@@ -2464,11 +2431,11 @@ __global__ __launch_bounds__(256) void k_pack_res(PackResArgs a)
                     const i32 f = f0 + u;
                     const i64 slot = a.rec_dest ? (i64)a.rec_dest[rec + (f < need ? f : 0)] : rec + f;
                     u32 *out = (u32 *)(a.records + slot * rec_bytes);
-                    const i64 time = (i64)a.dt * (left + spr * f);
-                    const i32 rest = plen - spr * f, length = rest < spr ? rest : spr;
+                    const RecHeader hd = rec_header(a.dt, w3, left, plen, f);
+                    const i32 length = (i32)hd.w[REC_LENGTH];
                     u32 w = (s0 < length ? two[u] & 0xffffu : 0u) | (s0 + 1 < length ? two[u] & 0xffff0000u : 0u);
-                    w = qd == 0 ? (u32)(u64)time : w; w = qd == 1 ? (u32)((u64)time >> 32) : w; w = qd == 2 ? (u32)length : w;
-                    w = qd == 3 ? w3 : w; w = qd == 4 ? (u32)plen : w; w = qd == 5 ? (u32)(uint16_t)f : w;          // record_i; baseline = 0
+#pragma unroll
+                    for (int j = 0; j < REC_HEADER_DWORDS; j++) w = qd == j ? hd.w[j] : w;      // (selected, not branched to)
                     if (f < need && qd < rec_dwords && rec + f < a.rec_capacity) out[qd] = w;
                 }
             }
@@ -2495,24 +2462,24 @@ __global__ __launch_bounds__(256) void k_pack(WfsDev d, ZleArgs a)
     const i64 ixr = q.ixr;
     const i64 base = q.itv_base;
     const i32 len32 = q.len_he_src & 0xfffff;
-    constexpr int spr = WFS_SPR; constexpr int rec_dwords = (24 + 2 * spr) / 4;
-    const i64 rec_bytes = 24 + 2 * (i64)spr;
+    constexpr int spr = WFS_SPR; constexpr int rec_dwords = REC_DWORDS;
+    const i64 rec_bytes = WFS_RECORD_BYTES;
     const bool noisy = NK != 0 && channel < d.noise_channels;
     constexpr bool TABLE = NK == 1 || NK == 2;
     const bool fast_loads = !TABLE || (d.noise_len >= NOISE_MIN_FAST && spr <= NOISE_MIN_FAST / 2);       // (as in k_zle: a scalar noise start per record)
     const u32 nixr = noisy ? (u32)ixr : 0u;
     const void *noise_row = noise_row_of<NK>(d, channel, noisy);
-    const u32 w3 = ((u32)(uint16_t)d.dt) | ((u32)(uint16_t)channel << 16);
+    const u32 w3 = rec_dt_channel(d.dt, channel);
     constexpr int PACK_U = NK >= 4 ? 1 : 4;         // (kind 4 draws where the others load: one record's draws at a time, one copy of their code)
     i64 rec = q.rec;
     for (i32 k = 0; k < count; k++) {
         const i64 left = k == 0 ? q.left0 : a.itv_left[base + k]; const i32 plen = k == 0 ? q.plen0 : (i32)(a.itv_right[base + k] - left + 1);
         if (plen <= 0) continue;
-        const i32 need = (plen + spr - 1) / spr;
+        const i32 need = records_of(plen);
         const i32 off = (i32)(left - row_abs);                     // first sample of the interval inside the row
         for (int q0 = 0; q0 < rec_dwords; q0 += 64) {              // (one pass unless a record is longer than 64 dwords)
             const int qd = q0 + lane;
-            const int s0 = (qd - 6) * 2;                            // first of the lane's two samples (lanes of the header: negative)
+            const int s0 = (qd - REC_HEADER_DWORDS) * 2;                           // first of the lane's two samples (lanes of the header: negative)
             u32 nrun = 0;                                           // noise index of the next record's first sample (a scalar)
             if constexpr (TABLE) { if (fast_loads) nrun = (nixr + (u32)off) % (u32)d.noise_len; }
             const u32 noff = (u32)(s0 < 0 ? 0 : s0);
@@ -2523,11 +2490,11 @@ __global__ __launch_bounds__(256) void k_pack(WfsDev d, ZleArgs a)
                     for (int u = 0; u < PACK_U; u++) {
                         const i32 f = f0 + u;
                         if (f >= need) break;                       // wave-uniform
-                        i32 i0 = off + spr * f + (i32)noff;
+                        i32 i0 = off + rec_fragment_first(f) + (i32)noff;
                         i0 = i0 > len32 - 1 ? len32 - 1 : i0;       // (lanes past the record's samples read a valid sample and drop it)
                         const i32 i1 = i0 + 1 > len32 - 1 ? len32 - 1 : i0 + 1;
                         lo[u] = load_sample<NK>(d, acc, i0, noise_row, nrun, noff, channel, row_abs); hi[u] = load_sample<NK>(d, acc, i1, noise_row, nrun, noff + 1u, channel, row_abs);
-                        if constexpr (TABLE) { nrun += (u32)spr; nrun = nrun >= (u32)d.noise_len ? nrun - (u32)d.noise_len : nrun; }
+                        if constexpr (TABLE) nrun = noise_advance(nrun, (u32)spr, (u32)d.noise_len);
                     }
                 }
 #pragma unroll
@@ -2536,25 +2503,25 @@ __global__ __launch_bounds__(256) void k_pack(WfsDev d, ZleArgs a)
                     if (f >= need) break;
                     if (rec + f >= a.rec_capacity) break;
                     u32 *out = (u32 *)(a.records + (a.rec_dest ? (i64)a.rec_dest[rec + f] : rec + f) * rec_bytes);
-                    const i64 time = (i64)d.dt * (left + spr * f);
-                    const i32 length = (plen < spr * (f + 1) ? plen : spr * (f + 1)) - spr * f;
+                    const RecHeader hd = rec_header<true>(d.dt, w3, left, plen, f);
+                    const i32 length = (i32)hd.w[REC_LENGTH];
                     u32 w;
-                    if (qd >= 6) {
+                    if (qd >= REC_HEADER_DWORDS) {
                         u32 vlo, vhi;
                         if (fast_loads) { vlo = (u32)(uint16_t)finish_loaded(d, lo[u], he, noisy); vhi = (u32)(uint16_t)finish_loaded(d, hi[u], he, noisy); }
                         else {
-                            const i64 i0 = (i64)off + spr * f + s0;
+                            const i64 i0 = (i64)off + rec_fragment_first(f) + s0;
                             vlo = s0 < length ? (u32)(uint16_t)finish_sample<NK>(d, acc, i0, channel, he, ixr, row_abs) : 0u;
                             vhi = s0 + 1 < length ? (u32)(uint16_t)finish_sample<NK>(d, acc, i0 + 1, channel, he, ixr, row_abs) : 0u;
                         }
                         w = (s0 < length ? vlo : 0u) | ((s0 + 1 < length ? vhi : 0u) << 16);
                     }
-                    else if (qd == 0) w = (u32)(u64)time;
-                    else if (qd == 1) w = (u32)((u64)time >> 32);
-                    else if (qd == 2) w = (u32)length;
-                    else if (qd == 3) w = w3;
-                    else if (qd == 4) w = (u32)plen;
-                    else w = (u32)(uint16_t)f;                        // record_i, baseline = 0
+                    else if (qd == REC_TIME_LO) w = hd.w[REC_TIME_LO];              // (branched to, not selected)
+                    else if (qd == REC_TIME_HI) w = hd.w[REC_TIME_HI];
+                    else if (qd == REC_LENGTH) w = hd.w[REC_LENGTH];
+                    else if (qd == REC_DT_CHANNEL) w = hd.w[REC_DT_CHANNEL];
+                    else if (qd == REC_PULSE_LENGTH) w = hd.w[REC_PULSE_LENGTH];
+                    else w = hd.w[REC_RECORD_I];
                     if (qd < rec_dwords) out[qd] = w;
                 }
             }
