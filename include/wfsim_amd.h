@@ -314,6 +314,9 @@ int wfs_wait_records(wfs_handle *h);
 int wfs_host_register(void *ptr, int64_t bytes);
 int wfs_host_unregister(void *ptr);
 int wfs_copy_records_dev(wfs_handle *h, void *dst_dev, int64_t capacity_records);
+/* The records of the last run in device memory.  wfs_run returns once the counts are known; the records are packed on a stream of the
+ * handle's own, under the front end of the next wfs_run.  The bytes behind this pointer are complete after wfs_synchronize or after
+ * any of the record copy calls above (the asynchronous one: after wfs_wait_records); until then they may still be written. */
 const void *wfs_records_dev_ptr(wfs_handle *h);
 /* digitise windows: rawdata.left / rawdata.right and the first record of each window (strax_interface.py:394-399) */
 int wfs_copy_groups(wfs_handle *h, int64_t *left, int64_t *right, int64_t *first_record, int64_t *ix_rand);

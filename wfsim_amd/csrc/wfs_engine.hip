@@ -1,5 +1,6 @@
 // wfs_engine.hip -- host side of libwfsim_amd.so: the C ABI of include/wfsim_amd.h, device memory arenas,
-// stage orchestration on one HIP stream.  gfx950 (MI355X) only.
+// stage orchestration on one HIP stream (the record packers of a batch on a second one, under the next run: wfs_pack_fence.h).
+// gfx950 (MI355X) only.
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
@@ -8,6 +9,7 @@
 #include "wfs_boundary.h"
 #include "wfs_devbuf.h"
 #include "wfs_batch.h"
+#include "wfs_pack_fence.h"
 #include "../../include/wfsim_amd.h"
 
 // Every pulse kernel exists in two forms: FMA = true (wfs_config.fma, one rounding per template * gain term) and FMA = false (numpy's two
@@ -123,6 +125,10 @@ struct wfs_handle {
     // runs under the kernels of the next batch
     DevBuf records_ab[2]; int rec_cur = 0; hipStream_t copy_stream = nullptr; hipEvent_t rec_copied[2] = {nullptr, nullptr}; bool rec_pending[2] = {false, false};
     DevBuf &records_buf() { return records_ab[rec_cur]; }
+    // the packers of a batch on a stream of their own, under the front end of the next run (wfs_pack_fence.h): pack_go[a] is recorded on
+    // the main stream once everything the packers of arena a read is written, rec_ready[a] on the pack stream behind them
+    hipStream_t pack_stream = nullptr; hipEvent_t pack_go[2] = {nullptr, nullptr}, rec_ready[2] = {nullptr, nullptr}; PackFence pack;
+    bool pack_sync = false;           // WFS_PACK_SYNC=1: the packers stay on the main stream in front of the last boundary (A/B runs, tests)
 
     // profiling and debug
     int debug_bits = 0, profiling = 0;      // wfs_set_debug (DBG_*), wfs_set_profiling
@@ -170,6 +176,9 @@ struct wfs_handle {
         if (own_stream) hipStreamDestroy(stream);
         if (copy_stream) { hipStreamSynchronize(copy_stream); hipStreamDestroy(copy_stream); }
         for (hipEvent_t e : rec_copied) if (e) hipEventDestroy(e);
+        if (pack_stream) { hipStreamSynchronize(pack_stream); hipStreamDestroy(pack_stream); }
+        for (hipEvent_t e : pack_go) if (e) hipEventDestroy(e);
+        for (hipEvent_t e : rec_ready) if (e) hipEventDestroy(e);
         if (h_scal) hipHostFree(h_scal);
     }
 };
@@ -193,8 +202,35 @@ static u32 ap_threshold(double prob, double modifier, bool dpe)
     return a <= 0.0 ? 0u : (a >= 134217728.0 ? 134217728u : (u32)a);
 }
 
+// The host waits for packers that may still be running on the pack stream: readers of the records, setters of the tables the packers
+// read, changes of mode.  Returns at once when none are pending.
+int pack_wait(wfs_handle *h)
+{
+    if (!h->pack.must_wait()) return WFS_OK;
+    HIPCHK(hipEventSynchronize(h->rec_ready[h->pack.arena]));
+    h->pack.host_waited();
+    return WFS_OK;
+}
+// The fence of a run: the main stream waits for the previous batch's packers.  Called in front of the first write of a run to a
+// buffer they read (the tile buffers, else the accumulators); one stream wait per pending pack, none otherwise.
+int pack_fence(wfs_handle *h)
+{
+    if (h->pack.take_fence()) HIPCHK(hipStreamWaitEvent(h->stream, h->rec_ready[h->pack.arena], 0));
+    return WFS_OK;
+}
+// the buffers the packers read or write (the noise tables behind WfsDev apart: their setters wait on the host)
+bool pack_uses(const wfs_handle *h, const DevBuf &b)
+{
+    for (const DevBuf *q : {&h->pack_desc, &h->row_desc, &h->rec_off, &h->itv_n, &h->itv_left, &h->itv_right, &h->rec_dest, &h->tbuf, &h->raw, &h->fin,
+                            &h->records_ab[0], &h->records_ab[1]})
+        if (q == &b) return true;
+    return false;
+}
+
+// (a grow frees the old block: one of a buffer that pending packers use waits for them on the host first)
 int ensure(wfs_handle *h, DevBuf &b, size_t bytes)
 {
+    if (b.cap < (bytes ? bytes : 16) && h->pack.must_wait() && pack_uses(h, b)) { int rc = pack_wait(h); if (rc) return rc; }
     if (int e = b.ensure(bytes)) return h->fail(WFS_E_HIP, std::string("hipMalloc: ") + hipGetErrorString((hipError_t)e));
     return WFS_OK;
 }
@@ -674,6 +710,11 @@ try {
     h->own_stream = true;
     if (hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&h->rec_copied[0], hipEventDisableTiming) != hipSuccess
         || hipEventCreateWithFlags(&h->rec_copied[1], hipEventDisableTiming) != hipSuccess) return WFS_E_HIP;
+    // (a lower priority for the pack stream, with or without a higher one for the main stream, did not help the headline step: DESIGN 7)
+    if (hipStreamCreateWithFlags(&h->pack_stream, hipStreamNonBlocking) != hipSuccess) return WFS_E_HIP;
+    for (int a = 0; a < 2; a++)
+        if (hipEventCreateWithFlags(&h->pack_go[a], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&h->rec_ready[a], hipEventDisableTiming) != hipSuccess) return WFS_E_HIP;
+    { const char *e = getenv("WFS_PACK_SYNC"); h->pack_sync = e && atoi(e) != 0; }
     if (ensure(h, h->scal, sizeof(WfsScal)) != WFS_OK) return WFS_E_HIP;
     {   // the host copy of the scalar block; mapped and coherent with the sequence word on the cache line behind it where the
         // device may write it (read_scal), else -- or with WFS_HOST_SYNC=copy, A/B runs -- page-locked for the copy as before
@@ -732,6 +773,7 @@ try {
     if (!h) return WFS_OK;
     hipSetDevice(h->device);
     hipStreamSynchronize(h->stream);
+    if (h->pack_stream) hipStreamSynchronize(h->pack_stream);      // (packers that nobody read: the buffers go with the handle)
 
 #ifdef WFS_STAMPS
     {   // diagnostic build: average cycles per workgroup and phase
@@ -751,12 +793,19 @@ const char *wfs_last_error(const wfs_handle *h) { return h ? h->err.c_str() : "n
 int wfs_set_stream(wfs_handle *h, void *s)
 try {
     if (!h) return WFS_E_INVALID;
+    TRY(pack_wait(h));          // (from here on the packers run on the caller's stream)
     if (h->own_stream) { hipStreamSynchronize(h->stream); hipStreamDestroy(h->stream); h->own_stream = false; }
     h->stream = (hipStream_t)s;
     return WFS_OK;
 } WFS_CATCH(h)
 
-int wfs_synchronize(wfs_handle *h) try { if (!h) return WFS_E_INVALID; HIPCHK(hipStreamSynchronize(h->stream)); return WFS_OK; } WFS_CATCH(h)
+int wfs_synchronize(wfs_handle *h)
+try {
+    if (!h) return WFS_E_INVALID;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipStreamSynchronize(h->pack_stream)); h->pack.host_waited();
+    return WFS_OK;
+} WFS_CATCH(h)
 // a noise array of floats (resource.noise_data of a float dtype with non-integral values): add_noise (rawdata.py:436) adds it into
 // the int64 row inside numba, which stores the TRUNCATED SUM -- not the sum with the truncated noise.  Replaces the int16 table.
 int wfs_set_noise_float(wfs_handle *h, const double *noise, int32_t noise_len, int32_t noise_channels)
@@ -765,6 +814,7 @@ try {
     if (!h->tables_set) return h->fail(WFS_E_STATE, "wfs_set_tables must be called first");
     if (!noise || noise_len <= 0 || noise_channels <= 0) return h->fail(WFS_E_INVALID, "wfs_set_noise_float: empty noise array");
     HIPCHK(hipSetDevice(h->device));
+    TRY(pack_wait(h));          // (pending packers read the table this call replaces)
     const size_t stride = (size_t)noise_len + NOISE_PAD;        // (every row followed by its own first samples: wfs_device.h NOISE_PAD)
     std::vector<double> nt(stride * noise_channels);
     for (int64_t i = 0; i < (int64_t)stride; i++) for (int c = 0; c < noise_channels; c++) nt[(size_t)c * stride + i] = noise[(size_t)(i % noise_len) * noise_channels + c];
@@ -779,6 +829,7 @@ try {
 int wfs_set_noise_offsets(wfs_handle *h, const int64_t *ix, int64_t n)
 try {
     if (!h || n < 0 || (n > 0 && !ix)) return WFS_E_INVALID;
+    TRY(pack_wait(h));
     h->n_noise_override = n;
     if (n) { TRY(upload(h, h->noise_override, ix, (size_t)n * 8)); HIPCHK(hipStreamSynchronize(h->stream)); }
     return WFS_OK;
@@ -791,8 +842,9 @@ try {
     HIPCHK(hipMemcpy(group, h->cl_group.p, (size_t)h->batch.n_clusters * 4, hipMemcpyDeviceToHost));
     return WFS_OK;
 } WFS_CATCH(h)
-int wfs_set_debug(wfs_handle *h, int32_t keep) try { if (!h) return WFS_E_INVALID; h->debug_bits = keep; return WFS_OK; } WFS_CATCH(h)
-int wfs_set_profiling(wfs_handle *h, int32_t on) try { if (!h) return WFS_E_INVALID; h->profiling = on; return WFS_OK; } WFS_CATCH(h)
+// (a mode that changes waits for pending packers; a call that leaves it as it is -- one per step is common -- does not)
+int wfs_set_debug(wfs_handle *h, int32_t keep) try { if (!h) return WFS_E_INVALID; if (keep != h->debug_bits) TRY(pack_wait(h)); h->debug_bits = keep; return WFS_OK; } WFS_CATCH(h)
+int wfs_set_profiling(wfs_handle *h, int32_t on) try { if (!h) return WFS_E_INVALID; if (on != h->profiling) TRY(pack_wait(h)); h->profiling = on; return WFS_OK; } WFS_CATCH(h)
 
 int wfs_set_tables(wfs_handle *h, const double *templates, const double *spe, int32_t n_spe, const double *gains,
                    const double *thr_truth, const int64_t *thr_zle, const double *lum_x, const double *lum_t, int32_t n_lum,
@@ -801,6 +853,7 @@ try {
     if (!h || !templates || !spe || !gains || !thr_truth || !thr_zle || n_spe < 1) return h ? h->fail(WFS_E_INVALID, "wfs_set_tables: null table") : WFS_E_INVALID;
     if (n_spe != 1 && n_spe < h->cfg.n_tpc) return h->fail(WFS_E_INVALID, "wfs_set_tables: n_spe must be 1 or >= n_tpc");
     HIPCHK(hipSetDevice(h->device));
+    TRY(pack_wait(h));          // (pending packers read the noise table this call replaces)
     const wfs_config &c = h->cfg;
     TRY(upload(h, h->t_templates, templates, sizeof(double) * c.dt * c.tlen));
     TRY(upload(h, h->t_spe, spe, sizeof(double) * SPE_ROW_LEN * (size_t)n_spe));
@@ -1732,6 +1785,7 @@ static int gen_tile_photons(wfs_handle *h, GenRun &r)
     // (k_tile_counts) and single photons are recomputed on request (wfs_gather_photon_times); no photon of a tile is generated)
     const bool counts_only = (h->debug_bits & DBG_GEN_ONLY) && !(h->debug_bits & DBG_KEEP_PHOTONS);
     if (h->run.fuse_on && n_tilegen_tiles(h) > 0 && !counts_only) {
+        TRY(pack_fence(h));         // the tile buffers: the first write of a run to what the previous batch's packers read
         TRY(ensure(h, h->tbuf, (size_t)h->h_scal->n_tbuf_samples * 4 + 64));
         TRY(ensure(h, h->tile_truth, (size_t)T * 8 * 8));
         f.tile_off = h->tile_off.as<i64>(); f.tile_tmin = h->tile_tmin.as<i32>(); f.tile_tmax = h->tile_tmax.as<i32>(); f.tile_truth = h->tile_truth.as<double>();
@@ -2059,6 +2113,7 @@ static int run_pulses(wfs_handle *h, RunState &r)
     const WfsDev &d = h->dev;
     PulseArgs &pa = r.pa;
     const i64 T = h->batch.n_tiles, S = h->batch.n_sets;
+    TRY(pack_fence(h));             // the accumulators are the first such write of a run without tile buffers (with them: gen_tile_photons)
     // (+64: a lane of k_zle reads 4 samples from its first valid one; the sum rows behind the accumulators are written whole by k_sum_signal)
     TRY(ensure(h, h->raw, (size_t)(h->run.s_sum > 0 ? h->run.sum_base + h->run.s_sum : h->run.s_raw) * 4 + 64));
     TRY(ensure(h, h->truth, (size_t)S * 16 * 8));
@@ -2256,6 +2311,9 @@ static int run_records(wfs_handle *h, RunState &r)
     const WfsDev &d = h->dev;
     ZleArgs &za = r.za;
     const i64 RS = r.RS;
+    // the packers keep their place on the main stream, in front of the last boundary, in a profiled step (kernel_times lists them), in
+    // the debug modes, on a caller's stream and under WFS_PACK_SYNC=1
+    const bool defer = h->own_stream && !h->profiling && h->debug_bits == 0 && !h->pack_sync;
     TRY(scan(h, h->row_nrec.as<i32>(), RS, h->rec_off, &WfsScal::n_records));
     TRY(read_scal(h));
     h->run.n_records = h->h_scal->n_records;
@@ -2284,14 +2342,27 @@ static int run_records(wfs_handle *h, RunState &r)
     }
     if (h->run.n_active_rows > 0 && h->run.n_records > 0) {
         TRY(ensure(h, h->pack_desc, (size_t)h->run.n_active_rows * sizeof(PackDesc))); za.pdesc = h->pack_desc.as<PackDesc>();
-        { Timer t(h, "k_pack_desc"); hipLaunchKernelGGL(k_pack_desc, dim3(nblocks(h->run.n_active_rows, 256)), dim3(256), 0, h->stream, za); }
+        // Nothing wfs_run returns depends on the packers: they go to the pack stream, behind everything on the main stream up to here,
+        // and run under the front end of the next wfs_run, which fences them in front of its first write to what they read
+        // (pack_fence).  Readers of the records wait for the arena's ready event.  (The timers are idle then: profiled steps are serial.)
+        hipStream_t ps = h->stream;
+        if (defer) {
+            HIPCHK(hipEventRecord(h->pack_go[h->rec_cur], h->stream));
+            HIPCHK(hipStreamWaitEvent(h->pack_stream, h->pack_go[h->rec_cur], 0));
+            ps = h->pack_stream;
+        }
+        { Timer t(h, "k_pack_desc"); hipLaunchKernelGGL(k_pack_desc, dim3(nblocks(h->run.n_active_rows, 256)), dim3(256), 0, ps, za); }
         if (h->run.n_res_rows > 0) {
             PackResArgs pr{h->pack_desc.as<PackDesc>() + h->run.n_front_rows, h->fin.as<int16_t>(), za.itv_left, za.itv_right, za.records, za.rec_dest, za.rec_capacity, h->run.n_res_rows, za.spr, (i32)d.dt};
-            Timer t(h, "k_pack_res"); hipLaunchKernelGGL(k_pack_res, dim3(nblocks(h->run.n_res_rows, 4)), dim3(256), 0, h->stream, pr);
+            Timer t(h, "k_pack_res"); hipLaunchKernelGGL(k_pack_res, dim3(nblocks(h->run.n_res_rows, 4)), dim3(256), 0, ps, pr);
         }
         if (h->run.n_front_rows > 0) {
             Timer t(h, "k_pack"); const dim3 grid(nblocks(h->run.n_front_rows, 4));
-            with_noise_kind(r.noise_kind, [&](auto nk) { hipLaunchKernelGGL(k_pack<decltype(nk)::value>, grid, dim3(256), 0, h->stream, d, za); });
+            with_noise_kind(r.noise_kind, [&](auto nk) { hipLaunchKernelGGL(k_pack<decltype(nk)::value>, grid, dim3(256), 0, ps, d, za); });
+        }
+        if (defer) {
+            HIPCHK(hipEventRecord(h->rec_ready[h->rec_cur], h->pack_stream));
+            h->pack.deferred(h->rec_cur);
         }
     }
     {   // totals of wfs_get_counts: afterpulse sets carry no truth (rawdata.py:322-323)
@@ -2346,6 +2417,7 @@ int wfs_copy_records(wfs_handle *h, void *dst, int64_t cap)
 try {
     if (!h || !run_finished(h)) return WFS_E_STATE;
     if (cap < h->run.n_records) return h->fail(WFS_E_CAPACITY, "record buffer too small");
+    TRY(pack_wait(h));
     if (h->run.n_records) HIPCHK(hipMemcpy(dst, h->records_buf().p, (size_t)h->run.n_records * WFS_RECORD_BYTES, hipMemcpyDeviceToHost));
     return WFS_OK;
 } WFS_CATCH(h)
@@ -2354,6 +2426,7 @@ int wfs_copy_records_range(wfs_handle *h, void *dst, int64_t first, int64_t coun
 try {
     if (!h || !run_finished(h)) return WFS_E_STATE;
     if (first < 0 || count < 0 || first + count > h->run.n_records) return h->fail(WFS_E_INVALID, "record range outside the batch");
+    TRY(pack_wait(h));
     if (count) HIPCHK(hipMemcpy(dst, (const uint8_t *)h->records_buf().p + (size_t)first * WFS_RECORD_BYTES, (size_t)count * WFS_RECORD_BYTES, hipMemcpyDeviceToHost));
     return WFS_OK;
 } WFS_CATCH(h)
@@ -2373,6 +2446,8 @@ try {
     if (!h || !run_finished(h)) return WFS_E_STATE;
     if (first < 0 || count < 0 || first + count > h->run.n_records) return h->fail(WFS_E_INVALID, "record range outside the batch");
     HIPCHK(hipSetDevice(h->device));
+    // (the copy stream waits for the packers of this arena; the host does not, and the pack stays pending for the next run's fence)
+    if (h->pack.must_wait()) HIPCHK(hipStreamWaitEvent(h->copy_stream, h->rec_ready[h->pack.arena], 0));
     if (count) HIPCHK(hipMemcpyAsync(dst, (const uint8_t *)h->records_buf().p + (size_t)first * WFS_RECORD_BYTES, (size_t)count * WFS_RECORD_BYTES, hipMemcpyDeviceToHost, h->copy_stream));
     HIPCHK(hipEventRecord(h->rec_copied[h->rec_cur], h->copy_stream));
     h->rec_pending[h->rec_cur] = true;
@@ -2393,6 +2468,7 @@ int wfs_copy_records_dev(wfs_handle *h, void *dst, int64_t cap)
 try {
     if (!h || !run_finished(h)) return WFS_E_STATE;
     if (cap < h->run.n_records) return h->fail(WFS_E_CAPACITY, "record buffer too small");
+    TRY(pack_wait(h));
     if (h->run.n_records) { HIPCHK(hipMemcpyAsync(dst, h->records_buf().p, (size_t)h->run.n_records * WFS_RECORD_BYTES, hipMemcpyDeviceToDevice, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); }
     return WFS_OK;
 } WFS_CATCH(h)
@@ -2445,6 +2521,7 @@ try {
     // unpack the records: fragments of one interval are consecutive
     if (!h || !run_finished(h)) return WFS_E_STATE;
     std::vector<uint8_t> rec((size_t)h->run.n_records * WFS_RECORD_BYTES);
+    TRY(pack_wait(h));
     if (h->run.n_records) HIPCHK(hipMemcpy(rec.data(), h->records_buf().p, rec.size(), hipMemcpyDeviceToHost));
     i64 k = 0;
     for (i64 r = 0; r < h->run.n_records; r++) {
@@ -2743,6 +2820,7 @@ int wfs_set_noise_model(wfs_handle *h, int32_t n_channels, int32_t n_values, int
 try {
     if (!h) return WFS_E_INVALID;
     HIPCHK(hipSetDevice(h->device));
+    TRY(pack_wait(h));          // (pending packers read the tables this call replaces)
     if (n_channels == 0) {
         HIPCHK(hipStreamSynchronize(h->stream));
         h->noise_moves(h->noise_state().model_cleared());
@@ -2783,6 +2861,7 @@ try {
     const NoiseModelState &m = h->noise;
     if (!m.set()) return h->fail(WFS_E_STATE, "wfs_set_noise_colour: no noise model is set");
     HIPCHK(hipSetDevice(h->device));
+    TRY(pack_wait(h));          // (pending packers read the tables this call replaces)
     if (n_taps == 0) {
         HIPCHK(hipStreamSynchronize(h->stream));
         // (the cells of the common streams leave the device with them)
@@ -2811,6 +2890,7 @@ try {
     if (!h) return WFS_E_INVALID;
     if (!h->noise.set()) return h->fail(WFS_E_STATE, "wfs_set_noise_slow: no noise model is set");
     HIPCHK(hipSetDevice(h->device));
+    TRY(pack_wait(h));          // (pending packers read the tables this call replaces)
     if (n_levels == 0) {
         HIPCHK(hipStreamSynchronize(h->stream));
         h->noise_moves(h->noise_state().slow_cleared());
