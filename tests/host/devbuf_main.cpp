@@ -1,4 +1,4 @@
-// Drives DevBuf (wfsim_amd/csrc/wfs_devbuf.h) on the host: a counting malloc / free pair plays the device allocator.
+// Drives DevBuf and DevArr (wfsim_amd/csrc/wfs_devbuf.h) on the host: a counting malloc / free pair plays the device allocator.
 // Prints one line "<case> ok|FAILED ..." per case and exits 0 when every case holds (tests/test_devbuf_cpu.py).
 #include "wfs_devbuf.h"
 
@@ -12,6 +12,17 @@
 static_assert(!std::is_copy_constructible<DevBuf>::value, "a DevBuf has one owner");
 static_assert(!std::is_copy_assignable<DevBuf>::value, "a DevBuf has one owner");
 static_assert(std::is_nothrow_move_constructible<DevBuf>::value && std::is_nothrow_move_assignable<DevBuf>::value, "a vector of them moves");
+
+// a typed array has one owner too, and is no DevBuf: what takes a DevBuf and a size in bytes (the engine's helper for sort_tmp and the
+// record arenas, ensure_bytes here) does not take it
+struct Wide { char c[64]; };
+static_assert(!std::is_copy_constructible<DevArr<int>>::value && !std::is_copy_assignable<DevArr<Wide>>::value, "a DevArr has one owner");
+static_assert(std::is_nothrow_move_constructible<DevArr<int>>::value && std::is_nothrow_move_assignable<DevArr<Wide>>::value, "a vector of them moves");
+inline int ensure_bytes(DevBuf &b, size_t bytes) { return b.ensure(bytes); }
+template <class B, class = void> struct takes_bytes : std::false_type {};
+template <class B> struct takes_bytes<B, std::void_t<decltype(ensure_bytes(std::declval<B &>(), (size_t)1))>> : std::true_type {};
+static_assert(takes_bytes<DevBuf>::value && !takes_bytes<DevArr<char>>::value && !takes_bytes<DevArr<double>>::value, "a byte count for an element count does not compile");
+static_assert(!std::is_convertible<DevArr<int> &, DevBuf &>::value && sizeof(DevArr<double>) == sizeof(DevBuf), "a DevArr owns a DevBuf and nothing else");
 
 static long n_alloc = 0, n_free = 0, n_bad_free = 0;
 static size_t last_bytes = 0;
@@ -48,6 +59,25 @@ static void report(const char *name, bool ok)
 }
 
 struct Several { DevBuf a, b, c; std::vector<DevBuf> v; DevBuf pair[2]; };
+struct SeveralTyped { DevArr<char> a; DevArr<double> b; DevArr<Wide> c; std::vector<DevArr<short>> v; DevArr<int> pair[2]; DevBuf bytes; };
+
+// ensure(count) of a DevArr<T> allocates what DevBuf::ensure(count * sizeof(T)) does, block for block: nothing, a first block, none for
+// a smaller count, none at the capacity, a grown one
+template <class T> static bool arr_matches_buf()
+{
+    bool ok = true;
+    for (size_t count : {(size_t)0, (size_t)1, (size_t)7, (size_t)1000, (size_t)100003}) {
+        DevArr<T> a; DevBuf b;
+        const long a0 = n_alloc;
+        ok = ok && a.p() == nullptr && a.grows(count) && a.ensure(count) == 0 && last_bytes == a.buf().cap && b.ensure(count * sizeof(T)) == 0 && last_bytes == b.cap;
+        ok = ok && a.buf().cap == b.cap && (void *)a.p() == a.buf().p && a.p() && n_alloc == a0 + 2 && !a.grows(count);
+        const size_t fits = a.buf().cap / sizeof(T);
+        ok = ok && a.ensure(count / 2) == 0 && a.ensure(fits) == 0 && n_alloc == a0 + 2 && a.grows(fits + 1) == b.grows((fits + 1) * sizeof(T));
+        ok = ok && a.ensure(fits + 1) == 0 && b.ensure((fits + 1) * sizeof(T)) == 0 && a.buf().cap == b.cap && n_alloc == a0 + 4;
+        ok = ok && live_bytes() == (long)(a.buf().cap + b.cap);
+    }
+    return ok && live() == 0;
+}
 
 int main()
 {
@@ -156,5 +186,50 @@ int main()
         report("struct", ok);
     }
     report("struct_scope_end", live() == 0 && live_bytes() == 0 && blocks.empty());
+    report("arr_sizes", arr_matches_buf<char>() && arr_matches_buf<short>() && arr_matches_buf<int>() && arr_matches_buf<double>() && arr_matches_buf<Wide>());
+    {   // counts of 0 and 1, a grow that frees the old block once, a failed allocation, reset
+        DevArr<double> a;
+        const long f0 = n_free, a0 = n_alloc;
+        bool ok = a.ensure(0) == 0 && a.buf().cap == 16 + 16 / 8 + 256 && live() == 1;
+        ok = ok && a.ensure(1) == 0 && n_alloc == a0 + 1;                  // (one double fits the block of nothing)
+        double *p0 = a.p();
+        ok = ok && a.ensure(1000) == 0 && a.buf().cap == 8000 + 8000 / 8 + 256 && n_free == f0 + 1 && n_alloc == a0 + 2 && blocks.count(p0) == 0 && blocks.count(a.p()) == 1 && live() == 1;
+        fail_next = true;
+        ok = ok && a.ensure(100000) == 2 && a.p() == nullptr && a.buf().cap == 0 && live() == 0 && live_bytes() == 0;
+        ok = ok && a.ensure(3) == 0 && live() == 1;
+        a.reset(); a.reset();
+        ok = ok && a.p() == nullptr && live() == 0;
+        report("arr_grow", ok);
+    }
+    {   // moves: the source is empty, nothing is freed twice; arrays of different T in one struct and in a vector
+        const long f0 = n_free;
+        DevArr<int> a;
+        bool ok = a.ensure(75) == 0;
+        int *pa = a.p(); const size_t ca = a.buf().cap;
+        DevArr<int> b(std::move(a));
+        ok = ok && a.p() == nullptr && a.buf().cap == 0 && b.p() == pa && b.buf().cap == ca && n_free == f0 && live() == 1;
+        DevArr<int> c;
+        ok = ok && c.ensure(10) == 0 && live() == 2;
+        c = std::move(b);
+        ok = ok && b.p() == nullptr && c.p() == pa && n_free == f0 + 1 && live() == 1 && a.ensure(2) == 0 && live() == 2;
+        std::vector<DevArr<Wide>> v(3);
+        for (auto &w : v) ok = ok && w.ensure(5) == 0;
+        Wide *p1 = v[1].p();
+        v.reserve(v.capacity() * 4 + 7);
+        ok = ok && v[1].p() == p1 && live() == 5;
+        v.erase(v.begin());
+        ok = ok && live() == 4;
+        auto s = new SeveralTyped();
+        ok = ok && s->a.ensure(10) == 0 && s->c.ensure(300) == 0 && s->pair[1].ensure(0) == 0 && s->bytes.ensure(99) == 0;
+        s->v.resize(4);
+        ok = ok && s->v[2].ensure(77) == 0 && live() == 9;
+        // (the address of the block's DevBuf tells buffers of different T apart: the engine's pack_uses)
+        ok = ok && (const void *)&s->a.buf() != (const void *)&s->b.buf() && &s->bytes != &s->c.buf();
+        SeveralTyped t(std::move(*s));
+        delete s;
+        ok = ok && live() == 9 && t.a.p() && !t.b.p() && t.c.p() && t.v.size() == 4 && t.v[2].p() && t.pair[1].p() && t.bytes.p;
+        report("arr_move", ok);
+    }
+    report("arr_scope_end", live() == 0 && live_bytes() == 0 && blocks.empty());
     return failures ? 1 : 0;
 }

@@ -42,7 +42,7 @@ namespace {
 
 struct Pmf { std::vector<double> p; long vmin = 0; };      // probability mass function of an integer delay term
 
-struct ApElem { int n_bins_delay = 0, n_bins_amp = 0, amp_2d = 0, is_uniform = 0; double delay_bin = 0, amp_bin = 0; DevBuf delay_cdf, amp_cdf, prob, thr, delay_guide, amp_guide;
+struct ApElem { int n_bins_delay = 0, n_bins_amp = 0, amp_2d = 0, is_uniform = 0; double delay_bin = 0, amp_bin = 0; DevArr<double> delay_cdf, amp_cdf, prob; DevArr<u32> thr; DevArr<ApGuide> delay_guide, amp_guide;
                 std::vector<double> prob_h; double thr_mod = -1.0;      // host copy of the probability column; modifier the thresholds were built for
                 int delay_sorted = 0, amp_sorted = 0; };
 
@@ -61,6 +61,12 @@ enum : int {
     DBG_CHECK_LAUNCHES = 8,      // check every kernel launch on the spot
     DBG_KEEP_PHOTONS = 16        // store the photons of tile-generated instructions
 };
+
+// elements per item of the arrays that hold several, as the kernels index them (wfs_kernels.h, wfs_tilegen.h)
+constexpr size_t TRUTH_PER_SET = 16;       // truth[set][16]: the sums of a pulse set, the moments of its photon times behind them (k_truth_reduce)
+constexpr size_t TRUTH_PER_TILE = 8;       // tile_truth[tile][8]: the partial sums of one tile
+constexpr size_t STAT_PER_INS = 4;         // el_stat[ins][4]: n, sum t, sum t^2 of its electrons
+constexpr size_t MINMAX = 2;               // (min, max) pairs of tminmax[set] and el_minmax[ins]; (first, last) emitter of blk_e[block]
 
 }  // namespace
 
@@ -98,16 +104,16 @@ struct wfs_handle {
     std::vector<double> h_templates, h_gains, h_lum_x, h_lum_t;      // host copies: [dt][tlen]; per channel; the luminescence table (enters the S2 delay table)
     ApElem ap[WFS_MAX_AP];
     // model variants of the photon delays
-    std::vector<DevBuf> x_alias; std::vector<AliasTab> h_tabs; i32 n_user_tabs = 0;
+    std::vector<DevArr<uint2>> x_alias; std::vector<AliasTab> h_tabs; i32 n_user_tabs = 0;
     std::vector<Pmf> base_pmf;           // transit time only, S1 terms, S2 terms, S2 terms without the 'simple' luminescence
     i32 prop_nz = 0, prop_nu = 0; double prop_u0 = 0, prop_du = 1;      // wfs_set_s1_propagation
     i32 gg_n = 0, gg_L = 0;              // 'garfield_gas_gap' luminescence (wfs_set_gas_gap_model)
     // pattern maps evaluated on the device
-    struct PatternMap { bool set = false; i32 dims = 0, n[3] = {1, 1, 1}, w[3] = {0, 0, 0}, n_map_ch = 0; double lo[3] = {0, 0, 0}, hgrid[3] = {1, 1, 1}; DevBuf values;
-                        i64 n_points = 0; DevBuf points;
-                        DevBuf cell_start, cell_pts; i32 cnx = 0, cny = 0; double cell_lo[2] = {0, 0}, cell_h = 1; } pmap[2];       // 2-D point lists: cell index (transverse diffusion)
+    struct PatternMap { bool set = false; i32 dims = 0, n[3] = {1, 1, 1}, w[3] = {0, 0, 0}, n_map_ch = 0; double lo[3] = {0, 0, 0}, hgrid[3] = {1, 1, 1}; DevArr<float> values;
+                        i64 n_points = 0; DevArr<double> points;
+                        DevArr<i32> cell_start, cell_pts; i32 cnx = 0, cny = 0; double cell_lo[2] = {0, 0}, cell_h = 1; } pmap[2];       // 2-D point lists: cell index (transverse diffusion)
     // scalar maps (kind 0: weighted nearest neighbours on a regular grid, 1: on a point list, 2: RectBivariateSpline)
-    struct ScalarMap { int kind = 0; int nv = 1; PatternMap g; i32 nx = 0, ny = 0, kx = 0, ky = 0; DevBuf tx, ty, c; };      // kind 0 / 1: nearest neighbours on a grid / a point list, 2: spline, 3: multilinear grid
+    struct ScalarMap { int kind = 0; int nv = 1; PatternMap g; DevArr<double> values; i32 nx = 0, ny = 0, kx = 0, ky = 0; DevArr<double> tx, ty, c; };      // kind 0 / 1: nearest neighbours on a grid / a point list, 2: spline, 3: multilinear grid
     std::vector<std::unique_ptr<ScalarMap>> smaps;
     // the noise model, its colour and its slow levels (wfs_noise.h): written by the transitions alone, which name the device buffers
     // (nm_cells, nc_buf: NoiseColourLayout, ns_buf: NoiseSlowLayout) that go with what they reset
@@ -143,33 +149,37 @@ struct wfs_handle {
     BatchRun state() { return BatchRun{batch, run}; }        // the transitions of wfs_batch.h: the only writers of batch.kind and run.stage
 
     // ---------------- device buffers: capacity, not state.  They grow on demand, free themselves, and no reset touches them
-    DevBuf set_gid, opt_t, opt_item, opt_first, opt_last, opt_ch, opt_time;
-    DevBuf t_templates, t_spe, t_gains, t_thr_truth, t_thr_zle, t_lumx, t_lumt, t_noise, t_noise_f;
-    DevBuf ins_type, ins_time, ins_amp, ins_gid, ins_p, ins_dm, ins_ds, ins_sc, ins_cdfrow, cdf_table, chan_alias, em_off, em_zg, ins_embase, ins_set, set_ins_off, set_ins_list;
-    DevBuf set_cluster, set_t0, set_mode, cl_tmin, cl_gid, cl_end, cl_group;
-    DevBuf em_time, em_nph, em_ins, em_ph_off, el_stat, el_minmax, blk_e, blk_base, blk_cnt, blk_ins, eblk_ins, ins_ph0, blk_desc;
-    DevBuf tile_count, tile_off, tile_cursor, tile_tmin, tile_tmax, active_tiles, sparse_tiles, dense_tiles, wave_tiles;
-    DevBuf ph, ph_gain, ph_idx, ap_key, order_list, order_list2, ins_sbase, tile_tail, tile_tailbase, ins_fullsort;
-    DevBuf grp_lo, grp_hi, grp_left, grp_right, grp_ixrand, grp_gid;
-    DevBuf row_lo, row_hi, acc_len, acc_off, itv_cap, itv_off, active_rows, raw;
-    DevBuf itv_left, itv_right, itv_n, row_nrec, rec_off;
-    DevBuf truth, tminmax, tile_truth, tile_desc, gather_idx, gather_out, currents, cur_len, cur_off, row_dbg, row_dbg_len, row_dbg_off;
-    DevBuf stamps, row_desc, rec_key, rec_key2, rec_val, rec_val2, rec_dest, sort_tmp, scan_tmp, scal, noise_override, nm_cells, nc_buf, ns_buf, pack_desc;
-    DevBuf row_bad, fin_len, res_cnt, fin_off, res_toff, res_desc, fin, res_long, res_rows;      // resident rows (k_row_pulse)
-    DevBuf tt_alias[6], ap_ins, ap_ch, ap_t, ap_gain, ap_cand, ap_args_dev, ap_seg;
-    DevBuf d_tabs, prop_top, prop_bot, ins_tab, ins_tabb, ins_pzi, ins_pzf, gg_inv, ins_gg, ins_ggw, ins_ggsum;
-    DevBuf pois_cdf, pois_kmin;         // Poisson tables of the secondary gain per instruction (k_poisson_tables)
-    DevBuf smap_pos, smap_out, smap_nb_idx, smap_nb_w, ins_aft;
+    // (the element type stands in the declaration and every size is a count: wfs_devbuf.h; bytes: the record arenas above and sort_tmp)
+    DevArr<u32> set_gid, opt_item; DevArr<i32> opt_t, opt_first, opt_last, opt_ch; DevArr<i64> opt_time;
+    DevArr<double> t_templates, t_spe, t_gains, t_thr_truth, t_lumx, t_lumt, t_noise_f; DevArr<i64> t_thr_zle; DevArr<int16_t> t_noise;
+    DevArr<int8_t> ins_type; DevArr<i64> ins_time, em_off, set_ins_off; DevArr<i32> ins_amp, ins_cdfrow, ins_set, set_ins_list; DevArr<u32> ins_gid, ins_embase;
+    DevArr<double> ins_p, ins_dm, ins_ds, ins_sc, cdf_table, em_zg; DevArr<uint2> chan_alias;
+    DevArr<i32> set_cluster, set_mode, cl_group; DevArr<i64> set_t0, cl_tmin, cl_end; DevArr<u32> cl_gid;
+    DevArr<i64> em_time, em_ph_off, el_minmax, blk_e, ins_ph0; DevArr<i32> em_nph, em_ins, blk_ins, eblk_ins; DevArr<double> el_stat; DevArr<u32> blk_base;
+    DevArr<unsigned short> blk_cnt; DevArr<BlockDesc> blk_desc;
+    DevArr<i32> tile_count, tile_cursor, tile_tmin, tile_tmax, active_tiles, sparse_tiles, dense_tiles, wave_tiles; DevArr<i64> tile_off;
+    DevArr<PhotonRec> ph; DevArr<double> ph_gain; DevArr<u32> ph_idx, ap_key, ins_sbase; DevArr<OrderRange> order_list, order_list2; DevArr<i32> tile_tail, tile_tailbase, ins_fullsort;
+    DevArr<i64> grp_lo, grp_hi, grp_left, grp_right, grp_ixrand; DevArr<u32> grp_gid;
+    DevArr<i64> row_lo, row_hi, acc_off, itv_off; DevArr<i32> acc_len, itv_cap, active_rows, raw;
+    DevArr<i64> itv_left, itv_right, rec_off; DevArr<i32> itv_n, row_nrec;
+    DevArr<double> truth, tile_truth, currents; DevArr<i64> tminmax, gather_idx, gather_out, cur_off, row_dbg_off; DevArr<TileDesc> tile_desc; DevArr<i32> row_dbg; DevArr<TileTimeReq> gather_req;      // (wfs_gather_photon_times: the requests of tile-generated instructions; gather_idx holds those of the block generator)
+    DevArr<unsigned long long> stamps; DevArr<RowDesc> row_desc; DevArr<u64> rec_key, rec_key2; DevArr<u32> rec_val, rec_val2, rec_dest; DevBuf sort_tmp;      // (sort_tmp: rocPRIM's scratch)
+    DevArr<i64> scan_tmp, noise_override; DevArr<WfsScal> scal; DevArr<NoiseCell> nm_cells; DevArr<i32> nc_buf, ns_buf; DevArr<PackDesc> pack_desc;
+    DevArr<i32> row_bad, fin_len, res_cnt, res_long; DevArr<i64> fin_off, res_toff; DevArr<TileDesc> res_desc; DevArr<int16_t> fin; DevArr<ResRow> res_rows;      // resident rows (k_row_pulse)
+    DevArr<uint2> tt_alias[6]; DevArr<i32> ap_ins, ap_ch, ap_t; DevArr<double> ap_gain; DevArr<ApCand> ap_cand; DevArr<ApArgs> ap_args_dev; DevArr<ApSeg> ap_seg;
+    DevArr<AliasTab> d_tabs; DevArr<double> prop_top, prop_bot, ins_pzf, gg_inv, ins_ggw; DevArr<i32> ins_tab, ins_tabb, ins_pzi, ins_gg; DevArr<i64> ins_ggsum;
+    DevArr<double> pois_cdf; DevArr<i32> pois_kmin;         // Poisson tables of the secondary gain per instruction (k_poisson_tables)
+    DevArr<double> smap_pos, smap_out, smap_nb_w, ins_aft; DevArr<i64> smap_nb_idx;
     // transverse diffusion with field maps: instructions whose pattern is averaged over their electrons (k_diffuse_patterns)
-    DevBuf ins_sigr, ins_siga, diff_row_ins, diff_row_id, diff_pre;
-    DevBuf map_row_ins[2], map_row_id[2], map_x, map_y, map_z, map_nb_idx[2], map_nb_w[2];
+    DevArr<double> ins_sigr, ins_siga, diff_pre; DevArr<i32> diff_row_ins; DevArr<i64> diff_row_id;
+    DevArr<i32> map_row_ins[2]; DevArr<i64> map_row_id[2], map_nb_idx[2]; DevArr<float> map_x, map_y, map_z; DevArr<double> map_nb_w[2];
     // tile-local generation (wfs_tilegen.h): S2 instructions whose photons are made inside the pulse workgroup
-    DevBuf huge_start, huge_cbeg, huge_keys, huge_keys2, huge_vals, huge_vals2, huge_rec, huge_gain;      // ordering of tiles beyond TILE_ORDER_MAX photons
-    DevBuf row_pmax, ins_fused, ins_nsurv, ins_bcap, ins_bcap_all, ins_boff, et32, ftiles, tbuf, row_cnt, row_tile, tile_done, tile_kind;
+    DevArr<i64> huge_start, huge_cbeg; DevArr<u32> huge_keys, huge_keys2, huge_vals, huge_vals2; DevArr<PhotonRec> huge_rec; DevArr<double> huge_gain;      // ordering of tiles beyond TILE_ORDER_MAX photons
+    DevArr<double> row_pmax; DevArr<i32> ins_fused, ins_nsurv, ins_bcap, ins_bcap_all, et32, tbuf, row_cnt, row_tile, tile_done; DevArr<i64> ins_boff; DevArr<FTile> ftiles; DevArr<int8_t> tile_kind;
     // the bottom-array sum row (k_sum_signal): range, length, chunks, offsets per window; its samples sit behind the accumulators in raw, from run.sum_base
-    DevBuf sum_lo, sum_hi, sum_len, sum_nchunk, sum_off, sum_chunk_off;
+    DevArr<i64> sum_lo, sum_hi, sum_off, sum_chunk_off; DevArr<i32> sum_len, sum_nchunk;
 
-    // what is not a DevBuf; the buffers, and the members that hold some, free themselves after this body
+    // what is not a device buffer; the buffers, and the members that hold some, free themselves after this body
     ~wfs_handle()
     {
         clear_times(times);
@@ -221,39 +231,51 @@ int pack_fence(wfs_handle *h)
 // the buffers the packers read or write (the noise tables behind WfsDev apart: their setters wait on the host)
 bool pack_uses(const wfs_handle *h, const DevBuf &b)
 {
-    for (const DevBuf *q : {&h->pack_desc, &h->row_desc, &h->rec_off, &h->itv_n, &h->itv_left, &h->itv_right, &h->rec_dest, &h->tbuf, &h->raw, &h->fin,
-                            &h->records_ab[0], &h->records_ab[1]})
+    for (const DevBuf *q : {&h->pack_desc.buf(), &h->row_desc.buf(), &h->rec_off.buf(), &h->itv_n.buf(), &h->itv_left.buf(), &h->itv_right.buf(), &h->rec_dest.buf(),
+                            &h->tbuf.buf(), &h->raw.buf(), &h->fin.buf(), &h->records_ab[0], &h->records_ab[1]})
         if (q == &b) return true;
     return false;
 }
-
-// (a grow frees the old block: one of a buffer that pending packers use waits for them on the host first)
-int ensure(wfs_handle *h, DevBuf &b, size_t bytes)
-{
-    if (b.cap < (bytes ? bytes : 16) && h->pack.must_wait() && pack_uses(h, b)) { int rc = pack_wait(h); if (rc) return rc; }
-    if (int e = b.ensure(bytes)) return h->fail(WFS_E_HIP, std::string("hipMalloc: ") + hipGetErrorString((hipError_t)e));
-    return WFS_OK;
-}
-
-int upload(wfs_handle *h, DevBuf &b, const void *src, size_t bytes)
-{
-    int rc = ensure(h, b, bytes); if (rc) return rc;
-    if (bytes) HIPCHK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, h->stream));
-    return WFS_OK;
-}
-
-// n elements of a device buffer on the host, a blocking copy.  A HIP error is recorded on the handle (fail) and thrown: the firewall of
-// the C ABI (wfs_caught) hands its code back like the return of a HIPCHK.
-struct WfsHipError { int code; };
-template <class T>
-std::vector<T> download(wfs_handle *h, const DevBuf &b, size_t n)
-{
-    std::vector<T> v(n);
-    if (n) { const hipError_t e = hipMemcpy(v.data(), b.p, n * sizeof(T), hipMemcpyDeviceToHost); if (e != hipSuccess) throw WfsHipError{h->fail(WFS_E_HIP, std::string("hipMemcpy (download): ") + hipGetErrorString(e))}; }
-    return v;
-}
+template <class T> bool pack_uses(const wfs_handle *h, const DevArr<T> &a) { return pack_uses(h, a.buf()); }
 
 #define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+
+// Room for n in the buffer's own unit: elements of a DevArr<T>, bytes of a DevBuf (the record arenas, sort_tmp).
+// (a grow frees the old block: one of a buffer that pending packers use waits for them on the host first)
+template <class B> int ensure(wfs_handle *h, B &b, size_t n)
+{
+    if (b.grows(n) && h->pack.must_wait() && pack_uses(h, b)) TRY(pack_wait(h));
+    if (int e = b.ensure(n)) return h->fail(WFS_E_HIP, std::string("hipMalloc: ") + hipGetErrorString((hipError_t)e));
+    return WFS_OK;
+}
+
+// Copies between typed pointers are sized by the element: the bytes of n elements.  The two sides name one type, or two integer types
+// of one size and signedness (the ABI's int64_t is long, i64 is long long).
+template <class D, class S> constexpr size_t copy_bytes(size_t n)
+{
+    static_assert(std::is_same<D, S>::value || (std::is_integral<D>::value && std::is_integral<S>::value && sizeof(D) == sizeof(S) && std::is_signed<D>::value == std::is_signed<S>::value),
+                  "source and destination of a copy hold the same elements");
+    return n * sizeof(S);
+}
+// n elements on the handle's stream; n elements of device memory to the host, a blocking copy
+template <class D, class S> int copy_async(wfs_handle *h, D *dst, const S *src, size_t n, hipMemcpyKind kind) { HIPCHK(hipMemcpyAsync(dst, src, copy_bytes<D, S>(n), kind, h->stream)); return WFS_OK; }
+template <class D, class S> int copy_out(wfs_handle *h, D *dst, const S *src, size_t n) { HIPCHK(hipMemcpy(dst, src, copy_bytes<D, S>(n), hipMemcpyDeviceToHost)); return WFS_OK; }
+
+template <class T, class S> int upload(wfs_handle *h, DevArr<T> &a, const S *src, size_t count)
+{
+    TRY(ensure(h, a, count));
+    return count ? copy_async(h, a.p(), src, count, hipMemcpyHostToDevice) : WFS_OK;
+}
+
+// n elements of a device array on the host, a blocking copy.  A HIP error is recorded on the handle (fail) and thrown: the firewall of
+// the C ABI (wfs_caught) hands its code back like the return of a HIPCHK.
+struct WfsHipError { int code; };
+template <class T> std::vector<T> download(wfs_handle *h, const DevArr<T> &a, size_t n)
+{
+    std::vector<T> v(n);
+    if (n) if (int rc = copy_out(h, v.data(), a.p(), n)) throw WfsHipError{rc};
+    return v;
+}
 
 // The listed tiles in work-list order with their sample windows, and the offsets of their currents (the total behind the last): what a
 // run with DBG_CURRENTS uploads as cur_off and what wfs_copy_pulses hands out.
@@ -262,9 +284,9 @@ ListedTiles listed_tiles(wfs_handle *h)
 {
     const WfsDev &d = h->dev;
     ListedTiles r;
-    r.tile = download<i32>(h, h->active_tiles, (size_t)h->run.n_active_tiles);
-    const std::vector<i32> tmn = download<i32>(h, h->tile_tmin, (size_t)h->batch.n_tiles), tmx = download<i32>(h, h->tile_tmax, (size_t)h->batch.n_tiles);
-    const std::vector<i64> t0 = download<i64>(h, h->set_t0, (size_t)h->batch.n_sets);
+    r.tile = download(h, h->active_tiles, (size_t)h->run.n_active_tiles);
+    const std::vector<i32> tmn = download(h, h->tile_tmin, (size_t)h->batch.n_tiles), tmx = download(h, h->tile_tmax, (size_t)h->batch.n_tiles);
+    const std::vector<i64> t0 = download(h, h->set_t0, (size_t)h->batch.n_sets);
     r.win.resize(r.tile.size()); r.off.assign(r.tile.size() + 1, 0);
     for (size_t k = 0; k < r.tile.size(); k++) {
         const i32 tile = r.tile[k];
@@ -280,10 +302,10 @@ ListedRows listed_rows(wfs_handle *h)
 {
     const WfsDev &d = h->dev;
     const size_t CG = (size_t)h->batch.n_clusters + 1;
-    const std::vector<i32> ar = download<i32>(h, h->active_rows, (size_t)h->run.n_active_rows);
-    const std::vector<i64> lo = download<i64>(h, h->row_lo, CG * d.n_tpc), hi = download<i64>(h, h->row_hi, CG * d.n_tpc);
+    const std::vector<i32> ar = download(h, h->active_rows, (size_t)h->run.n_active_rows);
+    const std::vector<i64> lo = download(h, h->row_lo, CG * d.n_tpc), hi = download(h, h->row_hi, CG * d.n_tpc);
     std::vector<i64> slo, shi;
-    if (d.sum_channel >= 0) { slo = download<i64>(h, h->sum_lo, CG); shi = download<i64>(h, h->sum_hi, CG); }
+    if (d.sum_channel >= 0) { slo = download(h, h->sum_lo, CG); shi = download(h, h->sum_hi, CG); }
     ListedRows r;
     r.slot.resize(ar.size()); r.lo.resize(ar.size()); r.hi.resize(ar.size()); r.off.assign(ar.size() + 1, 0);
     for (size_t k = 0; k < ar.size(); k++) {
@@ -351,12 +373,13 @@ struct FillGroup {
         n++; longest = std::max(longest, bytes);
         return WFS_OK;
     }
-    int bytes(void *p, size_t nbytes, unsigned char v) { const u32 w = 0x01010101u * v; return add(p, nbytes, w, w, w, w); }
-    int zero(void *p, size_t nbytes) { return add(p, nbytes, 0, 0, 0, 0); }
-    int i32s(void *p, i64 count, i32 v) { return add(p, (size_t)count * 4, (u32)v, (u32)v, (u32)v, (u32)v); }
-    int i64s(void *p, i64 count, i64 v) { return pairs(p, count, v, v); }
+    // count elements from p on (p may point into an array: tile_count + TP): every byte 0 or 0xff, or the value v
+    template <class T> int zero(T *p, i64 count) { return add(p, (size_t)count * sizeof(T), 0, 0, 0, 0); }
+    template <class T> int ones(T *p, i64 count) { return add(p, (size_t)count * sizeof(T), ~0u, ~0u, ~0u, ~0u); }
+    int fill(i32 *p, i64 count, i32 v) { return add(p, (size_t)count * sizeof(i32), (u32)v, (u32)v, (u32)v, (u32)v); }
+    int fill(i64 *p, i64 count, i64 v) { return pairs(p, count, v, v); }
     // count i64 that alternate between even and odd
-    int pairs(void *p, i64 count, i64 even, i64 odd) { return add(p, (size_t)count * 8, (u32)(u64)even, (u32)((u64)even >> 32), (u32)(u64)odd, (u32)((u64)odd >> 32)); }
+    int pairs(i64 *p, i64 count, i64 even, i64 odd) { return add(p, (size_t)count * sizeof(i64), (u32)(u64)even, (u32)((u64)even >> 32), (u32)(u64)odd, (u32)((u64)odd >> 32)); }
     int flush()
     {
         if (n == 0) return WFS_OK;
@@ -368,26 +391,24 @@ struct FillGroup {
     }
 };
 
-// exclusive scan i32[n] -> i64[n+1]; total written to the member `total` of the device scalar block
-int scan_into(wfs_handle *h, const i32 *in, i64 n, i64 *outp, i64 WfsScal::*total_member, i64 offset);
-
-int scan(wfs_handle *h, const i32 *in, i64 n, DevBuf &out, i64 WfsScal::*total_member)
-{
-    TRY(ensure(h, out, (size_t)(n + 1) * 8));
-    return scan_into(h, in, n, out.as<i64>(), total_member, 0);
-}
-
-// exclusive scan into a caller-provided range, every output shifted by offset
+// exclusive scan i32[n] -> i64[n+1] into a caller-provided range, every output shifted by offset; total as for scan
 int scan_into(wfs_handle *h, const i32 *in, i64 n, i64 *outp, i64 WfsScal::*total_member, i64 offset)
 {
     i64 nb = (n + SCAN_TILE - 1) / SCAN_TILE; if (nb < 1) nb = 1;
-    TRY(ensure(h, h->scan_tmp, (size_t)nb * 8));
-    i64 *total = &(h->scal.as<WfsScal>()->*total_member);       // (a device address: computed, never dereferenced here)
-    if (n == 0) { h->zero64 = offset; HIPCHK(hipMemcpyAsync(outp, &h->zero64, 8, hipMemcpyHostToDevice, h->stream)); HIPCHK(hipMemsetAsync(total, 0, 8, h->stream)); return WFS_OK; }
-    { Timer t(h, "k_scan_reduce"); hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)nb), dim3(SCAN_TPB), 0, h->stream, in, n, h->scan_tmp.as<i64>()); }
-    { Timer t(h, "k_scan_spine"); hipLaunchKernelGGL(k_scan_spine, dim3(1), dim3(1024), 0, h->stream, h->scan_tmp.as<i64>(), nb, total); }
-    { Timer t(h, "k_scan_down"); hipLaunchKernelGGL(k_scan_down, dim3((unsigned)nb), dim3(SCAN_TPB), 0, h->stream, in, n, h->scan_tmp.as<i64>(), outp, offset); }
+    TRY(ensure(h, h->scan_tmp, (size_t)nb));
+    i64 *total = &(h->scal.p()->*total_member);       // (a device address: computed, never dereferenced here)
+    if (n == 0) { h->zero64 = offset; TRY(copy_async(h, outp, &h->zero64, 1, hipMemcpyHostToDevice)); HIPCHK(hipMemsetAsync(total, 0, sizeof *total, h->stream)); return WFS_OK; }
+    { Timer t(h, "k_scan_reduce"); hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)nb), dim3(SCAN_TPB), 0, h->stream, in, n, h->scan_tmp.p()); }
+    { Timer t(h, "k_scan_spine"); hipLaunchKernelGGL(k_scan_spine, dim3(1), dim3(1024), 0, h->stream, h->scan_tmp.p(), nb, total); }
+    { Timer t(h, "k_scan_down"); hipLaunchKernelGGL(k_scan_down, dim3((unsigned)nb), dim3(SCAN_TPB), 0, h->stream, in, n, h->scan_tmp.p(), outp, offset); }
     return WFS_OK;
+}
+
+// exclusive scan i32[n] -> i64[n+1]; total written to the member `total` of the device scalar block
+int scan(wfs_handle *h, const i32 *in, i64 n, DevArr<i64> &out, i64 WfsScal::*total_member)
+{
+    TRY(ensure(h, out, (size_t)(n + 1)));
+    return scan_into(h, in, n, out.p(), total_member, 0);
 }
 
 // A step boundary: on return *h->h_scal is the device scalar block as of this point of the stream.  By default k_publish writes
@@ -400,7 +421,7 @@ int read_scal(wfs_handle *h)
     if (h->publish && h->own_stream && !(h->debug_bits & DBG_CHECK_LAUNCHES)) {
         const u64 seq = ++h->seq;
         // (the profiled step counts the boundaries that publish: one "k_publish" entry each, none for one that copies)
-        { Timer t(h, "k_publish"); hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, h->stream, h->scal.as<WfsScal>(), h->d_hscal, h->d_hseq, seq); }
+        { Timer t(h, "k_publish"); hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, h->stream, h->scal.p(), h->d_hscal, h->d_hseq, seq); }
         hipError_t qe = hipSuccess;
         const WfsWait w = wfs_wait_seq(h->h_seq, seq, [&]() {
             qe = hipStreamQuery(h->stream);
@@ -410,7 +431,7 @@ int read_scal(wfs_handle *h)
         published = w == WFS_WAIT_OK;
     }
     if (!published) {
-        HIPCHK(hipMemcpyAsync(h->h_scal, h->scal.p, sizeof(WfsScal), hipMemcpyDeviceToHost, h->stream));
+        TRY(copy_async(h, h->h_scal, h->scal.p(), 1, hipMemcpyDeviceToHost));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     if (!h->launch_err.empty()) { const std::string m = h->launch_err; h->launch_err.clear(); return h->fail(WFS_E_HIP, m); }     // (wfs_set_debug bit 3)
@@ -440,11 +461,11 @@ template <class T, class Launch> int noise_probe(wfs_handle *h, const char *fn, 
     if (t0 > I64_MAX - n) return h->fail(WFS_E_INVALID, std::string(fn) + ": t0 + n overflows");
     if (n == 0) return WFS_OK;
     HIPCHK(hipSetDevice(h->device));
-    DevBuf buf;
-    TRY(ensure(h, buf, (size_t)n * sizeof(T)));
-    launch(buf.as<T>());
+    DevArr<T> buf;
+    TRY(ensure(h, buf, (size_t)n));
+    launch(buf.p());
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, buf.p, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+    TRY(copy_async(h, out, buf.p(), (size_t)n, hipMemcpyDeviceToHost));
     HIPCHK(hipStreamSynchronize(h->stream));
     CHECK_LAUNCHES();
     return WFS_OK;
@@ -505,14 +526,14 @@ template <class Cell> static void build_alias(const std::vector<double> &cum, st
     }
 }
 
-static int upload_disc(wfs_handle *h, DevBuf &buf, const std::vector<double> &cum, int vmin, AliasTab &out)
+static int upload_disc(wfs_handle *h, DevArr<uint2> &buf, const std::vector<double> &cum, int vmin, AliasTab &out)
 {
     if (cum.size() > 65000) return h->fail(WFS_E_CAPACITY, "delay table too long (time constant above ~1.5 us)");
     std::vector<uint2> cell; int shift = 31;
     build_alias(cum, cell, shift);
-    TRY(upload(h, buf, cell.data(), cell.size() * sizeof(uint2)));
+    TRY(upload(h, buf, cell.data(), cell.size()));
     HIPCHK(hipStreamSynchronize(h->stream));
-    out.cell = buf.as<uint2>(); out.vmin = vmin; out.shift = shift;
+    out.cell = buf.p(); out.vmin = vmin; out.shift = shift;
     return WFS_OK;
 }
 
@@ -628,8 +649,8 @@ void refresh_dev(wfs_handle *h)
         const NoiseModelState &m = h->noise;
         const bool model = m.set(), colour = m.coloured(), slow = m.levels() > 0, grouped = colour && m.colour.groups > 0;
         const NoiseColourLayout cl(m.channels, m.colour.groups); const NoiseSlowLayout sl(m.channels, m.colour.groups, colour);
-        const i32 *nc = h->nc_buf.as<i32>(), *ns = h->ns_buf.as<i32>();
-        d.nm_cells = model ? h->nm_cells.as<uint2>() : nullptr; d.nm_cells_per_ch = m.k; d.nm_shift = m.shift; d.nm_vmin = m.vmin;
+        const i32 *nc = h->nc_buf.p(), *ns = h->ns_buf.p();
+        d.nm_cells = model ? (const uint2 *)h->nm_cells.p() : nullptr; d.nm_cells_per_ch = m.k; d.nm_shift = m.shift; d.nm_vmin = m.vmin;
         d.noise_channels = model ? m.channels : h->table_channels;
         // slow levels without a colour: the unit taps of the slow buffer are the taps
         d.nc_taps = colour ? nc + cl.taps : (slow ? ns + sl.unit_taps : nullptr); d.nc_n_taps = colour ? m.colour.n_taps : (slow ? 1 : 0);
@@ -715,7 +736,7 @@ try {
     for (int a = 0; a < 2; a++)
         if (hipEventCreateWithFlags(&h->pack_go[a], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&h->rec_ready[a], hipEventDisableTiming) != hipSuccess) return WFS_E_HIP;
     { const char *e = getenv("WFS_PACK_SYNC"); h->pack_sync = e && atoi(e) != 0; }
-    if (ensure(h, h->scal, sizeof(WfsScal)) != WFS_OK) return WFS_E_HIP;
+    if (ensure(h, h->scal, 1) != WFS_OK) return WFS_E_HIP;
     {   // the host copy of the scalar block; mapped and coherent with the sequence word on the cache line behind it where the
         // device may write it (read_scal), else -- or with WFS_HOST_SYNC=copy, A/B runs -- page-locked for the copy as before
         const char *e = getenv("WFS_HOST_SYNC");
@@ -733,8 +754,8 @@ try {
         if (h->publish) { h->d_hscal = (WfsScal *)dp; h->d_hseq = (u64 *)(h->d_hscal + 1); }
     }
 #ifdef WFS_STAMPS
-    if (ensure(h, h->stamps, 4096 * 64 * 8) != WFS_OK) return WFS_E_HIP;
-    hipMemset(h->stamps.p, 0, 4096 * 64 * 8); h->dev.stamps = h->stamps.as<unsigned long long>();
+    if (ensure(h, h->stamps, 4096 * 64) != WFS_OK) return WFS_E_HIP;
+    hipMemset(h->stamps.p(), 0, 4096 * 64 * sizeof(unsigned long long)); h->dev.stamps = h->stamps.p();
 #endif
     refresh_dev(h);
     if (const char *e = getenv("WFS_TAP_SPARSE_MAX")) h->tap_sparse_max = std::min(atoi(e), TAP_LIST_LEN - 1);      // tuning knob of tap_block (results do not depend on it)
@@ -778,7 +799,7 @@ try {
 #ifdef WFS_STAMPS
     {   // diagnostic build: average cycles per workgroup and phase
         std::vector<unsigned long long> all((size_t)4096 * 64); unsigned long long v[64] = {0};
-        if (hipMemcpy(all.data(), h->stamps.p, all.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
+        if (copy_out(h, all.data(), h->stamps.p(), all.size()) == WFS_OK) {
             for (size_t r = 0; r < 4096; r++) for (int i = 0; i < 64; i++) v[i] += all[r * 64 + i];
             for (int i = 0; i < 32; i++) if (v[i + 32]) fprintf(stderr, "stamp %2d: %10.0f cycles/wg  (%llu wgs, %.3e cycles total)\n", i, (double)v[i] / (double)v[i + 32], v[i + 32], (double)v[i]);
         }
@@ -818,10 +839,10 @@ try {
     const size_t stride = (size_t)noise_len + NOISE_PAD;        // (every row followed by its own first samples: wfs_device.h NOISE_PAD)
     std::vector<double> nt(stride * noise_channels);
     for (int64_t i = 0; i < (int64_t)stride; i++) for (int c = 0; c < noise_channels; c++) nt[(size_t)c * stride + i] = noise[(size_t)(i % noise_len) * noise_channels + c];
-    TRY(upload(h, h->t_noise_f, nt.data(), sizeof(double) * nt.size()));
+    TRY(upload(h, h->t_noise_f, nt.data(), nt.size()));
     HIPCHK(hipStreamSynchronize(h->stream));
     WfsDev &d = h->dev;
-    d.noise_f = h->t_noise_f.as<double>(); d.noise = (const int16_t *)d.noise_f; d.noise_len = noise_len; h->table_channels = noise_channels; d.noise_stride = (i32)stride;
+    d.noise_f = h->t_noise_f.p(); d.noise = (const int16_t *)d.noise_f; d.noise_len = noise_len; h->table_channels = noise_channels; d.noise_stride = (i32)stride;
     refresh_dev(h);
     return WFS_OK;
 } WFS_CATCH(h)
@@ -831,7 +852,7 @@ try {
     if (!h || n < 0 || (n > 0 && !ix)) return WFS_E_INVALID;
     TRY(pack_wait(h));
     h->n_noise_override = n;
-    if (n) { TRY(upload(h, h->noise_override, ix, (size_t)n * 8)); HIPCHK(hipStreamSynchronize(h->stream)); }
+    if (n) { TRY(upload(h, h->noise_override, ix, (size_t)n)); HIPCHK(hipStreamSynchronize(h->stream)); }
     return WFS_OK;
 } WFS_CATCH(h)
 int wfs_set_window_carry(wfs_handle *h, int32_t has, int64_t t) try { if (!h) return WFS_E_INVALID; h->carry_has = has; h->carry_runmax = t; return WFS_OK; } WFS_CATCH(h)
@@ -839,7 +860,7 @@ int wfs_copy_cluster_groups(wfs_handle *h, int32_t *group, int64_t cap)
 try {
     if (!h || !run_finished(h)) return WFS_E_STATE;
     if (cap < h->batch.n_clusters) return h->fail(WFS_E_CAPACITY, "cluster buffer too small");
-    HIPCHK(hipMemcpy(group, h->cl_group.p, (size_t)h->batch.n_clusters * 4, hipMemcpyDeviceToHost));
+    TRY(copy_out(h, group, h->cl_group.p(), (size_t)h->batch.n_clusters));
     return WFS_OK;
 } WFS_CATCH(h)
 // (a mode that changes waits for pending packers; a call that leaves it as it is -- one per step is common -- does not)
@@ -855,17 +876,17 @@ try {
     HIPCHK(hipSetDevice(h->device));
     TRY(pack_wait(h));          // (pending packers read the noise table this call replaces)
     const wfs_config &c = h->cfg;
-    TRY(upload(h, h->t_templates, templates, sizeof(double) * c.dt * c.tlen));
-    TRY(upload(h, h->t_spe, spe, sizeof(double) * SPE_ROW_LEN * (size_t)n_spe));
-    TRY(upload(h, h->t_gains, gains, sizeof(double) * c.n_tpc));
-    TRY(upload(h, h->t_thr_truth, thr_truth, sizeof(double) * c.n_rows));
-    TRY(upload(h, h->t_thr_zle, thr_zle, sizeof(int64_t) * c.n_rows));
+    TRY(upload(h, h->t_templates, templates, c.dt * c.tlen));
+    TRY(upload(h, h->t_spe, spe, SPE_ROW_LEN * (size_t)n_spe));
+    TRY(upload(h, h->t_gains, gains, c.n_tpc));
+    TRY(upload(h, h->t_thr_truth, thr_truth, c.n_rows));
+    TRY(upload(h, h->t_thr_zle, thr_zle, c.n_rows));
     WfsDev &d = h->dev;
     d.n_lum = 0; h->h_lum_x.clear(); h->h_lum_t.clear();
     if (lum_x && lum_t && n_lum >= 2) {
         for (int i = 0; i + 1 < n_lum; i++)
             if (!(lum_x[i + 1] >= lum_x[i]) || !(lum_t[i + 1] > lum_t[i])) return h->fail(WFS_E_INVALID, "luminescence table must be increasing");
-        TRY(upload(h, h->t_lumx, lum_x, sizeof(double) * n_lum)); TRY(upload(h, h->t_lumt, lum_t, sizeof(double) * n_lum));
+        TRY(upload(h, h->t_lumx, lum_x, n_lum)); TRY(upload(h, h->t_lumt, lum_t, n_lum));
         d.n_lum = n_lum; h->h_lum_x.assign(lum_x, lum_x + n_lum); h->h_lum_t.assign(lum_t, lum_t + n_lum);
     }
     TRY(build_time_tables(h));         // the S2 delay table contains the luminescence term
@@ -877,12 +898,12 @@ try {
         const size_t stride = (size_t)noise_len + NOISE_PAD;
         std::vector<int16_t> nt(stride * noise_channels);
         for (int64_t i = 0; i < (int64_t)stride; i++) for (int c = 0; c < noise_channels; c++) nt[(size_t)c * stride + i] = noise[(size_t)(i % noise_len) * noise_channels + c];
-        TRY(upload(h, h->t_noise, nt.data(), sizeof(int16_t) * nt.size()));
+        TRY(upload(h, h->t_noise, nt.data(), nt.size()));
         HIPCHK(hipStreamSynchronize(h->stream));
-        d.noise = h->t_noise.as<int16_t>(); d.noise_len = noise_len; h->table_channels = noise_channels; d.noise_stride = (i32)stride;
+        d.noise = h->t_noise.p(); d.noise_len = noise_len; h->table_channels = noise_channels; d.noise_stride = (i32)stride;
     }
-    d.templates = h->t_templates.as<double>(); d.spe = h->t_spe.as<double>(); d.n_spe = n_spe; d.gains = h->t_gains.as<double>();
-    d.thr_truth = h->t_thr_truth.as<double>(); d.thr_zle = h->t_thr_zle.as<i64>(); d.lum_x = h->t_lumx.as<double>(); d.lum_t = h->t_lumt.as<double>();
+    d.templates = h->t_templates.p(); d.spe = h->t_spe.p(); d.n_spe = n_spe; d.gains = h->t_gains.p();
+    d.thr_truth = h->t_thr_truth.p(); d.thr_zle = h->t_thr_zle.p(); d.lum_x = h->t_lumx.p(); d.lum_t = h->t_lumt.p();
     h->h_templates.assign(templates, templates + (size_t)c.dt * c.tlen);
     h->h_gains.assign(gains, gains + c.n_tpc);
     for (int r = 0; r < c.dt; r++) {                       // pulse.py:32 current_max
@@ -902,12 +923,12 @@ try {
     if (!h || e < 0 || e >= WFS_MAX_AP || !delay_cdf || !amp_cdf) return WFS_E_INVALID;
     ApElem &a = h->ap[e];
     a.n_bins_delay = n_bins_delay; a.n_bins_amp = n_bins_amp; a.amp_2d = amp_2d; a.is_uniform = is_uniform; a.delay_bin = delay_bin; a.amp_bin = amp_bin;
-    TRY(upload(h, a.delay_cdf, delay_cdf, sizeof(double) * (size_t)h->cfg.n_tpc * n_bins_delay));
-    TRY(upload(h, a.amp_cdf, amp_cdf, sizeof(double) * (size_t)(amp_2d ? h->cfg.n_tpc : 1) * n_bins_amp));
+    TRY(upload(h, a.delay_cdf, delay_cdf, (size_t)h->cfg.n_tpc * n_bins_delay));
+    TRY(upload(h, a.amp_cdf, amp_cdf, (size_t)(amp_2d ? h->cfg.n_tpc : 1) * n_bins_amp));
     // the probability column on its own (last entry of every channel's delay row): the generator keeps it in LDS
     std::vector<double> prob((size_t)h->cfg.n_tpc);
     for (int c = 0; c < h->cfg.n_tpc; c++) prob[c] = delay_cdf[(size_t)c * n_bins_delay + n_bins_delay - 1];
-    TRY(upload(h, a.prob, prob.data(), sizeof(double) * prob.size()));
+    TRY(upload(h, a.prob, prob.data(), prob.size()));
     a.prob_h = prob; a.thr_mod = -1.0;
     // non-decreasing rows (every cumulative distribution is): np.argmin(|cdf - u|) by bisection on the device
     auto rows_sorted = [](const double *c, size_t rows, int n) {
@@ -918,7 +939,7 @@ try {
     a.amp_sorted = rows_sorted(amp_cdf, (size_t)(amp_2d ? h->cfg.n_tpc : 1), n_bins_amp);
     // guides of the sorted rows (ApGuide): for every cell of u * scale a bracket of "first entry >= u" that holds for every u the
     // device can put into the cell -- the cell's ends moved outwards by 2^-40 (the one rounding of u * scale is 2^-53)
-    auto build_guides = [&](DevBuf &buf, const double *c, size_t rows, int n) -> int {
+    auto build_guides = [&](DevArr<ApGuide> &buf, const double *c, size_t rows, int n) -> int {
         buf.reset();
         if (n < 1 || n > 65535) return WFS_OK;
         std::vector<ApGuide> g(rows);
@@ -935,7 +956,7 @@ try {
                 g[r].hi[j] = j == AP_GUIDE - 1 ? (unsigned short)n : (unsigned short)first_ge(x_hi);       // (the last cell also takes every u above the row)
             }
         }
-        int rc = upload(h, buf, g.data(), g.size() * sizeof(ApGuide)); if (rc) return rc;
+        TRY(upload(h, buf, g.data(), g.size()));
         HIPCHK(hipStreamSynchronize(h->stream));
         return WFS_OK;
     };
@@ -958,8 +979,8 @@ static int load_clusters(wfs_handle *h, i64 n, const int32_t *cluster, const int
         else cl_tmin[cluster[i]] = std::min(cl_tmin[cluster[i]], (i64)tmin[i]);
     }
     h->batch.n_clusters = (i64)cl_tmin.size();
-    TRY(upload(h, h->cl_tmin, cl_tmin.data(), cl_tmin.size() * 8));
-    TRY(upload(h, h->cl_gid, cl_gid.data(), cl_gid.size() * 4));
+    TRY(upload(h, h->cl_tmin, cl_tmin.data(), cl_tmin.size()));
+    TRY(upload(h, h->cl_gid, cl_gid.data(), cl_gid.size()));
     HIPCHK(hipStreamSynchronize(h->stream));       // vectors go out of scope
     return WFS_OK;
 }
@@ -1015,10 +1036,10 @@ try {
     b.n_ins = n; b.n_psets = PS; b.n_sets = S; b.n_emitters = em_off[n]; b.n_tiles = S * h->cfg.n_tpc;
     b.h_rs_off = set_off; b.h_rs_list = set_list;
     if (b.n_tiles > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "too many tiles in one batch");
-    TRY(upload(h, h->ins_type, type, (size_t)n)); TRY(upload(h, h->ins_time, time, (size_t)n * 8)); TRY(upload(h, h->ins_amp, amp, (size_t)n * 4));
-    { std::vector<u32> eb((size_t)n, 0u); if (em_base) eb.assign(em_base, em_base + n); TRY(upload(h, h->ins_embase, eb.data(), (size_t)n * 4)); HIPCHK(hipStreamSynchronize(h->stream)); }
-    TRY(upload(h, h->ins_gid, gid, (size_t)n * 4)); TRY(upload(h, h->ins_p, p_hit, (size_t)n * 8)); TRY(upload(h, h->ins_dm, drift_mean, (size_t)n * 8));
-    TRY(upload(h, h->ins_ds, drift_spread, (size_t)n * 8)); TRY(upload(h, h->ins_sc, sc_gain, (size_t)n * 8));
+    TRY(upload(h, h->ins_type, type, (size_t)n)); TRY(upload(h, h->ins_time, time, (size_t)n)); TRY(upload(h, h->ins_amp, amp, (size_t)n));
+    { std::vector<u32> eb((size_t)n, 0u); if (em_base) eb.assign(em_base, em_base + n); TRY(upload(h, h->ins_embase, eb.data(), (size_t)n)); HIPCHK(hipStreamSynchronize(h->stream)); }
+    TRY(upload(h, h->ins_gid, gid, (size_t)n)); TRY(upload(h, h->ins_p, p_hit, (size_t)n)); TRY(upload(h, h->ins_dm, drift_mean, (size_t)n));
+    TRY(upload(h, h->ins_ds, drift_spread, (size_t)n)); TRY(upload(h, h->ins_sc, sc_gain, (size_t)n));
     // rows -1: the channel CDF of the instruction comes from the device pattern map (wfs_eval_pattern_rows), stored behind the host rows
     b.h_ins_type.assign(type, type + n); b.n_host_rows = n_cdf;
     {
@@ -1026,11 +1047,11 @@ try {
         for (i64 i = 0; i < n; i++) if (rows[i] < 0) { rows[i] = (i32)(n_cdf + (i64)b.dev_row_ins.size()); b.dev_row_ins.push_back((i32)i); }
         b.dev_rows_pending = !b.dev_row_ins.empty();
         const size_t total = (size_t)n_cdf + b.dev_row_ins.size();
-        TRY(ensure(h, h->cdf_table, total * h->cfg.n_tpc * 8));
-        TRY(upload(h, h->ins_cdfrow, rows.data(), (size_t)n * 4)); HIPCHK(hipStreamSynchronize(h->stream));
+        TRY(ensure(h, h->cdf_table, total * h->cfg.n_tpc));
+        TRY(upload(h, h->ins_cdfrow, rows.data(), (size_t)n)); HIPCHK(hipStreamSynchronize(h->stream));
     }
-    TRY(upload(h, h->cdf_table, cdf_table, (size_t)n_cdf * h->cfg.n_tpc * 8));
-    TRY(upload(h, h->em_off, em_off.data(), em_off.size() * 8));
+    TRY(upload(h, h->cdf_table, cdf_table, (size_t)n_cdf * h->cfg.n_tpc));
+    TRY(upload(h, h->em_off, em_off.data(), em_off.size()));
     {
         std::vector<i32> sc((size_t)S), sm((size_t)S, 0); std::vector<i64> st((size_t)S);
         for (i64 q = 0; q < S; q++) {
@@ -1041,10 +1062,10 @@ try {
             for (i64 k = set_off[ps]; k < set_off[ps + 1]; k++) t0 = std::min<i64>(t0, time[set_list[k]]);
             sc[q] = cluster[set_list[set_off[ps]]]; st[q] = t0;
         }
-        TRY(upload(h, h->ins_set, ins_set.data(), (size_t)n * 4)); TRY(upload(h, h->set_ins_off, set_off.data(), set_off.size() * 8));
-        TRY(upload(h, h->set_ins_list, set_list.data(), (size_t)n * 4));
-        TRY(upload(h, h->set_cluster, sc.data(), (size_t)S * 4)); TRY(upload(h, h->set_t0, st.data(), (size_t)S * 8));
-        TRY(upload(h, h->set_mode, sm.data(), (size_t)S * 4));
+        TRY(upload(h, h->ins_set, ins_set.data(), (size_t)n)); TRY(upload(h, h->set_ins_off, set_off.data(), set_off.size()));
+        TRY(upload(h, h->set_ins_list, set_list.data(), (size_t)n));
+        TRY(upload(h, h->set_cluster, sc.data(), (size_t)S)); TRY(upload(h, h->set_t0, st.data(), (size_t)S));
+        TRY(upload(h, h->set_mode, sm.data(), (size_t)S));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     TRY(load_clusters(h, n, cluster, tmin, gid));
@@ -1074,7 +1095,7 @@ try {
         TRY(upload_disc(h, h->x_alias[k], cum, (int)v0, h->h_tabs[k]));
     }
     h->h_tabs[n_tables] = h->dev.tab_s1; h->h_tabs[n_tables + 1] = h->dev.tab_s2;       // "-1": the default table of the type
-    TRY(upload(h, h->d_tabs, h->h_tabs.data(), h->h_tabs.size() * sizeof(AliasTab)));
+    TRY(upload(h, h->d_tabs, h->h_tabs.data(), h->h_tabs.size()));
     HIPCHK(hipStreamSynchronize(h->stream));
     return WFS_OK;
 } WFS_CATCH(h)
@@ -1099,9 +1120,9 @@ static int map_set_grid(wfs_handle *h, wfs_handle::PatternMap &m, int dims, int 
 static void map_args(const wfs_handle::PatternMap &pm, MapArgs &m)
 {
     m.dims = pm.dims; for (int q = 0; q < 3; q++) { m.n[q] = pm.n[q]; m.w[q] = pm.w[q]; m.lo[q] = pm.lo[q]; m.h[q] = pm.hgrid[q]; }
-    m.n_points = pm.n_points; m.points = pm.n_points ? pm.points.as<double>() : nullptr;
-    m.values = pm.values.as<float>(); m.n_map_ch = pm.n_map_ch;
-    m.cell_start = pm.cnx ? pm.cell_start.as<i32>() : nullptr; m.cell_pts = pm.cnx ? pm.cell_pts.as<i32>() : nullptr;
+    m.n_points = pm.n_points; m.points = pm.n_points ? pm.points.p() : nullptr;
+    m.values = pm.values.p(); m.n_map_ch = pm.n_map_ch;
+    m.cell_start = pm.cnx ? pm.cell_start.p() : nullptr; m.cell_pts = pm.cnx ? pm.cell_pts.p() : nullptr;
     m.cnx = pm.cnx; m.cny = pm.cny; m.cell_lo[0] = pm.cell_lo[0]; m.cell_lo[1] = pm.cell_lo[1]; m.cell_h = pm.cell_h;
 }
 
@@ -1123,7 +1144,7 @@ try {
     size_t nodes = 0;
     TRY(map_set_grid(h, m, dims, 2, n_nodes, lo, hi, nodes));
     m.n_map_ch = n_map_channels;
-    TRY(upload(h, m.values, values, nodes * (size_t)n_map_channels * 4));
+    TRY(upload(h, m.values, values, nodes * (size_t)n_map_channels));
     HIPCHK(hipStreamSynchronize(h->stream));
     m.set = true;
     return WFS_OK;
@@ -1139,8 +1160,8 @@ try {
         return h->fail(WFS_E_INVALID, "wfs_set_pattern_map_points: 2 or 3 dimensions, at least 2 * dims points, at most n_tpc channels");
     HIPCHK(hipSetDevice(h->device));
     m.dims = dims; m.n_points = n_points; m.n_map_ch = n_map_channels;
-    TRY(upload(h, m.points, points, (size_t)n_points * dims * 8));
-    TRY(upload(h, m.values, values, (size_t)n_points * (size_t)n_map_channels * 4));
+    TRY(upload(h, m.points, points, (size_t)n_points * dims));
+    TRY(upload(h, m.values, values, (size_t)n_points * (size_t)n_map_channels));
     m.cnx = m.cny = 0;
     if (dims == 2) {
         // cell index for the per-electron searches of the transverse diffusion (k_diffuse_patterns): square cells of about two points
@@ -1157,7 +1178,7 @@ try {
         }
         for (size_t c = 0; c + 1 < start.size(); c++) start[c + 1] += start[c];
         { std::vector<i32> cur(start.begin(), start.end() - 1); for (i64 q = 0; q < n_points; q++) pts[(size_t)cur[(size_t)cell[(size_t)q]]++] = (i32)q; }      // (ascending point index inside a cell)
-        TRY(upload(h, m.cell_start, start.data(), start.size() * 4)); TRY(upload(h, m.cell_pts, pts.data(), pts.size() * 4));
+        TRY(upload(h, m.cell_start, start.data(), start.size())); TRY(upload(h, m.cell_pts, pts.data(), pts.size()));
         m.cnx = cnx; m.cny = cny; m.cell_lo[0] = lo[0]; m.cell_lo[1] = lo[1]; m.cell_h = ch;
     }
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1174,7 +1195,7 @@ try {
     h->batch.ins_aft_set = false; h->state().option_changed();
     if (!factor) return WFS_OK;
     HIPCHK(hipSetDevice(h->device));
-    TRY(upload(h, h->ins_aft, factor, (size_t)n * 8));
+    TRY(upload(h, h->ins_aft, factor, (size_t)n));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->batch.ins_aft_set = true;
     return WFS_OK;
@@ -1203,8 +1224,8 @@ try {
     for (i64 i = 0; i < n; i++)
         if (h->batch.h_ins_type[i] != 1 && sigma_r[i] == sigma_r[i] && !is_dev[i]) return h->fail(WFS_E_STATE, "transverse diffusion: the instruction must take its pattern from the device map (cdf_row = -1)");
     h->batch.n_diff_rows = (i64)rows.size(); h->batch.diff_r2 = tpc_radius * tpc_radius;
-    TRY(upload(h, h->ins_sigr, sigma_r, (size_t)n * 8)); TRY(upload(h, h->ins_siga, sigma_a, (size_t)n * 8));
-    TRY(upload(h, h->diff_row_ins, rows.data(), rows.size() * 4)); TRY(upload(h, h->diff_row_id, ids.data(), ids.size() * 8));
+    TRY(upload(h, h->ins_sigr, sigma_r, (size_t)n)); TRY(upload(h, h->ins_siga, sigma_a, (size_t)n));
+    TRY(upload(h, h->diff_row_ins, rows.data(), rows.size())); TRY(upload(h, h->diff_row_id, ids.data(), ids.size()));
     HIPCHK(hipStreamSynchronize(h->stream));
     return WFS_OK;
 } WFS_CATCH(h)
@@ -1227,7 +1248,7 @@ static int scalar_map_grid(wfs_handle *h, int kind, int32_t dims, const int32_t 
     std::unique_ptr<wfs_handle::ScalarMap> m(new wfs_handle::ScalarMap()); size_t nodes = 0;
     m->kind = kind; m->nv = n_values;
     TRY(map_set_grid(h, m->g, dims, 1, n_nodes, lo, hi, nodes));
-    TRY(upload(h, m->g.values, values, nodes * (size_t)n_values * 8));
+    TRY(upload(h, m->values, values, nodes * (size_t)n_values));
     return smap_new(h, std::move(m), map_id);
 }
 
@@ -1247,8 +1268,8 @@ static int scalar_map_points(wfs_handle *h, int32_t dims, int64_t n_points, cons
     HIPCHK(hipSetDevice(h->device));
     std::unique_ptr<wfs_handle::ScalarMap> m(new wfs_handle::ScalarMap());
     m->kind = 1; m->nv = n_values; m->g.dims = dims; m->g.n_points = n_points;
-    TRY(upload(h, m->g.points, points, (size_t)n_points * dims * 8));
-    TRY(upload(h, m->g.values, values, (size_t)n_points * (size_t)n_values * 8));
+    TRY(upload(h, m->g.points, points, (size_t)n_points * dims));
+    TRY(upload(h, m->values, values, (size_t)n_points * (size_t)n_values));
     return smap_new(h, std::move(m), map_id);
 }
 
@@ -1265,8 +1286,8 @@ try {
     HIPCHK(hipSetDevice(h->device));
     std::unique_ptr<wfs_handle::ScalarMap> m(new wfs_handle::ScalarMap());
     m->kind = 2; m->nx = nx; m->ny = ny; m->kx = kx; m->ky = ky;
-    TRY(upload(h, m->tx, tx, (size_t)nx * 8)); TRY(upload(h, m->ty, ty, (size_t)ny * 8));
-    TRY(upload(h, m->c, c, (size_t)(nx - kx - 1) * (size_t)(ny - ky - 1) * 8));
+    TRY(upload(h, m->tx, tx, (size_t)nx)); TRY(upload(h, m->ty, ty, (size_t)ny));
+    TRY(upload(h, m->c, c, (size_t)(nx - kx - 1) * (size_t)(ny - ky - 1)));
     return smap_new(h, std::move(m), map_id);
 } WFS_CATCH(h)
 
@@ -1279,24 +1300,24 @@ static int scalar_map_eval(wfs_handle *h, int32_t map_id, int64_t n, const doubl
     if (n == 0) return WFS_OK;
     HIPCHK(hipSetDevice(h->device));
     const int dims = sm.kind == 2 ? 2 : sm.g.dims, nv = sm.nv;
-    TRY(upload(h, h->smap_pos, pos, (size_t)n * dims * 8)); TRY(ensure(h, h->smap_out, (size_t)n * nv * 8));
+    TRY(upload(h, h->smap_pos, pos, (size_t)n * dims)); TRY(ensure(h, h->smap_out, (size_t)n * nv));
     if (sm.kind == 2) {
-        SplineArgs a{sm.nx, sm.ny, sm.kx, sm.ky, sm.tx.as<double>(), sm.ty.as<double>(), sm.c.as<double>(), n, h->smap_pos.as<double>(), h->smap_out.as<double>()};
+        SplineArgs a{sm.nx, sm.ny, sm.kx, sm.ky, sm.tx.p(), sm.ty.p(), sm.c.p(), n, h->smap_pos.p(), h->smap_out.p()};
         Timer t(h, "k_map_spline"); hipLaunchKernelGGL(k_map_spline, dim3(nblocks(n, 128)), dim3(128), 0, h->stream, a);
     } else if (sm.kind == 3) {
         LinearMapArgs a{};
-        a.dims = dims; a.nv = nv; a.values = sm.g.values.as<double>(); a.n_rows = n; a.pos = h->smap_pos.as<double>(); a.out = h->smap_out.as<double>();
+        a.dims = dims; a.nv = nv; a.values = sm.values.p(); a.n_rows = n; a.pos = h->smap_pos.p(); a.out = h->smap_out.p();
         for (int q = 0; q < 3; q++) { a.n[q] = sm.g.n[q]; a.lo[q] = sm.g.lo[q]; a.h[q] = sm.g.hgrid[q]; }
         Timer t(h, "k_map_linear"); hipLaunchKernelGGL(k_map_linear, dim3(nblocks(n * nv, 128)), dim3(128), 0, h->stream, a);
     } else {
-        TRY(ensure(h, h->smap_nb_idx, (size_t)n * MAP_K * 8)); TRY(ensure(h, h->smap_nb_w, (size_t)n * MAP_K * 8));
+        TRY(ensure(h, h->smap_nb_idx, (size_t)n * MAP_K)); TRY(ensure(h, h->smap_nb_w, (size_t)n * MAP_K));
         MapArgs m{};
         map_args(sm.g, m);
-        m.n_rows = n; m.pos = h->smap_pos.as<double>(); m.nb_idx = h->smap_nb_idx.as<i64>(); m.nb_w = h->smap_nb_w.as<double>();
+        m.n_rows = n; m.pos = h->smap_pos.p(); m.nb_idx = h->smap_nb_idx.p(); m.nb_w = h->smap_nb_w.p();
         launch_neighbours(h, m);
-        { Timer t(h, "k_map_scalar"); hipLaunchKernelGGL(k_map_scalar, dim3(nblocks(n * nv, 128)), dim3(128), 0, h->stream, m, sm.g.values.as<double>(), h->smap_out.as<double>(), nv); }
+        { Timer t(h, "k_map_scalar"); hipLaunchKernelGGL(k_map_scalar, dim3(nblocks(n * nv, 128)), dim3(128), 0, h->stream, m, sm.values.p(), h->smap_out.p(), nv); }
     }
-    HIPCHK(hipMemcpyAsync(out, h->smap_out.p, (size_t)n * nv * 8, hipMemcpyDeviceToHost, h->stream));
+    TRY(copy_async(h, out, h->smap_out.p(), (size_t)n * nv, hipMemcpyDeviceToHost));
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipGetLastError());
     return WFS_OK;
@@ -1315,7 +1336,7 @@ try {
     if (h->batch.dev_row_ins.empty()) return WFS_OK;
     HIPCHK(hipSetDevice(h->device));
     const int nch = h->cfg.n_tpc;
-    TRY(upload(h, h->map_x, x, (size_t)n * 4)); TRY(upload(h, h->map_y, y, (size_t)n * 4)); TRY(upload(h, h->map_z, z, (size_t)n * 4));
+    TRY(upload(h, h->map_x, x, (size_t)n)); TRY(upload(h, h->map_y, y, (size_t)n)); TRY(upload(h, h->map_z, z, (size_t)n));
     i64 first = h->batch.n_host_rows;
     // rows were numbered in instruction order; evaluate them map by map, each over its own (ordered) subset
     std::vector<i32> rows_of[2]; std::vector<i64> row_id[2];
@@ -1327,15 +1348,15 @@ try {
         if (rows_of[w].empty()) continue;
         const auto &pm = h->pmap[w];
         const i64 nr = (i64)rows_of[w].size();
-        TRY(upload(h, h->map_row_ins[w], rows_of[w].data(), (size_t)nr * 4)); TRY(upload(h, h->map_row_id[w], row_id[w].data(), (size_t)nr * 8));
-        TRY(ensure(h, h->map_nb_idx[w], (size_t)nr * MAP_K * 8)); TRY(ensure(h, h->map_nb_w[w], (size_t)nr * MAP_K * 8));
+        TRY(upload(h, h->map_row_ins[w], rows_of[w].data(), (size_t)nr)); TRY(upload(h, h->map_row_id[w], row_id[w].data(), (size_t)nr));
+        TRY(ensure(h, h->map_nb_idx[w], (size_t)nr * MAP_K)); TRY(ensure(h, h->map_nb_w[w], (size_t)nr * MAP_K));
         MapArgs m{};
         map_args(pm, m);
-        m.n_rows = nr; m.row_ins = h->map_row_ins[w].as<i32>(); m.row_id = h->map_row_id[w].as<i64>();
-        m.aft = (w == 1 && h->batch.ins_aft_set) ? h->ins_aft.as<double>() : nullptr; m.n_top = h->cfg.n_top;
-        m.x = h->map_x.as<float>(); m.y = h->map_y.as<float>(); m.z = h->map_z.as<float>();
-        m.nb_idx = h->map_nb_idx[w].as<i64>(); m.nb_w = h->map_nb_w[w].as<double>();
-        m.cdf_table = h->cdf_table.as<double>(); m.gains = h->t_gains.as<double>();
+        m.n_rows = nr; m.row_ins = h->map_row_ins[w].p(); m.row_id = h->map_row_id[w].p();
+        m.aft = (w == 1 && h->batch.ins_aft_set) ? h->ins_aft.p() : nullptr; m.n_top = h->cfg.n_top;
+        m.x = h->map_x.p(); m.y = h->map_y.p(); m.z = h->map_z.p();
+        m.nb_idx = h->map_nb_idx[w].p(); m.nb_w = h->map_nb_w[w].p();
+        m.cdf_table = h->cdf_table.p(); m.gains = h->t_gains.p();
         launch_neighbours(h, m);
         { Timer t(h, "k_map_rows"); hipLaunchKernelGGL(k_map_rows, dim3((unsigned)nr), dim3(256), (size_t)map_rows_lds(nch).total, h->stream, m, nch); }
     }
@@ -1353,8 +1374,8 @@ try {
     const i64 total = h->batch.n_host_rows + (i64)h->batch.dev_row_ins.size();
     if (cap_rows < total) return h->fail(WFS_E_CAPACITY, "cdf row buffer too small");
     HIPCHK(hipSetDevice(h->device));
-    if (cdf_row) HIPCHK(hipMemcpy(cdf_row, h->ins_cdfrow.p, (size_t)h->batch.n_ins * 4, hipMemcpyDeviceToHost));
-    if (cdf_table) HIPCHK(hipMemcpy(cdf_table, h->cdf_table.p, (size_t)total * h->cfg.n_tpc * 8, hipMemcpyDeviceToHost));
+    if (cdf_row) TRY(copy_out(h, cdf_row, h->ins_cdfrow.p(), (size_t)h->batch.n_ins));
+    if (cdf_table) TRY(copy_out(h, cdf_table, h->cdf_table.p(), (size_t)total * h->cfg.n_tpc));
     return WFS_OK;
 } WFS_CATCH(h)
 
@@ -1364,7 +1385,7 @@ try {
     if (nz == 0) { h->prop_nz = 0; return WFS_OK; }
     if (nz < 2 || nu < 2 || !(du > 0) || !top || !bottom) return h->fail(WFS_E_INVALID, "wfs_set_s1_propagation: needs a grid of at least 2 x 2 nodes");
     HIPCHK(hipSetDevice(h->device));
-    TRY(upload(h, h->prop_top, top, (size_t)nz * nu * 8)); TRY(upload(h, h->prop_bot, bottom, (size_t)nz * nu * 8));
+    TRY(upload(h, h->prop_top, top, (size_t)nz * nu)); TRY(upload(h, h->prop_bot, bottom, (size_t)nz * nu));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->prop_nz = nz; h->prop_nu = nu; h->prop_u0 = u0; h->prop_du = du;
     return WFS_OK;
@@ -1374,10 +1395,9 @@ int wfs_set_instruction_models(wfs_handle *h, int64_t n, const int32_t *tab, con
 try {
     if (!h) return WFS_E_INVALID;
     if (!generator_batch_of(h, n)) return h->fail(WFS_E_STATE, "wfs_set_instruction_models follows wfs_load_instructions of the same batch");
-    if (h->d_tabs.p == nullptr) TRY(wfs_set_delay_models(h, 0, nullptr, nullptr, nullptr, nullptr));
+    if (h->d_tabs.p() == nullptr) TRY(wfs_set_delay_models(h, 0, nullptr, nullptr, nullptr, nullptr));
     HIPCHK(hipSetDevice(h->device));
-    std::vector<int8_t> type((size_t)n);
-    HIPCHK(hipMemcpy(type.data(), h->ins_type.p, (size_t)n, hipMemcpyDeviceToHost));
+    const std::vector<int8_t> type = download(h, h->ins_type, (size_t)n);
     std::vector<i32> t((size_t)n), tb((size_t)n), zi((size_t)n, -1); std::vector<double> zf((size_t)n, 0.0);
     for (i64 i = 0; i < n; i++) {
         const i32 dflt = h->n_user_tabs + (type[i] == 1 ? 0 : 1);
@@ -1389,8 +1409,8 @@ try {
             zi[i] = prop_zi[i]; zf[i] = prop_zf[i];
         }
     }
-    TRY(upload(h, h->ins_tab, t.data(), (size_t)n * 4)); TRY(upload(h, h->ins_tabb, tb.data(), (size_t)n * 4));
-    TRY(upload(h, h->ins_pzi, zi.data(), (size_t)n * 4)); TRY(upload(h, h->ins_pzf, zf.data(), (size_t)n * 8));
+    TRY(upload(h, h->ins_tab, t.data(), (size_t)n)); TRY(upload(h, h->ins_tabb, tb.data(), (size_t)n));
+    TRY(upload(h, h->ins_pzi, zi.data(), (size_t)n)); TRY(upload(h, h->ins_pzf, zf.data(), (size_t)n));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->batch.ins_models = true; h->state().option_changed();
     return WFS_OK;
@@ -1403,7 +1423,7 @@ try {
     if (n_gas_gaps == 0) { h->gg_n = 0; return WFS_OK; }
     if (n_gas_gaps < 1 || n_points < 3 || !timing_inv_cdf) return h->fail(WFS_E_INVALID, "wfs_set_gas_gap_model: at least one table of at least 3 points");
     HIPCHK(hipSetDevice(h->device));
-    TRY(upload(h, h->gg_inv, timing_inv_cdf, (size_t)n_gas_gaps * n_points * 8));
+    TRY(upload(h, h->gg_inv, timing_inv_cdf, (size_t)n_gas_gaps * n_points));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->gg_n = n_gas_gaps; h->gg_L = n_points;
     return WFS_OK;
@@ -1416,7 +1436,7 @@ try {
     if (h->gg_n < 1) return h->fail(WFS_E_STATE, "wfs_set_gas_gap_model first");
     for (i64 i = 0; i < n; i++) if (table[i] < -1 || table[i] >= h->gg_n) return h->fail(WFS_E_INVALID, "gas gap table index out of range");
     HIPCHK(hipSetDevice(h->device));
-    TRY(upload(h, h->ins_gg, table, (size_t)n * 4)); TRY(upload(h, h->ins_ggw, weight, (size_t)n * 8));
+    TRY(upload(h, h->ins_gg, table, (size_t)n)); TRY(upload(h, h->ins_ggw, weight, (size_t)n));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->batch.ins_gg_set = true; h->state().option_changed();
     return WFS_OK;
@@ -1456,15 +1476,15 @@ try {
         }
     }
     b.h_set_off.assign(set_off, set_off + n_sets + 1);
-    TRY(upload(h, h->set_cluster, set_cluster, (size_t)n_sets * 4)); TRY(upload(h, h->set_t0, t0.data(), (size_t)n_sets * 8));
-    TRY(upload(h, h->set_mode, mode.data(), (size_t)n_sets * 4));
-    TRY(upload(h, h->tile_count, count.data(), count.size() * 4)); TRY(upload(h, h->tile_tmin, tmn.data(), tmn.size() * 4));
-    TRY(upload(h, h->tile_tmax, tmx.data(), tmx.size() * 4));
-    TRY(upload(h, h->ph_gain, gain, (size_t)P * 8));
+    TRY(upload(h, h->set_cluster, set_cluster, (size_t)n_sets)); TRY(upload(h, h->set_t0, t0.data(), (size_t)n_sets));
+    TRY(upload(h, h->set_mode, mode.data(), (size_t)n_sets));
+    TRY(upload(h, h->tile_count, count.data(), count.size())); TRY(upload(h, h->tile_tmin, tmn.data(), tmn.size()));
+    TRY(upload(h, h->tile_tmax, tmx.data(), tmx.size()));
+    TRY(upload(h, h->ph_gain, gain, (size_t)P));
     {   // DPE flags ride in the code word (only the truth quirk pulse.py:255 reads them in explicit-gain mode)
         std::vector<PhotonRec> recs((size_t)P);
         for (i64 p = 0; p < P; p++) recs[p] = PhotonRec{rel[p], (dpe && dpe[p]) ? (1u << 16) : 0u};
-        TRY(upload(h, h->ph, recs.data(), (size_t)P * 8));
+        TRY(upload(h, h->ph, recs.data(), (size_t)P));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     TRY(load_clusters(h, n_sets, set_cluster, set_tmin, nullptr));
@@ -1502,34 +1522,34 @@ try {
     {
         std::vector<i32> mode((size_t)S, 0), sc((size_t)S); std::vector<i64> st((size_t)S); std::vector<u32> sg((size_t)S);
         for (i64 q = 0; q < S; q++) { sc[q] = cluster[q % n]; st[q] = time[q % n]; sg[q] = gid[q % n]; mode[q] = q >= n ? 1 : 0; }
-        TRY(upload(h, h->set_cluster, sc.data(), (size_t)S * 4)); TRY(upload(h, h->set_t0, st.data(), (size_t)S * 8)); TRY(upload(h, h->set_mode, mode.data(), (size_t)S * 4));
-        TRY(upload(h, h->set_gid, sg.data(), (size_t)S * 4)); TRY(upload(h, h->ins_time, time, (size_t)n * 8));
+        TRY(upload(h, h->set_cluster, sc.data(), (size_t)S)); TRY(upload(h, h->set_t0, st.data(), (size_t)S)); TRY(upload(h, h->set_mode, mode.data(), (size_t)S));
+        TRY(upload(h, h->set_gid, sg.data(), (size_t)S)); TRY(upload(h, h->ins_time, time, (size_t)n));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
-    TRY(upload(h, h->opt_first, first, (size_t)n * 4)); TRY(upload(h, h->opt_last, last, (size_t)n * 4));
-    TRY(upload(h, h->opt_ch, channels, (size_t)n_ph * 4)); TRY(upload(h, h->opt_time, timings, (size_t)n_ph * 8));
-    TRY(ensure(h, h->tile_count, (size_t)b.n_tiles * 4)); TRY(ensure(h, h->tile_cursor, (size_t)b.n_tiles * 4)); TRY(ensure(h, h->tile_off, (size_t)(b.n_tiles + 1) * 8));
+    TRY(upload(h, h->opt_first, first, (size_t)n)); TRY(upload(h, h->opt_last, last, (size_t)n));
+    TRY(upload(h, h->opt_ch, channels, (size_t)n_ph)); TRY(upload(h, h->opt_time, timings, (size_t)n_ph));
+    TRY(ensure(h, h->tile_count, (size_t)b.n_tiles)); TRY(ensure(h, h->tile_cursor, (size_t)b.n_tiles)); TRY(ensure(h, h->tile_off, (size_t)(b.n_tiles + 1)));
     // (the bucketed copies hold a slot per photon of every instruction's range, not per entry of the flat arrays)
-    TRY(ensure(h, h->opt_t, (size_t)n_ranged * 4)); TRY(ensure(h, h->opt_item, (size_t)n_ranged * 4));
+    TRY(ensure(h, h->opt_t, (size_t)n_ranged)); TRY(ensure(h, h->opt_item, (size_t)n_ranged));
     {
         FillGroup fg(h, "fills_optical");
-        TRY(fg.zero(h->tile_count.p, (size_t)T * 4)); TRY(fg.zero(h->tile_cursor.p, (size_t)T * 4)); TRY(fg.zero(h->scal.p, sizeof(WfsScal)));
+        TRY(fg.zero(h->tile_count.p(), T)); TRY(fg.zero(h->tile_cursor.p(), T)); TRY(fg.zero(h->scal.p(), 1));
         TRY(fg.flush());
     }
-    OptLoadArgs oa{n, h->opt_first.as<i32>(), h->opt_last.as<i32>(), h->opt_ch.as<i32>(), h->opt_time.as<i64>(), cutoff, h->t_gains.as<double>(),
-                   h->tile_count.as<i32>(), h->tile_off.as<i64>(), h->tile_cursor.as<i32>(), h->opt_t.as<i32>(), h->opt_item.as<u32>(), h->scal.as<WfsScal>()};
+    OptLoadArgs oa{n, h->opt_first.p(), h->opt_last.p(), h->opt_ch.p(), h->opt_time.p(), cutoff, h->t_gains.p(),
+                   h->tile_count.p(), h->tile_off.p(), h->tile_cursor.p(), h->opt_t.p(), h->opt_item.p(), h->scal.p()};
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_optical_bucket<false>), dim3(nblocks(n, 256)), dim3(256), 0, h->stream, h->dev, oa);
-    TRY(scan_into(h, h->tile_count.as<i32>(), T, h->tile_off.as<i64>(), &WfsScal::n_tile_photons, 0));
+    TRY(scan_into(h, h->tile_count.p(), T, h->tile_off.p(), &WfsScal::n_tile_photons, 0));
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_optical_bucket<true>), dim3(nblocks(n, 256)), dim3(256), 0, h->stream, h->dev, oa);
     TRY(read_scal(h));
     HIPCHK(hipGetLastError());
     TRY(device_error(h, h->h_scal->opt_error));
     const i64 P = b.n_photons = h->h_scal->n_tile_photons;
     // (with afterpulses the array also holds theirs, behind the primary photons: sized here, k_optical_finish writes into it)
-    TRY(ensure(h, h->ph, (size_t)(P + (b.ap_sets ? optical_ap_cap(P) : 0)) * 8));
-    TRY(ensure(h, h->tile_tmin, (size_t)b.n_tiles * 4)); TRY(ensure(h, h->tile_tmax, (size_t)b.n_tiles * 4));
-    TRY(ensure(h, h->el_stat, (size_t)n * 32)); TRY(ensure(h, h->el_minmax, (size_t)n * 16));
-    HIPCHK(hipMemsetAsync(h->el_stat.p, 0, (size_t)n * 32, h->stream));
+    TRY(ensure(h, h->ph, (size_t)(P + (b.ap_sets ? optical_ap_cap(P) : 0))));
+    TRY(ensure(h, h->tile_tmin, (size_t)b.n_tiles)); TRY(ensure(h, h->tile_tmax, (size_t)b.n_tiles));
+    TRY(ensure(h, h->el_stat, (size_t)n * STAT_PER_INS)); TRY(ensure(h, h->el_minmax, (size_t)n * MINMAX));
+    HIPCHK(hipMemsetAsync(h->el_stat.p(), 0, (size_t)n * STAT_PER_INS * sizeof(double), h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     TRY(load_clusters(h, n, cluster, tmin, gid));
     h->state().load_commits(BatchKind::Optical);
@@ -1543,7 +1563,7 @@ static bool tiles_made(const wfs_handle *h) { return from_generator(h) && h->run
 static i64 n_tilegen_tiles(const wfs_handle *h) { return h->run.n_fused_tiles + h->run.n_gen_tiles + h->run.n_bright_tiles; }
 // ph_gain holds the photons with an explicit gain only: every photon of an injected batch, or the PMT afterpulses, which follow the
 // n_photons primary ones; the kernels index it by photon number
-static const double *ph_gain_base(const wfs_handle *h) { return h->batch.ap_sets ? h->ph_gain.as<double>() - n_primary_photons(h) : h->ph_gain.as<double>(); }
+static const double *ph_gain_base(const wfs_handle *h) { return h->batch.ap_sets ? h->ph_gain.p() - n_primary_photons(h) : h->ph_gain.p(); }
 // the templates as the pulse kernels take them by value: t[tap * dt + ns remainder]
 static TemplateArg fill_template_arg(const wfs_handle *h)
 {
@@ -1564,30 +1584,30 @@ static int gen_electrons(wfs_handle *h, GenRun &r, FillGroup &fg)
     const WfsDev &d = h->dev;
     GenArgs &g = r.g; FuseArgs &f = r.f;
     const i64 N = h->batch.n_ins, E = h->batch.n_emitters, T = h->batch.n_tiles;
-    TRY(ensure(h, h->em_time, (size_t)E * 8)); TRY(ensure(h, h->em_nph, (size_t)E * 4)); TRY(ensure(h, h->em_ins, (size_t)E * 4));
-    TRY(ensure(h, h->el_stat, (size_t)N * 32)); TRY(ensure(h, h->el_minmax, (size_t)N * 16));
+    TRY(ensure(h, h->em_time, (size_t)E)); TRY(ensure(h, h->em_nph, (size_t)E)); TRY(ensure(h, h->em_ins, (size_t)E));
+    TRY(ensure(h, h->el_stat, (size_t)N * STAT_PER_INS)); TRY(ensure(h, h->el_minmax, (size_t)N * MINMAX));
     // (fg: the fills at the head of the generation, behind the scalar block's of wfs_run; flushed in front of the first kernel)
-    TRY(fg.zero(h->el_stat.p, (size_t)N * 32));
-    TRY(fg.pairs(h->el_minmax.p, 2 * N, I64_MAX, I64_MIN));      // (min, max) pairs: (I64_MAX, I64_MIN)
+    TRY(fg.zero(h->el_stat.p(), N * STAT_PER_INS));
+    TRY(fg.pairs(h->el_minmax.p(), N * MINMAX, I64_MAX, I64_MIN));      // (min, max) pairs: (I64_MAX, I64_MIN)
     g.n_ins = N; g.n_psets = h->batch.n_psets; g.n_emitters = E;
-    g.ins_embase = h->ins_embase.as<u32>(); g.ins_set = h->ins_set.as<i32>(); g.set_ins_off = h->set_ins_off.as<i64>(); g.set_ins_list = h->set_ins_list.as<i32>(); g.set_t0 = h->set_t0.as<i64>();
-    g.ins_type = h->ins_type.as<int8_t>(); g.ins_time = h->ins_time.as<i64>(); g.ins_amp = h->ins_amp.as<i32>(); g.ins_gid = h->ins_gid.as<u32>();
-    g.ins_p = h->ins_p.as<double>(); g.ins_dm = h->ins_dm.as<double>(); g.ins_ds = h->ins_ds.as<double>(); g.ins_sc = h->ins_sc.as<double>();
-    g.ins_cdfrow = h->ins_cdfrow.as<i32>(); g.cdf_table = h->cdf_table.as<double>(); g.em_off = h->em_off.as<i64>();
-    g.em_time = h->em_time.as<i64>(); g.em_nph = h->em_nph.as<i32>(); g.em_ins = h->em_ins.as<i32>();
-    g.el_stat = h->el_stat.as<double>(); g.el_minmax = h->el_minmax.as<i64>(); g.scal = h->scal.as<WfsScal>();
+    g.ins_embase = h->ins_embase.p(); g.ins_set = h->ins_set.p(); g.set_ins_off = h->set_ins_off.p(); g.set_ins_list = h->set_ins_list.p(); g.set_t0 = h->set_t0.p();
+    g.ins_type = h->ins_type.p(); g.ins_time = h->ins_time.p(); g.ins_amp = h->ins_amp.p(); g.ins_gid = h->ins_gid.p();
+    g.ins_p = h->ins_p.p(); g.ins_dm = h->ins_dm.p(); g.ins_ds = h->ins_ds.p(); g.ins_sc = h->ins_sc.p();
+    g.ins_cdfrow = h->ins_cdfrow.p(); g.cdf_table = h->cdf_table.p(); g.em_off = h->em_off.p();
+    g.em_time = h->em_time.p(); g.em_nph = h->em_nph.p(); g.em_ins = h->em_ins.p();
+    g.el_stat = h->el_stat.p(); g.el_minmax = h->el_minmax.p(); g.scal = h->scal.p();
     const bool ext = r.ext = h->batch.ins_models;
     if (ext) {
-        g.tabs = h->d_tabs.as<AliasTab>(); g.ins_tab = h->ins_tab.as<i32>(); g.ins_tabb = h->ins_tabb.as<i32>();
-        g.ins_pzi = h->ins_pzi.as<i32>(); g.ins_pzf = h->ins_pzf.as<double>();
-        if (h->prop_nz >= 2) { g.prop_top = h->prop_top.as<double>(); g.prop_bot = h->prop_bot.as<double>(); g.prop_nu = h->prop_nu; g.prop_u0 = h->prop_u0; g.prop_du = h->prop_du; }
+        g.tabs = h->d_tabs.p(); g.ins_tab = h->ins_tab.p(); g.ins_tabb = h->ins_tabb.p();
+        g.ins_pzi = h->ins_pzi.p(); g.ins_pzf = h->ins_pzf.p();
+        if (h->prop_nz >= 2) { g.prop_top = h->prop_top.p(); g.prop_bot = h->prop_bot.p(); g.prop_nu = h->prop_nu; g.prop_u0 = h->prop_u0; g.prop_du = h->prop_du; }
         if (h->batch.ins_gg_set && h->gg_n >= 1) {
-            TRY(ensure(h, h->ins_ggsum, (size_t)(N + 1) * 8)); TRY(fg.zero(h->ins_ggsum.p, (size_t)(N + 1) * 8));
-            g.gg_inv = h->gg_inv.as<double>(); g.gg_n = h->gg_n; g.gg_L = h->gg_L; g.ins_gg = h->ins_gg.as<i32>(); g.ins_ggw = h->ins_ggw.as<double>(); g.ins_ggsum = h->ins_ggsum.as<i64>();
+            TRY(ensure(h, h->ins_ggsum, (size_t)(N + 1))); TRY(fg.zero(h->ins_ggsum.p(), N + 1));
+            g.gg_inv = h->gg_inv.p(); g.gg_n = h->gg_n; g.gg_L = h->gg_L; g.ins_gg = h->ins_gg.p(); g.ins_ggw = h->ins_ggw.p(); g.ins_ggsum = h->ins_ggsum.p();
         }
     }
     // em_zg is NaN wherever k_s2_electrons did not store a gain: k_s2_photons alone reads it, and it runs only with any_ptrs
-    TRY(ensure(h, h->em_zg, (size_t)E * 8)); if (h->batch.any_ptrs) TRY(fg.bytes(h->em_zg.p, (size_t)E * 8, 0xff)); g.em_zg = h->em_zg.as<double>();
+    TRY(ensure(h, h->em_zg, (size_t)E)); if (h->batch.any_ptrs) TRY(fg.ones(h->em_zg.p(), E)); g.em_zg = h->em_zg.p();
     // tile-local generation (wfs_tilegen.h): which instructions take it is decided before the electrons are drawn -- theirs get no
     // photon numbers.  Debug modes that need the per-photon arrays (currents, generation only) run the generation half alone.
     // (PMT afterpulses of tile-generated photons are screened inside k_s2_tile)
@@ -1595,7 +1615,7 @@ static int gen_electrons(wfs_handle *h, GenRun &r, FillGroup &fg)
     h->run.fuse_full = h->run.fuse_on && !(h->debug_bits & (DBG_CURRENTS | DBG_GEN_ONLY));
     if (h->run.fuse_on) {
         f.lam_min = h->cfg.tile_gen_min; f.n_ins = N; f.nch = d.n_tpc; f.table_span = (i32)(1u << (32 - d.tab_s2.shift));
-        f.set_ins_off = h->batch.run_sets_given ? h->set_ins_off.as<i64>() : nullptr;
+        f.set_ins_off = h->batch.run_sets_given ? h->set_ins_off.p() : nullptr;
         f.n_top = d.n_top;
         if (ext) {       // timing-model variants: the instruction's tables (the longest one bounds every tile buffer)
             f.tabs = g.tabs; f.ins_tab = g.ins_tab; f.ins_tabb = g.ins_tabb; f.ins_gg = g.gg_inv ? g.ins_gg : nullptr;
@@ -1603,17 +1623,17 @@ static int gen_electrons(wfs_handle *h, GenRun &r, FillGroup &fg)
         }
         f.ins_type = g.ins_type; f.ins_amp = g.ins_amp; f.ins_sc = g.ins_sc; f.ins_embase = g.ins_embase; f.ins_gid = g.ins_gid; f.ins_cdfrow = g.ins_cdfrow;
         f.cdf_table = g.cdf_table; f.ins_time = g.ins_time; f.em_off = g.em_off; f.em_time = g.em_time; f.el_minmax = g.el_minmax; f.scal = g.scal;
-        TRY(ensure(h, h->ins_fused, (size_t)N * 4)); TRY(ensure(h, h->ins_nsurv, (size_t)N * 4)); TRY(ensure(h, h->ins_bcap, (size_t)N * 4));
-        TRY(ensure(h, h->ins_bcap_all, (size_t)N * 4)); TRY(ensure(h, h->et32, (size_t)E * 4));
-        TRY(fg.zero(h->ins_bcap.p, (size_t)N * 4)); TRY(fg.zero(h->ins_bcap_all.p, (size_t)N * 4));
-        f.ins_fused = h->ins_fused.as<i32>(); f.ins_nsurv = h->ins_nsurv.as<i32>(); f.ins_bcap = h->ins_bcap.as<i32>(); f.ins_bcap_all = h->ins_bcap_all.as<i32>();
-        f.et32 = h->et32.as<i32>();
+        TRY(ensure(h, h->ins_fused, (size_t)N)); TRY(ensure(h, h->ins_nsurv, (size_t)N)); TRY(ensure(h, h->ins_bcap, (size_t)N));
+        TRY(ensure(h, h->ins_bcap_all, (size_t)N)); TRY(ensure(h, h->et32, (size_t)E));
+        TRY(fg.zero(h->ins_bcap.p(), N)); TRY(fg.zero(h->ins_bcap_all.p(), N));
+        f.ins_fused = h->ins_fused.p(); f.ins_nsurv = h->ins_nsurv.p(); f.ins_bcap = h->ins_bcap.p(); f.ins_bcap_all = h->ins_bcap_all.p();
+        f.et32 = h->et32.p();
         {
             const i64 n_rows = h->batch.n_host_rows + (i64)h->batch.dev_row_ins.size();
-            TRY(ensure(h, h->row_pmax, (size_t)n_rows * 8)); f.row_pmax = h->row_pmax.as<double>();
+            TRY(ensure(h, h->row_pmax, (size_t)n_rows)); f.row_pmax = h->row_pmax.p();
             TRY(fg.flush());
             Timer t(h, "k_fuse_decide");
-            hipLaunchKernelGGL(k_row_pmax, dim3(nblocks(n_rows, 4)), dim3(256), 0, h->stream, f.cdf_table, d.n_tpc, n_rows, h->row_pmax.as<double>());
+            hipLaunchKernelGGL(k_row_pmax, dim3(nblocks(n_rows, 4)), dim3(256), 0, h->stream, f.cdf_table, d.n_tpc, n_rows, h->row_pmax.p());
             hipLaunchKernelGGL(k_fuse_decide, dim3(nblocks(N, 256)), dim3(256), 0, h->stream, f);
         }
         g.ins_fused = f.ins_fused;
@@ -1622,11 +1642,11 @@ static int gen_electrons(wfs_handle *h, GenRun &r, FillGroup &fg)
     { Timer t(h, "k_s1_hits"); hipLaunchKernelGGL(k_s1_hits, dim3(nblocks(N, 4)), dim3(256), 0, h->stream, d, g); }
     {
         const i64 neb = (E + 255) / 256;
-        TRY(ensure(h, h->eblk_ins, (size_t)(neb + 1) * 4)); g.eblk_ins = h->eblk_ins.as<i32>();
+        TRY(ensure(h, h->eblk_ins, (size_t)(neb + 1))); g.eblk_ins = h->eblk_ins.p();
         { Timer t(h, "k_emitter_blocks"); hipLaunchKernelGGL(k_emitter_blocks, dim3(nblocks(neb + 1, 256)), dim3(256), 0, h->stream, g, neb); }
-        TRY(ensure(h, h->pois_cdf, (size_t)N * POIS_W * 8)); TRY(ensure(h, h->pois_kmin, (size_t)N * 4));
-        g.pois_cdf = h->pois_cdf.as<double>(); g.pois_kmin = h->pois_kmin.as<i32>();
-        { Timer t(h, "k_poisson_tables"); hipLaunchKernelGGL(k_poisson_tables, dim3((unsigned)N), dim3(POIS_W), 0, h->stream, g, h->pois_cdf.as<double>(), h->pois_kmin.as<i32>()); }
+        TRY(ensure(h, h->pois_cdf, (size_t)N * POIS_W)); TRY(ensure(h, h->pois_kmin, (size_t)N));
+        g.pois_cdf = h->pois_cdf.p(); g.pois_kmin = h->pois_kmin.p();
+        { Timer t(h, "k_poisson_tables"); hipLaunchKernelGGL(k_poisson_tables, dim3((unsigned)N), dim3(POIS_W), 0, h->stream, g, h->pois_cdf.p(), h->pois_kmin.p()); }
         { Timer t(h, "k_s2_electrons"); hipLaunchKernelGGL(k_s2_electrons, dim3(nblocks(E, 256)), dim3(256), 0, h->stream, d, g); }
         if (h->batch.any_ptrs) { Timer t(h, "k_s2_photons"); hipLaunchKernelGGL(k_s2_photons, dim3(nblocks(E, 256)), dim3(256), 0, h->stream, d, g); }
     }
@@ -1634,42 +1654,42 @@ static int gen_electrons(wfs_handle *h, GenRun &r, FillGroup &fg)
         // transverse diffusion maps: the pattern of these instructions is the average over their surviving electrons (s2.py:560-613)
         const auto &pm = h->pmap[1];
         const i64 nr = h->batch.n_diff_rows;
-        TRY(ensure(h, h->diff_pre, (size_t)nr * pm.n_map_ch * 8));
+        TRY(ensure(h, h->diff_pre, (size_t)nr * pm.n_map_ch));
         MapArgs m{};
         map_args(pm, m);
-        m.n_rows = nr; m.row_ins = h->diff_row_ins.as<i32>(); m.row_id = h->diff_row_id.as<i64>();
-        m.x = h->map_x.as<float>(); m.y = h->map_y.as<float>(); m.z = h->map_z.as<float>();
-        m.cdf_table = h->cdf_table.as<double>(); m.gains = h->t_gains.as<double>();
-        m.aft = h->batch.ins_aft_set ? h->ins_aft.as<double>() : nullptr; m.n_top = h->cfg.n_top;
-        DiffArgs q{nr, m.row_ins, h->ins_sigr.as<double>(), h->ins_siga.as<double>(), h->batch.diff_r2, h->diff_pre.as<double>()};
+        m.n_rows = nr; m.row_ins = h->diff_row_ins.p(); m.row_id = h->diff_row_id.p();
+        m.x = h->map_x.p(); m.y = h->map_y.p(); m.z = h->map_z.p();
+        m.cdf_table = h->cdf_table.p(); m.gains = h->t_gains.p();
+        m.aft = h->batch.ins_aft_set ? h->ins_aft.p() : nullptr; m.n_top = h->cfg.n_top;
+        DiffArgs q{nr, m.row_ins, h->ins_sigr.p(), h->ins_siga.p(), h->batch.diff_r2, h->diff_pre.p()};
         { Timer t(h, "k_diffuse_patterns"); hipLaunchKernelGGL(k_diffuse_patterns, dim3((unsigned)nr), dim3(256), 0, h->stream, d, g, m, q); }
-        m.pre = h->diff_pre.as<double>();
+        m.pre = h->diff_pre.p();
         { Timer t(h, "k_map_rows"); hipLaunchKernelGGL(k_map_rows, dim3((unsigned)nr), dim3(256), (size_t)map_rows_lds(d.n_tpc).total, h->stream, m, d.n_tpc); }
     }
     const i64 TP = r.TP = h->batch.n_psets * d.n_tpc;
-    TRY(ensure(h, h->tile_count, (size_t)T * 4)); TRY(ensure(h, h->tile_cursor, (size_t)T * 4));
-    TRY(ensure(h, h->tile_tmin, (size_t)T * 4)); TRY(ensure(h, h->tile_tmax, (size_t)T * 4));
+    TRY(ensure(h, h->tile_count, (size_t)T)); TRY(ensure(h, h->tile_cursor, (size_t)T));
+    TRY(ensure(h, h->tile_tmin, (size_t)T)); TRY(ensure(h, h->tile_tmax, (size_t)T));
     {
         FillGroup ft(h, "fills_tiles");
-        TRY(ft.zero(h->tile_count.p, (size_t)T * 4)); TRY(ft.zero(h->tile_cursor.p, (size_t)T * 4));
-        TRY(ft.i32s(h->tile_tmin.p, T, 0x7fffffff)); TRY(ft.i32s(h->tile_tmax.p, T, (i32)0x80000000));
+        TRY(ft.zero(h->tile_count.p(), T)); TRY(ft.zero(h->tile_cursor.p(), T));
+        TRY(ft.fill(h->tile_tmin.p(), T, 0x7fffffff)); TRY(ft.fill(h->tile_tmax.p(), T, (i32)0x80000000));
         TRY(ft.flush());
     }
-    TRY(ensure(h, h->tile_off, (size_t)(T + 1) * 8));
+    TRY(ensure(h, h->tile_off, (size_t)(T + 1)));
     if (h->run.fuse_on) {
         // surviving electrons compacted per instruction, tile buffers sized from their time range, photons per tile (Poisson)
         { Timer t(h, "k_fuse_electrons"); hipLaunchKernelGGL(k_fuse_electrons, dim3((unsigned)N), dim3(256), 0, h->stream, d, f); }
-        TRY(scan(h, h->ins_bcap_all.as<i32>(), N, h->ins_boff, &WfsScal::n_tbuf_samples));
+        TRY(scan(h, h->ins_bcap_all.p(), N, h->ins_boff, &WfsScal::n_tbuf_samples));
         // (the work list: TP entries for the tiles of k_s2_tile, from the front and from the back, and TP more for those of k_s2_bright)
-        TRY(ensure(h, h->ftiles, (size_t)2 * TP * sizeof(FTile))); TRY(ensure(h, h->tile_done, (size_t)TP * 4)); TRY(ensure(h, h->tile_kind, (size_t)TP));
-        f.ins_boff = h->ins_boff.as<i64>(); f.tile_count = h->tile_count.as<i32>(); f.tiles = h->ftiles.as<FTile>();
-        f.tile_done = h->tile_done.as<i32>(); f.full = h->run.fuse_full ? 1 : 0; f.n_list = TP;
+        TRY(ensure(h, h->ftiles, (size_t)2 * TP)); TRY(ensure(h, h->tile_done, (size_t)TP)); TRY(ensure(h, h->tile_kind, (size_t)TP));
+        f.ins_boff = h->ins_boff.p(); f.tile_count = h->tile_count.p(); f.tiles = h->ftiles.p();
+        f.tile_done = h->tile_done.p(); f.full = h->run.fuse_full ? 1 : 0; f.n_list = TP;
         BrightArgs &b = h->bright_args;
         b.on = (h->run.fuse_full && h->bright_on && h->bright_max_bins > 0) ? 1 : 0; b.lds_bytes = h->bright_lds; b.max_bins = h->bright_max_bins; b.pad = 0;
-        b.list_first = TP; b.tile_kind = h->tile_kind.as<int8_t>();
+        b.list_first = TP; b.tile_kind = h->tile_kind.p();
         { Timer t(h, "k_tile_counts"); hipLaunchKernelGGL(k_tile_counts, dim3(nblocks(TP, 256)), dim3(256), 0, h->stream, d, f, b); }
     }
-    TRY(scan(h, h->em_nph.as<i32>(), E, h->em_ph_off, &WfsScal::n_block_photons));
+    TRY(scan(h, h->em_nph.p(), E, h->em_ph_off, &WfsScal::n_block_photons));
     TRY(read_scal(h));
     const WfsScal &sc = *h->h_scal;
     r.P = sc.n_block_photons;                   // the tiles' own photons come on top
@@ -1690,25 +1710,25 @@ static int fill_ap_args(wfs_handle *h, ApArgs &ap, i64 ap_cap)
     ap.n = d.n_ap;
     for (int e = 0; e < d.n_ap; e++) {
         const ApElem &s = h->ap[e];
-        ap.el[e] = ApElemDev{s.n_bins_delay, s.n_bins_amp, s.amp_2d, s.is_uniform, s.delay_bin, s.amp_bin, s.delay_cdf.as<double>(), s.amp_cdf.as<double>(),
-                             s.delay_sorted, s.amp_sorted, s.delay_guide.as<ApGuide>(), s.amp_guide.as<ApGuide>()};
-        ap.prob[e] = s.prob.as<double>();
+        ap.el[e] = ApElemDev{s.n_bins_delay, s.n_bins_amp, s.amp_2d, s.is_uniform, s.delay_bin, s.amp_bin, s.delay_cdf.p(), s.amp_cdf.p(),
+                             s.delay_sorted, s.amp_sorted, s.delay_guide.p(), s.amp_guide.p()};
+        ap.prob[e] = s.prob.p();
         ApElem &sm = h->ap[e];
-        if (sm.thr_mod != d.pmt_ap_modifier || !sm.thr.p) {           // screening thresholds of the generator (ap_threshold), once per modifier
+        if (sm.thr_mod != d.pmt_ap_modifier || !sm.thr.p()) {           // screening thresholds of the generator (ap_threshold), once per modifier
             std::vector<u32> th(sm.prob_h.size() * 2);
             for (size_t c = 0; c < sm.prob_h.size(); c++) for (int dpe = 0; dpe < 2; dpe++) th[2 * c + dpe] = ap_threshold(sm.prob_h[c], d.pmt_ap_modifier, dpe != 0);
-            TRY(upload(h, sm.thr, th.data(), th.size() * 4));
+            TRY(upload(h, sm.thr, th.data(), th.size()));
             HIPCHK(hipStreamSynchronize(h->stream));
             sm.thr_mod = d.pmt_ap_modifier;
         }
-        ap.thr[e] = sm.thr.as<u32>();
+        ap.thr[e] = sm.thr.p();
     }
-    TRY(ensure(h, h->ap_ins, (size_t)ap_cap * 4)); TRY(ensure(h, h->ap_ch, (size_t)ap_cap * 4)); TRY(ensure(h, h->ap_t, (size_t)ap_cap * 4));
-    TRY(ensure(h, h->ap_gain, (size_t)ap_cap * 8)); TRY(ensure(h, h->ph_gain, (size_t)ap_cap * 8)); TRY(ensure(h, h->ap_key, (size_t)ap_cap * 4));
-    ap.ap_key = h->ap_key.as<u32>();
-    ap.cap = ap_cap; ap.ap_ins = h->ap_ins.as<i32>(); ap.ap_ch = h->ap_ch.as<i32>(); ap.ap_t = h->ap_t.as<i32>(); ap.ap_gain = h->ap_gain.as<double>();
-    ap.count = &h->scal.as<WfsScal>()->n_ap_candidates;
-    TRY(ensure(h, h->ap_cand, (size_t)ap_cap * sizeof(ApCand))); ap.cand = h->ap_cand.as<ApCand>();
+    TRY(ensure(h, h->ap_ins, (size_t)ap_cap)); TRY(ensure(h, h->ap_ch, (size_t)ap_cap)); TRY(ensure(h, h->ap_t, (size_t)ap_cap));
+    TRY(ensure(h, h->ap_gain, (size_t)ap_cap)); TRY(ensure(h, h->ph_gain, (size_t)ap_cap)); TRY(ensure(h, h->ap_key, (size_t)ap_cap));
+    ap.ap_key = h->ap_key.p();
+    ap.cap = ap_cap; ap.ap_ins = h->ap_ins.p(); ap.ap_ch = h->ap_ch.p(); ap.ap_t = h->ap_t.p(); ap.ap_gain = h->ap_gain.p();
+    ap.count = &h->scal.p()->n_ap_candidates;
+    TRY(ensure(h, h->ap_cand, (size_t)ap_cap)); ap.cand = h->ap_cand.p();
     return WFS_OK;
 }
 
@@ -1719,33 +1739,33 @@ static int gen_block_photons(wfs_handle *h, GenRun &r)
     GenArgs &g = r.g; ApArgs &ap = r.ap;
     const i64 N = h->batch.n_ins, P = r.P, TP = r.TP;
     const bool ext = r.ext;
-    g.em_ph_off = h->em_ph_off.as<i64>(); g.n_photons = P;
+    g.em_ph_off = h->em_ph_off.p(); g.n_photons = P;
     const bool ap_on = r.ap_on = h->batch.ap_sets;
     const i64 ap_cap = r.ap_cap = ap_on ? (P + h->run.p_fused) / 8 + 65536 : 0;
-    TRY(ensure(h, h->ph, (size_t)(P + h->run.p_fused + ap_cap) * 8));
-    TRY(ensure(h, h->ph_idx, (size_t)(P + h->run.p_fused + ap_cap) * 4)); g.ph_idx = h->ph_idx.as<u32>();
-    g.tile_count = h->tile_count.as<i32>(); g.tile_cursor = h->tile_cursor.as<i32>(); g.tile_tmin = h->tile_tmin.as<i32>();
-    g.tile_tmax = h->tile_tmax.as<i32>(); g.ph = h->ph.as<PhotonRec>();
-    g.tile_off = h->tile_off.as<i64>();
+    TRY(ensure(h, h->ph, (size_t)(P + h->run.p_fused + ap_cap)));
+    TRY(ensure(h, h->ph_idx, (size_t)(P + h->run.p_fused + ap_cap))); g.ph_idx = h->ph_idx.p();
+    g.tile_count = h->tile_count.p(); g.tile_cursor = h->tile_cursor.p(); g.tile_tmin = h->tile_tmin.p();
+    g.tile_tmax = h->tile_tmax.p(); g.ph = h->ph.p();
+    g.tile_off = h->tile_off.p();
     if (ap_on) TRY(fill_ap_args(h, ap, ap_cap));
-    TRY(ensure(h, h->ins_ph0, (size_t)(N + 1) * 8)); g.ins_ph0 = h->ins_ph0.as<i64>();
+    TRY(ensure(h, h->ins_ph0, (size_t)(N + 1))); g.ins_ph0 = h->ins_ph0.p();
     { Timer t(h, "k_ins_ph0"); hipLaunchKernelGGL(k_ins_ph0, dim3(nblocks(N + 1, 256)), dim3(256), 0, h->stream, g); }
-    TRY(ensure(h, h->ins_sbase, (size_t)N * 4)); g.ins_sbase = h->ins_sbase.as<u32>();
-    TRY(ensure(h, h->ins_fullsort, (size_t)N * 4)); g.ins_fullsort = h->ins_fullsort.as<i32>();
-    TRY(ensure(h, h->tile_tail, (size_t)TP * 4)); TRY(ensure(h, h->tile_tailbase, (size_t)TP * 4));
+    TRY(ensure(h, h->ins_sbase, (size_t)N)); g.ins_sbase = h->ins_sbase.p();
+    TRY(ensure(h, h->ins_fullsort, (size_t)N)); g.ins_fullsort = h->ins_fullsort.p();
+    TRY(ensure(h, h->tile_tail, (size_t)TP)); TRY(ensure(h, h->tile_tailbase, (size_t)TP));
     {
         FillGroup fg(h, "fills_block_photons");
-        TRY(fg.zero(h->tile_tail.p, (size_t)TP * 4)); TRY(fg.zero(h->tile_tailbase.p, (size_t)TP * 4));
+        TRY(fg.zero(h->tile_tail.p(), TP)); TRY(fg.zero(h->tile_tailbase.p(), TP));
         TRY(fg.flush());
     }
-    g.tile_tail = h->tile_tail.as<i32>(); g.tile_tailbase = h->tile_tailbase.as<i32>();
+    g.tile_tail = h->tile_tail.p(); g.tile_tailbase = h->tile_tailbase.p();
     { Timer t(h, "k_set_bases"); hipLaunchKernelGGL(k_set_bases, dim3(nblocks(h->batch.n_psets, 256)), dim3(256), 0, h->stream, g); }
     if (P > 0) {
         const unsigned nb = (unsigned)((P + GEN_BLOCK - 1) / GEN_BLOCK);
         g.n_blocks = nb;
-        TRY(ensure(h, h->blk_e, (size_t)nb * 16)); TRY(ensure(h, h->blk_base, (size_t)nb * d.n_tpc * 4)); TRY(ensure(h, h->blk_cnt, (size_t)nb * d.n_tpc * 2)); TRY(ensure(h, h->blk_ins, (size_t)nb * 4));
-        g.blk_e = h->blk_e.as<i64>(); g.blk_base = h->blk_base.as<u32>(); g.blk_cnt = h->blk_cnt.as<unsigned short>(); g.blk_ins = h->blk_ins.as<i32>();
-        TRY(ensure(h, h->blk_desc, (size_t)nb * sizeof(BlockDesc))); g.blk_desc = h->blk_desc.as<BlockDesc>();
+        TRY(ensure(h, h->blk_e, (size_t)nb * MINMAX)); TRY(ensure(h, h->blk_base, (size_t)nb * d.n_tpc)); TRY(ensure(h, h->blk_cnt, (size_t)nb * d.n_tpc)); TRY(ensure(h, h->blk_ins, (size_t)nb));
+        g.blk_e = h->blk_e.p(); g.blk_base = h->blk_base.p(); g.blk_cnt = h->blk_cnt.p(); g.blk_ins = h->blk_ins.p();
+        TRY(ensure(h, h->blk_desc, (size_t)nb)); g.blk_desc = h->blk_desc.p();
         { Timer t(h, "k_block_emitters"); hipLaunchKernelGGL(k_block_emitters, dim3(nblocks(nb, 256)), dim3(256), 0, h->stream, g); }
         // XCD x (workgroup id % 8) walks the photon blocks [x * chunk, (x + 1) * chunk) in order: the blocks that share
         // cache lines of a tile (consecutive ranges, k_block_ranges) run close together in time on the same L2
@@ -1754,14 +1774,14 @@ static int gen_block_photons(wfs_handle *h, GenRun &r)
         {   // alias cells of every channel CDF row (host rows + rows from the device maps, the electron-averaged ones included)
             const i64 n_rows = h->batch.n_host_rows + (i64)h->batch.dev_row_ins.size();
             int lg = 1; while ((1 << lg) < d.n_tpc) lg++;
-            TRY(ensure(h, h->chan_alias, (size_t)n_rows * ((size_t)8 << lg)));
-            g.chan_alias = h->chan_alias.as<uint2>(); g.ch_lg = lg;
-            Timer t(h, "k_chan_alias"); hipLaunchKernelGGL(k_chan_alias, dim3((unsigned)n_rows), dim3(64), 0, h->stream, g.cdf_table, d.n_tpc, lg, h->chan_alias.as<uint2>());
+            TRY(ensure(h, h->chan_alias, (size_t)n_rows << lg));
+            g.chan_alias = h->chan_alias.p(); g.ch_lg = lg;
+            Timer t(h, "k_chan_alias"); hipLaunchKernelGGL(k_chan_alias, dim3((unsigned)n_rows), dim3(64), 0, h->stream, g.cdf_table, d.n_tpc, lg, h->chan_alias.p());
         }
         if (g.gg_inv) { Timer t(h, "k_gg_sum"); hipLaunchKernelGGL(k_gg_sum, dim3(nb), dim3(256), 0, h->stream, d, g); }
         { Timer t(h, "k_photon_count"); hipLaunchKernelGGL(k_photon_count, dim3(nbx), dim3(COUNT_TPB), (size_t)count_lds(d.n_tpc, g.ch_lg).total, h->stream, d, g); }
         { Timer t(h, "k_block_ranges"); hipLaunchKernelGGL(k_block_ranges, dim3(nblocks(TP, 256)), dim3(256), 0, h->stream, d, g); }
-        TRY(scan_into(h, h->tile_count.as<i32>(), TP, h->tile_off.as<i64>(), &WfsScal::n_tile_photons, 0));
+        TRY(scan_into(h, h->tile_count.p(), TP, h->tile_off.p(), &WfsScal::n_tile_photons, 0));
         const size_t gen_lds = (size_t)gen_fill_lds(d.n_tpc, g.ch_lg, ap_on).total;
         { Timer t(h, "k_photon_fill");
           if (ext && ap_on) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_photon_fill<true, true>), dim3(nbx), dim3(FILL_TPB), gen_lds, h->stream, d, g, ap);
@@ -1769,7 +1789,7 @@ static int gen_block_photons(wfs_handle *h, GenRun &r)
           else if (ap_on) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_photon_fill<true, false>), dim3(nbx), dim3(FILL_TPB), gen_lds, h->stream, d, g, ap);
           else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_photon_fill<false, false>), dim3(nbx), dim3(FILL_TPB), gen_lds, h->stream, d, g, ap); }
     } else {
-        TRY(scan_into(h, h->tile_count.as<i32>(), TP, h->tile_off.as<i64>(), &WfsScal::n_tile_photons, 0));
+        TRY(scan_into(h, h->tile_count.p(), TP, h->tile_off.p(), &WfsScal::n_tile_photons, 0));
     }
     return WFS_OK;
 }
@@ -1786,17 +1806,17 @@ static int gen_tile_photons(wfs_handle *h, GenRun &r)
     const bool counts_only = (h->debug_bits & DBG_GEN_ONLY) && !(h->debug_bits & DBG_KEEP_PHOTONS);
     if (h->run.fuse_on && n_tilegen_tiles(h) > 0 && !counts_only) {
         TRY(pack_fence(h));         // the tile buffers: the first write of a run to what the previous batch's packers read
-        TRY(ensure(h, h->tbuf, (size_t)h->h_scal->n_tbuf_samples * 4 + 64));
-        TRY(ensure(h, h->tile_truth, (size_t)T * 8 * 8));
-        f.tile_off = h->tile_off.as<i64>(); f.tile_tmin = h->tile_tmin.as<i32>(); f.tile_tmax = h->tile_tmax.as<i32>(); f.tile_truth = h->tile_truth.as<double>();
-        f.tbuf = h->tbuf.as<i32>(); f.ph = h->ph.as<PhotonRec>(); f.keep_ph = (h->debug_bits & DBG_KEEP_PHOTONS) ? 1 : 0;
+        TRY(ensure(h, h->tbuf, (size_t)h->h_scal->n_tbuf_samples + 16));
+        TRY(ensure(h, h->tile_truth, (size_t)T * TRUTH_PER_TILE));
+        f.tile_off = h->tile_off.p(); f.tile_tmin = h->tile_tmin.p(); f.tile_tmax = h->tile_tmax.p(); f.tile_truth = h->tile_truth.p();
+        f.tbuf = h->tbuf.p(); f.ph = h->ph.p(); f.keep_ph = (h->debug_bits & DBG_KEEP_PHOTONS) ? 1 : 0;
         const TemplateArg tp = fill_template_arg(h);
         const size_t lds = (size_t)tile_lds(h->cfg.fma != 0, ap_on).total;
         const ApArgs *app = nullptr;
         if (ap_on) {
-            TRY(ensure(h, h->ap_seg, (size_t)n_tilegen_tiles(h) * sizeof(ApSeg))); ap.seg = h->ap_seg.as<ApSeg>(); ap.n_seg = n_tilegen_tiles(h);      // (one segment per tile of every class)
+            TRY(ensure(h, h->ap_seg, (size_t)n_tilegen_tiles(h))); ap.seg = h->ap_seg.p(); ap.n_seg = n_tilegen_tiles(h);      // (one segment per tile of every class)
             f.n_ptiles = TP;
-            TRY(upload(h, h->ap_args_dev, &ap, sizeof ap)); app = h->ap_args_dev.as<ApArgs>();      // (`ap` outlives the copy: read_scal of gen_afterpulses)
+            TRY(upload(h, h->ap_args_dev, &ap, 1)); app = h->ap_args_dev.p();      // (`ap` outlives the copy: read_scal of gen_afterpulses)
         }
         f.sparse_max = h->tap_sparse_max;
         // tiles of up to 2048 photons: photons and pulse in one workgroup (listed from the front); brighter ones -- and every tile in the
@@ -1836,9 +1856,9 @@ static int gen_afterpulses(wfs_handle *h, GenRun &r)
     { Timer t(h, "k_ap_finish"); hipLaunchKernelGGL(k_ap_finish, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap); }
     { Timer t(h, "k_ap_count"); hipLaunchKernelGGL(k_ap_count, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap);
       if (ap.n_seg > 0) hipLaunchKernelGGL(k_ap_seg<false>, dim3(nblocks(ap.n_seg, 4)), dim3(256), 0, h->stream, d, g, ap, (double *)nullptr); }
-    TRY(scan_into(h, h->tile_count.as<i32>() + TP, TP, h->tile_off.as<i64>() + TP, &WfsScal::n_ap_photons, P + h->run.p_fused));      // (behind the slots of every primary tile, the tile-generated ones included)
-    { Timer t(h, "k_ap_place"); hipLaunchKernelGGL(k_ap_place, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap, h->ph_gain.as<double>() - (P + h->run.p_fused));
-      if (ap.n_seg > 0) hipLaunchKernelGGL(k_ap_seg<true>, dim3(nblocks(ap.n_seg, 4)), dim3(256), 0, h->stream, d, g, ap, h->ph_gain.as<double>() - (P + h->run.p_fused)); }
+    TRY(scan_into(h, h->tile_count.p() + TP, TP, h->tile_off.p() + TP, &WfsScal::n_ap_photons, P + h->run.p_fused));      // (behind the slots of every primary tile, the tile-generated ones included)
+    { Timer t(h, "k_ap_place"); hipLaunchKernelGGL(k_ap_place, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap, h->ph_gain.p() - (P + h->run.p_fused));
+      if (ap.n_seg > 0) hipLaunchKernelGGL(k_ap_seg<true>, dim3(nblocks(ap.n_seg, 4)), dim3(256), 0, h->stream, d, g, ap, h->ph_gain.p() - (P + h->run.p_fused)); }
     TRY(read_scal(h));
     if (h->h_scal->n_ap_candidates > ap_cap) return h->fail(WFS_E_CAPACITY, "more PMT afterpulse photons than 1/8 of the primary photons: afterpulse probability unreasonably high");
     h->run.n_ap_photons = h->h_scal->n_ap_photons;                   // (the accepted candidates: total of the afterpulse tiles' counts, the scan above)
@@ -1853,11 +1873,11 @@ static int gen_order(wfs_handle *h, GenRun &r)
     const WfsDev &d = h->dev;
     const i64 T = h->batch.n_tiles, P = r.P, TP = r.TP;
     const bool ap_on = r.ap_on;
-    TRY(ensure(h, h->order_list, (size_t)T * 2 * sizeof(OrderRange))); TRY(ensure(h, h->order_list2, (size_t)T * 2 * sizeof(OrderRange)));
-    OrderArgs oa{T, TP, h->tile_count.as<i32>(), h->tile_off.as<i64>(), h->ph.as<PhotonRec>(), h->ph_idx.as<u32>(),
-                 ap_on ? h->ph_gain.as<double>() : nullptr, P + h->run.p_fused, h->order_list.as<OrderRange>(), h->order_list2.as<OrderRange>(), h->scal.as<WfsScal>(),
-                 (h->run.fuse_on && n_tilegen_tiles(h) > 0) ? h->ins_fused.as<i32>() : nullptr, d.n_tpc,
-                 h->tile_cursor.as<i32>(), h->tile_tailbase.as<i32>(), h->ins_fullsort.as<i32>(), h->set_ins_off.as<i64>(), h->set_ins_list.as<i32>()};
+    TRY(ensure(h, h->order_list, (size_t)T * 2)); TRY(ensure(h, h->order_list2, (size_t)T * 2));
+    OrderArgs oa{T, TP, h->tile_count.p(), h->tile_off.p(), h->ph.p(), h->ph_idx.p(),
+                 ap_on ? h->ph_gain.p() : nullptr, P + h->run.p_fused, h->order_list.p(), h->order_list2.p(), h->scal.p(),
+                 (h->run.fuse_on && n_tilegen_tiles(h) > 0) ? h->ins_fused.p() : nullptr, d.n_tpc,
+                 h->tile_cursor.p(), h->tile_tailbase.p(), h->ins_fullsort.p(), h->set_ins_off.p(), h->set_ins_list.p()};
     return order_ranges(h, oa);
 }
 
@@ -1877,26 +1897,26 @@ static int order_ranges(wfs_handle *h, const OrderArgs &oa)
     if (n_huge > 0) {
         // ranges beyond the workgroup sort: compact copies, one segmented radix sort over (order key, position), records to their ranks
         std::vector<OrderRange> rg((size_t)n_huge);
-        HIPCHK(hipMemcpy(rg.data(), oa.big_list + (2 * T - n_huge), (size_t)n_huge * sizeof(OrderRange), hipMemcpyDeviceToHost));
+        TRY(copy_out(h, rg.data(), oa.big_list + (2 * T - n_huge), (size_t)n_huge));
         std::sort(rg.begin(), rg.end(), [](const OrderRange &x, const OrderRange &y) { return x.start < y.start; });      // (appended with atomics: a fixed order for the offsets)
         std::vector<i64> start((size_t)n_huge), cbeg((size_t)n_huge + 1, 0);
         for (i64 k = 0; k < n_huge; k++) { start[(size_t)k] = rg[(size_t)k].start; cbeg[(size_t)k + 1] = cbeg[(size_t)k] + rg[(size_t)k].n; }
         const i64 tot = cbeg[(size_t)n_huge];
         if (tot > 0xffffffffLL) return h->fail(WFS_E_CAPACITY, "more than 2^32 photons in tiles beyond 4096 photons");
-        TRY(upload(h, h->huge_start, start.data(), start.size() * 8)); TRY(upload(h, h->huge_cbeg, cbeg.data(), cbeg.size() * 8));
-        TRY(ensure(h, h->huge_keys, (size_t)tot * 4)); TRY(ensure(h, h->huge_keys2, (size_t)tot * 4)); TRY(ensure(h, h->huge_vals, (size_t)tot * 4)); TRY(ensure(h, h->huge_vals2, (size_t)tot * 4));
-        TRY(ensure(h, h->huge_rec, (size_t)tot * 8)); TRY(ensure(h, h->huge_gain, (size_t)tot * 8));
-        HugeOrderArgs ha{n_huge, tot, h->huge_start.as<i64>(), h->huge_cbeg.as<i64>(), oa.ph, oa.ph_idx, oa.ph_gain, oa.gain_first,
-                         h->huge_keys.as<u32>(), h->huge_vals.as<u32>(), h->huge_rec.as<PhotonRec>(), h->huge_gain.as<double>()};
+        TRY(upload(h, h->huge_start, start.data(), start.size())); TRY(upload(h, h->huge_cbeg, cbeg.data(), cbeg.size()));
+        TRY(ensure(h, h->huge_keys, (size_t)tot)); TRY(ensure(h, h->huge_keys2, (size_t)tot)); TRY(ensure(h, h->huge_vals, (size_t)tot)); TRY(ensure(h, h->huge_vals2, (size_t)tot));
+        TRY(ensure(h, h->huge_rec, (size_t)tot)); TRY(ensure(h, h->huge_gain, (size_t)tot));
+        HugeOrderArgs ha{n_huge, tot, h->huge_start.p(), h->huge_cbeg.p(), oa.ph, oa.ph_idx, oa.ph_gain, oa.gain_first,
+                         h->huge_keys.p(), h->huge_vals.p(), h->huge_rec.p(), h->huge_gain.p()};
         Timer t(h, "k_tile_order_huge");
         hipLaunchKernelGGL(k_order_huge_pack, dim3(nblocks(tot, 256)), dim3(256), 0, h->stream, ha);
         size_t bytes = 0;
-        HIPCHK(rocprim::segmented_radix_sort_pairs(nullptr, bytes, h->huge_keys.as<u32>(), h->huge_keys2.as<u32>(), h->huge_vals.as<u32>(), h->huge_vals2.as<u32>(),
-                                                   (unsigned)tot, (unsigned)n_huge, h->huge_cbeg.as<i64>(), h->huge_cbeg.as<i64>() + 1, 0u, 32u, h->stream));
+        HIPCHK(rocprim::segmented_radix_sort_pairs(nullptr, bytes, h->huge_keys.p(), h->huge_keys2.p(), h->huge_vals.p(), h->huge_vals2.p(),
+                                                   (unsigned)tot, (unsigned)n_huge, h->huge_cbeg.p(), h->huge_cbeg.p() + 1, 0u, 32u, h->stream));
         TRY(ensure(h, h->sort_tmp, bytes));
-        HIPCHK(rocprim::segmented_radix_sort_pairs(h->sort_tmp.p, bytes, h->huge_keys.as<u32>(), h->huge_keys2.as<u32>(), h->huge_vals.as<u32>(), h->huge_vals2.as<u32>(),
-                                                   (unsigned)tot, (unsigned)n_huge, h->huge_cbeg.as<i64>(), h->huge_cbeg.as<i64>() + 1, 0u, 32u, h->stream));
-        hipLaunchKernelGGL(k_order_huge_apply, dim3(nblocks(tot, 256)), dim3(256), 0, h->stream, ha, h->huge_keys2.as<u32>(), h->huge_vals2.as<u32>(), h->ph.as<PhotonRec>(), h->ph_idx.as<u32>(),
+        HIPCHK(rocprim::segmented_radix_sort_pairs(h->sort_tmp.p, bytes, h->huge_keys.p(), h->huge_keys2.p(), h->huge_vals.p(), h->huge_vals2.p(),
+                                                   (unsigned)tot, (unsigned)n_huge, h->huge_cbeg.p(), h->huge_cbeg.p() + 1, 0u, 32u, h->stream));
+        hipLaunchKernelGGL(k_order_huge_apply, dim3(nblocks(tot, 256)), dim3(256), 0, h->stream, ha, h->huge_keys2.p(), h->huge_vals2.p(), h->ph.p(), h->ph_idx.p(),
                            oa.ph_gain);
     }
     return WFS_OK;
@@ -1933,26 +1953,26 @@ static int optical_afterpulses(wfs_handle *h)
     const i64 P = h->batch.n_photons, TP = h->batch.n_ins * d.n_tpc, ap_cap = optical_ap_cap(P);
     GenArgs g{}; ApArgs ap{};
     TRY(fill_ap_args(h, ap, ap_cap));
-    TRY(ensure(h, h->ph_idx, (size_t)(P + ap_cap) * 4));
-    g.n_psets = h->batch.n_psets; g.tile_count = h->tile_count.as<i32>(); g.tile_cursor = h->tile_cursor.as<i32>(); g.tile_off = h->tile_off.as<i64>();
-    g.tile_tmin = h->tile_tmin.as<i32>(); g.tile_tmax = h->tile_tmax.as<i32>(); g.ph = h->ph.as<PhotonRec>(); g.ph_idx = h->ph_idx.as<u32>();
-    g.scal = h->scal.as<WfsScal>();
+    TRY(ensure(h, h->ph_idx, (size_t)(P + ap_cap)));
+    g.n_psets = h->batch.n_psets; g.tile_count = h->tile_count.p(); g.tile_cursor = h->tile_cursor.p(); g.tile_off = h->tile_off.p();
+    g.tile_tmin = h->tile_tmin.p(); g.tile_tmax = h->tile_tmax.p(); g.ph = h->ph.p(); g.ph_idx = h->ph_idx.p();
+    g.scal = h->scal.p();
     if (P > 0) {
-        OptApArgs sa{P, TP, h->tile_off.as<i64>(), h->set_gid.as<u32>(), h->set_t0.as<i64>(), h->opt_item.as<u32>(), h->ph.as<PhotonRec>()};
+        OptApArgs sa{P, TP, h->tile_off.p(), h->set_gid.p(), h->set_t0.p(), h->opt_item.p(), h->ph.p()};
         Timer t(h, "k_optical_ap_screen");
         hipLaunchKernelGGL(k_optical_ap_screen, dim3(nblocks(P, 256)), dim3(256), 0, h->stream, d, sa, ap);
     }
-    double *const gain_base = h->ph_gain.as<double>() - P;
+    double *const gain_base = h->ph_gain.p() - P;
     { Timer t(h, "k_ap_finish"); hipLaunchKernelGGL(k_ap_finish, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap); }
     { Timer t(h, "k_ap_count"); hipLaunchKernelGGL(k_ap_count, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap); }
-    TRY(scan_into(h, h->tile_count.as<i32>() + TP, TP, h->tile_off.as<i64>() + TP, &WfsScal::n_ap_photons, P));
+    TRY(scan_into(h, h->tile_count.p() + TP, TP, h->tile_off.p() + TP, &WfsScal::n_ap_photons, P));
     { Timer t(h, "k_ap_place"); hipLaunchKernelGGL(k_ap_place, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap, gain_base); }
     TRY(read_scal(h));
     if (h->h_scal->n_ap_candidates > ap_cap) return h->fail(WFS_E_CAPACITY, "more PMT afterpulse photons than 1/8 of the primary photons: afterpulse probability unreasonably high");
     h->run.n_ap_photons = h->h_scal->n_ap_photons;
-    TRY(ensure(h, h->order_list, (size_t)TP * 2 * sizeof(OrderRange))); TRY(ensure(h, h->order_list2, (size_t)TP * 2 * sizeof(OrderRange)));
-    OrderArgs oa{TP, 0, h->tile_count.as<i32>() + TP, h->tile_off.as<i64>() + TP, h->ph.as<PhotonRec>(), h->ph_idx.as<u32>(), h->ph_gain.as<double>(), P,
-                 h->order_list.as<OrderRange>(), h->order_list2.as<OrderRange>(), h->scal.as<WfsScal>(), nullptr, d.n_tpc, nullptr, nullptr, nullptr, nullptr, nullptr};
+    TRY(ensure(h, h->order_list, (size_t)TP * 2)); TRY(ensure(h, h->order_list2, (size_t)TP * 2));
+    OrderArgs oa{TP, 0, h->tile_count.p() + TP, h->tile_off.p() + TP, h->ph.p(), h->ph_idx.p(), h->ph_gain.p(), P,
+                 h->order_list.p(), h->order_list2.p(), h->scal.p(), nullptr, d.n_tpc, nullptr, nullptr, nullptr, nullptr, nullptr};
     return order_ranges(h, oa);
 }
 
@@ -1962,24 +1982,24 @@ static int run_input(wfs_handle *h)
     const WfsDev &d = h->dev;
     // the scalar block is cleared with the first fills of the run: the generator's (gen_electrons), or alone
     FillGroup fg(h, from_generator(h) ? "fills_electrons" : "fills_input");
-    TRY(fg.zero(h->scal.p, sizeof(WfsScal)));
+    TRY(fg.zero(h->scal.p(), 1));
     if (from_generator(h)) return run_generation(h, fg);
     const bool optical = h->batch.kind == BatchKind::Optical;
     if (optical && h->batch.ap_sets) {
         // the afterpulse tiles start every run empty (the primary tiles keep the counts and offsets of wfs_load_optical)
         const i64 TP = h->batch.n_ins * d.n_tpc;
-        TRY(fg.zero(h->tile_count.as<i32>() + TP, (size_t)TP * 4)); TRY(fg.zero(h->tile_cursor.as<i32>() + TP, (size_t)TP * 4));
-        TRY(fg.i32s(h->tile_tmin.as<i32>() + TP, TP, 0x7fffffff)); TRY(fg.i32s(h->tile_tmax.as<i32>() + TP, TP, (i32)0x80000000));
+        TRY(fg.zero(h->tile_count.p() + TP, TP)); TRY(fg.zero(h->tile_cursor.p() + TP, TP));
+        TRY(fg.fill(h->tile_tmin.p() + TP, TP, 0x7fffffff)); TRY(fg.fill(h->tile_tmax.p() + TP, TP, (i32)0x80000000));
     }
     TRY(fg.flush());
     if (optical) {
         const i64 T = h->batch.n_ins * d.n_tpc;                    // the primary tiles (afterpulse tiles follow them)
-        OpticalArgs oa{T, h->tile_count.as<i32>(), h->tile_off.as<i64>(), h->tile_tmin.as<i32>(), h->tile_tmax.as<i32>(), h->set_gid.as<u32>(),
-                       h->opt_t.as<i32>(), h->opt_item.as<u32>(), h->ph.as<PhotonRec>(), h->scal.as<WfsScal>()};
+        OpticalArgs oa{T, h->tile_count.p(), h->tile_off.p(), h->tile_tmin.p(), h->tile_tmax.p(), h->set_gid.p(),
+                       h->opt_t.p(), h->opt_item.p(), h->ph.p(), h->scal.p()};
         { Timer t(h, "k_optical_finish"); hipLaunchKernelGGL(k_optical_finish, dim3(nblocks(T, 256)), dim3(256), 0, h->stream, d, oa); }
         if (h->batch.ap_sets) TRY(optical_afterpulses(h));
     }
-    else { TRY(scan(h, h->tile_count.as<i32>(), h->batch.n_tiles, h->tile_off, &WfsScal::n_tile_photons)); }
+    else { TRY(scan(h, h->tile_count.p(), h->batch.n_tiles, h->tile_off, &WfsScal::n_tile_photons)); }
     return WFS_OK;
 }
 
@@ -1991,30 +2011,30 @@ static int run_geometry(wfs_handle *h, RunState &r)
     const i64 T = h->batch.n_tiles, S = h->batch.n_sets, C = h->batch.n_clusters;
     const i64 CG = r.CG = C + 1;
     FillGroup fg(h, "fills_geometry");
-    TRY(ensure(h, h->cl_end, (size_t)C * 8)); TRY(fg.i64s(h->cl_end.p, C, I64_MIN)); TRY(ensure(h, h->cl_group, (size_t)C * 4));
-    TRY(ensure(h, h->grp_lo, (size_t)CG * 8)); TRY(ensure(h, h->grp_hi, (size_t)CG * 8));
-    TRY(fg.i64s(h->grp_lo.p, CG, I64_MAX)); TRY(fg.i64s(h->grp_hi.p, CG, I64_MIN));
-    TRY(ensure(h, h->grp_left, (size_t)CG * 8)); TRY(ensure(h, h->grp_right, (size_t)CG * 8)); TRY(ensure(h, h->grp_ixrand, (size_t)CG * 8));
-    TRY(ensure(h, h->grp_gid, (size_t)CG * 4)); TRY(fg.bytes(h->grp_gid.p, (size_t)CG * 4, 0xff));
-    TRY(ensure(h, h->row_lo, (size_t)CG * d.n_tpc * 8)); TRY(ensure(h, h->row_hi, (size_t)CG * d.n_tpc * 8));
-    TRY(fg.i64s(h->row_lo.p, CG * d.n_tpc, I64_MAX)); TRY(fg.i64s(h->row_hi.p, CG * d.n_tpc, I64_MIN));
-    TRY(ensure(h, h->acc_len, (size_t)CG * d.n_tpc * 4)); TRY(fg.zero(h->acc_len.p, (size_t)CG * d.n_tpc * 4));
-    TRY(ensure(h, h->itv_cap, (size_t)CG * d.row_slots * 4)); TRY(ensure(h, h->active_rows, (size_t)CG * d.row_slots * 4));
-    TRY(ensure(h, h->active_tiles, (size_t)T * 4)); TRY(ensure(h, h->sparse_tiles, (size_t)T * 4)); TRY(ensure(h, h->dense_tiles, (size_t)T * 4)); TRY(ensure(h, h->wave_tiles, (size_t)T * 4));
+    TRY(ensure(h, h->cl_end, (size_t)C)); TRY(fg.fill(h->cl_end.p(), C, I64_MIN)); TRY(ensure(h, h->cl_group, (size_t)C));
+    TRY(ensure(h, h->grp_lo, (size_t)CG)); TRY(ensure(h, h->grp_hi, (size_t)CG));
+    TRY(fg.fill(h->grp_lo.p(), CG, I64_MAX)); TRY(fg.fill(h->grp_hi.p(), CG, I64_MIN));
+    TRY(ensure(h, h->grp_left, (size_t)CG)); TRY(ensure(h, h->grp_right, (size_t)CG)); TRY(ensure(h, h->grp_ixrand, (size_t)CG));
+    TRY(ensure(h, h->grp_gid, (size_t)CG)); TRY(fg.ones(h->grp_gid.p(), CG));
+    TRY(ensure(h, h->row_lo, (size_t)CG * d.n_tpc)); TRY(ensure(h, h->row_hi, (size_t)CG * d.n_tpc));
+    TRY(fg.fill(h->row_lo.p(), CG * d.n_tpc, I64_MAX)); TRY(fg.fill(h->row_hi.p(), CG * d.n_tpc, I64_MIN));
+    TRY(ensure(h, h->acc_len, (size_t)CG * d.n_tpc)); TRY(fg.zero(h->acc_len.p(), CG * d.n_tpc));
+    TRY(ensure(h, h->itv_cap, (size_t)CG * d.row_slots)); TRY(ensure(h, h->active_rows, (size_t)CG * d.row_slots));
+    TRY(ensure(h, h->active_tiles, (size_t)T)); TRY(ensure(h, h->sparse_tiles, (size_t)T)); TRY(ensure(h, h->dense_tiles, (size_t)T)); TRY(ensure(h, h->wave_tiles, (size_t)T));
     ga.n_sets = S; ga.n_tiles = T; ga.n_clusters = C; ga.n_gslots = CG;
-    ga.tile_count = h->tile_count.as<i32>(); ga.tile_tmin = h->tile_tmin.as<i32>(); ga.tile_tmax = h->tile_tmax.as<i32>();
-    ga.set_cluster = h->set_cluster.as<i32>(); ga.set_t0 = h->set_t0.as<i64>(); ga.cl_tmin = h->cl_tmin.as<i64>(); ga.cl_gid = h->cl_gid.as<u32>();
-    ga.cl_end = h->cl_end.as<i64>(); ga.cl_group = h->cl_group.as<i32>(); ga.grp_lo = h->grp_lo.as<i64>(); ga.grp_hi = h->grp_hi.as<i64>();
-    ga.grp_left = h->grp_left.as<i64>(); ga.grp_right = h->grp_right.as<i64>(); ga.grp_ixrand = h->grp_ixrand.as<i64>(); ga.grp_gid = h->grp_gid.as<u32>();
-    ga.row_lo = h->row_lo.as<i64>(); ga.row_hi = h->row_hi.as<i64>(); ga.acc_len = h->acc_len.as<i32>(); ga.itv_cap = h->itv_cap.as<i32>();
-    ga.active_rows = h->active_rows.as<i32>(); ga.scal = h->scal.as<WfsScal>(); ga.active_tiles = h->active_tiles.as<i32>(); ga.sparse_tiles = h->sparse_tiles.as<i32>(); ga.dense_tiles = h->dense_tiles.as<i32>(); ga.wave_tiles = h->wave_tiles.as<i32>(); ga.force_dense = ((h->debug_bits & DBG_FORCE_DENSE) || h->generic_geom) ? 1 : 0; ga.init_has = h->carry_has; ga.init_runmax = h->carry_runmax;
-    ga.noise_override = h->n_noise_override ? h->noise_override.as<i64>() : nullptr; ga.n_noise_override = h->n_noise_override;
+    ga.tile_count = h->tile_count.p(); ga.tile_tmin = h->tile_tmin.p(); ga.tile_tmax = h->tile_tmax.p();
+    ga.set_cluster = h->set_cluster.p(); ga.set_t0 = h->set_t0.p(); ga.cl_tmin = h->cl_tmin.p(); ga.cl_gid = h->cl_gid.p();
+    ga.cl_end = h->cl_end.p(); ga.cl_group = h->cl_group.p(); ga.grp_lo = h->grp_lo.p(); ga.grp_hi = h->grp_hi.p();
+    ga.grp_left = h->grp_left.p(); ga.grp_right = h->grp_right.p(); ga.grp_ixrand = h->grp_ixrand.p(); ga.grp_gid = h->grp_gid.p();
+    ga.row_lo = h->row_lo.p(); ga.row_hi = h->row_hi.p(); ga.acc_len = h->acc_len.p(); ga.itv_cap = h->itv_cap.p();
+    ga.active_rows = h->active_rows.p(); ga.scal = h->scal.p(); ga.active_tiles = h->active_tiles.p(); ga.sparse_tiles = h->sparse_tiles.p(); ga.dense_tiles = h->dense_tiles.p(); ga.wave_tiles = h->wave_tiles.p(); ga.force_dense = ((h->debug_bits & DBG_FORCE_DENSE) || h->generic_geom) ? 1 : 0; ga.init_has = h->carry_has; ga.init_runmax = h->carry_runmax;
+    ga.noise_override = h->n_noise_override ? h->noise_override.p() : nullptr; ga.n_noise_override = h->n_noise_override;
     if (d.sum_channel >= 0) {
-        TRY(ensure(h, h->sum_lo, (size_t)CG * 8)); TRY(ensure(h, h->sum_hi, (size_t)CG * 8));
-        TRY(fg.i64s(h->sum_lo.p, CG, I64_MAX)); TRY(fg.i64s(h->sum_hi.p, CG, I64_MIN));
-        TRY(ensure(h, h->sum_len, (size_t)CG * 4)); TRY(ensure(h, h->sum_nchunk, (size_t)CG * 4));
-        TRY(fg.zero(h->sum_len.p, (size_t)CG * 4)); TRY(fg.zero(h->sum_nchunk.p, (size_t)CG * 4));
-        ga.sum_lo = h->sum_lo.as<i64>(); ga.sum_hi = h->sum_hi.as<i64>(); ga.sum_len = h->sum_len.as<i32>(); ga.sum_nchunk = h->sum_nchunk.as<i32>();
+        TRY(ensure(h, h->sum_lo, (size_t)CG)); TRY(ensure(h, h->sum_hi, (size_t)CG));
+        TRY(fg.fill(h->sum_lo.p(), CG, I64_MAX)); TRY(fg.fill(h->sum_hi.p(), CG, I64_MIN));
+        TRY(ensure(h, h->sum_len, (size_t)CG)); TRY(ensure(h, h->sum_nchunk, (size_t)CG));
+        TRY(fg.zero(h->sum_len.p(), CG)); TRY(fg.zero(h->sum_nchunk.p(), CG));
+        ga.sum_lo = h->sum_lo.p(); ga.sum_hi = h->sum_hi.p(); ga.sum_len = h->sum_len.p(); ga.sum_nchunk = h->sum_nchunk.p();
     }
     const bool tiles_done = r.tiles_done = tiles_made(h);
     // resident rows (k_row_pulse): the usual digitiser geometry, a hold-off of at least a chunk and a noise table the fast row loads
@@ -2029,21 +2049,21 @@ static int run_geometry(wfs_handle *h, RunState &r)
     h->run.res_on = (res_mode == 2 ? res_auto : res_mode != 0) && !(h->debug_bits & (DBG_CURRENTS | DBG_FORCE_DENSE)) && !h->generic_geom && !d.he_rows && zle_holdoff(d.tw) >= ZLE_FAST_HOLD
                 && (!d.enable_noise || d.nm_cells || d.noise_len >= NOISE_MIN_FAST);
     if (tiles_done || h->run.res_on) {
-        TRY(ensure(h, h->row_cnt, (size_t)CG * d.n_tpc * 4)); TRY(ensure(h, h->row_tile, (size_t)CG * d.n_tpc * 4));
-        TRY(fg.zero(h->row_cnt.p, (size_t)CG * d.n_tpc * 4));
-        ga.row_cnt = h->row_cnt.as<i32>(); ga.row_tile = h->row_tile.as<i32>();
+        TRY(ensure(h, h->row_cnt, (size_t)CG * d.n_tpc)); TRY(ensure(h, h->row_tile, (size_t)CG * d.n_tpc));
+        TRY(fg.zero(h->row_cnt.p(), CG * d.n_tpc));
+        ga.row_cnt = h->row_cnt.p(); ga.row_tile = h->row_tile.p();
     }
     if (tiles_done) {
-        ga.tile_done = h->tile_done.as<i32>(); ga.n_done = h->batch.n_psets * d.n_tpc;
-        ga.ins_bcap = h->ins_bcap.as<i32>(); ga.ins_boff = h->ins_boff.as<i64>();
+        ga.tile_done = h->tile_done.p(); ga.n_done = h->batch.n_psets * d.n_tpc;
+        ga.ins_bcap = h->ins_bcap.p(); ga.ins_boff = h->ins_boff.p();
     }
     if (h->run.res_on) {
         const size_t nr = (size_t)CG * d.n_tpc;
-        TRY(ensure(h, h->row_bad, nr * 4)); TRY(ensure(h, h->fin_len, nr * 4)); TRY(ensure(h, h->res_cnt, nr * 4));
-        TRY(fg.zero(h->row_bad.p, nr * 4)); TRY(fg.zero(h->fin_len.p, nr * 4)); TRY(fg.zero(h->res_cnt.p, nr * 4));
-        ga.res_on = 1; ga.res_max_len = h->res_max_len; ga.row_bad = h->row_bad.as<i32>(); ga.fin_len = h->fin_len.as<i32>(); ga.res_cnt = h->res_cnt.as<i32>();
+        TRY(ensure(h, h->row_bad, nr)); TRY(ensure(h, h->fin_len, nr)); TRY(ensure(h, h->res_cnt, nr));
+        TRY(fg.zero(h->row_bad.p(), nr)); TRY(fg.zero(h->fin_len.p(), nr)); TRY(fg.zero(h->res_cnt.p(), nr));
+        ga.res_on = 1; ga.res_max_len = h->res_max_len; ga.row_bad = h->row_bad.p(); ga.fin_len = h->fin_len.p(); ga.res_cnt = h->res_cnt.p();
         ga.rows_cap = CG * d.row_slots;
-        TRY(ensure(h, h->res_long, nr * 4)); ga.res_long = h->res_long.as<i32>();
+        TRY(ensure(h, h->res_long, nr)); ga.res_long = h->res_long.p();
     }
     TRY(fg.flush());
     { Timer t(h, "k_tile_geom"); hipLaunchKernelGGL(k_tile_geom, dim3(nblocks(T, 1024)), dim3(1024), 0, h->stream, d, ga); }
@@ -2051,22 +2071,22 @@ static int run_geometry(wfs_handle *h, RunState &r)
     { Timer t(h, "k_tile_rows"); hipLaunchKernelGGL(k_tile_rows, dim3(nblocks(T, 256)), dim3(256), 0, h->stream, d, ga); }
     { Timer t(h, "k_group_final"); hipLaunchKernelGGL(k_group_final, dim3(nblocks(CG, 256)), dim3(256), 0, h->stream, d, ga); }
     { Timer t(h, "k_row_len"); hipLaunchKernelGGL(k_row_len, dim3(nblocks(CG * d.row_slots, 1024)), dim3(1024), 0, h->stream, d, ga); }
-    TRY(scan(h, h->acc_len.as<i32>(), CG * d.n_tpc, h->acc_off, &WfsScal::n_acc_samples));
-    TRY(scan(h, h->itv_cap.as<i32>(), CG * d.row_slots, h->itv_off, &WfsScal::n_itv_slots));
+    TRY(scan(h, h->acc_len.p(), CG * d.n_tpc, h->acc_off, &WfsScal::n_acc_samples));
+    TRY(scan(h, h->itv_cap.p(), CG * d.row_slots, h->itv_off, &WfsScal::n_itv_slots));
     if (d.sum_channel >= 0) {
-        TRY(scan(h, h->sum_len.as<i32>(), CG, h->sum_off, &WfsScal::n_sum_samples));
-        TRY(scan(h, h->sum_nchunk.as<i32>(), CG, h->sum_chunk_off, &WfsScal::n_sum_chunks));
+        TRY(scan(h, h->sum_len.p(), CG, h->sum_off, &WfsScal::n_sum_samples));
+        TRY(scan(h, h->sum_nchunk.p(), CG, h->sum_chunk_off, &WfsScal::n_sum_chunks));
     }
     if (h->run.res_on) {
-        TRY(scan(h, h->fin_len.as<i32>(), CG * d.n_tpc, h->fin_off, &WfsScal::n_fin_samples)); TRY(scan(h, h->res_cnt.as<i32>(), CG * d.n_tpc, h->res_toff, &WfsScal::n_res_tiles));
+        TRY(scan(h, h->fin_len.p(), CG * d.n_tpc, h->fin_off, &WfsScal::n_fin_samples)); TRY(scan(h, h->res_cnt.p(), CG * d.n_tpc, h->res_toff, &WfsScal::n_res_tiles));
         // rows are known: tiles onto their row's list or the work list of their class.  res_desc holds a descriptor slot for EVERY
         // tile of the batch (T * sizeof(TileDesc) bytes) although only the resident ones are written: their number (n_res_tiles) is
         // still on the device here, and sizing from it would cost one more host round trip before k_tile_assign
-        TRY(ensure(h, h->res_desc, (size_t)std::max<i64>(T, 1) * sizeof(TileDesc)));
-        ga.res_toff = h->res_toff.as<i64>(); ga.res_desc = h->res_desc.as<TileDesc>();
-        DescArgs da{}; da.tile_off = h->tile_off.as<i64>(); da.set_mode = h->set_mode.as<i32>();
-        TRY(ensure(h, h->tile_truth, (size_t)T * 8 * 8));
-        PulseArgs pt{}; pt.ph = h->ph.as<PhotonRec>(); pt.tile_truth = h->tile_truth.as<double>();
+        TRY(ensure(h, h->res_desc, (size_t)std::max<i64>(T, 1)));
+        ga.res_toff = h->res_toff.p(); ga.res_desc = h->res_desc.p();
+        DescArgs da{}; da.tile_off = h->tile_off.p(); da.set_mode = h->set_mode.p();
+        TRY(ensure(h, h->tile_truth, (size_t)T * TRUTH_PER_TILE));
+        PulseArgs pt{}; pt.ph = h->ph.p(); pt.tile_truth = h->tile_truth.p();
         pt.ph_gain = ph_gain_base(h);
         Timer t(h, "k_tile_assign"); hipLaunchKernelGGL(k_tile_assign, dim3(nblocks(T, 256)), dim3(256), 0, h->stream, d, ga, da, pt);
     }
@@ -2098,12 +2118,9 @@ static int run_geometry(wfs_handle *h, RunState &r)
                 (long long)(h->run.n_res_tiles + h->run.n_active_tiles), (long long)h->run.max_res_len, (long long)h->run.s_fin, (long long)h->run.s_raw);
     }
     // one work list: the sparse, dense and wave tiles behind the tiny ones
-    if (h->run.n_sparse_tiles > 0)
-        HIPCHK(hipMemcpyAsync(h->active_tiles.as<i32>() + r.first_sparse, h->sparse_tiles.p, (size_t)h->run.n_sparse_tiles * 4, hipMemcpyDeviceToDevice, h->stream));
-    if (h->run.n_dense_tiles > 0)
-        HIPCHK(hipMemcpyAsync(h->active_tiles.as<i32>() + r.first_dense, h->dense_tiles.p, (size_t)h->run.n_dense_tiles * 4, hipMemcpyDeviceToDevice, h->stream));
-    if (h->run.n_wave_tiles > 0)
-        HIPCHK(hipMemcpyAsync(h->active_tiles.as<i32>() + r.first_wave, h->wave_tiles.p, (size_t)h->run.n_wave_tiles * 4, hipMemcpyDeviceToDevice, h->stream));
+    if (h->run.n_sparse_tiles > 0) TRY(copy_async(h, h->active_tiles.p() + r.first_sparse, h->sparse_tiles.p(), (size_t)h->run.n_sparse_tiles, hipMemcpyDeviceToDevice));
+    if (h->run.n_dense_tiles > 0) TRY(copy_async(h, h->active_tiles.p() + r.first_dense, h->dense_tiles.p(), (size_t)h->run.n_dense_tiles, hipMemcpyDeviceToDevice));
+    if (h->run.n_wave_tiles > 0) TRY(copy_async(h, h->active_tiles.p() + r.first_wave, h->wave_tiles.p(), (size_t)h->run.n_wave_tiles, hipMemcpyDeviceToDevice));
     return WFS_OK;
 }
 
@@ -2114,53 +2131,53 @@ static int run_pulses(wfs_handle *h, RunState &r)
     PulseArgs &pa = r.pa;
     const i64 T = h->batch.n_tiles, S = h->batch.n_sets;
     TRY(pack_fence(h));             // the accumulators are the first such write of a run without tile buffers (with them: gen_tile_photons)
-    // (+64: a lane of k_zle reads 4 samples from its first valid one; the sum rows behind the accumulators are written whole by k_sum_signal)
-    TRY(ensure(h, h->raw, (size_t)(h->run.s_sum > 0 ? h->run.sum_base + h->run.s_sum : h->run.s_raw) * 4 + 64));
-    TRY(ensure(h, h->truth, (size_t)S * 16 * 8));
+    // (+16 samples, 64 bytes: a lane of k_zle reads 4 samples from its first valid one; the sum rows behind the accumulators are written whole by k_sum_signal)
+    TRY(ensure(h, h->raw, (size_t)(h->run.s_sum > 0 ? h->run.sum_base + h->run.s_sum : h->run.s_raw) + 16));
+    TRY(ensure(h, h->truth, (size_t)S * TRUTH_PER_SET));
     {
         FillGroup fg(h, "fills_pulses");
-        TRY(fg.zero(h->raw.p, (size_t)h->run.s_raw * 4)); TRY(fg.zero(h->truth.p, (size_t)S * 16 * 8));
+        TRY(fg.zero(h->raw.p(), h->run.s_raw)); TRY(fg.zero(h->truth.p(), S * TRUTH_PER_SET));
         TRY(fg.flush());
     }
-    TRY(ensure(h, h->tminmax, (size_t)S * 16)); TRY(ensure(h, h->tile_truth, (size_t)T * 8 * 8));
-    pa.ph = h->ph.as<PhotonRec>();
+    TRY(ensure(h, h->tminmax, (size_t)S * MINMAX)); TRY(ensure(h, h->tile_truth, (size_t)T * TRUTH_PER_TILE));
+    pa.ph = h->ph.p();
     pa.ph_gain = ph_gain_base(h);
-    pa.raw = h->raw.as<i32>();
-    pa.tile_truth = h->tile_truth.as<double>();
+    pa.raw = h->raw.p();
+    pa.tile_truth = h->tile_truth.p();
     if ((h->debug_bits & DBG_CURRENTS) && h->run.n_active_tiles > 0) {
         // debug: tile lengths in work-list order -> offsets
         HIPCHK(hipStreamSynchronize(h->stream));
         const ListedTiles lt = listed_tiles(h);
         h->run.cur_total = lt.off.back();
-        TRY(upload(h, h->cur_off, lt.off.data(), lt.off.size() * 8));
-        TRY(ensure(h, h->currents, (size_t)h->run.cur_total * 8));
+        TRY(upload(h, h->cur_off, lt.off.data(), lt.off.size()));
+        TRY(ensure(h, h->currents, (size_t)h->run.cur_total));
         HIPCHK(hipStreamSynchronize(h->stream));
-        pa.currents = h->currents.as<double>(); pa.cur_off = h->cur_off.as<i64>();
+        pa.currents = h->currents.p(); pa.cur_off = h->cur_off.p();
     }
     if (h->run.n_active_tiles > 0) {        // tile descriptors of the whole work list (read by every pulse kernel)
-        TRY(ensure(h, h->tile_desc, (size_t)h->run.n_active_tiles * sizeof(TileDesc)));
-        DescArgs da{h->active_tiles.as<i32>(), h->run.n_active_tiles, h->tile_count.as<i32>(), h->tile_tmin.as<i32>(), h->tile_tmax.as<i32>(), h->tile_off.as<i64>(),
-                    h->set_cluster.as<i32>(), h->set_t0.as<i64>(), h->set_mode.as<i32>(), h->cl_group.as<i32>(), h->row_lo.as<i64>(), h->acc_off.as<i64>(),
-                    h->tile_desc.as<TileDesc>()};
+        TRY(ensure(h, h->tile_desc, (size_t)h->run.n_active_tiles));
+        DescArgs da{h->active_tiles.p(), h->run.n_active_tiles, h->tile_count.p(), h->tile_tmin.p(), h->tile_tmax.p(), h->tile_off.p(),
+                    h->set_cluster.p(), h->set_t0.p(), h->set_mode.p(), h->cl_group.p(), h->row_lo.p(), h->acc_off.p(),
+                    h->tile_desc.p()};
         Timer t(h, "k_tile_desc");
         hipLaunchKernelGGL(k_tile_desc, dim3(nblocks(h->run.n_active_tiles, 256)), dim3(256), 0, h->stream, d, da);
     }
     if (h->run.n_tiny_tiles > 0) {
         PulseArgs pt = pa;
-        pt.desc = h->tile_desc.as<TileDesc>();
+        pt.desc = h->tile_desc.p();
         Timer t(h, "k_pulse_tiny");
         WFS_LAUNCH_F(h, K_PULSE_TINY, dim3(nblocks(h->run.n_tiny_tiles * TINY_LANES, 256)), dim3(256), 0, d, pt, h->run.n_tiny_tiles);
     }
     if (h->run.n_wave_tiles > 0) {
         PulseArgs pw = pa;
-        pw.desc = h->tile_desc.as<TileDesc>() + r.first_wave;
+        pw.desc = h->tile_desc.p() + r.first_wave;
         if (pw.cur_off) pw.cur_off += r.first_wave;
         Timer t(h, "k_pulse_wave");
         WFS_LAUNCH_F(h, K_PULSE_WAVE, dim3(nblocks(h->run.n_wave_tiles, 4)), dim3(256), 0, d, pw, h->run.n_wave_tiles);
     }
     if (h->run.n_sparse_tiles > 0) {
         PulseArgs ps = pa;
-        ps.desc = h->tile_desc.as<TileDesc>() + r.first_sparse;
+        ps.desc = h->tile_desc.p() + r.first_sparse;
         if (ps.cur_off) ps.cur_off += r.first_sparse;
         ps.W = (int)((h->run.max_nb + 7) / 8 * 8); ps.NP = (int)((h->run.max_tile + 7) / 8 * 8);
         // (tile_class lists a tile here with at most SPARSE_MAX_PHOTONS photons in at most SPARSE_MAX_BINS start bins: one form, 64 threads)
@@ -2170,7 +2187,7 @@ static int run_pulses(wfs_handle *h, RunState &r)
     }
     if (h->run.n_dense_tiles > 0 && h->generic_geom) {        // any digitiser geometry: one kernel for every tile
         PulseArgs pd = pa;
-        pd.desc = h->tile_desc.as<TileDesc>() + r.first_dense;
+        pd.desc = h->tile_desc.p() + r.first_dense;
         if (pd.cur_off) pd.cur_off += r.first_dense;
         // two H tables (order-independent merge of the gains of one cell) where they fit, one otherwise
         pd.n_win = generic_lds_split(d.dt, d.tlen) ? 1 : 0;
@@ -2180,7 +2197,7 @@ static int run_pulses(wfs_handle *h, RunState &r)
         WFS_LAUNCH_F(h, K_PULSE_GENERIC, dim3((unsigned)h->run.n_dense_tiles), dim3(256), lds, d, pd);
     } else if (h->run.n_dense_tiles > 0) {
         PulseArgs pd = pa;
-        pd.desc = h->tile_desc.as<TileDesc>() + r.first_dense;
+        pd.desc = h->tile_desc.p() + r.first_dense;
         if (pd.cur_off) pd.cur_off += r.first_dense;
         // chunks of TPB live samples per pass (TPB + 21 start-bin rows of 80 bytes in LDS: 22 KB for 256 -> 7 workgroups per CU)
         const i64 n_live_max = h->run.max_nb_dense + d.tlen - 1;
@@ -2210,7 +2227,7 @@ static int run_pulses(wfs_handle *h, RunState &r)
     }
 
     if (r.tiles_done && h->h_scal->n_shared_rows > 0) {   // tiles of k_s2_tile that share their row with other pulses: added into the row's accumulators
-        TileAddArgs ta{h->set_cluster.as<i32>(), h->cl_group.as<i32>(), h->row_lo.as<i64>(), h->acc_off.as<i64>(), h->row_cnt.as<i32>(), h->raw.as<i32>()};
+        TileAddArgs ta{h->set_cluster.p(), h->cl_group.p(), h->row_lo.p(), h->acc_off.p(), h->row_cnt.p(), h->raw.p()};
         Timer t(h, "k_tile_add");
         if (h->run.n_fused_tiles > 0) hipLaunchKernelGGL(k_tile_add, dim3((unsigned)h->run.n_fused_tiles), dim3(256), 0, h->stream, d, h->fuse_args, ta);
         if (h->run.n_bright_tiles > 0) {                       // (the tiles of k_s2_bright: their own stretch of the work list)
@@ -2228,42 +2245,42 @@ static int run_rows(wfs_handle *h, RunState &r)
     const GeomArgs &ga = r.ga; const PulseArgs &pa = r.pa; ZleArgs &za = r.za;
     const i64 S = h->batch.n_sets, CG = r.CG;
     const i64 RS = r.RS = CG * d.row_slots;
-    TRY(ensure(h, h->itv_left, (size_t)h->run.n_itv_slots * 8 + 16)); TRY(ensure(h, h->itv_right, (size_t)h->run.n_itv_slots * 8 + 16));      // (+16: k_pack reads the first two slots of a row whatever its capacity)
-    TRY(ensure(h, h->itv_n, (size_t)RS * 4)); TRY(ensure(h, h->row_nrec, (size_t)RS * 4));
+    TRY(ensure(h, h->itv_left, (size_t)h->run.n_itv_slots + 2)); TRY(ensure(h, h->itv_right, (size_t)h->run.n_itv_slots + 2));      // (+2: k_pack reads the first two slots of a row whatever its capacity)
+    TRY(ensure(h, h->itv_n, (size_t)RS)); TRY(ensure(h, h->row_nrec, (size_t)RS));
     FillGroup fg(h, "fills_rows");
-    TRY(fg.zero(h->itv_n.p, (size_t)RS * 4)); TRY(fg.zero(h->row_nrec.p, (size_t)RS * 4));
-    za.active_rows = h->active_rows.as<i32>(); za.n_active_rows = h->run.n_active_rows; za.row_lo = h->row_lo.as<i64>(); za.row_hi = h->row_hi.as<i64>();
-    za.acc_off = h->acc_off.as<i64>(); za.raw = h->raw.as<i32>(); za.grp_left = h->grp_left.as<i64>(); za.grp_ixrand = h->grp_ixrand.as<i64>();
-    za.itv_off = h->itv_off.as<i64>(); za.itv_left = h->itv_left.as<i64>(); za.itv_right = h->itv_right.as<i64>();
-    za.itv_n = h->itv_n.as<i32>(); za.row_nrec = h->row_nrec.as<i32>(); za.spr = WFS_SPR;
-    if (r.tiles_done) { za.tile_done = ga.tile_done; za.n_done = ga.n_done; za.row_cnt = ga.row_cnt; za.row_tile = ga.row_tile; za.ins_bcap = ga.ins_bcap; za.ins_boff = ga.ins_boff; za.tbuf = h->tbuf.as<i32>(); }
+    TRY(fg.zero(h->itv_n.p(), RS)); TRY(fg.zero(h->row_nrec.p(), RS));
+    za.active_rows = h->active_rows.p(); za.n_active_rows = h->run.n_active_rows; za.row_lo = h->row_lo.p(); za.row_hi = h->row_hi.p();
+    za.acc_off = h->acc_off.p(); za.raw = h->raw.p(); za.grp_left = h->grp_left.p(); za.grp_ixrand = h->grp_ixrand.p();
+    za.itv_off = h->itv_off.p(); za.itv_left = h->itv_left.p(); za.itv_right = h->itv_right.p();
+    za.itv_n = h->itv_n.p(); za.row_nrec = h->row_nrec.p(); za.spr = WFS_SPR;
+    if (r.tiles_done) { za.tile_done = ga.tile_done; za.n_done = ga.n_done; za.row_cnt = ga.row_cnt; za.row_tile = ga.row_tile; za.ins_bcap = ga.ins_bcap; za.ins_boff = ga.ins_boff; za.tbuf = h->tbuf.p(); }
     za.n_front = h->run.n_front_rows; za.rows_cap = CG * d.row_slots;
-    if (d.sum_channel >= 0) { za.sum_lo = h->sum_lo.as<i64>(); za.sum_hi = h->sum_hi.as<i64>(); za.sum_off = h->sum_off.as<i64>(); za.sum_base = h->run.sum_base; }
+    if (d.sum_channel >= 0) { za.sum_lo = h->sum_lo.p(); za.sum_hi = h->sum_hi.p(); za.sum_off = h->sum_off.p(); za.sum_base = h->run.sum_base; }
     if (h->run.n_res_rows > 0) {
-        TRY(ensure(h, h->fin, (size_t)h->run.s_fin * 2 + 16));
-        TRY(ensure(h, h->res_rows, (size_t)h->run.n_res_rows * sizeof(ResRow)));
-        za.res_toff = h->res_toff.as<i64>(); za.fin_off = h->fin_off.as<i64>(); za.fin = h->fin.as<int16_t>();
-        za.n_short = h->run.n_short_rows; za.res_long = h->res_long.as<i32>(); za.res_rows = h->res_rows.as<ResRow>();
+        TRY(ensure(h, h->fin, (size_t)h->run.s_fin + 8));
+        TRY(ensure(h, h->res_rows, (size_t)h->run.n_res_rows));
+        za.res_toff = h->res_toff.p(); za.fin_off = h->fin_off.p(); za.fin = h->fin.p();
+        za.n_short = h->run.n_short_rows; za.res_long = h->res_long.p(); za.res_rows = h->res_rows.p();
     }
     if ((h->debug_bits & DBG_CURRENTS) && h->run.n_active_rows > 0) {
         const ListedRows lr = listed_rows(h);
         h->run.row_dbg_total = lr.off.back();
-        TRY(upload(h, h->row_dbg_off, lr.off.data(), lr.off.size() * 8));
-        TRY(ensure(h, h->row_dbg, (size_t)h->run.row_dbg_total * 4));
+        TRY(upload(h, h->row_dbg_off, lr.off.data(), lr.off.size()));
+        TRY(ensure(h, h->row_dbg, (size_t)h->run.row_dbg_total));
         HIPCHK(hipStreamSynchronize(h->stream));
-        za.row_dbg = h->row_dbg.as<i32>(); za.row_dbg_off = h->row_dbg_off.as<i64>();
+        za.row_dbg = h->row_dbg.p(); za.row_dbg_off = h->row_dbg_off.p();
     }
-    TRY(ensure(h, h->row_desc, (size_t)h->run.n_active_rows * sizeof(RowDesc))); za.desc = h->row_desc.as<RowDesc>();
+    TRY(ensure(h, h->row_desc, (size_t)h->run.n_active_rows)); za.desc = h->row_desc.p();
     if (h->sort_records) {      // key_origin / key_end: first sample / end of the last row of the batch (k_row_desc): origin and span of the sort keys
-        za.key_base = h->scal.as<WfsScal>();
-        TRY(fg.i64s(&za.key_base->key_origin, 1, I64_MAX)); TRY(fg.i64s(&za.key_base->key_end, 1, I64_MIN));
+        za.key_base = h->scal.p();
+        TRY(fg.fill(&za.key_base->key_origin, 1, I64_MAX)); TRY(fg.fill(&za.key_base->key_end, 1, I64_MIN));
     }
     TRY(fg.flush());
     if (h->run.n_active_rows > 0) { Timer t(h, "k_row_desc"); hipLaunchKernelGGL(k_row_desc, dim3(nblocks(h->run.n_active_rows, 256)), dim3(256), 0, h->stream, d, za); }
     r.noise_kind = d.enable_noise ? noise_kind_of(d) : NOISE_NONE;
     if (h->run.n_res_rows > 0) {        // resident rows: pulses, finished samples and intervals by one wave per row
         PulseArgs pr = pa;
-        pr.desc = h->res_desc.as<TileDesc>(); pr.currents = nullptr; pr.cur_off = nullptr;
+        pr.desc = h->res_desc.p(); pr.currents = nullptr; pr.cur_off = nullptr;
         // two launches: the rows of at most RES_SHORT_LEN samples at full occupancy, the longer ones with LDS for the longest of them
         Timer t(h, "k_row_pulse");
 #define K_ROW_PULSE_SHORT(F) k_row_pulse<NK, F, false>
@@ -2282,8 +2299,8 @@ static int run_rows(wfs_handle *h, RunState &r)
         }
     }
     {   // truth accumulators of every pulse set from the per-tile partial sums
-        TruthArgs ta{S, h->tile_count.as<i32>(), h->tile_tmin.as<i32>(), h->tile_tmax.as<i32>(), h->set_t0.as<i64>(), h->tile_truth.as<double>(),
-                     h->truth.as<double>(), h->tminmax.as<i64>()};
+        TruthArgs ta{S, h->tile_count.p(), h->tile_tmin.p(), h->tile_tmax.p(), h->set_t0.p(), h->tile_truth.p(),
+                     h->truth.p(), h->tminmax.p()};
         Timer t(h, "k_truth_reduce");
         hipLaunchKernelGGL(k_truth_reduce, dim3(nblocks(S, 4)), dim3(256), 0, h->stream, d, ta);
     }
@@ -2292,9 +2309,9 @@ static int run_rows(wfs_handle *h, RunState &r)
     // more row per window through k_zle / k_pack; the sum rows then hold whatever the buffer held)
     if (h->run.n_sum_chunks > 0 && !getenv("WFS_SUM_SKIP_KERNEL")) {      // the windows' sum rows from their bottom rows: every accumulator and tile buffer is complete here (k_tile_add included)
         if (h->run.n_sum_chunks > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "more than 2^31 chunks of sum rows in one batch");
-        SumArgs sa{h->sum_chunk_off.as<i64>(), CG, h->sum_lo.as<i64>(), h->sum_off.as<i64>(), h->sum_len.as<i32>(),
-                   h->row_lo.as<i64>(), h->row_hi.as<i64>(), h->acc_off.as<i64>(), h->raw.as<i32>(), r.tiles_done ? h->tbuf.as<i32>() : nullptr,
-                   r.tiles_done ? ga.tile_done : nullptr, ga.row_cnt, ga.row_tile, ga.ins_bcap, ga.ins_boff, ga.n_done, h->raw.as<i32>() + h->run.sum_base};
+        SumArgs sa{h->sum_chunk_off.p(), CG, h->sum_lo.p(), h->sum_off.p(), h->sum_len.p(),
+                   h->row_lo.p(), h->row_hi.p(), h->acc_off.p(), h->raw.p(), r.tiles_done ? h->tbuf.p() : nullptr,
+                   r.tiles_done ? ga.tile_done : nullptr, ga.row_cnt, ga.row_tile, ga.ins_bcap, ga.ins_boff, ga.n_done, h->raw.p() + h->run.sum_base};
         Timer t(h, "k_sum_signal");
         hipLaunchKernelGGL(k_sum_signal, dim3((unsigned)h->run.n_sum_chunks), dim3(256), 0, h->stream, d, sa);
     }
@@ -2314,34 +2331,34 @@ static int run_records(wfs_handle *h, RunState &r)
     // the packers keep their place on the main stream, in front of the last boundary, in a profiled step (kernel_times lists them), in
     // the debug modes, on a caller's stream and under WFS_PACK_SYNC=1
     const bool defer = h->own_stream && !h->profiling && h->debug_bits == 0 && !h->pack_sync;
-    TRY(scan(h, h->row_nrec.as<i32>(), RS, h->rec_off, &WfsScal::n_records));
+    TRY(scan(h, h->row_nrec.p(), RS, h->rec_off, &WfsScal::n_records));
     TRY(read_scal(h));
     h->run.n_records = h->h_scal->n_records;
     // the other arena: the previous batch's records may still be on their way to the host
     h->rec_cur ^= 1;
     if (h->rec_pending[h->rec_cur]) { HIPCHK(hipEventSynchronize(h->rec_copied[h->rec_cur])); h->rec_pending[h->rec_cur] = false; }
     TRY(ensure(h, h->records_buf(), (size_t)h->run.n_records * WFS_RECORD_BYTES));
-    za.rec_off = h->rec_off.as<i64>(); za.records = h->records_buf().as<uint8_t>(); za.rec_capacity = h->run.n_records;
+    za.rec_off = h->rec_off.p(); za.records = h->records_buf().as<uint8_t>(); za.rec_capacity = h->run.n_records;
     if (h->sort_records && h->run.n_records > 1 && h->run.n_active_rows > 0) {
         // records by (time, channel): keys per record, one radix sort of the batch, k_pack writes to the sorted slots
         const i64 NR = h->run.n_records;
         if (NR > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "more than 2^31 records in one batch (the device sort takes an int count)");
-        TRY(ensure(h, h->rec_key, (size_t)NR * 8)); TRY(ensure(h, h->rec_key2, (size_t)NR * 8));
-        TRY(ensure(h, h->rec_val, (size_t)NR * 4)); TRY(ensure(h, h->rec_val2, (size_t)NR * 4)); TRY(ensure(h, h->rec_dest, (size_t)NR * 4));
-        za.rec_key = h->rec_key.as<u64>(); za.rec_val = h->rec_val.as<u32>();
+        TRY(ensure(h, h->rec_key, (size_t)NR)); TRY(ensure(h, h->rec_key2, (size_t)NR));
+        TRY(ensure(h, h->rec_val, (size_t)NR)); TRY(ensure(h, h->rec_val2, (size_t)NR)); TRY(ensure(h, h->rec_dest, (size_t)NR));
+        za.rec_key = h->rec_key.p(); za.rec_val = h->rec_val.p();
         { Timer t(h, "k_rec_keys"); hipLaunchKernelGGL(k_rec_keys, dim3(nblocks(h->run.n_active_rows, 4)), dim3(256), 0, h->stream, d, za); }
         // rocPRIM's radix sort, over the key bits that are in use only: (samples the batch spans) << 12 | channel
         unsigned end_bit = 13;
         { const u64 span = (u64)std::max<i64>(h->h_scal->key_end - h->h_scal->key_origin, 1); while (end_bit < 64 && ((span << 12) >> end_bit) != 0) end_bit++; }
         size_t bytes = 0;
-        HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, h->rec_key.as<u64>(), h->rec_key2.as<u64>(), h->rec_val.as<u32>(), h->rec_val2.as<u32>(), (size_t)NR, 0u, end_bit, h->stream));
+        HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, h->rec_key.p(), h->rec_key2.p(), h->rec_val.p(), h->rec_val2.p(), (size_t)NR, 0u, end_bit, h->stream));
         TRY(ensure(h, h->sort_tmp, bytes));
-        { Timer t(h, "record_sort"); HIPCHK(rocprim::radix_sort_pairs(h->sort_tmp.p, bytes, h->rec_key.as<u64>(), h->rec_key2.as<u64>(), h->rec_val.as<u32>(), h->rec_val2.as<u32>(), (size_t)NR, 0u, end_bit, h->stream)); }
-        { Timer t(h, "k_invert_perm"); hipLaunchKernelGGL(k_invert_perm, dim3(nblocks(NR, 256)), dim3(256), 0, h->stream, h->rec_val2.as<u32>(), h->rec_dest.as<u32>(), NR); }
-        za.rec_dest = h->rec_dest.as<u32>();
+        { Timer t(h, "record_sort"); HIPCHK(rocprim::radix_sort_pairs(h->sort_tmp.p, bytes, h->rec_key.p(), h->rec_key2.p(), h->rec_val.p(), h->rec_val2.p(), (size_t)NR, 0u, end_bit, h->stream)); }
+        { Timer t(h, "k_invert_perm"); hipLaunchKernelGGL(k_invert_perm, dim3(nblocks(NR, 256)), dim3(256), 0, h->stream, h->rec_val2.p(), h->rec_dest.p(), NR); }
+        za.rec_dest = h->rec_dest.p();
     }
     if (h->run.n_active_rows > 0 && h->run.n_records > 0) {
-        TRY(ensure(h, h->pack_desc, (size_t)h->run.n_active_rows * sizeof(PackDesc))); za.pdesc = h->pack_desc.as<PackDesc>();
+        TRY(ensure(h, h->pack_desc, (size_t)h->run.n_active_rows)); za.pdesc = h->pack_desc.p();
         // Nothing wfs_run returns depends on the packers: they go to the pack stream, behind everything on the main stream up to here,
         // and run under the front end of the next wfs_run, which fences them in front of its first write to what they read
         // (pack_fence).  Readers of the records wait for the arena's ready event.  (The timers are idle then: profiled steps are serial.)
@@ -2353,7 +2370,7 @@ static int run_records(wfs_handle *h, RunState &r)
         }
         { Timer t(h, "k_pack_desc"); hipLaunchKernelGGL(k_pack_desc, dim3(nblocks(h->run.n_active_rows, 256)), dim3(256), 0, ps, za); }
         if (h->run.n_res_rows > 0) {
-            PackResArgs pr{h->pack_desc.as<PackDesc>() + h->run.n_front_rows, h->fin.as<int16_t>(), za.itv_left, za.itv_right, za.records, za.rec_dest, za.rec_capacity, h->run.n_res_rows, za.spr, (i32)d.dt};
+            PackResArgs pr{h->pack_desc.p() + h->run.n_front_rows, h->fin.p(), za.itv_left, za.itv_right, za.records, za.rec_dest, za.rec_capacity, h->run.n_res_rows, za.spr, (i32)d.dt};
             Timer t(h, "k_pack_res"); hipLaunchKernelGGL(k_pack_res, dim3(nblocks(h->run.n_res_rows, 4)), dim3(256), 0, ps, pr);
         }
         if (h->run.n_front_rows > 0) {
@@ -2368,7 +2385,7 @@ static int run_records(wfs_handle *h, RunState &r)
     {   // totals of wfs_get_counts: afterpulse sets carry no truth (rawdata.py:322-323)
         const i64 n_prim = h->batch.ap_sets ? h->batch.n_psets : h->batch.n_sets;
         const i64 work = std::max<i64>(RS, n_prim);
-        hipLaunchKernelGGL(k_counts, dim3((unsigned)std::min<i64>(nblocks(work, 256), 128)), dim3(256), 0, h->stream, h->itv_n.as<i32>(), RS, h->truth.as<double>(), n_prim, h->scal.as<WfsScal>());
+        hipLaunchKernelGGL(k_counts, dim3((unsigned)std::min<i64>(nblocks(work, 256), 128)), dim3(256), 0, h->stream, h->itv_n.p(), RS, h->truth.p(), n_prim, h->scal.p());
     }
     TRY(read_scal(h));
     HIPCHK(hipGetLastError());
@@ -2486,11 +2503,11 @@ int wfs_copy_groups(wfs_handle *h, int64_t *left, int64_t *right, int64_t *first
 try {
     if (!h || !run_complete(h)) return WFS_E_STATE;
     const i64 G = h->run.n_groups;
-    if (left) HIPCHK(hipMemcpy(left, h->grp_left.p, (size_t)G * 8, hipMemcpyDeviceToHost));
-    if (right) HIPCHK(hipMemcpy(right, h->grp_right.p, (size_t)G * 8, hipMemcpyDeviceToHost));
-    if (ix_rand) HIPCHK(hipMemcpy(ix_rand, h->grp_ixrand.p, (size_t)G * 8, hipMemcpyDeviceToHost));
+    if (left) TRY(copy_out(h, left, h->grp_left.p(), (size_t)G));
+    if (right) TRY(copy_out(h, right, h->grp_right.p(), (size_t)G));
+    if (ix_rand) TRY(copy_out(h, ix_rand, h->grp_ixrand.p(), (size_t)G));
     if (first_record && G > 0)      // rec_off[g * row_slots]: a strided copy of one value per window (the whole array is 6 KB per cluster)
-        HIPCHK(hipMemcpy2D(first_record, 8, h->rec_off.p, (size_t)h->dev.row_slots * 8, 8, (size_t)G, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy2D(first_record, sizeof(i64), h->rec_off.p(), (size_t)h->dev.row_slots * sizeof(i64), sizeof(i64), (size_t)G, hipMemcpyDeviceToHost));
     return WFS_OK;
 } WFS_CATCH(h)
 
@@ -2499,9 +2516,9 @@ try {
     if (!h || !run_complete(h)) return WFS_E_STATE;
     const WfsDev &d = h->dev;
     const i64 RS = (h->batch.n_clusters + 1) * d.row_slots;
-    const std::vector<i32> n = download<i32>(h, h->itv_n, (size_t)RS);
-    const std::vector<i64> off = download<i64>(h, h->itv_off, (size_t)RS + 1);
-    const std::vector<i64> L = download<i64>(h, h->itv_left, (size_t)h->run.n_itv_slots), R = download<i64>(h, h->itv_right, (size_t)h->run.n_itv_slots);
+    const std::vector<i32> n = download(h, h->itv_n, (size_t)RS);
+    const std::vector<i64> off = download(h, h->itv_off, (size_t)RS + 1);
+    const std::vector<i64> L = download(h, h->itv_left, (size_t)h->run.n_itv_slots), R = download(h, h->itv_right, (size_t)h->run.n_itv_slots);
     i64 k = 0, doff = 0;
     for (i64 idx = 0; idx < RS; idx++) {
         const RowSlot s = row_slot(d, idx);
@@ -2540,7 +2557,7 @@ try {
     const i64 A = h->run.n_active_tiles;
     if (cap < A) return h->fail(WFS_E_CAPACITY, "pulse buffer too small");
     const ListedTiles lt = listed_tiles(h);
-    const std::vector<i32> cnt = download<i32>(h, h->tile_count, (size_t)h->batch.n_tiles);
+    const std::vector<i32> cnt = download(h, h->tile_count, (size_t)h->batch.n_tiles);
     for (i64 k = 0; k < A; k++) {
         const i64 tile = lt.tile[k], s = tile / d.n_tpc;
         set[k] = (i32)s; channel[k] = (i32)(tile - s * d.n_tpc);
@@ -2555,7 +2572,7 @@ try {
     if (!h || !run_finished(h)) return WFS_E_STATE;
     if (!(h->debug_bits & DBG_CURRENTS)) return h->fail(WFS_E_STATE, "wfs_set_debug(h, 1) before wfs_run");
     if (cap < h->run.cur_total) return h->fail(WFS_E_CAPACITY, "current buffer too small");
-    if (h->run.cur_total) HIPCHK(hipMemcpy(cur, h->currents.p, (size_t)h->run.cur_total * 8, hipMemcpyDeviceToHost));
+    if (h->run.cur_total) TRY(copy_out(h, cur, h->currents.p(), (size_t)h->run.cur_total));
     return WFS_OK;
 } WFS_CATCH(h)
 
@@ -2567,7 +2584,7 @@ try {
     const i64 A = h->run.n_active_rows;
     if (cap < A) return h->fail(WFS_E_CAPACITY, "row buffer too small");
     const ListedRows lr = listed_rows(h);
-    const std::vector<i64> gl = download<i64>(h, h->grp_left, (size_t)h->run.n_groups);
+    const std::vector<i64> gl = download(h, h->grp_left, (size_t)h->run.n_groups);
     for (i64 k = 0; k < A; k++) {
         const RowSlot &s = lr.slot[k];
         group[k] = (i32)s.g; channel[k] = s.channel;
@@ -2583,7 +2600,7 @@ int wfs_copy_row_data(wfs_handle *h, int32_t *data, int64_t cap)
 try {
     if (!h || !run_complete(h)) return WFS_E_STATE;
     if (cap < h->run.row_dbg_total) return h->fail(WFS_E_CAPACITY, "row data buffer too small");
-    if (h->run.row_dbg_total) HIPCHK(hipMemcpy(data, h->row_dbg.p, (size_t)h->run.row_dbg_total * 4, hipMemcpyDeviceToHost));
+    if (h->run.row_dbg_total) TRY(copy_out(h, data, h->row_dbg.p(), (size_t)h->run.row_dbg_total));
     return WFS_OK;
 } WFS_CATCH(h)
 
@@ -2595,16 +2612,11 @@ try {
     const WfsDev &d = h->dev;
     const i64 n_prim = n_primary_photons(h), P = n_prim + h->run.n_ap_photons, T = h->batch.n_tiles;
     if (cap < P) return h->fail(WFS_E_CAPACITY, "photon buffer too small");
-    std::vector<i64> off((size_t)T + 1), t0((size_t)h->batch.n_sets);
-    std::vector<PhotonRec> recs((size_t)P);
-    HIPCHK(hipMemcpy(off.data(), h->tile_off.p, off.size() * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(t0.data(), h->set_t0.p, t0.size() * 8, hipMemcpyDeviceToHost));
-    if (P) HIPCHK(hipMemcpy(recs.data(), h->ph.p, recs.size() * 8, hipMemcpyDeviceToHost));
-    std::vector<double> gains((size_t)d.n_tpc), spe((size_t)SPE_ROW_LEN * d.n_spe), pg;
-    HIPCHK(hipMemcpy(gains.data(), h->t_gains.p, gains.size() * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(spe.data(), h->t_spe.p, spe.size() * 8, hipMemcpyDeviceToHost));
+    const std::vector<i64> off = download(h, h->tile_off, (size_t)T + 1), t0 = download(h, h->set_t0, (size_t)h->batch.n_sets);
+    const std::vector<PhotonRec> recs = download(h, h->ph, (size_t)P);
+    const std::vector<double> gains = download(h, h->t_gains, (size_t)d.n_tpc), spe = download(h, h->t_spe, (size_t)SPE_ROW_LEN * d.n_spe);
     const i64 gain_first = h->batch.kind == BatchKind::Photons ? 0 : n_prim;        // ph_gain covers the explicit-gain photons only
-    if (P - gain_first > 0) { pg.resize((size_t)(P - gain_first)); HIPCHK(hipMemcpy(pg.data(), h->ph_gain.p, pg.size() * 8, hipMemcpyDeviceToHost)); }
+    const std::vector<double> pg = download(h, h->ph_gain, (size_t)std::max<i64>(P - gain_first, 0));
     if (off[(size_t)T] != P) { char msg[160]; snprintf(msg, sizeof msg, "wfs_copy_photons: tile offsets end at %lld, %lld photons (T %lld, sets %lld)", (long long)off[(size_t)T], (long long)P, (long long)T, (long long)h->batch.n_sets); return h->fail(WFS_E_STATE, msg); }
     for (i64 s = 0; s <= h->batch.n_sets; s++) set_off[s] = off[(size_t)s * d.n_tpc];
     for (i64 tile = 0; tile < T; tile++) {
@@ -2628,12 +2640,12 @@ static int gen_order_tables(wfs_handle *h)
 {
     if (h->run.gen_order_ready) return WFS_OK;
     const i64 N = h->batch.n_ins; const int nch = h->dev.n_tpc;
-    const std::vector<i64> emo = download<i64>(h, h->em_off, (size_t)N + 1), epo = download<i64>(h, h->em_ph_off, (size_t)h->batch.n_emitters + 1);
+    const std::vector<i64> emo = download(h, h->em_off, (size_t)N + 1), epo = download(h, h->em_ph_off, (size_t)h->batch.n_emitters + 1);
     h->run.go_fused.assign((size_t)N, 0); h->run.go_tile_count.clear();
     const bool any_fused = h->run.fuse_on && n_tilegen_tiles(h) > 0;
     if (any_fused) {
-        h->run.go_fused = download<i32>(h, h->ins_fused, (size_t)N);
-        h->run.go_tile_count = download<i32>(h, h->tile_count, (size_t)N * nch);      // (one pulse set per instruction: tile = instruction * n_tpc + channel)
+        h->run.go_fused = download(h, h->ins_fused, (size_t)N);
+        h->run.go_tile_count = download(h, h->tile_count, (size_t)N * nch);      // (one pulse set per instruction: tile = instruction * n_tpc + channel)
     }
     h->run.go_off.assign((size_t)N + 1, 0); h->run.go_block0.assign((size_t)N, 0);
     for (i64 i = 0; i < N; i++) {
@@ -2679,19 +2691,19 @@ try {
     std::vector<i64> got;
     if (!blk_idx.empty()) {
         const i64 m = (i64)blk_idx.size();
-        TRY(upload(h, h->gather_idx, blk_idx.data(), (size_t)m * 8)); TRY(ensure(h, h->gather_out, (size_t)m * 8));
-        hipLaunchKernelGGL(k_photon_times, dim3(nblocks(m, 256)), dim3(256), 0, h->stream, h->dev, h->gen_args, m, h->gather_idx.as<i64>(), h->gather_out.as<i64>());
+        TRY(upload(h, h->gather_idx, blk_idx.data(), (size_t)m)); TRY(ensure(h, h->gather_out, (size_t)m));
+        hipLaunchKernelGGL(k_photon_times, dim3(nblocks(m, 256)), dim3(256), 0, h->stream, h->dev, h->gen_args, m, h->gather_idx.p(), h->gather_out.p());
         got.resize((size_t)m);
-        HIPCHK(hipMemcpyAsync(got.data(), h->gather_out.p, (size_t)m * 8, hipMemcpyDeviceToHost, h->stream));
+        TRY(copy_async(h, got.data(), h->gather_out.p(), (size_t)m, hipMemcpyDeviceToHost));
         HIPCHK(hipStreamSynchronize(h->stream));
         for (i64 k = 0; k < m; k++) t_out[blk_pos[(size_t)k]] = got[(size_t)k];
     }
     if (!treq.empty()) {
         const i64 m = (i64)treq.size();
-        TRY(upload(h, h->gather_idx, treq.data(), (size_t)m * sizeof(TileTimeReq))); TRY(ensure(h, h->gather_out, (size_t)m * 8));
-        hipLaunchKernelGGL(k_tile_photon_times, dim3(nblocks(m, 256)), dim3(256), 0, h->stream, h->dev, h->fuse_args, m, h->gather_idx.as<TileTimeReq>(), h->gather_out.as<i64>());
+        TRY(upload(h, h->gather_req, treq.data(), (size_t)m)); TRY(ensure(h, h->gather_out, (size_t)m));
+        hipLaunchKernelGGL(k_tile_photon_times, dim3(nblocks(m, 256)), dim3(256), 0, h->stream, h->dev, h->fuse_args, m, h->gather_req.p(), h->gather_out.p());
         got.resize((size_t)m);
-        HIPCHK(hipMemcpyAsync(got.data(), h->gather_out.p, (size_t)m * 8, hipMemcpyDeviceToHost, h->stream));
+        TRY(copy_async(h, got.data(), h->gather_out.p(), (size_t)m, hipMemcpyDeviceToHost));
         HIPCHK(hipStreamSynchronize(h->stream));
         for (i64 k = 0; k < m; k++) t_out[tile_pos[(size_t)k]] = got[(size_t)k];
     }
@@ -2703,8 +2715,8 @@ try {
     if (!h || !run_finished(h)) return WFS_E_STATE;
     const i64 S = h->batch.n_sets;
     if (cap < S) return h->fail(WFS_E_CAPACITY, "truth buffer too small");
-    const std::vector<double> tr = download<double>(h, h->truth, (size_t)S * 16);
-    const std::vector<i64> mm = download<i64>(h, h->tminmax, (size_t)S * 2), t0 = download<i64>(h, h->set_t0, (size_t)S);
+    const std::vector<double> tr = download(h, h->truth, (size_t)S * TRUTH_PER_SET);
+    const std::vector<i64> mm = download(h, h->tminmax, (size_t)S * MINMAX), t0 = download(h, h->set_t0, (size_t)S);
     for (i64 s = 0; s < S; s++) {
         for (int f = 0; f < 12; f++) acc12[s * 12 + f] = tr[s * 16 + f];
         stat5(tstat5 + s * 5, tr[s * 16 + 12], tr[s * 16 + 13], tr[s * 16 + 14], (double)t0[s], mm[2 * s], mm[2 * s + 1]);
@@ -2717,8 +2729,8 @@ try {
     if (!h || !run_finished(h)) return WFS_E_STATE;
     const i64 S = h->batch.n_sets, nch = h->cfg.n_tpc, T = S * nch;
     if (cap < S) return h->fail(WFS_E_CAPACITY, "per-PMT truth buffer too small");
-    const std::vector<double> tt = download<double>(h, h->tile_truth, (size_t)T * 8), gains = download<double>(h, h->t_gains, (size_t)nch);
-    const std::vector<i32> cnt = download<i32>(h, h->tile_count, (size_t)T);
+    const std::vector<double> tt = download(h, h->tile_truth, (size_t)T * TRUTH_PER_TILE), gains = download(h, h->t_gains, (size_t)nch);
+    const std::vector<i32> cnt = download(h, h->tile_count, (size_t)T);
     for (i64 t = 0; t < T; t++) {
         double *o = acc6 + t * 6;
         if (cnt[t] <= 0) { for (int q = 0; q < 6; q++) o[q] = 0.0; continue; }     // tiles without photons were never written
@@ -2736,8 +2748,8 @@ try {
     const i64 PS = h->batch.n_psets;
     if (cap < PS) return h->fail(WFS_E_CAPACITY, "electron stats buffer too small");
     if (N == 0) return WFS_OK;
-    const std::vector<double> st = download<double>(h, h->el_stat, (size_t)N * 4);
-    const std::vector<i64> mm = download<i64>(h, h->el_minmax, (size_t)N * 2), t0 = download<i64>(h, h->ins_time, (size_t)N);
+    const std::vector<double> st = download(h, h->el_stat, (size_t)N * STAT_PER_INS);
+    const std::vector<i64> mm = download(h, h->el_minmax, (size_t)N * MINMAX), t0 = download(h, h->ins_time, (size_t)N);
     for (i64 q = 0; q < PS; q++) {
         // moments of the electrons of all instructions of the run set (rawdata.py:334-341), about the first instruction's time
         const i64 ref = h->batch.h_rs_off[q + 1] > h->batch.h_rs_off[q] ? t0[h->batch.h_rs_list[h->batch.h_rs_off[q]]] : 0;      // (an unused set number: no instructions, zero electrons)
@@ -2784,10 +2796,9 @@ try {
     const WfsDev &d = h->dev;
     if (d.sum_channel < 0 || h->run.n_groups == 0) { if (cap_rows > 0 && data_off) data_off[0] = 0; return WFS_OK; }
     const i64 G = h->run.n_groups;
-    std::vector<i64> lo((size_t)G), hi((size_t)G), off((size_t)G + 1); std::vector<i32> acc((size_t)h->run.s_sum);
-    HIPCHK(hipMemcpy(lo.data(), h->sum_lo.p, lo.size() * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(hi.data(), h->sum_hi.p, hi.size() * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(off.data(), h->sum_off.p, off.size() * 8, hipMemcpyDeviceToHost));
-    if (h->run.s_sum) HIPCHK(hipMemcpy(acc.data(), h->raw.as<i32>() + h->run.sum_base, acc.size() * 4, hipMemcpyDeviceToHost));
+    const std::vector<i64> lo = download(h, h->sum_lo, (size_t)G), hi = download(h, h->sum_hi, (size_t)G), off = download(h, h->sum_off, (size_t)G + 1);
+    std::vector<i32> acc((size_t)h->run.s_sum);
+    if (h->run.s_sum) TRY(copy_out(h, acc.data(), h->raw.p() + h->run.sum_base, acc.size()));
     i64 k = 0, doff = 0;
     for (i64 g = 0; g < G; g++) {
         if (lo[g] == I64_MAX) continue;
@@ -2832,7 +2843,7 @@ try {
     std::vector<NoiseCell> cells; int shift = 31;
     append_alias_rows(cum, n_channels, n_values, cells, shift);
     const i32 K = (i32)(cells.size() / (size_t)n_channels);
-    TRY(upload(h, h->nm_cells, cells.data(), cells.size() * sizeof(NoiseCell)));
+    TRY(upload(h, h->nm_cells, cells.data(), cells.size()));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->noise_moves(h->noise_state().model_set(n_channels, K, shift, vmin, n_values, std::move(cells)));
     refresh_dev(h);             // (HE rows may appear or go with the model's channel count: run again before copying rows)
@@ -2865,7 +2876,7 @@ try {
     if (n_taps == 0) {
         HIPCHK(hipStreamSynchronize(h->stream));
         // (the cells of the common streams leave the device with them)
-        if (m.colour.groups > 0) { TRY(upload(h, h->nm_cells, m.cells.data(), m.cells.size() * sizeof(NoiseCell))); HIPCHK(hipStreamSynchronize(h->stream)); }
+        if (m.colour.groups > 0) { TRY(upload(h, h->nm_cells, m.cells.data(), m.cells.size())); HIPCHK(hipStreamSynchronize(h->stream)); }
         h->noise_moves(h->noise_state().colour_cleared());
         refresh_dev(h);
         return WFS_OK;
@@ -2875,8 +2886,8 @@ try {
     std::vector<NoiseCell> cells(m.cells); int shift = 31;
     append_alias_rows(cum, n_groups, m.values, cells, shift);
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (n_groups > 0 || m.colour.groups > 0) TRY(upload(h, h->nm_cells, cells.data(), cells.size() * sizeof(NoiseCell)));
-    TRY(upload(h, h->nc_buf, buf.data(), buf.size() * sizeof(i32)));
+    if (n_groups > 0 || m.colour.groups > 0) TRY(upload(h, h->nm_cells, cells.data(), cells.size()));
+    TRY(upload(h, h->nc_buf, buf.data(), buf.size()));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->noise_moves(h->noise_state().colour_set(n_taps, n_groups, std::move(tapsum)));
     refresh_dev(h);
@@ -2900,7 +2911,7 @@ try {
     std::vector<i32> buf; std::string err;
     if (!noise_slow_pack(h->noise, n_levels, shifts, slow_q, buf, err)) return h->fail(WFS_E_INVALID, err);
     HIPCHK(hipStreamSynchronize(h->stream));
-    TRY(upload(h, h->ns_buf, buf.data(), buf.size() * sizeof(i32)));
+    TRY(upload(h, h->ns_buf, buf.data(), buf.size()));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->noise_moves(h->noise_state().slow_set(n_levels));
     refresh_dev(h);
@@ -2937,7 +2948,7 @@ try {
     if (capacity_cells < m.k) return h->fail(WFS_E_CAPACITY, "wfs_copy_noise_model: cell buffers too small");
     HIPCHK(hipSetDevice(h->device));
     std::vector<NoiseCell> cell((size_t)m.k);            // what the device samples from, not the host copy
-    HIPCHK(hipMemcpy(cell.data(), h->nm_cells.as<NoiseCell>() + (size_t)channel * m.k, cell.size() * sizeof(NoiseCell), hipMemcpyDeviceToHost));
+    TRY(copy_out(h, cell.data(), h->nm_cells.p() + (size_t)channel * m.k, cell.size()));
     for (i32 k = 0; k < m.k; k++) { thr[k] = cell[(size_t)k].x; alias[k] = cell[(size_t)k].y; }
     *n_cells = m.k; *shift = m.shift; *vmin = m.vmin;
     return WFS_OK;
@@ -2952,7 +2963,7 @@ try {
     if (!from_generator(h) || !h->run.fuse_on || TP == 0) { memset(kind, 0, (size_t)TP); return WFS_OK; }
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(kind, h->tile_kind.p, (size_t)TP, hipMemcpyDeviceToHost));
+    TRY(copy_out(h, kind, h->tile_kind.p(), (size_t)TP));
     return WFS_OK;
 } WFS_CATCH(h)
 
