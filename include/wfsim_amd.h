@@ -430,6 +430,24 @@ int wfs_set_sum_signal(wfs_handle *h, int32_t on);
  * data[data_off[k] .. data_off[k + 1]); data_off[rows] is written when capacity_rows exceeds the number of rows. */
 int wfs_copy_sum_signal(wfs_handle *h, int32_t *group, int64_t *left, int64_t *right, int64_t *data_off, int64_t *data,
                         int64_t capacity_rows, int64_t capacity_samples);
+/* Full readout (config 'full_readout'): every digitise window is read out on every channel, not only on those that hold a
+ * pulse.  A digitise window is still one with at least one pulse, and its left / right, its noise start index, the truth and the order
+ * of the Pulse calls do not change.  With the switch on every TPC row slot of such a window has a row, and every HE slot when HE rows
+ * exist, channels with gain 0 or turned off included (optical / nVeto input: every channel of the array).  Every one of these rows
+ * has the range of the window's union mask, min(left) - trigger_window .. max(right) + trigger_window over ALL pulses of the window:
+ * the range the row would have if a pulse reached both extremes on that channel.  Its value is the sum of the channel's pulses, zero
+ * where it has none (an HE slot: its top channel's sum times int(he_factor)), finished by the rule of every row: the configured noise
+ * (a table: sample i of the row reads index ix_rand + i; the model: its value at the absolute sample), baseline, clamp; channels at
+ * or beyond the noise source's channel count get no noise.  Zero-length encoding and record fragments are those of every row, with
+ * thr_zle[channel]; there is no separate "no suppression" switch: a threshold no sample can reach (zle_threshold below -2^15) stores
+ * whole rows.  The sum row (wfs_set_sum_signal) keeps its range and value.  Records of a window: ascending channel, TPC, HE, sum (or
+ * by time and channel, wfs_set_record_order).  wfs_counts.n_rows and n_intervals count what exists; n_raw_samples does not count rows
+ * without a pulse, which never exist unfinished.  wfs_copy_rows / wfs_copy_row_data (debug) list the rows WITH pulses, at their full
+ * range; wfs_copy_intervals and the records are the contract for the others.  Allowed between runs; waits for pending packers when
+ * the mode changes; takes effect from the next wfs_run.  A batch whose rows without a pulse need more finished samples than one batch
+ * may hold (2^36, WFS_FULL_READOUT_MAX_SAMPLES) ends in WFS_E_CAPACITY, one the device has no memory for in WFS_E_NOMEM, both with a
+ * message that names full readout.  Default: off -- no kernel, no buffer, no record differs. */
+int wfs_set_full_readout(wfs_handle *h, int32_t on);
 /* Which kernel made every primary (pulse set, channel) tile of the last wfs_run, indexed set * n_tpc + channel: 0 no photons or not
  * tile-generated, 1 photons and pulse in one workgroup (up to 2048 photons), 2 generation only + the pulse kernels, 3 k_s2_bright.
  * capacity: entries the buffer holds (>= n_run_sets * n_tpc). */

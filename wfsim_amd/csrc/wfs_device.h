@@ -299,7 +299,9 @@ struct WfsScal {
     i64 max_bright_bins;    // most start bins the H table of a tile above TILE_MAX_PHOTONS could need, whichever kernel takes it.  k_tile_counts -> host (WFS_BRIGHT_STATS)
     i64 n_sum_samples;      // samples of the bottom-array sum rows (wfs_set_sum_signal).  scan of sum_len -> host
     i64 n_sum_chunks;       // workgroups of k_sum_signal.  scan of sum_nchunk -> host
-    i64 reserved_[22];
+    i64 n_empty_rows;       // rows without a pulse of a fully read-out window (wfs_set_full_readout).  k_row_len -> host
+    i64 n_empty_samples;    // finished int16 samples reserved for them.  scan of fr_len -> host
+    i64 reserved_[20];
 };
 static_assert(sizeof(WfsScal) == 512, "WfsScal: 64 slots of 8 bytes");
 #define WFS_SCAL_SLOT(m, slot) static_assert(offsetof(WfsScal, m) == 8 * (slot), "WfsScal::" #m " moved: the layout is frozen")
@@ -316,6 +318,7 @@ struct WfsDev {
     i32 n_spe, n_lum, noise_len, noise_channels, n_ap, he_rows /* HE rows materialised */, row_slots /* per group */;
     i32 noise_stride;                          // samples between the noise rows of two channels: noise_len + NOISE_PAD, the pad repeats the row's start
     i32 sum_channel;                           // channel of the bottom-array sum row, the last of a window's row_slots (wfs_set_sum_signal); -1: no such row
+    i32 full_readout;                          // every TPC and HE row slot of a digitise window has a row of the window's range (wfs_set_full_readout)
     double c2a, tts_mean, tts_sigma, p_dpe, s1_decay_time, s1_decay_spread, sf_gas, t1_gas, t3_gas, s2_time_spread;
     double trap_time, gain_spread, pmt_ap_modifier, pmt_ap_t_modifier, rext;
     u32 k0, k1;

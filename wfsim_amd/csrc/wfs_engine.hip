@@ -98,6 +98,8 @@ struct wfs_handle {
     i32 bright_lds = 0, bright_max_bins = 0;      // LDS a bright tile may take for H table + ballots (device grant, BRIGHT_LDS_MAX); start bins (WFS_BRIGHT_MAX_BINS)
     bool bright_on = true, sum_on = false, sort_records = false;      // wfs_set_bright_tiles, wfs_set_sum_signal (one more row slot per window), wfs_set_record_order
     int carry_has = 0; i64 carry_runmax = 0, n_noise_override = 0;    // wfs_set_window_carry; wfs_set_noise_offsets
+    bool full_on = false;            // wfs_set_full_readout: every row slot of a digitise window has a row of the window's range
+    i64 full_max_samples = (i64)1 << 36;      // most finished samples of rows without a pulse in one batch (128 GiB of them); WFS_FULL_READOUT_MAX_SAMPLES overrides
 
     // tables, maps and noise
     bool tables_set = false;
@@ -178,6 +180,8 @@ struct wfs_handle {
     DevArr<double> row_pmax; DevArr<i32> ins_fused, ins_nsurv, ins_bcap, ins_bcap_all, et32, tbuf, row_cnt, row_tile, tile_done; DevArr<i64> ins_boff; DevArr<FTile> ftiles; DevArr<int8_t> tile_kind;
     // the bottom-array sum row (k_sum_signal): range, length, chunks, offsets per window; its samples sit behind the accumulators in raw, from run.sum_base
     DevArr<i64> sum_lo, sum_hi, sum_off, sum_chunk_off; DevArr<i32> sum_len, sum_nchunk;
+    // full readout (k_row_empty): finished samples reserved per row slot for a row without a pulse, their offsets, the list of those rows
+    DevArr<i32> fr_len, empty_rows; DevArr<i64> fr_off;
 
     // what is not a device buffer; the buffers, and the members that hold some, free themselves after this body
     ~wfs_handle()
@@ -249,6 +253,15 @@ template <class B> int ensure(wfs_handle *h, B &b, size_t n)
     return WFS_OK;
 }
 
+// The buffers of a run that full readout multiplies -- every row slot of every window has a row: interval slots, the wider accumulators,
+// finished samples, records.  One that cannot be had ends the run in WFS_E_NOMEM with a message that names the mode.
+template <class B> int ensure_rows(wfs_handle *h, B &b, size_t n, const char *what)
+{
+    const int rc = ensure(h, b, n);
+    if (rc == WFS_OK || !h->dev.full_readout) return rc;
+    return h->fail(WFS_E_NOMEM, std::string("full readout: no device memory for ") + what + " (" + h->err + "): every row slot of every window has a row, load fewer windows per batch");
+}
+
 // Copies between typed pointers are sized by the element: the bytes of n elements.  The two sides name one type, or two integer types
 // of one size and signedness (the ABI's int64_t is long, i64 is long long).
 template <class D, class S> constexpr size_t copy_bytes(size_t n)
@@ -295,6 +308,11 @@ ListedTiles listed_tiles(wfs_handle *h)
     }
     return r;
 }
+// full readout: the rows without a pulse of the last run (behind the resident rows of the row list) and their finished samples (behind
+// s_fin).  They live in the scalar block alone: k_row_len and the scan of fr_len write them before the geometry's read-back, nothing
+// clears them before the next run or load does, and a run with the switch off leaves both 0
+i64 n_empty_rows(const wfs_handle *h) { return h->h_scal->n_empty_rows; }
+i64 s_empty(const wfs_handle *h) { return h->h_scal->n_empty_samples; }
 // The rows with data in row-list order: slot, first and last pulse sample (absolute) of each, and the offsets of their debug copies
 // (the total behind the last): row_dbg_off of a run with DBG_CURRENTS and data_off of wfs_copy_rows.
 struct ListedRows { std::vector<RowSlot> slot; std::vector<i64> lo, hi, off; };
@@ -302,7 +320,7 @@ ListedRows listed_rows(wfs_handle *h)
 {
     const WfsDev &d = h->dev;
     const size_t CG = (size_t)h->batch.n_clusters + 1;
-    const std::vector<i32> ar = download(h, h->active_rows, (size_t)h->run.n_active_rows);
+    const std::vector<i32> ar = download(h, h->active_rows, (size_t)(h->run.n_active_rows - n_empty_rows(h)));      // (full readout: the rows with pulses)
     const std::vector<i64> lo = download(h, h->row_lo, CG * d.n_tpc), hi = download(h, h->row_hi, CG * d.n_tpc);
     std::vector<i64> slo, shi;
     if (d.sum_channel >= 0) { slo = download(h, h->sum_lo, CG); shi = download(h, h->sum_hi, CG); }
@@ -665,6 +683,7 @@ void refresh_dev(wfs_handle *h)
     // the bottom-array sum row: one more slot per window, behind the TPC and HE slots (XENONnT only, rawdata.py:241)
     d.sum_channel = (h->sum_on && c.detector_nt) ? c.sum_channel : -1;
     if (d.sum_channel >= 0) d.row_slots += 1;
+    d.full_readout = h->full_on ? 1 : 0;        // (no slot more or less: the layout the copy-outs decode with does not move)
     if (layout0[0] != d.row_slots || layout0[1] != d.he_rows || layout0[2] != d.sum_channel || layout0[3] != d.noise_channels) h->state().view_changed();
 }
 
@@ -772,6 +791,7 @@ try {
     for (int kind = 0; kind < NOISE_KINDS; kind++)           // every kind that with_noise_kind can launch
         with_noise_kind(kind, [](auto nk) { constexpr int NK = decltype(nk)::value; WFS_BIG_LDS_F(K_ROW_PULSE_SEG, LDS_CAP_ROW); });
     if (const char *e = getenv("WFS_ROW_RESIDENT")) h->res_env = atoi(e);          // 0 / 1 / 2 as the config switch (A/B runs)
+    if (const char *e = getenv("WFS_FULL_READOUT_MAX_SAMPLES")) h->full_max_samples = std::max<i64>(0, atoll(e));      // capacity knob of full readout (tests)
     if (const char *e = getenv("WFS_RES_MAX_LEN")) h->res_max_len = std::max(256, std::min(atoi(e), RES_MAX_LEN)) / 256 * 256;      // tuning knob (results do not depend on it)
     WFS_BIG_LDS_F(K_S2_TILE, LDS_CAP_TILE); WFS_BIG_LDS_F(K_S2_TILE_AP, LDS_CAP_TILE);
     WFS_BIG_LDS_F(K_PULSE_SPARSE, LDS_CAP_SPARSE);
@@ -2036,6 +2056,11 @@ static int run_geometry(wfs_handle *h, RunState &r)
         TRY(fg.zero(h->sum_len.p(), CG)); TRY(fg.zero(h->sum_nchunk.p(), CG));
         ga.sum_lo = h->sum_lo.p(); ga.sum_hi = h->sum_hi.p(); ga.sum_len = h->sum_len.p(); ga.sum_nchunk = h->sum_nchunk.p();
     }
+    if (d.full_readout) {
+        TRY(ensure(h, h->fr_len, (size_t)CG * d.row_slots)); TRY(ensure(h, h->empty_rows, (size_t)CG * d.row_slots));
+        TRY(fg.zero(h->fr_len.p(), CG * d.row_slots));
+        ga.fr_len = h->fr_len.p(); ga.empty_rows = h->empty_rows.p();
+    }
     const bool tiles_done = r.tiles_done = tiles_made(h);
     // resident rows (k_row_pulse): the usual digitiser geometry, a hold-off of at least a chunk and a noise table the fast row loads
     // can walk (as the fast path of k_zle), no HE rows, no debug copies of currents or rows
@@ -2070,6 +2095,7 @@ static int run_geometry(wfs_handle *h, RunState &r)
     { Timer t(h, "k_groups"); hipLaunchKernelGGL(k_groups, dim3(1), dim3(GROUPS_TPB), 0, h->stream, d, ga); }
     { Timer t(h, "k_tile_rows"); hipLaunchKernelGGL(k_tile_rows, dim3(nblocks(T, 256)), dim3(256), 0, h->stream, d, ga); }
     { Timer t(h, "k_group_final"); hipLaunchKernelGGL(k_group_final, dim3(nblocks(CG, 256)), dim3(256), 0, h->stream, d, ga); }
+    if (d.full_readout) { Timer t(h, "k_rows_widen"); hipLaunchKernelGGL(k_rows_widen, dim3(nblocks(CG * d.n_tpc, 256)), dim3(256), 0, h->stream, d, ga); }
     { Timer t(h, "k_row_len"); hipLaunchKernelGGL(k_row_len, dim3(nblocks(CG * d.row_slots, 1024)), dim3(1024), 0, h->stream, d, ga); }
     TRY(scan(h, h->acc_len.p(), CG * d.n_tpc, h->acc_off, &WfsScal::n_acc_samples));
     TRY(scan(h, h->itv_cap.p(), CG * d.row_slots, h->itv_off, &WfsScal::n_itv_slots));
@@ -2077,6 +2103,7 @@ static int run_geometry(wfs_handle *h, RunState &r)
         TRY(scan(h, h->sum_len.p(), CG, h->sum_off, &WfsScal::n_sum_samples));
         TRY(scan(h, h->sum_nchunk.p(), CG, h->sum_chunk_off, &WfsScal::n_sum_chunks));
     }
+    if (d.full_readout) TRY(scan(h, h->fr_len.p(), CG * d.row_slots, h->fr_off, &WfsScal::n_empty_samples));
     if (h->run.res_on) {
         TRY(scan(h, h->fin_len.p(), CG * d.n_tpc, h->fin_off, &WfsScal::n_fin_samples)); TRY(scan(h, h->res_cnt.p(), CG * d.n_tpc, h->res_toff, &WfsScal::n_res_tiles));
         // rows are known: tiles onto their row's list or the work list of their class.  res_desc holds a descriptor slot for EVERY
@@ -2097,7 +2124,11 @@ static int run_geometry(wfs_handle *h, RunState &r)
     h->run.n_front_rows = sc.n_front_rows;
     h->run.n_short_rows = h->run.res_on ? sc.n_short_rows : 0;
     h->run.n_res_rows = h->run.res_on ? sc.n_short_rows + sc.n_long_rows : 0;
-    h->run.n_active_rows = h->run.n_front_rows + h->run.n_res_rows;
+    h->run.n_active_rows = h->run.n_front_rows + h->run.n_res_rows + n_empty_rows(h);
+    // full readout sizes its buffers from groups x row slots x window length: a batch beyond the cap ends here, before any of them is asked for
+    if (s_empty(h) > h->full_max_samples)
+        return h->fail(WFS_E_CAPACITY, "full readout: " + std::to_string(n_empty_rows(h)) + " rows without a pulse need " + std::to_string(s_empty(h)) + " finished samples, more than the "
+                       + std::to_string(h->full_max_samples) + " of one batch (WFS_FULL_READOUT_MAX_SAMPLES): load fewer windows per batch");
     h->run.max_res_len = sc.max_res_len;
     h->run.s_fin = h->run.res_on ? sc.n_fin_samples : 0;
     h->run.n_res_tiles = h->run.res_on ? sc.n_res_tiles : 0;
@@ -2132,7 +2163,7 @@ static int run_pulses(wfs_handle *h, RunState &r)
     const i64 T = h->batch.n_tiles, S = h->batch.n_sets;
     TRY(pack_fence(h));             // the accumulators are the first such write of a run without tile buffers (with them: gen_tile_photons)
     // (+16 samples, 64 bytes: a lane of k_zle reads 4 samples from its first valid one; the sum rows behind the accumulators are written whole by k_sum_signal)
-    TRY(ensure(h, h->raw, (size_t)(h->run.s_sum > 0 ? h->run.sum_base + h->run.s_sum : h->run.s_raw) + 16));
+    TRY(ensure_rows(h, h->raw, (size_t)(h->run.s_sum > 0 ? h->run.sum_base + h->run.s_sum : h->run.s_raw) + 16, "the row accumulators"));
     TRY(ensure(h, h->truth, (size_t)S * TRUTH_PER_SET));
     {
         FillGroup fg(h, "fills_pulses");
@@ -2226,7 +2257,7 @@ static int run_pulses(wfs_handle *h, RunState &r)
         }
     }
 
-    if (r.tiles_done && h->h_scal->n_shared_rows > 0) {   // tiles of k_s2_tile that share their row with other pulses: added into the row's accumulators
+    if (r.tiles_done && (h->h_scal->n_shared_rows > 0 || d.full_readout)) {      // (full readout: no row is its tile, every one of them is added)   // tiles of k_s2_tile that share their row with other pulses: added into the row's accumulators
         TileAddArgs ta{h->set_cluster.p(), h->cl_group.p(), h->row_lo.p(), h->acc_off.p(), h->row_cnt.p(), h->raw.p()};
         Timer t(h, "k_tile_add");
         if (h->run.n_fused_tiles > 0) hipLaunchKernelGGL(k_tile_add, dim3((unsigned)h->run.n_fused_tiles), dim3(256), 0, h->stream, d, h->fuse_args, ta);
@@ -2245,7 +2276,7 @@ static int run_rows(wfs_handle *h, RunState &r)
     const GeomArgs &ga = r.ga; const PulseArgs &pa = r.pa; ZleArgs &za = r.za;
     const i64 S = h->batch.n_sets, CG = r.CG;
     const i64 RS = r.RS = CG * d.row_slots;
-    TRY(ensure(h, h->itv_left, (size_t)h->run.n_itv_slots + 2)); TRY(ensure(h, h->itv_right, (size_t)h->run.n_itv_slots + 2));      // (+2: k_pack reads the first two slots of a row whatever its capacity)
+    TRY(ensure_rows(h, h->itv_left, (size_t)h->run.n_itv_slots + 2, "the interval slots")); TRY(ensure_rows(h, h->itv_right, (size_t)h->run.n_itv_slots + 2, "the interval slots"));      // (+2: k_pack reads the first two slots of a row whatever its capacity)
     TRY(ensure(h, h->itv_n, (size_t)RS)); TRY(ensure(h, h->row_nrec, (size_t)RS));
     FillGroup fg(h, "fills_rows");
     TRY(fg.zero(h->itv_n.p(), RS)); TRY(fg.zero(h->row_nrec.p(), RS));
@@ -2256,11 +2287,18 @@ static int run_rows(wfs_handle *h, RunState &r)
     if (r.tiles_done) { za.tile_done = ga.tile_done; za.n_done = ga.n_done; za.row_cnt = ga.row_cnt; za.row_tile = ga.row_tile; za.ins_bcap = ga.ins_bcap; za.ins_boff = ga.ins_boff; za.tbuf = h->tbuf.p(); }
     za.n_front = h->run.n_front_rows; za.rows_cap = CG * d.row_slots;
     if (d.sum_channel >= 0) { za.sum_lo = h->sum_lo.p(); za.sum_hi = h->sum_hi.p(); za.sum_off = h->sum_off.p(); za.sum_base = h->run.sum_base; }
+    za.n_res = h->run.n_res_rows;
+    if (h->run.n_res_rows > 0 || n_empty_rows(h) > 0) {      // finished 16-bit samples: the resident rows', then those of the rows without a pulse
+        TRY(ensure_rows(h, h->fin, (size_t)(h->run.s_fin + s_empty(h)) + 8, "the finished samples of the rows without a pulse"));
+        za.fin = h->fin.p();
+    }
     if (h->run.n_res_rows > 0) {
-        TRY(ensure(h, h->fin, (size_t)h->run.s_fin + 8));
         TRY(ensure(h, h->res_rows, (size_t)h->run.n_res_rows));
-        za.res_toff = h->res_toff.p(); za.fin_off = h->fin_off.p(); za.fin = h->fin.p();
+        za.res_toff = h->res_toff.p(); za.fin_off = h->fin_off.p();
         za.n_short = h->run.n_short_rows; za.res_long = h->res_long.p(); za.res_rows = h->res_rows.p();
+    }
+    if (n_empty_rows(h) > 0) {
+        za.fin_base = h->run.s_fin; za.empty_rows = h->empty_rows.p(); za.fr_off = h->fr_off.p(); za.grp_lo = h->grp_lo.p(); za.grp_hi = h->grp_hi.p();
     }
     if ((h->debug_bits & DBG_CURRENTS) && h->run.n_active_rows > 0) {
         const ListedRows lr = listed_rows(h);
@@ -2297,6 +2335,11 @@ static int run_rows(wfs_handle *h, RunState &r)
                 else WFS_LAUNCH_F(h, K_ROW_PULSE_LONG, grid, dim3(256), lds, d, pr, za, first, n_rows, region);
             });
         }
+    }
+    if (n_empty_rows(h) > 0) {      // full readout: the rows without a pulse, finished samples and intervals by one wave per row
+        Timer t(h, "k_row_empty"); const dim3 grid(nblocks(n_empty_rows(h), 4));
+        const i64 first = h->run.n_front_rows + h->run.n_res_rows;
+        with_noise_kind(r.noise_kind, [&](auto nk) { hipLaunchKernelGGL(k_row_empty<decltype(nk)::value>, grid, dim3(256), 0, h->stream, d, za, first, n_empty_rows(h)); });
     }
     {   // truth accumulators of every pulse set from the per-tile partial sums
         TruthArgs ta{S, h->tile_count.p(), h->tile_tmin.p(), h->tile_tmax.p(), h->set_t0.p(), h->tile_truth.p(),
@@ -2337,7 +2380,7 @@ static int run_records(wfs_handle *h, RunState &r)
     // the other arena: the previous batch's records may still be on their way to the host
     h->rec_cur ^= 1;
     if (h->rec_pending[h->rec_cur]) { HIPCHK(hipEventSynchronize(h->rec_copied[h->rec_cur])); h->rec_pending[h->rec_cur] = false; }
-    TRY(ensure(h, h->records_buf(), (size_t)h->run.n_records * WFS_RECORD_BYTES));
+    TRY(ensure_rows(h, h->records_buf(), (size_t)h->run.n_records * WFS_RECORD_BYTES, "the records"));
     za.rec_off = h->rec_off.p(); za.records = h->records_buf().as<uint8_t>(); za.rec_capacity = h->run.n_records;
     if (h->sort_records && h->run.n_records > 1 && h->run.n_active_rows > 0) {
         // records by (time, channel): keys per record, one radix sort of the batch, k_pack writes to the sorted slots
@@ -2369,9 +2412,9 @@ static int run_records(wfs_handle *h, RunState &r)
             ps = h->pack_stream;
         }
         { Timer t(h, "k_pack_desc"); hipLaunchKernelGGL(k_pack_desc, dim3(nblocks(h->run.n_active_rows, 256)), dim3(256), 0, ps, za); }
-        if (h->run.n_res_rows > 0) {
-            PackResArgs pr{h->pack_desc.p() + h->run.n_front_rows, h->fin.p(), za.itv_left, za.itv_right, za.records, za.rec_dest, za.rec_capacity, h->run.n_res_rows, za.spr, (i32)d.dt};
-            Timer t(h, "k_pack_res"); hipLaunchKernelGGL(k_pack_res, dim3(nblocks(h->run.n_res_rows, 4)), dim3(256), 0, ps, pr);
+        if (const i64 n_fin_rows = h->run.n_res_rows + n_empty_rows(h); n_fin_rows > 0) {      // rows that exist as finished samples: resident, without a pulse
+            PackResArgs pr{h->pack_desc.p() + h->run.n_front_rows, h->fin.p(), za.itv_left, za.itv_right, za.records, za.rec_dest, za.rec_capacity, n_fin_rows, za.spr, (i32)d.dt};
+            Timer t(h, "k_pack_res"); hipLaunchKernelGGL(k_pack_res, dim3(nblocks(n_fin_rows, 4)), dim3(256), 0, ps, pr);
         }
         if (h->run.n_front_rows > 0) {
             Timer t(h, "k_pack"); const dim3 grid(nblocks(h->run.n_front_rows, 4));
@@ -2421,7 +2464,7 @@ try {
     c.n_instructions = h->batch.n_ins; c.n_pulse_sets = h->batch.n_sets; c.n_emitters = h->batch.n_emitters; c.n_photons = n_primary_photons(h) + h->run.n_ap_photons;
     const bool tiles_done = tiles_made(h);
     c.n_tiles = h->run.n_active_tiles + (tiles_done ? h->run.n_fused_tiles : 0) + h->run.n_res_tiles; c.n_groups = h->run.n_groups; c.n_rows = h->run.n_active_rows;
-    c.n_raw_samples = h->run.s_raw + (tiles_done ? h->run.s_raw_direct : 0) + h->run.s_res + h->run.s_sum;
+    c.n_raw_samples = h->run.s_raw + (tiles_done ? h->run.s_raw_direct : 0) + h->run.s_res + h->run.s_sum;      // (full readout: rows without a pulse have no raw sample)
     c.n_records = h->run.n_records;
     c.n_intervals = h->h_scal->n_intervals; c.n_pe = h->h_scal->n_pe;          // reduced on the device at the end of wfs_run (k_counts)
     *out = c;
@@ -2581,7 +2624,7 @@ try {
     if (!h || !run_complete(h)) return WFS_E_STATE;
     if (!(h->debug_bits & DBG_CURRENTS)) return h->fail(WFS_E_STATE, "wfs_set_debug(h, 1) before wfs_run");
     const WfsDev &d = h->dev;
-    const i64 A = h->run.n_active_rows;
+    const i64 A = h->run.n_active_rows - n_empty_rows(h);      // (full readout: the rows without a pulse never exist unfinished)
     if (cap < A) return h->fail(WFS_E_CAPACITY, "row buffer too small");
     const ListedRows lr = listed_rows(h);
     const std::vector<i64> gl = download(h, h->grp_left, (size_t)h->run.n_groups);
@@ -2786,6 +2829,17 @@ try {
     }
     h->sum_on = on != 0;
     refresh_dev(h);             // (a switch that changes the row slots: run again before copying rows)
+    return WFS_OK;
+} WFS_CATCH(h)
+
+// Every digitise window read out in full (include/wfsim_amd.h).  A change of mode: pending packers are waited for, like the other
+// setters that change what a run lays out; the row SLOTS stay, so the last run's copies still decode.
+int wfs_set_full_readout(wfs_handle *h, int32_t on)
+try {
+    if (!h) return WFS_E_INVALID;
+    if ((on != 0) != h->full_on) TRY(pack_wait(h));
+    h->full_on = on != 0;
+    refresh_dev(h);
     return WFS_OK;
 } WFS_CATCH(h)
 

@@ -174,6 +174,9 @@ struct GeomArgs {
     // the bottom-array sum row of every window (wfs_set_sum_signal; nullptr when the switch is off): union of the bottom rows' ranges,
     // its length and its chunks for k_sum_signal
     i64 *sum_lo, *sum_hi; i32 *sum_len, *sum_nchunk;
+    // full readout (wfs_set_full_readout; nullptr when the switch is off): finished int16 samples reserved for a row without a pulse
+    // [groups * row_slots], and the list of those rows
+    i32 *fr_len, *empty_rows;
 };
 
 // (SPARSE_MAX_PHOTONS, SPARSE_MAX_BINS, the class of the sorted-list kernel, and RES_SHORT_LEN: wfs_layout.h, which sizes LDS by them)
@@ -377,6 +380,17 @@ __global__ void k_group_final(WfsDev d, GeomArgs a)
     a.grp_ixrand[g] = ix;
 }
 
+// Full readout: a row with pulses spans its window's range instead of its own (full_row_span, wfs_layout.h).  Behind k_tile_rows and
+// k_group_final, in front of everything that places a tile in its row or sizes a row (k_row_len, k_tile_assign, k_tile_desc, k_tile_add,
+// k_sum_signal): they all count from row_lo.  Rows without a pulse keep I64_MAX: they have no accumulators (k_row_len lists them).
+__global__ void k_rows_widen(WfsDev d, GeomArgs a)
+{
+    const i64 ridx = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ridx >= a.scal->n_groups * d.n_tpc || a.row_lo[ridx] == I64_MAX) return;
+    const i64 g = ridx / d.n_tpc;
+    a.row_lo[ridx] = a.grp_lo[g]; a.row_hi[ridx] = a.grp_hi[g];
+}
+
 // the last row slot of a window is its bottom-array sum row when the switch is on (wfs_set_sum_signal; row_slot_is_sum, wfs_layout.h)
 #define SUM_CHUNK 1024             // samples of a sum row per workgroup of k_sum_signal
 
@@ -391,12 +405,12 @@ __device__ __forceinline__ bool row_is_direct(const i32 *tile_done, i64 n_done, 
 // (appended with one global atomic per workgroup)
 __global__ void k_row_len(WfsDev d, GeomArgs a)
 {
-    __shared__ i32 s_n, s_nres, s_nlong, s_direct, s_shared, s_maxres, s_reslen; __shared__ i64 s_base, s_rbase, s_lbase;
-    if (threadIdx.x == 0) { s_n = 0; s_nres = 0; s_nlong = 0; s_direct = 0; s_shared = 0; s_maxres = 0; s_reslen = 0; }
+    __shared__ i32 s_n, s_nres, s_nlong, s_direct, s_shared, s_maxres, s_reslen, s_nempty; __shared__ i64 s_base, s_rbase, s_lbase, s_ebase;
+    if (threadIdx.x == 0) { s_n = 0; s_nres = 0; s_nlong = 0; s_direct = 0; s_shared = 0; s_maxres = 0; s_reslen = 0; s_nempty = 0; }
     __syncthreads();
     const i64 idx = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     const i64 n = a.scal->n_groups * d.row_slots;
-    i32 cap = 0, rk = -1; bool resident = false, longrow = false;
+    i32 cap = 0, rk = -1; bool resident = false, longrow = false, empty = false;
     if (idx < n) {
         const i64 g = idx / d.row_slots; const i32 slot = (i32)(idx - g * d.row_slots);
         const bool sum = row_slot_is_sum(d, slot);
@@ -415,7 +429,8 @@ __global__ void k_row_len(WfsDev d, GeomArgs a)
             const i64 len = row_span(lo, a.row_hi[g * d.n_tpc + ch], d.tw).len;
             cap = (i32)zle_slots(len, zle_holdoff(d.tw));
             // a row made by ONE tile whose samples exist already (k_s2_tile) is read from the tile's buffer: no accumulators
-            const bool direct = row_is_direct(a.tile_done, a.n_done, a.row_cnt, a.row_tile, g * d.n_tpc + ch);
+            // (full readout: the row is longer than its tile -- accumulators and k_tile_add)
+            const bool direct = !d.full_readout && row_is_direct(a.tile_done, a.n_done, a.row_cnt, a.row_tile, g * d.n_tpc + ch);
             // a short row of small tiles is made in LDS by one wave (k_row_pulse): no accumulators either, 16-bit finished samples instead
             // (a row longer than res_max_len samples is made in segments of that length, its tiles looked at once per segment)
             resident = a.res_on && !direct && !a.row_bad[g * d.n_tpc + ch]
@@ -427,18 +442,27 @@ __global__ void k_row_len(WfsDev d, GeomArgs a)
             }
             if (slot < d.n_tpc && !resident && a.row_cnt && a.row_cnt[g * d.n_tpc + ch] > 1) atomicAdd(&s_shared, 1);
             rk = atomicAdd(resident ? (longrow ? &s_nlong : &s_nres) : &s_n, 1);
+        } else if (d.full_readout && a.grp_lo[g] != I64_MAX) {
+            // full readout: a TPC or HE slot without a pulse in a window that has one -- a row of the window's range, made finished by
+            // k_row_empty: no accumulators, no tile, 16-bit samples behind those of the resident rows
+            const i64 len = full_row_span(a.grp_lo[g], a.grp_hi[g], d.tw).len;
+            cap = (i32)zle_slots(len, zle_holdoff(d.tw));
+            a.fr_len[idx] = fin_padded_len((i32)len);
+            empty = true; rk = atomicAdd(&s_nempty, 1);
         }
     }
     __syncthreads();
     if (threadIdx.x == 0 && s_n) s_base = (i64)atomicAdd((u64 *)&a.scal->n_front_rows, (u64)s_n);
     if (threadIdx.x == 0 && s_nres) s_rbase = (i64)atomicAdd((u64 *)&a.scal->n_short_rows, (u64)s_nres);
     if (threadIdx.x == 0 && s_nlong) s_lbase = (i64)atomicAdd((u64 *)&a.scal->n_long_rows, (u64)s_nlong);
+    if (threadIdx.x == 0 && s_nempty) s_ebase = (i64)atomicAdd((u64 *)&a.scal->n_empty_rows, (u64)s_nempty);
     if (threadIdx.x == 0 && s_reslen) { atomicMax(&a.scal->max_res_len, (i64)s_maxres); atomicAdd((u64 *)&a.scal->n_res_samples, (u64)s_reslen); }
     if (threadIdx.x == 0 && s_direct) atomicAdd((u64 *)&a.scal->n_direct_samples, (u64)s_direct);      // samples of the rows read in place
     if (threadIdx.x == 0 && s_shared) atomicAdd((u64 *)&a.scal->n_shared_rows, (u64)s_shared);      // rows made by several tiles (k_tile_add is needed)
     __syncthreads();
     if (rk >= 0) {
-        if (!resident) a.active_rows[s_base + rk] = (i32)idx;
+        if (empty) a.empty_rows[s_ebase + rk] = (i32)idx;
+        else if (!resident) a.active_rows[s_base + rk] = (i32)idx;
         else if (!longrow) a.active_rows[a.rows_cap - 1 - (s_rbase + rk)] = (i32)idx;
         else a.res_long[s_lbase + rk] = (i32)idx;
     }
@@ -1559,6 +1583,9 @@ struct ZleArgs {
     struct PackDesc *pdesc;      // [n_active_rows] what k_pack needs of a row, in one scalar load (k_pack_desc)
     // sum rows (k_sum_signal): range per window, first sample of the window's row behind raw[sum_base]
     const i64 *sum_lo, *sum_hi, *sum_off; i64 sum_base;
+    // full readout: the rows without a pulse (k_row_empty) behind the n_res resident rows of the row list; their finished samples
+    // are fin[fin_base + fr_off[row slot] ..], their range is the window's (grp_lo / grp_hi)
+    i64 n_res, fin_base; const i32 *empty_rows; const i64 *fr_off, *grp_lo, *grp_hi;
 };
 
 // One 64-byte descriptor per active row (thread per row: the divisions and the five dependent look-ups of a row are
@@ -1580,7 +1607,21 @@ __global__ void k_row_desc(WfsDev d, ZleArgs a)
 {
     const i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= a.n_active_rows) return;
+    if (r >= a.n_front + a.n_res) {
+        // full readout: the rows without a pulse, behind the resident rows and read like them (src 2) -- the window's range, finished
+        // samples behind those of the resident rows
+        const i64 idx = a.empty_rows[r - a.n_front - a.n_res];
+        const RowSlot rs = row_slot(d, idx);
+        const RowSpan sp = full_row_span(a.grp_lo[rs.g], a.grp_hi[rs.g], d.tw);
+        RowDesc q;
+        q.acc_off = a.fin_base + a.fr_off[idx]; q.row_abs = sp.left; q.ixr = a.grp_ixrand[rs.g]; q.itv_base = a.itv_off[idx];
+        q.thr = d.thr_zle[rs.channel]; q.idx = idx; q.len = (i32)sp.len; q.channel = rs.channel; q.he = rs.he ? 1 : 0; q.src = 2;
+        a.desc[r] = q;
+        if (a.key_base) { atomicMin(&a.key_base->key_origin, q.row_abs); atomicMax(&a.key_base->key_end, q.row_abs + (i64)q.len); }
+        return;
+    }
     // row list order: accumulator rows | short resident rows (from the end of active_rows backwards, k_row_len) | long resident rows
+    // | rows without a pulse (full readout)
     const i64 idx = r < a.n_front ? a.active_rows[r] : (r < a.n_front + a.n_short ? a.active_rows[a.rows_cap - 1 - (r - a.n_front)] : a.res_long[r - a.n_front - a.n_short]);
     const RowSlot rs = row_slot(d, idx);
     const i64 g = rs.g;
@@ -1605,7 +1646,7 @@ __global__ void k_row_desc(WfsDev d, ZleArgs a)
         const i64 t0 = a.res_toff[ridx];
         a.res_rows[r - a.n_front] = ResRow{t0, (i32)(a.res_toff[ridx + 1] - t0), 0};
     }
-    if (row_is_direct(a.tile_done, a.n_done, a.row_cnt, a.row_tile, ridx)) {
+    if (!d.full_readout && row_is_direct(a.tile_done, a.n_done, a.row_cnt, a.row_tile, ridx)) {
         const i32 tile = a.row_tile[ridx]; const i32 ins = tile / d.n_tpc;
         q.acc_off = a.ins_boff[ins] + (i64)(tile - ins * d.n_tpc) * a.ins_bcap[ins]; q.src = 1;
     }
@@ -1908,7 +1949,7 @@ __global__ __launch_bounds__(256) void k_noise_white_samples(WfsDev d, i32 row, 
 //
 // Sample i of a row in one step, its noise fetched behind a branch: the general paths of k_zle and k_pack
 template <int NK>
-__device__ __forceinline__ i32 finish_sample(const WfsDev &d, const i32 *acc, i64 i, i32 slot_ch, bool he, i64 ix_rand, i64 row_abs)
+__device__ __forceinline__ i32 finish_sample_of(const WfsDev &d, i32 acc_i, i64 i, i32 slot_ch, bool he, i64 ix_rand, i64 row_abs)
 {
     const bool noisy = NK != 0 && (NK >= 3 || d.enable_noise) && slot_ch < d.noise_channels;
     i32 nz = 0; double nzf = 0;
@@ -1921,7 +1962,12 @@ __device__ __forceinline__ i32 finish_sample(const WfsDev &d, const i32 *acc, i6
             if constexpr (NK == 2) nzf = d.noise_f[(i64)slot_ch * d.noise_stride + in]; else nz = d.noise[(i64)slot_ch * d.noise_stride + in];
         }
     }
-    return finish_value<NK>(d, acc[i], he, noisy, nz, nzf);
+    return finish_value<NK>(d, acc_i, he, noisy, nz, nzf);
+}
+template <int NK>
+__device__ __forceinline__ i32 finish_sample(const WfsDev &d, const i32 *acc, i64 i, i32 slot_ch, bool he, i64 ix_rand, i64 row_abs)
+{
+    return finish_sample_of<NK>(d, acc[i], i, slot_ch, he, ix_rand, row_abs);
 }
 
 // The same in two steps, for loops that want ALL their loads in flight before the first use: with the load inside finish_sample
@@ -2047,6 +2093,44 @@ struct ZleFast {
     }
 };
 
+// The interval bookkeeping for ANY hold-off (the general path of k_zle; k_row_empty): a lane per sample of a chunk of 64, `mask` the
+// ballot of the chunk's hits and `hit` the lane's own bit of it.  An interval is closed (zle_window) by the lane that finds the next
+// one's start, the last one by lane 0 at the end of the row.
+struct ZleChunks {
+    i32 carry_last = -1, open_left = -1, count = 0, nrec = 0;      // (a row is shorter than 10^6 samples: 32-bit indices)
+    // close interval k = [rawl, rawr] (first / last hit) in the lane that found it: absolute sample indices (rawdata.py:311); returns the records it needs
+    __device__ __forceinline__ i32 close(const WfsDev &d, const ZleArgs &a, i64 base, i64 row_abs, i32 len32, i32 k, i32 rawl, i32 rawr)
+    {
+        const ZleWindow w = zle_window(rawl, rawr, d.tw, len32);
+        a.itv_left[base + k] = row_abs + w.left; a.itv_right[base + k] = row_abs + w.right;
+        return w.nrec;
+    }
+    __device__ __forceinline__ void chunk(const WfsDev &d, const ZleArgs &a, int lane, i64 base, i64 row_abs, i32 len32, i32 hold32, bool hit, u64 mask, i32 c0)
+    {
+        const i32 i = c0 + lane;
+        const u64 lt = (1ull << lane) - 1ull;
+        const u64 below = mask & lt;
+        const i32 prev = below ? c0 + 63 - __clzll(below) : carry_last;       // last hit before this sample
+        const bool start = hit && (prev < 0 || i - prev > hold32);
+        const u64 smask = ballot64(start);
+        if (start) {
+            const u64 sbelow = smask & lt;
+            const i32 k = count + __popcll(sbelow);
+            const i32 prev_left = sbelow ? c0 + 63 - __clzll(sbelow) : open_left;
+            if (k > 0) nrec += close(d, a, base, row_abs, len32, k - 1, prev_left, prev);
+        }
+        count += __popcll(smask);
+        if (smask) open_left = c0 + 63 - __clzll(smask);
+        if (mask) carry_last = c0 + 63 - __clzll(mask);
+    }
+    __device__ __forceinline__ void finish(const WfsDev &d, const ZleArgs &a, int lane, i64 base, i64 row_abs, i32 len32, i64 idx)
+    {
+        if (lane == 0 && count > 0) nrec += close(d, a, base, row_abs, len32, count - 1, open_left, carry_last);
+        for (int o = 32; o > 0; o >>= 1) nrec += __shfl_down(nrec, o, 64);
+        if (lane == 0) { a.itv_n[idx] = count; a.row_nrec[idx] = nrec; }
+    }
+};
+
 // one wave per row: find_intervals_below_threshold (utils.py:13-58) in its parallel form: consecutive
 // hit samples a < b belong to one interval iff b - a <= max(holdoff, 1); then the window of rawdata.py:302-308.
 template <int NK>
@@ -2062,15 +2146,8 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
     const i64 ixr = q.ixr;
     const i64 base = q.itv_base;
     const i64 row_abs = q.row_abs;
-    i32 carry_last = -1, open_left = -1; i32 count = 0, nrec = 0;      // (a row is shorter than 10^6 samples: 32-bit indices)
     const i32 len32 = q.len, hold32 = (i32)zle_holdoff(d.tw);
-    // the general path closes interval k = [rawl, rawr] (first / last hit, zle_window) in the lane that found it: absolute sample
-    // indices (rawdata.py:311); returns the records it needs
-    auto close_at = [&](i32 k, i32 rawl, i32 rawr) -> i32 {
-        const ZleWindow w = zle_window(rawl, rawr, d.tw, len32);
-        a.itv_left[base + k] = row_abs + w.left; a.itv_right[base + k] = row_abs + w.right;
-        return w.nrec;
-    };
+    ZleChunks zc;                                           // (the general path)
     const bool noisy = NK != 0 && channel < d.noise_channels;
     // the noise index of a row's sample i is (ix + i) mod noise_len (rawdata.py:433-434): a scalar start per block of samples that
     // steps with the block and wraps, plus the lane's offset inside the block -- rows may be any number of noise lengths long.
@@ -2155,26 +2232,10 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
             if (c0 >= len32) break;                             // wave-uniform
             const i32 i = c0 + lane;
             const bool hit = i < len32 && (i64)vv[u] < thr;
-            const u64 mask = ballot64(hit);
-            const u64 lt = (1ull << lane) - 1ull;
-            const u64 below = mask & lt;
-            const i32 prev = below ? c0 + 63 - __clzll(below) : carry_last;       // last hit before this sample
-            const bool start = hit && (prev < 0 || i - prev > hold32);
-            const u64 smask = ballot64(start);
-            if (start) {
-                const u64 sbelow = smask & lt;
-                const i32 k = count + __popcll(sbelow);
-                const i32 prev_left = sbelow ? c0 + 63 - __clzll(sbelow) : open_left;
-                if (k > 0) nrec += close_at(k - 1, prev_left, prev);
-            }
-            count += __popcll(smask);
-            if (smask) open_left = c0 + 63 - __clzll(smask);
-            if (mask) carry_last = c0 + 63 - __clzll(mask);
+            zc.chunk(d, a, lane, base, row_abs, len32, hold32, hit, ballot64(hit), c0);
         }
     }
-    if (lane == 0 && count > 0) nrec += close_at(count - 1, open_left, carry_last);
-    for (int o = 32; o > 0; o >>= 1) nrec += __shfl_down(nrec, o, 64);
-    if (lane == 0) { a.itv_n[idx] = count; a.row_nrec[idx] = nrec; }
+    zc.finish(d, a, lane, base, row_abs, len32, idx);
 }
 
 // The bottom-array sum row of a window (wfs_set_sum_signal): row 800 of the reference's digitiser array, the per-pulse rounded ADC
@@ -2214,7 +2275,7 @@ __global__ __launch_bounds__(256) void k_sum_signal(WfsDev d, SumArgs a)
         const i32 rel = (i32)(lo - slo) - s0, rl = (i32)row_span(lo, a.row_hi[ridx], d.tw).len;      // both rows start tw samples ahead of their first pulse
         if (rel >= SUM_CHUNK || rel + rl <= 0) continue;
         i64 off;                                                // sample offset into raw, or ~(offset into tbuf)
-        if (row_is_direct(a.tile_done, a.n_done, a.row_cnt, a.row_tile, ridx)) {
+        if (!d.full_readout && row_is_direct(a.tile_done, a.n_done, a.row_cnt, a.row_tile, ridx)) {
             const i32 tile = a.row_tile[ridx]; const i32 ins = tile / d.n_tpc;
             off = ~(a.ins_boff[ins] + (i64)(tile - ins * d.n_tpc) * a.ins_bcap[ins]);
         } else off = a.acc_off[ridx];
@@ -2346,6 +2407,71 @@ __global__ __launch_bounds__(256) void k_row_pulse(WfsDev d, PulseArgs a, ZleArg
         if (!SEG) break;
     }
     zf.finish(d, z, lane, base, row_abs, len32, idx);
+}
+
+// Full readout: the rows WITHOUT a pulse (wfs_set_full_readout; most rows of a fully read-out window).  Their sample is the finished
+// value of an accumulator of 0 -- finish_four / finish_sample_of, the rule of every row -- so a row is noise, baseline and clamp:
+// nothing is accumulated, no int32 sample exists anywhere, and the row is on no tile list.  One wave per row walks it in blocks of 256
+// samples, four consecutive samples per lane: the noise of the block through noise_four (one Philox call of the white kind per lane,
+// the quads of the coloured and slow kinds shared across the lanes, 8 / 32 bytes of a table), finished in registers, stored ONCE as
+// 16-bit samples where k_pack_res reads them (RowDesc::src 2, like a resident row), and zero-suppressed from the lanes' hit nibbles.
+// A block is addressed by its absolute first sample alone, so a row of any length is a run of blocks: there is no row buffer in LDS
+// whose size would cut a long row into segments, and the taps and knots a block needs beyond its edges are drawn by the generators
+// themselves (colour_stream_four / slow_stream_four).  Any hold-off (the resident path needs ZLE_FAST_HOLD): the bookkeeping is the
+// general one of k_zle, a lane per sample of a 64-sample chunk, fed with the chunk's hit mask, which is put together from the ballots
+// of the nibbles' four bits (sample 4 l + j of a chunk is bit j of lane l of its 16 lanes); a block without a hit -- almost all of
+// them at an ordinary threshold -- costs four ballots.
+__device__ __forceinline__ u64 spread16_by4(u64 x)      // bit k of the low 16 -> bit 4 k
+{
+    x &= 0xffffull;
+    x = (x | (x << 24)) & 0x000000ff000000ffull; x = (x | (x << 12)) & 0x000f000f000f000full;
+    x = (x | (x << 6)) & 0x0303030303030303ull; x = (x | (x << 3)) & 0x1111111111111111ull;
+    return x;
+}
+template <int NK>
+__global__ __launch_bounds__(256) void k_row_empty(WfsDev d, ZleArgs a, i64 first, i64 n_rows)
+{
+    const int lane = threadIdx.x & 63;
+    const i64 r = (i64)blockIdx.x * 4 + wave_in_block();
+    if (r >= n_rows) return;                                // wave-uniform
+    const RowDesc q = a.desc[first + r];
+    const i32 channel = q.channel; const bool he = q.he != 0;
+    const i64 thr = q.thr, base = q.itv_base, row_abs = q.row_abs, ixr = q.ixr;
+    const i32 len32 = q.len, hold32 = (i32)zle_holdoff(d.tw), fin_len = fin_padded_len(len32);
+    int16_t *fin = a.fin + q.acc_off;
+    const bool noisy = NK != 0 && channel < d.noise_channels;
+    constexpr bool TABLE = NK == 1 || NK == 2;
+    const bool fast_noise = !TABLE || d.noise_len >= NOISE_MIN_FAST;      // (a shorter table wraps more than once inside a block: sample by sample, as k_zle)
+    const void *noise_row = noise_row_of<NK>(d, channel, noisy);
+    u32 nrun = (noisy && TABLE) ? (u32)ixr : 0u;            // tables: noise index of the block's first sample (rawdata.py:433-434); drawn kinds: its index in the row
+    ZleChunks zc;
+    for (i32 b0 = 0; b0 < len32; b0 += 256) {
+        const i32 i = b0 + 4 * lane;                        // the lane's first sample in the row
+        i32 v[4];
+        if (fast_noise) {                                   // (wave-uniform: all 64 lanes draw, noise_four)
+            Raw4<NK> s4;
+            s4.acc[0] = s4.acc[1] = s4.acc[2] = s4.acc[3] = 0;
+            noise_four<NK>(d, s4, noise_row, channel, row_abs, nrun, lane);
+#pragma unroll
+            for (int j = 0; j < 4; j++) v[j] = finish_four<NK>(d, s4, j, he, noisy);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; j++) v[j] = i + j < len32 ? finish_sample_of<NK>(d, 0, (i64)(i + j), channel, he, ixr, row_abs) : 0;
+        }
+        if constexpr (TABLE) nrun = fast_noise ? noise_advance(nrun, 256u, (u32)d.noise_len) : 0u; else nrun += 256u;
+        u32 nib = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) nib |= (i + j < len32 && (i64)v[j] < thr) ? (1u << j) : 0u;
+        if (i < fin_len) *(uint2 *)(fin + i) = make_uint2(((u32)v[0] & 0xffffu) | ((u32)v[1] << 16), ((u32)v[2] & 0xffffu) | ((u32)v[3] << 16));
+        const u64 bj0 = ballot64((nib & 1u) != 0), bj1 = ballot64((nib & 2u) != 0), bj2 = ballot64((nib & 4u) != 0), bj3 = ballot64((nib & 8u) != 0);
+        if ((bj0 | bj1 | bj2 | bj3) == 0) continue;         // wave-uniform
+        for (int c = 0; c < 4; c++) {
+            const u64 mask = spread16_by4(bj0 >> (16 * c)) | (spread16_by4(bj1 >> (16 * c)) << 1) | (spread16_by4(bj2 >> (16 * c)) << 2) | (spread16_by4(bj3 >> (16 * c)) << 3);
+            if (mask == 0) continue;                        // (no hit: nothing of the bookkeeping moves)
+            zc.chunk(d, a, lane, base, row_abs, len32, hold32, ((mask >> lane) & 1ull) != 0, mask, b0 + 64 * c);      // lane l stands for sample c0 + l
+        }
+    }
+    zc.finish(d, a, lane, base, row_abs, len32, q.idx);
 }
 
 // Records ordered by (time, channel) as strax.sort_by_time leaves them (strax_interface.py:453): one key per record; the

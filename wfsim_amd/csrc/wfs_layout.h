@@ -287,3 +287,7 @@ WFS_HD RowSlot row_slot(const D &d, i64 idx)
 // last sample (relative to the window when lo and hi are)
 struct RowSpan { i64 len, left, right; };
 WFS_HD RowSpan row_span(i64 lo, i64 hi, i64 tw) { return RowSpan{hi - lo + 1 + 2 * tw, lo - tw, hi + tw}; }
+// Full readout (wfs_set_full_readout): every row of a window, with or without a pulse of its own, has the range of the window's union
+// mask -- the range row_span gives a channel whose pulses reach both grp_lo and grp_hi, the minimum left and the maximum right over
+// all pulses of the window.  The window's sum row keeps the union of the bottom rows' pulses.
+WFS_HD RowSpan full_row_span(i64 grp_lo, i64 grp_hi, i64 tw) { return row_span(grp_lo, grp_hi, tw); }

@@ -1,6 +1,6 @@
 // The rules of the back end of a row, each written once for host and device: hold-off and interval slots, closing a ZLE interval, the
 // records of an interval and the layout of a record, the noise index, the padded length of a finished 16-bit row, the finished sample.
-// They decide the bytes of a raw_record; two encoders (ZleFast, the general path of k_zle) and three packers (k_rec_keys, k_pack_res,
+// They decide the bytes of a raw_record; two encoders (ZleFast; ZleChunks, the general path of k_zle and k_row_empty) and three packers (k_rec_keys, k_pack_res,
 // k_pack) must agree on them to the sample.  All of it is integer arithmetic on a few scalars.
 //
 // No HIP types: tests/host/rows_main.cpp compiles this header with the host compiler and tests/test_row_rules_cpu.py holds what it
@@ -132,5 +132,8 @@ WFS_HD i32 finish_resident(const D &d, i32 acc, bool noisy, i32 nz)
     return v < 0 ? 0 : v;
 }
 // The ZLE threshold in 32 bits: `v < zle_thr32(thr)` is `(i64)v < thr` for every finished sample 0 <= v < 2^31 - 1 whatever the
-// threshold (a saturated sample of exactly 2^31 - 1 is no hit in 32 bits under a threshold beyond them)
+// threshold (a saturated sample of exactly 2^31 - 1 is no hit in 32 bits under a threshold beyond them).  That includes a threshold
+// NO sample can reach: with zle_threshold below -2^15, thr_zle = baseline - zle_threshold - 1 lies above every finished sample a
+// 16-bit record can hold, every sample of a row is a hit in either form, the row is ONE interval (zle_window: clipped into the row,
+// even landing) and is stored whole -- the "no suppression" mode of full readout is this rule and nothing else.
 WFS_HD i32 zle_thr32(i64 thr) { return thr > 0x7fffffffLL ? 0x7fffffff : (thr < -0x7fffffffLL ? -0x7fffffff : (i32)thr); }

@@ -110,7 +110,7 @@ EXPORTS = ['wfs_create', 'wfs_destroy', 'wfs_last_error', 'wfs_device_count', 'w
            'wfs_set_gas_gap_model', 'wfs_set_instruction_gas_gap', 'wfs_set_pattern_map_points', 'wfs_set_instruction_aft',
            'wfs_scalar_map_grid', 'wfs_scalar_map_points', 'wfs_scalar_map_spline', 'wfs_scalar_map_eval', 'wfs_set_noise_float', 'wfs_set_instruction_diffusion',
            'wfs_scalar_map_grid_array', 'wfs_scalar_map_points_array', 'wfs_scalar_map_linear', 'wfs_scalar_map_eval_array',
-           'wfs_set_sum_signal', 'wfs_copy_sum_signal', 'wfs_device_allocations',
+           'wfs_set_sum_signal', 'wfs_copy_sum_signal', 'wfs_set_full_readout', 'wfs_device_allocations',
            'wfs_set_noise_model', 'wfs_noise_model_samples', 'wfs_copy_noise_model', 'wfs_set_noise_colour', 'wfs_noise_white_samples', 'wfs_set_noise_slow', 'wfs_noise_slow_samples']
 
 
@@ -229,6 +229,10 @@ class Engine:
         # the bottom-array sum channel (config 'emit_sum_signal'; the library's default is off): XENONnT only (rawdata.py:241)
         self._check(self.lib.wfs_set_sum_signal(self._h, C.c_int32(params['sum_signal'])))
         self.emits_sum_records = bool(params['sum_signal'] and params['detector_nt'])
+        # every channel of a digitise window, not only the hit ones (config 'full_readout'; the library's default is off)
+        self.full_readout = False
+        if params['full_readout']:
+            self.set_full_readout(True)
         if self.keep_photons or os.environ.get('WFS_CHECK_LAUNCHES', '0') not in ('', '0'):
             self.set_debug(False)          # (every launch checked from the first run on)
         # HE records exist only when the HE rows can differ from a flat baseline (wfs_engine.hip refresh_dev): a non-zero
@@ -587,18 +591,33 @@ class Engine:
         return out
 
     def rows(self):
+        """debug copy (``set_debug(True)`` before ``run()``) of the rows before zero suppression.  With ``full_readout`` it lists the rows
+        WITH pulses only, each over its window's full range; a row without a pulse is made finished and never exists in this form
+        (``counts['n_rows']`` counts it, ``intervals()`` and ``records()`` hold what it stores)."""
         n = self.counts['n_rows']
         g, ch = np.zeros(n, np.int32), np.zeros(n, np.int32)
         left, right, off = (np.zeros(n, np.int64) for _ in range(3))
+        right -= 1                      # (an entry the library does not write -- a row without a pulse under full_readout -- stays empty)
         self._check(self.lib.wfs_copy_rows(self._h, _p(g), _p(ch), _p(left), _p(right), _p(off), C.c_int64(n)))
+        listed = right >= left
+        g, ch, left, right, off = g[listed], ch[listed], left[listed], right[listed], off[listed]
         total = int((right - left + 1).sum())
         data = np.zeros(total, dtype=np.int32)
         self._check(self.lib.wfs_copy_row_data(self._h, _p(data), C.c_int64(total)))
         return dict(group=g, channel=ch, left=left, right=right, data_off=off, data=data)
 
+    def set_full_readout(self, on):
+        """config 'full_readout' between runs (wfs_set_full_readout): from the next ``run()`` every TPC and HE row slot of
+        a digitise window has a row of the window's range, with or without a pulse.  ``intervals()`` and ``records()`` are the
+        contract for those rows; ``rows()`` (debug) lists the rows WITH pulses only, at the window's range, and ``sum_signal()`` the
+        unchanged sum rows -- a row without a pulse never exists unfinished."""
+        self._check(self.lib.wfs_set_full_readout(self._h, C.c_int32(bool(on))))
+        self.full_readout = bool(on)
+
     def sum_signal(self):
         """the bottom-array sum rows of the last run before they are finished (config 'emit_sum_signal'): per row its window, its
-        absolute first and last sample and S[t] = int(he_factor) * sum of the bottom rows, at data[data_off[k]:data_off[k + 1]]"""
+        absolute first and last sample and S[t] = int(he_factor) * sum of the bottom rows, at data[data_off[k]:data_off[k + 1]].
+        ``full_readout`` does not change them: range and value stay the union and the sum of the bottom-array PULSES of the window."""
         n, total = self.counts['n_groups'], self.counts['n_raw_samples']
         g = np.zeros(n, np.int32)
         left, right, off = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n + 1, np.int64)

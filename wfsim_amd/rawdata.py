@@ -32,6 +32,20 @@ log = logging.getLogger('wfsim_amd.core')
 PULSE_TYPE_NAMES = ('RESERVED', 's1', 's2', 'unknown', 'pi_el', 'pmt_ap', 'pe_el')
 
 
+def full_readout_records(config, params, s_ins):
+    """Records per instruction that ``config['full_readout']`` adds: row slots x the record fragments of the window's length, as
+    if the instruction had a window of its own and every row were stored whole.  An ESTIMATE that sizes a batch before anything ran:
+    the row slots are exact when HE rows come from the HE factor (noise columns for the HE channels alone also create them and are
+    not known here); the window is the samples stored around one photon plus a guessed spread of the signal, 30 samples for an S1
+    and 300 for an S2, which a deep or very large S2 exceeds.  The ratio of the records a batch really made to this estimate
+    (``_rec_scale``) corrects the next batch."""
+    he = bool(params['detector_nt']) and params['n_top'] > 0 and params['he_factor'] != 0
+    slots = int(params['n_tpc']) + (int(params['n_top']) if he else 0)
+    window = (2 * int(params['trigger_window']) + int(params['store_before']) + int(params['store_after']) + int(params['tlen'])
+              + np.where(s_ins['type'] == 1, 30, 300))
+    return slots * np.ceil(window / 110.0)
+
+
 class RawData:
     #: upper bound on the expected photons of one GPU batch (sizes the HBM arenas; 288 GB HBM3E leaves room for ~10^10)
     max_batch_quanta = 2_000_000_000
@@ -274,7 +288,10 @@ class RawData:
     def _expected_records(self, s_ins):
         """crude: a record per quantum for small signals, up to ~5 records on every PMT plus one per 400 quanta for big ones"""
         q = self._expected_quanta(s_ins)
-        return np.minimum(q, 5 * len(self.config.get('gains', np.zeros(494))) + q / 400)
+        rec = np.minimum(q, 5 * len(self.config.get('gains', np.zeros(494))) + q / 400)
+        if self.config.get('full_readout', False):
+            rec = rec + full_readout_records(self.config, self.engine.params, s_ins)
+        return rec
 
     def _load_batch(self, ins, gid, cl, key):
         ip = instruction_params(ins, self.config, self.engine.resource, gids=gid, device_maps=self.engine.device_maps, device_aft=self.engine._aft_on_device)
