@@ -448,6 +448,35 @@ int wfs_copy_sum_signal(wfs_handle *h, int32_t *group, int64_t *left, int64_t *r
  * may hold (2^36, WFS_FULL_READOUT_MAX_SAMPLES) ends in WFS_E_CAPACITY, one the device has no memory for in WFS_E_NOMEM, both with a
  * message that names full readout.  Default: off -- no kernel, no buffer, no record differs. */
 int wfs_set_full_readout(wfs_handle *h, int32_t on);
+/* PMT dark counts (config 'dark_count_rate'): single-electron pulses a PMT makes on its own, drawn on the device as a pure
+ * function of (seed, channel, absolute time) and added where a sample is finished.  rate_hz: [n_channels] in Hz, n_channels <= n_tpc.
+ * Definition -- dt the sample duration, tlen the template length, before = samples_before, L = 64 samples in a cell, m the cell index
+ * of a channel's absolute sample axis (cell m holds the samples 64 m .. 64 m + 63; m may be negative, shifts are arithmetic):
+ *   count   w = philox4x32_10(counter (low 32 bits of m, high 32 bits of m, ch, 112), key = seed);
+ *           n(ch, m) = sum_{k = 1 .. 4} [w[0] < T[ch][k]], T[ch][k] = floor(2^32 P(N >= k)), N ~ Poisson(mu_ch), mu_ch = rate_ch L dt 1e-9;
+ *           the tails are summed as the series sum_{i >= k}.  mu_ch <= 1/8: the mass above 4, below 2.6e-7, is folded into 4.
+ *   photon  j < n: the call at site 113 + (j >> 1), same first three counter words, words a = 2 (j & 1) and a + 1:
+ *           t_ns = m L dt + (((u64) w[a] (L dt)) >> 32); gain = gains[ch] * spe[row of ch][(((u64) w[a + 1] * 2000) >> 32) + 1], a single
+ *           PE always (the first index of the gain draw of every photon): a thermionic electron is one electron.
+ *   pulse   idx = t_ns div dt, r = t_ns mod dt (floor): samples idx - before + k, k < tlen, value round(gain templates[r][k] c2a), negated
+ *           as every pulse is, each photon rounded on its own, like a pulse of its own.
+ *   row     D(ch, t) = the sum of these values over the channel's dark photons that reach sample t;  acc' = acc + D(pmt channel of the
+ *           slot, row_abs + i) in front of everything else: an HE slot gets its top channel's D times int(he_factor), noise, baseline
+ *           and clamp follow unchanged.  A channel with rate 0 or gain 0 gets nothing, nor does one at or beyond n_channels.
+ * The sum row (wfs_set_sum_signal) carries no dark counts.  Windows, row ranges, ix_rand, truth, the order of the Pulse calls and the
+ * record order do not change: a dark pulse shows where a row is read out, its tail too when it began in front of the row; outside
+ * digitise windows nothing is read out (no lone-hit windows of their own).  n_channels = 0 clears; rates that are all zero are the
+ * feature off.  WFS_E_INVALID, with the argument named: n_channels > n_tpc, a negative or non-finite rate, mu > 1/8.  Takes effect
+ * from the next wfs_run; waits for pending packers.  Default: off -- no kernel, no buffer, no record differs. */
+int wfs_set_dark_counts(wfs_handle *h, int32_t n_channels, const double *rate_hz);
+/* D(channel, t0 .. t0 + n - 1), evaluated on the device (n <= 2^30, |t0| <= 2^48).  WFS_E_STATE without rates or tables. */
+int wfs_dark_count_samples(wfs_handle *h, int32_t channel, int64_t t0, int64_t n, int32_t *out);
+/* The dark photons of a channel whose start sample idx lies in [t0, t0 + n), in time order (equal times: in the order of j): the truth
+ * does not hold them, this is how a hit is matched to a dark count.  *count: how many there are; more than capacity: WFS_E_CAPACITY
+ * (the first `capacity` are written). */
+int wfs_dark_count_photons(wfs_handle *h, int32_t channel, int64_t t0, int64_t n, int64_t *t_ns, double *gain, int64_t capacity, int64_t *count);
+/* The thresholds T[channel][1 .. 4] as the device holds them.  WFS_E_STATE without rates. */
+int wfs_copy_dark_counts(wfs_handle *h, int32_t channel, uint32_t thr[4]);
 /* Which kernel made every primary (pulse set, channel) tile of the last wfs_run, indexed set * n_tpc + channel: 0 no photons or not
  * tile-generated, 1 photons and pulse in one workgroup (up to 2048 photons), 2 generation only + the pulse kernels, 3 k_s2_bright.
  * capacity: entries the buffer holds (>= n_run_sets * n_tpc). */

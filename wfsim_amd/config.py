@@ -124,6 +124,7 @@ def kernel_params(config):
         tile_local_bright=int(bool(c.get('tile_local_bright', True))),      # (not a wfs_config field: Engine passes it through wfs_set_bright_tiles)
         sum_signal=int(bool(c.get('emit_sum_signal', False))),             # (nor is this one: wfs_set_sum_signal -- the bottom-array sum row on sum_channel)
         full_readout=int(bool(c.get('full_readout', False))),              # (nor this: wfs_set_full_readout -- every channel of a digitise window)
+        dark_counts=int(c.get('dark_count_rate') is not None and bool(np.any(np.asarray(c['dark_count_rate'], dtype=np.float64) != 0))),      # (nor this: wfs_set_dark_counts -- PMT dark counts; dark_counts.rates_from validates the rates)
         fma=int(bool(c.get('fused_multiply_add', True))), row_resident=(2 if c.get('row_resident', 'auto') == 'auto' else int(bool(c.get('row_resident')))),
         c2a=float(current_2_adc(c)),
         tts_mean=float(c['pmt_transit_time_mean']),

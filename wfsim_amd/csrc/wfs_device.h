@@ -10,6 +10,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "wfs_noise.h"       // NoiseKind, the NC_ / NS_ constants of the coloured model and its slow levels
+#include "wfs_dark.h"        // PMT dark counts: the definition, the cell and site constants
 #include "wfs_layout.h"      // the sizes the LDS layouts are made of (WFS_DT, WFS_MAX_CH, SPE_ROW_LEN, ..), floordiv, the window rules
 #include "wfs_rows.h"        // the rules of the back end of a row: ZLE intervals, records, the noise index, the finished sample
 
@@ -43,7 +44,10 @@ enum WfsSite : u32 {
     SITE_NOISE_COMMON = 66,
     // the slow levels of the model (wfs_set_noise_slow): level j of a channel at site 80 + j, of common stream g (in place of the
     // channel) at 96 + j, j < 8; counter (low, high 32 bits of m >> 2, ..), m the knot index t >> shift[j]; knot m owns word m & 3
-    SITE_NOISE_SLOW = 80, SITE_NOISE_SLOW_COMMON = 96
+    SITE_NOISE_SLOW = 80, SITE_NOISE_SLOW_COMMON = 96,
+    // PMT dark counts (wfs_set_dark_counts, wfs_dark.h): counter (low, high 32 bits of the cell m, channel, site); 112: word 0 -> photons
+    // of the cell; 113 + (j >> 1): words 2 (j & 1), 2 (j & 1) + 1 -> time and SPE index of photon j < 4 (113, 114); 115 is kept free
+    SITE_DARK_N = DK_SITE_COUNT, SITE_DARK_PH = DK_SITE_PHOTON
 };
 
 struct u32x4 { u32 x, y, z, w; };
@@ -344,4 +348,7 @@ struct WfsDev {
     // ns_amp [noise_channels + nc_groups][NS_MAX_LEVELS].  With levels nc_taps is never null: a model without a colour gets unit taps
     const i32 *ns_shift, *ns_amp;
     i32 ns_levels;
+    // PMT dark counts (wfs_set_dark_counts): dk_thr [dk_channels][DK_MAX], floor(2^32 P(N >= k)) of a cell's Poisson count, nullptr: off
+    i32 dk_channels;
+    const u32 *dk_thr;
 };

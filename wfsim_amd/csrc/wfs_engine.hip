@@ -128,6 +128,8 @@ struct wfs_handle {
         if (dropped & NOISE_BUF_SLOW) ns_buf.reset();
     }
     i32 table_channels = 0;           // columns of the noise table (dev.noise_channels counts the model's channels while a model is set)
+    // PMT dark counts (wfs_dark.h): the thresholds as dk_thr holds them; written by wfs_set_dark_counts alone
+    DarkState dark;
 
     // packed records: two arenas used in turn, so that the device -> host copy of one batch (copy stream, pinned host memory)
     // runs under the kernels of the next batch
@@ -166,7 +168,7 @@ struct wfs_handle {
     DevArr<i64> itv_left, itv_right, rec_off; DevArr<i32> itv_n, row_nrec;
     DevArr<double> truth, tile_truth, currents; DevArr<i64> tminmax, gather_idx, gather_out, cur_off, row_dbg_off; DevArr<TileDesc> tile_desc; DevArr<i32> row_dbg; DevArr<TileTimeReq> gather_req;      // (wfs_gather_photon_times: the requests of tile-generated instructions; gather_idx holds those of the block generator)
     DevArr<unsigned long long> stamps; DevArr<RowDesc> row_desc; DevArr<u64> rec_key, rec_key2; DevArr<u32> rec_val, rec_val2, rec_dest; DevBuf sort_tmp;      // (sort_tmp: rocPRIM's scratch)
-    DevArr<i64> scan_tmp, noise_override; DevArr<WfsScal> scal; DevArr<NoiseCell> nm_cells; DevArr<i32> nc_buf, ns_buf; DevArr<PackDesc> pack_desc;
+    DevArr<i64> scan_tmp, noise_override; DevArr<WfsScal> scal; DevArr<NoiseCell> nm_cells; DevArr<i32> nc_buf, ns_buf; DevArr<u32> dk_thr; DevArr<PackDesc> pack_desc;
     DevArr<i32> row_bad, fin_len, res_cnt, res_long; DevArr<i64> fin_off, res_toff; DevArr<TileDesc> res_desc; DevArr<int16_t> fin; DevArr<ResRow> res_rows;      // resident rows (k_row_pulse)
     DevArr<uint2> tt_alias[6]; DevArr<i32> ap_ins, ap_ch, ap_t; DevArr<double> ap_gain; DevArr<ApCand> ap_cand; DevArr<ApArgs> ap_args_dev; DevArr<ApSeg> ap_seg;
     DevArr<AliasTab> d_tabs; DevArr<double> prop_top, prop_bot, ins_pzf, gg_inv, ins_ggw; DevArr<i32> ins_tab, ins_tabb, ins_pzi, ins_gg; DevArr<i64> ins_ggsum;
@@ -470,6 +472,12 @@ template <class F, int... K> void with_noise_kind(int kind, F &&f, std::integer_
     (void)((kind == K && (f(std::integral_constant<int, K>{}), true)) || ...);
 }
 template <class F> void with_noise_kind(int kind, F &&f) { with_noise_kind(kind, f, std::make_integer_sequence<int, NOISE_KINDS>{}); }
+// The row kernels that finish samples take the dark counts (wfs_set_dark_counts) as a second template parameter, DK: with the feature
+// off they are the kernels they were.  f is called with the kind and a std::bool_constant of the switch.
+template <class F> void with_row_kind(int kind, bool dark, F &&f)
+{
+    with_noise_kind(kind, [&](auto nk) { if (dark) f(nk, std::true_type{}); else f(nk, std::false_type{}); });
+}
 
 // What the probe entry points of the noise model share once they know their stream: the checks of (t0, n, out), a scratch buffer of n
 // elements, the launch into it (launch(T *device_buffer): timer and kernel) and the copy back.  fn: the entry point, for the messages.
@@ -675,6 +683,7 @@ void refresh_dev(wfs_handle *h)
         d.nc_groups = colour ? m.colour.groups : 0; d.nc_group = grouped ? nc + cl.group : nullptr; d.nc_mix = grouped ? nc + cl.mix : nullptr;
         d.ns_shift = slow ? ns + sl.shifts : nullptr; d.ns_amp = slow ? ns + sl.amps : nullptr; d.ns_levels = m.levels();
     }
+    d.dk_channels = h->dark.channels; d.dk_thr = h->dark.set() ? h->dk_thr.p() : nullptr;
     const bool model = h->noise.set();
     d.enable_noise = (c.enable_noise && (model || d.noise != nullptr)) ? 1 : 0;
     bool he_noise = d.enable_noise && d.noise_channels > c.he_first;
@@ -787,9 +796,10 @@ try {
     WFS_BIG_LDS(HIP_KERNEL_NAME(k_photon_fill<false, true>), LDS_CAP_FILL); WFS_BIG_LDS(HIP_KERNEL_NAME(k_photon_fill<true, true>), LDS_CAP_FILL);
     WFS_BIG_LDS(k_tile_order_big, LDS_CAP_ORDER);
     WFS_BIG_LDS_F(K_PULSE_GENERIC, LDS_CAP_GENERIC);
-#define K_ROW_PULSE_SEG(F) k_row_pulse<NK, F, true>
-    for (int kind = 0; kind < NOISE_KINDS; kind++)           // every kind that with_noise_kind can launch
-        with_noise_kind(kind, [](auto nk) { constexpr int NK = decltype(nk)::value; WFS_BIG_LDS_F(K_ROW_PULSE_SEG, LDS_CAP_ROW); });
+#define K_ROW_PULSE_SEG(F) k_row_pulse<NK, F, true, DK>
+    for (int kind = 0; kind < NOISE_KINDS; kind++)           // every kind that with_row_kind can launch, with and without dark counts
+        for (int dark = 0; dark < 2; dark++)
+            with_row_kind(kind, dark != 0, [](auto nk, auto dk) { constexpr int NK = decltype(nk)::value; constexpr bool DK = decltype(dk)::value; WFS_BIG_LDS_F(K_ROW_PULSE_SEG, LDS_CAP_ROW); });
     if (const char *e = getenv("WFS_ROW_RESIDENT")) h->res_env = atoi(e);          // 0 / 1 / 2 as the config switch (A/B runs)
     if (const char *e = getenv("WFS_FULL_READOUT_MAX_SAMPLES")) h->full_max_samples = std::max<i64>(0, atoll(e));      // capacity knob of full readout (tests)
     if (const char *e = getenv("WFS_RES_MAX_LEN")) h->res_max_len = std::max(256, std::min(atoi(e), RES_MAX_LEN)) / 256 * 256;      // tuning knob (results do not depend on it)
@@ -1961,6 +1971,7 @@ struct RunState {
     i64 CG = 0, RS = 0;                                     // group slots; row slots
     i64 first_sparse = 0, first_dense = 0, first_wave = 0;  // the one work list: tiny tiles, then sparse, dense, wave
     int noise_kind = 0;                                     // with_noise_kind
+    bool dark = false;                                      // with_row_kind: PMT dark counts are on
 };
 
 // ---- PMT afterpulses of an optical batch: the supplied photons are screened (k_optical_ap_screen), the candidates go through the
@@ -2316,21 +2327,22 @@ static int run_rows(wfs_handle *h, RunState &r)
     TRY(fg.flush());
     if (h->run.n_active_rows > 0) { Timer t(h, "k_row_desc"); hipLaunchKernelGGL(k_row_desc, dim3(nblocks(h->run.n_active_rows, 256)), dim3(256), 0, h->stream, d, za); }
     r.noise_kind = d.enable_noise ? noise_kind_of(d) : NOISE_NONE;
+    r.dark = d.dk_thr != nullptr;
     if (h->run.n_res_rows > 0) {        // resident rows: pulses, finished samples and intervals by one wave per row
         PulseArgs pr = pa;
         pr.desc = h->res_desc.p(); pr.currents = nullptr; pr.cur_off = nullptr;
         // two launches: the rows of at most RES_SHORT_LEN samples at full occupancy, the longer ones with LDS for the longest of them
         Timer t(h, "k_row_pulse");
-#define K_ROW_PULSE_SHORT(F) k_row_pulse<NK, F, false>
-#define K_ROW_PULSE_LONG(F) k_row_pulse<NK, F, true>
+#define K_ROW_PULSE_SHORT(F) k_row_pulse<NK, F, false, DK>
+#define K_ROW_PULSE_LONG(F) k_row_pulse<NK, F, true, DK>
         for (int part = 0; part < 2; part++) {
             const i64 first = part == 0 ? 0 : h->run.n_short_rows, n_rows = part == 0 ? h->run.n_short_rows : h->run.n_res_rows - h->run.n_short_rows;
             if (n_rows <= 0) continue;
             const i32 region = part == 0 ? RES_SHORT_LEN : (i32)((std::min<i64>(h->run.max_res_len, h->res_max_len) + 255) / 256 * 256);
             const size_t lds = (size_t)row_pulse_lds(region).total;
             const dim3 grid(nblocks(n_rows, 4));
-            with_noise_kind(r.noise_kind, [&](auto nk) {
-                constexpr int NK = decltype(nk)::value;
+            with_row_kind(r.noise_kind, r.dark, [&](auto nk, auto dk) {
+                constexpr int NK = decltype(nk)::value; constexpr bool DK = decltype(dk)::value;
                 if (part == 0) WFS_LAUNCH_F(h, K_ROW_PULSE_SHORT, grid, dim3(256), lds, d, pr, za, first, n_rows, region);
                 else WFS_LAUNCH_F(h, K_ROW_PULSE_LONG, grid, dim3(256), lds, d, pr, za, first, n_rows, region);
             });
@@ -2339,7 +2351,7 @@ static int run_rows(wfs_handle *h, RunState &r)
     if (n_empty_rows(h) > 0) {      // full readout: the rows without a pulse, finished samples and intervals by one wave per row
         Timer t(h, "k_row_empty"); const dim3 grid(nblocks(n_empty_rows(h), 4));
         const i64 first = h->run.n_front_rows + h->run.n_res_rows;
-        with_noise_kind(r.noise_kind, [&](auto nk) { hipLaunchKernelGGL(k_row_empty<decltype(nk)::value>, grid, dim3(256), 0, h->stream, d, za, first, n_empty_rows(h)); });
+        with_row_kind(r.noise_kind, r.dark, [&](auto nk, auto dk) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_row_empty<decltype(nk)::value, decltype(dk)::value>), grid, dim3(256), 0, h->stream, d, za, first, n_empty_rows(h)); });
     }
     {   // truth accumulators of every pulse set from the per-tile partial sums
         TruthArgs ta{S, h->tile_count.p(), h->tile_tmin.p(), h->tile_tmax.p(), h->set_t0.p(), h->tile_truth.p(),
@@ -2360,7 +2372,7 @@ static int run_rows(wfs_handle *h, RunState &r)
     }
     if (h->run.n_front_rows > 0) {
         Timer t(h, "k_zle"); const dim3 grid(nblocks(h->run.n_front_rows, 4));
-        with_noise_kind(r.noise_kind, [&](auto nk) { hipLaunchKernelGGL(k_zle<decltype(nk)::value>, grid, dim3(256), 0, h->stream, d, za); });
+        with_row_kind(r.noise_kind, r.dark, [&](auto nk, auto dk) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_zle<decltype(nk)::value, decltype(dk)::value>), grid, dim3(256), 0, h->stream, d, za); });
     }
     return WFS_OK;
 }
@@ -2418,7 +2430,7 @@ static int run_records(wfs_handle *h, RunState &r)
         }
         if (h->run.n_front_rows > 0) {
             Timer t(h, "k_pack"); const dim3 grid(nblocks(h->run.n_front_rows, 4));
-            with_noise_kind(r.noise_kind, [&](auto nk) { hipLaunchKernelGGL(k_pack<decltype(nk)::value>, grid, dim3(256), 0, ps, d, za); });
+            with_row_kind(r.noise_kind, r.dark, [&](auto nk, auto dk) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack<decltype(nk)::value, decltype(dk)::value>), grid, dim3(256), 0, ps, d, za); });
         }
         if (defer) {
             HIPCHK(hipEventRecord(h->rec_ready[h->rec_cur], h->pack_stream));
@@ -2916,6 +2928,96 @@ try {
         else if (kind == NOISE_COLOUR) { Timer t(h, "k_noise_colour_samples"); hipLaunchKernelGGL(k_noise_colour_samples<false>, waves, dim3(256), 0, h->stream, h->dev, channel, t0, n, buf); }
         else { Timer t(h, "k_noise_model_samples"); hipLaunchKernelGGL(k_noise_model_samples, dim3(nblocks((n + 3) / 4, 256)), dim3(256), 0, h->stream, h->dev, channel, t0, n, buf); }
     });
+} WFS_CATCH(h)
+
+// PMT dark counts (wfs_dark.h): the rates become the thresholds of the cells' Poisson counts, checked and computed by
+// dark_check; the row kernels draw the photons where they finish a sample.  Rates that are all zero are the feature switched off.
+int wfs_set_dark_counts(wfs_handle *h, int32_t n_channels, const double *rate_hz)
+try {
+    if (!h) return WFS_E_INVALID;
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<u32> thr; std::string err;
+    if (!dark_check(n_channels, h->cfg.n_tpc, rate_hz, h->cfg.dt, thr, err)) return h->fail(WFS_E_INVALID, err);
+    TRY(pack_wait(h));          // (pending packers read the thresholds this call replaces)
+    bool any = false;
+    for (u32 t : thr) any = any || t != 0;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (!any) { h->dark = DarkState{}; h->dk_thr.reset(); refresh_dev(h); return WFS_OK; }
+    TRY(upload(h, h->dk_thr, thr.data(), thr.size()));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->dark = DarkState{}; h->dark.channels = n_channels; h->dark.thr = std::move(thr);
+    refresh_dev(h);
+    return WFS_OK;
+} WFS_CATCH(h)
+
+// the checks the three read-backs share; fn: the entry point, for the messages
+static int dark_probe_check(wfs_handle *h, const char *fn, int32_t channel, int64_t t0, int64_t n)
+{
+    const std::string f = std::string(fn) + ": ";
+    if (!h->dark.set()) return h->fail(WFS_E_STATE, f + "no dark-count rates are set");
+    if (!h->tables_set) return h->fail(WFS_E_STATE, f + "tables not set");
+    if (channel < 0 || channel >= h->dark.channels) return h->fail(WFS_E_INVALID, f + "channel outside the given rates");
+    if (t0 < -((i64)1 << 48) || t0 > ((i64)1 << 48)) return h->fail(WFS_E_INVALID, f + "t0 beyond 2^48 in magnitude");
+    if (n < 0 || n > ((i64)1 << 30)) return h->fail(WFS_E_INVALID, f + "n outside 0 .. 2^30");
+    return WFS_OK;
+}
+
+int wfs_dark_count_samples(wfs_handle *h, int32_t channel, int64_t t0, int64_t n, int32_t *out)
+try {
+    if (!h) return WFS_E_INVALID;
+    TRY(dark_probe_check(h, __func__, channel, t0, n));
+    return noise_probe(h, __func__, t0, n, out, [&](i32 *buf) {
+        Timer t(h, "k_dark_samples");
+        hipLaunchKernelGGL(k_dark_samples, dim3(nblocks((n + 255) / 256, 4)), dim3(256), 0, h->stream, h->dev, channel, t0, n, buf);
+    });
+} WFS_CATCH(h)
+
+int wfs_dark_count_photons(wfs_handle *h, int32_t channel, int64_t t0, int64_t n, int64_t *t_ns, double *gain, int64_t capacity, int64_t *count)
+try {
+    if (!h) return WFS_E_INVALID;
+    TRY(dark_probe_check(h, __func__, channel, t0, n));
+    if (!count || capacity < 0 || (capacity > 0 && (!t_ns || !gain))) return h->fail(WFS_E_INVALID, "wfs_dark_count_photons: null count, negative capacity or null buffers");
+    *count = 0;
+    if (n == 0) return WFS_OK;
+    HIPCHK(hipSetDevice(h->device));
+    // a photon's start bin lies in its own cell: the cells of the samples t0 .. t0 + n - 1
+    const i64 m0 = t0 >> DK_CELL_SHIFT, n_cells = ((t0 + n - 1) >> DK_CELL_SHIFT) - m0 + 1;
+    DevArr<i32> d_cnt; DevArr<i64> d_t; DevArr<double> d_g;
+    TRY(ensure(h, d_cnt, (size_t)n_cells)); TRY(ensure(h, d_t, (size_t)n_cells * DK_MAX)); TRY(ensure(h, d_g, (size_t)n_cells * DK_MAX));
+    { Timer t(h, "k_dark_photons"); hipLaunchKernelGGL(k_dark_photons, dim3(nblocks(n_cells, 256)), dim3(256), 0, h->stream, h->dev, channel, m0, n_cells, d_cnt.p(), d_t.p(), d_g.p()); }
+    HIPCHK(hipGetLastError());
+    std::vector<i32> cnt((size_t)n_cells); std::vector<i64> tt((size_t)n_cells * DK_MAX); std::vector<double> gg((size_t)n_cells * DK_MAX);
+    TRY(copy_async(h, cnt.data(), d_cnt.p(), cnt.size(), hipMemcpyDeviceToHost));
+    TRY(copy_async(h, tt.data(), d_t.p(), tt.size(), hipMemcpyDeviceToHost));
+    TRY(copy_async(h, gg.data(), d_g.p(), gg.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    CHECK_LAUNCHES();
+    // time order: cells ascend, inside a cell a stable sort by time (equal times keep the order of j)
+    const i64 dt = h->cfg.dt;
+    i64 k = 0;
+    for (i64 c = 0; c < n_cells; c++) {
+        std::vector<std::pair<i64, double>> ph;
+        for (int j = 0; j < cnt[(size_t)c] && j < DK_MAX; j++) {
+            const i64 t = tt[(size_t)c * DK_MAX + j], idx = floordiv(t, dt);
+            if (idx >= t0 && idx < t0 + n) ph.emplace_back(t, gg[(size_t)c * DK_MAX + j]);
+        }
+        std::stable_sort(ph.begin(), ph.end(), [](const std::pair<i64, double> &a, const std::pair<i64, double> &b) { return a.first < b.first; });
+        for (const auto &q : ph) { if (k < capacity) { t_ns[k] = q.first; gain[k] = q.second; } k++; }
+    }
+    *count = k;
+    if (k > capacity) return h->fail(WFS_E_CAPACITY, "wfs_dark_count_photons: " + std::to_string(k) + " photons, capacity " + std::to_string(capacity));
+    return WFS_OK;
+} WFS_CATCH(h)
+
+int wfs_copy_dark_counts(wfs_handle *h, int32_t channel, uint32_t thr[4])
+try {
+    if (!h || !thr) return WFS_E_INVALID;
+    if (!h->dark.set()) return h->fail(WFS_E_STATE, "wfs_copy_dark_counts: no dark-count rates are set");
+    if (channel < 0 || channel >= h->dark.channels) return h->fail(WFS_E_INVALID, "wfs_copy_dark_counts: channel outside the given rates");
+    HIPCHK(hipSetDevice(h->device));
+    const std::vector<u32> all = download(h, h->dk_thr, (size_t)h->dark.channels * DK_MAX);
+    for (int k = 0; k < DK_MAX; k++) thr[k] = all[(size_t)channel * DK_MAX + k];
+    return WFS_OK;
 } WFS_CATCH(h)
 
 // The colour of the noise model: FIR taps per stream and common streams shared by groups of channels.  Everything the

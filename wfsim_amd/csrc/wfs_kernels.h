@@ -586,6 +586,113 @@ __device__ __forceinline__ i64 adc_of(const WfsDev &d, double c) { return -(i64)
 // Samples of a tile in front of its first start bin (pulse.py:118-127)
 __host__ __device__ __forceinline__ int tile_lead(const WfsDev &d) { return d.store_before + d.samples_before; }
 
+// ---- PMT dark counts (wfs_set_dark_counts; the definition: wfs_dark.h).  One rule in two forms that must agree: dark_sample,
+// a sample on its own (the general paths: finish_sample_of, load_sample), and dark_block, 256 consecutive samples of a wave, four per
+// lane (the finish_four loops of k_zle, k_row_pulse and k_row_empty).  The row kernels take the switch as a template parameter DK beside
+// NK: with the feature off they are the kernels they were.
+__device__ __forceinline__ u32x4 dark_call(const WfsDev &d, i32 ch, i64 m, u32 site) { return philox4x32_10((u32)(u64)m, (u32)((u64)m >> 32), (u32)ch, site, d.k0, d.k1); }
+// photons of a cell from word 0 of its count call; T: the channel's four thresholds, descending
+__device__ __forceinline__ int dark_count_of(const u32 *T, u32 w) { return (int)(w < T[0]) + (int)(w < T[1]) + (int)(w < T[2]) + (int)(w < T[3]); }
+// the PMT channel whose dark counts a row slot gets, or -1: an HE slot its top channel's, the sum row and channels beyond the given count none
+__device__ __forceinline__ i32 dark_channel_of(const WfsDev &d, i32 channel, bool he)
+{
+    const i32 c = he ? (channel == d.sum_channel ? -1 : channel - d.he_first) : channel;
+    return (d.dk_thr && c >= 0 && c < d.dk_channels && c < d.n_tpc) ? c : -1;
+}
+// photon j of cell m: its start bin idx = t_ns div dt relative to the cell's first sample (0 .. DK_CELL - 1), r = t_ns mod dt, its gain
+struct DarkPhoton { i32 bin, r; i64 t_ns; double gain; };
+__device__ __forceinline__ DarkPhoton dark_photon_of(const WfsDev &d, i32 ch, i64 m, int j, const u32x4 &W)
+{
+    const u32 wt = (j & 1) ? W.z : W.x, wg = (j & 1) ? W.w : W.y;
+    const u32 off = (u32)(((u64)wt * (u32)(DK_CELL * d.dt)) >> 32);          // ns behind the cell's start, below DK_CELL dt
+    DarkPhoton p;
+    p.bin = (i32)(off / (u32)d.dt); p.r = (i32)(off - (u32)p.bin * (u32)d.dt);
+    p.t_ns = m * (i64)(DK_CELL * d.dt) + (i64)off;
+    const u32 code = (u32)(((u64)wg * (u32)SPE_BINS) >> 32) + 1u;             // the first index of gain_code: a single PE
+    p.gain = photon_gain(spe_row_of(d, ch), d.gains[ch], code);
+    return p;
+}
+// what a photon of gain g and remainder r adds at tap k (0 <= k < tlen) of its pulse: a pulse of its own, rounded on its own
+__device__ __forceinline__ i32 dark_tap(const WfsDev &d, double gain, i32 r, i32 k) { return (i32)adc_of(d, gain * d.templates[r * d.tlen + k]); }
+// D(ch, t); ch: a channel dark_channel_of gave
+__device__ __forceinline__ i32 dark_sample(const WfsDev &d, i32 ch, i64 t)
+{
+    const u32 *T = d.dk_thr + (size_t)ch * DK_MAX;
+    if (T[0] == 0u || d.gains[ch] == 0.0) return 0;
+    i32 D = 0;
+    const i64 m_hi = (t + d.samples_before) >> DK_CELL_SHIFT;
+    for (i64 m = (t + d.samples_before - d.tlen + 1) >> DK_CELL_SHIFT; m <= m_hi; m++) {
+        const int n = dark_count_of(T, dark_call(d, ch, m, SITE_DARK_N).x);
+        for (int j = 0; j < n; j++) {
+            const DarkPhoton p = dark_photon_of(d, ch, m, j, dark_call(d, ch, m, SITE_DARK_PH + (u32)(j >> 1)));
+            const i64 k = t - (m * DK_CELL + p.bin) + d.samples_before;
+            if (k >= 0 && k < d.tlen) D += dark_tap(d, p.gain, p.r, (i32)k);
+        }
+    }
+    return D;
+}
+// acc[j] += D(ch, tb + 4 lane + j), j < 4: the wave's 256 samples from tb (wave-uniform, as ch) on.  ALL 64 LANES MUST BE EXECUTING.
+// The first lanes draw the count words of the cells the block's samples can see a photon of (at most (255 + tlen) / 64 + 2); one ballot,
+// and in the overwhelmingly common empty case nothing more happens.  Otherwise a wave-uniform loop over the photons of the non-empty
+// cells: the photon's constants are broadcast (readfirstlane), and every lane adds the taps that fall on its own samples.
+static_assert((255 + WFS_MAX_TLEN) / DK_CELL + 2 <= 64, "a lane per cell of a block");
+__device__ __forceinline__ void dark_block(const WfsDev &d, i32 ch, i64 tb, int lane, i32 (&acc)[4])
+{
+    const u32 *T = d.dk_thr + (size_t)ch * DK_MAX;
+    if (T[0] == 0u || d.gains[ch] == 0.0) return;                            // (wave-uniform)
+    const i64 m_lo = (tb + d.samples_before - d.tlen + 1) >> DK_CELL_SHIFT, m_hi = (tb + 255 + d.samples_before) >> DK_CELL_SHIFT;
+    int n = 0;
+    if ((i64)lane <= m_hi - m_lo) n = dark_count_of(T, dark_call(d, ch, m_lo + lane, SITE_DARK_N).x);
+    u64 mask = ballot64(n > 0);
+    if (mask == 0) return;                                                   // wave-uniform
+    const i64 t_lane = tb + 4 * lane;
+    while (mask) {
+        const int l = (int)__builtin_ctzll(mask); mask &= mask - 1;
+        const i64 m = m_lo + l;
+        const int nl = __builtin_amdgcn_readlane(n, l);
+        for (int j = 0; j < nl; j++) {
+            const DarkPhoton p = dark_photon_of(d, ch, m, j, dark_call(d, ch, m, SITE_DARK_PH + (u32)(j >> 1)));
+            const i32 bin = __builtin_amdgcn_readfirstlane(p.bin), r = __builtin_amdgcn_readfirstlane(p.r);
+            const long long gb = __double_as_longlong(p.gain);
+            const double gain = __longlong_as_double((long long)(((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)((u64)gb >> 32)) << 32)
+                                                                 | (u32)__builtin_amdgcn_readfirstlane((int)(u32)gb)));
+            const i64 k0 = t_lane - (m * DK_CELL + bin) + d.samples_before;  // tap of the lane's first sample
+#pragma unroll
+            for (int s = 0; s < 4; s++) { const i64 k = k0 + s; if (k >= 0 && k < d.tlen) acc[s] += dark_tap(d, gain, r, (i32)k); }
+        }
+    }
+}
+// wfs_dark_count_samples: D(channel, t0 .. t0 + n - 1) through both forms -- a wave takes 256 consecutive samples through dark_block
+// (every lane, whatever n: only the stores look at n), the last n & 3 samples go through dark_sample
+__global__ __launch_bounds__(256) void k_dark_samples(WfsDev d, i32 channel, i64 t0, i64 n, i32 *out)
+{
+    const int lane = threadIdx.x & 63;
+    const i64 b = ((i64)blockIdx.x * 4 + wave_in_block()) * 256;
+    i32 v[4] = {0, 0, 0, 0};
+    dark_block(d, channel, t0 + b, lane, v);
+    const i64 s = b + 4 * lane;
+    if (s + 3 < n) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) out[s + j] = v[j];
+    } else {
+        for (i64 u = s; u < n; u++) out[u] = dark_sample(d, channel, t0 + u);
+    }
+}
+// wfs_dark_count_photons: a thread per cell m0 + c writes the cell's count and its photons (time, gain) into slots [c][DK_MAX]
+__global__ __launch_bounds__(256) void k_dark_photons(WfsDev d, i32 channel, i64 m0, i64 n_cells, i32 *count, i64 *t_ns, double *gain)
+{
+    const i64 c = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_cells) return;
+    const u32 *T = d.dk_thr + (size_t)channel * DK_MAX;
+    const i64 m = m0 + c;
+    const int n = (T[0] == 0u || d.gains[channel] == 0.0) ? 0 : dark_count_of(T, dark_call(d, channel, m, SITE_DARK_N).x);
+    count[c] = n;
+    for (int j = 0; j < n; j++) {
+        const DarkPhoton p = dark_photon_of(d, channel, m, j, dark_call(d, channel, m, SITE_DARK_PH + (u32)(j >> 1)));
+        t_ns[c * DK_MAX + j] = p.t_ns; gain[c * DK_MAX + j] = p.gain;
+    }
+}
+
 struct DescArgs { const i32 *list; i64 n; const i32 *tile_count, *tile_tmin, *tile_tmax; const i64 *tile_off; const i32 *set_cluster; const i64 *set_t0;
                   const i32 *set_mode; const i32 *cl_group; const i64 *row_lo; const i64 *acc_off; TileDesc *desc; };
 __global__ void k_tile_desc(WfsDev d, DescArgs a)
@@ -1948,9 +2055,11 @@ __global__ __launch_bounds__(256) void k_noise_white_samples(WfsDev d, i32 row, 
 // and 5 count from.  The finished sample itself -- finish_value, and finish_resident of k_row_pulse -- is a rule of wfs_rows.h.
 //
 // Sample i of a row in one step, its noise fetched behind a branch: the general paths of k_zle and k_pack
-template <int NK>
-__device__ __forceinline__ i32 finish_sample_of(const WfsDev &d, i32 acc_i, i64 i, i32 slot_ch, bool he, i64 ix_rand, i64 row_abs)
+// (DK: PMT dark counts are on, dch the channel dark_channel_of gave the row -- D is added to the accumulated value in front of everything else)
+template <int NK, bool DK = false>
+__device__ __forceinline__ i32 finish_sample_of(const WfsDev &d, i32 acc_i, i64 i, i32 slot_ch, bool he, i64 ix_rand, i64 row_abs, i32 dch = -1)
 {
+    if constexpr (DK) { if (dch >= 0) acc_i += dark_sample(d, dch, row_abs + i); }
     const bool noisy = NK != 0 && (NK >= 3 || d.enable_noise) && slot_ch < d.noise_channels;
     i32 nz = 0; double nzf = 0;
     if (noisy) {
@@ -1964,10 +2073,10 @@ __device__ __forceinline__ i32 finish_sample_of(const WfsDev &d, i32 acc_i, i64 
     }
     return finish_value<NK>(d, acc_i, he, noisy, nz, nzf);
 }
-template <int NK>
-__device__ __forceinline__ i32 finish_sample(const WfsDev &d, const i32 *acc, i64 i, i32 slot_ch, bool he, i64 ix_rand, i64 row_abs)
+template <int NK, bool DK = false>
+__device__ __forceinline__ i32 finish_sample(const WfsDev &d, const i32 *acc, i64 i, i32 slot_ch, bool he, i64 ix_rand, i64 row_abs, i32 dch = -1)
 {
-    return finish_sample_of<NK>(d, acc[i], i, slot_ch, he, ix_rand, row_abs);
+    return finish_sample_of<NK, DK>(d, acc[i], i, slot_ch, he, ix_rand, row_abs, dch);
 }
 
 // The same in two steps, for loops that want ALL their loads in flight before the first use: with the load inside finish_sample
@@ -1986,12 +2095,13 @@ __device__ __forceinline__ const void *noise_row_of(const WfsDev &d, i32 channel
 template <int NK> struct RawSample { i32 acc; i32 nz; };
 template <> struct RawSample<0> { i32 acc; };
 template <> struct RawSample<2> { i32 acc; double nzf; };
-template <int NK>
-__device__ __forceinline__ RawSample<NK> load_sample(const WfsDev &d, const i32 *acc, i32 i, const void *noise_row, u32 nstart, u32 noff, i32 channel = 0, i64 row_abs = 0)
+template <int NK, bool DK = false>
+__device__ __forceinline__ RawSample<NK> load_sample(const WfsDev &d, const i32 *acc, i32 i, const void *noise_row, u32 nstart, u32 noff, i32 channel = 0, i64 row_abs = 0, i32 dch = -1)
 {
     // (32-bit offsets from wave-uniform row pointers: the address arithmetic is one add per load, the bases stay in SGPRs)
     // noise sample nstart + noff of the row, nstart < noise_len a scalar, noff < noise_len (noise_wrap)
     RawSample<NK> s; s.acc = acc[(u32)i];
+    if constexpr (DK) { if (dch >= 0) s.acc += dark_sample(d, dch, row_abs + i); }      // (dch is wave-uniform)
     if constexpr (NK == 3) s.nz = noise_row ? noise_model_sample(d, (const uint2 *)noise_row, channel, row_abs + i) : 0;      // (wave-uniform)
     else if constexpr (NK == 4 || NK == 5) s.nz = noise_row ? noise_colour_sample<NK == 5>(d, channel, row_abs + i) : 0;
     else if constexpr (NK != 0) {
@@ -2133,7 +2243,7 @@ struct ZleChunks {
 
 // one wave per row: find_intervals_below_threshold (utils.py:13-58) in its parallel form: consecutive
 // hit samples a < b belong to one interval iff b - a <= max(holdoff, 1); then the window of rawdata.py:302-308.
-template <int NK>
+template <int NK, bool DK>
 __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
 {
     const int lane = threadIdx.x & 63;
@@ -2147,6 +2257,7 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
     const i64 base = q.itv_base;
     const i64 row_abs = q.row_abs;
     const i32 len32 = q.len, hold32 = (i32)zle_holdoff(d.tw);
+    const i32 dch = DK ? dark_channel_of(d, channel, he) : -1;
     ZleChunks zc;                                           // (the general path)
     const bool noisy = NK != 0 && channel < d.noise_channels;
     // the noise index of a row's sample i is (ix + i) mod noise_len (rawdata.py:433-434): a scalar start per block of samples that
@@ -2184,6 +2295,8 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
                 } else
                 buf[u] = load_four<NK>(d, acc, i < len32 ? i : 0, noise_row, NK >= 4 ? (u32)(g0 + 256 * u) : nrun, lane, channel, row_abs);
                 if constexpr (TABLE) nrun = noise_advance(nrun, 256u, (u32)d.noise_len);
+                // (the dark counts of the block's own samples, whatever the clamped load read: a lane past the row drops both)
+                if constexpr (DK) { if (dch >= 0 && g0 + 256 * u < len32) dark_block(d, dch, row_abs + g0 + 256 * u, lane, buf[u].acc); }
             }
         };
         auto look = [&](const Raw4<NK> *buf, i32 g0) {
@@ -2213,14 +2326,14 @@ __global__ __launch_bounds__(256) void k_zle(WfsDev d, ZleArgs a)
 #pragma unroll
             for (int u = 0; u < ZLE_GROUP; u++) {
                 const i32 i = g0 + 64 * u + lane;
-                rs[u] = load_sample<NK>(d, acc, i < len32 ? i : len32 - 1, noise_row, nrun1, (u32)lane, channel, row_abs);
+                rs[u] = load_sample<NK, DK>(d, acc, i < len32 ? i : len32 - 1, noise_row, nrun1, (u32)lane, channel, row_abs, dch);
                 if constexpr (TABLE) nrun1 = noise_advance(nrun1, 64u, (u32)d.noise_len);
             }
 #pragma unroll
             for (int u = 0; u < ZLE_GROUP; u++) { const i32 i = g0 + 64 * u + lane; vv[u] = i < len32 ? finish_loaded(d, rs[u], he, noisy) : 0x7fffffff; }
         } else {
 #pragma unroll
-            for (int u = 0; u < ZLE_GROUP; u++) { const i32 i = g0 + 64 * u + lane; vv[u] = i < len32 ? finish_sample<NK>(d, acc, i, channel, he, ixr, row_abs) : 0x7fffffff; }
+            for (int u = 0; u < ZLE_GROUP; u++) { const i32 i = g0 + 64 * u + lane; vv[u] = i < len32 ? finish_sample<NK, DK>(d, acc, i, channel, he, ixr, row_abs, dch) : 0x7fffffff; }
         }
         if (a.row_dbg) {
 #pragma unroll
@@ -2319,7 +2432,7 @@ __global__ __launch_bounds__(256) void k_sum_signal(WfsDev d, SumArgs a)
 // (noise, baseline, clamp: rawdata.py:398-458), runs the zero-length encoding on them and writes them ONCE, as 16-bit samples.
 // Against the accumulator path (memset 4 B + atomics + 6 B read by k_zle + 6 B read by k_pack per sample) a row costs 2 B of noise
 // read and 2 B written here and 2 B read by k_pack.  rawdata.py:231-239 (per-pulse rounding into the row), :302-311 (intervals).
-template <int NK, bool FMA, bool SEG>
+template <int NK, bool FMA, bool SEG, bool DK>
 __global__ __launch_bounds__(256) void k_row_pulse(WfsDev d, PulseArgs a, ZleArgs z, i64 first, i64 n_res, i32 region)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char row_lds[];
@@ -2341,6 +2454,7 @@ __global__ __launch_bounds__(256) void k_row_pulse(WfsDev d, PulseArgs a, ZleArg
     const i32 thr32 = zle_thr32(thr);
     const i32 hold32 = (i32)zle_holdoff(d.tw);
     const bool noisy = NK != 0 && q.channel < d.noise_channels;
+    const i32 dch = DK ? dark_channel_of(d, q.channel, false) : -1;
     const void *noise_row = noise_row_of<NK>(d, q.channel, noisy);
     u32 nrun = (noisy && NK < 3) ? (u32)q.ixr : 0u;       // noise index of the next block's first sample (rawdata.py:433-434); kinds 3, 4: that sample's index in the row
     int16_t *fin = z.fin + q.acc_off;
@@ -2385,6 +2499,7 @@ __global__ __launch_bounds__(256) void k_row_pulse(WfsDev d, PulseArgs a, ZleArg
             Raw4<NK> nxt = s4;
             if (i - 4 * lane + 256 < len32) load_noise(nxt);      // the next block's noise on its way under this block's arithmetic
             *(int4 *)s4.acc = *(const int4 *)(acc + b0 + 4 * lane);
+            if constexpr (DK) { if (dch >= 0) dark_block(d, dch, row_abs + seg0 + b0, lane, s4.acc); }      // (every lane of the wave is here)
             u32 nib = 0; u32 v16[4];
             if constexpr (NK == 2) {
 #pragma unroll
@@ -2428,7 +2543,7 @@ __device__ __forceinline__ u64 spread16_by4(u64 x)      // bit k of the low 16 -
     x = (x | (x << 6)) & 0x0303030303030303ull; x = (x | (x << 3)) & 0x1111111111111111ull;
     return x;
 }
-template <int NK>
+template <int NK, bool DK>
 __global__ __launch_bounds__(256) void k_row_empty(WfsDev d, ZleArgs a, i64 first, i64 n_rows)
 {
     const int lane = threadIdx.x & 63;
@@ -2442,6 +2557,7 @@ __global__ __launch_bounds__(256) void k_row_empty(WfsDev d, ZleArgs a, i64 firs
     const bool noisy = NK != 0 && channel < d.noise_channels;
     constexpr bool TABLE = NK == 1 || NK == 2;
     const bool fast_noise = !TABLE || d.noise_len >= NOISE_MIN_FAST;      // (a shorter table wraps more than once inside a block: sample by sample, as k_zle)
+    const i32 dch = DK ? dark_channel_of(d, channel, he) : -1;
     const void *noise_row = noise_row_of<NK>(d, channel, noisy);
     u32 nrun = (noisy && TABLE) ? (u32)ixr : 0u;            // tables: noise index of the block's first sample (rawdata.py:433-434); drawn kinds: its index in the row
     ZleChunks zc;
@@ -2452,11 +2568,12 @@ __global__ __launch_bounds__(256) void k_row_empty(WfsDev d, ZleArgs a, i64 firs
             Raw4<NK> s4;
             s4.acc[0] = s4.acc[1] = s4.acc[2] = s4.acc[3] = 0;
             noise_four<NK>(d, s4, noise_row, channel, row_abs, nrun, lane);
+            if constexpr (DK) { if (dch >= 0) dark_block(d, dch, row_abs + b0, lane, s4.acc); }
 #pragma unroll
             for (int j = 0; j < 4; j++) v[j] = finish_four<NK>(d, s4, j, he, noisy);
         } else {
 #pragma unroll
-            for (int j = 0; j < 4; j++) v[j] = i + j < len32 ? finish_sample_of<NK>(d, 0, (i64)(i + j), channel, he, ixr, row_abs) : 0;
+            for (int j = 0; j < 4; j++) v[j] = i + j < len32 ? finish_sample_of<NK, DK>(d, 0, (i64)(i + j), channel, he, ixr, row_abs, dch) : 0;
         }
         if constexpr (TABLE) nrun = fast_noise ? noise_advance(nrun, 256u, (u32)d.noise_len) : 0u; else nrun += 256u;
         u32 nib = 0;
@@ -2573,7 +2690,7 @@ __global__ __launch_bounds__(256) void k_pack_res(PackResArgs a)
 // one wave per row: write its intervals as strax raw_records (strax_interface.py:425-435).  A record is 24 bytes of header and
 // samples_per_record int16: lane q writes dword q of the record (61 dwords with 110 samples: three idle lanes, no division by the
 // record length anywhere), PACK_U records in flight so that the loads of one do not wait behind the stores of the one before.
-template <int NK>
+template <int NK, bool DK>
 __global__ __launch_bounds__(256) void k_pack(WfsDev d, ZleArgs a)
 {
     const int lane = threadIdx.x & 63;
@@ -2591,6 +2708,7 @@ __global__ __launch_bounds__(256) void k_pack(WfsDev d, ZleArgs a)
     constexpr int spr = WFS_SPR; constexpr int rec_dwords = REC_DWORDS;
     const i64 rec_bytes = WFS_RECORD_BYTES;
     const bool noisy = NK != 0 && channel < d.noise_channels;
+    const i32 dch = DK ? dark_channel_of(d, channel, he) : -1;
     constexpr bool TABLE = NK == 1 || NK == 2;
     const bool fast_loads = !TABLE || (d.noise_len >= NOISE_MIN_FAST && spr <= NOISE_MIN_FAST / 2);       // (as in k_zle: a scalar noise start per record)
     const u32 nixr = noisy ? (u32)ixr : 0u;
@@ -2619,7 +2737,7 @@ __global__ __launch_bounds__(256) void k_pack(WfsDev d, ZleArgs a)
                         i32 i0 = off + rec_fragment_first(f) + (i32)noff;
                         i0 = i0 > len32 - 1 ? len32 - 1 : i0;       // (lanes past the record's samples read a valid sample and drop it)
                         const i32 i1 = i0 + 1 > len32 - 1 ? len32 - 1 : i0 + 1;
-                        lo[u] = load_sample<NK>(d, acc, i0, noise_row, nrun, noff, channel, row_abs); hi[u] = load_sample<NK>(d, acc, i1, noise_row, nrun, noff + 1u, channel, row_abs);
+                        lo[u] = load_sample<NK, DK>(d, acc, i0, noise_row, nrun, noff, channel, row_abs, dch); hi[u] = load_sample<NK, DK>(d, acc, i1, noise_row, nrun, noff + 1u, channel, row_abs, dch);
                         if constexpr (TABLE) nrun = noise_advance(nrun, (u32)spr, (u32)d.noise_len);
                     }
                 }
@@ -2637,8 +2755,8 @@ __global__ __launch_bounds__(256) void k_pack(WfsDev d, ZleArgs a)
                         if (fast_loads) { vlo = (u32)(uint16_t)finish_loaded(d, lo[u], he, noisy); vhi = (u32)(uint16_t)finish_loaded(d, hi[u], he, noisy); }
                         else {
                             const i64 i0 = (i64)off + rec_fragment_first(f) + s0;
-                            vlo = s0 < length ? (u32)(uint16_t)finish_sample<NK>(d, acc, i0, channel, he, ixr, row_abs) : 0u;
-                            vhi = s0 + 1 < length ? (u32)(uint16_t)finish_sample<NK>(d, acc, i0 + 1, channel, he, ixr, row_abs) : 0u;
+                            vlo = s0 < length ? (u32)(uint16_t)finish_sample<NK, DK>(d, acc, i0, channel, he, ixr, row_abs, dch) : 0u;
+                            vhi = s0 + 1 < length ? (u32)(uint16_t)finish_sample<NK, DK>(d, acc, i0 + 1, channel, he, ixr, row_abs, dch) : 0u;
                         }
                         w = (s0 < length ? vlo : 0u) | ((s0 + 1 < length ? vhi : 0u) << 16);
                     }

@@ -111,7 +111,8 @@ EXPORTS = ['wfs_create', 'wfs_destroy', 'wfs_last_error', 'wfs_device_count', 'w
            'wfs_scalar_map_grid', 'wfs_scalar_map_points', 'wfs_scalar_map_spline', 'wfs_scalar_map_eval', 'wfs_set_noise_float', 'wfs_set_instruction_diffusion',
            'wfs_scalar_map_grid_array', 'wfs_scalar_map_points_array', 'wfs_scalar_map_linear', 'wfs_scalar_map_eval_array',
            'wfs_set_sum_signal', 'wfs_copy_sum_signal', 'wfs_set_full_readout', 'wfs_device_allocations',
-           'wfs_set_noise_model', 'wfs_noise_model_samples', 'wfs_copy_noise_model', 'wfs_set_noise_colour', 'wfs_noise_white_samples', 'wfs_set_noise_slow', 'wfs_noise_slow_samples']
+           'wfs_set_noise_model', 'wfs_noise_model_samples', 'wfs_copy_noise_model', 'wfs_set_noise_colour', 'wfs_noise_white_samples', 'wfs_set_noise_slow', 'wfs_noise_slow_samples',
+           'wfs_set_dark_counts', 'wfs_dark_count_samples', 'wfs_dark_count_photons', 'wfs_copy_dark_counts']
 
 
 def load_library():
@@ -250,6 +251,12 @@ class Engine:
                 self.set_noise_colour(**self.noise_colour)
             if self.noise_slow is not None:
                 self.set_noise_slow(**self.noise_slow)
+        # PMT dark counts (config 'dark_count_rate', dark_counts.py; the library's default is off)
+        from .dark_counts import rates_from
+        self.dark_count_rate = None
+        rates = rates_from(config, params['n_tpc'])
+        if rates is not None:
+            self.set_dark_counts(rates)
         he_noise = bool(params['enable_noise']) and nc > params['he_first']
         self.emits_he_records = bool(params['detector_nt'] and params['n_top'] > 0 and (params['he_factor'] != 0 or he_noise))
         # pattern maps on regular grids are evaluated on the device (one channel CDF row per instruction)
@@ -758,6 +765,48 @@ class Engine:
         out = np.zeros(int(n), dtype=np.int16)
         self._check(self.lib.wfs_noise_model_samples(self._h, C.c_int32(int(channel)), C.c_int64(int(t0)), C.c_int64(int(n)), _p(out)))
         return out
+
+    def set_dark_counts(self, rate_hz):
+        """PMT dark counts between runs (wfs_set_dark_counts): a rate in Hz for every PMT, or one value per channel for the
+        first len(rate_hz) of them; None (or rates that are all zero) switches them off.  From the next ``run()`` every finished
+        sample of a TPC or HE row carries the single-electron pulses its PMT makes on its own, a pure function of (seed, channel,
+        absolute time); windows, truth and record order do not change, the sum row carries none."""
+        if rate_hz is None:
+            self._check(self.lib.wfs_set_dark_counts(self._h, C.c_int32(0), C.c_void_p(0)))
+            self.dark_count_rate = None
+            return
+        r = np.asarray(rate_hz, dtype=np.float64)
+        if r.ndim == 0:
+            r = np.full(self.params['n_tpc'], float(r))
+        r = np.ascontiguousarray(r.ravel())
+        self._check(self.lib.wfs_set_dark_counts(self._h, C.c_int32(len(r)), _p(r)))
+        self.dark_count_rate = r.copy() if np.any(r > 0) else None
+
+    def dark_count_samples(self, channel, t0, n):
+        """D(channel, t0 .. t0 + n - 1): what the dark counts of a PMT add to its accumulated ADC at the absolute samples (time / dt),
+        evaluated on the device"""
+        out = np.zeros(int(n), dtype=np.int32)
+        self._check(self.lib.wfs_dark_count_samples(self._h, C.c_int32(int(channel)), C.c_int64(int(t0)), C.c_int64(int(n)), _p(out)))
+        return out
+
+    def dark_count_photons(self, channel, t0, n):
+        """(t_ns int64[k], gain float64[k]) of the dark photons of a PMT whose pulse starts at a sample in [t0, t0 + n), in time order:
+        the truth does not hold them, this is how a hit is matched to a dark count"""
+        cap = 64
+        while True:
+            t, g, k = np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.float64), C.c_int64(0)
+            rc = self.lib.wfs_dark_count_photons(self._h, C.c_int32(int(channel)), C.c_int64(int(t0)), C.c_int64(int(n)), _p(t), _p(g), C.c_int64(cap), C.byref(k))
+            if rc == -3 and k.value > cap:          # (WFS_E_CAPACITY: the count is known now)
+                cap = int(k.value)
+                continue
+            self._check(rc)
+            return t[:k.value].copy(), g[:k.value].copy()
+
+    def dark_count_thresholds(self, channel):
+        """uint32[4]: floor(2^32 P(N >= k)), k = 1 .. 4, of the channel's photons per cell of 64 samples, as the device holds them"""
+        thr = np.zeros(4, dtype=np.uint32)
+        self._check(self.lib.wfs_copy_dark_counts(self._h, C.c_int32(int(channel)), _p(thr)))
+        return thr
 
     def noise_model_cells(self, channel):
         """the Walker alias cells the device samples a channel's noise from: dict(thr, alias, shift, vmin); cell c = word >> shift gives

@@ -46,6 +46,21 @@ def full_readout_records(config, params, s_ins):
     return slots * np.ceil(window / 110.0)
 
 
+def dark_count_records(config, params, s_ins, quanta):
+    """Records per instruction that ``config['dark_count_rate']`` adds, an ESTIMATE as ``full_readout_records`` is one: a
+    dark photon outside the signal is an interval of its own, one record; the rows are every row slot under full readout, else a row
+    per quantum up to the PMTs of the array, the window that of ``full_readout_records``, the rate the mean over the PMTs."""
+    from .dark_counts import rates_from
+    rates = rates_from(config, params['n_tpc'])
+    if rates is None:
+        return 0.0
+    n_tpc = int(params['n_tpc'])
+    rows = np.full(len(s_ins), float(n_tpc)) if config.get('full_readout', False) else np.minimum(quanta, n_tpc)
+    window = (2 * int(params['trigger_window']) + int(params['store_before']) + int(params['store_after']) + int(params['tlen'])
+              + np.where(s_ins['type'] == 1, 30, 300))
+    return rows * window * int(params['dt']) * 1e-9 * float(rates.sum()) / n_tpc
+
+
 class RawData:
     #: upper bound on the expected photons of one GPU batch (sizes the HBM arenas; 288 GB HBM3E leaves room for ~10^10)
     max_batch_quanta = 2_000_000_000
@@ -291,6 +306,8 @@ class RawData:
         rec = np.minimum(q, 5 * len(self.config.get('gains', np.zeros(494))) + q / 400)
         if self.config.get('full_readout', False):
             rec = rec + full_readout_records(self.config, self.engine.params, s_ins)
+        if self.config.get('dark_count_rate') is not None:
+            rec = rec + dark_count_records(self.config, self.engine.params, s_ins, q)
         return rec
 
     def _load_batch(self, ins, gid, cl, key):

@@ -624,6 +624,9 @@ class RawRecordsFromFaxnVeto(RawRecordsFromFaxOpticalNT):
         overrides = c.get('fax_config_override_nveto') or c.get('fax_config_override')
         if overrides:
             c.update(overrides)
+        # PMT dark counts: the veto tubes have rates of their own, under a key of their own
+        if 'dark_count_rate_nveto' in c:
+            c['dark_count_rate'] = c['dark_count_rate_nveto']
         if 'gains' not in c:
             to_pe = np.asarray(c['to_pe_nveto'], dtype=np.float64)
             # strax_interface.py:776: nveto digitiser 2 V range, 14 bit, 50 Ohm, 2 ns sampling constant
@@ -691,6 +694,9 @@ class RawRecordsFromMcChain(SimulatorPlugin):
             import copy
             skip = ('instructions_epix', 'instructions_nveto', 'nveto_channels', 'nveto_timings')
             cn = {k: (v if k in skip else copy.deepcopy(v)) for k, v in self.config.items()}
+            # PMT dark counts: 'dark_count_rate' is the TPC engine's (one value per TPC PMT); the veto engine reads
+            # 'dark_count_rate_nveto' (or a 'dark_count_rate' inside fax_config_nveto) and has none otherwise
+            cn['dark_count_rate'] = cn.pop('dark_count_rate_nveto', None)
             cn.update(self.config.get('fax_config_nveto') or {})
             cn['detector'] = 'XENONnT_neutron_veto'
             cn['channel_map'] = dict(cn['channel_map'])
