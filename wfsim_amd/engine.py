@@ -1,25 +1,25 @@
 """ctypes binding of libwfsim_amd.so (include/wfsim_amd.h) -- the only way the Python host side reaches the GPU.
 
+Signatures, struct layouts and the export list come from the header (abi.py): scalars are passed as plain numbers, input arrays as
+any array-like (converted to the header's element type for the duration of the call), output arrays as ndarrays of exactly the
+header's element type, and a mismatch is a TypeError before the library is entered.
+
 There is no CPU fallback: if the HIP library is missing, fails to load, or no MI355X is visible, constructing an
 ``Engine`` raises.  Nothing in this module (or anywhere under wfsim_amd/) imports the test oracle.
 """
 import ctypes as C
+import dataclasses
 import os
 
 import numpy as np
 
+from .abi import EXPORTS, WfsConfig, WfsCounts, WfsError, bind          # noqa: F401 (the names other modules and the tests take from here)
 from .config import kernel_params, N_ROWS
 from .dtypes import raw_record_dtype
 from . import tables as T
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('WFSIM_AMD_LIB') or os.path.join(HERE, 'libwfsim_amd.so')
-
-_I32 = ['dt', 'samples_before', 'samples_after', 'store_before', 'store_after', 'tlen', 'trigger_window', 'baseline',
-        'n_rows', 'n_tpc', 'n_top', 'he_first', 'he_factor', 'sum_channel', 'last_bottom', 'detector_nt', 'enable_noise',
-        's1_simple', 's2_time_model', 'enable_pmt_ap', 'tile_gen', 'tile_gen_min', 'fma', 'row_resident']
-_F64 = ['c2a', 'tts_mean', 'tts_sigma', 'p_dpe', 's1_decay_time', 's1_decay_spread', 'sf_gas', 't1_gas', 't3_gas',
-        's2_time_spread', 'trap_time', 'gain_spread', 'pmt_ap_modifier', 'pmt_ap_t_modifier', 'rext', 'drift_velocity']
 
 
 def pin_host(array):
@@ -28,11 +28,11 @@ def pin_host(array):
     a = np.asarray(array)
     if a.nbytes == 0 or not a.flags['C_CONTIGUOUS']:
         return False
-    return load_library().wfs_host_register(C.c_void_p(a.ctypes.data), C.c_int64(a.nbytes)) == 0
+    return load_library().wfs_host_register(a.ctypes.data, a.nbytes) == 0
 
 
 def unpin_host(array):
-    load_library().wfs_host_unregister(C.c_void_p(np.asarray(array).ctypes.data))
+    load_library().wfs_host_unregister(np.asarray(array).ctypes.data)
 
 
 _RECORD_BUFFERS = []        # [array, in use]: page-locked record buffers, recycled between chunkers
@@ -85,38 +85,12 @@ def lease_record_buffer(buf, n):
     return arr
 
 
-class WfsConfig(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in _I32] + [(n, C.c_double) for n in _F64] + [('seed', C.c_uint64)]
-
-
-class WfsCounts(C.Structure):
-    _fields_ = [(n, C.c_int64) for n in ['n_instructions', 'n_pulse_sets', 'n_emitters', 'n_photons', 'n_pe', 'n_tiles',
-                                         'n_groups', 'n_rows', 'n_raw_samples', 'n_intervals', 'n_records']]
-
-
-class WfsError(RuntimeError):
-    pass
-
-
 _lib = None
-EXPORTS = ['wfs_create', 'wfs_destroy', 'wfs_last_error', 'wfs_device_count', 'wfs_set_tables', 'wfs_set_ap_element',
-           'wfs_load_instructions', 'wfs_load_photons', 'wfs_load_optical', 'wfs_run', 'wfs_get_counts', 'wfs_copy_records',
-           'wfs_copy_records_dev', 'wfs_records_dev_ptr', 'wfs_copy_groups', 'wfs_copy_intervals',
-           'wfs_copy_interval_data', 'wfs_copy_pulses', 'wfs_copy_currents', 'wfs_copy_rows', 'wfs_copy_row_data',
-           'wfs_copy_photons', 'wfs_copy_truth', 'wfs_copy_truth_per_pmt', 'wfs_copy_instruction_photon_offsets', 'wfs_gather_photon_times', 'wfs_copy_electron_stats', 'wfs_set_window_carry', 'wfs_copy_cluster_groups', 'wfs_set_noise_offsets', 'wfs_set_debug', 'wfs_set_stream', 'wfs_synchronize',
-           'wfs_kernel_times', 'wfs_set_profiling', 'wfs_set_bright_tiles', 'wfs_copy_tile_kernels', 'wfs_set_delay_models', 'wfs_set_s1_propagation', 'wfs_set_instruction_models',
-           'wfs_set_pattern_map', 'wfs_eval_pattern_rows', 'wfs_copy_cdf_rows', 'wfs_set_record_order', 'wfs_copy_records_range',
-           'wfs_copy_records_range_async', 'wfs_wait_records', 'wfs_host_register', 'wfs_host_unregister',
-           'wfs_set_gas_gap_model', 'wfs_set_instruction_gas_gap', 'wfs_set_pattern_map_points', 'wfs_set_instruction_aft',
-           'wfs_scalar_map_grid', 'wfs_scalar_map_points', 'wfs_scalar_map_spline', 'wfs_scalar_map_eval', 'wfs_set_noise_float', 'wfs_set_instruction_diffusion',
-           'wfs_scalar_map_grid_array', 'wfs_scalar_map_points_array', 'wfs_scalar_map_linear', 'wfs_scalar_map_eval_array',
-           'wfs_set_sum_signal', 'wfs_copy_sum_signal', 'wfs_set_full_readout', 'wfs_device_allocations',
-           'wfs_set_noise_model', 'wfs_noise_model_samples', 'wfs_copy_noise_model', 'wfs_set_noise_colour', 'wfs_noise_white_samples', 'wfs_set_noise_slow', 'wfs_noise_slow_samples',
-           'wfs_set_dark_counts', 'wfs_dark_count_samples', 'wfs_dark_count_photons', 'wfs_copy_dark_counts']
 
 
 def load_library():
-    """Loads libwfsim_amd.so; raises if it is missing (build it with ``python -c "import __graft_entry__ as g; g.build()"``)."""
+    """Loads libwfsim_amd.so and gives every entry point the restype and argtypes of the header; raises if it is missing (build it
+    with ``python -c "import __graft_entry__ as g; g.build()"``)."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -129,15 +103,7 @@ def load_library():
                 sys.modules['torch'].cuda.init()
             except Exception:
                 pass
-        lib = C.CDLL(LIB_PATH)
-        for name in EXPORTS:
-            getattr(lib, name)          # AttributeError if a declared symbol is missing
-        lib.wfs_last_error.restype = C.c_char_p
-        lib.wfs_last_error.argtypes = [C.c_void_p]
-        lib.wfs_records_dev_ptr.restype = C.c_void_p
-        lib.wfs_records_dev_ptr.argtypes = [C.c_void_p]
-        lib.wfs_device_allocations.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        _lib = lib
+        _lib = bind(C.CDLL(LIB_PATH))          # AttributeError if a declared symbol is missing
     return _lib
 
 
@@ -149,19 +115,20 @@ def device_count():
 
 def device_allocations():
     """(buffers, bytes) of device memory that the engines of this process hold now; every ``close()`` gives its share back."""
-    n, b = C.c_int64(0), C.c_int64(0)
-    rc = load_library().wfs_device_allocations(C.byref(n), C.byref(b))
+    n, b = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64)
+    rc = load_library().wfs_device_allocations(n, b)
     if rc != 0:
         raise WfsError(f'wfs_device_allocations failed ({rc})')
-    return n.value, b.value
-
-
-def _p(a):
-    return C.c_void_p(a.ctypes.data) if a is not None else C.c_void_p(0)
+    return int(n[0]), int(b[0])
 
 
 def _arr(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
+
+
+def _grid(grid):
+    """(nodes per axis, first node, last node) of a regular grid, as the map entry points take it"""
+    return [len(g) for g in grid], [g[0] for g in grid], [g[-1] for g in grid]
 
 
 def first_instruction_of_sets(run_set, n_sets):
@@ -175,6 +142,16 @@ def first_instruction_of_sets(run_set, n_sets):
     first = np.full(n_sets, n, dtype=np.int64)
     np.minimum.at(first, run_set, np.arange(n))
     return first if np.all(first < n) else None
+
+
+@dataclasses.dataclass
+class Batch:
+    """What Python knows of the loaded batch.  Every load_* replaces it whole, as the library replaces its batch (wfs_batch.h)."""
+    n_loaded: int = 0               # instructions
+    n_cdf_rows: int = 0             # rows of the channel CDF table, device-evaluated ones included
+    n_run_sets: object = None       # run sets of the caller (None: a batch without: optical input, injected photons)
+    set_rows: object = None         # the library's row of every run set of the caller (None: the library's own rows, in order)
+    lib_sets: int = 0               # the library's pulse-set rows of the last run (run sets numbered by their first instruction leave gaps)
 
 
 class Engine:
@@ -196,9 +173,25 @@ class Engine:
         self._h = C.c_void_p(0)
         self.device = int(device)
         self._pinned = []
-        rc = self.lib.wfs_create(C.byref(cfg), C.c_int(device), C.byref(self._h))
+        self._batch = Batch()
+        self._smap_nv = {}              # values per node of every array-valued scalar map
+        self._noise_rows = None         # (channels, common streams) of the noise model that is set
+        rc = self.lib.wfs_create(C.byref(cfg), device, C.byref(self._h))
         if rc != 0:
             raise WfsError(f'wfs_create failed with code {rc}: no usable MI355X / HIP runtime (device {device})')
+        nl, nc = self._init_tables(resource)
+        self._init_ap_elements(resource)
+        nc = self._init_switches_and_noise(resource, nl, nc)
+        self._init_dark_counts()
+        he_noise = bool(params['enable_noise']) and nc > params['he_first']
+        self.emits_he_records = bool(params['detector_nt'] and params['n_top'] > 0 and (params['he_factor'] != 0 or he_noise))
+        self._init_pattern_maps(resource)
+        self._init_scalar_maps(resource)
+        self._init_delay_models(resource)
+
+    def _init_tables(self, resource):
+        """uploads the init-time tables; returns the shape of the noise array (0, 0 without one)"""
+        config, params = self.config, self.params
         thr_truth, thr_zle = T.thresholds(config, N_ROWS)
         lum_x, lum_t = T.luminescence_table(config)
         # a noise model (noise_model.py) takes precedence over the noise array of the resource, which is then not uploaded
@@ -214,21 +207,25 @@ class Engine:
         t = self.tables
         assert t['templates'].shape == (params['dt'], params['tlen'])
         nl, nc = t['noise'].shape if t['noise'] is not None else (0, 0)
-        self._check(self.lib.wfs_set_tables(
-            self._h, _p(t['templates']), _p(t['spe']), C.c_int32(t['spe'].shape[0]), _p(t['gains']), _p(t['thr_truth']),
-            _p(t['thr_zle']), _p(t['lum_x']), _p(t['lum_t']), C.c_int32(len(t['lum_x'])), _p(t['noise']), C.c_int32(nl), C.c_int32(nc)))
-        if params['enable_pmt_ap'] and hasattr(resource, 'uniform_to_pmt_ap'):
+        self._call('wfs_set_tables', t['templates'], t['spe'], t['spe'].shape[0], t['gains'], t['thr_truth'], t['thr_zle'],
+                   t['lum_x'], t['lum_t'], len(t['lum_x']), t['noise'], nl, nc)
+        return nl, nc
+
+    def _init_ap_elements(self, resource):
+        if self.params['enable_pmt_ap'] and hasattr(resource, 'uniform_to_pmt_ap'):
             for e, (name, d) in enumerate(resource.uniform_to_pmt_ap.items()):
                 dc, ac = _arr(d['delaytime_cdf'], np.float64), _arr(d['amplitude_cdf'], np.float64)
-                self._check(self.lib.wfs_set_ap_element(
-                    self._h, C.c_int32(e), C.c_int32(dc.shape[1]), C.c_int32(ac.shape[-1]), C.c_int32(ac.ndim == 2),
-                    C.c_int32('Uniform' in name), C.c_double(d['delaytime_bin_size']), C.c_double(d['amplitude_bin_size']), _p(dc), _p(ac)))
+                self._call('wfs_set_ap_element', e, dc.shape[1], ac.shape[-1], ac.ndim == 2, 'Uniform' in name,
+                           d['delaytime_bin_size'], d['amplitude_bin_size'], dc, ac)
 
+    def _init_switches_and_noise(self, resource, nl, nc):
+        """the handle's switches, then the noise source; returns the channels of that source (nc of the noise array, or the model's)"""
+        params, t = self.params, self.tables
         self.tile_local_bright = bool(params['tile_local_bright'])
         if not self.tile_local_bright:         # (the library's default is on)
-            self._check(self.lib.wfs_set_bright_tiles(self._h, C.c_int32(0)))
+            self._call('wfs_set_bright_tiles', 0)
         # the bottom-array sum channel (config 'emit_sum_signal'; the library's default is off): XENONnT only (rawdata.py:241)
-        self._check(self.lib.wfs_set_sum_signal(self._h, C.c_int32(params['sum_signal'])))
+        self._call('wfs_set_sum_signal', params['sum_signal'])
         self.emits_sum_records = bool(params['sum_signal'] and params['detector_nt'])
         # every channel of a digitise window, not only the hit ones (config 'full_readout'; the library's default is off)
         self.full_readout = False
@@ -241,8 +238,7 @@ class Engine:
                 and not np.array_equal(np.asarray(resource.noise_data), np.trunc(resource.noise_data)):
             # a float noise array with non-integral values: numba's `int64 row += float64 noise` (rawdata.py:436) stores the
             # truncated SUM, which the int16 table cannot express -- the device then adds in f64 and truncates as well
-            nf = _arr(resource.noise_data, np.float64)
-            self._check(self.lib.wfs_set_noise_float(self._h, _p(nf), C.c_int32(nl), C.c_int32(nc)))
+            self._call('wfs_set_noise_float', resource.noise_data, nl, nc)
         # int(high_energy_deamplification_factor) (rawdata.py:242) or noise columns for the HE channels
         if self.noise_model is not None:
             self.set_noise_model(*self.noise_model)
@@ -251,15 +247,19 @@ class Engine:
                 self.set_noise_colour(**self.noise_colour)
             if self.noise_slow is not None:
                 self.set_noise_slow(**self.noise_slow)
+        return nc
+
+    def _init_dark_counts(self):
         # PMT dark counts (config 'dark_count_rate', dark_counts.py; the library's default is off)
         from .dark_counts import rates_from
         self.dark_count_rate = None
-        rates = rates_from(config, params['n_tpc'])
+        rates = rates_from(self.config, self.params['n_tpc'])
         if rates is not None:
             self.set_dark_counts(rates)
-        he_noise = bool(params['enable_noise']) and nc > params['he_first']
-        self.emits_he_records = bool(params['detector_nt'] and params['n_top'] > 0 and (params['he_factor'] != 0 or he_noise))
+
+    def _init_pattern_maps(self, resource):
         # pattern maps on regular grids are evaluated on the device (one channel CDF row per instruction)
+        config, params = self.config, self.params
         self.device_maps = set()
         if config.get('device_pattern_maps', True):
             from .itp_map import InterpolatingMap
@@ -276,13 +276,12 @@ class Engine:
                     continue
                 if pm.grid is None:           # a point list (irregular coordinate system): brute-force neighbour search on the device
                     vals = np.asarray(pm.data['map'])
-                    pts = np.ascontiguousarray(pm.coordinate_system, dtype=np.float64)
+                    pts = pm.coordinate_system
                     if vals.ndim != 2 or len(vals) != len(pts) or vals.shape[1] > params['n_tpc'] or len(pts) < 2 * dims:
                         continue
                     if kind == 's2' and vals.shape[1] != params['n_tpc'] and (vals.shape[1] - 1) in np.asarray(config['channels_bottom']):
                         continue
-                    v = np.ascontiguousarray(vals, dtype=np.float32)
-                    self._check(self.lib.wfs_set_pattern_map_points(self._h, C.c_int32(which), C.c_int32(dims), C.c_int64(len(pts)), _p(pts), _p(v), C.c_int32(v.shape[1])))
+                    self._call('wfs_set_pattern_map_points', which, dims, len(pts), pts, vals, vals.shape[1])
                     self.device_maps.add(kind)
                     continue
                 grid, vals = pm.regular_grid()
@@ -290,36 +289,47 @@ class Engine:
                     continue
                 if kind == 's2' and vals.shape[-1] != params['n_tpc'] and (vals.shape[-1] - 1) in np.asarray(config['channels_bottom']):
                     continue          # s2.py:648: such a map is not padded; leave the odd case to the host
-                v = np.ascontiguousarray(vals.reshape(-1, vals.shape[-1]), dtype=np.float32)
-                nn = np.asarray([len(g) for g in grid], dtype=np.int32)
-                lo, hi = np.asarray([g[0] for g in grid], dtype=np.float64), np.asarray([g[-1] for g in grid], dtype=np.float64)
-                self._check(self.lib.wfs_set_pattern_map(self._h, C.c_int32(which), C.c_int32(dims), _p(nn), _p(lo), _p(hi), _p(v), C.c_int32(v.shape[1])))
+                self._call('wfs_set_pattern_map', which, dims, *_grid(grid), vals.reshape(-1, vals.shape[-1]), vals.shape[-1])
                 self.device_maps.add(kind)
         # s2_aft_sigma on device rows needs top = the first n_top channels and bottom = the rest (s2.py:660-665 scales exactly those)
         cb = np.asarray(config['channels_bottom'])
         self._aft_on_device = bool(len(cb)) and np.array_equal(cb, np.arange(params['n_top'], params['n_tpc']))
+
+    def _init_scalar_maps(self, resource):
         # scalar maps of the resource on the device: physics.instruction_params evaluates through this view
         self._scalar_maps = []
-        if config.get('device_scalar_maps', True):
+        if self.config.get('device_scalar_maps', True):
             from .device_maps import DeviceResource
             self.resource = DeviceResource(resource, self)
         else:
             self.resource = resource
+
+    def _init_delay_models(self, resource):
         # model variants of the photon delays (S1 custom / optical propagation, S2 garfield / optical propagation)
         from .delay_models import DelayModels
-        self.models = DelayModels(config, resource)
+        self.models = DelayModels(self.config, resource)
         if self.models.active:
-            base, off, pmf, vmin = self.models.table_arrays()
-            self._check(self.lib.wfs_set_delay_models(self._h, C.c_int32(len(base)), _p(base), _p(off), _p(pmf), _p(vmin)))
+            self._set_delay_models()
             sp = self.models.s1_prop
             if sp is not None:
-                self._check(self.lib.wfs_set_s1_propagation(self._h, C.c_int32(len(sp['z'])), C.c_int32(sp['nu']), C.c_double(sp['u0']),
-                                                            C.c_double(sp['du']), _p(sp['top']), _p(sp['bottom'])))
+                self._call('wfs_set_s1_propagation', len(sp['z']), sp['nu'], sp['u0'], sp['du'], sp['top'], sp['bottom'])
             gg = self.models.gas_gap
             if gg is not None:
-                self._check(self.lib.wfs_set_gas_gap_model(self._h, C.c_int32(gg['inv'].shape[0]), C.c_int32(gg['inv'].shape[1]), _p(gg['inv'])))
+                self._call('wfs_set_gas_gap_model', gg['inv'].shape[0], gg['inv'].shape[1], gg['inv'])
+
+    def _set_delay_models(self):
+        base, off, pmf, vmin = self.models.table_arrays()
+        self._call('wfs_set_delay_models', len(base), base, off, pmf, vmin)
 
     # ------------------------------------------------------------------------------------------
+    def _call(self, name, *args, check=True):
+        """the entry point ``name`` on this engine's handle, its arguments checked and converted by the argtypes of abi.py; raises on an
+        error code (``check=False``: returns whatever the entry point returns)"""
+        rc = getattr(self.lib, name)(self._h, *args)
+        if check:
+            self._check(rc)
+        return rc
+
     def _check(self, rc):
         if rc != 0:
             msg = self.lib.wfs_last_error(self._h)
@@ -327,9 +337,9 @@ class Engine:
 
     def close(self):
         if self._h:
-            self.lib.wfs_wait_records(self._h)
+            self._call('wfs_wait_records', check=False)
             self.unpin_all()
-            self.lib.wfs_destroy(self._h)
+            self._call('wfs_destroy', check=False)
             self._h = C.c_void_p(0)
 
     def __del__(self):
@@ -343,58 +353,47 @@ class Engine:
         """ins: instruction array sorted by the scheduler key; ip: dict from physics.instruction_params;
         run_set: pulse set of every instruction (scheduler.run_sets), None = one set per instruction."""
         n = len(ins)
-        a = [_arr(ins['type'], np.int8), _arr(ins['time'], np.int64), _arr(ins['amp'], np.int32), _arr(gid, np.uint32),
-             _arr(cluster, np.int32), _arr(tmin, np.int64), _arr(ip['p_hit'], np.float64), _arr(ip['drift_mean'], np.float64),
-             _arr(ip['drift_spread'], np.float64), _arr(ip['sc_gain'], np.float64), _arr(ip['cdf_row'], np.int32),
-             _arr(ip['cdf_table'], np.float64)]
+        cdf_row, cdf_table = _arr(ip['cdf_row'], np.int32), _arr(ip['cdf_table'], np.float64)
+        from_maps = cdf_row < 0           # rows from the device pattern maps
         rs = _arr(run_set, np.int32) if run_set is not None else None
-        self._n_loaded = n
-        self._n_run_sets = (int(rs.max()) + 1 if len(rs) else 0) if rs is not None else n
+        n_run_sets = (int(rs.max()) + 1 if len(rs) else 0) if rs is not None else n
         # Run sets go to the library numbered by their FIRST instruction (the numbers of the other members stay unused): a set of one
         # instruction then carries that instruction's index, which is what lets it take the tile-local generator (wfs_tilegen.h) next to
-        # the shared Pulse calls of electron afterpulses.  _set_rows: the library's row of every set of the caller, for the outputs below.
-        self._set_rows = None
-        if rs is not None and len(rs):
-            first = first_instruction_of_sets(rs, self._n_run_sets)
-            if first is not None:
-                self._set_rows = first
-                rs = _arr(first[rs], np.int32)
-        eb = _arr(em_base, np.uint32) if em_base is not None else None       # (a local: the converted copy must outlive the call)
-        self._check(self.lib.wfs_load_instructions(self._h, C.c_int64(n), *[_p(x) for x in a], C.c_int32(a[-1].shape[0]),
-                                                   _p(rs), C.c_int64((n if self._set_rows is not None else int(rs.max()) + 1) if rs is not None and len(rs) else 0), _p(eb)))
-        if np.any(a[10] < 0):           # rows from the device pattern maps
+        # the shared Pulse calls of electron afterpulses.  set_rows: the library's row of every set of the caller, for the outputs below.
+        first = first_instruction_of_sets(rs, n_run_sets) if rs is not None and len(rs) else None
+        if first is not None:
+            rs = first[rs]
+        self._batch = Batch(n_loaded=n, n_cdf_rows=cdf_table.shape[0] + int(np.sum(from_maps)), n_run_sets=n_run_sets, set_rows=first)
+        self._call('wfs_load_instructions', n, ins['type'], ins['time'], ins['amp'], gid, cluster, tmin, ip['p_hit'], ip['drift_mean'],
+                   ip['drift_spread'], ip['sc_gain'], cdf_row, cdf_table, cdf_table.shape[0],
+                   rs, (n if first is not None else int(rs.max()) + 1) if rs is not None and len(rs) else 0, em_base)
+        if np.any(from_maps):
             aft = ip.get('aft_factor')
             if aft is not None:
-                aft = _arr(aft, np.float64)
-                self._check(self.lib.wfs_set_instruction_aft(self._h, C.c_int64(n), _p(aft)))
+                self._call('wfs_set_instruction_aft', n, aft)
             ds = ip.get('diff_sigma')
             if ds is not None:                  # diffusion_transverse_map: those rows are averaged over the electrons inside wfs_run
-                sr, sa = _arr(ds[0], np.float64), _arr(ds[1], np.float64)
-                self._check(self.lib.wfs_set_instruction_diffusion(self._h, C.c_int64(n), _p(sr), _p(sa), C.c_double(float(self.config['tpc_radius']))))
+                self._call('wfs_set_instruction_diffusion', n, ds[0], ds[1], self.config['tpc_radius'])
             pxy = ip.get('pattern_xy')          # S2: the observed position under a field distortion model
-            xyz = [_arr(ins['x'] if pxy is None else pxy[:, 0], np.float32), _arr(ins['y'] if pxy is None else pxy[:, 1], np.float32), _arr(ins['z'], np.float32)]
-            self._check(self.lib.wfs_eval_pattern_rows(self._h, C.c_int64(n), *[_p(q) for q in xyz]))
-        self._n_cdf_rows = a[11].shape[0] + int(np.sum(a[10] < 0))
+            self._call('wfs_eval_pattern_rows', n, ins['x'] if pxy is None else pxy[:, 0], ins['y'] if pxy is None else pxy[:, 1], ins['z'])
         if self.models.active:
             tab, tabb, zi, zf = self.models.instruction_tables(ins, gid)
             if self.models.per_batch:           # tables that depend on the batch (gas gap warping): upload them first
-                base, off, pmf, vmin = self.models.table_arrays()
-                self._check(self.lib.wfs_set_delay_models(self._h, C.c_int32(len(base)), _p(base), _p(off), _p(pmf), _p(vmin)))
-            self._check(self.lib.wfs_set_instruction_models(self._h, C.c_int64(n), _p(tab), _p(tabb), _p(zi), _p(zf)))
+                self._set_delay_models()
+            self._call('wfs_set_instruction_models', n, tab, tabb, zi, zf)
             if self.models.gas_gap is not None:
-                gi, gw = self.models.instruction_gas_gap(ins)
-                self._check(self.lib.wfs_set_instruction_gas_gap(self._h, C.c_int64(n), _p(gi), _p(gw)))
+                self._call('wfs_set_instruction_gas_gap', n, *self.models.instruction_gas_gap(ins))
 
     def register_scalar_map(self, m, name='map'):
         """one map of an itp_map.InterpolatingMap on the device: (map id, host result has a trailing axis) or None if it is not of
         a kind the device evaluates (see device_maps.py)"""
-        mid = C.c_int32(-1)
+        mid = np.full(1, -1, dtype=np.int32)          # (scalar outs are arrays of one element: their dtype is checked like any output's)
         if m.method == 'RectBivariateSpline' and name in m.splines:
             spl = m.splines[name]
-            tx, ty, c = (np.ascontiguousarray(q, dtype=np.float64) for q in spl.tck)
+            tx, ty, c = spl.tck
             kx, ky = spl.degrees
-            self._check(self.lib.wfs_scalar_map_spline(self._h, C.c_int32(len(tx)), _p(tx), C.c_int32(len(ty)), _p(ty), C.c_int32(kx), C.c_int32(ky), _p(c), C.byref(mid)))
-            return mid.value, False
+            self._call('wfs_scalar_map_spline', len(tx), tx, len(ty), ty, kx, ky, c, mid)
+            return int(mid[0]), False
         if m.method not in ('WeightedNearestNeighbors', 'RegularGridInterpolator') or not 1 <= m.dimensions <= 3:
             return None
         v = np.asarray(m.data[name], dtype=np.float64)
@@ -407,141 +406,128 @@ class Engine:
         if nv > 1 and not array_valued:
             return None
         trailing = array_valued and nv == 1
-        v = np.ascontiguousarray(v.reshape(n_points, nv))
+        v = v.reshape(n_points, nv)
         if m.method == 'RegularGridInterpolator' and m.grid is None:
             return None                 # (straxen falls back to nearest neighbours on a point list: the WeightedNearestNeighbors path below)
         if m.grid is not None:
-            nn = np.asarray([len(g) for g in m.grid], dtype=np.int32)
-            lo, hi = np.asarray([g[0] for g in m.grid], dtype=np.float64), np.asarray([g[-1] for g in m.grid], dtype=np.float64)
             if m.method == 'RegularGridInterpolator':
-                self._check(self.lib.wfs_scalar_map_linear(self._h, C.c_int32(m.dimensions), _p(nn), _p(lo), _p(hi), _p(v), C.c_int32(nv), C.byref(mid)))
+                self._call('wfs_scalar_map_linear', m.dimensions, *_grid(m.grid), v, nv, mid)
             elif nv == 1:
-                self._check(self.lib.wfs_scalar_map_grid(self._h, C.c_int32(m.dimensions), _p(nn), _p(lo), _p(hi), _p(v), C.byref(mid)))
+                self._call('wfs_scalar_map_grid', m.dimensions, *_grid(m.grid), v, mid)
             else:
-                self._check(self.lib.wfs_scalar_map_grid_array(self._h, C.c_int32(m.dimensions), _p(nn), _p(lo), _p(hi), _p(v), C.c_int32(nv), C.byref(mid)))
+                self._call('wfs_scalar_map_grid_array', m.dimensions, *_grid(m.grid), v, nv, mid)
         else:
             if n_points < 2 * m.dimensions:
                 return None
-            pts = np.ascontiguousarray(m.coordinate_system, dtype=np.float64)
             if nv == 1:
-                self._check(self.lib.wfs_scalar_map_points(self._h, C.c_int32(m.dimensions), C.c_int64(n_points), _p(pts), _p(v), C.byref(mid)))
+                self._call('wfs_scalar_map_points', m.dimensions, n_points, m.coordinate_system, v, mid)
             else:
-                self._check(self.lib.wfs_scalar_map_points_array(self._h, C.c_int32(m.dimensions), C.c_int64(n_points), _p(pts), _p(v), C.c_int32(nv), C.byref(mid)))
-        self._smap_nv = getattr(self, '_smap_nv', {})
-        self._smap_nv[mid.value] = nv
-        return mid.value, bool(trailing)
+                self._call('wfs_scalar_map_points_array', m.dimensions, n_points, m.coordinate_system, v, nv, mid)
+        self._smap_nv[int(mid[0])] = nv
+        return int(mid[0]), bool(trailing)
 
     def eval_scalar_map(self, map_id, positions):
-        pos = np.ascontiguousarray(positions, dtype=np.float64)
+        pos = _arr(positions, np.float64)
         pos = pos.reshape(len(pos), -1)
-        nv = getattr(self, '_smap_nv', {}).get(map_id, 1)
+        nv = self._smap_nv.get(map_id, 1)
         if nv == 1:
             out = np.empty(len(pos), dtype=np.float64)
-            self._check(self.lib.wfs_scalar_map_eval(self._h, C.c_int32(map_id), C.c_int64(len(pos)), _p(pos), _p(out)))
+            self._call('wfs_scalar_map_eval', map_id, len(pos), pos, out)
             return out
         out = np.empty((len(pos), nv), dtype=np.float64)          # array-valued map: one row of values per position
-        self._check(self.lib.wfs_scalar_map_eval_array(self._h, C.c_int32(map_id), C.c_int64(len(pos)), _p(pos), _p(out), C.c_int32(nv)))
+        self._call('wfs_scalar_map_eval_array', map_id, len(pos), pos, out, nv)
         return out
 
     def cdf_rows(self):
         """(cdf_row, cdf_table) of the loaded batch as the generator uses them, device-evaluated rows included"""
-        n, rows = self._n_loaded, self._n_cdf_rows
+        n, rows = self._batch.n_loaded, self._batch.n_cdf_rows
         cdf_row, table = np.zeros(n, dtype=np.int32), np.zeros((rows, self.params['n_tpc']), dtype=np.float64)
-        self._check(self.lib.wfs_copy_cdf_rows(self._h, _p(cdf_row), _p(table), C.c_int64(rows)))
+        self._call('wfs_copy_cdf_rows', cdf_row, table, rows)
         return cdf_row, table
 
     def load_optical(self, ins, gid, cluster, tmin, channels, timings, time_cutoff):
         """ins: optical instructions (with _first/_last) sorted by time; channels/timings: the flat photon arrays"""
-        self._forget_run_sets()
-        a = [_arr(ins['time'], np.int64), _arr(gid, np.uint32), _arr(cluster, np.int32), _arr(tmin, np.int64),
-             _arr(ins['_first'], np.int32), _arr(ins['_last'], np.int32), _arr(channels, np.int32), _arr(timings, np.int64)]
-        self._check(self.lib.wfs_load_optical(self._h, C.c_int64(len(ins)), *[_p(x) for x in a], C.c_int64(len(a[-1])),
-                                              C.c_int64(int(time_cutoff))))
-
-    def _forget_run_sets(self):
-        """a batch without run sets follows (optical input, injected photons): the outputs are the library's rows again, not the rows
-        of the run sets of an earlier load_instructions"""
-        self._set_rows = self._n_run_sets = None
+        self._batch = Batch(n_loaded=len(ins))           # no run sets: the outputs are the library's rows, not those of an earlier load_instructions
+        self._call('wfs_load_optical', len(ins), ins['time'], gid, cluster, tmin, ins['_first'], ins['_last'], channels, timings,
+                   len(timings), int(time_cutoff))
 
     def load_photons(self, set_cluster, set_tmin, set_off, t, ch, gain, dpe=None):
-        self._forget_run_sets()
-        a = [_arr(set_cluster, np.int32), _arr(set_tmin, np.int64), _arr(set_off, np.int64), _arr(t, np.int64),
-             _arr(ch, np.int16), _arr(gain, np.float64), _arr(dpe, np.uint8) if dpe is not None else None]
-        self._check(self.lib.wfs_load_photons(self._h, C.c_int64(len(a[0])), *[_p(x) for x in a]))
+        self._batch = Batch()           # (as above)
+        self._call('wfs_load_photons', len(set_cluster), set_cluster, set_tmin, set_off, t, ch, gain, dpe)
 
     def run(self):
-        self._check(self.lib.wfs_run(self._h))
+        self._call('wfs_run')
         c = WfsCounts()
-        self._check(self.lib.wfs_get_counts(self._h, C.byref(c)))
+        self._call('wfs_get_counts', C.byref(c))
         self.counts = {n: getattr(c, n) for n, _ in WfsCounts._fields_}
-        self._lib_sets = self.counts['n_pulse_sets']            # the library's pulse-set rows (run sets numbered by their first instruction leave gaps)
+        self._batch.lib_sets = self.counts['n_pulse_sets']
         rows = self._caller_sets(self._lib_sets)
         if rows is not None:
             self.counts['n_pulse_sets'] = len(rows)
         return self.counts
+
+    _lib_sets = property(lambda self: self._batch.lib_sets)
 
     def set_debug(self, on=True, force_dense=False, generate_only=False, check_launches=None):
         """check_launches (default: the environment variable WFS_CHECK_LAUNCHES): every kernel launch of wfs_run is checked and
         synchronised on the spot, so that a failing kernel is reported under its own name (slow; debugging only)"""
         if check_launches is None:
             check_launches = os.environ.get('WFS_CHECK_LAUNCHES', '0') not in ('', '0')
-        self._check(self.lib.wfs_set_debug(self._h, C.c_int32(int(bool(on)) | (2 if force_dense else 0) | (4 if generate_only else 0)
-                                                              | (8 if check_launches else 0) | (16 if self.keep_photons else 0))))
+        self._call('wfs_set_debug', int(bool(on)) | (2 if force_dense else 0) | (4 if generate_only else 0)
+                   | (8 if check_launches else 0) | (16 if self.keep_photons else 0))
 
     def generate(self):
         """photon generation only (no pulses / records): the pre-pass of the electron afterpulses"""
         self.set_debug(False, generate_only=True)
         try:
-            self._check(self.lib.wfs_run(self._h))
+            self._call('wfs_run')
         finally:
             self.set_debug(False)
 
     def instruction_photon_offsets(self):
         """first generated photon of every instruction of the batch (+ the total): generation order"""
-        n = getattr(self, '_n_loaded', 0)
-        out = np.zeros(n + 1, dtype=np.int64)
-        self._check(self.lib.wfs_copy_instruction_photon_offsets(self._h, _p(out), C.c_int64(n + 1)))
+        out = np.zeros(self._batch.n_loaded + 1, dtype=np.int64)
+        self._call('wfs_copy_instruction_photon_offsets', out, len(out))
         return out
 
     def gather_photon_times(self, index):
         """arrival times [ns] of photons given by their index in generation order"""
-        i = _arr(index, np.int64)
-        out = np.zeros(len(i), dtype=np.int64)
-        if len(i):
-            self._check(self.lib.wfs_gather_photon_times(self._h, C.c_int64(len(i)), _p(i), _p(out)))
+        out = np.zeros(len(index), dtype=np.int64)
+        if len(out):
+            self._call('wfs_gather_photon_times', len(out), index, out)
         return out
 
     def set_profiling(self, on=True):
-        self._check(self.lib.wfs_set_profiling(self._h, C.c_int32(int(on))))
+        self._call('wfs_set_profiling', on)
 
     def set_stream(self, stream_ptr):
-        self._check(self.lib.wfs_set_stream(self._h, C.c_void_p(stream_ptr)))
+        self._call('wfs_set_stream', stream_ptr)
 
     # ---- results ---------------------------------------------------------------------------------
     def records(self):
         n = self.counts['n_records']
         out = np.zeros(n, dtype=raw_record_dtype())
-        self._check(self.lib.wfs_copy_records(self._h, _p(out), C.c_int64(n)))
+        self._call('wfs_copy_records', out, n)
         return out
+
+    def _records_range(self, entry, out, count):
+        n = self.counts['n_records'] if count is None else int(count)
+        assert out.flags['C_CONTIGUOUS'] and out.dtype.itemsize == np.dtype(raw_record_dtype()).itemsize and len(out) >= n
+        self._call(entry, out, 0, n)
+        return out[:n]
 
     def records_into(self, out, count=None):
         """device -> host copy of the first ``count`` packed records (default: all) straight into ``out`` (a contiguous
         raw_record array, e.g. a slice of the chunker's record buffer)"""
-        n = self.counts['n_records'] if count is None else int(count)
-        assert out.flags['C_CONTIGUOUS'] and out.dtype.itemsize == np.dtype(raw_record_dtype()).itemsize and len(out) >= n
-        self._check(self.lib.wfs_copy_records_range(self._h, C.c_void_p(out.ctypes.data), C.c_int64(0), C.c_int64(n)))
-        return out[:n]
+        return self._records_range('wfs_copy_records_range', out, count)
 
     def records_into_async(self, out, count=None):
         """the same on the copy stream, without waiting: ``out`` must stay alive (and should be pinned, ``pin``) until
         ``wait_records`` returns; the copy overlaps the next ``run``"""
-        n = self.counts['n_records'] if count is None else int(count)
-        assert out.flags['C_CONTIGUOUS'] and out.dtype.itemsize == np.dtype(raw_record_dtype()).itemsize and len(out) >= n
-        self._check(self.lib.wfs_copy_records_range_async(self._h, C.c_void_p(out.ctypes.data), C.c_int64(0), C.c_int64(n)))
-        return out[:n]
+        return self._records_range('wfs_copy_records_range_async', out, count)
 
     def wait_records(self):
-        self._check(self.lib.wfs_wait_records(self._h))
+        self._call('wfs_wait_records')
 
     def pin(self, array):
         """page-locks a host array for this engine's lifetime (see ``pin_host``)"""
@@ -556,34 +542,34 @@ class Engine:
         self._pinned = []
 
     def set_record_order(self, by_time):
-        self._check(self.lib.wfs_set_record_order(self._h, C.c_int32(int(bool(by_time)))))
+        self._call('wfs_set_record_order', bool(by_time))
 
     def records_dev_ptr(self):
-        return self.lib.wfs_records_dev_ptr(self._h)
+        return self._call('wfs_records_dev_ptr', check=False)
 
     def copy_records_to_device(self, dev_ptr, capacity):
-        self._check(self.lib.wfs_copy_records_dev(self._h, C.c_void_p(dev_ptr), C.c_int64(capacity)))
+        self._call('wfs_copy_records_dev', dev_ptr, capacity)
 
     def groups(self):
         g = self.counts['n_groups']
         left, right, first, ix = (np.zeros(g, dtype=np.int64) for _ in range(4))
-        self._check(self.lib.wfs_copy_groups(self._h, _p(left), _p(right), _p(first), _p(ix)))
+        self._call('wfs_copy_groups', left, right, first, ix)
         return dict(left=left, right=right, first_record=first, ix_rand=ix)
 
     def intervals(self):
         n = self.counts['n_intervals']
         group, ch = np.zeros(n, np.int32), np.zeros(n, np.int32)
         left, right, off = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n + 1, np.int64)
-        self._check(self.lib.wfs_copy_intervals(self._h, _p(group), _p(ch), _p(left), _p(right), _p(off), C.c_int64(n + 1)))
+        self._call('wfs_copy_intervals', group, ch, left, right, off, n + 1)
         data = np.zeros(int(off[n]), dtype=np.int16)
-        self._check(self.lib.wfs_copy_interval_data(self._h, _p(data), C.c_int64(len(data))))
+        self._call('wfs_copy_interval_data', data, len(data))
         return dict(group=group, channel=ch, left=left, right=right, data_off=off, data=data)
 
     def pulses(self, currents=False):
         n = self.counts['n_tiles']
         s, ch = np.zeros(n, np.int32), np.zeros(n, np.int32)
         left, right, nph, off = (np.zeros(n, np.int64) for _ in range(4))
-        self._check(self.lib.wfs_copy_pulses(self._h, _p(s), _p(ch), _p(left), _p(right), _p(nph), _p(off), C.c_int64(n)))
+        self._call('wfs_copy_pulses', s, ch, left, right, nph, off, n)
         rows = self._caller_sets(self._lib_sets)
         if rows is not None:                        # the library's set numbers -> the caller's
             inv = np.full(self._lib_sets, -1, dtype=np.int32)
@@ -593,7 +579,7 @@ class Engine:
         if currents:
             total = int((right - left + 1).sum())
             cur = np.zeros(total, dtype=np.float64)
-            self._check(self.lib.wfs_copy_currents(self._h, _p(cur), C.c_int64(total)))
+            self._call('wfs_copy_currents', cur, total)
             out['current'] = cur
         return out
 
@@ -605,12 +591,12 @@ class Engine:
         g, ch = np.zeros(n, np.int32), np.zeros(n, np.int32)
         left, right, off = (np.zeros(n, np.int64) for _ in range(3))
         right -= 1                      # (an entry the library does not write -- a row without a pulse under full_readout -- stays empty)
-        self._check(self.lib.wfs_copy_rows(self._h, _p(g), _p(ch), _p(left), _p(right), _p(off), C.c_int64(n)))
+        self._call('wfs_copy_rows', g, ch, left, right, off, n)
         listed = right >= left
         g, ch, left, right, off = g[listed], ch[listed], left[listed], right[listed], off[listed]
         total = int((right - left + 1).sum())
         data = np.zeros(total, dtype=np.int32)
-        self._check(self.lib.wfs_copy_row_data(self._h, _p(data), C.c_int64(total)))
+        self._call('wfs_copy_row_data', data, total)
         return dict(group=g, channel=ch, left=left, right=right, data_off=off, data=data)
 
     def set_full_readout(self, on):
@@ -618,7 +604,7 @@ class Engine:
         a digitise window has a row of the window's range, with or without a pulse.  ``intervals()`` and ``records()`` are the
         contract for those rows; ``rows()`` (debug) lists the rows WITH pulses only, at the window's range, and ``sum_signal()`` the
         unchanged sum rows -- a row without a pulse never exists unfinished."""
-        self._check(self.lib.wfs_set_full_readout(self._h, C.c_int32(bool(on))))
+        self._call('wfs_set_full_readout', bool(on))
         self.full_readout = bool(on)
 
     def sum_signal(self):
@@ -629,14 +615,14 @@ class Engine:
         g = np.zeros(n, np.int32)
         left, right, off = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n + 1, np.int64)
         data = np.zeros(total, dtype=np.int64)
-        self._check(self.lib.wfs_copy_sum_signal(self._h, _p(g), _p(left), _p(right), _p(off), _p(data), C.c_int64(n + 1), C.c_int64(total)))
+        self._call('wfs_copy_sum_signal', g, left, right, off, data, n + 1, total)
         k = int(np.argmax(off))         # rows: data_off rises up to the total, the entries behind it stay 0
         return dict(group=g[:k], left=left[:k], right=right[:k], data_off=off[:k + 1], data=data[:int(off[k])])
 
     def _caller_sets(self, s):
         """rows of the library's pulse sets that belong to the caller's run sets (None: all of them, in order): primaries, then -- when the
         library made PMT-afterpulse sets, a second block of the same size -- theirs"""
-        rows = getattr(self, '_set_rows', None)
+        rows = self._batch.set_rows
         if rows is None or not self.counts['n_instructions']:
             return None
         n = self.counts['n_instructions']
@@ -646,7 +632,7 @@ class Engine:
         n, s = self.counts['n_photons'], self._lib_sets
         off = np.zeros(s + 1, np.int64)
         t, ch, gain, dpe = np.zeros(n, np.int64), np.zeros(n, np.int16), np.zeros(n, np.float64), np.zeros(n, np.uint8)
-        self._check(self.lib.wfs_copy_photons(self._h, _p(off), _p(t), _p(ch), _p(gain), _p(dpe), C.c_int64(n)))
+        self._call('wfs_copy_photons', off, t, ch, gain, dpe, n)
         rows = self._caller_sets(s)
         if rows is not None:                        # the caller's sets, in the caller's order (the unused set numbers hold no photons)
             lens = off[rows + 1] - off[rows]
@@ -661,7 +647,7 @@ class Engine:
     def truth(self):
         s = self._lib_sets
         acc, ts = np.zeros((s, 12)), np.zeros((s, 5))
-        self._check(self.lib.wfs_copy_truth(self._h, _p(acc), _p(ts), C.c_int64(s)))
+        self._call('wfs_copy_truth', acc, ts, s)
         rows = self._caller_sets(s)
         return (acc, ts) if rows is None else (acc[rows], ts[rows])
 
@@ -670,7 +656,7 @@ class Engine:
         s = self._lib_sets
         acc = np.zeros((s, int(self.params['n_tpc']), 6))
         if s:
-            self._check(self.lib.wfs_copy_truth_per_pmt(self._h, _p(acc), C.c_int64(s)))
+            self._call('wfs_copy_truth_per_pmt', acc, s)
         rows = self._caller_sets(s)
         return acc if rows is None else acc[rows]
 
@@ -680,28 +666,25 @@ class Engine:
         s, nch = self._lib_sets, int(self.params['n_tpc'])
         kind = np.full(s * nch, -1, dtype=np.int8)
         if s:
-            self._check(self.lib.wfs_copy_tile_kernels(self._h, _p(kind), C.c_int64(len(kind))))
+            self._call('wfs_copy_tile_kernels', kind, len(kind))
         kind = kind[kind >= 0].reshape(-1, nch)         # (the library fills the primary sets: PMT-afterpulse sets follow them and have no entry)
-        rows = getattr(self, '_set_rows', None)
+        rows = self._batch.set_rows
         return kind if rows is None or not self.counts['n_instructions'] else kind[rows]
 
     def set_noise_offsets(self, ix_rand):
-        a = _arr(ix_rand, np.int64)
-        self._check(self.lib.wfs_set_noise_offsets(self._h, _p(a), C.c_int64(len(a))))
-
-    _noise_rows = None          # (channels, common streams) of the noise model that is set
+        self._call('wfs_set_noise_offsets', ix_rand, len(ix_rand))
 
     def set_noise_model(self, pmf, vmin=0):
         """pmf[n_channels][n_values] over the ADC offsets vmin .. vmin + n_values - 1 (noise_model.py); None clears the model: the noise
         array, if any, is replayed again.  Acts with enable_noise, from the next run."""
         if pmf is None:
-            self._check(self.lib.wfs_set_noise_model(self._h, C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_void_p(0)))
+            self._call('wfs_set_noise_model', 0, 0, 0, None)
             self._noise_rows = None
             return
         pmf = _arr(pmf, np.float64)
         if pmf.ndim != 2:
             raise ValueError('set_noise_model: pmf must be [n_channels][n_values]')
-        self._check(self.lib.wfs_set_noise_model(self._h, C.c_int32(pmf.shape[0]), C.c_int32(pmf.shape[1]), C.c_int32(int(vmin)), _p(pmf)))
+        self._call('wfs_set_noise_model', pmf.shape[0], pmf.shape[1], vmin, pmf)
         # (channels, common streams) of the model as the library holds it: the C entry points of the colour and of the slow levels take
         # no row count and read n_channels + n_groups rows, so the arrays are checked against it here
         self._noise_rows = (int(pmf.shape[0]), 0)
@@ -711,7 +694,7 @@ class Engine:
         group int32[n_channels] (-1: none), mix_q int32[n_channels] in Q16, common_pmf[n_groups][n_values] on the model's values; the
         last three may be None without common streams.  taps_q None clears the colour: the white values return.  From the next run."""
         if taps_q is None:
-            self._check(self.lib.wfs_set_noise_colour(self._h, C.c_int32(0), C.c_void_p(0), C.c_int32(0), C.c_void_p(0), C.c_void_p(0), C.c_void_p(0)))
+            self._call('wfs_set_noise_colour', 0, None, 0, None, None, None)
             self._noise_rows = (self._noise_rows[0], 0) if self._noise_rows else None
             return
         taps_q = _arr(taps_q, np.int32)
@@ -726,9 +709,9 @@ class Engine:
             group, mix_q, common_pmf = _arr(group, np.int32), _arr(mix_q, np.int32), _arr(common_pmf, np.float64)
             if group.ndim != 1 or mix_q.shape != group.shape or common_pmf.ndim != 2 or taps_q.shape[0] != len(group) + n_groups:
                 raise ValueError('set_noise_colour: group and mix_q must be [n_channels], common_pmf [n_groups][n_values], taps_q [n_channels + n_groups][n_taps]')
-        self._check(self.lib.wfs_set_noise_colour(
-            self._h, C.c_int32(taps_q.shape[1]), _p(taps_q), C.c_int32(n_groups), _p(group) if n_groups else C.c_void_p(0),
-            _p(mix_q) if n_groups else C.c_void_p(0), _p(common_pmf) if n_groups else C.c_void_p(0)))
+        else:
+            group = mix_q = common_pmf = None
+        self._call('wfs_set_noise_colour', taps_q.shape[1], taps_q, n_groups, group, mix_q, common_pmf)
         self._noise_rows = (self._noise_rows[0], n_groups) if self._noise_rows else None
 
     def set_noise_slow(self, shifts, slow_q=None):
@@ -736,7 +719,7 @@ class Engine:
         samples apart), slow_q int32[n_channels + n_groups][n_levels] in Q16.  Set the colour first: setting a model or a colour clears
         the levels.  shifts None clears them.  From the next run."""
         if shifts is None:
-            self._check(self.lib.wfs_set_noise_slow(self._h, C.c_int32(0), C.c_void_p(0), C.c_void_p(0)))
+            self._call('wfs_set_noise_slow', 0, None, None)
             return
         shifts, slow_q = _arr(shifts, np.int32), _arr(slow_q, np.int32)
         if shifts.ndim != 1 or slow_q.ndim != 2 or slow_q.shape[1] != len(shifts):
@@ -745,26 +728,25 @@ class Engine:
         if rows is not None and slow_q.shape[0] != rows[0] + rows[1]:
             raise ValueError(f'set_noise_slow: the model has {rows[0]} channels and {rows[1]} common streams: slow_q must have {rows[0] + rows[1]} rows, '
                              f'not {slow_q.shape[0]}')
-        self._check(self.lib.wfs_set_noise_slow(self._h, C.c_int32(len(shifts)), _p(shifts), _p(slow_q)))
+        self._call('wfs_set_noise_slow', len(shifts), shifts, slow_q)
+
+    def _samples(self, entry, dtype, row, t0, n):
+        out = np.zeros(int(n), dtype=dtype)
+        self._call(entry, row, t0, n, out)
+        return out
 
     def noise_slow_samples(self, row, t0, n):
         """the slow part S(row, t0 .. t0 + n - 1) in Q16 (int32): row < n_channels a channel, n_channels + g common stream g"""
-        out = np.zeros(int(n), dtype=np.int32)
-        self._check(self.lib.wfs_noise_slow_samples(self._h, C.c_int32(int(row)), C.c_int64(int(t0)), C.c_int64(int(n)), _p(out)))
-        return out
+        return self._samples('wfs_noise_slow_samples', np.int32, row, t0, n)
 
     def noise_white_samples(self, row, t0, n):
         """the white sequence w(row, t0 .. t0 + n - 1) under the colour: row < n_channels a channel, n_channels + g common stream g"""
-        out = np.zeros(int(n), dtype=np.int16)
-        self._check(self.lib.wfs_noise_white_samples(self._h, C.c_int32(int(row)), C.c_int64(int(t0)), C.c_int64(int(n)), _p(out)))
-        return out
+        return self._samples('wfs_noise_white_samples', np.int16, row, t0, n)
 
     def noise_samples(self, channel, t0, n):
         """noise(channel, t0 .. t0 + n - 1) of the noise model (colour and slow levels included), evaluated on the device: t is the
         absolute sample index (time / dt)"""
-        out = np.zeros(int(n), dtype=np.int16)
-        self._check(self.lib.wfs_noise_model_samples(self._h, C.c_int32(int(channel)), C.c_int64(int(t0)), C.c_int64(int(n)), _p(out)))
-        return out
+        return self._samples('wfs_noise_model_samples', np.int16, channel, t0, n)
 
     def set_dark_counts(self, rate_hz):
         """PMT dark counts between runs (wfs_set_dark_counts): a rate in Hz for every PMT, or one value per channel for the
@@ -772,40 +754,38 @@ class Engine:
         sample of a TPC or HE row carries the single-electron pulses its PMT makes on its own, a pure function of (seed, channel,
         absolute time); windows, truth and record order do not change, the sum row carries none."""
         if rate_hz is None:
-            self._check(self.lib.wfs_set_dark_counts(self._h, C.c_int32(0), C.c_void_p(0)))
+            self._call('wfs_set_dark_counts', 0, None)
             self.dark_count_rate = None
             return
         r = np.asarray(rate_hz, dtype=np.float64)
         if r.ndim == 0:
             r = np.full(self.params['n_tpc'], float(r))
         r = np.ascontiguousarray(r.ravel())
-        self._check(self.lib.wfs_set_dark_counts(self._h, C.c_int32(len(r)), _p(r)))
+        self._call('wfs_set_dark_counts', len(r), r)
         self.dark_count_rate = r.copy() if np.any(r > 0) else None
 
     def dark_count_samples(self, channel, t0, n):
         """D(channel, t0 .. t0 + n - 1): what the dark counts of a PMT add to its accumulated ADC at the absolute samples (time / dt),
         evaluated on the device"""
-        out = np.zeros(int(n), dtype=np.int32)
-        self._check(self.lib.wfs_dark_count_samples(self._h, C.c_int32(int(channel)), C.c_int64(int(t0)), C.c_int64(int(n)), _p(out)))
-        return out
+        return self._samples('wfs_dark_count_samples', np.int32, channel, t0, n)
 
     def dark_count_photons(self, channel, t0, n):
         """(t_ns int64[k], gain float64[k]) of the dark photons of a PMT whose pulse starts at a sample in [t0, t0 + n), in time order:
         the truth does not hold them, this is how a hit is matched to a dark count"""
         cap = 64
         while True:
-            t, g, k = np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.float64), C.c_int64(0)
-            rc = self.lib.wfs_dark_count_photons(self._h, C.c_int32(int(channel)), C.c_int64(int(t0)), C.c_int64(int(n)), _p(t), _p(g), C.c_int64(cap), C.byref(k))
-            if rc == -3 and k.value > cap:          # (WFS_E_CAPACITY: the count is known now)
-                cap = int(k.value)
+            t, g, k = np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.float64), np.zeros(1, dtype=np.int64)
+            rc = self._call('wfs_dark_count_photons', channel, t0, n, t, g, cap, k, check=False)
+            if rc == -3 and k[0] > cap:          # (WFS_E_CAPACITY: the count is known now)
+                cap = int(k[0])
                 continue
             self._check(rc)
-            return t[:k.value].copy(), g[:k.value].copy()
+            return t[:k[0]].copy(), g[:k[0]].copy()
 
     def dark_count_thresholds(self, channel):
         """uint32[4]: floor(2^32 P(N >= k)), k = 1 .. 4, of the channel's photons per cell of 64 samples, as the device holds them"""
         thr = np.zeros(4, dtype=np.uint32)
-        self._check(self.lib.wfs_copy_dark_counts(self._h, C.c_int32(int(channel)), _p(thr)))
+        self._call('wfs_copy_dark_counts', channel, thr)
         return thr
 
     def noise_model_cells(self, channel):
@@ -813,37 +793,34 @@ class Engine:
         vmin + c if (word << (32 - shift)) mod 2^32 < thr[c], else vmin + alias[c]"""
         cap = 4096
         thr, alias = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
-        n, shift, vmin = C.c_int32(0), C.c_int32(0), C.c_int32(0)
-        self._check(self.lib.wfs_copy_noise_model(self._h, C.c_int32(int(channel)), _p(thr), _p(alias), C.c_int32(cap), C.byref(n), C.byref(shift), C.byref(vmin)))
-        return dict(thr=thr[:n.value].copy(), alias=alias[:n.value].copy(), shift=shift.value, vmin=vmin.value)
+        n, shift, vmin = (np.zeros(1, dtype=np.int32) for _ in range(3))
+        self._call('wfs_copy_noise_model', channel, thr, alias, cap, n, shift, vmin)
+        return dict(thr=thr[:n[0]].copy(), alias=alias[:n[0]].copy(), shift=int(shift[0]), vmin=int(vmin[0]))
 
     def set_window_carry(self, has_pulse, last_pulse_end_time):
-        self._check(self.lib.wfs_set_window_carry(self._h, C.c_int32(int(has_pulse)), C.c_int64(int(last_pulse_end_time))))
+        self._call('wfs_set_window_carry', has_pulse, last_pulse_end_time)
 
     def cluster_groups(self, n_clusters):
         g = np.zeros(n_clusters, dtype=np.int32)
         if n_clusters:
-            self._check(self.lib.wfs_copy_cluster_groups(self._h, _p(g), C.c_int64(n_clusters)))
+            self._call('wfs_copy_cluster_groups', g, n_clusters)
         return g
 
     def electron_stats(self):
         """per run set (= per instruction unless run sets were given): n, mean, min, max, std of the electron times"""
-        n = getattr(self, '_n_run_sets', None)
-        rows = getattr(self, '_set_rows', None)
+        n, rows = self._batch.n_run_sets, self._batch.set_rows
         if n is None or self.counts['n_instructions'] == 0:
             n, rows = self.counts['n_instructions'], None
         if rows is not None:
             n = self.counts['n_instructions']
         es = np.zeros((n, 5))
         if n:
-            self._check(self.lib.wfs_copy_electron_stats(self._h, _p(es), C.c_int64(n)))
+            self._call('wfs_copy_electron_stats', es, n)
         return es if rows is None else es[rows]
 
     def kernel_times(self):
         names = C.create_string_buffer(4096)
-        ms = (C.c_float * 64)()
-        nl = (C.c_int32 * 64)()
-        nk = C.c_int32(0)
-        self._check(self.lib.wfs_kernel_times(self._h, names, C.c_int64(4096), ms, nl, C.byref(nk)))
-        parts = names.raw.split(b'\0')[:nk.value]
-        return {parts[k].decode(): (float(ms[k]), int(nl[k])) for k in range(nk.value)}
+        ms, nl, nk = np.zeros(64, dtype=np.float32), np.zeros(64, dtype=np.int32), np.zeros(1, dtype=np.int32)
+        self._call('wfs_kernel_times', names, 4096, ms, nl, nk)
+        parts = names.raw.split(b'\0')[:nk[0]]
+        return {parts[k].decode(): (float(ms[k]), int(nl[k])) for k in range(nk[0])}
