@@ -43,7 +43,8 @@ _GETTERS = dict(
     dg_left=np.int64, dg_right=np.int64, dg_first_pulse=np.int64, dg_n_pulses=np.int64, dg_ix_rand=np.int64,
     dg_row_off=np.int64, row_ch=np.int32, row_left=np.int64, row_right=np.int64, row_data_off=np.int64,
     row_data=np.int32, zl_digit=np.int64, zl_ch=np.int32, zl_left=np.int64, zl_right=np.int64,
-    zl_data_off=np.int64, zl_data=np.int32, truth=np.float64, opt_in_t=np.int64, opt_in_ch=np.int16)
+    zl_data_off=np.int64, zl_data=np.int32, truth=np.float64, opt_in_t=np.int64, opt_in_ch=np.int16,
+    em_nph=np.int64)          # photons per candidate emitter, zeros included, per instruction as loaded (S1: one emitter, S2: amp)
 
 
 def lib():

@@ -92,6 +92,9 @@ typedef struct orc_session_s {
     /* all generated photons (channel sorted per pulse call) */
     vec_i64 ph_t; vec_i16 ph_ch; vec_u8 ph_dpe; vec_f64 ph_gain; vec_i64 call_ph_off; vec_i32 call_kind, call_runset;
     vec_i64 e_t; vec_i64 call_e_off;
+    /* photons of every candidate emitter, zeros included, per instruction in the order orc_simulate(_scheduled) received them: an S1 is
+     * one emitter (its hits), an S2 `amp` emitters (0 for a lost electron; all 0 for a tile-generated S2, whose photons have no emitter) */
+    vec_i64 em_nph; i64 em_cur;
     /* optical input: the photons RawDataOptical.sim_primary hands to Pulse.__call__, before the transit-time draw (input order inside
      * a call; the calls are those of call_ph_off) */
     vec_i64 opt_in_t; vec_i16 opt_in_ch;
@@ -232,7 +235,7 @@ orc_session *orc_new(const orc_config *c, const double *templates, const double 
                      const int16_t *noise)
 {
     orc_session *s = (orc_session *)calloc(1, sizeof(orc_session));
-    s->cur_tab = s->cur_tabb = s->cur_pzi = -1; s->cur_gg = -1;
+    s->cur_tab = s->cur_tabb = s->cur_pzi = -1; s->cur_gg = -1; s->em_cur = -1;
     s->c = *c; s->templates = templates; s->spe = spe; s->gains = gains; s->thr_truth = thr_truth; s->thr_zle = thr_zle;
     s->lum_x = lum_x; s->lum_t = lum_t; s->noise = noise; s->save_full_truth = 1;
     tab_normal(s, TAB_TTS, c->tts_mean, c->tts_sigma); tab_exp(s, TAB_S1_EXP, c->s1_decay_time); tab_normal(s, TAB_S1_SPREAD, 0.0, c->s1_decay_spread);
@@ -270,7 +273,7 @@ void orc_free(orc_session *s)
         (void **)&s->dg_row_off.p, (void **)&s->row_ch.p, (void **)&s->row_left.p, (void **)&s->row_right.p,
         (void **)&s->row_data_off.p, (void **)&s->row_data.p, (void **)&s->zl_digit.p, (void **)&s->zl_left.p,
         (void **)&s->zl_right.p, (void **)&s->zl_data_off.p, (void **)&s->zl_ch.p, (void **)&s->zl_data.p,
-        (void **)&s->truth.p, (void **)&s->opt_in_t.p, (void **)&s->opt_in_ch.p };
+        (void **)&s->truth.p, (void **)&s->opt_in_t.p, (void **)&s->opt_in_ch.p, (void **)&s->em_nph.p };
     for (size_t i = 0; i < sizeof(ptrs) / sizeof(ptrs[0]); i++) free(*ptrs[i]);
     for (int q = 0; q < TAB_N; q++) { free(s->tab[q].cum); free(s->tab[q].thr); free(s->tab[q].alias); }
     for (i32 k = 0; k < s->n_xtab; k++) { free(s->xtab[k].cum); free(s->xtab[k].thr); free(s->xtab[k].alias); }
@@ -961,6 +964,15 @@ static void ctx_push(call_ctx *x, i64 t, int ch, int dpe, double g, u32 gid, i64
     VEC_PUSH(x->pb.t, i64, t); VEC_PUSH(x->pb.ch, int16_t, (int16_t)ch); VEC_PUSH(x->pb.dpe, uint8_t, (uint8_t)dpe); VEC_PUSH(x->pb.gain, double, g);
     VEC_PUSH(x->gid, i64, (i64)gid); VEC_PUSH(x->em, i64, em); VEC_PUSH(x->it, i64, it);
 }
+/* room in em_nph for a batch (zeroed); returns, per instruction in the order given, where its emitters start */
+static i64 *em_reserve(orc_session *s, i64 n, const int8_t *type, const i32 *amp)
+{
+    i64 *off = (i64 *)malloc((size_t)(n + 1) * 8); off[0] = s->em_nph.n;
+    for (i64 i = 0; i < n; i++) off[i + 1] = off[i] + (type[i] == 1 ? 1 : (amp[i] > 0 ? amp[i] : 0));
+    VEC_RESERVE(s->em_nph, i64, off[n] - off[0] + 1);
+    memset(s->em_nph.p + off[0], 0, (size_t)(off[n] - off[0]) * 8); s->em_nph.n = off[n];
+    return off;
+}
 /* s1.py:117-238 for one instruction: Binomial(amp, ly) hits as Bernoulli trials, then one_photon() each */
 static i64 gen_s1(orc_session *s, call_ctx *x, u32 gid, i64 time, i64 amp, double p_hit, const double *cdf)
 {
@@ -975,6 +987,7 @@ static i64 gen_s1(orc_session *s, call_ctx *x, u32 gid, i64 time, i64 amp, doubl
         one_photon(s, 0, 0, gid, (u32)k, 0, (u32)k, time, cdf, &t, &ch, &dpe, &g);
         ctx_push(x, t, ch, dpe, g, gid, 0, k);
     }
+    if (s->em_cur >= 0) s->em_nph.p[s->em_cur] = n_hits;
     return n_hits;
 }
 /* s2.py:73-136 S2.__call__ (luminescence 'simple') for one instruction.  Candidate electron j < amp survives with
@@ -1019,6 +1032,7 @@ static i64 gen_s2(orc_session *s, call_ctx *x, int type, u32 gid, u32 em_base, i
         i64 nph = poisson_any(s, je, gid, sc_gain);
         nph += (i64)(0.0 + c->gain_spread * z_gain);
         if (nph < 0) nph = 0;
+        if (s->em_cur >= 0) s->em_nph.p[s->em_cur + j] = nph;
         VEC_PUSH(s->e_t, i64, et);
         for (i64 m = 0; m < nph; m++) {
             i64 t; int ch, dpe; double g;
@@ -1144,6 +1158,7 @@ void orc_simulate(orc_session *s, i64 n, const int8_t *type, const i64 *time, co
     const orc_config *c = &s->c;
     if (n == 0) return;
     i64 *it = (i64 *)malloc((size_t)n * 8); tkey *ord = (tkey *)malloc((size_t)n * sizeof(tkey));
+    i64 *em_off = em_reserve(s, n, type, amp);
     for (i64 i = 0; i < n; i++) {
         /* rawdata.py:61: time + (z / v * (type % 2 - 1)).astype(int64); z is a float32 array and v a python float,
          * so numpy evaluates the quotient and the product in float32 */
@@ -1177,7 +1192,7 @@ void orc_simulate(orc_session *s, i64 n, const int8_t *type, const i64 *time, co
                 if (alone && !s->save_full_truth)
                     for (i64 q = k + 1; q < b; q++) if (type[ord[q].i] == ptype) { alone = ord[q].t - ord[k].t > gap; break; }
                 const double *cdf = cdf_table + (i64)cdf_row[i] * c->n_tpc;
-                set_cur(s, i);
+                set_cur(s, i); s->em_cur = em_off[i];
                 if (ptype == 1) gen_s1(s, &x, gid[i], time[i], amp[i], p_hit[i], cdf);
                 else gen_s2(s, &x, alone ? ptype : -1, gid[i], em_base ? em_base[i] : 0u, time[i], amp[i], p_hit[i], drift_mean[i], drift_spread[i], sc_gain[i], cdf);
                 open = 1; last_key = ord[k].t;
@@ -1188,7 +1203,7 @@ void orc_simulate(orc_session *s, i64 n, const int8_t *type, const i64 *time, co
         a = b;
     }
     digitize_window(s);                                       /* rawdata.py:154-155 */
-    free(it); free(ord);
+    free(it); free(ord); free(em_off); s->em_cur = -1;
 }
 
 /* The same with the schedule given: instructions in processing order, cluster[] non-decreasing, tmin[] the key the
@@ -1202,6 +1217,7 @@ void orc_simulate_scheduled(orc_session *s, i64 n, const int8_t *type, const i64
 {
     const orc_config *c = &s->c;
     if (n == 0) return;
+    i64 *em_off = em_reserve(s, n, type, amp);
     i64 a = 0;
     while (a < n) {
         i64 b = a + 1, cmin = tmin[a];
@@ -1215,7 +1231,7 @@ void orc_simulate_scheduled(orc_session *s, i64 n, const int8_t *type, const i64
             call_ctx x; memset(&x, 0, sizeof x);
             for (i64 i = k; i < e; i++) {
                 const double *cdf = cdf_table + (i64)cdf_row[i] * c->n_tpc;
-                set_cur(s, i);
+                set_cur(s, i); s->em_cur = em_off[i];
                 if (type[i] == 1) gen_s1(s, &x, gid[i], time[i], amp[i], p_hit[i], cdf);
                 /* an instruction that shares its Pulse call is never generated tile by tile; one that is alone in its call follows the
                  * usual rule (the device: k_fuse_decide, set i = {instruction i}) */
@@ -1228,6 +1244,7 @@ void orc_simulate_scheduled(orc_session *s, i64 n, const int8_t *type, const i64
         a = b;
     }
     digitize_window(s);
+    free(em_off); s->em_cur = -1;
 }
 
 /* ---------------------------------------------------------------- record packing ----------------- */
@@ -1261,7 +1278,7 @@ GETTER(pl_ch, pl_ch, i32) GETTER(pl_runset, pl_runset, i32) GETTER(pl_left, pl_l
 GETTER(pl_cur_off, pl_cur_off, i64) GETTER(pl_nph, pl_nph, i64) GETTER(cur, cur, double)
 GETTER(ph_t, ph_t, i64) GETTER(ph_ch, ph_ch, int16_t) GETTER(ph_dpe, ph_dpe, uint8_t) GETTER(ph_gain, ph_gain, double)
 GETTER(call_ph_off, call_ph_off, i64) GETTER(call_kind, call_kind, i32) GETTER(call_runset, call_runset, i32)
-GETTER(e_t, e_t, i64) GETTER(call_e_off, call_e_off, i64) GETTER(opt_in_t, opt_in_t, i64) GETTER(opt_in_ch, opt_in_ch, int16_t)
+GETTER(e_t, e_t, i64) GETTER(call_e_off, call_e_off, i64) GETTER(em_nph, em_nph, i64) GETTER(opt_in_t, opt_in_t, i64) GETTER(opt_in_ch, opt_in_ch, int16_t)
 GETTER(dg_left, dg_left, i64) GETTER(dg_right, dg_right, i64) GETTER(dg_first_pulse, dg_first_pulse, i64)
 GETTER(dg_n_pulses, dg_n_pulses, i64) GETTER(dg_ix_rand, dg_ix_rand, i64) GETTER(dg_row_off, dg_row_off, i64)
 GETTER(row_ch, row_ch, i32) GETTER(row_left, row_left, i64) GETTER(row_right, row_right, i64)

@@ -246,3 +246,48 @@ def host_diffuse_patterns(orc, pattern_map, xy, gids, amps, p_survive, sigma_r, 
         n_in.append(len(pos))
         err.append(p.std(axis=0) / np.sqrt(max(len(pos), 1)) if len(pos) else None)
     return out, n_in, err
+
+
+# ------------------------------------------------------------------------------------------------ tile order
+def assert_tiles_in_oracle_order(eng, o, sets, live=None):
+    """The device's tiles are in the oracle's order, photon by photon.  A tile is the photons of one Pulse call on one channel; its order
+    is part of the result (n_pe_trigger counts among the FIRST n_dpe photons of the channel slice, pulse.py:255; three or more photons
+    of one ns are merged in that order).  For every oracle call k and its device pulse set sets[k] both sides are split by channel
+    WITHOUT reordering -- the device stores a set tile after tile (eng.photons()), the oracle's call is o['ph_*'][a:b] -- and the stored
+    sequence of (t, gain, dpe) of every channel must equal the oracle's, element by element.  Implies the comparison sorted by
+    (channel, time, gain) that it replaces.  live: bool per channel -- photons on the other channels are left out on both sides (the oracle
+    lists photons on a turned-off PMT, the device may drop them on entry).  On failure: the call, the channel, the first differing position
+    and both tile sizes."""
+    ph = eng.photons() if hasattr(eng, 'photons') else eng
+    off = o['call_ph_off']
+    assert len(sets) == len(off) - 1, f'{len(sets)} device sets for {len(off) - 1} oracle calls'
+    for k, i in enumerate(sets):
+        a, b = int(off[k]), int(off[k + 1])
+        c, e = int(ph['set_off'][i]), int(ph['set_off'][i + 1])
+        och, dch = np.asarray(o['ph_ch'][a:b]), np.asarray(ph['ch'][c:e])
+        ko, kd = np.argsort(och, kind='stable'), np.argsort(dch, kind='stable')      # split by channel, the order inside a channel kept
+        if live is not None:
+            ko, kd = ko[np.asarray(live)[och[ko]]], kd[np.asarray(live)[dch[kd]]]
+        if len(ko) == len(kd) and np.array_equal(och[ko], dch[kd]) and all(
+                np.array_equal(np.asarray(o['ph_' + f][a:b])[ko], np.asarray(ph[f][c:e])[kd]) for f in ('t', 'gain', 'dpe')):
+            continue
+        for ch in np.union1d(och, dch):              # something differs: name the first place
+            if live is not None and not live[ch]:
+                continue
+            so, sd = och == ch, dch == ch
+            ref = (o['ph_t'][a:b][so], o['ph_gain'][a:b][so], o['ph_dpe'][a:b][so])
+            got = (ph['t'][c:e][sd], ph['gain'][c:e][sd], ph['dpe'][c:e][sd])
+            n_o, n_d = len(ref[0]), len(got[0])
+            m = min(n_o, n_d)
+            diff = np.zeros(m, dtype=bool)
+            for x, y in zip(ref, got):
+                diff |= np.asarray(x[:m]) != np.asarray(y[:m])
+            if n_o != n_d or diff.any():
+                at = int(np.argmax(diff)) if diff.any() else m
+                what = ''
+                if at < m:
+                    what = (f': oracle (t, gain, dpe) = ({ref[0][at]}, {ref[1][at]!r}, {ref[2][at]}), '
+                            f'device = ({got[0][at]}, {got[1][at]!r}, {got[2][at]})')
+                raise AssertionError(f'call {k} (device set {i}), channel {int(ch)}: first difference at position {at}; '
+                                     f'tile sizes oracle {n_o}, device {n_d}{what}')
+        raise AssertionError(f'call {k} (device set {i}): the photon lists differ')          # (not reached: a difference lies in some channel)

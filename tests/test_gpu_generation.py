@@ -8,7 +8,7 @@ in principle differ by 1 ns when a value lands within ~1e-13 of an integer; none
 import numpy as np
 import pytest
 
-from tests.helpers import make_engine, make_oracle
+from tests.helpers import assert_tiles_in_oracle_order, make_engine, make_oracle
 from wfsim_amd.config import xenonnt_test_config
 from wfsim_amd.dtypes import instruction_dtype
 from wfsim_amd.physics import instruction_params
@@ -84,7 +84,7 @@ def _assert_truth_rows(eng, o, s_ins):
 
 
 def _compare(orc, o, eng, counts, s_ins):
-    # ---- photons per pulse set (sets are matched by instruction)
+    # ---- photons per pulse set (sets are matched by instruction), every tile in generation order
     ph = eng.photons()
     assert counts['n_photons'] == len(o['ph_t'])
     n_ins = len(s_ins)
@@ -95,12 +95,7 @@ def _compare(orc, o, eng, counts, s_ins):
         a, b = o['call_ph_off'][k], o['call_ph_off'][k + 1]
         c, e = ph['set_off'][i], ph['set_off'][i + 1]
         assert b - a == e - c, f'instruction {i}: {b - a} vs {e - c} photons'
-        ko = np.lexsort((o['ph_gain'][a:b], o['ph_t'][a:b], o['ph_ch'][a:b]))
-        kg = np.lexsort((ph['gain'][c:e], ph['t'][c:e], ph['ch'][c:e]))
-        assert np.array_equal(o['ph_ch'][a:b][ko], ph['ch'][c:e][kg])
-        assert np.array_equal(o['ph_t'][a:b][ko], ph['t'][c:e][kg])
-        assert np.array_equal(o['ph_gain'][a:b][ko], ph['gain'][c:e][kg])
-        assert np.array_equal(o['ph_dpe'][a:b][ko], ph['dpe'][c:e][kg])
+    assert_tiles_in_oracle_order(eng, o, sets)          # every tile in the oracle's order, photon by photon (t, gain, dpe)
     # ---- digitise windows, intervals, records
     g = eng.groups()
     keep = g['right'] >= g['left']
@@ -186,7 +181,7 @@ def test_run_sets_several_instructions_per_pulse_call():
         assert prim.sum() == n_sets
         # photons per pulse set: oracle calls are in processing order = set numbering
         ph = eng.photons()
-        k_set = 0
+        k_set, sets = 0, []
         for k, kind in enumerate(o['call_kind']):
             i = (n_sets + k_set - 1) if kind == 3 else k_set
             if kind != 3:
@@ -194,10 +189,8 @@ def test_run_sets_several_instructions_per_pulse_call():
             a, b = o['call_ph_off'][k], o['call_ph_off'][k + 1]
             c, e = ph['set_off'][i], ph['set_off'][i + 1]
             assert b - a == e - c
-            ko = np.lexsort((o['ph_gain'][a:b], o['ph_t'][a:b], o['ph_ch'][a:b]))
-            kg = np.lexsort((ph['gain'][c:e], ph['t'][c:e], ph['ch'][c:e]))
-            assert np.array_equal(o['ph_t'][a:b][ko], ph['t'][c:e][kg]) and np.array_equal(o['ph_ch'][a:b][ko], ph['ch'][c:e][kg])
-            assert np.array_equal(o['ph_gain'][a:b][ko], ph['gain'][c:e][kg])
+            sets.append(i)
+        assert_tiles_in_oracle_order(eng, o, sets)      # tiles of shared calls too: the instructions' photons one behind the other
         assert eng.records().tobytes() == orc.pack_records().tobytes()
         assert counts['n_pe'] == orc.n_pe
         # electron statistics per run set
@@ -256,7 +249,8 @@ def test_pmt_afterpulses_of_large_tile_generated_tiles():
     """PMT afterpulses of tile-generated S2s (k_s2_tile<.., AP>): ~800 photons per tile, afterpulse probabilities x 4 so that about half
     of the tiles have more candidates than the workgroup's LDS stage holds (AP_STAGE = 128: the excess goes to the list entry by
     entry and is placed by the generic kernels, the rest as one key-ordered stretch per tile by k_ap_seg); one small S2 and an S1
-    through the block generator in the same batch.  Device == oracle photon by photon, afterpulse tiles in generation order."""
+    through the block generator in the same batch.  Device == oracle photon by photon, afterpulse tiles in generation order
+    (_compare: assert_tiles_in_oracle_order, parents' and afterpulses' tiles alike)."""
     from tests.helpers import ap_tables_from_golden
     ap = ap_tables_from_golden()
     for name in ap: ap[name] = dict(ap[name], delaytime_cdf=ap[name]['delaytime_cdf'] * 4.0)

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from tests import hot_patterns as H
-from tests.helpers import make_engine
+from tests.helpers import assert_tiles_in_oracle_order, make_engine
 from tests.sum_signal import SUM_CHANNEL, assert_sum_rows, expected_sum_rows
 from tests.test_gpu_bright_tiles import _oracle_truth_per_pmt
 from wfsim_amd import workloads as W
@@ -93,8 +93,8 @@ def _device_sets(o, s):
 
 
 def _compare(cfg, noise, orc, o, eng, counts, s):
-    """the comparison of tests/test_gpu_generation.py::_compare with run sets and the sum row allowed for: photons per pulse set sorted by
-    (channel, time, gain), digitise windows, record bytes, n_pe; then the 12 truth columns of every call, set by set"""
+    """the comparison of tests/test_gpu_generation.py::_compare with run sets and the sum row allowed for: photons per pulse set, every tile in
+    the oracle's order (tests/helpers.py: assert_tiles_in_oracle_order), digitise windows, record bytes, n_pe; then the 12 truth columns of every call, set by set"""
     ph = eng.photons()
     assert counts['n_photons'] == len(o['ph_t'])
     sets, of_call, n_prim = _device_sets(o, s)
@@ -105,12 +105,7 @@ def _compare(cfg, noise, orc, o, eng, counts, s):
         a, b = o['call_ph_off'][k], o['call_ph_off'][k + 1]
         c, e = ph['set_off'][i], ph['set_off'][i + 1]
         assert b - a == e - c, f'call {k}, set {i}: {b - a} vs {e - c} photons'
-        ko = np.lexsort((o['ph_gain'][a:b], o['ph_t'][a:b], o['ph_ch'][a:b]))
-        kg = np.lexsort((ph['gain'][c:e], ph['t'][c:e], ph['ch'][c:e]))
-        assert np.array_equal(o['ph_ch'][a:b][ko], ph['ch'][c:e][kg]), (k, i)
-        assert np.array_equal(o['ph_t'][a:b][ko], ph['t'][c:e][kg]), (k, i)
-        assert np.array_equal(o['ph_gain'][a:b][ko], ph['gain'][c:e][kg]), (k, i)
-        assert np.array_equal(o['ph_dpe'][a:b][ko], ph['dpe'][c:e][kg]), (k, i)
+    assert_tiles_in_oracle_order(eng, o, sets)
     g = eng.groups()
     keep = g['right'] >= g['left']
     assert np.array_equal(g['left'][keep], o['dg_left']) and np.array_equal(g['right'][keep], o['dg_right'])

@@ -3,7 +3,7 @@ import numpy as np
 import pytest
 
 import wfsim_amd
-from tests.helpers import (OPTICAL_CHAINS, golden, make_engine, make_oracle, optical_chain_config, photons_by_call_and_channel)
+from tests.helpers import (OPTICAL_CHAINS, assert_tiles_in_oracle_order, golden, make_engine, make_oracle, optical_chain_config, photons_by_call_and_channel)
 from wfsim_amd.config import xenonnt_test_config
 from wfsim_amd.dtypes import instruction_dtype, optical_extra_dtype, truth_extra_dtype
 
@@ -228,6 +228,9 @@ def test_raw_data_optical_on_the_reference_inputs(case):
         assert mo.sum() == mg.sum() == d['truth']['n_photon'][k], k
         for f, g in [('ph_ch', 'ch'), ('ph_t', 't'), ('ph_gain', 'gain'), ('ph_dpe', 'dpe')]:
             assert np.array_equal(o[f][a:b][mo][ko], ph[g][c:e][mg][kg]), (k, f)
+    # DESIGN.md 4 leaves the order of supplied photons inside a channel unpinned against the REFERENCE (numpy's unstable argsort); device and
+    # oracle both keep the input's order, so between them the tiles are compared in order
+    assert_tiles_in_oracle_order(rd.engine, o, list(range(len(ins))), live=live)
     # ---- photons per call and channel as the reference's sim_primary left them
     chan_of = lambda off, ch: [np.bincount(np.asarray(ch[a:b])[live[ch[a:b]]], minlength=120).tolist() for a, b in zip(off[:-1], off[1:])]
     assert chan_of(ph['set_off'], ph['ch']) == chan_of(d['call_in_off'], d['in_ch'])

@@ -23,7 +23,7 @@ import pytest
 
 from tests import pulse_edges as PE
 from tests import spe_channels as SC
-from tests.helpers import ap_tables_from_golden, make_engine, optical_chain_config, pulse_edges_config, with_fma
+from tests.helpers import ap_tables_from_golden, assert_tiles_in_oracle_order, make_engine, optical_chain_config, pulse_edges_config, with_fma
 from tests.test_gpu_generation import _call_sets
 from tests.test_spe_channels_reference import MS, SUPPLIED_OVERRIDES, oracle_on_instructions, oracle_on_supplied_photons, table_of
 from wfsim_amd import tables as T
@@ -62,7 +62,9 @@ def _per_pmt_of_call(cfg, o, call):
 
 
 def _compare(family, cfg, orc, o, eng, counts, sets, must_hit=None):
-    """device against oracle, set by set (sets[k]: the device pulse set of oracle call k); returns the photons of the primary calls"""
+    """device against oracle, set by set (sets[k]: the device pulse set of oracle call k); returns the photons of the primary calls.
+    Every tile in the oracle's order (tests/helpers.py: assert_tiles_in_oracle_order) -- supplied photons (load_optical) too: DESIGN.md 4
+    leaves their order inside a channel unpinned against the REFERENCE (numpy's unstable argsort), device and oracle both keep the input's."""
     G = np.asarray(cfg['gains'], dtype=np.float64)
     n_ch = len(G)
     ph = eng.photons()
@@ -77,6 +79,7 @@ def _compare(family, cfg, orc, o, eng, counts, sets, must_hit=None):
         kg = mg[np.lexsort((ph['gain'][c:e][mg], ph['t'][c:e][mg], ph['ch'][c:e][mg]))]
         for f, g in [('ph_ch', 'ch'), ('ph_t', 't'), ('ph_dpe', 'dpe'), ('ph_gain', 'gain')]:
             assert np.array_equal(o[f][a:b][ko], ph[g][c:e][kg]), (k, i, f)
+    assert_tiles_in_oracle_order(eng, o, sets, live=G > 0)
     g = eng.groups()
     keep = g['right'] >= g['left']
     assert np.array_equal(g['left'][keep], o['dg_left']) and np.array_equal(g['right'][keep], o['dg_right'])

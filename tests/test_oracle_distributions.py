@@ -161,7 +161,7 @@ def test_s2_photon_times_and_survival():
     assert abs(t.mean() - m) < 6 * s / np.sqrt(ne.sum()) and abs(t.std() / s - 1) < 0.03
 
 
-@pytest.mark.parametrize('lam', [0.3, 9.9, 17.5, 82.03, 216.9, 400.0])
+@pytest.mark.parametrize('lam', [0.3, 9.9, 17.5, 82.03, 216.9, 217.0, float(np.nextafter(217.0, np.inf)), 400.0, 1000.0])          # (217: POIS_LAM_MAX of the device's table)
 def test_photons_per_electron_are_poisson(orc, lam):
     """the per-instruction Poisson table (gains up to 217) and PTRS (above) against scipy's exact pmf: chi-square over the
     populated values, mean and variance"""
