@@ -8,27 +8,10 @@
 #include "wfs_tilegen.h"
 #include "wfs_boundary.h"
 #include "wfs_devbuf.h"
+#include "wfs_family.h"
 #include "wfs_batch.h"
 #include "wfs_pack_fence.h"
 #include "../../include/wfsim_amd.h"
-
-// Every pulse kernel exists in two forms: FMA = true (wfs_config.fma, one rounding per template * gain term) and FMA = false (numpy's two
-// roundings, currents bit-exact with the reference).  The handle's switch picks one at launch time.
-#define K_S2_TILE(F) k_s2_tile<false, F>
-#define K_S2_TILE_AP(F) k_s2_tile<true, F>
-#define K_S2_BRIGHT(F) k_s2_bright<false, F>
-#define K_S2_BRIGHT_AP(F) k_s2_bright<true, F>
-#define K_PULSE_256_RES(F) k_pulse<256, true, F>
-#define K_PULSE_128_RES(F) k_pulse<128, true, F>
-#define K_PULSE_256_WIN(F) k_pulse<256, false, F>
-#define K_PULSE_128_WIN(F) k_pulse<128, false, F>
-#define K_PULSE_GENERIC(F) k_pulse_generic<256, F>
-#define K_PULSE_SPARSE(F) k_pulse_sparse<SPARSE_TPB, F>
-#define K_PULSE_TINY(F) k_pulse_tiny<F>
-#define K_PULSE_WAVE(F) k_pulse_wave<F>
-#define WFS_LAUNCH_F(h, KM, grid, block, lds, ...) do { \
-    if ((h)->cfg.fma) hipLaunchKernelGGL(HIP_KERNEL_NAME(KM(true)), grid, block, lds, (h)->stream, __VA_ARGS__); \
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(KM(false)), grid, block, lds, (h)->stream, __VA_ARGS__); } while (0)
 
 #include <algorithm>
 #include <cstdio>
@@ -344,12 +327,12 @@ void stat5(double *o, double n, double s1, double s2, double origin, i64 lo, i64
     o[4] = n > 0 ? sqrt(var > 0 ? var : 0) : NAN;
 }
 
-// Brackets one kernel launch: HIP events when profiling is on; with wfs_set_debug bit 3 the launch is checked on the spot
-// (hipGetLastError + a stream synchronisation), so that a failed launch or a faulting kernel is reported under its own name
-// instead of ~25 launches later at the end of wfs_run.
+// Brackets one kernel launch, or several under one name: HIP events when profiling is on; with wfs_set_debug bit 3 what was launched is
+// checked on the spot (hipGetLastError + a stream synchronisation), so that a failed launch or a faulting kernel is reported under its
+// own name instead of ~25 launches later at the end of wfs_run.  timed = false: the check alone, no entry in wfs_kernel_times.
 struct Timer {
     wfs_handle *h; bool on; const char *name;
-    Timer(wfs_handle *h_, const char *name_) : h(h_), on(h_->profiling != 0), name(name_)
+    Timer(wfs_handle *h_, const char *name_, bool timed = true) : h(h_), on(timed && h_->profiling != 0), name(name_)
     {
         if (!on) return;
         KernelTime kt; kt.name = name;
@@ -371,6 +354,72 @@ struct Timer {
 
 // grid size for n items; never 0 (a launch with an empty grid is an error, every kernel bounds-checks its index)
 inline unsigned nblocks(i64 n, int tpb) { return n > 0 ? (unsigned)((n + tpb - 1) / tpb) : 1u; }
+
+// The shape of a launch.  The recurring ones have names: a thread, a wave or a workgroup per item.
+struct Shape {
+    dim3 grid, block; size_t lds = 0;
+    bool elsewhere = false; hipStream_t other = nullptr;      // on(): not the handle's stream
+    Shape(dim3 grid_, dim3 block_, size_t lds_ = 0) : grid(grid_), block(block_), lds(lds_) {}
+    Shape on(hipStream_t s) const { Shape r = *this; r.elsewhere = true; r.other = s; return r; }
+};
+inline Shape per_thread(i64 n, int tpb = 256) { return Shape(dim3(nblocks(n, tpb)), dim3((unsigned)tpb)); }
+inline Shape per_wave(i64 n, size_t lds = 0) { return Shape(dim3(nblocks(n, 4)), dim3(256), lds); }                  // four waves of 64 to a workgroup
+inline Shape per_group(i64 n, int tpb = 256, size_t lds = 0) { return Shape(dim3((unsigned)n), dim3((unsigned)tpb), lds); }      // (the callers have n > 0)
+
+// The one way a kernel is launched: under a Timer of its own name, on the handle's stream unless the shape names another (the packers;
+// their entry is recorded on the main stream all the same).  A null kernel -- a family member picked with an index outside its axis --
+// is refused and nothing is launched.
+template <class... P, class... A> int launch_as(wfs_handle *h, bool timed, Kernel<void (*)(P...)> k, const Shape &s, A &&...args)
+{
+    if (!k.fn) return h->fail(WFS_E_STATE, std::string("internal: kernel family ") + k.name + " has no such member");
+    Timer t(h, k.name, timed);
+    hipLaunchKernelGGL(k.fn, s.grid, s.block, s.lds, s.elsewhere ? s.other : h->stream, std::forward<A>(args)...);
+    return WFS_OK;
+}
+template <class K, class... A> int launch(wfs_handle *h, K k, const Shape &s, A &&...args) { return launch_as(h, true, k, s, std::forward<A>(args)...); }
+// Not timed: no entry in wfs_kernel_times, the check of bit 3 under the kernel's own name all the same.  For the launches inside a Timer
+// scope that brackets several under one name, and for those outside the profiled step.
+template <class K, class... A> int launch_untimed(wfs_handle *h, K k, const Shape &s, A &&...args) { return launch_as(h, false, k, s, std::forward<A>(args)...); }
+// a kernel that is no template, under its own name
+#define PLAIN(k) kernel(&k, #k)
+
+// ---- The kernel families of this file: every template kernel's instantiations, each axis with what picks it at run time.
+// fma: every pulse kernel exists in two forms, FMA = true (wfs_config.fma, one rounding per template * gain term) and FMA = false (numpy's
+//      two roundings, currents bit-exact with the reference); cfg.fma picks one at launch time.
+// ap:  batch.ap_sets -- PMT afterpulses are on and the batch has sets that take them (run_generation's ap_on).
+// ext: batch.ins_models -- some instruction carries a delay model of its own (wfs_set_delay_models).
+// nk:  noise_kind_of(dev) when the configuration enables noise, else NOISE_NONE (RowsRun::noise_kind).  The row kernels take the kind as
+//      a template parameter (no branch between their loads): NoiseKind of wfs_noise.h, 0 none, 1 int16 table, 2 float table, 3 the
+//      noise model, 4 the noise model with a colour, 5 the same with slow levels.
+// dk:  dev.dk_thr -- PMT dark counts are set (wfs_set_dark_counts); with the feature off the row kernels are the kernels they were.
+// The cap is the LDS_CAP_ constant of wfs_layout.h, checked there against the largest total of the kernel's layout; wfs_create raises
+// the limit of every member that has one.
+constexpr int LDS_CAP_GRANT = -1;       // k_s2_bright: what the device grants one workgroup, worked out by wfs_create
+const auto K_S2_TILE = family<2, 2>("k_s2_tile", LDS_CAP_TILE, [](auto ap, auto fma) { return &k_s2_tile<ap() != 0, fma() != 0>; });
+const auto K_S2_TILE_GEN = family<2>("k_s2_tile_gen", 0, [](auto ap) { return &k_s2_tile_gen<ap() != 0>; });
+const auto K_S2_BRIGHT = family<2, 2>("k_s2_bright", LDS_CAP_GRANT, [](auto ap, auto fma) { return &k_s2_bright<ap() != 0, fma() != 0>; });
+const auto K_PHOTON_FILL = family<2, 2>("k_photon_fill", LDS_CAP_FILL, [](auto ap, auto ext) { return &k_photon_fill<ap() != 0, ext() != 0>; });
+// k_pulse: wide -- 256 threads, not 128: the `small` rule of run_pulses (tiles of few samples); res -- the `resident` rule there
+// (the templates of the tile's dt sit in LDS)
+const auto K_PULSE = family<2, 2, 2>("k_pulse_dense", LDS_CAP_PULSE, [](auto wide, auto res, auto fma) { return &k_pulse<wide() ? 256 : 128, res() != 0, fma() != 0>; });
+const auto K_PULSE_GENERIC = family<2>("k_pulse_generic", LDS_CAP_GENERIC, [](auto fma) { return &k_pulse_generic<256, fma() != 0>; });
+const auto K_PULSE_SPARSE = family<2>("k_pulse_sparse", LDS_CAP_SPARSE, [](auto fma) { return &k_pulse_sparse<SPARSE_TPB, fma() != 0>; });
+const auto K_PULSE_TINY = family<2>("k_pulse_tiny", 0, [](auto fma) { return &k_pulse_tiny<fma() != 0>; });
+const auto K_PULSE_WAVE = family<2>("k_pulse_wave", 0, [](auto fma) { return &k_pulse_wave<fma() != 0>; });
+// k_row_pulse: seg -- the long rows of a run, which take several segments of res_max_len samples (run_rows' second part); they alone
+// ask for more LDS than the default limit
+const auto K_ROW_PULSE = family<NOISE_KINDS, 2, 2, 2>("k_row_pulse", [](int, int, int seg, int) { return seg ? LDS_CAP_ROW : 0; },
+                                                      [](auto nk, auto fma, auto seg, auto dk) { return &k_row_pulse<nk(), fma() != 0, seg() != 0, dk() != 0>; });
+const auto K_ROW_EMPTY = family<NOISE_KINDS, 2>("k_row_empty", 0, [](auto nk, auto dk) { return &k_row_empty<nk(), dk() != 0>; });
+const auto K_ZLE = family<NOISE_KINDS, 2>("k_zle", 0, [](auto nk, auto dk) { return &k_zle<nk(), dk() != 0>; });
+const auto K_PACK = family<NOISE_KINDS, 2>("k_pack", 0, [](auto nk, auto dk) { return &k_pack<nk(), dk() != 0>; });
+// place: the second of the two passes (count, then place) of the afterpulse segments and of the optical load
+const auto K_AP_SEG = family<2>("k_ap_seg", 0, [](auto place) { return &k_ap_seg<place() != 0>; });
+const auto K_OPTICAL_BUCKET = family<2>("k_optical_bucket", 0, [](auto place) { return &k_optical_bucket<place() != 0>; });
+// slow: noise_kind_of(dev) == NOISE_SLOW, the probe of a colour with slow levels
+const auto K_NOISE_COLOUR_SAMPLES = family<2>("k_noise_colour_samples", 0, [](auto slow) { return &k_noise_colour_samples<slow() != 0>; });
+// (no template, but a cap)
+const auto K_TILE_ORDER_BIG = family<1>("k_tile_order_big", LDS_CAP_ORDER, [](auto) { return &k_tile_order_big; });
 
 // The fills of one stage, collected and written by one dispatch of k_fill_group instead of one runtime fill or fill kernel each.
 // A stage adds its segments where it used to fill them and calls flush() before it launches the first kernel that reads or writes
@@ -405,7 +454,7 @@ struct FillGroup {
         if (n == 0) return WFS_OK;
         // 64 bytes per thread of the longest segment, at most 1024 workgroups per segment (the rest is the grid stride)
         const unsigned gx = (unsigned)std::min<size_t>((longest + 256 * 64 - 1) / (256 * 64), 1024);
-        { Timer t(h, name); hipLaunchKernelGGL(k_fill_group, dim3(gx, (unsigned)n), dim3(256), 0, h->stream, a); }
+        TRY(launch(h, kernel(&k_fill_group, name), Shape(dim3(gx, (unsigned)n), dim3(256)), a));
         n = 0; longest = 0;
         return WFS_OK;
     }
@@ -418,9 +467,9 @@ int scan_into(wfs_handle *h, const i32 *in, i64 n, i64 *outp, i64 WfsScal::*tota
     TRY(ensure(h, h->scan_tmp, (size_t)nb));
     i64 *total = &(h->scal.p()->*total_member);       // (a device address: computed, never dereferenced here)
     if (n == 0) { h->zero64 = offset; TRY(copy_async(h, outp, &h->zero64, 1, hipMemcpyHostToDevice)); HIPCHK(hipMemsetAsync(total, 0, sizeof *total, h->stream)); return WFS_OK; }
-    { Timer t(h, "k_scan_reduce"); hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)nb), dim3(SCAN_TPB), 0, h->stream, in, n, h->scan_tmp.p()); }
-    { Timer t(h, "k_scan_spine"); hipLaunchKernelGGL(k_scan_spine, dim3(1), dim3(1024), 0, h->stream, h->scan_tmp.p(), nb, total); }
-    { Timer t(h, "k_scan_down"); hipLaunchKernelGGL(k_scan_down, dim3((unsigned)nb), dim3(SCAN_TPB), 0, h->stream, in, n, h->scan_tmp.p(), outp, offset); }
+    TRY(launch(h, PLAIN(k_scan_reduce), per_group(nb, SCAN_TPB), in, n, h->scan_tmp.p()));
+    TRY(launch(h, PLAIN(k_scan_spine), Shape(dim3(1), dim3(1024)), h->scan_tmp.p(), nb, total));
+    TRY(launch(h, PLAIN(k_scan_down), per_group(nb, SCAN_TPB), in, n, h->scan_tmp.p(), outp, offset));
     return WFS_OK;
 }
 
@@ -441,7 +490,7 @@ int read_scal(wfs_handle *h)
     if (h->publish && h->own_stream && !(h->debug_bits & DBG_CHECK_LAUNCHES)) {
         const u64 seq = ++h->seq;
         // (the profiled step counts the boundaries that publish: one "k_publish" entry each, none for one that copies)
-        { Timer t(h, "k_publish"); hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, h->stream, h->scal.p(), h->d_hscal, h->d_hseq, seq); }
+        TRY(launch(h, PLAIN(k_publish), Shape(dim3(1), dim3(64)), h->scal.p(), h->d_hscal, h->d_hseq, seq));
         hipError_t qe = hipSuccess;
         const WfsWait w = wfs_wait_seq(h->h_seq, seq, [&]() {
             qe = hipStreamQuery(h->stream);
@@ -458,30 +507,16 @@ int read_scal(wfs_handle *h)
     return WFS_OK;
 }
 
-// The row kernels take the kind of noise as a template parameter (no branch between their loads): NoiseKind of wfs_noise.h, 0 none,
-// 1 int16 table, 2 float table, 3 the noise model, 4 the noise model with a colour, 5 the same with slow levels.
-// The kind that the device view holds, whether or not the configuration enables noise (wfs_run asks d.enable_noise first):
+// The kind of noise (the nk axis of the row kernels' families) that the device view holds, whether or not the configuration enables noise (wfs_run asks d.enable_noise first):
 static NoiseKind noise_kind_of(const WfsDev &d)
 {
     if (d.nm_cells) return d.ns_shift ? NOISE_SLOW : (d.nc_taps ? NOISE_COLOUR : NOISE_MODEL);
     return d.noise_f ? NOISE_TABLE_F64 : (d.noise ? NOISE_TABLE_I16 : NOISE_NONE);
 }
-// f is called with a std::integral_constant of the kind.
-template <class F, int... K> void with_noise_kind(int kind, F &&f, std::integer_sequence<int, K...>)
-{
-    (void)((kind == K && (f(std::integral_constant<int, K>{}), true)) || ...);
-}
-template <class F> void with_noise_kind(int kind, F &&f) { with_noise_kind(kind, f, std::make_integer_sequence<int, NOISE_KINDS>{}); }
-// The row kernels that finish samples take the dark counts (wfs_set_dark_counts) as a second template parameter, DK: with the feature
-// off they are the kernels they were.  f is called with the kind and a std::bool_constant of the switch.
-template <class F> void with_row_kind(int kind, bool dark, F &&f)
-{
-    with_noise_kind(kind, [&](auto nk) { if (dark) f(nk, std::true_type{}); else f(nk, std::false_type{}); });
-}
 
 // What the probe entry points of the noise model share once they know their stream: the checks of (t0, n, out), a scratch buffer of n
-// elements, the launch into it (launch(T *device_buffer): timer and kernel) and the copy back.  fn: the entry point, for the messages.
-template <class T, class Launch> int noise_probe(wfs_handle *h, const char *fn, int64_t t0, int64_t n, T *out, Launch &&launch)
+// elements, the launch into it (probe(T *device_buffer), which hands back launch's code) and the copy back.  fn: the entry point, for the messages.
+template <class T, class Probe> int noise_probe(wfs_handle *h, const char *fn, int64_t t0, int64_t n, T *out, Probe &&probe)
 {
     if (n < 0 || n > ((i64)1 << 30) || (n > 0 && !out)) return h->fail(WFS_E_INVALID, std::string(fn) + ": n outside 0 .. 2^30 or null buffer");
     if (t0 > I64_MAX - n) return h->fail(WFS_E_INVALID, std::string(fn) + ": t0 + n overflows");
@@ -489,7 +524,7 @@ template <class T, class Launch> int noise_probe(wfs_handle *h, const char *fn, 
     HIPCHK(hipSetDevice(h->device));
     DevArr<T> buf;
     TRY(ensure(h, buf, (size_t)n));
-    launch(buf.p());
+    TRY(probe(buf.p()));
     HIPCHK(hipGetLastError());
     TRY(copy_async(h, out, buf.p(), (size_t)n, hipMemcpyDeviceToHost));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -788,33 +823,22 @@ try {
     refresh_dev(h);
     if (const char *e = getenv("WFS_TAP_SPARSE_MAX")) h->tap_sparse_max = std::min(atoi(e), TAP_LIST_LEN - 1);      // tuning knob of tap_block (results do not depend on it)
     if (build_time_tables(h) != WFS_OK) return WFS_E_HIP;
-    // dynamic-LDS caps: the LDS_CAP_ constants of wfs_layout.h, each checked there against the largest total of its kernel's layout
-#define WFS_BIG_LDS(K, B) hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, (B))
-#define WFS_BIG_LDS_F(KM, B) do { WFS_BIG_LDS(HIP_KERNEL_NAME(KM(true)), B); WFS_BIG_LDS(HIP_KERNEL_NAME(KM(false)), B); } while (0)
-    WFS_BIG_LDS_F(K_PULSE_256_RES, LDS_CAP_PULSE); WFS_BIG_LDS_F(K_PULSE_128_RES, LDS_CAP_PULSE); WFS_BIG_LDS_F(K_PULSE_256_WIN, LDS_CAP_PULSE); WFS_BIG_LDS_F(K_PULSE_128_WIN, LDS_CAP_PULSE);
-    WFS_BIG_LDS(HIP_KERNEL_NAME(k_photon_fill<false, false>), LDS_CAP_FILL); WFS_BIG_LDS(HIP_KERNEL_NAME(k_photon_fill<true, false>), LDS_CAP_FILL);
-    WFS_BIG_LDS(HIP_KERNEL_NAME(k_photon_fill<false, true>), LDS_CAP_FILL); WFS_BIG_LDS(HIP_KERNEL_NAME(k_photon_fill<true, true>), LDS_CAP_FILL);
-    WFS_BIG_LDS(k_tile_order_big, LDS_CAP_ORDER);
-    WFS_BIG_LDS_F(K_PULSE_GENERIC, LDS_CAP_GENERIC);
-#define K_ROW_PULSE_SEG(F) k_row_pulse<NK, F, true, DK>
-    for (int kind = 0; kind < NOISE_KINDS; kind++)           // every kind that with_row_kind can launch, with and without dark counts
-        for (int dark = 0; dark < 2; dark++)
-            with_row_kind(kind, dark != 0, [](auto nk, auto dk) { constexpr int NK = decltype(nk)::value; constexpr bool DK = decltype(dk)::value; WFS_BIG_LDS_F(K_ROW_PULSE_SEG, LDS_CAP_ROW); });
     if (const char *e = getenv("WFS_ROW_RESIDENT")) h->res_env = atoi(e);          // 0 / 1 / 2 as the config switch (A/B runs)
     if (const char *e = getenv("WFS_FULL_READOUT_MAX_SAMPLES")) h->full_max_samples = std::max<i64>(0, atoll(e));      // capacity knob of full readout (tests)
     if (const char *e = getenv("WFS_RES_MAX_LEN")) h->res_max_len = std::max(256, std::min(atoi(e), RES_MAX_LEN)) / 256 * 256;      // tuning knob (results do not depend on it)
-    WFS_BIG_LDS_F(K_S2_TILE, LDS_CAP_TILE); WFS_BIG_LDS_F(K_S2_TILE_AP, LDS_CAP_TILE);
-    WFS_BIG_LDS_F(K_PULSE_SPARSE, LDS_CAP_SPARSE);
     {   // k_s2_bright: what the device grants one workgroup, less the SPE row, the afterpulse stage and the kernel's static arrays
         int granted = 0;
         if (hipDeviceGetAttribute(&granted, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess || granted <= 0) granted = 64 * 1024;
         h->bright_lds = bright_lds_of_grant(granted);
         h->bright_max_bins = bright_bins_of_lds(h->bright_lds);
         if (const char *e = getenv("WFS_BRIGHT_MAX_BINS")) h->bright_max_bins = std::max(0, std::min(atoi(e), h->bright_max_bins));      // tuning knob (results do not depend on it)
-        const int total = bright_lds_layout(h->bright_lds, true).total;      // (the AP forms: the largest layout)
-        WFS_BIG_LDS(HIP_KERNEL_NAME(k_s2_bright<false, false>), total); WFS_BIG_LDS(HIP_KERNEL_NAME(k_s2_bright<false, true>), total);
-        WFS_BIG_LDS(HIP_KERNEL_NAME(k_s2_bright<true, false>), total); WFS_BIG_LDS(HIP_KERNEL_NAME(k_s2_bright<true, true>), total);
     }
+    // dynamic-LDS caps: every member with a cap of every family that declares one (k_s2_bright: the AP forms' layout, the largest)
+    const int bright_cap = bright_lds_layout(h->bright_lds, true).total;
+    FamilyBase::each([&](const FamilyBase &f) {
+        for (int m = 0; m < f.size(); m++)
+            if (const int cap = f.lds_cap(m)) hipFuncSetAttribute(f.address(m), hipFuncAttributeMaxDynamicSharedMemorySize, cap == LDS_CAP_GRANT ? bright_cap : cap);
+    });
     *out = owner.release();
     return WFS_OK;
 } WFS_CATCH(nullptr)
@@ -1156,10 +1180,10 @@ static void map_args(const wfs_handle::PatternMap &pm, MapArgs &m)
     m.cnx = pm.cnx; m.cny = pm.cny; m.cell_lo[0] = pm.cell_lo[0]; m.cell_lo[1] = pm.cell_lo[1]; m.cell_h = pm.cell_h;
 }
 
-static void launch_neighbours(wfs_handle *h, const MapArgs &m)
+static int launch_neighbours(wfs_handle *h, const MapArgs &m)
 {
-    if (m.points) { Timer t(h, "k_map_neighbours_points"); hipLaunchKernelGGL(k_map_neighbours_points, dim3(nblocks(m.n_rows, 4)), dim3(256), 0, h->stream, m); }
-    else { Timer t(h, "k_map_neighbours"); hipLaunchKernelGGL(k_map_neighbours, dim3(nblocks(m.n_rows, 128)), dim3(128), 0, h->stream, m); }
+    if (m.points) return launch(h, PLAIN(k_map_neighbours_points), per_wave(m.n_rows), m);
+    return launch(h, PLAIN(k_map_neighbours), per_thread(m.n_rows, 128), m);
 }
 
 int wfs_set_pattern_map(wfs_handle *h, int32_t which, int32_t dims, const int32_t *n_nodes, const double *lo, const double *hi,
@@ -1333,19 +1357,19 @@ static int scalar_map_eval(wfs_handle *h, int32_t map_id, int64_t n, const doubl
     TRY(upload(h, h->smap_pos, pos, (size_t)n * dims)); TRY(ensure(h, h->smap_out, (size_t)n * nv));
     if (sm.kind == 2) {
         SplineArgs a{sm.nx, sm.ny, sm.kx, sm.ky, sm.tx.p(), sm.ty.p(), sm.c.p(), n, h->smap_pos.p(), h->smap_out.p()};
-        Timer t(h, "k_map_spline"); hipLaunchKernelGGL(k_map_spline, dim3(nblocks(n, 128)), dim3(128), 0, h->stream, a);
+        TRY(launch(h, PLAIN(k_map_spline), per_thread(n, 128), a));
     } else if (sm.kind == 3) {
         LinearMapArgs a{};
         a.dims = dims; a.nv = nv; a.values = sm.values.p(); a.n_rows = n; a.pos = h->smap_pos.p(); a.out = h->smap_out.p();
         for (int q = 0; q < 3; q++) { a.n[q] = sm.g.n[q]; a.lo[q] = sm.g.lo[q]; a.h[q] = sm.g.hgrid[q]; }
-        Timer t(h, "k_map_linear"); hipLaunchKernelGGL(k_map_linear, dim3(nblocks(n * nv, 128)), dim3(128), 0, h->stream, a);
+        TRY(launch(h, PLAIN(k_map_linear), per_thread(n * nv, 128), a));
     } else {
         TRY(ensure(h, h->smap_nb_idx, (size_t)n * MAP_K)); TRY(ensure(h, h->smap_nb_w, (size_t)n * MAP_K));
         MapArgs m{};
         map_args(sm.g, m);
         m.n_rows = n; m.pos = h->smap_pos.p(); m.nb_idx = h->smap_nb_idx.p(); m.nb_w = h->smap_nb_w.p();
-        launch_neighbours(h, m);
-        { Timer t(h, "k_map_scalar"); hipLaunchKernelGGL(k_map_scalar, dim3(nblocks(n * nv, 128)), dim3(128), 0, h->stream, m, sm.values.p(), h->smap_out.p(), nv); }
+        TRY(launch_neighbours(h, m));
+        TRY(launch(h, PLAIN(k_map_scalar), per_thread(n * nv, 128), m, sm.values.p(), h->smap_out.p(), nv));
     }
     TRY(copy_async(h, out, h->smap_out.p(), (size_t)n * nv, hipMemcpyDeviceToHost));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1387,8 +1411,8 @@ try {
         m.x = h->map_x.p(); m.y = h->map_y.p(); m.z = h->map_z.p();
         m.nb_idx = h->map_nb_idx[w].p(); m.nb_w = h->map_nb_w[w].p();
         m.cdf_table = h->cdf_table.p(); m.gains = h->t_gains.p();
-        launch_neighbours(h, m);
-        { Timer t(h, "k_map_rows"); hipLaunchKernelGGL(k_map_rows, dim3((unsigned)nr), dim3(256), (size_t)map_rows_lds(nch).total, h->stream, m, nch); }
+        TRY(launch_neighbours(h, m));
+        TRY(launch(h, PLAIN(k_map_rows), per_group(nr, 256, (size_t)map_rows_lds(nch).total), m, nch));
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipGetLastError());
@@ -1568,9 +1592,10 @@ try {
     }
     OptLoadArgs oa{n, h->opt_first.p(), h->opt_last.p(), h->opt_ch.p(), h->opt_time.p(), cutoff, h->t_gains.p(),
                    h->tile_count.p(), h->tile_off.p(), h->tile_cursor.p(), h->opt_t.p(), h->opt_item.p(), h->scal.p()};
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_optical_bucket<false>), dim3(nblocks(n, 256)), dim3(256), 0, h->stream, h->dev, oa);
+    // (not timed: part of the load, whose entries wfs_run clears before anyone can read them)
+    TRY(launch_untimed(h, K_OPTICAL_BUCKET(false), per_thread(n), h->dev, oa));
     TRY(scan_into(h, h->tile_count.p(), T, h->tile_off.p(), &WfsScal::n_tile_photons, 0));
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_optical_bucket<true>), dim3(nblocks(n, 256)), dim3(256), 0, h->stream, h->dev, oa);
+    TRY(launch_untimed(h, K_OPTICAL_BUCKET(true), per_thread(n), h->dev, oa));      // (not timed: as the count pass above)
     TRY(read_scal(h));
     HIPCHK(hipGetLastError());
     TRY(device_error(h, h->h_scal->opt_error));
@@ -1663,22 +1688,22 @@ static int gen_electrons(wfs_handle *h, GenRun &r, FillGroup &fg)
             TRY(ensure(h, h->row_pmax, (size_t)n_rows)); f.row_pmax = h->row_pmax.p();
             TRY(fg.flush());
             Timer t(h, "k_fuse_decide");
-            hipLaunchKernelGGL(k_row_pmax, dim3(nblocks(n_rows, 4)), dim3(256), 0, h->stream, f.cdf_table, d.n_tpc, n_rows, h->row_pmax.p());
-            hipLaunchKernelGGL(k_fuse_decide, dim3(nblocks(N, 256)), dim3(256), 0, h->stream, f);
+            TRY(launch_untimed(h, PLAIN(k_row_pmax), per_wave(n_rows), f.cdf_table, d.n_tpc, n_rows, h->row_pmax.p()));
+            TRY(launch_untimed(h, PLAIN(k_fuse_decide), per_thread(N), f));
         }
         g.ins_fused = f.ins_fused;
     }
     TRY(fg.flush());
-    { Timer t(h, "k_s1_hits"); hipLaunchKernelGGL(k_s1_hits, dim3(nblocks(N, 4)), dim3(256), 0, h->stream, d, g); }
+    TRY(launch(h, PLAIN(k_s1_hits), per_wave(N), d, g));
     {
         const i64 neb = (E + 255) / 256;
         TRY(ensure(h, h->eblk_ins, (size_t)(neb + 1))); g.eblk_ins = h->eblk_ins.p();
-        { Timer t(h, "k_emitter_blocks"); hipLaunchKernelGGL(k_emitter_blocks, dim3(nblocks(neb + 1, 256)), dim3(256), 0, h->stream, g, neb); }
+        TRY(launch(h, PLAIN(k_emitter_blocks), per_thread(neb + 1), g, neb));
         TRY(ensure(h, h->pois_cdf, (size_t)N * POIS_W)); TRY(ensure(h, h->pois_kmin, (size_t)N));
         g.pois_cdf = h->pois_cdf.p(); g.pois_kmin = h->pois_kmin.p();
-        { Timer t(h, "k_poisson_tables"); hipLaunchKernelGGL(k_poisson_tables, dim3((unsigned)N), dim3(POIS_W), 0, h->stream, g, h->pois_cdf.p(), h->pois_kmin.p()); }
-        { Timer t(h, "k_s2_electrons"); hipLaunchKernelGGL(k_s2_electrons, dim3(nblocks(E, 256)), dim3(256), 0, h->stream, d, g); }
-        if (h->batch.any_ptrs) { Timer t(h, "k_s2_photons"); hipLaunchKernelGGL(k_s2_photons, dim3(nblocks(E, 256)), dim3(256), 0, h->stream, d, g); }
+        TRY(launch(h, PLAIN(k_poisson_tables), per_group(N, POIS_W), g, h->pois_cdf.p(), h->pois_kmin.p()));
+        TRY(launch(h, PLAIN(k_s2_electrons), per_thread(E), d, g));
+        if (h->batch.any_ptrs) TRY(launch(h, PLAIN(k_s2_photons), per_thread(E), d, g));
     }
     if (h->batch.n_diff_rows > 0) {
         // transverse diffusion maps: the pattern of these instructions is the average over their surviving electrons (s2.py:560-613)
@@ -1692,9 +1717,9 @@ static int gen_electrons(wfs_handle *h, GenRun &r, FillGroup &fg)
         m.cdf_table = h->cdf_table.p(); m.gains = h->t_gains.p();
         m.aft = h->batch.ins_aft_set ? h->ins_aft.p() : nullptr; m.n_top = h->cfg.n_top;
         DiffArgs q{nr, m.row_ins, h->ins_sigr.p(), h->ins_siga.p(), h->batch.diff_r2, h->diff_pre.p()};
-        { Timer t(h, "k_diffuse_patterns"); hipLaunchKernelGGL(k_diffuse_patterns, dim3((unsigned)nr), dim3(256), 0, h->stream, d, g, m, q); }
+        TRY(launch(h, PLAIN(k_diffuse_patterns), per_group(nr), d, g, m, q));
         m.pre = h->diff_pre.p();
-        { Timer t(h, "k_map_rows"); hipLaunchKernelGGL(k_map_rows, dim3((unsigned)nr), dim3(256), (size_t)map_rows_lds(d.n_tpc).total, h->stream, m, d.n_tpc); }
+        TRY(launch(h, PLAIN(k_map_rows), per_group(nr, 256, (size_t)map_rows_lds(d.n_tpc).total), m, d.n_tpc));
     }
     const i64 TP = r.TP = h->batch.n_psets * d.n_tpc;
     TRY(ensure(h, h->tile_count, (size_t)T)); TRY(ensure(h, h->tile_cursor, (size_t)T));
@@ -1708,7 +1733,7 @@ static int gen_electrons(wfs_handle *h, GenRun &r, FillGroup &fg)
     TRY(ensure(h, h->tile_off, (size_t)(T + 1)));
     if (h->run.fuse_on) {
         // surviving electrons compacted per instruction, tile buffers sized from their time range, photons per tile (Poisson)
-        { Timer t(h, "k_fuse_electrons"); hipLaunchKernelGGL(k_fuse_electrons, dim3((unsigned)N), dim3(256), 0, h->stream, d, f); }
+        TRY(launch(h, PLAIN(k_fuse_electrons), per_group(N), d, f));
         TRY(scan(h, h->ins_bcap_all.p(), N, h->ins_boff, &WfsScal::n_tbuf_samples));
         // (the work list: TP entries for the tiles of k_s2_tile, from the front and from the back, and TP more for those of k_s2_bright)
         TRY(ensure(h, h->ftiles, (size_t)2 * TP)); TRY(ensure(h, h->tile_done, (size_t)TP)); TRY(ensure(h, h->tile_kind, (size_t)TP));
@@ -1717,7 +1742,7 @@ static int gen_electrons(wfs_handle *h, GenRun &r, FillGroup &fg)
         BrightArgs &b = h->bright_args;
         b.on = (h->run.fuse_full && h->bright_on && h->bright_max_bins > 0) ? 1 : 0; b.lds_bytes = h->bright_lds; b.max_bins = h->bright_max_bins; b.pad = 0;
         b.list_first = TP; b.tile_kind = h->tile_kind.p();
-        { Timer t(h, "k_tile_counts"); hipLaunchKernelGGL(k_tile_counts, dim3(nblocks(TP, 256)), dim3(256), 0, h->stream, d, f, b); }
+        TRY(launch(h, PLAIN(k_tile_counts), per_thread(TP), d, f, b));
     }
     TRY(scan(h, h->em_nph.p(), E, h->em_ph_off, &WfsScal::n_block_photons));
     TRY(read_scal(h));
@@ -1779,7 +1804,7 @@ static int gen_block_photons(wfs_handle *h, GenRun &r)
     g.tile_off = h->tile_off.p();
     if (ap_on) TRY(fill_ap_args(h, ap, ap_cap));
     TRY(ensure(h, h->ins_ph0, (size_t)(N + 1))); g.ins_ph0 = h->ins_ph0.p();
-    { Timer t(h, "k_ins_ph0"); hipLaunchKernelGGL(k_ins_ph0, dim3(nblocks(N + 1, 256)), dim3(256), 0, h->stream, g); }
+    TRY(launch(h, PLAIN(k_ins_ph0), per_thread(N + 1), g));
     TRY(ensure(h, h->ins_sbase, (size_t)N)); g.ins_sbase = h->ins_sbase.p();
     TRY(ensure(h, h->ins_fullsort, (size_t)N)); g.ins_fullsort = h->ins_fullsort.p();
     TRY(ensure(h, h->tile_tail, (size_t)TP)); TRY(ensure(h, h->tile_tailbase, (size_t)TP));
@@ -1789,14 +1814,14 @@ static int gen_block_photons(wfs_handle *h, GenRun &r)
         TRY(fg.flush());
     }
     g.tile_tail = h->tile_tail.p(); g.tile_tailbase = h->tile_tailbase.p();
-    { Timer t(h, "k_set_bases"); hipLaunchKernelGGL(k_set_bases, dim3(nblocks(h->batch.n_psets, 256)), dim3(256), 0, h->stream, g); }
+    TRY(launch(h, PLAIN(k_set_bases), per_thread(h->batch.n_psets), g));
     if (P > 0) {
         const unsigned nb = (unsigned)((P + GEN_BLOCK - 1) / GEN_BLOCK);
         g.n_blocks = nb;
         TRY(ensure(h, h->blk_e, (size_t)nb * MINMAX)); TRY(ensure(h, h->blk_base, (size_t)nb * d.n_tpc)); TRY(ensure(h, h->blk_cnt, (size_t)nb * d.n_tpc)); TRY(ensure(h, h->blk_ins, (size_t)nb));
         g.blk_e = h->blk_e.p(); g.blk_base = h->blk_base.p(); g.blk_cnt = h->blk_cnt.p(); g.blk_ins = h->blk_ins.p();
         TRY(ensure(h, h->blk_desc, (size_t)nb)); g.blk_desc = h->blk_desc.p();
-        { Timer t(h, "k_block_emitters"); hipLaunchKernelGGL(k_block_emitters, dim3(nblocks(nb, 256)), dim3(256), 0, h->stream, g); }
+        TRY(launch(h, PLAIN(k_block_emitters), per_thread(nb), g));
         // XCD x (workgroup id % 8) walks the photon blocks [x * chunk, (x + 1) * chunk) in order: the blocks that share
         // cache lines of a tile (consecutive ranges, k_block_ranges) run close together in time on the same L2
         g.xcd_chunk = (nb + 7) / 8;
@@ -1806,18 +1831,14 @@ static int gen_block_photons(wfs_handle *h, GenRun &r)
             int lg = 1; while ((1 << lg) < d.n_tpc) lg++;
             TRY(ensure(h, h->chan_alias, (size_t)n_rows << lg));
             g.chan_alias = h->chan_alias.p(); g.ch_lg = lg;
-            Timer t(h, "k_chan_alias"); hipLaunchKernelGGL(k_chan_alias, dim3((unsigned)n_rows), dim3(64), 0, h->stream, g.cdf_table, d.n_tpc, lg, h->chan_alias.p());
+            TRY(launch(h, PLAIN(k_chan_alias), per_group(n_rows, 64), g.cdf_table, d.n_tpc, lg, h->chan_alias.p()));
         }
-        if (g.gg_inv) { Timer t(h, "k_gg_sum"); hipLaunchKernelGGL(k_gg_sum, dim3(nb), dim3(256), 0, h->stream, d, g); }
-        { Timer t(h, "k_photon_count"); hipLaunchKernelGGL(k_photon_count, dim3(nbx), dim3(COUNT_TPB), (size_t)count_lds(d.n_tpc, g.ch_lg).total, h->stream, d, g); }
-        { Timer t(h, "k_block_ranges"); hipLaunchKernelGGL(k_block_ranges, dim3(nblocks(TP, 256)), dim3(256), 0, h->stream, d, g); }
+        if (g.gg_inv) TRY(launch(h, PLAIN(k_gg_sum), Shape(dim3(nb), dim3(256)), d, g));
+        TRY(launch(h, PLAIN(k_photon_count), Shape(dim3(nbx), dim3(COUNT_TPB), (size_t)count_lds(d.n_tpc, g.ch_lg).total), d, g));
+        TRY(launch(h, PLAIN(k_block_ranges), per_thread(TP), d, g));
         TRY(scan_into(h, h->tile_count.p(), TP, h->tile_off.p(), &WfsScal::n_tile_photons, 0));
         const size_t gen_lds = (size_t)gen_fill_lds(d.n_tpc, g.ch_lg, ap_on).total;
-        { Timer t(h, "k_photon_fill");
-          if (ext && ap_on) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_photon_fill<true, true>), dim3(nbx), dim3(FILL_TPB), gen_lds, h->stream, d, g, ap);
-          else if (ext) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_photon_fill<false, true>), dim3(nbx), dim3(FILL_TPB), gen_lds, h->stream, d, g, ap);
-          else if (ap_on) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_photon_fill<true, false>), dim3(nbx), dim3(FILL_TPB), gen_lds, h->stream, d, g, ap);
-          else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_photon_fill<false, false>), dim3(nbx), dim3(FILL_TPB), gen_lds, h->stream, d, g, ap); }
+        TRY(launch(h, K_PHOTON_FILL(ap_on, ext), Shape(dim3(nbx), dim3(FILL_TPB), gen_lds), d, g, ap));
     } else {
         TRY(scan_into(h, h->tile_count.p(), TP, h->tile_off.p(), &WfsScal::n_tile_photons, 0));
     }
@@ -1841,7 +1862,8 @@ static int gen_tile_photons(wfs_handle *h, GenRun &r)
         f.tile_off = h->tile_off.p(); f.tile_tmin = h->tile_tmin.p(); f.tile_tmax = h->tile_tmax.p(); f.tile_truth = h->tile_truth.p();
         f.tbuf = h->tbuf.p(); f.ph = h->ph.p(); f.keep_ph = (h->debug_bits & DBG_KEEP_PHOTONS) ? 1 : 0;
         const TemplateArg tp = fill_template_arg(h);
-        const size_t lds = (size_t)tile_lds(h->cfg.fma != 0, ap_on).total;
+        const bool fma = h->cfg.fma != 0;
+        const size_t lds = (size_t)tile_lds(fma, ap_on).total;
         const ApArgs *app = nullptr;
         if (ap_on) {
             TRY(ensure(h, h->ap_seg, (size_t)n_tilegen_tiles(h))); ap.seg = h->ap_seg.p(); ap.n_seg = n_tilegen_tiles(h);      // (one segment per tile of every class)
@@ -1852,25 +1874,16 @@ static int gen_tile_photons(wfs_handle *h, GenRun &r)
         // tiles of up to 2048 photons: photons and pulse in one workgroup (listed from the front); brighter ones -- and every tile in the
         // debug modes -- generation only (listed from the back), their pulses are made by the ordinary kernels below
         if (h->run.n_fused_tiles > 0) {
-            Timer t(h, "k_s2_tile");
-            const dim3 grid((unsigned)h->run.n_fused_tiles);
-            if (ap_on) WFS_LAUNCH_F(h, K_S2_TILE_AP, grid, dim3(256), lds, d, f, tp, app);
-            else WFS_LAUNCH_F(h, K_S2_TILE, grid, dim3(256), lds, d, f, tp, app);
+            TRY(launch(h, K_S2_TILE(ap_on, fma), per_group(h->run.n_fused_tiles, 256, lds), d, f, tp, app));
         }
         if (h->run.n_gen_tiles > 0) {
-            Timer t(h, "k_s2_tile_gen");
-            const dim3 grid((unsigned)h->run.n_gen_tiles);
-            if (ap_on) hipLaunchKernelGGL(k_s2_tile_gen<true>, grid, dim3(256), (size_t)tile_gen_lds(true).total, h->stream, d, f, app, (int)h->run.n_fused_tiles);
-            else hipLaunchKernelGGL(k_s2_tile_gen<false>, grid, dim3(256), (size_t)tile_gen_lds(false).total, h->stream, d, f, app, (int)h->run.n_fused_tiles);
+            TRY(launch(h, K_S2_TILE_GEN(ap_on), per_group(h->run.n_gen_tiles, 256, (size_t)tile_gen_lds(ap_on).total), d, f, app, (int)h->run.n_fused_tiles));
         }
         // tiles above 2048 photons whose H table fits the LDS as a whole: photons and pulse in one workgroup of 1024 threads, no photon array
         if (h->run.n_bright_tiles > 0) {
-            Timer t(h, "k_s2_bright");
-            const dim3 grid((unsigned)h->run.n_bright_tiles);
             const size_t blds = (size_t)bright_lds_layout(h->bright_lds, ap_on).total;
             const int seg_first = (int)(h->run.n_fused_tiles + h->run.n_gen_tiles);
-            if (ap_on) WFS_LAUNCH_F(h, K_S2_BRIGHT_AP, grid, dim3(BRIGHT_TPB), blds, d, f, h->bright_args, tp, app, seg_first);
-            else WFS_LAUNCH_F(h, K_S2_BRIGHT, grid, dim3(BRIGHT_TPB), blds, d, f, h->bright_args, tp, app, seg_first);
+            TRY(launch(h, K_S2_BRIGHT(ap_on, fma), per_group(h->run.n_bright_tiles, BRIGHT_TPB, blds), d, f, h->bright_args, tp, app, seg_first));
         }
     }
     h->fuse_args = f;
@@ -1883,12 +1896,12 @@ static int gen_afterpulses(wfs_handle *h, GenRun &r)
     const WfsDev &d = h->dev;
     const GenArgs &g = r.g; const ApArgs &ap = r.ap;
     const i64 P = r.P, TP = r.TP, ap_cap = r.ap_cap;
-    { Timer t(h, "k_ap_finish"); hipLaunchKernelGGL(k_ap_finish, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap); }
-    { Timer t(h, "k_ap_count"); hipLaunchKernelGGL(k_ap_count, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap);
-      if (ap.n_seg > 0) hipLaunchKernelGGL(k_ap_seg<false>, dim3(nblocks(ap.n_seg, 4)), dim3(256), 0, h->stream, d, g, ap, (double *)nullptr); }
+    TRY(launch(h, PLAIN(k_ap_finish), per_thread(ap_cap), d, g, ap));
+    { Timer t(h, "k_ap_count"); TRY(launch_untimed(h, PLAIN(k_ap_count), per_thread(ap_cap), d, g, ap));
+      if (ap.n_seg > 0) TRY(launch_untimed(h, K_AP_SEG(false), per_wave(ap.n_seg), d, g, ap, (double *)nullptr)); }
     TRY(scan_into(h, h->tile_count.p() + TP, TP, h->tile_off.p() + TP, &WfsScal::n_ap_photons, P + h->run.p_fused));      // (behind the slots of every primary tile, the tile-generated ones included)
-    { Timer t(h, "k_ap_place"); hipLaunchKernelGGL(k_ap_place, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap, h->ph_gain.p() - (P + h->run.p_fused));
-      if (ap.n_seg > 0) hipLaunchKernelGGL(k_ap_seg<true>, dim3(nblocks(ap.n_seg, 4)), dim3(256), 0, h->stream, d, g, ap, h->ph_gain.p() - (P + h->run.p_fused)); }
+    { Timer t(h, "k_ap_place"); TRY(launch_untimed(h, PLAIN(k_ap_place), per_thread(ap_cap), d, g, ap, h->ph_gain.p() - (P + h->run.p_fused)));
+      if (ap.n_seg > 0) TRY(launch_untimed(h, K_AP_SEG(true), per_wave(ap.n_seg), d, g, ap, h->ph_gain.p() - (P + h->run.p_fused))); }
     TRY(read_scal(h));
     if (h->h_scal->n_ap_candidates > ap_cap) return h->fail(WFS_E_CAPACITY, "more PMT afterpulse photons than 1/8 of the primary photons: afterpulse probability unreasonably high");
     h->run.n_ap_photons = h->h_scal->n_ap_photons;                   // (the accepted candidates: total of the afterpulse tiles' counts, the scan above)
@@ -1915,13 +1928,12 @@ static int gen_order(wfs_handle *h, GenRun &r)
 static int order_ranges(wfs_handle *h, const OrderArgs &oa)
 {
     const i64 T = oa.n_tiles;
-    { Timer t(h, "k_tile_order_scan"); hipLaunchKernelGGL(k_tile_order_scan, dim3(nblocks(T, 256)), dim3(256), 0, h->stream, oa); }
+    TRY(launch(h, PLAIN(k_tile_order_scan), per_thread(T), oa));
     TRY(read_scal(h));
     const i64 n_wave = h->h_scal->n_order_wave, n_big = h->h_scal->n_order_big;
-    if (n_wave > 0) { Timer t(h, "k_tile_order"); hipLaunchKernelGGL(k_tile_order, dim3(nblocks(n_wave, 4)), dim3(256), 0, h->stream, oa, n_wave); }
+    if (n_wave > 0) TRY(launch(h, PLAIN(k_tile_order), per_wave(n_wave), oa, n_wave));
     if (n_big > 0) {
-        Timer t(h, "k_tile_order_big");
-        hipLaunchKernelGGL(k_tile_order_big, dim3((unsigned)n_big), dim3(256), (size_t)order_lds(TILE_ORDER_MAX).total, h->stream, oa);
+        TRY(launch(h, K_TILE_ORDER_BIG(0), per_group(n_big, 256, (size_t)order_lds(TILE_ORDER_MAX).total), oa));
     }
     const i64 n_huge = h->h_scal->n_order_huge;
     if (n_huge > 0) {
@@ -1939,15 +1951,14 @@ static int order_ranges(wfs_handle *h, const OrderArgs &oa)
         HugeOrderArgs ha{n_huge, tot, h->huge_start.p(), h->huge_cbeg.p(), oa.ph, oa.ph_idx, oa.ph_gain, oa.gain_first,
                          h->huge_keys.p(), h->huge_vals.p(), h->huge_rec.p(), h->huge_gain.p()};
         Timer t(h, "k_tile_order_huge");
-        hipLaunchKernelGGL(k_order_huge_pack, dim3(nblocks(tot, 256)), dim3(256), 0, h->stream, ha);
+        TRY(launch_untimed(h, PLAIN(k_order_huge_pack), per_thread(tot), ha));
         size_t bytes = 0;
         HIPCHK(rocprim::segmented_radix_sort_pairs(nullptr, bytes, h->huge_keys.p(), h->huge_keys2.p(), h->huge_vals.p(), h->huge_vals2.p(),
                                                    (unsigned)tot, (unsigned)n_huge, h->huge_cbeg.p(), h->huge_cbeg.p() + 1, 0u, 32u, h->stream));
         TRY(ensure(h, h->sort_tmp, bytes));
         HIPCHK(rocprim::segmented_radix_sort_pairs(h->sort_tmp.p, bytes, h->huge_keys.p(), h->huge_keys2.p(), h->huge_vals.p(), h->huge_vals2.p(),
                                                    (unsigned)tot, (unsigned)n_huge, h->huge_cbeg.p(), h->huge_cbeg.p() + 1, 0u, 32u, h->stream));
-        hipLaunchKernelGGL(k_order_huge_apply, dim3(nblocks(tot, 256)), dim3(256), 0, h->stream, ha, h->huge_keys2.p(), h->huge_vals2.p(), h->ph.p(), h->ph_idx.p(),
-                           oa.ph_gain);
+        TRY(launch_untimed(h, PLAIN(k_order_huge_apply), per_thread(tot), ha, h->huge_keys2.p(), h->huge_vals2.p(), h->ph.p(), h->ph_idx.p(), oa.ph_gain));
     }
     return WFS_OK;
 }
@@ -1970,8 +1981,8 @@ struct RunState {
     bool tiles_done = false;                                // pulses made by k_s2_tile (wfs_tilegen.h)
     i64 CG = 0, RS = 0;                                     // group slots; row slots
     i64 first_sparse = 0, first_dense = 0, first_wave = 0;  // the one work list: tiny tiles, then sparse, dense, wave
-    int noise_kind = 0;                                     // with_noise_kind
-    bool dark = false;                                      // with_row_kind: PMT dark counts are on
+    int noise_kind = 0;                                     // the nk axis of the row kernels' families
+    bool dark = false;                                      // their dk axis: PMT dark counts are on
 };
 
 // ---- PMT afterpulses of an optical batch: the supplied photons are screened (k_optical_ap_screen), the candidates go through the
@@ -1990,14 +2001,13 @@ static int optical_afterpulses(wfs_handle *h)
     g.scal = h->scal.p();
     if (P > 0) {
         OptApArgs sa{P, TP, h->tile_off.p(), h->set_gid.p(), h->set_t0.p(), h->opt_item.p(), h->ph.p()};
-        Timer t(h, "k_optical_ap_screen");
-        hipLaunchKernelGGL(k_optical_ap_screen, dim3(nblocks(P, 256)), dim3(256), 0, h->stream, d, sa, ap);
+        TRY(launch(h, PLAIN(k_optical_ap_screen), per_thread(P), d, sa, ap));
     }
     double *const gain_base = h->ph_gain.p() - P;
-    { Timer t(h, "k_ap_finish"); hipLaunchKernelGGL(k_ap_finish, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap); }
-    { Timer t(h, "k_ap_count"); hipLaunchKernelGGL(k_ap_count, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap); }
+    TRY(launch(h, PLAIN(k_ap_finish), per_thread(ap_cap), d, g, ap));
+    TRY(launch(h, PLAIN(k_ap_count), per_thread(ap_cap), d, g, ap));
     TRY(scan_into(h, h->tile_count.p() + TP, TP, h->tile_off.p() + TP, &WfsScal::n_ap_photons, P));
-    { Timer t(h, "k_ap_place"); hipLaunchKernelGGL(k_ap_place, dim3(nblocks(ap_cap, 256)), dim3(256), 0, h->stream, d, g, ap, gain_base); }
+    TRY(launch(h, PLAIN(k_ap_place), per_thread(ap_cap), d, g, ap, gain_base));
     TRY(read_scal(h));
     if (h->h_scal->n_ap_candidates > ap_cap) return h->fail(WFS_E_CAPACITY, "more PMT afterpulse photons than 1/8 of the primary photons: afterpulse probability unreasonably high");
     h->run.n_ap_photons = h->h_scal->n_ap_photons;
@@ -2027,7 +2037,7 @@ static int run_input(wfs_handle *h)
         const i64 T = h->batch.n_ins * d.n_tpc;                    // the primary tiles (afterpulse tiles follow them)
         OpticalArgs oa{T, h->tile_count.p(), h->tile_off.p(), h->tile_tmin.p(), h->tile_tmax.p(), h->set_gid.p(),
                        h->opt_t.p(), h->opt_item.p(), h->ph.p(), h->scal.p()};
-        { Timer t(h, "k_optical_finish"); hipLaunchKernelGGL(k_optical_finish, dim3(nblocks(T, 256)), dim3(256), 0, h->stream, d, oa); }
+        TRY(launch(h, PLAIN(k_optical_finish), per_thread(T), d, oa));
         if (h->batch.ap_sets) TRY(optical_afterpulses(h));
     }
     else { TRY(scan(h, h->tile_count.p(), h->batch.n_tiles, h->tile_off, &WfsScal::n_tile_photons)); }
@@ -2102,12 +2112,12 @@ static int run_geometry(wfs_handle *h, RunState &r)
         TRY(ensure(h, h->res_long, nr)); ga.res_long = h->res_long.p();
     }
     TRY(fg.flush());
-    { Timer t(h, "k_tile_geom"); hipLaunchKernelGGL(k_tile_geom, dim3(nblocks(T, 1024)), dim3(1024), 0, h->stream, d, ga); }
-    { Timer t(h, "k_groups"); hipLaunchKernelGGL(k_groups, dim3(1), dim3(GROUPS_TPB), 0, h->stream, d, ga); }
-    { Timer t(h, "k_tile_rows"); hipLaunchKernelGGL(k_tile_rows, dim3(nblocks(T, 256)), dim3(256), 0, h->stream, d, ga); }
-    { Timer t(h, "k_group_final"); hipLaunchKernelGGL(k_group_final, dim3(nblocks(CG, 256)), dim3(256), 0, h->stream, d, ga); }
-    if (d.full_readout) { Timer t(h, "k_rows_widen"); hipLaunchKernelGGL(k_rows_widen, dim3(nblocks(CG * d.n_tpc, 256)), dim3(256), 0, h->stream, d, ga); }
-    { Timer t(h, "k_row_len"); hipLaunchKernelGGL(k_row_len, dim3(nblocks(CG * d.row_slots, 1024)), dim3(1024), 0, h->stream, d, ga); }
+    TRY(launch(h, PLAIN(k_tile_geom), per_thread(T, 1024), d, ga));
+    TRY(launch(h, PLAIN(k_groups), Shape(dim3(1), dim3(GROUPS_TPB)), d, ga));
+    TRY(launch(h, PLAIN(k_tile_rows), per_thread(T), d, ga));
+    TRY(launch(h, PLAIN(k_group_final), per_thread(CG), d, ga));
+    if (d.full_readout) TRY(launch(h, PLAIN(k_rows_widen), per_thread(CG * d.n_tpc), d, ga));
+    TRY(launch(h, PLAIN(k_row_len), per_thread(CG * d.row_slots, 1024), d, ga));
     TRY(scan(h, h->acc_len.p(), CG * d.n_tpc, h->acc_off, &WfsScal::n_acc_samples));
     TRY(scan(h, h->itv_cap.p(), CG * d.row_slots, h->itv_off, &WfsScal::n_itv_slots));
     if (d.sum_channel >= 0) {
@@ -2126,7 +2136,7 @@ static int run_geometry(wfs_handle *h, RunState &r)
         TRY(ensure(h, h->tile_truth, (size_t)T * TRUTH_PER_TILE));
         PulseArgs pt{}; pt.ph = h->ph.p(); pt.tile_truth = h->tile_truth.p();
         pt.ph_gain = ph_gain_base(h);
-        Timer t(h, "k_tile_assign"); hipLaunchKernelGGL(k_tile_assign, dim3(nblocks(T, 256)), dim3(256), 0, h->stream, d, ga, da, pt);
+        TRY(launch(h, PLAIN(k_tile_assign), per_thread(T), d, ga, da, pt));
     }
     TRY(read_scal(h));
     const WfsScal &sc = *h->h_scal;
@@ -2172,6 +2182,7 @@ static int run_pulses(wfs_handle *h, RunState &r)
     const WfsDev &d = h->dev;
     PulseArgs &pa = r.pa;
     const i64 T = h->batch.n_tiles, S = h->batch.n_sets;
+    const bool fma = h->cfg.fma != 0;
     TRY(pack_fence(h));             // the accumulators are the first such write of a run without tile buffers (with them: gen_tile_photons)
     // (+16 samples, 64 bytes: a lane of k_zle reads 4 samples from its first valid one; the sum rows behind the accumulators are written whole by k_sum_signal)
     TRY(ensure_rows(h, h->raw, (size_t)(h->run.s_sum > 0 ? h->run.sum_base + h->run.s_sum : h->run.s_raw) + 16, "the row accumulators"));
@@ -2201,21 +2212,18 @@ static int run_pulses(wfs_handle *h, RunState &r)
         DescArgs da{h->active_tiles.p(), h->run.n_active_tiles, h->tile_count.p(), h->tile_tmin.p(), h->tile_tmax.p(), h->tile_off.p(),
                     h->set_cluster.p(), h->set_t0.p(), h->set_mode.p(), h->cl_group.p(), h->row_lo.p(), h->acc_off.p(),
                     h->tile_desc.p()};
-        Timer t(h, "k_tile_desc");
-        hipLaunchKernelGGL(k_tile_desc, dim3(nblocks(h->run.n_active_tiles, 256)), dim3(256), 0, h->stream, d, da);
+        TRY(launch(h, PLAIN(k_tile_desc), per_thread(h->run.n_active_tiles), d, da));
     }
     if (h->run.n_tiny_tiles > 0) {
         PulseArgs pt = pa;
         pt.desc = h->tile_desc.p();
-        Timer t(h, "k_pulse_tiny");
-        WFS_LAUNCH_F(h, K_PULSE_TINY, dim3(nblocks(h->run.n_tiny_tiles * TINY_LANES, 256)), dim3(256), 0, d, pt, h->run.n_tiny_tiles);
+        TRY(launch(h, K_PULSE_TINY(fma), per_thread(h->run.n_tiny_tiles * TINY_LANES), d, pt, h->run.n_tiny_tiles));
     }
     if (h->run.n_wave_tiles > 0) {
         PulseArgs pw = pa;
         pw.desc = h->tile_desc.p() + r.first_wave;
         if (pw.cur_off) pw.cur_off += r.first_wave;
-        Timer t(h, "k_pulse_wave");
-        WFS_LAUNCH_F(h, K_PULSE_WAVE, dim3(nblocks(h->run.n_wave_tiles, 4)), dim3(256), 0, d, pw, h->run.n_wave_tiles);
+        TRY(launch(h, K_PULSE_WAVE(fma), per_wave(h->run.n_wave_tiles), d, pw, h->run.n_wave_tiles));
     }
     if (h->run.n_sparse_tiles > 0) {
         PulseArgs ps = pa;
@@ -2224,8 +2232,7 @@ static int run_pulses(wfs_handle *h, RunState &r)
         ps.W = (int)((h->run.max_nb + 7) / 8 * 8); ps.NP = (int)((h->run.max_tile + 7) / 8 * 8);
         // (tile_class lists a tile here with at most SPARSE_MAX_PHOTONS photons in at most SPARSE_MAX_BINS start bins: one form, 64 threads)
         const size_t lds = (size_t)sparse_lds(ps.NP, ps.W, SPARSE_TPB).total;
-        Timer t(h, "k_pulse_sparse");
-        WFS_LAUNCH_F(h, K_PULSE_SPARSE, dim3((unsigned)h->run.n_sparse_tiles), dim3(SPARSE_TPB), lds, d, ps);
+        TRY(launch(h, K_PULSE_SPARSE(fma), per_group(h->run.n_sparse_tiles, SPARSE_TPB, lds), d, ps));
     }
     if (h->run.n_dense_tiles > 0 && h->generic_geom) {        // any digitiser geometry: one kernel for every tile
         PulseArgs pd = pa;
@@ -2235,8 +2242,7 @@ static int run_pulses(wfs_handle *h, RunState &r)
         pd.n_win = generic_lds_split(d.dt, d.tlen) ? 1 : 0;
         const size_t lds = (size_t)generic_lds(d.dt, d.tlen, pd.n_win != 0).total;
         if (lds > (size_t)LDS_CAP_GENERIC) return h->fail(WFS_E_CAPACITY, "sample_duration x template length too large for the LDS tables of k_pulse_generic");
-        Timer t(h, "k_pulse_generic");
-        WFS_LAUNCH_F(h, K_PULSE_GENERIC, dim3((unsigned)h->run.n_dense_tiles), dim3(256), lds, d, pd);
+        TRY(launch(h, K_PULSE_GENERIC(fma), per_group(h->run.n_dense_tiles, 256, lds), d, pd));
     } else if (h->run.n_dense_tiles > 0) {
         PulseArgs pd = pa;
         pd.desc = h->tile_desc.p() + r.first_dense;
@@ -2257,24 +2263,16 @@ static int run_pulses(wfs_handle *h, RunState &r)
         const size_t lds = (size_t)pulse_lds(tpb).total;
         pd.sparse_max = (h->debug_bits & DBG_FORCE_DENSE) ? -1 : h->tap_sparse_max;      // (force_dense: every wave takes the dense gather)
         pd.spe_lds = ((size_t)(tpb + d.tlen - 1) * d.dt >= SPE_ROW_LEN) ? 1 : 0;
-        const unsigned grid = (unsigned)(h->run.n_dense_tiles * pd.n_win);
-        Timer t(h, "k_pulse_dense");
-        if (resident) {
-            if (small) WFS_LAUNCH_F(h, K_PULSE_128_RES, dim3(grid), dim3(128), lds, d, pd, tp);
-            else WFS_LAUNCH_F(h, K_PULSE_256_RES, dim3(grid), dim3(256), lds, d, pd, tp);
-        } else {
-            if (small) WFS_LAUNCH_F(h, K_PULSE_128_WIN, dim3(grid), dim3(128), lds, d, pd, tp);
-            else WFS_LAUNCH_F(h, K_PULSE_256_WIN, dim3(grid), dim3(256), lds, d, pd, tp);
-        }
+        TRY(launch(h, K_PULSE(!small, resident, fma), per_group(h->run.n_dense_tiles * pd.n_win, tpb, lds), d, pd, tp));
     }
 
     if (r.tiles_done && (h->h_scal->n_shared_rows > 0 || d.full_readout)) {      // (full readout: no row is its tile, every one of them is added)   // tiles of k_s2_tile that share their row with other pulses: added into the row's accumulators
         TileAddArgs ta{h->set_cluster.p(), h->cl_group.p(), h->row_lo.p(), h->acc_off.p(), h->row_cnt.p(), h->raw.p()};
         Timer t(h, "k_tile_add");
-        if (h->run.n_fused_tiles > 0) hipLaunchKernelGGL(k_tile_add, dim3((unsigned)h->run.n_fused_tiles), dim3(256), 0, h->stream, d, h->fuse_args, ta);
+        if (h->run.n_fused_tiles > 0) TRY(launch_untimed(h, PLAIN(k_tile_add), per_group(h->run.n_fused_tiles), d, h->fuse_args, ta));
         if (h->run.n_bright_tiles > 0) {                       // (the tiles of k_s2_bright: their own stretch of the work list)
             FuseArgs fb = h->fuse_args; fb.tiles += h->bright_args.list_first;
-            hipLaunchKernelGGL(k_tile_add, dim3((unsigned)h->run.n_bright_tiles), dim3(256), 0, h->stream, d, fb, ta);
+            TRY(launch_untimed(h, PLAIN(k_tile_add), per_group(h->run.n_bright_tiles), d, fb, ta));
         }
     }
     return WFS_OK;
@@ -2325,7 +2323,7 @@ static int run_rows(wfs_handle *h, RunState &r)
         TRY(fg.fill(&za.key_base->key_origin, 1, I64_MAX)); TRY(fg.fill(&za.key_base->key_end, 1, I64_MIN));
     }
     TRY(fg.flush());
-    if (h->run.n_active_rows > 0) { Timer t(h, "k_row_desc"); hipLaunchKernelGGL(k_row_desc, dim3(nblocks(h->run.n_active_rows, 256)), dim3(256), 0, h->stream, d, za); }
+    if (h->run.n_active_rows > 0) TRY(launch(h, PLAIN(k_row_desc), per_thread(h->run.n_active_rows), d, za));
     r.noise_kind = d.enable_noise ? noise_kind_of(d) : NOISE_NONE;
     r.dark = d.dk_thr != nullptr;
     if (h->run.n_res_rows > 0) {        // resident rows: pulses, finished samples and intervals by one wave per row
@@ -2333,31 +2331,22 @@ static int run_rows(wfs_handle *h, RunState &r)
         pr.desc = h->res_desc.p(); pr.currents = nullptr; pr.cur_off = nullptr;
         // two launches: the rows of at most RES_SHORT_LEN samples at full occupancy, the longer ones with LDS for the longest of them
         Timer t(h, "k_row_pulse");
-#define K_ROW_PULSE_SHORT(F) k_row_pulse<NK, F, false, DK>
-#define K_ROW_PULSE_LONG(F) k_row_pulse<NK, F, true, DK>
         for (int part = 0; part < 2; part++) {
             const i64 first = part == 0 ? 0 : h->run.n_short_rows, n_rows = part == 0 ? h->run.n_short_rows : h->run.n_res_rows - h->run.n_short_rows;
             if (n_rows <= 0) continue;
             const i32 region = part == 0 ? RES_SHORT_LEN : (i32)((std::min<i64>(h->run.max_res_len, h->res_max_len) + 255) / 256 * 256);
             const size_t lds = (size_t)row_pulse_lds(region).total;
-            const dim3 grid(nblocks(n_rows, 4));
-            with_row_kind(r.noise_kind, r.dark, [&](auto nk, auto dk) {
-                constexpr int NK = decltype(nk)::value; constexpr bool DK = decltype(dk)::value;
-                if (part == 0) WFS_LAUNCH_F(h, K_ROW_PULSE_SHORT, grid, dim3(256), lds, d, pr, za, first, n_rows, region);
-                else WFS_LAUNCH_F(h, K_ROW_PULSE_LONG, grid, dim3(256), lds, d, pr, za, first, n_rows, region);
-            });
+            TRY(launch_untimed(h, K_ROW_PULSE(r.noise_kind, h->cfg.fma != 0, part == 1, r.dark), per_wave(n_rows, lds), d, pr, za, first, n_rows, region));
         }
     }
     if (n_empty_rows(h) > 0) {      // full readout: the rows without a pulse, finished samples and intervals by one wave per row
-        Timer t(h, "k_row_empty"); const dim3 grid(nblocks(n_empty_rows(h), 4));
         const i64 first = h->run.n_front_rows + h->run.n_res_rows;
-        with_row_kind(r.noise_kind, r.dark, [&](auto nk, auto dk) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_row_empty<decltype(nk)::value, decltype(dk)::value>), grid, dim3(256), 0, h->stream, d, za, first, n_empty_rows(h)); });
+        TRY(launch(h, K_ROW_EMPTY(r.noise_kind, r.dark), per_wave(n_empty_rows(h)), d, za, first, n_empty_rows(h)));
     }
     {   // truth accumulators of every pulse set from the per-tile partial sums
         TruthArgs ta{S, h->tile_count.p(), h->tile_tmin.p(), h->tile_tmax.p(), h->set_t0.p(), h->tile_truth.p(),
                      h->truth.p(), h->tminmax.p()};
-        Timer t(h, "k_truth_reduce");
-        hipLaunchKernelGGL(k_truth_reduce, dim3(nblocks(S, 4)), dim3(256), 0, h->stream, d, ta);
+        TRY(launch(h, PLAIN(k_truth_reduce), per_wave(S), d, ta));
     }
 
     // (WFS_SUM_SKIP_KERNEL: A/B runs that price what the switch costs apart from the kernel -- bottom rows off the resident path, one
@@ -2367,12 +2356,10 @@ static int run_rows(wfs_handle *h, RunState &r)
         SumArgs sa{h->sum_chunk_off.p(), CG, h->sum_lo.p(), h->sum_off.p(), h->sum_len.p(),
                    h->row_lo.p(), h->row_hi.p(), h->acc_off.p(), h->raw.p(), r.tiles_done ? h->tbuf.p() : nullptr,
                    r.tiles_done ? ga.tile_done : nullptr, ga.row_cnt, ga.row_tile, ga.ins_bcap, ga.ins_boff, ga.n_done, h->raw.p() + h->run.sum_base};
-        Timer t(h, "k_sum_signal");
-        hipLaunchKernelGGL(k_sum_signal, dim3((unsigned)h->run.n_sum_chunks), dim3(256), 0, h->stream, d, sa);
+        TRY(launch(h, PLAIN(k_sum_signal), per_group(h->run.n_sum_chunks), d, sa));
     }
     if (h->run.n_front_rows > 0) {
-        Timer t(h, "k_zle"); const dim3 grid(nblocks(h->run.n_front_rows, 4));
-        with_row_kind(r.noise_kind, r.dark, [&](auto nk, auto dk) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_zle<decltype(nk)::value, decltype(dk)::value>), grid, dim3(256), 0, h->stream, d, za); });
+        TRY(launch(h, K_ZLE(r.noise_kind, r.dark), per_wave(h->run.n_front_rows), d, za));
     }
     return WFS_OK;
 }
@@ -2401,7 +2388,7 @@ static int run_records(wfs_handle *h, RunState &r)
         TRY(ensure(h, h->rec_key, (size_t)NR)); TRY(ensure(h, h->rec_key2, (size_t)NR));
         TRY(ensure(h, h->rec_val, (size_t)NR)); TRY(ensure(h, h->rec_val2, (size_t)NR)); TRY(ensure(h, h->rec_dest, (size_t)NR));
         za.rec_key = h->rec_key.p(); za.rec_val = h->rec_val.p();
-        { Timer t(h, "k_rec_keys"); hipLaunchKernelGGL(k_rec_keys, dim3(nblocks(h->run.n_active_rows, 4)), dim3(256), 0, h->stream, d, za); }
+        TRY(launch(h, PLAIN(k_rec_keys), per_wave(h->run.n_active_rows), d, za));
         // rocPRIM's radix sort, over the key bits that are in use only: (samples the batch spans) << 12 | channel
         unsigned end_bit = 13;
         { const u64 span = (u64)std::max<i64>(h->h_scal->key_end - h->h_scal->key_origin, 1); while (end_bit < 64 && ((span << 12) >> end_bit) != 0) end_bit++; }
@@ -2409,7 +2396,7 @@ static int run_records(wfs_handle *h, RunState &r)
         HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, h->rec_key.p(), h->rec_key2.p(), h->rec_val.p(), h->rec_val2.p(), (size_t)NR, 0u, end_bit, h->stream));
         TRY(ensure(h, h->sort_tmp, bytes));
         { Timer t(h, "record_sort"); HIPCHK(rocprim::radix_sort_pairs(h->sort_tmp.p, bytes, h->rec_key.p(), h->rec_key2.p(), h->rec_val.p(), h->rec_val2.p(), (size_t)NR, 0u, end_bit, h->stream)); }
-        { Timer t(h, "k_invert_perm"); hipLaunchKernelGGL(k_invert_perm, dim3(nblocks(NR, 256)), dim3(256), 0, h->stream, h->rec_val2.p(), h->rec_dest.p(), NR); }
+        TRY(launch(h, PLAIN(k_invert_perm), per_thread(NR), h->rec_val2.p(), h->rec_dest.p(), NR));
         za.rec_dest = h->rec_dest.p();
     }
     if (h->run.n_active_rows > 0 && h->run.n_records > 0) {
@@ -2423,14 +2410,13 @@ static int run_records(wfs_handle *h, RunState &r)
             HIPCHK(hipStreamWaitEvent(h->pack_stream, h->pack_go[h->rec_cur], 0));
             ps = h->pack_stream;
         }
-        { Timer t(h, "k_pack_desc"); hipLaunchKernelGGL(k_pack_desc, dim3(nblocks(h->run.n_active_rows, 256)), dim3(256), 0, ps, za); }
+        TRY(launch(h, PLAIN(k_pack_desc), per_thread(h->run.n_active_rows).on(ps), za));
         if (const i64 n_fin_rows = h->run.n_res_rows + n_empty_rows(h); n_fin_rows > 0) {      // rows that exist as finished samples: resident, without a pulse
             PackResArgs pr{h->pack_desc.p() + h->run.n_front_rows, h->fin.p(), za.itv_left, za.itv_right, za.records, za.rec_dest, za.rec_capacity, n_fin_rows, za.spr, (i32)d.dt};
-            Timer t(h, "k_pack_res"); hipLaunchKernelGGL(k_pack_res, dim3(nblocks(n_fin_rows, 4)), dim3(256), 0, ps, pr);
+            TRY(launch(h, PLAIN(k_pack_res), per_wave(n_fin_rows).on(ps), pr));
         }
         if (h->run.n_front_rows > 0) {
-            Timer t(h, "k_pack"); const dim3 grid(nblocks(h->run.n_front_rows, 4));
-            with_row_kind(r.noise_kind, r.dark, [&](auto nk, auto dk) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack<decltype(nk)::value, decltype(dk)::value>), grid, dim3(256), 0, ps, d, za); });
+            TRY(launch(h, K_PACK(r.noise_kind, r.dark), per_wave(h->run.n_front_rows).on(ps), d, za));
         }
         if (defer) {
             HIPCHK(hipEventRecord(h->rec_ready[h->rec_cur], h->pack_stream));
@@ -2440,7 +2426,9 @@ static int run_records(wfs_handle *h, RunState &r)
     {   // totals of wfs_get_counts: afterpulse sets carry no truth (rawdata.py:322-323)
         const i64 n_prim = h->batch.ap_sets ? h->batch.n_psets : h->batch.n_sets;
         const i64 work = std::max<i64>(RS, n_prim);
-        hipLaunchKernelGGL(k_counts, dim3((unsigned)std::min<i64>(nblocks(work, 256), 128)), dim3(256), 0, h->stream, h->itv_n.p(), RS, h->truth.p(), n_prim, h->scal.p());
+        // (not timed, as ever: an entry would change the (name, launches) list that profiled steps are compared by, and tools/make_profiles.py
+        // counts the runs of a trace by this kernel, not by an entry)
+        TRY(launch_untimed(h, PLAIN(k_counts), Shape(dim3((unsigned)std::min<i64>(nblocks(work, 256), 128)), dim3(256)), h->itv_n.p(), RS, h->truth.p(), n_prim, h->scal.p()));
     }
     TRY(read_scal(h));
     HIPCHK(hipGetLastError());
@@ -2747,7 +2735,8 @@ try {
     if (!blk_idx.empty()) {
         const i64 m = (i64)blk_idx.size();
         TRY(upload(h, h->gather_idx, blk_idx.data(), (size_t)m)); TRY(ensure(h, h->gather_out, (size_t)m));
-        hipLaunchKernelGGL(k_photon_times, dim3(nblocks(m, 256)), dim3(256), 0, h->stream, h->dev, h->gen_args, m, h->gather_idx.p(), h->gather_out.p());
+        // (not timed: a copy-out after the run, whose entry would lengthen the list of the last profiled step)
+        TRY(launch_untimed(h, PLAIN(k_photon_times), per_thread(m), h->dev, h->gen_args, m, h->gather_idx.p(), h->gather_out.p()));
         got.resize((size_t)m);
         TRY(copy_async(h, got.data(), h->gather_out.p(), (size_t)m, hipMemcpyDeviceToHost));
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -2756,7 +2745,8 @@ try {
     if (!treq.empty()) {
         const i64 m = (i64)treq.size();
         TRY(upload(h, h->gather_req, treq.data(), (size_t)m)); TRY(ensure(h, h->gather_out, (size_t)m));
-        hipLaunchKernelGGL(k_tile_photon_times, dim3(nblocks(m, 256)), dim3(256), 0, h->stream, h->dev, h->fuse_args, m, h->gather_req.p(), h->gather_out.p());
+        // (not timed: as k_photon_times above)
+        TRY(launch_untimed(h, PLAIN(k_tile_photon_times), per_thread(m), h->dev, h->fuse_args, m, h->gather_req.p(), h->gather_out.p()));
         got.resize((size_t)m);
         TRY(copy_async(h, got.data(), h->gather_out.p(), (size_t)m, hipMemcpyDeviceToHost));
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -2923,10 +2913,9 @@ try {
     if (channel < 0 || channel >= h->noise.channels) return h->fail(WFS_E_INVALID, "wfs_noise_model_samples: channel outside the model");
     return noise_probe(h, __func__, t0, n, out, [&](int16_t *buf) {
         const NoiseKind kind = noise_kind_of(h->dev);
-        const dim3 waves(nblocks((n + 255) / 256, 4));          // (the coloured forms: a wave takes 256 samples)
-        if (kind == NOISE_SLOW) { Timer t(h, "k_noise_colour_samples"); hipLaunchKernelGGL(k_noise_colour_samples<true>, waves, dim3(256), 0, h->stream, h->dev, channel, t0, n, buf); }
-        else if (kind == NOISE_COLOUR) { Timer t(h, "k_noise_colour_samples"); hipLaunchKernelGGL(k_noise_colour_samples<false>, waves, dim3(256), 0, h->stream, h->dev, channel, t0, n, buf); }
-        else { Timer t(h, "k_noise_model_samples"); hipLaunchKernelGGL(k_noise_model_samples, dim3(nblocks((n + 3) / 4, 256)), dim3(256), 0, h->stream, h->dev, channel, t0, n, buf); }
+        // (the coloured forms: a wave takes 256 samples)
+        if (kind == NOISE_SLOW || kind == NOISE_COLOUR) return launch(h, K_NOISE_COLOUR_SAMPLES(kind == NOISE_SLOW), per_wave((n + 255) / 256), h->dev, channel, t0, n, buf);
+        return launch(h, PLAIN(k_noise_model_samples), per_thread((n + 3) / 4), h->dev, channel, t0, n, buf);
     });
 } WFS_CATCH(h)
 
@@ -2967,8 +2956,7 @@ try {
     if (!h) return WFS_E_INVALID;
     TRY(dark_probe_check(h, __func__, channel, t0, n));
     return noise_probe(h, __func__, t0, n, out, [&](i32 *buf) {
-        Timer t(h, "k_dark_samples");
-        hipLaunchKernelGGL(k_dark_samples, dim3(nblocks((n + 255) / 256, 4)), dim3(256), 0, h->stream, h->dev, channel, t0, n, buf);
+        return launch(h, PLAIN(k_dark_samples), per_wave((n + 255) / 256), h->dev, channel, t0, n, buf);
     });
 } WFS_CATCH(h)
 
@@ -2984,7 +2972,7 @@ try {
     const i64 m0 = t0 >> DK_CELL_SHIFT, n_cells = ((t0 + n - 1) >> DK_CELL_SHIFT) - m0 + 1;
     DevArr<i32> d_cnt; DevArr<i64> d_t; DevArr<double> d_g;
     TRY(ensure(h, d_cnt, (size_t)n_cells)); TRY(ensure(h, d_t, (size_t)n_cells * DK_MAX)); TRY(ensure(h, d_g, (size_t)n_cells * DK_MAX));
-    { Timer t(h, "k_dark_photons"); hipLaunchKernelGGL(k_dark_photons, dim3(nblocks(n_cells, 256)), dim3(256), 0, h->stream, h->dev, channel, m0, n_cells, d_cnt.p(), d_t.p(), d_g.p()); }
+    TRY(launch(h, PLAIN(k_dark_photons), per_thread(n_cells), h->dev, channel, m0, n_cells, d_cnt.p(), d_t.p(), d_g.p()));
     HIPCHK(hipGetLastError());
     std::vector<i32> cnt((size_t)n_cells); std::vector<i64> tt((size_t)n_cells * DK_MAX); std::vector<double> gg((size_t)n_cells * DK_MAX);
     TRY(copy_async(h, cnt.data(), d_cnt.p(), cnt.size(), hipMemcpyDeviceToHost));
@@ -3080,7 +3068,7 @@ try {
     if (h->noise.levels() <= 0) return h->fail(WFS_E_STATE, "wfs_noise_slow_samples: no noise model with slow levels is set");
     if (row < 0 || row >= h->noise.rows()) return h->fail(WFS_E_INVALID, "wfs_noise_slow_samples: row outside the model's channels and common streams");
     return noise_probe(h, __func__, t0, n, out, [&](int32_t *buf) {
-        Timer t(h, "k_noise_slow_samples"); hipLaunchKernelGGL(k_noise_slow_samples, dim3(nblocks((n + 255) / 256, 4)), dim3(256), 0, h->stream, h->dev, row, t0, n, buf);
+        return launch(h, PLAIN(k_noise_slow_samples), per_wave((n + 255) / 256), h->dev, row, t0, n, buf);
     });
 } WFS_CATCH(h)
 
@@ -3090,7 +3078,7 @@ try {
     if (!h->noise.set()) return h->fail(WFS_E_STATE, "wfs_noise_white_samples: no noise model is set");
     if (row < 0 || row >= h->noise.rows()) return h->fail(WFS_E_INVALID, "wfs_noise_white_samples: row outside the model's channels and common streams");
     return noise_probe(h, __func__, t0, n, out, [&](int16_t *buf) {
-        Timer t(h, "k_noise_white_samples"); hipLaunchKernelGGL(k_noise_white_samples, dim3(nblocks(n, 256)), dim3(256), 0, h->stream, h->dev, row, t0, n, buf);
+        return launch(h, PLAIN(k_noise_white_samples), per_thread(n), h->dev, row, t0, n, buf);
     });
 } WFS_CATCH(h)
 
