@@ -465,7 +465,7 @@ int wfs_set_full_readout(wfs_handle *h, int32_t on);
  *           and clamp follow unchanged.  A channel with rate 0 or gain 0 gets nothing, nor does one at or beyond n_channels.
  * The sum row (wfs_set_sum_signal) carries no dark counts.  Windows, row ranges, ix_rand, truth, the order of the Pulse calls and the
  * record order do not change: a dark pulse shows where a row is read out, its tail too when it began in front of the row; outside
- * digitise windows nothing is read out (no lone-hit windows of their own).  n_channels = 0 clears; rates that are all zero are the
+ * the rows of a run a dark photon is read out by wfs_lone_hits alone.  n_channels = 0 clears; rates that are all zero are the
  * feature off.  WFS_E_INVALID, with the argument named: n_channels > n_tpc, a negative or non-finite rate, mu > 1/8.  Takes effect
  * from the next wfs_run; waits for pending packers.  Default: off -- no kernel, no buffer, no record differs. */
 int wfs_set_dark_counts(wfs_handle *h, int32_t n_channels, const double *rate_hz);
@@ -477,6 +477,32 @@ int wfs_dark_count_samples(wfs_handle *h, int32_t channel, int64_t t0, int64_t n
 int wfs_dark_count_photons(wfs_handle *h, int32_t channel, int64_t t0, int64_t n, int64_t *t_ns, double *gain, int64_t capacity, int64_t *count);
 /* The thresholds T[channel][1 .. 4] as the device holds them.  WFS_E_STATE without rates. */
 int wfs_copy_dark_counts(wfs_handle *h, int32_t channel, uint32_t thr[4]);
+/* Lone-hit rows (config 'dark_count_lone_hits'): the dark photons outside the rows of a run, read out in rows of their own.
+ * start = idx - before is the first sample of a dark photon's pulse, G = tlen + 2 tw.
+ *   lone     a dark photon of PMT channel ch whose pulse samples start .. start + tlen - 1 lie in no row of ch's TPC slot.  Rows: those
+ *            of the last completed wfs_run at their final range (every channel of a window under full readout), none when no run is
+ *            complete.  HE slots and the sum row get no lone rows.
+ *   row      the lone photons of a channel in time order; a maximal chain whose consecutive starts are at most G apart is one row of
+ *            range first start - tw .. last start + tlen - 1 + tw, clipped so that it reaches no sample of a row of the channel.
+ *   content  D(ch, t) over the range (every dark photon that reaches a sample), finished like every row: noise (kinds 3 - 5 at the
+ *            absolute sample; tables at index ix_rand + i, ix_rand = ((u64) w[0] noise_len) >> 32, w = philox4x32_10(counter (low, high
+ *            32 bits of the row's first sample, ch, 115))), baseline, clamp; ZLE with thr_zle[ch], hold-off, even landing, fragments.
+ *   owner    the pass over the absolute samples [s0, s1) owns the rows whose first photon starts there; it looks back G samples in front
+ *            of s0 and follows a chain beyond s1, but takes no photon that starts at or behind s_limit >= s1 and ends the row at
+ *            s_limit - 1 at the latest (what such a chain holds beyond s_limit is read out by no pass).  However [s0, s1) is split into
+ *            passes of one s_limit, the records are the same.
+ * The windows of the run must lie more than G samples apart (WFS_E_STATE otherwise).  The pass has buffers of its own, runs behind the
+ * packers of the batch and leaves that batch's records as they are; it returns when its records exist.  *n_records: how many.
+ * WFS_E_STATE without rates or tables; WFS_E_INVALID for s1 < s0, s_limit < s1 or a range beyond 2^48; WFS_E_CAPACITY, with a message
+ * that names lone hits, for a pass of more than 2^40 samples, 2^34 cells (channels x 64-sample cells), 2^24 rows or 2^31 records, or
+ * a lone row of more than 2^19 samples. */
+int wfs_lone_hits(wfs_handle *h, int64_t s0, int64_t s1, int64_t s_limit, int64_t *n_records);
+/* The records of the last pass in (time, channel) order, in the layout of wfs_copy_records.  capacity: records the buffer holds. */
+int wfs_copy_lone_records(wfs_handle *h, void *dst, int64_t capacity);
+/* The rows of the last pass in (channel, time) order: channel, first and last sample, ix_rand (0 without a noise table) and the number
+ * of lone photons of the chain (the photons themselves: wfs_dark_count_photons).  *count: how many rows; more than capacity:
+ * WFS_E_CAPACITY and nothing is written. */
+int wfs_copy_lone_rows(wfs_handle *h, int32_t *channel, int64_t *left, int64_t *right, int64_t *ix_rand, int32_t *n_photons, int64_t capacity, int64_t *count);
 /* Which kernel made every primary (pulse set, channel) tile of the last wfs_run, indexed set * n_tpc + channel: 0 no photons or not
  * tile-generated, 1 photons and pulse in one workgroup (up to 2048 photons), 2 generation only + the pulse kernels, 3 k_s2_bright.
  * capacity: entries the buffer holds (>= n_run_sets * n_tpc). */

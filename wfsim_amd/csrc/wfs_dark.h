@@ -20,7 +20,7 @@
 //           A channel with rate 0 or gain 0 gets nothing, nor does one at or beyond the given count.
 // The sum row (wfs_set_sum_signal) carries NO dark counts: k_sum_signal adds unfinished rows, and a per-sample sum over the bottom
 // array is a kernel of its own.  Windows, their left / right, row ranges, ix_rand, truth, the order of the Pulse calls and the record
-// order do not move; outside digitise windows nothing is read out (no lone-hit windows of their own).
+// order do not move.  Outside the rows of a run a dark photon is read out by a pass of wfs_lone_hits alone (wfs_lone.h).
 // No HIP types: a host compiler takes this header.
 #pragma once
 #include <cmath>
@@ -31,7 +31,7 @@
 constexpr int DK_CELL_SHIFT = 6, DK_CELL = 1 << DK_CELL_SHIFT;      // samples in a cell
 constexpr int DK_MAX = 4;                                          // photons of a cell at most
 constexpr double DK_MU_MAX = 0.125;                                // largest mean count of a cell the setter takes
-constexpr unsigned DK_SITE_COUNT = 112, DK_SITE_PHOTON = 113;      // Philox sites: the count; photons 0, 1 (113) and 2, 3 (114); 115 is kept free
+constexpr unsigned DK_SITE_COUNT = 112, DK_SITE_PHOTON = 113;      // Philox sites: the count; photons 0, 1 (113) and 2, 3 (114); 115: wfs_lone.h
 
 struct DarkState {
     int channels = 0;                         // 0: off

@@ -13,6 +13,7 @@
 #include "wfs_dark.h"        // PMT dark counts: the definition, the cell and site constants
 #include "wfs_layout.h"      // the sizes the LDS layouts are made of (WFS_DT, WFS_MAX_CH, SPE_ROW_LEN, ..), floordiv, the window rules
 #include "wfs_rows.h"        // the rules of the back end of a row: ZLE intervals, records, the noise index, the finished sample
+#include "wfs_lone.h"        // lone-hit rows: the rule, the site of a row's noise offset, the limits of a pass
 
 typedef long long i64;
 typedef unsigned long long u64;
@@ -46,8 +47,10 @@ enum WfsSite : u32 {
     // channel) at 96 + j, j < 8; counter (low, high 32 bits of m >> 2, ..), m the knot index t >> shift[j]; knot m owns word m & 3
     SITE_NOISE_SLOW = 80, SITE_NOISE_SLOW_COMMON = 96,
     // PMT dark counts (wfs_set_dark_counts, wfs_dark.h): counter (low, high 32 bits of the cell m, channel, site); 112: word 0 -> photons
-    // of the cell; 113 + (j >> 1): words 2 (j & 1), 2 (j & 1) + 1 -> time and SPE index of photon j < 4 (113, 114); 115 is kept free
-    SITE_DARK_N = DK_SITE_COUNT, SITE_DARK_PH = DK_SITE_PHOTON
+    // of the cell; 113 + (j >> 1): words 2 (j & 1), 2 (j & 1) + 1 -> time and SPE index of photon j < 4 (113, 114)
+    SITE_DARK_N = DK_SITE_COUNT, SITE_DARK_PH = DK_SITE_PHOTON,
+    // lone-hit rows (wfs_lone_hits, wfs_lone.h): counter (low, high 32 bits of the row's first sample, channel, 115): word 0 -> ix_rand
+    SITE_LONE_IX = DK_SITE_LONE_IX
 };
 
 struct u32x4 { u32 x, y, z, w; };
@@ -305,7 +308,12 @@ struct WfsScal {
     i64 n_sum_chunks;       // workgroups of k_sum_signal.  scan of sum_nchunk -> host
     i64 n_empty_rows;       // rows without a pulse of a fully read-out window (wfs_set_full_readout).  k_row_len -> host
     i64 n_empty_samples;    // finished int16 samples reserved for them.  scan of fr_len -> host
-    i64 reserved_[20];
+    // a pass of wfs_lone_hits counts in a block of its own (wfs_handle::lone_scal), never in the run's: these, n_itv_slots, n_records,
+    // n_empty_samples and the key range mean there what they mean for a batch
+    i64 n_lone_photons;     // lone-photon candidates k_lone_scan appended (may exceed the list: the pass is repeated with room).  k_lone_scan -> host
+    i64 n_lone_rows;        // lone rows of the pass.  scan of the chain-start flags -> host
+    i64 lone_error;         // 1: a lone row longer than LONE_MAX_ROW_LEN.  k_lone_rows -> host
+    i64 reserved_[17];
 };
 static_assert(sizeof(WfsScal) == 512, "WfsScal: 64 slots of 8 bytes");
 #define WFS_SCAL_SLOT(m, slot) static_assert(offsetof(WfsScal, m) == 8 * (slot), "WfsScal::" #m " moved: the layout is frozen")

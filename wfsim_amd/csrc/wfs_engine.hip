@@ -167,6 +167,16 @@ struct wfs_handle {
     DevArr<i64> sum_lo, sum_hi, sum_off, sum_chunk_off; DevArr<i32> sum_len, sum_nchunk;
     // full readout (k_row_empty): finished samples reserved per row slot for a row without a pulse, their offsets, the list of those rows
     DevArr<i32> fr_len, empty_rows; DevArr<i64> fr_off;
+    // lone-hit rows (wfs_lone_hits, wfs_lone.h): a pass has buffers of its own for everything it writes -- counters, photon keys, rows,
+    // intervals, finished samples, records -- so that the batch it follows, whose packers may still run, keeps every byte
+    struct Lone {
+        DevArr<WfsScal> scal; DevArr<u64> keys, keys2, rec_key, rec_key2; DevArr<u32> rec_val, rec_val2, rec_dest;
+        DevArr<i64> win_l, win_r, row_of, itv_off, fin_off, itv_left, itv_right, rec_off, out_left, out_right, out_ixr;
+        DevArr<i32> win_g, flag, cap, flen, itv_n, row_nrec, out_channel, out_nph;
+        DevArr<int16_t> fin; DevArr<RowDesc> desc; DevArr<PackDesc> pdesc; DevBuf sort_tmp, records_ab[1];      // (one record arena: a pass returns when its records exist)
+        i64 n_rows = 0, n_records = 0;      // of the last pass
+        DevBuf &records_buf() { return records_ab[0]; }
+    } lone;
 
     // what is not a device buffer; the buffers, and the members that hold some, free themselves after this body
     ~wfs_handle()
@@ -461,11 +471,12 @@ struct FillGroup {
 };
 
 // exclusive scan i32[n] -> i64[n+1] into a caller-provided range, every output shifted by offset; total as for scan
-int scan_into(wfs_handle *h, const i32 *in, i64 n, i64 *outp, i64 WfsScal::*total_member, i64 offset)
+// (block: the scalar block that takes the total -- the run's, or the one a pass of wfs_lone_hits counts in)
+int scan_into(wfs_handle *h, const i32 *in, i64 n, i64 *outp, i64 WfsScal::*total_member, i64 offset, WfsScal *block = nullptr)
 {
     i64 nb = (n + SCAN_TILE - 1) / SCAN_TILE; if (nb < 1) nb = 1;
     TRY(ensure(h, h->scan_tmp, (size_t)nb));
-    i64 *total = &(h->scal.p()->*total_member);       // (a device address: computed, never dereferenced here)
+    i64 *total = &((block ? block : h->scal.p())->*total_member);       // (a device address: computed, never dereferenced here)
     if (n == 0) { h->zero64 = offset; TRY(copy_async(h, outp, &h->zero64, 1, hipMemcpyHostToDevice)); HIPCHK(hipMemsetAsync(total, 0, sizeof *total, h->stream)); return WFS_OK; }
     TRY(launch(h, PLAIN(k_scan_reduce), per_group(nb, SCAN_TPB), in, n, h->scan_tmp.p()));
     TRY(launch(h, PLAIN(k_scan_spine), Shape(dim3(1), dim3(1024)), h->scan_tmp.p(), nb, total));
@@ -474,10 +485,10 @@ int scan_into(wfs_handle *h, const i32 *in, i64 n, i64 *outp, i64 WfsScal::*tota
 }
 
 // exclusive scan i32[n] -> i64[n+1]; total written to the member `total` of the device scalar block
-int scan(wfs_handle *h, const i32 *in, i64 n, DevArr<i64> &out, i64 WfsScal::*total_member)
+int scan(wfs_handle *h, const i32 *in, i64 n, DevArr<i64> &out, i64 WfsScal::*total_member, WfsScal *block = nullptr)
 {
     TRY(ensure(h, out, (size_t)(n + 1)));
-    return scan_into(h, in, n, out.p(), total_member, 0);
+    return scan_into(h, in, n, out.p(), total_member, 0, block);
 }
 
 // A step boundary: on return *h->h_scal is the device scalar block as of this point of the stream.  By default k_publish writes
@@ -3005,6 +3016,168 @@ try {
     HIPCHK(hipSetDevice(h->device));
     const std::vector<u32> all = download(h, h->dk_thr, (size_t)h->dark.channels * DK_MAX);
     for (int k = 0; k < DK_MAX; k++) thr[k] = all[(size_t)channel * DK_MAX + k];
+    return WFS_OK;
+} WFS_CATCH(h)
+
+// Lone-hit rows (wfs_lone.h): one pass over the starts [s0, s1) against the rows of the last wfs_run, or against no rows
+// when none is finished.  Everything the pass writes is a buffer of wfs_handle::lone and a counter block of its own; of the run it
+// reads the rows' ranges alone.  The work goes to the main stream behind the batch's packers.
+static int lone_windows(wfs_handle *h, std::vector<i64> &wl, std::vector<i64> &wr, std::vector<i32> &wg)
+{
+    if (!run_finished(h) || h->run.n_groups == 0) return WFS_OK;
+    const WfsDev &d = h->dev;
+    const std::vector<i64> lo = download(h, h->grp_lo, (size_t)h->run.n_groups), hi = download(h, h->grp_hi, (size_t)h->run.n_groups);
+    for (i64 g = 0; g < h->run.n_groups; g++) {
+        if (lo[(size_t)g] == I64_MAX) continue;         // (a window without a pulse has no row)
+        const RowSpan sp = full_row_span(lo[(size_t)g], hi[(size_t)g], d.tw);
+        if (!wl.empty() && !lone_windows_apart(wr.back(), sp.left, d.tlen, d.tw))
+            return h->fail(WFS_E_STATE, "wfs_lone_hits: two digitise windows of the last run lie within tlen + 2 tw samples of each other (right_raw_extension below (2 G + 64) dt)");
+        wl.push_back(sp.left); wr.push_back(sp.right); wg.push_back((i32)g);
+    }
+    return WFS_OK;
+}
+
+int wfs_lone_hits(wfs_handle *h, int64_t s0, int64_t s1, int64_t s_limit, int64_t *n_records)
+try {
+    if (!h) return WFS_E_INVALID;
+    if (!h->dark.set()) return h->fail(WFS_E_STATE, "wfs_lone_hits: no dark-count rates are set");
+    if (!h->tables_set) return h->fail(WFS_E_STATE, "wfs_lone_hits: tables not set");
+    if (!n_records) return h->fail(WFS_E_INVALID, "wfs_lone_hits: null n_records");
+    const WfsDev &d = h->dev;
+    auto &L = h->lone;
+    std::string err;
+    if (const int bad = lone_check(s0, s1, s_limit, h->dark.channels, d.tlen, d.tw, d.samples_before, err)) return h->fail(bad == 1 ? WFS_E_INVALID : WFS_E_CAPACITY, err);
+    HIPCHK(hipSetDevice(h->device));
+    L.n_rows = 0; L.n_records = 0; *n_records = 0;
+    if (s1 == s0) return WFS_OK;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    std::vector<i64> wl, wr; std::vector<i32> wg;
+    TRY(lone_windows(h, wl, wr, wg));
+    if (h->pack.must_wait()) HIPCHK(hipStreamWaitEvent(h->stream, h->rec_ready[h->pack.arena], 0));      // behind the batch's packers (the fence state stays as it is)
+    TRY(upload(h, L.win_l, wl.data(), wl.size())); TRY(upload(h, L.win_r, wr.data(), wr.size())); TRY(upload(h, L.win_g, wg.data(), wg.size()));
+    TRY(ensure(h, L.scal, 1));
+    LoneArgs a{};
+    a.s0 = s0; a.s1 = s1; a.s_limit = s_limit; a.a0 = s0 - lone_gap(d.tlen, d.tw);
+    a.m0 = lone_first_cell(a.a0, d.samples_before); a.n_cells = lone_last_cell(s_limit, d.samples_before) - a.m0 + 1;
+    a.n_win = (i64)wl.size(); a.win_l = L.win_l.p(); a.win_r = L.win_r.p(); a.win_g = L.win_g.p(); a.row_lo = h->row_lo.p(); a.row_hi = h->row_hi.p();
+    a.scal = L.scal.p();
+    // the list: twice the expected photons of the scanned cells and room for a small pass; a pass that finds more is scanned again with room
+    double expect = 0;
+    for (int c = 0; c < h->dark.channels; c++) expect += (double)h->dark.thr[(size_t)c * DK_MAX] / 4294967296.0 * 1.2 * (double)a.n_cells;
+    i64 cap = (i64)(2.0 * expect) + 4096;
+    WfsScal sc{};
+    for (int attempt = 0; ; attempt++) {
+        TRY(ensure(h, L.keys, (size_t)cap)); TRY(ensure(h, L.keys2, (size_t)cap));
+        a.keys = L.keys.p(); a.key_cap = cap;
+        HIPCHK(hipMemsetAsync(L.scal.p(), 0, sizeof(WfsScal), h->stream));
+        const i64 nb = (a.n_cells + LONE_SCAN_CELLS - 1) / LONE_SCAN_CELLS;
+        if (nb > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "wfs_lone_hits: lone hits: a pass of more than 2^39 cells per channel, split it");
+        TRY(launch(h, PLAIN(k_lone_scan), Shape(dim3((unsigned)nb, (unsigned)h->dark.channels), dim3(LONE_SCAN_CELLS)), d, a));
+        TRY(copy_async(h, &sc, L.scal.p(), 1, hipMemcpyDeviceToHost));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (sc.n_lone_photons <= cap) break;
+        if (attempt > 0) return h->fail(WFS_E_STATE, "wfs_lone_hits: internal: the photon list overflowed twice");
+        cap = sc.n_lone_photons;
+    }
+    const i64 NK = a.n_keys = sc.n_lone_photons;
+    if (NK == 0) return WFS_OK;
+    if (NK > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "wfs_lone_hits: lone hits: more than 2^31 lone photons in one pass, split it");
+    {   // by (channel, start): rocPRIM's radix sort over the key bits in use
+        unsigned end_bit = LONE_KEY_SHIFT; while (end_bit < 64 && ((u64)h->dark.channels >> (end_bit - LONE_KEY_SHIFT)) != 0) end_bit++;
+        size_t bytes = 0;
+        HIPCHK(rocprim::radix_sort_keys(nullptr, bytes, L.keys.p(), L.keys2.p(), (size_t)NK, 0u, end_bit, h->stream));
+        TRY(ensure(h, L.sort_tmp, bytes));
+        HIPCHK(rocprim::radix_sort_keys(L.sort_tmp.p, bytes, L.keys.p(), L.keys2.p(), (size_t)NK, 0u, end_bit, h->stream));
+        a.keys = L.keys2.p();
+    }
+    TRY(ensure(h, L.flag, (size_t)NK)); TRY(ensure(h, L.cap, (size_t)NK)); TRY(ensure(h, L.flen, (size_t)NK));
+    a.flag = L.flag.p(); a.cap = L.cap.p(); a.flen = L.flen.p();
+    TRY(launch(h, PLAIN(k_lone_rows), per_thread(NK), d, a));
+    TRY(scan(h, L.flag.p(), NK, L.row_of, &WfsScal::n_lone_rows, L.scal.p()));
+    TRY(scan(h, L.cap.p(), NK, L.itv_off, &WfsScal::n_itv_slots, L.scal.p()));
+    TRY(scan(h, L.flen.p(), NK, L.fin_off, &WfsScal::n_empty_samples, L.scal.p()));
+    TRY(copy_async(h, &sc, L.scal.p(), 1, hipMemcpyDeviceToHost));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (sc.lone_error) return h->fail(WFS_E_CAPACITY, "wfs_lone_hits: lone hits: a lone row of more than 2^19 samples (a chain of dark photons that long: lower the rate or s_limit)");
+    const i64 NR = sc.n_lone_rows;
+    if (NR > LONE_MAX_ROWS) return h->fail(WFS_E_CAPACITY, "wfs_lone_hits: lone hits: more than 2^24 lone rows in one pass, split it");
+    if (NR == 0) return WFS_OK;
+    TRY(ensure(h, L.desc, (size_t)NR)); TRY(ensure(h, L.pdesc, (size_t)NR));
+    TRY(ensure(h, L.out_channel, (size_t)NR)); TRY(ensure(h, L.out_nph, (size_t)NR)); TRY(ensure(h, L.out_left, (size_t)NR)); TRY(ensure(h, L.out_right, (size_t)NR)); TRY(ensure(h, L.out_ixr, (size_t)NR));
+    TRY(ensure(h, L.itv_left, (size_t)sc.n_itv_slots + 2)); TRY(ensure(h, L.itv_right, (size_t)sc.n_itv_slots + 2));
+    TRY(ensure(h, L.itv_n, (size_t)NR)); TRY(ensure(h, L.row_nrec, (size_t)NR));
+    TRY(ensure(h, L.fin, (size_t)sc.n_empty_samples + 8));
+    {
+        FillGroup fg(h, "fills_lone");
+        TRY(fg.zero(L.itv_n.p(), NR)); TRY(fg.zero(L.row_nrec.p(), NR));
+        TRY(fg.fill(&L.scal.p()->key_origin, 1, I64_MAX)); TRY(fg.fill(&L.scal.p()->key_end, 1, I64_MIN));
+        TRY(fg.flush());
+    }
+    a.row_of = L.row_of.p(); a.itv_off = L.itv_off.p(); a.fin_off = L.fin_off.p();
+    a.out_channel = L.out_channel.p(); a.out_nph = L.out_nph.p(); a.out_left = L.out_left.p(); a.out_right = L.out_right.p(); a.out_ixr = L.out_ixr.p();
+    TRY(launch(h, PLAIN(k_lone_desc), per_thread(NK), d, a, L.desc.p()));
+    // from here on the row list goes the way of a batch's rows without a pulse: k_row_empty with dark counts on, the record scan, the
+    // keys and the sort by (time, channel), k_pack_desc, k_pack_res
+    ZleArgs za{};
+    za.n_active_rows = NR; za.desc = L.desc.p(); za.fin = L.fin.p(); za.itv_left = L.itv_left.p(); za.itv_right = L.itv_right.p();
+    za.itv_n = L.itv_n.p(); za.row_nrec = L.row_nrec.p(); za.spr = WFS_SPR; za.key_base = L.scal.p(); za.pdesc = L.pdesc.p();
+    const int kind = d.enable_noise ? (int)noise_kind_of(d) : (int)NOISE_NONE;
+    TRY(launch(h, K_ROW_EMPTY(kind, true), per_wave(NR), d, za, (i64)0, NR));
+    TRY(scan(h, L.row_nrec.p(), NR, L.rec_off, &WfsScal::n_records, L.scal.p()));
+    TRY(copy_async(h, &sc, L.scal.p(), 1, hipMemcpyDeviceToHost));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const i64 NREC = sc.n_records;
+    L.n_rows = NR;
+    if (NREC > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "wfs_lone_hits: lone hits: more than 2^31 records in one pass, split it");
+    if (NREC > 0) {
+        TRY(ensure(h, L.records_buf(), (size_t)NREC * WFS_RECORD_BYTES));
+        za.rec_off = L.rec_off.p(); za.records = L.records_buf().as<uint8_t>(); za.rec_capacity = NREC;
+        if (NREC > 1) {
+            TRY(ensure(h, L.rec_key, (size_t)NREC)); TRY(ensure(h, L.rec_key2, (size_t)NREC));
+            TRY(ensure(h, L.rec_val, (size_t)NREC)); TRY(ensure(h, L.rec_val2, (size_t)NREC)); TRY(ensure(h, L.rec_dest, (size_t)NREC));
+            za.rec_key = L.rec_key.p(); za.rec_val = L.rec_val.p();
+            TRY(launch(h, PLAIN(k_rec_keys), per_wave(NR), d, za));
+            unsigned end_bit = 13;
+            { const u64 span = (u64)std::max<i64>(sc.key_end - sc.key_origin, 1); while (end_bit < 64 && ((span << 12) >> end_bit) != 0) end_bit++; }
+            size_t bytes = 0;
+            HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, L.rec_key.p(), L.rec_key2.p(), L.rec_val.p(), L.rec_val2.p(), (size_t)NREC, 0u, end_bit, h->stream));
+            TRY(ensure(h, L.sort_tmp, bytes));
+            HIPCHK(rocprim::radix_sort_pairs(L.sort_tmp.p, bytes, L.rec_key.p(), L.rec_key2.p(), L.rec_val.p(), L.rec_val2.p(), (size_t)NREC, 0u, end_bit, h->stream));
+            TRY(launch(h, PLAIN(k_invert_perm), per_thread(NREC), L.rec_val2.p(), L.rec_dest.p(), NREC));
+            za.rec_dest = L.rec_dest.p();
+        }
+        TRY(launch(h, PLAIN(k_pack_desc), per_thread(NR), za));
+        PackResArgs pr{L.pdesc.p(), L.fin.p(), za.itv_left, za.itv_right, za.records, za.rec_dest, za.rec_capacity, NR, za.spr, (i32)d.dt};
+        TRY(launch(h, PLAIN(k_pack_res), per_wave(NR), pr));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipGetLastError());
+    CHECK_LAUNCHES();
+    L.n_records = NREC; *n_records = NREC;
+    return WFS_OK;
+} WFS_CATCH(h)
+
+int wfs_copy_lone_records(wfs_handle *h, void *dst, int64_t capacity)
+try {
+    if (!h) return WFS_E_INVALID;
+    if (capacity < h->lone.n_records || (h->lone.n_records > 0 && !dst)) return h->fail(WFS_E_CAPACITY, "wfs_copy_lone_records: record buffer too small");
+    HIPCHK(hipSetDevice(h->device));
+    if (h->lone.n_records) HIPCHK(hipMemcpy(dst, h->lone.records_buf().p, (size_t)h->lone.n_records * WFS_RECORD_BYTES, hipMemcpyDeviceToHost));
+    return WFS_OK;
+} WFS_CATCH(h)
+
+int wfs_copy_lone_rows(wfs_handle *h, int32_t *channel, int64_t *left, int64_t *right, int64_t *ix_rand, int32_t *n_photons, int64_t capacity, int64_t *count)
+try {
+    if (!h || !count) return WFS_E_INVALID;
+    const i64 n = h->lone.n_rows;
+    *count = n;
+    if (capacity < n) return h->fail(WFS_E_CAPACITY, "wfs_copy_lone_rows: " + std::to_string(n) + " lone rows, capacity " + std::to_string(capacity));
+    if (n == 0) return WFS_OK;
+    if (!channel || !left || !right || !ix_rand || !n_photons) return h->fail(WFS_E_INVALID, "wfs_copy_lone_rows: null buffers");
+    HIPCHK(hipSetDevice(h->device));
+    auto &L = h->lone;
+    TRY(copy_out(h, channel, L.out_channel.p(), (size_t)n)); TRY(copy_out(h, n_photons, L.out_nph.p(), (size_t)n));
+    TRY(copy_out(h, left, L.out_left.p(), (size_t)n)); TRY(copy_out(h, right, L.out_right.p(), (size_t)n)); TRY(copy_out(h, ix_rand, L.out_ixr.p(), (size_t)n));
     return WFS_OK;
 } WFS_CATCH(h)
 

@@ -2591,6 +2591,149 @@ __global__ __launch_bounds__(256) void k_row_empty(WfsDev d, ZleArgs a, i64 firs
     zc.finish(d, a, lane, base, row_abs, len32, q.idx);
 }
 
+// ---- Lone-hit rows (wfs_lone_hits; the rule: wfs_lone.h): the dark photons outside the rows of the last run, read out in
+// rows of their own.  k_lone_scan finds them, the host sorts their keys by (channel, start), k_lone_rows / k_lone_desc form the chains
+// and describe their rows like rows without a pulse (RowDesc::src 2), and k_row_empty<NK, DK = 1>, k_rec_keys, k_pack_desc and
+// k_pack_res take that row list as they take a batch's: nothing of a finished sample or a record is defined a second time.
+struct LoneArgs {
+    i64 s0, s1, s_limit;         // the pass owns the rows whose first photon starts in [s0, s1); chains are followed up to s_limit
+    i64 a0;                      // s0 - G: first start the scan lists, origin of the photon keys
+    i64 m0, n_cells;             // first cell and cells of a channel: those of the starts a0 .. s_limit - 1
+    // the windows of the last run that hold a pulse, in time order: range of their widest row, group; rows of the run (k_tile_rows, k_rows_widen)
+    i64 n_win; const i64 *win_l, *win_r; const i32 *win_g; const i64 *row_lo, *row_hi;
+    u64 *keys; i64 key_cap, n_keys;      // lone photons: channel << LONE_KEY_SHIFT | start - a0; n_keys: the sorted ones (k_lone_rows, k_lone_desc)
+    WfsScal *scal;               // the pass's own counter block
+    i32 *flag, *cap, *flen;      // [n_keys] 1 / interval slots / finished samples of the row whose first photon this is, else 0
+    const i64 *row_of, *itv_off, *fin_off;       // their scans
+    i32 *out_channel, *out_nph; i64 *out_left, *out_right, *out_ixr;      // [rows] the listing of wfs_copy_lone_rows
+};
+constexpr int LONE_KEY_SHIFT = 40;
+static_assert(LONE_MAX_SPAN <= ((int64_t)1 << LONE_KEY_SHIFT), "a start of a pass fits the low bits of its key");
+static_assert(LONE_SCAN_CELLS == 256, "k_lone_scan: a workgroup of 256 lanes, a cell each");
+
+// the last window that begins at or in front of sample t, or -1 (bisection: the windows are in time order)
+__device__ __forceinline__ i64 lone_window_at(const LoneArgs &a, i64 t)
+{
+    i64 lo = 0, hi = a.n_win;
+    while (lo < hi) { const i64 mid = (lo + hi) >> 1; if (a.win_l[mid] <= t) lo = mid + 1; else hi = mid; }
+    return lo - 1;
+}
+// the row of channel ch in window w at its final range
+struct LoneRow { bool has; i64 l, r; };
+__device__ __forceinline__ LoneRow lone_row_of(const WfsDev &d, const LoneArgs &a, i64 w, i32 ch)
+{
+    LoneRow q{false, 0, 0};
+    if (w < 0) return q;
+    const i64 ridx = (i64)a.win_g[w] * d.n_tpc + ch;
+    const i64 lo = a.row_lo[ridx];
+    if (lo != I64_MAX) { const RowSpan sp = row_span(lo, a.row_hi[ridx], d.tw); q.has = true; q.l = sp.left; q.r = sp.right; }
+    else if (d.full_readout) { q.has = true; q.l = a.win_l[w]; q.r = a.win_r[w]; }
+    return q;
+}
+// a pulse that starts at `start`: does it stay clear of every row of ch?  (the windows lie more than G apart: one can meet it)
+__device__ __forceinline__ bool lone_is_lone(const WfsDev &d, const LoneArgs &a, i32 ch, i64 start)
+{
+    const LoneRow q = lone_row_of(d, a, lone_window_at(a, start + d.tlen - 1), ch);
+    return !(q.has && lone_pulse_meets(start, d.tlen, q.l, q.r));
+}
+
+// A lane per cell over a grid of (block of LONE_SCAN_CELLS cells, channel).  The count word is word 0 of site 112 -- the definition of
+// the cell's photons cannot differ from dark_sample's --, one ballot per wave, and the all-empty wave does nothing more.  Lanes of
+// non-empty cells take their photons from sites 113 / 114, test them against the one row that can hold them, and the wave appends
+// its lone ones to the list with one reservation.  The channel's thresholds and constants are uniform over the workgroup.
+__global__ __launch_bounds__(LONE_SCAN_CELLS) void k_lone_scan(WfsDev d, LoneArgs a)
+{
+    const i32 ch = (i32)blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const u32 *T = d.dk_thr + (size_t)ch * DK_MAX;
+    if (T[0] == 0u || d.gains[ch] == 0.0) return;                            // (uniform)
+    const i64 c = (i64)blockIdx.x * LONE_SCAN_CELLS + threadIdx.x;
+    const i64 m = a.m0 + c;
+    int n = 0;
+    if (c < a.n_cells) n = dark_count_of(T, dark_call(d, ch, m, SITE_DARK_N).x);
+    if (ballot64(n > 0) == 0) return;                                        // wave-uniform
+    i64 st[DK_MAX]; u32 lone = 0;
+#pragma unroll
+    for (int j = 0; j < DK_MAX; j++) {
+        st[j] = 0;
+        if (j < n) {
+            const DarkPhoton p = dark_photon_of(d, ch, m, j, dark_call(d, ch, m, SITE_DARK_PH + (u32)(j >> 1)));
+            st[j] = m * DK_CELL + p.bin - d.samples_before;
+            if (st[j] >= a.a0 && st[j] < a.s_limit && lone_is_lone(d, a, ch, st[j])) lone |= 1u << j;
+        }
+    }
+    u64 b[DK_MAX]; i32 total = 0;
+#pragma unroll
+    for (int j = 0; j < DK_MAX; j++) { b[j] = ballot64(((lone >> j) & 1u) != 0); total += __popcll(b[j]); }
+    if (total == 0) return;                                                  // wave-uniform
+    i64 base = 0;
+    if (lane == 0) base = (i64)atomicAdd((u64 *)&a.scal->n_lone_photons, (u64)total);
+    base = __shfl(base, 0, 64);
+    const u64 lt = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int j = 0; j < DK_MAX; j++) {
+        const i64 at = base + __popcll(b[j] & lt);
+        if (((lone >> j) & 1u) && at < a.key_cap) a.keys[at] = ((u64)(u32)ch << LONE_KEY_SHIFT) | (u64)(st[j] - a.a0);
+        base += __popcll(b[j]);
+    }
+}
+
+// The chain that photon i of the sorted list begins, if it begins one this pass owns: photon i has no lone photon of its channel
+// within G in front of it and starts in [s0, s1); the chain runs on while the next photon of the channel starts at most G behind the
+// last (the list ends in front of s_limit).  Its range: lone_range, clipped by the one row that can lie within its margins on either
+// side.  A chain cannot straddle a row (lone_cannot_straddle): every row of the run holds a pulse or spans its window.
+struct LoneChain { bool owned; i32 ch, n; i64 left, right; };
+__device__ __forceinline__ LoneChain lone_chain_of(const WfsDev &d, const LoneArgs &a, i64 i)
+{
+    const u64 lowmask = (1ull << LONE_KEY_SHIFT) - 1ull;
+    const i64 G = lone_gap(d.tlen, d.tw);
+    const u64 key = a.keys[i];
+    LoneChain c{false, (i32)(key >> LONE_KEY_SHIFT), 0, 0, 0};
+    const i64 first = a.a0 + (i64)(key & lowmask);
+    if (first < a.s0 || first >= a.s1) return c;
+    if (i > 0) { const u64 pk = a.keys[i - 1]; if ((i32)(pk >> LONE_KEY_SHIFT) == c.ch && first - (a.a0 + (i64)(pk & lowmask)) <= G) return c; }
+    i64 last = first, j = i + 1;
+    for (; j < a.n_keys; j++) {
+        const u64 nk = a.keys[j];
+        const i64 s = a.a0 + (i64)(nk & lowmask);
+        if ((i32)(nk >> LONE_KEY_SHIFT) != c.ch || s - last > G) break;
+        last = s;
+    }
+    const LoneRow pr = lone_row_of(d, a, lone_window_at(a, first - 1), c.ch);
+    const LoneRow nr = lone_row_of(d, a, lone_window_at(a, last + d.tlen - 1 + d.tw), c.ch);
+    const LoneRange rg = lone_range(first, last, d.tlen, d.tw, (pr.has && pr.r < first) ? pr.r : I64_MIN, (nr.has && nr.l > last) ? nr.l : I64_MAX, a.s_limit);
+    c.owned = true; c.n = (i32)(j - i); c.left = rg.left; c.right = rg.right;
+    return c;
+}
+// thread per listed photon: the flag of a row's first photon, the interval slots and the finished samples its row reserves
+__global__ void k_lone_rows(WfsDev d, LoneArgs a)
+{
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_keys) return;
+    const LoneChain c = lone_chain_of(d, a, i);
+    i64 len = c.owned ? c.right - c.left + 1 : 0;
+    if (len > LONE_MAX_ROW_LEN) { atomicMax(&a.scal->lone_error, (i64)1); len = 0; }
+    a.flag[i] = len > 0 ? 1 : 0;
+    a.cap[i] = len > 0 ? (i32)zle_slots(len, zle_holdoff(d.tw)) : 0;
+    a.flen[i] = len > 0 ? fin_padded_len((i32)len) : 0;
+}
+// thread per listed photon, behind the scans: the descriptor of its row (as k_row_desc writes one for a row without a pulse) and the listing
+__global__ void k_lone_desc(WfsDev d, LoneArgs a, RowDesc *desc)
+{
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_keys || !a.flag[i]) return;
+    const LoneChain c = lone_chain_of(d, a, i);
+    const i64 row = a.row_of[i];
+    const bool table = d.enable_noise && !d.nm_cells && (d.noise || d.noise_f);
+    RowDesc q;
+    q.acc_off = a.fin_off[i]; q.row_abs = c.left; q.itv_base = a.itv_off[i];
+    q.ixr = lone_ix_rand(philox4x32_10((u32)(u64)c.left, (u32)((u64)c.left >> 32), (u32)c.ch, SITE_LONE_IX, d.k0, d.k1).x, table ? (i64)d.noise_len : 0);
+    q.thr = d.thr_zle[c.ch]; q.idx = row; q.len = (i32)(c.right - c.left + 1); q.channel = c.ch; q.he = 0; q.src = 2;
+    desc[row] = q;
+    atomicMin(&a.scal->key_origin, q.row_abs); atomicMax(&a.scal->key_end, q.row_abs + (i64)q.len);
+    a.out_channel[row] = c.ch; a.out_nph[row] = c.n; a.out_left[row] = c.left; a.out_right[row] = c.right; a.out_ixr[row] = q.ixr;
+}
+
 // Records ordered by (time, channel) as strax.sort_by_time leaves them (strax_interface.py:453): one key per record; the
 // windows of a batch do not overlap in time, so one sort of the whole batch keeps every window contiguous.
 __global__ __launch_bounds__(256) void k_rec_keys(WfsDev d, ZleArgs a)

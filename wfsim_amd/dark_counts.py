@@ -84,3 +84,45 @@ def rates_from(config, n_channels=None):
     if np.any(mu_of(r, dt) > MU_MAX):
         raise ValueError(f'dark_count_rate: above {max_rate(dt):.4g} Hz, more than 1/8 photons per cell of {CELL} samples')
     return r if np.any(r > 0) else None
+
+
+# ---- lone-hit rows (config 'dark_count_lone_hits', wfs_lone_hits)
+
+def lone_gap(params):
+    """G = tlen + 2 tw [samples]: lone photons of a channel whose starts are at most G apart share a row"""
+    return int(params['tlen']) + 2 * int(params['trigger_window'])
+
+
+def lone_min_rext(params):
+    """the smallest right_raw_extension [ns] the lone-hit passes of RawData take: (2 G + 64) dt (wfs_lone.h, lone_min_rext)"""
+    return (2 * lone_gap(params) + CELL) * int(params['dt'])
+
+
+def lone_hits_from(config, params=None):
+    """True when config['dark_count_lone_hits'] asks for lone-hit rows; raises ValueError when it does and they cannot be had"""
+    if not config.get('dark_count_lone_hits', False):
+        return False
+    if rates_from(config, None if params is None else params['n_tpc']) is None:
+        raise ValueError("dark_count_lone_hits: needs config['dark_count_rate'] (a rate above zero on some channel)")
+    if params is None:
+        from .config import kernel_params
+        params = kernel_params(config)
+    # A new window begins where a cluster's first time lies more than right_raw_extension (rext) behind the end of the last pulse,
+    # (a_hi - tw) dt for rows that end at sample a_hi.  A pulse begins `before` + samples_to_store_before samples ahead of its first
+    # photon, a row tw ahead of that, and a window's left may go one sample down to an even one: the next window's rows begin at
+    # b_lo >= a_hi + rext / dt - (2 tw + before + store_before + 2).  From rext >= (2 G + 64) dt = (2 tlen + 4 tw + 64) dt follows
+    # b_lo - a_hi >= G + tlen + (64 - before - store_before - 2), which is more than G + tlen - 1 while before + store_before + 2 < 64:
+    #  * a pulse (tlen samples) or a row's margins (G in all) cannot reach from the rows of one window into those of the next, so a
+    #    lone row meets at most one window at either end -- what the single window look-up of k_lone_scan / k_lone_rows relies on
+    #    (wfs_lone_hits checks the distance of the windows it is given);
+    #  * a photon that starts within G samples behind a window ends in front of the next one's rows, so RawData can end a batch's
+    #    pass G samples behind the batch's last window without knowing the next.
+    # 64, a cell, is the slack that pays for `before` and samples_to_store_before.
+    if int(params['samples_before']) + int(params['store_before']) + 2 >= CELL:
+        raise ValueError('dark_count_lone_hits: samples_to_store_before + samples_before_pulse_center + 2 must stay below 64 '
+                         '(the bound on right_raw_extension assumes it)')
+    need = lone_min_rext(params)
+    if int(params['rext']) < need:
+        raise ValueError(f"dark_count_lone_hits: right_raw_extension {int(params['rext'])} ns below (2 G + 64) dt = {need} ns "
+                         f"(G = tlen + 2 trigger_window = {lone_gap(params)} samples)")
+    return True

@@ -256,6 +256,9 @@ class Engine:
         rates = rates_from(self.config, self.params['n_tpc'])
         if rates is not None:
             self.set_dark_counts(rates)
+        # lone-hit rows (config 'dark_count_lone_hits'): RawData runs a pass of lone_hits behind every batch
+        from .dark_counts import lone_hits_from
+        self.lone_hits_on = lone_hits_from(self.config, self.params)
 
     def _init_pattern_maps(self, resource):
         # pattern maps on regular grids are evaluated on the device (one channel CDF row per instruction)
@@ -787,6 +790,31 @@ class Engine:
         thr = np.zeros(4, dtype=np.uint32)
         self._call('wfs_copy_dark_counts', channel, thr)
         return thr
+
+    def lone_hits(self, s0, s1, s_limit=None):
+        """raw_records of the lone-hit rows (wfs_lone_hits) whose first dark photon starts at an absolute sample in [s0, s1),
+        in (time, channel) order: the dark photons outside the rows of the last ``run()`` (outside every row when there was none).
+        A chain of photons is followed beyond s1 but no further than ``s_limit`` (default: s1).  Needs dark-count rates."""
+        n = np.zeros(1, dtype=np.int64)
+        self._call('wfs_lone_hits', int(s0), int(s1), int(s1 if s_limit is None else s_limit), n)
+        out = np.zeros(int(n[0]), dtype=raw_record_dtype())
+        if len(out):
+            self._call('wfs_copy_lone_records', out, len(out))
+        return out
+
+    def lone_hit_rows(self):
+        """the rows of the last ``lone_hits`` pass in (channel, time) order: a structured array (channel, left, right, ix_rand,
+        n_photons) -- first and last absolute sample, the noise-table offset (0 without a table), the lone photons of the chain"""
+        k = np.zeros(1, dtype=np.int64)
+        self._call('wfs_copy_lone_rows', None, None, None, None, None, 0, k, check=False)
+        n = int(k[0])
+        ch, nph = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        left, right, ixr = (np.zeros(n, dtype=np.int64) for _ in range(3))
+        if n:
+            self._call('wfs_copy_lone_rows', ch, left, right, ixr, nph, n, k)
+        out = np.zeros(n, dtype=[('channel', np.int32), ('left', np.int64), ('right', np.int64), ('ix_rand', np.int64), ('n_photons', np.int32)])
+        out['channel'], out['left'], out['right'], out['ix_rand'], out['n_photons'] = ch, left, right, ixr, nph
+        return out
 
     def noise_model_cells(self, channel):
         """the Walker alias cells the device samples a channel's noise from: dict(thr, alias, shift, vmin); cell c = word >> shift gives

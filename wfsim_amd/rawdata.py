@@ -61,6 +61,23 @@ def dark_count_records(config, params, s_ins, quanta):
     return rows * window * int(params['dt']) * 1e-9 * float(rates.sum()) / n_tpc
 
 
+def lone_stretches(rec):
+    """Lone-hit records (time sorted) cut into stretches that do not overlap in time -- a lone row and the rows of other channels that
+    overlap it: (left[], right[] in samples, first[] record offsets, one more than stretches).  No stretch cuts a row: the fragments of
+    an interval follow each other without a gap."""
+    n = len(rec)
+    if n == 0:
+        z = np.zeros(0, dtype=np.int64)
+        return z, z, np.zeros(1, dtype=np.int64)
+    dt = rec['dt'].astype(np.int64)
+    start = rec['time'] // dt
+    end = start + rec['length'].astype(np.int64)             # one past the record's last sample
+    reach = np.maximum.accumulate(end)
+    cut = np.flatnonzero(start[1:] > reach[:-1]) + 1          # a record that begins behind everything before it
+    first = np.concatenate([[0], cut, [n]]).astype(np.int64)
+    return start[first[:-1]], reach[first[1:] - 1] - 1, first
+
+
 class RawData:
     #: upper bound on the expected photons of one GPU batch (sizes the HBM arenas; 288 GB HBM3E leaves room for ~10^10)
     max_batch_quanta = 2_000_000_000
@@ -120,7 +137,9 @@ class RawData:
 
     def iter_windows(self, instructions, truth_buffer=None, **kwargs):
         """Yields dict(left, right, records) per digitise window, in time order.  ``records`` are packed strax
-        raw_records in the order the reference yields pulses (channel ascending, interval ascending)."""
+        raw_records in the order the reference yields pulses (channel ascending, interval ascending).  With
+        config['dark_count_lone_hits'] the lone-hit rows come between the windows, in time order, as entries
+        dict(left, right, records, lone=True): one per stretch of lone rows that overlap in time, records by (time, channel)."""
         if truth_buffer is None:
             truth_buffer = []
         self.engine.set_record_order(False)
@@ -128,23 +147,39 @@ class RawData:
             table, rows, before = batch['truth_table'], batch['truth_rows'], batch['truth_before']
             k = 0
             n_win = len(batch['left'])
+            lone, q = batch.get('lone_records'), 0
+            if lone is not None:
+                lone_left, lone_right, lone_first = lone_stretches(lone)
             for w in range(n_win):
                 k1 = int(np.searchsorted(before, w, side='right'))      # the rows of this window's clusters (and of empty ones before it)
                 if k1 > k:
                     self._write_truth(table, rows[k:k1], truth_buffer)
                     k = k1
+                if lone is not None:            # the lone-hit rows in front of this window
+                    stop = int(np.searchsorted(lone_left, int(batch['left'][w]), side='left'))
+                    yield from self._lone_entries(lone, lone_left, lone_right, lone_first, q, stop)
+                    q = stop
                 self.left, self.right = int(batch['left'][w]), int(batch['right'][w])
-                if batch['finished'] and w == n_win - 1:
+                if batch['finished'] and w == n_win - 1 and (lone is None or q == len(lone_left)):
                     self.source_finished = True
                 yield dict(left=self.left, right=self.right, records=batch['records'][batch['first'][w]:batch['first'][w + 1]])
+            if lone is not None:
+                yield from self._lone_entries(lone, lone_left, lone_right, lone_first, q, len(lone_left))
             if k < len(rows):
                 self._write_truth(table, rows[k:], truth_buffer)
         self.source_finished = True
 
+    def _lone_entries(self, lone, left, right, first, a, b):
+        """entries dict(left, right, records, lone=True) of the lone-hit stretches a .. b - 1 of a batch (lone_stretches)"""
+        for j in range(a, b):
+            self.left, self.right = int(left[j]), int(right[j])
+            yield dict(left=self.left, right=self.right, records=lone[first[j]:first[j + 1]], lone=True)
+
     def iter_batches(self, instructions, want_truth=False, record_sink=None, device_records=False, **kwargs):
         """The same stream batch by batch (what the chunker consumes): dict(left[], right[] of the batch's digitise windows
         in time order, first[] record offsets (one more than windows), records, truth_table + truth_rows + truth_before (row truth_rows[k] of the table belongs in
-        front of window truth_before[k]; == number of windows: after the last), finished).  ``record_sink(n, first_left)`` may hand out
+        front of window truth_before[k]; == number of windows: after the last), finished; with config['dark_count_lone_hits'] also
+        lone_records, the lone-hit rows up to the end of the batch's last window, by (time, channel)).  ``record_sink(n, first_left)`` may hand out
         the array the records are copied into (device -> host without a staging copy); ``device_records``: the records stay
         on the GPU (``records`` is a torch uint8 tensor of n * 244 bytes)."""
         self.source_finished = False
@@ -228,6 +263,8 @@ class RawData:
                 batch = dict(left=groups['left'][keep], right=groups['right'][keep],
                              first=np.append(first[keep], first[n_emit]) if len(keep) else np.array([first[n_emit]]),
                              records=records, truth_table=truth_table, truth_rows=truth_rows, truth_before=truth_before, finished=L['b'] >= n)
+                if L.get('lone_records') is not None:       # config['dark_count_lone_hits']: the pass behind this batch's run (_launch)
+                    batch['lone_records'] = L['lone_records']
                 # everything else of this batch is on the host now: the engine is free for the next one (it keeps the records of
                 # two batches: this batch's copy overlaps the next batch's kernels)
                 if L['b'] < n:
@@ -293,8 +330,67 @@ class RawData:
                 e = ends[keep]
                 runmax = max(int(e.max()), runmax) if has_pulse else int(e.max())
                 has_pulse = True
-            return dict(b=b, ins=ins, cl=cl, n_emit=n_emit, first=first, nonempty=nonempty, ins_group=ins_group, groups=groups,
-                        run_set=getattr(self, '_run_set', None), has_pulse=has_pulse, runmax=runmax)
+            out = dict(b=b, ins=ins, cl=cl, n_emit=n_emit, first=first, nonempty=nonempty, ins_group=ins_group, groups=groups,
+                       run_set=getattr(self, '_run_set', None), has_pulse=has_pulse, runmax=runmax)
+            if getattr(self.engine, 'lone_hits_on', False):
+                # directly behind the batch's run, on the thread that owns the engine: the rows of that run are what a photon is lone against
+                out['lone_records'] = self._lone_pass(st, groups, keep, nonempty, n_emit, b >= n)
+            return out
+
+    #: samples of one pass of wfs_lone_hits at most; a longer range is a run of passes with the same records (_lone_range)
+    lone_pass_samples = 1 << 28
+
+    def _lone_pass(self, st, groups, keep, nonempty, n_emit, finished):
+        """The lone-hit pass of a batch: from the end of the previous pass to G samples behind dg_right of the batch's last
+        emitted window; the first pass begins at config['lone_hits_begin'] (ns; default: the first window's left minus
+        right_raw_extension), the last one ends at config['lone_hits_end'] (default: the last window's right plus
+        right_raw_extension).  s_limit: the left of the next window where the run knows it, else G + 64 samples short of dg_right + 1 +
+        right_raw_extension / dt; no later window begins in front of either, and both lie behind s1 (dark_counts.lone_hits_from)."""
+        from .dark_counts import lone_gap
+        cfg, p = self.config, self.engine.params
+        dt, rext = int(p['dt']), int(p['rext']) // int(p['dt'])
+        empty = np.zeros(0, dtype=raw_record_dtype())
+        if st.get('lone_next') is None:
+            begin = cfg.get('lone_hits_begin', getattr(self, 'lone_begin_ns', None))
+            if begin is None and not len(keep):
+                return empty                    # (no window yet: the first pass waits for one)
+            st['lone_next'] = int(begin) // dt if begin is not None else int(groups['left'][keep[0]]) - rext
+        s0 = st['lone_next']
+        if len(keep):
+            st['lone_last_right'] = int(groups['right'][keep[-1]])
+        if finished:
+            end = cfg.get('lone_hits_end')
+            if end is None and st.get('lone_last_right') is None:
+                return empty
+            s1 = int(end) // dt if end is not None else st['lone_last_right'] + 1 + rext
+            s_limit = s1
+        else:
+            if not len(keep):
+                return empty
+            # G samples beyond the last emitted window: the next pass then looks back at samples behind that window alone, whose rows
+            # it no longer has (a photon there could pass for lone and keep the one behind it from beginning a row)
+            s1 = st['lone_last_right'] + 1 + lone_gap(p)
+            later = np.flatnonzero(nonempty[n_emit:])
+            s_limit = int(groups['left'][n_emit + later[0]]) if len(later) else st['lone_last_right'] + 1 + rext - (lone_gap(p) + 64)
+        s1 = max(s1, s0)
+        s_limit = max(s_limit, s1)
+        st['lone_next'] = s1
+        return self._lone_range(s0, s1, s_limit)
+
+    def _lone_range(self, s0, s1, s_limit):
+        """Engine.lone_hits over [s0, s1) in passes of at most lone_pass_samples.  A piece that ends at b follows its chains to
+        b + 2^19 + G at most: a lone row is at most 2^19 samples long (a longer one ends the pass in an error), so no chain that begins in
+        front of b is cut there and the pieces' records are those of the one pass."""
+        from .dark_counts import lone_gap
+        reach = (1 << 19) + lone_gap(self.engine.params)
+        parts, a = [], s0
+        while a < s1:
+            b = min(a + self.lone_pass_samples, s1)
+            parts.append(self.engine.lone_hits(a, b, s_limit if b == s1 else min(s_limit, b + reach)))
+            a = b
+        if not parts:
+            return np.zeros(0, dtype=raw_record_dtype())
+        return parts[0] if len(parts) == 1 else np.concatenate(parts)
 
     def _expected_quanta(self, s_ins):
         return np.where(s_ins['type'] == 1, s_ins['amp'] * 0.15,
@@ -308,7 +404,19 @@ class RawData:
             rec = rec + full_readout_records(self.config, self.engine.params, s_ins)
         if self.config.get('dark_count_rate') is not None:
             rec = rec + dark_count_records(self.config, self.engine.params, s_ins, q)
+        if self.config.get('dark_count_lone_hits', False) and len(s_ins):
+            # the lone-hit pass of a batch covers the time from the batch before it: every instruction is charged the span since the
+            # one before it (the first: right_raw_extension)
+            t = s_ins['time'].astype(np.int64)
+            rec = rec + self.lone_hit_records(np.maximum(np.diff(t, prepend=t[0] - int(self.config['right_raw_extension'])), 0))
         return rec
+
+    def lone_hit_records(self, span_ns):
+        """expected lone-hit records of a time span [ns] (config['dark_count_lone_hits']): a record per dark photon, the sum of the
+        rates x the span -- an estimate, as dark_count_records is one"""
+        from .dark_counts import rates_from
+        rates = rates_from(self.config, self.engine.params['n_tpc'])
+        return np.asarray(span_ns, dtype=np.float64) * (0.0 if rates is None else float(rates.sum()) * 1e-9)
 
     def _load_batch(self, ins, gid, cl, key):
         ip = instruction_params(ins, self.config, self.engine.resource, gids=gid, device_maps=self.engine.device_maps, device_aft=self.engine._aft_on_device)

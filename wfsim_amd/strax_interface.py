@@ -181,8 +181,16 @@ class ChunkRawRecords(object):
                     return spare[:n]
             return self.record_buffer[self.blevel:self.blevel + n] if self.blevel + n <= L else None
 
-        for batch in rd.iter_batches(instructions, want_truth=True, record_sink=sink, **kwargs):
+        # lone-hit rows (config 'dark_count_lone_hits'): a batch's lone records are merged with its window records by time on
+        # the host, so a batch does not arrive where it stays and the sink is not offered
+        lone_on = bool(getattr(getattr(rd, 'engine', None), 'lone_hits_on', False))
+        if lone_on and self.config.get('lone_hits_begin') is None:
+            # no lone record in front of the first chunk: a row begins trigger_window samples ahead of its first photon
+            rd.lone_begin_ns = self.chunk_time_pre + int(self.config['trigger_window']) * dt
+        for batch in rd.iter_batches(instructions, want_truth=True, record_sink=None if lone_on else sink, **kwargs):
             self._batch_leases = []             # buffers handed out while this batch is worked on stay taken until it is done
+            if len(batch.get('lone_records', ())):
+                batch = merge_lone_records(batch)
             rec, first, left, right = batch['records'], batch['first'], batch['left'], batch['right']
             table, rows, before = batch['truth_table'], batch['truth_rows'], batch['truth_before']
             left_ns = left * dt
@@ -413,6 +421,49 @@ class ChunkRawRecords(object):
 
     def source_finished(self):
         return self.rawdata.source_finished
+
+
+def merge_lone_records(batch):
+    """A batch of RawData.iter_batches with its lone-hit records merged in by time.  The digitise windows and the
+    stretches of lone rows (rawdata.lone_stretches) are entries [left, right]; entries that overlap in time -- a lone row on a channel
+    that has no row in a window -- are joined into one, so that the entries of the result do not overlap, follow each other in time and
+    hold their records by (time, channel), as the windows of a batch do.  The chunker treats such an entry as it treats a window:
+    committed whole, and a chunk's end moves behind an entry that holds it, so no lone row is cut.  Truth rows keep their windows."""
+    from .rawdata import lone_stretches
+    lone = batch['lone_records']
+    l_left, l_right, l_first = lone_stretches(lone)
+    left, right, first, rec = batch['left'], batch['right'], batch['first'], batch['records']
+    n_win = len(left)
+    e_left, e_right = np.concatenate([left, l_left]).astype(np.int64), np.concatenate([right, l_right]).astype(np.int64)
+    order = np.argsort(e_left, kind='stable')
+    reach = np.maximum.accumulate(e_right[order])
+    new = np.concatenate([[True], e_left[order][1:] > reach[:-1]])
+    entry_of = np.empty(len(order), dtype=np.int64)
+    entry_of[order] = np.cumsum(new) - 1
+    n = int(new.sum())
+    m_left, m_right = e_left[order][new], reach[np.append(np.flatnonzero(new)[1:] - 1, len(order) - 1)]
+    m_len = (np.bincount(entry_of[:n_win], weights=np.diff(first), minlength=n)
+             + np.bincount(entry_of[n_win:], weights=np.diff(l_first), minlength=n)).astype(np.int64)
+    m_first = np.concatenate([[0], np.cumsum(m_len)]).astype(np.int64)
+    # both record lists are in (time, channel) order and entries do not overlap: one merge by time puts every record into its entry
+    rec = rec[:int(first[-1])]
+    t_w, t_l = rec['time'], lone['time']
+    at = np.searchsorted(t_w, t_l, side='left')
+    tie = (at < len(t_w)) & (t_w[np.minimum(at, max(len(t_w) - 1, 0))] == t_l) if len(t_w) else np.zeros(len(t_l), dtype=bool)
+    out = np.empty(len(rec) + len(lone), dtype=lone.dtype)
+    if tie.any():               # a lone record and a window record of one time: by channel
+        both = np.concatenate([rec, lone])
+        out[:] = both[np.lexsort((both['channel'], both['time']))]
+    else:
+        where = at + np.arange(len(lone))
+        mask = np.ones(len(out), dtype=bool)
+        mask[where] = False
+        out[where], out[mask] = lone, rec
+    before = np.asarray(batch['truth_before'], dtype=np.int64)
+    new_before = np.where(before < n_win, entry_of[np.minimum(before, max(n_win - 1, 0))], n) if n_win else np.full(len(before), n, dtype=np.int64)
+    merged = dict(batch, left=m_left, right=m_right, first=m_first, records=out, truth_before=new_before)
+    del merged['lone_records']
+    return merged
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -698,6 +749,8 @@ class RawRecordsFromMcChain(SimulatorPlugin):
             # 'dark_count_rate_nveto' (or a 'dark_count_rate' inside fax_config_nveto) and has none otherwise
             cn['dark_count_rate'] = cn.pop('dark_count_rate_nveto', None)
             cn.update(self.config.get('fax_config_nveto') or {})
+            if cn.get('dark_count_rate') is None:       # 'dark_count_lone_hits'  reaches the veto engine with veto rates alone
+                cn.pop('dark_count_lone_hits', None)
             cn['detector'] = 'XENONnT_neutron_veto'
             cn['channel_map'] = dict(cn['channel_map'])
             if self.config.get('fax_config_override_nveto') is not None:
