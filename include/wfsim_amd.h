@@ -477,7 +477,8 @@ int wfs_dark_count_samples(wfs_handle *h, int32_t channel, int64_t t0, int64_t n
 int wfs_dark_count_photons(wfs_handle *h, int32_t channel, int64_t t0, int64_t n, int64_t *t_ns, double *gain, int64_t capacity, int64_t *count);
 /* The thresholds T[channel][1 .. 4] as the device holds them.  WFS_E_STATE without rates. */
 int wfs_copy_dark_counts(wfs_handle *h, int32_t channel, uint32_t thr[4]);
-/* Lone-hit rows (config 'dark_count_lone_hits'): the dark photons outside the rows of a run, read out in rows of their own.
+/* Lone-hit rows (config 'dark_count_lone_hits'): the dark photons outside the rows of a run, read out in rows of their own;
+ * with wfs_set_lone_noise_hits (below) the samples of the noise model that cross their threshold there are seeds of such rows too.
  * start = idx - before is the first sample of a dark photon's pulse, G = tlen + 2 tw.
  *   lone     a dark photon of PMT channel ch whose pulse samples start .. start + tlen - 1 lie in no row of ch's TPC slot.  Rows: those
  *            of the last completed wfs_run at their final range (every channel of a window under full readout), none when no run is
@@ -493,16 +494,42 @@ int wfs_copy_dark_counts(wfs_handle *h, int32_t channel, uint32_t thr[4]);
  *            passes of one s_limit, the records are the same.
  * The windows of the run must lie more than G samples apart (WFS_E_STATE otherwise).  The pass has buffers of its own, runs behind the
  * packers of the batch and leaves that batch's records as they are; it returns when its records exist.  *n_records: how many.
- * WFS_E_STATE without rates or tables; WFS_E_INVALID for s1 < s0, s_limit < s1 or a range beyond 2^48; WFS_E_CAPACITY, with a message
- * that names lone hits, for a pass of more than 2^40 samples, 2^34 cells (channels x 64-sample cells), 2^24 rows or 2^31 records, or
- * a lone row of more than 2^19 samples. */
+ * WFS_E_STATE without tables, and without rates unless noise hits are on; WFS_E_INVALID for s1 < s0, s_limit < s1 or a range beyond 2^48; WFS_E_CAPACITY, with a message
+ * that names lone hits, for a pass of more than 2^40 samples, 2^34 cells (channels x 64-sample cells), 2^31 seeds (lone photons and
+ * noise hits), 2^24 rows or 2^31 records, or a lone row of more than 2^19 samples (a chain of dark photons, or noise that stays across
+ * the threshold). */
 int wfs_lone_hits(wfs_handle *h, int64_t s0, int64_t s1, int64_t s_limit, int64_t *n_records);
 /* The records of the last pass in (time, channel) order, in the layout of wfs_copy_records.  capacity: records the buffer holds. */
 int wfs_copy_lone_records(wfs_handle *h, void *dst, int64_t capacity);
 /* The rows of the last pass in (channel, time) order: channel, first and last sample, ix_rand (0 without a noise table) and the number
- * of lone photons of the chain (the photons themselves: wfs_dark_count_photons).  *count: how many rows; more than capacity:
- * WFS_E_CAPACITY and nothing is written. */
+ * of lone photons of the chain (the photons themselves: wfs_dark_count_photons; noise-hit seeds are not counted here).  *count: how
+ * many rows; more than capacity: WFS_E_CAPACITY and nothing is written. */
 int wfs_copy_lone_rows(wfs_handle *h, int32_t *channel, int64_t *left, int64_t *right, int64_t *ix_rand, int32_t *n_photons, int64_t capacity, int64_t *count);
+/* Noise-hit seeds of the lone-hit passes (config 'noise_lone_hits').  Symbols as above.
+ *   value    v(ch, t) is the finished sample a row without a pulse would hold at absolute sample t: finish_value<NK>(d, D(ch, t), he =
+ *            false, noisy = ch < model channels, noise(ch, t)), D = 0 where no dark-count rate is set.  Defined for the drawn noise kinds
+ *            3, 4 and 5 alone: a noise table has no value at an absolute sample.
+ *   seed     a sample t of a PMT channel ch inside the noise model is a noise-hit seed when v(ch, t) < thr_zle[ch] -- the very comparison
+ *            the ZLE kernels make -- and t lies in no row of ch's TPC slot (under full readout every channel of a window has a row).
+ *            The seed's start is t itself, not t - before: a seed directly behind a row must start behind that row, or the clipping of
+ *            the range does not see the row.  A photon is lone when its whole pulse is clear of the rows; a seed needs only its own
+ *            sample to be clear.  What made the sample cross -- noise alone, the tail of a dark pulse that is not lone, both together --
+ *            does not matter.
+ *   rows     the seeds of a channel are its lone dark photons (the rule above, if rates are set) and its noise-hit seeds, merged by
+ *            start; from there on everything above applies without change: a maximal chain with consecutive starts at most G apart is
+ *            one row of range first start - tw .. last start + tlen - 1 + tw, clipped against the row in front, the row behind and
+ *            s_limit; content D finished like every row; ZLE, hold-off, even landing, 110-sample fragments, ownership by the first
+ *            seed's start in [s0, s1) and the look-back of G samples as before.  Two seeds on the two sides of a row of length len >= G
+ *            start at least len + 1 > G apart: a chain straddles no row.
+ * Every noise-hit seed is a hit of the row that holds it, so it lies inside exactly one stored interval of its channel.  A dark pulse
+ * that crosses the threshold contributes its crossing samples as seeds: the first start of a chain does not move, the last can move by
+ * up to tlen - 1 samples, so a row can be that much longer than under dark_count_lone_hits alone.  No HE rows, no sum-row entries, no
+ * truth.  A pass needs no dark-count rates then (noise only).  on != 0: WFS_E_STATE without a drawn noise model (wfs_set_noise_model)
+ * or with enable_noise off; wfs_set_noise_model(h, 0, ..) switches it off.  Default: off -- no kernel, no buffer, no record differs. */
+int wfs_set_lone_noise_hits(wfs_handle *h, int32_t on);
+/* The noise-hit seeds of every row of the last pass, in the row order of wfs_copy_lone_rows.  *count: how many rows; more than capacity:
+ * WFS_E_CAPACITY and nothing is written. */
+int wfs_copy_lone_row_noise_hits(wfs_handle *h, int32_t *n_noise_hits, int64_t capacity, int64_t *count);
 /* Which kernel made every primary (pulse set, channel) tile of the last wfs_run, indexed set * n_tpc + channel: 0 no photons or not
  * tile-generated, 1 photons and pulse in one workgroup (up to 2048 photons), 2 generation only + the pulse kernels, 3 k_s2_bright.
  * capacity: entries the buffer holds (>= n_run_sets * n_tpc). */

@@ -310,7 +310,7 @@ struct WfsScal {
     i64 n_empty_samples;    // finished int16 samples reserved for them.  scan of fr_len -> host
     // a pass of wfs_lone_hits counts in a block of its own (wfs_handle::lone_scal), never in the run's: these, n_itv_slots, n_records,
     // n_empty_samples and the key range mean there what they mean for a batch
-    i64 n_lone_photons;     // lone-photon candidates k_lone_scan appended (may exceed the list: the pass is repeated with room).  k_lone_scan -> host
+    i64 n_lone_seeds;       // seeds k_lone_scan and k_lone_noise_scan appended (may exceed the list: the pass is repeated with room).  the scans -> host
     i64 n_lone_rows;        // lone rows of the pass.  scan of the chain-start flags -> host
     i64 lone_error;         // 1: a lone row longer than LONE_MAX_ROW_LEN.  k_lone_rows -> host
     i64 reserved_[17];

@@ -167,14 +167,15 @@ struct wfs_handle {
     DevArr<i64> sum_lo, sum_hi, sum_off, sum_chunk_off; DevArr<i32> sum_len, sum_nchunk;
     // full readout (k_row_empty): finished samples reserved per row slot for a row without a pulse, their offsets, the list of those rows
     DevArr<i32> fr_len, empty_rows; DevArr<i64> fr_off;
-    // lone-hit rows (wfs_lone_hits, wfs_lone.h): a pass has buffers of its own for everything it writes -- counters, photon keys, rows,
+    // lone-hit rows (wfs_lone_hits, wfs_lone.h): a pass has buffers of its own for everything it writes -- counters, seed keys, rows,
     // intervals, finished samples, records -- so that the batch it follows, whose packers may still run, keeps every byte
     struct Lone {
         DevArr<WfsScal> scal; DevArr<u64> keys, keys2, rec_key, rec_key2; DevArr<u32> rec_val, rec_val2, rec_dest;
         DevArr<i64> win_l, win_r, row_of, itv_off, fin_off, itv_left, itv_right, rec_off, out_left, out_right, out_ixr;
-        DevArr<i32> win_g, flag, cap, flen, itv_n, row_nrec, out_channel, out_nph;
+        DevArr<i32> win_g, flag, cap, flen, itv_n, row_nrec, out_channel, out_nph, out_nnz;
         DevArr<int16_t> fin; DevArr<RowDesc> desc; DevArr<PackDesc> pdesc; DevBuf sort_tmp, records_ab[1];      // (one record arena: a pass returns when its records exist)
         i64 n_rows = 0, n_records = 0;      // of the last pass
+        bool noise_hits = false;            // wfs_set_lone_noise_hits: samples of the noise model that cross are seeds too
         DevBuf &records_buf() { return records_ab[0]; }
     } lone;
 
@@ -2902,6 +2903,7 @@ try {
     if (n_channels == 0) {
         HIPCHK(hipStreamSynchronize(h->stream));
         h->noise_moves(h->noise_state().model_cleared());
+        h->lone.noise_hits = false;         // (no model, no value at an absolute sample: wfs_set_lone_noise_hits)
         refresh_dev(h);
         return WFS_OK;
     }
@@ -3019,8 +3021,8 @@ try {
     return WFS_OK;
 } WFS_CATCH(h)
 
-// Lone-hit rows (wfs_lone.h, DESIGN 3f): one pass over the starts [s0, s1) against the rows of the last wfs_run, or against no rows
-// when none is finished.  Everything the pass writes is a buffer of wfs_handle::lone and a counter block of its own; of the run it
+// Lone-hit rows (wfs_lone.h, DESIGN 3f / 3g): one pass over the starts [s0, s1) against the rows of the last wfs_run, or against no rows
+// when none is finished.  The seeds: lone dark photons where rates are set, noise-hit seeds where wfs_set_lone_noise_hits is on.  Everything the pass writes is a buffer of wfs_handle::lone and a counter block of its own; of the run it
 // reads the rows' ranges alone.  The work goes to the main stream behind the batch's packers.
 static int lone_windows(wfs_handle *h, std::vector<i64> &wl, std::vector<i64> &wr, std::vector<i32> &wg)
 {
@@ -3040,13 +3042,18 @@ static int lone_windows(wfs_handle *h, std::vector<i64> &wl, std::vector<i64> &w
 int wfs_lone_hits(wfs_handle *h, int64_t s0, int64_t s1, int64_t s_limit, int64_t *n_records)
 try {
     if (!h) return WFS_E_INVALID;
-    if (!h->dark.set()) return h->fail(WFS_E_STATE, "wfs_lone_hits: no dark-count rates are set");
+    if (!h->dark.set() && !h->lone.noise_hits) return h->fail(WFS_E_STATE, "wfs_lone_hits: no dark-count rates are set");
     if (!h->tables_set) return h->fail(WFS_E_STATE, "wfs_lone_hits: tables not set");
     if (!n_records) return h->fail(WFS_E_INVALID, "wfs_lone_hits: null n_records");
     const WfsDev &d = h->dev;
     auto &L = h->lone;
+    const bool photons = h->dark.set(), noise_hits = L.noise_hits;
+    const int kind = d.enable_noise ? (int)noise_kind_of(d) : (int)NOISE_NONE;
+    if (noise_hits && kind < (int)NOISE_MODEL) return h->fail(WFS_E_STATE, "wfs_lone_hits: noise hits are on without a drawn noise model");
+    const int noise_ch = noise_hits ? std::min((int)d.noise_channels, (int)d.n_tpc) : 0;      // PMT channels inside the model
     std::string err;
     if (const int bad = lone_check(s0, s1, s_limit, h->dark.channels, d.tlen, d.tw, d.samples_before, err)) return h->fail(bad == 1 ? WFS_E_INVALID : WFS_E_CAPACITY, err);
+    if (noise_hits) if (const int bad = lone_noise_check(s0, s_limit, d.tlen, d.tw, err)) return h->fail(bad == 1 ? WFS_E_INVALID : WFS_E_CAPACITY, err);
     HIPCHK(hipSetDevice(h->device));
     L.n_rows = 0; L.n_records = 0; *n_records = 0;
     if (s1 == s0) return WFS_OK;
@@ -3059,9 +3066,11 @@ try {
     LoneArgs a{};
     a.s0 = s0; a.s1 = s1; a.s_limit = s_limit; a.a0 = s0 - lone_gap(d.tlen, d.tw);
     a.m0 = lone_first_cell(a.a0, d.samples_before); a.n_cells = lone_last_cell(s_limit, d.samples_before) - a.m0 + 1;
+    a.n_blocks = noise_hits ? lone_noise_blocks(a.a0, s_limit) : 0;
     a.n_win = (i64)wl.size(); a.win_l = L.win_l.p(); a.win_r = L.win_r.p(); a.win_g = L.win_g.p(); a.row_lo = h->row_lo.p(); a.row_hi = h->row_hi.p();
     a.scal = L.scal.p();
-    // the list: twice the expected photons of the scanned cells and room for a small pass; a pass that finds more is scanned again with room
+    // the list: twice the expected photons of the scanned cells and room for a small pass; a pass that finds more is scanned again with
+    // room (the number of noise hits cannot be had from the model cheaply: they come out of that room or out of the second scan)
     double expect = 0;
     for (int c = 0; c < h->dark.channels; c++) expect += (double)h->dark.thr[(size_t)c * DK_MAX] / 4294967296.0 * 1.2 * (double)a.n_cells;
     i64 cap = (i64)(2.0 * expect) + 4096;
@@ -3072,18 +3081,21 @@ try {
         HIPCHK(hipMemsetAsync(L.scal.p(), 0, sizeof(WfsScal), h->stream));
         const i64 nb = (a.n_cells + LONE_SCAN_CELLS - 1) / LONE_SCAN_CELLS;
         if (nb > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "wfs_lone_hits: lone hits: a pass of more than 2^39 cells per channel, split it");
-        TRY(launch(h, PLAIN(k_lone_scan), Shape(dim3((unsigned)nb, (unsigned)h->dark.channels), dim3(LONE_SCAN_CELLS)), d, a));
+        if (photons) TRY(launch(h, PLAIN(k_lone_scan), Shape(dim3((unsigned)nb, (unsigned)h->dark.channels), dim3(LONE_SCAN_CELLS)), d, a));
+        if (noise_hits && noise_ch > 0 && a.n_blocks > 0)
+            TRY(launch(h, K_LONE_NOISE_SCAN(kind - (int)NOISE_MODEL, photons), Shape(dim3((unsigned)((a.n_blocks + 3) / 4), (unsigned)noise_ch), dim3(256)), d, a));
         TRY(copy_async(h, &sc, L.scal.p(), 1, hipMemcpyDeviceToHost));
         HIPCHK(hipStreamSynchronize(h->stream));
-        if (sc.n_lone_photons <= cap) break;
-        if (attempt > 0) return h->fail(WFS_E_STATE, "wfs_lone_hits: internal: the photon list overflowed twice");
-        cap = sc.n_lone_photons;
+        if (sc.n_lone_seeds <= cap) break;
+        if (attempt > 0) return h->fail(WFS_E_STATE, "wfs_lone_hits: internal: the seed list overflowed twice");
+        cap = sc.n_lone_seeds;
     }
-    const i64 NK = a.n_keys = sc.n_lone_photons;
+    const i64 NK = a.n_keys = sc.n_lone_seeds;
     if (NK == 0) return WFS_OK;
-    if (NK > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "wfs_lone_hits: lone hits: more than 2^31 lone photons in one pass, split it");
-    {   // by (channel, start): rocPRIM's radix sort over the key bits in use
-        unsigned end_bit = LONE_KEY_SHIFT; while (end_bit < 64 && ((u64)h->dark.channels >> (end_bit - LONE_KEY_SHIFT)) != 0) end_bit++;
+    if (NK > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "wfs_lone_hits: lone hits: more than 2^31 seeds (lone photons and noise hits) in one pass, split it");
+    {   // by (channel, start, kind): rocPRIM's radix sort over the key bits in use
+        const u64 n_ch = (u64)std::max(h->dark.channels, noise_ch);
+        unsigned end_bit = LONE_KEY_SHIFT; while (end_bit < 64 && (n_ch >> (end_bit - LONE_KEY_SHIFT)) != 0) end_bit++;
         size_t bytes = 0;
         HIPCHK(rocprim::radix_sort_keys(nullptr, bytes, L.keys.p(), L.keys2.p(), (size_t)NK, 0u, end_bit, h->stream));
         TRY(ensure(h, L.sort_tmp, bytes));
@@ -3098,12 +3110,12 @@ try {
     TRY(scan(h, L.flen.p(), NK, L.fin_off, &WfsScal::n_empty_samples, L.scal.p()));
     TRY(copy_async(h, &sc, L.scal.p(), 1, hipMemcpyDeviceToHost));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (sc.lone_error) return h->fail(WFS_E_CAPACITY, "wfs_lone_hits: lone hits: a lone row of more than 2^19 samples (a chain of dark photons that long: lower the rate or s_limit)");
+    if (sc.lone_error) return h->fail(WFS_E_CAPACITY, "wfs_lone_hits: lone hits: a lone row of more than 2^19 samples (a chain of dark photons that long, or with noise hits on a baseline that stays across the threshold: lower the rate, the threshold or s_limit)");
     const i64 NR = sc.n_lone_rows;
     if (NR > LONE_MAX_ROWS) return h->fail(WFS_E_CAPACITY, "wfs_lone_hits: lone hits: more than 2^24 lone rows in one pass, split it");
     if (NR == 0) return WFS_OK;
     TRY(ensure(h, L.desc, (size_t)NR)); TRY(ensure(h, L.pdesc, (size_t)NR));
-    TRY(ensure(h, L.out_channel, (size_t)NR)); TRY(ensure(h, L.out_nph, (size_t)NR)); TRY(ensure(h, L.out_left, (size_t)NR)); TRY(ensure(h, L.out_right, (size_t)NR)); TRY(ensure(h, L.out_ixr, (size_t)NR));
+    TRY(ensure(h, L.out_channel, (size_t)NR)); TRY(ensure(h, L.out_nph, (size_t)NR)); TRY(ensure(h, L.out_nnz, (size_t)NR)); TRY(ensure(h, L.out_left, (size_t)NR)); TRY(ensure(h, L.out_right, (size_t)NR)); TRY(ensure(h, L.out_ixr, (size_t)NR));
     TRY(ensure(h, L.itv_left, (size_t)sc.n_itv_slots + 2)); TRY(ensure(h, L.itv_right, (size_t)sc.n_itv_slots + 2));
     TRY(ensure(h, L.itv_n, (size_t)NR)); TRY(ensure(h, L.row_nrec, (size_t)NR));
     TRY(ensure(h, L.fin, (size_t)sc.n_empty_samples + 8));
@@ -3114,15 +3126,14 @@ try {
         TRY(fg.flush());
     }
     a.row_of = L.row_of.p(); a.itv_off = L.itv_off.p(); a.fin_off = L.fin_off.p();
-    a.out_channel = L.out_channel.p(); a.out_nph = L.out_nph.p(); a.out_left = L.out_left.p(); a.out_right = L.out_right.p(); a.out_ixr = L.out_ixr.p();
+    a.out_channel = L.out_channel.p(); a.out_nph = L.out_nph.p(); a.out_nnz = L.out_nnz.p(); a.out_left = L.out_left.p(); a.out_right = L.out_right.p(); a.out_ixr = L.out_ixr.p();
     TRY(launch(h, PLAIN(k_lone_desc), per_thread(NK), d, a, L.desc.p()));
-    // from here on the row list goes the way of a batch's rows without a pulse: k_row_empty with dark counts on, the record scan, the
+    // from here on the row list goes the way of a batch's rows without a pulse: k_row_empty (dark counts on where rates are set), the record scan, the
     // keys and the sort by (time, channel), k_pack_desc, k_pack_res
     ZleArgs za{};
     za.n_active_rows = NR; za.desc = L.desc.p(); za.fin = L.fin.p(); za.itv_left = L.itv_left.p(); za.itv_right = L.itv_right.p();
     za.itv_n = L.itv_n.p(); za.row_nrec = L.row_nrec.p(); za.spr = WFS_SPR; za.key_base = L.scal.p(); za.pdesc = L.pdesc.p();
-    const int kind = d.enable_noise ? (int)noise_kind_of(d) : (int)NOISE_NONE;
-    TRY(launch(h, K_ROW_EMPTY(kind, true), per_wave(NR), d, za, (i64)0, NR));
+    TRY(launch(h, K_ROW_EMPTY(kind, photons), per_wave(NR), d, za, (i64)0, NR));
     TRY(scan(h, L.row_nrec.p(), NR, L.rec_off, &WfsScal::n_records, L.scal.p()));
     TRY(copy_async(h, &sc, L.scal.p(), 1, hipMemcpyDeviceToHost));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -3178,6 +3189,31 @@ try {
     auto &L = h->lone;
     TRY(copy_out(h, channel, L.out_channel.p(), (size_t)n)); TRY(copy_out(h, n_photons, L.out_nph.p(), (size_t)n));
     TRY(copy_out(h, left, L.out_left.p(), (size_t)n)); TRY(copy_out(h, right, L.out_right.p(), (size_t)n)); TRY(copy_out(h, ix_rand, L.out_ixr.p(), (size_t)n));
+    return WFS_OK;
+} WFS_CATCH(h)
+
+int wfs_copy_lone_row_noise_hits(wfs_handle *h, int32_t *n_noise_hits, int64_t capacity, int64_t *count)
+try {
+    if (!h || !count) return WFS_E_INVALID;
+    const i64 n = h->lone.n_rows;
+    *count = n;
+    if (capacity < n) return h->fail(WFS_E_CAPACITY, "wfs_copy_lone_row_noise_hits: " + std::to_string(n) + " lone rows, capacity " + std::to_string(capacity));
+    if (n == 0) return WFS_OK;
+    if (!n_noise_hits) return h->fail(WFS_E_INVALID, "wfs_copy_lone_row_noise_hits: null buffer");
+    HIPCHK(hipSetDevice(h->device));
+    TRY(copy_out(h, n_noise_hits, h->lone.out_nnz.p(), (size_t)n));
+    return WFS_OK;
+} WFS_CATCH(h)
+
+// Noise-hit seeds of the lone-hit passes (include/wfsim_amd.h).  The switch changes nothing a run lays out: no packer is waited for.
+int wfs_set_lone_noise_hits(wfs_handle *h, int32_t on)
+try {
+    if (!h) return WFS_E_INVALID;
+    if (on) {
+        if (!h->noise.set()) return h->fail(WFS_E_STATE, "wfs_set_lone_noise_hits: no drawn noise model is set (wfs_set_noise_model; a noise table has no value at an absolute sample)");
+        if (!h->cfg.enable_noise) return h->fail(WFS_E_STATE, "wfs_set_lone_noise_hits: enable_noise is off");
+    }
+    h->lone.noise_hits = on != 0;
     return WFS_OK;
 } WFS_CATCH(h)
 

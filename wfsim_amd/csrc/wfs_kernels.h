@@ -10,6 +10,7 @@
 //   intervals   = ZLE output per row, reserved slots; records = 244-byte strax raw_records
 #pragma once
 #include "wfs_device.h"
+#include "wfs_family.h"      // the family of a template kernel that is declared beside it (k_lone_noise_scan)
 #include <cstddef>
 
 #define I64_MAX 0x7fffffffffffffffLL
@@ -2591,24 +2592,24 @@ __global__ __launch_bounds__(256) void k_row_empty(WfsDev d, ZleArgs a, i64 firs
     zc.finish(d, a, lane, base, row_abs, len32, q.idx);
 }
 
-// ---- Lone-hit rows (wfs_lone_hits; the rule: wfs_lone.h): the dark photons outside the rows of the last run, read out in
-// rows of their own.  k_lone_scan finds them, the host sorts their keys by (channel, start), k_lone_rows / k_lone_desc form the chains
-// and describe their rows like rows without a pulse (RowDesc::src 2), and k_row_empty<NK, DK = 1>, k_rec_keys, k_pack_desc and
+// ---- Lone-hit rows (wfs_lone_hits; the rule: wfs_lone.h): what crosses a threshold outside the rows of the last run,
+// read out in rows of its own.  The seeds of a row are lone dark photons (k_lone_scan) and, with wfs_set_lone_noise_hits, samples of
+// the noise model that cross (k_lone_noise_scan); the host sorts their keys by (channel, start), k_lone_rows / k_lone_desc form the
+// chains and describe their rows like rows without a pulse (RowDesc::src 2), and k_row_empty<NK, DK>, k_rec_keys, k_pack_desc and
 // k_pack_res take that row list as they take a batch's: nothing of a finished sample or a record is defined a second time.
 struct LoneArgs {
-    i64 s0, s1, s_limit;         // the pass owns the rows whose first photon starts in [s0, s1); chains are followed up to s_limit
-    i64 a0;                      // s0 - G: first start the scan lists, origin of the photon keys
+    i64 s0, s1, s_limit;         // the pass owns the rows whose first seed starts in [s0, s1); chains are followed up to s_limit
+    i64 a0;                      // s0 - G: first start the scans list, origin of the seed keys
     i64 m0, n_cells;             // first cell and cells of a channel: those of the starts a0 .. s_limit - 1
+    i64 n_blocks;                // blocks of LONE_NOISE_BLOCK samples of a channel from a0 on that reach s_limit - 1 (k_lone_noise_scan)
     // the windows of the last run that hold a pulse, in time order: range of their widest row, group; rows of the run (k_tile_rows, k_rows_widen)
     i64 n_win; const i64 *win_l, *win_r; const i32 *win_g; const i64 *row_lo, *row_hi;
-    u64 *keys; i64 key_cap, n_keys;      // lone photons: channel << LONE_KEY_SHIFT | start - a0; n_keys: the sorted ones (k_lone_rows, k_lone_desc)
+    u64 *keys; i64 key_cap, n_keys;      // seeds: lone_key(channel, start - a0, kind); n_keys: the sorted ones (k_lone_rows, k_lone_desc)
     WfsScal *scal;               // the pass's own counter block
-    i32 *flag, *cap, *flen;      // [n_keys] 1 / interval slots / finished samples of the row whose first photon this is, else 0
+    i32 *flag, *cap, *flen;      // [n_keys] 1 / interval slots / finished samples of the row whose first seed this is, else 0
     const i64 *row_of, *itv_off, *fin_off;       // their scans
-    i32 *out_channel, *out_nph; i64 *out_left, *out_right, *out_ixr;      // [rows] the listing of wfs_copy_lone_rows
+    i32 *out_channel, *out_nph, *out_nnz; i64 *out_left, *out_right, *out_ixr;      // [rows] the listing of wfs_copy_lone_rows (out_nnz: wfs_copy_lone_row_noise_hits)
 };
-constexpr int LONE_KEY_SHIFT = 40;
-static_assert(LONE_MAX_SPAN <= ((int64_t)1 << LONE_KEY_SHIFT), "a start of a pass fits the low bits of its key");
 static_assert(LONE_SCAN_CELLS == 256, "k_lone_scan: a workgroup of 256 lanes, a cell each");
 
 // the last window that begins at or in front of sample t, or -1 (bisection: the windows are in time order)
@@ -2667,45 +2668,99 @@ __global__ __launch_bounds__(LONE_SCAN_CELLS) void k_lone_scan(WfsDev d, LoneArg
     for (int j = 0; j < DK_MAX; j++) { b[j] = ballot64(((lone >> j) & 1u) != 0); total += __popcll(b[j]); }
     if (total == 0) return;                                                  // wave-uniform
     i64 base = 0;
-    if (lane == 0) base = (i64)atomicAdd((u64 *)&a.scal->n_lone_photons, (u64)total);
+    if (lane == 0) base = (i64)atomicAdd((u64 *)&a.scal->n_lone_seeds, (u64)total);
     base = __shfl(base, 0, 64);
     const u64 lt = (1ull << lane) - 1ull;
 #pragma unroll
     for (int j = 0; j < DK_MAX; j++) {
         const i64 at = base + __popcll(b[j] & lt);
-        if (((lone >> j) & 1u) && at < a.key_cap) a.keys[at] = ((u64)(u32)ch << LONE_KEY_SHIFT) | (u64)(st[j] - a.a0);
+        if (((lone >> j) & 1u) && at < a.key_cap) a.keys[at] = lone_key(ch, st[j] - a.a0, LONE_KIND_PHOTON);
         base += __popcll(b[j]);
     }
 }
 
-// The chain that photon i of the sorted list begins, if it begins one this pass owns: photon i has no lone photon of its channel
-// within G in front of it and starts in [s0, s1); the chain runs on while the next photon of the channel starts at most G behind the
-// last (the list ends in front of s_limit).  Its range: lone_range, clipped by the one row that can lie within its margins on either
-// side.  A chain cannot straddle a row (lone_cannot_straddle): every row of the run holds a pulse or spans its window.
-struct LoneChain { bool owned; i32 ch, n; i64 left, right; };
+// The noise-hit seeds (wfs_set_lone_noise_hits): a wave per block of LONE_NOISE_BLOCK consecutive absolute samples of a
+// channel from a0 on, four samples per lane, over a grid of (four blocks, channel).  The value is made exactly as k_row_empty makes the
+// sample of a row without a pulse -- noise_four (every lane of the wave draws), dark_block when rates are set, finish_four -- and
+// compared with thr_zle[ch] as the ZLE kernels compare; nothing is stored.  Four ballots of the hit nibbles, and the wave without a
+// hit, almost all of them, is done.  Otherwise the hit lanes test their samples against the one row that can hold them, and the wave
+// appends its seeds to the list with one reservation, as k_lone_scan does.  No LDS, no scratch.  ch < min(noise_channels, n_tpc).
+template <int NK, bool DK>
+__global__ __launch_bounds__(256) void k_lone_noise_scan(WfsDev d, LoneArgs a)
+{
+    static_assert(NK >= 3, "a noise table has no value at an absolute sample");
+    static_assert(LONE_NOISE_BLOCK == 256, "a wave takes 256 samples, four per lane");
+    const i32 ch = (i32)blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const i64 blk = (i64)blockIdx.x * 4 + wave_in_block();
+    if (blk >= a.n_blocks) return;                                           // wave-uniform
+    const i64 tb = a.a0 + blk * LONE_NOISE_BLOCK;
+    Raw4<NK> s4;
+    s4.acc[0] = s4.acc[1] = s4.acc[2] = s4.acc[3] = 0;
+    noise_four<NK>(d, s4, noise_row_of<NK>(d, ch, true), ch, tb, 0u, lane);
+    if constexpr (DK) { const i32 dch = dark_channel_of(d, ch, false); if (dch >= 0) dark_block(d, dch, tb, lane, s4.acc); }      // (every lane of the wave is here)
+    const i64 thr = d.thr_zle[ch], t = tb + 4 * lane;
+    u32 nib = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) nib |= (t + j < a.s_limit && (i64)finish_four<NK>(d, s4, j, false, true) < thr) ? (1u << j) : 0u;
+    if ((ballot64((nib & 1u) != 0) | ballot64((nib & 2u) != 0) | ballot64((nib & 4u) != 0) | ballot64((nib & 8u) != 0)) == 0) return;      // wave-uniform
+    if (nib) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (!((nib >> j) & 1u)) continue;
+            const LoneRow q = lone_row_of(d, a, lone_window_at(a, t + j), ch);
+            if (!lone_seed_clear(t + j, q.has, q.l, q.r)) nib &= ~(1u << j);
+        }
+    }
+    u64 b[4]; i32 total = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) { b[j] = ballot64(((nib >> j) & 1u) != 0); total += __popcll(b[j]); }
+    if (total == 0) return;                                                  // wave-uniform
+    i64 base = 0;
+    if (lane == 0) base = (i64)atomicAdd((u64 *)&a.scal->n_lone_seeds, (u64)total);
+    base = __shfl(base, 0, 64);
+    const u64 lt = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const i64 at = base + __popcll(b[j] & lt);
+        if (((nib >> j) & 1u) && at < a.key_cap) a.keys[at] = lone_key(ch, t + j - a.a0, LONE_KIND_NOISE);
+        base += __popcll(b[j]);
+    }
+}
+
+// Its family (wfs_family.h), declared beside the kernel: the axes are nk - 3, the drawn noise kinds alone, and dk, dev.dk_thr -- dark-count
+// rates are set and D is part of the value.  No dynamic LDS, hence no cap.
+const auto K_LONE_NOISE_SCAN = family<3, 2>("k_lone_noise_scan", 0, [](auto nk, auto dk) { return &k_lone_noise_scan<nk() + 3, dk() != 0>; });
+
+// The chain that seed i of the sorted list begins, if it begins one this pass owns: seed i has no seed of its channel within G in
+// front of it and starts in [s0, s1); the chain runs on while the next seed of the channel starts at most G behind the last (the list
+// ends in front of s_limit).  Its range: lone_range, clipped by the one row that can lie within its margins on either side.  A chain
+// cannot straddle a row (lone_cannot_straddle, lone_seeds_cannot_straddle): every row of the run holds a pulse or spans its window.
+// n: the lone dark photons among the chain's seeds, nn: the noise-hit seeds.
+struct LoneChain { bool owned; i32 ch, n, nn; i64 left, right; };
 __device__ __forceinline__ LoneChain lone_chain_of(const WfsDev &d, const LoneArgs &a, i64 i)
 {
-    const u64 lowmask = (1ull << LONE_KEY_SHIFT) - 1ull;
     const i64 G = lone_gap(d.tlen, d.tw);
     const u64 key = a.keys[i];
-    LoneChain c{false, (i32)(key >> LONE_KEY_SHIFT), 0, 0, 0};
-    const i64 first = a.a0 + (i64)(key & lowmask);
+    LoneChain c{false, lone_key_channel(key), 0, 0, 0, 0};
+    const i64 first = a.a0 + lone_key_rel(key);
     if (first < a.s0 || first >= a.s1) return c;
-    if (i > 0) { const u64 pk = a.keys[i - 1]; if ((i32)(pk >> LONE_KEY_SHIFT) == c.ch && first - (a.a0 + (i64)(pk & lowmask)) <= G) return c; }
+    if (i > 0) { const u64 pk = a.keys[i - 1]; if (lone_key_channel(pk) == c.ch && first - (a.a0 + lone_key_rel(pk)) <= G) return c; }
     i64 last = first, j = i + 1;
+    i32 nn = lone_key_kind(key) == LONE_KIND_NOISE ? 1 : 0;
     for (; j < a.n_keys; j++) {
         const u64 nk = a.keys[j];
-        const i64 s = a.a0 + (i64)(nk & lowmask);
-        if ((i32)(nk >> LONE_KEY_SHIFT) != c.ch || s - last > G) break;
-        last = s;
+        const i64 s = a.a0 + lone_key_rel(nk);
+        if (lone_key_channel(nk) != c.ch || s - last > G) break;
+        last = s; nn += lone_key_kind(nk) == LONE_KIND_NOISE ? 1 : 0;
     }
     const LoneRow pr = lone_row_of(d, a, lone_window_at(a, first - 1), c.ch);
     const LoneRow nr = lone_row_of(d, a, lone_window_at(a, last + d.tlen - 1 + d.tw), c.ch);
     const LoneRange rg = lone_range(first, last, d.tlen, d.tw, (pr.has && pr.r < first) ? pr.r : I64_MIN, (nr.has && nr.l > last) ? nr.l : I64_MAX, a.s_limit);
-    c.owned = true; c.n = (i32)(j - i); c.left = rg.left; c.right = rg.right;
+    c.owned = true; c.n = (i32)(j - i) - nn; c.nn = nn; c.left = rg.left; c.right = rg.right;
     return c;
 }
-// thread per listed photon: the flag of a row's first photon, the interval slots and the finished samples its row reserves
+// thread per listed seed: the flag of a row's first seed, the interval slots and the finished samples its row reserves
 __global__ void k_lone_rows(WfsDev d, LoneArgs a)
 {
     const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2717,7 +2772,7 @@ __global__ void k_lone_rows(WfsDev d, LoneArgs a)
     a.cap[i] = len > 0 ? (i32)zle_slots(len, zle_holdoff(d.tw)) : 0;
     a.flen[i] = len > 0 ? fin_padded_len((i32)len) : 0;
 }
-// thread per listed photon, behind the scans: the descriptor of its row (as k_row_desc writes one for a row without a pulse) and the listing
+// thread per listed seed, behind the scans: the descriptor of its row (as k_row_desc writes one for a row without a pulse) and the listing
 __global__ void k_lone_desc(WfsDev d, LoneArgs a, RowDesc *desc)
 {
     const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2731,7 +2786,7 @@ __global__ void k_lone_desc(WfsDev d, LoneArgs a, RowDesc *desc)
     q.thr = d.thr_zle[c.ch]; q.idx = row; q.len = (i32)(c.right - c.left + 1); q.channel = c.ch; q.he = 0; q.src = 2;
     desc[row] = q;
     atomicMin(&a.scal->key_origin, q.row_abs); atomicMax(&a.scal->key_end, q.row_abs + (i64)q.len);
-    a.out_channel[row] = c.ch; a.out_nph[row] = c.n; a.out_left[row] = c.left; a.out_right[row] = c.right; a.out_ixr[row] = q.ixr;
+    a.out_channel[row] = c.ch; a.out_nph[row] = c.n; a.out_nnz[row] = c.nn; a.out_left[row] = c.left; a.out_right[row] = c.right; a.out_ixr[row] = q.ixr;
 }
 
 // Records ordered by (time, channel) as strax.sort_by_time leaves them (strax_interface.py:453): one key per record; the

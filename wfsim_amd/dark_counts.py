@@ -107,6 +107,29 @@ def lone_hits_from(config, params=None):
     if params is None:
         from .config import kernel_params
         params = kernel_params(config)
+    _lone_window_bounds('dark_count_lone_hits', params)
+    return True
+
+
+def noise_lone_hits_from(config, params=None):
+    """True when config['noise_lone_hits'] asks for the noise-hit seeds of the lone-hit rows; raises ValueError when it
+    does and they cannot be had: without config['noise_model'] (a drawn model: a noise table has no value at an absolute sample), with
+    enable_noise off, or below the right_raw_extension bound of the lone-hit passes.  Independent of 'dark_count_lone_hits'."""
+    if not config.get('noise_lone_hits', False):
+        return False
+    if config.get('noise_model') is None:
+        raise ValueError("noise_lone_hits: needs config['noise_model'] (a noise table has no value between the rows)")
+    if not config.get('enable_noise', True):
+        raise ValueError('noise_lone_hits: enable_noise is off')
+    if params is None:
+        from .config import kernel_params
+        params = kernel_params(config)
+    _lone_window_bounds('noise_lone_hits', params)
+    return True
+
+
+def _lone_window_bounds(key, params):
+    """the bounds a lone-hit pass of RawData puts on the configuration; key: the config key that asks for the pass"""
     # A new window begins where a cluster's first time lies more than right_raw_extension (rext) behind the end of the last pulse,
     # (a_hi - tw) dt for rows that end at sample a_hi.  A pulse begins `before` + samples_to_store_before samples ahead of its first
     # photon, a row tw ahead of that, and a window's left may go one sample down to an even one: the next window's rows begin at
@@ -119,10 +142,9 @@ def lone_hits_from(config, params=None):
     #    pass G samples behind the batch's last window without knowing the next.
     # 64, a cell, is the slack that pays for `before` and samples_to_store_before.
     if int(params['samples_before']) + int(params['store_before']) + 2 >= CELL:
-        raise ValueError('dark_count_lone_hits: samples_to_store_before + samples_before_pulse_center + 2 must stay below 64 '
+        raise ValueError(f'{key}: samples_to_store_before + samples_before_pulse_center + 2 must stay below 64 '
                          '(the bound on right_raw_extension assumes it)')
     need = lone_min_rext(params)
     if int(params['rext']) < need:
-        raise ValueError(f"dark_count_lone_hits: right_raw_extension {int(params['rext'])} ns below (2 G + 64) dt = {need} ns "
+        raise ValueError(f"{key}: right_raw_extension {int(params['rext'])} ns below (2 G + 64) dt = {need} ns "
                          f"(G = tlen + 2 trigger_window = {lone_gap(params)} samples)")
-    return True

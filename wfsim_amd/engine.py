@@ -257,8 +257,14 @@ class Engine:
         if rates is not None:
             self.set_dark_counts(rates)
         # lone-hit rows (config 'dark_count_lone_hits'): RawData runs a pass of lone_hits behind every batch
-        from .dark_counts import lone_hits_from
+        from .dark_counts import lone_hits_from, noise_lone_hits_from
         self.lone_hits_on = lone_hits_from(self.config, self.params)
+        # ... and the samples of the noise model that cross their threshold there (config 'noise_lone_hits'): either key
+        # makes RawData run the pass
+        self.noise_lone_hits = False
+        if noise_lone_hits_from(self.config, self.params):
+            self.set_lone_noise_hits(True)
+            self.lone_hits_on = True
 
     def _init_pattern_maps(self, resource):
         # pattern maps on regular grids are evaluated on the device (one channel CDF row per instruction)
@@ -683,6 +689,7 @@ class Engine:
         if pmf is None:
             self._call('wfs_set_noise_model', 0, 0, 0, None)
             self._noise_rows = None
+            self.noise_lone_hits = False        # (the library switches the noise-hit seeds off with the model)
             return
         pmf = _arr(pmf, np.float64)
         if pmf.ndim != 2:
@@ -792,9 +799,10 @@ class Engine:
         return thr
 
     def lone_hits(self, s0, s1, s_limit=None):
-        """raw_records of the lone-hit rows (wfs_lone_hits) whose first dark photon starts at an absolute sample in [s0, s1),
-        in (time, channel) order: the dark photons outside the rows of the last ``run()`` (outside every row when there was none).
-        A chain of photons is followed beyond s1 but no further than ``s_limit`` (default: s1).  Needs dark-count rates."""
+        """raw_records of the lone-hit rows (wfs_lone_hits) whose first seed starts at an absolute sample in [s0, s1),
+        in (time, channel) order.  The seeds are the dark photons outside the rows of the last ``run()`` (outside every row when there
+        was none) and, with ``set_lone_noise_hits(True)``, the samples of the noise model that cross their threshold there.  A chain of
+        seeds is followed beyond s1 but no further than ``s_limit`` (default: s1).  Needs dark-count rates or the noise-hit seeds."""
         n = np.zeros(1, dtype=np.int64)
         self._call('wfs_lone_hits', int(s0), int(s1), int(s1 if s_limit is None else s_limit), n)
         out = np.zeros(int(n[0]), dtype=raw_record_dtype())
@@ -804,7 +812,8 @@ class Engine:
 
     def lone_hit_rows(self):
         """the rows of the last ``lone_hits`` pass in (channel, time) order: a structured array (channel, left, right, ix_rand,
-        n_photons) -- first and last absolute sample, the noise-table offset (0 without a table), the lone photons of the chain"""
+        n_photons) -- first and last absolute sample, the noise-table offset (0 without a table), the lone dark photons of the chain
+        (its noise-hit seeds: ``lone_hit_noise_seeds``)"""
         k = np.zeros(1, dtype=np.int64)
         self._call('wfs_copy_lone_rows', None, None, None, None, None, 0, k, check=False)
         n = int(k[0])
@@ -814,6 +823,23 @@ class Engine:
             self._call('wfs_copy_lone_rows', ch, left, right, ixr, nph, n, k)
         out = np.zeros(n, dtype=[('channel', np.int32), ('left', np.int64), ('right', np.int64), ('ix_rand', np.int64), ('n_photons', np.int32)])
         out['channel'], out['left'], out['right'], out['ix_rand'], out['n_photons'] = ch, left, right, ixr, nph
+        return out
+
+    def set_lone_noise_hits(self, on):
+        """config 'noise_lone_hits' between passes (wfs_set_lone_noise_hits): from the next ``lone_hits`` on, every sample of
+        a PMT channel inside the noise model whose finished value -- noise, dark counts where rates are set, baseline, clamp -- lies
+        below the channel's ZLE threshold, and which lies in no row of the channel, is a seed of a lone-hit row, as a lone dark photon
+        is one.  Needs a drawn noise model and enable_noise; clearing the model switches it off."""
+        self._call('wfs_set_lone_noise_hits', bool(on))
+        self.noise_lone_hits = bool(on)
+
+    def lone_hit_noise_seeds(self):
+        """the noise-hit seeds of every row of the last ``lone_hits`` pass, int32 in the row order of ``lone_hit_rows``"""
+        k = np.zeros(1, dtype=np.int64)
+        self._call('wfs_copy_lone_row_noise_hits', None, 0, k, check=False)
+        out = np.zeros(int(k[0]), dtype=np.int32)
+        if len(out):
+            self._call('wfs_copy_lone_row_noise_hits', out, len(out), k)
         return out
 
     def noise_model_cells(self, channel):

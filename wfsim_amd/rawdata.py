@@ -138,7 +138,7 @@ class RawData:
     def iter_windows(self, instructions, truth_buffer=None, **kwargs):
         """Yields dict(left, right, records) per digitise window, in time order.  ``records`` are packed strax
         raw_records in the order the reference yields pulses (channel ascending, interval ascending).  With
-        config['dark_count_lone_hits'] the lone-hit rows come between the windows, in time order, as entries
+        config['dark_count_lone_hits'] or config['noise_lone_hits'] the lone-hit rows come between the windows, in time order, as entries
         dict(left, right, records, lone=True): one per stretch of lone rows that overlap in time, records by (time, channel)."""
         if truth_buffer is None:
             truth_buffer = []
@@ -178,7 +178,7 @@ class RawData:
     def iter_batches(self, instructions, want_truth=False, record_sink=None, device_records=False, **kwargs):
         """The same stream batch by batch (what the chunker consumes): dict(left[], right[] of the batch's digitise windows
         in time order, first[] record offsets (one more than windows), records, truth_table + truth_rows + truth_before (row truth_rows[k] of the table belongs in
-        front of window truth_before[k]; == number of windows: after the last), finished; with config['dark_count_lone_hits'] also
+        front of window truth_before[k]; == number of windows: after the last), finished; with config['dark_count_lone_hits'] or config['noise_lone_hits'] also
         lone_records, the lone-hit rows up to the end of the batch's last window, by (time, channel)).  ``record_sink(n, first_left)`` may hand out
         the array the records are copied into (device -> host without a staging copy); ``device_records``: the records stay
         on the GPU (``records`` is a torch uint8 tensor of n * 244 bytes)."""
@@ -263,7 +263,7 @@ class RawData:
                 batch = dict(left=groups['left'][keep], right=groups['right'][keep],
                              first=np.append(first[keep], first[n_emit]) if len(keep) else np.array([first[n_emit]]),
                              records=records, truth_table=truth_table, truth_rows=truth_rows, truth_before=truth_before, finished=L['b'] >= n)
-                if L.get('lone_records') is not None:       # config['dark_count_lone_hits']: the pass behind this batch's run (_launch)
+                if L.get('lone_records') is not None:       # config['dark_count_lone_hits'] / ['noise_lone_hits']: the pass behind this batch's run (_launch)
                     batch['lone_records'] = L['lone_records']
                 # everything else of this batch is on the host now: the engine is free for the next one (it keeps the records of
                 # two batches: this batch's copy overlaps the next batch's kernels)
@@ -341,7 +341,7 @@ class RawData:
     lone_pass_samples = 1 << 28
 
     def _lone_pass(self, st, groups, keep, nonempty, n_emit, finished):
-        """The lone-hit pass of a batch: from the end of the previous pass to G samples behind dg_right of the batch's last
+        """The lone-hit pass of a batch (with config['noise_lone_hits'] it takes the noise-hit seeds of 3g too): from the end of the previous pass to G samples behind dg_right of the batch's last
         emitted window; the first pass begins at config['lone_hits_begin'] (ns; default: the first window's left minus
         right_raw_extension), the last one ends at config['lone_hits_end'] (default: the last window's right plus
         right_raw_extension).  s_limit: the left of the next window where the run knows it, else G + 64 samples short of dg_right + 1 +

@@ -181,7 +181,7 @@ class ChunkRawRecords(object):
                     return spare[:n]
             return self.record_buffer[self.blevel:self.blevel + n] if self.blevel + n <= L else None
 
-        # lone-hit rows (config 'dark_count_lone_hits'): a batch's lone records are merged with its window records by time on
+        # lone-hit rows (config 'dark_count_lone_hits' or 'noise_lone_hits'): a batch's lone records are merged with its window records by time on
         # the host, so a batch does not arrive where it stays and the sink is not offered
         lone_on = bool(getattr(getattr(rd, 'engine', None), 'lone_hits_on', False))
         if lone_on and self.config.get('lone_hits_begin') is None:
@@ -748,6 +748,10 @@ class RawRecordsFromMcChain(SimulatorPlugin):
             # PMT dark counts: 'dark_count_rate' is the TPC engine's (one value per TPC PMT); the veto engine reads
             # 'dark_count_rate_nveto' (or a 'dark_count_rate' inside fax_config_nveto) and has none otherwise
             cn['dark_count_rate'] = cn.pop('dark_count_rate_nveto', None)
+            # ... and 'noise_lone_hits_nveto' as its 'noise_lone_hits' (DESIGN 3g): the TPC's key is not the veto's
+            cn.pop('noise_lone_hits', None)
+            if cn.pop('noise_lone_hits_nveto', False):
+                cn['noise_lone_hits'] = True
             cn.update(self.config.get('fax_config_nveto') or {})
             if cn.get('dark_count_rate') is None:       # 'dark_count_lone_hits'  reaches the veto engine with veto rates alone
                 cn.pop('dark_count_lone_hits', None)
