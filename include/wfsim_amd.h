@@ -530,6 +530,26 @@ int wfs_set_lone_noise_hits(wfs_handle *h, int32_t on);
 /* The noise-hit seeds of every row of the last pass, in the row order of wfs_copy_lone_rows.  *count: how many rows; more than capacity:
  * WFS_E_CAPACITY and nothing is written. */
 int wfs_copy_lone_row_noise_hits(wfs_handle *h, int32_t *n_noise_hits, int64_t capacity, int64_t *count);
+/* The overlay pass (config 'overlay_records'): two streams of 244-byte raw_records merged per channel into one valid stream.
+ *   A        the simulation's stream: sim_host[n_sim], or with sim_host = NULL the records of the last wfs_run where the device holds
+ *            them (WFS_E_STATE before a run has completed; the batch's own records keep every byte) -- all of them with n_sim < 0,
+ *            else the first n_sim in the order of wfs_copy_records (the windows of a batch that its caller emits are a prefix).
+ *   B        the recorded background: bg_host[n_bg].
+ *   pulse    the fragments record_i = 0 .. k of one (channel, time0); it covers the samples time0 / dt .. time0 / dt + pulse_length - 1.
+ *   valid    dt == cfg.dt, time % dt == 0, 1 <= length <= 110, 0 <= channel < n_rows; the fragments of every pulse complete, 110 dt
+ *            apart, with the lengths of their place; no two pulses of ONE stream share a sample on a channel.  Otherwise WFS_E_INVALID
+ *            with a message that names the first offending record, and nothing of it is read out of range.
+ *   merging  per channel, pulses of A and B that share a sample become one pulse, transitively; pulses that only touch stay apart.
+ *   sample   covered by B alone: b; by A alone: clamp(a - cfg.baseline + base[ch]); by both: clamp(b + a - cfg.baseline), clamped to
+ *            0 .. 32767.  base = bg_baseline, int32[n_rows], the recorded baseline per channel; NULL: cfg.baseline everywhere.
+ *   output   fragments of 110 samples again, samples behind length 0, baseline 0, ordered by (time, channel).  B empty (and base NULL)
+ *            gives A sorted, A empty gives B sorted, byte for byte.
+ * The pass has buffers of its own, allocated by its first call, and runs behind the packers of the last run.  WFS_E_CAPACITY, with a
+ * message that names the overlay: more than 2^31 records in or out, a merged pulse beyond 2^31 - 1 samples, or a span of samples that
+ * does not fit the sort keys beside the channel and the stream (63 bits in all).  *n_records: the records of the merged stream. */
+int wfs_overlay_records(wfs_handle *h, const void *sim_host, int64_t n_sim, const void *bg_host, int64_t n_bg, const int32_t *bg_baseline, int64_t *n_records);
+/* The records of the last pass; dst is a host or a device pointer. */
+int wfs_copy_overlay_records(wfs_handle *h, void *dst, int64_t capacity_records);
 /* Which kernel made every primary (pulse set, channel) tile of the last wfs_run, indexed set * n_tpc + channel: 0 no photons or not
  * tile-generated, 1 photons and pulse in one workgroup (up to 2048 photons), 2 generation only + the pulse kernels, 3 k_s2_bright.
  * capacity: entries the buffer holds (>= n_run_sets * n_tpc). */

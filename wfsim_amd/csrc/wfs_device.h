@@ -14,6 +14,7 @@
 #include "wfs_layout.h"      // the sizes the LDS layouts are made of (WFS_DT, WFS_MAX_CH, SPE_ROW_LEN, ..), floordiv, the window rules
 #include "wfs_rows.h"        // the rules of the back end of a row: ZLE intervals, records, the noise index, the finished sample
 #include "wfs_lone.h"        // lone-hit rows: the rule, the site of a row's noise offset, the limits of a pass
+#include "wfs_overlay.h"     // the overlay pass: validity of a record stream, its keys, merging, the sample of a merged pulse
 
 typedef long long i64;
 typedef unsigned long long u64;

@@ -4,6 +4,7 @@
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 #include "wfs_kernels.h"
 #include "wfs_tilegen.h"
 #include "wfs_boundary.h"
@@ -178,6 +179,13 @@ struct wfs_handle {
         bool noise_hits = false;            // wfs_set_lone_noise_hits: samples of the noise model that cross are seeds too
         DevBuf &records_buf() { return records_ab[0]; }
     } lone;
+    // the overlay pass (wfs_overlay_records, wfs_overlay.h): buffers of its own for everything it writes, allocated by its first call
+    struct Overlay {
+        DevArr<OverlayScal> scal; DevArr<u32> src_a, src_b, val, val2, plen, plen2, oval, oval2, out;
+        DevArr<u64> key, key2, pkey, pkey2, ekey, run_max, m_first, m_last, okey, okey2;
+        DevArr<i32> base, flag, pulse_of, head, merged_of; DevArr<i64> m_nrec, rec_end; DevBuf sort_tmp;
+        i64 n_records = 0;                  // of the last pass
+    } overlay;
 
     // what is not a device buffer; the buffers, and the members that hold some, free themselves after this body
     ~wfs_handle()
@@ -3202,6 +3210,151 @@ try {
     if (!n_noise_hits) return h->fail(WFS_E_INVALID, "wfs_copy_lone_row_noise_hits: null buffer");
     HIPCHK(hipSetDevice(h->device));
     TRY(copy_out(h, n_noise_hits, h->lone.out_nnz.p(), (size_t)n));
+    return WFS_OK;
+} WFS_CATCH(h)
+
+// The overlay pass (wfs_overlay.h): the records of two streams merged per channel into one valid stream in (time, channel)
+// order.  A: sim_host, or the records of the last wfs_run where they lie; B: bg_host.  Everything the pass writes is a buffer of
+// wfs_handle::overlay; of the run it reads the record arena alone.  The work goes to the main stream behind the batch's packers.
+extern "C++" {
+template <class K, class V> static int overlay_sort(wfs_handle *h, K *k_in, K *k_out, V *v_in, V *v_out, i64 n, int bits)
+{
+    size_t bytes = 0;
+    HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, k_in, k_out, v_in, v_out, (size_t)n, 0u, (unsigned)bits, h->stream));
+    TRY(ensure(h, h->overlay.sort_tmp, bytes));
+    HIPCHK(rocprim::radix_sort_pairs(h->overlay.sort_tmp.p, bytes, k_in, k_out, v_in, v_out, (size_t)n, 0u, (unsigned)bits, h->stream));
+    return WFS_OK;
+}
+template <class T, class Op> static int overlay_scan(wfs_handle *h, const T *in, T *out, i64 n, Op op)
+{
+    size_t bytes = 0;
+    HIPCHK(rocprim::inclusive_scan(nullptr, bytes, in, out, (size_t)n, op, h->stream));
+    TRY(ensure(h, h->overlay.sort_tmp, bytes));
+    HIPCHK(rocprim::inclusive_scan(h->overlay.sort_tmp.p, bytes, in, out, (size_t)n, op, h->stream));
+    return WFS_OK;
+}
+// the last element of an inclusive scan over n > 0 elements: its total (a blocking read behind the stream)
+template <class T> static int overlay_total(wfs_handle *h, const T *scanned, i64 n, T *total)
+{
+    TRY(copy_async(h, total, scanned + (n - 1), 1, hipMemcpyDeviceToHost));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return WFS_OK;
+}
+}  // extern "C++"
+
+int wfs_overlay_records(wfs_handle *h, const void *sim_host, int64_t n_sim, const void *bg_host, int64_t n_bg, const int32_t *bg_baseline, int64_t *n_records)
+try {
+    if (!h) return WFS_E_INVALID;
+    if (!n_records) return h->fail(WFS_E_INVALID, "wfs_overlay_records: null n_records");
+    if (n_bg < 0 || (n_bg > 0 && !bg_host)) return h->fail(WFS_E_INVALID, "wfs_overlay_records: n_bg is negative or bg_host is null");
+    if (sim_host && n_sim < 0) return h->fail(WFS_E_INVALID, "wfs_overlay_records: n_sim is negative");
+    if (!sim_host && !run_finished(h)) return h->fail(WFS_E_STATE, "wfs_overlay_records: no simulated records: wfs_run has not completed and sim_host is null");
+    const WfsDev &d = h->dev;
+    auto &O = h->overlay;
+    if (!sim_host && n_sim > h->run.n_records) return h->fail(WFS_E_INVALID, "wfs_overlay_records: n_sim beyond the records of the last run");
+    const i64 NA = sim_host ? n_sim : (n_sim < 0 ? h->run.n_records : n_sim), N = NA + n_bg;
+    O.n_records = 0; *n_records = 0;
+    if (NA > 0x7fffffffLL || n_bg > 0x7fffffffLL || N > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "wfs_overlay_records: overlay: more than 2^31 records in one pass, split it");
+    if (N == 0) return WFS_OK;
+    HIPCHK(hipSetDevice(h->device));
+    if (h->pack.must_wait()) HIPCHK(hipStreamWaitEvent(h->stream, h->rec_ready[h->pack.arena], 0));      // behind the batch's packers (the fence state stays as it is)
+    OverlayArgs a{};
+    a.n_a = NA; a.n = N; a.dt = (i32)d.dt; a.n_rows = (i32)h->cfg.n_rows; a.baseline = (i32)d.baseline;
+    if (sim_host) { TRY(upload(h, O.src_a, (const u32 *)sim_host, (size_t)NA * REC_DWORDS)); a.src_a = O.src_a.p(); }
+    else a.src_a = (const u32 *)h->records_buf().p;
+    TRY(upload(h, O.src_b, (const u32 *)bg_host, (size_t)n_bg * REC_DWORDS)); a.src_b = O.src_b.p();
+    {
+        std::vector<i32> base((size_t)a.n_rows, a.baseline);
+        if (bg_baseline) base.assign(bg_baseline, bg_baseline + a.n_rows);
+        TRY(upload(h, O.base, base.data(), base.size()));
+        HIPCHK(hipStreamSynchronize(h->stream));            // (base is a local)
+        a.base = O.base.p();
+    }
+    TRY(ensure(h, O.scal, 1));
+    a.scal = O.scal.p();
+    OverlayScal sc{}; sc.smin = I64_MAX; sc.smax = I64_MIN; sc.first_bad = ~0ull;
+    TRY(copy_async(h, O.scal.p(), &sc, 1, hipMemcpyHostToDevice));
+    HIPCHK(hipStreamSynchronize(h->stream));                // (sc is written below)
+    auto invalid = [&](const OverlayScal &s) {
+        const i64 i = (i64)(s.first_bad >> 8);
+        return h->fail(WFS_E_INVALID, std::string("wfs_overlay_records: ") + (i < NA ? "simulated record " + std::to_string(i) : "background record " + std::to_string(i - NA)) + ": " +
+                       ov_bad_name((int)(s.first_bad & 0xffu)) + " (" + std::to_string(s.n_bad) + " records in all)");
+    };
+    TRY(launch(h, PLAIN(k_ov_check), per_thread(N), a));
+    TRY(copy_async(h, &sc, O.scal.p(), 1, hipMemcpyDeviceToHost));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (sc.n_bad) return invalid(sc);
+    a.smin = sc.smin;
+    a.bits.sbits = ov_bits_of((u64)sc.smax - (u64)sc.smin + 1ull); a.bits.chbits = ov_bits_of((u64)std::max(a.n_rows - 1, 1));
+    if (!ov_bits_fit(a.bits)) return h->fail(WFS_E_CAPACITY, "wfs_overlay_records: overlay: the records span more samples than the sort keys hold beside the channel (2^" + std::to_string(63 - a.bits.chbits) + "), split the pass");
+    const int key_bits = a.bits.sbits + a.bits.chbits + 1;
+    // the records by (stream, channel, time)
+    TRY(ensure(h, O.key, (size_t)N)); TRY(ensure(h, O.key2, (size_t)N)); TRY(ensure(h, O.val, (size_t)N)); TRY(ensure(h, O.val2, (size_t)N));
+    TRY(ensure(h, O.flag, (size_t)N)); TRY(ensure(h, O.pulse_of, (size_t)N));
+    a.key = O.key.p(); a.val = O.val.p();
+    TRY(launch(h, PLAIN(k_ov_keys), per_thread(N), a));
+    TRY(overlay_sort(h, O.key.p(), O.key2.p(), O.val.p(), O.val2.p(), N, key_bits));
+    a.key = O.key2.p(); a.val = O.val2.p(); a.flag = O.flag.p();
+    TRY(launch(h, PLAIN(k_ov_valid), per_thread(N), a));
+    TRY(overlay_scan(h, O.flag.p(), O.pulse_of.p(), N, rocprim::plus<i32>()));
+    a.pulse_of = O.pulse_of.p();
+    i32 n_pulses = 0;
+    TRY(copy_async(h, &sc, O.scal.p(), 1, hipMemcpyDeviceToHost));
+    TRY(overlay_total(h, O.pulse_of.p(), N, &n_pulses));
+    if (sc.n_bad) return invalid(sc);
+    const i64 P = a.n_pulses = n_pulses;
+    if (P <= 0) return h->fail(WFS_E_STATE, "wfs_overlay_records: internal: valid records without a pulse");
+    // the pulses by (channel, start, stream); merged pulses from the running maximum of their ends
+    TRY(ensure(h, O.pkey, (size_t)P)); TRY(ensure(h, O.pkey2, (size_t)P)); TRY(ensure(h, O.plen, (size_t)P)); TRY(ensure(h, O.plen2, (size_t)P));
+    TRY(ensure(h, O.ekey, (size_t)P)); TRY(ensure(h, O.run_max, (size_t)P)); TRY(ensure(h, O.head, (size_t)P)); TRY(ensure(h, O.merged_of, (size_t)P));
+    a.pkey = O.pkey.p(); a.plen = O.plen.p();
+    TRY(launch(h, PLAIN(k_ov_pulses), per_thread(N), a));
+    TRY(overlay_sort(h, O.pkey.p(), O.pkey2.p(), O.plen.p(), O.plen2.p(), P, key_bits));
+    a.pkey = O.pkey2.p(); a.plen = O.plen2.p(); a.ekey = O.ekey.p();
+    TRY(launch(h, PLAIN(k_ov_ends), per_thread(P), a));
+    TRY(overlay_scan(h, O.ekey.p(), O.run_max.p(), P, rocprim::maximum<u64>()));
+    a.run_max = O.run_max.p(); a.head = O.head.p();
+    TRY(launch(h, PLAIN(k_ov_heads), per_thread(P), a));
+    TRY(overlay_scan(h, O.head.p(), O.merged_of.p(), P, rocprim::plus<i32>()));
+    a.merged_of = O.merged_of.p();
+    i32 n_merged = 0;
+    TRY(overlay_total(h, O.merged_of.p(), P, &n_merged));
+    const i64 M = a.n_merged = n_merged;
+    if (M <= 0 || M > P) return h->fail(WFS_E_STATE, "wfs_overlay_records: internal: the merged pulses do not follow from the pulses");
+    TRY(ensure(h, O.m_first, (size_t)M)); TRY(ensure(h, O.m_last, (size_t)M)); TRY(ensure(h, O.m_nrec, (size_t)M)); TRY(ensure(h, O.rec_end, (size_t)M));
+    a.m_first = O.m_first.p(); a.m_last = O.m_last.p(); a.m_nrec = O.m_nrec.p();
+    TRY(launch(h, PLAIN(k_ov_merged), per_thread(P), a));
+    TRY(launch(h, PLAIN(k_ov_count), per_thread(M), a));
+    TRY(overlay_scan(h, O.m_nrec.p(), O.rec_end.p(), M, rocprim::plus<i64>()));
+    a.rec_end = O.rec_end.p();
+    i64 n_out = 0;
+    TRY(copy_async(h, &sc, O.scal.p(), 1, hipMemcpyDeviceToHost));
+    TRY(overlay_total(h, O.rec_end.p(), M, &n_out));
+    if (sc.too_long) return h->fail(WFS_E_CAPACITY, "wfs_overlay_records: overlay: a merged pulse of more than 2^31 - 1 samples");
+    if (n_out > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "wfs_overlay_records: overlay: more than 2^31 records come out of one pass, split it");
+    const i64 NO = a.n_out = n_out;
+    if (NO <= 0) return h->fail(WFS_E_STATE, "wfs_overlay_records: internal: merged pulses without a record");
+    // the output records by (time, channel), each filled in its sorted slot
+    TRY(ensure(h, O.okey, (size_t)NO)); TRY(ensure(h, O.okey2, (size_t)NO)); TRY(ensure(h, O.oval, (size_t)NO)); TRY(ensure(h, O.oval2, (size_t)NO));
+    TRY(ensure(h, O.out, (size_t)NO * REC_DWORDS));
+    a.okey = O.okey.p(); a.oval = O.oval.p();
+    TRY(launch(h, PLAIN(k_ov_out_keys), per_thread(M), a));
+    TRY(overlay_sort(h, O.okey.p(), O.okey2.p(), O.oval.p(), O.oval2.p(), NO, a.bits.sbits + a.bits.chbits));
+    a.okey = O.okey2.p(); a.oval = O.oval2.p(); a.out = O.out.p();
+    TRY(launch(h, PLAIN(k_ov_fill), per_wave(NO), a));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipGetLastError());
+    CHECK_LAUNCHES();
+    O.n_records = NO; *n_records = NO;
+    return WFS_OK;
+} WFS_CATCH(h)
+
+int wfs_copy_overlay_records(wfs_handle *h, void *dst, int64_t capacity_records)
+try {
+    if (!h) return WFS_E_INVALID;
+    if (capacity_records < h->overlay.n_records || (h->overlay.n_records > 0 && !dst)) return h->fail(WFS_E_CAPACITY, "wfs_copy_overlay_records: record buffer too small");
+    HIPCHK(hipSetDevice(h->device));
+    if (h->overlay.n_records) HIPCHK(hipMemcpy(dst, h->overlay.out.p(), (size_t)h->overlay.n_records * WFS_RECORD_BYTES, hipMemcpyDefault));
     return WFS_OK;
 } WFS_CATCH(h)
 

@@ -2789,6 +2789,185 @@ __global__ void k_lone_desc(WfsDev d, LoneArgs a, RowDesc *desc)
     a.out_channel[row] = c.ch; a.out_nph[row] = c.n; a.out_nnz[row] = c.nn; a.out_left[row] = c.left; a.out_right[row] = c.right; a.out_ixr[row] = q.ixr;
 }
 
+// ---- The overlay pass (wfs_overlay_records; the rule: wfs_overlay.h): two streams of raw_records, A the simulation's and B
+// the recorded background, merged per channel into one valid stream.  Records i < n_a are A's.  The host sorts three times between
+// these kernels -- the records by (stream, channel, time), the pulses by (channel, start, stream), the output records by (time, channel)
+// -- and scans three flags; everything the kernels write is a buffer of wfs_handle::overlay.
+struct OverlayScal {
+    i64 smin, smax;              // smallest fragment start, largest last sample of a pulse (absolute samples).  k_ov_check -> host
+    i64 n_bad; u64 first_bad;    // records that break validity; the first of them, index << 8 | OvBad.  k_ov_check, k_ov_valid -> host
+    i64 too_long;                // merged pulses of more than 2^31 - 1 samples.  k_ov_count -> host
+};
+struct OverlayArgs {
+    const u32 *src_a, *src_b; i64 n_a, n;        // the records of the two streams, REC_DWORDS each; n = n_a + n_b
+    i32 dt, n_rows, baseline; const i32 *base;   // cfg.dt, row slots, cfg.baseline; the recorded baseline per channel
+    OvBits bits; i64 smin;
+    OverlayScal *scal;
+    u64 *key; u32 *val;                          // [n] record keys and indices: unsorted for k_ov_keys, sorted from k_ov_valid on
+    i32 *flag; const i32 *pulse_of;              // [n] 1 for the first fragment of a pulse (sorted order); its inclusive scan
+    i64 n_pulses; u64 *pkey; u32 *plen;          // [pulses] pulse keys and lengths: unsorted for k_ov_pulses, sorted from k_ov_ends on
+    u64 *ekey; const u64 *run_max;               // [pulses] channel | last sample; its running maximum
+    i32 *head; const i32 *merged_of;             // [pulses] 1 for the first pulse of a merged pulse; its inclusive scan
+    i64 n_merged; u64 *m_first, *m_last;         // [merged] channel | first sample, channel | last sample
+    i64 *m_nrec; const i64 *rec_end;             // [merged] records; their inclusive scan
+    i64 n_out; u64 *okey; u32 *oval;             // [records] output keys and merged pulses: unsorted for k_ov_out_keys, sorted for k_ov_fill
+    u32 *out;                                    // the output records in (time, channel) order
+};
+__device__ __forceinline__ const u32 *ov_record(const OverlayArgs &a, i64 i) { return i < a.n_a ? a.src_a + (size_t)i * REC_DWORDS : a.src_b + (size_t)(i - a.n_a) * REC_DWORDS; }
+__device__ __forceinline__ void ov_report(const OverlayArgs &a, i64 i, int bad)
+{
+    atomicAdd((u64 *)&a.scal->n_bad, 1ull); atomicMin(&a.scal->first_bad, ((u64)i << 8) | (u64)bad);
+}
+// thread per record: what the record alone decides, and the range of the pass (one atomic pair per wave)
+__global__ void k_ov_check(OverlayArgs a)
+{
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    i64 lo = I64_MAX, hi = I64_MIN;
+    if (i < a.n) {
+        const OvHeader q = ov_header(ov_record(a, i));
+        const int bad = ov_record_check(q, a.dt, a.n_rows);
+        if (bad) ov_report(a, i, bad);
+        else { lo = ov_fragment_sample(q); hi = ov_pulse_last(q); }
+    }
+    for (int o = 32; o > 0; o >>= 1) { const i64 l2 = __shfl_down(lo, o, 64), h2 = __shfl_down(hi, o, 64); lo = l2 < lo ? l2 : lo; hi = h2 > hi ? h2 : hi; }
+    if ((threadIdx.x & 63) == 0 && lo != I64_MAX) { atomicMin(&a.scal->smin, lo); atomicMax(&a.scal->smax, hi); }
+}
+__global__ void k_ov_keys(OverlayArgs a)
+{
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const OvHeader q = ov_header(ov_record(a, i));
+    a.key[i] = ov_record_key(a.bits, i < a.n_a ? 0 : 1, q.channel, ov_fragment_sample(q) - a.smin);
+    a.val[i] = (u32)i;
+}
+// thread per sorted record: the record against the one in front of it on its channel in its stream; the flag of a pulse's first fragment
+__global__ void k_ov_valid(OverlayArgs a)
+{
+    const i64 p = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.n) return;
+    const u64 k = a.key[p];
+    const OvHeader q = ov_header(ov_record(a, a.val[p]));
+    const bool has_prev = p > 0 && (a.key[p - 1] >> a.bits.sbits) == (k >> a.bits.sbits);
+    const bool is_last = p == a.n - 1 || (a.key[p + 1] >> a.bits.sbits) != (k >> a.bits.sbits);
+    OvHeader pr = q;
+    if (has_prev) pr = ov_header(ov_record(a, a.val[p - 1]));
+    int bad = ov_pair_check(has_prev, pr, q);
+    if (!bad && is_last) bad = ov_last_check(q);
+    if (bad) ov_report(a, a.val[p], bad);
+    a.flag[p] = q.record_i == 0 ? 1 : 0;
+}
+// thread per sorted record: the key and the length of the pulse it begins
+__global__ void k_ov_pulses(OverlayArgs a)
+{
+    const i64 p = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.n || !a.flag[p]) return;
+    const u64 k = a.key[p];
+    const i64 j = a.pulse_of[p] - 1;
+    a.pkey[j] = ov_pulse_key(a.bits, (int)(k >> (a.bits.sbits + a.bits.chbits)), ov_key_channel(a.bits, k), ov_key_rel(a.bits, k));
+    a.plen[j] = ov_record(a, a.val[p])[REC_PULSE_LENGTH];
+}
+// thread per sorted pulse: channel | last sample (the last sample is at most smax - smin: no carry into the channel)
+__global__ void k_ov_ends(OverlayArgs a)
+{
+    const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < a.n_pulses) a.ekey[j] = (a.pkey[j] >> 1) + (u64)(a.plen[j] - 1u);
+}
+__global__ void k_ov_heads(OverlayArgs a)
+{
+    const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < a.n_pulses) a.head[j] = (j == 0 || ov_begins_merged(a.run_max[j - 1], a.pkey[j])) ? 1 : 0;
+}
+// thread per sorted pulse: the first pulse of a merged pulse writes where it begins, the last where it ends
+__global__ void k_ov_merged(OverlayArgs a)
+{
+    const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= a.n_pulses) return;
+    const i64 m = a.merged_of[j] - 1;
+    if (a.head[j]) a.m_first[m] = a.pkey[j] >> 1;
+    if (j == a.n_pulses - 1 || a.head[j + 1]) a.m_last[m] = a.run_max[j];
+}
+__global__ void k_ov_count(OverlayArgs a)
+{
+    const i64 m = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= a.n_merged) return;
+    const u64 len = a.m_last[m] - a.m_first[m] + 1ull;         // (one channel in both)
+    if (len > 0x7fffffffull) { atomicAdd((u64 *)&a.scal->too_long, 1ull); a.m_nrec[m] = 0; return; }
+    a.m_nrec[m] = records_of((i32)len);
+}
+// thread per merged pulse: the keys of its records
+__global__ void k_ov_out_keys(OverlayArgs a)
+{
+    const i64 m = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= a.n_merged) return;
+    const i64 nrec = a.m_nrec[m], o0 = a.rec_end[m] - nrec;
+    const u64 first = a.m_first[m];
+    const i32 ch = ov_key_channel(a.bits, first); const i64 rel = ov_key_rel(a.bits, first);
+    for (i64 f = 0; f < nrec; f++) {
+        if (o0 + f >= a.n_out) break;
+        a.okey[o0 + f] = ov_output_key(a.bits, ch, rec_fragment_sample(rel, f)); a.oval[o0 + f] = (u32)m;
+    }
+}
+// the first sorted record at or behind `key` (bisection over the record keys)
+__device__ __forceinline__ i64 ov_lower_bound(const OverlayArgs &a, u64 key)
+{
+    i64 lo = 0, hi = a.n;
+    while (lo < hi) { const i64 mid = (lo + hi) >> 1; if (a.key[mid] < key) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+// Wave per output record, in its sorted slot.  Lane l < 55 holds the samples 2 l and 2 l + 1 of the record.  The source fragments that
+// can meet its samples S .. S + L - 1 start in S - 109 .. S + L - 1 on its channel: per stream a bisection over the sorted record keys
+// and a walk over the few that follow (a fragment has at least one sample and the fragments of a stream share none: at most L + 109).
+// Every one of them belongs to this merged pulse, which holds every pulse that shares a sample with it.  Sums in registers as i32, the
+// rule of ov_sample, one dword store per lane; lane 0 writes the header.
+__global__ __launch_bounds__(256) void k_ov_fill(OverlayArgs a)
+{
+    const int lane = threadIdx.x & 63;
+    const i64 r = (i64)blockIdx.x * 4 + wave_in_block();
+    if (r >= a.n_out) return;
+    const u64 ok = a.okey[r];
+    const i64 m = a.oval[r];
+    const i32 ch = ov_output_channel(a.bits, ok);
+    const i64 S = ov_output_rel(a.bits, ok), first = ov_key_rel(a.bits, a.m_first[m]);
+    const i32 plen = (i32)(a.m_last[m] - a.m_first[m] + 1ull), f = (i32)((S - first) / WFS_SPR), L = rec_fragment_len(plen, f);
+    const i64 s0 = S + 2 * lane;
+    i32 va[2] = {0, 0}, vb[2] = {0, 0}; bool ca[2] = {false, false}, cb[2] = {false, false};
+    for (int stream = 0; stream < 2; stream++) {
+        const u64 kbase = ov_record_key(a.bits, stream, ch, 0);
+        const u64 kend = kbase + (u64)(S + L);
+        for (i64 p = ov_lower_bound(a, kbase + (u64)(S > WFS_SPR - 1 ? S - (WFS_SPR - 1) : 0)); p < a.n; p++) {
+            const u64 k = a.key[p];
+            if (k >= kend) break;
+            const u32 *rec = ov_record(a, a.val[p]);
+            const i64 fs = ov_key_rel(a.bits, k); const i32 flen = (i32)rec[REC_LENGTH];
+            const int16_t *data = (const int16_t *)(rec + REC_HEADER_DWORDS);
+#pragma unroll
+            for (int u = 0; u < 2; u++) {
+                const i64 at = s0 + u - fs;
+                if (lane < WFS_SPR / 2 && at >= 0 && at < flen && 2 * lane + u < L) {
+                    const i32 v = data[at];
+                    if (stream == 0) { va[u] = v; ca[u] = true; } else { vb[u] = v; cb[u] = true; }
+                }
+            }
+        }
+    }
+    u32 *dst = a.out + (size_t)r * REC_DWORDS;
+    if (lane < WFS_SPR / 2) {
+        const i32 base = a.base[ch];
+        u32 w = 0;
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            const i32 v = (ca[u] || cb[u]) ? ov_sample(ca[u], cb[u], va[u], vb[u], a.baseline, base) : 0;
+            w |= (u32)(uint16_t)(int16_t)v << (16 * u);
+        }
+        dst[REC_HEADER_DWORDS + lane] = w;
+    }
+    if (lane == 0) {
+        const RecHeader h = rec_header(a.dt, rec_dt_channel(a.dt, ch), a.smin + first, plen, f);
+#pragma unroll
+        for (int q = 0; q < REC_HEADER_DWORDS; q++) dst[q] = h.w[q];
+    }
+}
+
 // Records ordered by (time, channel) as strax.sort_by_time leaves them (strax_interface.py:453): one key per record; the
 // windows of a batch do not overlap in time, so one sort of the whole batch keeps every window contiguous.
 __global__ __launch_bounds__(256) void k_rec_keys(WfsDev d, ZleArgs a)

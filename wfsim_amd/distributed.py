@@ -165,6 +165,8 @@ def simulate_sharded(config, instructions, device=None, dst=0, max_batch_quanta=
     import torch.distributed as dist
     from .dtypes import raw_record_dtype
     from .rawdata import RawData
+    if config.get('overlay_records') is not None:       # (a pass hands the rest of a cut pulse to the next batch of its own run)
+        raise ValueError('overlay_records: not under sharding (distributed.simulate_sharded)')
     rank, world = dist.get_rank(), dist.get_world_size()
     device = int(os.environ.get('LOCAL_RANK', rank)) if device is None else device
     on_gpu = dist.get_backend() == 'nccl'

@@ -810,6 +810,34 @@ class Engine:
             self._call('wfs_copy_lone_records', out, len(out))
         return out
 
+    def overlay_records(self, bg, sim=None, baseline=None, n_sim=None):
+        """raw_records of the overlay pass (wfs_overlay_records): the simulation's stream ``sim`` -- None: the records of the
+        last ``run()``, where the device holds them -- merged per channel with the recorded background ``bg``, in (time, channel)
+        order.  Pulses of the two streams that share a sample become one pulse; where both cover a sample it holds b + a - baseline,
+        where the simulation alone does a - baseline + ``baseline[channel]`` (int32 per row slot; None: the configuration's baseline).
+        ``n_sim`` (with ``sim`` None): only the first n_sim records of the run, in the order of ``records()``."""
+        dtype = raw_record_dtype()
+
+        def stream(x, name):
+            x = np.ascontiguousarray(x)
+            if x.dtype != dtype or x.ndim != 1:
+                raise ValueError(f'overlay_records: {name} must be a 1-d array of raw_record_dtype()')
+            return x
+        bg = stream(bg, 'bg')
+        sim = None if sim is None else stream(sim, 'sim')
+        if baseline is not None:
+            baseline = np.ascontiguousarray(baseline, dtype=np.int32)
+            if baseline.shape != (int(self.params['n_rows']),):
+                raise ValueError(f"overlay_records: baseline must hold one value per row slot ({int(self.params['n_rows'])})")
+        n = np.zeros(1, dtype=np.int64)
+        # (an empty array still has an address: NULL means "the last run's records")
+        self._call('wfs_overlay_records', None if sim is None else sim.view(np.uint8).reshape(-1) if len(sim) else np.zeros(1, dtype=np.uint8),
+                   (-1 if n_sim is None else int(n_sim)) if sim is None else len(sim), bg.view(np.uint8).reshape(-1) if len(bg) else None, len(bg), baseline, n)
+        out = np.zeros(int(n[0]), dtype=dtype)
+        if len(out):
+            self._call('wfs_copy_overlay_records', out, len(out))
+        return out
+
     def lone_hit_rows(self):
         """the rows of the last ``lone_hits`` pass in (channel, time) order: a structured array (channel, left, right, ix_rand,
         n_photons) -- first and last absolute sample, the noise-table offset (0 without a table), the lone dark photons of the chain

@@ -100,6 +100,9 @@ class RawData:
                                  'resource.uniform_to_ele_ap, the delay-time histogram (load_resource.py:233)')
             self._pi_hist = ea.DelayHistogram.wrap(self.resource.uniform_to_ele_ap)
             self._pi_grid = ea.coarse_delay_grid(self._pi_hist, config)
+        # config['overlay_records']: the recorded stream a run is overlaid on, one pass behind every batch (_overlay_pass)
+        from .overlay import overlay_from
+        self.overlay, self.overlay_baseline = overlay_from(config, self.engine.params)
         self.source_finished = False
         self.left = self.right = 0
         #: run the kernels of the next batch while the consumer of iter_batches works on the current one
@@ -148,6 +151,9 @@ class RawData:
             k = 0
             n_win = len(batch['left'])
             lone, q = batch.get('lone_records'), 0
+            over = batch.get('overlay_records')
+            if over is not None:                # config['overlay_records']: the stretches of the pass carry the records, the windows none
+                lone = over
             if lone is not None:
                 lone_left, lone_right, lone_first = lone_stretches(lone)
             for w in range(n_win):
@@ -157,23 +163,25 @@ class RawData:
                     k = k1
                 if lone is not None:            # the lone-hit rows in front of this window
                     stop = int(np.searchsorted(lone_left, int(batch['left'][w]), side='left'))
-                    yield from self._lone_entries(lone, lone_left, lone_right, lone_first, q, stop)
+                    yield from self._lone_entries(lone, lone_left, lone_right, lone_first, q, stop, over is not None)
                     q = stop
                 self.left, self.right = int(batch['left'][w]), int(batch['right'][w])
                 if batch['finished'] and w == n_win - 1 and (lone is None or q == len(lone_left)):
                     self.source_finished = True
-                yield dict(left=self.left, right=self.right, records=batch['records'][batch['first'][w]:batch['first'][w + 1]])
+                w_rec = batch['records'][batch['first'][w]:batch['first'][w + 1]]
+                yield dict(left=self.left, right=self.right, records=w_rec[:0] if over is not None else w_rec)
             if lone is not None:
-                yield from self._lone_entries(lone, lone_left, lone_right, lone_first, q, len(lone_left))
+                yield from self._lone_entries(lone, lone_left, lone_right, lone_first, q, len(lone_left), over is not None)
             if k < len(rows):
                 self._write_truth(table, rows[k:], truth_buffer)
         self.source_finished = True
 
-    def _lone_entries(self, lone, left, right, first, a, b):
-        """entries dict(left, right, records, lone=True) of the lone-hit stretches a .. b - 1 of a batch (lone_stretches)"""
+    def _lone_entries(self, lone, left, right, first, a, b, overlay=False):
+        """entries dict(left, right, records, lone=True) of the lone-hit stretches a .. b - 1 of a batch (lone_stretches); those of an
+        overlay pass carry overlay=True instead"""
         for j in range(a, b):
             self.left, self.right = int(left[j]), int(right[j])
-            yield dict(left=self.left, right=self.right, records=lone[first[j]:first[j + 1]], lone=True)
+            yield dict(left=self.left, right=self.right, records=lone[first[j]:first[j + 1]], **({'overlay': True} if overlay else {'lone': True}))
 
     def iter_batches(self, instructions, want_truth=False, record_sink=None, device_records=False, **kwargs):
         """The same stream batch by batch (what the chunker consumes): dict(left[], right[] of the batch's digitise windows
@@ -265,6 +273,8 @@ class RawData:
                              records=records, truth_table=truth_table, truth_rows=truth_rows, truth_before=truth_before, finished=L['b'] >= n)
                 if L.get('lone_records') is not None:       # config['dark_count_lone_hits'] / ['noise_lone_hits']: the pass behind this batch's run (_launch)
                     batch['lone_records'] = L['lone_records']
+                if L.get('overlay_records') is not None:    # config['overlay_records']: the whole output of the pass behind this batch's run, by time
+                    batch['overlay_records'] = L['overlay_records']
                 # everything else of this batch is on the host now: the engine is free for the next one (it keeps the records of
                 # two batches: this batch's copy overlaps the next batch's kernels)
                 if L['b'] < n:
@@ -335,7 +345,53 @@ class RawData:
             if getattr(self.engine, 'lone_hits_on', False):
                 # directly behind the batch's run, on the thread that owns the engine: the rows of that run are what a photon is lone against
                 out['lone_records'] = self._lone_pass(st, groups, keep, nonempty, n_emit, b >= n)
+            if self.overlay is not None:
+                # directly behind the batch's run, on the thread that owns the engine: the records of that run are stream A where they lie
+                out['overlay_records'] = self._overlay_pass(st, groups, keep, nonempty, n_emit, int(first[n_emit]), b >= n)
             return out
+
+    def _next_window_bound(self, groups, nonempty, n_emit, last_right, gap):
+        """The sample in front of which no window of a later batch begins: the left of the next window where the run knows it, else
+        gap + 64 samples short of last_right + 1 + right_raw_extension / dt (dark_counts.lone_hits_from)."""
+        p = self.engine.params
+        later = np.flatnonzero(nonempty[n_emit:])
+        return int(groups['left'][n_emit + later[0]]) if len(later) else last_right + 1 + int(p['rext']) // int(p['dt']) - (gap + 64)
+
+    def _overlay_pass(self, st, groups, keep, nonempty, n_emit, n_sim, finished):
+        """The overlay pass of a batch: the records of the batch's emitted windows merged with the background pulses that
+        start in front of T, the right of its last emitted window plus 1, and have not been taken yet.  The first pass begins at
+        config['overlay_begin'] (ns; default: the first window's left minus right_raw_extension), the last one ends at
+        config['overlay_end'] (default: the last window's right plus right_raw_extension).  A taken pulse that runs past the sample at
+        which a window of a later batch can first begin (_next_window_bound, no gap) is cut there: its front goes to this pass, the
+        rest is a pulse of the next."""
+        from .overlay import pass_pulses
+        cfg, p = self.config, self.engine.params
+        dt, rext = int(p['dt']), int(p['rext']) // int(p['dt'])
+        empty = np.zeros(0, dtype=raw_record_dtype())
+        if st.get('overlay_next') is None:
+            begin = cfg.get('overlay_begin', getattr(self, 'overlay_begin_ns', None))
+            if begin is None and not len(keep):
+                return empty                    # (no window yet: the first pass waits for one)
+            st['overlay_next'] = int(begin) if begin is not None else (int(groups['left'][keep[0]]) - rext) * dt
+            st['overlay_carry'] = empty
+        t0 = st['overlay_next']
+        if len(keep):
+            st['overlay_last_right'] = int(groups['right'][keep[-1]])
+        cut = None
+        if finished:
+            end = cfg.get('overlay_end')
+            if end is None and st.get('overlay_last_right') is None:
+                return empty
+            t1 = int(end) if end is not None else (st['overlay_last_right'] + 1 + rext) * dt
+        else:
+            if not len(keep):
+                return empty
+            t1 = (st['overlay_last_right'] + 1) * dt
+            cut = max(self._next_window_bound(groups, nonempty, n_emit, st['overlay_last_right'], 0), st['overlay_last_right'] + 1)
+        t1 = max(t1, t0)
+        bg, st['overlay_carry'] = pass_pulses(self.overlay, st['overlay_carry'], t0, t1, cut, dt)
+        st['overlay_next'] = t1
+        return self.engine.overlay_records(bg, baseline=self.overlay_baseline, n_sim=n_sim)
 
     #: samples of one pass of wfs_lone_hits at most; a longer range is a run of passes with the same records (_lone_range)
     lone_pass_samples = 1 << 28
@@ -370,8 +426,7 @@ class RawData:
             # G samples beyond the last emitted window: the next pass then looks back at samples behind that window alone, whose rows
             # it no longer has (a photon there could pass for lone and keep the one behind it from beginning a row)
             s1 = st['lone_last_right'] + 1 + lone_gap(p)
-            later = np.flatnonzero(nonempty[n_emit:])
-            s_limit = int(groups['left'][n_emit + later[0]]) if len(later) else st['lone_last_right'] + 1 + rext - (lone_gap(p) + 64)
+            s_limit = self._next_window_bound(groups, nonempty, n_emit, st['lone_last_right'], lone_gap(p))
         s1 = max(s1, s0)
         s_limit = max(s_limit, s1)
         st['lone_next'] = s1

@@ -187,10 +187,17 @@ class ChunkRawRecords(object):
         if lone_on and self.config.get('lone_hits_begin') is None:
             # no lone record in front of the first chunk: a row begins trigger_window samples ahead of its first photon
             rd.lone_begin_ns = self.chunk_time_pre + int(self.config['trigger_window']) * dt
-        for batch in rd.iter_batches(instructions, want_truth=True, record_sink=None if lone_on else sink, **kwargs):
+        # the overlay (config 'overlay_records'): the output of a batch's pass takes the place of its records, its stretches are
+        # treated as lone stretches are; the buffer is not offered to the device copy either
+        overlay_on = getattr(rd, 'overlay', None) is not None
+        if overlay_on and self.config.get('overlay_begin') is None:
+            rd.overlay_begin_ns = self.chunk_time_pre           # no recorded pulse in front of the first chunk
+        for batch in rd.iter_batches(instructions, want_truth=True, record_sink=None if lone_on or overlay_on else sink, **kwargs):
             self._batch_leases = []             # buffers handed out while this batch is worked on stay taken until it is done
             if len(batch.get('lone_records', ())):
                 batch = merge_lone_records(batch)
+            if batch.get('overlay_records') is not None:
+                batch = overlay_batch(batch)
             rec, first, left, right = batch['records'], batch['first'], batch['left'], batch['right']
             table, rows, before = batch['truth_table'], batch['truth_rows'], batch['truth_before']
             left_ns = left * dt
@@ -466,6 +473,16 @@ def merge_lone_records(batch):
     return merged
 
 
+def overlay_batch(batch):
+    """A batch of RawData.iter_batches with the output of its overlay pass in place of its records: the digitise windows,
+    now without records of their own, and the stretches of the output are joined into entries as merge_lone_records joins lone
+    stretches, so no pulse is cut at a chunk end and truth rows keep their windows."""
+    n_win = len(batch['left'])
+    bare = dict(batch, records=batch['overlay_records'][:0], first=np.zeros(n_win + 1, dtype=np.int64), lone_records=batch['overlay_records'])
+    del bare['overlay_records']
+    return merge_lone_records(bare)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 class SimulatorPlugin(_Plugin):
     """strax_interface.py:536-663: stateful source plugin around a ChunkRawRecords iterator."""
@@ -586,6 +603,8 @@ class RawRecordsFromFaxNT(SimulatorPlugin):
         shard = self.config.get('shard')
         if shard is None:
             return None
+        if self.config.get('overlay_records') is not None:      # 
+            raise ValueError("overlay_records: not under sharding (config['shard'])")
         if shard == 'auto':
             import torch.distributed as dist
             if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
@@ -743,7 +762,7 @@ class RawRecordsFromMcChain(SimulatorPlugin):
         super().set_config()
         if 'nveto' in self.config['targets']:
             import copy
-            skip = ('instructions_epix', 'instructions_nveto', 'nveto_channels', 'nveto_timings')
+            skip = ('instructions_epix', 'instructions_nveto', 'nveto_channels', 'nveto_timings', 'overlay_records', 'overlay_records_nveto')
             cn = {k: (v if k in skip else copy.deepcopy(v)) for k, v in self.config.items()}
             # PMT dark counts: 'dark_count_rate' is the TPC engine's (one value per TPC PMT); the veto engine reads
             # 'dark_count_rate_nveto' (or a 'dark_count_rate' inside fax_config_nveto) and has none otherwise
@@ -752,6 +771,8 @@ class RawRecordsFromMcChain(SimulatorPlugin):
             cn.pop('noise_lone_hits', None)
             if cn.pop('noise_lone_hits_nveto', False):
                 cn['noise_lone_hits'] = True
+            # ... and 'overlay_records_nveto' as its 'overlay_records' (DESIGN 3h): a recorded TPC stream is not the veto's
+            cn['overlay_records'] = cn.pop('overlay_records_nveto', None)
             cn.update(self.config.get('fax_config_nveto') or {})
             if cn.get('dark_count_rate') is None:       # 'dark_count_lone_hits'  reaches the veto engine with veto rates alone
                 cn.pop('dark_count_lone_hits', None)
