@@ -1,6 +1,8 @@
 // Drives wfsim_amd/csrc/wfs_rows.h on the host (tests/test_row_rules_cpu.py).
 //
-//   rows_main                      the rules that need no rows: one line "<case> ok|FAILED ..." for geometry, noise_index, finish, padded_len
+//   rows_main                      the rules that need no rows: one line "<case> ok|FAILED ..." for geometry, noise_index, finish, padded_len,
+//                                  key_bits (bits_below and the three rules written through it: the end bits of the record sort and of the
+//                                  lone seed sort, the key fields of the overlay -- each against the loop it replaced, written out here)
 //   rows_main noise <file>         noise_index once more, on the rows of a file of lines "<noise_len> <row length>"
 //   rows_main rows <file>          a family of designed rows, one per line: length, trigger window, absolute first sample, channel, dt, and
 //                                  the positions of its hits.  The hits are grouped one after the other with zle_holdoff, every interval is
@@ -10,6 +12,8 @@
 //                                  printed is consistent with itself.  The comparison with the reference's tuples and records is the test's.
 // Exits 0 when every case holds.
 #include "wfs_rows.h"
+#include "wfs_lone.h"        // lone_key_end_bit
+#include "wfs_overlay.h"     // ov_bits_of
 
 #include <cstdio>
 #include <cstring>
@@ -165,6 +169,52 @@ static bool padded_len()
            && fin_padded_len(7167) == 7168 && fin_last_pair(1) == 2 && fin_last_pair(7168) == 7166;
 }
 
+// ---- key_bits ---------------------------------------------------------------------------------------------------------------------------
+// the loops the engine and wfs_overlay.h held before bits_below, literally
+static unsigned old_record_end_bit(u64 span) { unsigned end_bit = 13; while (end_bit < 64 && ((span << 12) >> end_bit) != 0) end_bit++; return end_bit; }
+static unsigned old_seed_end_bit(u64 n_ch) { unsigned end_bit = 41; while (end_bit < 64 && (n_ch >> (end_bit - 41)) != 0) end_bit++; return end_bit; }
+static int old_ov_bits_of(u64 v) { int b = 1; while (b < 64 && (v >> b) != 0) b++; return b; }
+static bool key_bits(std::string &what)
+{
+    bool ok = true;
+    auto want = [&](const char *name, u64 arg, long long got, long long exp) {
+        if (got != exp) { std::ostringstream o; o << name << "(" << arg << "): " << got << " for " << exp; what = o.str(); ok = false; }
+    };
+    // bits needed for values below v: the smallest b with v <= 2^b
+    want("bits_below", 0, bits_below(0), 0); want("bits_below", 1, bits_below(1), 0); want("bits_below", 2, bits_below(2), 1);
+    for (int k = 1; k <= 51; k++) {
+        const u64 p = (u64)1 << k;
+        want("bits_below 2^k - 1", p - 1, bits_below(p - 1), k == 1 ? 0 : (k == 2 ? 2 : k));      // 1: no bit; 3: two bits; above, 2^(k-1) < 2^k - 1
+        want("bits_below 2^k", p, bits_below(p), k);
+        want("bits_below 2^k + 1", p + 1, bits_below(p + 1), k + 1);
+    }
+    want("bits_below 2^63", (u64)1 << 63, bits_below((u64)1 << 63), 63);
+    want("bits_below 2^63 + 1", ((u64)1 << 63) + 1, bits_below(((u64)1 << 63) + 1), 64);
+    want("bits_below 2^64 - 1", ~0ull, bits_below(~0ull), 64);
+    // the record key: span << 12 | channel
+    static_assert(REC_KEY_SHIFT == 12, "the literal of the old loop");
+    for (u64 span : {(u64)1, (u64)2, (u64)4095, (u64)4096, (u64)1 << 31, ((u64)1 << 51) - 1})
+        want("rec_key_end_bit", span, rec_key_end_bit(span), old_record_end_bit(span));
+    want("rec_key_end_bit", 0, rec_key_end_bit(0), 13);                          // (the engine hands in at least 1)
+    want("rec_key_end_bit", 1, rec_key_end_bit(1), 13);
+    want("rec_key_end_bit", 4096, rec_key_end_bit(4096), 25);
+    want("rec_key_end_bit 2^52", (u64)1 << 52, rec_key_end_bit((u64)1 << 52), 64);      // where the old loop began to lose bits: every bit is sorted
+    // the lone seed key: channel << 41 | start << 1 | kind
+    static_assert(LONE_KEY_SHIFT == 41, "the literal of the old loop");
+    for (int n_ch : {1, 2, 493, 494, 512, 4095})
+        want("lone_key_end_bit", (u64)n_ch, lone_key_end_bit(n_ch), old_seed_end_bit((u64)n_ch));
+    want("lone_key_end_bit", 494, lone_key_end_bit(494), 50);
+    want("lone_key_end_bit", 0, lone_key_end_bit(0), 41);
+    // the overlay's key fields, at its three uses: the samples of a pass, n_rows - 1, the 800 of the key case of overlay_rules_main.cpp
+    for (u64 span : {(u64)1, (u64)2, (u64)1000, (u64)1 << 40, ((u64)1 << 40) + 1, ((u64)1 << 53) - 1})
+        want("ov_bits_of span + 1", span, ov_bits_of(span + 1), old_ov_bits_of(span + 1));
+    for (u64 n_rows : {(u64)1, (u64)2, (u64)3, (u64)494, (u64)513, (u64)801, (u64)1025})
+        want("ov_bits_of n_rows - 1", n_rows, ov_bits_of(n_rows - 1 > 1 ? n_rows - 1 : 1), old_ov_bits_of(n_rows - 1 > 1 ? n_rows - 1 : 1));
+    want("ov_bits_of", 800, ov_bits_of(800), old_ov_bits_of(800));
+    for (u64 v : {(u64)0, (u64)1, (u64)2, (u64)1023, (u64)1024, ~0ull}) want("ov_bits_of", v, ov_bits_of(v), old_ov_bits_of(v));
+    return ok;
+}
+
 // ---- rows -------------------------------------------------------------------------------------------------------------------------------
 static int rows(const char *path)
 {
@@ -234,5 +284,7 @@ int main(int argc, char **argv)
     what.clear();
     { const bool ok = finish(what); report("finish", ok, what); }
     report("padded_len", padded_len());
+    what.clear();
+    { const bool ok = key_bits(what); report("key_bits", ok, what); }
     return failures ? 1 : 0;
 }

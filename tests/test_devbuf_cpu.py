@@ -98,3 +98,5 @@ def test_element_types_stand_in_the_declarations():
     assert len(sized) > 150
     for args in sized:
         assert not re.search(r'\*\s*[48]\b|\b[48]\s*\*|sizeof', args[-1]), args
+    for args in _calls(src, 'ensure_each')[1:]:                 # (the first is the definition; the count stands in front of the arrays)
+        assert not re.search(r'\*\s*[48]\b|\b[48]\s*\*|sizeof', args[1]), args

@@ -99,6 +99,26 @@ def test_every_family_is_declared_once(engine_src):
     assert len(inst) == len(decl) - 1 and all('= family<' in ln or ln.lstrip().startswith('[](auto') for ln in inst), inst
 
 
+def test_one_record_back_end_and_one_way_to_call_rocprim(engine_src):
+    """Every rocPRIM operation is spelled once, inside a caller of two_step, which alone holds the sizing call, the scratch and the
+    real call; the record order (k_invert_perm) and the packers of finished rows (k_pack_res) are launched in one place each, for the
+    rows of a run and of a lone-hit pass alike; one scratch buffer."""
+    for call in ('radix_sort_pairs(', 'radix_sort_keys(', 'segmented_radix_sort_pairs(', 'inclusive_scan('):
+        assert len(re.findall(r'\b' + re.escape(call), engine_src)) == 1, call
+    assert len(re.findall(r'\bk_invert_perm\b', engine_src)) == 1 and engine_src.count('PLAIN(k_invert_perm)') == 1
+    assert len(re.findall(r'\bk_pack_res\b', engine_src)) == 1 and engine_src.count('PLAIN(k_pack_res)') == 1
+    assert engine_src.count('DevBuf sort_tmp') == 1 and len(re.findall(r'\bDevBuf\b[^;()]*\bsort_tmp\b', engine_src)) == 1
+    # the scratch is named in its declaration and in two_step, nowhere else; a null scratch is handed over in two_step alone
+    m = re.search(r'int two_step\(wfs_handle \*h,[^\n]*\n\{\n(.*?)\n\}\n', engine_src, re.S)
+    assert m and m.group(1).count('sort_tmp') == len(re.findall(r'\bsort_tmp\b', engine_src)) - 1 == 2
+    assert m.group(1).count('call(nullptr, bytes)') == 1 and engine_src.count('(nullptr, bytes') == 1
+    assert len(re.findall(r'\brocprim::', engine_src)) == 4 + 4            # the four operations; the four operators of the overlay's scans
+    # the key bits in use come from wfs_rows.h: no loop over end_bit is left, and the record key shift is named
+    assert 'end_bit++' not in engine_src and '<< 12' not in engine_src
+    kernels = re.sub(r'//[^\n]*', '', open(os.path.join(ROOT, 'wfsim_amd', 'csrc', 'wfs_kernels.h')).read())
+    assert '<< REC_KEY_SHIFT) | (u64)(u32)q.channel' in kernels and 'key_base) << 12' not in kernels
+
+
 def test_lds_caps_are_raised_in_one_place(engine_src):
     assert engine_src.count('hipFuncAttributeMaxDynamicSharedMemorySize') == 1
     assert engine_src.count('hipFuncSetAttribute') == 1 and engine_src.count('FamilyBase::each') == 1

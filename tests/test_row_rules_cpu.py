@@ -9,7 +9,8 @@ rec_header.  What it prints is compared HERE with the reference's ZLE tuples (al
 the records zle_edges.expected_records makes of them, field by field.  The rules that need no rows -- the record geometry, the noise
 index walked as the kernels walk it, the finished sample and the resident rule on its domain, the 32-bit threshold, the padded length
 of a finished row -- are checked by the program itself on values worked out by hand from rawdata.py:398-458 and strax_interface.py:
-391-436.  The last test holds that the kernels and the engine no longer write any of these rules out."""
+391-436; so are the bits of the sort keys (bits_below; the end bits of the record sort and the lone seed sort and the key fields of the
+overlay against the loops they replaced, which the program writes out).  The last test holds that the kernels and the engine no longer write any of these rules out."""
 import os
 import re
 import shutil
@@ -23,7 +24,7 @@ from tests.test_zle_edges_reference import case_rows, fixture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'wfsim_amd', 'csrc')
-SELF_CASES = ['geometry', 'noise_index', 'finish', 'padded_len']
+SELF_CASES = ['geometry', 'noise_index', 'finish', 'padded_len', 'key_bits']
 N_ROWS, N_RECORDS = 499, 2499
 
 

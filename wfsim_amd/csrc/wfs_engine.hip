@@ -58,6 +58,8 @@ constexpr size_t MINMAX = 2;               // (min, max) pairs of tminmax[set] a
 static int wfs_dev_alloc(void **p, size_t bytes) { return (int)hipMalloc(p, bytes); }
 static void wfs_dev_free(void *p) { (void)hipFree(p); }
 
+// What orders the records of a row list by (time, channel) (order_records): keys and record indices in and out of the sort, each record's sorted slot
+struct RecOrder { DevArr<u64> key, key2; DevArr<u32> val, val2, dest; };
 struct wfs_handle {
     // ---------------- the handle: written by wfs_create and the wfs_set_* calls, kept until wfs_destroy; no load and no run resets it
     // device and streams
@@ -151,7 +153,7 @@ struct wfs_handle {
     DevArr<i64> row_lo, row_hi, acc_off, itv_off; DevArr<i32> acc_len, itv_cap, active_rows, raw;
     DevArr<i64> itv_left, itv_right, rec_off; DevArr<i32> itv_n, row_nrec;
     DevArr<double> truth, tile_truth, currents; DevArr<i64> tminmax, gather_idx, gather_out, cur_off, row_dbg_off; DevArr<TileDesc> tile_desc; DevArr<i32> row_dbg; DevArr<TileTimeReq> gather_req;      // (wfs_gather_photon_times: the requests of tile-generated instructions; gather_idx holds those of the block generator)
-    DevArr<unsigned long long> stamps; DevArr<RowDesc> row_desc; DevArr<u64> rec_key, rec_key2; DevArr<u32> rec_val, rec_val2, rec_dest; DevBuf sort_tmp;      // (sort_tmp: rocPRIM's scratch)
+    DevArr<unsigned long long> stamps; DevArr<RowDesc> row_desc; RecOrder rec; DevBuf sort_tmp;      // (sort_tmp: rocPRIM's scratch, of every rocPRIM call of the file: two_step)
     DevArr<i64> scan_tmp, noise_override; DevArr<WfsScal> scal; DevArr<NoiseCell> nm_cells; DevArr<i32> nc_buf, ns_buf; DevArr<u32> dk_thr; DevArr<PackDesc> pack_desc;
     DevArr<i32> row_bad, fin_len, res_cnt, res_long; DevArr<i64> fin_off, res_toff; DevArr<TileDesc> res_desc; DevArr<int16_t> fin; DevArr<ResRow> res_rows;      // resident rows (k_row_pulse)
     DevArr<uint2> tt_alias[6]; DevArr<i32> ap_ins, ap_ch, ap_t; DevArr<double> ap_gain; DevArr<ApCand> ap_cand; DevArr<ApArgs> ap_args_dev; DevArr<ApSeg> ap_seg;
@@ -171,10 +173,10 @@ struct wfs_handle {
     // lone-hit rows (wfs_lone_hits, wfs_lone.h): a pass has buffers of its own for everything it writes -- counters, seed keys, rows,
     // intervals, finished samples, records -- so that the batch it follows, whose packers may still run, keeps every byte
     struct Lone {
-        DevArr<WfsScal> scal; DevArr<u64> keys, keys2, rec_key, rec_key2; DevArr<u32> rec_val, rec_val2, rec_dest;
+        DevArr<WfsScal> scal; DevArr<u64> keys, keys2; RecOrder rec;
         DevArr<i64> win_l, win_r, row_of, itv_off, fin_off, itv_left, itv_right, rec_off, out_left, out_right, out_ixr;
         DevArr<i32> win_g, flag, cap, flen, itv_n, row_nrec, out_channel, out_nph, out_nnz;
-        DevArr<int16_t> fin; DevArr<RowDesc> desc; DevArr<PackDesc> pdesc; DevBuf sort_tmp, records_ab[1];      // (one record arena: a pass returns when its records exist)
+        DevArr<int16_t> fin; DevArr<RowDesc> desc; DevArr<PackDesc> pdesc; DevBuf records_ab[1];      // (one record arena: a pass returns when its records exist)
         i64 n_rows = 0, n_records = 0;      // of the last pass
         bool noise_hits = false;            // wfs_set_lone_noise_hits: samples of the noise model that cross are seeds too
         DevBuf &records_buf() { return records_ab[0]; }
@@ -183,7 +185,7 @@ struct wfs_handle {
     struct Overlay {
         DevArr<OverlayScal> scal; DevArr<u32> src_a, src_b, val, val2, plen, plen2, oval, oval2, out;
         DevArr<u64> key, key2, pkey, pkey2, ekey, run_max, m_first, m_last, okey, okey2;
-        DevArr<i32> base, flag, pulse_of, head, merged_of; DevArr<i64> m_nrec, rec_end; DevBuf sort_tmp;
+        DevArr<i32> base, flag, pulse_of, head, merged_of; DevArr<i64> m_nrec, rec_end;
         i64 n_records = 0;                  // of the last pass
     } overlay;
 
@@ -239,7 +241,7 @@ int pack_fence(wfs_handle *h)
 // the buffers the packers read or write (the noise tables behind WfsDev apart: their setters wait on the host)
 bool pack_uses(const wfs_handle *h, const DevBuf &b)
 {
-    for (const DevBuf *q : {&h->pack_desc.buf(), &h->row_desc.buf(), &h->rec_off.buf(), &h->itv_n.buf(), &h->itv_left.buf(), &h->itv_right.buf(), &h->rec_dest.buf(),
+    for (const DevBuf *q : {&h->pack_desc.buf(), &h->row_desc.buf(), &h->rec_off.buf(), &h->itv_n.buf(), &h->itv_left.buf(), &h->itv_right.buf(), &h->rec.dest.buf(),
                             &h->tbuf.buf(), &h->raw.buf(), &h->fin.buf(), &h->records_ab[0], &h->records_ab[1]})
         if (q == &b) return true;
     return false;
@@ -348,10 +350,10 @@ void stat5(double *o, double n, double s1, double s2, double origin, i64 lo, i64
 
 // Brackets one kernel launch, or several under one name: HIP events when profiling is on; with wfs_set_debug bit 3 what was launched is
 // checked on the spot (hipGetLastError + a stream synchronisation), so that a failed launch or a faulting kernel is reported under its
-// own name instead of ~25 launches later at the end of wfs_run.  timed = false: the check alone, no entry in wfs_kernel_times.
+// own name instead of ~25 launches later at the end of wfs_run.  timed = false: the check alone, no entry in wfs_kernel_times; no name: neither.
 struct Timer {
     wfs_handle *h; bool on; const char *name;
-    Timer(wfs_handle *h_, const char *name_, bool timed = true) : h(h_), on(timed && h_->profiling != 0), name(name_)
+    Timer(wfs_handle *h_, const char *name_, bool timed = true) : h(h_), on(timed && name_ && h_->profiling != 0), name(name_)
     {
         if (!on) return;
         KernelTime kt; kt.name = name;
@@ -362,7 +364,7 @@ struct Timer {
     ~Timer()
     {
         if (on) hipEventRecord(h->times.back().b, h->stream);
-        if (h->debug_bits & DBG_CHECK_LAUNCHES) {
+        if (name && (h->debug_bits & DBG_CHECK_LAUNCHES)) {
             hipError_t e = hipGetLastError();
             if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
             if (e != hipSuccess && h->launch_err.empty()) { try { h->launch_err = std::string(name) + ": " + hipGetErrorString(e); } catch (...) {} }
@@ -499,6 +501,52 @@ int scan(wfs_handle *h, const i32 *in, i64 n, DevArr<i64> &out, i64 WfsScal::*to
     TRY(ensure(h, out, (size_t)(n + 1)));
     return scan_into(h, in, n, out.p(), total_member, 0, block);
 }
+
+// The one way rocPRIM is called.  Its device functions take a scratch block and its size and, given a null block, only say how much
+// they need: call(tmp, bytes) is made once for the size and, with sort_tmp grown to it, once for the work (under a Timer where timed_as
+// names one).  One block serves every user: all are enqueued on the handle's stream, and a grow frees through hipFree, which waits.
+template <class Call> int two_step(wfs_handle *h, const char *what, Call call, const char *timed_as = nullptr)
+{
+    size_t bytes = 0; hipError_t e = call(nullptr, bytes);
+    if (e == hipSuccess) TRY(ensure(h, h->sort_tmp, bytes));
+    if (e == hipSuccess) { Timer t(h, timed_as); e = call(h->sort_tmp.p, bytes); }
+    return e == hipSuccess ? WFS_OK : h->fail(WFS_E_HIP, std::string("rocPRIM, ") + what + ": " + hipGetErrorString(e));
+}
+// the two operations with several users: n (key, value) pairs sorted by the key bits below end_bit; an inclusive scan of n elements
+template <class K, class V> int sort_pairs(wfs_handle *h, const char *what, K *k_in, K *k_out, V *v_in, V *v_out, i64 n, unsigned end_bit, const char *timed_as = nullptr)
+{ return two_step(h, what, [&](void *tmp, size_t &bytes) { return rocprim::radix_sort_pairs(tmp, bytes, k_in, k_out, v_in, v_out, (size_t)n, 0u, end_bit, h->stream); }, timed_as); }
+template <class T, class Op> int scan_inclusive(wfs_handle *h, const char *what, const T *in, T *out, i64 n, Op op)
+{ return two_step(h, what, [&](void *tmp, size_t &bytes) { return rocprim::inclusive_scan(tmp, bytes, in, out, (size_t)n, op, h->stream); }); }
+template <class... A> int ensure_each(wfs_handle *h, size_t n, A &...arrays) { int rc = WFS_OK; ((rc = rc ? rc : ensure(h, arrays, n)), ...); return rc; }      // room for n elements in each array
+
+// The records of a row list into (time, channel) order as strax.sort_by_time leaves them: a key per record (k_rec_keys), one radix sort
+// over the key bits in use, the sorted slot of every record (k_invert_perm), which the packers write to.  za describes the n_rows rows and
+// takes keys, values and slots; key_origin, key_end: of the rows' counter block.  too_many: the caller's words for more records than
+// the sort counts; timed_as: the sort's entry in wfs_kernel_times, if any.
+int order_records(wfs_handle *h, RecOrder &o, ZleArgs &za, i64 n_rows, i64 n_rec, i64 key_origin, i64 key_end, const char *too_many, const char *timed_as = nullptr)
+{
+    if (n_rec > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, too_many);
+    TRY(ensure_each(h, (size_t)n_rec, o.key, o.key2, o.val, o.val2, o.dest));
+    za.rec_key = o.key.p(); za.rec_val = o.val.p();
+    TRY(launch(h, PLAIN(k_rec_keys), per_wave(n_rows), h->dev, za));
+    TRY(sort_pairs(h, "record sort", o.key.p(), o.key2.p(), o.val.p(), o.val2.p(), n_rec, rec_key_end_bit((u64)std::max<i64>(key_end - key_origin, 1)), timed_as));
+    TRY(launch(h, PLAIN(k_invert_perm), per_thread(n_rec), o.val2.p(), o.dest.p(), n_rec));
+    za.rec_dest = o.dest.p(); return WFS_OK;
+}
+// The packers of rows that exist as finished samples, on the stream `on`: k_pack_desc over the n_rows rows of za, k_pack_res over the
+// n_fin of them from row first_fin on, whose samples lie in fin.
+int pack_finished_rows(wfs_handle *h, const ZleArgs &za, i64 n_rows, const int16_t *fin, i64 first_fin, i64 n_fin, hipStream_t on)
+{
+    TRY(launch(h, PLAIN(k_pack_desc), per_thread(n_rows).on(on), za));
+    if (n_fin == 0) return WFS_OK;
+    PackResArgs pr{za.pdesc + first_fin, fin, za.itv_left, za.itv_right, za.records, za.rec_dest, za.rec_capacity, n_fin, za.spr, (i32)h->dev.dt};
+    return launch(h, PLAIN(k_pack_res), per_wave(n_fin).on(on), pr);
+}
+// A pass's counter block on the host as of this point of the stream, and the host waits; the same for the last element of an inclusive
+// scan, its total, alone or beside the block under the one wait.  pass_done: the end of a pass, a failed launch is reported.
+template <class D, class S> int read_block(wfs_handle *h, D &host, const S *dev) { TRY(copy_async(h, &host, dev, 1, hipMemcpyDeviceToHost)); HIPCHK(hipStreamSynchronize(h->stream)); return WFS_OK; }
+template <class D, class S, class T> int read_block(wfs_handle *h, D &host, const S *dev, T &total, const T *last) { TRY(copy_async(h, &host, dev, 1, hipMemcpyDeviceToHost)); return read_block(h, total, last); }
+int pass_done(wfs_handle *h) { HIPCHK(hipStreamSynchronize(h->stream)); HIPCHK(hipGetLastError()); CHECK_LAUNCHES(); return WFS_OK; }
 
 // A step boundary: on return *h->h_scal is the device scalar block as of this point of the stream.  By default k_publish writes
 // it into the mapped host copy and the host spins on the sequence word (no copy command, no wake-up through the runtime's signal);
@@ -1928,22 +1976,6 @@ static int gen_afterpulses(wfs_handle *h, GenRun &r)
     return WFS_OK;
 }
 
-static int order_ranges(wfs_handle *h, const OrderArgs &oa);
-
-// ---- generation 5: every tile of the block generator into generation order (k_tile_order): the order the reference's Pulse call sees
-static int gen_order(wfs_handle *h, GenRun &r)
-{
-    const WfsDev &d = h->dev;
-    const i64 T = h->batch.n_tiles, P = r.P, TP = r.TP;
-    const bool ap_on = r.ap_on;
-    TRY(ensure(h, h->order_list, (size_t)T * 2)); TRY(ensure(h, h->order_list2, (size_t)T * 2));
-    OrderArgs oa{T, TP, h->tile_count.p(), h->tile_off.p(), h->ph.p(), h->ph_idx.p(),
-                 ap_on ? h->ph_gain.p() : nullptr, P + h->run.p_fused, h->order_list.p(), h->order_list2.p(), h->scal.p(),
-                 (h->run.fuse_on && n_tilegen_tiles(h) > 0) ? h->ins_fused.p() : nullptr, d.n_tpc,
-                 h->tile_cursor.p(), h->tile_tailbase.p(), h->ins_fullsort.p(), h->set_ins_off.p(), h->set_ins_list.p()};
-    return order_ranges(h, oa);
-}
-
 // the order pass over the tiles oa describes: scan, then every listed range by the kernel of its class
 static int order_ranges(wfs_handle *h, const OrderArgs &oa)
 {
@@ -1972,15 +2004,26 @@ static int order_ranges(wfs_handle *h, const OrderArgs &oa)
                          h->huge_keys.p(), h->huge_vals.p(), h->huge_rec.p(), h->huge_gain.p()};
         Timer t(h, "k_tile_order_huge");
         TRY(launch_untimed(h, PLAIN(k_order_huge_pack), per_thread(tot), ha));
-        size_t bytes = 0;
-        HIPCHK(rocprim::segmented_radix_sort_pairs(nullptr, bytes, h->huge_keys.p(), h->huge_keys2.p(), h->huge_vals.p(), h->huge_vals2.p(),
-                                                   (unsigned)tot, (unsigned)n_huge, h->huge_cbeg.p(), h->huge_cbeg.p() + 1, 0u, 32u, h->stream));
-        TRY(ensure(h, h->sort_tmp, bytes));
-        HIPCHK(rocprim::segmented_radix_sort_pairs(h->sort_tmp.p, bytes, h->huge_keys.p(), h->huge_keys2.p(), h->huge_vals.p(), h->huge_vals2.p(),
-                                                   (unsigned)tot, (unsigned)n_huge, h->huge_cbeg.p(), h->huge_cbeg.p() + 1, 0u, 32u, h->stream));
+        TRY(two_step(h, "tile order sort", [&](void *tmp, size_t &bytes) {
+            return rocprim::segmented_radix_sort_pairs(tmp, bytes, h->huge_keys.p(), h->huge_keys2.p(), h->huge_vals.p(), h->huge_vals2.p(),
+                                                       (unsigned)tot, (unsigned)n_huge, h->huge_cbeg.p(), h->huge_cbeg.p() + 1, 0u, 32u, h->stream); }));
         TRY(launch_untimed(h, PLAIN(k_order_huge_apply), per_thread(tot), ha, h->huge_keys2.p(), h->huge_vals2.p(), h->ph.p(), h->ph_idx.p(), oa.ph_gain));
     }
     return WFS_OK;
+}
+
+// ---- generation 5: every tile of the block generator into generation order (k_tile_order): the order the reference's Pulse call sees
+static int gen_order(wfs_handle *h, GenRun &r)
+{
+    const WfsDev &d = h->dev;
+    const i64 T = h->batch.n_tiles, P = r.P, TP = r.TP;
+    const bool ap_on = r.ap_on;
+    TRY(ensure(h, h->order_list, (size_t)T * 2)); TRY(ensure(h, h->order_list2, (size_t)T * 2));
+    OrderArgs oa{T, TP, h->tile_count.p(), h->tile_off.p(), h->ph.p(), h->ph_idx.p(),
+                 ap_on ? h->ph_gain.p() : nullptr, P + h->run.p_fused, h->order_list.p(), h->order_list2.p(), h->scal.p(),
+                 (h->run.fuse_on && n_tilegen_tiles(h) > 0) ? h->ins_fused.p() : nullptr, d.n_tpc,
+                 h->tile_cursor.p(), h->tile_tailbase.p(), h->ins_fullsort.p(), h->set_ins_off.p(), h->set_ins_list.p()};
+    return order_ranges(h, oa);
 }
 
 static int run_generation(wfs_handle *h, FillGroup &fg)
@@ -2401,24 +2444,8 @@ static int run_records(wfs_handle *h, RunState &r)
     if (h->rec_pending[h->rec_cur]) { HIPCHK(hipEventSynchronize(h->rec_copied[h->rec_cur])); h->rec_pending[h->rec_cur] = false; }
     TRY(ensure_rows(h, h->records_buf(), (size_t)h->run.n_records * WFS_RECORD_BYTES, "the records"));
     za.rec_off = h->rec_off.p(); za.records = h->records_buf().as<uint8_t>(); za.rec_capacity = h->run.n_records;
-    if (h->sort_records && h->run.n_records > 1 && h->run.n_active_rows > 0) {
-        // records by (time, channel): keys per record, one radix sort of the batch, k_pack writes to the sorted slots
-        const i64 NR = h->run.n_records;
-        if (NR > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "more than 2^31 records in one batch (the device sort takes an int count)");
-        TRY(ensure(h, h->rec_key, (size_t)NR)); TRY(ensure(h, h->rec_key2, (size_t)NR));
-        TRY(ensure(h, h->rec_val, (size_t)NR)); TRY(ensure(h, h->rec_val2, (size_t)NR)); TRY(ensure(h, h->rec_dest, (size_t)NR));
-        za.rec_key = h->rec_key.p(); za.rec_val = h->rec_val.p();
-        TRY(launch(h, PLAIN(k_rec_keys), per_wave(h->run.n_active_rows), d, za));
-        // rocPRIM's radix sort, over the key bits that are in use only: (samples the batch spans) << 12 | channel
-        unsigned end_bit = 13;
-        { const u64 span = (u64)std::max<i64>(h->h_scal->key_end - h->h_scal->key_origin, 1); while (end_bit < 64 && ((span << 12) >> end_bit) != 0) end_bit++; }
-        size_t bytes = 0;
-        HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, h->rec_key.p(), h->rec_key2.p(), h->rec_val.p(), h->rec_val2.p(), (size_t)NR, 0u, end_bit, h->stream));
-        TRY(ensure(h, h->sort_tmp, bytes));
-        { Timer t(h, "record_sort"); HIPCHK(rocprim::radix_sort_pairs(h->sort_tmp.p, bytes, h->rec_key.p(), h->rec_key2.p(), h->rec_val.p(), h->rec_val2.p(), (size_t)NR, 0u, end_bit, h->stream)); }
-        TRY(launch(h, PLAIN(k_invert_perm), per_thread(NR), h->rec_val2.p(), h->rec_dest.p(), NR));
-        za.rec_dest = h->rec_dest.p();
-    }
+    if (h->sort_records && h->run.n_records > 1 && h->run.n_active_rows > 0)      // records by (time, channel): the packers write to the sorted slots
+        TRY(order_records(h, h->rec, za, h->run.n_active_rows, h->run.n_records, h->h_scal->key_origin, h->h_scal->key_end, "more than 2^31 records in one batch (the device sort takes an int count)", "record_sort"));
     if (h->run.n_active_rows > 0 && h->run.n_records > 0) {
         TRY(ensure(h, h->pack_desc, (size_t)h->run.n_active_rows)); za.pdesc = h->pack_desc.p();
         // Nothing wfs_run returns depends on the packers: they go to the pack stream, behind everything on the main stream up to here,
@@ -2430,11 +2457,8 @@ static int run_records(wfs_handle *h, RunState &r)
             HIPCHK(hipStreamWaitEvent(h->pack_stream, h->pack_go[h->rec_cur], 0));
             ps = h->pack_stream;
         }
-        TRY(launch(h, PLAIN(k_pack_desc), per_thread(h->run.n_active_rows).on(ps), za));
-        if (const i64 n_fin_rows = h->run.n_res_rows + n_empty_rows(h); n_fin_rows > 0) {      // rows that exist as finished samples: resident, without a pulse
-            PackResArgs pr{h->pack_desc.p() + h->run.n_front_rows, h->fin.p(), za.itv_left, za.itv_right, za.records, za.rec_dest, za.rec_capacity, n_fin_rows, za.spr, (i32)d.dt};
-            TRY(launch(h, PLAIN(k_pack_res), per_wave(n_fin_rows).on(ps), pr));
-        }
+        // (rows that exist as finished samples: resident, without a pulse; behind the front rows of the list)
+        TRY(pack_finished_rows(h, za, h->run.n_active_rows, h->fin.p(), h->run.n_front_rows, h->run.n_res_rows + n_empty_rows(h), ps));
         if (h->run.n_front_rows > 0) {
             TRY(launch(h, K_PACK(r.noise_kind, r.dark), per_wave(h->run.n_front_rows).on(ps), d, za));
         }
@@ -3047,132 +3071,121 @@ static int lone_windows(wfs_handle *h, std::vector<i64> &wl, std::vector<i64> &w
     return WFS_OK;
 }
 
+// What crosses the stage boundaries of one wfs_lone_hits (on its stack).
+struct LoneRun {
+    LoneArgs a{}; ZleArgs za{}; WfsScal sc{}; i64 NK = 0, NR = 0, NREC = 0;      // (sc: the pass's counter block as last read; seeds, lone rows, records)
+    bool photons = false, noise_hits = false; int kind = 0, noise_ch = 0;       // the seeds: dark photons, noise hits; the nk axis; PMT channels inside the model (noise hits)
+};
+
+// ---- lone 1: the seeds -- the windows of the run, the scans into a list (once more with room when it overflowed), the sort by (channel, start, kind)
+static int lone_seeds(wfs_handle *h, LoneRun &r)
+{
+    const WfsDev &d = h->dev; auto &L = h->lone; LoneArgs &a = r.a;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    std::vector<i64> wl, wr; std::vector<i32> wg; TRY(lone_windows(h, wl, wr, wg));
+    if (h->pack.must_wait()) HIPCHK(hipStreamWaitEvent(h->stream, h->rec_ready[h->pack.arena], 0));      // behind the batch's packers (the fence state stays as it is)
+    TRY(upload(h, L.win_l, wl.data(), wl.size())); TRY(upload(h, L.win_r, wr.data(), wr.size())); TRY(upload(h, L.win_g, wg.data(), wg.size()));
+    TRY(ensure(h, L.scal, 1)); a.scal = L.scal.p();
+    a.a0 = a.s0 - lone_gap(d.tlen, d.tw); a.m0 = lone_first_cell(a.a0, d.samples_before); a.n_cells = lone_last_cell(a.s_limit, d.samples_before) - a.m0 + 1;
+    a.n_blocks = r.noise_hits ? lone_noise_blocks(a.a0, a.s_limit) : 0;
+    a.n_win = (i64)wl.size(); a.win_l = L.win_l.p(); a.win_r = L.win_r.p(); a.win_g = L.win_g.p(); a.row_lo = h->row_lo.p(); a.row_hi = h->row_hi.p();
+    // the list: twice the expected photons of the scanned cells and room for a small pass; a pass that finds more is scanned again with
+    // room (the number of noise hits cannot be had from the model cheaply: they come out of that room or out of the second scan)
+    double expect = 0;
+    for (int c = 0; c < h->dark.channels; c++) expect += (double)h->dark.thr[(size_t)c * DK_MAX] / 4294967296.0 * 1.2 * (double)a.n_cells;
+    i64 cap = (i64)(2.0 * expect) + 4096;
+    for (int attempt = 0; ; attempt++) {
+        TRY(ensure_each(h, (size_t)cap, L.keys, L.keys2));
+        a.keys = L.keys.p(); a.key_cap = cap;
+        HIPCHK(hipMemsetAsync(L.scal.p(), 0, sizeof(WfsScal), h->stream));
+        const i64 nb = (a.n_cells + LONE_SCAN_CELLS - 1) / LONE_SCAN_CELLS;
+        if (nb > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "wfs_lone_hits: lone hits: a pass of more than 2^39 cells per channel, split it");
+        if (r.photons) TRY(launch(h, PLAIN(k_lone_scan), Shape(dim3((unsigned)nb, (unsigned)h->dark.channels), dim3(LONE_SCAN_CELLS)), d, a));
+        if (r.noise_hits && r.noise_ch > 0 && a.n_blocks > 0)
+            TRY(launch(h, K_LONE_NOISE_SCAN(r.kind - (int)NOISE_MODEL, r.photons), Shape(dim3((unsigned)((a.n_blocks + 3) / 4), (unsigned)r.noise_ch), dim3(256)), d, a));
+        TRY(read_block(h, r.sc, L.scal.p()));
+        if (r.sc.n_lone_seeds <= cap) break;
+        if (attempt > 0) return h->fail(WFS_E_STATE, "wfs_lone_hits: internal: the seed list overflowed twice");
+        cap = r.sc.n_lone_seeds;
+    }
+    const i64 NK = r.NK = a.n_keys = r.sc.n_lone_seeds; if (NK == 0) return WFS_OK;
+    if (NK > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "wfs_lone_hits: lone hits: more than 2^31 seeds (lone photons and noise hits) in one pass, split it");
+    const unsigned end_bit = lone_key_end_bit(std::max(h->dark.channels, r.noise_ch));      // the key bits in use: of the channels that can have a seed
+    TRY(two_step(h, "seed sort", [&](void *tmp, size_t &bytes) { return rocprim::radix_sort_keys(tmp, bytes, L.keys.p(), L.keys2.p(), (size_t)NK, 0u, end_bit, h->stream); }));
+    a.keys = L.keys2.p();
+    return WFS_OK;
+}
+
+// ---- lone 2: the rows -- chains of seeds, their places, descriptors and listing, and (k_row_empty: from there on like a batch's rows without a pulse) samples and intervals
+static int lone_rows(wfs_handle *h, LoneRun &r)
+{
+    const WfsDev &d = h->dev; auto &L = h->lone; LoneArgs &a = r.a; ZleArgs &za = r.za; const i64 NK = r.NK;
+    TRY(ensure_each(h, (size_t)NK, L.flag, L.cap, L.flen));
+    a.flag = L.flag.p(); a.cap = L.cap.p(); a.flen = L.flen.p();
+    TRY(launch(h, PLAIN(k_lone_rows), per_thread(NK), d, a));
+    TRY(scan(h, L.flag.p(), NK, L.row_of, &WfsScal::n_lone_rows, L.scal.p()));
+    TRY(scan(h, L.cap.p(), NK, L.itv_off, &WfsScal::n_itv_slots, L.scal.p()));
+    TRY(scan(h, L.flen.p(), NK, L.fin_off, &WfsScal::n_empty_samples, L.scal.p()));
+    TRY(read_block(h, r.sc, L.scal.p()));
+    if (r.sc.lone_error) return h->fail(WFS_E_CAPACITY, "wfs_lone_hits: lone hits: a lone row of more than 2^19 samples (a chain of dark photons that long, or with noise hits on a baseline that stays across the threshold: lower the rate, the threshold or s_limit)");
+    const i64 NR = r.NR = r.sc.n_lone_rows;
+    if (NR > LONE_MAX_ROWS) return h->fail(WFS_E_CAPACITY, "wfs_lone_hits: lone hits: more than 2^24 lone rows in one pass, split it");
+    if (NR == 0) return WFS_OK;
+    TRY(ensure_each(h, (size_t)NR, L.desc, L.pdesc, L.out_channel, L.out_nph, L.out_nnz, L.out_left, L.out_right, L.out_ixr));
+    TRY(ensure_each(h, (size_t)r.sc.n_itv_slots + 2, L.itv_left, L.itv_right));
+    TRY(ensure_each(h, (size_t)NR, L.itv_n, L.row_nrec));
+    TRY(ensure(h, L.fin, (size_t)r.sc.n_empty_samples + 8));
+    FillGroup fg(h, "fills_lone");
+    TRY(fg.zero(L.itv_n.p(), NR)); TRY(fg.zero(L.row_nrec.p(), NR));
+    TRY(fg.fill(&L.scal.p()->key_origin, 1, I64_MAX)); TRY(fg.fill(&L.scal.p()->key_end, 1, I64_MIN));
+    TRY(fg.flush());
+    a.row_of = L.row_of.p(); a.itv_off = L.itv_off.p(); a.fin_off = L.fin_off.p();
+    a.out_channel = L.out_channel.p(); a.out_nph = L.out_nph.p(); a.out_nnz = L.out_nnz.p(); a.out_left = L.out_left.p(); a.out_right = L.out_right.p(); a.out_ixr = L.out_ixr.p();
+    TRY(launch(h, PLAIN(k_lone_desc), per_thread(NK), d, a, L.desc.p()));
+    za.n_active_rows = NR; za.desc = L.desc.p(); za.fin = L.fin.p(); za.itv_left = L.itv_left.p(); za.itv_right = L.itv_right.p();
+    za.itv_n = L.itv_n.p(); za.row_nrec = L.row_nrec.p(); za.spr = WFS_SPR; za.key_base = L.scal.p(); za.pdesc = L.pdesc.p();
+    return launch(h, K_ROW_EMPTY(r.kind, r.photons), per_wave(NR), d, za, (i64)0, NR);
+}
+
+// ---- lone 3: the records -- how many, their order by (time, channel) and the packers, as run_records has them for the rows of a batch
+static int lone_records(wfs_handle *h, LoneRun &r)
+{
+    auto &L = h->lone; ZleArgs &za = r.za;
+    TRY(scan(h, L.row_nrec.p(), r.NR, L.rec_off, &WfsScal::n_records, L.scal.p()));
+    TRY(read_block(h, r.sc, L.scal.p()));
+    const i64 NREC = r.NREC = r.sc.n_records; L.n_rows = r.NR;
+    if (NREC == 0) return WFS_OK;
+    za.rec_off = L.rec_off.p(); za.rec_capacity = NREC;
+    // (the order comes in front of the record arena: its count check is what a pass of too many records meets, whatever memory there is)
+    if (NREC > 1) TRY(order_records(h, L.rec, za, r.NR, NREC, r.sc.key_origin, r.sc.key_end, "wfs_lone_hits: lone hits: more than 2^31 records in one pass, split it"));
+    TRY(ensure(h, L.records_buf(), (size_t)NREC * WFS_RECORD_BYTES)); za.records = L.records_buf().as<uint8_t>();
+    return pack_finished_rows(h, za, r.NR, L.fin.p(), 0, r.NR, h->stream);
+}
+
 int wfs_lone_hits(wfs_handle *h, int64_t s0, int64_t s1, int64_t s_limit, int64_t *n_records)
 try {
     if (!h) return WFS_E_INVALID;
     if (!h->dark.set() && !h->lone.noise_hits) return h->fail(WFS_E_STATE, "wfs_lone_hits: no dark-count rates are set");
     if (!h->tables_set) return h->fail(WFS_E_STATE, "wfs_lone_hits: tables not set");
     if (!n_records) return h->fail(WFS_E_INVALID, "wfs_lone_hits: null n_records");
-    const WfsDev &d = h->dev;
-    auto &L = h->lone;
-    const bool photons = h->dark.set(), noise_hits = L.noise_hits;
-    const int kind = d.enable_noise ? (int)noise_kind_of(d) : (int)NOISE_NONE;
-    if (noise_hits && kind < (int)NOISE_MODEL) return h->fail(WFS_E_STATE, "wfs_lone_hits: noise hits are on without a drawn noise model");
-    const int noise_ch = noise_hits ? std::min((int)d.noise_channels, (int)d.n_tpc) : 0;      // PMT channels inside the model
+    const WfsDev &d = h->dev; auto &L = h->lone; LoneRun r;
+    r.photons = h->dark.set(); r.noise_hits = L.noise_hits;
+    r.kind = d.enable_noise ? (int)noise_kind_of(d) : (int)NOISE_NONE;
+    if (r.noise_hits && r.kind < (int)NOISE_MODEL) return h->fail(WFS_E_STATE, "wfs_lone_hits: noise hits are on without a drawn noise model");
+    r.noise_ch = r.noise_hits ? std::min((int)d.noise_channels, (int)d.n_tpc) : 0;
     std::string err;
     if (const int bad = lone_check(s0, s1, s_limit, h->dark.channels, d.tlen, d.tw, d.samples_before, err)) return h->fail(bad == 1 ? WFS_E_INVALID : WFS_E_CAPACITY, err);
-    if (noise_hits) if (const int bad = lone_noise_check(s0, s_limit, d.tlen, d.tw, err)) return h->fail(bad == 1 ? WFS_E_INVALID : WFS_E_CAPACITY, err);
-    HIPCHK(hipSetDevice(h->device));
-    L.n_rows = 0; L.n_records = 0; *n_records = 0;
+    if (r.noise_hits) if (const int bad = lone_noise_check(s0, s_limit, d.tlen, d.tw, err)) return h->fail(bad == 1 ? WFS_E_INVALID : WFS_E_CAPACITY, err);
+    HIPCHK(hipSetDevice(h->device)); L.n_rows = 0; L.n_records = 0; *n_records = 0;
     if (s1 == s0) return WFS_OK;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    std::vector<i64> wl, wr; std::vector<i32> wg;
-    TRY(lone_windows(h, wl, wr, wg));
-    if (h->pack.must_wait()) HIPCHK(hipStreamWaitEvent(h->stream, h->rec_ready[h->pack.arena], 0));      // behind the batch's packers (the fence state stays as it is)
-    TRY(upload(h, L.win_l, wl.data(), wl.size())); TRY(upload(h, L.win_r, wr.data(), wr.size())); TRY(upload(h, L.win_g, wg.data(), wg.size()));
-    TRY(ensure(h, L.scal, 1));
-    LoneArgs a{};
-    a.s0 = s0; a.s1 = s1; a.s_limit = s_limit; a.a0 = s0 - lone_gap(d.tlen, d.tw);
-    a.m0 = lone_first_cell(a.a0, d.samples_before); a.n_cells = lone_last_cell(s_limit, d.samples_before) - a.m0 + 1;
-    a.n_blocks = noise_hits ? lone_noise_blocks(a.a0, s_limit) : 0;
-    a.n_win = (i64)wl.size(); a.win_l = L.win_l.p(); a.win_r = L.win_r.p(); a.win_g = L.win_g.p(); a.row_lo = h->row_lo.p(); a.row_hi = h->row_hi.p();
-    a.scal = L.scal.p();
-    // the list: twice the expected photons of the scanned cells and room for a small pass; a pass that finds more is scanned again with
-    // room (the number of noise hits cannot be had from the model cheaply: they come out of that room or out of the second scan)
-    double expect = 0;
-    for (int c = 0; c < h->dark.channels; c++) expect += (double)h->dark.thr[(size_t)c * DK_MAX] / 4294967296.0 * 1.2 * (double)a.n_cells;
-    i64 cap = (i64)(2.0 * expect) + 4096;
-    WfsScal sc{};
-    for (int attempt = 0; ; attempt++) {
-        TRY(ensure(h, L.keys, (size_t)cap)); TRY(ensure(h, L.keys2, (size_t)cap));
-        a.keys = L.keys.p(); a.key_cap = cap;
-        HIPCHK(hipMemsetAsync(L.scal.p(), 0, sizeof(WfsScal), h->stream));
-        const i64 nb = (a.n_cells + LONE_SCAN_CELLS - 1) / LONE_SCAN_CELLS;
-        if (nb > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "wfs_lone_hits: lone hits: a pass of more than 2^39 cells per channel, split it");
-        if (photons) TRY(launch(h, PLAIN(k_lone_scan), Shape(dim3((unsigned)nb, (unsigned)h->dark.channels), dim3(LONE_SCAN_CELLS)), d, a));
-        if (noise_hits && noise_ch > 0 && a.n_blocks > 0)
-            TRY(launch(h, K_LONE_NOISE_SCAN(kind - (int)NOISE_MODEL, photons), Shape(dim3((unsigned)((a.n_blocks + 3) / 4), (unsigned)noise_ch), dim3(256)), d, a));
-        TRY(copy_async(h, &sc, L.scal.p(), 1, hipMemcpyDeviceToHost));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (sc.n_lone_seeds <= cap) break;
-        if (attempt > 0) return h->fail(WFS_E_STATE, "wfs_lone_hits: internal: the seed list overflowed twice");
-        cap = sc.n_lone_seeds;
-    }
-    const i64 NK = a.n_keys = sc.n_lone_seeds;
-    if (NK == 0) return WFS_OK;
-    if (NK > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "wfs_lone_hits: lone hits: more than 2^31 seeds (lone photons and noise hits) in one pass, split it");
-    {   // by (channel, start, kind): rocPRIM's radix sort over the key bits in use
-        const u64 n_ch = (u64)std::max(h->dark.channels, noise_ch);
-        unsigned end_bit = LONE_KEY_SHIFT; while (end_bit < 64 && (n_ch >> (end_bit - LONE_KEY_SHIFT)) != 0) end_bit++;
-        size_t bytes = 0;
-        HIPCHK(rocprim::radix_sort_keys(nullptr, bytes, L.keys.p(), L.keys2.p(), (size_t)NK, 0u, end_bit, h->stream));
-        TRY(ensure(h, L.sort_tmp, bytes));
-        HIPCHK(rocprim::radix_sort_keys(L.sort_tmp.p, bytes, L.keys.p(), L.keys2.p(), (size_t)NK, 0u, end_bit, h->stream));
-        a.keys = L.keys2.p();
-    }
-    TRY(ensure(h, L.flag, (size_t)NK)); TRY(ensure(h, L.cap, (size_t)NK)); TRY(ensure(h, L.flen, (size_t)NK));
-    a.flag = L.flag.p(); a.cap = L.cap.p(); a.flen = L.flen.p();
-    TRY(launch(h, PLAIN(k_lone_rows), per_thread(NK), d, a));
-    TRY(scan(h, L.flag.p(), NK, L.row_of, &WfsScal::n_lone_rows, L.scal.p()));
-    TRY(scan(h, L.cap.p(), NK, L.itv_off, &WfsScal::n_itv_slots, L.scal.p()));
-    TRY(scan(h, L.flen.p(), NK, L.fin_off, &WfsScal::n_empty_samples, L.scal.p()));
-    TRY(copy_async(h, &sc, L.scal.p(), 1, hipMemcpyDeviceToHost));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (sc.lone_error) return h->fail(WFS_E_CAPACITY, "wfs_lone_hits: lone hits: a lone row of more than 2^19 samples (a chain of dark photons that long, or with noise hits on a baseline that stays across the threshold: lower the rate, the threshold or s_limit)");
-    const i64 NR = sc.n_lone_rows;
-    if (NR > LONE_MAX_ROWS) return h->fail(WFS_E_CAPACITY, "wfs_lone_hits: lone hits: more than 2^24 lone rows in one pass, split it");
-    if (NR == 0) return WFS_OK;
-    TRY(ensure(h, L.desc, (size_t)NR)); TRY(ensure(h, L.pdesc, (size_t)NR));
-    TRY(ensure(h, L.out_channel, (size_t)NR)); TRY(ensure(h, L.out_nph, (size_t)NR)); TRY(ensure(h, L.out_nnz, (size_t)NR)); TRY(ensure(h, L.out_left, (size_t)NR)); TRY(ensure(h, L.out_right, (size_t)NR)); TRY(ensure(h, L.out_ixr, (size_t)NR));
-    TRY(ensure(h, L.itv_left, (size_t)sc.n_itv_slots + 2)); TRY(ensure(h, L.itv_right, (size_t)sc.n_itv_slots + 2));
-    TRY(ensure(h, L.itv_n, (size_t)NR)); TRY(ensure(h, L.row_nrec, (size_t)NR));
-    TRY(ensure(h, L.fin, (size_t)sc.n_empty_samples + 8));
-    {
-        FillGroup fg(h, "fills_lone");
-        TRY(fg.zero(L.itv_n.p(), NR)); TRY(fg.zero(L.row_nrec.p(), NR));
-        TRY(fg.fill(&L.scal.p()->key_origin, 1, I64_MAX)); TRY(fg.fill(&L.scal.p()->key_end, 1, I64_MIN));
-        TRY(fg.flush());
-    }
-    a.row_of = L.row_of.p(); a.itv_off = L.itv_off.p(); a.fin_off = L.fin_off.p();
-    a.out_channel = L.out_channel.p(); a.out_nph = L.out_nph.p(); a.out_nnz = L.out_nnz.p(); a.out_left = L.out_left.p(); a.out_right = L.out_right.p(); a.out_ixr = L.out_ixr.p();
-    TRY(launch(h, PLAIN(k_lone_desc), per_thread(NK), d, a, L.desc.p()));
-    // from here on the row list goes the way of a batch's rows without a pulse: k_row_empty (dark counts on where rates are set), the record scan, the
-    // keys and the sort by (time, channel), k_pack_desc, k_pack_res
-    ZleArgs za{};
-    za.n_active_rows = NR; za.desc = L.desc.p(); za.fin = L.fin.p(); za.itv_left = L.itv_left.p(); za.itv_right = L.itv_right.p();
-    za.itv_n = L.itv_n.p(); za.row_nrec = L.row_nrec.p(); za.spr = WFS_SPR; za.key_base = L.scal.p(); za.pdesc = L.pdesc.p();
-    TRY(launch(h, K_ROW_EMPTY(kind, photons), per_wave(NR), d, za, (i64)0, NR));
-    TRY(scan(h, L.row_nrec.p(), NR, L.rec_off, &WfsScal::n_records, L.scal.p()));
-    TRY(copy_async(h, &sc, L.scal.p(), 1, hipMemcpyDeviceToHost));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    const i64 NREC = sc.n_records;
-    L.n_rows = NR;
-    if (NREC > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "wfs_lone_hits: lone hits: more than 2^31 records in one pass, split it");
-    if (NREC > 0) {
-        TRY(ensure(h, L.records_buf(), (size_t)NREC * WFS_RECORD_BYTES));
-        za.rec_off = L.rec_off.p(); za.records = L.records_buf().as<uint8_t>(); za.rec_capacity = NREC;
-        if (NREC > 1) {
-            TRY(ensure(h, L.rec_key, (size_t)NREC)); TRY(ensure(h, L.rec_key2, (size_t)NREC));
-            TRY(ensure(h, L.rec_val, (size_t)NREC)); TRY(ensure(h, L.rec_val2, (size_t)NREC)); TRY(ensure(h, L.rec_dest, (size_t)NREC));
-            za.rec_key = L.rec_key.p(); za.rec_val = L.rec_val.p();
-            TRY(launch(h, PLAIN(k_rec_keys), per_wave(NR), d, za));
-            unsigned end_bit = 13;
-            { const u64 span = (u64)std::max<i64>(sc.key_end - sc.key_origin, 1); while (end_bit < 64 && ((span << 12) >> end_bit) != 0) end_bit++; }
-            size_t bytes = 0;
-            HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, L.rec_key.p(), L.rec_key2.p(), L.rec_val.p(), L.rec_val2.p(), (size_t)NREC, 0u, end_bit, h->stream));
-            TRY(ensure(h, L.sort_tmp, bytes));
-            HIPCHK(rocprim::radix_sort_pairs(L.sort_tmp.p, bytes, L.rec_key.p(), L.rec_key2.p(), L.rec_val.p(), L.rec_val2.p(), (size_t)NREC, 0u, end_bit, h->stream));
-            TRY(launch(h, PLAIN(k_invert_perm), per_thread(NREC), L.rec_val2.p(), L.rec_dest.p(), NREC));
-            za.rec_dest = L.rec_dest.p();
-        }
-        TRY(launch(h, PLAIN(k_pack_desc), per_thread(NR), za));
-        PackResArgs pr{L.pdesc.p(), L.fin.p(), za.itv_left, za.itv_right, za.records, za.rec_dest, za.rec_capacity, NR, za.spr, (i32)d.dt};
-        TRY(launch(h, PLAIN(k_pack_res), per_wave(NR), pr));
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipGetLastError());
-    CHECK_LAUNCHES();
-    L.n_records = NREC; *n_records = NREC;
+    r.a.s0 = s0; r.a.s1 = s1; r.a.s_limit = s_limit;
+    TRY(lone_seeds(h, r));
+    if (r.NK == 0) return WFS_OK;
+    TRY(lone_rows(h, r));
+    if (r.NR == 0) return WFS_OK;
+    TRY(lone_records(h, r));
+    TRY(pass_done(h));
+    L.n_records = r.NREC; *n_records = r.NREC;
     return WFS_OK;
 } WFS_CATCH(h)
 
@@ -3216,31 +3229,98 @@ try {
 // The overlay pass (wfs_overlay.h): the records of two streams merged per channel into one valid stream in (time, channel)
 // order.  A: sim_host, or the records of the last wfs_run where they lie; B: bg_host.  Everything the pass writes is a buffer of
 // wfs_handle::overlay; of the run it reads the record arena alone.  The work goes to the main stream behind the batch's packers.
-extern "C++" {
-template <class K, class V> static int overlay_sort(wfs_handle *h, K *k_in, K *k_out, V *v_in, V *v_out, i64 n, int bits)
+// What crosses the stage boundaries of one wfs_overlay_records (on its stack); records, pulses, merged pulses, output records: a's n, n_pulses, n_merged, n_out
+struct OverlayRun { OverlayArgs a{}; OverlayScal sc{}; int key_bits = 0; };      // (sc: the counter block as last read; key_bits: of the record and pulse keys)
+static int overlay_invalid(wfs_handle *h, const OverlayRun &r)
 {
-    size_t bytes = 0;
-    HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, k_in, k_out, v_in, v_out, (size_t)n, 0u, (unsigned)bits, h->stream));
-    TRY(ensure(h, h->overlay.sort_tmp, bytes));
-    HIPCHK(rocprim::radix_sort_pairs(h->overlay.sort_tmp.p, bytes, k_in, k_out, v_in, v_out, (size_t)n, 0u, (unsigned)bits, h->stream));
+    const i64 i = (i64)(r.sc.first_bad >> 8);
+    return h->fail(WFS_E_INVALID, std::string("wfs_overlay_records: ") + (i < r.a.n_a ? "simulated record " + std::to_string(i) : "background record " + std::to_string(i - r.a.n_a)) + ": " +
+                   ov_bad_name((int)(r.sc.first_bad & 0xffu)) + " (" + std::to_string(r.sc.n_bad) + " records in all)");
+}
+// ---- overlay 1: the two streams and the recorded baselines on the device, every record checked on its own (k_ov_check), the key bits
+static int overlay_load(wfs_handle *h, OverlayRun &r, const void *sim_host, const void *bg_host, const int32_t *bg_baseline)
+{
+    auto &O = h->overlay; OverlayArgs &a = r.a;
+    if (h->pack.must_wait()) HIPCHK(hipStreamWaitEvent(h->stream, h->rec_ready[h->pack.arena], 0));      // behind the batch's packers (the fence state stays as it is)
+    if (sim_host) { TRY(upload(h, O.src_a, (const u32 *)sim_host, (size_t)a.n_a * REC_DWORDS)); a.src_a = O.src_a.p(); }
+    else a.src_a = (const u32 *)h->records_buf().p;
+    TRY(upload(h, O.src_b, (const u32 *)bg_host, (size_t)(a.n - a.n_a) * REC_DWORDS)); a.src_b = O.src_b.p();
+    std::vector<i32> base((size_t)a.n_rows, a.baseline);
+    if (bg_baseline) base.assign(bg_baseline, bg_baseline + a.n_rows);
+    TRY(upload(h, O.base, base.data(), base.size())); a.base = O.base.p();
+    HIPCHK(hipStreamSynchronize(h->stream));                // (the copy reads host memory that is a local)
+    TRY(ensure(h, O.scal, 1)); a.scal = O.scal.p();
+    r.sc = OverlayScal{}; r.sc.smin = I64_MAX; r.sc.smax = I64_MIN; r.sc.first_bad = ~0ull;
+    TRY(copy_async(h, O.scal.p(), &r.sc, 1, hipMemcpyHostToDevice));
+    HIPCHK(hipStreamSynchronize(h->stream));                // (sc is written below)
+    TRY(launch(h, PLAIN(k_ov_check), per_thread(a.n), a));
+    TRY(read_block(h, r.sc, O.scal.p()));
+    if (r.sc.n_bad) return overlay_invalid(h, r);
+    a.smin = r.sc.smin; a.bits.sbits = ov_bits_of((u64)r.sc.smax - (u64)r.sc.smin + 1ull); a.bits.chbits = ov_bits_of((u64)std::max(a.n_rows - 1, 1));
+    if (!ov_bits_fit(a.bits)) return h->fail(WFS_E_CAPACITY, "wfs_overlay_records: overlay: the records span more samples than the sort keys hold beside the channel (2^" + std::to_string(63 - a.bits.chbits) + "), split the pass");
+    r.key_bits = a.bits.sbits + a.bits.chbits + 1; return WFS_OK;
+}
+
+// ---- overlay 2: records to pulses -- the records by (stream, channel, time), each against the one in front (k_ov_valid), a pulse per first fragment
+static int overlay_pulses(wfs_handle *h, OverlayRun &r)
+{
+    auto &O = h->overlay; OverlayArgs &a = r.a; const i64 N = a.n;
+    TRY(ensure_each(h, (size_t)N, O.key, O.key2, O.val, O.val2, O.flag, O.pulse_of));
+    a.key = O.key.p(); a.val = O.val.p();
+    TRY(launch(h, PLAIN(k_ov_keys), per_thread(N), a));
+    TRY(sort_pairs(h, "overlay record sort", O.key.p(), O.key2.p(), O.val.p(), O.val2.p(), N, (unsigned)r.key_bits));
+    a.key = O.key2.p(); a.val = O.val2.p(); a.flag = O.flag.p();
+    TRY(launch(h, PLAIN(k_ov_valid), per_thread(N), a));
+    TRY(scan_inclusive(h, "overlay pulse scan", O.flag.p(), O.pulse_of.p(), N, rocprim::plus<i32>()));
+    a.pulse_of = O.pulse_of.p(); i32 n_pulses = 0;
+    TRY(read_block(h, r.sc, O.scal.p(), n_pulses, O.pulse_of.p() + (N - 1)));
+    if (r.sc.n_bad) return overlay_invalid(h, r);
+    if ((a.n_pulses = n_pulses) <= 0) return h->fail(WFS_E_STATE, "wfs_overlay_records: internal: valid records without a pulse");
     return WFS_OK;
 }
-template <class T, class Op> static int overlay_scan(wfs_handle *h, const T *in, T *out, i64 n, Op op)
+
+// ---- overlay 3: pulses to merged pulses -- the pulses by (channel, start, stream), the running maximum of their ends, a merged pulse per head
+static int overlay_merge(wfs_handle *h, OverlayRun &r)
 {
-    size_t bytes = 0;
-    HIPCHK(rocprim::inclusive_scan(nullptr, bytes, in, out, (size_t)n, op, h->stream));
-    TRY(ensure(h, h->overlay.sort_tmp, bytes));
-    HIPCHK(rocprim::inclusive_scan(h->overlay.sort_tmp.p, bytes, in, out, (size_t)n, op, h->stream));
-    return WFS_OK;
+    auto &O = h->overlay; OverlayArgs &a = r.a; const i64 N = a.n, P = a.n_pulses;
+    TRY(ensure_each(h, (size_t)P, O.pkey, O.pkey2, O.plen, O.plen2, O.ekey, O.run_max, O.head, O.merged_of));
+    a.pkey = O.pkey.p(); a.plen = O.plen.p();
+    TRY(launch(h, PLAIN(k_ov_pulses), per_thread(N), a));
+    TRY(sort_pairs(h, "overlay pulse sort", O.pkey.p(), O.pkey2.p(), O.plen.p(), O.plen2.p(), P, (unsigned)r.key_bits));
+    a.pkey = O.pkey2.p(); a.plen = O.plen2.p(); a.ekey = O.ekey.p();
+    TRY(launch(h, PLAIN(k_ov_ends), per_thread(P), a));
+    TRY(scan_inclusive(h, "overlay end scan", O.ekey.p(), O.run_max.p(), P, rocprim::maximum<u64>()));
+    a.run_max = O.run_max.p(); a.head = O.head.p();
+    TRY(launch(h, PLAIN(k_ov_heads), per_thread(P), a));
+    TRY(scan_inclusive(h, "overlay head scan", O.head.p(), O.merged_of.p(), P, rocprim::plus<i32>()));
+    a.merged_of = O.merged_of.p(); i32 n_merged = 0;
+    TRY(read_block(h, n_merged, O.merged_of.p() + (P - 1)));
+    const i64 M = a.n_merged = n_merged;
+    if (M <= 0 || M > P) return h->fail(WFS_E_STATE, "wfs_overlay_records: internal: the merged pulses do not follow from the pulses");
+    TRY(ensure_each(h, (size_t)M, O.m_first, O.m_last, O.m_nrec, O.rec_end));
+    a.m_first = O.m_first.p(); a.m_last = O.m_last.p(); a.m_nrec = O.m_nrec.p();
+    return launch(h, PLAIN(k_ov_merged), per_thread(P), a);
 }
-// the last element of an inclusive scan over n > 0 elements: its total (a blocking read behind the stream)
-template <class T> static int overlay_total(wfs_handle *h, const T *scanned, i64 n, T *total)
+
+// ---- overlay 4: the output records -- how many per merged pulse, their keys, the sort by (time, channel), each filled in its sorted slot
+static int overlay_output(wfs_handle *h, OverlayRun &r)
 {
-    TRY(copy_async(h, total, scanned + (n - 1), 1, hipMemcpyDeviceToHost));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return WFS_OK;
+    auto &O = h->overlay; OverlayArgs &a = r.a; const i64 M = a.n_merged;
+    TRY(launch(h, PLAIN(k_ov_count), per_thread(M), a));
+    TRY(scan_inclusive(h, "overlay record scan", O.m_nrec.p(), O.rec_end.p(), M, rocprim::plus<i64>()));
+    a.rec_end = O.rec_end.p(); i64 n_out = 0;
+    TRY(read_block(h, r.sc, O.scal.p(), n_out, O.rec_end.p() + (M - 1)));
+    if (r.sc.too_long) return h->fail(WFS_E_CAPACITY, "wfs_overlay_records: overlay: a merged pulse of more than 2^31 - 1 samples");
+    if (n_out > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "wfs_overlay_records: overlay: more than 2^31 records come out of one pass, split it");
+    const i64 NO = a.n_out = n_out;
+    if (NO <= 0) return h->fail(WFS_E_STATE, "wfs_overlay_records: internal: merged pulses without a record");
+    TRY(ensure_each(h, (size_t)NO, O.okey, O.okey2, O.oval, O.oval2)); TRY(ensure(h, O.out, (size_t)NO * REC_DWORDS));
+    a.okey = O.okey.p(); a.oval = O.oval.p();
+    TRY(launch(h, PLAIN(k_ov_out_keys), per_thread(M), a));
+    TRY(sort_pairs(h, "overlay output sort", O.okey.p(), O.okey2.p(), O.oval.p(), O.oval2.p(), NO, (unsigned)(a.bits.sbits + a.bits.chbits)));
+    a.okey = O.okey2.p(); a.oval = O.oval2.p(); a.out = O.out.p();
+    return launch(h, PLAIN(k_ov_fill), per_wave(NO), a);
 }
-}  // extern "C++"
 
 int wfs_overlay_records(wfs_handle *h, const void *sim_host, int64_t n_sim, const void *bg_host, int64_t n_bg, const int32_t *bg_baseline, int64_t *n_records)
 try {
@@ -3249,103 +3329,20 @@ try {
     if (n_bg < 0 || (n_bg > 0 && !bg_host)) return h->fail(WFS_E_INVALID, "wfs_overlay_records: n_bg is negative or bg_host is null");
     if (sim_host && n_sim < 0) return h->fail(WFS_E_INVALID, "wfs_overlay_records: n_sim is negative");
     if (!sim_host && !run_finished(h)) return h->fail(WFS_E_STATE, "wfs_overlay_records: no simulated records: wfs_run has not completed and sim_host is null");
-    const WfsDev &d = h->dev;
-    auto &O = h->overlay;
+    const WfsDev &d = h->dev; auto &O = h->overlay;
     if (!sim_host && n_sim > h->run.n_records) return h->fail(WFS_E_INVALID, "wfs_overlay_records: n_sim beyond the records of the last run");
     const i64 NA = sim_host ? n_sim : (n_sim < 0 ? h->run.n_records : n_sim), N = NA + n_bg;
     O.n_records = 0; *n_records = 0;
     if (NA > 0x7fffffffLL || n_bg > 0x7fffffffLL || N > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "wfs_overlay_records: overlay: more than 2^31 records in one pass, split it");
     if (N == 0) return WFS_OK;
     HIPCHK(hipSetDevice(h->device));
-    if (h->pack.must_wait()) HIPCHK(hipStreamWaitEvent(h->stream, h->rec_ready[h->pack.arena], 0));      // behind the batch's packers (the fence state stays as it is)
-    OverlayArgs a{};
-    a.n_a = NA; a.n = N; a.dt = (i32)d.dt; a.n_rows = (i32)h->cfg.n_rows; a.baseline = (i32)d.baseline;
-    if (sim_host) { TRY(upload(h, O.src_a, (const u32 *)sim_host, (size_t)NA * REC_DWORDS)); a.src_a = O.src_a.p(); }
-    else a.src_a = (const u32 *)h->records_buf().p;
-    TRY(upload(h, O.src_b, (const u32 *)bg_host, (size_t)n_bg * REC_DWORDS)); a.src_b = O.src_b.p();
-    {
-        std::vector<i32> base((size_t)a.n_rows, a.baseline);
-        if (bg_baseline) base.assign(bg_baseline, bg_baseline + a.n_rows);
-        TRY(upload(h, O.base, base.data(), base.size()));
-        HIPCHK(hipStreamSynchronize(h->stream));            // (base is a local)
-        a.base = O.base.p();
-    }
-    TRY(ensure(h, O.scal, 1));
-    a.scal = O.scal.p();
-    OverlayScal sc{}; sc.smin = I64_MAX; sc.smax = I64_MIN; sc.first_bad = ~0ull;
-    TRY(copy_async(h, O.scal.p(), &sc, 1, hipMemcpyHostToDevice));
-    HIPCHK(hipStreamSynchronize(h->stream));                // (sc is written below)
-    auto invalid = [&](const OverlayScal &s) {
-        const i64 i = (i64)(s.first_bad >> 8);
-        return h->fail(WFS_E_INVALID, std::string("wfs_overlay_records: ") + (i < NA ? "simulated record " + std::to_string(i) : "background record " + std::to_string(i - NA)) + ": " +
-                       ov_bad_name((int)(s.first_bad & 0xffu)) + " (" + std::to_string(s.n_bad) + " records in all)");
-    };
-    TRY(launch(h, PLAIN(k_ov_check), per_thread(N), a));
-    TRY(copy_async(h, &sc, O.scal.p(), 1, hipMemcpyDeviceToHost));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (sc.n_bad) return invalid(sc);
-    a.smin = sc.smin;
-    a.bits.sbits = ov_bits_of((u64)sc.smax - (u64)sc.smin + 1ull); a.bits.chbits = ov_bits_of((u64)std::max(a.n_rows - 1, 1));
-    if (!ov_bits_fit(a.bits)) return h->fail(WFS_E_CAPACITY, "wfs_overlay_records: overlay: the records span more samples than the sort keys hold beside the channel (2^" + std::to_string(63 - a.bits.chbits) + "), split the pass");
-    const int key_bits = a.bits.sbits + a.bits.chbits + 1;
-    // the records by (stream, channel, time)
-    TRY(ensure(h, O.key, (size_t)N)); TRY(ensure(h, O.key2, (size_t)N)); TRY(ensure(h, O.val, (size_t)N)); TRY(ensure(h, O.val2, (size_t)N));
-    TRY(ensure(h, O.flag, (size_t)N)); TRY(ensure(h, O.pulse_of, (size_t)N));
-    a.key = O.key.p(); a.val = O.val.p();
-    TRY(launch(h, PLAIN(k_ov_keys), per_thread(N), a));
-    TRY(overlay_sort(h, O.key.p(), O.key2.p(), O.val.p(), O.val2.p(), N, key_bits));
-    a.key = O.key2.p(); a.val = O.val2.p(); a.flag = O.flag.p();
-    TRY(launch(h, PLAIN(k_ov_valid), per_thread(N), a));
-    TRY(overlay_scan(h, O.flag.p(), O.pulse_of.p(), N, rocprim::plus<i32>()));
-    a.pulse_of = O.pulse_of.p();
-    i32 n_pulses = 0;
-    TRY(copy_async(h, &sc, O.scal.p(), 1, hipMemcpyDeviceToHost));
-    TRY(overlay_total(h, O.pulse_of.p(), N, &n_pulses));
-    if (sc.n_bad) return invalid(sc);
-    const i64 P = a.n_pulses = n_pulses;
-    if (P <= 0) return h->fail(WFS_E_STATE, "wfs_overlay_records: internal: valid records without a pulse");
-    // the pulses by (channel, start, stream); merged pulses from the running maximum of their ends
-    TRY(ensure(h, O.pkey, (size_t)P)); TRY(ensure(h, O.pkey2, (size_t)P)); TRY(ensure(h, O.plen, (size_t)P)); TRY(ensure(h, O.plen2, (size_t)P));
-    TRY(ensure(h, O.ekey, (size_t)P)); TRY(ensure(h, O.run_max, (size_t)P)); TRY(ensure(h, O.head, (size_t)P)); TRY(ensure(h, O.merged_of, (size_t)P));
-    a.pkey = O.pkey.p(); a.plen = O.plen.p();
-    TRY(launch(h, PLAIN(k_ov_pulses), per_thread(N), a));
-    TRY(overlay_sort(h, O.pkey.p(), O.pkey2.p(), O.plen.p(), O.plen2.p(), P, key_bits));
-    a.pkey = O.pkey2.p(); a.plen = O.plen2.p(); a.ekey = O.ekey.p();
-    TRY(launch(h, PLAIN(k_ov_ends), per_thread(P), a));
-    TRY(overlay_scan(h, O.ekey.p(), O.run_max.p(), P, rocprim::maximum<u64>()));
-    a.run_max = O.run_max.p(); a.head = O.head.p();
-    TRY(launch(h, PLAIN(k_ov_heads), per_thread(P), a));
-    TRY(overlay_scan(h, O.head.p(), O.merged_of.p(), P, rocprim::plus<i32>()));
-    a.merged_of = O.merged_of.p();
-    i32 n_merged = 0;
-    TRY(overlay_total(h, O.merged_of.p(), P, &n_merged));
-    const i64 M = a.n_merged = n_merged;
-    if (M <= 0 || M > P) return h->fail(WFS_E_STATE, "wfs_overlay_records: internal: the merged pulses do not follow from the pulses");
-    TRY(ensure(h, O.m_first, (size_t)M)); TRY(ensure(h, O.m_last, (size_t)M)); TRY(ensure(h, O.m_nrec, (size_t)M)); TRY(ensure(h, O.rec_end, (size_t)M));
-    a.m_first = O.m_first.p(); a.m_last = O.m_last.p(); a.m_nrec = O.m_nrec.p();
-    TRY(launch(h, PLAIN(k_ov_merged), per_thread(P), a));
-    TRY(launch(h, PLAIN(k_ov_count), per_thread(M), a));
-    TRY(overlay_scan(h, O.m_nrec.p(), O.rec_end.p(), M, rocprim::plus<i64>()));
-    a.rec_end = O.rec_end.p();
-    i64 n_out = 0;
-    TRY(copy_async(h, &sc, O.scal.p(), 1, hipMemcpyDeviceToHost));
-    TRY(overlay_total(h, O.rec_end.p(), M, &n_out));
-    if (sc.too_long) return h->fail(WFS_E_CAPACITY, "wfs_overlay_records: overlay: a merged pulse of more than 2^31 - 1 samples");
-    if (n_out > 0x7fffffffLL) return h->fail(WFS_E_CAPACITY, "wfs_overlay_records: overlay: more than 2^31 records come out of one pass, split it");
-    const i64 NO = a.n_out = n_out;
-    if (NO <= 0) return h->fail(WFS_E_STATE, "wfs_overlay_records: internal: merged pulses without a record");
-    // the output records by (time, channel), each filled in its sorted slot
-    TRY(ensure(h, O.okey, (size_t)NO)); TRY(ensure(h, O.okey2, (size_t)NO)); TRY(ensure(h, O.oval, (size_t)NO)); TRY(ensure(h, O.oval2, (size_t)NO));
-    TRY(ensure(h, O.out, (size_t)NO * REC_DWORDS));
-    a.okey = O.okey.p(); a.oval = O.oval.p();
-    TRY(launch(h, PLAIN(k_ov_out_keys), per_thread(M), a));
-    TRY(overlay_sort(h, O.okey.p(), O.okey2.p(), O.oval.p(), O.oval2.p(), NO, a.bits.sbits + a.bits.chbits));
-    a.okey = O.okey2.p(); a.oval = O.oval2.p(); a.out = O.out.p();
-    TRY(launch(h, PLAIN(k_ov_fill), per_wave(NO), a));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipGetLastError());
-    CHECK_LAUNCHES();
-    O.n_records = NO; *n_records = NO;
+    OverlayRun r; r.a.n_a = NA; r.a.n = N; r.a.dt = (i32)d.dt; r.a.n_rows = (i32)h->cfg.n_rows; r.a.baseline = (i32)d.baseline;
+    TRY(overlay_load(h, r, sim_host, bg_host, bg_baseline));
+    TRY(overlay_pulses(h, r));
+    TRY(overlay_merge(h, r));
+    TRY(overlay_output(h, r));
+    TRY(pass_done(h));
+    O.n_records = r.a.n_out; *n_records = r.a.n_out;
     return WFS_OK;
 } WFS_CATCH(h)
 

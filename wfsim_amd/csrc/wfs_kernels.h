@@ -2986,7 +2986,7 @@ __global__ __launch_bounds__(256) void k_rec_keys(WfsDev d, ZleArgs a)
         const i32 need = records_of(plen);
         for (i32 f = lane; f < need; f += 64) {
             if (rec + f >= a.rec_capacity) break;
-            a.rec_key[rec + f] = ((u64)(rec_fragment_sample(left, (i64)f) - key_base) << 12) | (u64)(u32)q.channel;
+            a.rec_key[rec + f] = ((u64)(rec_fragment_sample(left, (i64)f) - key_base) << REC_KEY_SHIFT) | (u64)(u32)q.channel;
             a.rec_val[rec + f] = (u32)(rec + f);
         }
         rec += need;

@@ -50,6 +50,7 @@
 #include <cstdint>
 #include <string>
 #include "wfs_layout.h"     // WFS_HD, i32, i64, row_span
+#include "wfs_rows.h"       // bits_below
 #include "wfs_dark.h"
 
 constexpr unsigned DK_SITE_LONE_IX = 115;                          // Philox site of a lone row's noise offset
@@ -72,6 +73,8 @@ WFS_HD unsigned long long lone_key(i32 ch, i64 rel, int kind) { return ((unsigne
 WFS_HD i32 lone_key_channel(unsigned long long key) { return (i32)(key >> LONE_KEY_SHIFT); }
 WFS_HD i64 lone_key_rel(unsigned long long key) { return (i64)((key & (((unsigned long long)1 << LONE_KEY_SHIFT) - 1)) >> LONE_KEY_KIND_BITS); }
 WFS_HD int lone_key_kind(unsigned long long key) { return (int)(key & (((unsigned long long)1 << LONE_KEY_KIND_BITS) - 1)); }
+// the end bit of the sort over the seed keys of a pass with n_channels channels: start and kind, and channel bits for values up to n_channels
+WFS_HD unsigned lone_key_end_bit(int n_channels) { return (unsigned)(LONE_KEY_SHIFT + bits_below((u64)n_channels + 1)); }
 
 WFS_HD i64 lone_gap(i64 tlen, i64 tw) { return tlen + 2 * tw; }                          // G
 // the cells whose photons can start in [a, b): idx = start + before lies in cell idx >> 6

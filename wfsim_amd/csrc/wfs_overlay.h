@@ -79,7 +79,8 @@ WFS_HD int ov_last_check(const OvHeader &q) { return q.record_i == records_of(q.
 //   output key  sample | channel               (time, channel), the order of the output
 // sbits: bits of the largest relative sample (the end of the last pulse), chbits: bits of n_rows - 1
 struct OvBits { int sbits, chbits; };
-WFS_HD int ov_bits_of(u64 v) { int b = 1; while (b < 64 && (v >> b) != 0) b++; return b; }
+// the bits of a key field that holds the values up to v: one, and those of the values up to v >> 1 (bits_below of wfs_rows.h; no v overflows)
+WFS_HD int ov_bits_of(u64 v) { return 1 + bits_below((v >> 1) + 1); }
 WFS_HD bool ov_bits_fit(const OvBits &b) { return b.sbits + b.chbits + 1 <= 64; }
 WFS_HD u64 ov_record_key(const OvBits &b, int stream, i32 channel, i64 rel) { return ((u64)stream << (b.sbits + b.chbits)) | ((u64)channel << b.sbits) | (u64)rel; }
 WFS_HD u64 ov_pulse_key(const OvBits &b, int stream, i32 channel, i64 rel) { return ((((u64)channel << b.sbits) | (u64)rel) << 1) | (u64)stream; }

@@ -63,6 +63,18 @@ WFS_HD RecHeader rec_header(i32 dt, u32 dt_channel, i64 left, i32 plen, i32 f)
     return h;
 }
 
+// ---- sort keys: the bits in use --------------------------------------------------------------------------------------------------------
+// Bits needed for values below v, the smallest b with v <= 2^b: 0 for v <= 1, k for 2^(k-1) < v <= 2^k, 64 above 2^63.  A radix sort
+// over keys below v ends at this bit; every "how many key bits are in use" of the engine is this function (the record sort, the seed
+// sort of the lone-hit passes, the keys of the overlay).
+WFS_HD int bits_below(u64 v) { if (v < 2) return 0; int b = 1; while (b < 64 && ((v - 1) >> b) != 0) b++; return b; }
+// The record key of k_rec_keys: (first sample of the record - key origin) << REC_KEY_SHIFT | channel, channels below 2^REC_KEY_SHIFT.
+constexpr int REC_KEY_SHIFT = 12;
+// The end bit of the sort over the record keys of rows that span `span` = key_end - key_origin samples: relative samples up to span, at
+// least one bit of them.  (The loop this replaces, `end = 13; while (((span << 12) >> end) != 0) end++`, gave the same for every span
+// below 2^52 and lost the top bits of span << 12 from there on, which no batch reaches; here such a span sorts all 64 bits.)
+WFS_HD unsigned rec_key_end_bit(u64 span) { const int b = REC_KEY_SHIFT + bits_below((span < 1 ? 1 : span) + 1); return b < 64 ? (unsigned)b : 64u; }
+
 // ---- closing an interval ------------------------------------------------------------------------------------------------------------
 // The interval of the hits rawl .. rawr of a row of len samples (rawdata.py:302-311): tw samples more on either side, clipped into the
 // row, left up and right down to an even sample; the records it needs.  Relative to the row, which is shorter than 10^6 samples
